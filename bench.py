@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the panfeed hot path (k-mer extraction + pattern hashing) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints its line; the legs
+beside the timed one (the every-copy pass, the 'N'-bearing pass, the CPU oracle's baseline and parity sample, the end to
+end runs, the weak-scaling figure at N > 1) run only with `--full`.  `--dump-outputs DIR` writes what the timed path
+computed in its last step as DIR/<name>.npy (float64; a fixed, seeded sample of the larger arrays, under 64 MB in all).
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself (torch.distributed.run as a
 child process; this parent never touches HIP) and fails loudly when the box has fewer than N devices.
@@ -22,8 +27,9 @@ clusters PER GPU) is measured too and reported under `weak_scaling`.  `--scaling
 Prints ONE JSON line on rank 0.  `value` = k-mer instances/s over all ranks (trip count of
 /root/reference/panfeed/panfeed.py:64); `patterns_per_s` = unique patterns/s (rows of hashes_to_patterns.tsv).
 `roofline` prices the chain of kernels one pf_submit runs (dedup -> scan -> finish -> md5) against HBM with SURVEY
-8(d)'s algorithmic bytes, and lists every kernel with the roof that actually bounds it; `cpu_baseline` is the CPU
-oracle (a port, not the reference) on a bounded sample of the same workload, rank 0 at N=1 only; `parity_sample` is
+8(d)'s algorithmic bytes, and lists every kernel with the roof that actually bounds it.  With `--full`:
+`cpu_baseline` is the CPU oracle (a port, not the reference) on a bounded sample of the same workload, rank 0 at N=1
+only; `scan_every_copy` is the same pass with the identical-sequence shortcut off, checked row for row; `parity_sample` is
 that sample's kmers_to_hashes / hashes_to_patterns text, oracle against GPU, byte for byte; `with_N` is the same
 workload with SURVEY 8d's share of 'N's (0.1 % of the sequences); `end_to_end` is files on disk -> the three files
 (pipeline.run_files) and Seqinfo records -> the three files, with the stage split.
@@ -89,7 +95,15 @@ def parse(argv=None):
     ap.add_argument("--targets-clusters", type=int, default=0, help="clusters of the --targets second pass leg")
     ap.add_argument("--sweep-alleles", action="store_true", help="extra leg: throughput vs distinct sequences per cluster")
     ap.add_argument("--merge-method", default="owner", choices=["owner", "allgather"])
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the timed one: every-copy, 'N'-bearing, CPU baseline + oracle parity "
+                         "sample, end to end, weak scaling at N > 1 (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -217,7 +231,7 @@ def make_step(eng, dbs, world, dist, dev, method):
     from panfeed_amd import _lib
     from panfeed_amd.distributed import merge_patterns
 
-    def step(eng=eng, checksum=False):
+    def step(eng=eng, checksum=False, on_batch=None):
         _lib.check(eng.L.pf_reset_patterns(eng.ctx))
         sums = []
         tot = {"kept": 0, "new": 0, "scan_ms": 0.0, "rows_ms": 0.0, "emit_ms": 0.0, "total_ms": 0.0, "dedup_ms": 0.0,
@@ -239,6 +253,8 @@ def make_step(eng, dbs, world, dist, dev, method):
             tot["binned"] += tm["n_binned_clusters"]
             if checksum:                 # untimed legs only: what the files of this batch would hold, row for row
                 sums.append(eng.result_checksum())
+            if on_batch is not None:     # untimed only (--dump-outputs): the batch's results, fetched
+                on_batch(eng, d)
         tot["checksums"] = sums
         n_global = tot["new"]
         if world > 1:
@@ -250,6 +266,114 @@ def make_step(eng, dbs, world, dist, dev, method):
         tot["global_patterns"] = n_global
         return tot
     return step
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BYTES = 60_000_000          # all the .npy files of one run together (under 64 MB)
+
+
+def _u32_words(a):
+    """uint64 -> (hi, lo) uint32 halves side by side: exact in float64"""
+    a = np.asarray(a, dtype=np.uint64)
+    return np.stack([a >> np.uint64(32), a & np.uint64(0xFFFFFFFF)], axis=-1)
+
+
+class OutputDump:
+    """What a caller of the timed path (pf_submit, then pf_fetch) receives for one step, in a form that does not depend
+    on where the library placed its rows or which ids its patterns got: per cluster (batch order over the step) its kept
+    and unique k-mer counts and the MD5 digest of its own pattern row; per kept k-mer (the cluster's output order) its
+    cluster, position, key words and its pattern's digest; per new pattern (first-seen order) its digest, first_seen,
+    strain count and bit row; the device-side checksum of every row of every batch (pf_result_checksum).  Arrays longer
+    than their share of DUMP_BYTES are a fixed, seeded sample of their rows (the first columns say which rows).
+    Every value is an integer (u64 words split into u32 halves), exact in float64."""
+
+    def __init__(self, n_clusters, n_kept, n_new, budget=DUMP_BYTES):
+        self.budget = budget
+        self.n = {"clusters": int(n_clusters), "kmers": int(n_kept), "patterns": int(n_new)}
+        self.base = {"clusters": 0, "kmers": 0, "patterns": 0}
+        self.parts = {"clusters": [], "kmers": [], "patterns": []}
+        self.pick = {}
+        self.checksums = []
+
+    def _sample(self, what, row_bytes, share):
+        """global row indices of `what` to keep (sorted): all of them, or a seeded sample within `share` of the budget"""
+        if what not in self.pick:
+            n, m = self.n[what], max(1, int(self.budget * share) // row_bytes)
+            seed = {"clusters": 0x5EED01, "kmers": 0x5EED02, "patterns": 0x5EED03}[what]
+            self.pick[what] = (np.arange(n, dtype=np.int64) if n <= m else
+                               np.sort(np.random.default_rng(seed).choice(n, size=m, replace=False)).astype(np.int64))
+        return self.pick[what]
+
+    def _local(self, what, row_bytes, share, count):
+        """this batch's rows of the sample, as indices into the batch"""
+        g = self._sample(what, row_bytes, share)
+        b = self.base[what]
+        sel = g[(g >= b) & (g < b + count)] - b
+        self.base[what] = b + count
+        return sel, b
+
+    def add(self, eng, d):
+        import ctypes as C
+
+        def arr(ptr, count, ctype, dtype):
+            if count == 0 or not ptr:
+                return np.zeros(0, dtype=dtype)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(count,)).view(dtype)
+        self.checksums.append(eng.result_checksum())
+        f = eng.fetch()
+        cb = self.base["clusters"]
+        n, kw, W = int(d.n_clusters), int(f.key_words), int(f.W)
+        off = arr(f.cluster_kmer_off, n, C.c_uint64, np.uint64).astype(np.int64)
+        cnt = arr(f.cluster_kmer_cnt, n, C.c_uint32, np.uint32).astype(np.int64)
+        uniq = arr(f.cluster_unique, n, C.c_uint32, np.uint32)
+        cpat = arr(f.cluster_pattern, n, C.c_uint32, np.uint32)
+        tot = int(cnt.sum())
+        keys = arr(f.kmer_key, tot * kw, C.c_uint64, np.uint64).reshape(tot, kw)
+        kpid = arr(f.kmer_pattern, tot, C.c_uint32, np.uint32)
+        P = int(f.n_patterns)
+        md5 = arr(f.pattern_md5, P * 16, C.c_uint8, np.uint8).view("<u4").reshape(P, 4)
+        n_new = int(f.n_new_patterns)
+        new = arr(f.new_pattern_id, n_new, C.c_uint32, np.uint32)
+        first_seen = arr(f.pattern_first_seen, P, C.c_uint64, np.uint64)
+        pat_n = arr(f.pattern_n, P, C.c_uint32, np.uint32)
+        bits = arr(f.pattern_bits, P * W, C.c_uint32, np.uint32).reshape(P, W)
+
+        def digests(pids):
+            out = np.full((len(pids), 4), -1.0)
+            ok = pids != 0xFFFFFFFF
+            out[ok] = md5[pids[ok]]
+            return out
+
+        # clusters: [index, kept, unique, digest x 4]
+        sel, b = self._local("clusters", 7 * 8, 0.13, n)
+        self.parts["clusters"].append(np.column_stack([sel + b, cnt[sel], uniq[sel], digests(cpat[sel])]))
+        # kept k-mers: [cluster, position in the cluster, key words (hi, lo) x kw, digest x 4]
+        sel, b = self._local("kmers", (6 + 2 * kw) * 8, 0.47, tot)
+        ends = np.cumsum(cnt)
+        ci = np.searchsorted(ends, sel, side="right")
+        pos = sel - (ends[ci] - cnt[ci])
+        src = off[ci] + pos
+        self.parts["kmers"].append(np.column_stack([ci + cb, pos,
+                                                    _u32_words(keys[src]).reshape(len(sel), 2 * kw), digests(kpid[src])]))
+        # new patterns: [index, digest x 4, first_seen (hi, lo), strains, bit row words x W]
+        sel, b = self._local("patterns", (8 + W) * 8, 0.40, n_new)
+        pids = new[sel]
+        self.parts["patterns"].append(np.column_stack([sel + b, md5[pids], _u32_words(first_seen[pids]), pat_n[pids],
+                                                       bits[pids]]))
+
+    def write(self, outdir, suffix="", counts=None):
+        os.makedirs(outdir, exist_ok=True)
+        out = {"clusters": np.concatenate(self.parts["clusters"]), "kmers": np.concatenate(self.parts["kmers"]),
+               "patterns": np.concatenate(self.parts["patterns"]),
+               "result_checksums": _u32_words(np.array(self.checksums, dtype=np.uint64)).reshape(len(self.checksums), 6)}
+        if counts is not None:
+            out["counts"] = np.asarray(counts)
+        total = 0
+        for name, a in out.items():
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a)
+            total += a.nbytes
+        return total
 
 
 def targets_pass(args, local):
@@ -623,10 +747,18 @@ def main():
     dt, last = timed(step, args.steps, args.warmup)
     (dt, max_kernel_ms, max_merge_ms), (tot_inst, tot_kept, tot_packed) = reduce_max_sum(
         [dt, last["total_ms"], last["merge_ms"]], [float(n_inst), float(last["kept"]), float(packed_bytes)])
+    if args.dump_outputs:
+        dump = OutputDump(sum(d.n_clusters for d in dbs), last["kept"], last["new"], budget=DUMP_BYTES // world)
+        if world == 1 and len(dbs) == 1:
+            dump.add(eng, dbs[0])        # the last timed step's results, still on the device
+        else:      # only the last batch's are (and the merge is collective): the step once more, untimed, batch by batch
+            step(on_batch=dump.add)
+        dump.write(args.dump_outputs, "" if world == 1 else f"_rank{rank}",
+                   counts=[n_inst, last["unique"], last["kept"], last["new"], last["global_patterns"]])
 
     # N > 1, strong scaling: the weak figure beside it (--clusters per GPU, rank r owns [r * clusters, (r + 1) * clusters))
     weak = None
-    if world > 1 and strong and not args.no_weak_leg:
+    if args.full and world > 1 and strong and not args.no_weak_leg:
         for d in dbs:
             d.free()
         dbs = []
@@ -644,7 +776,7 @@ def main():
 
     # transparency leg (untimed for `value`): the same pass with the identical-sequence shortcut off
     every = None
-    if world == 1 and not args.no_dedup and not args.no_every_copy_leg:
+    if args.full and world == 1 and not args.no_dedup and not args.no_every_copy_leg:
         eng2 = Engine(klength=k, max_strains=(S + 31) // 32 * 32, device=local, max_items=min(args.max_items, 8192),
                       pattern_capacity=1 << 25, dedup=False)
         step(eng2)                       # untimed: first-use allocations of the second context
@@ -669,7 +801,7 @@ def main():
                      args.allele_model) == (50000, 1000, 31, 100, False, 7.0, 0.5, "star")
     # SURVEY 8d's generator proper: 0.1 % of the sequences carry one 'N' (the value above is its pure-ACGT variant)
     with_n = None
-    if world == 1 and default_shape and args.n_rate == 0.0 and not args.no_n_leg:
+    if args.full and world == 1 and default_shape and args.n_rate == 0.0 and not args.no_n_leg:
         for d in dbs:
             d.free()
         dbs = []
@@ -822,14 +954,14 @@ def main():
         if args.sweep_alleles:
             out["allele_sweep"] = allele_sweep(args, local)
             out["allele_sweep_tree"] = allele_sweep(args, local, "tree")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = min(len(os.sched_getaffinity(0)), 16)   # a 1-GPU box's CPU share
             per_cluster = max(1, S // 1000)
             n = args.cpu_clusters or max(8, min(args.clusters, 80 * threads // per_cluster))   # ~15-25 s at ~5e6 instances/s/thread
             out["cpu_baseline"], out["parity_sample"] = oracle_sample(args, local, threads, n, args.n_rate, True)
             if with_n is not None:
                 _, with_n["parity_sample"] = oracle_sample(args, local, threads, max(8, n // 4), 0.001, False)
-        if world == 1 and default_shape and not args.no_e2e_leg:
+        if args.full and world == 1 and default_shape and not args.no_e2e_leg:
             try:
                 out["end_to_end"] = end_to_end(args, local)
             except OSError as e:             # no room for the 1.2 GB scratch pangenome: the line is still worth printing

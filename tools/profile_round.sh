@@ -17,7 +17,7 @@ python tools/pmc_summary.py 4 $OUT/final_pmc_summary.json $OUT/fetch $OUT/write 
 # roofline.traffic then comes from the passes above (traffic_commit, traffic_matches_this_build: true)
 R=$(basename $OUT); mkdir -p profiles/$R && cp $OUT/final_pmc_summary.json profiles/$R/final_pmc_summary.json
 if [ "$PROF_ONLY" = 0 ]; then
-timeout -k 10 500 python bench.py --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 500 python bench.py --steps 5 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err
 fi
 find $OUT -name "*kernel_trace.csv" -delete
 find $OUT -name "*counter_collection.csv" -delete
