@@ -479,6 +479,18 @@ int pf_render_kmers_tsv_device(pf_ctx* ctx, const pf_target_seq* seqs, uint32_t 
  * the context: valid until the next call of this function (the block after it is already being copied when the call
  * returns, so that the caller's write of one block overlaps the copy of the next). */
 int pf_device_text_chunk(pf_ctx* ctx, uint64_t offset, uint64_t max_bytes, const char** ptr, uint64_t* nbytes);
+/* The same text (same bytes, same order as pf_render_kmers_tsv_device) in device memory of at most budget_bytes: cut
+ * into ranges at tile boundaries and at boundaries of host-rendered sequences, each range at most budget_bytes / 2, written
+ * by the GPU into two buffers used alternately (range r + 1 is written while range r is copied out).  A text that fits
+ * the budget is one range.  *total_bytes: the text's size; *n_ranges: the ranges; *peak_text_bytes (may be NULL): the
+ * most text the device holds at one time.  A tile or host-rendered sequence larger than budget_bytes / 2 (less 64 bytes)
+ * is PF_ERR_ARG; the message names the smallest budget that works.  `seqs` must stay valid until the stream ends (its
+ * last block handed out, the next pf_submit or stream begin).  Ends the text of pf_render_kmers_tsv_device. */
+int pf_kmers_tsv_stream_begin(pf_ctx* ctx, const pf_target_seq* seqs, uint32_t n, uint64_t budget_bytes,
+                              uint64_t* total_bytes, uint32_t* n_ranges, uint64_t* peak_text_bytes);
+/* The next block of that text (at most 64 MiB) in pinned host memory owned by the context, valid until the next call;
+ * the block after it is already being copied.  *nbytes == 0 at the end (the stream is then over). */
+int pf_kmers_tsv_stream_next(pf_ctx* ctx, const char** ptr, uint64_t* nbytes);
 
 /* The bodies of kmers_to_hashes.tsv and hashes_to_patterns.tsv of the last pf_submit written ON THE DEVICE
  * (panfeed.py:177,208 and :181-187,217-223): rows assembled in LDS, coalesced stores, one copy to pinned host memory.

@@ -1,0 +1,151 @@
+"""`python -m panfeed_amd`: the `panfeed` command (the reference's `panfeed/__main__.py`) on one GPU.
+
+Option names, short forms, defaults and meanings are the reference's (`__main__.py:86-222`); so are the refusals, their
+order and their exit status (`__main__.py:234-242`, `input.py:213-216`).  The run itself is `pipeline.run_files`: the
+native reader, the GPU, a writer thread.  Two options are added: `--device` (as the downstream tools have) and
+`--batch-clusters`.  `--cores` and `-ql/--queue-limit` are accepted and change nothing (the GPU takes the place of the
+worker processes).  One refusal is new: `-k` outside 1..PF_MAX_K, before any file is read or the GPU touched.
+
+Unlike the reference, no `<output>/fastas/` directory is made (the reader splits the GFFs' `##FASTA` sections in
+memory), so none is left behind.  A run on more than one GPU is `sharded.run_files_sharded` under torchrun.
+"""
+import argparse
+import logging
+import os
+import sys
+
+from . import __version__
+
+logger = logging.getLogger("panfeed")
+
+PF_MAX_K = 126          # include/panfeed_hip.h: 2 bits per base in at most four 63-bit key words
+BATCH_CLUSTERS = 256    # pipeline.run_files' default
+
+
+def get_options(argv=None):
+    p = argparse.ArgumentParser(
+        prog="panfeed",
+        description="Gene-cluster-specific k-mers and their presence/absence patterns over a pangenome, on one AMD GPU. "
+                    "For a run over several GPUs use panfeed_amd.sharded.run_files_sharded under torchrun.")
+    p.add_argument("-g", "--gff", required=True,
+                   help="GFF files: a directory of them, or a file naming one path per line (the sequences come from "
+                        "each GFF's ##FASTA section unless -f is given; file names must match the table's strain columns)")
+    p.add_argument("-p", "--presence-absence", required=True,
+                   help="panaroo's gene_presence_absence.csv")
+    p.add_argument("--targets", default=None,
+                   help="strains whose k-mer positions go to kmers.tsv, one name per line (default: none)")
+    p.add_argument("--genes", default=None,
+                   help="gene clusters to work on, one name per line (default: every cluster of the table)")
+    p.add_argument("-o", "--output", default="panfeed",
+                   help="output directory; it must not exist yet (default: %(default)s)")
+    p.add_argument("-f", "--fasta", default=None,
+                   help="nucleotide FASTA files (.fasta / .fna): a directory of them, or a file naming one path per line")
+    p.add_argument("-k", "--kmer-length", type=int, default=31,
+                   help=f"k-mer length, 1..{PF_MAX_K} (default: %(default)d)")
+    p.add_argument("--maf", type=float, default=0.01,
+                   help="minor allele frequency: patterns rarer than this, or commoner than 1 - maf, are left out of "
+                        "the pattern files (kmers.tsv keeps them; default: %(default).2f)")
+    p.add_argument("--upstream", type=int, default=0,
+                   help="bases added before each gene (default: %(default)d)")
+    p.add_argument("--downstream", type=int, default=0,
+                   help="bases added after each gene (default: %(default)d)")
+    p.add_argument("--downstream-start-codon", action="store_true", default=False,
+                   help="count --downstream from the start codon instead of the stop codon")
+    p.add_argument("--non-canonical", action="store_true", default=False,
+                   help="keep k-mers as read instead of their canonical form")
+    p.add_argument("--no-filter", action="store_true", default=False,
+                   help="keep k-mers whose pattern is the gene cluster's own presence/absence pattern")
+    p.add_argument("--consider-missing", action="store_true", default=False,
+                   help="leave a pattern's entry empty (NaN) for strains without the gene, instead of 0")
+    p.add_argument("--multiple-files", action="store_true", default=False,
+                   help="one output directory per gene cluster instead of one set of files")
+    p.add_argument("--compress", action="store_true", default=False,
+                   help="gzip the output files")
+    p.add_argument("--cores", type=int, default=1,
+                   help="accepted for compatibility; the GPU does the work of the worker processes")
+    p.add_argument("-ql", "--queue-limit", type=int, default=3,
+                   help="accepted for compatibility; has no effect here")
+    p.add_argument("--stop-on-missing", action="store_true", default=False,
+                   help="fail when a strain, contig or gene of the table is not found (default: warn and go on)")
+    p.add_argument("--device", type=int, default=0, help="GPU to run on (default: %(default)d)")
+    p.add_argument("--batch-clusters", type=int, default=BATCH_CLUSTERS,
+                   help="gene clusters per GPU batch (default: %(default)d)")
+    p.add_argument("-v", action="count", default=0, help="more log output (-v: debug)")
+    p.add_argument("--version", action="version", version="%(prog)s " + __version__)
+    return p.parse_args(argv)
+
+
+def set_logging(v):
+    """log records to stderr: info by default, debug from -v on"""
+    logger.setLevel(logging.DEBUG)
+    for h in list(logger.handlers):
+        if getattr(h, "_panfeed_cli", False):
+            logger.removeHandler(h)
+    ch = logging.StreamHandler(sys.stderr)
+    ch.setLevel(logging.INFO if v == 0 else logging.DEBUG)
+    ch.setFormatter(logging.Formatter("%(asctime)s - %(name)s - %(levelname)s - %(message)s", "%H:%M:%S"))
+    ch._panfeed_cli = True
+    logger.addHandler(ch)
+
+
+def read_names(path):
+    """one name per line, only the trailing newline stripped (input.py:198-211)"""
+    with open(path) as fh:
+        return {line.rstrip("\n") for line in fh}
+
+
+def main(argv=None, run=None):
+    """the panfeed command; returns the exit status.  run: what does the work (default pipeline.run_files; tests
+    pass their own)"""
+    args = get_options(argv)
+    set_logging(args.v)
+    k = args.kmer_length
+    if args.downstream_start_codon and args.upstream + args.downstream < k:
+        logger.warning("The sequence around the start codon (--upstream + --downstream) is shorter than the k-mer "
+                       "length: lower -k or widen the flanks")
+        return 1
+    if args.maf > 0.5:
+        logger.warning("--maf must not be above 0.5")
+        return 1
+    if not 1 <= k <= PF_MAX_K:
+        logger.error(f"-k {k} is outside 1..{PF_MAX_K} (PF_MAX_K): the GPU's k-mer keys hold at most {PF_MAX_K} bases")
+        return 2
+    if args.cores != 1 or args.queue_limit != 3:
+        logger.debug(f"--cores {args.cores} / --queue-limit {args.queue_limit}: no effect, the GPU does the workers' part")
+    if args.batch_clusters < 1:
+        logger.error("--batch-clusters must be at least 1")
+        return 2
+    if args.targets is not None:
+        logger.debug(f"Reading target strains ({args.targets})")
+        targets = read_names(args.targets)
+    else:
+        logger.warning("No target strains given: kmers.tsv will hold its header only")
+        targets = set()
+    genes = None
+    if args.genes is not None:
+        logger.debug(f"Reading gene clusters ({args.genes})")
+        genes = read_names(args.genes)
+    if os.path.exists(args.output):
+        logger.error(f"Output directory {args.output} exists: remove it or choose another")
+        return 1
+    if run is None:
+        from .pipeline import run_files as run
+    from ._lib import PanfeedHipError
+    logger.info("Extracting k-mers")
+    try:
+        stats = run(args.presence_absence, args.gff, args.output, fastadir=args.fasta, klength=k,
+                    canon=not args.non_canonical, consider_missing=args.consider_missing, patfilt=not args.no_filter,
+                    maf=args.maf, upstream=args.upstream, downstream=args.downstream,
+                    downstream_start_codon=args.downstream_start_codon, targets=tuple(sorted(targets)),
+                    genes=sorted(genes) if genes is not None else None, compress=args.compress,
+                    multiple_files=args.multiple_files, batch_clusters=args.batch_clusters, device=args.device,
+                    raise_missing=args.stop_on_missing)
+    except PanfeedHipError as e:          # the reader's message under --stop-on-missing, or the library's error
+        logger.error(str(e))
+        return 1
+    stats = stats or {}
+    for line in (stats.get("log") or "").splitlines():
+        logger.warning(line)
+    logger.info(f"{stats.get('clusters', 0)} gene clusters, {stats.get('instances', 0)} k-mer instances, "
+                f"{stats.get('patterns', 0)} patterns written to {args.output}")
+    return 0

@@ -69,7 +69,7 @@ struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     bool view = false;     // points into another DevBuf (staged uploads): never freed, never grown
-    int ensure(size_t bytes) {
+    int ensure(size_t bytes, bool exact = false) {
         if (view) { p = nullptr; cap = 0; view = false; }
         if (bytes <= cap) return PF_OK;
         const bool regrow = p != nullptr;
@@ -80,7 +80,8 @@ struct DevBuf {
         // take 0.25 s in the middle of a submit when a batch's key-partition queues came out a little larger than the batch
         // before's; a first allocation -- the scratch slices are 123 GB in bench.py -- gets a sixteenth).  The slack is a
         // convenience, never a requirement: when it does not fit, the exact size is asked for before giving up.
-        size_t want = bytes + (regrow ? bytes / 4 : bytes / 16) + 256;
+        // (exact: a buffer whose size a caller's memory budget bounds gets none)
+        size_t want = exact ? bytes : bytes + (regrow ? bytes / 4 : bytes / 16) + 256;
         hipError_t e = dev_malloc(&p, want);
         if (e != hipSuccess) {
             (void)hipGetLastError();
@@ -165,6 +166,26 @@ struct pf_ctx {
     bool kt_pref_valid = false;
     uint64_t kt_pref_off = 0, kt_pref_n = 0;
     int kt_pref_slot = 0;
+    // the same text in ranges of bounded size (pf_kmers_tsv_stream_begin / _next): range r is written into kt_text
+    // (r even) or kt_text2 (r odd) while the range before it leaves through the pinned blocks above
+    DevBuf kt_text2;
+    struct KtStream {
+        struct Range { uint32_t t0, t1, h0, h1; uint64_t base, bytes; };   // tiles [t0, t1), host sequences [h0, h1)
+        bool active = false;
+        const pf_target_seq* seqs = nullptr;   // the caller's, until the stream ends
+        std::vector<Range> ranges;
+        std::vector<uint32_t> host_idx, sso;
+        std::vector<uint64_t> hsizes, hoff;
+        pf::KtParams kp{};
+        uint32_t cur = 0;                      // the block to hand out next: range cur, bytes from cur_off
+        uint64_t cur_off = 0;
+        bool pref_valid = false;               // its copy is queued on `side`, into kt_pins[pref_slot]
+        int pref_slot = 0;
+        uint64_t pref_n = 0, pin_bytes = 0;
+        char* htext[2] = {nullptr, nullptr};   // the host's share of the range being written into each buffer
+        hipEvent_t ev_prod[2] = {nullptr, nullptr};    // on `stream`: the range in buffer b is written
+        hipEvent_t ev_copied[2] = {nullptr, nullptr};  // on `side`: the range in buffer b has left the device
+    } kts;
     pf_batch last{};                      // the last pf_submit's batch arrays as device pointers (valid until the next submit)
     uint32_t last_nseg = 0;
     DevBuf g_store, b_literal, g_src_off, g_src_start, g_src_flags;   // genomes resident in HBM + per-batch gather lists
@@ -230,6 +251,18 @@ struct pf_ctx {
 };
 
 namespace {
+
+// the end of a kmers.tsv stream (its last block handed out, a new one begun, the next pf_submit, pf_destroy): nothing of
+// it is in flight afterwards, its host text is freed
+void kt_stream_end(pf_ctx* c) {
+    pf_ctx::KtStream& S = c->kts;
+    if (!S.active) return;
+    (void)hipStreamSynchronize(c->side);
+    (void)hipStreamSynchronize(c->stream);
+    for (int b = 0; b < 2; b++) { free(S.htext[b]); S.htext[b] = nullptr; }
+    S.active = false; S.seqs = nullptr; S.pref_valid = false;
+    S.ranges.clear(); S.host_idx.clear(); S.sso.clear(); S.hsizes.clear(); S.hoff.clear();
+}
 
 int get_event(pf_ctx* c, hipEvent_t* ev) {
     if (!c->ev_pool.empty()) { *ev = c->ev_pool.back(); c->ev_pool.pop_back(); return PF_OK; }
@@ -596,8 +629,13 @@ void pf_destroy(pf_ctx* c) {
     c->scan_desc.release(); c->pat_b64.release(); c->txt_dev.release(); c->txt_meta.release();
     c->rp_order.release(); c->rp_rlen.release(); c->rp_rowoff.release(); c->wide_list.release();
     for (int i = 0; i < 2; i++) if (c->txt_pins[i]) (void)hipHostFree(c->txt_pins[i]); c->md5_list.release();
+    kt_stream_end(c);                     // (before its pinned blocks go)
     for (int i = 0; i < 2; i++) if (c->kt_pins[i]) (void)hipHostFree(c->kt_pins[i]);
-    for (DevBuf* b : {&c->kt_seqs, &c->kt_tiles, &c->kt_prefix, &c->kt_tbytes, &c->kt_toff, &c->kt_text}) b->release();
+    for (int i = 0; i < 2; i++) {
+        if (c->kts.ev_prod[i]) (void)hipEventDestroy(c->kts.ev_prod[i]);
+        if (c->kts.ev_copied[i]) (void)hipEventDestroy(c->kts.ev_copied[i]);
+    }
+    for (DevBuf* b : {&c->kt_seqs, &c->kt_tiles, &c->kt_prefix, &c->kt_tbytes, &c->kt_toff, &c->kt_text, &c->kt_text2}) b->release();
     c->g_store.release(); c->b_literal.release(); c->g_src_off.release(); c->g_src_start.release(); c->g_src_flags.release();
     c->mg_lo.release(); c->mg_cnt.release();
     if (c->ev_t0) (void)hipEventDestroy(c->ev_t0);
@@ -758,6 +796,7 @@ constexpr int PF_RETRY_PATTERNS = 1;   // internal: the batch ran out of pattern
 
 int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* counters, uint64_t* need, bool rerun) {
     c->have_batch = false;
+    kt_stream_end(c);                     // a kmers.tsv stream of the batch before is over
     // whatever way this call ends, nothing it queued is still reading the caller's arrays or the pinned staging
     // blocks afterwards (the successful path has waited already; an error return may come with work in flight)
     struct Drain { hipStream_t s, s2; ~Drain() { (void)hipStreamSynchronize(s2); (void)hipStreamSynchronize(s); } } drain{c->stream, c->side};
@@ -2231,9 +2270,10 @@ inline size_t len_i64(long long v) { char t[24]; return (size_t)(put_i64(t, v) -
 }  // namespace
 
 namespace {
+// sizes_only: pass 1 alone -- the sizes of the sequences' rows in *sizes_out, their sum in *nbytes, no text (out unused)
 int render_kmers_tsv_host(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, const uint32_t* seg_strand_off, char** out,
-                          uint64_t* nbytes, std::vector<uint64_t>* sizes_out) {
-    if (!c || !out || !nbytes || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
+                          uint64_t* nbytes, std::vector<uint64_t>* sizes_out, bool sizes_only = false) {
+    if (!c || (!out && !sizes_only) || !nbytes || (n && !seqs) || (sizes_only && !sizes_out)) return fail(PF_ERR_ARG, "null argument");
     if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_kmers_tsv without a successful pf_submit");
     HIPCHK(hipSetDevice(c->device));
     PFCHK(fetch_strand_bits(c));          // all this renderer needs from the device (pf_fetch is not required)
@@ -2291,6 +2331,11 @@ int render_kmers_tsv_host(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, cons
     });
     if (bad) return fail(PF_ERR_STATE, "pf_render_kmers_tsv: strand bits missing for a target window");
     for (uint32_t i = 0; i < n; i++) off[i + 1] = off[i] + size[i];
+    if (sizes_only) {
+        *nbytes = off[n];
+        sizes_out->swap(size);
+        return PF_OK;
+    }
     char* buf = (char*)malloc(off[n] + 1);
     if (!buf) return fail(PF_ERR_OOM, "malloc(%llu) failed", (unsigned long long)off[n]);
     std::atomic<bool> bad2{false};
@@ -2357,25 +2402,27 @@ int pf_render_kmers_tsv(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, const 
     return render_kmers_tsv_host(c, seqs, n, seg_strand_off, out, nbytes, nullptr);
 }
 
-// The same rows written by the GPU (kt_len_kernel / kt_text_kernel) for the sequences that are pure A/C/G/T -- one
-// segment of the batch covering every window -- and by the host renderer above for the others (a target sequence with
-// an 'N', a row too long for the kernel's tile), which are copied to their places in the device text: the text of all
-// n sequences, in order, stays in device memory and is handed out block by block (pf_device_text_chunk).
-int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t* nbytes) {
-    if (!c || !nbytes || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
-    if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_kmers_tsv_device without a successful pf_submit");
-    HIPCHK(hipSetDevice(c->device));
-    c->kt_bytes = 0; c->kt_pref_valid = false;
+namespace {
+// Which of the n target sequences the device writes: those that are pure A/C/G/T -- one segment of the batch covering
+// every window -- and whose rows fit kt_text_kernel's tile; the others (a target sequence with an 'N', a row too long
+// for the tile) are left to the host renderer.  The device's sequences go up as descriptors, one text prefix each, and
+// tiles of KT_ROWS rows; kt_len_kernel sizes every tile.  kp is set up for kt_text_kernel but for tile_off / text.
+struct KtLayout {
+    std::vector<uint2> tiles;
+    std::vector<uint32_t> tbytes;       // bytes of every tile
+    std::vector<uint32_t> host_idx;     // sequences left to the host renderer
+    std::vector<uint8_t> on_dev;
+    pf::KtParams kp{};
+};
+int kt_layout(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, KtLayout& L) {
     const uint32_t k = c->o.klength;
     const bool canon = c->o.canon != 0;
     const uint32_t reps = canon ? 1u : 2u;
     if (canon && n && (!c->last.seg_strand_off || !c->n_strand_words))
         for (uint32_t i = 0; i < n; i++) if ((long long)seqs[i].len - k + 1 > 0 && seqs[i].n_segs) return fail(PF_ERR_STATE, "the last pf_submit carried no strand bits for target segments");
-    // ---- which sequences the device writes; their descriptors, the prefix block, the tiles
     std::vector<pf::KtSeq> ks;
-    std::vector<uint2> tiles;
-    std::vector<uint32_t> host_idx;              // sequences left to the host renderer
-    std::vector<uint8_t> on_dev(n, 0);
+    std::vector<uint2>& tiles = L.tiles;
+    L.on_dev.assign(n, 0);
     std::string prefix;
     auto digits = [](long long v) { return len_i64(v); };
     for (uint32_t i = 0; i < n; i++) {
@@ -2394,8 +2441,8 @@ int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n,
             const size_t rowmax = plen + 2 * num + 2 * gnum + std::max(digits(s.strand), digits(-(long long)s.strand)) + 5 + k + 1;
             if (rowmax * pf::KT_ROWS > pf::KT_TILE || prefix.size() + plen > 0x7FFFFFF0u) dev = false;
         }
-        if (!dev) { host_idx.push_back(i); continue; }
-        on_dev[i] = 1;
+        if (!dev) { L.host_idx.push_back(i); continue; }
+        L.on_dev[i] = 1;
         pf::KtSeq q{};
         q.base = s.strand > 0 ? s.start : s.end; q.offset = s.offset; q.strand = s.strand;
         q.seg = s.seg_index[0]; q.nk = (uint32_t)nk; q.prefix_off = (uint32_t)prefix.size(); q.prefix_len = (uint32_t)plen;
@@ -2407,26 +2454,10 @@ int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n,
         for (uint32_t r0 = 0; r0 < rows; r0 += pf::KT_ROWS) tiles.push_back(make_uint2(si, r0));
         ks.push_back(q);
     }
-    // ---- the host's share, rendered in one go (its sequences' sizes come back with it)
-    char* htext = nullptr;
-    uint64_t hbytes = 0;
-    std::vector<uint64_t> hsizes;
-    struct FreeText { char*& p; ~FreeText() { free(p); } } free_htext{htext};
-    if (!host_idx.empty()) {
-        std::vector<pf_target_seq> hs(host_idx.size());
-        for (size_t j = 0; j < host_idx.size(); j++) hs[j] = seqs[host_idx[j]];
-        // (the batch's strand offsets, host side: the caller's array went to the device with the batch)
-        std::vector<uint32_t> sso;
-        if (canon && c->last.seg_strand_off && c->last_nseg) {
-            sso.resize(c->last_nseg);
-            HIPCHK(hipMemcpy(sso.data(), c->last.seg_strand_off, (size_t)c->last_nseg * 4, hipMemcpyDeviceToHost));
-        }
-        PFCHK(render_kmers_tsv_host(c, hs.data(), (uint32_t)hs.size(), sso.empty() ? nullptr : sso.data(), &htext, &hbytes, &hsizes));
-    }
     // ---- tile sizes
     const uint32_t NT = (uint32_t)tiles.size();
-    pf::KtParams kp{};
-    std::vector<uint32_t> tbytes(NT);
+    pf::KtParams& kp = L.kp;
+    L.tbytes.assign(NT, 0);
     if (NT) {
         PFCHK(c->kt_seqs.ensure(ks.size() * sizeof(pf::KtSeq)));
         PFCHK(c->kt_tiles.ensure((size_t)NT * 8));
@@ -2443,18 +2474,58 @@ int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n,
         kp.k = k; kp.canon = canon ? 1u : 0u;
         hipLaunchKernelGGL(pf::kt_len_kernel, dim3(NT), dim3(pf::KT_ROWS), 0, c->stream, kp);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(tbytes.data(), c->kt_tbytes.p, (size_t)NT * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(L.tbytes.data(), c->kt_tbytes.p, (size_t)NT * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
+    return PF_OK;
+}
+
+// the batch's strand offsets, host side (the caller's array went to the device with the batch), for the host renderer
+int kt_host_sso(pf_ctx* c, std::vector<uint32_t>& sso) {
+    sso.clear();
+    if (c->o.canon && c->last.seg_strand_off && c->last_nseg) {
+        sso.resize(c->last_nseg);
+        HIPCHK(hipMemcpy(sso.data(), c->last.seg_strand_off, (size_t)c->last_nseg * 4, hipMemcpyDeviceToHost));
+    }
+    return PF_OK;
+}
+}  // namespace
+
+// The same rows written by the GPU (kt_len_kernel / kt_text_kernel) for the sequences kt_layout gives it and by the host
+// renderer above for the others, which are copied to their places in the device text: the text of all n sequences, in
+// order, stays in device memory and is handed out block by block (pf_device_text_chunk).
+int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t* nbytes) {
+    if (!c || !nbytes || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
+    if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_kmers_tsv_device without a successful pf_submit");
+    HIPCHK(hipSetDevice(c->device));
+    kt_stream_end(c);
+    c->kt_bytes = 0; c->kt_pref_valid = false;
+    KtLayout L;
+    PFCHK(kt_layout(c, seqs, n, L));
+    const std::vector<uint2>& tiles = L.tiles;
+    const std::vector<uint32_t>& host_idx = L.host_idx;
+    // ---- the host's share, rendered in one go (its sequences' sizes come back with it)
+    char* htext = nullptr;
+    uint64_t hbytes = 0;
+    std::vector<uint64_t> hsizes;
+    struct FreeText { char*& p; ~FreeText() { free(p); } } free_htext{htext};
+    if (!host_idx.empty()) {
+        std::vector<pf_target_seq> hs(host_idx.size());
+        for (size_t j = 0; j < host_idx.size(); j++) hs[j] = seqs[host_idx[j]];
+        std::vector<uint32_t> sso;
+        PFCHK(kt_host_sso(c, sso));
+        PFCHK(render_kmers_tsv_host(c, hs.data(), (uint32_t)hs.size(), sso.empty() ? nullptr : sso.data(), &htext, &hbytes, &hsizes));
+    }
     // ---- offsets, in the order of the sequences
+    const uint32_t NT = (uint32_t)tiles.size();
     std::vector<uint64_t> toff(NT), hoff(host_idx.size());
     uint64_t total = 0;
     {
         size_t ti = 0, hi = 0;
         uint32_t si = 0;
         for (uint32_t i = 0; i < n; i++) {
-            if (on_dev[i]) {
-                while (ti < NT && tiles[ti].x == si) { toff[ti] = total; total += tbytes[ti]; ti++; }
+            if (L.on_dev[i]) {
+                while (ti < NT && tiles[ti].x == si) { toff[ti] = total; total += L.tbytes[ti]; ti++; }
                 si++;
             } else if (hi < host_idx.size() && host_idx[hi] == i) {
                 hoff[hi] = total; total += hsizes[hi]; hi++;
@@ -2464,6 +2535,7 @@ int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n,
     PFCHK(c->kt_text.ensure((size_t)total + 64));
     if (NT) {
         HIPCHK(hipMemcpyAsync(c->kt_toff.p, toff.data(), (size_t)NT * 8, hipMemcpyHostToDevice, c->stream));
+        pf::KtParams kp = L.kp;
         kp.text = c->kt_text.as<char>();
         hipLaunchKernelGGL(pf::kt_text_kernel, dim3(NT), dim3(pf::KT_ROWS), 0, c->stream, kp);
         HIPCHK(hipGetLastError());
@@ -2479,6 +2551,202 @@ int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n,
     c->kt_bytes = total;
     c->kt_host_seqs = (uint32_t)host_idx.size();
     *nbytes = total;
+    return PF_OK;
+}
+
+namespace {
+constexpr uint64_t KT_BLOCK = 64ull << 20;    // bytes per block a stream hands out (DeviceText.chunks' default too)
+
+int kt_ensure_pin(pf_ctx* c, int slot, uint64_t bytes) {
+    if (c->kt_pin_caps[slot] >= bytes) return PF_OK;
+    if (c->kt_pins[slot]) (void)hipHostFree(c->kt_pins[slot]);
+    c->kt_pins[slot] = nullptr; c->kt_pin_caps[slot] = 0;
+    hipError_t e = hipHostMalloc((void**)&c->kt_pins[slot], bytes, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(PF_ERR_OOM, "hipHostMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+    c->kt_pin_caps[slot] = bytes;
+    return PF_OK;
+}
+
+// range r of the stream written into its buffer (kt_text for even r, kt_text2 for odd) on c->stream: its tiles by
+// kt_text_kernel, its host-rendered sequences by the host renderer now and copied up.  From r = 2 on the buffer's range
+// before (r - 2) must have left the device first: c->stream waits for that range's last copy on c->side.
+int kt_produce(pf_ctx* c, uint32_t r) {
+    pf_ctx::KtStream& S = c->kts;
+    const pf_ctx::KtStream::Range& R = S.ranges[r];
+    const int b = (int)(r & 1);
+    char* buf = (b ? c->kt_text2 : c->kt_text).as<char>();
+    if (r >= 2) {
+        HIPCHK(hipEventSynchronize(S.ev_prod[b]));          // (its host text has been copied up: free it)
+        free(S.htext[b]); S.htext[b] = nullptr;
+        HIPCHK(hipStreamWaitEvent(c->stream, S.ev_copied[b], 0));
+    }
+    if (R.t1 > R.t0) {
+        pf::KtParams kp = S.kp;
+        kp.text = buf; kp.tile_first = R.t0; kp.text_base = R.base;
+        hipLaunchKernelGGL(pf::kt_text_kernel, dim3(R.t1 - R.t0), dim3(pf::KT_ROWS), 0, c->stream, kp);
+        HIPCHK(hipGetLastError());
+    }
+    if (R.h1 > R.h0) {
+        std::vector<pf_target_seq> hs(R.h1 - R.h0);
+        for (uint32_t j = R.h0; j < R.h1; j++) hs[j - R.h0] = S.seqs[S.host_idx[j]];
+        uint64_t hbytes = 0;
+        std::vector<uint64_t> hsizes;
+        PFCHK(render_kmers_tsv_host(c, hs.data(), (uint32_t)hs.size(), S.sso.empty() ? nullptr : S.sso.data(), &S.htext[b],
+                                    &hbytes, &hsizes));
+        uint64_t at = 0;
+        for (uint32_t j = R.h0; j < R.h1; j++) {
+            if (hsizes[j - R.h0] != S.hsizes[j]) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream: a sequence's size changed between its two renderings");
+            if (S.hsizes[j]) HIPCHK(hipMemcpyAsync(buf + (S.hoff[j] - R.base), S.htext[b] + at, (size_t)S.hsizes[j], hipMemcpyHostToDevice, c->stream));
+            at += S.hsizes[j];
+        }
+    }
+    HIPCHK(hipEventRecord(S.ev_prod[b], c->stream));
+    return PF_OK;
+}
+
+// the copy of the block at (S.cur, S.cur_off) into pinned slot `slot`, queued on c->side behind its range's writing; the
+// last block of range r also marks the range's buffer free, and range r + 2 is queued into it
+int kt_copy_block(pf_ctx* c, int slot) {
+    pf_ctx::KtStream& S = c->kts;
+    const pf_ctx::KtStream::Range& R = S.ranges[S.cur];
+    const int b = (int)(S.cur & 1);
+    const char* buf = (b ? c->kt_text2 : c->kt_text).as<char>();
+    const uint64_t n = std::min<uint64_t>(S.pin_bytes, R.bytes - S.cur_off);
+    PFCHK(kt_ensure_pin(c, slot, S.pin_bytes));
+    HIPCHK(hipStreamWaitEvent(c->side, S.ev_prod[b], 0));
+    HIPCHK(hipMemcpyAsync(c->kt_pins[slot], buf + S.cur_off, n, hipMemcpyDeviceToHost, c->side));
+    S.pref_valid = true; S.pref_slot = slot; S.pref_n = n;
+    if (S.cur_off + n == R.bytes) {
+        HIPCHK(hipEventRecord(S.ev_copied[b], c->side));
+        if (S.cur + 2 < S.ranges.size()) PFCHK(kt_produce(c, S.cur + 2));
+    }
+    return PF_OK;
+}
+}  // namespace
+
+// The text of pf_render_kmers_tsv_device in ranges: cut at tile and host-sequence boundaries so that each range takes at
+// most half the budget, written range by range into two device buffers used alternately, range r + 1 written while range
+// r leaves the device.  A batch whose text fits the budget is one range, the single-buffer path's work.
+int pf_kmers_tsv_stream_begin(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget_bytes,
+                              uint64_t* total_bytes, uint32_t* n_ranges, uint64_t* peak_text_bytes) {
+    if (!c || !total_bytes || !n_ranges || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
+    if (!c->have_batch) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_begin without a successful pf_submit");
+    HIPCHK(hipSetDevice(c->device));
+    kt_stream_end(c);
+    c->kt_bytes = 0; c->kt_pref_valid = false;     // (pf_device_text_chunk's text is gone: the buffers are reused)
+    *total_bytes = 0; *n_ranges = 0;
+    if (peak_text_bytes) *peak_text_bytes = 0;
+    pf_ctx::KtStream& S = c->kts;
+    KtLayout L;
+    PFCHK(kt_layout(c, seqs, n, L));
+    const uint32_t NT = (uint32_t)L.tiles.size();
+    S.host_idx.swap(L.host_idx);
+    // ---- the host's share: sizes only (its rows are rendered range by range)
+    S.hsizes.clear();
+    if (!S.host_idx.empty()) {
+        std::vector<pf_target_seq> hs(S.host_idx.size());
+        for (size_t j = 0; j < S.host_idx.size(); j++) hs[j] = seqs[S.host_idx[j]];
+        PFCHK(kt_host_sso(c, S.sso));
+        uint64_t hb = 0;
+        PFCHK(render_kmers_tsv_host(c, hs.data(), (uint32_t)hs.size(), S.sso.empty() ? nullptr : S.sso.data(), nullptr, &hb,
+                                    &S.hsizes, true));
+    }
+    // ---- offsets in the order of the sequences, the largest unit
+    std::vector<uint64_t> toff(NT);
+    S.hoff.assign(S.host_idx.size(), 0);
+    uint64_t total = 0, max_unit = 0;
+    {
+        size_t ti = 0, hi = 0;
+        uint32_t si = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            if (L.on_dev[i]) {
+                while (ti < NT && L.tiles[ti].x == si) { toff[ti] = total; total += L.tbytes[ti]; max_unit = std::max<uint64_t>(max_unit, L.tbytes[ti]); ti++; }
+                si++;
+            } else if (hi < S.host_idx.size() && S.host_idx[hi] == i) {
+                S.hoff[hi] = total; total += S.hsizes[hi]; max_unit = std::max(max_unit, S.hsizes[hi]); hi++;
+            }
+        }
+    }
+    // ---- the ranges: the whole text when it fits the budget, else pieces of at most budget / 2 (with the 64 bytes of
+    // slack every text buffer has)
+    const bool one = total + 64 <= budget_bytes;
+    const uint64_t cap = one ? total : (budget_bytes / 2 > 64 ? budget_bytes / 2 - 64 : 0);
+    if (!one && max_unit > cap)
+        return fail(PF_ERR_ARG, "kmers.tsv budget of %llu bytes is too small for this batch: its largest tile or host-rendered "
+                    "sequence is %llu bytes, the smallest budget that works is %llu", (unsigned long long)budget_bytes,
+                    (unsigned long long)max_unit, (unsigned long long)(2 * (max_unit + 64)));
+    S.ranges.clear();
+    {
+        pf_ctx::KtStream::Range cur{0, 0, 0, 0, 0, 0};
+        size_t ti = 0, hi = 0;
+        uint32_t si = 0;
+        auto add = [&](uint64_t bytes) {
+            if (cur.bytes && cur.bytes + bytes > cap) {
+                S.ranges.push_back(cur);
+                cur = pf_ctx::KtStream::Range{cur.t1, cur.t1, cur.h1, cur.h1, cur.base + cur.bytes, 0};
+            }
+            cur.bytes += bytes;
+        };
+        for (uint32_t i = 0; i < n; i++) {
+            if (L.on_dev[i]) {
+                while (ti < NT && L.tiles[ti].x == si) { add(L.tbytes[ti]); cur.t1 = (uint32_t)++ti; }
+                si++;
+            } else if (hi < S.host_idx.size() && S.host_idx[hi] == i) {
+                add(S.hsizes[hi]); cur.h1 = (uint32_t)++hi;
+            }
+        }
+        if (cur.bytes) S.ranges.push_back(cur);
+    }
+    const uint32_t NR = (uint32_t)S.ranges.size();
+    uint64_t max_range = 0, peak = 0;
+    for (uint32_t r = 0; r < NR; r++) {
+        max_range = std::max(max_range, S.ranges[r].bytes);
+        peak = std::max(peak, S.ranges[r].bytes + (r + 1 < NR ? S.ranges[r + 1].bytes : 0));
+    }
+    // ---- the buffers, the events, the first two ranges on their way
+    if (NR == 1) PFCHK(c->kt_text.ensure((size_t)total + 64));
+    else if (NR > 1) {
+        PFCHK(c->kt_text.ensure((size_t)max_range + 64, true));
+        PFCHK(c->kt_text2.ensure((size_t)max_range + 64, true));
+    }
+    if (NT) HIPCHK(hipMemcpyAsync(c->kt_toff.p, toff.data(), (size_t)NT * 8, hipMemcpyHostToDevice, c->stream));
+    for (int b = 0; b < 2; b++) {
+        if (!S.ev_prod[b]) HIPCHK(hipEventCreateWithFlags(&S.ev_prod[b], hipEventDisableTiming));
+        if (!S.ev_copied[b]) HIPCHK(hipEventCreateWithFlags(&S.ev_copied[b], hipEventDisableTiming));
+    }
+    S.kp = L.kp;
+    S.seqs = seqs;
+    S.cur = 0; S.cur_off = 0; S.pref_valid = false;
+    S.pin_bytes = std::max<uint64_t>(1, std::min(KT_BLOCK, max_range));
+    S.active = true;
+    for (uint32_t r = 0; r < std::min(NR, 2u); r++) {
+        const int rc = kt_produce(c, r);
+        if (rc != PF_OK) { kt_stream_end(c); return rc; }
+    }
+    c->kt_host_seqs = (uint32_t)S.host_idx.size();
+    *total_bytes = total;
+    *n_ranges = NR;
+    if (peak_text_bytes) *peak_text_bytes = peak;
+    return PF_OK;
+}
+
+int pf_kmers_tsv_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
+    if (!c || !ptr || !nbytes) return fail(PF_ERR_ARG, "null argument");
+    *ptr = nullptr; *nbytes = 0;
+    pf_ctx::KtStream& S = c->kts;
+    if (!S.active) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_next without an open pf_kmers_tsv_stream_begin");
+    HIPCHK(hipSetDevice(c->device));
+    if (S.cur >= S.ranges.size()) { kt_stream_end(c); return PF_OK; }
+    if (!S.pref_valid) PFCHK(kt_copy_block(c, 0));
+    HIPCHK(hipStreamSynchronize(c->side));
+    const int slot = S.pref_slot;
+    const uint64_t n = S.pref_n;
+    S.pref_valid = false;
+    S.cur_off += n;
+    if (S.cur_off == S.ranges[S.cur].bytes) { S.cur++; S.cur_off = 0; }
+    if (S.cur < S.ranges.size()) PFCHK(kt_copy_block(c, slot ^ 1));      // the next block on its way meanwhile
+    *ptr = c->kt_pins[slot];
+    *nbytes = n;
     return PF_OK;
 }
 

@@ -4916,6 +4916,10 @@ struct KtParams {
     uint32_t* tile_bytes;                    // kt_len_kernel out
     const uint64_t* tile_off; char* text;    // kt_text_kernel in / out
     uint32_t k, canon;
+    // kt_text_kernel: workgroup b writes tile tile_first + b at text + tile_off[tile_first + b] - text_base (a range of
+    // the text in a buffer of its own, pf_kmers_tsv_stream_begin; 0 and 0 for the whole text in one buffer)
+    uint32_t tile_first;
+    uint64_t text_base;
 };
 __device__ __forceinline__ uint32_t kt_dec_len(int64_t v) {
     uint64_t a = v < 0 ? 0ull - (uint64_t)v : (uint64_t)v;
@@ -4973,7 +4977,8 @@ __global__ __launch_bounds__(KT_ROWS) void kt_len_kernel(KtParams p) {
 __global__ __launch_bounds__(KT_ROWS) void kt_text_kernel(KtParams p) {
     __shared__ __align__(16) char tile[KT_TILE + 32];
     __shared__ uint32_t wsum[KT_ROWS / 64 + 1];
-    const uint2 t = p.tiles[blockIdx.x];
+    const uint32_t ti = p.tile_first + blockIdx.x;
+    const uint2 t = p.tiles[ti];
     const KtSeq s = p.seqs[t.x];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     KtRow r;
@@ -4985,7 +4990,7 @@ __global__ __launch_bounds__(KT_ROWS) void kt_text_kernel(KtParams p) {
     __syncthreads();
     uint32_t before = x - len, total = 0;
     for (uint32_t i = 0; i < KT_ROWS / 64; i++) { if (i < wave) before += wsum[i]; total += wsum[i]; }
-    const uint64_t gbase = p.tile_off[blockIdx.x];
+    const uint64_t gbase = p.tile_off[ti] - p.text_base;
     const uint32_t mis = (uint32_t)(gbase & 15);                             // tile[mis + i] <-> text[gbase + i]
     if (have && before + len <= KT_TILE) {
         char* w = tile + mis + before;

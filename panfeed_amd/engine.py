@@ -110,8 +110,11 @@ class BatchOutput:
 class Engine:
     def __init__(self, klength=31, canon=True, consider_missing=False, patfilt=True, maf=0.01,
                  multiple_files=False, max_strains=1024, stroi=(), device=0, pattern_capacity=0,
-                 max_items=0, dedup=True, unit_dedup=True, key_binning=True, device_plan=False):
+                 max_items=0, dedup=True, unit_dedup=True, key_binning=True, device_plan=False,
+                 targets_text_budget=8 << 30):
         self.L = _lib.load()
+        # device memory a batch's kmers.tsv text may take when it is streamed to a targets_sink (stream_targets_device)
+        self.targets_text_budget = int(targets_text_budget)
         self.k = int(klength)
         self.canon = bool(canon)
         self.consider_missing = bool(consider_missing)
@@ -253,7 +256,10 @@ class Engine:
         targets_sink (with device_text): called with every block of a batch's kmers.tsv rows as it leaves the device
         (a bytes-like view, valid during the call) instead of the rows being gathered into `out.kmers_tsv` -- with every
         strain a target a batch's rows are tens of gigabytes (BASELINE configs[4]'s second pass: 256 clusters x 5 000
-        samples = 150 GB), which no host buffer should hold; `out.stats["kmers_tsv_streamed"]` says how many bytes went."""
+        samples = 150 GB), which neither a host buffer nor one device buffer should hold: the GPU writes them in ranges of
+        at most `targets_text_budget` bytes of device memory (stream_targets_device); `out.stats["kmers_tsv_streamed"]`
+        says how many bytes went, `"kmers_tsv_ranges"` / `"kmers_tsv_peak_device_bytes"` in how many ranges and with how
+        much device memory at most."""
         from concurrent.futures import ThreadPoolExecutor
         import time as _time
         it = iter(host_batches)
@@ -303,15 +309,15 @@ class Engine:
                     out.kmers_to_hashes, out.hashes_to_patterns = texts
                     # target strains: their rows written by the GPU too (the next submit reuses the device's text
                     # block, so the rows come over now)
-                    streamed = 0
+                    streamed, ranges, peak = 0, 0, 0
                     if hb.n_targets and targets_sink is not None:
-                        for blk in self.render_targets_device(hb).chunks():
-                            targets_sink(blk)
-                            streamed += len(blk)
+                        # in ranges of at most targets_text_budget bytes of device memory
+                        streamed, ranges, peak = self.stream_targets_device(hb, targets_sink)
                         out.kmers_tsv = b""
                     else:
                         out.kmers_tsv = bytes(self.render_targets_device(hb)) if hb.n_targets else b""
                     out.stats = {"clusters": int(hb.n_clusters), "instances": int(hb.n_instances), "kmers_tsv_streamed": streamed,
+                                 "kmers_tsv_ranges": ranges, "kmers_tsv_peak_device_bytes": peak,
                                  "device_instances": int(res.n_instances), "unique_kmers": int(res.n_unique),
                                  "kept_kmers": int(res.n_kept), "new_patterns": int(res.n_new_patterns),
                                  "patterns": self.pattern_count()}
@@ -490,6 +496,46 @@ class Engine:
         del keep
         self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": _time.time() - t1, "copy_s": 0.0}
         return DeviceText(self, nb.value)
+
+    def stream_targets_device(self, hb, sink, budget=None):
+        """kmers.tsv rows of every target sequence of `hb` (the last submit), written on the device in ranges that take
+        at most `budget` bytes of device memory (default: targets_text_budget) and handed to `sink` block by block (a
+        memoryview of pinned memory, valid during the call) -- pf_kmers_tsv_stream_begin / _next.  The blocks joined are
+        the bytes of `render_targets_device(hb)`.  Returns (bytes, ranges, peak device text bytes)."""
+        import time as _time
+        t0 = _time.time()
+        budget = self.targets_text_budget if budget is None else int(budget)
+        if hb.target_table is not None and hb.target_table.resolve is not None and hb._targets is None:
+            rec, n, keep, held = self._marshal_table(hb, hb.target_table)
+        else:
+            rec, n, keep = self._marshal_targets(hb, hb.targets)
+            held = None
+        streamed = 0
+        try:
+            # (the records and the strings they point to are read until the last block: the host renders its share of
+            # every range when the range is written)
+            arr = C.cast(rec.ctypes.data, C.POINTER(_lib.TargetSeq))
+            total, ranges, peak = C.c_uint64(), C.c_uint32(), C.c_uint64()
+            t1 = _time.time()
+            _lib.check(self.L.pf_kmers_tsv_stream_begin(self.ctx, arr, n, budget, C.byref(total), C.byref(ranges),
+                                                        C.byref(peak)))
+            ptr, nb = C.c_void_p(), C.c_uint64()
+            while True:
+                _lib.check(self.L.pf_kmers_tsv_stream_next(self.ctx, C.byref(ptr), C.byref(nb)))
+                m = int(nb.value)
+                if not m:
+                    break
+                sink(memoryview((C.c_char * m).from_address(ptr.value)).cast("B"))
+                streamed += m
+        finally:
+            if held is not None:
+                from .packing import _release_held
+                _release_held(held)
+            del keep
+        if streamed != int(total.value):
+            raise _lib.PanfeedHipError(_lib.ERR_STATE, f"kmers.tsv stream: {streamed} bytes handed out of {total.value}")
+        self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": _time.time() - t1, "copy_s": 0.0}
+        return streamed, int(ranges.value), int(peak.value)
 
     _TS = np.dtype([("cluster", "u8"), ("strain", "u8"), ("id", "u8"), ("chromosome", "u8"), ("sequence", "u8"),
                     ("compsequence", "u8"), ("len", "u4"), ("strand", "i4"), ("start", "i8"), ("end", "i8"),

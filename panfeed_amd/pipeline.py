@@ -36,13 +36,14 @@ def _peek_n_strains(presence_absence):
 def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon=True, consider_missing=False,
               patfilt=True, maf=0.01, upstream=0, downstream=0, downstream_start_codon=False, targets=(), genes=None,
               compress=False, multiple_files=False, batch_clusters=256, resident=True, device_text=True, device=0,
-              max_items=0, pattern_capacity=0, overlap=True, one_pass=True):
+              max_items=0, pattern_capacity=0, overlap=True, one_pass=True, raise_missing=False):
     """One directory of outputs (`kmers.tsv`, `kmers_to_hashes.tsv`, `hashes_to_patterns.tsv`, `.gz` under
     `compress`; under `multiple_files` one such directory per gene cluster, `<output>/<cluster>/`, the pattern set
     starting empty in each: `panfeed.py:35-43,153-167`) from a panaroo table and a directory (or file of files) of GFFs.  Option names and meaning follow
     the reference's (`__main__.py:86-186`); `patfilt` is what `pattern_hasher` receives (`--no-filter` inverted,
     `__main__.py:283-297`).  one_pass (with resident): the genomes go to the GPU as their files are read
-    (pf_pangenome_open_device) instead of being read into host strings first and uploaded afterwards.
+    (pf_pangenome_open_device) instead of being read into host strings first and uploaded afterwards.  raise_missing
+    (`--stop-on-missing`): a strain, contig or gene of the table that is not found is an error instead of a warning.
     Returns a dict of counters."""
     import time as _time
     t_start = _time.perf_counter()
@@ -89,7 +90,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
             return early["eng"]
         try:
             pg = Pangenome(presence_absence, gffdir, fastadir, upstream, downstream, downstream_start_codon,
-                           targets=targets, genes=genes, engine=engine_when_needed)
+                           targets=targets, genes=genes, raise_missing=raise_missing, engine=engine_when_needed)
         except BaseException:
             et.join()
             if "eng" in early:
@@ -107,7 +108,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
             et.start()
         try:
             pg = Pangenome(presence_absence, gffdir, fastadir, upstream, downstream, downstream_start_codon, targets=targets,
-                           genes=genes)
+                           genes=genes, raise_missing=raise_missing)
         except BaseException:
             if et is not None:
                 et.join()
