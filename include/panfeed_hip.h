@@ -538,6 +538,39 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
 int pf_rowfilter_stats(pf_rowfilter* f, uint64_t* bytes_scanned, float* device_ms);
 void pf_rowfilter_destroy(pf_rowfilter* f);
 
+/*
+ * panfeed-plot's per-cluster grids on the device, over the annotated k-mer table that
+ * panfeed-get-kmers writes.  Replaces /root/reference/panfeed/plot.py:195-222 (the whole table in one pandas frame, the
+ * `isin` strain filter at :200, the base letter / scalar at :209-222) and the three pivot_tables per cluster at
+ * :261-305 (max of the significances, handle_paralogs, handle_paralogs_text).
+ *
+ * pf_plotgrid_create: the phenotype strains (their index is the grid row), the column indices of cluster, strain,
+ * gene_start, k-mer, strand and the p-value column (columns[6], in that order), and the --start/--stop zoom (zoom != 0).
+ * pf_plotgrid_scan: a block of the table's data lines (no header) that starts at a line start; the complete lines are
+ * read, *consumed = their bytes (the caller puts the rest in front of its next block).  Rows of other strains are
+ * dropped; the cluster names of the rest, before the zoom, make the cluster table; rows inside the zoom become records.
+ * A row whose gene_start is not an integer is dropped.  Cluster names and p-value texts are matched by their bytes.
+ * pf_plotgrid_finish ends the scan.  Clusters and distinct p-value texts then have dense ids (arbitrary order): names /
+ * texts are the joined bytes, offsets n + 1 entries, min / max gene_start and row count per cluster (pointers valid
+ * until destroy).  pf_plotgrid_set_significance: per p-value id, the 64-bit ordered key of -log10(p) computed by the
+ * caller (bits ^ 0x8000... for a positive double, ~bits for a negative one; 0 for NaN) -- the device never computes it.
+ * pf_plotgrid_grids: the grids of n clusters (ids), one after the other, n_strains x (max - min + 1) cells each,
+ * strain-major: key_out = the largest key of the cell's rows (0: none but NaN), cnt_out = rows << 32 | sum of the
+ * rows' base letters (with one row: its letter; 0 for an empty k-mer).  Integer atomics only: the same bits every run.
+ */
+typedef struct pf_plotgrid pf_plotgrid;
+int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* strain_len, uint32_t n_strains,
+                       const int32_t* columns, int zoom, int64_t start, int64_t stop, pf_plotgrid** out);
+int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t* consumed);
+int pf_plotgrid_finish(pf_plotgrid* g, uint32_t* n_clusters, uint64_t* n_pvalues, uint64_t* n_records);
+int pf_plotgrid_clusters(pf_plotgrid* g, const char** names, const uint64_t** name_off, const int32_t** min_pos,
+                         const int32_t** max_pos, const uint64_t** rows);
+int pf_plotgrid_pvalues(pf_plotgrid* g, const char** texts, const uint64_t** text_off);
+int pf_plotgrid_set_significance(pf_plotgrid* g, const uint64_t* keys);
+int pf_plotgrid_grids(pf_plotgrid* g, const uint32_t* ids, uint32_t n, uint64_t* key_out, uint64_t* cnt_out);
+int pf_plotgrid_stats(pf_plotgrid* g, uint64_t* bytes_scanned, uint64_t* lines, uint64_t* records, float* device_ms);
+void pf_plotgrid_destroy(pf_plotgrid* g);
+
 #ifdef __cplusplus
 }
 #endif

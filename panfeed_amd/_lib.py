@@ -146,6 +146,8 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_pangenome_set_store", "pf_genomes_upload", "pf_genomes_clear", "pf_submit_gather", "pf_gzip_members", "pf_render_device",
            "pf_render_device_ex", "pf_render_pattern_rows", "pf_pangenome_weights", "pf_pangenome_set_range",
            "pf_rowfilter_create", "pf_rowfilter_scan", "pf_rowfilter_stats", "pf_rowfilter_destroy",
+           "pf_plotgrid_create", "pf_plotgrid_scan", "pf_plotgrid_finish", "pf_plotgrid_clusters", "pf_plotgrid_pvalues",
+           "pf_plotgrid_set_significance", "pf_plotgrid_grids", "pf_plotgrid_stats", "pf_plotgrid_destroy",
            "pf_py_str_addresses", "pf_pangenome_close_async", "pf_py_seqinfo_columns", "pf_py_release"]
 
 RENDER_NO_PATTERN_ROWS = 1
@@ -261,6 +263,20 @@ def _load_locked():
     L.pf_rowfilter_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
     L.pf_rowfilter_destroy.argtypes = [C.c_void_p]
     L.pf_rowfilter_destroy.restype = None
+    L.pf_plotgrid_create.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.c_void_p, C.c_int,
+                                     C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
+    L.pf_plotgrid_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.pf_plotgrid_finish.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.pf_plotgrid_clusters.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_uint64)),
+                                       C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),
+                                       C.POINTER(C.POINTER(C.c_uint64))]
+    L.pf_plotgrid_pvalues.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_uint64))]
+    L.pf_plotgrid_set_significance.argtypes = [C.c_void_p, C.c_void_p]
+    L.pf_plotgrid_grids.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.pf_plotgrid_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_float)]
+    L.pf_plotgrid_destroy.argtypes = [C.c_void_p]
+    L.pf_plotgrid_destroy.restype = None
     L.pf_gzip_members.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pf_submit_gather.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Gather), C.POINTER(Result)]
     L.pf_records_free.argtypes = [C.c_void_p]

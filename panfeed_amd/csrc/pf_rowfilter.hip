@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <unordered_set>
 #include <thread>
@@ -303,6 +304,754 @@ int pf_rowfilter_stats(pf_rowfilter* f, uint64_t* bytes_scanned, float* device_m
     if (!f) return rf_fail(PF_ERR_ARG, "pf_rowfilter_stats: null argument");
     if (bytes_scanned) *bytes_scanned = f->bytes_scanned;
     if (device_ms) *device_ms = f->device_ms;
+    return PF_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// panfeed-plot's grids: /root/reference/panfeed/plot.py:195-222 (the table, the strain filter, the
+// base scalar) and :261-305 (three pivot_tables per cluster) on the device.
+//
+// pf_plotgrid_scan takes blocks of complete lines of the annotated k-mer table.  One thread per line end finds the
+// line behind it and its six fields; a row whose strain is a phenotype strain (device hash set, verified by bytes)
+// gets its cluster name found or inserted in a device name table, its gene_start / strand parsed, its base letter
+// taken from the k-mer, the --start/--stop zoom applied and its p-value TEXT found or inserted in a dictionary of
+// distinct strings; then one 16-byte record goes to an HBM buffer.  Both tables are open addressing on 64-bit hashes:
+// the slot is the id, the thread that claims a slot copies its bytes to an arena, and a second kernel checks every
+// row's bytes against its slot's (a 64-bit collision stops the run instead of merging two names).  No arithmetic on
+// floats happens on the device: the significance of every distinct p-value string is computed by the host and comes
+// back as a 64-bit ordered integer key, and the grid kernel reduces with integer atomics only (atomicMax of the key,
+// atomicAdd of a count | letter word), so grids are the same bits whatever the order of the rows.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t PG_MAX_FIELD = 4095;          // longer name / p-value fields drop the row (PG_ERR_LONG)
+constexpr uint32_t PG_NONE = 0xFFFFFFFFu;
+enum : uint32_t { PG_ERR_CLUSTER = 1, PG_ERR_PVALUE = 2, PG_ERR_LONG = 4, PG_ERR_RANGE = 8 };
+
+struct PgTable {              // open addressing; hash 0 = free; str = arena offset << 16 | length
+    unsigned long long* hash;
+    unsigned long long* str;
+    uint64_t cap;             // power of two
+    unsigned char* arena;
+    unsigned long long* arena_used;
+    unsigned long long* count;
+};
+
+struct PgRecord {             // 16 B per kept row
+    uint32_t cluster;         // cluster table slot
+    uint32_t strain_letter;   // phenotype strain id << 8 | base letter (0: no letter)
+    int32_t pos;              // gene_start
+    uint32_t pvalue;          // p-value dictionary slot
+};
+
+struct PgCheck {              // one row that passed the strain filter: its fields, to be checked against the tables
+    uint32_t cl_off, cl_len, cl_slot, pv_off, pv_len, pv_slot;
+};
+
+struct PgScanParams {
+    const unsigned char* text;
+    uint64_t n;
+    int32_t col[6];           // cluster, strain, gene_start, k-mer, strand, p-value
+    int32_t max_col;
+    const unsigned long long* strain_hash;   // static set: hash, strain id
+    const uint32_t* strain_id;
+    uint64_t strain_cap;
+    const unsigned char* strain_bytes;
+    const uint64_t* strain_str;              // offset << 16 | length, by strain id
+    PgTable clusters, pvalues;
+    int zoom;
+    int64_t start, stop;
+    PgRecord* rec;
+    unsigned long long* n_rec;
+    PgCheck* chk;
+    unsigned long long* n_chk;
+    unsigned long long* n_lines;
+    unsigned int* err;
+};
+
+__device__ __forceinline__ uint64_t pg_hash(const unsigned char* s, uint32_t n) {
+    uint64_t h = 0xCBF29CE484222325ull;
+    for (uint32_t i = 0; i < n; i++) h = rf_hash_step(h, s[i]);
+    return rf_hash_fin(h);
+}
+
+// an integer field as pandas reads an int column ("12", "-3"; "12.0" as a float column holds it); false if it is not one
+__device__ __forceinline__ bool pg_int(const unsigned char* s, uint32_t n, int64_t* v) {
+    uint32_t i = 0;
+    bool neg = false;
+    if (i < n && (s[i] == '-' || s[i] == '+')) { neg = s[i] == '-'; i++; }
+    const uint32_t d0 = i;
+    int64_t x = 0;
+    while (i < n && s[i] >= '0' && s[i] <= '9') {
+        if (x > ((int64_t)1 << 40)) return false;
+        x = x * 10 + (s[i] - '0');
+        i++;
+    }
+    if (i == d0) return false;
+    if (i < n && s[i] == '.') { i++; while (i < n && s[i] == '0') i++; }
+    if (i != n) return false;
+    *v = neg ? -x : x;
+    return true;
+}
+
+__device__ __forceinline__ unsigned char pg_upper(unsigned char c) { return (c >= 'a' && c <= 'z') ? c - 32 : c; }
+
+// find or insert; returns the slot.  The claimer copies the bytes; others are checked later (pg_check_kernel).
+__device__ uint32_t pg_find_insert(const PgTable& t, const unsigned char* s, uint32_t n) {
+    const unsigned long long h = pg_hash(s, n);
+    uint64_t slot = h & (t.cap - 1);
+    for (uint64_t probes = 0; probes < t.cap; probes++) {
+        unsigned long long cur = t.hash[slot];
+        if (cur == 0) cur = atomicCAS(&t.hash[slot], 0ull, h);
+        if (cur == 0) {                                         // claimed: this thread's bytes name the slot
+            const unsigned long long off = atomicAdd(t.arena_used, (unsigned long long)n);
+            for (uint32_t i = 0; i < n; i++) t.arena[off + i] = s[i];
+            t.str[slot] = (off << 16) | n;
+            atomicAdd(t.count, 1ull);
+            return (uint32_t)slot;
+        }
+        if (cur == h) return (uint32_t)slot;
+        slot = (slot + 1) & (t.cap - 1);
+    }
+    return PG_NONE;                                             // cannot happen: the host keeps the load under 1/2
+}
+
+__device__ __forceinline__ int64_t pg_strain(const PgScanParams& p, const unsigned char* s, uint32_t n) {
+    const uint64_t h = pg_hash(s, n);
+    uint64_t slot = h & (p.strain_cap - 1);
+    for (uint64_t probes = 0; probes < p.strain_cap; probes++) {
+        const unsigned long long cur = p.strain_hash[slot];
+        if (cur == 0) return -1;
+        if (cur == h) {
+            const uint32_t id = p.strain_id[slot];
+            const uint64_t st = p.strain_str[id];
+            if ((uint32_t)(st & 0xFFFF) == n) {
+                const unsigned char* b = p.strain_bytes + (st >> 16);
+                uint32_t i = 0;
+                while (i < n && b[i] == s[i]) i++;
+                if (i == n) return id;
+            }
+        }
+        slot = (slot + 1) & (p.strain_cap - 1);
+    }
+    return -1;
+}
+
+__device__ void pg_line(const PgScanParams& p, uint64_t s) {
+    if (s >= p.n || p.text[s] == '\n') return;                  // a blank line: pandas skips it
+    atomicAdd(p.n_lines, 1ull);
+    uint64_t fs[6], fe[6];
+    int found = 0;
+    int f = 0;
+    uint64_t b = s;
+    for (uint64_t e = s; e < p.n; e++) {
+        const unsigned char c = p.text[e];
+        if (c != '\t' && c != '\n') continue;
+#pragma unroll
+        for (int q = 0; q < 6; q++)
+            if (p.col[q] == f) { fs[q] = b; fe[q] = e; found |= 1 << q; }
+        f++;
+        b = e + 1;
+        if (c == '\n' || f > p.max_col) break;
+    }
+    if (found != 0x3F) return;                                  // a short line: no strain to keep it by
+    const unsigned char* t = p.text;
+    const int64_t sid = pg_strain(p, t + fs[1], (uint32_t)(fe[1] - fs[1]));
+    if (sid < 0) return;                                        // plot.py:200, the isin
+    const uint32_t cl_len = (uint32_t)(fe[0] - fs[0]), pv_len = (uint32_t)(fe[5] - fs[5]);
+    if (cl_len > PG_MAX_FIELD || pv_len > PG_MAX_FIELD) { atomicOr(p.err, PG_ERR_LONG); return; }
+    const uint32_t cslot = pg_find_insert(p.clusters, t + fs[0], cl_len);
+    int64_t pos;
+    const bool pos_ok = pg_int(t + fs[2], (uint32_t)(fe[2] - fs[2]), &pos);
+    if (pos_ok && (pos < -2147483647ll || pos > 2147483647ll)) atomicOr(p.err, PG_ERR_RANGE);
+    const bool keep = pos_ok && pos >= -2147483647ll && pos <= 2147483647ll && (!p.zoom || (pos >= p.start && pos <= p.stop));
+    uint32_t pslot = PG_NONE;
+    if (keep) {
+        int64_t strand = 0;
+        const bool minus = pg_int(t + fs[4], (uint32_t)(fe[4] - fs[4]), &strand) && strand == -1;
+        unsigned char letter = 0;                               // an empty k-mer is NaN: no letter, no scalar
+        if (fe[3] > fs[3]) {
+            if (minus) {                                        // plot.py:215-220: complement of the last letter
+                const unsigned char c = pg_upper(t[fe[3] - 1]);
+                letter = c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'G' ? 'C' : c == 'C' ? 'G' : 'N';
+            } else {
+                letter = pg_upper(t[fs[3]]);
+            }
+        }
+        pslot = pg_find_insert(p.pvalues, t + fs[5], pv_len);
+        const unsigned long long r = atomicAdd(p.n_rec, 1ull);
+        p.rec[r] = PgRecord{cslot, ((uint32_t)sid << 8) | letter, (int32_t)pos, pslot};
+    }
+    const unsigned long long k = atomicAdd(p.n_chk, 1ull);
+    p.chk[k] = PgCheck{(uint32_t)fs[0], cl_len, cslot, (uint32_t)fs[5], pv_len, pslot};
+}
+
+__global__ __launch_bounds__(256) void pg_scan_kernel(PgScanParams p) {
+    const uint64_t nvec = (p.n + 15) / 16;
+    for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < nvec; v += (uint64_t)gridDim.x * blockDim.x) {
+        const uint4 w = reinterpret_cast<const uint4*>(p.text)[v];
+        const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+        if (v == 0) pg_line(p, 0);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint32_t x = ws[q] ^ 0x0A0A0A0Au;
+            uint32_t m = (x - 0x01010101u) & ~x & 0x80808080u;
+            while (m) {
+                const int b = (__ffs((int)m) - 1) >> 3;
+                m &= m - 1;
+                const uint64_t at = v * 16 + q * 4 + b;
+                if (at + 1 < p.n) pg_line(p, at + 1);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ bool pg_same(const PgTable& t, uint32_t slot, const unsigned char* s, uint32_t n) {
+    if (slot == PG_NONE) return false;
+    const unsigned long long st = t.str[slot];
+    if ((uint32_t)(st & 0xFFFF) != n) return false;
+    const unsigned char* b = t.arena + (st >> 16);
+    for (uint32_t i = 0; i < n; i++)
+        if (b[i] != s[i]) return false;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void pg_check_kernel(const unsigned char* text, const PgCheck* chk, uint64_t n_chk,
+                                                        PgTable clusters, PgTable pvalues, unsigned int* err) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_chk; i += (uint64_t)gridDim.x * blockDim.x) {
+        const PgCheck c = chk[i];
+        if (!pg_same(clusters, c.cl_slot, text + c.cl_off, c.cl_len)) atomicOr(err, PG_ERR_CLUSTER);
+        if (c.pv_slot != PG_NONE && !pg_same(pvalues, c.pv_slot, text + c.pv_off, c.pv_len)) atomicOr(err, PG_ERR_PVALUE);
+    }
+}
+
+// a table grown to a new capacity: every entry re-inserted (all hashes are distinct), remap[old slot] = new slot
+__global__ __launch_bounds__(256) void pg_rehash_kernel(PgTable from, PgTable to, uint32_t* remap) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < from.cap; i += (uint64_t)gridDim.x * blockDim.x) {
+        const unsigned long long h = from.hash[i];
+        if (!h) continue;
+        uint64_t slot = h & (to.cap - 1);
+        while (atomicCAS(&to.hash[slot], 0ull, h) != 0ull) slot = (slot + 1) & (to.cap - 1);
+        to.str[slot] = from.str[i];
+        remap[i] = (uint32_t)slot;
+    }
+}
+
+__global__ __launch_bounds__(256) void pg_remap_kernel(PgRecord* rec, uint64_t n, const uint32_t* remap, int field) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t& id = field == 0 ? rec[i].cluster : rec[i].pvalue;
+        if (id != PG_NONE) id = remap[id];
+    }
+}
+
+// per cluster slot: smallest and largest gene_start, row count (plot.py:266 / :297, the reindexed column range)
+__global__ __launch_bounds__(256) void pg_stats_kernel(const PgRecord* rec, uint64_t n, int* mn, int* mx,
+                                                        unsigned long long* cnt) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const PgRecord r = rec[i];
+        if (r.cluster == PG_NONE) continue;
+        atomicMin(&mn[r.cluster], r.pos);
+        atomicMax(&mx[r.cluster], r.pos);
+        atomicAdd(&cnt[r.cluster], 1ull);
+    }
+}
+
+struct PgGridParams {
+    const PgRecord* rec;
+    uint64_t n;
+    const int32_t* slot_item;                  // cluster slot -> item of this batch, -1 if not in it
+    const uint64_t* item_off;                  // first cell of the item's grid (strain-major, n_strains x width)
+    const int32_t* item_min;
+    const uint32_t* item_width;
+    uint32_t n_strains;
+    const unsigned long long* sig_key;         // p-value slot -> ordered key of its significance; 0 = NaN
+    unsigned long long* key;                   // per cell: max key (0: no non-NaN significance)
+    unsigned long long* cnt;                   // per cell: rows << 32 | sum of their letters
+    unsigned int* err;
+};
+
+__global__ __launch_bounds__(256) void pg_grid_kernel(PgGridParams p) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < p.n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const PgRecord r = p.rec[i];
+        if (r.cluster == PG_NONE || r.pvalue == PG_NONE) { atomicOr(p.err, PG_ERR_RANGE); continue; }
+        const int32_t item = p.slot_item[r.cluster];
+        if (item < 0) continue;
+        const uint32_t strain = r.strain_letter >> 8;
+        const int64_t col = (int64_t)r.pos - p.item_min[item];
+        if (strain >= p.n_strains || col < 0 || col >= (int64_t)p.item_width[item]) { atomicOr(p.err, PG_ERR_RANGE); continue; }
+        const uint64_t cell = p.item_off[item] + (uint64_t)strain * p.item_width[item] + (uint64_t)col;
+        const unsigned long long k = p.sig_key[r.pvalue];
+        if (k) atomicMax(&p.key[cell], k);                     // pandas' NaN-skipping max (plot.py:261-264)
+        atomicAdd(&p.cnt[cell], (1ull << 32) | (r.strain_letter & 0xFF));   // handle_paralogs: the count decides
+    }
+}
+
+inline uint32_t pg_blocks(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 256 * 16)); }
+
+}  // namespace
+
+struct pf_plotgrid {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float device_ms = 0;
+    int32_t col[6] = {};
+    int32_t max_col = 0;
+    int zoom = 0;
+    int64_t start = 0, stop = 0;
+    uint32_t n_strains = 0;
+    // the phenotype strains (static)
+    unsigned long long* d_strain_hash = nullptr;
+    uint32_t* d_strain_id = nullptr;
+    uint64_t strain_cap = 0;
+    unsigned char* d_strain_bytes = nullptr;
+    uint64_t* d_strain_str = nullptr;
+    // the two growing tables
+    struct Tab {
+        unsigned long long* hash = nullptr;
+        unsigned long long* str = nullptr;
+        uint64_t cap = 0;
+        unsigned char* arena = nullptr;
+        uint64_t arena_cap = 0;
+        unsigned long long* ctr = nullptr;       // [0] arena bytes used, [1] entries
+        uint64_t used = 0, count = 0;            // host copies after the last scan
+    } cl, pv;
+    PgRecord* d_rec = nullptr;
+    uint64_t rec_cap = 0, n_rec = 0;
+    PgCheck* d_chk = nullptr;
+    uint64_t chk_cap = 0;
+    unsigned long long* d_ctr = nullptr;        // [0] records [1] checks [2] lines ; err as [3]
+    unsigned char* d_text = nullptr;
+    size_t text_cap = 0;
+    char* pin = nullptr;
+    uint64_t bytes_scanned = 0, lines = 0;
+    // after pf_plotgrid_finish
+    int finished = 0;
+    std::vector<uint32_t> cl_slot, pv_slot;     // dense id -> slot
+    std::vector<int32_t> cl_min, cl_max;
+    std::vector<uint64_t> cl_rows;
+    std::string cl_names, pv_texts;
+    std::vector<uint64_t> cl_off, pv_off;
+    unsigned long long* d_sig = nullptr;       // by p-value slot
+    int sig_set = 0;
+    unsigned long long* d_key = nullptr;
+    unsigned long long* d_cnt = nullptr;
+    uint64_t grid_cap = 0;
+    int32_t* d_slot_item = nullptr;
+    uint64_t* d_item = nullptr;                // off[n] | min[n] | width[n], packed in one buffer
+    uint64_t item_cap = 0;
+};
+
+namespace {
+
+PgTable pg_view(pf_plotgrid::Tab& t) { return PgTable{t.hash, t.str, t.cap, t.arena, t.ctr, t.ctr + 1}; }
+
+int pg_tab_alloc(pf_plotgrid::Tab& t, uint64_t cap, hipStream_t s) {
+    RFCHK(hipMalloc((void**)&t.hash, cap * 8));
+    RFCHK(hipMalloc((void**)&t.str, cap * 8));
+    RFCHK(hipMemsetAsync(t.hash, 0, cap * 8, s));
+    t.cap = cap;
+    return PF_OK;
+}
+
+// room for `more` new entries (and `bytes` new arena bytes) at a load of at most 1/2; records' slots follow a move
+int pg_tab_reserve(pf_plotgrid* g, pf_plotgrid::Tab& t, uint64_t more, uint64_t bytes, int field) {
+    if (t.used + bytes > t.arena_cap) {
+        uint64_t want = std::max<uint64_t>((t.used + bytes) * 2, 1 << 20);
+        if (want >= ((uint64_t)1 << 47)) return rf_fail(PF_ERR_CAPACITY, "pf_plotgrid: name arena over 2^47 bytes");
+        unsigned char* a = nullptr;
+        RFCHK(hipMalloc((void**)&a, want));
+        if (t.used) RFCHK(hipMemcpyAsync(a, t.arena, t.used, hipMemcpyDeviceToDevice, g->stream));
+        RFCHK(hipStreamSynchronize(g->stream));
+        if (t.arena) (void)hipFree(t.arena);
+        t.arena = a;
+        t.arena_cap = want;
+    }
+    uint64_t cap = std::max<uint64_t>(t.cap, 1024);
+    while (cap < 2 * (t.count + more)) cap <<= 1;
+    if (cap >= ((uint64_t)1 << 32)) return rf_fail(PF_ERR_CAPACITY, "pf_plotgrid: over 2^31 distinct names in a table");
+    if (cap == t.cap) return PF_OK;
+    pf_plotgrid::Tab n = t;
+    n.hash = nullptr; n.str = nullptr;
+    if (int rc = pg_tab_alloc(n, cap, g->stream)) return rc;
+    if (t.hash) {
+        uint32_t* remap = nullptr;
+        RFCHK(hipMalloc((void**)&remap, t.cap * 4));
+        hipLaunchKernelGGL(pg_rehash_kernel, dim3(pg_blocks(t.cap)), dim3(256), 0, g->stream, pg_view(t), pg_view(n), remap);
+        RFCHK(hipGetLastError());
+        if (g->n_rec) {
+            hipLaunchKernelGGL(pg_remap_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->stream, g->d_rec, g->n_rec,
+                               (const uint32_t*)remap, field);
+            RFCHK(hipGetLastError());
+        }
+        RFCHK(hipStreamSynchronize(g->stream));
+        (void)hipFree(remap);
+        (void)hipFree(t.hash);
+        (void)hipFree(t.str);
+    }
+    t.hash = n.hash; t.str = n.str; t.cap = cap;
+    return PF_OK;
+}
+
+void pg_tab_free(pf_plotgrid::Tab& t) {
+    if (t.hash) (void)hipFree(t.hash);
+    if (t.str) (void)hipFree(t.str);
+    if (t.arena) (void)hipFree(t.arena);
+    if (t.ctr) (void)hipFree(t.ctr);
+}
+
+// the table's entries in slot order: dense id -> slot, their bytes joined, offsets (n + 1)
+int pg_tab_list(pf_plotgrid* g, pf_plotgrid::Tab& t, std::vector<uint32_t>& slots, std::string& bytes, std::vector<uint64_t>& off) {
+    std::vector<unsigned long long> h(t.cap), st(t.cap);
+    std::string arena(t.used, '\0');
+    if (t.cap) {
+        RFCHK(hipMemcpy(h.data(), t.hash, t.cap * 8, hipMemcpyDeviceToHost));
+        RFCHK(hipMemcpy(st.data(), t.str, t.cap * 8, hipMemcpyDeviceToHost));
+    }
+    if (t.used) RFCHK(hipMemcpy(&arena[0], t.arena, t.used, hipMemcpyDeviceToHost));
+    slots.clear(); bytes.clear(); off.assign(1, 0);
+    for (uint64_t i = 0; i < t.cap; i++) {
+        if (!h[i]) continue;
+        slots.push_back((uint32_t)i);
+        bytes.append(arena, (size_t)(st[i] >> 16), (size_t)(st[i] & 0xFFFF));
+        off.push_back(bytes.size());
+    }
+    return PF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pf_plotgrid_destroy(pf_plotgrid* g) {
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    for (void* q : {(void*)g->d_strain_hash, (void*)g->d_strain_id, (void*)g->d_strain_bytes, (void*)g->d_strain_str,
+                    (void*)g->d_rec, (void*)g->d_chk, (void*)g->d_ctr, (void*)g->d_text, (void*)g->d_sig, (void*)g->d_key,
+                    (void*)g->d_cnt, (void*)g->d_slot_item, (void*)g->d_item})
+        if (q) (void)hipFree(q);
+    pg_tab_free(g->cl);
+    pg_tab_free(g->pv);
+    if (g->pin) (void)hipHostFree(g->pin);
+    if (g->e0) (void)hipEventDestroy(g->e0);
+    if (g->e1) (void)hipEventDestroy(g->e1);
+    if (g->stream) (void)hipStreamDestroy(g->stream);
+    delete g;
+}
+
+int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* strain_len, uint32_t n_strains,
+                       const int32_t* columns, int zoom, int64_t start, int64_t stop, pf_plotgrid** out) {
+    if (!out || !columns || (n_strains && (!strains || !strain_len))) return rf_fail(PF_ERR_ARG, "pf_plotgrid_create: null argument");
+    *out = nullptr;
+    if (n_strains >= (1u << 24)) return rf_fail(PF_ERR_ARG, "pf_plotgrid_create: at most 2^24 - 1 phenotype strains");
+    int ndev = 0;
+    RFCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return rf_fail(PF_ERR_ARG, "pf_plotgrid_create: no such device");
+    RFCHK(hipSetDevice(device));
+    std::unique_ptr<pf_plotgrid, void (*)(pf_plotgrid*)> g(new pf_plotgrid(), pf_plotgrid_destroy);
+    g->device = device;
+    g->zoom = zoom ? 1 : 0;
+    g->start = start; g->stop = stop;
+    g->n_strains = n_strains;
+    for (int q = 0; q < 6; q++) {
+        if (columns[q] < 0) return rf_fail(PF_ERR_ARG, "pf_plotgrid_create: negative column index");
+        g->col[q] = columns[q];
+        g->max_col = std::max(g->max_col, columns[q]);
+    }
+    // the strain set: distinct names (a repeated phenotype name keeps its first id)
+    uint64_t cap = 1024;
+    while (cap < 2 * ((uint64_t)n_strains + 1)) cap <<= 1;
+    std::vector<unsigned long long> hs(cap, 0);
+    std::vector<uint32_t> ids(cap, 0);
+    std::string bytes;
+    std::vector<uint64_t> str(std::max<uint32_t>(n_strains, 1), 0);
+    for (uint32_t i = 0; i < n_strains; i++) {
+        if (strain_len[i] > 0xFFFF) return rf_fail(PF_ERR_ARG, "pf_plotgrid_create: strain name over 65535 bytes");
+        str[i] = ((uint64_t)bytes.size() << 16) | strain_len[i];
+        bytes.append(strains[i], strain_len[i]);
+        const uint64_t h = rf_hash(strains[i], strain_len[i]);
+        uint64_t slot = h & (cap - 1);
+        bool dup = false;
+        while (hs[slot]) {
+            if (hs[slot] == h) {
+                const uint64_t o = str[ids[slot]];
+                if ((o & 0xFFFF) == strain_len[i] && !memcmp(bytes.data() + (o >> 16), strains[i], strain_len[i])) { dup = true; break; }
+            }
+            slot = (slot + 1) & (cap - 1);
+        }
+        if (dup) continue;
+        hs[slot] = h;
+        ids[slot] = i;
+    }
+    g->strain_cap = cap;
+    RFCHK(hipStreamCreate(&g->stream));
+    RFCHK(hipEventCreate(&g->e0));
+    RFCHK(hipEventCreate(&g->e1));
+    RFCHK(hipMalloc((void**)&g->d_strain_hash, cap * 8));
+    RFCHK(hipMalloc((void**)&g->d_strain_id, cap * 4));
+    RFCHK(hipMalloc((void**)&g->d_strain_bytes, std::max<size_t>(bytes.size(), 1)));
+    RFCHK(hipMalloc((void**)&g->d_strain_str, str.size() * 8));
+    RFCHK(hipMemcpy(g->d_strain_hash, hs.data(), cap * 8, hipMemcpyHostToDevice));
+    RFCHK(hipMemcpy(g->d_strain_id, ids.data(), cap * 4, hipMemcpyHostToDevice));
+    if (!bytes.empty()) RFCHK(hipMemcpy(g->d_strain_bytes, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+    RFCHK(hipMemcpy(g->d_strain_str, str.data(), str.size() * 8, hipMemcpyHostToDevice));
+    RFCHK(hipMalloc((void**)&g->d_ctr, 4 * 8));
+    RFCHK(hipMemset(g->d_ctr, 0, 4 * 8));
+    for (auto* t : {&g->cl, &g->pv}) {
+        RFCHK(hipMalloc((void**)&t->ctr, 2 * 8));
+        RFCHK(hipMemset(t->ctr, 0, 2 * 8));
+    }
+    *out = g.release();
+    return PF_OK;
+}
+
+int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t* consumed) {
+    if (!g || !consumed || (nbytes && !text)) return rf_fail(PF_ERR_ARG, "pf_plotgrid_scan: null argument");
+    if (g->finished) return rf_fail(PF_ERR_STATE, "pf_plotgrid_scan: after pf_plotgrid_finish");
+    RFCHK(hipSetDevice(g->device));
+    *consumed = 0;
+    uint64_t n = nbytes;
+    while (n && text[n - 1] != '\n') n--;
+    *consumed = n;
+    if (!n) return PF_OK;
+    if (n >= ((uint64_t)1 << 32)) return rf_fail(PF_ERR_ARG, "pf_plotgrid_scan: a block of 4 GiB or more");
+    // every row needs max_col tabs and a newline: at most this many rows pass
+    const uint64_t rows = n / ((uint64_t)g->max_col + 1) + 1;
+    const size_t padded = (n + 15) / 16 * 16 + 16;
+    if (padded > g->text_cap) {
+        if (g->d_text) (void)hipFree(g->d_text);
+        if (g->pin) (void)hipHostFree(g->pin);
+        g->d_text = nullptr; g->pin = nullptr; g->text_cap = 0;
+        const size_t want = padded + padded / 8;
+        RFCHK(hipMalloc((void**)&g->d_text, want));
+        RFCHK(hipHostMalloc((void**)&g->pin, want, hipHostMallocDefault));
+        g->text_cap = want;
+    }
+    if (rows > g->chk_cap) {
+        if (g->d_chk) (void)hipFree(g->d_chk);
+        g->d_chk = nullptr; g->chk_cap = 0;
+        RFCHK(hipMalloc((void**)&g->d_chk, rows * sizeof(PgCheck)));
+        g->chk_cap = rows;
+    }
+    if (g->n_rec + rows > g->rec_cap) {
+        const uint64_t want = std::max<uint64_t>((g->n_rec + rows) * 3 / 2, 1 << 16);
+        PgRecord* r = nullptr;
+        RFCHK(hipMalloc((void**)&r, want * sizeof(PgRecord)));
+        if (g->n_rec) RFCHK(hipMemcpyAsync(r, g->d_rec, g->n_rec * sizeof(PgRecord), hipMemcpyDeviceToDevice, g->stream));
+        RFCHK(hipStreamSynchronize(g->stream));
+        if (g->d_rec) (void)hipFree(g->d_rec);
+        g->d_rec = r;
+        g->rec_cap = want;
+    }
+    if (int rc = pg_tab_reserve(g, g->cl, rows, n, 0)) return rc;
+    if (int rc = pg_tab_reserve(g, g->pv, rows, n, 1)) return rc;
+    {
+        const unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(8, n >> 22));
+        std::vector<std::thread> th;
+        const uint64_t step = (n + nt - 1) / nt;
+        for (unsigned t = 1; t < nt; t++) {
+            const uint64_t a = t * step, b = std::min<uint64_t>(n, a + step);
+            if (a < b) th.emplace_back([=] { memcpy(g->pin + a, text + a, (size_t)(b - a)); });
+        }
+        memcpy(g->pin, text, (size_t)std::min<uint64_t>(n, step));
+        for (auto& t : th) t.join();
+    }
+    memset(g->pin + n, 0, padded - n);
+    RFCHK(hipMemcpyAsync(g->d_text, g->pin, padded, hipMemcpyHostToDevice, g->stream));
+    unsigned long long ctr[4] = {g->n_rec, 0, 0, 0};
+    RFCHK(hipMemcpyAsync(g->d_ctr, ctr, 3 * 8, hipMemcpyHostToDevice, g->stream));   // records continue; checks, lines restart
+    PgScanParams p{};
+    p.text = g->d_text; p.n = n;
+    for (int q = 0; q < 6; q++) p.col[q] = g->col[q];
+    p.max_col = g->max_col;
+    p.strain_hash = g->d_strain_hash; p.strain_id = g->d_strain_id; p.strain_cap = g->strain_cap;
+    p.strain_bytes = g->d_strain_bytes; p.strain_str = g->d_strain_str;
+    p.clusters = pg_view(g->cl); p.pvalues = pg_view(g->pv);
+    p.zoom = g->zoom; p.start = g->start; p.stop = g->stop;
+    p.rec = g->d_rec; p.n_rec = g->d_ctr; p.chk = g->d_chk; p.n_chk = g->d_ctr + 1; p.n_lines = g->d_ctr + 2;
+    p.err = (unsigned int*)(g->d_ctr + 3);
+    RFCHK(hipEventRecord(g->e0, g->stream));
+    hipLaunchKernelGGL(pg_scan_kernel, dim3(pg_blocks((n + 15) / 16)), dim3(256), 0, g->stream, p);
+    RFCHK(hipGetLastError());
+    unsigned long long n_chk = 0;
+    RFCHK(hipMemcpyAsync(&n_chk, g->d_ctr + 1, 8, hipMemcpyDeviceToHost, g->stream));
+    RFCHK(hipStreamSynchronize(g->stream));
+    if (n_chk) {
+        hipLaunchKernelGGL(pg_check_kernel, dim3(pg_blocks(n_chk)), dim3(256), 0, g->stream, (const unsigned char*)g->d_text,
+                           (const PgCheck*)g->d_chk, (uint64_t)n_chk, pg_view(g->cl), pg_view(g->pv), (unsigned int*)(g->d_ctr + 3));
+        RFCHK(hipGetLastError());
+    }
+    RFCHK(hipEventRecord(g->e1, g->stream));
+    RFCHK(hipMemcpyAsync(ctr, g->d_ctr, 4 * 8, hipMemcpyDeviceToHost, g->stream));
+    unsigned long long tc[2][2];
+    RFCHK(hipMemcpyAsync(tc[0], g->cl.ctr, 16, hipMemcpyDeviceToHost, g->stream));
+    RFCHK(hipMemcpyAsync(tc[1], g->pv.ctr, 16, hipMemcpyDeviceToHost, g->stream));
+    RFCHK(hipStreamSynchronize(g->stream));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, g->e0, g->e1) == hipSuccess) g->device_ms += ms;
+    g->cl.used = tc[0][0]; g->cl.count = tc[0][1];
+    g->pv.used = tc[1][0]; g->pv.count = tc[1][1];
+    g->n_rec = ctr[0];
+    g->lines += ctr[2];
+    g->bytes_scanned += n;
+    const unsigned err = (unsigned)(ctr[3] & 0xFFFFFFFFu);
+    if (err & (PG_ERR_CLUSTER | PG_ERR_PVALUE))
+        return rf_fail(PF_ERR_CAPACITY, "pf_plotgrid_scan: two different cluster names or p-value texts share a 64-bit hash");
+    if (err & PG_ERR_LONG) return rf_fail(PF_ERR_ARG, "pf_plotgrid_scan: a cluster name or p-value field over 4095 bytes");
+    if (err & PG_ERR_RANGE) return rf_fail(PF_ERR_ARG, "pf_plotgrid_scan: a gene_start outside the 32-bit range");
+    return PF_OK;
+}
+
+int pf_plotgrid_finish(pf_plotgrid* g, uint32_t* n_clusters, uint64_t* n_pvalues, uint64_t* n_records) {
+    if (!g || !n_clusters || !n_pvalues || !n_records) return rf_fail(PF_ERR_ARG, "pf_plotgrid_finish: null argument");
+    RFCHK(hipSetDevice(g->device));
+    if (!g->finished) {
+        if (int rc = pg_tab_list(g, g->cl, g->cl_slot, g->cl_names, g->cl_off)) return rc;
+        if (int rc = pg_tab_list(g, g->pv, g->pv_slot, g->pv_texts, g->pv_off)) return rc;
+        const uint64_t cap = std::max<uint64_t>(g->cl.cap, 1);
+        int *mn = nullptr, *mx = nullptr;
+        unsigned long long* cnt = nullptr;
+        RFCHK(hipMalloc((void**)&mn, cap * 4));
+        RFCHK(hipMalloc((void**)&mx, cap * 4));
+        RFCHK(hipMalloc((void**)&cnt, cap * 8));
+        std::vector<int> init(cap, 0x7FFFFFFF);
+        RFCHK(hipMemcpy(mn, init.data(), cap * 4, hipMemcpyHostToDevice));
+        init.assign(cap, (int)0x80000000);
+        RFCHK(hipMemcpy(mx, init.data(), cap * 4, hipMemcpyHostToDevice));
+        RFCHK(hipMemset(cnt, 0, cap * 8));
+        if (g->n_rec) {
+            hipLaunchKernelGGL(pg_stats_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->stream, (const PgRecord*)g->d_rec,
+                               g->n_rec, mn, mx, cnt);
+            RFCHK(hipGetLastError());
+            RFCHK(hipStreamSynchronize(g->stream));
+        }
+        std::vector<int> hmn(cap), hmx(cap);
+        std::vector<unsigned long long> hc(cap);
+        RFCHK(hipMemcpy(hmn.data(), mn, cap * 4, hipMemcpyDeviceToHost));
+        RFCHK(hipMemcpy(hmx.data(), mx, cap * 4, hipMemcpyDeviceToHost));
+        RFCHK(hipMemcpy(hc.data(), cnt, cap * 8, hipMemcpyDeviceToHost));
+        (void)hipFree(mn); (void)hipFree(mx); (void)hipFree(cnt);
+        g->cl_min.clear(); g->cl_max.clear(); g->cl_rows.clear();
+        for (uint32_t s : g->cl_slot) {
+            g->cl_min.push_back(hmn[s]);
+            g->cl_max.push_back(hmx[s]);
+            g->cl_rows.push_back(hc[s]);
+        }
+        g->finished = 1;
+    }
+    *n_clusters = (uint32_t)g->cl_slot.size();
+    *n_pvalues = g->pv_slot.size();
+    *n_records = g->n_rec;
+    return PF_OK;
+}
+
+int pf_plotgrid_clusters(pf_plotgrid* g, const char** names, const uint64_t** name_off, const int32_t** min_pos,
+                         const int32_t** max_pos, const uint64_t** rows) {
+    if (!g || !names || !name_off || !min_pos || !max_pos || !rows) return rf_fail(PF_ERR_ARG, "pf_plotgrid_clusters: null argument");
+    if (!g->finished) return rf_fail(PF_ERR_STATE, "pf_plotgrid_clusters: before pf_plotgrid_finish");
+    *names = g->cl_names.data(); *name_off = g->cl_off.data();
+    *min_pos = g->cl_min.data(); *max_pos = g->cl_max.data(); *rows = g->cl_rows.data();
+    return PF_OK;
+}
+
+int pf_plotgrid_pvalues(pf_plotgrid* g, const char** texts, const uint64_t** text_off) {
+    if (!g || !texts || !text_off) return rf_fail(PF_ERR_ARG, "pf_plotgrid_pvalues: null argument");
+    if (!g->finished) return rf_fail(PF_ERR_STATE, "pf_plotgrid_pvalues: before pf_plotgrid_finish");
+    *texts = g->pv_texts.data(); *text_off = g->pv_off.data();
+    return PF_OK;
+}
+
+int pf_plotgrid_set_significance(pf_plotgrid* g, const uint64_t* keys) {
+    if (!g || (!keys && !g->pv_slot.empty())) return rf_fail(PF_ERR_ARG, "pf_plotgrid_set_significance: null argument");
+    if (!g->finished) return rf_fail(PF_ERR_STATE, "pf_plotgrid_set_significance: before pf_plotgrid_finish");
+    RFCHK(hipSetDevice(g->device));
+    const uint64_t cap = std::max<uint64_t>(g->pv.cap, 1);
+    std::vector<unsigned long long> by_slot(cap, 0);
+    for (size_t i = 0; i < g->pv_slot.size(); i++) by_slot[g->pv_slot[i]] = keys[i];
+    if (!g->d_sig) RFCHK(hipMalloc((void**)&g->d_sig, cap * 8));
+    RFCHK(hipMemcpy(g->d_sig, by_slot.data(), cap * 8, hipMemcpyHostToDevice));
+    g->sig_set = 1;
+    return PF_OK;
+}
+
+int pf_plotgrid_grids(pf_plotgrid* g, const uint32_t* ids, uint32_t n, uint64_t* key_out, uint64_t* cnt_out) {
+    if (!g || (n && (!ids || !key_out || !cnt_out))) return rf_fail(PF_ERR_ARG, "pf_plotgrid_grids: null argument");
+    if (!g->finished || !g->sig_set) return rf_fail(PF_ERR_STATE, "pf_plotgrid_grids: before pf_plotgrid_set_significance");
+    if (!n) return PF_OK;
+    RFCHK(hipSetDevice(g->device));
+    const uint64_t cap = std::max<uint64_t>(g->cl.cap, 1);
+    std::vector<int32_t> slot_item(cap, -1);
+    std::vector<uint64_t> item(3 * (size_t)n);
+    uint64_t cells = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (ids[i] >= g->cl_slot.size()) return rf_fail(PF_ERR_ARG, "pf_plotgrid_grids: no such cluster");
+        if (!g->cl_rows[ids[i]]) return rf_fail(PF_ERR_ARG, "pf_plotgrid_grids: a cluster without rows has no grid");
+        const uint32_t s = g->cl_slot[ids[i]];
+        if (slot_item[s] >= 0) return rf_fail(PF_ERR_ARG, "pf_plotgrid_grids: a cluster twice in one call");
+        slot_item[s] = (int32_t)i;
+        const uint64_t width = (uint64_t)((int64_t)g->cl_max[ids[i]] - g->cl_min[ids[i]] + 1);
+        item[i] = cells;
+        item[n + i] = (uint64_t)(int64_t)g->cl_min[ids[i]];
+        item[2 * (size_t)n + i] = width;
+        cells += width * g->n_strains;
+    }
+    if (cells > g->grid_cap) {
+        if (g->d_key) (void)hipFree(g->d_key);
+        if (g->d_cnt) (void)hipFree(g->d_cnt);
+        g->d_key = nullptr; g->d_cnt = nullptr; g->grid_cap = 0;
+        RFCHK(hipMalloc((void**)&g->d_key, cells * 8));
+        RFCHK(hipMalloc((void**)&g->d_cnt, cells * 8));
+        g->grid_cap = cells;
+    }
+    if (3 * (uint64_t)n > g->item_cap) {
+        if (g->d_item) (void)hipFree(g->d_item);
+        g->d_item = nullptr;
+        RFCHK(hipMalloc((void**)&g->d_item, 3 * (size_t)n * 8));
+        g->item_cap = 3 * (uint64_t)n;
+    }
+    if (!g->d_slot_item) RFCHK(hipMalloc((void**)&g->d_slot_item, cap * 4));
+    // the device-side item table: off (u64), min (i32), width (u32)
+    std::vector<int32_t> imin(n);
+    std::vector<uint32_t> iwidth(n);
+    for (uint32_t i = 0; i < n; i++) { imin[i] = (int32_t)(int64_t)item[n + i]; iwidth[i] = (uint32_t)item[2 * (size_t)n + i]; }
+    char* dit = (char*)g->d_item;
+    RFCHK(hipMemcpyAsync(dit, item.data(), (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    RFCHK(hipMemcpyAsync(dit + (size_t)n * 8, imin.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    RFCHK(hipMemcpyAsync(dit + (size_t)n * 12, iwidth.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    RFCHK(hipMemcpyAsync(g->d_slot_item, slot_item.data(), cap * 4, hipMemcpyHostToDevice, g->stream));
+    RFCHK(hipMemsetAsync(g->d_key, 0, cells * 8, g->stream));
+    RFCHK(hipMemsetAsync(g->d_cnt, 0, cells * 8, g->stream));
+    RFCHK(hipMemsetAsync(g->d_ctr + 3, 0, 8, g->stream));
+    PgGridParams p{};
+    p.rec = g->d_rec; p.n = g->n_rec; p.slot_item = g->d_slot_item;
+    p.item_off = (const uint64_t*)dit; p.item_min = (const int32_t*)(dit + (size_t)n * 8);
+    p.item_width = (const uint32_t*)(dit + (size_t)n * 12);
+    p.n_strains = g->n_strains; p.sig_key = g->d_sig; p.key = g->d_key; p.cnt = g->d_cnt;
+    p.err = (unsigned int*)(g->d_ctr + 3);
+    RFCHK(hipEventRecord(g->e0, g->stream));
+    hipLaunchKernelGGL(pg_grid_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->stream, p);
+    RFCHK(hipGetLastError());
+    RFCHK(hipEventRecord(g->e1, g->stream));
+    unsigned long long err = 0;
+    RFCHK(hipMemcpyAsync(key_out, g->d_key, cells * 8, hipMemcpyDeviceToHost, g->stream));
+    RFCHK(hipMemcpyAsync(cnt_out, g->d_cnt, cells * 8, hipMemcpyDeviceToHost, g->stream));
+    RFCHK(hipMemcpyAsync(&err, g->d_ctr + 3, 8, hipMemcpyDeviceToHost, g->stream));
+    RFCHK(hipStreamSynchronize(g->stream));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, g->e0, g->e1) == hipSuccess) g->device_ms += ms;
+    if (err) return rf_fail(PF_ERR_STATE, "pf_plotgrid_grids: a record outside its cluster's grid");
+    return PF_OK;
+}
+
+int pf_plotgrid_stats(pf_plotgrid* g, uint64_t* bytes_scanned, uint64_t* lines, uint64_t* records, float* device_ms) {
+    if (!g) return rf_fail(PF_ERR_ARG, "pf_plotgrid_stats: null argument");
+    if (bytes_scanned) *bytes_scanned = g->bytes_scanned;
+    if (lines) *lines = g->lines;
+    if (records) *records = g->n_rec;
+    if (device_ms) *device_ms = g->device_ms;
     return PF_OK;
 }
 

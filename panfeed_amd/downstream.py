@@ -73,28 +73,44 @@ class RowFilter:
         """(header line, matching data lines) of a TSV file (.gz read through gzip, as pandas does by the name).  The file
         is read block by block straight into one buffer; what follows a block's last complete line is moved to the front
         for the next block."""
-        block_bytes = block_bytes or BLOCK_BYTES
-        opener = gzip.open if str(path).endswith(".gz") else open
         out = []
-        with opener(path, "rb") as fh:
+
+        def scan(buf, n):
+            got, used = self.scan_block(buf, n)
+            out.append(got)
+            return used
+
+        with open_table(path) as fh:
             header = fh.readline()
-            buf = bytearray(block_bytes + (1 << 16))
-            have = 0                                         # bytes carried over, at the front of buf
-            while True:
-                if have + block_bytes > len(buf):            # a line longer than the slack
-                    buf.extend(bytes(have + block_bytes - len(buf)))
-                got_n = fh.readinto(memoryview(buf)[have:have + block_bytes])
-                if not got_n:
-                    break
-                total = have + got_n
-                got, used = self.scan_block(buf, total)
-                out.append(got)
-                have = total - used
-                buf[:have] = buf[used:total]
-            if have:                                         # a last line without its newline
-                got, _ = self.scan_block(bytes(buf[:have]) + b"\n")
-                out.append(got)
+            scan_lines(fh, scan, block_bytes)
         return header, b"".join(out)
+
+
+def open_table(path):
+    """a TSV file for reading bytes (.gz through gzip, as pandas does by the name)"""
+    return (gzip.open if str(path).endswith(".gz") else open)(path, "rb")
+
+
+def scan_lines(fh, scan, block_bytes=None):
+    """Feed the rest of `fh` to `scan(buf, n)` block by block, read straight into one buffer; scan looks at the complete
+    lines of buf[:n] and returns the bytes it consumed.  What follows a block's last complete line is moved to the front
+    for the next block; a last line without its newline is given one."""
+    block_bytes = block_bytes or BLOCK_BYTES
+    buf = bytearray(block_bytes + (1 << 16))
+    have = 0                                         # bytes carried over, at the front of buf
+    while True:
+        if have + block_bytes > len(buf):            # a line longer than the slack
+            buf.extend(bytes(have + block_bytes - len(buf)))
+        got_n = fh.readinto(memoryview(buf)[have:have + block_bytes])
+        if not got_n:
+            break
+        total = have + got_n
+        used = scan(buf, total)
+        have = total - used
+        buf[:have] = buf[used:total]
+    if have:                                         # a last line without its newline
+        tail = bytearray(buf[:have]) + b"\n"
+        scan(tail, len(tail))
 
 
 def _table(header, rows):
