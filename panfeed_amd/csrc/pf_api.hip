@@ -12,6 +12,7 @@
 #include "pf_kernels.h"
 #include "../../include/panfeed_hip.h"
 #include "pf_ingest.h"
+#include "pf_buf.h"
 
 #include <sys/stat.h>
 #include <condition_variable>
@@ -19,9 +20,9 @@
 #include <algorithm>
 #include <cmath>
 #include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <numeric>
 #include <thread>
 #include <string>
@@ -31,75 +32,6 @@
 namespace {
 
 thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIPCHK(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return fail(e_ == hipErrorOutOfMemory ? PF_ERR_OOM : PF_ERR_HIP, "%s failed: %s (%s:%d)", \
-                        #expr, hipGetErrorString(e_), __FILE__, __LINE__);                             \
-    } while (0)
-#define PFCHK(expr)             \
-    do {                        \
-        int r_ = (expr);        \
-        if (r_ != PF_OK) return r_; \
-    } while (0)
-
-// test hook (pf_debug_limit_alloc): single device allocations above the limit are refused as if the device were out of
-// memory; the largest request and the exact-size retries that succeeded are counted
-std::atomic<uint64_t> g_alloc_limit{0}, g_alloc_max_request{0}, g_alloc_exact_retries{0};
-
-hipError_t dev_malloc(void** p, size_t bytes) {
-    const uint64_t lim = g_alloc_limit.load(std::memory_order_relaxed);
-    if (lim && bytes > lim) { *p = nullptr; return hipErrorOutOfMemory; }
-    return hipMalloc(p, bytes);
-}
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    bool view = false;     // points into another DevBuf (staged uploads): never freed, never grown
-    int ensure(size_t bytes, bool exact = false) {
-        if (view) { p = nullptr; cap = 0; view = false; }
-        if (bytes <= cap) return PF_OK;
-        const bool regrow = p != nullptr;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        uint64_t seen = g_alloc_max_request.load(std::memory_order_relaxed);
-        while (bytes > seen && !g_alloc_max_request.compare_exchange_weak(seen, bytes)) {}
-        // (a buffer that has to be re-made gets a quarter of slack: hipFree + hipMalloc of a multi-gigabyte buffer was seen to
-        // take 0.25 s in the middle of a submit when a batch's key-partition queues came out a little larger than the batch
-        // before's; a first allocation -- the scratch slices are 123 GB in bench.py -- gets a sixteenth).  The slack is a
-        // convenience, never a requirement: when it does not fit, the exact size is asked for before giving up.
-        // (exact: a buffer whose size a caller's memory budget bounds gets none)
-        size_t want = exact ? bytes : bytes + (regrow ? bytes / 4 : bytes / 16) + 256;
-        hipError_t e = dev_malloc(&p, want);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            want = bytes;
-            e = dev_malloc(&p, want);
-            if (e == hipSuccess) g_alloc_exact_retries.fetch_add(1, std::memory_order_relaxed);
-        }
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            return fail(PF_ERR_OOM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-        }
-        cap = want;
-        return PF_OK;
-    }
-    void release() { if (p && !view) (void)hipFree(p); p = nullptr; cap = 0; view = false; }
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 struct Item {
     uint32_t cluster, part, nparts, nslots, slice, sib0, nsib, extra_first, is_extra;
@@ -151,18 +83,17 @@ struct pf_ctx {
     DevBuf v_bits, view_off;
     // unit view (unit_class_kernel): one pool of view entries per part of a batch's first pass, and the list
     // {clusters, their places in the pool} that goes up with it
-    struct UPool { DevBuf word_off, len, sample, ord, bits, list; uint32_t* pin = nullptr; size_t pin_cap = 0; };
+    struct UPool { DevBuf word_off, len, sample, ord, bits, list; PinBuf pin; };
     DevBuf pat_b64, txt_dev, txt_meta;   // device-side rendering: base64 of every digest, the text, its per-row tables
     uint32_t b64_done = 0;               // patterns whose base64 is in pat_b64
-    char* txt_pins[2] = {nullptr, nullptr};   // pinned host copies of the rendered text, used alternately so that a
-    size_t txt_pin_caps[2] = {0, 0};          // writer thread may still be on the previous batch's
+    PinBuf txt_pins[2];                  // pinned host copies of the rendered text, used alternately so that a writer thread
+                                         // may still be on the previous batch's
     int txt_slot = 0;
     // kmers.tsv written on the device (pf_render_kmers_tsv_device): descriptors, tiles, the text; pinned blocks for its way out
     DevBuf kt_seqs, kt_tiles, kt_prefix, kt_tbytes, kt_toff, kt_text;
     uint64_t kt_bytes = 0;
     uint32_t kt_host_seqs = 0;
-    char* kt_pins[2] = {nullptr, nullptr};
-    size_t kt_pin_caps[2] = {0, 0};
+    PinBuf kt_pins[2];
     bool kt_pref_valid = false;
     uint64_t kt_pref_off = 0, kt_pref_n = 0;
     int kt_pref_slot = 0;
@@ -200,7 +131,7 @@ struct pf_ctx {
     std::vector<uint32_t> hs_binned, hs_bin[4];
     DevBuf it_cluster, it_part, it_nparts, it_nslots, it_slice, it_sib0, it_nsib, it_extra_first, it_count,
         it_unique, it_kept, work_scan, work_extra, work_fin, work_fin2, work_fin3, work_fin5, work_rows, sub_cluster, sub_item0, sub_nitems;
-    std::vector<Arena*> arenas;
+    std::vector<std::unique_ptr<Arena>> arenas;
     uint32_t n_passes = 0;                 // arenas the last pf_submit used (arenas[] itself only ever grows)
     DevBuf rp_order, rp_rlen, rp_rowoff;   // pf_render_pattern_rows: the id list, row lengths, row offsets
     uint32_t n_grown = 0;                  // times the pattern table / pool were enlarged
@@ -212,21 +143,19 @@ struct pf_ctx {
     // the small per-pass arrays: one device block + its pinned host mirror, two of each because the two halves of a
     // batch's first pass are in flight together (stage_slot picks the pair)
     DevBuf stage_devs[2];
-    void* stage_pins[2] = {nullptr, nullptr};
-    size_t stage_pin_caps[2] = {0, 0};
+    PinBuf stage_pins[2];
     int stage_slot = 0;
-    void* pin_dedup = nullptr;     // pinned host copies of the per-cluster arrays the dedup kernel leaves
-    size_t pin_dedup_cap = 0;
-    uint64_t* pin_small = nullptr; // pinned scratch: cursor values going up [0..15], cursor read-backs of deferred passes [16..47],
-                                   // the last pass's cursor triple [48..50] and pattern counters [52..53]
-    uint32_t* pin_ovf = nullptr;   // pinned: the per-cluster overflow words of the last pass (a pageable destination makes
-    size_t pin_ovf_cap = 0;        // hipMemcpyAsync a staged, blocking copy)
+    PinBuf pin_dedup;              // pinned host copies of the per-cluster arrays the dedup kernel leaves
+    PinBuf pin_small;              // pinned scratch (uint64): cursor values going up [0..15], cursor read-backs of deferred
+                                   // passes [16..47], the last pass's cursor triple [48..50] and pattern counters [52..53]
+    PinBuf pin_ovf;                // pinned: the per-cluster overflow words of the last pass (a pageable destination makes
+                                   // hipMemcpyAsync a staged, blocking copy)
     static constexpr int MAX_PARTS = 8;
     UPool upool[2 * MAX_PARTS];            // [2 h]: the device-planned clusters of part h, [2 h + 1]: the host-planned rest
     hipEvent_t ev_part[MAX_PARTS] = {};    // a part's dedup results have arrived in pinned memory
     // plan_kernel's output per part: item arrays, work lists, unit-view list (one device block), its 40-byte summary in
     // pinned memory; and the constant item arrays (zeros | ones | 0, 1, 2, ...) every device-planned pass shares
-    struct DPlan { DevBuf block, it_count, out; pf::PlanOut* pin_out = nullptr; uint32_t n = 0; };
+    struct DPlan { DevBuf block, it_count, out; PinBuf pin_out; uint32_t n = 0; };
     DPlan dplan[MAX_PARTS];
     DevBuf dp_const, plan_room, plan_arena;
     uint32_t dp_const_n = 0;
@@ -329,28 +258,20 @@ int staged_upload(pf_ctx* c, std::vector<std::pair<DevBuf*, const std::vector<ui
     }
     for (auto& a : arrs) if (!a.first->view) a.first->release();
     DevBuf& stage_dev = c->stage_devs[c->stage_slot];
-    void*& stage_pin = c->stage_pins[c->stage_slot];
-    size_t& stage_pin_cap = c->stage_pin_caps[c->stage_slot];
+    PinBuf& stage_pin = c->stage_pins[c->stage_slot];
     // several passes are queued without a host sync in between: the copy that last used this slot (two passes ago) has
     // to have left the pinned block before it is written again
     HIPCHK(hipEventSynchronize(c->ev_stage[c->stage_slot]));
     PFCHK(stage_dev.ensure(total));
-    if (total > stage_pin_cap) {
-        if (stage_pin) (void)hipHostFree(stage_pin);
-        stage_pin = nullptr; stage_pin_cap = 0;
-        const size_t want = total + total / 4;
-        hipError_t e = hipHostMalloc(&stage_pin, want, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(PF_ERR_OOM, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-        stage_pin_cap = want;
-    }
+    PFCHK(stage_pin.ensure(total));
     for (size_t i = 0; i < arrs.size(); i++) {
         const auto& v = *arrs[i].second;
-        if (!v.empty()) memcpy((char*)stage_pin + off[i], v.data(), v.size() * 4);
+        if (!v.empty()) memcpy(stage_pin.as<char>() + off[i], v.data(), v.size() * 4);
         arrs[i].first->p = (char*)stage_dev.p + off[i];
         arrs[i].first->cap = 0;
         arrs[i].first->view = true;
     }
-    HIPCHK(hipMemcpyAsync(stage_dev.p, stage_pin, total, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(stage_dev.p, stage_pin.p, total, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->ev_stage[c->stage_slot], c->stream));
     return PF_OK;
 }
@@ -360,7 +281,6 @@ struct PatternBufs {
     DevBuf lo, val, first, bits, nan, n, md5, b64;
     uint64_t cap = 0;
     uint32_t pool = 0;
-    void release() { lo.release(); val.release(); first.release(); bits.release(); nan.release(); n.release(); md5.release(); b64.release(); }
 };
 int alloc_pattern_bufs(pf_ctx* c, uint64_t slots, bool with_b64, PatternBufs& pb) {
     if (c->pt_slot_limit && slots > c->pt_slot_limit)
@@ -379,7 +299,7 @@ int alloc_pattern_bufs(pf_ctx* c, uint64_t slots, bool with_b64, PatternBufs& pb
     if (with_b64) PFCHK(pb.b64.ensure(pool * 24));
     return PF_OK;
 }
-// the context takes the buffers over (its old ones, if any, are the caller's to release: they are moved into `pb`)
+// the context takes the buffers over (its old ones, if any, are moved into `pb`, which frees them)
 void adopt_pattern_bufs(pf_ctx* c, PatternBufs& pb) {
     std::swap(c->pt_lo, pb.lo); std::swap(c->pt_val, pb.val); std::swap(c->pt_first, pb.first);
     std::swap(c->pat_bits, pb.bits); std::swap(c->pat_nan, pb.nan); std::swap(c->pat_n, pb.n);
@@ -391,12 +311,10 @@ void adopt_pattern_bufs(pf_ctx* c, PatternBufs& pb) {
 }
 int alloc_patterns(pf_ctx* c, uint64_t slots) {
     PatternBufs pb;
-    int rc = alloc_pattern_bufs(c, slots, false, pb);
-    if (rc == PF_OK) rc = c->pt_counters.ensure(16);
-    if (rc != PF_OK) { pb.release(); return rc; }
+    PFCHK(alloc_pattern_bufs(c, slots, false, pb));
+    PFCHK(c->pt_counters.ensure(16));
     adopt_pattern_bufs(c, pb);
     c->pt.counters = c->pt_counters.as<uint32_t>();
-    pb.release();
     return PF_OK;
 }
 
@@ -436,15 +354,13 @@ int grow_patterns(pf_ctx* c, uint64_t min_pool) {
     }
     if (rc == PF_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(PF_ERR_HIP, "growing the pattern table failed");
     if (rc != PF_OK) {
-        (void)hipStreamSynchronize(c->stream);       // nothing queued above may still touch the buffers released here
-        nb.release();
+        (void)hipStreamSynchronize(c->stream);       // nothing queued above may still touch nb's buffers when they go
         // the failed batch's additions are still in the old table: forget them, as the successful path does
         const uint32_t cnt[4] = {keep, 0, 0, 0};
         (void)hipMemcpy(c->pt_counters.p, cnt, 16, hipMemcpyHostToDevice);
         return rc;
     }
     adopt_pattern_bufs(c, nb);                       // nb now holds the old buffers
-    nb.release();
     const uint32_t cnt[4] = {keep, 0, 0, 0};
     HIPCHK(hipMemcpy(c->pt_counters.p, cnt, 16, hipMemcpyHostToDevice));
     c->b64_done = std::min(c->b64_done, keep);
@@ -597,54 +513,17 @@ void pf_destroy(pf_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    DevBuf* bufs[] = {&c->d_maf_lo, &c->d_maf_hi, &c->pt_lo, &c->pt_val, &c->pt_first, &c->pt_counters, &c->pat_bits,
-                      &c->pat_nan, &c->pat_n, &c->pat_md5, &c->tab_key, &c->tab_ord, &c->chunkbits, &c->chunkmask,
-                      &c->slot_hash, &c->sorted_pair, &c->kept_prefix, &c->b_packed, &c->b_seg_word_off, &c->b_seg_len,
-                      &c->b_seg_sample, &c->b_seg_ord, &c->b_cl_seg_off, &c->b_cl_nstr, &c->b_cl_npres, &c->b_cl_presab,
-                      &c->b_cl_ordinal, &c->b_extra_ord, &c->b_extra_bits, &c->b_seg_strand_off, &c->cl_rec, &c->v_word_off, &c->v_len, &c->v_sample, &c->v_ord,
-                      &c->seg_distinct, &c->v_nseg, &c->v_nstr, &c->v_mode, &c->v_dense, &c->extra_off, &c->extra_dense,
-                      &c->bm4, &c->bm2, &c->mrows, &c->slot_out, &c->it_is_extra,
-                      &c->cmask_lo, &c->cmask_hi, &c->it_compact, &c->cl_overflow, &c->cl_kmer_off, &c->cl_kmer_cnt, &c->cl_unique, &c->cl_pattern,
-                      &c->cl_first, &c->cursor, &c->strand_bits, &c->it_cluster, &c->it_part, &c->it_nparts,
-                      &c->it_nslots, &c->it_slice, &c->it_sib0, &c->it_nsib, &c->it_extra_first, &c->it_count,
-                      &c->it_unique, &c->it_kept, &c->work_scan, &c->work_extra, &c->work_fin, &c->work_fin2, &c->work_fin3, &c->work_fin5, &c->work_rows, &c->sub_cluster, &c->sub_item0,
-                      &c->sub_nitems, &c->it_binned, &c->bin_lists, &c->q_key, &c->q_ord, &c->q_bit, &c->q_off};
-    for (DevBuf* b : bufs) b->release();
-    for (Arena* a : c->arenas) { a->key.release(); a->pid.release(); a->first.release(); delete a; }
+    kt_stream_end(c);                     // (before its pinned blocks go)
     for (auto& e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    for (int i = 0; i < 2; i++) { if (c->stage_pins[i]) (void)hipHostFree(c->stage_pins[i]); c->stage_devs[i].release(); if (c->ev_stage[i]) (void)hipEventDestroy(c->ev_stage[i]); }
+    for (auto e : c->ev_stage) if (e) (void)hipEventDestroy(e);
     for (auto e : c->ev_part) if (e) (void)hipEventDestroy(e);
-
-    for (auto& d : c->dplan) { d.block.release(); d.it_count.release(); d.out.release(); if (d.pin_out) (void)hipHostFree(d.pin_out); }
-    c->dp_const.release(); c->plan_room.release(); c->plan_arena.release();
-    for (auto& u : c->upool) {
-        u.word_off.release(); u.len.release(); u.sample.release(); u.ord.release(); u.bits.release(); u.list.release();
-        if (u.pin) (void)hipHostFree(u.pin);
-    }
-    c->v_bits.release(); c->view_off.release();
-    if (c->pin_dedup) (void)hipHostFree(c->pin_dedup);
-    if (c->pin_small) (void)hipHostFree(c->pin_small);
-    if (c->pin_ovf) (void)hipHostFree(c->pin_ovf);
-    c->scan_desc.release(); c->pat_b64.release(); c->txt_dev.release(); c->txt_meta.release();
-    c->rp_order.release(); c->rp_rlen.release(); c->rp_rowoff.release(); c->wide_list.release();
-    for (int i = 0; i < 2; i++) if (c->txt_pins[i]) (void)hipHostFree(c->txt_pins[i]); c->md5_list.release();
-    kt_stream_end(c);                     // (before its pinned blocks go)
-    for (int i = 0; i < 2; i++) if (c->kt_pins[i]) (void)hipHostFree(c->kt_pins[i]);
-    for (int i = 0; i < 2; i++) {
-        if (c->kts.ev_prod[i]) (void)hipEventDestroy(c->kts.ev_prod[i]);
-        if (c->kts.ev_copied[i]) (void)hipEventDestroy(c->kts.ev_copied[i]);
-    }
-    for (DevBuf* b : {&c->kt_seqs, &c->kt_tiles, &c->kt_prefix, &c->kt_tbytes, &c->kt_toff, &c->kt_text, &c->kt_text2}) b->release();
-    c->g_store.release(); c->b_literal.release(); c->g_src_off.release(); c->g_src_start.release(); c->g_src_flags.release();
-    c->mg_lo.release(); c->mg_cnt.release();
-    if (c->ev_t0) (void)hipEventDestroy(c->ev_t0);
-    if (c->ev_t1) (void)hipEventDestroy(c->ev_t1);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+    for (auto e : {c->kts.ev_prod[0], c->kts.ev_prod[1], c->kts.ev_copied[0], c->kts.ev_copied[1], c->ev_t0, c->ev_t1,
+                   c->ev_fork, c->ev_join})
+        if (e) (void)hipEventDestroy(e);
     if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                             // (the buffers go with it)
 }
 
 int pf_create(pf_ctx** out, int device, const pf_opts* o) {
@@ -695,7 +574,7 @@ int pf_create(pf_ctx** out, int device, const pf_opts* o) {
         for (auto& ev : c->ev_part) ev_ok = ev_ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
         for (auto& ev : c->ev_stage) ev_ok = ev_ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
         if (!ev_ok ||
-            hipHostMalloc((void**)&c->pin_small, 512, hipHostMallocDefault) != hipSuccess ||
+            c->pin_small.ensure(512, true) != PF_OK ||
             hipEventCreate(&c->ev_t0) != hipSuccess || hipEventCreate(&c->ev_t1) != hipSuccess) {
             rc = fail(PF_ERR_HIP, "hipEventCreate failed"); break;
         }
@@ -944,20 +823,11 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
     // host builds and launches the first half's work items while the GPU is still on the second half's dedup, and the
     // second half's while the first half's scan runs -- otherwise the GPU idles for the ~1.2 ms that takes.
     const size_t C8 = ((size_t)C + 1) & ~(size_t)1;
-    {
-        const size_t need = C8 * sizeof(pf::ClusterRec) + 64 + ((size_t)C + 2) * 4;
-        if (need > c->pin_dedup_cap) {
-            if (c->pin_dedup) (void)hipHostFree(c->pin_dedup);
-            c->pin_dedup = nullptr; c->pin_dedup_cap = 0;
-            hipError_t e = hipHostMalloc(&c->pin_dedup, need + need / 4, hipHostMallocDefault);
-            if (e != hipSuccess) return fail(PF_ERR_OOM, "hipHostMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-            c->pin_dedup_cap = need + need / 4;
-        }
-    }
+    PFCHK(c->pin_dedup.ensure(C8 * sizeof(pf::ClusterRec) + 64 + ((size_t)C + 2) * 4));
     // what the host needs of the dedup pass per cluster, one 40-byte record each (pf::ClusterRec, written by
     // cluster_ninst_kernel): ONE copy per part brings them over -- six small copies in a row were 40 us of the part's
     // critical path
-    pf::ClusterRec* rec = reinterpret_cast<pf::ClusterRec*>(c->pin_dedup);
+    pf::ClusterRec* rec = c->pin_dedup.as<pf::ClusterRec>();
     uint32_t* h_exfirst = reinterpret_cast<uint32_t*>(rec + C8);   // [C + 1] + the "bad list" flag (device-side CSR only)
     if (ex_on_device) {
         PFCHK(c->extra_off.ensure(((size_t)C + 2) * 4));
@@ -1023,10 +893,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         PFCHK(dp.block.ensure(((size_t)dp.n * 8 + (size_t)nblk * pf::PLAN_BLK_WORDS) * 4));
         PFCHK(dp.it_count.ensure((size_t)dp.n * 4));
         PFCHK(dp.out.ensure(sizeof(pf::PlanOut)));
-        if (!dp.pin_out) {
-            hipError_t e = hipHostMalloc((void**)&dp.pin_out, 64, hipHostMallocDefault);
-            if (e != hipSuccess) return fail(PF_ERR_OOM, "hipHostMalloc(64) failed: %s", hipGetErrorString(e));
-        }
+        PFCHK(dp.pin_out.ensure(64, true));
         const DPtrs q = dplan_ptrs(dp);
         pf::PlanParams pp{};
         pp.rec = c->cl_rec.as<pf::ClusterRec>(); pp.plan_room = c->plan_room.as<uint32_t>(); pp.plan_arena = c->plan_arena.as<uint32_t>();
@@ -1039,7 +906,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         hipLaunchKernelGGL(pf::plan_scan_kernel, dim3(1), dim3(256), 0, c->stream, pp, nblk);
         hipLaunchKernelGGL(pf::plan_scatter_kernel, dim3(nblk), dim3(pf::PLAN_THREADS), 0, c->stream, pp);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(dp.pin_out, dp.out.p, sizeof(pf::PlanOut), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(dp.pin_out.p, dp.out.p, sizeof(pf::PlanOut), hipMemcpyDeviceToHost, c->stream));
         return PF_OK;
     };
     if (use_plan && C > c->dp_const_n) {
@@ -1181,24 +1048,18 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         if (!(c->o.flags & PF_FLAG_NO_UNIT_DEDUP)) {
             pf_ctx::UPool& up = c->upool[2 * h + 1];
             const size_t need_pin = (size_t)(c1 - c0) * 8 + 64;
-            if (need_pin > up.pin_cap) {
-                if (up.pin) (void)hipHostFree(up.pin);
-                up.pin = nullptr; up.pin_cap = 0;
-                hipError_t e = hipHostMalloc((void**)&up.pin, need_pin + need_pin / 4, hipHostMallocDefault);
-                if (e != hipSuccess) return fail(PF_ERR_OOM, "hipHostMalloc(%zu) failed: %s", need_pin, hipGetErrorString(e));
-                up.pin_cap = need_pin + need_pin / 4;
-            }
+            PFCHK(up.pin.ensure(need_pin));
             // clusters of up to 64 distinct sequences first (one wave each, no table), then the wider ones
             uint32_t nu = 0, nsmall = 0;
             uint64_t room = 0;
-            uint32_t* lc = up.pin;
+            uint32_t* lc = up.pin.as<uint32_t>();
             auto takes = [&](uint32_t i) { return !(rec[i].pad & pf::PLAN_PLANNED) && rec[i].mode && rec[i].vnstr >= 2 && rec[i].words && room + rec[i].words / 2 < 0x7FFFFFF0ull; };
             for (uint32_t i = c0; i < c1; i++)
                 if (rec[i].vnstr <= pf::UNIT_SMALL_MAX_D && takes(i)) { lc[nu++] = i; room += rec[i].words / 2; }
             nsmall = nu;
             for (uint32_t i = c0; i < c1; i++)
                 if (rec[i].vnstr > pf::UNIT_SMALL_MAX_D && takes(i)) { lc[nu++] = i; room += rec[i].words / 2; }
-            uint32_t* lb = up.pin + nu;
+            uint32_t* lb = lc + nu;
             room = 0;
             for (uint32_t j = 0; j < nu; j++) { lb[j] = (uint32_t)room; room += rec[lc[j]].words / 2; }
             if (nu) {
@@ -1207,7 +1068,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
                 if (R2 > 0xFFFFFFF0ull) return fail(PF_ERR_CAPACITY, "unit view of %zu pieces: submit fewer clusters at a time", R);
                 PFCHK(up.word_off.ensure(R2 * 8)); PFCHK(up.len.ensure(R2 * 4)); PFCHK(up.sample.ensure(R2 * 4));
                 PFCHK(up.ord.ensure(R2 * 4)); PFCHK(up.bits.ensure(R2 * 4)); PFCHK(up.list.ensure((size_t)nu * 8));
-                HIPCHK(hipMemcpyAsync(up.list.p, up.pin, (size_t)nu * 8, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(hipMemcpyAsync(up.list.p, up.pin.p, (size_t)nu * 8, hipMemcpyHostToDevice, c->stream));
                 pf::UnitParams q{};
                 q.packed = d.packed; q.cluster_seg_off = d.cluster_seg_off; q.v_nstr = c->v_nstr.as<uint32_t>();
                 q.list_cluster = up.list.as<uint32_t>(); q.list_base = up.list.as<uint32_t>() + nu;
@@ -1299,7 +1160,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
     // ---- the device-planned clusters of part h: unit view, scan, fused finish -- launched from plan_kernel's 40-byte summary
     auto launch_planned = [&](uint32_t h) -> int {
         pf_ctx::DPlan& dp = c->dplan[h];
-        const pf::PlanOut po = *dp.pin_out;
+        const pf::PlanOut po = *dp.pin_out.as<pf::PlanOut>();
         const uint32_t n = po.n_items;
         if (!n) return PF_OK;
         if (n > c->max_items || n > dp.n || po.n_fin + po.n_fin2 + po.n_fin5 != n || po.n_unit > n)
@@ -1309,15 +1170,15 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         const uint32_t* ones = zeros + c->dp_const_n;
         const uint32_t* iota = zeros + 2 * (size_t)c->dp_const_n;
         const ItemPtrs ip{q.it_cluster, zeros, ones, q.it_nslots, iota, ones, zeros, dp.it_count.as<uint32_t>()};
-        while (c->arenas.size() <= arena_i) c->arenas.push_back(new Arena());
-        Arena* ar = c->arenas[arena_i];
+        while (c->arenas.size() <= arena_i) c->arenas.push_back(std::make_unique<Arena>());
+        Arena* ar = c->arenas[arena_i].get();
         ar->cap = std::max<uint64_t>(po.arena_cap, 1);
         ar->base = arena_base;
         PFCHK(ar->key.ensure((size_t)ar->cap * 8 * KW));
         PFCHK(ar->pid.ensure((size_t)ar->cap * 4));
         PFCHK(ar->first.ensure((size_t)ar->cap * 8));
-        c->pin_small[arena_i & 15] = arena_base;
-        HIPCHK(hipMemcpyAsync(c->cursor.p, &c->pin_small[arena_i & 15], 8, hipMemcpyHostToDevice, c->stream));
+        c->pin_small.as<uint64_t>()[arena_i & 15] = arena_base;
+        HIPCHK(hipMemcpyAsync(c->cursor.p, c->pin_small.as<uint64_t>() + (arena_i & 15), 8, hipMemcpyHostToDevice, c->stream));
         pf_ctx::UPool& up = c->upool[2 * h];
         if (po.n_unit) {
             const size_t R = (size_t)po.unit_room + 1, R2 = 2 * R;
@@ -1373,7 +1234,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         c->timing.n_items += n;
         c->timing.n_device_planned += n;
         const uint32_t pin = 16 + (arena_i & 31);
-        HIPCHK(hipMemcpyAsync(&c->pin_small[pin], c->cursor.p, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->pin_small.as<uint64_t>() + pin, c->cursor.p, 8, hipMemcpyDeviceToHost, c->stream));
         deferred.push_back(Deferred{ar, pin});
         arena_base += ar->cap;
         arena_i++;
@@ -1507,8 +1368,8 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
 
         lap("  items");
         // ---- arena of this pass
-        while (c->arenas.size() <= arena_i) c->arenas.push_back(new Arena());
-        Arena* ar = c->arenas[arena_i];
+        while (c->arenas.size() <= arena_i) c->arenas.push_back(std::make_unique<Arena>());
+        Arena* ar = c->arenas[arena_i].get();
         ar->cap = std::max<uint64_t>(arena_cap, 1);
         ar->base = arena_base;
         PFCHK(ar->key.ensure((size_t)ar->cap * 8 * KW));
@@ -1601,8 +1462,8 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         }
         // the cursor's next free index restarts at this arena's base
         {
-            c->pin_small[arena_i & 15] = arena_base;
-            HIPCHK(hipMemcpyAsync(c->cursor.p, &c->pin_small[arena_i & 15], 8, hipMemcpyHostToDevice, c->stream));
+            c->pin_small.as<uint64_t>()[arena_i & 15] = arena_base;
+            HIPCHK(hipMemcpyAsync(c->cursor.p, c->pin_small.as<uint64_t>() + (arena_i & 15), 8, hipMemcpyHostToDevice, c->stream));
         }
 
         lap("upload items");
@@ -1788,7 +1649,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         if (pass + 1 < P) {
             // no wait: the next part's pass is built now and goes in behind this one
             const uint32_t pin = 16 + (arena_i & 31);
-            HIPCHK(hipMemcpyAsync(&c->pin_small[pin], c->cursor.p, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(c->pin_small.as<uint64_t>() + pin, c->cursor.p, 8, hipMemcpyDeviceToHost, c->stream));
             deferred.push_back(Deferred{ar, pin});
             arena_base += ar->cap;
             arena_i++;
@@ -1796,17 +1657,10 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
             continue;
         }
         // ---- who overflowed?
-        if ((size_t)C * 4 + 64 > c->pin_ovf_cap) {
-            if (c->pin_ovf) (void)hipHostFree(c->pin_ovf);
-            c->pin_ovf = nullptr; c->pin_ovf_cap = 0;
-            const size_t want = ((size_t)C * 4 + 64) * 5 / 4;
-            hipError_t e = hipHostMalloc((void**)&c->pin_ovf, want, hipHostMallocDefault);
-            if (e != hipSuccess) return fail(PF_ERR_OOM, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-            c->pin_ovf_cap = want;
-        }
-        uint32_t* const ovf = c->pin_ovf;
-        uint64_t* const cur3 = &c->pin_small[48];
-        uint32_t* const cnt_pin = reinterpret_cast<uint32_t*>(&c->pin_small[52]);
+        PFCHK(c->pin_ovf.ensure((size_t)C * 4 + 64));
+        uint32_t* const ovf = c->pin_ovf.as<uint32_t>();
+        uint64_t* const cur3 = c->pin_small.as<uint64_t>() + 48;
+        uint32_t* const cnt_pin = reinterpret_cast<uint32_t*>(c->pin_small.as<uint64_t>() + 52);
         // clusters of this pass the key-partition estimate can learn from: their items' key counts come along
         bool learn = false;
         // (8 192 clusters settle the line; after that every 16th submit still looks, at half the old weight, so that a
@@ -1815,7 +1669,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         uint32_t learn_planned = 0;            // ... and plan_kernel's items of the last part (their clusters, their key counts)
         if (!rerun && (c->reg_n < 8192 || (c->n_submits & 15) == 0)) {
             for (uint32_t ci : todo) if (rec[ci].mode && rec[ci].vnstr >= 2) { learn = true; break; }
-            if (use_plan && pass + 1 == P) learn_planned = std::min<uint32_t>(c->dplan[pass].pin_out->n_items, 4096u);
+            if (use_plan && pass + 1 == P) learn_planned = std::min<uint32_t>(c->dplan[pass].pin_out.as<pf::PlanOut>()->n_items, 4096u);
         }
         if (learn) {
             c->hs_count.resize(NI);
@@ -1841,7 +1695,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         arena_i++;
         if (!deferred.empty()) {                   // the earlier passes finished before this one
             for (const Deferred& df : deferred) {
-                df.ar->used = c->pin_small[df.pin] - df.ar->base;
+                df.ar->used = c->pin_small.as<uint64_t>()[df.pin] - df.ar->base;
                 if (df.ar->used > df.ar->cap)
                     return fail(PF_ERR_CAPACITY, "output arena overflow (%llu > %llu)", (unsigned long long)df.ar->used,
                                 (unsigned long long)df.ar->cap);
@@ -2078,7 +1932,7 @@ int pf_fetch(pf_ctx* c, pf_result* res) {
     c->h_kmer_key.resize((size_t)total * KW);
     c->h_kmer_pid.resize((size_t)total);
     for (size_t a = 0; a < c->arenas.size(); a++) {
-        Arena* ar = c->arenas[a];
+        const Arena* ar = c->arenas[a].get();
         if (!ar->used) continue;
         HIPCHK(hipMemcpy(c->h_kmer_key.data() + host_base[a] * KW, ar->key.p, (size_t)ar->used * 8 * KW, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(c->h_kmer_pid.data() + host_base[a], ar->pid.p, (size_t)ar->used * 4, hipMemcpyDeviceToHost));
@@ -2557,16 +2411,6 @@ int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n,
 namespace {
 constexpr uint64_t KT_BLOCK = 64ull << 20;    // bytes per block a stream hands out (DeviceText.chunks' default too)
 
-int kt_ensure_pin(pf_ctx* c, int slot, uint64_t bytes) {
-    if (c->kt_pin_caps[slot] >= bytes) return PF_OK;
-    if (c->kt_pins[slot]) (void)hipHostFree(c->kt_pins[slot]);
-    c->kt_pins[slot] = nullptr; c->kt_pin_caps[slot] = 0;
-    hipError_t e = hipHostMalloc((void**)&c->kt_pins[slot], bytes, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(PF_ERR_OOM, "hipHostMalloc(%llu) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
-    c->kt_pin_caps[slot] = bytes;
-    return PF_OK;
-}
-
 // range r of the stream written into its buffer (kt_text for even r, kt_text2 for odd) on c->stream: its tiles by
 // kt_text_kernel, its host-rendered sequences by the host renderer now and copied up.  From r = 2 on the buffer's range
 // before (r - 2) must have left the device first: c->stream waits for that range's last copy on c->side.
@@ -2612,9 +2456,9 @@ int kt_copy_block(pf_ctx* c, int slot) {
     const int b = (int)(S.cur & 1);
     const char* buf = (b ? c->kt_text2 : c->kt_text).as<char>();
     const uint64_t n = std::min<uint64_t>(S.pin_bytes, R.bytes - S.cur_off);
-    PFCHK(kt_ensure_pin(c, slot, S.pin_bytes));
+    PFCHK(c->kt_pins[slot].ensure(S.pin_bytes, true));
     HIPCHK(hipStreamWaitEvent(c->side, S.ev_prod[b], 0));
-    HIPCHK(hipMemcpyAsync(c->kt_pins[slot], buf + S.cur_off, n, hipMemcpyDeviceToHost, c->side));
+    HIPCHK(hipMemcpyAsync(c->kt_pins[slot].p, buf + S.cur_off, n, hipMemcpyDeviceToHost, c->side));
     S.pref_valid = true; S.pref_slot = slot; S.pref_n = n;
     if (S.cur_off + n == R.bytes) {
         HIPCHK(hipEventRecord(S.ev_copied[b], c->side));
@@ -2745,7 +2589,7 @@ int pf_kmers_tsv_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
     S.cur_off += n;
     if (S.cur_off == S.ranges[S.cur].bytes) { S.cur++; S.cur_off = 0; }
     if (S.cur < S.ranges.size()) PFCHK(kt_copy_block(c, slot ^ 1));      // the next block on its way meanwhile
-    *ptr = c->kt_pins[slot];
+    *ptr = c->kt_pins[slot].as<char>();
     *nbytes = n;
     return PF_OK;
 }
@@ -2756,15 +2600,6 @@ int pf_device_text_chunk(pf_ctx* c, uint64_t offset, uint64_t max_bytes, const c
     if (!c || !ptr || !nbytes || !max_bytes) return fail(PF_ERR_ARG, "null argument");
     if (offset > c->kt_bytes) return fail(PF_ERR_ARG, "offset beyond the text");
     HIPCHK(hipSetDevice(c->device));
-    auto ensure_pin = [&](int slot) -> int {
-        if (c->kt_pin_caps[slot] >= max_bytes) return PF_OK;
-        if (c->kt_pins[slot]) (void)hipHostFree(c->kt_pins[slot]);
-        c->kt_pins[slot] = nullptr; c->kt_pin_caps[slot] = 0;
-        hipError_t e = hipHostMalloc((void**)&c->kt_pins[slot], max_bytes, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(PF_ERR_OOM, "hipHostMalloc(%llu) failed: %s", (unsigned long long)max_bytes, hipGetErrorString(e));
-        c->kt_pin_caps[slot] = max_bytes;
-        return PF_OK;
-    };
     const uint64_t n = std::min<uint64_t>(max_bytes, c->kt_bytes - offset);
     int slot;
     if (c->kt_pref_valid && c->kt_pref_off == offset && c->kt_pref_n == n) {
@@ -2773,20 +2608,20 @@ int pf_device_text_chunk(pf_ctx* c, uint64_t offset, uint64_t max_bytes, const c
     } else {
         HIPCHK(hipStreamSynchronize(c->side));        // (a block in flight that nobody asked for)
         slot = 0;
-        PFCHK(ensure_pin(slot));
-        if (n) HIPCHK(hipMemcpyAsync(c->kt_pins[slot], c->kt_text.as<char>() + offset, n, hipMemcpyDeviceToHost, c->side));
+        PFCHK(c->kt_pins[slot].ensure(max_bytes, true));
+        if (n) HIPCHK(hipMemcpyAsync(c->kt_pins[slot].p, c->kt_text.as<char>() + offset, n, hipMemcpyDeviceToHost, c->side));
         HIPCHK(hipStreamSynchronize(c->side));
     }
     c->kt_pref_valid = false;
     const uint64_t next = offset + n;
     if (n && next < c->kt_bytes) {
         const int ns = slot ^ 1;
-        PFCHK(ensure_pin(ns));
+        PFCHK(c->kt_pins[ns].ensure(max_bytes, true));
         const uint64_t nn = std::min<uint64_t>(max_bytes, c->kt_bytes - next);
-        HIPCHK(hipMemcpyAsync(c->kt_pins[ns], c->kt_text.as<char>() + next, nn, hipMemcpyDeviceToHost, c->side));
+        HIPCHK(hipMemcpyAsync(c->kt_pins[ns].p, c->kt_text.as<char>() + next, nn, hipMemcpyDeviceToHost, c->side));
         c->kt_pref_valid = true; c->kt_pref_off = next; c->kt_pref_n = nn; c->kt_pref_slot = ns;
     }
-    *ptr = c->kt_pins[slot];
+    *ptr = c->kt_pins[slot].as<char>();
     *nbytes = n;
     return PF_OK;
 }
@@ -2852,7 +2687,7 @@ int pf_result_checksum(pf_ctx* c, uint64_t out[3]) {
     std::vector<const uint64_t*> kp(C);
     std::vector<const uint32_t*> pp(C);
     for (uint32_t i = 0; i < C; i++) {
-        const Arena* ar = c->arenas[c->cluster_arena[i]];
+        const Arena* ar = c->arenas[c->cluster_arena[i]].get();
         const uint64_t local = off[i] >= ar->base ? off[i] - ar->base : 0;      // clusters without k-mers: never read
         kp[i] = ar->key.as<uint64_t>() + local * KW;
         pp[i] = ar->pid.as<uint32_t>() + local;
@@ -2872,7 +2707,6 @@ int pf_result_checksum(pf_ctx* c, uint64_t out[3]) {
             hipMemcpy(out, d_acc.p, 24, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(PF_ERR_HIP, "pf_result_checksum: kernel failed");
     }
-    d_kp.release(); d_pp.release(); d_acc.release();
     return rc;
 }
 
@@ -2902,7 +2736,7 @@ struct IngestSlot {
     char* pin = nullptr; size_t cap = 0;
     bool own = false;         // its blocks are its own (a file larger than the ring's slots), not parts of the ring's two blocks
     DevBuf dev, dpieces;
-    pf::TextPiece* pin_pieces = nullptr; size_t pieces_cap = 0;
+    PinBuf pin_pieces;
     hipEvent_t ev = nullptr;
     bool held = false;        // a reader thread is filling it
     bool inflight = false;    // its copy / kernel may not have finished (ev)
@@ -2948,7 +2782,6 @@ int ingest_acquire(void* self, size_t bytes, char** host, uint32_t* slot) {
             if (s.cap < bytes) {
                 lk.unlock();                                   // (the slot is ours: nobody else looks at it while it is held)
                 if (s.pin && s.own) { (void)hipHostUnregister(s.pin); free(s.pin); }
-                if (!s.own) { s.dev.p = nullptr; s.dev.cap = 0; s.dev.view = false; }     // (a part of the ring's block: not ours to free)
                 s.pin = nullptr; s.cap = 0; s.own = true;
                 const size_t want = bytes + bytes / 4 + 4096;
                 bool ok = posix_memalign((void**)&s.pin, 4096, want) == 0 && s.pin;
@@ -2988,17 +2821,12 @@ int ingest_submit(void* self, uint32_t slot, size_t text_bytes, const pf_ingest_
     const size_t tail = (text_bytes + 63) & ~(size_t)63;
     const bool inline_pieces = tail + (size_t)n * sizeof(pf::TextPiece) <= s.cap;
     pf::TextPiece* const pcs = inline_pieces ? reinterpret_cast<pf::TextPiece*>(s.pin + tail) : nullptr;
-    if (!inline_pieces && n > s.pieces_cap) {
-        if (s.pin_pieces) (void)hipHostFree(s.pin_pieces);
-        s.pin_pieces = nullptr; s.pieces_cap = 0;
-        const size_t want = (size_t)n + n / 2 + 64;
-        if (hipHostMalloc((void**)&s.pin_pieces, want * sizeof(pf::TextPiece), hipHostMallocDefault) != hipSuccess)
-            return done(I->failed(PF_ERR_OOM, "hipHostMalloc failed (ingest pieces)"));
-        s.pieces_cap = want;
-    }
+    if (!inline_pieces && (size_t)n * sizeof(pf::TextPiece) > s.pin_pieces.cap &&
+        s.pin_pieces.ensure(((size_t)n + n / 2 + 64) * sizeof(pf::TextPiece), true) != PF_OK)
+        return done(I->failed(PF_ERR_OOM, "ingest pieces: " + g_err));
     uint64_t lo = text_bytes, blocks = 0;
     for (uint32_t i = 0; i < n; i++) {
-        pf::TextPiece& t = (inline_pieces ? pcs : s.pin_pieces)[i];
+        pf::TextPiece& t = (inline_pieces ? pcs : s.pin_pieces.as<pf::TextPiece>())[i];
         t.text_off = pieces[i].text_off; t.dst_word = pieces[i].dst_word; t.nbases = (uint32_t)pieces[i].nbases;
         t.nwords = (uint32_t)(2 * ((pieces[i].nbases + 63) / 64) + 4);
         t.width = pieces[i].width; t.eol = pieces[i].eol; t.block0 = (uint32_t)blocks; t.pad = 0;
@@ -3021,7 +2849,7 @@ int ingest_submit(void* self, uint32_t slot, size_t text_bytes, const pf_ingest_
     } else {
         if (s.dpieces.ensure((size_t)n * sizeof(pf::TextPiece)) != PF_OK) return done(I->failed(PF_ERR_OOM, "device block for ingest pieces"));
         if (hipMemcpyAsync((char*)s.dev.p + lo, s.pin + lo, text_bytes - lo, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(s.dpieces.p, s.pin_pieces, (size_t)n * sizeof(pf::TextPiece), hipMemcpyHostToDevice, st) != hipSuccess)
+            hipMemcpyAsync(s.dpieces.p, s.pin_pieces.p, (size_t)n * sizeof(pf::TextPiece), hipMemcpyHostToDevice, st) != hipSuccess)
             return done(I->failed(PF_ERR_HIP, "ingest: upload of a genome's text failed"));
         dpcs = (const pf::TextPiece*)s.dpieces.p;
     }
@@ -3121,13 +2949,9 @@ int pf_pangenome_open_device_cb(const pf_pangenome_opts* o, pf_ctx* (*get_ctx)(v
     }
     lap("last uploads");
     if (I.ring_pin) { (void)hipHostUnregister(I.ring_pin); free(I.ring_pin); }
-    I.ring_dev.release();
     for (auto& s : I.slots) {
         if (s.pin && s.own) { (void)hipHostUnregister(s.pin); free(s.pin); }
-        if (!s.own) { s.dev.p = nullptr; s.dev.cap = 0; s.dev.view = false; }
-        if (s.pin_pieces) (void)hipHostFree(s.pin_pieces);
         if (s.ev) (void)hipEventDestroy(s.ev);
-        s.dev.release(); s.dpieces.release();
     }
     if (rc != PF_OK) {
         if (P) pf_pangenome_close(P);
@@ -3195,13 +3019,13 @@ int pf_genomes_upload(pf_ctx* c, uint32_t n, const char* const* ascii, const uin
             if (!last) blks.emplace_back();
         } while (done < L);
     }
-    char* pin[2] = {nullptr, nullptr};
+    PinBuf pin[2];
     DevBuf dasc[2], dpieces[2];
     hipEvent_t ev[2] = {nullptr, nullptr};
     int rc = PF_OK;
     do {
         for (int q = 0; q < 2 && rc == PF_OK; q++) {
-            if (hipHostMalloc((void**)&pin[q], BLOCK, hipHostMallocDefault) != hipSuccess) { rc = fail(PF_ERR_OOM, "hipHostMalloc(%zu) failed", BLOCK); break; }
+            if ((rc = pin[q].ensure(BLOCK, true)) != PF_OK) break;
             if ((rc = dasc[q].ensure(BLOCK)) != PF_OK) break;
             if (hipEventCreateWithFlags(&ev[q], hipEventDisableTiming) != hipSuccess) { rc = fail(PF_ERR_HIP, "hipEventCreate failed"); break; }
         }
@@ -3212,7 +3036,7 @@ int pf_genomes_upload(pf_ctx* c, uint32_t n, const char* const* ascii, const uin
             const int q = (int)(bi & 1);
             if (hipEventSynchronize(ev[q]) != hipSuccess) { rc = fail(PF_ERR_HIP, "hipEventSynchronize failed"); break; }   // the slot's last block has left it
             // the block's pieces into the pinned block, on the host threads (padding bases are 'A')
-            char* dst = pin[q];
+            char* dst = pin[q].as<char>();
             parallel_for(bk.fill, [&](uint64_t a, uint64_t e) {          // every thread takes a byte range of the block
                 for (const Src& sp : bk.src) {
                     const uint64_t lo = std::max<uint64_t>(a, sp.at), hi = std::min<uint64_t>(e, sp.at + sp.n);
@@ -3221,7 +3045,7 @@ int pf_genomes_upload(pf_ctx* c, uint32_t n, const char* const* ascii, const uin
             });
             for (const Src& sp : bk.src) { const size_t padded = (sp.n + 31) / 32 * 32; memset(dst + sp.at + sp.n, 'A', padded - sp.n); }
             if ((rc = dpieces[q].ensure(bk.pieces.size() * sizeof(pf::PackPiece))) != PF_OK) break;
-            if (hipMemcpyAsync(dasc[q].p, pin[q], bk.fill, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            if (hipMemcpyAsync(dasc[q].p, pin[q].p, bk.fill, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
                 hipMemcpyAsync(dpieces[q].p, bk.pieces.data(), bk.pieces.size() * sizeof(pf::PackPiece), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
                 rc = fail(PF_ERR_HIP, "genome upload failed"); break;
             }
@@ -3231,12 +3055,8 @@ int pf_genomes_upload(pf_ctx* c, uint32_t n, const char* const* ascii, const uin
         }
     } while (0);
     if (hipStreamSynchronize(c->stream) != hipSuccess && rc == PF_OK) rc = fail(PF_ERR_HIP, "genome upload failed");
-    for (int q = 0; q < 2; q++) {
-        if (pin[q]) (void)hipHostFree(pin[q]);
-        if (ev[q]) (void)hipEventDestroy(ev[q]);
-        dasc[q].release(); dpieces[q].release();
-    }
-    return rc;
+    for (auto e : ev) if (e) (void)hipEventDestroy(e);
+    return rc;                            // (the staging buffers go now, after the sync)
 }
 
 namespace {
@@ -3255,16 +3075,7 @@ int ensure_b64_dev(pf_ctx* c) {
 // pinned host block `slot` of the rendered text, at least `total` bytes
 int text_pin(pf_ctx* c, size_t total) {
     c->txt_slot ^= 1;
-    char*& pin = c->txt_pins[c->txt_slot];
-    size_t& cap = c->txt_pin_caps[c->txt_slot];
-    if (total > cap) {
-        if (pin) (void)hipHostFree(pin);
-        pin = nullptr; cap = 0;
-        const size_t want = total + total / 4;
-        if (hipHostMalloc((void**)&pin, want, hipHostMallocDefault) != hipSuccess) return fail(PF_ERR_OOM, "hipHostMalloc(%zu) failed", want);
-        cap = want;
-    }
-    return PF_OK;
+    return c->txt_pins[c->txt_slot].ensure(total);
 }
 }  // namespace
 
@@ -3304,7 +3115,7 @@ int pf_render_pattern_rows(pf_ctx* c, const uint32_t* pids, uint64_t n, const ch
     hpp.text = c->txt_dev.as<char>(); hpp.n = P; hpp.W = W;
     hipLaunchKernelGGL(pf::hp_text_kernel, dim3(P), dim3(256), 0, st, hpp);
     HIPCHK(hipGetLastError());
-    char* pin = c->txt_pins[c->txt_slot];
+    char* pin = c->txt_pins[c->txt_slot].as<char>();
     HIPCHK(hipMemcpyAsync(pin, c->txt_dev.p, total, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *text = pin; *nbytes = total;
@@ -3349,7 +3160,6 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
     }
     PFCHK(ensure_b64_dev(c));
     HIPCHK(hipStreamSynchronize(st));
-    d_rlen.release();
     // ---- kmers_to_hashes layout: rows per cluster, workgroups per cluster
     std::vector<uint64_t> text_off(C + 1, 0);
     std::vector<uint32_t> name_off(C + 1, 0), arena_of(C), blk_cluster, blk_row0;
@@ -3380,7 +3190,7 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
     const uint64_t total = hp_at + hp_n + 16;
     PFCHK(c->txt_dev.ensure(total));
     PFCHK(text_pin(c, total));
-    char* txt_pin = c->txt_pins[c->txt_slot];
+    char* txt_pin = c->txt_pins[c->txt_slot].as<char>();
     // ---- one block of tables for both kernels
     auto pad8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
     size_t o = 0;

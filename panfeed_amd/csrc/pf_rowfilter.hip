@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/panfeed_hip.h"
+#include "pf_buf.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -25,18 +26,7 @@
 #include <thread>
 #include <vector>
 
-extern "C" void pf_set_error_(const char* msg);
-
 namespace {
-
-int rf_fail(int code, const std::string& msg) { pf_set_error_(msg.c_str()); return code; }
-#define RFCHK(expr)                                                                                       \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess)                                                                             \
-            return rf_fail(e_ == hipErrorOutOfMemory ? PF_ERR_OOM : PF_ERR_HIP,                           \
-                           std::string(#expr) + " failed: " + hipGetErrorString(e_));                     \
-    } while (0)
 
 constexpr uint64_t RF_EMPTY = 0;
 constexpr uint32_t RF_MAX_FIELD = 4096;       // a key field longer than this never matches (nor do the keys)
@@ -128,15 +118,12 @@ struct pf_rowfilter {
     int first_field = 0;
     hipStream_t stream = nullptr;
     std::unordered_set<std::string> keys;
-    uint64_t* d_set = nullptr;
+    DevBuf d_set;                              // the keys' hashes (uint64), cap slots
     uint64_t cap = 0;
-    unsigned char* d_text = nullptr;
-    size_t text_cap = 0;
-    char* pin = nullptr;
-    size_t pin_cap = 0;
-    uint64_t* d_out = nullptr;
-    size_t out_cap = 0;
-    unsigned long long* d_count = nullptr;
+    DevBuf d_text;                             // the block, padded
+    PinBuf pin;                                // its pinned host copy
+    DevBuf d_out;                              // candidate positions (uint64)
+    DevBuf d_count;
     std::vector<uint64_t> begin, end;          // result of the last scan
     uint64_t bytes_scanned = 0;
     float device_ms = 0;
@@ -149,11 +136,6 @@ void pf_rowfilter_destroy(pf_rowfilter* f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
     if (f->stream) (void)hipStreamSynchronize(f->stream);
-    if (f->d_set) (void)hipFree(f->d_set);
-    if (f->d_text) (void)hipFree(f->d_text);
-    if (f->d_out) (void)hipFree(f->d_out);
-    if (f->d_count) (void)hipFree(f->d_count);
-    if (f->pin) (void)hipHostFree(f->pin);
     if (f->e0) (void)hipEventDestroy(f->e0);
     if (f->e1) (void)hipEventDestroy(f->e1);
     if (f->stream) (void)hipStreamDestroy(f->stream);
@@ -162,12 +144,12 @@ void pf_rowfilter_destroy(pf_rowfilter* f) {
 
 int pf_rowfilter_create(int device, int first_field, const char* const* keys, const uint32_t* key_len, uint64_t n_keys,
                         pf_rowfilter** out) {
-    if (!out || (n_keys && (!keys || !key_len))) return rf_fail(PF_ERR_ARG, "pf_rowfilter_create: null argument");
+    if (!out || (n_keys && (!keys || !key_len))) return fail(PF_ERR_ARG, "pf_rowfilter_create: null argument");
     *out = nullptr;
     int ndev = 0;
-    RFCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return rf_fail(PF_ERR_ARG, "pf_rowfilter_create: no such device");
-    RFCHK(hipSetDevice(device));
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_rowfilter_create: no such device");
+    HIPCHK(hipSetDevice(device));
     pf_rowfilter* f = new pf_rowfilter();
     f->device = device;
     f->first_field = first_field ? 1 : 0;
@@ -188,12 +170,12 @@ int pf_rowfilter_create(int device, int first_field, const char* const* keys, co
     int rc = PF_OK;
     do {
         if (hipStreamCreate(&f->stream) != hipSuccess || hipEventCreate(&f->e0) != hipSuccess || hipEventCreate(&f->e1) != hipSuccess ||
-            hipMalloc((void**)&f->d_set, cap * 8) != hipSuccess || hipMalloc((void**)&f->d_count, 8) != hipSuccess) {
-            rc = rf_fail(PF_ERR_HIP, "pf_rowfilter_create: device allocation failed");
+            f->d_set.ensure(cap * 8, true) != PF_OK || f->d_count.ensure(8, true) != PF_OK) {
+            rc = fail(PF_ERR_HIP, "pf_rowfilter_create: device allocation failed");
             break;
         }
-        if (hipMemcpy(f->d_set, table.data(), cap * 8, hipMemcpyHostToDevice) != hipSuccess)
-            rc = rf_fail(PF_ERR_HIP, "pf_rowfilter_create: upload failed");
+        if (hipMemcpy(f->d_set.p, table.data(), cap * 8, hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(PF_ERR_HIP, "pf_rowfilter_create: upload failed");
     } while (0);
     if (rc != PF_OK) { pf_rowfilter_destroy(f); return rc; }
     *out = f;
@@ -203,8 +185,8 @@ int pf_rowfilter_create(int device, int first_field, const char* const* keys, co
 int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const uint64_t** line_begin,
                       const uint64_t** line_end, uint64_t* n_lines, uint64_t* consumed) {
     if (!f || !line_begin || !line_end || !n_lines || !consumed || (nbytes && !text))
-        return rf_fail(PF_ERR_ARG, "pf_rowfilter_scan: null argument");
-    RFCHK(hipSetDevice(f->device));
+        return fail(PF_ERR_ARG, "pf_rowfilter_scan: null argument");
+    HIPCHK(hipSetDevice(f->device));
     f->begin.clear(); f->end.clear();
     *line_begin = nullptr; *line_end = nullptr; *n_lines = 0; *consumed = 0;
     // complete lines only: the caller carries the rest over to its next block
@@ -213,65 +195,52 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
     *consumed = n;
     if (!n || f->keys.empty()) return PF_OK;
     const size_t padded = (n + 15) / 16 * 16 + 16;
-    if (padded > f->text_cap) {
-        if (f->d_text) (void)hipFree(f->d_text);
-        if (f->pin) (void)hipHostFree(f->pin);
-        f->d_text = nullptr; f->pin = nullptr; f->text_cap = 0;
-        const size_t want = padded + padded / 8;
-        RFCHK(hipMalloc((void**)&f->d_text, want));
-        RFCHK(hipHostMalloc((void**)&f->pin, want, hipHostMallocDefault));
-        f->text_cap = want;
-    }
+    if (padded > f->d_text.cap) PFCHK(f->d_text.ensure(padded + padded / 8, true));
+    if (padded > f->pin.cap) PFCHK(f->pin.ensure(padded + padded / 8, true));
     // room for the candidates: the filter keeps few rows, so the room is a guess (a position per 64 bytes of text, a
     // million at least) and the kernel is run again with what it asked for should the guess be too small -- counting
     // the lines of the block on the host to size it for the worst case cost more than the kernel itself
     const size_t guess = std::max<size_t>((size_t)1 << 20, (size_t)(n / 64));
-    if (guess > f->out_cap) {
-        if (f->d_out) (void)hipFree(f->d_out);
-        f->d_out = nullptr; f->out_cap = 0;
-        RFCHK(hipMalloc((void**)&f->d_out, guess * 8));
-        f->out_cap = guess;
-    }
+    PFCHK(f->d_out.ensure(guess * 8, true));
     {   // the block into pinned memory on a few threads (one memcpy of 256 MB is slower than the rest of the call)
+        char* const pin = f->pin.as<char>();
         const unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(8, n >> 22));
         std::vector<std::thread> th;
         const uint64_t step = (n + nt - 1) / nt;
         for (unsigned t = 1; t < nt; t++) {
             const uint64_t a = t * step, b = std::min<uint64_t>(n, a + step);
-            if (a < b) th.emplace_back([=] { memcpy(f->pin + a, text + a, (size_t)(b - a)); });
+            if (a < b) th.emplace_back([=] { memcpy(pin + a, text + a, (size_t)(b - a)); });
         }
-        memcpy(f->pin, text, (size_t)std::min<uint64_t>(n, step));
+        memcpy(pin, text, (size_t)std::min<uint64_t>(n, step));
         for (auto& t : th) t.join();
+        memset(pin + n, 0, padded - n);
     }
-    memset(f->pin + n, 0, padded - n);
-    RFCHK(hipMemcpyAsync(f->d_text, f->pin, padded, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipMemcpyAsync(f->d_text.p, f->pin.p, padded, hipMemcpyHostToDevice, f->stream));
     unsigned long long cnt = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
-        RFCHK(hipMemsetAsync(f->d_count, 0, 8, f->stream));
+        HIPCHK(hipMemsetAsync(f->d_count.p, 0, 8, f->stream));
         RfParams p{};
-        p.text = f->d_text; p.n = n; p.set = f->d_set; p.cap = f->cap; p.first_field = f->first_field;
-        p.out = f->d_out; p.count = f->d_count; p.out_cap = f->out_cap;
+        p.text = f->d_text.as<unsigned char>(); p.n = n; p.set = f->d_set.as<uint64_t>(); p.cap = f->cap;
+        p.first_field = f->first_field;
+        p.out = f->d_out.as<uint64_t>(); p.count = f->d_count.as<unsigned long long>(); p.out_cap = f->d_out.cap / 8;
         const uint64_t nvec = (n + 15) / 16;
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((nvec + 255) / 256, 256 * 16);
-        RFCHK(hipEventRecord(f->e0, f->stream));
+        HIPCHK(hipEventRecord(f->e0, f->stream));
         hipLaunchKernelGGL(rowfilter_kernel, dim3(blocks), dim3(256), 0, f->stream, p);
-        RFCHK(hipGetLastError());
-        RFCHK(hipEventRecord(f->e1, f->stream));
-        RFCHK(hipMemcpyAsync(&cnt, f->d_count, 8, hipMemcpyDeviceToHost, f->stream));
-        RFCHK(hipStreamSynchronize(f->stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(f->e1, f->stream));
+        HIPCHK(hipMemcpyAsync(&cnt, f->d_count.p, 8, hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(hipStreamSynchronize(f->stream));
         float ms = 0;
         if (hipEventElapsedTime(&ms, f->e0, f->e1) == hipSuccess) f->device_ms += ms;
-        if (cnt <= f->out_cap) break;
+        if (cnt <= f->d_out.cap / 8) break;
         // more candidates than room (the kernel counted them all and kept what fitted): again, with room for all
-        (void)hipFree(f->d_out);
-        f->d_out = nullptr; f->out_cap = 0;
-        RFCHK(hipMalloc((void**)&f->d_out, ((size_t)cnt + (size_t)cnt / 8) * 8));
-        f->out_cap = (size_t)cnt + (size_t)cnt / 8;
+        PFCHK(f->d_out.ensure(((size_t)cnt + (size_t)cnt / 8) * 8, true));
     }
     f->bytes_scanned += n;
-    if (cnt > f->out_cap) return rf_fail(PF_ERR_STATE, "pf_rowfilter_scan: more candidates than room, twice");
+    if (cnt > f->d_out.cap / 8) return fail(PF_ERR_STATE, "pf_rowfilter_scan: more candidates than room, twice");
     std::vector<uint64_t> pos((size_t)cnt);
-    if (cnt) RFCHK(hipMemcpy(pos.data(), f->d_out, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+    if (cnt) HIPCHK(hipMemcpy(pos.data(), f->d_out.p, (size_t)cnt * 8, hipMemcpyDeviceToHost));
     std::sort(pos.begin(), pos.end());
     // exact check of every candidate (a 64-bit hash collision must not add a row), then the line's extent
     for (uint64_t q : pos) {
@@ -301,7 +270,7 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
 }
 
 int pf_rowfilter_stats(pf_rowfilter* f, uint64_t* bytes_scanned, float* device_ms) {
-    if (!f) return rf_fail(PF_ERR_ARG, "pf_rowfilter_stats: null argument");
+    if (!f) return fail(PF_ERR_ARG, "pf_rowfilter_stats: null argument");
     if (bytes_scanned) *bytes_scanned = f->bytes_scanned;
     if (device_ms) *device_ms = f->device_ms;
     return PF_OK;
@@ -602,30 +571,23 @@ struct pf_plotgrid {
     int zoom = 0;
     int64_t start = 0, stop = 0;
     uint32_t n_strains = 0;
-    // the phenotype strains (static)
-    unsigned long long* d_strain_hash = nullptr;
-    uint32_t* d_strain_id = nullptr;
+    // the phenotype strains (static): hash set (unsigned long long, uint32 ids), the names, offset << 16 | length per id
+    DevBuf d_strain_hash, d_strain_id, d_strain_bytes, d_strain_str;
     uint64_t strain_cap = 0;
-    unsigned char* d_strain_bytes = nullptr;
-    uint64_t* d_strain_str = nullptr;
-    // the two growing tables
+    // the two growing tables (PgTable)
     struct Tab {
-        unsigned long long* hash = nullptr;
-        unsigned long long* str = nullptr;
+        DevBuf hash, str;                        // cap slots each (unsigned long long)
         uint64_t cap = 0;
-        unsigned char* arena = nullptr;
-        uint64_t arena_cap = 0;
-        unsigned long long* ctr = nullptr;       // [0] arena bytes used, [1] entries
+        DevBuf arena;
+        DevBuf ctr;                              // [0] arena bytes used, [1] entries
         uint64_t used = 0, count = 0;            // host copies after the last scan
     } cl, pv;
-    PgRecord* d_rec = nullptr;
-    uint64_t rec_cap = 0, n_rec = 0;
-    PgCheck* d_chk = nullptr;
-    uint64_t chk_cap = 0;
-    unsigned long long* d_ctr = nullptr;        // [0] records [1] checks [2] lines ; err as [3]
-    unsigned char* d_text = nullptr;
-    size_t text_cap = 0;
-    char* pin = nullptr;
+    DevBuf d_rec;                               // PgRecord
+    uint64_t n_rec = 0;
+    DevBuf d_chk;                               // PgCheck
+    DevBuf d_ctr;                               // [0] records [1] checks [2] lines ; err as [3]
+    DevBuf d_text;                              // the block, padded
+    PinBuf pin;                                 // its pinned host copy
     uint64_t bytes_scanned = 0, lines = 0;
     // after pf_plotgrid_finish
     int finished = 0;
@@ -634,72 +596,57 @@ struct pf_plotgrid {
     std::vector<uint64_t> cl_rows;
     std::string cl_names, pv_texts;
     std::vector<uint64_t> cl_off, pv_off;
-    unsigned long long* d_sig = nullptr;       // by p-value slot
+    DevBuf d_sig;                              // significance key by p-value slot
     int sig_set = 0;
-    unsigned long long* d_key = nullptr;
-    unsigned long long* d_cnt = nullptr;
-    uint64_t grid_cap = 0;
-    int32_t* d_slot_item = nullptr;
-    uint64_t* d_item = nullptr;                // off[n] | min[n] | width[n], packed in one buffer
-    uint64_t item_cap = 0;
+    DevBuf d_key, d_cnt;                       // the grids' cells
+    DevBuf d_slot_item;
+    DevBuf d_item;                             // off[n] | min[n] | width[n], packed in one buffer
 };
 
 namespace {
 
-PgTable pg_view(pf_plotgrid::Tab& t) { return PgTable{t.hash, t.str, t.cap, t.arena, t.ctr, t.ctr + 1}; }
+using ull = unsigned long long;
 
-int pg_tab_alloc(pf_plotgrid::Tab& t, uint64_t cap, hipStream_t s) {
-    RFCHK(hipMalloc((void**)&t.hash, cap * 8));
-    RFCHK(hipMalloc((void**)&t.str, cap * 8));
-    RFCHK(hipMemsetAsync(t.hash, 0, cap * 8, s));
-    t.cap = cap;
-    return PF_OK;
+PgTable pg_view(pf_plotgrid::Tab& t) {
+    return PgTable{t.hash.as<ull>(), t.str.as<ull>(), t.cap, t.arena.as<unsigned char>(), t.ctr.as<ull>(), t.ctr.as<ull>() + 1};
 }
 
 // room for `more` new entries (and `bytes` new arena bytes) at a load of at most 1/2; records' slots follow a move
 int pg_tab_reserve(pf_plotgrid* g, pf_plotgrid::Tab& t, uint64_t more, uint64_t bytes, int field) {
-    if (t.used + bytes > t.arena_cap) {
+    if (t.used + bytes > t.arena.cap) {
         uint64_t want = std::max<uint64_t>((t.used + bytes) * 2, 1 << 20);
-        if (want >= ((uint64_t)1 << 47)) return rf_fail(PF_ERR_CAPACITY, "pf_plotgrid: name arena over 2^47 bytes");
-        unsigned char* a = nullptr;
-        RFCHK(hipMalloc((void**)&a, want));
-        if (t.used) RFCHK(hipMemcpyAsync(a, t.arena, t.used, hipMemcpyDeviceToDevice, g->stream));
-        RFCHK(hipStreamSynchronize(g->stream));
-        if (t.arena) (void)hipFree(t.arena);
-        t.arena = a;
-        t.arena_cap = want;
+        if (want >= ((uint64_t)1 << 47)) return fail(PF_ERR_CAPACITY, "pf_plotgrid: name arena over 2^47 bytes");
+        DevBuf a;
+        PFCHK(a.ensure(want, true));
+        if (t.used) HIPCHK(hipMemcpyAsync(a.p, t.arena.p, t.used, hipMemcpyDeviceToDevice, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+        std::swap(t.arena, a);                  // (the old arena goes at the end of this block)
     }
     uint64_t cap = std::max<uint64_t>(t.cap, 1024);
     while (cap < 2 * (t.count + more)) cap <<= 1;
-    if (cap >= ((uint64_t)1 << 32)) return rf_fail(PF_ERR_CAPACITY, "pf_plotgrid: over 2^31 distinct names in a table");
+    if (cap >= ((uint64_t)1 << 32)) return fail(PF_ERR_CAPACITY, "pf_plotgrid: over 2^31 distinct names in a table");
     if (cap == t.cap) return PF_OK;
-    pf_plotgrid::Tab n = t;
-    n.hash = nullptr; n.str = nullptr;
-    if (int rc = pg_tab_alloc(n, cap, g->stream)) return rc;
-    if (t.hash) {
-        uint32_t* remap = nullptr;
-        RFCHK(hipMalloc((void**)&remap, t.cap * 4));
-        hipLaunchKernelGGL(pg_rehash_kernel, dim3(pg_blocks(t.cap)), dim3(256), 0, g->stream, pg_view(t), pg_view(n), remap);
-        RFCHK(hipGetLastError());
+    DevBuf hash, str;
+    PFCHK(hash.ensure(cap * 8, true));
+    PFCHK(str.ensure(cap * 8, true));
+    HIPCHK(hipMemsetAsync(hash.p, 0, cap * 8, g->stream));
+    if (t.hash.p) {
+        DevBuf remap;
+        PFCHK(remap.ensure(t.cap * 4, true));
+        PgTable n = pg_view(t);
+        n.hash = hash.as<ull>(); n.str = str.as<ull>(); n.cap = cap;
+        hipLaunchKernelGGL(pg_rehash_kernel, dim3(pg_blocks(t.cap)), dim3(256), 0, g->stream, pg_view(t), n, remap.as<uint32_t>());
+        HIPCHK(hipGetLastError());
         if (g->n_rec) {
-            hipLaunchKernelGGL(pg_remap_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->stream, g->d_rec, g->n_rec,
-                               (const uint32_t*)remap, field);
-            RFCHK(hipGetLastError());
+            hipLaunchKernelGGL(pg_remap_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->stream, g->d_rec.as<PgRecord>(), g->n_rec,
+                               (const uint32_t*)remap.p, field);
+            HIPCHK(hipGetLastError());
         }
-        RFCHK(hipStreamSynchronize(g->stream));
-        (void)hipFree(remap);
-        (void)hipFree(t.hash);
-        (void)hipFree(t.str);
+        HIPCHK(hipStreamSynchronize(g->stream));
     }
-    t.hash = n.hash; t.str = n.str; t.cap = cap;
+    std::swap(t.hash, hash); std::swap(t.str, str);   // (the old ones go on return)
+    t.cap = cap;
     return PF_OK;
-}
-
-void pg_tab_free(pf_plotgrid::Tab& t) {
-    if (t.hash) (void)hipFree(t.hash);
-    if (t.str) (void)hipFree(t.str);
-    if (t.arena) (void)hipFree(t.arena);
-    if (t.ctr) (void)hipFree(t.ctr);
 }
 
 // the table's entries in slot order: dense id -> slot, their bytes joined, offsets (n + 1)
@@ -707,10 +654,10 @@ int pg_tab_list(pf_plotgrid* g, pf_plotgrid::Tab& t, std::vector<uint32_t>& slot
     std::vector<unsigned long long> h(t.cap), st(t.cap);
     std::string arena(t.used, '\0');
     if (t.cap) {
-        RFCHK(hipMemcpy(h.data(), t.hash, t.cap * 8, hipMemcpyDeviceToHost));
-        RFCHK(hipMemcpy(st.data(), t.str, t.cap * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h.data(), t.hash.p, t.cap * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(st.data(), t.str.p, t.cap * 8, hipMemcpyDeviceToHost));
     }
-    if (t.used) RFCHK(hipMemcpy(&arena[0], t.arena, t.used, hipMemcpyDeviceToHost));
+    if (t.used) HIPCHK(hipMemcpy(&arena[0], t.arena.p, t.used, hipMemcpyDeviceToHost));
     slots.clear(); bytes.clear(); off.assign(1, 0);
     for (uint64_t i = 0; i < t.cap; i++) {
         if (!h[i]) continue;
@@ -729,13 +676,6 @@ void pf_plotgrid_destroy(pf_plotgrid* g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
-    for (void* q : {(void*)g->d_strain_hash, (void*)g->d_strain_id, (void*)g->d_strain_bytes, (void*)g->d_strain_str,
-                    (void*)g->d_rec, (void*)g->d_chk, (void*)g->d_ctr, (void*)g->d_text, (void*)g->d_sig, (void*)g->d_key,
-                    (void*)g->d_cnt, (void*)g->d_slot_item, (void*)g->d_item})
-        if (q) (void)hipFree(q);
-    pg_tab_free(g->cl);
-    pg_tab_free(g->pv);
-    if (g->pin) (void)hipHostFree(g->pin);
     if (g->e0) (void)hipEventDestroy(g->e0);
     if (g->e1) (void)hipEventDestroy(g->e1);
     if (g->stream) (void)hipStreamDestroy(g->stream);
@@ -744,20 +684,20 @@ void pf_plotgrid_destroy(pf_plotgrid* g) {
 
 int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* strain_len, uint32_t n_strains,
                        const int32_t* columns, int zoom, int64_t start, int64_t stop, pf_plotgrid** out) {
-    if (!out || !columns || (n_strains && (!strains || !strain_len))) return rf_fail(PF_ERR_ARG, "pf_plotgrid_create: null argument");
+    if (!out || !columns || (n_strains && (!strains || !strain_len))) return fail(PF_ERR_ARG, "pf_plotgrid_create: null argument");
     *out = nullptr;
-    if (n_strains >= (1u << 24)) return rf_fail(PF_ERR_ARG, "pf_plotgrid_create: at most 2^24 - 1 phenotype strains");
+    if (n_strains >= (1u << 24)) return fail(PF_ERR_ARG, "pf_plotgrid_create: at most 2^24 - 1 phenotype strains");
     int ndev = 0;
-    RFCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return rf_fail(PF_ERR_ARG, "pf_plotgrid_create: no such device");
-    RFCHK(hipSetDevice(device));
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_plotgrid_create: no such device");
+    HIPCHK(hipSetDevice(device));
     std::unique_ptr<pf_plotgrid, void (*)(pf_plotgrid*)> g(new pf_plotgrid(), pf_plotgrid_destroy);
     g->device = device;
     g->zoom = zoom ? 1 : 0;
     g->start = start; g->stop = stop;
     g->n_strains = n_strains;
     for (int q = 0; q < 6; q++) {
-        if (columns[q] < 0) return rf_fail(PF_ERR_ARG, "pf_plotgrid_create: negative column index");
+        if (columns[q] < 0) return fail(PF_ERR_ARG, "pf_plotgrid_create: negative column index");
         g->col[q] = columns[q];
         g->max_col = std::max(g->max_col, columns[q]);
     }
@@ -769,7 +709,7 @@ int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* s
     std::string bytes;
     std::vector<uint64_t> str(std::max<uint32_t>(n_strains, 1), 0);
     for (uint32_t i = 0; i < n_strains; i++) {
-        if (strain_len[i] > 0xFFFF) return rf_fail(PF_ERR_ARG, "pf_plotgrid_create: strain name over 65535 bytes");
+        if (strain_len[i] > 0xFFFF) return fail(PF_ERR_ARG, "pf_plotgrid_create: strain name over 65535 bytes");
         str[i] = ((uint64_t)bytes.size() << 16) | strain_len[i];
         bytes.append(strains[i], strain_len[i]);
         const uint64_t h = rf_hash(strains[i], strain_len[i]);
@@ -787,109 +727,97 @@ int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* s
         ids[slot] = i;
     }
     g->strain_cap = cap;
-    RFCHK(hipStreamCreate(&g->stream));
-    RFCHK(hipEventCreate(&g->e0));
-    RFCHK(hipEventCreate(&g->e1));
-    RFCHK(hipMalloc((void**)&g->d_strain_hash, cap * 8));
-    RFCHK(hipMalloc((void**)&g->d_strain_id, cap * 4));
-    RFCHK(hipMalloc((void**)&g->d_strain_bytes, std::max<size_t>(bytes.size(), 1)));
-    RFCHK(hipMalloc((void**)&g->d_strain_str, str.size() * 8));
-    RFCHK(hipMemcpy(g->d_strain_hash, hs.data(), cap * 8, hipMemcpyHostToDevice));
-    RFCHK(hipMemcpy(g->d_strain_id, ids.data(), cap * 4, hipMemcpyHostToDevice));
-    if (!bytes.empty()) RFCHK(hipMemcpy(g->d_strain_bytes, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
-    RFCHK(hipMemcpy(g->d_strain_str, str.data(), str.size() * 8, hipMemcpyHostToDevice));
-    RFCHK(hipMalloc((void**)&g->d_ctr, 4 * 8));
-    RFCHK(hipMemset(g->d_ctr, 0, 4 * 8));
+    HIPCHK(hipStreamCreate(&g->stream));
+    HIPCHK(hipEventCreate(&g->e0));
+    HIPCHK(hipEventCreate(&g->e1));
+    PFCHK(g->d_strain_hash.ensure(cap * 8, true));
+    PFCHK(g->d_strain_id.ensure(cap * 4, true));
+    PFCHK(g->d_strain_bytes.ensure(std::max<size_t>(bytes.size(), 1), true));
+    PFCHK(g->d_strain_str.ensure(str.size() * 8, true));
+    HIPCHK(hipMemcpy(g->d_strain_hash.p, hs.data(), cap * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(g->d_strain_id.p, ids.data(), cap * 4, hipMemcpyHostToDevice));
+    if (!bytes.empty()) HIPCHK(hipMemcpy(g->d_strain_bytes.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(g->d_strain_str.p, str.data(), str.size() * 8, hipMemcpyHostToDevice));
+    PFCHK(g->d_ctr.ensure(4 * 8, true));
+    HIPCHK(hipMemset(g->d_ctr.p, 0, 4 * 8));
     for (auto* t : {&g->cl, &g->pv}) {
-        RFCHK(hipMalloc((void**)&t->ctr, 2 * 8));
-        RFCHK(hipMemset(t->ctr, 0, 2 * 8));
+        PFCHK(t->ctr.ensure(2 * 8, true));
+        HIPCHK(hipMemset(t->ctr.p, 0, 2 * 8));
     }
     *out = g.release();
     return PF_OK;
 }
 
 int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t* consumed) {
-    if (!g || !consumed || (nbytes && !text)) return rf_fail(PF_ERR_ARG, "pf_plotgrid_scan: null argument");
-    if (g->finished) return rf_fail(PF_ERR_STATE, "pf_plotgrid_scan: after pf_plotgrid_finish");
-    RFCHK(hipSetDevice(g->device));
+    if (!g || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_plotgrid_scan: null argument");
+    if (g->finished) return fail(PF_ERR_STATE, "pf_plotgrid_scan: after pf_plotgrid_finish");
+    HIPCHK(hipSetDevice(g->device));
     *consumed = 0;
     uint64_t n = nbytes;
     while (n && text[n - 1] != '\n') n--;
     *consumed = n;
     if (!n) return PF_OK;
-    if (n >= ((uint64_t)1 << 32)) return rf_fail(PF_ERR_ARG, "pf_plotgrid_scan: a block of 4 GiB or more");
+    if (n >= ((uint64_t)1 << 32)) return fail(PF_ERR_ARG, "pf_plotgrid_scan: a block of 4 GiB or more");
     // every row needs max_col tabs and a newline: at most this many rows pass
     const uint64_t rows = n / ((uint64_t)g->max_col + 1) + 1;
     const size_t padded = (n + 15) / 16 * 16 + 16;
-    if (padded > g->text_cap) {
-        if (g->d_text) (void)hipFree(g->d_text);
-        if (g->pin) (void)hipHostFree(g->pin);
-        g->d_text = nullptr; g->pin = nullptr; g->text_cap = 0;
-        const size_t want = padded + padded / 8;
-        RFCHK(hipMalloc((void**)&g->d_text, want));
-        RFCHK(hipHostMalloc((void**)&g->pin, want, hipHostMallocDefault));
-        g->text_cap = want;
-    }
-    if (rows > g->chk_cap) {
-        if (g->d_chk) (void)hipFree(g->d_chk);
-        g->d_chk = nullptr; g->chk_cap = 0;
-        RFCHK(hipMalloc((void**)&g->d_chk, rows * sizeof(PgCheck)));
-        g->chk_cap = rows;
-    }
-    if (g->n_rec + rows > g->rec_cap) {
+    if (padded > g->d_text.cap) PFCHK(g->d_text.ensure(padded + padded / 8, true));
+    if (padded > g->pin.cap) PFCHK(g->pin.ensure(padded + padded / 8, true));
+    PFCHK(g->d_chk.ensure(rows * sizeof(PgCheck), true));
+    if (g->n_rec + rows > g->d_rec.cap / sizeof(PgRecord)) {
         const uint64_t want = std::max<uint64_t>((g->n_rec + rows) * 3 / 2, 1 << 16);
-        PgRecord* r = nullptr;
-        RFCHK(hipMalloc((void**)&r, want * sizeof(PgRecord)));
-        if (g->n_rec) RFCHK(hipMemcpyAsync(r, g->d_rec, g->n_rec * sizeof(PgRecord), hipMemcpyDeviceToDevice, g->stream));
-        RFCHK(hipStreamSynchronize(g->stream));
-        if (g->d_rec) (void)hipFree(g->d_rec);
-        g->d_rec = r;
-        g->rec_cap = want;
+        DevBuf r;
+        PFCHK(r.ensure(want * sizeof(PgRecord), true));
+        if (g->n_rec) HIPCHK(hipMemcpyAsync(r.p, g->d_rec.p, g->n_rec * sizeof(PgRecord), hipMemcpyDeviceToDevice, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+        std::swap(g->d_rec, r);                 // (the old records go at the end of this block)
     }
     if (int rc = pg_tab_reserve(g, g->cl, rows, n, 0)) return rc;
     if (int rc = pg_tab_reserve(g, g->pv, rows, n, 1)) return rc;
     {
+        char* const pin = g->pin.as<char>();
         const unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(8, n >> 22));
         std::vector<std::thread> th;
         const uint64_t step = (n + nt - 1) / nt;
         for (unsigned t = 1; t < nt; t++) {
             const uint64_t a = t * step, b = std::min<uint64_t>(n, a + step);
-            if (a < b) th.emplace_back([=] { memcpy(g->pin + a, text + a, (size_t)(b - a)); });
+            if (a < b) th.emplace_back([=] { memcpy(pin + a, text + a, (size_t)(b - a)); });
         }
-        memcpy(g->pin, text, (size_t)std::min<uint64_t>(n, step));
+        memcpy(pin, text, (size_t)std::min<uint64_t>(n, step));
         for (auto& t : th) t.join();
+        memset(pin + n, 0, padded - n);
     }
-    memset(g->pin + n, 0, padded - n);
-    RFCHK(hipMemcpyAsync(g->d_text, g->pin, padded, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(g->d_text.p, g->pin.p, padded, hipMemcpyHostToDevice, g->stream));
+    unsigned long long* const d_ctr = g->d_ctr.as<ull>();
     unsigned long long ctr[4] = {g->n_rec, 0, 0, 0};
-    RFCHK(hipMemcpyAsync(g->d_ctr, ctr, 3 * 8, hipMemcpyHostToDevice, g->stream));   // records continue; checks, lines restart
+    HIPCHK(hipMemcpyAsync(d_ctr, ctr, 3 * 8, hipMemcpyHostToDevice, g->stream));   // records continue; checks, lines restart
     PgScanParams p{};
-    p.text = g->d_text; p.n = n;
+    p.text = g->d_text.as<unsigned char>(); p.n = n;
     for (int q = 0; q < 6; q++) p.col[q] = g->col[q];
     p.max_col = g->max_col;
-    p.strain_hash = g->d_strain_hash; p.strain_id = g->d_strain_id; p.strain_cap = g->strain_cap;
-    p.strain_bytes = g->d_strain_bytes; p.strain_str = g->d_strain_str;
+    p.strain_hash = g->d_strain_hash.as<ull>(); p.strain_id = g->d_strain_id.as<uint32_t>(); p.strain_cap = g->strain_cap;
+    p.strain_bytes = g->d_strain_bytes.as<unsigned char>(); p.strain_str = g->d_strain_str.as<uint64_t>();
     p.clusters = pg_view(g->cl); p.pvalues = pg_view(g->pv);
     p.zoom = g->zoom; p.start = g->start; p.stop = g->stop;
-    p.rec = g->d_rec; p.n_rec = g->d_ctr; p.chk = g->d_chk; p.n_chk = g->d_ctr + 1; p.n_lines = g->d_ctr + 2;
-    p.err = (unsigned int*)(g->d_ctr + 3);
-    RFCHK(hipEventRecord(g->e0, g->stream));
+    p.rec = g->d_rec.as<PgRecord>(); p.n_rec = d_ctr; p.chk = g->d_chk.as<PgCheck>(); p.n_chk = d_ctr + 1; p.n_lines = d_ctr + 2;
+    p.err = (unsigned int*)(d_ctr + 3);
+    HIPCHK(hipEventRecord(g->e0, g->stream));
     hipLaunchKernelGGL(pg_scan_kernel, dim3(pg_blocks((n + 15) / 16)), dim3(256), 0, g->stream, p);
-    RFCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     unsigned long long n_chk = 0;
-    RFCHK(hipMemcpyAsync(&n_chk, g->d_ctr + 1, 8, hipMemcpyDeviceToHost, g->stream));
-    RFCHK(hipStreamSynchronize(g->stream));
+    HIPCHK(hipMemcpyAsync(&n_chk, d_ctr + 1, 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
     if (n_chk) {
-        hipLaunchKernelGGL(pg_check_kernel, dim3(pg_blocks(n_chk)), dim3(256), 0, g->stream, (const unsigned char*)g->d_text,
-                           (const PgCheck*)g->d_chk, (uint64_t)n_chk, pg_view(g->cl), pg_view(g->pv), (unsigned int*)(g->d_ctr + 3));
-        RFCHK(hipGetLastError());
+        hipLaunchKernelGGL(pg_check_kernel, dim3(pg_blocks(n_chk)), dim3(256), 0, g->stream, g->d_text.as<const unsigned char>(),
+                           g->d_chk.as<const PgCheck>(), (uint64_t)n_chk, pg_view(g->cl), pg_view(g->pv), (unsigned int*)(d_ctr + 3));
+        HIPCHK(hipGetLastError());
     }
-    RFCHK(hipEventRecord(g->e1, g->stream));
-    RFCHK(hipMemcpyAsync(ctr, g->d_ctr, 4 * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipEventRecord(g->e1, g->stream));
+    HIPCHK(hipMemcpyAsync(ctr, d_ctr, 4 * 8, hipMemcpyDeviceToHost, g->stream));
     unsigned long long tc[2][2];
-    RFCHK(hipMemcpyAsync(tc[0], g->cl.ctr, 16, hipMemcpyDeviceToHost, g->stream));
-    RFCHK(hipMemcpyAsync(tc[1], g->pv.ctr, 16, hipMemcpyDeviceToHost, g->stream));
-    RFCHK(hipStreamSynchronize(g->stream));
+    HIPCHK(hipMemcpyAsync(tc[0], g->cl.ctr.p, 16, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(tc[1], g->pv.ctr.p, 16, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
     float ms = 0;
     if (hipEventElapsedTime(&ms, g->e0, g->e1) == hipSuccess) g->device_ms += ms;
     g->cl.used = tc[0][0]; g->cl.count = tc[0][1];
@@ -899,41 +827,39 @@ int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t
     g->bytes_scanned += n;
     const unsigned err = (unsigned)(ctr[3] & 0xFFFFFFFFu);
     if (err & (PG_ERR_CLUSTER | PG_ERR_PVALUE))
-        return rf_fail(PF_ERR_CAPACITY, "pf_plotgrid_scan: two different cluster names or p-value texts share a 64-bit hash");
-    if (err & PG_ERR_LONG) return rf_fail(PF_ERR_ARG, "pf_plotgrid_scan: a cluster name or p-value field over 4095 bytes");
-    if (err & PG_ERR_RANGE) return rf_fail(PF_ERR_ARG, "pf_plotgrid_scan: a gene_start outside the 32-bit range");
+        return fail(PF_ERR_CAPACITY, "pf_plotgrid_scan: two different cluster names or p-value texts share a 64-bit hash");
+    if (err & PG_ERR_LONG) return fail(PF_ERR_ARG, "pf_plotgrid_scan: a cluster name or p-value field over 4095 bytes");
+    if (err & PG_ERR_RANGE) return fail(PF_ERR_ARG, "pf_plotgrid_scan: a gene_start outside the 32-bit range");
     return PF_OK;
 }
 
 int pf_plotgrid_finish(pf_plotgrid* g, uint32_t* n_clusters, uint64_t* n_pvalues, uint64_t* n_records) {
-    if (!g || !n_clusters || !n_pvalues || !n_records) return rf_fail(PF_ERR_ARG, "pf_plotgrid_finish: null argument");
-    RFCHK(hipSetDevice(g->device));
+    if (!g || !n_clusters || !n_pvalues || !n_records) return fail(PF_ERR_ARG, "pf_plotgrid_finish: null argument");
+    HIPCHK(hipSetDevice(g->device));
     if (!g->finished) {
         if (int rc = pg_tab_list(g, g->cl, g->cl_slot, g->cl_names, g->cl_off)) return rc;
         if (int rc = pg_tab_list(g, g->pv, g->pv_slot, g->pv_texts, g->pv_off)) return rc;
         const uint64_t cap = std::max<uint64_t>(g->cl.cap, 1);
-        int *mn = nullptr, *mx = nullptr;
-        unsigned long long* cnt = nullptr;
-        RFCHK(hipMalloc((void**)&mn, cap * 4));
-        RFCHK(hipMalloc((void**)&mx, cap * 4));
-        RFCHK(hipMalloc((void**)&cnt, cap * 8));
+        DevBuf mn, mx, cnt;
+        PFCHK(mn.ensure(cap * 4, true));
+        PFCHK(mx.ensure(cap * 4, true));
+        PFCHK(cnt.ensure(cap * 8, true));
         std::vector<int> init(cap, 0x7FFFFFFF);
-        RFCHK(hipMemcpy(mn, init.data(), cap * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(mn.p, init.data(), cap * 4, hipMemcpyHostToDevice));
         init.assign(cap, (int)0x80000000);
-        RFCHK(hipMemcpy(mx, init.data(), cap * 4, hipMemcpyHostToDevice));
-        RFCHK(hipMemset(cnt, 0, cap * 8));
+        HIPCHK(hipMemcpy(mx.p, init.data(), cap * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(cnt.p, 0, cap * 8));
         if (g->n_rec) {
-            hipLaunchKernelGGL(pg_stats_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->stream, (const PgRecord*)g->d_rec,
-                               g->n_rec, mn, mx, cnt);
-            RFCHK(hipGetLastError());
-            RFCHK(hipStreamSynchronize(g->stream));
+            hipLaunchKernelGGL(pg_stats_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->stream, g->d_rec.as<const PgRecord>(),
+                               g->n_rec, mn.as<int>(), mx.as<int>(), cnt.as<ull>());
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(g->stream));
         }
         std::vector<int> hmn(cap), hmx(cap);
         std::vector<unsigned long long> hc(cap);
-        RFCHK(hipMemcpy(hmn.data(), mn, cap * 4, hipMemcpyDeviceToHost));
-        RFCHK(hipMemcpy(hmx.data(), mx, cap * 4, hipMemcpyDeviceToHost));
-        RFCHK(hipMemcpy(hc.data(), cnt, cap * 8, hipMemcpyDeviceToHost));
-        (void)hipFree(mn); (void)hipFree(mx); (void)hipFree(cnt);
+        HIPCHK(hipMemcpy(hmn.data(), mn.p, cap * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hmx.data(), mx.p, cap * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hc.data(), cnt.p, cap * 8, hipMemcpyDeviceToHost));
         g->cl_min.clear(); g->cl_max.clear(); g->cl_rows.clear();
         for (uint32_t s : g->cl_slot) {
             g->cl_min.push_back(hmn[s]);
@@ -950,47 +876,47 @@ int pf_plotgrid_finish(pf_plotgrid* g, uint32_t* n_clusters, uint64_t* n_pvalues
 
 int pf_plotgrid_clusters(pf_plotgrid* g, const char** names, const uint64_t** name_off, const int32_t** min_pos,
                          const int32_t** max_pos, const uint64_t** rows) {
-    if (!g || !names || !name_off || !min_pos || !max_pos || !rows) return rf_fail(PF_ERR_ARG, "pf_plotgrid_clusters: null argument");
-    if (!g->finished) return rf_fail(PF_ERR_STATE, "pf_plotgrid_clusters: before pf_plotgrid_finish");
+    if (!g || !names || !name_off || !min_pos || !max_pos || !rows) return fail(PF_ERR_ARG, "pf_plotgrid_clusters: null argument");
+    if (!g->finished) return fail(PF_ERR_STATE, "pf_plotgrid_clusters: before pf_plotgrid_finish");
     *names = g->cl_names.data(); *name_off = g->cl_off.data();
     *min_pos = g->cl_min.data(); *max_pos = g->cl_max.data(); *rows = g->cl_rows.data();
     return PF_OK;
 }
 
 int pf_plotgrid_pvalues(pf_plotgrid* g, const char** texts, const uint64_t** text_off) {
-    if (!g || !texts || !text_off) return rf_fail(PF_ERR_ARG, "pf_plotgrid_pvalues: null argument");
-    if (!g->finished) return rf_fail(PF_ERR_STATE, "pf_plotgrid_pvalues: before pf_plotgrid_finish");
+    if (!g || !texts || !text_off) return fail(PF_ERR_ARG, "pf_plotgrid_pvalues: null argument");
+    if (!g->finished) return fail(PF_ERR_STATE, "pf_plotgrid_pvalues: before pf_plotgrid_finish");
     *texts = g->pv_texts.data(); *text_off = g->pv_off.data();
     return PF_OK;
 }
 
 int pf_plotgrid_set_significance(pf_plotgrid* g, const uint64_t* keys) {
-    if (!g || (!keys && !g->pv_slot.empty())) return rf_fail(PF_ERR_ARG, "pf_plotgrid_set_significance: null argument");
-    if (!g->finished) return rf_fail(PF_ERR_STATE, "pf_plotgrid_set_significance: before pf_plotgrid_finish");
-    RFCHK(hipSetDevice(g->device));
+    if (!g || (!keys && !g->pv_slot.empty())) return fail(PF_ERR_ARG, "pf_plotgrid_set_significance: null argument");
+    if (!g->finished) return fail(PF_ERR_STATE, "pf_plotgrid_set_significance: before pf_plotgrid_finish");
+    HIPCHK(hipSetDevice(g->device));
     const uint64_t cap = std::max<uint64_t>(g->pv.cap, 1);
     std::vector<unsigned long long> by_slot(cap, 0);
     for (size_t i = 0; i < g->pv_slot.size(); i++) by_slot[g->pv_slot[i]] = keys[i];
-    if (!g->d_sig) RFCHK(hipMalloc((void**)&g->d_sig, cap * 8));
-    RFCHK(hipMemcpy(g->d_sig, by_slot.data(), cap * 8, hipMemcpyHostToDevice));
+    PFCHK(g->d_sig.ensure(cap * 8, true));
+    HIPCHK(hipMemcpy(g->d_sig.p, by_slot.data(), cap * 8, hipMemcpyHostToDevice));
     g->sig_set = 1;
     return PF_OK;
 }
 
 int pf_plotgrid_grids(pf_plotgrid* g, const uint32_t* ids, uint32_t n, uint64_t* key_out, uint64_t* cnt_out) {
-    if (!g || (n && (!ids || !key_out || !cnt_out))) return rf_fail(PF_ERR_ARG, "pf_plotgrid_grids: null argument");
-    if (!g->finished || !g->sig_set) return rf_fail(PF_ERR_STATE, "pf_plotgrid_grids: before pf_plotgrid_set_significance");
+    if (!g || (n && (!ids || !key_out || !cnt_out))) return fail(PF_ERR_ARG, "pf_plotgrid_grids: null argument");
+    if (!g->finished || !g->sig_set) return fail(PF_ERR_STATE, "pf_plotgrid_grids: before pf_plotgrid_set_significance");
     if (!n) return PF_OK;
-    RFCHK(hipSetDevice(g->device));
+    HIPCHK(hipSetDevice(g->device));
     const uint64_t cap = std::max<uint64_t>(g->cl.cap, 1);
     std::vector<int32_t> slot_item(cap, -1);
     std::vector<uint64_t> item(3 * (size_t)n);
     uint64_t cells = 0;
     for (uint32_t i = 0; i < n; i++) {
-        if (ids[i] >= g->cl_slot.size()) return rf_fail(PF_ERR_ARG, "pf_plotgrid_grids: no such cluster");
-        if (!g->cl_rows[ids[i]]) return rf_fail(PF_ERR_ARG, "pf_plotgrid_grids: a cluster without rows has no grid");
+        if (ids[i] >= g->cl_slot.size()) return fail(PF_ERR_ARG, "pf_plotgrid_grids: no such cluster");
+        if (!g->cl_rows[ids[i]]) return fail(PF_ERR_ARG, "pf_plotgrid_grids: a cluster without rows has no grid");
         const uint32_t s = g->cl_slot[ids[i]];
-        if (slot_item[s] >= 0) return rf_fail(PF_ERR_ARG, "pf_plotgrid_grids: a cluster twice in one call");
+        if (slot_item[s] >= 0) return fail(PF_ERR_ARG, "pf_plotgrid_grids: a cluster twice in one call");
         slot_item[s] = (int32_t)i;
         const uint64_t width = (uint64_t)((int64_t)g->cl_max[ids[i]] - g->cl_min[ids[i]] + 1);
         item[i] = cells;
@@ -998,56 +924,46 @@ int pf_plotgrid_grids(pf_plotgrid* g, const uint32_t* ids, uint32_t n, uint64_t*
         item[2 * (size_t)n + i] = width;
         cells += width * g->n_strains;
     }
-    if (cells > g->grid_cap) {
-        if (g->d_key) (void)hipFree(g->d_key);
-        if (g->d_cnt) (void)hipFree(g->d_cnt);
-        g->d_key = nullptr; g->d_cnt = nullptr; g->grid_cap = 0;
-        RFCHK(hipMalloc((void**)&g->d_key, cells * 8));
-        RFCHK(hipMalloc((void**)&g->d_cnt, cells * 8));
-        g->grid_cap = cells;
-    }
-    if (3 * (uint64_t)n > g->item_cap) {
-        if (g->d_item) (void)hipFree(g->d_item);
-        g->d_item = nullptr;
-        RFCHK(hipMalloc((void**)&g->d_item, 3 * (size_t)n * 8));
-        g->item_cap = 3 * (uint64_t)n;
-    }
-    if (!g->d_slot_item) RFCHK(hipMalloc((void**)&g->d_slot_item, cap * 4));
+    PFCHK(g->d_key.ensure(cells * 8, true));
+    PFCHK(g->d_cnt.ensure(cells * 8, true));
+    PFCHK(g->d_item.ensure(3 * (size_t)n * 8, true));
+    PFCHK(g->d_slot_item.ensure(cap * 4, true));
     // the device-side item table: off (u64), min (i32), width (u32)
     std::vector<int32_t> imin(n);
     std::vector<uint32_t> iwidth(n);
     for (uint32_t i = 0; i < n; i++) { imin[i] = (int32_t)(int64_t)item[n + i]; iwidth[i] = (uint32_t)item[2 * (size_t)n + i]; }
-    char* dit = (char*)g->d_item;
-    RFCHK(hipMemcpyAsync(dit, item.data(), (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    RFCHK(hipMemcpyAsync(dit + (size_t)n * 8, imin.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-    RFCHK(hipMemcpyAsync(dit + (size_t)n * 12, iwidth.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-    RFCHK(hipMemcpyAsync(g->d_slot_item, slot_item.data(), cap * 4, hipMemcpyHostToDevice, g->stream));
-    RFCHK(hipMemsetAsync(g->d_key, 0, cells * 8, g->stream));
-    RFCHK(hipMemsetAsync(g->d_cnt, 0, cells * 8, g->stream));
-    RFCHK(hipMemsetAsync(g->d_ctr + 3, 0, 8, g->stream));
+    char* dit = g->d_item.as<char>();
+    HIPCHK(hipMemcpyAsync(dit, item.data(), (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(dit + (size_t)n * 8, imin.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(dit + (size_t)n * 12, iwidth.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    unsigned long long* const d_err = g->d_ctr.as<ull>() + 3;
+    HIPCHK(hipMemcpyAsync(g->d_slot_item.p, slot_item.data(), cap * 4, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemsetAsync(g->d_key.p, 0, cells * 8, g->stream));
+    HIPCHK(hipMemsetAsync(g->d_cnt.p, 0, cells * 8, g->stream));
+    HIPCHK(hipMemsetAsync(d_err, 0, 8, g->stream));
     PgGridParams p{};
-    p.rec = g->d_rec; p.n = g->n_rec; p.slot_item = g->d_slot_item;
+    p.rec = g->d_rec.as<PgRecord>(); p.n = g->n_rec; p.slot_item = g->d_slot_item.as<int32_t>();
     p.item_off = (const uint64_t*)dit; p.item_min = (const int32_t*)(dit + (size_t)n * 8);
     p.item_width = (const uint32_t*)(dit + (size_t)n * 12);
-    p.n_strains = g->n_strains; p.sig_key = g->d_sig; p.key = g->d_key; p.cnt = g->d_cnt;
-    p.err = (unsigned int*)(g->d_ctr + 3);
-    RFCHK(hipEventRecord(g->e0, g->stream));
+    p.n_strains = g->n_strains; p.sig_key = g->d_sig.as<ull>(); p.key = g->d_key.as<ull>(); p.cnt = g->d_cnt.as<ull>();
+    p.err = (unsigned int*)d_err;
+    HIPCHK(hipEventRecord(g->e0, g->stream));
     hipLaunchKernelGGL(pg_grid_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->stream, p);
-    RFCHK(hipGetLastError());
-    RFCHK(hipEventRecord(g->e1, g->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(g->e1, g->stream));
     unsigned long long err = 0;
-    RFCHK(hipMemcpyAsync(key_out, g->d_key, cells * 8, hipMemcpyDeviceToHost, g->stream));
-    RFCHK(hipMemcpyAsync(cnt_out, g->d_cnt, cells * 8, hipMemcpyDeviceToHost, g->stream));
-    RFCHK(hipMemcpyAsync(&err, g->d_ctr + 3, 8, hipMemcpyDeviceToHost, g->stream));
-    RFCHK(hipStreamSynchronize(g->stream));
+    HIPCHK(hipMemcpyAsync(key_out, g->d_key.p, cells * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(cnt_out, g->d_cnt.p, cells * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
     float ms = 0;
     if (hipEventElapsedTime(&ms, g->e0, g->e1) == hipSuccess) g->device_ms += ms;
-    if (err) return rf_fail(PF_ERR_STATE, "pf_plotgrid_grids: a record outside its cluster's grid");
+    if (err) return fail(PF_ERR_STATE, "pf_plotgrid_grids: a record outside its cluster's grid");
     return PF_OK;
 }
 
 int pf_plotgrid_stats(pf_plotgrid* g, uint64_t* bytes_scanned, uint64_t* lines, uint64_t* records, float* device_ms) {
-    if (!g) return rf_fail(PF_ERR_ARG, "pf_plotgrid_stats: null argument");
+    if (!g) return fail(PF_ERR_ARG, "pf_plotgrid_stats: null argument");
     if (bytes_scanned) *bytes_scanned = g->bytes_scanned;
     if (lines) *lines = g->lines;
     if (records) *records = g->n_rec;

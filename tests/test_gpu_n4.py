@@ -134,3 +134,25 @@ def test_numeric_cluster_ids_with_an_na(tmp_path):
         "contig_end\tgene_start\tgene_end\tstrand\n7.0\tACGTA\tH1\t0.001\ts1\tg\tc\t1\t1\t6\t0\t5\t1\n")
     got, rc = _run("get_clusters", ["-a", str(tmp_path / "a.tsv"), "-p", str(tmp_path / "kh.tsv"), "-t", "0.01"])
     assert rc == 0 and sorted(got.split()) == ["7.0", "nan"]
+
+
+def test_scan_out_of_memory_fails_cleanly(tmp_path):
+    """pf_debug_limit_alloc below the scan's candidate buffer (a million positions at least): the scan fails as out of
+    memory, the filter still closes, and with the limit lifted fresh filters give the reference's output again"""
+    from panfeed_amd import _lib
+    from panfeed_amd.downstream import RowFilter
+    fx = FIX[0]
+    paths, pa = _files(tmp_path, fx)
+    run = next(r for r in fx["runs"] if r["tool"] == "get_kmers" and r["args"] == ["-t", "0.01"])
+    L = _lib.load()
+    f = RowFilter(["x"], first_field=True)
+    try:
+        _lib.check(L.pf_debug_limit_alloc(1 << 20, None))
+        with pytest.raises(_lib.PanfeedHipError) as ei:
+            f.filter_file(paths["kmers.tsv"])
+        assert ei.value.status == _lib.ERR_OOM
+        f.close()
+    finally:
+        _lib.check(L.pf_debug_limit_alloc(0, None))
+    got, rc = _run("get_kmers", ["-a", pa, "-p", paths["kmers_to_hashes.tsv"], "-k", paths["kmers.tsv"], "-t", "0.01"])
+    assert rc == 0 and got == run["stdout"]

@@ -212,3 +212,25 @@ def test_one_cluster_of_8192_strains_by_20000_positions(tmp_path):
         assert np.array_equal(count, exp)
     finally:
         gb.close()
+
+
+def test_scan_out_of_memory_fails_cleanly(tmp_path):
+    """pf_debug_limit_alloc below the scan's record buffer (65 536 records at least): the scan fails as out of memory,
+    the grid builder still closes, and with the limit lifted a fresh one gives the reference's arrays again"""
+    from panfeed_amd import _lib
+    from panfeed_amd.plot import GridBuilder, table_columns
+    name, i = RUNS[0]
+    fx = next(f for f in FIX if f["name"] == name)
+    run = fx["runs"][i]
+    pk, pp = _write(tmp_path, fx)
+    L = _lib.load()
+    gb = GridBuilder(["x"], table_columns(pk, _kwargs(run["args"])["column"]))
+    try:
+        _lib.check(L.pf_debug_limit_alloc(256 << 10, None))
+        with pytest.raises(_lib.PanfeedHipError) as ei:
+            gb.scan_file(pk)
+        assert ei.value.status == _lib.ERR_OOM
+        gb.close()
+    finally:
+        _lib.check(L.pf_debug_limit_alloc(0, None))
+    _compare(_figures(pk, pp, run["args"]), run)
