@@ -44,7 +44,51 @@ struct Arena {
     uint64_t used = 0;
 };
 
-struct EvPair { hipEvent_t a, b; int cat; };
+// what a timed stretch of the stream counts towards (pf_timing); the extra-row fill counts as emit
+enum class TimeCat { scan, rows, emit, dedup, pattern_rows, md5, finish };
+
+struct EvPair { hipEvent_t a, b; TimeCat cat; };
+
+// What this context has seen of its clusters of many distinct sequences: g = new k-mers per further sequence against
+// L = windows of one sequence, as running sums for the line g = a + b L (related alleles: a few tens whatever L is;
+// SURVEY 8d's: flanks + a share of L) -- see the key-partition estimate (first_nparts)
+struct PartModel {
+    double n = 0, x = 0, y = 0, xx = 0, xy = 0, yy = 0;
+    struct Fit { double a = 0.0, b = 0.0, half_sd = 0.0; bool ready = false; };
+    void add(double L, double g) { n += 1; x += L; y += g; xx += L * L; xy += L * g; yy += g * g; }
+    void halve() { n *= 0.5; x *= 0.5; y *= 0.5; xx *= 0.5; xy *= 0.5; yy *= 0.5; }
+    Fit fit() const {
+        Fit f{0.0, 0.0, 0.0, n >= 16};
+        if (!f.ready) return f;
+        const double den = n * xx - x * x;
+        f.a = y / n;
+        if (den > 1e-6 * n * xx) { f.b = (n * xy - x * y) / den; f.a = (y - f.b * x) / n; }
+        const double ss = std::max(0.0, yy - f.a * y - f.b * xy);     // residual sum of squares
+        // (half a residual standard deviation on top: with `room` at 0.9 of the table's limit that left no
+        // cluster of the headline workload, with or without 'N's, to overflow; 0 left 6, 1 to 3 standard
+        // deviations cost 0.5 % to 5 % in surplus partitions -- profiles/r02/partition_margin_experiment.txt)
+        f.half_sd = 0.5 * std::sqrt(ss / std::max(1.0, n - 2.0));
+        return f;
+    }
+};
+
+// host scratch of pf_submit, kept between calls (capacity persists: no allocation / page faults in steady state)
+struct SubmitScratch {
+    std::vector<Item> items;             // the work items of a pass
+    std::vector<uint8_t> fused;          // per item: 0 general path; 1 / 2 / 5 one item, fused small / large / huge class;
+                                         // 3 the first of several partitions (fused large class), 4 the others
+    // the item columns that go up (Item's fields, plus compact = fused at all, binned = its cluster's windows are binned)
+    std::vector<uint32_t> it_cluster, it_part, it_nparts, it_nslots, it_slice, it_sib0, it_nsib, it_extra_first,
+        it_is_extra, it_compact, it_binned;
+    // the work lists of the pass's sub-batches, concatenated
+    std::vector<uint32_t> w_scan, w_extra, w_fin, w_fin2, w_fin3, w_fin5, w_rows;
+    // the general path's clusters, per sub-batch: cluster, first item, items
+    std::vector<uint32_t> sub_cluster, sub_item0, sub_nitems;
+    // the binned clusters: cluster, first item, partitions, first queue entry; the four as one upload block
+    std::vector<uint32_t> bin_cluster, bin_item0, bin_nparts, bin_base, bin_block;
+    std::vector<uint32_t> wide;          // a part's clusters for the wide dedup class
+    std::vector<uint32_t> count, plan;   // key counts read back for the key-partition estimate (host items, plan_kernel's)
+};
 
 }  // namespace
 
@@ -61,12 +105,8 @@ struct pf_ctx {
     // pattern table + pool
     pf::PatternTable pt{};
     DevBuf pt_lo, pt_val, pt_first, pt_counters, pat_bits, pat_nan, pat_n, pat_md5;
-    // what this context has seen of its clusters of many distinct sequences: g = new k-mers per further sequence against
-    // L = windows of one sequence, as running sums for the line g = a + b L (related alleles: a few tens whatever L is;
-    // SURVEY 8d's: flanks + a share of L) -- see the key-partition estimate
-    double reg_n = 0, reg_x = 0, reg_y = 0, reg_xx = 0, reg_xy = 0, reg_yy = 0;
+    PartModel part_model;
     uint64_t n_submits = 0;
-    std::vector<uint32_t> hs_count, hs_plan;
     uint32_t n_patterns = 0;       // patterns allocated after the last submit
     uint32_t pid0 = 0;             // first pattern id of the last submit
     // scratch slices
@@ -122,13 +162,9 @@ struct pf_ctx {
     DevBuf g_store, b_literal, g_src_off, g_src_start, g_src_flags;   // genomes resident in HBM + per-batch gather lists
     uint64_t g_words = 0;
     const pf_gather* pending_gather = nullptr;
-    // host scratch of pf_submit, kept between calls (capacity persists: no allocation / page faults in steady state)
-    std::vector<Item> hs_items;
-    std::vector<uint8_t> hs_fused;
-    std::vector<uint32_t> hs_v[10], hs_w[7], hs_sub[3];
+    SubmitScratch hs;
     int n_cu = 256;
     DevBuf it_binned, bin_lists, q_key, q_ord, q_bit, q_off;      // key-partition queues of binned clusters (bin_kernel)
-    std::vector<uint32_t> hs_binned, hs_bin[4];
     DevBuf it_cluster, it_part, it_nparts, it_nslots, it_slice, it_sib0, it_nsib, it_extra_first, it_count,
         it_unique, it_kept, work_scan, work_extra, work_fin, work_fin2, work_fin3, work_fin5, work_rows, sub_cluster, sub_item0, sub_nitems;
     std::vector<std::unique_ptr<Arena>> arenas;
@@ -200,7 +236,7 @@ int get_event(pf_ctx* c, hipEvent_t* ev) {
 }
 // a timed stretch of one category on `s` (the context's stream unless the launches go to the side stream); the pairs are
 // read after the batch's last synchronisation, when both streams have drained
-int mark_begin(pf_ctx* c, int cat, hipStream_t s = nullptr) {
+int mark_begin(pf_ctx* c, TimeCat cat, hipStream_t s = nullptr) {
     EvPair e; e.cat = cat;
     PFCHK(get_event(c, &e.a));
     PFCHK(get_event(c, &e.b));
@@ -673,266 +709,199 @@ void pf_b64_digest(const uint8_t d[16], char out[24]) {
 namespace {
 constexpr int PF_RETRY_PATTERNS = 1;   // internal: the batch ran out of pattern ids, *need = ids it asked for
 
-int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* counters, uint64_t* need, bool rerun) {
-    c->have_batch = false;
-    kt_stream_end(c);                     // a kmers.tsv stream of the batch before is over
-    // whatever way this call ends, nothing it queued is still reading the caller's arrays or the pinned staging
-    // blocks afterwards (the successful path has waited already; an error return may come with work in flight)
-    struct Drain { hipStream_t s, s2; ~Drain() { (void)hipStreamSynchronize(s2); (void)hipStreamSynchronize(s); } } drain{c->stream, c->side};
-    const uint32_t C = b->n_clusters, NSEG = b->n_segs, W = c->W, NS = c->NS, KW = (uint32_t)c->KW;
-    if (b->n_segs && (!b->packed || !b->seg_word_off || !b->seg_len || !b->seg_sample || !b->seg_ord_base))
-        return fail(PF_ERR_ARG, "segment arrays missing");
-    if (C && (!b->cluster_seg_off || !b->cluster_nstrains || !b->cluster_npresab || !b->cluster_presab ||
-              !b->cluster_ordinal))
-        return fail(PF_ERR_ARG, "cluster arrays missing");
-    if (b->n_extra && (!b->extra_cluster || !b->extra_ord || !b->extra_bits))
-        return fail(PF_ERR_ARG, "extra arrays missing");
-    for (auto& e : c->events) { c->ev_pool.push_back(e.a); c->ev_pool.push_back(e.b); }
-    c->events.clear();
-    c->timing = pf_timing{};
+// A cluster of three or more key partitions (a dedup view, keys of up to two words) has its windows sorted by
+// partition first (bin_kernel): its items then read their own windows instead of each walking the whole view.
+// The entry arrays belong to a sub-batch; a sub-batch ends where they would pass BIN_MAX_ENTRIES.
+constexpr uint32_t BIN_MIN_PARTS = 3;      // (at two, a cluster's own bin_kernel workgroup takes longer than the second walk it saves)
+constexpr uint64_t BIN_MAX_ENTRIES = 1ull << 28;
+
+// plan_kernel's output block of a part: item arrays, work lists, unit-view list, the scan's block sums
+struct DPtrs { uint32_t *it_cluster, *it_nslots, *w_scan, *w_fin, *w_fin2, *w_fin5, *unit_cluster, *unit_base, *blk; };
+DPtrs dplan_ptrs(const pf_ctx::DPlan& plan) {
+    uint32_t* b = plan.block.as<uint32_t>();
+    const size_t n = plan.n;
+    return DPtrs{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, b + 6 * n, b + 7 * n, b + 8 * n};
+}
+// a pass's item arrays as the scan and the fused finish kernels read them
+struct ItemPtrs { const uint32_t *cluster, *part, *nparts, *nslots, *slice, *compact, *binned; uint32_t* count; };
+struct FinWork { const uint32_t* work; uint32_t n; };   // one class of the fused finish kernels in a launch
+// a host-planned pass: its sub-batches (one launch each) and their stretches of the work lists (off[s] to off[s + 1])
+struct Sub { uint32_t item0, nitems, cl0, ncl, pool, bin0, nbin; uint64_t q_total; };
+struct SubLists { uint32_t scan, extra, fin, fin2, fin3, fin5, rows; };
+struct Pass { std::vector<Sub> subs; std::vector<SubLists> off; uint64_t arena_cap = 0; size_t NB = 0; };
+
+// What one submit_once call carries from stage to stage (what outlives the call is in pf_ctx).  The member functions
+// are the stages and their shared launches, in the order a batch meets them.
+struct SubmitRun {
+    pf_ctx* c; const pf_batch* b; const pf_gather* gth;
+    pf_batch d;                            // the batch as device pointers
+    const uint32_t C, NSEG, W, NS, KW;
+    const uint64_t mult;                   // a window's instances: both strands unless canonical
+    uint32_t P = 1, part_end[pf_ctx::MAX_PARTS] = {};   // part h: clusters [part_end[h - 1], part_end[h])
+    pf::ClusterRec* rec = nullptr;         // the dedup pass's record per cluster, in pinned memory
+    uint32_t* h_exfirst = nullptr;         // [C + 1] + the "bad list" flag, in pinned memory (device-side CSR only)
+    bool ex_on_device = false; std::vector<uint32_t> ex_first;     // extras per cluster (CSR)
+    std::vector<uint32_t> nparts, todo;    // key partitions per cluster; the clusters of the pass being built
+    pf::DedupParams dp{};
+    bool use_plan = false; pf::PlanClassify pcls{};   // what cluster_ninst_kernel works out per cluster for plan_kernel
+    double share = 0.0; PartModel::Fit fit;           // the key-partition estimate (first_nparts) and the line it learned
+    struct Deferred { Arena* ar; uint32_t pin; }; std::vector<Deferred> deferred;   // passes not yet waited for (read-backs queued)
+    uint64_t arena_base = 0; uint32_t arena_i = 0;    // arenas used so far: one per launched pass, the device-planned ones included
+    Arena* ar = nullptr;                   // the arena of the pass being launched
+    uint32_t cnt2[3] = {0, 0, 0};          // pattern counters {ids handed out, pool overflow, arena overflow}
+    uint64_t total_inst = 0;
     const bool dbg = getenv("PF_DEBUG_TIMING") != nullptr;
-    auto t_host0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
+    std::chrono::steady_clock::time_point t_host0 = std::chrono::steady_clock::now();
+
+    SubmitRun(pf_ctx* c_, const pf_batch* b_, const pf_gather* g_)
+        : c(c_), b(b_), gth(g_), d(*b_), C(b_->n_clusters), NSEG(b_->n_segs), W(c_->W), NS(c_->NS), KW((uint32_t)c_->KW), mult(c_->o.canon ? 1 : 2) {}
+    void lap(const char* what) {
         if (!dbg) return;
         auto t = std::chrono::steady_clock::now();
         fprintf(stderr, "[pf_submit] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_host0).count());
         t_host0 = t;
-    };
-    HIPCHK(hipEventRecord(c->ev_t0, c->stream));
+    }
+    uint32_t part_begin(uint32_t h) const { return h ? part_end[h - 1] : 0; }
 
     // ---- batch arrays on the device
-    pf_batch d = *b;
-    std::vector<uint32_t> h_extra_cluster;
-    if (gth && b->on_device) return fail(PF_ERR_ARG, "pf_submit_gather takes host arrays");
-    const uint64_t total_words = gth ? gth->n_words : b->n_words;
-    if (!b->on_device) {
-        // validate what the kernels index with (host copies are at hand)
-        for (uint32_t i = 0; i < C; i++) {
-            if (b->cluster_seg_off[i] > b->cluster_seg_off[i + 1] || b->cluster_seg_off[i + 1] > NSEG)
-                return fail(PF_ERR_ARG, "cluster_seg_off not monotone / out of range at %u", i);
-            if (b->cluster_nstrains[i] > c->o.max_strains || b->cluster_npresab[i] > c->o.max_strains)
-                return fail(PF_ERR_ARG, "cluster %u has more strains than max_strains", i);
-            // init_presabs_vector, panfeed.py:19: a boolean mask must have the vector's length (numpy IndexError)
-            if (c->o.consider_missing && b->cluster_nstrains[i] != b->cluster_npresab[i])
-                return fail(PF_ERR_ARG, "cluster %u: consider_missing needs len(clusterpresab) == number of strains "
-                            "(%u != %u)", i, b->cluster_npresab[i], b->cluster_nstrains[i]);
-        }
-        if (C && b->cluster_seg_off[0] != 0) return fail(PF_ERR_ARG, "cluster_seg_off[0] must be 0");
-        const uint32_t pad_words = KW <= 2 ? 2u : 4u;     // a lane reads KW + 1 words from its window's first word
-        for (uint32_t s = 0; s < NSEG; s++) {
-            const uint64_t nw = 2ull * ((b->seg_len[s] + 63) / 64);
-            if ((b->seg_word_off[s] & 1) || b->seg_word_off[s] + nw + pad_words > total_words)
-                return fail(PF_ERR_ARG, "segment %u: misaligned or outside packed[] (needs %u words of tail padding)", s, pad_words);
-        }
-        for (uint32_t i = 0; i < C; i++)
-            for (uint32_t s = b->cluster_seg_off[i]; s < b->cluster_seg_off[i + 1]; s++) {
-                if (b->seg_sample[s] >= b->cluster_nstrains[i])
-                    return fail(PF_ERR_ARG, "segment %u: sample column %u >= n_strains %u", s, b->seg_sample[s],
-                                b->cluster_nstrains[i]);
-                if (s > b->cluster_seg_off[i] && b->seg_sample[s] < b->seg_sample[s - 1])
-                    return fail(PF_ERR_ARG, "segments of cluster %u are not sorted by sample", i);
+    int upload_batch() {
+        std::vector<uint32_t> h_extra_cluster;
+        if (gth && b->on_device) return fail(PF_ERR_ARG, "pf_submit_gather takes host arrays");
+        const uint64_t total_words = gth ? gth->n_words : b->n_words;
+        if (!b->on_device) {
+            // validate what the kernels index with (host copies are at hand)
+            for (uint32_t i = 0; i < C; i++) {
+                if (b->cluster_seg_off[i] > b->cluster_seg_off[i + 1] || b->cluster_seg_off[i + 1] > NSEG)
+                    return fail(PF_ERR_ARG, "cluster_seg_off not monotone / out of range at %u", i);
+                if (b->cluster_nstrains[i] > c->o.max_strains || b->cluster_npresab[i] > c->o.max_strains)
+                    return fail(PF_ERR_ARG, "cluster %u has more strains than max_strains", i);
+                // init_presabs_vector, panfeed.py:19: a boolean mask must have the vector's length (numpy IndexError)
+                if (c->o.consider_missing && b->cluster_nstrains[i] != b->cluster_npresab[i])
+                    return fail(PF_ERR_ARG, "cluster %u: consider_missing needs len(clusterpresab) == number of strains "
+                                "(%u != %u)", i, b->cluster_npresab[i], b->cluster_nstrains[i]);
             }
-        if (!gth) PFCHK(upload(c, c->b_packed, b->packed, (size_t)b->n_words, &d.packed));
-        PFCHK(upload(c, c->b_seg_word_off, b->seg_word_off, NSEG, &d.seg_word_off));
-        PFCHK(upload(c, c->b_seg_len, b->seg_len, NSEG, &d.seg_len));
-        if (gth) {
-            // the packed input is produced on the device: segments copied (or reverse-complemented) out of the
-            // resident genomes, plus the few the host packed itself (b->packed = the literal words)
-            if (NSEG && (!gth->src_off || !gth->src_start || !gth->src_flags)) return fail(PF_ERR_ARG, "gather arrays missing");
+            if (C && b->cluster_seg_off[0] != 0) return fail(PF_ERR_ARG, "cluster_seg_off[0] must be 0");
+            const uint32_t pad_words = KW <= 2 ? 2u : 4u;     // a lane reads KW + 1 words from its window's first word
             for (uint32_t s = 0; s < NSEG; s++) {
                 const uint64_t nw = 2ull * ((b->seg_len[s] + 63) / 64);
-                const uint64_t last = (uint64_t)gth->src_start[s] + b->seg_len[s];         // bases
-                if (gth->src_flags[s] & 1u) {
-                    if (gth->src_off[s] + nw + 1 > b->n_words || gth->src_start[s] != 0 || (gth->src_flags[s] & 2u))
-                        return fail(PF_ERR_ARG, "segment %u: literal source outside packed[]", s);
-                } else if (gth->src_off[s] + (last + 31) / 32 + 1 > c->g_words) {
-                    return fail(PF_ERR_ARG, "segment %u: source range outside the resident genomes", s);
+                if ((b->seg_word_off[s] & 1) || b->seg_word_off[s] + nw + pad_words > total_words)
+                    return fail(PF_ERR_ARG, "segment %u: misaligned or outside packed[] (needs %u words of tail padding)", s, pad_words);
+            }
+            for (uint32_t i = 0; i < C; i++)
+                for (uint32_t s = b->cluster_seg_off[i]; s < b->cluster_seg_off[i + 1]; s++) {
+                    if (b->seg_sample[s] >= b->cluster_nstrains[i])
+                        return fail(PF_ERR_ARG, "segment %u: sample column %u >= n_strains %u", s, b->seg_sample[s],
+                                    b->cluster_nstrains[i]);
+                    if (s > b->cluster_seg_off[i] && b->seg_sample[s] < b->seg_sample[s - 1])
+                        return fail(PF_ERR_ARG, "segments of cluster %u are not sorted by sample", i);
+                }
+            if (!gth) PFCHK(upload(c, c->b_packed, b->packed, (size_t)b->n_words, &d.packed));
+            PFCHK(upload(c, c->b_seg_word_off, b->seg_word_off, NSEG, &d.seg_word_off));
+            PFCHK(upload(c, c->b_seg_len, b->seg_len, NSEG, &d.seg_len));
+            if (gth) {
+                // the packed input is produced on the device: segments copied (or reverse-complemented) out of the
+                // resident genomes, plus the few the host packed itself (b->packed = the literal words)
+                if (NSEG && (!gth->src_off || !gth->src_start || !gth->src_flags)) return fail(PF_ERR_ARG, "gather arrays missing");
+                for (uint32_t s = 0; s < NSEG; s++) {
+                    const uint64_t nw = 2ull * ((b->seg_len[s] + 63) / 64);
+                    const uint64_t last = (uint64_t)gth->src_start[s] + b->seg_len[s];         // bases
+                    if (gth->src_flags[s] & 1u) {
+                        if (gth->src_off[s] + nw + 1 > b->n_words || gth->src_start[s] != 0 || (gth->src_flags[s] & 2u))
+                            return fail(PF_ERR_ARG, "segment %u: literal source outside packed[]", s);
+                    } else if (gth->src_off[s] + (last + 31) / 32 + 1 > c->g_words) {
+                        return fail(PF_ERR_ARG, "segment %u: source range outside the resident genomes", s);
+                    }
+                }
+                PFCHK(c->b_packed.ensure((size_t)std::max<uint64_t>(total_words, 4) * 8));
+                d.packed = c->b_packed.as<uint64_t>();
+                const uint64_t* lit; const uint64_t* so; const uint32_t* ss; const uint32_t* sf;
+                PFCHK(upload(c, c->b_literal, b->packed, (size_t)b->n_words, &lit));
+                PFCHK(upload(c, c->g_src_off, gth->src_off, NSEG, &so));
+                PFCHK(upload(c, c->g_src_start, gth->src_start, NSEG, &ss));
+                PFCHK(upload(c, c->g_src_flags, gth->src_flags, NSEG, &sf));
+                if (total_words >= 4)
+                    HIPCHK(hipMemsetAsync(c->b_packed.as<uint64_t>() + (total_words - 4), 0, 32, c->stream));
+                if (NSEG) {
+                    pf::GatherParams gp{};
+                    gp.store = c->g_store.as<uint64_t>(); gp.literal = lit; gp.src_off = so; gp.src_start = ss; gp.src_flags = sf;
+                    gp.seg_word_off = d.seg_word_off; gp.seg_len = d.seg_len; gp.packed = c->b_packed.as<uint64_t>(); gp.n_segs = NSEG;
+                    hipLaunchKernelGGL(pf::gather_segments_kernel, dim3((NSEG + 15) / 16), dim3(256), 0, c->stream, gp);
+                    HIPCHK(hipGetLastError());
                 }
             }
-            PFCHK(c->b_packed.ensure((size_t)std::max<uint64_t>(total_words, 4) * 8));
-            d.packed = c->b_packed.as<uint64_t>();
-            const uint64_t* lit; const uint64_t* so; const uint32_t* ss; const uint32_t* sf;
-            PFCHK(upload(c, c->b_literal, b->packed, (size_t)b->n_words, &lit));
-            PFCHK(upload(c, c->g_src_off, gth->src_off, NSEG, &so));
-            PFCHK(upload(c, c->g_src_start, gth->src_start, NSEG, &ss));
-            PFCHK(upload(c, c->g_src_flags, gth->src_flags, NSEG, &sf));
-            if (total_words >= 4)
-                HIPCHK(hipMemsetAsync(c->b_packed.as<uint64_t>() + (total_words - 4), 0, 32, c->stream));
-            if (NSEG) {
-                pf::GatherParams gp{};
-                gp.store = c->g_store.as<uint64_t>(); gp.literal = lit; gp.src_off = so; gp.src_start = ss; gp.src_flags = sf;
-                gp.seg_word_off = d.seg_word_off; gp.seg_len = d.seg_len; gp.packed = c->b_packed.as<uint64_t>(); gp.n_segs = NSEG;
-                hipLaunchKernelGGL(pf::gather_segments_kernel, dim3((NSEG + 15) / 16), dim3(256), 0, c->stream, gp);
-                HIPCHK(hipGetLastError());
+            PFCHK(upload(c, c->b_seg_sample, b->seg_sample, NSEG, &d.seg_sample));
+            PFCHK(upload(c, c->b_seg_ord, b->seg_ord_base, NSEG, &d.seg_ord_base));
+            PFCHK(upload(c, c->b_cl_seg_off, b->cluster_seg_off, (size_t)C + 1, &d.cluster_seg_off));
+            PFCHK(upload(c, c->b_cl_nstr, b->cluster_nstrains, C, &d.cluster_nstrains));
+            PFCHK(upload(c, c->b_cl_npres, b->cluster_npresab, C, &d.cluster_npresab));
+            PFCHK(upload(c, c->b_cl_presab, b->cluster_presab, (size_t)C * W, &d.cluster_presab));
+            PFCHK(upload(c, c->b_cl_ordinal, b->cluster_ordinal, C, &d.cluster_ordinal));
+            PFCHK(upload(c, c->b_extra_ord, b->extra_ord, b->n_extra, &d.extra_ord));
+            PFCHK(upload(c, c->b_extra_bits, b->extra_bits, (size_t)b->n_extra * W, &d.extra_bits));
+            if (b->seg_strand_off) PFCHK(upload(c, c->b_seg_strand_off, b->seg_strand_off, NSEG, &d.seg_strand_off));
+            if (b->n_extra) h_extra_cluster.assign(b->extra_cluster, b->extra_cluster + b->n_extra);
+        }
+        // extras per cluster (CSR).  A batch that is in device memory already has its list checked and counted there
+        // (extra_csr_kernel); the counts come back with the first dedup results -- reading the list back and walking it here
+        // was 1 ms in front of the first kernel with SURVEY 8d's share of 'N's (1.5 M rows per 50 000 clusters).
+        ex_on_device = b->on_device && b->n_extra;
+        if (ex_on_device && !C) return fail(PF_ERR_ARG, "extra_cluster must be non-decreasing and < n_clusters");
+        ex_first.assign((size_t)C + 1, 0);
+        if (!ex_on_device) {
+            for (uint32_t e = 0; e < b->n_extra; e++) {
+                if (h_extra_cluster[e] >= C || (e && h_extra_cluster[e] < h_extra_cluster[e - 1]))
+                    return fail(PF_ERR_ARG, "extra_cluster must be non-decreasing and < n_clusters");
             }
+            for (uint32_t e = 0; e < b->n_extra; e++) ex_first[h_extra_cluster[e] + 1]++;
+            for (uint32_t i = 0; i < C; i++) ex_first[i + 1] += ex_first[i];
+            PFCHK(upload_vec(c, c->extra_off, ex_first));
         }
-        PFCHK(upload(c, c->b_seg_sample, b->seg_sample, NSEG, &d.seg_sample));
-        PFCHK(upload(c, c->b_seg_ord, b->seg_ord_base, NSEG, &d.seg_ord_base));
-        PFCHK(upload(c, c->b_cl_seg_off, b->cluster_seg_off, (size_t)C + 1, &d.cluster_seg_off));
-        PFCHK(upload(c, c->b_cl_nstr, b->cluster_nstrains, C, &d.cluster_nstrains));
-        PFCHK(upload(c, c->b_cl_npres, b->cluster_npresab, C, &d.cluster_npresab));
-        PFCHK(upload(c, c->b_cl_presab, b->cluster_presab, (size_t)C * W, &d.cluster_presab));
-        PFCHK(upload(c, c->b_cl_ordinal, b->cluster_ordinal, C, &d.cluster_ordinal));
-        PFCHK(upload(c, c->b_extra_ord, b->extra_ord, b->n_extra, &d.extra_ord));
-        PFCHK(upload(c, c->b_extra_bits, b->extra_bits, (size_t)b->n_extra * W, &d.extra_bits));
-        if (b->seg_strand_off) PFCHK(upload(c, c->b_seg_strand_off, b->seg_strand_off, NSEG, &d.seg_strand_off));
-        if (b->n_extra) h_extra_cluster.assign(b->extra_cluster, b->extra_cluster + b->n_extra);
+        return PF_OK;
     }
-    // extras per cluster (CSR).  A batch that is in device memory already has its list checked and counted there
-    // (extra_csr_kernel); the counts come back with the first dedup results -- reading the list back and walking it here
-    // was 1 ms in front of the first kernel with SURVEY 8d's share of 'N's (1.5 M rows per 50 000 clusters).
-    const bool ex_on_device = b->on_device && b->n_extra;
-    if (ex_on_device && !C) return fail(PF_ERR_ARG, "extra_cluster must be non-decreasing and < n_clusters");
-    std::vector<uint32_t> ex_first(C + 1, 0);
-    if (!ex_on_device) {
-        for (uint32_t e = 0; e < b->n_extra; e++) {
-            if (h_extra_cluster[e] >= C || (e && h_extra_cluster[e] < h_extra_cluster[e - 1]))
-                return fail(PF_ERR_ARG, "extra_cluster must be non-decreasing and < n_clusters");
-        }
-        for (uint32_t e = 0; e < b->n_extra; e++) ex_first[h_extra_cluster[e] + 1]++;
-        for (uint32_t i = 0; i < C; i++) ex_first[i + 1] += ex_first[i];
-        PFCHK(upload_vec(c, c->extra_off, ex_first));
-    }
-
     // ---- per batch outputs
-    const size_t C1 = std::max(C, 1u), NSEG1 = std::max(NSEG, 1u), NEX1 = std::max(b->n_extra, 1u);
-    PFCHK(c->cl_overflow.ensure(C1 * 4));
-    PFCHK(c->cl_kmer_off.ensure(C1 * 8));
-    PFCHK(c->cl_kmer_cnt.ensure(C1 * 4));
-    PFCHK(c->cl_unique.ensure(C1 * 4));
-    PFCHK(c->cl_pattern.ensure(C1 * 4));
-    PFCHK(c->cl_first.ensure(C1 * 8));
-    PFCHK(c->cl_rec.ensure(C1 * sizeof(pf::ClusterRec)));
-    PFCHK(c->v_word_off.ensure(NSEG1 * 8));
-    PFCHK(c->v_len.ensure(NSEG1 * 4));
-    PFCHK(c->v_sample.ensure(NSEG1 * 4));
-    PFCHK(c->v_ord.ensure(NSEG1 * 4));
-    PFCHK(c->v_bits.ensure(NSEG1 * 4));
-    PFCHK(c->view_off.ensure(C1 * 4));
-    PFCHK(c->seg_distinct.ensure(NSEG1 * 4));
-    PFCHK(c->v_nseg.ensure(C1 * 4));
-    PFCHK(c->v_nstr.ensure(C1 * 4));
-    PFCHK(c->v_mode.ensure(C1 * 4));
-    PFCHK(c->v_dense.ensure(C1 * 4));
-    PFCHK(c->extra_dense.ensure(NEX1 * 4));
-    // (cl_overflow / cl_kmer_cnt / cl_unique / cl_pattern get their start values from the dedup kernel)
-    HIPCHK(hipMemsetAsync(c->cursor.p, 0, 64, c->stream));
-
-    // ---- identical segments -> scan view (mode 1) or the caller's list as it is (mode 0)
-    // The dedup kernel's per-cluster results come back into pinned memory, in two halves for a large batch: the
-    // host builds and launches the first half's work items while the GPU is still on the second half's dedup, and the
-    // second half's while the first half's scan runs -- otherwise the GPU idles for the ~1.2 ms that takes.
-    const size_t C8 = ((size_t)C + 1) & ~(size_t)1;
-    PFCHK(c->pin_dedup.ensure(C8 * sizeof(pf::ClusterRec) + 64 + ((size_t)C + 2) * 4));
-    // what the host needs of the dedup pass per cluster, one 40-byte record each (pf::ClusterRec, written by
-    // cluster_ninst_kernel): ONE copy per part brings them over -- six small copies in a row were 40 us of the part's
-    // critical path
-    pf::ClusterRec* rec = c->pin_dedup.as<pf::ClusterRec>();
-    uint32_t* h_exfirst = reinterpret_cast<uint32_t*>(rec + C8);   // [C + 1] + the "bad list" flag (device-side CSR only)
-    if (ex_on_device) {
-        PFCHK(c->extra_off.ensure(((size_t)C + 2) * 4));
-        uint32_t* exo = c->extra_off.as<uint32_t>();
-        HIPCHK(hipMemsetAsync(exo + C + 1, 0, 4, c->stream));
-        hipLaunchKernelGGL(pf::extra_csr_kernel, dim3(std::min<uint32_t>((std::max(C + 1, b->n_extra) + 255) / 256, 2048u)), dim3(256), 0,
-                           c->stream, b->extra_cluster, b->n_extra, C, exo, exo + C + 1);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h_exfirst, exo, ((size_t)C + 2) * 4, hipMemcpyDeviceToHost, c->stream));
+    int ensure_batch_outputs() {
+        const size_t C1 = std::max(C, 1u), NSEG1 = std::max(NSEG, 1u), NEX1 = std::max(b->n_extra, 1u);
+        const std::pair<DevBuf*, size_t> bufs[] = {
+            {&c->cl_overflow, C1 * 4}, {&c->cl_kmer_off, C1 * 8}, {&c->cl_kmer_cnt, C1 * 4}, {&c->cl_unique, C1 * 4},
+            {&c->cl_pattern, C1 * 4}, {&c->cl_first, C1 * 8}, {&c->cl_rec, C1 * sizeof(pf::ClusterRec)},
+            {&c->v_word_off, NSEG1 * 8}, {&c->v_len, NSEG1 * 4}, {&c->v_sample, NSEG1 * 4}, {&c->v_ord, NSEG1 * 4},
+            {&c->v_bits, NSEG1 * 4}, {&c->view_off, C1 * 4}, {&c->seg_distinct, NSEG1 * 4}, {&c->v_nseg, C1 * 4},
+            {&c->v_nstr, C1 * 4}, {&c->v_mode, C1 * 4}, {&c->v_dense, C1 * 4}, {&c->extra_dense, NEX1 * 4}};
+        for (const auto& [buf, bytes] : bufs) PFCHK(buf->ensure(bytes));
+        // (cl_overflow / cl_kmer_cnt / cl_unique / cl_pattern get their start values from the dedup kernel)
+        HIPCHK(hipMemsetAsync(c->cursor.p, 0, 64, c->stream));
+        return PF_OK;
     }
-    // A large batch goes through in parts, all queued without a host sync in between: the host builds and launches a
-    // part's work items while the GPU is on earlier parts (otherwise it idles for the ~1.2 ms that takes).  Two parts,
-    // a quarter first: enough GPU work to hide building the rest.  (More, equal parts with the MD5 of part i on a second
-    // stream beside part i + 1's finish kernels or part i + 2's dedup were measured and lose: DESIGN.md section 6.)
-    uint32_t P = C >= 8192 ? 2u : 1u;
-    uint32_t part_end[pf_ctx::MAX_PARTS];
-    for (uint32_t q = 0; q < P; q++) part_end[q] = q + 1 == P ? C : (uint32_t)((uint64_t)C * (q + 1) / (2 * P));
-    pf::DedupParams dp{};
-    if (C) {
-        dp.packed = d.packed; dp.seg_word_off = d.seg_word_off; dp.seg_len = d.seg_len;
-        dp.seg_sample = d.seg_sample; dp.seg_ord_base = d.seg_ord_base;
-        dp.cluster_seg_off = d.cluster_seg_off; dp.cluster_nstrains = d.cluster_nstrains;
-        dp.extra_off = c->extra_off.as<uint32_t>(); dp.extra_ord = d.extra_ord;
-        dp.v_word_off = c->v_word_off.as<uint64_t>(); dp.v_len = c->v_len.as<uint32_t>();
-        dp.v_sample = c->v_sample.as<uint32_t>(); dp.v_ord = c->v_ord.as<uint32_t>();
-        dp.seg_distinct = c->seg_distinct.as<uint32_t>();
-        dp.v_bits = c->v_bits.as<uint32_t>(); dp.view_off = c->view_off.as<uint32_t>();
-        dp.cl_overflow = c->cl_overflow.as<uint32_t>(); dp.cl_kmer_cnt = c->cl_kmer_cnt.as<uint32_t>();
-        dp.cl_unique = c->cl_unique.as<uint32_t>(); dp.cl_pattern = c->cl_pattern.as<uint32_t>();
-        dp.v_nseg = c->v_nseg.as<uint32_t>(); dp.v_nstr = c->v_nstr.as<uint32_t>();
-        dp.v_mode = c->v_mode.as<uint32_t>(); dp.v_dense = c->v_dense.as<uint32_t>();
-        dp.extra_dense = c->extra_dense.as<uint32_t>();
-        dp.k = c->o.klength; dp.W = W; dp.canon = c->o.canon;
-        dp.enable = (c->o.flags & PF_FLAG_NO_DEDUP) ? 0u : 1u;
-    }
-    // ---- the device plan (plan_kernel): the simple clusters' work items laid out behind the part's dedup, a 40-byte
-    // summary on its way to pinned memory.  The estimate's learned line is what this context knew when the batch came in
-    // (the host's own estimate for the rest of the part reads the same sums: they change at the end of a submit only).
-    const bool use_plan = (c->o.flags & PF_FLAG_DEVICE_PLAN) && C > 0 && c->max_items < (1u << 22);
-    const double share = 1.0 - std::pow(0.99, (double)c->o.klength) + 0.06;
-    double reg_a = 0.0, reg_b = 0.0, reg_half_sd = 0.0;
-    const bool reg_ready = c->reg_n >= 16;
-    if (reg_ready) {
-        const double n = c->reg_n, den = n * c->reg_xx - c->reg_x * c->reg_x;
-        reg_a = c->reg_y / n;
-        if (den > 1e-6 * n * c->reg_xx) { reg_b = (n * c->reg_xy - c->reg_x * c->reg_y) / den; reg_a = (c->reg_y - reg_b * c->reg_x) / n; }
-        const double ss = std::max(0.0, c->reg_yy - reg_a * c->reg_y - reg_b * c->reg_xy);     // residual sum of squares
-        // (half a residual standard deviation on top: with `room` at 0.9 of the table's limit that left no
-        // cluster of the headline workload, with or without 'N's, to overflow; 0 left 6, 1 to 3 standard
-        // deviations cost 0.5 % to 5 % in surplus partitions -- profiles/r02/partition_margin_experiment.txt)
-        reg_half_sd = 0.5 * std::sqrt(ss / std::max(1.0, n - 2.0));
-    }
-    struct DPtrs { uint32_t *it_cluster, *it_nslots, *w_scan, *w_fin, *w_fin2, *w_fin5, *unit_cluster, *unit_base, *blk; };
-    auto dplan_ptrs = [&](const pf_ctx::DPlan& dp) {
-        uint32_t* b = dp.block.as<uint32_t>();
-        const size_t n = dp.n;
-        return DPtrs{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, b + 6 * n, b + 7 * n, b + 8 * n};
-    };
-    auto launch_plan = [&](uint32_t h, uint32_t c0, uint32_t c1) -> int {
-        pf_ctx::DPlan& dp = c->dplan[h];
-        dp.n = c1 - c0;
-        const uint32_t nblk = (dp.n + pf::PLAN_THREADS - 1) / pf::PLAN_THREADS;
-        PFCHK(dp.block.ensure(((size_t)dp.n * 8 + (size_t)nblk * pf::PLAN_BLK_WORDS) * 4));
-        PFCHK(dp.it_count.ensure((size_t)dp.n * 4));
-        PFCHK(dp.out.ensure(sizeof(pf::PlanOut)));
-        PFCHK(dp.pin_out.ensure(64, true));
-        const DPtrs q = dplan_ptrs(dp);
+    // ---- the device plan (plan_kernel) of part h: the simple clusters' work items laid out behind the part's dedup, a
+    // 40-byte summary on its way to pinned memory
+    int launch_plan(uint32_t h, uint32_t c0, uint32_t c1) {
+        pf_ctx::DPlan& plan = c->dplan[h];
+        plan.n = c1 - c0;
+        const uint32_t nblk = (plan.n + pf::PLAN_THREADS - 1) / pf::PLAN_THREADS;
+        PFCHK(plan.block.ensure(((size_t)plan.n * 8 + (size_t)nblk * pf::PLAN_BLK_WORDS) * 4));
+        PFCHK(plan.it_count.ensure((size_t)plan.n * 4));
+        PFCHK(plan.out.ensure(sizeof(pf::PlanOut)));
+        PFCHK(plan.pin_out.ensure(64, true));
+        const DPtrs q = dplan_ptrs(plan);
         pf::PlanParams pp{};
         pp.rec = c->cl_rec.as<pf::ClusterRec>(); pp.plan_room = c->plan_room.as<uint32_t>(); pp.plan_arena = c->plan_arena.as<uint32_t>();
-        pp.c0 = c0; pp.c1 = c1;
-        pp.NS = NS; pp.max_items = c->max_items;
+        pp.c0 = c0; pp.c1 = c1; pp.NS = NS; pp.max_items = c->max_items;
         pp.it_cluster = q.it_cluster; pp.it_nslots = q.it_nslots; pp.w_scan = q.w_scan; pp.w_fin = q.w_fin; pp.w_fin2 = q.w_fin2;
         pp.w_fin5 = q.w_fin5; pp.unit_cluster = q.unit_cluster; pp.unit_base = q.unit_base; pp.blk = q.blk;
-        pp.out = dp.out.as<pf::PlanOut>();
+        pp.out = plan.out.as<pf::PlanOut>();
         hipLaunchKernelGGL(pf::plan_count_kernel, dim3(nblk), dim3(pf::PLAN_THREADS), 0, c->stream, pp);
         hipLaunchKernelGGL(pf::plan_scan_kernel, dim3(1), dim3(256), 0, c->stream, pp, nblk);
         hipLaunchKernelGGL(pf::plan_scatter_kernel, dim3(nblk), dim3(pf::PLAN_THREADS), 0, c->stream, pp);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(dp.pin_out.p, dp.out.p, sizeof(pf::PlanOut), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(plan.pin_out.p, plan.out.p, sizeof(pf::PlanOut), hipMemcpyDeviceToHost, c->stream));
         return PF_OK;
-    };
-    if (use_plan && C > c->dp_const_n) {
-        // zeros | ones | 0, 1, 2, ...: item_part / extra_first / is_extra / binned, item_nparts / nsib / compact, slice / sib0
-        const uint32_t n = C + C / 4 + 64;
-        std::vector<uint32_t> h(3 * (size_t)n, 0u);
-        for (uint32_t i = 0; i < n; i++) { h[n + i] = 1u; h[2 * (size_t)n + i] = i; }
-        PFCHK(c->dp_const.ensure(h.size() * 4));
-        HIPCHK(hipMemcpy(c->dp_const.p, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-        c->dp_const_n = n;
     }
-    // what cluster_ninst_kernel works out per cluster for plan_kernel (nothing when the host builds every item)
-    pf::PlanClassify pcls{};
-    if (use_plan) {
-        PFCHK(c->plan_room.ensure((size_t)C * 4));
-        PFCHK(c->plan_arena.ensure((size_t)C * 4));
-        pcls.extra_off = c->extra_off.as<uint32_t>(); pcls.plan_room = c->plan_room.as<uint32_t>(); pcls.plan_arena = c->plan_arena.as<uint32_t>();
-        pcls.mult = c->o.canon ? 1u : 2u; pcls.NS = NS; pcls.W = W; pcls.unit_view = (c->o.flags & PF_FLAG_NO_UNIT_DEDUP) ? 0u : 1u;
-        pcls.reg_ready = reg_ready ? 1u : 0u; pcls.share = share; pcls.reg_a = reg_a; pcls.reg_b = reg_b; pcls.reg_half_sd = reg_half_sd;
-    }
-    // the dedup of part h and its results on their way to pinned memory (ev_part[h]); all parts are queued up front
-    auto launch_dedup_part = [&](uint32_t h) -> int {
-        const uint32_t c0 = h ? part_end[h - 1] : 0, c1 = part_end[h], n = c1 - c0;
+    // the dedup of part h and its results on their way to pinned memory (ev_part[h])
+    int launch_dedup_part(uint32_t h) {
+        const uint32_t c0 = part_begin(h), c1 = part_end[h], n = c1 - c0;
         if (n) {
             dp.cluster_base = c0;
-            PFCHK(mark_begin(c, 3));
+            PFCHK(mark_begin(c, TimeCat::dedup));
             hipLaunchKernelGGL(pf::cluster_dedup_kernel<pf::DedupSmall>, dim3(n), dim3(pf::DEDUP_THREADS), 0, c->stream, dp);
             HIPCHK(hipGetLastError());
             PFCHK(mark_end(c));
@@ -946,167 +915,172 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         }
         HIPCHK(hipEventRecord(c->ev_part[h], c->stream));
         return PF_OK;
-    };
-    if (C)
-        for (uint32_t h = 0; h < P; h++) PFCHK(launch_dedup_part(h));
-    // ---- strand bits of target-strain segments (canonical mode)
-    c->n_strand_words = (b->seg_strand_off && c->o.canon) ? b->n_strand_words : 0;
-    if (c->n_strand_words && NSEG) {
-        PFCHK(c->strand_bits.ensure((size_t)c->n_strand_words * 8));
-        HIPCHK(hipMemsetAsync(c->strand_bits.p, 0, (size_t)c->n_strand_words * 8, c->stream));
-        const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)NSEG + 3) / 4, 4096);
-        auto strand = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, c->stream, d.packed, d.seg_word_off, d.seg_len,
-                               d.seg_strand_off, NSEG, c->o.klength, c->strand_bits.as<uint64_t>());
-        };
-        switch (KW) {
-            case 1: strand(pf::strand_bits_kernel<1>); break;
-            case 2: strand(pf::strand_bits_kernel<2>); break;
-            case 3: strand(pf::strand_bits_kernel<3>); break;
-            default: strand(pf::strand_bits_kernel<4>); break;
-        }
-        HIPCHK(hipGetLastError());
     }
-    lap("upload+dedup launch");
-    const uint64_t mult = c->o.canon ? 1 : 2;
-    uint64_t total_inst = 0;
-
-    c->pid0 = c->n_patterns;
-    if (!rerun) c->n_submits++;
-    c->cluster_arena.assign(C, 0);
-
-    std::vector<uint32_t> nparts(C, 1);
-    std::vector<uint32_t> todo;
-    // a deduplicated cluster whose distinct sequences alone carry far more windows than one table holds will
-    // overflow it: start it with two key partitions instead of paying for a failed first scan (a wrong guess
-    // only costs time: an overflow still triggers the doubling retry)
-    // Estimate of the distinct windows of D near-identical sequences of average length L = vinst / D: the first
-    // contributes all of its windows, every further one the share a 1 % divergence touches (1 - 0.99^k: 27 % of the
-    // 31-mers, 40 % of the 51-mers) plus a margin.
-    // what the host does with a part's dedup results once they have arrived (ev_part[h])
-    std::vector<uint32_t> wide_list;
-    auto prep_half = [&](int h) -> int {
-        const uint32_t c0 = h ? part_end[h - 1] : 0, c1 = part_end[h];
-        // clusters the small dedup class gave up on for lack of room (more than 64 distinct sequences, a sample-set
-        // matrix or an ordinal bitmap that does not fit): the wide class on those alone, then their counts again
-        wide_list.clear();
-        for (uint32_t i = c0; i < c1; i++) if (rec[i].mode & pf::MODE_RETRY_WIDE) wide_list.push_back(i);
-        if (!wide_list.empty()) {
-            const uint32_t nw = (uint32_t)wide_list.size();
-            PFCHK(c->wide_list.ensure((size_t)nw * 4));
-            HIPCHK(hipMemcpyAsync(c->wide_list.p, wide_list.data(), (size_t)nw * 4, hipMemcpyHostToDevice, c->stream));
-            pf::DedupParams dw = dp;
-            dw.cluster_base = 0; dw.cluster_list = c->wide_list.as<uint32_t>();
-            PFCHK(mark_begin(c, 3));
-            hipLaunchKernelGGL(pf::cluster_dedup_kernel<pf::DedupWide>, dim3(nw), dim3(pf::DEDUP_THREADS), 0, c->stream, dw);
+    // ---- identical segments -> scan view (mode 1) or the caller's list as it is (mode 0); then the strand bits
+    // The dedup kernel's per-cluster results come back into pinned memory, in two halves for a large batch: the
+    // host builds and launches the first half's work items while the GPU is still on the second half's dedup, and the
+    // second half's while the first half's scan runs -- otherwise the GPU idles for the ~1.2 ms that takes.
+    int launch_dedup_parts() {
+        const size_t C8 = ((size_t)C + 1) & ~(size_t)1;
+        PFCHK(c->pin_dedup.ensure(C8 * sizeof(pf::ClusterRec) + 64 + ((size_t)C + 2) * 4));
+        // what the host needs of the dedup pass per cluster, one 40-byte record each (pf::ClusterRec, written by
+        // cluster_ninst_kernel): ONE copy per part brings them over -- six small copies in a row were 40 us of the part's
+        // critical path
+        rec = c->pin_dedup.as<pf::ClusterRec>();
+        h_exfirst = reinterpret_cast<uint32_t*>(rec + C8);
+        if (ex_on_device) {
+            PFCHK(c->extra_off.ensure(((size_t)C + 2) * 4));
+            uint32_t* exo = c->extra_off.as<uint32_t>();
+            HIPCHK(hipMemsetAsync(exo + C + 1, 0, 4, c->stream));
+            hipLaunchKernelGGL(pf::extra_csr_kernel, dim3(std::min<uint32_t>((std::max(C + 1, b->n_extra) + 255) / 256, 2048u)), dim3(256), 0,
+                               c->stream, b->extra_cluster, b->n_extra, C, exo, exo + C + 1);
             HIPCHK(hipGetLastError());
-            PFCHK(mark_end(c));
-            hipLaunchKernelGGL(pf::cluster_ninst_kernel, dim3((nw + 3) / 4), dim3(256), 0, c->stream, d.cluster_seg_off,
-                               d.seg_len, c->v_len.as<uint32_t>(), c->v_nseg.as<uint32_t>(), c->o.klength, 0u, nw,
-                               c->wide_list.as<uint32_t>(),
-                               c->v_mode.as<uint32_t>(), c->v_dense.as<uint32_t>(), c->v_nstr.as<uint32_t>(), c->cl_rec.as<pf::ClusterRec>(),
-                               pf::PlanClassify{});        // (the wide class's clusters are the host's: no plan bits)
+            HIPCHK(hipMemcpyAsync(h_exfirst, exo, ((size_t)C + 2) * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+        // A large batch goes through in parts, all queued without a host sync in between: the host builds and launches a
+        // part's work items while the GPU is on earlier parts (otherwise it idles for the ~1.2 ms that takes).  Two parts,
+        // a quarter first: enough GPU work to hide building the rest.  (More, equal parts with the MD5 of part i on a second
+        // stream beside part i + 1's finish kernels or part i + 2's dedup were measured and lose: DESIGN.md section 6.)
+        P = C >= 8192 ? 2u : 1u;
+        for (uint32_t q = 0; q < P; q++) part_end[q] = q + 1 == P ? C : (uint32_t)((uint64_t)C * (q + 1) / (2 * P));
+        if (C) {
+            dp.packed = d.packed; dp.seg_word_off = d.seg_word_off; dp.seg_len = d.seg_len;
+            dp.seg_sample = d.seg_sample; dp.seg_ord_base = d.seg_ord_base;
+            dp.cluster_seg_off = d.cluster_seg_off; dp.cluster_nstrains = d.cluster_nstrains;
+            dp.extra_off = c->extra_off.as<uint32_t>(); dp.extra_ord = d.extra_ord;
+            dp.v_word_off = c->v_word_off.as<uint64_t>(); dp.v_len = c->v_len.as<uint32_t>();
+            dp.v_sample = c->v_sample.as<uint32_t>(); dp.v_ord = c->v_ord.as<uint32_t>();
+            dp.seg_distinct = c->seg_distinct.as<uint32_t>();
+            dp.v_bits = c->v_bits.as<uint32_t>(); dp.view_off = c->view_off.as<uint32_t>();
+            dp.cl_overflow = c->cl_overflow.as<uint32_t>(); dp.cl_kmer_cnt = c->cl_kmer_cnt.as<uint32_t>();
+            dp.cl_unique = c->cl_unique.as<uint32_t>(); dp.cl_pattern = c->cl_pattern.as<uint32_t>();
+            dp.v_nseg = c->v_nseg.as<uint32_t>(); dp.v_nstr = c->v_nstr.as<uint32_t>();
+            dp.v_mode = c->v_mode.as<uint32_t>(); dp.v_dense = c->v_dense.as<uint32_t>();
+            dp.extra_dense = c->extra_dense.as<uint32_t>();
+            dp.k = c->o.klength; dp.W = W; dp.canon = c->o.canon;
+            dp.enable = (c->o.flags & PF_FLAG_NO_DEDUP) ? 0u : 1u;
+        }
+        // ---- the device plan: the estimate's learned line is what this context knew when the batch came in (the host's
+        // own estimate for the rest of the part reads the same sums: they change at the end of a submit only)
+        use_plan = (c->o.flags & PF_FLAG_DEVICE_PLAN) && C > 0 && c->max_items < (1u << 22);
+        share = 1.0 - std::pow(0.99, (double)c->o.klength) + 0.06;
+        fit = c->part_model.fit();
+        if (use_plan) {
+            if (C > c->dp_const_n) {
+                // zeros | ones | 0, 1, 2, ...: item_part / extra_first / is_extra / binned, item_nparts / nsib / compact, slice / sib0
+                const uint32_t n = C + C / 4 + 64;
+                std::vector<uint32_t> h(3 * (size_t)n, 0u);
+                for (uint32_t i = 0; i < n; i++) { h[n + i] = 1u; h[2 * (size_t)n + i] = i; }
+                PFCHK(c->dp_const.ensure(h.size() * 4));
+                HIPCHK(hipMemcpy(c->dp_const.p, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+                c->dp_const_n = n;
+            }
+            PFCHK(c->plan_room.ensure((size_t)C * 4));
+            PFCHK(c->plan_arena.ensure((size_t)C * 4));
+            pcls.extra_off = c->extra_off.as<uint32_t>(); pcls.plan_room = c->plan_room.as<uint32_t>(); pcls.plan_arena = c->plan_arena.as<uint32_t>();
+            pcls.mult = c->o.canon ? 1u : 2u; pcls.NS = NS; pcls.W = W; pcls.unit_view = (c->o.flags & PF_FLAG_NO_UNIT_DEDUP) ? 0u : 1u;
+            pcls.reg_ready = fit.ready ? 1u : 0u; pcls.share = share; pcls.reg_a = fit.a; pcls.reg_b = fit.b; pcls.reg_half_sd = fit.half_sd;
+        }
+        if (C)
+            for (uint32_t h = 0; h < P; h++) PFCHK(launch_dedup_part(h));   // all parts are queued up front
+        // ---- strand bits of target-strain segments (canonical mode)
+        c->n_strand_words = (b->seg_strand_off && c->o.canon) ? b->n_strand_words : 0;
+        if (c->n_strand_words && NSEG) {
+            PFCHK(c->strand_bits.ensure((size_t)c->n_strand_words * 8));
+            HIPCHK(hipMemsetAsync(c->strand_bits.p, 0, (size_t)c->n_strand_words * 8, c->stream));
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)NSEG + 3) / 4, 4096);
+            auto strand = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, c->stream, d.packed, d.seg_word_off, d.seg_len,
+                                   d.seg_strand_off, NSEG, c->o.klength, c->strand_bits.as<uint64_t>());
+            };
+            switch (KW) {
+                case 1: strand(pf::strand_bits_kernel<1>); break;
+                case 2: strand(pf::strand_bits_kernel<2>); break;
+                case 3: strand(pf::strand_bits_kernel<3>); break;
+                default: strand(pf::strand_bits_kernel<4>); break;
+            }
             HIPCHK(hipGetLastError());
-            const size_t n = c1 - c0;
-            HIPCHK(hipMemcpyAsync(rec + c0, c->cl_rec.as<pf::ClusterRec>() + c0, n * sizeof(pf::ClusterRec), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->timing.n_wide_clusters += nw;
-        }
-        for (uint32_t i = c0; i < c1; i++) {
-            rec[i].mode &= 3u;
-            if (rec[i].ninst * mult >= 0xFFFFFFF0ull) return fail(PF_ERR_ARG, "cluster %u has too many k-mer instances", i);
-            total_inst += rec[i].ninst * mult;
-            c->timing.n_dedup_clusters += rec[i].mode ? 1u : 0u;
-            if (rec[i].pad & pf::PLAN_PLANNED) continue;          // laid out by plan_kernel: one key partition
-            if (rec[i].mode && rec[i].vnstr) {
-                const double D = (double)rec[i].vnstr, L = (double)(rec[i].vinst * mult) / D;
-                const double est = L * (1.0 + share * (D - 1.0));
-                const double room = 0.9 * (double)pf::insert_limit(NS);
-                // The estimate is right for SURVEY 8d's alleles, each with its own substitutions and flanks.  The many
-                // alleles of a population descend from one another and share far more (tens of new k-mers each, not
-                // hundreds): past 24 distinct sequences the cluster starts as ONE item instead, and if that overflows
-                // the scan reports how far it came and the retry gets the partitions it needs.  A failed first attempt
-                // costs 1/P of the P scans that follow; an over-partitioned cluster costs every surplus scan in full.
-                // Once the context has scanned enough such clusters it knows what a further sequence brings in THIS
-                // pangenome (the line through what it observed, plus a margin) and the first
-                // attempt is sized by that.
-                if (D >= 2.0 && reg_ready) {
-                    const double g = std::max(0.0, reg_a + reg_b * L) + reg_half_sd;      // (the line: see launch_plan)
-                    const double est2 = L + g * (D - 1.0);
-                    // (an estimate never asks for more items than a sub-batch holds: the cluster then starts with what
-                    // fits and an overflowing scan says how many partitions it really needs)
-                    if (est2 > room)
-                        nparts[i] = (uint32_t)std::min<double>(std::ceil(est2 / room), (double)std::min(4096u, std::max(1u, c->max_items / 2)));
-                } else if (est > room) {
-                    nparts[i] = D > 24.0 ? 1u : (uint32_t)std::min<double>(std::ceil(est / room), (double)std::min(64u, std::max(1u, c->max_items / 2)));
-                }
-            }
-        }
-        // ---- unit view: identical 64-window units among the distinct sequences of a cluster are scanned once
-        // (unit_class_kernel).  A cluster's pieces number at most the units of its plain view: that is its room in
-        // this part's pool.
-        if (!(c->o.flags & PF_FLAG_NO_UNIT_DEDUP)) {
-            pf_ctx::UPool& up = c->upool[2 * h + 1];
-            const size_t need_pin = (size_t)(c1 - c0) * 8 + 64;
-            PFCHK(up.pin.ensure(need_pin));
-            // clusters of up to 64 distinct sequences first (one wave each, no table), then the wider ones
-            uint32_t nu = 0, nsmall = 0;
-            uint64_t room = 0;
-            uint32_t* lc = up.pin.as<uint32_t>();
-            auto takes = [&](uint32_t i) { return !(rec[i].pad & pf::PLAN_PLANNED) && rec[i].mode && rec[i].vnstr >= 2 && rec[i].words && room + rec[i].words / 2 < 0x7FFFFFF0ull; };
-            for (uint32_t i = c0; i < c1; i++)
-                if (rec[i].vnstr <= pf::UNIT_SMALL_MAX_D && takes(i)) { lc[nu++] = i; room += rec[i].words / 2; }
-            nsmall = nu;
-            for (uint32_t i = c0; i < c1; i++)
-                if (rec[i].vnstr > pf::UNIT_SMALL_MAX_D && takes(i)) { lc[nu++] = i; room += rec[i].words / 2; }
-            uint32_t* lb = lc + nu;
-            room = 0;
-            for (uint32_t j = 0; j < nu; j++) { lb[j] = (uint32_t)room; room += rec[lc[j]].words / 2; }
-            if (nu) {
-                // (twice the room: the wide kernel parks a cluster's pieces in the second stretch before it orders them by chunk)
-                const size_t R = (size_t)room + 1, R2 = 2 * R;
-                if (R2 > 0xFFFFFFF0ull) return fail(PF_ERR_CAPACITY, "unit view of %zu pieces: submit fewer clusters at a time", R);
-                PFCHK(up.word_off.ensure(R2 * 8)); PFCHK(up.len.ensure(R2 * 4)); PFCHK(up.sample.ensure(R2 * 4));
-                PFCHK(up.ord.ensure(R2 * 4)); PFCHK(up.bits.ensure(R2 * 4)); PFCHK(up.list.ensure((size_t)nu * 8));
-                HIPCHK(hipMemcpyAsync(up.list.p, up.pin.p, (size_t)nu * 8, hipMemcpyHostToDevice, c->stream));
-                pf::UnitParams q{};
-                q.packed = d.packed; q.cluster_seg_off = d.cluster_seg_off; q.v_nstr = c->v_nstr.as<uint32_t>();
-                q.list_cluster = up.list.as<uint32_t>(); q.list_base = up.list.as<uint32_t>() + nu;
-                q.v_word_off = c->v_word_off.as<uint64_t>(); q.v_len = c->v_len.as<uint32_t>(); q.v_ord = c->v_ord.as<uint32_t>();
-                q.u_word_off = up.word_off.as<uint64_t>(); q.u_len = up.len.as<uint32_t>(); q.u_sample = up.sample.as<uint32_t>();
-                q.u_ord = up.ord.as<uint32_t>(); q.u_bits = up.bits.as<uint32_t>();
-                q.v_nseg = c->v_nseg.as<uint32_t>(); q.view_off = c->view_off.as<uint32_t>(); q.k = c->o.klength; q.tmp_off = (uint32_t)R;
-                PFCHK(mark_begin(c, 3));
-                if (nsmall) {
-                    const dim3 g((nsmall + 3) / 4), b(256);
-                    switch ((63 + c->o.klength + 31) / 32) {       // words a unit's 63 + k bases take
-                        case 2: hipLaunchKernelGGL(pf::unit_class_small_kernel<2>, g, b, 0, c->stream, q, nsmall); break;
-                        case 3: hipLaunchKernelGGL(pf::unit_class_small_kernel<3>, g, b, 0, c->stream, q, nsmall); break;
-                        case 4: hipLaunchKernelGGL(pf::unit_class_small_kernel<4>, g, b, 0, c->stream, q, nsmall); break;
-                        case 5: hipLaunchKernelGGL(pf::unit_class_small_kernel<5>, g, b, 0, c->stream, q, nsmall); break;
-                        default: hipLaunchKernelGGL(pf::unit_class_small_kernel<6>, g, b, 0, c->stream, q, nsmall); break;
-                    }
-                    HIPCHK(hipGetLastError());
-                }
-                if (nu > nsmall) {
-                    pf::UnitParams qw = q;
-                    qw.list_cluster += nsmall; qw.list_base += nsmall;
-                    hipLaunchKernelGGL(pf::unit_class_kernel, dim3(nu - nsmall), dim3(pf::UNIT_THREADS), 0, c->stream, qw);
-                    HIPCHK(hipGetLastError());
-                }
-                PFCHK(mark_end(c));
-            }
         }
         return PF_OK;
-    };
+    }
+    // clusters the small dedup class gave up on for lack of room (more than 64 distinct sequences, a sample-set
+    // matrix or an ordinal bitmap that does not fit): the wide class on those alone, then their counts again
+    int retry_wide(uint32_t c0, uint32_t c1) {
+        std::vector<uint32_t>& wide_list = c->hs.wide;
+        wide_list.clear();
+        for (uint32_t i = c0; i < c1; i++) if (rec[i].mode & pf::MODE_RETRY_WIDE) wide_list.push_back(i);
+        if (wide_list.empty()) return PF_OK;
+        const uint32_t nw = (uint32_t)wide_list.size();
+        PFCHK(c->wide_list.ensure((size_t)nw * 4));
+        HIPCHK(hipMemcpyAsync(c->wide_list.p, wide_list.data(), (size_t)nw * 4, hipMemcpyHostToDevice, c->stream));
+        pf::DedupParams dw = dp;
+        dw.cluster_base = 0; dw.cluster_list = c->wide_list.as<uint32_t>();
+        PFCHK(mark_begin(c, TimeCat::dedup));
+        hipLaunchKernelGGL(pf::cluster_dedup_kernel<pf::DedupWide>, dim3(nw), dim3(pf::DEDUP_THREADS), 0, c->stream, dw);
+        HIPCHK(hipGetLastError());
+        PFCHK(mark_end(c));
+        hipLaunchKernelGGL(pf::cluster_ninst_kernel, dim3((nw + 3) / 4), dim3(256), 0, c->stream, d.cluster_seg_off,
+                           d.seg_len, c->v_len.as<uint32_t>(), c->v_nseg.as<uint32_t>(), c->o.klength, 0u, nw,
+                           c->wide_list.as<uint32_t>(),
+                           c->v_mode.as<uint32_t>(), c->v_dense.as<uint32_t>(), c->v_nstr.as<uint32_t>(), c->cl_rec.as<pf::ClusterRec>(),
+                           pf::PlanClassify{});        // (the wide class's clusters are the host's: no plan bits)
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rec + c0, c->cl_rec.as<pf::ClusterRec>() + c0, (size_t)(c1 - c0) * sizeof(pf::ClusterRec), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->timing.n_wide_clusters += nw;
+        return PF_OK;
+    }
+    // ---- unit view: identical 64-window units among the distinct sequences of a cluster are scanned once
+    // (unit_class_kernel): the clusters of up to 64 distinct sequences first (one wave each, no table), then the wider
+    // ones.  Their list {clusters | places in the pool} is plan_kernel's (`plan`), or the host's in up.pin (plan null).
+    int launch_unit_classes(pf_ctx::UPool& up, uint32_t nsmall, uint32_t nwide, uint64_t room, const DPtrs* plan) {
+        const uint32_t nu = nsmall + nwide;
+        // (twice the room: the wide kernel parks a cluster's pieces in the second stretch before it orders them by chunk)
+        const size_t R = (size_t)room + 1, R2 = 2 * R;
+        if (R2 > 0xFFFFFFF0ull) return fail(PF_ERR_CAPACITY, "unit view of %zu pieces: submit fewer clusters at a time", R);
+        PFCHK(up.word_off.ensure(R2 * 8)); PFCHK(up.len.ensure(R2 * 4)); PFCHK(up.sample.ensure(R2 * 4));
+        PFCHK(up.ord.ensure(R2 * 4)); PFCHK(up.bits.ensure(R2 * 4));
+        pf::UnitParams q{};
+        if (plan) {
+            q.list_cluster = plan->unit_cluster; q.list_base = plan->unit_base;
+        } else {
+            PFCHK(up.list.ensure((size_t)nu * 8));
+            HIPCHK(hipMemcpyAsync(up.list.p, up.pin.p, (size_t)nu * 8, hipMemcpyHostToDevice, c->stream));
+            q.list_cluster = up.list.as<uint32_t>(); q.list_base = up.list.as<uint32_t>() + nu;
+        }
+        q.packed = d.packed; q.cluster_seg_off = d.cluster_seg_off; q.v_nstr = c->v_nstr.as<uint32_t>();
+        q.v_word_off = c->v_word_off.as<uint64_t>(); q.v_len = c->v_len.as<uint32_t>(); q.v_ord = c->v_ord.as<uint32_t>();
+        q.u_word_off = up.word_off.as<uint64_t>(); q.u_len = up.len.as<uint32_t>(); q.u_sample = up.sample.as<uint32_t>();
+        q.u_ord = up.ord.as<uint32_t>(); q.u_bits = up.bits.as<uint32_t>();
+        q.v_nseg = c->v_nseg.as<uint32_t>(); q.view_off = c->view_off.as<uint32_t>(); q.k = c->o.klength; q.tmp_off = (uint32_t)R;
+        PFCHK(mark_begin(c, TimeCat::dedup));
+        if (nsmall) {
+            const dim3 g((nsmall + 3) / 4), b(256);
+            switch ((63 + c->o.klength + 31) / 32) {       // words a unit's 63 + k bases take
+                case 2: hipLaunchKernelGGL(pf::unit_class_small_kernel<2>, g, b, 0, c->stream, q, nsmall); break;
+                case 3: hipLaunchKernelGGL(pf::unit_class_small_kernel<3>, g, b, 0, c->stream, q, nsmall); break;
+                case 4: hipLaunchKernelGGL(pf::unit_class_small_kernel<4>, g, b, 0, c->stream, q, nsmall); break;
+                case 5: hipLaunchKernelGGL(pf::unit_class_small_kernel<5>, g, b, 0, c->stream, q, nsmall); break;
+                default: hipLaunchKernelGGL(pf::unit_class_small_kernel<6>, g, b, 0, c->stream, q, nsmall); break;
+            }
+            HIPCHK(hipGetLastError());
+        }
+        if (nwide) {
+            pf::UnitParams qw = q;
+            qw.list_cluster += nsmall; qw.list_base += nsmall;
+            hipLaunchKernelGGL(pf::unit_class_kernel, dim3(nwide), dim3(pf::UNIT_THREADS), 0, c->stream, qw);
+            HIPCHK(hipGetLastError());
+        }
+        PFCHK(mark_end(c));
+        return PF_OK;
+    }
     // ---- parameter blocks of the scan and the fused finish kernels, from a pass's item arrays (the host's staged
     // upload, or plan_kernel's block with the constant arrays standing in for what is the same for every simple cluster)
-    struct ItemPtrs { const uint32_t *cluster, *part, *nparts, *nslots, *slice, *compact, *binned; uint32_t* count; };
-    auto host_items = [&]() {
+    ItemPtrs host_items() const {
         return ItemPtrs{c->it_cluster.as<uint32_t>(), c->it_part.as<uint32_t>(), c->it_nparts.as<uint32_t>(), c->it_nslots.as<uint32_t>(),
                         c->it_slice.as<uint32_t>(), c->it_compact.as<uint32_t>(), c->it_binned.as<uint32_t>(), c->it_count.as<uint32_t>()};
-    };
-    auto scan_params = [&](const ItemPtrs& ip, const pf_ctx::UPool& up, const uint32_t* work) {
+    }
+    pf::ScanParams scan_params(const ItemPtrs& ip, const pf_ctx::UPool& up, const uint32_t* work) const {
         pf::ScanParams sp{};
         sp.packed = d.packed; sp.seg_word_off = c->v_word_off.as<uint64_t>(); sp.seg_len = c->v_len.as<uint32_t>();
         sp.seg_sample = c->v_sample.as<uint32_t>(); sp.seg_ord_base = c->v_ord.as<uint32_t>();
@@ -1125,8 +1099,8 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         sp.k = c->o.klength; sp.W = W; sp.NS = NS;
         sp.item_binned = ip.binned;
         return sp;
-    };
-    auto finish_params = [&](const ItemPtrs& ip, Arena* ar) {
+    }
+    pf::FinishParams finish_params(const ItemPtrs& ip) const {
         pf::FinishParams fp{};
         fp.item_cluster = ip.cluster; fp.item_nslots = ip.nslots;
         fp.item_scratch = ip.slice; fp.cluster_overflow = c->cl_overflow.as<uint32_t>();
@@ -1152,153 +1126,191 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         fp.out_base = ar->base; fp.out_cap = ar->cap; fp.W = W; fp.NS = NS; fp.KW = KW;
         fp.consider_missing = c->o.consider_missing; fp.patfilt = c->o.patfilt; fp.multiple_files = c->o.multiple_files;
         return fp;
-    };
-    uint64_t arena_base = 0;
-    struct Deferred { Arena* ar; uint32_t pin; };
-    std::vector<Deferred> deferred;        // passes launched and not yet waited for (their cursor read-backs are queued)
-    uint32_t arena_i = 0;                  // arenas used so far: one per launched pass, the device-planned ones included
-    // ---- the device-planned clusters of part h: unit view, scan, fused finish -- launched from plan_kernel's 40-byte summary
-    auto launch_planned = [&](uint32_t h) -> int {
-        pf_ctx::DPlan& dp = c->dplan[h];
-        const pf::PlanOut po = *dp.pin_out.as<pf::PlanOut>();
-        const uint32_t n = po.n_items;
-        if (!n) return PF_OK;
-        if (n > c->max_items || n > dp.n || po.n_fin + po.n_fin2 + po.n_fin5 != n || po.n_unit > n)
-            return fail(PF_ERR_STATE, "plan_kernel summary out of range (%u items of %u clusters)", n, dp.n);
-        const DPtrs q = dplan_ptrs(dp);
-        const uint32_t* zeros = c->dp_const.as<uint32_t>();
-        const uint32_t* ones = zeros + c->dp_const_n;
-        const uint32_t* iota = zeros + 2 * (size_t)c->dp_const_n;
-        const ItemPtrs ip{q.it_cluster, zeros, ones, q.it_nslots, iota, ones, zeros, dp.it_count.as<uint32_t>()};
+    }
+    // the fused finish kernels of a launch on stream `s`, the heaviest clusters first
+    int launch_fused_finish(pf::FinishParams fp, hipStream_t s, FinWork huge, FinWork large_m, FinWork large, FinWork small) {
+        PFCHK(mark_begin(c, TimeCat::finish, s));      // (on the side stream too: finish_ms must not leave these launches out)
+        const FinWork order[4] = {huge, large_m, large, small};
+        for (int k = 0; k < 4; k++) {
+            if (!order[k].n) continue;
+            fp.work = order[k].work;
+            const dim3 g(order[k].n);
+            switch (k) {      // (the cases in this order keep the kernels' order in the device code object)
+                case 0: hipLaunchKernelGGL((pf::finish_kernel<pf::FinHuge, true>), g, dim3(pf::FinHuge::THREADS), 0, s, fp); break;
+                case 2: hipLaunchKernelGGL((pf::finish_kernel<pf::FinLarge, false>), g, dim3(pf::FinLarge::THREADS), 0, s, fp); break;
+                case 3: hipLaunchKernelGGL((pf::finish_kernel<pf::FinSmall, false>), g, dim3(pf::FinSmall::THREADS), 0, s, fp); break;
+                default: hipLaunchKernelGGL((pf::finish_kernel<pf::FinLargeM, true>), g, dim3(pf::FinLargeM::THREADS), 0, s, fp); break;
+            }
+            HIPCHK(hipGetLastError());
+        }
+        PFCHK(mark_end(c, s));
+        return PF_OK;
+    }
+    // ---- output arenas: the next pass's, `cap` entries from the batch's next free index on
+    int begin_arena(uint64_t cap) {
         while (c->arenas.size() <= arena_i) c->arenas.push_back(std::make_unique<Arena>());
-        Arena* ar = c->arenas[arena_i].get();
-        ar->cap = std::max<uint64_t>(po.arena_cap, 1);
+        ar = c->arenas[arena_i].get();
+        ar->cap = std::max<uint64_t>(cap, 1);
         ar->base = arena_base;
         PFCHK(ar->key.ensure((size_t)ar->cap * 8 * KW));
         PFCHK(ar->pid.ensure((size_t)ar->cap * 4));
         PFCHK(ar->first.ensure((size_t)ar->cap * 8));
+        return PF_OK;
+    }
+    // the cursor's next free index restarts at the arena's base (a host-planned pass queues its item upload first)
+    int upload_cursor_start() {
         c->pin_small.as<uint64_t>()[arena_i & 15] = arena_base;
         HIPCHK(hipMemcpyAsync(c->cursor.p, c->pin_small.as<uint64_t>() + (arena_i & 15), 8, hipMemcpyHostToDevice, c->stream));
-        pf_ctx::UPool& up = c->upool[2 * h];
-        if (po.n_unit) {
-            const size_t R = (size_t)po.unit_room + 1, R2 = 2 * R;
-            if (R2 > 0xFFFFFFF0ull) return fail(PF_ERR_CAPACITY, "unit view of %zu pieces: submit fewer clusters at a time", R);
-            PFCHK(up.word_off.ensure(R2 * 8)); PFCHK(up.len.ensure(R2 * 4)); PFCHK(up.sample.ensure(R2 * 4));
-            PFCHK(up.ord.ensure(R2 * 4)); PFCHK(up.bits.ensure(R2 * 4));
-            pf::UnitParams uq{};
-            uq.packed = d.packed; uq.cluster_seg_off = d.cluster_seg_off; uq.v_nstr = c->v_nstr.as<uint32_t>();
-            uq.list_cluster = q.unit_cluster; uq.list_base = q.unit_base;
-            uq.v_word_off = c->v_word_off.as<uint64_t>(); uq.v_len = c->v_len.as<uint32_t>(); uq.v_ord = c->v_ord.as<uint32_t>();
-            uq.u_word_off = up.word_off.as<uint64_t>(); uq.u_len = up.len.as<uint32_t>(); uq.u_sample = up.sample.as<uint32_t>();
-            uq.u_ord = up.ord.as<uint32_t>(); uq.u_bits = up.bits.as<uint32_t>();
-            uq.v_nseg = c->v_nseg.as<uint32_t>(); uq.view_off = c->view_off.as<uint32_t>(); uq.k = c->o.klength; uq.tmp_off = (uint32_t)R;
-            PFCHK(mark_begin(c, 3));
-            const dim3 g((po.n_unit + 3) / 4), b(256);
-            switch ((63 + c->o.klength + 31) / 32) {       // words a unit's 63 + k bases take
-                case 2: hipLaunchKernelGGL(pf::unit_class_small_kernel<2>, g, b, 0, c->stream, uq, po.n_unit); break;
-                case 3: hipLaunchKernelGGL(pf::unit_class_small_kernel<3>, g, b, 0, c->stream, uq, po.n_unit); break;
-                case 4: hipLaunchKernelGGL(pf::unit_class_small_kernel<4>, g, b, 0, c->stream, uq, po.n_unit); break;
-                case 5: hipLaunchKernelGGL(pf::unit_class_small_kernel<5>, g, b, 0, c->stream, uq, po.n_unit); break;
-                default: hipLaunchKernelGGL(pf::unit_class_small_kernel<6>, g, b, 0, c->stream, uq, po.n_unit); break;
-            }
-            HIPCHK(hipGetLastError());
-            PFCHK(mark_end(c));
-        }
-        {
-            const pf::ScanParams sp = scan_params(ip, up, q.w_scan);
-            PFCHK(mark_begin(c, 0));
-            PFCHK(launch_scan(c, sp, n));
-            PFCHK(mark_end(c));
-            c->timing.scan_launches++;
-        }
-        {
-            pf::FinishParams fp = finish_params(ip, ar);
-            PFCHK(mark_begin(c, 6));
-            if (po.n_fin5) {
-                fp.work = q.w_fin5;
-                hipLaunchKernelGGL((pf::finish_kernel<pf::FinHuge, true>), dim3(po.n_fin5), dim3(pf::FinHuge::THREADS), 0, c->stream, fp);
-                HIPCHK(hipGetLastError());
-            }
-            if (po.n_fin2) {
-                fp.work = q.w_fin2;
-                hipLaunchKernelGGL((pf::finish_kernel<pf::FinLarge, false>), dim3(po.n_fin2), dim3(pf::FinLarge::THREADS), 0, c->stream, fp);
-                HIPCHK(hipGetLastError());
-            }
-            if (po.n_fin) {
-                fp.work = q.w_fin;
-                hipLaunchKernelGGL((pf::finish_kernel<pf::FinSmall, false>), dim3(po.n_fin), dim3(pf::FinSmall::THREADS), 0, c->stream, fp);
-                HIPCHK(hipGetLastError());
-            }
-            PFCHK(mark_end(c));
-        }
-        c->timing.n_items += n;
-        c->timing.n_device_planned += n;
+        return PF_OK;
+    }
+    // a pass not waited for: its cursor comes back with the last pass's results
+    int defer_pass() {
         const uint32_t pin = 16 + (arena_i & 31);
         HIPCHK(hipMemcpyAsync(c->pin_small.as<uint64_t>() + pin, c->cursor.p, 8, hipMemcpyDeviceToHost, c->stream));
         deferred.push_back(Deferred{ar, pin});
         arena_base += ar->cap;
         arena_i++;
         return PF_OK;
-    };
-    uint32_t pass = 0;                     // host-planned passes: the parts' (what plan_kernel left of them), then the re-runs
-    uint32_t cnt2[3] = {0, 0, 0};          // pattern counters {ids handed out, pool overflow, arena overflow}
-    c->counters = pf_result{};
-    const uint32_t lim_full = pf::insert_limit(NS);
-    for (;;) {
-        c->stage_slot = (int)(pass & 1);
-        if (pass < P) {
-            // this part's dedup results (queued with the others up front) have to be here; its clusters are the pass
-            HIPCHK(hipEventSynchronize(c->ev_part[pass]));
-            if (pass == 0) lap("first part's dedup results");
-            if (pass == 0 && ex_on_device) {
-                if (h_exfirst[C + 1]) {
-                    HIPCHK(hipStreamSynchronize(c->stream));
-                    return fail(PF_ERR_ARG, "extra_cluster must be non-decreasing and < n_clusters");
-                }
-                ex_first.assign(h_exfirst, h_exfirst + C + 1);
-            }
-            // the clusters plan_kernel laid out go first: the GPU starts on them while the rest of the part is built here
-            const uint32_t planned_arena = arena_i;
-            if (use_plan) PFCHK(launch_planned(pass));
-            PFCHK(prep_half((int)pass));
-            lap("  prep (records, unit view)");
-            todo.clear();
-            for (uint32_t ci = pass ? part_end[pass - 1] : 0; ci < part_end[pass]; ci++) {
-                if (!(rec[ci].pad & pf::PLAN_PLANNED)) { todo.push_back(ci); continue; }
-                c->timing.scan_packed_bytes += rec[ci].words * 8;
-                c->cluster_arena[ci] = planned_arena;
-            }
+    }
+    // what a waited-for pass wrote (`cursor`: the next free index it left)
+    static int close_arena(Arena* a, uint64_t cursor) {
+        a->used = cursor - a->base;
+        if (a->used > a->cap) return fail(PF_ERR_CAPACITY, "output arena overflow (%llu > %llu)", (unsigned long long)a->used, (unsigned long long)a->cap);
+        return PF_OK;
+    }
+    // ---- the device-planned clusters of part h: unit view, scan, fused finish -- launched from plan_kernel's 40-byte summary
+    int launch_planned(uint32_t h) {
+        const pf_ctx::DPlan& plan = c->dplan[h];
+        const pf::PlanOut po = *plan.pin_out.as<pf::PlanOut>();
+        const uint32_t n = po.n_items;
+        if (!n) return PF_OK;
+        if (n > c->max_items || n > plan.n || po.n_fin + po.n_fin2 + po.n_fin5 != n || po.n_unit > n)
+            return fail(PF_ERR_STATE, "plan_kernel summary out of range (%u items of %u clusters)", n, plan.n);
+        const DPtrs q = dplan_ptrs(plan);
+        const uint32_t* zeros = c->dp_const.as<uint32_t>();
+        const uint32_t* ones = zeros + c->dp_const_n;
+        const uint32_t* iota = zeros + 2 * (size_t)c->dp_const_n;
+        const ItemPtrs ip{q.it_cluster, zeros, ones, q.it_nslots, iota, ones, zeros, plan.it_count.as<uint32_t>()};
+        PFCHK(begin_arena(po.arena_cap));
+        PFCHK(upload_cursor_start());
+        pf_ctx::UPool& up = c->upool[2 * h];
+        if (po.n_unit) PFCHK(launch_unit_classes(up, po.n_unit, 0, po.unit_room, &q));
+        PFCHK(mark_begin(c, TimeCat::scan));
+        PFCHK(launch_scan(c, scan_params(ip, up, q.w_scan), n));
+        PFCHK(mark_end(c));
+        c->timing.scan_launches++;
+        PFCHK(launch_fused_finish(finish_params(ip), c->stream, {q.w_fin5, po.n_fin5}, {nullptr, 0}, {q.w_fin2, po.n_fin2},
+                                  {q.w_fin, po.n_fin}));
+        c->timing.n_items += n;
+        c->timing.n_device_planned += n;
+        return defer_pass();
+    }
+    // A deduplicated cluster whose distinct sequences alone carry far more windows than one table holds will
+    // overflow it: start it with two key partitions instead of paying for a failed first scan (a wrong guess
+    // only costs time: an overflow still triggers the doubling retry)
+    // Estimate of the distinct windows of D near-identical sequences of average length L = vinst / D: the first
+    // contributes all of its windows, every further one the share a 1 % divergence touches (1 - 0.99^k: 27 % of the
+    // 31-mers, 40 % of the 51-mers) plus a margin.
+    uint32_t first_nparts(const pf::ClusterRec& cr) const {
+        if (!cr.mode || !cr.vnstr) return 1;
+        const double D = (double)cr.vnstr, L = (double)(cr.vinst * mult) / D;
+        const double est = L * (1.0 + share * (D - 1.0));
+        const double room = 0.9 * (double)pf::insert_limit(NS);
+        // The estimate is right for SURVEY 8d's alleles, each with its own substitutions and flanks.  The many
+        // alleles of a population descend from one another and share far more (tens of new k-mers each, not
+        // hundreds): past 24 distinct sequences the cluster starts as ONE item instead, and if that overflows
+        // the scan reports how far it came and the retry gets the partitions it needs.  A failed first attempt
+        // costs 1/P of the P scans that follow; an over-partitioned cluster costs every surplus scan in full.
+        // Once the context has scanned enough such clusters it knows what a further sequence brings in THIS
+        // pangenome (the line through what it observed, plus a margin) and the first
+        // attempt is sized by that.
+        if (D >= 2.0 && fit.ready) {
+            const double g = std::max(0.0, fit.a + fit.b * L) + fit.half_sd;      // (the line: see launch_plan)
+            const double est2 = L + g * (D - 1.0);
+            // (an estimate never asks for more items than a sub-batch holds: the cluster then starts with what
+            // fits and an overflowing scan says how many partitions it really needs)
+            if (est2 > room)
+                return (uint32_t)std::min<double>(std::ceil(est2 / room), (double)std::min(4096u, std::max(1u, c->max_items / 2)));
+        } else if (est > room) {
+            return D > 24.0 ? 1u : (uint32_t)std::min<double>(std::ceil(est / room), (double)std::min(64u, std::max(1u, c->max_items / 2)));
         }
-        if (todo.empty() && pass >= P) break;
-        // ---- items of this pass
-        std::vector<Item>& items = c->hs_items;
-        std::vector<uint8_t>& item_fused = c->hs_fused;      // 0 unfused, 1 fused small class, 2 fused large class
-        items.clear(); item_fused.clear();
-        items.reserve(todo.size() + 64); item_fused.reserve(todo.size() + 64);
-        struct Sub { uint32_t item0, nitems, cl0, ncl, pool, bin0, nbin; uint64_t q_total; };
-        // A cluster of three or more key partitions (a dedup view, keys of up to two words) has its windows sorted by
-        // partition first (bin_kernel): its items then read their own windows instead of each walking the whole view.
-        // The entry arrays belong to a sub-batch; a sub-batch ends where they would pass BIN_MAX_ENTRIES.
-        constexpr uint32_t BIN_MIN_PARTS = 3;      // (at two, a cluster's own bin_kernel workgroup takes longer than the second walk it saves)
-        constexpr uint64_t BIN_MAX_ENTRIES = 1ull << 28;
-        std::vector<uint32_t>& v_binned = c->hs_binned;
-        std::vector<uint32_t>&bin_cluster = c->hs_bin[0], &bin_item0 = c->hs_bin[1], &bin_nparts = c->hs_bin[2], &bin_base = c->hs_bin[3];
-        v_binned.clear(); bin_cluster.clear(); bin_item0.clear(); bin_nparts.clear(); bin_base.clear();
-        // (which unit-view pool a cluster's view lies in: its part's device-planned one or the host-planned one)
-        auto part_of = [&](uint32_t ci) { uint32_t q = 0; while (q + 1 < P && ci >= part_end[q]) q++; return 2 * q + ((rec[ci].pad & pf::PLAN_PLANNED) ? 0u : 1u); };
-        std::vector<Sub> subs;
-        std::vector<uint32_t>&sub_cluster = c->hs_sub[0], &sub_item0 = c->hs_sub[1], &sub_nitems = c->hs_sub[2];
-        sub_cluster.clear(); sub_item0.clear(); sub_nitems.clear();
-        uint64_t arena_cap = 0;
-        Sub cur{0, 0, 0, 0, todo.empty() ? 0u : part_of(todo[0]), 0, 0, 0};
+        return 1;
+    }
+    // ---- the first pass of part h: its dedup results (queued with the others up front) have to be here
+    int begin_part(uint32_t h) {
+        const uint32_t c0 = part_begin(h), c1 = part_end[h];
+        HIPCHK(hipEventSynchronize(c->ev_part[h]));
+        if (h == 0) lap("first part's dedup results");
+        if (h == 0 && ex_on_device) {
+            if (h_exfirst[C + 1]) {
+                HIPCHK(hipStreamSynchronize(c->stream));
+                return fail(PF_ERR_ARG, "extra_cluster must be non-decreasing and < n_clusters");
+            }
+            ex_first.assign(h_exfirst, h_exfirst + C + 1);
+        }
+        // the clusters plan_kernel laid out go first: the GPU starts on them while the rest of the part is built here
+        const uint32_t planned_arena = arena_i;
+        if (use_plan) PFCHK(launch_planned(h));
+        PFCHK(retry_wide(c0, c1));
+        for (uint32_t i = c0; i < c1; i++) {
+            rec[i].mode &= 3u;
+            if (rec[i].ninst * mult >= 0xFFFFFFF0ull) return fail(PF_ERR_ARG, "cluster %u has too many k-mer instances", i);
+            total_inst += rec[i].ninst * mult;
+            c->timing.n_dedup_clusters += rec[i].mode ? 1u : 0u;
+            if (rec[i].pad & pf::PLAN_PLANNED) continue;          // laid out by plan_kernel: one key partition
+            nparts[i] = first_nparts(rec[i]);
+        }
+        // the host-planned clusters' unit view.  A cluster's pieces number at most the units of its plain view: that is
+        // its room in this part's pool.
+        if (!(c->o.flags & PF_FLAG_NO_UNIT_DEDUP)) {
+            pf_ctx::UPool& up = c->upool[2 * h + 1];
+            PFCHK(up.pin.ensure((size_t)(c1 - c0) * 8 + 64));
+            uint32_t nu = 0;
+            uint64_t room = 0;
+            uint32_t* lc = up.pin.as<uint32_t>();
+            auto takes = [&](uint32_t i) { return !(rec[i].pad & pf::PLAN_PLANNED) && rec[i].mode && rec[i].vnstr >= 2 && rec[i].words && room + rec[i].words / 2 < 0x7FFFFFF0ull; };
+            for (uint32_t i = c0; i < c1; i++)
+                if (rec[i].vnstr <= pf::UNIT_SMALL_MAX_D && takes(i)) { lc[nu++] = i; room += rec[i].words / 2; }
+            const uint32_t nsmall = nu;
+            for (uint32_t i = c0; i < c1; i++)
+                if (rec[i].vnstr > pf::UNIT_SMALL_MAX_D && takes(i)) { lc[nu++] = i; room += rec[i].words / 2; }
+            uint32_t* lb = lc + nu;
+            room = 0;
+            for (uint32_t j = 0; j < nu; j++) { lb[j] = (uint32_t)room; room += rec[lc[j]].words / 2; }
+            if (nu) PFCHK(launch_unit_classes(up, nsmall, nu - nsmall, room, nullptr));
+        }
+        lap("  prep (records, unit view)");
+        todo.clear();
+        for (uint32_t ci = c0; ci < c1; ci++) {
+            if (!(rec[ci].pad & pf::PLAN_PLANNED)) { todo.push_back(ci); continue; }
+            c->timing.scan_packed_bytes += rec[ci].words * 8;
+            c->cluster_arena[ci] = planned_arena;
+        }
+        return PF_OK;
+    }
+    // which unit-view pool a cluster's view lies in: its part's device-planned one or the host-planned one
+    uint32_t pool_of(uint32_t ci) const {
+        uint32_t q = 0;
+        while (q + 1 < P && ci >= part_end[q]) q++;
+        return 2 * q + ((rec[ci].pad & pf::PLAN_PLANNED) ? 0u : 1u);
+    }
+    // ---- items of this pass: the todo clusters' key partitions and extra-row items, cut into sub-batches
+    int build_items(Pass& ps) {
+        SubmitScratch& hs = c->hs;
+        const uint32_t lim_full = pf::insert_limit(NS);
+        std::vector<Item>& items = hs.items;
+        items.clear(); hs.fused.clear();
+        items.reserve(todo.size() + 64); hs.fused.reserve(todo.size() + 64);
+        hs.it_binned.clear(); hs.bin_cluster.clear(); hs.bin_item0.clear(); hs.bin_nparts.clear(); hs.bin_base.clear();
+        hs.sub_cluster.clear(); hs.sub_item0.clear(); hs.sub_nitems.clear();
+        Sub cur{0, 0, 0, 0, todo.empty() ? 0u : pool_of(todo[0]), 0, 0, 0};
         for (uint32_t ci : todo) {
             const uint32_t np = nparts[ci];
             const uint32_t nex = ex_first[ci + 1] - ex_first[ci];
             // a deduplicated cluster that is one work item (or a few key partitions) is finished by one fused kernel
             // (rows + emit in LDS); its slow-path rows (a few k-mers around an 'N') are folded in by that kernel
             const uint32_t mwords = rec[ci].vnstr * ((W + 3) & ~3u);
-            uint8_t fused = 0;   // 1/2: single item, small/large class; 3: first of several partitions; 4: the others;
-                                 // 5: single item, huge class
+            uint8_t fused = 0;   // (SubmitScratch::fused)
             if (rec[ci].mode == 1 && nex <= pf::FUSED_MAX_EXTRA && NS <= 9600) {
                 const bool fits_large = rec[ci].dense < pf::FinLarge::DW * 32 - 1 && mwords <= pf::FinLarge::MR;
                 const bool fits_huge = rec[ci].dense < pf::FinHuge::DW * 32 - 1 && mwords <= pf::FinHuge::MR;
@@ -1323,12 +1335,12 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
             const bool binned = !(c->o.flags & PF_FLAG_NO_KEY_BINNING) && np >= BIN_MIN_PARTS && KW <= 2 && rec[ci].mode != 0 &&
                                 vch <= pf::BIN_CHUNKS && (uint64_t)np * vch <= pf::BIN_CELLS && qn && qn <= BIN_MAX_ENTRIES;
             // (a launch reads one unit-view pool: a re-run pass does not mix the pools' clusters in a sub-batch)
-            if (cur.nitems + nit > c->max_items || (cur.nitems && part_of(ci) != cur.pool) ||
+            if (cur.nitems + nit > c->max_items || (cur.nitems && pool_of(ci) != cur.pool) ||
                 (binned && cur.q_total + qn > BIN_MAX_ENTRIES)) {
-                subs.push_back(cur);
-                cur = Sub{(uint32_t)items.size(), 0, (uint32_t)sub_cluster.size(), 0, part_of(ci), (uint32_t)bin_cluster.size(), 0, 0};
+                ps.subs.push_back(cur);
+                cur = Sub{(uint32_t)items.size(), 0, (uint32_t)hs.sub_cluster.size(), 0, pool_of(ci), (uint32_t)hs.bin_cluster.size(), 0, 0};
             }
-            if (!cur.nitems) cur.pool = part_of(ci);
+            if (!cur.nitems) cur.pool = pool_of(ci);
             const uint32_t sib0 = (uint32_t)items.size();
             // table size: a cluster that cannot overflow a small table gets one (less flush traffic)
             uint32_t ns = NS;
@@ -1337,13 +1349,13 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
             else if (np == 1 && NS > 6144 + pf::INSERT_SLACK && inst <= pf::insert_limit(6144)) ns = 6144;
             for (uint32_t q = 0; q < np; q++) {
                 items.push_back(Item{ci, q, np, ns, cur.nitems + q, sib0, nit, 0, 0});
-                item_fused.push_back(fused == 3 && q > 0 ? 4 : fused);
+                hs.fused.push_back(fused == 3 && q > 0 ? 4 : fused);
             }
-            v_binned.resize(items.size() + nex_items, 0);
+            hs.it_binned.resize(items.size() + nex_items, 0);
             if (binned) {
-                for (uint32_t q = 0; q < np; q++) v_binned[sib0 + q] = 1;
-                bin_cluster.push_back(ci); bin_item0.push_back(sib0); bin_nparts.push_back(np);
-                bin_base.push_back((uint32_t)cur.q_total);
+                for (uint32_t q = 0; q < np; q++) hs.it_binned[sib0 + q] = 1;
+                hs.bin_cluster.push_back(ci); hs.bin_item0.push_back(sib0); hs.bin_nparts.push_back(np);
+                hs.bin_base.push_back((uint32_t)cur.q_total);
                 cur.q_total += qn; cur.nbin++;
                 c->timing.n_binned_clusters++;
             }
@@ -1351,55 +1363,44 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
                 const uint32_t first = ex_first[ci] + q * lim_full;
                 const uint32_t cnt = std::min(lim_full, ex_first[ci + 1] - first);
                 items.push_back(Item{ci, 0, 1, cnt, cur.nitems + np + q, sib0, nit, first, 1});
-                item_fused.push_back(0);
+                hs.fused.push_back(0);
             }
-            for (uint32_t q = 0; q < np; q++) arena_cap += std::min<uint64_t>(pf::insert_limit(ns), inst);
-            arena_cap += nex;
+            for (uint32_t q = 0; q < np; q++) ps.arena_cap += std::min<uint64_t>(pf::insert_limit(ns), inst);
+            ps.arena_cap += nex;
             if (!fused) {
-                sub_cluster.push_back(ci);
-                sub_item0.push_back(sib0);
-                sub_nitems.push_back(nit);
+                hs.sub_cluster.push_back(ci);
+                hs.sub_item0.push_back(sib0);
+                hs.sub_nitems.push_back(nit);
                 cur.ncl++;
             }
             cur.nitems += nit;
             c->cluster_arena[ci] = arena_i;
         }
-        if (cur.nitems) subs.push_back(cur);
-
+        if (cur.nitems) ps.subs.push_back(cur);
         lap("  items");
-        // ---- arena of this pass
-        while (c->arenas.size() <= arena_i) c->arenas.push_back(std::make_unique<Arena>());
-        Arena* ar = c->arenas[arena_i].get();
-        ar->cap = std::max<uint64_t>(arena_cap, 1);
-        ar->base = arena_base;
-        PFCHK(ar->key.ensure((size_t)ar->cap * 8 * KW));
-        PFCHK(ar->pid.ensure((size_t)ar->cap * 4));
-        PFCHK(ar->first.ensure((size_t)ar->cap * 8));
-
-        // ---- item arrays
+        return PF_OK;
+    }
+    // ---- item arrays and work lists of this pass, up in one staged copy
+    int build_work_lists(Pass& ps) {
+        SubmitScratch& hs = c->hs;
+        const std::vector<Item>& items = hs.items;
         const size_t NI = items.size();
-        std::vector<uint32_t>&v_cluster = c->hs_v[0], &v_part = c->hs_v[1], &v_nparts = c->hs_v[2], &v_nslots = c->hs_v[3],
-            &v_slice = c->hs_v[4], &v_sib0 = c->hs_v[5], &v_nsib = c->hs_v[6], &v_exfirst = c->hs_v[7], &v_isex = c->hs_v[8],
-            &v_compact = c->hs_v[9], &w_scan = c->hs_w[0], &w_extra = c->hs_w[1], &w_fin = c->hs_w[2], &w_fin2 = c->hs_w[3],
-            &w_fin3 = c->hs_w[4], &w_rows = c->hs_w[5], &w_fin5 = c->hs_w[6];
-        for (auto& v : c->hs_v) v.resize(NI);
-        v_binned.resize(NI, 0);
-        for (auto& v : c->hs_w) { v.clear(); v.reserve(NI); }
+        for (auto* v : {&hs.it_cluster, &hs.it_part, &hs.it_nparts, &hs.it_nslots, &hs.it_slice, &hs.it_sib0, &hs.it_nsib,
+                        &hs.it_extra_first, &hs.it_is_extra, &hs.it_compact})
+            v->resize(NI);
+        hs.it_binned.resize(NI, 0);
+        for (auto* v : {&hs.w_scan, &hs.w_extra, &hs.w_fin, &hs.w_fin2, &hs.w_fin3, &hs.w_rows, &hs.w_fin5}) { v->clear(); v->reserve(NI); }
         for (size_t i = 0; i < NI; i++) {
-            v_cluster[i] = items[i].cluster; v_part[i] = items[i].part; v_nparts[i] = items[i].nparts;
-            v_nslots[i] = items[i].nslots; v_slice[i] = items[i].slice; v_sib0[i] = items[i].sib0;
-            v_nsib[i] = items[i].nsib; v_exfirst[i] = items[i].extra_first; v_isex[i] = items[i].is_extra;
-            v_compact[i] = item_fused[i] ? 1 : 0;
+            hs.it_cluster[i] = items[i].cluster; hs.it_part[i] = items[i].part; hs.it_nparts[i] = items[i].nparts;
+            hs.it_nslots[i] = items[i].nslots; hs.it_slice[i] = items[i].slice; hs.it_sib0[i] = items[i].sib0;
+            hs.it_nsib[i] = items[i].nsib; hs.it_extra_first[i] = items[i].extra_first; hs.it_is_extra[i] = items[i].is_extra;
+            hs.it_compact[i] = hs.fused[i] ? 1 : 0;
         }
         lap("  arena + item columns");
-        PFCHK(c->it_count.ensure(std::max<size_t>(NI, 1) * 4));
-        PFCHK(c->it_unique.ensure(std::max<size_t>(NI, 1) * 4));
-        PFCHK(c->it_kept.ensure(std::max<size_t>(NI, 1) * 4));
-        // work lists per sub-batch, concatenated; scan items heaviest first (the grid drains evenly)
-        std::vector<uint32_t> scan_off(subs.size() + 1, 0), extra_off(subs.size() + 1, 0), fin_off(subs.size() + 1, 0),
-            fin2_off(subs.size() + 1, 0), fin3_off(subs.size() + 1, 0), fin5_off(subs.size() + 1, 0), rows_off(subs.size() + 1, 0);
-        // heaviest items first inside each launch (the grid then drains evenly): a coarse O(n) order by
-        // log2(scan instances) is enough
+        for (DevBuf* v : {&c->it_count, &c->it_unique, &c->it_kept}) PFCHK(v->ensure(std::max<size_t>(NI, 1) * 4));
+        // work lists per sub-batch, concatenated; heaviest items first inside each launch (the grid then drains evenly):
+        // a coarse O(n) order by log2(scan instances) is enough
+        ps.off.assign(ps.subs.size() + 1, SubLists{0, 0, 0, 0, 0, 0, 0});
         auto wclass = [&](uint32_t it) -> int {
             const uint64_t w = rec[items[it].cluster].vinst;
             return w ? 63 - __builtin_clzll(w) : 0;
@@ -1418,245 +1419,203 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
             }
             src.clear();
         };
-        for (size_t s = 0; s < subs.size(); s++) {
-            for (uint32_t i = subs[s].item0; i < subs[s].item0 + subs[s].nitems; i++) {
-                if (items[i].is_extra) w_extra.push_back(i); else tmp_scan.push_back(i);
-                if (item_fused[i] == 1) tmp_fin.push_back(i);
-                else if (item_fused[i] == 2) tmp_fin2.push_back(i);
-                else if (item_fused[i] == 3) w_fin3.push_back(i);
-                else if (item_fused[i] == 5) w_fin5.push_back(i);
-                else if (item_fused[i] == 0) w_rows.push_back(i);
+        for (size_t s = 0; s < ps.subs.size(); s++) {
+            for (uint32_t i = ps.subs[s].item0; i < ps.subs[s].item0 + ps.subs[s].nitems; i++) {
+                if (items[i].is_extra) hs.w_extra.push_back(i); else tmp_scan.push_back(i);
+                if (hs.fused[i] == 1) tmp_fin.push_back(i);
+                else if (hs.fused[i] == 2) tmp_fin2.push_back(i);
+                else if (hs.fused[i] == 3) hs.w_fin3.push_back(i);
+                else if (hs.fused[i] == 5) hs.w_fin5.push_back(i);
+                else if (hs.fused[i] == 0) hs.w_rows.push_back(i);
             }
-            append_by_weight(tmp_scan, w_scan);
-            append_by_weight(tmp_fin, w_fin);
-            append_by_weight(tmp_fin2, w_fin2);
-            scan_off[s + 1] = (uint32_t)w_scan.size();
-            extra_off[s + 1] = (uint32_t)w_extra.size();
-            fin_off[s + 1] = (uint32_t)w_fin.size();
-            fin2_off[s + 1] = (uint32_t)w_fin2.size();
-            fin3_off[s + 1] = (uint32_t)w_fin3.size();
-            fin5_off[s + 1] = (uint32_t)w_fin5.size();
-            rows_off[s + 1] = (uint32_t)w_rows.size();
+            append_by_weight(tmp_scan, hs.w_scan);
+            append_by_weight(tmp_fin, hs.w_fin);
+            append_by_weight(tmp_fin2, hs.w_fin2);
+            ps.off[s + 1] = SubLists{(uint32_t)hs.w_scan.size(), (uint32_t)hs.w_extra.size(), (uint32_t)hs.w_fin.size(),
+                                     (uint32_t)hs.w_fin2.size(), (uint32_t)hs.w_fin3.size(), (uint32_t)hs.w_fin5.size(),
+                                     (uint32_t)hs.w_rows.size()};
         }
         // the four lists of the binned clusters travel as one block (cluster | first item | partitions | first entry)
-        const size_t NB = bin_cluster.size();
-        if (NB) {
-            std::vector<uint32_t>& all = c->hs_bin[0];
-            all.insert(all.end(), bin_item0.begin(), bin_item0.end());
-            all.insert(all.end(), bin_nparts.begin(), bin_nparts.end());
-            all.insert(all.end(), bin_base.begin(), bin_base.end());
+        ps.NB = hs.bin_cluster.size();
+        hs.bin_block.clear();
+        if (ps.NB) {
+            for (auto* v : {&hs.bin_cluster, &hs.bin_item0, &hs.bin_nparts, &hs.bin_base}) hs.bin_block.insert(hs.bin_block.end(), v->begin(), v->end());
             PFCHK(c->q_off.ensure(NI * (pf::BIN_CHUNKS + 1) * 4));
         }
-        {
-            std::vector<std::pair<DevBuf*, const std::vector<uint32_t>*>> arrs = {
-                {&c->bin_lists, &c->hs_bin[0]},
-                {&c->it_cluster, &v_cluster}, {&c->it_part, &v_part}, {&c->it_nparts, &v_nparts},
-                {&c->it_nslots, &v_nslots}, {&c->it_slice, &v_slice}, {&c->it_sib0, &v_sib0}, {&c->it_nsib, &v_nsib},
-                {&c->it_extra_first, &v_exfirst}, {&c->it_is_extra, &v_isex}, {&c->it_compact, &v_compact},
-                {&c->it_binned, &v_binned},
-                {&c->sub_cluster, &sub_cluster},
-                {&c->sub_item0, &sub_item0}, {&c->sub_nitems, &sub_nitems}, {&c->work_scan, &w_scan},
-                {&c->work_extra, &w_extra}, {&c->work_fin, &w_fin}, {&c->work_fin2, &w_fin2}, {&c->work_fin3, &w_fin3}, {&c->work_fin5, &w_fin5}, {&c->work_rows, &w_rows}};
-            lap("  work lists");
-            PFCHK(staged_upload(c, arrs));
-        }
-        // the cursor's next free index restarts at this arena's base
-        {
-            c->pin_small.as<uint64_t>()[arena_i & 15] = arena_base;
-            HIPCHK(hipMemcpyAsync(c->cursor.p, c->pin_small.as<uint64_t>() + (arena_i & 15), 8, hipMemcpyHostToDevice, c->stream));
-        }
-
-        lap("upload items");
-        for (size_t s = 0; s < subs.size(); s++) {
-            const Sub& sb = subs[s];
-            const uint32_t n_scan = scan_off[s + 1] - scan_off[s], n_extra_items = extra_off[s + 1] - extra_off[s];
-            if (n_extra_items) {
-                pf::ExtraParams ep{};
-                ep.extra_ord = c->extra_dense.as<uint32_t>(); ep.extra_bits = d.extra_bits;
-                ep.item_first = c->it_extra_first.as<uint32_t>(); ep.item_nslots = c->it_nslots.as<uint32_t>();
-                ep.item_scratch = c->it_slice.as<uint32_t>();
-                ep.tab_key = c->tab_key.as<uint64_t>(); ep.tab_ord = c->tab_ord.as<uint32_t>();
-                ep.chunkbits = c->chunkbits.as<uint32_t>(); ep.chunkmask = c->chunkmask.as<uint32_t>();
-                ep.item_count = c->it_count.as<uint32_t>();
-                ep.work = c->work_extra.as<uint32_t>() + extra_off[s];
-                ep.W = W; ep.NS = NS; ep.KW = KW;
-                PFCHK(mark_begin(c, 2));
-                hipLaunchKernelGGL(pf::extra_fill_kernel, dim3(n_extra_items), dim3(256), 0, c->stream, ep);
-                HIPCHK(hipGetLastError());
-                PFCHK(mark_end(c));
-            }
-            if (n_scan) {
-                pf::ScanParams sp = scan_params(host_items(), c->upool[sb.pool], c->work_scan.as<uint32_t>() + scan_off[s]);
-                PFCHK(mark_begin(c, 0));
-                if (sb.nbin) {
-                    const size_t qcap = (size_t)sb.q_total + 64;
-                    PFCHK(c->q_key.ensure(qcap * 8 * KW)); PFCHK(c->q_ord.ensure(qcap * 4)); PFCHK(c->q_bit.ensure(qcap * 4));
-                    sp.q_key = c->q_key.as<uint64_t>(); sp.q_ord = c->q_ord.as<uint32_t>(); sp.q_bit = c->q_bit.as<uint32_t>();
-                    sp.q_stride = qcap; sp.q_off = c->q_off.as<uint32_t>();
-                    sp.bin_cluster = c->bin_lists.as<uint32_t>() + sb.bin0; sp.bin_item0 = c->bin_lists.as<uint32_t>() + NB + sb.bin0;
-                    sp.bin_nparts = c->bin_lists.as<uint32_t>() + 2 * NB + sb.bin0; sp.bin_base = c->bin_lists.as<uint32_t>() + 3 * NB + sb.bin0;
-                    PFCHK(launch_bin(c, sp, sb.nbin));
-                }
-                PFCHK(launch_scan(c, sp, n_scan));
-                PFCHK(mark_end(c));
-                c->timing.scan_launches++;
-            }
-            const uint32_t n_fin = fin_off[s + 1] - fin_off[s], n_fin2 = fin2_off[s + 1] - fin2_off[s],
-                           n_fin3 = fin3_off[s + 1] - fin3_off[s], n_fin5 = fin5_off[s + 1] - fin5_off[s],
-                           n_rows = rows_off[s + 1] - rows_off[s];
-            // A launch whose fused-finish workgroups do not fill the GPU while general-path items wait behind them (a batch
-            // of many-allele clusters with a few dozen simple ones: two 1 024-thread workgroups took 0.4 ms each with the
-            // other 250 CUs idle; any batch of a few hundred clusters): the finish kernels go to the context's second
-            // stream and run BESIDE rows / emit / pattern rows -- they share nothing but atomically claimed output room
-            // and the run-global pattern table.  (Not for full launches: two latency-bound kernels that each fill the GPU
-            // take each other's wave slots -- five such pairings lost in rounds 2-3.)
-            const uint32_t n_fused_wg = n_fin + n_fin2 + n_fin3 + n_fin5;
-            const bool beside = n_fused_wg && n_rows && n_fused_wg <= 2u * (uint32_t)c->n_cu;
-            if (n_fused_wg) {
-                pf::FinishParams fp = finish_params(host_items(), ar);
-                hipStream_t fs = c->stream;
-                if (beside) {
-                    HIPCHK(hipEventRecord(c->ev_fork, c->stream));
-                    HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-                    fs = c->side;
-                    c->timing.n_side_launches++;
-                }
-                PFCHK(mark_begin(c, 6, fs));      // (on the side stream too: finish_ms must not leave these launches out)
-                if (n_fin5) {   // the heaviest clusters first
-                    fp.work = c->work_fin5.as<uint32_t>() + fin5_off[s];
-                    hipLaunchKernelGGL((pf::finish_kernel<pf::FinHuge, true>), dim3(n_fin5), dim3(pf::FinHuge::THREADS), 0, fs, fp);
-                    HIPCHK(hipGetLastError());
-                }
-                if (n_fin3) {
-                    fp.work = c->work_fin3.as<uint32_t>() + fin3_off[s];
-                    hipLaunchKernelGGL((pf::finish_kernel<pf::FinLargeM, true>), dim3(n_fin3), dim3(pf::FinLargeM::THREADS), 0, fs, fp);
-                    HIPCHK(hipGetLastError());
-                }
-                if (n_fin2) {
-                    fp.work = c->work_fin2.as<uint32_t>() + fin2_off[s];
-                    hipLaunchKernelGGL((pf::finish_kernel<pf::FinLarge, false>), dim3(n_fin2), dim3(pf::FinLarge::THREADS), 0, fs, fp);
-                    HIPCHK(hipGetLastError());
-                }
-                if (n_fin) {
-                    fp.work = c->work_fin.as<uint32_t>() + fin_off[s];
-                    hipLaunchKernelGGL((pf::finish_kernel<pf::FinSmall, false>), dim3(n_fin), dim3(pf::FinSmall::THREADS), 0, fs, fp);
-                    HIPCHK(hipGetLastError());
-                }
-                PFCHK(mark_end(c, fs));
-                if (beside) HIPCHK(hipEventRecord(c->ev_join, c->side));
-            }
-            if (!n_rows) continue;
-            pf::RowsParams rp{};
-            rp.item_cluster = c->it_cluster.as<uint32_t>(); rp.item_nslots = c->it_nslots.as<uint32_t>();
-            rp.item_scratch = c->it_slice.as<uint32_t>(); rp.item_count = c->it_count.as<uint32_t>();
-            rp.item_is_extra = c->it_is_extra.as<uint32_t>();
-            rp.cluster_overflow = c->cl_overflow.as<uint32_t>();
-            rp.cluster_seg_off = d.cluster_seg_off; rp.seg_sample = d.seg_sample;
-            rp.seg_distinct = c->seg_distinct.as<uint32_t>();
-            rp.v_mode = c->v_mode.as<uint32_t>(); rp.v_nstr = c->v_nstr.as<uint32_t>(); rp.v_dense = c->v_dense.as<uint32_t>();
-            rp.cluster_nstrains = d.cluster_nstrains; rp.cluster_npresab = d.cluster_npresab;
-            rp.cluster_presab = d.cluster_presab; rp.cluster_ordinal = d.cluster_ordinal;
-            rp.maf_lo = c->d_maf_lo.as<uint32_t>(); rp.maf_hi = c->d_maf_hi.as<uint32_t>();
-            rp.tab_ord = c->tab_ord.as<uint32_t>(); rp.chunkbits = c->chunkbits.as<uint32_t>();
-            rp.chunkmask = c->chunkmask.as<uint32_t>();
-            rp.slot_hash = c->slot_hash.as<uint4>(); rp.sorted_pair = c->sorted_pair.as<uint64_t>();
-            rp.kept_prefix = c->kept_prefix.as<uint32_t>();
-            rp.bm4 = c->bm4.as<uint4>(); rp.bm2 = c->bm2.as<uint2>(); rp.item_nsib = c->it_nsib.as<uint32_t>();
-            rp.mrows = c->mrows.as<uint32_t>();
-            rp.item_unique = c->it_unique.as<uint32_t>(); rp.item_kept = c->it_kept.as<uint32_t>();
-            rp.work = c->work_rows.as<uint32_t>() + rows_off[s]; rp.W = W; rp.NS = NS;
-            rp.consider_missing = c->o.consider_missing; rp.patfilt = c->o.patfilt; rp.multiple_files = c->o.multiple_files;
-            PFCHK(mark_begin(c, 1));
-            hipLaunchKernelGGL(pf::rows_kernel, dim3(n_rows), dim3(pf::ROWS_THREADS), 0, c->stream, rp);
+        std::vector<std::pair<DevBuf*, const std::vector<uint32_t>*>> arrs = {
+            {&c->bin_lists, &hs.bin_block},
+            {&c->it_cluster, &hs.it_cluster}, {&c->it_part, &hs.it_part}, {&c->it_nparts, &hs.it_nparts},
+            {&c->it_nslots, &hs.it_nslots}, {&c->it_slice, &hs.it_slice}, {&c->it_sib0, &hs.it_sib0}, {&c->it_nsib, &hs.it_nsib},
+            {&c->it_extra_first, &hs.it_extra_first}, {&c->it_is_extra, &hs.it_is_extra}, {&c->it_compact, &hs.it_compact},
+            {&c->it_binned, &hs.it_binned},
+            {&c->sub_cluster, &hs.sub_cluster}, {&c->sub_item0, &hs.sub_item0}, {&c->sub_nitems, &hs.sub_nitems},
+            {&c->work_scan, &hs.w_scan}, {&c->work_extra, &hs.w_extra}, {&c->work_fin, &hs.w_fin}, {&c->work_fin2, &hs.w_fin2},
+            {&c->work_fin3, &hs.w_fin3}, {&c->work_fin5, &hs.w_fin5}, {&c->work_rows, &hs.w_rows}};
+        lap("  work lists");
+        return staged_upload(c, arrs);
+    }
+    // ---- sub-batch s of a host-planned pass: extra-row fill, (bin and) scan, the fused finish beside or in line, then
+    // the general path: rows -> cluster base (+ bitmap merge) -> emit -> pattern rows
+    int launch_sub_batch(const Pass& ps, size_t s) {
+        const Sub& sb = ps.subs[s];
+        const SubLists &o0 = ps.off[s], &o1 = ps.off[s + 1];
+        const uint32_t n_scan = o1.scan - o0.scan, n_extra_items = o1.extra - o0.extra;
+        if (n_extra_items) {
+            pf::ExtraParams ep{};
+            ep.extra_ord = c->extra_dense.as<uint32_t>(); ep.extra_bits = d.extra_bits;
+            ep.item_first = c->it_extra_first.as<uint32_t>(); ep.item_nslots = c->it_nslots.as<uint32_t>();
+            ep.item_scratch = c->it_slice.as<uint32_t>();
+            ep.tab_key = c->tab_key.as<uint64_t>(); ep.tab_ord = c->tab_ord.as<uint32_t>();
+            ep.chunkbits = c->chunkbits.as<uint32_t>(); ep.chunkmask = c->chunkmask.as<uint32_t>();
+            ep.item_count = c->it_count.as<uint32_t>();
+            ep.work = c->work_extra.as<uint32_t>() + o0.extra;
+            ep.W = W; ep.NS = NS; ep.KW = KW;
+            PFCHK(mark_begin(c, TimeCat::emit));
+            hipLaunchKernelGGL(pf::extra_fill_kernel, dim3(n_extra_items), dim3(256), 0, c->stream, ep);
             HIPCHK(hipGetLastError());
             PFCHK(mark_end(c));
-
-            pf::BaseParams bp{};
-            bp.sub_cluster = c->sub_cluster.as<uint32_t>() + sb.cl0;
-            bp.cluster_item0 = c->sub_item0.as<uint32_t>() + sb.cl0;
-            bp.cluster_nitems = c->sub_nitems.as<uint32_t>() + sb.cl0;
-            bp.item_kept = c->it_kept.as<uint32_t>(); bp.item_unique = c->it_unique.as<uint32_t>();
-            bp.cluster_overflow = c->cl_overflow.as<uint32_t>();
-            bp.cluster_kmer_off = c->cl_kmer_off.as<uint64_t>(); bp.cluster_kmer_cnt = c->cl_kmer_cnt.as<uint32_t>();
-            bp.cluster_unique = c->cl_unique.as<uint32_t>(); bp.cursor = c->cursor.as<uint64_t>();
-            bp.n = sb.ncl;
-            PFCHK(mark_begin(c, 2));
-            hipLaunchKernelGGL(pf::cluster_base_kernel, dim3(1), dim3(1024), 0, c->stream, bp);
-            HIPCHK(hipGetLastError());
-            if (sb.nitems > sb.ncl) {     // some cluster of this sub-batch has several items
-                pf::BitmapMergeParams bm{};
-                bm.sub_cluster = bp.sub_cluster; bm.cluster_item0 = bp.cluster_item0; bm.cluster_nitems = bp.cluster_nitems;
-                bm.item_scratch = c->it_slice.as<uint32_t>(); bm.cluster_overflow = bp.cluster_overflow;
-                bm.v_mode = c->v_mode.as<uint32_t>(); bm.v_dense = c->v_dense.as<uint32_t>();
-                bm.item_fused = c->it_compact.as<uint32_t>();
-                bm.bm4 = c->bm4.as<uint4>(); bm.bm2 = c->bm2.as<uint2>();
-                hipLaunchKernelGGL(pf::bitmap_merge_kernel, dim3(sb.ncl), dim3(256), 0, c->stream, bm);
-                HIPCHK(hipGetLastError());
+        }
+        if (n_scan) {
+            pf::ScanParams sp = scan_params(host_items(), c->upool[sb.pool], c->work_scan.as<uint32_t>() + o0.scan);
+            PFCHK(mark_begin(c, TimeCat::scan));
+            if (sb.nbin) {
+                const size_t qcap = (size_t)sb.q_total + 64, NB = ps.NB;
+                PFCHK(c->q_key.ensure(qcap * 8 * KW)); PFCHK(c->q_ord.ensure(qcap * 4)); PFCHK(c->q_bit.ensure(qcap * 4));
+                sp.q_key = c->q_key.as<uint64_t>(); sp.q_ord = c->q_ord.as<uint32_t>(); sp.q_bit = c->q_bit.as<uint32_t>();
+                sp.q_stride = qcap; sp.q_off = c->q_off.as<uint32_t>();
+                sp.bin_cluster = c->bin_lists.as<uint32_t>() + sb.bin0; sp.bin_item0 = c->bin_lists.as<uint32_t>() + NB + sb.bin0;
+                sp.bin_nparts = c->bin_lists.as<uint32_t>() + 2 * NB + sb.bin0; sp.bin_base = c->bin_lists.as<uint32_t>() + 3 * NB + sb.bin0;
+                PFCHK(launch_bin(c, sp, sb.nbin));
             }
-
-            pf::EmitParams em{};
-            em.item_cluster = c->it_cluster.as<uint32_t>(); em.item_scratch = c->it_slice.as<uint32_t>();
-            em.item_unique = c->it_unique.as<uint32_t>(); em.item_nslots = c->it_nslots.as<uint32_t>();
-            em.item_sib0 = c->it_sib0.as<uint32_t>();
-            em.item_nsib = c->it_nsib.as<uint32_t>(); em.cluster_overflow = c->cl_overflow.as<uint32_t>();
-            em.v_mode = c->v_mode.as<uint32_t>(); em.v_dense = c->v_dense.as<uint32_t>();
-            em.cluster_nstrains = d.cluster_nstrains; em.cluster_npresab = d.cluster_npresab;
-            em.cluster_presab = d.cluster_presab; em.cluster_ordinal = d.cluster_ordinal;
-            em.cluster_kmer_off = c->cl_kmer_off.as<uint64_t>();
-            em.tab_key = c->tab_key.as<uint64_t>(); em.tab_ord = c->tab_ord.as<uint32_t>();
-            em.slot_hash = c->slot_hash.as<uint4>();
-            em.sorted_pair = c->sorted_pair.as<uint64_t>(); em.kept_prefix = c->kept_prefix.as<uint32_t>(); em.kept_prefix_rw = c->kept_prefix.as<uint32_t>();
-            em.bm4 = c->bm4.as<uint4>();
-            em.slot_out = c->slot_out.as<uint32_t>();
-            em.out_key = ar->key.as<uint64_t>(); em.out_pid = ar->pid.as<uint32_t>(); em.out_first = ar->first.as<uint64_t>();
-            em.cluster_pattern = c->cl_pattern.as<uint32_t>(); em.cluster_first = c->cl_first.as<uint64_t>();
-            em.pt = c->pt; em.out_base = ar->base; em.out_cap = ar->cap;
-            em.work = c->work_rows.as<uint32_t>() + rows_off[s]; em.W = W; em.NS = NS; em.KW = KW;
-            em.consider_missing = c->o.consider_missing; em.multiple_files = c->o.multiple_files;
-            hipLaunchKernelGGL(pf::emit_kernel, dim3(n_rows), dim3(pf::EMIT_THREADS), 0, c->stream, em);
-            HIPCHK(hipGetLastError());
+            PFCHK(launch_scan(c, sp, n_scan));
             PFCHK(mark_end(c));
-            PFCHK(mark_begin(c, 4));
+            c->timing.scan_launches++;
+        }
+        const uint32_t n_fin = o1.fin - o0.fin, n_fin2 = o1.fin2 - o0.fin2, n_fin3 = o1.fin3 - o0.fin3,
+                       n_fin5 = o1.fin5 - o0.fin5, n_rows = o1.rows - o0.rows;
+        // A launch whose fused-finish workgroups do not fill the GPU while general-path items wait behind them (a batch
+        // of many-allele clusters with a few dozen simple ones: two 1 024-thread workgroups took 0.4 ms each with the
+        // other 250 CUs idle; any batch of a few hundred clusters): the finish kernels go to the context's second
+        // stream and run BESIDE rows / emit / pattern rows -- they share nothing but atomically claimed output room
+        // and the run-global pattern table.  (Not for full launches: two latency-bound kernels that each fill the GPU
+        // take each other's wave slots -- five such pairings lost in rounds 2-3.)
+        const uint32_t n_fused_wg = n_fin + n_fin2 + n_fin3 + n_fin5;
+        const bool beside = n_fused_wg && n_rows && n_fused_wg <= 2u * (uint32_t)c->n_cu;
+        if (n_fused_wg) {
+            hipStream_t fs = c->stream;
+            if (beside) {
+                HIPCHK(hipEventRecord(c->ev_fork, c->stream));
+                HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+                fs = c->side;
+                c->timing.n_side_launches++;
+            }
+            PFCHK(launch_fused_finish(finish_params(host_items()), fs, {c->work_fin5.as<uint32_t>() + o0.fin5, n_fin5},
+                                      {c->work_fin3.as<uint32_t>() + o0.fin3, n_fin3}, {c->work_fin2.as<uint32_t>() + o0.fin2, n_fin2},
+                                      {c->work_fin.as<uint32_t>() + o0.fin, n_fin}));
+            if (beside) HIPCHK(hipEventRecord(c->ev_join, c->side));
+        }
+        if (!n_rows) return PF_OK;
+        pf::RowsParams rp{};
+        rp.item_cluster = c->it_cluster.as<uint32_t>(); rp.item_nslots = c->it_nslots.as<uint32_t>();
+        rp.item_scratch = c->it_slice.as<uint32_t>(); rp.item_count = c->it_count.as<uint32_t>();
+        rp.item_is_extra = c->it_is_extra.as<uint32_t>();
+        rp.cluster_overflow = c->cl_overflow.as<uint32_t>();
+        rp.cluster_seg_off = d.cluster_seg_off; rp.seg_sample = d.seg_sample;
+        rp.seg_distinct = c->seg_distinct.as<uint32_t>();
+        rp.v_mode = c->v_mode.as<uint32_t>(); rp.v_nstr = c->v_nstr.as<uint32_t>(); rp.v_dense = c->v_dense.as<uint32_t>();
+        rp.cluster_nstrains = d.cluster_nstrains; rp.cluster_npresab = d.cluster_npresab;
+        rp.cluster_presab = d.cluster_presab; rp.cluster_ordinal = d.cluster_ordinal;
+        rp.maf_lo = c->d_maf_lo.as<uint32_t>(); rp.maf_hi = c->d_maf_hi.as<uint32_t>();
+        rp.tab_ord = c->tab_ord.as<uint32_t>(); rp.chunkbits = c->chunkbits.as<uint32_t>();
+        rp.chunkmask = c->chunkmask.as<uint32_t>();
+        rp.slot_hash = c->slot_hash.as<uint4>(); rp.sorted_pair = c->sorted_pair.as<uint64_t>();
+        rp.kept_prefix = c->kept_prefix.as<uint32_t>();
+        rp.bm4 = c->bm4.as<uint4>(); rp.bm2 = c->bm2.as<uint2>(); rp.item_nsib = c->it_nsib.as<uint32_t>();
+        rp.mrows = c->mrows.as<uint32_t>();
+        rp.item_unique = c->it_unique.as<uint32_t>(); rp.item_kept = c->it_kept.as<uint32_t>();
+        rp.work = c->work_rows.as<uint32_t>() + o0.rows; rp.W = W; rp.NS = NS;
+        rp.consider_missing = c->o.consider_missing; rp.patfilt = c->o.patfilt; rp.multiple_files = c->o.multiple_files;
+        PFCHK(mark_begin(c, TimeCat::rows));
+        hipLaunchKernelGGL(pf::rows_kernel, dim3(n_rows), dim3(pf::ROWS_THREADS), 0, c->stream, rp);
+        HIPCHK(hipGetLastError());
+        PFCHK(mark_end(c));
 
-            pf::PatRowsParams pr{};
-            pr.item_cluster = em.item_cluster; pr.item_scratch = em.item_scratch; pr.item_unique = em.item_unique;
-            pr.item_nslots = em.item_nslots; pr.item_is_extra = c->it_is_extra.as<uint32_t>();
-            pr.item_sib0 = em.item_sib0; pr.item_nsib = em.item_nsib; pr.cluster_overflow = em.cluster_overflow;
-            pr.v_mode = em.v_mode; pr.v_nstr = c->v_nstr.as<uint32_t>(); pr.v_dense = em.v_dense;
-            pr.cluster_seg_off = d.cluster_seg_off; pr.seg_sample = d.seg_sample; pr.seg_distinct = c->seg_distinct.as<uint32_t>();
-            pr.cluster_nstrains = d.cluster_nstrains; pr.cluster_npresab = d.cluster_npresab;
-            pr.cluster_presab = d.cluster_presab; pr.cluster_kmer_off = em.cluster_kmer_off;
-            pr.sorted_pair = em.sorted_pair; pr.kept_prefix = em.kept_prefix;
-            pr.chunkbits = c->chunkbits.as<uint32_t>(); pr.chunkmask = c->chunkmask.as<uint32_t>();
-            pr.slot_out = c->slot_out.as<uint32_t>(); pr.mrows = c->mrows.as<uint32_t>();
-            pr.out_pid = em.out_pid; pr.out_first = em.out_first;
-            pr.cluster_pattern = em.cluster_pattern; pr.cluster_first = em.cluster_first;
-            pr.pat_first_seen = c->pt.first_seen;
-            pr.pat_bits = c->pat_bits.as<uint32_t>();
-            pr.pat_nan = c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr;
-            pr.pat_n = c->pat_n.as<uint32_t>();
-            pr.out_base = ar->base; pr.out_cap = ar->cap; pr.pool = c->pt.pool;
-            pr.work = em.work; pr.W = W; pr.NS = NS; pr.consider_missing = c->o.consider_missing;
-            hipLaunchKernelGGL(pf::pattern_rows_kernel, dim3(n_rows), dim3(pf::PR_THREADS), 0, c->stream, pr);
+        pf::BaseParams bp{};
+        bp.sub_cluster = c->sub_cluster.as<uint32_t>() + sb.cl0;
+        bp.cluster_item0 = c->sub_item0.as<uint32_t>() + sb.cl0;
+        bp.cluster_nitems = c->sub_nitems.as<uint32_t>() + sb.cl0;
+        bp.item_kept = c->it_kept.as<uint32_t>(); bp.item_unique = c->it_unique.as<uint32_t>();
+        bp.cluster_overflow = c->cl_overflow.as<uint32_t>();
+        bp.cluster_kmer_off = c->cl_kmer_off.as<uint64_t>(); bp.cluster_kmer_cnt = c->cl_kmer_cnt.as<uint32_t>();
+        bp.cluster_unique = c->cl_unique.as<uint32_t>(); bp.cursor = c->cursor.as<uint64_t>();
+        bp.n = sb.ncl;
+        PFCHK(mark_begin(c, TimeCat::emit));
+        hipLaunchKernelGGL(pf::cluster_base_kernel, dim3(1), dim3(1024), 0, c->stream, bp);
+        HIPCHK(hipGetLastError());
+        if (sb.nitems > sb.ncl) {     // some cluster of this sub-batch has several items
+            pf::BitmapMergeParams bm{};
+            bm.sub_cluster = bp.sub_cluster; bm.cluster_item0 = bp.cluster_item0; bm.cluster_nitems = bp.cluster_nitems;
+            bm.item_scratch = c->it_slice.as<uint32_t>(); bm.cluster_overflow = bp.cluster_overflow;
+            bm.v_mode = c->v_mode.as<uint32_t>(); bm.v_dense = c->v_dense.as<uint32_t>();
+            bm.item_fused = c->it_compact.as<uint32_t>();
+            bm.bm4 = c->bm4.as<uint4>(); bm.bm2 = c->bm2.as<uint2>();
+            hipLaunchKernelGGL(pf::bitmap_merge_kernel, dim3(sb.ncl), dim3(256), 0, c->stream, bm);
             HIPCHK(hipGetLastError());
-            PFCHK(mark_end(c));
-            if (beside) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));   // the next sub-batch takes the scratch slices over
         }
-        c->timing.n_items += (uint32_t)NI;
-        for (uint32_t ci : todo) c->timing.scan_packed_bytes += rec[ci].words * 8 * nparts[ci];
 
-        lap("launch pass");
-        if (pass + 1 < P) {
-            // no wait: the next part's pass is built now and goes in behind this one
-            const uint32_t pin = 16 + (arena_i & 31);
-            HIPCHK(hipMemcpyAsync(c->pin_small.as<uint64_t>() + pin, c->cursor.p, 8, hipMemcpyDeviceToHost, c->stream));
-            deferred.push_back(Deferred{ar, pin});
-            arena_base += ar->cap;
-            arena_i++;
-            pass++;
-            continue;
-        }
-        // ---- who overflowed?
+        pf::EmitParams em{};
+        em.item_cluster = c->it_cluster.as<uint32_t>(); em.item_scratch = c->it_slice.as<uint32_t>();
+        em.item_unique = c->it_unique.as<uint32_t>(); em.item_nslots = c->it_nslots.as<uint32_t>();
+        em.item_sib0 = c->it_sib0.as<uint32_t>();
+        em.item_nsib = c->it_nsib.as<uint32_t>(); em.cluster_overflow = c->cl_overflow.as<uint32_t>();
+        em.v_mode = c->v_mode.as<uint32_t>(); em.v_dense = c->v_dense.as<uint32_t>();
+        em.cluster_nstrains = d.cluster_nstrains; em.cluster_npresab = d.cluster_npresab;
+        em.cluster_presab = d.cluster_presab; em.cluster_ordinal = d.cluster_ordinal;
+        em.cluster_kmer_off = c->cl_kmer_off.as<uint64_t>();
+        em.tab_key = c->tab_key.as<uint64_t>(); em.tab_ord = c->tab_ord.as<uint32_t>();
+        em.slot_hash = c->slot_hash.as<uint4>();
+        em.sorted_pair = c->sorted_pair.as<uint64_t>(); em.kept_prefix = c->kept_prefix.as<uint32_t>(); em.kept_prefix_rw = c->kept_prefix.as<uint32_t>();
+        em.bm4 = c->bm4.as<uint4>();
+        em.slot_out = c->slot_out.as<uint32_t>();
+        em.out_key = ar->key.as<uint64_t>(); em.out_pid = ar->pid.as<uint32_t>(); em.out_first = ar->first.as<uint64_t>();
+        em.cluster_pattern = c->cl_pattern.as<uint32_t>(); em.cluster_first = c->cl_first.as<uint64_t>();
+        em.pt = c->pt; em.out_base = ar->base; em.out_cap = ar->cap;
+        em.work = c->work_rows.as<uint32_t>() + o0.rows; em.W = W; em.NS = NS; em.KW = KW;
+        em.consider_missing = c->o.consider_missing; em.multiple_files = c->o.multiple_files;
+        hipLaunchKernelGGL(pf::emit_kernel, dim3(n_rows), dim3(pf::EMIT_THREADS), 0, c->stream, em);
+        HIPCHK(hipGetLastError());
+        PFCHK(mark_end(c));
+        PFCHK(mark_begin(c, TimeCat::pattern_rows));
+
+        pf::PatRowsParams pr{};
+        pr.item_cluster = em.item_cluster; pr.item_scratch = em.item_scratch; pr.item_unique = em.item_unique;
+        pr.item_nslots = em.item_nslots; pr.item_is_extra = c->it_is_extra.as<uint32_t>();
+        pr.item_sib0 = em.item_sib0; pr.item_nsib = em.item_nsib; pr.cluster_overflow = em.cluster_overflow;
+        pr.v_mode = em.v_mode; pr.v_nstr = c->v_nstr.as<uint32_t>(); pr.v_dense = em.v_dense;
+        pr.cluster_seg_off = d.cluster_seg_off; pr.seg_sample = d.seg_sample; pr.seg_distinct = c->seg_distinct.as<uint32_t>();
+        pr.cluster_nstrains = d.cluster_nstrains; pr.cluster_npresab = d.cluster_npresab;
+        pr.cluster_presab = d.cluster_presab; pr.cluster_kmer_off = em.cluster_kmer_off;
+        pr.sorted_pair = em.sorted_pair; pr.kept_prefix = em.kept_prefix;
+        pr.chunkbits = c->chunkbits.as<uint32_t>(); pr.chunkmask = c->chunkmask.as<uint32_t>();
+        pr.slot_out = c->slot_out.as<uint32_t>(); pr.mrows = c->mrows.as<uint32_t>();
+        pr.out_pid = em.out_pid; pr.out_first = em.out_first;
+        pr.cluster_pattern = em.cluster_pattern; pr.cluster_first = em.cluster_first;
+        pr.pat_first_seen = c->pt.first_seen;
+        pr.pat_bits = c->pat_bits.as<uint32_t>();
+        pr.pat_nan = c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr;
+        pr.pat_n = c->pat_n.as<uint32_t>();
+        pr.out_base = ar->base; pr.out_cap = ar->cap; pr.pool = c->pt.pool;
+        pr.work = em.work; pr.W = W; pr.NS = NS; pr.consider_missing = c->o.consider_missing;
+        hipLaunchKernelGGL(pf::pattern_rows_kernel, dim3(n_rows), dim3(pf::PR_THREADS), 0, c->stream, pr);
+        HIPCHK(hipGetLastError());
+        PFCHK(mark_end(c));
+        if (beside) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));   // the next sub-batch takes the scratch slices over
+        return PF_OK;
+    }
+    // ---- the pass waited for (the last part's, or a re-run): who overflowed?  Read-back, learning, the next pass's clusters
+    int finish_pass(const Pass& ps, uint32_t pass, bool rerun) {
+        SubmitScratch& hs = c->hs;
+        const size_t NI = hs.items.size();
         PFCHK(c->pin_ovf.ensure((size_t)C * 4 + 64));
         uint32_t* const ovf = c->pin_ovf.as<uint32_t>();
         uint64_t* const cur3 = c->pin_small.as<uint64_t>() + 48;
@@ -1667,18 +1626,18 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         // pangenome whose later clusters differ from its first is followed -- the read-back is not free)
         // (not in the re-run of a batch after the pattern table grew: its clusters have been counted)
         uint32_t learn_planned = 0;            // ... and plan_kernel's items of the last part (their clusters, their key counts)
-        if (!rerun && (c->reg_n < 8192 || (c->n_submits & 15) == 0)) {
+        if (!rerun && (c->part_model.n < 8192 || (c->n_submits & 15) == 0)) {
             for (uint32_t ci : todo) if (rec[ci].mode && rec[ci].vnstr >= 2) { learn = true; break; }
             if (use_plan && pass + 1 == P) learn_planned = std::min<uint32_t>(c->dplan[pass].pin_out.as<pf::PlanOut>()->n_items, 4096u);
         }
         if (learn) {
-            c->hs_count.resize(NI);
-            HIPCHK(hipMemcpyAsync(c->hs_count.data(), c->it_count.p, NI * 4, hipMemcpyDeviceToHost, c->stream));
+            hs.count.resize(NI);
+            HIPCHK(hipMemcpyAsync(hs.count.data(), c->it_count.p, NI * 4, hipMemcpyDeviceToHost, c->stream));
         }
         if (learn_planned) {
-            c->hs_plan.resize(2 * (size_t)learn_planned);
-            HIPCHK(hipMemcpyAsync(c->hs_plan.data(), dplan_ptrs(c->dplan[pass]).it_cluster, (size_t)learn_planned * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(c->hs_plan.data() + learn_planned, c->dplan[pass].it_count.p, (size_t)learn_planned * 4, hipMemcpyDeviceToHost, c->stream));
+            hs.plan.resize(2 * (size_t)learn_planned);
+            HIPCHK(hipMemcpyAsync(hs.plan.data(), dplan_ptrs(c->dplan[pass]).it_cluster, (size_t)learn_planned * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(hs.plan.data() + learn_planned, c->dplan[pass].it_count.p, (size_t)learn_planned * 4, hipMemcpyDeviceToHost, c->stream));
         }
         HIPCHK(hipMemcpyAsync(ovf, c->cl_overflow.p, (size_t)C * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(cur3, c->cursor.p, 24, hipMemcpyDeviceToHost, c->stream));
@@ -1688,48 +1647,36 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         cnt2[0] = cnt_pin[0]; cnt2[1] = cnt_pin[1]; cnt2[2] = cnt_pin[2];
         c->counters.n_unique = cur3[1]; c->counters.n_kept = cur3[2];
         lap("sync pass");
-        ar->used = cur3[0] - ar->base;
-        if (ar->used > ar->cap) return fail(PF_ERR_CAPACITY, "output arena overflow (%llu > %llu)",
-                                            (unsigned long long)ar->used, (unsigned long long)ar->cap);
+        PFCHK(close_arena(ar, cur3[0]));
         arena_base += ar->cap;
         arena_i++;
         if (!deferred.empty()) {                   // the earlier passes finished before this one
-            for (const Deferred& df : deferred) {
-                df.ar->used = c->pin_small.as<uint64_t>()[df.pin] - df.ar->base;
-                if (df.ar->used > df.ar->cap)
-                    return fail(PF_ERR_CAPACITY, "output arena overflow (%llu > %llu)", (unsigned long long)df.ar->used,
-                                (unsigned long long)df.ar->cap);
-            }
+            for (const Deferred& df : deferred) PFCHK(close_arena(df.ar, c->pin_small.as<uint64_t>()[df.pin]));
             deferred.clear();
             todo.resize(C);                        // every cluster has been through its first pass now
             std::iota(todo.begin(), todo.end(), 0u);
         }
         if (learn || learn_planned) {
-            if (c->reg_n >= 8192) {
-                c->reg_n *= 0.5; c->reg_x *= 0.5; c->reg_y *= 0.5; c->reg_xx *= 0.5; c->reg_xy *= 0.5; c->reg_yy *= 0.5;
-            }
+            PartModel& m = c->part_model;
+            if (m.n >= 8192) m.halve();
             uint32_t looked = 0;               // (the GPU waits while this runs: a few thousand clusters say enough)
-            for (uint32_t i = 0; i < learn_planned && looked < 4096; i++) {
-                const uint32_t ci = c->hs_plan[i];
-                if (ci >= C || ovf[ci] || !rec[ci].mode || rec[ci].vnstr < 2 || !rec[ci].vinst) continue;
+            // a cluster that did not overflow: what each of its further distinct sequences brought in
+            auto look = [&](uint32_t ci, uint64_t keys) {
+                if (ovf[ci] || !rec[ci].mode || rec[ci].vnstr < 2 || !rec[ci].vinst) return;
                 looked++;
                 const double D = (double)rec[ci].vnstr, L = (double)(rec[ci].vinst * mult) / D;
-                const double g = std::max(0.0, ((double)c->hs_plan[learn_planned + i] - L) / (D - 1.0));
-                c->reg_n += 1; c->reg_x += L; c->reg_y += g; c->reg_xx += L * L; c->reg_xy += L * g; c->reg_yy += g * g;
-            }
+                m.add(L, std::max(0.0, ((double)keys - L) / (D - 1.0)));
+            };
+            for (uint32_t i = 0; i < learn_planned && looked < 4096; i++)
+                if (hs.plan[i] < C) look(hs.plan[i], hs.plan[learn_planned + i]);
             if (learn)
-            for (size_t i = 0; i < NI && looked < 4096; i++) {
-                const Item& it = items[i];
-                if (it.is_extra || it.part != 0) continue;
-                const uint32_t ci = it.cluster;
-                if (ovf[ci] || !rec[ci].mode || rec[ci].vnstr < 2 || !rec[ci].vinst) continue;
-                looked++;
-                uint64_t keys = 0;
-                for (uint32_t q = 0; q < it.nparts; q++) keys += c->hs_count[i + q];
-                const double D = (double)rec[ci].vnstr, L = (double)(rec[ci].vinst * mult) / D;
-                const double g = std::max(0.0, ((double)keys - L) / (D - 1.0));
-                c->reg_n += 1; c->reg_x += L; c->reg_y += g; c->reg_xx += L * L; c->reg_xy += L * g; c->reg_yy += g * g;
-            }
+                for (size_t i = 0; i < NI && looked < 4096; i++) {
+                    const Item& it = hs.items[i];
+                    if (it.is_extra || it.part != 0) continue;
+                    uint64_t keys = 0;
+                    for (uint32_t q = 0; q < it.nparts; q++) keys += hs.count[i + q];
+                    look(it.cluster, keys);
+                }
         }
         std::vector<uint32_t> next;
         for (uint32_t ci : todo)
@@ -1747,24 +1694,13 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
             }
         if (!next.empty()) {
             c->timing.n_retried += (uint32_t)next.size();
-            HIPCHK(hipMemsetAsync(c->cl_overflow.p, 0, C1 * 4, c->stream));
+            HIPCHK(hipMemsetAsync(c->cl_overflow.p, 0, (size_t)std::max(C, 1u) * 4, c->stream));
         }
         todo.swap(next);
-        pass++;
-        if (todo.empty()) break;
+        return PF_OK;
     }
-    for (size_t a = arena_i; a < c->arenas.size(); a++) c->arenas[a]->used = 0;   // arenas of an earlier, longer batch
-    c->n_passes = arena_i;
-
-    // ---- MD5 of the patterns this batch created (cnt2: read with the last pass's results)
-    if (!C) {
-        HIPCHK(hipMemcpyAsync(cnt2, c->pt_counters.p, 12, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    if (cnt2[2]) return fail(PF_ERR_CAPACITY, "output arena overflow inside a kernel");
-    if (cnt2[1] || cnt2[0] > c->pt.pool) { *need = cnt2[0]; return PF_RETRY_PATTERNS; }
-    const uint32_t pid1 = cnt2[0];
-    if (pid1 > c->pid0) {
+    // ---- MD5 of the patterns this batch created, ids [pid0, pid1)
+    int launch_md5(uint32_t pid1) {
         pf::Md5Params mp{};
         mp.pat_bits = c->pat_bits.as<uint32_t>();
         mp.pat_nan = c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr;
@@ -1773,7 +1709,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         // int64 rows are the clusters' own rows: the int pass goes by cluster (cl_pattern) and runs BESIDE the float pass, on
         // the side stream, instead of behind it
         mp.cluster_pattern = c->cl_pattern.as<uint32_t>(); mp.n_clusters = C;
-        PFCHK(mark_begin(c, 5));
+        PFCHK(mark_begin(c, TimeCat::md5));
         // A small launch is spread over the chip: the float pass's workgroups (four waves, one per SIMD) number a few per
         // CU, and the dispatcher fills CUs with up to eight before it moves on -- a SIMD gets through its rows at one rate
         // however many waves share it, so the pass took as long as the FULLEST SIMD (a rank's share of configs[3]: 5 waves
@@ -1800,43 +1736,106 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         HIPCHK(hipEventRecord(c->ev_join, c->side));
         HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
         PFCHK(mark_end(c));
+        return PF_OK;
     }
+    // ---- timing (both streams have drained) and the batch's results, which become the context's
+    int publish_batch(uint32_t pid1, pf_result* counters) {
+        HIPCHK(hipEventElapsedTime(&c->timing.total_ms, c->ev_t0, c->ev_t1));
+        for (auto& e : c->events) {
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, e.a, e.b));
+            switch (e.cat) {
+                case TimeCat::scan: c->timing.scan_ms += ms; break;
+                case TimeCat::rows: c->timing.rows_ms += ms; break;
+                case TimeCat::emit: c->timing.emit_ms += ms; break;
+                case TimeCat::dedup: c->timing.dedup_ms += ms; break;
+                case TimeCat::pattern_rows: c->timing.patrows_ms += ms; break;
+                case TimeCat::md5: c->timing.md5_ms += ms; break;
+                case TimeCat::finish: c->timing.finish_ms += ms; break;
+            }
+        }
+        c->n_clusters = C; c->last = d; c->last_nseg = NSEG;
+        if (!c->n_strand_words) c->last.seg_strand_off = nullptr;
+        c->kt_bytes = 0; c->kt_pref_valid = false;
+        pf_result res{};
+        res.n_instances = total_inst; res.n_unique = c->counters.n_unique; res.n_kept = c->counters.n_kept;   // (the last pass's cursor)
+        res.n_new_patterns = pid1 - c->pid0; res.n_patterns = pid1; res.W = W; res.key_words = KW;
+        c->counters = res;
+        c->have_batch = true;
+        c->h_strand_fresh = false;
+        if (counters) *counters = c->counters;
+        return PF_OK;
+    }
+};
+
+int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* counters, uint64_t* need, bool rerun) {
+    c->have_batch = false;
+    kt_stream_end(c);                     // a kmers.tsv stream of the batch before is over
+    // whatever way this call ends, nothing it queued is still reading the caller's arrays or the pinned staging
+    // blocks afterwards (the successful path has waited already; an error return may come with work in flight)
+    struct Drain { hipStream_t s, s2; ~Drain() { (void)hipStreamSynchronize(s2); (void)hipStreamSynchronize(s); } } drain{c->stream, c->side};
+    if (b->n_segs && (!b->packed || !b->seg_word_off || !b->seg_len || !b->seg_sample || !b->seg_ord_base))
+        return fail(PF_ERR_ARG, "segment arrays missing");
+    if (b->n_clusters && (!b->cluster_seg_off || !b->cluster_nstrains || !b->cluster_npresab || !b->cluster_presab ||
+                          !b->cluster_ordinal))
+        return fail(PF_ERR_ARG, "cluster arrays missing");
+    if (b->n_extra && (!b->extra_cluster || !b->extra_ord || !b->extra_bits))
+        return fail(PF_ERR_ARG, "extra arrays missing");
+    for (auto& e : c->events) { c->ev_pool.push_back(e.a); c->ev_pool.push_back(e.b); }
+    c->events.clear();
+    c->timing = pf_timing{};
+    SubmitRun r(c, b, gth);
+    HIPCHK(hipEventRecord(c->ev_t0, c->stream));
+
+    PFCHK(r.upload_batch());
+    PFCHK(r.ensure_batch_outputs());
+    PFCHK(r.launch_dedup_parts());
+    r.lap("upload+dedup launch");
+
+    c->pid0 = c->n_patterns;
+    if (!rerun) c->n_submits++;
+    c->cluster_arena.assign(r.C, 0);
+    r.nparts.assign(r.C, 1);
+    c->counters = pf_result{};
+    // host-planned passes: the parts' (what plan_kernel left of them, queued back to back), then the re-runs
+    for (uint32_t pass = 0;; pass++) {
+        c->stage_slot = (int)(pass & 1);
+        if (pass < r.P) PFCHK(r.begin_part(pass));
+        if (r.todo.empty() && pass >= r.P) break;
+        Pass ps;
+        PFCHK(r.build_items(ps));
+        PFCHK(r.begin_arena(ps.arena_cap));
+        PFCHK(r.build_work_lists(ps));
+        PFCHK(r.upload_cursor_start());
+        r.lap("upload items");
+        for (size_t s = 0; s < ps.subs.size(); s++) PFCHK(r.launch_sub_batch(ps, s));
+        c->timing.n_items += (uint32_t)c->hs.items.size();
+        for (uint32_t ci : r.todo) c->timing.scan_packed_bytes += r.rec[ci].words * 8 * r.nparts[ci];
+        r.lap("launch pass");
+        if (pass + 1 < r.P) {
+            PFCHK(r.defer_pass());   // no wait: the next part's pass is built now and goes in behind this one
+            continue;
+        }
+        PFCHK(r.finish_pass(ps, pass, rerun));
+        if (r.todo.empty()) break;
+    }
+    for (size_t a = r.arena_i; a < c->arenas.size(); a++) c->arenas[a]->used = 0;   // arenas of an earlier, longer batch
+    c->n_passes = r.arena_i;
+
+    // ---- MD5 of the patterns this batch created (cnt2: read with the last pass's results)
+    if (!r.C) {
+        HIPCHK(hipMemcpyAsync(r.cnt2, c->pt_counters.p, 12, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (r.cnt2[2]) return fail(PF_ERR_CAPACITY, "output arena overflow inside a kernel");
+    if (r.cnt2[1] || r.cnt2[0] > c->pt.pool) { *need = r.cnt2[0]; return PF_RETRY_PATTERNS; }
+    const uint32_t pid1 = r.cnt2[0];
+    if (pid1 > c->pid0) PFCHK(r.launch_md5(pid1));
     c->n_patterns = pid1;
-    const uint64_t n_unique_total = c->counters.n_unique, n_kept_total = c->counters.n_kept;   // the last pass's cursor
     HIPCHK(hipEventRecord(c->ev_t1, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-
-    lap("md5 + final sync");
-    // ---- timing
-    HIPCHK(hipEventElapsedTime(&c->timing.total_ms, c->ev_t0, c->ev_t1));
-    for (auto& e : c->events) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e.a, e.b));
-        if (e.cat == 0) c->timing.scan_ms += ms;
-        else if (e.cat == 1) c->timing.rows_ms += ms;
-        else if (e.cat == 3) c->timing.dedup_ms += ms;
-        else if (e.cat == 4) c->timing.patrows_ms += ms;
-        else if (e.cat == 5) c->timing.md5_ms += ms;
-        else if (e.cat == 6) c->timing.finish_ms += ms;
-        else c->timing.emit_ms += ms;
-    }
-
-    c->n_clusters = C;
-    c->last = d; c->last_nseg = NSEG;
-    if (!c->n_strand_words) c->last.seg_strand_off = nullptr;
-    c->kt_bytes = 0; c->kt_pref_valid = false;
-    c->counters = pf_result{};
-    c->counters.n_instances = total_inst;
-    c->counters.n_unique = n_unique_total;
-    c->counters.n_kept = n_kept_total;
-    c->counters.n_new_patterns = pid1 - c->pid0;
-    c->counters.n_patterns = pid1;
-    c->counters.W = W;
-    c->counters.key_words = KW;
-    c->have_batch = true;
-    c->h_strand_fresh = false;
-    if (counters) *counters = c->counters;
-    return PF_OK;
+    r.lap("md5 + final sync");
+    return r.publish_batch(pid1, counters);
 }
 }  // namespace
 
