@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .engine import BATCH_ARRAYS
 from .packing import pack_codes
 
 
@@ -62,21 +63,9 @@ def from_host_batch(engine, hb):
     db = DeviceBatch(engine)
     b = db.batch
     b.n_clusters, b.n_segs, b.n_words, b.on_device = hb.n_clusters, len(hb.seg_len), len(hb.packed), 1
-    b.packed = db._put("packed", hb.packed)
-    b.seg_word_off = db._put("seg_word_off", hb.seg_word_off)
-    b.seg_len = db._put("seg_len", hb.seg_len)
-    b.seg_sample = db._put("seg_sample", hb.seg_sample)
-    b.seg_ord_base = db._put("seg_ord_base", hb.seg_ord_base)
-    b.cluster_seg_off = db._put("cluster_seg_off", hb.cluster_seg_off)
-    b.cluster_nstrains = db._put("cluster_nstrains", hb.cluster_nstrains)
-    b.cluster_npresab = db._put("cluster_npresab", hb.cluster_npresab)
-    b.cluster_presab = db._put("cluster_presab", hb.cluster_presab)
-    b.cluster_ordinal = db._put("cluster_ordinal", hb.cluster_ordinal)
     b.n_extra = len(hb.extra_ord)
-    if b.n_extra:
-        b.extra_cluster = db._put("extra_cluster", hb.extra_cluster)
-        b.extra_ord = db._put("extra_ord", hb.extra_ord)
-        b.extra_bits = db._put("extra_bits", hb.extra_bits)
+    for f in (BATCH_ARRAYS if b.n_extra else BATCH_ARRAYS[:-3]):
+        setattr(b, f, db._put(f, getattr(hb, f)))
     db.n_instances = hb.n_instances
     db.packed_bytes = int(((hb.seg_len.astype(np.int64) + 3) // 4).sum())
     db.n_clusters, db.n_segs = hb.n_clusters, len(hb.seg_len)

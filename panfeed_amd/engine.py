@@ -5,12 +5,14 @@ ctypes, and renders the three TSV bodies exactly as the reference writes them
 One ``Engine`` = one panfeed run on one GPU: it owns the run-global pattern set
 (panfeed.py:149-150) in device memory, so clusters must be fed in processing order.
 """
+import contextlib
 import ctypes as C
+import time
 
 import numpy as np
 
 from . import _lib
-from .packing import build_batch_native, decode_keys, maf_tables
+from .packing import _release_held, _seqinfo_columns, build_batch_native, decode_keys, maf_tables
 
 KMERS_TSV_HEADER = ("cluster\tstrain\tfeature_id\tcontig\tfeature_strand\tcontig_start\tcontig_end\t"
                     "gene_start\tgene_end\tstrand\tk-mer\n")           # input.py:243
@@ -25,12 +27,21 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
 
+def _mem(ptr, n):
+    """n bytes at `ptr` as a memoryview of bytes: no copy, valid as long as the memory is"""
+    p = ptr.value if isinstance(ptr, C.c_void_p) else ptr
+    return memoryview((C.c_char * int(n)).from_address(p)).cast("B") if n else memoryview(b"")
+
+
 def _take(ptr, n):
     """n bytes at `ptr` as `bytes` (ctypes.string_at takes a C int: texts beyond 2 GiB need this)"""
-    p = ptr.value if isinstance(ptr, C.c_void_p) else ptr
-    if not n:
-        return b""
-    return bytes(memoryview((C.c_char * int(n)).from_address(p)))
+    return bytes(_mem(ptr, n))
+
+
+# pf_batch's array fields, under the names HostBatch gives them too: Engine.submit_host_batch hands them over by host
+# pointer, devbatch.from_host_batch uploads them (the last three only when the batch has slow-path rows)
+BATCH_ARRAYS = ("packed", "seg_word_off", "seg_len", "seg_sample", "seg_ord_base", "cluster_seg_off", "cluster_nstrains",
+                "cluster_npresab", "cluster_presab", "cluster_ordinal", "extra_cluster", "extra_ord", "extra_bits")
 
 
 class OwnedText:
@@ -39,7 +50,7 @@ class OwnedText:
 
     def __init__(self, L, ptr, n):
         self._L, self._p, self._n = L, (ptr.value if isinstance(ptr, C.c_void_p) else ptr), int(n)
-        self.view = memoryview((C.c_char * self._n).from_address(self._p)).cast("B") if self._n else memoryview(b"")
+        self.view = _mem(self._p, self._n)
 
     def __len__(self):
         return self._n
@@ -76,9 +87,8 @@ class DeviceText:
         ptr, nb = C.c_void_p(), C.c_uint64()
         while off < self._n:
             _lib.check(eng.L.pf_device_text_chunk(eng.ctx, off, int(max_bytes), C.byref(ptr), C.byref(nb)))
-            n = int(nb.value)
-            yield memoryview((C.c_char * n).from_address(ptr.value)).cast("B")
-            off += n
+            yield _mem(ptr, nb.value)
+            off += int(nb.value)
 
     def __bytes__(self):
         out = bytearray(self._n)
@@ -105,6 +115,19 @@ class BatchOutput:
         self.per_cluster = []   # multiple_files: [(idx, kmers_tsv, kmers_to_hashes, hashes_to_patterns)]
         self.stats = {}
         self.timing = {}
+
+
+def _batch_stats(hb, res, patterns, **streamed):
+    """the counters of one batch (BatchOutput.stats); `streamed`: the kmers_tsv_* counters of a device-text batch"""
+    return {"clusters": int(hb.n_clusters), "instances": int(hb.n_instances), **streamed,
+            "device_instances": int(res.n_instances), "unique_kmers": int(res.n_unique), "kept_kmers": int(res.n_kept),
+            "new_patterns": int(res.n_new_patterns), "patterns": int(patterns)}
+
+
+def add_batch_stats(totals, out, keys=("clusters", "instances", "kept_kmers", "device_ms")):
+    """add a finished batch's counters (and its device time) to the totals a run reports"""
+    for key in keys:
+        totals[key] += out.timing.get("total_ms", 0.0) if key == "device_ms" else out.stats.get(key, 0)
 
 
 class Engine:
@@ -165,20 +188,9 @@ class Engine:
         b.n_segs = len(hb.seg_len)
         b.n_words = len(hb.packed)
         b.on_device = 0
-        b.packed = _ptr(hb.packed)
-        b.seg_word_off = _ptr(hb.seg_word_off)
-        b.seg_len = _ptr(hb.seg_len)
-        b.seg_sample = _ptr(hb.seg_sample)
-        b.seg_ord_base = _ptr(hb.seg_ord_base)
-        b.cluster_seg_off = _ptr(hb.cluster_seg_off)
-        b.cluster_nstrains = _ptr(hb.cluster_nstrains)
-        b.cluster_npresab = _ptr(hb.cluster_npresab)
-        b.cluster_presab = _ptr(hb.cluster_presab)
-        b.cluster_ordinal = _ptr(hb.cluster_ordinal)
         b.n_extra = len(hb.extra_ord)
-        b.extra_cluster = _ptr(hb.extra_cluster)
-        b.extra_ord = _ptr(hb.extra_ord)
-        b.extra_bits = _ptr(hb.extra_bits)
+        for f in BATCH_ARRAYS:
+            setattr(b, f, _ptr(getattr(hb, f)))
         if hb.n_strand_words:
             b.seg_strand_off = _ptr(hb.seg_strand_off)
             b.n_strand_words = hb.n_strand_words
@@ -261,7 +273,6 @@ class Engine:
         says how many bytes went, `"kmers_tsv_ranges"` / `"kmers_tsv_peak_device_bytes"` in how many ranges and with how
         much device memory at most."""
         from concurrent.futures import ThreadPoolExecutor
-        import time as _time
         it = iter(host_batches)
         # where the wall time of this run goes (seconds; bench.py's end-to-end leg): the packer thread's busy time
         # (read + pack, overlapped with the GPU), the time this thread waited for it, pf_submit (upload + kernels),
@@ -270,29 +281,29 @@ class Engine:
                             "batches": 0}
 
         def pack_next():
-            t0 = _time.perf_counter()
+            t0 = time.perf_counter()
             hb = next(it, None)
-            st["pack_busy_s"] += _time.perf_counter() - t0
+            st["pack_busy_s"] += time.perf_counter() - t0
             return hb
 
         with ThreadPoolExecutor(max_workers=1) as pool:      # one packer thread keeps the record order
             pending = [pool.submit(pack_next) for _ in range(max(1, prefetch))]
             while pending:
-                t0 = _time.perf_counter()
+                t0 = time.perf_counter()
                 hb = pending.pop(0).result()
-                st["pack_wait_s"] += _time.perf_counter() - t0
+                st["pack_wait_s"] += time.perf_counter() - t0
                 if hb is None:
                     break
                 pending.append(pool.submit(pack_next))
                 self.next_ordinal = int(hb.cluster_ordinal[-1]) + 1 if hb.n_clusters else self.next_ordinal
                 if before_first_submit is not None:
-                    t0 = _time.perf_counter()
+                    t0 = time.perf_counter()
                     before_first_submit()
                     before_first_submit = None
-                    st["first_submit_wait_s"] = _time.perf_counter() - t0
-                t0 = _time.perf_counter()
+                    st["first_submit_wait_s"] = time.perf_counter() - t0
+                t0 = time.perf_counter()
                 res = self.submit_host_batch(hb)
-                t1 = _time.perf_counter()
+                t1 = time.perf_counter()
                 st["submit_s"] += t1 - t0
                 st["batches"] += 1
                 texts = None
@@ -316,11 +327,8 @@ class Engine:
                         out.kmers_tsv = b""
                     else:
                         out.kmers_tsv = bytes(self.render_targets_device(hb)) if hb.n_targets else b""
-                    out.stats = {"clusters": int(hb.n_clusters), "instances": int(hb.n_instances), "kmers_tsv_streamed": streamed,
-                                 "kmers_tsv_ranges": ranges, "kmers_tsv_peak_device_bytes": peak,
-                                 "device_instances": int(res.n_instances), "unique_kmers": int(res.n_unique),
-                                 "kept_kmers": int(res.n_kept), "new_patterns": int(res.n_new_patterns),
-                                 "patterns": self.pattern_count()}
+                    out.stats = _batch_stats(hb, res, self.pattern_count(), kmers_tsv_streamed=streamed,
+                                             kmers_tsv_ranges=ranges, kmers_tsv_peak_device_bytes=peak)
                     out.timing = self.timing()
                 else:
                     out = self._render(hb, self.fetch(), defer_patterns)
@@ -329,7 +337,7 @@ class Engine:
                         out.stats["kmers_tsv_streamed"] = len(out.kmers_tsv)
                         targets_sink(out.kmers_tsv)
                         out.kmers_tsv = ""
-                st["text_s"] += _time.perf_counter() - t1
+                st["text_s"] += time.perf_counter() - t1
                 st["device_ms"] += out.timing.get("total_ms", 0.0)
                 yield out
 
@@ -427,10 +435,7 @@ class Engine:
         out.kmers_to_hashes = kh_all
         out.hashes_to_patterns = hp_all
         out.kmers_tsv = "".join("".join(x) for x in kt_by_cluster)
-        out.stats = {"clusters": int(hb.n_clusters), "instances": int(hb.n_instances),
-                     "device_instances": int(res.n_instances),
-                     "unique_kmers": int(res.n_unique), "kept_kmers": int(res.n_kept),
-                     "new_patterns": int(res.n_new_patterns), "patterns": int(res.n_patterns)}
+        out.stats = _batch_stats(hb, res, res.n_patterns)
         out.timing = self.timing()
         return out
 
@@ -445,8 +450,7 @@ class Engine:
         _lib.check(self.L.pf_render_device_ex(self.ctx, names, extra, len(hb.extra_keys),
                                               _lib.RENDER_NO_PATTERN_ROWS if defer_patterns else 0,
                                               C.byref(kh), C.byref(kn), C.byref(hp), C.byref(hn)))
-        mk = (lambda p, n: memoryview((C.c_char * n).from_address(p)).cast("B") if n else memoryview(b""))
-        return mk(kh.value, kn.value), mk(hp.value, hn.value)
+        return _mem(kh, kn.value), _mem(hp, hn.value)
 
     # ------------------------------------------------------------------ run-global patterns (multi-GPU)
     def export_patterns(self):
@@ -477,24 +481,12 @@ class Engine:
     def render_targets_device(self, hb):
         """kmers.tsv rows of every target sequence of `hb` (the last submit), written on the device
         (pf_render_kmers_tsv_device): a DeviceText.  Same bytes as `_render_targets(hb, hb.targets)`."""
-        import time as _time
-        t0 = _time.time()
-        if hb.target_table is not None and hb.target_table.resolve is not None and hb._targets is None:
-            rec, n, keep, held = self._marshal_table(hb, hb.target_table)
-        else:
-            rec, n, keep = self._marshal_targets(hb, hb.targets)
-            held = None
-        try:
-            arr = C.cast(rec.ctypes.data, C.POINTER(_lib.TargetSeq))
-            nb = C.c_uint64()
-            t1 = _time.time()
+        t0 = time.time()
+        nb = C.c_uint64()
+        with self._target_records(hb) as (arr, n):
+            t1 = time.time()
             _lib.check(self.L.pf_render_kmers_tsv_device(self.ctx, arr, n, C.byref(nb)))
-        finally:
-            if held is not None:
-                from .packing import _release_held
-                _release_held(held)
-        del keep
-        self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": _time.time() - t1, "copy_s": 0.0}
+        self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": time.time() - t1, "copy_s": 0.0}
         return DeviceText(self, nb.value)
 
     def stream_targets_device(self, hb, sink, budget=None):
@@ -502,143 +494,97 @@ class Engine:
         at most `budget` bytes of device memory (default: targets_text_budget) and handed to `sink` block by block (a
         memoryview of pinned memory, valid during the call) -- pf_kmers_tsv_stream_begin / _next.  The blocks joined are
         the bytes of `render_targets_device(hb)`.  Returns (bytes, ranges, peak device text bytes)."""
-        import time as _time
-        t0 = _time.time()
+        t0 = time.time()
         budget = self.targets_text_budget if budget is None else int(budget)
-        if hb.target_table is not None and hb.target_table.resolve is not None and hb._targets is None:
-            rec, n, keep, held = self._marshal_table(hb, hb.target_table)
-        else:
-            rec, n, keep = self._marshal_targets(hb, hb.targets)
-            held = None
         streamed = 0
-        try:
-            # (the records and the strings they point to are read until the last block: the host renders its share of
-            # every range when the range is written)
-            arr = C.cast(rec.ctypes.data, C.POINTER(_lib.TargetSeq))
+        # (the records and the strings they point to are read until the last block: the host renders its share of
+        # every range when the range is written)
+        with self._target_records(hb) as (arr, n):
             total, ranges, peak = C.c_uint64(), C.c_uint32(), C.c_uint64()
-            t1 = _time.time()
+            t1 = time.time()
             _lib.check(self.L.pf_kmers_tsv_stream_begin(self.ctx, arr, n, budget, C.byref(total), C.byref(ranges),
                                                         C.byref(peak)))
             ptr, nb = C.c_void_p(), C.c_uint64()
             while True:
                 _lib.check(self.L.pf_kmers_tsv_stream_next(self.ctx, C.byref(ptr), C.byref(nb)))
-                m = int(nb.value)
-                if not m:
+                if not nb.value:
                     break
-                sink(memoryview((C.c_char * m).from_address(ptr.value)).cast("B"))
-                streamed += m
-        finally:
-            if held is not None:
-                from .packing import _release_held
-                _release_held(held)
-            del keep
+                sink(_mem(ptr, nb.value))
+                streamed += int(nb.value)
         if streamed != int(total.value):
             raise _lib.PanfeedHipError(_lib.ERR_STATE, f"kmers.tsv stream: {streamed} bytes handed out of {total.value}")
-        self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": _time.time() - t1, "copy_s": 0.0}
+        self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": time.time() - t1, "copy_s": 0.0}
         return streamed, int(ranges.value), int(peak.value)
 
-    _TS = np.dtype([("cluster", "u8"), ("strain", "u8"), ("id", "u8"), ("chromosome", "u8"), ("sequence", "u8"),
-                    ("compsequence", "u8"), ("len", "u4"), ("strand", "i4"), ("start", "i8"), ("end", "i8"),
-                    ("offset", "i8"), ("n_segs", "u4"), ("n_ambig", "u4"), ("seg_index", "u8"), ("seg_start", "u8"),
-                    ("seg_nwin", "u8"), ("ambig_pos", "u8"), ("ambig_used", "u8"), ("ambig_key", "u8")])
-
-    def _marshal_table(self, hb, tt):
-        """pf_target_seq records straight from the packer's flat target arrays (packing.TargetTable): no per-sequence
-        Python objects, numpy columns only.  Returns (records, n, what must stay alive, held string references)."""
-        from .packing import _seqinfo_columns
-        TS = self._TS
-        assert TS.itemsize == C.sizeof(_lib.TargetSeq)
-        n = len(tt)
-        rec = np.zeros(max(n, 1), dtype=TS)
-        keep = [rec]
-        held = None
-        if not n:
-            return rec, 0, keep, None
-
-        def block(strings):
-            blob = ("\0".join(strings) + "\0").encode()
-            ends = np.flatnonzero(np.frombuffer(blob, dtype=np.uint8) == 0)
-            if len(ends) != len(strings):
-                raise ValueError("a NUL byte inside a name or sequence")
-            starts = np.concatenate(([0], ends[:-1] + 1)).astype(np.uint64)
-            keep.append(blob)
-            return starts + np.uint64(C.cast(C.c_char_p(blob), C.c_void_p).value), (ends - starts.astype(np.int64)).astype(np.uint32)
-
-        ci, strains, seqs = tt.resolve(tt.t_seq)
-        rec["cluster"][:n] = block(list(hb.idx))[0][ci]
-        for field, values in (("strain", [str(x) for x in strains]), ("id", [str(s.id) for s in seqs]),
-                              ("chromosome", [str(s.chromosome) for s in seqs])):
-            uniq = {}
-            idx = np.fromiter((uniq.setdefault(v, len(uniq)) for v in values), dtype=np.int64, count=n)
-            rec[field][:n] = block(list(uniq))[0][idx]
-        fast = _seqinfo_columns(seqs)
-        if fast is not None:
-            a_seq, a_comp, a_len, held = fast
-            rec["sequence"][:n], rec["compsequence"][:n], rec["len"][:n] = a_seq, a_comp, a_len
-        else:
-            addr, lens = block([s.sequence for s in seqs])
-            rec["sequence"][:n], rec["len"][:n] = addr, lens
-            addr, lens2 = block([s.compsequence for s in seqs])
-            rec["compsequence"][:n] = addr
-            if not np.array_equal(lens, lens2):
-                raise ValueError("sequence and compsequence of different lengths")
-        rec["strand"][:n] = np.fromiter((int(s.strand) for s in seqs), dtype=np.int32, count=n)
-        rec["start"][:n] = np.fromiter((int(s.start) for s in seqs), dtype=np.int64, count=n)
-        rec["end"][:n] = np.fromiter((int(s.end) for s in seqs), dtype=np.int64, count=n)
-        rec["offset"][:n] = np.fromiter((int(s.offset) for s in seqs), dtype=np.int64, count=n)
-        so, ao = tt.t_so.astype(np.uint64), tt.t_ao.astype(np.uint64)
-        cols = [np.ascontiguousarray(x, dtype=np.uint32) if len(x) else np.zeros(1, np.uint32) for x in (tt.t_si, tt.t_ss, tt.t_sn)]
-        keep += cols
-        rec["n_segs"][:n] = np.diff(tt.t_so.astype(np.int64))
-        for field, col in zip(("seg_index", "seg_start", "seg_nwin"), cols):
-            rec[field][:n] = np.uint64(col.ctypes.data) + so[:-1] * np.uint64(4)
-        rec["n_ambig"][:n] = np.diff(tt.t_ao.astype(np.int64))
-        ap = np.ascontiguousarray(tt.t_ap, dtype=np.uint32) if len(tt.t_ap) else np.zeros(1, np.uint32)
-        au = np.ascontiguousarray(tt.t_au, dtype=np.int8) if len(tt.t_au) else np.zeros(1, np.int8)
-        akeys = bytes(tt.akeys) + b"\0"
-        kaddr = np.uint64(C.cast(C.c_char_p(akeys), C.c_void_p).value) + np.arange(max(len(tt.t_ap), 1), dtype=np.uint64) * np.uint64(tt.k)
-        kaddr = np.ascontiguousarray(kaddr)
-        keep += [ap, au, akeys, kaddr]
-        rec["ambig_pos"][:n] = np.uint64(ap.ctypes.data) + ao[:-1] * np.uint64(4)
-        rec["ambig_used"][:n] = np.uint64(au.ctypes.data) + ao[:-1]
-        rec["ambig_key"][:n] = np.uint64(kaddr.ctypes.data) + ao[:-1] * np.uint64(8)
-        return rec, n, keep, held
-
-    def _render_targets(self, hb, metas, as_bytes=False, owned=False):
-        """kmers.tsv rows of `metas` (packing.SeqMeta, in order) through pf_render_kmers_tsv: str, `bytes` (as_bytes) or
-        the library's own block without a copy (owned: an OwnedText)"""
-        import time as _time
-        t0 = _time.time()
-        rec, n, keep = self._marshal_targets(hb, metas)
-        arr = C.cast(rec.ctypes.data, C.POINTER(_lib.TargetSeq))
+    def _render_targets(self, hb, metas, owned=False):
+        """kmers.tsv rows of `metas` (packing.SeqMeta, in order) through pf_render_kmers_tsv: str, or the library's own
+        block without a copy (owned: an OwnedText)"""
+        t0 = time.time()
         buf, nb = C.c_void_p(), C.c_uint64()
         sso = hb.seg_strand_off.ctypes.data_as(C.c_void_p) if hb.n_strand_words else None
-        t1 = _time.time()
-        _lib.check(self.L.pf_render_kmers_tsv(self.ctx, arr, n, sso, C.byref(buf), C.byref(nb)))
-        t2 = _time.time()
-        del keep
+        with self._target_records(hb, metas) as (arr, n):
+            t1 = time.time()
+            _lib.check(self.L.pf_render_kmers_tsv(self.ctx, arr, n, sso, C.byref(buf), C.byref(nb)))
+        t2 = time.time()
         if owned:
             self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": t2 - t1, "copy_s": 0.0}
             return OwnedText(self.L, buf, nb.value)
         text = _take(buf, nb.value)
         self.L.pf_free_text(buf)
         # where the time of the last call went: Python marshalling of the records, the library's renderer, the copy out
-        self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": t2 - t1, "copy_s": _time.time() - t2}
-        return text if as_bytes else text.decode()
+        self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": t2 - t1, "copy_s": time.time() - t2}
+        return text.decode()
 
-    def _marshal_targets(self, hb, metas):
-        """pf_target_seq records of `metas` (packing.SeqMeta): (records, n, what must stay alive while they are used)"""
-        n = len(metas)
+    _TS = np.dtype([("cluster", "u8"), ("strain", "u8"), ("id", "u8"), ("chromosome", "u8"), ("sequence", "u8"),
+                    ("compsequence", "u8"), ("len", "u4"), ("strand", "i4"), ("start", "i8"), ("end", "i8"),
+                    ("offset", "i8"), ("n_segs", "u4"), ("n_ambig", "u4"), ("seg_index", "u8"), ("seg_start", "u8"),
+                    ("seg_nwin", "u8"), ("ambig_pos", "u8"), ("ambig_used", "u8"), ("ambig_key", "u8")])
+
+    @staticmethod
+    def _target_columns(hb, metas):
+        """What the pf_target_seq records of a batch are made of: the packer's flat arrays (t_so, t_si, t_ss, t_sn, t_ao,
+        t_ap, t_au, the ambiguous windows' keys back to back) and, per sequence, (cluster indices, strain names,
+        Seqinfos).  metas=None: every target sequence of `hb`, straight from packing.TargetTable where the records behind
+        it are still there -- no per-sequence Python objects; else from the SeqMeta objects, flattened."""
+        tt = hb.target_table
+        if metas is None and tt is not None and tt.resolve is not None and hb._targets is None:
+            return (tt.t_so, tt.t_si, tt.t_ss, tt.t_sn, tt.t_ao, tt.t_ap, tt.t_au, bytes(tt.akeys)), tt.resolve(tt.t_seq)
+        metas = hb.targets if metas is None else metas
+        who = (np.fromiter((m.cluster for m in metas), dtype=np.int64, count=len(metas)), [m.strain for m in metas],
+               [m.seq for m in metas])
+        # ACGT runs: (segment index, first window, windows) per run, flat
+        t_so = np.concatenate(([0], np.cumsum([len(m.segs) for m in metas], dtype=np.int64)))
+        runs = np.array([x for m in metas for t in m.segs for x in t], dtype=np.uint32).reshape(-1, 3)
+        # windows with a non-ACGT letter (rare): position, strand used and text, as the packer worked them out
+        t_ao = np.concatenate(([0], np.cumsum([len(m.ambig) for m in metas], dtype=np.int64)))
+        amb = [(q, m.ambig[q]) for m in metas if m.ambig for q in sorted(m.ambig)]
+        t_ap = np.array([q for q, _ in amb], dtype=np.uint32)
+        t_au = np.array([a[1] for _, a in amb], dtype=np.int8)
+        akeys = "".join(a[0] for _, a in amb).encode("latin-1")
+        if len(akeys) != hb.k * len(amb):
+            raise ValueError("an ambiguous window's text is not k letters long")
+        return (t_so, runs[:, 0], runs[:, 1], runs[:, 2], t_ao, t_ap, t_au, akeys), who
+
+    @contextlib.contextmanager
+    def _target_records(self, hb, metas=None):
+        """`with` this: (pf_target_seq array, n) of the target sequences of `hb` -- all of them, or `metas`
+        (packing.SeqMeta, in order).  The records, and the strings and arrays they point into, live as long as the
+        block; the references `_seqinfo_columns` holds on the sequences' str objects go back when it ends, error or not."""
         # The C structs are filled column by column (numpy) instead of sequence by sequence (ctypes): every kind of
         # string goes into ONE NUL-separated block whose pieces are addressed by offset, the few per-sequence lists
         # (ACGT runs, non-ACGT windows) into flat arrays.  23 -> ~4 us per target sequence.
         TS = self._TS
         assert TS.itemsize == C.sizeof(_lib.TargetSeq)
+        n = len(metas) if metas is not None else hb.n_targets
         rec = np.zeros(max(n, 1), dtype=TS)
-        keep = [rec]
+        arr = C.cast(rec.ctypes.data, C.POINTER(_lib.TargetSeq))
+        if not n:
+            yield arr, 0
+            return
+        keep = []
 
         def block(strings):
-            """addresses of `strings` laid out NUL-terminated in one bytes object"""
+            """(addresses, lengths) of `strings` laid out NUL-terminated in one bytes object"""
             blob = ("\0".join(strings) + "\0").encode()
             ends = np.flatnonzero(np.frombuffer(blob, dtype=np.uint8) == 0)
             if len(ends) != len(strings):
@@ -648,53 +594,46 @@ class Engine:
             base = C.cast(C.c_char_p(blob), C.c_void_p).value
             return starts + np.uint64(base), (ends - starts.astype(np.int64)).astype(np.uint32)
 
-        if n:
-            seqs = [m.seq for m in metas]
-            # names repeat (a cluster, a strain, a contig): one copy each
-            for field, values in (("cluster", [hb.idx[m.cluster] for m in metas]), ("strain", [str(m.strain) for m in metas]),
-                                  ("id", [str(s.id) for s in seqs]), ("chromosome", [str(s.chromosome) for s in seqs])):
-                uniq = {}
-                idx = np.fromiter((uniq.setdefault(v, len(uniq)) for v in values), dtype=np.int64, count=n)
-                addr, _ = block(list(uniq))
-                rec[field][:n] = addr[idx]
-            addr, lens = block([s.sequence for s in seqs])
-            rec["sequence"][:n], rec["len"][:n] = addr, lens
-            addr, lens2 = block([s.compsequence for s in seqs])
-            rec["compsequence"][:n] = addr
-            if not np.array_equal(lens, lens2):
+        (t_so, t_si, t_ss, t_sn, t_ao, t_ap, t_au, akeys), (ci, strains, seqs) = self._target_columns(hb, metas)
+        rec["cluster"] = block(list(hb.idx))[0][ci]
+        # names repeat (a strain, a contig): one copy each
+        for field, values in (("strain", [str(x) for x in strains]), ("id", [str(s.id) for s in seqs]),
+                              ("chromosome", [str(s.chromosome) for s in seqs])):
+            uniq = {}
+            idx = np.fromiter((uniq.setdefault(v, len(uniq)) for v in values), dtype=np.int64, count=n)
+            rec[field] = block(list(uniq))[0][idx]
+        rec["strand"] = np.fromiter((int(s.strand) for s in seqs), dtype=np.int32, count=n)
+        rec["start"] = np.fromiter((int(s.start) for s in seqs), dtype=np.int64, count=n)
+        rec["end"] = np.fromiter((int(s.end) for s in seqs), dtype=np.int64, count=n)
+        rec["offset"] = np.fromiter((int(s.offset) for s in seqs), dtype=np.int64, count=n)
+        so, ao = np.asarray(t_so).astype(np.uint64), np.asarray(t_ao).astype(np.uint64)
+        cols = [np.ascontiguousarray(x, dtype=np.uint32) if len(x) else np.zeros(1, np.uint32) for x in (t_si, t_ss, t_sn)]
+        rec["n_segs"] = np.diff(so.astype(np.int64))
+        for field, col in zip(("seg_index", "seg_start", "seg_nwin"), cols):
+            rec[field] = np.uint64(col.ctypes.data) + so[:-1] * np.uint64(4)
+        rec["n_ambig"] = np.diff(ao.astype(np.int64))
+        ap = np.ascontiguousarray(t_ap, dtype=np.uint32) if len(t_ap) else np.zeros(1, np.uint32)
+        au = np.ascontiguousarray(t_au, dtype=np.int8) if len(t_au) else np.zeros(1, np.int8)
+        akeys += b"\0"
+        # (the library copies k bytes from each key's address, pf_render_kmers_tsv: no terminator between the keys)
+        kaddr = np.ascontiguousarray(np.uint64(C.cast(C.c_char_p(akeys), C.c_void_p).value) +
+                                     np.arange(max(len(t_ap), 1), dtype=np.uint64) * np.uint64(hb.k))
+        keep += cols + [ap, au, akeys, kaddr]
+        rec["ambig_pos"] = np.uint64(ap.ctypes.data) + ao[:-1] * np.uint64(4)
+        rec["ambig_used"] = np.uint64(au.ctypes.data) + ao[:-1]
+        rec["ambig_key"] = np.uint64(kaddr.ctypes.data) + ao[:-1] * np.uint64(8)
+        # the sequences last: from here to the end of the block the str objects are held by reference
+        fast = _seqinfo_columns(seqs)
+        if fast is None:
+            held = None
+            rec["sequence"], rec["len"] = block([s.sequence for s in seqs])
+            rec["compsequence"], lens2 = block([s.compsequence for s in seqs])
+            if not np.array_equal(rec["len"], lens2):
                 raise ValueError("sequence and compsequence of different lengths")
-            rec["strand"][:n] = np.fromiter((int(s.strand) for s in seqs), dtype=np.int32, count=n)
-            rec["start"][:n] = np.fromiter((int(s.start) for s in seqs), dtype=np.int64, count=n)
-            rec["end"][:n] = np.fromiter((int(s.end) for s in seqs), dtype=np.int64, count=n)
-            rec["offset"][:n] = np.fromiter((int(s.offset) for s in seqs), dtype=np.int64, count=n)
-            # ACGT runs: (segment index, first window, windows) per run, flat
-            nseg = np.fromiter((len(m.segs) for m in metas), dtype=np.int64, count=n)
-            flat = np.array([x for m in metas for t in m.segs for x in t], dtype=np.uint32).reshape(-1, 3)
-            cols = [np.ascontiguousarray(flat[:, j]) for j in range(3)] if len(flat) else [np.zeros(1, np.uint32)] * 3
-            keep += cols
-            soff = (np.concatenate(([0], np.cumsum(nseg)[:-1])) * 4).astype(np.uint64)
-            rec["n_segs"][:n] = nseg
-            for field, col in zip(("seg_index", "seg_start", "seg_nwin"), cols):
-                rec[field][:n] = np.uint64(col.ctypes.data) + soff
-            # windows with a non-ACGT letter (rare): position, strand used and text, as the packer worked them out
-            namb = np.fromiter((len(m.ambig) for m in metas), dtype=np.int64, count=n)
-            rec["n_ambig"][:n] = namb
-            tot = int(namb.sum())
-            ap = np.zeros(max(tot, 1), dtype=np.uint32)
-            au = np.zeros(max(tot, 1), dtype=np.int8)
-            akeys = []
-            at = 0
-            for i in np.flatnonzero(namb):
-                m = metas[int(i)]
-                for q in sorted(m.ambig):
-                    ap[at], au[at] = q, m.ambig[q][1]
-                    akeys.append(m.ambig[q][0])
-                    at += 1
-            kaddr = block(akeys)[0] if akeys else np.zeros(1, dtype=np.uint64)
-            kaddr = np.ascontiguousarray(kaddr)
-            keep += [ap, au, kaddr]
-            aoff = np.concatenate(([0], np.cumsum(namb)[:-1])).astype(np.uint64)
-            rec["ambig_pos"][:n] = np.uint64(ap.ctypes.data) + aoff * np.uint64(4)
-            rec["ambig_used"][:n] = np.uint64(au.ctypes.data) + aoff
-            rec["ambig_key"][:n] = np.uint64(kaddr.ctypes.data) + aoff * np.uint64(8)
-        return rec, n, keep
+        else:
+            rec["sequence"], rec["compsequence"], rec["len"], held = fast
+        try:
+            yield arr, n
+        finally:
+            if held is not None:
+                _release_held(held)

@@ -1,10 +1,11 @@
 """Output file surface of the hot path (names, headers, gzip mode), as the reference fixes it in
 /root/reference/panfeed/input.py:235-259 and /root/reference/panfeed/panfeed.py:116-129."""
 import ctypes as C
+import io
 import os
 
 from . import _lib
-from .engine import KMERS_TSV_HEADER, KMERS_TO_HASHES_HEADER, hashes_to_patterns_header
+from .engine import KMERS_TSV_HEADER, KMERS_TO_HASHES_HEADER, _mem, hashes_to_patterns_header
 
 
 class ParallelGzipWriter:
@@ -38,7 +39,7 @@ class ParallelGzipWriter:
         out, n = C.c_void_p(), C.c_uint64()
         _lib.check(self.L.pf_gzip_members(data, len(data), self.level, self.chunk_bytes, C.byref(out), C.byref(n)))
         try:
-            self.fh.write(memoryview((C.c_char * n.value).from_address(out.value)) if n.value else b"")
+            self.fh.write(_mem(out, n.value))
         finally:
             self.L.pf_free_text(out)
         self.wrote = True
@@ -89,7 +90,42 @@ def create_hash_files(output, compress=False):
 
 def write_headers(hash_pat, kmer_hash, genepres):
     """panfeed.py:116-129; `genepres` only needs `.columns` (the strain names)."""
-    hash_pat.write(hashes_to_patterns_header(list(genepres.columns)))
+    write_strain_headers(hash_pat, kmer_hash, list(genepres.columns))
+
+
+def write_strain_headers(hash_pat, kmer_hash, strains):
+    """write_headers for callers that have the strain names and no table"""
+    hash_pat.write(hashes_to_patterns_header(strains))
     hash_pat.flush()
     kmer_hash.write(KMERS_TO_HASHES_HEADER)
     kmer_hash.flush()
+
+
+def write_cluster_dir(output, idx, strains, kmers_tsv, kmers_to_hashes, hashes_to_patterns, compress=False):
+    """--multiple-files: the three files of gene cluster `idx`, headers and all, in `<output>/<idx>/`
+    (panfeed.py:38-43, 159-167)"""
+    path = os.path.join(output, idx)
+    os.makedirs(path, exist_ok=True)
+    ks = create_kmer_stroi(path, compress)
+    ks.write(kmers_tsv)
+    ks.close()
+    hash_pat, kmer_hash = create_hash_files(path, compress)
+    write_strain_headers(hash_pat, kmer_hash, strains)
+    hash_pat.write(hashes_to_patterns)
+    kmer_hash.write(kmers_to_hashes)
+    hash_pat.close()
+    kmer_hash.close()
+
+
+def write_text(fh, data):
+    """`data` -- str, or the bytes-like text the GPU wrote -- into `fh`: a text file, a binary file or a
+    ParallelGzipWriter.  Bytes go straight into a text file's binary layer."""
+    if isinstance(data, str):
+        fh.write(data.encode() if isinstance(fh, io.BufferedIOBase) else data)
+    elif len(data):
+        raw = getattr(fh, "buffer", None)
+        if raw is not None:
+            fh.flush()
+            raw.write(data)
+        else:
+            fh.write(data)

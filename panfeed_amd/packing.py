@@ -73,7 +73,7 @@ class TargetTable:
     """The target-strain sequences of a batch as the packer's flat arrays (pf_packed's target_* arrays): which input
     sequence each is, its A/C/G/T runs (segment index in the batch, first window, windows) and its windows with another
     letter (position, strand used, canonical text).  `metas()` gives the per-sequence SeqMeta objects the host renderer's
-    marshalling and the tests read; the device renderer's marshalling (Engine._marshal_table) goes by the arrays, with
+    marshalling and the tests read; the device renderer's marshalling (Engine._target_records) goes by the arrays, with
     `resolve(t_seq) -> (cluster indices, strain names, Seqinfos)` for what only the records know."""
 
     def __init__(self, k, t_seq, t_so, t_si, t_ss, t_sn, t_ao, t_ap, t_au, akeys, seq_ref, resolve=None):

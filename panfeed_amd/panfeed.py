@@ -18,12 +18,10 @@ pattern_hasher consumes it -- feed it many results per call (any iterable) to ba
 `patterns` is a `PatternSet` that keeps the run-global pattern table on the device.
 There is no CPU fallback: without the HIP library or a GPU the calls raise.
 """
-import os
-
 import numpy as np
 
 from .engine import Engine
-from .output import create_hash_files, create_kmer_stroi, write_headers  # noqa: F401  (re-exported)
+from .output import create_hash_files, create_kmer_stroi, write_cluster_dir, write_headers  # noqa: F401  (re-exported)
 
 
 def init_presabs_vector(n_strains, clusterpresab, missing_nan=False):
@@ -110,18 +108,7 @@ def pattern_hasher(cluster_dict_iter, kmer_stroi, hash_pat, kmer_hash, genepres,
 
     if multiple_files:
         for (idx, _h, _p, _m), (cidx, kt, kh, hp) in zip(results, out.per_cluster):
-            path = os.path.join(output, idx)                           # panfeed.py:38-43, 159-167
-            if not os.path.exists(path):
-                os.mkdir(path)
-            ks = create_kmer_stroi(path, compress)
-            ks.write(kt)
-            ks.close()
-            f_hp, f_kh = create_hash_files(path, compress)
-            write_headers(f_hp, f_kh, genepres)
-            f_hp.write(hp)
-            f_kh.write(kh)
-            f_hp.close()
-            f_kh.close()
+            write_cluster_dir(output, idx, list(genepres.columns), kt, kh, hp, compress)   # panfeed.py:38-43, 159-167
         return patterns
     if results[0][3] is not None:
         kmer_stroi.write(out.kmers_tsv)                                # panfeed.py:171

@@ -5,32 +5,227 @@ serial loop :350-356): the native reader hands out table rows (host threads), th
 works on the current one (`Engine.run_batches`), the texts of a finished batch are written -- and, under `compress`,
 deflated on all host threads -- by a writer thread while the GPU has the next batch.  Output order is the table order
 (the reference's --cores 1 order) whatever finishes first."""
+import csv
+import functools
 import os
 import queue
 import threading
+import time
 
-from .engine import Engine, OwnedText
+from . import _lib
+from .engine import Engine, add_batch_stats
 from .native_input import Pangenome
-from .output import create_hash_files, create_kmer_stroi, write_headers
+from .output import create_hash_files, create_kmer_stroi, write_cluster_dir, write_strain_headers, write_text
 
 
-class _Columns:
-    """what write_headers needs of the reference's `genepres` (panfeed.py:116-129)"""
-
-    def __init__(self, columns):
-        self.columns = list(columns)
-
-
+# ---------------------------------------------------------------------- the start-up both file pipelines share
 def _peek_n_strains(presence_absence):
     """strain columns of the panaroo table, from its header record alone (input.py:188-191: index_col=0, the columns
     'Non-unique Gene name' and 'Annotation' dropped); 0 when the file cannot be read that way"""
-    import csv
     try:
         with open(presence_absence, newline="") as fh:
             header = next(csv.reader(fh))
         return sum(1 for h in header[1:] if h not in ("Non-unique Gene name", "Annotation"))
     except Exception:       # noqa: BLE001
         return 0
+
+
+def existing_output_error(output):
+    """the reference refuses an existing directory (input.py:213-216): the error to raise, or None"""
+    if os.path.isdir(output):
+        return FileExistsError(f"Output directory {output} already exists; remove it or change the output path")
+    return None
+
+
+def sized_engine(n_strains, batch_clusters, max_items=0, **options):
+    """The context of a files -> files run, sized for that run; `options`: Engine's other keyword arguments."""
+    return Engine(max_strains=max(32, (n_strains + 31) // 32 * 32),
+                  # work items in flight = scratch slices (1.9 MB each at 1 000 strains): sized for the batches of this
+                  # run, not the library's default of 2 048 -- creating and freeing 4 GB of scratch was a third of a
+                  # one-second run's time (a cluster that needs more makes the library re-make its scratch)
+                  max_items=max_items or max(512, 2 * int(batch_clusters)), **options)
+
+
+def settle_context(pg, eng, open_reader):
+    """`(pg, eng)` once the reader knows the number of strains: a context made from the table's header line (`eng`, or
+    None) that turns out too small is closed -- the header was not what the reader made of it -- and a reader whose
+    genomes went into that context's store is opened again the classic two-step way (`open_reader(engine=None)`).
+    Where `eng` comes back None the caller makes the context from `pg.n_strains`."""
+    if eng is None or eng.max_strains >= pg.n_strains:
+        return pg, eng
+    if pg.resident:
+        pg.close()
+        pg = None
+    eng.close()
+    return pg or open_reader(engine=None), None
+
+
+# ---------------------------------------------------------------------- one run_files call
+class _FileRun:
+    """What the steps of one `run_files` call share."""
+
+    def __init__(self, output, compress, multiple_files):
+        self.output, self.compress, self.multiple_files = output, compress, multiple_files
+        self.t_start = time.perf_counter()
+        # where the wall time went: opening + parsing the inputs, creating the context, uploading the genomes, then the
+        # overlapped stages of the batches (Engine.run_batches: read + pack on its thread, pf_submit = upload + kernels,
+        # text = device text + D2H or fetch + host renderers) and the writer thread's busy time
+        self.stages = {"open_parse_s": 0.0, "write_busy_s": 0.0}
+        self.context_thread = None                      # "panfeed-context": what it made (or its error), in how long
+        self.context, self.context_err, self.context_s = None, None, 0.0
+        self.uploader, self.upload_err = None, None     # "panfeed-genomes" and its error
+        self.write_err = None                           # the first failure of "panfeed-writer"
+        self.strains = ()
+        self.kmer_stroi = self.kmer_hash = self.hash_pat = None     # the run's three files (not under multiple_files)
+
+    def start_context(self, make_engine, n_strains):
+        """the context (stream, tables, ~1 GB of scratch: 7 ms) is made on a thread of its own while the reader opens
+        the pangenome; it needs the number of strains, which the table's header line says"""
+        def make():
+            t0 = time.perf_counter()
+            try:
+                self.context = make_engine(n_strains)
+            except Exception as e:       # noqa: BLE001  (made again in _open, where the error belongs)
+                self.context_err = e
+            self.context_s = time.perf_counter() - t0
+        self.context_thread = threading.Thread(target=make, name="panfeed-context")
+        self.context_thread.start()
+
+    def join_context(self):
+        """the early context, or None when there is none (not started, or it could not be made)"""
+        if self.context_thread is not None:
+            self.context_thread.join()
+        return self.context
+
+    def context_when_needed(self):
+        """for the one-pass reader, which asks when the first genome needs the context"""
+        if self.join_context() is None:
+            raise self.context_err
+        return self.context
+
+    def wait_for_genomes(self):
+        if self.uploader is not None:
+            self.uploader.join()
+        if self.upload_err is not None:
+            raise self.upload_err
+
+    def write_one(self, o):
+        if not self.multiple_files:
+            write_text(self.kmer_stroi, o.kmers_tsv)
+            write_text(self.kmer_hash, o.kmers_to_hashes)
+            write_text(self.hash_pat, o.hashes_to_patterns)
+            return
+        for idx, kt, kh, hp in o.per_cluster:
+            write_cluster_dir(self.output, idx, self.strains, kt, kh, hp, self.compress)
+
+    def writer(self, q, slots):
+        while True:
+            o = q.get()
+            if o is None:
+                return
+            try:
+                if self.write_err is None:
+                    tw = time.perf_counter()
+                    self.write_one(o)
+                    self.stages["write_busy_s"] += time.perf_counter() - tw
+            except Exception as e:          # keep draining so that the producer never blocks on a dead writer
+                self.write_err = e
+            finally:
+                slots.release()
+
+
+def _open(run, open_reader, make_engine, n_peek, one_pass):
+    """Reader and context, `(pg, eng)`.  With the strain count of the header line (`n_peek`) the context is made on its
+    thread meanwhile; one_pass: one pass over the input -- the genomes go into the context's store as their files are
+    read, the reader asking for the context when the first genome needs it."""
+    if n_peek:
+        run.start_context(make_engine, n_peek)
+    pg = eng = None
+    try:
+        pg = open_reader(engine=run.context_when_needed if n_peek and one_pass else None)
+        run.stages["open_parse_s"] = time.perf_counter() - run.t_start
+        t0 = time.perf_counter()
+        pg, eng = settle_context(pg, run.join_context(), open_reader)
+        early = eng is not None
+        if not early:
+            eng = make_engine(pg.n_strains)
+        run.stages["context_s"] = run.context_s if early else time.perf_counter() - t0
+        run.stages["context_wait_s"] = time.perf_counter() - t0
+        return pg, eng
+    except BaseException:
+        for x in (pg, run.join_context(), eng):
+            if x is not None:
+                x.close()
+        raise
+
+
+def _start_upload(run, pg, eng, resident, overlap):
+    """The genomes of a reader that was opened the two-step way go to the GPU: at once, or on a thread of their own."""
+    run.stages["genome_upload_s"] = 0.0
+    run.stages["one_pass_ingest"] = bool(pg.one_pass)
+    if not resident or pg.resident:
+        return
+    t0 = time.perf_counter()
+    if not overlap:
+        pg.make_resident(eng)
+        run.stages["genome_upload_s"] = time.perf_counter() - t0
+        return
+    # The genome store's layout follows from the contig lengths: the reader switches to by-reference records at
+    # once and the packer thread starts on the first batches while the contigs go up on a thread of their own
+    # (the library packs them to 2 bits per base on the device); the first pf_submit waits for that thread.
+    pg.assign_store()
+
+    def upload():
+        t1 = time.perf_counter()
+        try:
+            pg.upload_store(eng)
+        except Exception as e:       # noqa: BLE001
+            run.upload_err = e
+        run.stages["genome_upload_s"] = time.perf_counter() - t1
+    run.uploader = threading.Thread(target=upload, name="panfeed-genomes")
+    run.uploader.start()
+
+
+def _open_outputs(run, strains):
+    run.strains = list(strains)
+    if not run.multiple_files:
+        run.kmer_stroi = create_kmer_stroi(run.output, run.compress)
+        run.hash_pat, run.kmer_hash = create_hash_files(run.output, run.compress)
+        write_strain_headers(run.hash_pat, run.kmer_hash, run.strains)
+
+
+def _write_batches(run, eng, pg, stats, batch_clusters, device_text):
+    """The batches, in table order, through the writer thread; closes the run's files."""
+    q = queue.Queue(maxsize=4)
+    # text the GPU wrote lives in two pinned blocks used alternately: a batch may only be rendered once the batch
+    # before the previous one has been written out
+    slots = threading.Semaphore(2)
+    wt = threading.Thread(target=run.writer, args=(q, slots), name="panfeed-writer")
+    wt.start()
+    try:
+        # (target strains' rows go to kmers.tsv block by block as they leave the device, from this thread: the file is
+        # the writer thread's only when a batch's rows come as one object -- the host renderers' path)
+        sink = (lambda blk: write_text(run.kmer_stroi, blk)) if (device_text and not run.multiple_files) else None
+        batches = eng.run_pangenome(pg, batch_clusters=batch_clusters, device_text=device_text,
+                                    before_first_submit=run.wait_for_genomes, targets_sink=sink)
+        while True:
+            slots.acquire()
+            o = next(batches, None)
+            if o is None:
+                break
+            add_batch_stats(stats, o)
+            stats["patterns"] = o.stats.get("patterns", stats["patterns"])
+            stats["bytes"] += (len(o.kmers_tsv) + len(o.kmers_to_hashes) + len(o.hashes_to_patterns) +
+                               o.stats.get("kmers_tsv_streamed", 0))
+            q.put(o)
+    finally:
+        q.put(None)
+        wt.join()
+        for fh in (run.kmer_stroi, run.kmer_hash, run.hash_pat):
+            if fh is not None:
+                fh.close()
+    if run.write_err is not None:
+        raise run.write_err
 
 
 def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon=True, consider_missing=False,
@@ -45,232 +240,39 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
     (pf_pangenome_open_device) instead of being read into host strings first and uploaded afterwards.  raise_missing
     (`--stop-on-missing`): a strain, contig or gene of the table that is not found is an error instead of a warning.
     Returns a dict of counters."""
-    import time as _time
-    t_start = _time.perf_counter()
-    if os.path.isdir(output):                       # the reference refuses an existing directory (input.py:213-216)
-        raise FileExistsError(f"Output directory {output} already exists; remove it or change the output path")
+    run = _FileRun(output, compress, multiple_files)
+    err = existing_output_error(output)
+    if err is not None:
+        raise err
     os.makedirs(output)
     targets = tuple(targets or ())
-
-    def make_engine(n_strains):
-        return Engine(klength=klength, canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
-                      multiple_files=multiple_files, max_strains=max(32, (n_strains + 31) // 32 * 32),
-                      stroi=set(targets), device=device,
-                      # work items in flight = scratch slices (1.9 MB each at 1 000 strains): sized for the batches of this
-                      # run, not the library's default of 2 048 -- creating and freeing 4 GB of scratch was a third of a
-                      # one-second run's time
-                      max_items=max_items or max(512, 2 * int(batch_clusters)), pattern_capacity=pattern_capacity)
-
-    # the context (stream, tables, ~1 GB of scratch: 7 ms) is made on a thread of its own while the reader opens the
-    # pangenome; it needs the number of strains, which the table's header line says
-    early = {}
+    make_engine = functools.partial(sized_engine, batch_clusters=batch_clusters, max_items=max_items, klength=klength,
+                                    canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
+                                    multiple_files=multiple_files, stroi=set(targets), device=device,
+                                    pattern_capacity=pattern_capacity)
+    open_reader = functools.partial(Pangenome, presence_absence, gffdir, fastadir, upstream, downstream,
+                                    downstream_start_codon, targets=targets, genes=genes, raise_missing=raise_missing)
     n_peek = _peek_n_strains(presence_absence) if overlap else 0
-    from . import _lib
     _lib.load()        # once, on this thread, before two threads could both make the process's first call to it
-
-    def early_engine():
-        t0 = _time.perf_counter()
-        try:
-            early["eng"] = make_engine(n_peek)
-        except Exception as e:       # noqa: BLE001  (made again below, where the error belongs)
-            early["err"] = e
-        early["s"] = _time.perf_counter() - t0
-    et = None
-    pg = None
-    if n_peek and resident and one_pass:
-        # one pass over the input: the genomes go into the context's store as their files are read; the context is made on
-        # its thread while the reader parses the table and is asked for when the first genome needs it
-        et = threading.Thread(target=early_engine, name="panfeed-context")
-        et.start()
-
-        def engine_when_needed():
-            et.join()
-            if "err" in early:
-                raise early["err"]
-            return early["eng"]
-        try:
-            pg = Pangenome(presence_absence, gffdir, fastadir, upstream, downstream, downstream_start_codon,
-                           targets=targets, genes=genes, raise_missing=raise_missing, engine=engine_when_needed)
-        except BaseException:
-            et.join()
-            if "eng" in early:
-                early["eng"].close()
-            raise
-        et.join()
-        if "eng" in early and early["eng"].max_strains < pg.n_strains:       # (the header was not what the reader made of it: the classic way)
-            pg.close()
-            early.pop("eng").close()
-            pg = None
-        et = None
-    if pg is None:
-        if n_peek:
-            et = threading.Thread(target=early_engine, name="panfeed-context")
-            et.start()
-        try:
-            pg = Pangenome(presence_absence, gffdir, fastadir, upstream, downstream, downstream_start_codon, targets=targets,
-                           genes=genes, raise_missing=raise_missing)
-        except BaseException:
-            if et is not None:
-                et.join()
-                if "eng" in early:
-                    early["eng"].close()
-            raise
-    eng = None
-    uploader = None
+    pg, eng = _open(run, open_reader, make_engine, n_peek, one_pass=resident and one_pass)
     stats = {"clusters": 0, "instances": 0, "kept_kmers": 0, "patterns": 0, "device_ms": 0.0, "bytes": 0}
-    stages = {"open_parse_s": _time.perf_counter() - t_start, "write_busy_s": 0.0}
     try:
-        t0 = _time.perf_counter()
-        if et is not None:
-            et.join()
-        if et is not None or pg.resident:
-            eng = early.get("eng")
-            if eng is not None and eng.max_strains < pg.n_strains:        # (the header was not what the reader made of it)
-                eng.close()
-                eng = None
-        if eng is None:
-            eng = make_engine(pg.n_strains)
-        stages["context_s"] = early.get("s", 0.0) if "eng" in early and eng is early["eng"] else _time.perf_counter() - t0
-        stages["context_wait_s"] = _time.perf_counter() - t0
-        t0 = _time.perf_counter()
-        upload_err = []
-        stages["genome_upload_s"] = 0.0
-        stages["one_pass_ingest"] = bool(pg.one_pass)
-        if resident and not pg.resident:
-            # The genome store's layout follows from the contig lengths: the reader switches to by-reference records at
-            # once and the packer thread starts on the first batches while the contigs go up on a thread of their own
-            # (the library packs them to 2 bits per base on the device); the first pf_submit waits for that thread.
-            if not overlap:
-                pg.make_resident(eng)
-                stages["genome_upload_s"] = _time.perf_counter() - t0
-        if resident and overlap and not pg.resident:
-            pg.assign_store()
-
-            def upload():
-                t1 = _time.perf_counter()
-                try:
-                    pg.upload_store(eng)
-                except Exception as e:       # noqa: BLE001
-                    upload_err.append(e)
-                stages["genome_upload_s"] = _time.perf_counter() - t1
-            uploader = threading.Thread(target=upload, name="panfeed-genomes")
-            uploader.start()
-
-        def wait_for_genomes():
-            if uploader is not None:
-                uploader.join()
-            if upload_err:
-                raise upload_err[0]
-        cols = _Columns(pg.strains)
-        if multiple_files:
-            kmer_stroi = hash_pat = kmer_hash = None
-        else:
-            kmer_stroi = create_kmer_stroi(output, compress)
-            hash_pat, kmer_hash = create_hash_files(output, compress)
-            write_headers(hash_pat, kmer_hash, cols)
-        q = queue.Queue(maxsize=4)
-        # text the GPU wrote lives in two pinned blocks used alternately: a batch may only be rendered once the batch
-        # before the previous one has been written out
-        slots = threading.Semaphore(2)
-        failed = []
-
-        def put(fh, data):
-            # text the GPU wrote arrives as bytes: straight into the file's binary layer (or the gzip writer)
-            if isinstance(data, str):
-                fh.write(data)
-            elif isinstance(data, OwnedText):        # engine.OwnedText: the library's block, written where it lies
-                try:
-                    put(fh, data.view)
-                finally:
-                    data.release()
-            elif len(data):
-                raw = getattr(fh, "buffer", None)
-                if raw is not None:
-                    fh.flush()
-                    raw.write(data)
-                else:
-                    fh.write(data)
-
-        def write_one(o):
-            if not multiple_files:
-                put(kmer_stroi, o.kmers_tsv)
-                put(kmer_hash, o.kmers_to_hashes)
-                put(hash_pat, o.hashes_to_patterns)
-                return
-            for idx, kt, kh, hp in o.per_cluster:
-                path = os.path.join(output, idx)
-                os.makedirs(path, exist_ok=True)
-                ks = create_kmer_stroi(path, compress)
-                ks.write(kt)
-                ks.close()
-                f_hp, f_kh = create_hash_files(path, compress)
-                write_headers(f_hp, f_kh, cols)
-                f_hp.write(hp)
-                f_kh.write(kh)
-                f_hp.close()
-                f_kh.close()
-
-        def writer():
-            while True:
-                o = q.get()
-                if o is None:
-                    return
-                try:
-                    if not failed:
-                        tw = _time.perf_counter()
-                        write_one(o)
-                        stages["write_busy_s"] += _time.perf_counter() - tw
-                except Exception as e:          # keep draining so that the producer never blocks on a dead writer
-                    failed.append(e)
-                finally:
-                    slots.release()
-
-        wt = threading.Thread(target=writer, name="panfeed-writer")
-        wt.start()
-        try:
-            # (target strains' rows go to kmers.tsv block by block as they leave the device, from this thread: the file is
-            # the writer thread's only when a batch's rows come as one object -- the host renderers' path)
-            sink = (lambda blk: put(kmer_stroi, blk)) if (device_text and not multiple_files) else None
-            batches = eng.run_pangenome(pg, batch_clusters=batch_clusters, device_text=device_text,
-                                        before_first_submit=wait_for_genomes, targets_sink=sink)
-            while True:
-                slots.acquire()
-                o = next(batches, None)
-                if o is None:
-                    break
-                stats["clusters"] += o.stats.get("clusters", 0)
-                stats["instances"] += o.stats.get("instances", 0)
-                stats["kept_kmers"] += o.stats.get("kept_kmers", 0)
-                stats["patterns"] = o.stats.get("patterns", stats["patterns"])
-                stats["device_ms"] += o.timing.get("total_ms", 0.0)
-                stats["bytes"] += (len(o.kmers_tsv) + len(o.kmers_to_hashes) + len(o.hashes_to_patterns) +
-                                   o.stats.get("kmers_tsv_streamed", 0))
-                q.put(o)
-        finally:
-            q.put(None)
-            wt.join()
-            for fh in (kmer_stroi, kmer_hash, hash_pat):
-                if fh is not None:
-                    fh.close()
-        if failed:
-            raise failed[0]
-        wait_for_genomes()      # a run that submitted nothing (empty table, --genes matching nothing) still reports a failed upload
+        _start_upload(run, pg, eng, resident, overlap)
+        _open_outputs(run, pg.strains)
+        _write_batches(run, eng, pg, stats, batch_clusters, device_text)
+        run.wait_for_genomes()  # a run that submitted nothing (empty table, --genes matching nothing) still reports a failed upload
         stats["log"] = pg.take_log()
-        # where the wall time went: opening + parsing the inputs, creating the context, uploading the genomes, then the
-        # overlapped stages of the batches (Engine.run_batches: read + pack on its thread, pf_submit = upload + kernels,
-        # text = device text + D2H or fetch + host renderers) and the writer thread's busy time
-        stages.update(getattr(eng, "stages", {}))
-        stages["total_s"] = _time.perf_counter() - t_start
-        stats["stages"] = stages
+        run.stages.update(getattr(eng, "stages", {}))
+        run.stages["total_s"] = time.perf_counter() - run.t_start
+        stats["stages"] = run.stages
         return stats
     finally:
-        if uploader is not None:
-            uploader.join()                  # (an error on the way: the upload reads the reader's contigs)
-        t0 = _time.perf_counter()
+        if run.uploader is not None:
+            run.uploader.join()              # (an error on the way: the upload reads the reader's contigs)
+        t0 = time.perf_counter()
         pg.close(wait=False)                 # the run is over: the reader's memory goes back in the background
-        t1 = _time.perf_counter()
-        if eng is not None:
-            eng.close()
+        t1 = time.perf_counter()
+        eng.close()
         if "stages" in stats:                                             # reader and context given back
             stats["stages"]["close_reader_s"] = t1 - t0
-            stats["stages"]["close_context_s"] = _time.perf_counter() - t1
+            stats["stages"]["close_context_s"] = time.perf_counter() - t1

@@ -20,32 +20,20 @@ run-global `patterns` set and the three file handles, panfeed.py:146-150, 179-18
 `PatternSource` is the little a rank needs from its engine after the shard has run; `Engine` provides it, and the CPU
 tests drive the same merge / assembly code with a stand-in.
 """
+import functools
 import os
 import shutil
 
 import numpy as np
 
-from .engine import KMERS_TO_HASHES_HEADER, KMERS_TSV_HEADER, OwnedText, hashes_to_patterns_header
+from .engine import KMERS_TO_HASHES_HEADER, KMERS_TSV_HEADER, add_batch_stats, hashes_to_patterns_header
+from .output import ParallelGzipWriter, write_cluster_dir, write_text
 
 FILES = ("kmers.tsv", "kmers_to_hashes.tsv", "hashes_to_patterns.tsv")
 
 
 def _part_path(output, name, rank, compress):
     return os.path.join(output, ".parts", f"{name}{'.gz' if compress else ''}.part{rank:04d}")
-
-
-class _PlainPart:
-    def __init__(self, path):
-        self.fh = open(path, "wb")
-
-    def write(self, data):
-        if isinstance(data, str):
-            data = data.encode()
-        if len(data):
-            self.fh.write(data)
-
-    def close(self):
-        self.fh.close()
 
 
 class ShardWriter:
@@ -58,30 +46,21 @@ class ShardWriter:
         for name in FILES:
             path = _part_path(output, name, rank, compress)
             if compress:
-                from .output import ParallelGzipWriter
                 h = ParallelGzipWriter(path, compresslevel=9)
                 h.wrote = True            # an empty part adds nothing (no empty gzip member in the middle of the file)
                 self.handles[name] = h
             else:
-                self.handles[name] = _PlainPart(path)
+                self.handles[name] = open(path, "wb")
         self.bytes = 0
 
     def write_batch(self, kmers_tsv, kmers_to_hashes):
-        if isinstance(kmers_tsv, OwnedText):     # engine.OwnedText: the library's block, written where it lies
-            try:
-                self.handles["kmers.tsv"].write(kmers_tsv.view)
-            finally:
-                n_kt = len(kmers_tsv)
-                kmers_tsv.release()
-        else:
-            self.handles["kmers.tsv"].write(kmers_tsv)
-            n_kt = len(kmers_tsv)
-        self.handles["kmers_to_hashes.tsv"].write(kmers_to_hashes)
-        self.bytes += n_kt + len(kmers_to_hashes)
+        write_text(self.handles["kmers.tsv"], kmers_tsv)
+        write_text(self.handles["kmers_to_hashes.tsv"], kmers_to_hashes)
+        self.bytes += len(kmers_tsv) + len(kmers_to_hashes)
 
     def write_patterns(self, blocks):
         for b in blocks:
-            self.handles["hashes_to_patterns.tsv"].write(b)
+            write_text(self.handles["hashes_to_patterns.tsv"], b)
             self.bytes += len(b)
 
     def close(self):
@@ -214,44 +193,35 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
     (balanced by the number of gene entries per table row) and writes its parts; rank 0 assembles.  Option names as
     in the reference's CLI (`__main__.py:86-186`)."""
     from .distributed import shard_range
-    from .engine import Engine
     from .native_input import Pangenome
+    from .pipeline import _peek_n_strains, existing_output_error, settle_context, sized_engine
     _bind_device(device)
     targets = tuple(targets or ())
-    exists = os.path.isdir(output)
+    err = existing_output_error(output)
     _barrier(dist, device)                                        # every rank has looked before rank 0 creates it
-    if exists:                                            # input.py:213-216
-        raise FileExistsError(f"Output directory {output} already exists; remove it or change --output")
+    if err is not None:
+        raise err
     if rank == 0:
         os.makedirs(output)
     _barrier(dist, device)
-    def make_engine(n_strains):
-        return Engine(klength=klength, canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
-                      multiple_files=multiple_files, max_strains=max(32, (n_strains + 31) // 32 * 32),
-                      stroi=set(targets), device=gpu,
-                      # the same rule as pipeline.run_files (a cluster that needs more makes the library re-make its scratch)
-                      max_items=max_items or max(512, 2 * int(batch_clusters)), pattern_capacity=pattern_capacity)
+    make_engine = functools.partial(sized_engine, batch_clusters=batch_clusters, max_items=max_items, klength=klength,
+                                    canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
+                                    multiple_files=multiple_files, stroi=set(targets), device=gpu,
+                                    pattern_capacity=pattern_capacity)
+    open_reader = functools.partial(Pangenome, presence_absence, gffdir, fastadir, upstream, downstream,
+                                    downstream_start_codon, targets=targets, genes=genes)
     # every rank reads every genome (a cluster's sequences come from all of them): with resident genomes the files go to
-    # the rank's GPU as they are read (pf_pangenome_open_device), as in pipeline.run_files; the context is made first, from
-    # the table's header line
-    from .pipeline import _peek_n_strains
-    eng = pg = None
+    # the rank's GPU as they are read (pf_pangenome_open_device), as in pipeline.run_files; the context is made first, on
+    # this thread, from the table's header line
     n_peek = _peek_n_strains(presence_absence) if resident else 0
-    if n_peek:
-        eng = make_engine(n_peek)
-        try:
-            pg = Pangenome(presence_absence, gffdir, fastadir, upstream, downstream, downstream_start_codon, targets=targets,
-                           genes=genes, engine=eng)
-        except BaseException:
+    eng = make_engine(n_peek) if n_peek else None
+    try:
+        pg = open_reader(engine=eng)
+    except BaseException:
+        if eng is not None:
             eng.close()
-            raise
-        if eng.max_strains < pg.n_strains:               # (the header was not what the reader made of it)
-            pg.close()
-            eng.close()
-            eng = pg = None
-    if pg is None:
-        pg = Pangenome(presence_absence, gffdir, fastadir, upstream, downstream, downstream_start_codon, targets=targets,
-                       genes=genes)
+        raise
+    pg, eng = settle_context(pg, eng, open_reader)
     try:
         w = pg.weights()
         start, stop = shard_range(len(w), rank, world, w)
@@ -274,38 +244,19 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
 
 
 def _drive(eng, batches, output, strains, rank, world, dist, device, compress, multiple_files, method, rng):
-    from .output import create_hash_files, create_kmer_stroi, write_headers
     stats = {"rank": rank, "clusters": 0, "instances": 0, "kept_kmers": 0, "range": list(rng), "device_ms": 0.0}
-
-    class _Cols:
-        columns = list(strains)
-
     if multiple_files:
         for o in batches:
             for idx, kt, kh, hp in o.per_cluster:
-                path = os.path.join(output, idx)                      # panfeed.py:38-43, 159-167
-                os.makedirs(path, exist_ok=True)
-                ks = create_kmer_stroi(path, compress)
-                ks.write(kt)
-                ks.close()
-                f_hp, f_kh = create_hash_files(path, compress)
-                write_headers(f_hp, f_kh, _Cols)
-                f_hp.write(hp)
-                f_kh.write(kh)
-                f_hp.close()
-                f_kh.close()
-            stats["clusters"] += o.stats.get("clusters", 0)
-            stats["instances"] += o.stats.get("instances", 0)
+                write_cluster_dir(output, idx, list(strains), kt, kh, hp, compress)
+            add_batch_stats(stats, o, ("clusters", "instances"))
         _barrier(dist, device)
         return stats
     writer = ShardWriter(output, rank, compress)
     try:
         for o in batches:
             writer.write_batch(o.kmers_tsv, o.kmers_to_hashes)
-            stats["clusters"] += o.stats.get("clusters", 0)
-            stats["instances"] += o.stats.get("instances", 0)
-            stats["kept_kmers"] += o.stats.get("kept_kmers", 0)
-            stats["device_ms"] += o.timing.get("total_ms", 0.0)
+            add_batch_stats(stats, o)
         stats["local_patterns"] = eng.pattern_count()
         stats["pattern_rows"], stats["patterns"] = finish_shard(eng, writer, dist, device, method)
     finally:

@@ -49,9 +49,7 @@ def main():
                       "output_bytes": nbytes, "device_ms_total": dev_ms,
                       "note": "host strings -> three files; 1 target strain; record generation excluded"}))
     eng.close()
-    # the same with the two big files' text written by the GPU (bytes into binary files; kmers.tsv from the library's
-    # renderer, handed over without a copy)
-    from panfeed_amd.engine import OwnedText
+    # the same with the two big files' text written by the GPU (bytes into binary files)
     eng = Engine(klength=k, max_strains=1024, stroi=stroi)
     t0 = time.time()
     nbytes = 0
@@ -62,13 +60,8 @@ def main():
         hp.write(hashes_to_patterns_header(names).encode())
         for o in eng.run_stream(iter(recs), batch_clusters=128, device_text=True):
             kt = o.kmers_tsv
-            if isinstance(kt, OwnedText):
-                ks.write(kt.view)
-                nbytes += len(kt)
-                kt.release()
-            else:
-                ks.write(kt.encode() if isinstance(kt, str) else kt)
-                nbytes += len(kt)
+            ks.write(kt.encode() if isinstance(kt, str) else kt)
+            nbytes += len(kt)
             kh.write(o.kmers_to_hashes)
             hp.write(o.hashes_to_patterns)
             nbytes += len(o.kmers_to_hashes) + len(o.hashes_to_patterns)
