@@ -11,6 +11,7 @@ before the import -- the procedure SURVEY.md section 8(c) records.  Nothing of t
 copied: only its outputs on our inputs are stored.
 
 Usage: python tools/gen_golden.py            (rewrites tests/golden/)
+       python tools/gen_golden.py tails      (only the named fixtures: handmade, seeded, wide, tails)
 """
 import gzip
 import io
@@ -35,6 +36,9 @@ from panfeed.panfeed import cluster_cutter, pattern_hasher, write_headers  # noq
 from panfeed.classes import Seqinfo as RefSeqinfo  # noqa: E402
 
 from panfeed_amd import synth  # noqa: E402
+
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import pattern_model as pm  # noqa: E402  (the count-exact generator the sample-count tests use)
 
 _COMP = str.maketrans("ACGTN", "TGCAN")
 
@@ -232,15 +236,55 @@ def wide():
     return cases
 
 
+def tails():
+    """the reference itself at the sample counts where the row kernels change shape: MD5 tails of 7 elements (S = 7, 15,
+    39, 1007, 8191: the extra padding block), the float64 MAF boundary at S = 1000 (counts 9 and 991 go, 10 and 990
+    stay), NaN cells in a 126-block image, 157-word rows with a target strain, and the 8 192-strain ceiling.  Clusters
+    come from tests/pattern_model.py (presence counts chosen, ~90 bp); the files hold those inputs and the reference's
+    outputs only."""
+    cases = []
+    k = 11
+
+    def cx(S, maf, missing=False, seed=0, counts=None):
+        nabs = min(S - 1, max(1, S // 5)) if missing else 0
+        counts = pm.edge_counts(S - nabs, maf) if counts is None else counts
+        c = pm.count_exact_cluster(S, k, counts, seed=seed + S, idx=f"S{S}", n_absent=nabs, keep_present=(-1,))
+        return c.record, c.names
+
+    for S in (7, 15, 39):
+        r, names = cx(S, 0.05, seed=1)
+        cases.append(make_case(f"tail{S}_plain", [r], names, klength=k, stroi=[names[-1]], maf=0.0))
+        cases.append(make_case(f"tail{S}_nofilter", [r], names, klength=k, stroi=None, maf=0.0, patfilt=False))
+        r, names = cx(S, 0.05, missing=True, seed=2)
+        cases.append(make_case(f"tail{S}_missing", [r], names, klength=k, stroi=None, maf=0.0, consider_missing=True))
+    r, names = cx(1000, 0.01, seed=3, counts=[9, 10, 500])
+    cases.append(make_case("s1000_maf_boundary", [r], names, klength=k, stroi=None, maf=0.01))
+    r, names = cx(1007, 0.01, missing=True, seed=4)
+    cases.append(make_case("s1007_missing", [r], names, klength=k, stroi=None, maf=0.01, consider_missing=True))
+    c = pm.count_exact_cluster(5000, 21, pm.edge_counts(5000, 0.01)[:3], seed=5, idx="S5000", keep_present=(-1,))
+    cases.append(make_case("s5000_k21_target", [c.record], c.names, klength=21, stroi=[c.names[-1]], maf=0.01))
+    for S in (8191, 8192):
+        r, names = cx(S, 0.01, seed=6)
+        cases.append(make_case(f"s{S}_ceiling", [r], names, klength=k, stroi=[names[-1]], maf=0.01))
+    return cases
+
+
+FIXTURES = {"handmade": handmade, "seeded": seeded, "wide": wide, "tails": tails}
+
+
 def main():
     outdir = os.path.join(REPO, "tests", "golden")
     os.makedirs(outdir, exist_ok=True)
-    for fname, cases in [("handmade.json.gz", handmade()), ("seeded.json.gz", seeded()), ("wide.json.gz", wide())]:
+    which = sys.argv[1:] or list(FIXTURES)
+    for name in which:
+        fname, cases = name + ".json.gz", FIXTURES[name]()
         path = os.path.join(outdir, fname)
         with gzip.GzipFile(path, "wb", mtime=0) as fh:
             fh.write(json.dumps({"generator": "tools/gen_golden.py", "cases": cases},
                                 sort_keys=True).encode())
         print(f"{path}: {len(cases)} cases, {os.path.getsize(path)} bytes")
+    if sys.argv[1:]:
+        return
     # known-answer vectors for the hash image (panfeed.py:175-176, 206-207)
     import binascii
     import hashlib
