@@ -132,6 +132,104 @@ __device__ __forceinline__ void mm3_final(H128& s, uint32_t len) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The rule of a k-mer's presence row, written once: its 128-bit identity, whether the k-mer is kept,
+// and the NaN mask of the row.  rows_kernel and finish_kernel only say where a row's words come from.
+// ---------------------------------------------------------------------------------------------
+struct RowRule {
+    const uint32_t* presab;        // the cluster's own row (clusterpresab), one bit per sample
+    uint32_t nstr, nchunks;        // samples of the row, 32-sample words of it
+    uint32_t lo, hi;               // carrier counts of the MAF window
+    uint64_t ordinal;
+    bool multiple_files, consider_missing, same_possible;
+};
+// (P: RowsParams or FinishParams; npresent = popcount of presab)
+template <class P>
+__device__ __forceinline__ RowRule row_rule(const P& p, const uint32_t* presab, uint32_t nstr, uint32_t npres, uint32_t npresent,
+                                            uint64_t ordinal) {
+    RowRule r;
+    r.presab = presab; r.nstr = nstr; r.nchunks = (nstr + 31) >> 5;
+    // denominators of panfeed.py:191 / :196
+    const uint32_t n_eff = p.consider_missing ? npresent : nstr;
+    r.lo = p.maf_lo[n_eff]; r.hi = p.maf_hi[n_eff];
+    r.ordinal = ordinal;
+    r.multiple_files = p.multiple_files; r.consider_missing = p.consider_missing;
+    // tuple(vec) == tuple(clusterpresab) can only hold for equal lengths and a NaN-free vector (panfeed.py:203)
+    r.same_possible = !p.patfilt && nstr == npres && (!p.consider_missing || npresent == nstr);
+    return r;
+}
+struct RowAcc {
+    H128 s;
+    uint32_t cnt;                  // carriers so far
+    bool eq;                       // the words so far are presab's (meaningful under same_possible only)
+};
+__device__ __forceinline__ void seed_ordinal(H128& s, uint64_t ordinal, bool multiple_files) {
+    s.h2 = 0x1b873593u; s.h3 = 0xe6546b64u; s.h4 = 0x85ebca6bu;
+    if (multiple_files) { s.h2 ^= (uint32_t)ordinal; s.h3 ^= (uint32_t)(ordinal >> 32); }
+}
+__device__ __forceinline__ RowAcc row_begin(const RowRule& r) {
+    RowAcc a;
+    a.s.h1 = 0x9747b28cu ^ r.nstr;
+    seed_ordinal(a.s, r.ordinal, r.multiple_files);
+    a.cnt = 0; a.eq = true;
+    return a;
+}
+// words [ch, ch + 4) of a row: carriers and equality with the cluster's own row ...
+__device__ __forceinline__ void row_tally(const RowRule& r, RowAcc& a, uint32_t ch, const uint32_t (&wv)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        if (ch + j < r.nchunks) { a.cnt += __popc(wv[j]); if (r.same_possible) a.eq = a.eq && (wv[j] == r.presab[ch + j]); }
+}
+// ... and the same with the block's hash step (row_eval8 hashes words other lanes tallied)
+__device__ __forceinline__ void row_fold(const RowRule& r, RowAcc& a, uint32_t ch, const uint32_t (&wv)[4]) {
+    row_tally(r, a, ch, wv);
+    mm3_block(a.s, wv[0], wv[1], wv[2], wv[3]);
+}
+__device__ __forceinline__ uint4 row_finish(const RowRule& r, RowAcc& a) {
+    if (r.consider_missing) {
+        // NaN where clusterpresab == 0 (panfeed.py:19): the image depends on presab too
+        for (uint32_t ch = 0; ch < r.nchunks; ch += 4) {
+            uint32_t wv[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) wv[j] = (ch + j < r.nchunks) ? ~r.presab[ch + j] : 0;
+            mm3_block(a.s, wv[0], wv[1], wv[2], wv[3]);
+        }
+    }
+    mm3_final(a.s, r.nchunks * 4);
+    return make_uint4(a.s.h1, a.s.h2, a.s.h3, a.s.h4);
+}
+__device__ __forceinline__ bool row_keep(const RowRule& r, uint32_t cnt, bool eq) {
+    bool keep = cnt >= r.lo && cnt <= r.hi;             // panfeed.py:197-200 (host-tabulated float64)
+    if (r.same_possible && eq) keep = false;            // panfeed.py:202-204
+    return keep;
+}
+// the cluster's own row: md5 of the int64 image of clusterpresab (panfeed.py:175-187)
+__device__ __forceinline__ uint4 own_row_hash(const uint32_t* presab, uint32_t npres, uint64_t ordinal, bool multiple_files) {
+    const uint32_t nw = (npres + 31) >> 5;
+    H128 s;
+    s.h1 = 0x9747b28cu ^ npres;
+    seed_ordinal(s, ordinal, multiple_files);
+    s.h2 ^= 0x5bd1e995u;
+    for (uint32_t w = 0; w < nw; w += 4) {
+        uint32_t wv[4];
+        for (int j = 0; j < 4; j++) wv[j] = (w + j < nw) ? presab[w + j] : 0;
+        mm3_block(s, wv[0], wv[1], wv[2], wv[3]);
+    }
+    mm3_final(s, nw * 4 + 1);
+    return make_uint4(s.h1, s.h2, s.h3, s.h4);
+}
+// word w of a row's NaN mask (pat_nan): the samples of the word that clusterpresab does not have
+__device__ __forceinline__ uint32_t nan_word(const uint32_t* presab, uint32_t nstr, uint32_t nchunks, uint32_t consider_missing,
+                                             uint32_t w) {
+    uint32_t nn = 0;
+    if (consider_missing && w < nchunks) {
+        nn = ~presab[w];
+        const uint32_t rem = nstr - (w << 5);
+        if (rem < 32) nn &= (1u << rem) - 1;
+    }
+    return nn;
+}
+
+// ---------------------------------------------------------------------------------------------
 // kmer_scan_kernel
 // ---------------------------------------------------------------------------------------------
 // The scan reads a "view" of each cluster's segments: either the caller's segments as they are
@@ -2066,13 +2164,8 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
         for (uint32_t i = tid; i < mw; i += ROWS_THREADS) p.mrows[(size_t)slice * DEDUP_MROWS + i] = M[i];
         PF_PROF_STAMP(57);
     }
-    const uint32_t npresent = sh_npres;
-    // denominators of panfeed.py:191 / :196
-    const uint32_t n_eff = p.consider_missing ? npresent : nstr;
-    const uint32_t lo = p.maf_lo[n_eff], hi = p.maf_hi[n_eff];
-    // tuple(vec) == tuple(clusterpresab) can only hold for equal lengths and a NaN-free vector (panfeed.py:203)
-    const bool same_possible = !p.patfilt && nstr == npres && (!p.consider_missing || npresent == nstr);
     const uint64_t ordinal = p.cluster_ordinal[c];
+    const RowRule rule = row_rule(p, presab, nstr, npres, sh_npres, ordinal);
 
     const uint32_t* ordp = p.tab_ord + (size_t)slice * NS;
     const uint32_t* cb = p.chunkbits + (size_t)slice * W * NS;
@@ -2081,17 +2174,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
     // presence row of one k-mer -> (128-bit row hash, keep flag).  The row comes either from the chunk words of
     // slot i, or (mode 1) from the union of the sample sets of the distinct sequences in `amask`.
     auto row_eval = [&](bool from_mask, uint64_t amask, uint32_t i, uint4& hout) -> bool {
-        H128 s;
-        s.h1 = 0x9747b28cu ^ nstr; s.h2 = 0x1b873593u; s.h3 = 0xe6546b64u; s.h4 = 0x85ebca6bu;
-        if (p.multiple_files) { s.h2 ^= (uint32_t)ordinal; s.h3 ^= (uint32_t)(ordinal >> 32); }
-        uint32_t cnt = 0;
-        bool eq = true;
-        auto fold = [&](uint32_t ch, const uint32_t (&wv)[4]) {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                if (ch + j < nchunks) { cnt += __popc(wv[j]); eq = eq && (wv[j] == presab[ch + j]); }
-            mm3_block(s, wv[0], wv[1], wv[2], wv[3]);
-        };
+        RowAcc a = row_begin(rule);
         if (from_mask) {
             for (uint32_t ch = 0; ch < nchunks; ch += 4) {
                 uint32_t wv[4] = {0, 0, 0, 0};
@@ -2102,7 +2185,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
                     const uint4 m = *reinterpret_cast<const uint4*>(&M[d * Wp + ch]);
                     wv[0] |= m.x; wv[1] |= m.y; wv[2] |= m.z; wv[3] |= m.w;
                 }
-                fold(ch, wv);
+                row_fold(rule, a, ch, wv);
             }
         } else {
             // (sixteen chunk words of the slot asked for at a time, NS words apart in the scan's dump: the hash is a chain, the
@@ -2121,24 +2204,12 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
                 for (uint32_t q = 0; q < 4; q++) {
                     if (ch0 + 4 * q >= nchunks) break;
                     const uint32_t wv[4] = {w16[4 * q], w16[4 * q + 1], w16[4 * q + 2], w16[4 * q + 3]};
-                    fold(ch0 + 4 * q, wv);
+                    row_fold(rule, a, ch0 + 4 * q, wv);
                 }
             }
         }
-        if (p.consider_missing) {
-            // NaN where clusterpresab == 0 (panfeed.py:19): the image depends on presab too
-            for (uint32_t ch = 0; ch < nchunks; ch += 4) {
-                uint32_t wv[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) wv[j] = (ch + j < nchunks) ? ~presab[ch + j] : 0;
-                mm3_block(s, wv[0], wv[1], wv[2], wv[3]);
-            }
-        }
-        mm3_final(s, nchunks * 4);
-        bool keep = cnt >= lo && cnt <= hi;                 // panfeed.py:197-200 (host-tabulated float64)
-        if (same_possible && eq) keep = false;              // panfeed.py:202-204
-        hout = make_uint4(s.h1, s.h2, s.h3, s.h4);
-        return keep;
+        hout = row_finish(rule, a);
+        return row_keep(rule, a.cnt, a.eq);
     };
 
     // slot_tag of a wide item's slot: position of its mask in the table of the round (< AT_SLOTS), or one of these
@@ -2267,11 +2338,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
         };
         // the row of one mask, read back by ONE lane: hash, count, comparison with the cluster's own row
         auto row_hash = [&](const uint32_t* row, uint4& hout) -> bool {
-            H128 st;
-            st.h1 = 0x9747b28cu ^ nstr; st.h2 = 0x1b873593u; st.h3 = 0xe6546b64u; st.h4 = 0x85ebca6bu;
-            if (p.multiple_files) { st.h2 ^= (uint32_t)ordinal; st.h3 ^= (uint32_t)(ordinal >> 32); }
-            uint32_t cnt = 0;
-            bool eq = true;
+            RowAcc a = row_begin(rule);
             // (four 16-byte pieces of the row asked for at a time: the hash is a chain, the loads need not be -- piece by piece
             // a row of 1 000 samples was eight trips to L2 one after the other per mask, 40 at 5 000)
             for (uint32_t ch0 = 0; ch0 < nchunks; ch0 += 16) {
@@ -2284,25 +2351,11 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
                     const uint32_t ch = ch0 + 4 * q;
                     if (ch >= nchunks) break;
                     const uint32_t wv[4] = {vq[q].x, vq[q].y, vq[q].z, vq[q].w};
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        if (ch + j < nchunks) { cnt += __popc(wv[j]); eq = eq && (wv[j] == presab[ch + j]); }
-                    mm3_block(st, wv[0], wv[1], wv[2], wv[3]);
+                    row_fold(rule, a, ch, wv);
                 }
             }
-            if (p.consider_missing) {
-                for (uint32_t ch = 0; ch < nchunks; ch += 4) {
-                    uint32_t wv[4];
-#pragma unroll
-                    for (int j = 0; j < 4; j++) wv[j] = (ch + j < nchunks) ? ~presab[ch + j] : 0;
-                    mm3_block(st, wv[0], wv[1], wv[2], wv[3]);
-                }
-            }
-            mm3_final(st, nchunks * 4);
-            bool keep = cnt >= lo && cnt <= hi;                 // panfeed.py:197-200
-            if (same_possible && eq) keep = false;              // panfeed.py:202-204
-            hout = make_uint4(st.h1, st.h2, st.h3, st.h4);
-            return keep;
+            hout = row_finish(rule, a);
+            return row_keep(rule, a.cnt, a.eq);
         };
         // ---- singleton masks: M[d] = the samples that carry distinct sequence d, in the place the round's table will
         // take afterwards; one lane per d hashes its row
@@ -3163,21 +3216,9 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(EmitParams p) {
                                                                  // ordinal bitmaps
 
     if (item == sib0 && tid == 0) {
-        // the cluster's own row: md5 of the int64 image of clusterpresab (panfeed.py:175-187)
-        const uint32_t npres = p.cluster_npresab[c];
-        const uint32_t nw = (npres + 31) >> 5;
-        const uint32_t* presab = p.cluster_presab + (size_t)c * W;
-        H128 s;
-        s.h1 = 0x9747b28cu ^ npres; s.h2 = 0x1b873593u ^ 0x5bd1e995u; s.h3 = 0xe6546b64u; s.h4 = 0x85ebca6bu;
-        if (p.multiple_files) { s.h2 ^= (uint32_t)ordinal; s.h3 ^= (uint32_t)(ordinal >> 32); }
-        for (uint32_t w = 0; w < nw; w += 4) {
-            uint32_t wv[4];
-            for (int j = 0; j < 4; j++) wv[j] = (w + j < nw) ? presab[w + j] : 0;
-            mm3_block(s, wv[0], wv[1], wv[2], wv[3]);
-        }
-        mm3_final(s, nw * 4 + 1);
+        const uint4 h = own_row_hash(p.cluster_presab + (size_t)c * W, p.cluster_npresab[c], ordinal, p.multiple_files);
         const uint64_t fs = ordinal << 32;
-        p.cluster_pattern[c] = pattern_insert(p.pt, make_uint4(s.h1, s.h2, s.h3, s.h4), fs);
+        p.cluster_pattern[c] = pattern_insert(p.pt, h, fs);
         p.cluster_first[c] = fs;
     }
 
@@ -3526,12 +3567,9 @@ __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(8,
     __syncthreads();
     PF_PROF_STAMP(1);
     PF_KO_FINISH_AT(1);
-    const uint32_t npresent = sh_npres;
-    const uint32_t n_eff = p.consider_missing ? npresent : nstr;               // panfeed.py:191 / :196
-    const uint32_t lo = p.maf_lo[n_eff], hi = p.maf_hi[n_eff];
-    const bool same_possible = !p.patfilt && nstr == npres && (!p.consider_missing || npresent == nstr);
+    const RowRule rule = row_rule(p, presab, nstr, npres, sh_npres, ordinal);
 
-    auto row_word4 = [&](uint64_t amask, uint32_t ch, uint32_t wv[4]) {
+    auto row_word4 = [&](uint64_t amask, uint32_t ch, uint32_t (&wv)[4]) {
         wv[0] = wv[1] = wv[2] = wv[3] = 0;
         uint64_t t = amask;
         while (t) {
@@ -3542,145 +3580,69 @@ __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(8,
         }
     };
     auto row_eval = [&](uint64_t amask, uint4& hout) -> bool {
-        H128 s;
-        s.h1 = 0x9747b28cu ^ nstr; s.h2 = 0x1b873593u; s.h3 = 0xe6546b64u; s.h4 = 0x85ebca6bu;
-        if (p.multiple_files) { s.h2 ^= (uint32_t)ordinal; s.h3 ^= (uint32_t)(ordinal >> 32); }
-        uint32_t cnt = 0;
-        bool eq = true;
+        RowAcc a = row_begin(rule);
         for (uint32_t ch = 0; ch < nchunks; ch += 4) {
             uint32_t wv[4];
             row_word4(amask, ch, wv);
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                if (ch + j < nchunks) { cnt += __popc(wv[j]); if (same_possible) eq = eq && (wv[j] == presab[ch + j]); }
-            mm3_block(s, wv[0], wv[1], wv[2], wv[3]);
+            row_fold(rule, a, ch, wv);
         }
-        if (p.consider_missing) {
-            for (uint32_t ch = 0; ch < nchunks; ch += 4) {
-                uint32_t wv[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) wv[j] = (ch + j < nchunks) ? ~presab[ch + j] : 0;
-                mm3_block(s, wv[0], wv[1], wv[2], wv[3]);
-            }
-        }
-        mm3_final(s, nchunks * 4);
-        bool keep = cnt >= lo && cnt <= hi;                 // panfeed.py:197-200
-        if (same_possible && eq) keep = false;              // panfeed.py:202-204
-        hout = make_uint4(s.h1, s.h2, s.h3, s.h4);
-        return keep;
+        hout = row_finish(rule, a);
+        return row_keep(rule, a.cnt, a.eq);
     };
     // the same for a row given word by word (the cluster's slow-path rows)
+    auto words4 = [&](const uint32_t* words, uint32_t ch, uint32_t (&wv)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) wv[j] = ch + j < nchunks ? words[ch + j] : 0;
+    };
     auto row_eval_words = [&](const uint32_t* words, uint4& hout) -> bool {
-        H128 s;
-        s.h1 = 0x9747b28cu ^ nstr; s.h2 = 0x1b873593u; s.h3 = 0xe6546b64u; s.h4 = 0x85ebca6bu;
-        if (p.multiple_files) { s.h2 ^= (uint32_t)ordinal; s.h3 ^= (uint32_t)(ordinal >> 32); }
-        uint32_t cnt = 0;
-        bool eq = true;
+        RowAcc a = row_begin(rule);
         for (uint32_t ch = 0; ch < nchunks; ch += 4) {
             uint32_t wv[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                wv[j] = ch + j < nchunks ? words[ch + j] : 0;
-                if (ch + j < nchunks) { cnt += __popc(wv[j]); if (same_possible) eq = eq && (wv[j] == presab[ch + j]); }
-            }
-            mm3_block(s, wv[0], wv[1], wv[2], wv[3]);
+            words4(words, ch, wv);
+            row_fold(rule, a, ch, wv);
         }
-        if (p.consider_missing) {
-            for (uint32_t ch = 0; ch < nchunks; ch += 4) {
-                uint32_t wv[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) wv[j] = (ch + j < nchunks) ? ~presab[ch + j] : 0;
-                mm3_block(s, wv[0], wv[1], wv[2], wv[3]);
-            }
-        }
-        mm3_final(s, nchunks * 4);
-        bool keep = cnt >= lo && cnt <= hi;                 // panfeed.py:197-200
-        if (same_possible && eq) keep = false;              // panfeed.py:202-204
-        hout = make_uint4(s.h1, s.h2, s.h3, s.h4);
-        return keep;
+        hout = row_finish(rule, a);
+        return row_keep(rule, a.cnt, a.eq);
     };
     const uint32_t ex0 = p.extra_off ? p.extra_off[c] : 0, ex1 = p.extra_off ? p.extra_off[c + 1] : 0;
-    auto write_row = [&](uint32_t pid, uint64_t amask) {
-        for (uint32_t w = 0; w < W; w += 4) {
+    // a pattern's row into pat_bits / pat_nan / pat_n: the lane stores words [w, w + 4) for w = first, first + stride, ...
+    // (src fills the four words; the lane with first == 0 stores the row's length)
+    auto write_row = [&](uint32_t pid, uint32_t first, uint32_t stride, auto src) {
+        for (uint32_t w = first; w < W; w += stride) {
             uint32_t wv[4] = {0, 0, 0, 0};
-            if (w < nchunks) row_word4(amask, w, wv);
+            if (w < nchunks) src(w, wv);
             for (uint32_t j = 0; j < 4 && w + j < W; j++) {
                 p.pat_bits[(size_t)pid * W + w + j] = (w + j < nchunks) ? wv[j] : 0;
-                if (p.pat_nan) {
-                    uint32_t nn = 0;
-                    if (p.consider_missing && w + j < nchunks) {
-                        nn = ~presab[w + j];
-                        const uint32_t rem = nstr - ((w + j) << 5);
-                        if (rem < 32) nn &= (1u << rem) - 1;
-                    }
-                    p.pat_nan[(size_t)pid * W + w + j] = nn;
-                }
+                if (p.pat_nan) p.pat_nan[(size_t)pid * W + w + j] = nan_word(presab, nstr, nchunks, p.consider_missing, w + j);
             }
         }
-        p.pat_n[pid] = nstr;
+        if (first == 0) p.pat_n[pid] = nstr;
     };
 
-    // the same two, eight lanes per mask: lane `sub` gathers words [32 r + 4 sub, +4) of the row; the row hash is
+    // row_eval, eight lanes per mask: lane `sub` gathers words [32 r + 4 sub, +4) of the row; the row hash is
     // sequential, so all eight run it on the shuffled words; popcount / equality are reduced over the eight lanes
     auto row_eval8 = [&](uint64_t amask, uint32_t sub, uint4& hout) -> bool {
-        H128 s;
-        s.h1 = 0x9747b28cu ^ nstr; s.h2 = 0x1b873593u; s.h3 = 0xe6546b64u; s.h4 = 0x85ebca6bu;
-        if (p.multiple_files) { s.h2 ^= (uint32_t)ordinal; s.h3 ^= (uint32_t)(ordinal >> 32); }
-        uint32_t cnt = 0;
-        bool eq = true;
+        RowAcc a = row_begin(rule);
         const uint32_t gbase = (tid & 63u) & ~7u;
         for (uint32_t ch0 = 0; ch0 < nchunks; ch0 += 32) {
             const uint32_t ch = ch0 + 4 * sub;
             uint32_t wv[4] = {0, 0, 0, 0};
             if (ch < nchunks) {
                 row_word4(amask, ch, wv);
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (ch + j < nchunks) { cnt += __popc(wv[j]); if (same_possible) eq = eq && (wv[j] == presab[ch + j]); }
+                row_tally(rule, a, ch, wv);
             }
             const uint32_t nb = min(8u, (nchunks - ch0 + 3) >> 2);
             for (uint32_t j = 0; j < nb; j++) {
                 const uint32_t b0 = __shfl(wv[0], gbase + j), b1 = __shfl(wv[1], gbase + j);
                 const uint32_t b2 = __shfl(wv[2], gbase + j), b3 = __shfl(wv[3], gbase + j);
-                mm3_block(s, b0, b1, b2, b3);
+                mm3_block(a.s, b0, b1, b2, b3);
             }
         }
-        if (p.consider_missing) {
-            for (uint32_t ch = 0; ch < nchunks; ch += 4) {
-                uint32_t wv[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) wv[j] = (ch + j < nchunks) ? ~presab[ch + j] : 0;
-                mm3_block(s, wv[0], wv[1], wv[2], wv[3]);
-            }
-        }
-        mm3_final(s, nchunks * 4);
-        int ne = eq ? 0 : 1;
+        hout = row_finish(rule, a);
+        uint32_t cnt = a.cnt;
+        int ne = a.eq ? 0 : 1;
         for (int d = 1; d < 8; d <<= 1) { cnt += __shfl_xor(cnt, d); ne |= __shfl_xor(ne, d); }
-        bool keep = cnt >= lo && cnt <= hi;                 // panfeed.py:197-200
-        if (same_possible && !ne) keep = false;             // panfeed.py:202-204
-        hout = make_uint4(s.h1, s.h2, s.h3, s.h4);
-        return keep;
-    };
-    auto write_row8 = [&](uint32_t pid, uint64_t amask, uint32_t sub) {
-        for (uint32_t w0 = 0; w0 < W; w0 += 32) {
-            const uint32_t w = w0 + 4 * sub;
-            if (w >= W) break;
-            uint32_t wv[4] = {0, 0, 0, 0};
-            if (w < nchunks) row_word4(amask, w, wv);
-            for (uint32_t j = 0; j < 4 && w + j < W; j++) {
-                p.pat_bits[(size_t)pid * W + w + j] = (w + j < nchunks) ? wv[j] : 0;
-                if (p.pat_nan) {
-                    uint32_t nn = 0;
-                    if (p.consider_missing && w + j < nchunks) {
-                        nn = ~presab[w + j];
-                        const uint32_t rem = nstr - ((w + j) << 5);
-                        if (rem < 32) nn &= (1u << rem) - 1;
-                    }
-                    p.pat_nan[(size_t)pid * W + w + j] = nn;
-                }
-            }
-        }
-        if (sub == 0) p.pat_n[pid] = nstr;
+        return row_keep(rule, cnt, !ne);
     };
 
     // phase B: one row evaluation per distinct mask (eight lanes each)
@@ -3801,18 +3763,8 @@ __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(8,
         p.cluster_unique[c] = tot_o;
     }
     if (is_row_entry) {
-        // the cluster's own row: md5 of the int64 image of clusterpresab (panfeed.py:175-187)
-        const uint32_t nw = (npres + 31) >> 5;
-        H128 hs;
-        hs.h1 = 0x9747b28cu ^ npres; hs.h2 = 0x1b873593u ^ 0x5bd1e995u; hs.h3 = 0xe6546b64u; hs.h4 = 0x85ebca6bu;
-        if (p.multiple_files) { hs.h2 ^= (uint32_t)ordinal; hs.h3 ^= (uint32_t)(ordinal >> 32); }
-        for (uint32_t w = 0; w < nw; w += 4) {
-            uint32_t wv[4];
-            for (int j = 0; j < 4; j++) wv[j] = (w + j < nw) ? presab[w + j] : 0;
-            mm3_block(hs, wv[0], wv[1], wv[2], wv[3]);
-        }
-        mm3_final(hs, nw * 4 + 1);
-        e_lo = ((uint64_t)hs.h1 << 32) | hs.h2; e_hi = hs.h3; e_fs = ordinal << 32;
+        const uint4 hs = own_row_hash(presab, npres, ordinal, p.multiple_files);
+        e_lo = ((uint64_t)hs.x << 32) | hs.y; e_hi = hs.z; e_fs = ordinal << 32;
         e_state = 0;
     } else if (tid < AT - 1) {
         e_key = at_key[tid];
@@ -3890,7 +3842,8 @@ __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(8,
     // mask-table positions)
     for (uint32_t g = tid >> 3, nw = wl_count; g < nw; g += T >> 3) {
         const uint32_t t = at_minord[g];
-        write_row8(at_pid[t], at_key[t], tid & 7u);
+        const uint64_t key = at_key[t];
+        write_row(at_pid[t], 4 * (tid & 7u), 32, [&](uint32_t w, uint32_t (&wv)[4]) { row_word4(key, w, wv); });
     }
     // outputs: key + pattern id per kept k-mer, in first-occurrence order
     for (uint32_t q = 0; q < nparts; q++) {
@@ -3941,7 +3894,7 @@ __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(8,
                 bool lw;
                 const uint32_t pid = pattern_insert_lower(p.pt, ((uint64_t)h.x << 32) | h.y, h.z,
                                                           (ordinal << 32) | (uint64_t)(rank_of(o) + 1), &lw);
-                if (lw && pid < p.pt.pool) write_row(pid, amask);
+                if (lw && pid < p.pt.pool) write_row(pid, 0, 4, [&](uint32_t w, uint32_t (&wv)[4]) { row_word4(amask, w, wv); });
                 const uint64_t oi = obase + kept_before(o);
                 if (oi >= p.out_cap) { p.pt.counters[2] = 1; continue; }
                 p.out_key[oi * KW] = p.tab_key[((size_t)slice * KW) * NS + i];
@@ -3961,21 +3914,7 @@ __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(8,
         bool lw;
         const uint32_t pid = pattern_insert_lower(p.pt, ((uint64_t)h.x << 32) | h.y, h.z,
                                                   (ordinal << 32) | (uint64_t)(rank_of(o) + 1), &lw);
-        if (lw && pid < p.pt.pool) {
-            for (uint32_t w = 0; w < W; w++) {
-                p.pat_bits[(size_t)pid * W + w] = w < nchunks ? words[w] : 0;
-                if (p.pat_nan) {
-                    uint32_t nn = 0;
-                    if (p.consider_missing && w < nchunks) {
-                        nn = ~presab[w];
-                        const uint32_t rem = nstr - (w << 5);
-                        if (rem < 32) nn &= (1u << rem) - 1;
-                    }
-                    p.pat_nan[(size_t)pid * W + w] = nn;
-                }
-            }
-            p.pat_n[pid] = nstr;
-        }
+        if (lw && pid < p.pt.pool) write_row(pid, 0, 4, [&](uint32_t w, uint32_t (&wv)[4]) { words4(words, w, wv); });
         const uint64_t oi = obase + kept_before(o);
         if (oi >= p.out_cap) { p.pt.counters[2] = 1; continue; }
         p.out_key[oi * KW] = KEY_EXTRA_FLAG | (uint64_t)e;
@@ -4079,15 +4018,8 @@ __global__ __launch_bounds__(PR_THREADS) void pattern_rows_kernel(PatRowsParams 
             p.pat_n[pid] = npres | 0x80000000u;
         }
     }
-    auto nan_word = [&](uint32_t w) -> uint32_t {
-        uint32_t nn = 0;
-        if (p.consider_missing && w < nchunks) {
-            nn = ~presab[w];
-            const uint32_t rem = nstr - (w << 5);
-            if (rem < 32) nn &= (1u << rem) - 1;
-        }
-        return nn;
-    };
+    // (through a lambda: called in place, the row loop below is scheduled differently and the kernel takes 58 VGPRs for 55)
+    auto nan_at = [&](uint32_t w) -> uint32_t { return nan_word(presab, nstr, nchunks, p.consider_missing, w); };
     if (expand) {
         const uint32_t mw = min(p.v_nstr[c] * Wp, DEDUP_MROWS);
         for (uint32_t i = tid; i < mw; i += blockDim.x) Ml[i] = M[i];
@@ -4224,7 +4156,7 @@ __global__ __launch_bounds__(PR_THREADS) void pattern_rows_kernel(PatRowsParams 
                     }
                 }
                 p.pat_bits[(size_t)pid * W + w] = v;
-                if (p.pat_nan) p.pat_nan[(size_t)pid * W + w] = nan_word(w);
+                if (p.pat_nan) p.pat_nan[(size_t)pid * W + w] = nan_at(w);
             }
             if (lane == 0) p.pat_n[pid] = nstr;
         }
