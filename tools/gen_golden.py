@@ -11,7 +11,7 @@ before the import -- the procedure SURVEY.md section 8(c) records.  Nothing of t
 copied: only its outputs on our inputs are stored.
 
 Usage: python tools/gen_golden.py            (rewrites tests/golden/)
-       python tools/gen_golden.py tails      (only the named fixtures: handmade, seeded, wide, tails)
+       python tools/gen_golden.py tails      (only the named fixtures: handmade, seeded, wide, tails, content)
 """
 import gzip
 import io
@@ -39,6 +39,7 @@ from panfeed_amd import synth  # noqa: E402
 
 sys.path.insert(0, os.path.join(REPO, "tests"))
 import pattern_model as pm  # noqa: E402  (the count-exact generator the sample-count tests use)
+import kmer_content as kc  # noqa: E402  (palindromes, repeats, A-tails, a sequence beside its reverse complement)
 
 _COMP = str.maketrans("ACGTN", "TGCAN")
 
@@ -269,7 +270,36 @@ def tails():
     return cases
 
 
-FIXTURES = {"handmade": handmade, "seeded": seeded, "wide": wide, "tails": tails}
+CONTENT_K = (8, 31, 32, 62, 63, 64, 94, 95, 96, 126)
+CONTENT_K_NONCANON = (32, 64, 126)
+
+
+def content():
+    """the reference itself on the k-mer content of tests/kmer_content.py: per k a cluster of near- and exact
+    palindromes, (AT)n and a sequence beside its reverse complement, and a cluster of homopolymers, tandem repeats and
+    sequences that differ only by trailing 'A's; one, two, three and four key words, canonical and not.  Every case has
+    maf = 0.0 (kmer_content.check_kmers applies) and as targets a strain with an exact palindrome (a near one when k is
+    odd), the (AT)n strain and the strain that carries the reverse complement of another's sequence."""
+    cases = []
+
+    def targets(kinds):
+        return [kinds[0]["pal0"], kinds[0]["rep_AT"], kinds[0]["rc"]]
+
+    for k in CONTENT_K:
+        r, names, kinds = kc.content_clusters(k)
+        cases.append(make_case(f"content_k{k}", r, names, klength=k, stroi=targets(kinds), maf=0.0))
+    for k in CONTENT_K_NONCANON:
+        r, names, kinds = kc.content_clusters(k)
+        cases.append(make_case(f"content_k{k}_noncanon", r, names, klength=k, stroi=targets(kinds)[:2], canon=False, maf=0.0))
+    r, names, kinds = kc.content_clusters(31, seed=1, absent=5)
+    cases.append(make_case("content_k31_missing", r, names, klength=31, stroi=targets(kinds), maf=0.0, consider_missing=True))
+    r, names, kinds = kc.content_clusters(64, seed=1, absent=5)
+    cases.append(make_case("content_k64_missing_nofilter", r, names, klength=64, stroi=None, maf=0.0, consider_missing=True,
+                           patfilt=False))
+    return cases
+
+
+FIXTURES = {"handmade": handmade, "seeded": seeded, "wide": wide, "tails": tails, "content": content}
 
 
 def main():
