@@ -257,6 +257,14 @@ int pf_debug_limit_pattern_slots(pf_ctx* ctx, uint64_t max_slots);
  * whose exact-size retry succeeded.  A buffer's slack is a convenience: a run must not fail while the bytes it needs
  * exist (the reference's structures grow until the machine is full, panfeed.py:146-150). */
 int pf_debug_limit_alloc(uint64_t max_bytes, uint64_t stats[2]);
+/* Test hook, read-only: out[0 .. n) = words [first, first + n) of the genome store (which = 0: what pf_genomes_upload /
+ * pf_pangenome_open_device packed, g_words of them) or of the device's packed-segment buffer of the last pf_submit /
+ * pf_submit_gather (which = 1: that call's n_words, tails and padding included -- the input the dedup pass compares word
+ * by word, which no output text shows).  Waits for the context's stream, copies with hipMemcpy; a range outside the
+ * buffer is PF_ERR_ARG.  The buffer of which = 1 is the one the batch was scanned from: no stage writes to it.  It is the
+ * context's own for a batch of host arrays and for pf_submit_gather; for a batch with on_device = 1 it is the caller's
+ * `packed`, which the context does not own: read it only while the caller keeps that buffer alive. */
+int pf_debug_read_words(pf_ctx* ctx, int which, uint64_t first, uint64_t n, uint64_t* out);
 
 /* Device buffers for callers that keep batches resident (bench.py, tests): plain hipMalloc /
  * hipMemcpy / hipFree on the context's device. */

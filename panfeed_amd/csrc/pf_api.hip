@@ -159,6 +159,7 @@ struct pf_ctx {
     } kts;
     pf_batch last{};                      // the last pf_submit's batch arrays as device pointers (valid until the next submit)
     uint32_t last_nseg = 0;
+    uint64_t last_words = 0;              // words of last.packed: the batch's, or the buffer pf_submit_gather filled
     DevBuf g_store, b_literal, g_src_off, g_src_start, g_src_flags;   // genomes resident in HBM + per-batch gather lists
     uint64_t g_words = 0;
     const pf_gather* pending_gather = nullptr;
@@ -1755,6 +1756,7 @@ struct SubmitRun {
             }
         }
         c->n_clusters = C; c->last = d; c->last_nseg = NSEG;
+        c->last_words = gth ? gth->n_words : b->n_words;
         if (!c->n_strand_words) c->last.seg_strand_off = nullptr;
         c->kt_bytes = 0; c->kt_pref_valid = false;
         pf_result res{};
@@ -1890,6 +1892,20 @@ int pf_debug_limit_alloc(uint64_t max_bytes, uint64_t stats[2]) {
         stats[1] = g_alloc_exact_retries.exchange(0);
     }
     g_alloc_limit.store(max_bytes);
+    return PF_OK;
+}
+
+int pf_debug_read_words(pf_ctx* c, int which, uint64_t first, uint64_t n, uint64_t* out) {
+    if (!c || (n && !out)) return fail(PF_ERR_ARG, "pf_debug_read_words: null argument");
+    if (which != 0 && which != 1) return fail(PF_ERR_ARG, "pf_debug_read_words: which must be 0 (genome store) or 1 (packed segments)");
+    if (which == 1 && !c->have_batch) return fail(PF_ERR_STATE, "pf_debug_read_words without a successful pf_submit");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint64_t bound = which == 0 ? c->g_words : c->last_words;
+    const uint64_t* src = which == 0 ? c->g_store.as<uint64_t>() : c->last.packed;
+    if (first > bound || n > bound - first) return fail(PF_ERR_ARG, "pf_debug_read_words: words [%llu, +%llu) outside the %llu held",
+                                                        (unsigned long long)first, (unsigned long long)n, (unsigned long long)bound);
+    if (n) HIPCHK(hipMemcpy(out, src + first, (size_t)n * 8, hipMemcpyDeviceToHost));
     return PF_OK;
 }
 
