@@ -90,6 +90,21 @@ struct SubmitScratch {
     std::vector<uint32_t> count, plan;   // key counts read back for the key-partition estimate (host items, plan_kernel's)
 };
 
+// kmers.tsv of target strains.  What the host renderer's measure pass leaves for its write pass, per sequence:
+struct KtHostText {
+    std::vector<uint8_t> rcflags;        // canonical mode, a byte per window: 0 forward, 1 the reverse complement is the
+                                         // canonical one, 2 unknown
+    std::vector<uint64_t> fl_off, size;  // the sequence's first flag; the bytes of its rows
+    uint64_t bytes = 0;                  // of all rows
+};
+// The device text's plan (kt_plan): where every tile and every host-rendered sequence starts, and the ranges
+struct KtPlan {
+    struct Range { uint32_t t0, t1, h0, h1; uint64_t base, bytes; };   // tiles [t0, t1), host sequences [h0, h1)
+    std::vector<uint64_t> toff, hoff;
+    std::vector<Range> ranges;
+    uint64_t total = 0, cap = 0, max_unit = 0, max_range = 0, peak = 0;   // peak: of two neighbouring ranges
+};
+
 }  // namespace
 
 struct pf_ctx {
@@ -129,30 +144,24 @@ struct pf_ctx {
     PinBuf txt_pins[2];                  // pinned host copies of the rendered text, used alternately so that a writer thread
                                          // may still be on the previous batch's
     int txt_slot = 0;
-    // kmers.tsv written on the device (pf_render_kmers_tsv_device): descriptors, tiles, the text; pinned blocks for its way out
-    DevBuf kt_seqs, kt_tiles, kt_prefix, kt_tbytes, kt_toff, kt_text;
+    // kmers.tsv written on the device: descriptors, tiles, and the text in ranges -- range r is written into kt_text (r
+    // even) or kt_text2 (r odd) while the range before it leaves through the pinned blocks.  pf_kmers_tsv_stream_begin /
+    // _next hand the ranges out in order; pf_render_kmers_tsv_device writes the whole text as one range into kt_text,
+    // where kt_bytes of it stay for pf_device_text_chunk.  Each begin ends the other's text.
+    DevBuf kt_seqs, kt_tiles, kt_prefix, kt_tbytes, kt_toff, kt_text, kt_text2;
     uint64_t kt_bytes = 0;
     uint32_t kt_host_seqs = 0;
     PinBuf kt_pins[2];
-    bool kt_pref_valid = false;
-    uint64_t kt_pref_off = 0, kt_pref_n = 0;
-    int kt_pref_slot = 0;
-    // the same text in ranges of bounded size (pf_kmers_tsv_stream_begin / _next): range r is written into kt_text
-    // (r even) or kt_text2 (r odd) while the range before it leaves through the pinned blocks above
-    DevBuf kt_text2;
+    struct { bool valid = false; int slot = 0; uint64_t off = 0, n = 0; } kt_pref;   // the block on its way, on `side`, into
+                                                                                     // kt_pins[slot]: n bytes from `off` of the text
     struct KtStream {
-        struct Range { uint32_t t0, t1, h0, h1; uint64_t base, bytes; };   // tiles [t0, t1), host sequences [h0, h1)
         bool active = false;
-        const pf_target_seq* seqs = nullptr;   // the caller's, until the stream ends
-        std::vector<Range> ranges;
-        std::vector<uint32_t> host_idx, sso;
-        std::vector<uint64_t> hsizes, hoff;
+        std::vector<pf_target_seq> hseqs;      // the host-rendered sequences (the caller's strings, until the stream ends)
+        KtHostText host;                       // their one measurement
+        KtPlan plan;
         pf::KtParams kp{};
         uint32_t cur = 0;                      // the block to hand out next: range cur, bytes from cur_off
-        uint64_t cur_off = 0;
-        bool pref_valid = false;               // its copy is queued on `side`, into kt_pins[pref_slot]
-        int pref_slot = 0;
-        uint64_t pref_n = 0, pin_bytes = 0;
+        uint64_t cur_off = 0, pin_bytes = 0;
         char* htext[2] = {nullptr, nullptr};   // the host's share of the range being written into each buffer
         hipEvent_t ev_prod[2] = {nullptr, nullptr};    // on `stream`: the range in buffer b is written
         hipEvent_t ev_copied[2] = {nullptr, nullptr};  // on `side`: the range in buffer b has left the device
@@ -222,12 +231,13 @@ namespace {
 // it is in flight afterwards, its host text is freed
 void kt_stream_end(pf_ctx* c) {
     pf_ctx::KtStream& S = c->kts;
-    if (!S.active) return;
-    (void)hipStreamSynchronize(c->side);
-    (void)hipStreamSynchronize(c->stream);
+    if (S.active) {
+        (void)hipStreamSynchronize(c->side);
+        (void)hipStreamSynchronize(c->stream);
+    }
     for (int b = 0; b < 2; b++) { free(S.htext[b]); S.htext[b] = nullptr; }
-    S.active = false; S.seqs = nullptr; S.pref_valid = false;
-    S.ranges.clear(); S.host_idx.clear(); S.sso.clear(); S.hsizes.clear(); S.hoff.clear();
+    S.active = false; c->kt_pref.valid = false;
+    S.hseqs.clear(); S.host = KtHostText{}; S.plan = KtPlan{};
 }
 
 int get_event(pf_ctx* c, hipEvent_t* ev) {
@@ -532,6 +542,79 @@ void ensure_b64(pf_ctx* c) {
 }
 }  // namespace
 
+namespace {
+inline char* put_i64(char* w, long long v) {
+    char tmp[24];
+    int n = 0;
+    unsigned long long u = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
+    do { tmp[n++] = (char)('0' + u % 10); u /= 10; } while (u);
+    if (v < 0) *w++ = '-';
+    while (n) *w++ = tmp[--n];
+    return w;
+}
+inline size_t len_i64(long long v) { char t[24]; return (size_t)(put_i64(t, v) - t); }
+
+// the host renderer of kmers.tsv (pf_render_kmers_tsv).  Where the fields of a row go: counted (the measure pass), or
+// written
+struct RowCount {
+    uint64_t n = 0;
+    void text(const char*, size_t l) { n += l; }
+    void ch(char) { n++; }
+    void num(long long v) { n += len_i64(v); }
+    void revcomp(const char*, uint32_t k) { n += k; }
+};
+struct RowWrite {
+    char* w;
+    void text(const char* p, size_t l) { memcpy(w, p, l); w += l; }
+    void ch(char x) { *w++ = x; }
+    void num(long long v) { w = put_i64(w, v); }
+    void revcomp(const char* last, uint32_t k) { for (uint32_t q = 0; q < k; q++) w[q] = *(last - q); w += k; }   // complement letters, backwards
+};
+
+// The rows of target sequence s, in order, field by field into `out` (two rows per window in non-canonical mode).
+// rcflag, canonical mode only: per window 0 forward, 1 the reverse complement is the canonical one, 2 unknown; a non-ACGT
+// window takes strand column and letters from the caller's list instead.  False: a window had neither.
+template <class Out>
+bool kt_host_rows(const pf_target_seq& s, uint32_t k, bool canon, const uint8_t* rcflag, Out& out) {
+    const long long nk = (long long)s.len - k + 1;
+    if (nk <= 0) return true;                    // no window, no row (panfeed.py:59,64)
+    const size_t lc = strlen(s.cluster), ls = strlen(s.strain), li = strlen(s.id), lh = strlen(s.chromosome);
+    bool ok = true;
+    uint32_t ai = 0;
+    for (long long pos = 0; pos < nk; pos++) {
+        long long ts, te;
+        if (s.strand > 0) { ts = s.start + pos; te = s.start + pos + k; }       // panfeed.py:91-94
+        else { te = s.end - pos; ts = s.end - pos - k; }                         // panfeed.py:96-99
+        for (int rep = 0; rep < (canon ? 1 : 2); rep++) {
+            out.text(s.cluster, lc); out.ch('\t');
+            out.text(s.strain, ls); out.ch('\t');
+            out.text(s.id, li); out.ch('\t');
+            out.text(s.chromosome, lh); out.ch('\t');
+            out.num(s.strand); out.ch('\t');
+            out.num(ts); out.ch('\t');
+            out.num(te); out.ch('\t');
+            out.num(pos - s.offset); out.ch('\t');                               // panfeed.py:101
+            out.num(pos + k - s.offset); out.ch('\t');                           // panfeed.py:102
+            // strand column and letters: the window's own, or what the caller worked out for a non-ACGT window
+            bool rc = rep == 1;
+            const char* given = nullptr;
+            if (canon) {
+                while (ai < s.n_ambig && s.ambig_pos[ai] < (uint64_t)pos) ai++;
+                if (ai < s.n_ambig && s.ambig_pos[ai] == (uint64_t)pos) { out.num(s.ambig_used[ai]); given = s.ambig_key[ai]; }
+                else { if (rcflag[pos] > 1) ok = false; rc = rcflag[pos] == 1; out.num(rc ? -1 : 1); }
+            } else {
+                out.num(rc ? -(long long)s.strand : s.strand);                   // panfeed.py:106-107
+            }
+            out.ch('\t');
+            if (given) out.text(given, k);
+            else if (rc) out.revcomp(s.compsequence + pos + k - 1, k);
+            else out.text(s.sequence + pos, k);
+            out.ch('\n');
+        }
+    }
+    return ok;
+}
+}  // namespace
 
 extern "C" {
 
@@ -1758,7 +1841,7 @@ struct SubmitRun {
         c->n_clusters = C; c->last = d; c->last_nseg = NSEG;
         c->last_words = gth ? gth->n_words : b->n_words;
         if (!c->n_strand_words) c->last.seg_strand_off = nullptr;
-        c->kt_bytes = 0; c->kt_pref_valid = false;
+        c->kt_bytes = 0; c->kt_pref.valid = false;
         pf_result res{};
         res.n_instances = total_inst; res.n_unique = c->counters.n_unique; res.n_kept = c->counters.n_kept;   // (the last pass's cursor)
         res.n_new_patterns = pid1 - c->pid0; res.n_patterns = pid1; res.W = W; res.key_words = KW;
@@ -2126,44 +2209,29 @@ int pf_render_hashes_to_patterns(pf_ctx* c, char** out, uint64_t* nbytes) {
 }
 
 namespace {
-inline char* put_i64(char* w, long long v) {
-    char tmp[24];
-    int n = 0;
-    unsigned long long u = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
-    do { tmp[n++] = (char)('0' + u % 10); u /= 10; } while (u);
-    if (v < 0) *w++ = '-';
-    while (n) *w++ = tmp[--n];
-    return w;
-}
-inline size_t len_i64(long long v) { char t[24]; return (size_t)(put_i64(t, v) - t); }
-}  // namespace
-
-namespace {
-// sizes_only: pass 1 alone -- the sizes of the sequences' rows in *sizes_out, their sum in *nbytes, no text (out unused)
-int render_kmers_tsv_host(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, const uint32_t* seg_strand_off, char** out,
-                          uint64_t* nbytes, std::vector<uint64_t>* sizes_out, bool sizes_only = false) {
-    if (!c || (!out && !sizes_only) || !nbytes || (n && !seqs) || (sizes_only && !sizes_out)) return fail(PF_ERR_ARG, "null argument");
+// Measure: which strand every window of the n target sequences uses, taken once from the device's strand bits, and with
+// that the exact size of every sequence's rows -- no worst-case sizing, no compaction afterwards.
+int kt_host_measure(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, const uint32_t* seg_strand_off, KtHostText& M) {
+    if (!c || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
     if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_kmers_tsv without a successful pf_submit");
     HIPCHK(hipSetDevice(c->device));
     PFCHK(fetch_strand_bits(c));          // all this renderer needs from the device (pf_fetch is not required)
     const uint32_t k = c->o.klength;
     const bool canon = c->o.canon != 0;
-    // pass 1 (parallel): which strand every window of a target sequence uses (from the device's strand bits), and with
-    // that the exact size of the sequence's rows -- no worst-case sizing, no compaction afterwards
-    std::vector<uint64_t> off((size_t)n + 1, 0), fl_off((size_t)n + 1, 0);
+    M.fl_off.assign((size_t)n + 1, 0);
     for (uint32_t i = 0; i < n; i++) {
         const long long nk = (long long)seqs[i].len - k + 1;
-        fl_off[i + 1] = fl_off[i] + (canon && nk > 0 ? (uint64_t)nk : 0);
+        M.fl_off[i + 1] = M.fl_off[i] + (canon && nk > 0 ? (uint64_t)nk : 0);
     }
-    std::vector<uint8_t> rcflags(fl_off[n], 2);     // 2 = unknown, 0 forward, 1 reverse complement is canonical
-    std::vector<uint64_t> size(n, 0);
+    M.rcflags.assign(M.fl_off[n], 2);
+    M.size.assign(n, 0);
     std::atomic<bool> bad{false};
     parallel_for(n, [&](uint64_t a, uint64_t b) {
         for (uint64_t i = a; i < b; i++) {
             const pf_target_seq& s = seqs[i];
             const long long nk = (long long)s.len - k + 1;
             if (nk <= 0) continue;
-            uint8_t* rcflag = canon ? rcflags.data() + fl_off[i] : nullptr;
+            uint8_t* rcflag = canon ? M.rcflags.data() + M.fl_off[i] : nullptr;
             if (canon) {
                 for (uint32_t j = 0; j < s.n_segs; j++) {
                     if (!seg_strand_off || c->h_strand.empty()) { bad = true; break; }
@@ -2175,100 +2243,48 @@ int render_kmers_tsv_host(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, cons
                     }
                 }
             }
-            const size_t head = strlen(s.cluster) + strlen(s.strain) + strlen(s.id) + strlen(s.chromosome) + 4 +
-                                len_i64(s.strand) + 1;
-            uint64_t bytes = 0;
-            uint32_t ai = 0;
-            for (long long pos = 0; pos < nk; pos++) {
-                long long ts, te;
-                if (s.strand > 0) { ts = s.start + pos; te = s.start + pos + k; }
-                else { te = s.end - pos; ts = s.end - pos - k; }
-                const size_t mid = len_i64(ts) + len_i64(te) + len_i64(pos - s.offset) + len_i64(pos + k - s.offset) + 4;
-                if (canon) {
-                    // strand column: the window's own (+-1), or what the caller worked out for a non-ACGT window
-                    size_t us;
-                    while (ai < s.n_ambig && s.ambig_pos[ai] < (uint64_t)pos) ai++;
-                    if (ai < s.n_ambig && s.ambig_pos[ai] == (uint64_t)pos) us = len_i64(s.ambig_used[ai]);
-                    else { if (rcflag[pos] > 1) bad = true; us = rcflag[pos] == 1 ? 2 : 1; }
-                    bytes += head + mid + us + 1 + k + 1;
-                } else {
-                    bytes += 2 * (head + mid + k + 2) + len_i64(s.strand) + len_i64(-(long long)s.strand);
-                }
-            }
-            size[i] = bytes;
+            RowCount cnt;
+            if (!kt_host_rows(s, k, canon, rcflag, cnt)) bad = true;
+            M.size[i] = cnt.n;
         }
     });
     if (bad) return fail(PF_ERR_STATE, "pf_render_kmers_tsv: strand bits missing for a target window");
-    for (uint32_t i = 0; i < n; i++) off[i + 1] = off[i] + size[i];
-    if (sizes_only) {
-        *nbytes = off[n];
-        sizes_out->swap(size);
-        return PF_OK;
-    }
-    char* buf = (char*)malloc(off[n] + 1);
-    if (!buf) return fail(PF_ERR_OOM, "malloc(%llu) failed", (unsigned long long)off[n]);
-    std::atomic<bool> bad2{false};
-    // pass 2 (parallel): the rows, each sequence at its exact place
-    parallel_for(n, [&](uint64_t a, uint64_t b) {
-        for (uint64_t i = a; i < b; i++) {
-            const pf_target_seq& s = seqs[i];
-            const long long nk = (long long)s.len - k + 1;
-            char* w = buf + off[i];
-            if (nk > 0) {
-                const uint8_t* rcflag = canon ? rcflags.data() + fl_off[i] : nullptr;
-                uint32_t ai = 0;
-                for (long long pos = 0; pos < nk; pos++) {
-                    long long ts, te;
-                    if (s.strand > 0) { ts = s.start + pos; te = s.start + pos + k; }       // panfeed.py:91-94
-                    else { te = s.end - pos; ts = s.end - pos - k; }                         // panfeed.py:96-99
-                    for (int rep = 0; rep < (canon ? 1 : 2); rep++) {
-                        size_t l;
-                        l = strlen(s.cluster); memcpy(w, s.cluster, l); w += l; *w++ = '\t';
-                        l = strlen(s.strain); memcpy(w, s.strain, l); w += l; *w++ = '\t';
-                        l = strlen(s.id); memcpy(w, s.id, l); w += l; *w++ = '\t';
-                        l = strlen(s.chromosome); memcpy(w, s.chromosome, l); w += l; *w++ = '\t';
-                        w = put_i64(w, s.strand); *w++ = '\t';
-                        w = put_i64(w, ts); *w++ = '\t';
-                        w = put_i64(w, te); *w++ = '\t';
-                        w = put_i64(w, pos - s.offset); *w++ = '\t';                        // panfeed.py:101
-                        w = put_i64(w, pos + k - s.offset); *w++ = '\t';                    // panfeed.py:102
-                        if (canon) {
-                            while (ai < s.n_ambig && s.ambig_pos[ai] < (uint64_t)pos) ai++;
-                            if (ai < s.n_ambig && s.ambig_pos[ai] == (uint64_t)pos) {
-                                w = put_i64(w, s.ambig_used[ai]); *w++ = '\t';
-                                memcpy(w, s.ambig_key[ai], k); w += k;
-                            } else {
-                                const uint8_t rc = rcflag[(size_t)pos];
-                                w = put_i64(w, rc == 1 ? -1 : 1); *w++ = '\t';
-                                if (rc == 1) for (uint32_t q = 0; q < k; q++) w[q] = s.compsequence[pos + k - 1 - q];
-                                else memcpy(w, s.sequence + pos, k);
-                                w += k;
-                            }
-                        } else {
-                            w = put_i64(w, rep == 0 ? s.strand : -(long long)s.strand); *w++ = '\t';   // panfeed.py:106-107
-                            if (rep == 0) memcpy(w, s.sequence + pos, k);
-                            else for (uint32_t q = 0; q < k; q++) w[q] = s.compsequence[pos + k - 1 - q];
-                            w += k;
-                        }
-                        *w++ = '\n';
-                    }
-                }
-            }
-            if ((uint64_t)(w - (buf + off[i])) != size[i]) bad2 = true;
+    M.bytes = std::accumulate(M.size.begin(), M.size.end(), (uint64_t)0);
+    return PF_OK;
+}
+
+// Write: the rows of the measured sequences [i0, i1), back to back from dst on, each sequence at its exact place
+int kt_host_write(pf_ctx* c, const pf_target_seq* seqs, const KtHostText& M, uint32_t i0, uint32_t i1, char* dst) {
+    const uint32_t k = c->o.klength;
+    const bool canon = c->o.canon != 0;
+    std::vector<uint64_t> off((size_t)(i1 - i0) + 1, 0);
+    for (uint32_t i = i0; i < i1; i++) off[i - i0 + 1] = off[i - i0] + M.size[i];
+    std::atomic<bool> bad{false};
+    parallel_for(i1 - i0, [&](uint64_t a, uint64_t b) {
+        for (uint64_t j = a; j < b; j++) {
+            RowWrite wr{dst + off[j]};
+            kt_host_rows(seqs[i0 + j], k, canon, canon ? M.rcflags.data() + M.fl_off[i0 + j] : nullptr, wr);
+            if ((uint64_t)(wr.w - (dst + off[j])) != M.size[i0 + j]) bad = true;
         }
     });
-    if (bad2) { free(buf); return fail(PF_ERR_STATE, "pf_render_kmers_tsv: row sizes of the two passes differ"); }
-    buf[off[n]] = 0;
-    *out = buf;
-    *nbytes = off[n];
-    if (sizes_out) sizes_out->swap(size);
+    if (bad) return fail(PF_ERR_STATE, "pf_render_kmers_tsv: row sizes of the two passes differ");
     return PF_OK;
 }
 }  // namespace
 
 int pf_render_kmers_tsv(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, const uint32_t* seg_strand_off, char** out,
                         uint64_t* nbytes) {
-    return render_kmers_tsv_host(c, seqs, n, seg_strand_off, out, nbytes, nullptr);
+    if (!out || !nbytes) return fail(PF_ERR_ARG, "null argument");
+    KtHostText M;
+    PFCHK(kt_host_measure(c, seqs, n, seg_strand_off, M));
+    char* buf = (char*)malloc(M.bytes + 1);
+    if (!buf) return fail(PF_ERR_OOM, "malloc(%llu) failed", (unsigned long long)M.bytes);
+    const int rc = kt_host_write(c, seqs, M, 0, n, buf);
+    if (rc != PF_OK) { free(buf); return rc; }
+    buf[M.bytes] = 0;
+    *out = buf;
+    *nbytes = M.bytes;
+    return PF_OK;
 }
 
 namespace {
@@ -2358,80 +2374,57 @@ int kt_host_sso(pf_ctx* c, std::vector<uint32_t>& sso) {
     }
     return PF_OK;
 }
-}  // namespace
 
-// The same rows written by the GPU (kt_len_kernel / kt_text_kernel) for the sequences kt_layout gives it and by the host
-// renderer above for the others, which are copied to their places in the device text: the text of all n sequences, in
-// order, stays in device memory and is handed out block by block (pf_device_text_chunk).
-int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t* nbytes) {
-    if (!c || !nbytes || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
-    if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_kmers_tsv_device without a successful pf_submit");
-    HIPCHK(hipSetDevice(c->device));
-    kt_stream_end(c);
-    c->kt_bytes = 0; c->kt_pref_valid = false;
-    KtLayout L;
-    PFCHK(kt_layout(c, seqs, n, L));
-    const std::vector<uint2>& tiles = L.tiles;
-    const std::vector<uint32_t>& host_idx = L.host_idx;
-    // ---- the host's share, rendered in one go (its sequences' sizes come back with it)
-    char* htext = nullptr;
-    uint64_t hbytes = 0;
-    std::vector<uint64_t> hsizes;
-    struct FreeText { char*& p; ~FreeText() { free(p); } } free_htext{htext};
-    if (!host_idx.empty()) {
-        std::vector<pf_target_seq> hs(host_idx.size());
-        for (size_t j = 0; j < host_idx.size(); j++) hs[j] = seqs[host_idx[j]];
-        std::vector<uint32_t> sso;
-        PFCHK(kt_host_sso(c, sso));
-        PFCHK(render_kmers_tsv_host(c, hs.data(), (uint32_t)hs.size(), sso.empty() ? nullptr : sso.data(), &htext, &hbytes, &hsizes));
-    }
-    // ---- offsets, in the order of the sequences
-    const uint32_t NT = (uint32_t)tiles.size();
-    std::vector<uint64_t> toff(NT), hoff(host_idx.size());
-    uint64_t total = 0;
-    {
-        size_t ti = 0, hi = 0;
-        uint32_t si = 0;
-        for (uint32_t i = 0; i < n; i++) {
-            if (L.on_dev[i]) {
-                while (ti < NT && tiles[ti].x == si) { toff[ti] = total; total += L.tbytes[ti]; ti++; }
-                si++;
-            } else if (hi < host_idx.size() && host_idx[hi] == i) {
-                hoff[hi] = total; total += hsizes[hi]; hi++;
-            }
+// The plan of a text: its units in the order of the sequences -- a tile of a device-written sequence, or a whole
+// host-rendered sequence; a sequence with no window is neither and drops out -- each unit's offset, and the ranges the
+// text is produced in: the whole text when it fits the budget, else pieces of at most budget / 2 (with the 64 bytes of
+// slack every text buffer has), cut between units.
+void kt_plan(const KtLayout& L, const std::vector<uint64_t>& hsizes, uint64_t budget, KtPlan& P) {
+    const size_t NT = L.tiles.size(), NH = L.host_idx.size();
+    P = KtPlan{};
+    P.toff.resize(NT); P.hoff.resize(NH);
+    const uint64_t all = std::accumulate(L.tbytes.begin(), L.tbytes.end(), (uint64_t)0) + std::accumulate(hsizes.begin(), hsizes.end(), (uint64_t)0);
+    P.cap = all + 64 <= budget ? all : (budget / 2 > 64 ? budget / 2 - 64 : 0);
+    KtPlan::Range cur{0, 0, 0, 0, 0, 0};
+    auto unit = [&](uint64_t bytes, uint64_t& off) {
+        if (cur.bytes && cur.bytes + bytes > P.cap) {
+            P.ranges.push_back(cur);
+            cur = KtPlan::Range{cur.t1, cur.t1, cur.h1, cur.h1, cur.base + cur.bytes, 0};
+        }
+        off = cur.base + cur.bytes;
+        cur.bytes += bytes;
+        P.max_unit = std::max(P.max_unit, bytes);
+    };
+    size_t ti = 0, hi = 0;
+    uint32_t si = 0;                             // device-written sequences so far: tiles[].x counts those
+    for (uint32_t i = 0; i < (uint32_t)L.on_dev.size(); i++) {
+        if (L.on_dev[i]) {
+            for (; ti < NT && L.tiles[ti].x == si; cur.t1 = (uint32_t)++ti) unit(L.tbytes[ti], P.toff[ti]);
+            si++;
+        } else if (hi < NH && L.host_idx[hi] == i) {
+            unit(hsizes[hi], P.hoff[hi]);
+            cur.h1 = (uint32_t)++hi;
         }
     }
-    PFCHK(c->kt_text.ensure((size_t)total + 64));
-    if (NT) {
-        HIPCHK(hipMemcpyAsync(c->kt_toff.p, toff.data(), (size_t)NT * 8, hipMemcpyHostToDevice, c->stream));
-        pf::KtParams kp = L.kp;
-        kp.text = c->kt_text.as<char>();
-        hipLaunchKernelGGL(pf::kt_text_kernel, dim3(NT), dim3(pf::KT_ROWS), 0, c->stream, kp);
-        HIPCHK(hipGetLastError());
+    if (cur.bytes) P.ranges.push_back(cur);
+    P.total = cur.base + cur.bytes;
+    for (size_t r = 0; r < P.ranges.size(); r++) {
+        P.max_range = std::max(P.max_range, P.ranges[r].bytes);
+        P.peak = std::max(P.peak, P.ranges[r].bytes + (r + 1 < P.ranges.size() ? P.ranges[r + 1].bytes : 0));
     }
-    {
-        uint64_t at = 0;
-        for (size_t j = 0; j < host_idx.size(); j++) {
-            if (hsizes[j]) HIPCHK(hipMemcpyAsync(c->kt_text.as<char>() + hoff[j], htext + at, (size_t)hsizes[j], hipMemcpyHostToDevice, c->stream));
-            at += hsizes[j];
-        }
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->kt_bytes = total;
-    c->kt_host_seqs = (uint32_t)host_idx.size();
-    *nbytes = total;
-    return PF_OK;
 }
+}  // namespace
 
 namespace {
 constexpr uint64_t KT_BLOCK = 64ull << 20;    // bytes per block a stream hands out (DeviceText.chunks' default too)
 
-// range r of the stream written into its buffer (kt_text for even r, kt_text2 for odd) on c->stream: its tiles by
-// kt_text_kernel, its host-rendered sequences by the host renderer now and copied up.  From r = 2 on the buffer's range
-// before (r - 2) must have left the device first: c->stream waits for that range's last copy on c->side.
+// range r of the open text written into its buffer (kt_text for even r, kt_text2 for odd) on c->stream: its tiles by
+// kt_text_kernel, its host-rendered sequences written by the host now, from their one measurement, and copied up.  From
+// r = 2 on the buffer's range before (r - 2) must have left the device first: c->stream waits for that range's last
+// copy on c->side.
 int kt_produce(pf_ctx* c, uint32_t r) {
     pf_ctx::KtStream& S = c->kts;
-    const pf_ctx::KtStream::Range& R = S.ranges[r];
+    const KtPlan::Range& R = S.plan.ranges[r];
     const int b = (int)(r & 1);
     char* buf = (b ? c->kt_text2 : c->kt_text).as<char>();
     if (r >= 2) {
@@ -2446,20 +2439,72 @@ int kt_produce(pf_ctx* c, uint32_t r) {
         HIPCHK(hipGetLastError());
     }
     if (R.h1 > R.h0) {
-        std::vector<pf_target_seq> hs(R.h1 - R.h0);
-        for (uint32_t j = R.h0; j < R.h1; j++) hs[j - R.h0] = S.seqs[S.host_idx[j]];
-        uint64_t hbytes = 0;
-        std::vector<uint64_t> hsizes;
-        PFCHK(render_kmers_tsv_host(c, hs.data(), (uint32_t)hs.size(), S.sso.empty() ? nullptr : S.sso.data(), &S.htext[b],
-                                    &hbytes, &hsizes));
+        const uint64_t* hsize = S.host.size.data();
+        const uint64_t hbytes = std::accumulate(hsize + R.h0, hsize + R.h1, (uint64_t)0);
+        if (!(S.htext[b] = (char*)malloc(hbytes + 1))) return fail(PF_ERR_OOM, "malloc(%llu) failed", (unsigned long long)hbytes);
+        PFCHK(kt_host_write(c, S.hseqs.data(), S.host, R.h0, R.h1, S.htext[b]));
         uint64_t at = 0;
         for (uint32_t j = R.h0; j < R.h1; j++) {
-            if (hsizes[j - R.h0] != S.hsizes[j]) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream: a sequence's size changed between its two renderings");
-            if (S.hsizes[j]) HIPCHK(hipMemcpyAsync(buf + (S.hoff[j] - R.base), S.htext[b] + at, (size_t)S.hsizes[j], hipMemcpyHostToDevice, c->stream));
-            at += S.hsizes[j];
+            if (hsize[j]) HIPCHK(hipMemcpyAsync(buf + (S.plan.hoff[j] - R.base), S.htext[b] + at, (size_t)hsize[j], hipMemcpyHostToDevice, c->stream));
+            at += hsize[j];
         }
     }
     HIPCHK(hipEventRecord(S.ev_prod[b], c->stream));
+    return PF_OK;
+}
+
+// What the two device texts share: the layout, the host's share measured, the plan within `budget`, the buffers, and
+// the first two ranges on their way (there is only one when the text fits the budget).  The stream is open afterwards;
+// a failure leaves none.
+int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget) {
+    kt_stream_end(c);
+    c->kt_bytes = 0; c->kt_pref.valid = false;     // (pf_device_text_chunk's text is gone: the buffers are reused)
+    pf_ctx::KtStream& S = c->kts;
+    S.active = true;
+    struct Guard { pf_ctx* c; bool ok; ~Guard() { if (!ok) kt_stream_end(c); } } guard{c, false};
+    KtLayout L;
+    PFCHK(kt_layout(c, seqs, n, L));
+    // ---- the host's share: measured here, written range by range
+    S.hseqs.resize(L.host_idx.size());
+    for (size_t j = 0; j < L.host_idx.size(); j++) S.hseqs[j] = seqs[L.host_idx[j]];
+    if (!S.hseqs.empty()) {
+        std::vector<uint32_t> sso;
+        PFCHK(kt_host_sso(c, sso));
+        PFCHK(kt_host_measure(c, S.hseqs.data(), (uint32_t)S.hseqs.size(), sso.empty() ? nullptr : sso.data(), S.host));
+    }
+    const KtPlan& P = S.plan;
+    kt_plan(L, S.host.size, budget, S.plan);
+    if (P.max_unit > P.cap)
+        return fail(PF_ERR_ARG, "kmers.tsv budget of %llu bytes is too small for this batch: its largest tile or host-rendered "
+                    "sequence is %llu bytes, the smallest budget that works is %llu", (unsigned long long)budget,
+                    (unsigned long long)P.max_unit, (unsigned long long)(2 * (P.max_unit + 64)));
+    // ---- the buffers, the events, the first two ranges on their way
+    const uint32_t NR = (uint32_t)P.ranges.size(), NT = (uint32_t)L.tiles.size();
+    if (NR <= 1) PFCHK(c->kt_text.ensure((size_t)P.total + 64));
+    else {
+        PFCHK(c->kt_text.ensure((size_t)P.max_range + 64, true));
+        PFCHK(c->kt_text2.ensure((size_t)P.max_range + 64, true));
+    }
+    if (NT) HIPCHK(hipMemcpyAsync(c->kt_toff.p, P.toff.data(), (size_t)NT * 8, hipMemcpyHostToDevice, c->stream));
+    for (int b = 0; b < 2; b++) {
+        if (!S.ev_prod[b]) HIPCHK(hipEventCreateWithFlags(&S.ev_prod[b], hipEventDisableTiming));
+        if (!S.ev_copied[b]) HIPCHK(hipEventCreateWithFlags(&S.ev_copied[b], hipEventDisableTiming));
+    }
+    S.kp = L.kp;
+    S.cur = 0; S.cur_off = 0;
+    S.pin_bytes = std::max<uint64_t>(1, std::min(KT_BLOCK, P.max_range));
+    for (uint32_t r = 0; r < std::min(NR, 2u); r++) PFCHK(kt_produce(c, r));
+    c->kt_host_seqs = (uint32_t)S.hseqs.size();
+    guard.ok = true;
+    return PF_OK;
+}
+
+// n bytes at src, which start at byte `off` of the text, on their way into pinned slot `slot` (of `block` bytes) on
+// c->side: the one block in flight that pf_device_text_chunk or pf_kmers_tsv_stream_next picks up next
+int kt_prefetch(pf_ctx* c, int slot, const char* src, uint64_t off, uint64_t n, uint64_t block) {
+    PFCHK(c->kt_pins[slot].ensure(block, true));
+    if (n) HIPCHK(hipMemcpyAsync(c->kt_pins[slot].p, src, n, hipMemcpyDeviceToHost, c->side));
+    c->kt_pref.valid = true; c->kt_pref.slot = slot; c->kt_pref.off = off; c->kt_pref.n = n;
     return PF_OK;
 }
 
@@ -2467,21 +2512,37 @@ int kt_produce(pf_ctx* c, uint32_t r) {
 // last block of range r also marks the range's buffer free, and range r + 2 is queued into it
 int kt_copy_block(pf_ctx* c, int slot) {
     pf_ctx::KtStream& S = c->kts;
-    const pf_ctx::KtStream::Range& R = S.ranges[S.cur];
+    const KtPlan::Range& R = S.plan.ranges[S.cur];
     const int b = (int)(S.cur & 1);
     const char* buf = (b ? c->kt_text2 : c->kt_text).as<char>();
     const uint64_t n = std::min<uint64_t>(S.pin_bytes, R.bytes - S.cur_off);
-    PFCHK(c->kt_pins[slot].ensure(S.pin_bytes, true));
     HIPCHK(hipStreamWaitEvent(c->side, S.ev_prod[b], 0));
-    HIPCHK(hipMemcpyAsync(c->kt_pins[slot].p, buf + S.cur_off, n, hipMemcpyDeviceToHost, c->side));
-    S.pref_valid = true; S.pref_slot = slot; S.pref_n = n;
+    PFCHK(kt_prefetch(c, slot, buf + S.cur_off, R.base + S.cur_off, n, S.pin_bytes));
     if (S.cur_off + n == R.bytes) {
         HIPCHK(hipEventRecord(S.ev_copied[b], c->side));
-        if (S.cur + 2 < S.ranges.size()) PFCHK(kt_produce(c, S.cur + 2));
+        if (S.cur + 2 < S.plan.ranges.size()) PFCHK(kt_produce(c, S.cur + 2));
     }
     return PF_OK;
 }
 }  // namespace
+
+// The same rows written by the GPU (kt_len_kernel / kt_text_kernel) for the sequences kt_layout gives it and by the host
+// renderer above for the others, which are copied to their places in the device text: the text of all n sequences, in
+// order, stays in device memory and is handed out block by block (pf_device_text_chunk).  It is the stream's plan with
+// no budget -- one range, written into kt_text -- and no stream is left open: the caller's seqs die with the call.
+int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t* nbytes) {
+    if (!c || !nbytes || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
+    if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_kmers_tsv_device without a successful pf_submit");
+    HIPCHK(hipSetDevice(c->device));
+    PFCHK(kt_open(c, seqs, n, ~0ull));
+    const uint64_t total = c->kts.plan.total;
+    const hipError_t text_written = hipStreamSynchronize(c->stream);
+    kt_stream_end(c);
+    HIPCHK(text_written);
+    c->kt_bytes = total;
+    *nbytes = total;
+    return PF_OK;
+}
 
 // The text of pf_render_kmers_tsv_device in ranges: cut at tile and host-sequence boundaries so that each range takes at
 // most half the budget, written range by range into two device buffers used alternately, range r + 1 written while range
@@ -2491,101 +2552,13 @@ int pf_kmers_tsv_stream_begin(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, 
     if (!c || !total_bytes || !n_ranges || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
     if (!c->have_batch) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_begin without a successful pf_submit");
     HIPCHK(hipSetDevice(c->device));
-    kt_stream_end(c);
-    c->kt_bytes = 0; c->kt_pref_valid = false;     // (pf_device_text_chunk's text is gone: the buffers are reused)
     *total_bytes = 0; *n_ranges = 0;
     if (peak_text_bytes) *peak_text_bytes = 0;
-    pf_ctx::KtStream& S = c->kts;
-    KtLayout L;
-    PFCHK(kt_layout(c, seqs, n, L));
-    const uint32_t NT = (uint32_t)L.tiles.size();
-    S.host_idx.swap(L.host_idx);
-    // ---- the host's share: sizes only (its rows are rendered range by range)
-    S.hsizes.clear();
-    if (!S.host_idx.empty()) {
-        std::vector<pf_target_seq> hs(S.host_idx.size());
-        for (size_t j = 0; j < S.host_idx.size(); j++) hs[j] = seqs[S.host_idx[j]];
-        PFCHK(kt_host_sso(c, S.sso));
-        uint64_t hb = 0;
-        PFCHK(render_kmers_tsv_host(c, hs.data(), (uint32_t)hs.size(), S.sso.empty() ? nullptr : S.sso.data(), nullptr, &hb,
-                                    &S.hsizes, true));
-    }
-    // ---- offsets in the order of the sequences, the largest unit
-    std::vector<uint64_t> toff(NT);
-    S.hoff.assign(S.host_idx.size(), 0);
-    uint64_t total = 0, max_unit = 0;
-    {
-        size_t ti = 0, hi = 0;
-        uint32_t si = 0;
-        for (uint32_t i = 0; i < n; i++) {
-            if (L.on_dev[i]) {
-                while (ti < NT && L.tiles[ti].x == si) { toff[ti] = total; total += L.tbytes[ti]; max_unit = std::max<uint64_t>(max_unit, L.tbytes[ti]); ti++; }
-                si++;
-            } else if (hi < S.host_idx.size() && S.host_idx[hi] == i) {
-                S.hoff[hi] = total; total += S.hsizes[hi]; max_unit = std::max(max_unit, S.hsizes[hi]); hi++;
-            }
-        }
-    }
-    // ---- the ranges: the whole text when it fits the budget, else pieces of at most budget / 2 (with the 64 bytes of
-    // slack every text buffer has)
-    const bool one = total + 64 <= budget_bytes;
-    const uint64_t cap = one ? total : (budget_bytes / 2 > 64 ? budget_bytes / 2 - 64 : 0);
-    if (!one && max_unit > cap)
-        return fail(PF_ERR_ARG, "kmers.tsv budget of %llu bytes is too small for this batch: its largest tile or host-rendered "
-                    "sequence is %llu bytes, the smallest budget that works is %llu", (unsigned long long)budget_bytes,
-                    (unsigned long long)max_unit, (unsigned long long)(2 * (max_unit + 64)));
-    S.ranges.clear();
-    {
-        pf_ctx::KtStream::Range cur{0, 0, 0, 0, 0, 0};
-        size_t ti = 0, hi = 0;
-        uint32_t si = 0;
-        auto add = [&](uint64_t bytes) {
-            if (cur.bytes && cur.bytes + bytes > cap) {
-                S.ranges.push_back(cur);
-                cur = pf_ctx::KtStream::Range{cur.t1, cur.t1, cur.h1, cur.h1, cur.base + cur.bytes, 0};
-            }
-            cur.bytes += bytes;
-        };
-        for (uint32_t i = 0; i < n; i++) {
-            if (L.on_dev[i]) {
-                while (ti < NT && L.tiles[ti].x == si) { add(L.tbytes[ti]); cur.t1 = (uint32_t)++ti; }
-                si++;
-            } else if (hi < S.host_idx.size() && S.host_idx[hi] == i) {
-                add(S.hsizes[hi]); cur.h1 = (uint32_t)++hi;
-            }
-        }
-        if (cur.bytes) S.ranges.push_back(cur);
-    }
-    const uint32_t NR = (uint32_t)S.ranges.size();
-    uint64_t max_range = 0, peak = 0;
-    for (uint32_t r = 0; r < NR; r++) {
-        max_range = std::max(max_range, S.ranges[r].bytes);
-        peak = std::max(peak, S.ranges[r].bytes + (r + 1 < NR ? S.ranges[r + 1].bytes : 0));
-    }
-    // ---- the buffers, the events, the first two ranges on their way
-    if (NR == 1) PFCHK(c->kt_text.ensure((size_t)total + 64));
-    else if (NR > 1) {
-        PFCHK(c->kt_text.ensure((size_t)max_range + 64, true));
-        PFCHK(c->kt_text2.ensure((size_t)max_range + 64, true));
-    }
-    if (NT) HIPCHK(hipMemcpyAsync(c->kt_toff.p, toff.data(), (size_t)NT * 8, hipMemcpyHostToDevice, c->stream));
-    for (int b = 0; b < 2; b++) {
-        if (!S.ev_prod[b]) HIPCHK(hipEventCreateWithFlags(&S.ev_prod[b], hipEventDisableTiming));
-        if (!S.ev_copied[b]) HIPCHK(hipEventCreateWithFlags(&S.ev_copied[b], hipEventDisableTiming));
-    }
-    S.kp = L.kp;
-    S.seqs = seqs;
-    S.cur = 0; S.cur_off = 0; S.pref_valid = false;
-    S.pin_bytes = std::max<uint64_t>(1, std::min(KT_BLOCK, max_range));
-    S.active = true;
-    for (uint32_t r = 0; r < std::min(NR, 2u); r++) {
-        const int rc = kt_produce(c, r);
-        if (rc != PF_OK) { kt_stream_end(c); return rc; }
-    }
-    c->kt_host_seqs = (uint32_t)S.host_idx.size();
-    *total_bytes = total;
-    *n_ranges = NR;
-    if (peak_text_bytes) *peak_text_bytes = peak;
+    PFCHK(kt_open(c, seqs, n, budget_bytes));
+    const KtPlan& P = c->kts.plan;
+    *total_bytes = P.total;
+    *n_ranges = (uint32_t)P.ranges.size();
+    if (peak_text_bytes) *peak_text_bytes = P.peak;
     return PF_OK;
 }
 
@@ -2595,15 +2568,15 @@ int pf_kmers_tsv_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
     pf_ctx::KtStream& S = c->kts;
     if (!S.active) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_next without an open pf_kmers_tsv_stream_begin");
     HIPCHK(hipSetDevice(c->device));
-    if (S.cur >= S.ranges.size()) { kt_stream_end(c); return PF_OK; }
-    if (!S.pref_valid) PFCHK(kt_copy_block(c, 0));
+    if (S.cur >= S.plan.ranges.size()) { kt_stream_end(c); return PF_OK; }
+    if (!c->kt_pref.valid) PFCHK(kt_copy_block(c, 0));
     HIPCHK(hipStreamSynchronize(c->side));
-    const int slot = S.pref_slot;
-    const uint64_t n = S.pref_n;
-    S.pref_valid = false;
+    const int slot = c->kt_pref.slot;
+    const uint64_t n = c->kt_pref.n;
+    c->kt_pref.valid = false;
     S.cur_off += n;
-    if (S.cur_off == S.ranges[S.cur].bytes) { S.cur++; S.cur_off = 0; }
-    if (S.cur < S.ranges.size()) PFCHK(kt_copy_block(c, slot ^ 1));      // the next block on its way meanwhile
+    if (S.cur_off == S.plan.ranges[S.cur].bytes) { S.cur++; S.cur_off = 0; }
+    if (S.cur < S.plan.ranges.size()) PFCHK(kt_copy_block(c, slot ^ 1));      // the next block on its way meanwhile
     *ptr = c->kt_pins[slot].as<char>();
     *nbytes = n;
     return PF_OK;
@@ -2616,26 +2589,21 @@ int pf_device_text_chunk(pf_ctx* c, uint64_t offset, uint64_t max_bytes, const c
     if (offset > c->kt_bytes) return fail(PF_ERR_ARG, "offset beyond the text");
     HIPCHK(hipSetDevice(c->device));
     const uint64_t n = std::min<uint64_t>(max_bytes, c->kt_bytes - offset);
-    int slot;
-    if (c->kt_pref_valid && c->kt_pref_off == offset && c->kt_pref_n == n) {
-        slot = c->kt_pref_slot;                       // requested by the call before: wait for it
-        HIPCHK(hipStreamSynchronize(c->side));
-    } else {
+    const char* text = c->kt_text.as<char>();
+    if (!n) {                                         // (nothing to copy, and the block in flight, if any, stays)
+        PFCHK(c->kt_pins[0].ensure(max_bytes, true));
+        *ptr = c->kt_pins[0].as<char>(); *nbytes = 0;
+        return PF_OK;
+    }
+    if (!(c->kt_pref.valid && c->kt_pref.off == offset && c->kt_pref.n == n)) {
         HIPCHK(hipStreamSynchronize(c->side));        // (a block in flight that nobody asked for)
-        slot = 0;
-        PFCHK(c->kt_pins[slot].ensure(max_bytes, true));
-        if (n) HIPCHK(hipMemcpyAsync(c->kt_pins[slot].p, c->kt_text.as<char>() + offset, n, hipMemcpyDeviceToHost, c->side));
-        HIPCHK(hipStreamSynchronize(c->side));
+        PFCHK(kt_prefetch(c, 0, text + offset, offset, n, max_bytes));
     }
-    c->kt_pref_valid = false;
+    HIPCHK(hipStreamSynchronize(c->side));            // requested by the call before, or just now: wait for it
+    const int slot = c->kt_pref.slot;
+    c->kt_pref.valid = false;
     const uint64_t next = offset + n;
-    if (n && next < c->kt_bytes) {
-        const int ns = slot ^ 1;
-        PFCHK(c->kt_pins[ns].ensure(max_bytes, true));
-        const uint64_t nn = std::min<uint64_t>(max_bytes, c->kt_bytes - next);
-        HIPCHK(hipMemcpyAsync(c->kt_pins[ns].p, c->kt_text.as<char>() + next, nn, hipMemcpyDeviceToHost, c->side));
-        c->kt_pref_valid = true; c->kt_pref_off = next; c->kt_pref_n = nn; c->kt_pref_slot = ns;
-    }
+    if (next < c->kt_bytes) PFCHK(kt_prefetch(c, slot ^ 1, text + next, next, std::min<uint64_t>(max_bytes, c->kt_bytes - next), max_bytes));
     *ptr = c->kt_pins[slot].as<char>();
     *nbytes = n;
     return PF_OK;
@@ -3092,6 +3060,26 @@ int text_pin(pf_ctx* c, size_t total) {
     c->txt_slot ^= 1;
     return c->txt_pins[c->txt_slot].ensure(total);
 }
+// hashes_to_patterns rows on the device.  The lengths of n rows into d_len: of the patterns order[0 .. n) (a device
+// list), or of patterns pid0 .. pid0 + n without a list
+int hp_rowlen(pf_ctx* c, const uint32_t* order, uint32_t pid0, uint32_t n, uint32_t* d_len) {
+    hipLaunchKernelGGL(pf::hp_rowlen_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->pat_n.as<uint32_t>(),
+                       c->o.consider_missing ? c->pat_nan.as<uint32_t>() : (const uint32_t*)nullptr, c->W, pid0, order, n, d_len);
+    HIPCHK(hipGetLastError());
+    return PF_OK;
+}
+// the rows of the patterns order[0 .. n), row i written at text + row_off[i] (device arrays)
+int hp_text(pf_ctx* c, const uint32_t* order, const uint64_t* row_off, uint32_t n, char* text) {
+    pf::HpTextParams hpp{};
+    hpp.order = order; hpp.row_off = row_off;
+    hpp.pat_bits = c->pat_bits.as<uint32_t>();
+    hpp.pat_nan = c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr;
+    hpp.pat_n = c->pat_n.as<uint32_t>(); hpp.b64 = c->pat_b64.as<char>();
+    hpp.text = text; hpp.n = n; hpp.W = c->W;
+    hipLaunchKernelGGL(pf::hp_text_kernel, dim3(n), dim3(256), 0, c->stream, hpp);
+    HIPCHK(hipGetLastError());
+    return PF_OK;
+}
 }  // namespace
 
 int pf_render_pattern_rows(pf_ctx* c, const uint32_t* pids, uint64_t n, const char** text, uint64_t* nbytes) {
@@ -3103,16 +3091,13 @@ int pf_render_pattern_rows(pf_ctx* c, const uint32_t* pids, uint64_t n, const ch
     for (uint64_t i = 0; i < n; i++)
         if (pids[i] >= c->n_patterns) return fail(PF_ERR_ARG, "pf_render_pattern_rows: pattern id %u out of range (%u patterns)", pids[i], c->n_patterns);
     hipStream_t st = c->stream;
-    const uint32_t P = (uint32_t)n, W = c->W;
+    const uint32_t P = (uint32_t)n;
     PFCHK(ensure_b64_dev(c));
     PFCHK(c->rp_order.ensure((size_t)P * 4));
     PFCHK(c->rp_rlen.ensure((size_t)P * 4));
     PFCHK(c->rp_rowoff.ensure(((size_t)P + 1) * 8));
     HIPCHK(hipMemcpyAsync(c->rp_order.p, pids, (size_t)P * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(pf::hp_rowlen_kernel, dim3((P + 255) / 256), dim3(256), 0, st, c->pat_n.as<uint32_t>(),
-                       c->o.consider_missing ? c->pat_nan.as<uint32_t>() : (const uint32_t*)nullptr, W, 0u,
-                       c->rp_order.as<uint32_t>(), P, c->rp_rlen.as<uint32_t>());
-    HIPCHK(hipGetLastError());
+    PFCHK(hp_rowlen(c, c->rp_order.as<uint32_t>(), 0u, P, c->rp_rlen.as<uint32_t>()));
     std::vector<uint32_t> rlen(P);
     HIPCHK(hipMemcpyAsync(rlen.data(), c->rp_rlen.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -3122,14 +3107,7 @@ int pf_render_pattern_rows(pf_ctx* c, const uint32_t* pids, uint64_t n, const ch
     PFCHK(c->txt_dev.ensure(total + 16));
     PFCHK(text_pin(c, total + 16));
     HIPCHK(hipMemcpyAsync(c->rp_rowoff.p, row_off.data(), ((size_t)P + 1) * 8, hipMemcpyHostToDevice, st));
-    pf::HpTextParams hpp{};
-    hpp.order = c->rp_order.as<uint32_t>(); hpp.row_off = c->rp_rowoff.as<uint64_t>();
-    hpp.pat_bits = c->pat_bits.as<uint32_t>();
-    hpp.pat_nan = c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr;
-    hpp.pat_n = c->pat_n.as<uint32_t>(); hpp.b64 = c->pat_b64.as<char>();
-    hpp.text = c->txt_dev.as<char>(); hpp.n = P; hpp.W = W;
-    hipLaunchKernelGGL(pf::hp_text_kernel, dim3(P), dim3(256), 0, st, hpp);
-    HIPCHK(hipGetLastError());
+    PFCHK(hp_text(c, c->rp_order.as<uint32_t>(), c->rp_rowoff.as<uint64_t>(), P, c->txt_dev.as<char>()));
     char* pin = c->txt_pins[c->txt_slot].as<char>();
     HIPCHK(hipMemcpyAsync(pin, c->txt_dev.p, total, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -3149,7 +3127,7 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
     if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_device needs a successful pf_submit");
     if (c->o.multiple_files) return fail(PF_ERR_ARG, "pf_render_device writes one pair of texts per batch; use the host renderers under multiple_files");
     HIPCHK(hipSetDevice(c->device));
-    const uint32_t C = c->n_clusters, W = c->W, KW = (uint32_t)c->KW, k = c->o.klength;
+    const uint32_t C = c->n_clusters, KW = (uint32_t)c->KW, k = c->o.klength;
     if (C && !names) return fail(PF_ERR_ARG, "pf_render_device: cluster names missing");
     if (c->n_passes > pf::TEXT_MAX_ARENAS) return fail(PF_ERR_CAPACITY, "pf_render_device: too many passes (%u)", c->n_passes);
     hipStream_t st = c->stream;
@@ -3166,10 +3144,7 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
     DevBuf d_rlen;
     if (P) {
         PFCHK(d_rlen.ensure((size_t)P * 4));
-        hipLaunchKernelGGL(pf::hp_rowlen_kernel, dim3((P + 255) / 256), dim3(256), 0, st, c->pat_n.as<uint32_t>(),
-                           c->o.consider_missing ? c->pat_nan.as<uint32_t>() : (const uint32_t*)nullptr, W, p0,
-                           (const uint32_t*)nullptr, P, d_rlen.as<uint32_t>());
-        HIPCHK(hipGetLastError());
+        PFCHK(hp_rowlen(c, nullptr, p0, P, d_rlen.as<uint32_t>()));
         HIPCHK(hipMemcpyAsync(fs.data(), c->pt.first_seen + p0, (size_t)P * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(rlen.data(), d_rlen.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
     }
@@ -3184,7 +3159,7 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
         const uint32_t L = (uint32_t)strlen(names[i]);
         blob.append(names[i], L);
         name_off[i + 1] = (uint32_t)blob.size();
-        const uint64_t head = L + 2 + 24 + 1, rowlen = (uint64_t)L + 1 + k + 1 + 24 + 1;
+        const uint64_t head = pf::kh_head_len(L), rowlen = pf::kh_row_len(L, k);
         if (head + rowlen > pf::TEXT_TILE) return fail(PF_ERR_ARG, "cluster name too long for the text kernel (%u bytes)", L);
         rows_per_block = std::min<uint32_t>(rows_per_block, (uint32_t)((pf::TEXT_TILE - head) / rowlen));
         text_off[i + 1] = text_off[i] + head + (uint64_t)kcnt[i] * rowlen;
@@ -3245,16 +3220,7 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
         hipLaunchKernelGGL(pf::kh_text_kernel, dim3((uint32_t)blk_cluster.size()), dim3(256), 0, st, kp);
         HIPCHK(hipGetLastError());
     }
-    if (P) {
-        pf::HpTextParams hpp{};
-        hpp.order = (const uint32_t*)(dm + o_order); hpp.row_off = (const uint64_t*)(dm + o_rowoff);
-        hpp.pat_bits = c->pat_bits.as<uint32_t>();
-        hpp.pat_nan = c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr;
-        hpp.pat_n = c->pat_n.as<uint32_t>(); hpp.b64 = c->pat_b64.as<char>();
-        hpp.text = c->txt_dev.as<char>() + hp_at; hpp.n = P; hpp.W = W;
-        hipLaunchKernelGGL(pf::hp_text_kernel, dim3(P), dim3(256), 0, st, hpp);
-        HIPCHK(hipGetLastError());
-    }
+    if (P) PFCHK(hp_text(c, (const uint32_t*)(dm + o_order), (const uint64_t*)(dm + o_rowoff), P, c->txt_dev.as<char>() + hp_at));
     if (kh_n) HIPCHK(hipMemcpyAsync(txt_pin, c->txt_dev.p, kh_n, hipMemcpyDeviceToHost, st));
     if (hp_n) HIPCHK(hipMemcpyAsync(txt_pin + hp_at, c->txt_dev.as<char>() + hp_at, hp_n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

@@ -4742,6 +4742,21 @@ __global__ __launch_bounds__(256) void b64_kernel(const uint8_t* md5, uint32_t p
 
 constexpr uint32_t TEXT_TILE = 24576;        // bytes of text a workgroup assembles at a time
 constexpr uint32_t TEXT_MAX_ARENAS = 16;
+// an LDS tile out to the text, tile[mis + i] -> g[i] with g + (16 - mis) 16-byte aligned: the unaligned head and tail
+// byte by byte, the middle as 16-byte pieces
+__device__ __forceinline__ void tile_store(const char* tile, uint32_t mis, char* g, uint32_t nbytes) {
+    const uint32_t lead = min(nbytes, (16 - mis) & 15);
+    for (uint32_t i = threadIdx.x; i < lead; i += blockDim.x) g[i] = tile[mis + i];
+    const uint32_t mid = (nbytes - lead) >> 4;
+    const uint4* src = reinterpret_cast<const uint4*>(tile + mis + lead);
+    uint4* dst = reinterpret_cast<uint4*>(g + lead);
+    for (uint32_t i = threadIdx.x; i < mid; i += blockDim.x) dst[i] = src[i];
+    for (uint32_t i = lead + (mid << 4) + threadIdx.x; i < nbytes; i += blockDim.x) g[i] = tile[mis + i];
+}
+// kmers_to_hashes.tsv, a cluster whose name has L bytes: its own row "<idx>\t\t<hash>\n", a k-mer's row
+// "<idx>\t<k-mer>\t<hash>\n" -- the kernel that writes the rows and the host code that lays them out both ask here
+__host__ __device__ inline uint32_t kh_head_len(uint32_t L) { return L + 2 + 24 + 1; }
+__host__ __device__ inline uint32_t kh_row_len(uint32_t L, uint32_t k) { return L + 1 + k + 1 + 24 + 1; }
 struct KhTextParams {
     // per cluster
     const uint64_t* text_off;        // [C+1] byte offset of the cluster's rows in the text
@@ -4763,7 +4778,7 @@ __global__ __launch_bounds__(256) void kh_text_kernel(KhTextParams p) {
     const uint32_t c = p.block_cluster[blockIdx.x], row0 = p.block_row0[blockIdx.x];
     const uint32_t n0 = p.name_off[c], L = p.name_off[c + 1] - n0;
     const uint32_t k = p.k, cnt = p.kmer_cnt[c];
-    const uint32_t head = L + 2 + 24 + 1, rowlen = L + 1 + k + 1 + 24 + 1;
+    const uint32_t head = kh_head_len(L), rowlen = kh_row_len(L, k);
     const uint32_t nrows_total = cnt + 1;                                   // row 0 is the cluster's own row
     const uint32_t nrows = min(p.rows_per_block, nrows_total - row0);
     // byte range of these rows inside the cluster's text
@@ -4808,16 +4823,7 @@ __global__ __launch_bounds__(256) void kh_text_kernel(KhTextParams p) {
         w[24] = '\n';
     }
     __syncthreads();
-    // out: the unaligned head and tail byte by byte, the middle as 16-byte pieces
-    const uint32_t nbytes = (uint32_t)(b1 - b0);
-    char* g = p.text + gbase;
-    const uint32_t lead = min(nbytes, (16 - mis) & 15);
-    for (uint32_t i = threadIdx.x; i < lead; i += blockDim.x) g[i] = tile[mis + i];
-    const uint32_t mid = (nbytes - lead) >> 4;
-    const uint4* src = reinterpret_cast<const uint4*>(tile + mis + lead);
-    uint4* dst = reinterpret_cast<uint4*>(g + lead);
-    for (uint32_t i = threadIdx.x; i < mid; i += blockDim.x) dst[i] = src[i];
-    for (uint32_t i = lead + (mid << 4) + threadIdx.x; i < nbytes; i += blockDim.x) g[i] = tile[mis + i];
+    tile_store(tile, mis, p.text + gbase, (uint32_t)(b1 - b0));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4848,8 +4854,8 @@ struct KtParams {
     uint32_t* tile_bytes;                    // kt_len_kernel out
     const uint64_t* tile_off; char* text;    // kt_text_kernel in / out
     uint32_t k, canon;
-    // kt_text_kernel: workgroup b writes tile tile_first + b at text + tile_off[tile_first + b] - text_base (a range of
-    // the text in a buffer of its own, pf_kmers_tsv_stream_begin; 0 and 0 for the whole text in one buffer)
+    // kt_text_kernel: workgroup b writes tile tile_first + b at text + tile_off[tile_first + b] - text_base (kt_produce:
+    // a range of the text in a buffer of its own; 0 and 0 for the first range, which may be the whole text)
     uint32_t tile_first;
     uint64_t text_base;
 };
@@ -4946,15 +4952,7 @@ __global__ __launch_bounds__(KT_ROWS) void kt_text_kernel(KtParams p) {
         w[k] = '\n';
     }
     __syncthreads();
-    const uint32_t nbytes = min(total, KT_TILE);
-    char* g = p.text + gbase;
-    const uint32_t lead = min(nbytes, (16 - mis) & 15);
-    for (uint32_t i = threadIdx.x; i < lead; i += blockDim.x) g[i] = tile[mis + i];
-    const uint32_t mid = (nbytes - lead) >> 4;
-    const uint4* src = reinterpret_cast<const uint4*>(tile + mis + lead);
-    uint4* dst = reinterpret_cast<uint4*>(g + lead);
-    for (uint32_t i = threadIdx.x; i < mid; i += blockDim.x) dst[i] = src[i];
-    for (uint32_t i = lead + (mid << 4) + threadIdx.x; i < nbytes; i += blockDim.x) g[i] = tile[mis + i];
+    tile_store(tile, mis, p.text + gbase, min(total, KT_TILE));
 }
 
 struct HpTextParams {

@@ -148,3 +148,70 @@ def test_budget_below_one_tile_is_an_argument_error():
         assert eng.L.pf_kmers_tsv_stream_next(eng.ctx, C.byref(ptr), C.byref(nb)) == _lib.ERR_STATE
     finally:
         eng.close()
+
+
+@pytest.mark.parametrize("canon", [True, False], ids=["canonical", "non_canonical"])
+def test_unit_order_at_the_seams_of_the_plan(canon):
+    """a hand-made batch that fixes the order of the text's units where the plan decides it: sequences with no window
+    first, last and between a device unit and a host unit, host-rendered sequences next to each other, a tile seam
+    inside a sequence, a one-window sequence, a host-rendered sequence as the last text -- whole text, chunks taken
+    twice, one range, ranges at the smallest budget and the host renderer all give the oracle's bytes"""
+    import re
+
+    import numpy as np
+    from oracle import oracle as po
+    from panfeed_amd import _lib
+    from panfeed_amd.classes import Seqinfo
+    from panfeed_amd.engine import Engine
+    from panfeed_amd.packing import build_batch_native
+    rng = np.random.default_rng(31)
+    comp = bytes.maketrans(b"ACGTN", b"TGCAN")
+
+    def seq(n, n_at=None):
+        s = bytearray(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), n).tobytes())
+        if n_at is not None:
+            s[n_at] = ord("N")
+        return bytes(s)
+    k = 31
+    seqs = [seq(20),                 # no window: the batch's first sequence drops out
+            seq(400, 200),           # host-rendered
+            seq(1000),               # 970 windows: 4 tiles canonical, 8 not
+            seq(25),                 # no window, between a device unit and a host unit
+            seq(300, 150),           # host next to host
+            seq(200, 199),           # ... its last base an 'N'
+            seq(159),                # 129 windows: 258 rows when not canonical, a tile seam after row 256
+            seq(31),                 # exactly one window
+            seq(100, 50),            # host-rendered, the last text of the batch
+            seq(10)]                 # no window: the batch's last sequence
+    names = [f"s{i:02d}" for i in range(1, 11)]
+    gs = {nm: [Seqinfo(s.decode(), s.translate(comp).decode(), f"{nm}_g", f"{nm}_c", 100 + i, 100 + i + len(s) - 1,
+                       -1 if i % 2 else 1, i)]
+          for i, (nm, s) in enumerate(zip(names, seqs))}
+    recs = [(gs, "grp1", np.ones(10, dtype=np.int64))]
+    stroi = set(names)
+    run = po.OracleRun(klength=k, stroi=stroi, canon=canon)
+    run.feed(recs)
+    ek = run.texts()[0].encode()
+    assert 100_000 < len(ek) < 400_000
+    eng = Engine(klength=k, canon=canon, max_strains=32, stroi=stroi)
+    try:
+        hb = build_batch_native(recs, k, canon, eng.W, stroi=stroi, first_ordinal=0)
+        eng.submit_host_batch(hb)
+        text = eng.render_targets_device(hb)
+        assert bytes(text) == ek
+        assert b"".join(bytes(blk) for blk in text.chunks(1000)) == ek
+        assert b"".join(bytes(blk) for blk in text.chunks(1000)) == ek
+        got = bytearray()
+        n, ranges, peak = eng.stream_targets_device(hb, got.extend, budget=8 << 30)
+        assert bytes(got) == ek and n == len(ek) and ranges == 1
+        with pytest.raises(_lib.PanfeedHipError) as ei:
+            eng.stream_targets_device(hb, got.extend, budget=4096)
+        assert ei.value.status == _lib.ERR_ARG
+        smallest = int(re.search(r"smallest budget that works is (\d+)", str(ei.value)).group(1))
+        got = bytearray()
+        n, ranges, peak = eng.stream_targets_device(hb, got.extend, budget=smallest)
+        assert bytes(got) == ek and n == len(ek)
+        assert ranges > 1 and peak <= smallest
+        assert eng._render_targets(hb, hb.targets).encode() == ek
+    finally:
+        eng.close()
