@@ -620,7 +620,11 @@ extern "C" {
 
 const char* pf_last_error(void) { return g_err.c_str(); }
 void pf_set_error_(const char* msg) { g_err = msg; }   /* for the other translation units of the library */
+#ifdef PF_WEAK_HASH
+const char* pf_version(void) { return "panfeed_hip 0.1 (gfx950) weak-hash test build"; }
+#else
 const char* pf_version(void) { return "panfeed_hip 0.1 (gfx950)"; }
+#endif
 
 int pf_device_count(void) {
     int n = 0;
@@ -3236,6 +3240,40 @@ int pf_debug_prof(uint64_t* out, int reset) {
     if (reset) {
         static const uint64_t zero[64] = {};
         if (hipMemcpyToSymbol(HIP_SYMBOL(pf::pf_prof), zero, sizeof zero) != hipSuccess) return PF_ERR_HIP;
+    }
+    return PF_OK;
+}
+#endif
+
+#ifdef PF_WEAK_HASH
+/* weak-hash test builds only (not part of the ABI): the mask the verified content hashes are ANDed with -- all sites, or one
+   of PF_WHS_* -- and the counts of compares that failed behind an equal hash, see PF_WEAK in pf_kernels.h */
+int pf_rowfilter_weakhash_mask(uint64_t mask);
+int pf_rowfilter_weakhash_counts(uint64_t* rowfilter_rejects, uint64_t* strain_rejects, int reset);
+
+int pf_debug_set_hash_mask_site(int site, uint64_t mask) {
+    if (site < 0 || site >= pf::PF_WHS_N) return fail(PF_ERR_ARG, "pf_debug_set_hash_mask_site: no such site");
+    if (site == pf::PF_WHS_TEXT) return pf_rowfilter_weakhash_mask(mask);
+    const unsigned long long m = mask;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(pf::pf_wh_mask), &m, sizeof m, sizeof m * (size_t)site) != hipSuccess) return PF_ERR_HIP;
+    return PF_OK;
+}
+
+int pf_debug_set_hash_mask(uint64_t mask) {
+    for (int site = 0; site < pf::PF_WHS_N; site++) PFCHK(pf_debug_set_hash_mask_site(site, mask));
+    return PF_OK;
+}
+
+int pf_debug_weakhash_counts(uint64_t out[8], int reset) {
+    unsigned long long d[pf::PF_WHC_N] = {};
+    if (hipMemcpyFromSymbol(d, HIP_SYMBOL(pf::pf_wh_count), sizeof d) != hipSuccess) return PF_ERR_HIP;
+    uint64_t rf = 0, strain = 0;
+    PFCHK(pf_rowfilter_weakhash_counts(&rf, &strain, reset));
+    d[pf::PF_WHC_ROWFILTER] = rf; d[pf::PF_WHC_STRAIN] = strain;
+    if (out) for (int i = 0; i < pf::PF_WHC_N; i++) out[i] = d[i];
+    if (reset) {
+        static const unsigned long long zero[pf::PF_WHC_N] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(pf::pf_wh_count), zero, sizeof zero) != hipSuccess) return PF_ERR_HIP;
     }
     return PF_OK;
 }

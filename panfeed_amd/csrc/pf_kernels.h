@@ -37,6 +37,26 @@ __device__ unsigned long long pf_prof[64];
 #define PF_PROF_BEGIN() do { } while (0)
 #define PF_PROF_STAMP(k) do { } while (0)
 #endif
+// weak-hash test build (-DPF_WEAK_HASH, libpanfeed_hip_weakhash.so; never the shipped one): the content hashes that are
+// followed by an exact compare -- the dedup group hash, the unit-class hash, the mask-table hash of rows_kernel -- keep only
+// the bits of pf_wh_mask, so that tests reach the compares with different content under one hash; pf_wh_count counts the
+// compares that fail (pf_debug_weakhash_counts).  Without the gate both macros expand to nothing.
+// One mask per site (pf_debug_set_hash_mask sets them all; pf_debug_set_hash_mask_site one of them: the unit-class and
+// mask-table compares are only reached by clusters whose dedup pass found no collision, so their tests leave that hash whole).
+enum { PF_WHC_DEDUP_SMALL = 0, PF_WHC_DEDUP_WIDE = 1, PF_WHC_UNIT = 2, PF_WHC_ROWS = 3, PF_WHC_ROWFILTER = 4, PF_WHC_STRAIN = 5,
+       PF_WHC_ROWS_HANDOVER = 6 /* slots a round of the mask table left to the next one */,
+       PF_WHC_ROWS_GIVEUP = 7 /* of those: after AT_SLOTS probes or 4096 looks at a busy entry */, PF_WHC_N = 8 };
+enum { PF_WHS_DEDUP = 0, PF_WHS_UNIT = 1, PF_WHS_ROWS = 2, PF_WHS_TEXT = 3, PF_WHS_N = 4 };
+#ifdef PF_WEAK_HASH
+// (the kernels' three sites; PF_WHS_TEXT is pf_rowfilter.hip's own pair of masks, host and device)
+static __device__ unsigned long long pf_wh_mask[PF_WHS_TEXT] = {~0ull, ~0ull, ~0ull};
+static __device__ unsigned long long pf_wh_count[PF_WHC_N];
+#define PF_WEAK(site, h) ((h) & pf_wh_mask[site])
+#define PF_WEAK_COUNT(i) atomicAdd(&pf_wh_count[i], 1ull)
+#else
+#define PF_WEAK(site, h) (h)
+#define PF_WEAK_COUNT(i) do { } while (0)
+#endif
 // timing experiments (never shipped): -DPF_KO_FINISH=n, n = 0 .. 4, makes finish_kernel return behind its phase n (0 set-up +
 // sample sets, 1 mask table, 2 row evaluation, 3 ordinal bitmaps, 4 prefix counts) -- nothing has been claimed or written by
 // then, the later passes find empty clusters; n = 7 keeps every phase but gives every pattern the id 0 without touching the
@@ -1385,6 +1405,10 @@ void cluster_dedup_kernel(DedupParams p) {
     __shared__ uint32_t r_ord0[MAXD], r_ninst[MAXD], r_dense[MAXD];   // by distinct index
     __shared__ uint32_t sh_bad, sh_many, sh_nrep, sh_total, sh_ngroups, sh_pool_used;
     __shared__ uint32_t s_ex[DEDUP_EX_LDS];    // the cluster's slow-path ordinals (read E times per row further down)
+#ifdef PF_WEAK_HASH
+    __shared__ uint32_t sh_diff;               // a compare failed in this cluster (counted once per cluster)
+    if (threadIdx.x == 0) sh_diff = 0;
+#endif
 
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t c = p.cluster_list ? p.cluster_list[blockIdx.x] : blockIdx.x + p.cluster_base;
@@ -1498,7 +1522,7 @@ void cluster_dedup_kernel(DedupParams p) {
             for (int u = 0; u < (int)DEDUP_U; u++) {
                 uint64_t a = 0;                                  // the group's sum (GL is not a power of two in general)
                 for (uint32_t i = 0; i < GL; i++) a += __shfl(acc[u], (int)(gbase + i));
-                uint64_t h = mix64(a ^ ((uint64_t)len[u] << 40));
+                uint64_t h = PF_WEAK(PF_WHS_DEDUP, mix64(a ^ ((uint64_t)len[u] << 40)));
                 if (h == EMPTY64) h = EMPTY64 - 1;
                 uint32_t sl = 0, reg = 0;
                 if (gl == 0 && has[u]) {
@@ -1597,10 +1621,16 @@ void cluster_dedup_kernel(DedupParams p) {
                         }
                     }
                     if (diff) sh_bad = 1;     // a 64-bit hash collision: give up on this cluster (mode 0), stay exact
+#ifdef PF_WEAK_HASH
+                    if (diff) sh_diff = 1;
+#endif
                 }
             }
         }
         __syncthreads();
+#ifdef PF_WEAK_HASH
+        if (tid == 0 && sh_diff) PF_WEAK_COUNT(CFG::MODE == 1 ? PF_WHC_DEDUP_SMALL : PF_WHC_DEDUP_WIDE);
+#endif
         // ---- 4. hash groups -> distinct indices in the ordinal order of their representatives
         for (uint32_t t = tid; t < GTAB; t += DEDUP_THREADS)
             if (t_key[t] != EMPTY64) {
@@ -1796,12 +1826,16 @@ __global__ __launch_bounds__(UNIT_THREADS) void unit_class_kernel(UnitParams p) 
                 if (len < k || 64 * u + k > len) continue;            // the sequence has no window in this unit
                 const uint32_t nb = min(len - 64 * u, span), nw = (nb + 31) >> 5;
                 const uint64_t* w = p.packed + (((uint64_t)d_whi[d] << 32) | d_wlo[d]) + 2 * (size_t)u;
-                uint64_t h = 0x9E3779B97F4A7C15ull * (nb + 1) + u;
+                // (the seed is mixed before the first word is folded in: as a plain sum its low bits are u, the first word's
+                // low bits are base 31 of the unit, and a tandem repeat with a substitution there met its neighbour
+                // unit under one hash -- exact all the same, through the position compare below, but back on the plain view)
+                uint64_t h = mix64(0x9E3779B97F4A7C15ull * (nb + 1) + u);
                 for (uint32_t j = 0; j < nw; j++) {
                     uint64_t x = w[j];
                     if (j + 1 == nw && (nb & 31)) x &= ~0ull << (64 - 2 * (nb & 31));      // bases past the unit's span
                     h = mix64(h ^ x) + 0xC2B2AE3D27D4EB4Full * (j + 1);
                 }
+                h = PF_WEAK(PF_WHS_UNIT, h);
                 if (h == EMPTY64) h = EMPTY64 - 1;
                 uint32_t sl = (uint32_t)(h >> 20) & (UNIT_TAB - 1);
                 for (;;) {
@@ -1867,6 +1901,9 @@ __global__ __launch_bounds__(UNIT_THREADS) void unit_class_kernel(UnitParams p) 
             }
             __syncthreads();
         }
+#ifdef PF_WEAK_HASH
+        if (tid == 0 && sh_bad) PF_WEAK_COUNT(PF_WHC_UNIT);
+#endif
         if (sh_bad) return;                                          // (uniform) the cluster keeps its plain view
         if (tid == 0) {
             uint32_t run = 0;
@@ -2406,7 +2443,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
                         a1 += (uint64_t)w[j] * (kj | 1u);
                         a2 += (uint64_t)w[j] * (((kj >> 9) | (kj << 23)) | 1u);
                     }
-                    const uint64_t hsh = mix64(a1 ^ ((a2 << 32) | (a2 >> 32)));
+                    const uint64_t hsh = PF_WEAK(PF_WHS_ROWS, mix64(a1 ^ ((a2 << 32) | (a2 >> 32))));
                     uint64_t h50 = hsh >> 14;
                     if (!h50) h50 = 1;
                     uint32_t a = (uint32_t)(hsh & (AT_SLOTS - 1));
@@ -2447,14 +2484,18 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
                                     for (uint32_t j = 0; j < NWA; j++)
                                         if (j < nmw) diff |= tabw[st * nmw + j] ^ w[j];
                                     if (!diff) { tag = st; done = true; }
+                                    else { PF_WEAK_COUNT(PF_WHC_ROWS); }
                                 }
                             }
                             a = (a + adv) & (AT_SLOTS - 1);
                             probes += adv;
-                            if (probes >= AT_SLOTS || spins >= 4096u) done = true;   // (gives up for this round; never met)
+                            // (gives up for this round.  Not met even with every mask under one hash: a round's table holds at
+                            // most cap <= AT_LIMIT < AT_SLOTS entries, so a walk ends at a free slot or at the full table first,
+                            // and an entry is busy for the few stores of its writer only; counted in the weak-hash build)
+                            if (probes >= AT_SLOTS || spins >= 4096u) { done = true; PF_WEAK_COUNT(PF_WHC_ROWS_GIVEUP); }
                         }
                     }
-                    if (tag == WIDE_PENDING) sh_more = 1;
+                    if (tag == WIDE_PENDING) { sh_more = 1; PF_WEAK_COUNT(PF_WHC_ROWS_HANDOVER); }
                     else slot_tag[i] = (uint16_t)tag;
                 };
                 for (uint32_t i0 = tid; i0 < ns; i0 += U * ROWS_THREADS) {

@@ -32,8 +32,24 @@ constexpr uint64_t RF_EMPTY = 0;
 constexpr uint32_t RF_MAX_FIELD = 4096;       // a key field longer than this never matches (nor do the keys)
 
 __host__ __device__ inline uint64_t rf_hash_step(uint64_t h, unsigned char c) { return (h ^ c) * 0x100000001B3ull; }
+// weak-hash test build (-DPF_WEAK_HASH, see pf_kernels.h): the key / name hash keeps only the bits of a mask that the host
+// and the device copy of rf_hash_fin read alike; rejected candidates are counted
+#ifdef PF_WEAK_HASH
+static __device__ unsigned long long rf_wh_mask = ~0ull;
+static __device__ unsigned long long rf_wh_strain_rejects;
+static uint64_t rf_wh_mask_host = ~0ull;
+static uint64_t rf_wh_rowfilter_rejects;
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RF_WEAK(h) ((h) & rf_wh_mask)
+#else
+#define RF_WEAK(h) ((h) & rf_wh_mask_host)
+#endif
+#else
+#define RF_WEAK(h) (h)
+#endif
 __host__ __device__ inline uint64_t rf_hash_fin(uint64_t h) {
     h ^= h >> 32; h *= 0xD6E8FEB86659FD93ull; h ^= h >> 32;
+    h = RF_WEAK(h);
     return h ? h : 1;                                   // 0 marks an empty slot
 }
 inline uint64_t rf_hash(const char* s, size_t n) {
@@ -261,6 +277,9 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
             while (t > b && text[t - 1] != '\t') t--;
             key.assign(text + t, (size_t)(e - t));
         }
+#ifdef PF_WEAK_HASH
+        if (!f->keys.count(key)) rf_wh_rowfilter_rejects++;
+#endif
         if (!f->keys.count(key)) continue;
         f->begin.push_back(b);
         f->end.push_back(e + 1 <= n ? e + 1 : n);          // the '\n' is part of the line
@@ -402,6 +421,9 @@ __device__ __forceinline__ int64_t pg_strain(const PgScanParams& p, const unsign
                 while (i < n && b[i] == s[i]) i++;
                 if (i == n) return id;
             }
+#ifdef PF_WEAK_HASH
+            atomicAdd(&rf_wh_strain_rejects, 1ull);
+#endif
         }
         slot = (slot + 1) & (p.strain_cap - 1);
     }
@@ -972,3 +994,24 @@ int pf_plotgrid_stats(pf_plotgrid* g, uint64_t* bytes_scanned, uint64_t* lines, 
 }
 
 }  // extern "C"
+
+#ifdef PF_WEAK_HASH
+extern "C" {
+// weak-hash test build only (not part of the ABI): this file's share of pf_debug_set_hash_mask / pf_debug_weakhash_counts
+int pf_rowfilter_weakhash_mask(uint64_t mask) {
+    rf_wh_mask_host = mask;
+    const unsigned long long m = mask;
+    return hipMemcpyToSymbol(HIP_SYMBOL(rf_wh_mask), &m, sizeof m) == hipSuccess ? PF_OK : PF_ERR_HIP;
+}
+int pf_rowfilter_weakhash_counts(uint64_t* rowfilter_rejects, uint64_t* strain_rejects, int reset) {
+    unsigned long long d = 0;
+    if (hipMemcpyFromSymbol(&d, HIP_SYMBOL(rf_wh_strain_rejects), sizeof d) != hipSuccess) return PF_ERR_HIP;
+    *rowfilter_rejects = rf_wh_rowfilter_rejects; *strain_rejects = d;
+    if (reset) {
+        rf_wh_rowfilter_rejects = 0; d = 0;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(rf_wh_strain_rejects), &d, sizeof d) != hipSuccess) return PF_ERR_HIP;
+    }
+    return PF_OK;
+}
+}  // extern "C"
+#endif
