@@ -105,6 +105,14 @@ __device__ __forceinline__ void rf_line(const RfParams& p, int64_t at) {
     if (k < p.out_cap) p.out[k] = pos;
 }
 
+// the bytes of a 32-bit word that are '\n', as bit 7 of each such byte.  The sum never carries from one byte into the
+// next (both operands have bit 7 clear), so a byte is flagged by its own value alone: the shorter (x - 0x01010101) & ~x
+// form lets the borrow of a matching byte flag a 0x0B that stands above it in the word
+__device__ __forceinline__ uint32_t rf_newlines(uint32_t w) {
+    const uint32_t x = w ^ 0x0A0A0A0Au;
+    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
+}
+
 __global__ __launch_bounds__(256) void rowfilter_kernel(RfParams p) {
     const uint64_t nvec = (p.n + 15) / 16;
     for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < nvec; v += (uint64_t)gridDim.x * blockDim.x) {
@@ -114,9 +122,7 @@ __global__ __launch_bounds__(256) void rowfilter_kernel(RfParams p) {
         if (v == 0 && p.first_field) rf_line(p, -1);     // the line that starts the block
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            // bytes equal to '\n' in this word
-            const uint32_t x = ws[q] ^ 0x0A0A0A0Au;
-            uint32_t m = (x - 0x01010101u) & ~x & 0x80808080u;
+            uint32_t m = rf_newlines(ws[q]);
             while (m) {
                 const int b = (__ffs((int)m) - 1) >> 3;
                 m &= m - 1;
@@ -487,8 +493,7 @@ __global__ __launch_bounds__(256) void pg_scan_kernel(PgScanParams p) {
         if (v == 0) pg_line(p, 0);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            const uint32_t x = ws[q] ^ 0x0A0A0A0Au;
-            uint32_t m = (x - 0x01010101u) & ~x & 0x80808080u;
+            uint32_t m = rf_newlines(ws[q]);
             while (m) {
                 const int b = (__ffs((int)m) - 1) >> 3;
                 m &= m - 1;
