@@ -810,8 +810,6 @@ DPtrs dplan_ptrs(const pf_ctx::DPlan& plan) {
     const size_t n = plan.n;
     return DPtrs{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, b + 6 * n, b + 7 * n, b + 8 * n};
 }
-// a pass's item arrays as the scan and the fused finish kernels read them
-struct ItemPtrs { const uint32_t *cluster, *part, *nparts, *nslots, *slice, *compact, *binned; uint32_t* count; };
 struct FinWork { const uint32_t* work; uint32_t n; };   // one class of the fused finish kernels in a launch
 // a host-planned pass: its sub-batches (one launch each) and their stretches of the work lists (off[s] to off[s + 1])
 struct Sub { uint32_t item0, nitems, cl0, ncl, pool, bin0, nbin; uint64_t q_total; };
@@ -1036,13 +1034,11 @@ struct SubmitRun {
             dp.seg_sample = d.seg_sample; dp.seg_ord_base = d.seg_ord_base;
             dp.cluster_seg_off = d.cluster_seg_off; dp.cluster_nstrains = d.cluster_nstrains;
             dp.extra_off = c->extra_off.as<uint32_t>(); dp.extra_ord = d.extra_ord;
-            dp.v_word_off = c->v_word_off.as<uint64_t>(); dp.v_len = c->v_len.as<uint32_t>();
-            dp.v_sample = c->v_sample.as<uint32_t>(); dp.v_ord = c->v_ord.as<uint32_t>();
+            dp.view = view(nullptr);
             dp.seg_distinct = c->seg_distinct.as<uint32_t>();
-            dp.v_bits = c->v_bits.as<uint32_t>(); dp.view_off = c->view_off.as<uint32_t>();
             dp.cl_overflow = c->cl_overflow.as<uint32_t>(); dp.cl_kmer_cnt = c->cl_kmer_cnt.as<uint32_t>();
             dp.cl_unique = c->cl_unique.as<uint32_t>(); dp.cl_pattern = c->cl_pattern.as<uint32_t>();
-            dp.v_nseg = c->v_nseg.as<uint32_t>(); dp.v_nstr = c->v_nstr.as<uint32_t>();
+            dp.v_nstr = c->v_nstr.as<uint32_t>();
             dp.v_mode = c->v_mode.as<uint32_t>(); dp.v_dense = c->v_dense.as<uint32_t>();
             dp.extra_dense = c->extra_dense.as<uint32_t>();
             dp.k = c->o.klength; dp.W = W; dp.canon = c->o.canon;
@@ -1137,10 +1133,7 @@ struct SubmitRun {
             q.list_cluster = up.list.as<uint32_t>(); q.list_base = up.list.as<uint32_t>() + nu;
         }
         q.packed = d.packed; q.cluster_seg_off = d.cluster_seg_off; q.v_nstr = c->v_nstr.as<uint32_t>();
-        q.v_word_off = c->v_word_off.as<uint64_t>(); q.v_len = c->v_len.as<uint32_t>(); q.v_ord = c->v_ord.as<uint32_t>();
-        q.u_word_off = up.word_off.as<uint64_t>(); q.u_len = up.len.as<uint32_t>(); q.u_sample = up.sample.as<uint32_t>();
-        q.u_ord = up.ord.as<uint32_t>(); q.u_bits = up.bits.as<uint32_t>();
-        q.v_nseg = c->v_nseg.as<uint32_t>(); q.view_off = c->view_off.as<uint32_t>(); q.k = c->o.klength; q.tmp_off = (uint32_t)R;
+        q.view = view(&up); q.k = c->o.klength; q.tmp_off = (uint32_t)R;
         PFCHK(mark_begin(c, TimeCat::dedup));
         if (nsmall) {
             const dim3 g((nsmall + 3) / 4), b(256);
@@ -1162,57 +1155,96 @@ struct SubmitRun {
         PFCHK(mark_end(c));
         return PF_OK;
     }
-    // ---- parameter blocks of the scan and the fused finish kernels, from a pass's item arrays (the host's staged
-    // upload, or plan_kernel's block with the constant arrays standing in for what is the same for every simple cluster)
-    ItemPtrs host_items() const {
-        return ItemPtrs{c->it_cluster.as<uint32_t>(), c->it_part.as<uint32_t>(), c->it_nparts.as<uint32_t>(), c->it_nslots.as<uint32_t>(),
-                        c->it_slice.as<uint32_t>(), c->it_compact.as<uint32_t>(), c->it_binned.as<uint32_t>(), c->it_count.as<uint32_t>()};
+    // ---- the kernels' argument groups (pf_kernels.h), one builder each.  A group is built at the launch that uses it and
+    // never kept across a DevBuf::ensure, which may move a buffer (q_key, the arenas, the unit pools).
+    pf::CallerSegs caller_segs() const {
+        return pf::CallerSegs{d.cluster_seg_off, d.seg_sample, c->seg_distinct.as<uint32_t>(), d.cluster_nstrains,
+                              d.cluster_npresab, d.cluster_presab, d.cluster_ordinal};
     }
-    pf::ScanParams scan_params(const ItemPtrs& ip, const pf_ctx::UPool& up, const uint32_t* work) const {
+    pf::View view(const pf_ctx::UPool* up) const {     // (the dedup pass has no pool yet)
+        pf::View v{};
+        v.plain = pf::ViewSegs{c->v_word_off.as<uint64_t>(), c->v_len.as<uint32_t>(), c->v_sample.as<uint32_t>(),
+                               c->v_ord.as<uint32_t>(), c->v_bits.as<uint32_t>()};
+        if (up) v.pool = pf::ViewSegs{up->word_off.as<uint64_t>(), up->len.as<uint32_t>(), up->sample.as<uint32_t>(),
+                                      up->ord.as<uint32_t>(), up->bits.as<uint32_t>()};
+        v.view_off = c->view_off.as<uint32_t>(); v.v_nseg = c->v_nseg.as<uint32_t>();
+        return v;
+    }
+    pf::ViewFacts view_facts() const {
+        return pf::ViewFacts{c->v_nstr.as<uint32_t>(), c->v_mode.as<uint32_t>(), c->v_dense.as<uint32_t>(), c->cl_overflow.as<uint32_t>(),
+                             c->extra_off.as<uint32_t>(), c->extra_dense.as<uint32_t>(), d.extra_bits};
+    }
+    // a host-planned pass's items (the staged upload) ...
+    pf::Items host_items() const {
+        return pf::Items{c->it_cluster.as<uint32_t>(), c->it_part.as<uint32_t>(), c->it_nparts.as<uint32_t>(), c->it_nslots.as<uint32_t>(),
+                         c->it_slice.as<uint32_t>(), c->it_compact.as<uint32_t>(), c->it_binned.as<uint32_t>(), c->it_is_extra.as<uint32_t>(),
+                         c->it_extra_first.as<uint32_t>(), c->it_sib0.as<uint32_t>(), c->it_nsib.as<uint32_t>()};
+    }
+    // ... and plan_kernel's, all "one partition, own slice, compact, nothing else": three constant arrays stand in
+    static pf::Items planned_items(const uint32_t* cluster, const uint32_t* nslots, const uint32_t* zeros, const uint32_t* ones, const uint32_t* iota) {
+        return pf::Items{cluster, zeros, ones, nslots, iota, ones, zeros, zeros, zeros, iota, ones};
+    }
+    pf::SlotDump slot_dump(uint32_t* item_count) const {       // (the key counts go beside the pass's items)
+        return pf::SlotDump{c->cmask_lo.as<uint32_t>(), c->cmask_hi.as<uint32_t>(), c->tab_key.as<uint64_t>(), c->tab_ord.as<uint32_t>(),
+                            c->chunkbits.as<uint32_t>(), c->chunkmask.as<uint32_t>(), item_count};
+    }
+    pf::RowScratch row_scratch() const {
+        return pf::RowScratch{c->slot_hash.as<uint4>(), c->sorted_pair.as<uint64_t>(), c->kept_prefix.as<uint32_t>(), c->bm4.as<uint4>(),
+                              c->bm2.as<uint2>(), c->mrows.as<uint32_t>(), c->slot_out.as<uint32_t>(), c->it_unique.as<uint32_t>(),
+                              c->it_kept.as<uint32_t>()};
+    }
+    pf::Outputs outputs() const {                              // (of the arena of the pass being launched)
+        return pf::Outputs{ar->key.as<uint64_t>(), ar->pid.as<uint32_t>(), ar->first.as<uint64_t>(), ar->base, ar->cap,
+                           c->cl_kmer_off.as<uint64_t>(), c->cl_kmer_cnt.as<uint32_t>(), c->cl_unique.as<uint32_t>(),
+                           c->cl_pattern.as<uint32_t>(), c->cl_first.as<uint64_t>(), c->cursor.as<uint64_t>()};
+    }
+    pf::PatternPool pattern_pool() const {
+        return pf::PatternPool{c->pat_bits.as<uint32_t>(), c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr,
+                               c->pat_n.as<uint32_t>()};
+    }
+    pf::RowOpts row_opts() const {
+        return pf::RowOpts{c->d_maf_lo.as<uint32_t>(), c->d_maf_hi.as<uint32_t>(), W, NS, KW,
+                           (uint32_t)c->o.consider_missing, (uint32_t)c->o.patfilt, (uint32_t)c->o.multiple_files};
+    }
+    // ---- parameter blocks of the scan and the fused finish kernels, from a pass's items and their key counts
+    pf::ScanParams scan_params(const pf::Items& items, uint32_t* item_count, const pf_ctx::UPool& up, const uint32_t* work) const {
         pf::ScanParams sp{};
-        sp.packed = d.packed; sp.seg_word_off = c->v_word_off.as<uint64_t>(); sp.seg_len = c->v_len.as<uint32_t>();
-        sp.seg_sample = c->v_sample.as<uint32_t>(); sp.seg_ord_base = c->v_ord.as<uint32_t>();
-        sp.seg_bits = c->v_bits.as<uint32_t>();
-        sp.u_word_off = up.word_off.as<uint64_t>(); sp.u_len = up.len.as<uint32_t>(); sp.u_sample = up.sample.as<uint32_t>();
-        sp.u_ord_base = up.ord.as<uint32_t>(); sp.u_bits = up.bits.as<uint32_t>();
-        sp.cluster_seg_off = c->view_off.as<uint32_t>(); sp.cluster_vnseg = c->v_nseg.as<uint32_t>();
-        sp.cluster_vnstr = c->v_nstr.as<uint32_t>();
-        sp.item_cluster = ip.cluster; sp.item_part = ip.part; sp.item_nparts = ip.nparts; sp.item_nslots = ip.nslots;
-        sp.item_scratch = ip.slice; sp.item_compact = ip.compact;
-        sp.cmask_lo = c->cmask_lo.as<uint32_t>(); sp.cmask_hi = c->cmask_hi.as<uint32_t>();
-        sp.tab_key = c->tab_key.as<uint64_t>(); sp.tab_ord = c->tab_ord.as<uint32_t>();
-        sp.chunkbits = c->chunkbits.as<uint32_t>(); sp.chunkmask = c->chunkmask.as<uint32_t>();
-        sp.item_count = ip.count; sp.cluster_overflow = c->cl_overflow.as<uint32_t>();
+        const pf::ViewFacts vf = view_facts();
+        sp.packed = d.packed; sp.view = view(&up); sp.v_nstr = vf.v_nstr; sp.cluster_overflow = vf.cluster_overflow;
+        sp.item_cluster = items.item_cluster; sp.item_part = items.item_part; sp.item_nparts = items.item_nparts;
+        sp.item_nslots = items.item_nslots; sp.item_scratch = items.item_scratch; sp.item_compact = items.item_compact;
+        sp.item_binned = items.item_binned;
+        sp.dump = slot_dump(item_count);
         sp.work = work;
         sp.k = c->o.klength; sp.W = W; sp.NS = NS;
-        sp.item_binned = ip.binned;
         return sp;
     }
-    pf::FinishParams finish_params(const ItemPtrs& ip) const {
+    pf::FinishParams finish_params(const pf::Items& items, uint32_t* item_count) const {
         pf::FinishParams fp{};
-        fp.item_cluster = ip.cluster; fp.item_nslots = ip.nslots;
-        fp.item_scratch = ip.slice; fp.cluster_overflow = c->cl_overflow.as<uint32_t>();
-        fp.item_nparts = ip.nparts;
-        fp.cluster_seg_off = d.cluster_seg_off; fp.seg_sample = d.seg_sample;
-        fp.seg_distinct = c->seg_distinct.as<uint32_t>();
-        fp.v_nstr = c->v_nstr.as<uint32_t>(); fp.v_dense = c->v_dense.as<uint32_t>();
-        fp.cluster_nstrains = d.cluster_nstrains; fp.cluster_npresab = d.cluster_npresab;
-        fp.cluster_presab = d.cluster_presab; fp.cluster_ordinal = d.cluster_ordinal;
-        fp.maf_lo = c->d_maf_lo.as<uint32_t>(); fp.maf_hi = c->d_maf_hi.as<uint32_t>();
-        fp.tab_key = c->tab_key.as<uint64_t>(); fp.tab_ord = c->tab_ord.as<uint32_t>();
-        fp.cmask_lo = c->cmask_lo.as<uint32_t>(); fp.cmask_hi = c->cmask_hi.as<uint32_t>();
-        fp.item_count = ip.count;
-        fp.extra_off = c->extra_off.as<uint32_t>(); fp.extra_dense = c->extra_dense.as<uint32_t>();
-        fp.extra_bits = d.extra_bits;
-        fp.out_key = ar->key.as<uint64_t>(); fp.out_pid = ar->pid.as<uint32_t>();
-        fp.cluster_kmer_off = c->cl_kmer_off.as<uint64_t>(); fp.cluster_kmer_cnt = c->cl_kmer_cnt.as<uint32_t>();
-        fp.cluster_unique = c->cl_unique.as<uint32_t>(); fp.cluster_pattern = c->cl_pattern.as<uint32_t>();
-        fp.cursor = c->cursor.as<uint64_t>(); fp.pt = c->pt;
-        fp.pat_bits = c->pat_bits.as<uint32_t>();
-        fp.pat_nan = c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr;
-        fp.pat_n = c->pat_n.as<uint32_t>();
-        fp.out_base = ar->base; fp.out_cap = ar->cap; fp.W = W; fp.NS = NS; fp.KW = KW;
-        fp.consider_missing = c->o.consider_missing; fp.patfilt = c->o.patfilt; fp.multiple_files = c->o.multiple_files;
+        // (flat, in the order it always had: finish_kernel's register allocation follows the block's layout)
+        const pf::CallerSegs cl = caller_segs();
+        const pf::ViewFacts vf = view_facts();
+        const pf::SlotDump dump = slot_dump(item_count);
+        const pf::Outputs out = outputs();
+        const pf::PatternPool pats = pattern_pool();
+        const pf::RowOpts opt = row_opts();
+        fp.item_cluster = items.item_cluster; fp.item_nslots = items.item_nslots; fp.item_scratch = items.item_scratch;
+        fp.item_nparts = items.item_nparts; fp.cluster_overflow = vf.cluster_overflow;
+        fp.cluster_seg_off = cl.cluster_seg_off; fp.seg_sample = cl.seg_sample; fp.seg_distinct = cl.seg_distinct;
+        fp.v_nstr = vf.v_nstr; fp.v_dense = vf.v_dense;
+        fp.cluster_nstrains = cl.cluster_nstrains; fp.cluster_npresab = cl.cluster_npresab;
+        fp.cluster_presab = cl.cluster_presab; fp.cluster_ordinal = cl.cluster_ordinal;
+        fp.maf_lo = opt.maf_lo; fp.maf_hi = opt.maf_hi;
+        fp.item_count = dump.item_count; fp.tab_key = dump.tab_key; fp.tab_ord = dump.tab_ord;
+        fp.cmask_lo = dump.cmask_lo; fp.cmask_hi = dump.cmask_hi;
+        fp.extra_off = vf.extra_off; fp.extra_dense = vf.extra_dense; fp.extra_bits = vf.extra_bits;
+        fp.out_key = out.out_key; fp.out_pid = out.out_pid;
+        fp.cluster_kmer_off = out.cluster_kmer_off; fp.cluster_kmer_cnt = out.cluster_kmer_cnt;
+        fp.cluster_unique = out.cluster_unique; fp.cluster_pattern = out.cluster_pattern;
+        fp.cursor = out.cursor; fp.pt = c->pt;
+        fp.pat_bits = pats.pat_bits; fp.pat_nan = pats.pat_nan; fp.pat_n = pats.pat_n;
+        fp.out_base = out.out_base; fp.out_cap = out.out_cap; fp.W = opt.W; fp.NS = opt.NS; fp.KW = opt.KW;
+        fp.consider_missing = opt.consider_missing; fp.patfilt = opt.patfilt; fp.multiple_files = opt.multiple_files;
         return fp;
     }
     // the fused finish kernels of a launch on stream `s`, the heaviest clusters first
@@ -1278,16 +1310,17 @@ struct SubmitRun {
         const uint32_t* zeros = c->dp_const.as<uint32_t>();
         const uint32_t* ones = zeros + c->dp_const_n;
         const uint32_t* iota = zeros + 2 * (size_t)c->dp_const_n;
-        const ItemPtrs ip{q.it_cluster, zeros, ones, q.it_nslots, iota, ones, zeros, plan.it_count.as<uint32_t>()};
+        const pf::Items ip = planned_items(q.it_cluster, q.it_nslots, zeros, ones, iota);
+        uint32_t* const count = plan.it_count.as<uint32_t>();
         PFCHK(begin_arena(po.arena_cap));
         PFCHK(upload_cursor_start());
         pf_ctx::UPool& up = c->upool[2 * h];
         if (po.n_unit) PFCHK(launch_unit_classes(up, po.n_unit, 0, po.unit_room, &q));
         PFCHK(mark_begin(c, TimeCat::scan));
-        PFCHK(launch_scan(c, scan_params(ip, up, q.w_scan), n));
+        PFCHK(launch_scan(c, scan_params(ip, count, up, q.w_scan), n));
         PFCHK(mark_end(c));
         c->timing.scan_launches++;
-        PFCHK(launch_fused_finish(finish_params(ip), c->stream, {q.w_fin5, po.n_fin5}, {nullptr, 0}, {q.w_fin2, po.n_fin2},
+        PFCHK(launch_fused_finish(finish_params(ip, count), c->stream, {q.w_fin5, po.n_fin5}, {nullptr, 0}, {q.w_fin2, po.n_fin2},
                                   {q.w_fin, po.n_fin}));
         c->timing.n_items += n;
         c->timing.n_device_planned += n;
@@ -1550,21 +1583,15 @@ struct SubmitRun {
         const uint32_t n_scan = o1.scan - o0.scan, n_extra_items = o1.extra - o0.extra;
         if (n_extra_items) {
             pf::ExtraParams ep{};
-            ep.extra_ord = c->extra_dense.as<uint32_t>(); ep.extra_bits = d.extra_bits;
-            ep.item_first = c->it_extra_first.as<uint32_t>(); ep.item_nslots = c->it_nslots.as<uint32_t>();
-            ep.item_scratch = c->it_slice.as<uint32_t>();
-            ep.tab_key = c->tab_key.as<uint64_t>(); ep.tab_ord = c->tab_ord.as<uint32_t>();
-            ep.chunkbits = c->chunkbits.as<uint32_t>(); ep.chunkmask = c->chunkmask.as<uint32_t>();
-            ep.item_count = c->it_count.as<uint32_t>();
+            ep.vf = view_facts(); ep.items = host_items(); ep.dump = slot_dump(c->it_count.as<uint32_t>()); ep.opt = row_opts();
             ep.work = c->work_extra.as<uint32_t>() + o0.extra;
-            ep.W = W; ep.NS = NS; ep.KW = KW;
             PFCHK(mark_begin(c, TimeCat::emit));
             hipLaunchKernelGGL(pf::extra_fill_kernel, dim3(n_extra_items), dim3(256), 0, c->stream, ep);
             HIPCHK(hipGetLastError());
             PFCHK(mark_end(c));
         }
         if (n_scan) {
-            pf::ScanParams sp = scan_params(host_items(), c->upool[sb.pool], c->work_scan.as<uint32_t>() + o0.scan);
+            pf::ScanParams sp = scan_params(host_items(), c->it_count.as<uint32_t>(), c->upool[sb.pool], c->work_scan.as<uint32_t>() + o0.scan);
             PFCHK(mark_begin(c, TimeCat::scan));
             if (sb.nbin) {
                 const size_t qcap = (size_t)sb.q_total + 64, NB = ps.NB;
@@ -1597,32 +1624,23 @@ struct SubmitRun {
                 fs = c->side;
                 c->timing.n_side_launches++;
             }
-            PFCHK(launch_fused_finish(finish_params(host_items()), fs, {c->work_fin5.as<uint32_t>() + o0.fin5, n_fin5},
+            PFCHK(launch_fused_finish(finish_params(host_items(), c->it_count.as<uint32_t>()), fs, {c->work_fin5.as<uint32_t>() + o0.fin5, n_fin5},
                                       {c->work_fin3.as<uint32_t>() + o0.fin3, n_fin3}, {c->work_fin2.as<uint32_t>() + o0.fin2, n_fin2},
                                       {c->work_fin.as<uint32_t>() + o0.fin, n_fin}));
             if (beside) HIPCHK(hipEventRecord(c->ev_join, c->side));
         }
         if (!n_rows) return PF_OK;
+        // the general path's four kernels read the same groups (nothing between here and the last launch resizes a buffer)
+        const pf::CallerSegs cl = caller_segs();
+        const pf::ViewFacts vf = view_facts();
+        const pf::Items items = host_items();
+        const pf::SlotDump dump = slot_dump(c->it_count.as<uint32_t>());
+        const pf::RowScratch rs = row_scratch();
+        const pf::Outputs out = outputs();
+        const pf::RowOpts opt = row_opts();
+        const uint32_t* const work = c->work_rows.as<uint32_t>() + o0.rows;
         pf::RowsParams rp{};
-        rp.item_cluster = c->it_cluster.as<uint32_t>(); rp.item_nslots = c->it_nslots.as<uint32_t>();
-        rp.item_scratch = c->it_slice.as<uint32_t>(); rp.item_count = c->it_count.as<uint32_t>();
-        rp.item_is_extra = c->it_is_extra.as<uint32_t>();
-        rp.cluster_overflow = c->cl_overflow.as<uint32_t>();
-        rp.cluster_seg_off = d.cluster_seg_off; rp.seg_sample = d.seg_sample;
-        rp.seg_distinct = c->seg_distinct.as<uint32_t>();
-        rp.v_mode = c->v_mode.as<uint32_t>(); rp.v_nstr = c->v_nstr.as<uint32_t>(); rp.v_dense = c->v_dense.as<uint32_t>();
-        rp.cluster_nstrains = d.cluster_nstrains; rp.cluster_npresab = d.cluster_npresab;
-        rp.cluster_presab = d.cluster_presab; rp.cluster_ordinal = d.cluster_ordinal;
-        rp.maf_lo = c->d_maf_lo.as<uint32_t>(); rp.maf_hi = c->d_maf_hi.as<uint32_t>();
-        rp.tab_ord = c->tab_ord.as<uint32_t>(); rp.chunkbits = c->chunkbits.as<uint32_t>();
-        rp.chunkmask = c->chunkmask.as<uint32_t>();
-        rp.slot_hash = c->slot_hash.as<uint4>(); rp.sorted_pair = c->sorted_pair.as<uint64_t>();
-        rp.kept_prefix = c->kept_prefix.as<uint32_t>();
-        rp.bm4 = c->bm4.as<uint4>(); rp.bm2 = c->bm2.as<uint2>(); rp.item_nsib = c->it_nsib.as<uint32_t>();
-        rp.mrows = c->mrows.as<uint32_t>();
-        rp.item_unique = c->it_unique.as<uint32_t>(); rp.item_kept = c->it_kept.as<uint32_t>();
-        rp.work = c->work_rows.as<uint32_t>() + o0.rows; rp.W = W; rp.NS = NS;
-        rp.consider_missing = c->o.consider_missing; rp.patfilt = c->o.patfilt; rp.multiple_files = c->o.multiple_files;
+        rp.cl = cl; rp.vf = vf; rp.items = items; rp.dump = dump; rp.rs = rs; rp.opt = opt; rp.work = work;
         PFCHK(mark_begin(c, TimeCat::rows));
         hipLaunchKernelGGL(pf::rows_kernel, dim3(n_rows), dim3(pf::ROWS_THREADS), 0, c->stream, rp);
         HIPCHK(hipGetLastError());
@@ -1632,10 +1650,7 @@ struct SubmitRun {
         bp.sub_cluster = c->sub_cluster.as<uint32_t>() + sb.cl0;
         bp.cluster_item0 = c->sub_item0.as<uint32_t>() + sb.cl0;
         bp.cluster_nitems = c->sub_nitems.as<uint32_t>() + sb.cl0;
-        bp.item_kept = c->it_kept.as<uint32_t>(); bp.item_unique = c->it_unique.as<uint32_t>();
-        bp.cluster_overflow = c->cl_overflow.as<uint32_t>();
-        bp.cluster_kmer_off = c->cl_kmer_off.as<uint64_t>(); bp.cluster_kmer_cnt = c->cl_kmer_cnt.as<uint32_t>();
-        bp.cluster_unique = c->cl_unique.as<uint32_t>(); bp.cursor = c->cursor.as<uint64_t>();
+        bp.vf = vf; bp.rs = rs; bp.out = out;
         bp.n = sb.ncl;
         PFCHK(mark_begin(c, TimeCat::emit));
         hipLaunchKernelGGL(pf::cluster_base_kernel, dim3(1), dim3(1024), 0, c->stream, bp);
@@ -1643,57 +1658,22 @@ struct SubmitRun {
         if (sb.nitems > sb.ncl) {     // some cluster of this sub-batch has several items
             pf::BitmapMergeParams bm{};
             bm.sub_cluster = bp.sub_cluster; bm.cluster_item0 = bp.cluster_item0; bm.cluster_nitems = bp.cluster_nitems;
-            bm.item_scratch = c->it_slice.as<uint32_t>(); bm.cluster_overflow = bp.cluster_overflow;
-            bm.v_mode = c->v_mode.as<uint32_t>(); bm.v_dense = c->v_dense.as<uint32_t>();
-            bm.item_fused = c->it_compact.as<uint32_t>();
-            bm.bm4 = c->bm4.as<uint4>(); bm.bm2 = c->bm2.as<uint2>();
+            bm.vf = vf; bm.items = items; bm.rs = rs;
             hipLaunchKernelGGL(pf::bitmap_merge_kernel, dim3(sb.ncl), dim3(256), 0, c->stream, bm);
             HIPCHK(hipGetLastError());
         }
 
         pf::EmitParams em{};
-        em.item_cluster = c->it_cluster.as<uint32_t>(); em.item_scratch = c->it_slice.as<uint32_t>();
-        em.item_unique = c->it_unique.as<uint32_t>(); em.item_nslots = c->it_nslots.as<uint32_t>();
-        em.item_sib0 = c->it_sib0.as<uint32_t>();
-        em.item_nsib = c->it_nsib.as<uint32_t>(); em.cluster_overflow = c->cl_overflow.as<uint32_t>();
-        em.v_mode = c->v_mode.as<uint32_t>(); em.v_dense = c->v_dense.as<uint32_t>();
-        em.cluster_nstrains = d.cluster_nstrains; em.cluster_npresab = d.cluster_npresab;
-        em.cluster_presab = d.cluster_presab; em.cluster_ordinal = d.cluster_ordinal;
-        em.cluster_kmer_off = c->cl_kmer_off.as<uint64_t>();
-        em.tab_key = c->tab_key.as<uint64_t>(); em.tab_ord = c->tab_ord.as<uint32_t>();
-        em.slot_hash = c->slot_hash.as<uint4>();
-        em.sorted_pair = c->sorted_pair.as<uint64_t>(); em.kept_prefix = c->kept_prefix.as<uint32_t>(); em.kept_prefix_rw = c->kept_prefix.as<uint32_t>();
-        em.bm4 = c->bm4.as<uint4>();
-        em.slot_out = c->slot_out.as<uint32_t>();
-        em.out_key = ar->key.as<uint64_t>(); em.out_pid = ar->pid.as<uint32_t>(); em.out_first = ar->first.as<uint64_t>();
-        em.cluster_pattern = c->cl_pattern.as<uint32_t>(); em.cluster_first = c->cl_first.as<uint64_t>();
-        em.pt = c->pt; em.out_base = ar->base; em.out_cap = ar->cap;
-        em.work = c->work_rows.as<uint32_t>() + o0.rows; em.W = W; em.NS = NS; em.KW = KW;
-        em.consider_missing = c->o.consider_missing; em.multiple_files = c->o.multiple_files;
+        em.cl = cl; em.vf = vf; em.items = items; em.dump = dump; em.rs = rs; em.out = out; em.pt = c->pt; em.opt = opt;
+        em.work = work;
         hipLaunchKernelGGL(pf::emit_kernel, dim3(n_rows), dim3(pf::EMIT_THREADS), 0, c->stream, em);
         HIPCHK(hipGetLastError());
         PFCHK(mark_end(c));
         PFCHK(mark_begin(c, TimeCat::pattern_rows));
 
         pf::PatRowsParams pr{};
-        pr.item_cluster = em.item_cluster; pr.item_scratch = em.item_scratch; pr.item_unique = em.item_unique;
-        pr.item_nslots = em.item_nslots; pr.item_is_extra = c->it_is_extra.as<uint32_t>();
-        pr.item_sib0 = em.item_sib0; pr.item_nsib = em.item_nsib; pr.cluster_overflow = em.cluster_overflow;
-        pr.v_mode = em.v_mode; pr.v_nstr = c->v_nstr.as<uint32_t>(); pr.v_dense = em.v_dense;
-        pr.cluster_seg_off = d.cluster_seg_off; pr.seg_sample = d.seg_sample; pr.seg_distinct = c->seg_distinct.as<uint32_t>();
-        pr.cluster_nstrains = d.cluster_nstrains; pr.cluster_npresab = d.cluster_npresab;
-        pr.cluster_presab = d.cluster_presab; pr.cluster_kmer_off = em.cluster_kmer_off;
-        pr.sorted_pair = em.sorted_pair; pr.kept_prefix = em.kept_prefix;
-        pr.chunkbits = c->chunkbits.as<uint32_t>(); pr.chunkmask = c->chunkmask.as<uint32_t>();
-        pr.slot_out = c->slot_out.as<uint32_t>(); pr.mrows = c->mrows.as<uint32_t>();
-        pr.out_pid = em.out_pid; pr.out_first = em.out_first;
-        pr.cluster_pattern = em.cluster_pattern; pr.cluster_first = em.cluster_first;
-        pr.pat_first_seen = c->pt.first_seen;
-        pr.pat_bits = c->pat_bits.as<uint32_t>();
-        pr.pat_nan = c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr;
-        pr.pat_n = c->pat_n.as<uint32_t>();
-        pr.out_base = ar->base; pr.out_cap = ar->cap; pr.pool = c->pt.pool;
-        pr.work = em.work; pr.W = W; pr.NS = NS; pr.consider_missing = c->o.consider_missing;
+        pr.cl = cl; pr.vf = vf; pr.items = items; pr.dump = dump; pr.rs = rs; pr.out = out; pr.pt = c->pt;
+        pr.pats = pattern_pool(); pr.opt = opt; pr.work = work;
         hipLaunchKernelGGL(pf::pattern_rows_kernel, dim3(n_rows), dim3(pf::PR_THREADS), 0, c->stream, pr);
         HIPCHK(hipGetLastError());
         PFCHK(mark_end(c));
@@ -1790,9 +1770,7 @@ struct SubmitRun {
     // ---- MD5 of the patterns this batch created, ids [pid0, pid1)
     int launch_md5(uint32_t pid1) {
         pf::Md5Params mp{};
-        mp.pat_bits = c->pat_bits.as<uint32_t>();
-        mp.pat_nan = c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr;
-        mp.pat_n = c->pat_n.as<uint32_t>(); mp.pat_md5 = c->pat_md5.as<uint8_t>();
+        mp.pats = pattern_pool(); mp.pat_md5 = c->pat_md5.as<uint8_t>();
         mp.pid0 = c->pid0; mp.pid1 = pid1; mp.W = W; mp.range = nullptr;
         // int64 rows are the clusters' own rows: the int pass goes by cluster (cl_pattern) and runs BESIDE the float pass, on
         // the side stream, instead of behind it
@@ -1811,7 +1789,7 @@ struct SubmitRun {
         const dim3 g_int(std::min<uint32_t>((C + pf::MD5_THREADS - 1) / pf::MD5_THREADS, 1024u));
         HIPCHK(hipEventRecord(c->ev_fork, c->stream));
         HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        if (mp.pat_nan) {
+        if (mp.pats.pat_nan) {
             hipLaunchKernelGGL((pf::md5_kernel<false, true>), g_int, dim3(pf::MD5_THREADS), 0, c->side, mp);
             HIPCHK(hipGetLastError());
             hipLaunchKernelGGL((pf::md5_kernel<true, true>), g_float, dim3(pf::MD5_THREADS), lds_cap, c->stream, mp);

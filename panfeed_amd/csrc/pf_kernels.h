@@ -152,6 +152,103 @@ __device__ __forceinline__ void mm3_final(H128& s, uint32_t len) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Argument groups of the submit chain.  Every device array that more than one kernel of a submit sees is named here,
+// once, with its shape and its writer; a kernel's parameter block embeds the groups it reads and keeps only what is
+// its own.  The host fills a group in one place (SubmitRun's builder of the same name in pf_api.hip).
+// [C] per cluster of the batch, [seg] per segment, [item] per work item, [slice] per scratch slice of an item,
+// NS = slots of a slice, W = 32-sample words of a row, KW = words of a key.
+// ---------------------------------------------------------------------------------------------
+// The caller's clusters and segments (pf_batch, in device memory), read-only but for seg_distinct.
+struct CallerSegs {
+    const uint32_t* cluster_seg_off;   // [C + 1] first segment of the cluster
+    const uint32_t* seg_sample;        // [seg] sample column, ascending inside a cluster
+    uint32_t* seg_distinct;            // [seg] distinct-sequence index of the segment (cluster_dedup_kernel, modes 1 and 2)
+    // [C] len(cluster) = the columns of its rows; [C] samples of cluster_presab; [C][W] the cluster's own row (clusterpresab)
+    const uint32_t* cluster_nstrains; const uint32_t* cluster_npresab; const uint32_t* cluster_presab;
+    const uint64_t* cluster_ordinal;   // [C] run-global number of the cluster
+};
+// The dedup view: what the scan walks instead of the caller's segments.  A type of its own, so that the scan cannot be
+// handed the caller's arrays by name.  Written by cluster_dedup_kernel (plain: one entry per distinct sequence, or per
+// segment in mode 0) and unit_class_kernel / unit_class_small_kernel (pool: one-unit pieces of the clusters that take the
+// unit view; view_off[c] carries VIEW_IN_POOL then).
+struct ViewSegs {
+    uint64_t* word_off;                // first packed word of the entry
+    uint32_t* len;                     // bases
+    uint32_t* sample;                  // sample column (mode 0) / distinct index (modes 1, 2) / first column of the chunk (pool)
+    uint32_t* ord;                     // instance ordinal of the entry's first window
+    uint32_t* bits;                    // presence bits a window of the entry sets in its chunk's word
+};
+struct View {
+    ViewSegs plain, pool;              // [seg] / [the unit pool of the launch]
+    uint32_t* view_off; uint32_t* v_nseg;   // [C] first entry of the cluster's view, entries of it
+};
+// What the dedup pass found per cluster, the scan's overflow mark, the slow-path rows per cluster.
+struct ViewFacts {
+    // [C], cluster_dedup_kernel: columns of the view (len(cluster) / distinct sequences); 0 every segment, 1 distinct sequences
+    // (D <= 64), 2 wide; dense ordinals of the cluster (ranks by bitmap)
+    const uint32_t* v_nstr; const uint32_t* v_mode; const uint32_t* v_dense;
+    uint32_t* cluster_overflow;        // [C] nonzero when a key partition overflowed: 64 * (units of the item / units scanned
+                                       // when the table was full), the largest over its partitions (kmer_scan_kernel)
+    // slow-path rows: [C + 1] CSR per cluster (host or extra_csr_kernel); [n_extra] ordinal of the row in the cluster's
+    // dense numbering (cluster_dedup_kernel); [n_extra][W] the rows themselves (caller)
+    const uint32_t* extra_off; const uint32_t* extra_dense; const uint32_t* extra_bits;
+};
+// A pass's work items: the host's upload, or plan_kernel's arrays and constants (SubmitRun::planned_items).
+struct Items {
+    const uint32_t* item_cluster;      // [item] batch-local cluster
+    const uint32_t* item_part; const uint32_t* item_nparts;   // [item] key partition of the item, of so many of its cluster
+    const uint32_t* item_nslots;       // [item] table slots (slow-path item: its rows)
+    const uint32_t* item_scratch;      // [item] scratch slice
+    const uint32_t* item_compact;      // [item] 1: finished by finish_kernel -> compact dump: occupied slots only, any order,
+                                       //        {key, ordinal, 64-bit allele mask}
+    const uint32_t* item_binned;       // [item] nonzero: the item's windows come from bin_kernel's queue
+    const uint32_t* item_is_extra; const uint32_t* item_extra_first;   // [item] slow-path rows; the first of them
+    const uint32_t* item_sib0; const uint32_t* item_nsib;     // [item] first item of the same cluster (absolute); its items
+};
+// What the scan (or extra_fill_kernel) leaves of an item's table in its scratch slice.
+struct SlotDump {
+    uint32_t* cmask_lo; uint32_t* cmask_hi;   // [slice][NS] allele mask words of the compact dump
+    uint64_t* tab_key; uint32_t* tab_ord;       // [slice][KW][NS] keys, [slice][NS] first-occurrence ordinals
+    uint32_t* chunkbits; uint32_t* chunkmask;   // [slice][W][NS] presence words, [slice][8] bit ch set: chunk ch was flushed
+    uint32_t* item_count;              // [item] keys in the item's table
+};
+// The general path's scratch: rows_kernel writes, (bitmap_merge_kernel,) emit_kernel and pattern_rows_kernel read.
+struct RowScratch {
+    uint4* slot_hash;                  // [slice][NS] 128-bit row identity
+    uint64_t* sorted_pair;             // [slice][NS] ranks by sorting: ord << 32 | slot, ascending
+    uint32_t* kept_prefix;             // [slice][NS + 1] exclusive prefix of keep flags in sorted order; with bitmaps emit_kernel
+                                       // puts the kept k-mers' output indices into words 1..
+    uint4* bm4;                        // [slice][DENSE_WORDS_BIG] per ordinal word {occupied, kept, ordinals before it, kept ones
+                                       // before it}: one 16-byte record, emit_kernel asks for all four at a random word per k-mer
+    uint2* bm2;                        // [slice][DENSE_WORDS_BIG] {occupied, kept} of an item that is one of several of its cluster:
+                                       // bitmap_merge_kernel reads them and writes the cluster's records into the first item's bm4
+    uint32_t* mrows;                   // [slice][DEDUP_MROWS] M[d][Wp]: samples that carry distinct sequence d
+    uint32_t* slot_out;                // [slice][NS] index of the slot's k-mer inside the cluster's output (emit_kernel)
+    uint32_t* item_unique; uint32_t* item_kept;   // [item] k-mers of the item, kept ones
+};
+// The pass's output arena and the per-cluster outputs.
+struct Outputs {
+    // [out_cap][KW] kept k-mers; [out_cap] their patterns; [out_cap] the first_seen each offered (emit_kernel -> pattern_rows_kernel)
+    uint64_t* out_key; uint32_t* out_pid; uint64_t* out_first;
+    uint64_t out_base, out_cap;        // run-global index of entry 0; entries
+    // [C] first output index of the cluster, its kept k-mers, its k-mers (cluster_base_kernel / finish_kernel)
+    uint64_t* cluster_kmer_off; uint32_t* cluster_kmer_cnt; uint32_t* cluster_unique;
+    uint32_t* cluster_pattern; uint64_t* cluster_first;   // [C] pattern of the cluster's own row, the first_seen it offered
+    uint64_t* cursor;                  // [0] next free output index  [1] total unique  [2] total kept
+};
+// Pattern rows by pattern id (beside PatternTable): whoever lowers a pattern's first_seen writes its row.
+struct PatternPool {
+    // [pool][W] the row; [pool][W] its NaN mask, null unless consider_missing; [pool] samples of the row, bit 31: an int64 row
+    uint32_t* pat_bits; uint32_t* pat_nan; uint32_t* pat_n;
+};
+struct RowOpts {
+    const uint32_t* maf_lo; const uint32_t* maf_hi;   // [max_strains + 1] carrier counts of the MAF window by denominator (host)
+    uint32_t W, NS, KW, consider_missing, patfilt, multiple_files;
+};
+// a block goes to its kernel by value: plain data, well inside the 4 KiB of kernel arguments
+#define PF_ARG_BLOCK(T) static_assert(std::is_trivially_copyable<T>::value && sizeof(T) <= 1024, #T " is a kernel argument block")
+
+// ---------------------------------------------------------------------------------------------
 // The rule of a k-mer's presence row, written once: its 128-bit identity, whether the k-mer is kept,
 // and the NaN mask of the row.  rows_kernel and finish_kernel only say where a row's words come from.
 // ---------------------------------------------------------------------------------------------
@@ -162,9 +259,8 @@ struct RowRule {
     uint64_t ordinal;
     bool multiple_files, consider_missing, same_possible;
 };
-// (P: RowsParams or FinishParams; npresent = popcount of presab)
-template <class P>
-__device__ __forceinline__ RowRule row_rule(const P& p, const uint32_t* presab, uint32_t nstr, uint32_t npres, uint32_t npresent,
+// (npresent = popcount of presab)
+__device__ __forceinline__ RowRule row_rule(const RowOpts& p, const uint32_t* presab, uint32_t nstr, uint32_t npres, uint32_t npresent,
                                             uint64_t ordinal) {
     RowRule r;
     r.presab = presab; r.nstr = nstr; r.nchunks = (nstr + 31) >> 5;
@@ -257,48 +353,27 @@ __device__ __forceinline__ uint32_t nan_word(const uint32_t* presab, uint32_t ns
 // distinct sequence with the distinct index in place of the sample column (mode 1).
 struct ScanParams {
     const uint64_t* packed;
-    const uint64_t* seg_word_off;     // view
-    const uint32_t* seg_len;          // view
-    const uint32_t* seg_sample;       // view: sample column (mode 0) / distinct index (mode 1)
-    const uint32_t* seg_ord_base;     // view: instance ordinal of the segment's first window
-    const uint32_t* seg_bits;         // view: presence bits a window of the segment sets in its chunk's word
-    // the unit view (unit_class_kernel) of the clusters that have one: same five arrays in a pool of their own;
-    // cluster_seg_off[c] carries VIEW_IN_POOL then
-    const uint64_t* u_word_off; const uint32_t* u_len; const uint32_t* u_sample; const uint32_t* u_ord_base; const uint32_t* u_bits;
-    const uint32_t* cluster_seg_off;  // first view segment of the cluster (view_off)
-    const uint32_t* cluster_vnseg;    // view segments of the cluster
-    const uint32_t* cluster_vnstr;    // columns of the view (len(cluster) / distinct sequences)
-    // per item (item = work[blockIdx.x])
-    const uint32_t* item_cluster;     // batch-local cluster index
-    const uint32_t* item_part;
-    const uint32_t* item_nparts;
-    const uint32_t* item_nslots;
-    const uint32_t* item_scratch;     // scratch slice of the item
-    const uint32_t* item_compact;     // 1: deduplicated cluster finished by finish_kernel -> compact table dump:
-                                      //    only occupied slots, {key, ordinal, 64-bit allele mask}, any order
-    uint32_t* cmask_lo; uint32_t* cmask_hi;   // [slice][NS] allele mask words of the compact dump
-    // scratch, indexed by slice
-    uint64_t* tab_key;                // [slice][KW][NS]
-    uint32_t* tab_ord;                // [slice][NS]
-    uint32_t* chunkbits;              // [slice][W][NS]
-    uint32_t* chunkmask;              // [slice][8]  bit ch set: chunk ch was flushed
-    uint32_t* item_count;             // [item] unique keys in the item's table
-    uint32_t* cluster_overflow;       // [cluster] nonzero when a partition overflowed: 64 * (units of the item / units
-                                      // scanned when the table was full), the largest over its partitions (>= 64)
+    View view;
+    // The rest of the block is flat, in a fixed order: the scan kernels spill over a hundred SGPRs and their VGPR spills
+    // follow the block's layout.  scan_params fills these from the groups.
+    const uint32_t* v_nstr;           // ViewFacts
+    const uint32_t* item_cluster; const uint32_t* item_part; const uint32_t* item_nparts; const uint32_t* item_nslots;   // Items
+    const uint32_t* item_scratch; const uint32_t* item_compact;
+    SlotDump dump;                    // what the scan leaves
+    uint32_t* cluster_overflow;       // ViewFacts
     const uint32_t* work;             // [n_work] item ids of this launch
     const struct ScanDesc* desc;      // [n_work] what a workgroup needs to start on work[i] (scan_desc_kernel)
     // binned clusters (bin_kernel): the windows of the cluster's view as (key, ordinal, presence bit) entries, sorted by
     // key partition and chunk; an item of such a cluster reads ITS entries instead of walking the whole view
-    const uint32_t* item_binned;      // [item] nonzero: the item's windows come from the queue
+    const uint32_t* item_binned;      // Items
     uint64_t* q_key; uint32_t* q_ord; uint32_t* q_bit;    // entries; word j of entry e's key: q_key[j * q_stride + e]
     uint64_t q_stride;
     uint32_t* q_off;                  // [item][BIN_CHUNKS + 1] first entry of every chunk of the item; [nchunks]: the end
     const uint32_t* bin_cluster; const uint32_t* bin_item0; const uint32_t* bin_nparts; const uint32_t* bin_base;   // [grid of bin_kernel]
-    uint32_t n_work;
-    uint32_t k;
-    uint32_t W;
+    uint32_t n_work, k, W;
     uint32_t NS;                      // slots per scratch slice (= nslots_max(KW))
 };
+PF_ARG_BLOCK(ScanParams);
 
 // One 64-byte record per work entry, so that a workgroup starts an item with one load instead of a chain of
 // four dependent ones (work -> item arrays -> cluster arrays); the scan kernel requests the next one while it
@@ -318,7 +393,7 @@ __global__ __launch_bounds__(256) void scan_desc_kernel(ScanParams p, ScanDesc* 
     d.ns = p.item_nslots[d.item]; d.slice = p.item_scratch[d.item];
     d.compact = p.item_compact[d.item];
     d.binned = p.item_binned ? p.item_binned[d.item] : 0u;
-    d.seg0 = p.cluster_seg_off[d.c]; d.nseg = p.cluster_vnseg[d.c]; d.nstr = p.cluster_vnstr[d.c];
+    d.seg0 = p.view.view_off[d.c]; d.nseg = p.view.v_nseg[d.c]; d.nstr = p.v_nstr[d.c];
     out[i] = d;
 }
 
@@ -715,11 +790,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void kmer_scan_kernel(ScanParams p) {
         if (tid < min(nseg, SEG_TILE)) {
             const uint32_t s = (seg0raw & ~VIEW_IN_POOL) + tid;
             if (seg0raw & VIEW_IN_POOL) {
-                pm_len = p.u_len[s]; pm_wo = p.u_word_off[s]; pm_ordb = p.u_ord_base[s]; pm_sample = p.u_sample[s];
-                pm_bits = p.u_bits[s];
+                pm_len = p.view.pool.len[s]; pm_wo = p.view.pool.word_off[s]; pm_ordb = p.view.pool.ord[s]; pm_sample = p.view.pool.sample[s];
+                pm_bits = p.view.pool.bits[s];
             } else {
-                pm_len = p.seg_len[s]; pm_wo = p.seg_word_off[s]; pm_ordb = p.seg_ord_base[s]; pm_sample = p.seg_sample[s];
-                pm_bits = p.seg_bits[s];
+                pm_len = p.view.plain.len[s]; pm_wo = p.view.plain.word_off[s]; pm_ordb = p.view.plain.ord[s]; pm_sample = p.view.plain.sample[s];
+                pm_bits = p.view.plain.bits[s];
             }
         }
     };
@@ -747,11 +822,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void kmer_scan_kernel(ScanParams p) {
     const uint32_t ns = misc[dcur + 4], slice = misc[dcur + 5];
     const bool in_pool = (misc[dcur + 6] & VIEW_IN_POOL) != 0;
     const uint32_t seg0 = misc[dcur + 6] & ~VIEW_IN_POOL, seg1 = seg0 + misc[dcur + 7];
-    const uint64_t* const a_woff = in_pool ? p.u_word_off : p.seg_word_off;
-    const uint32_t* const a_len = in_pool ? p.u_len : p.seg_len;
-    const uint32_t* const a_sample = in_pool ? p.u_sample : p.seg_sample;
-    const uint32_t* const a_ordb = in_pool ? p.u_ord_base : p.seg_ord_base;
-    const uint32_t* const a_bits = in_pool ? p.u_bits : p.seg_bits;
+    const uint64_t* const a_woff = in_pool ? p.view.pool.word_off : p.view.plain.word_off;
+    const uint32_t* const a_len = in_pool ? p.view.pool.len : p.view.plain.len;
+    const uint32_t* const a_sample = in_pool ? p.view.pool.sample : p.view.plain.sample;
+    const uint32_t* const a_ordb = in_pool ? p.view.pool.ord : p.view.plain.ord;
+    const uint32_t* const a_bits = in_pool ? p.view.pool.bits : p.view.plain.bits;
     const uint32_t nstr = misc[dcur + 8];
     const bool compact = misc[dcur + 9] != 0;  // view has <= 64 columns: at most chunks 0 and 1
     const bool binned = misc[dcur + 10] != 0;  // the cluster's windows were sorted by key partition (bin_kernel)
@@ -801,7 +876,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void kmer_scan_kernel(ScanParams p) {
 
     // flush the presence words of chunk `ch` (coalesced) and clear them
     auto flush_chunk = [&]() {
-        uint32_t* dst = p.chunkbits + ((size_t)slice * p.W + ch) * NS;
+        uint32_t* dst = p.dump.chunkbits + ((size_t)slice * p.W + ch) * NS;
         for (uint32_t i = tid; i < ns; i += SCAN_THREADS) {
             dst[i] = bits[i];
             bits[i] = 0;
@@ -1028,7 +1103,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void kmer_scan_kernel(ScanParams p) {
             const uint64_t all = misc[M_TMP], done = min(misc[M_PROG], (uint32_t)all) + 1;
             const uint64_t ratio = min((all * 64 + done - 1) / done, (uint64_t)0x7FFFFFFFu);
             atomicMax(&p.cluster_overflow[c], (uint32_t)max(ratio, (uint64_t)64));
-            p.item_count[item] = 0;
+            p.dump.item_count[item] = 0;
         }
         for (uint32_t i = tid; i < ns; i += SCAN_THREADS) {      // nothing is dumped: the table is emptied as a whole
 #pragma unroll
@@ -1043,7 +1118,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void kmer_scan_kernel(ScanParams p) {
         if (tid == 0) { misc[M_TMP] = c0_flushed ? 1u : 0u; misc[M_COUNT] = 0; }
         __syncthreads();
         const bool have_c0 = misc[M_TMP] != 0;
-        const uint32_t* g0 = p.chunkbits + ((size_t)slice * p.W) * NS;
+        const uint32_t* g0 = p.dump.chunkbits + ((size_t)slice * p.W) * NS;
         // occupied slots -> consecutive entries.  All of a thread's slots are looked at first (their LDS reads in flight
         // together), positions inside the wave's block come from ballots, and ONE LDS atomic per wave reserves the block:
         // an atomic per trip was ten dependent LDS round trips per wave with nothing to hide them.
@@ -1075,28 +1150,28 @@ __global__ __launch_bounds__(SCAN_THREADS) void kmer_scan_kernel(ScanParams p) {
             if (last_live && ch == 1) hi = bits[i];
             const uint32_t e = blk + at_[u];
 #pragma unroll
-            for (int j = 0; j < KW; j++) p.tab_key[((size_t)slice * KW + j) * NS + e] = keys[(size_t)j * NS + i];
-            p.tab_ord[(size_t)slice * NS + e] = o;
-            p.cmask_lo[(size_t)slice * NS + e] = lo;
-            if (nstr > 32) p.cmask_hi[(size_t)slice * NS + e] = hi;      // (at most 32 columns: nobody reads the upper word)
+            for (int j = 0; j < KW; j++) p.dump.tab_key[((size_t)slice * KW + j) * NS + e] = keys[(size_t)j * NS + i];
+            p.dump.tab_ord[(size_t)slice * NS + e] = o;
+            p.dump.cmask_lo[(size_t)slice * NS + e] = lo;
+            if (nstr > 32) p.dump.cmask_hi[(size_t)slice * NS + e] = hi;      // (at most 32 columns: nobody reads the upper word)
 #pragma unroll
             for (int j = 0; j < KW; j++) keys[(size_t)j * NS + i] = EMPTY64;
             ord[i] = NO_ORD;
             bits[i] = 0;
         }
         __syncthreads();
-        if (tid == 0) p.item_count[item] = misc[M_COUNT];
+        if (tid == 0) p.dump.item_count[item] = misc[M_COUNT];
     } else {
         for (uint32_t i = tid; i < ns; i += SCAN_THREADS) {
 #pragma unroll
-            for (int j = 0; j < KW; j++) p.tab_key[((size_t)slice * KW + j) * NS + i] = keys[(size_t)j * NS + i];
-            p.tab_ord[(size_t)slice * NS + i] = ord[i];
+            for (int j = 0; j < KW; j++) p.dump.tab_key[((size_t)slice * KW + j) * NS + i] = keys[(size_t)j * NS + i];
+            p.dump.tab_ord[(size_t)slice * NS + i] = ord[i];
 #pragma unroll
             for (int j = 0; j < KW; j++) keys[(size_t)j * NS + i] = EMPTY64;
             ord[i] = NO_ORD;                                    // (bits[] went out, and to zero, with the last chunk)
         }
-        if (tid < 8) p.chunkmask[slice * 8 + tid] = mask_word;
-        if (tid == 0) p.item_count[item] = misc[M_COUNT];
+        if (tid < 8) p.dump.chunkmask[slice * 8 + tid] = mask_word;
+        if (tid == 0) p.dump.item_count[item] = misc[M_COUNT];
     }
     __syncthreads();                               // the table and misc[] are free again
     PF_PROF_STAMP(20);
@@ -1124,15 +1199,15 @@ __global__ __launch_bounds__(BIN_THREADS) void bin_kernel(ScanParams p) {
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t b = blockIdx.x;
     const uint32_t c = p.bin_cluster[b], item0 = p.bin_item0[b], P = p.bin_nparts[b], base = p.bin_base[b];
-    const uint32_t raw = p.cluster_seg_off[c];
+    const uint32_t raw = p.view.view_off[c];
     const bool in_pool = (raw & VIEW_IN_POOL) != 0;
-    const uint32_t seg0 = raw & ~VIEW_IN_POOL, seg1 = seg0 + p.cluster_vnseg[c];
-    const uint64_t* const a_woff = in_pool ? p.u_word_off : p.seg_word_off;
-    const uint32_t* const a_len = in_pool ? p.u_len : p.seg_len;
-    const uint32_t* const a_sample = in_pool ? p.u_sample : p.seg_sample;
-    const uint32_t* const a_ordb = in_pool ? p.u_ord_base : p.seg_ord_base;
-    const uint32_t* const a_bits = in_pool ? p.u_bits : p.seg_bits;
-    const uint32_t nch = (p.cluster_vnstr[c] + 31) >> 5;          // <= BIN_CHUNKS (host)
+    const uint32_t seg0 = raw & ~VIEW_IN_POOL, seg1 = seg0 + p.view.v_nseg[c];
+    const uint64_t* const a_woff = in_pool ? p.view.pool.word_off : p.view.plain.word_off;
+    const uint32_t* const a_len = in_pool ? p.view.pool.len : p.view.plain.len;
+    const uint32_t* const a_sample = in_pool ? p.view.pool.sample : p.view.plain.sample;
+    const uint32_t* const a_ordb = in_pool ? p.view.pool.ord : p.view.plain.ord;
+    const uint32_t* const a_bits = in_pool ? p.view.pool.bits : p.view.plain.bits;
+    const uint32_t nch = (p.v_nstr[c] + 31) >> 5;          // <= BIN_CHUNKS (host)
     const uint32_t cells = P * nch;                                // <= BIN_CELLS (host)
     const uint32_t k = p.k;
     for (uint32_t i = tid; i < BIN_CELLS; i += BIN_THREADS) cell[i] = 0;
@@ -1334,16 +1409,14 @@ __host__ __device__ inline bool ranks_by_bitmap(uint32_t mode, uint32_t v_dense)
 // ("wide"): rows gathered through the (distinct index, sample) list of the segments, ranks by sorting.
 
 struct DedupParams {
-    const uint64_t* packed; const uint64_t* seg_word_off; const uint32_t* seg_len;
+    const uint64_t* packed; const uint64_t* seg_word_off; const uint32_t* seg_len;     // the caller's segments
     const uint32_t* seg_sample; const uint32_t* seg_ord_base;
     const uint32_t* cluster_seg_off; const uint32_t* cluster_nstrains;
     const uint32_t* extra_off;        // [C+1] extras per cluster (CSR)
-    const uint32_t* extra_ord;        // [n_extra]
-    uint64_t* v_word_off; uint32_t* v_len; uint32_t* v_sample; uint32_t* v_ord;   // view, [n_segs]
+    const uint32_t* extra_ord;        // [n_extra] the caller's ordinals of them
+    View view;                        // the plain view and its place per cluster are written here
     uint32_t* seg_distinct;           // [n_segs] distinct index of every original segment (modes 1, 2)
-    uint32_t* v_bits;                 // view, [n_segs]: the presence bits a window of the segment sets in its chunk's word
-    uint32_t* v_nseg; uint32_t* v_nstr; uint32_t* v_mode; uint32_t* v_dense;       // [C]
-    uint32_t* view_off;               // [C] first entry of the cluster's view in the view arrays
+    uint32_t* v_nstr; uint32_t* v_mode; uint32_t* v_dense;       // [C] (ViewFacts)
     // per-cluster outputs of the passes that follow, given their start values here (small class only: it sees every
     // cluster of a batch first) instead of by four memsets in front of the batch
     uint32_t* cl_overflow; uint32_t* cl_kmer_cnt; uint32_t* cl_unique; uint32_t* cl_pattern;
@@ -1352,6 +1425,7 @@ struct DedupParams {
     uint32_t cluster_base;            // first cluster of this launch (the batch's clusters may be launched in two halves)
     const uint32_t* cluster_list;     // or: the clusters of this launch (the wide class runs on the flagged ones only)
 };
+PF_ARG_BLOCK(DedupParams);
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull; x ^= x >> 27; x *= 0x94d049bb133111ebull; x ^= x >> 31;
@@ -1691,11 +1765,11 @@ void cluster_dedup_kernel(DedupParams p) {
                 for (uint32_t s = tid; s < n; s += DEDUP_THREADS) p.seg_distinct[seg0 + s] = t_rank[s_slot[s]];
                 for (uint32_t d = tid; d < D; d += DEDUP_THREADS) {
                     const uint32_t s = r_rep[d];
-                    p.v_word_off[seg0 + d] = p.seg_word_off[seg0 + s];
-                    p.v_len[seg0 + d] = p.seg_len[seg0 + s];
-                    p.v_sample[seg0 + d] = d;
-                    p.v_bits[seg0 + d] = 1u << (d & 31);
-                    p.v_ord[seg0 + d] = r_dense[d];
+                    p.view.plain.word_off[seg0 + d] = p.seg_word_off[seg0 + s];
+                    p.view.plain.len[seg0 + d] = p.seg_len[seg0 + s];
+                    p.view.plain.sample[seg0 + d] = d;
+                    p.view.plain.bits[seg0 + d] = 1u << (d & 31);
+                    p.view.plain.ord[seg0 + d] = r_dense[d];
                 }
                 for (uint32_t e = ex0 + tid; e < ex1; e += DEDUP_THREADS) {
                     // F(o) = scanned instances below o + slow-path rows below o  (monotone in the reference order)
@@ -1711,8 +1785,8 @@ void cluster_dedup_kernel(DedupParams p) {
                     p.extra_dense[e] = (below + er) * mult;
                 }
                 if (tid == 0) {
-                    p.view_off[c] = seg0;
-                    p.v_nseg[c] = D; p.v_nstr[c] = D; p.v_mode[c] = CFG::MODE;
+                    p.view.view_off[c] = seg0;
+                    p.view.v_nseg[c] = D; p.v_nstr[c] = D; p.v_mode[c] = CFG::MODE;
                     p.v_dense[c] = (uint32_t)min(dense_bits, (uint64_t)0xFFFFFFFFu);
                 }
             }
@@ -1721,17 +1795,17 @@ void cluster_dedup_kernel(DedupParams p) {
     if (!mode1) {
         // mode 0: the view is the caller's segment list
         for (uint32_t s = tid; s < n; s += DEDUP_THREADS) {
-            p.v_word_off[seg0 + s] = p.seg_word_off[seg0 + s];
-            p.v_len[seg0 + s] = p.seg_len[seg0 + s];
+            p.view.plain.word_off[seg0 + s] = p.seg_word_off[seg0 + s];
+            p.view.plain.len[seg0 + s] = p.seg_len[seg0 + s];
             const uint32_t smp = p.seg_sample[seg0 + s];
-            p.v_sample[seg0 + s] = smp;
-            p.v_bits[seg0 + s] = 1u << (smp & 31);
-            p.v_ord[seg0 + s] = p.seg_ord_base[seg0 + s];
+            p.view.plain.sample[seg0 + s] = smp;
+            p.view.plain.bits[seg0 + s] = 1u << (smp & 31);
+            p.view.plain.ord[seg0 + s] = p.seg_ord_base[seg0 + s];
         }
         for (uint32_t e = ex0 + tid; e < ex1; e += DEDUP_THREADS) p.extra_dense[e] = p.extra_ord[e];
         if (tid == 0) {
-            p.view_off[c] = seg0;
-            p.v_nseg[c] = n; p.v_nstr[c] = p.cluster_nstrains[c]; p.v_dense[c] = 0;
+            p.view.view_off[c] = seg0;
+            p.view.v_nseg[c] = n; p.v_nstr[c] = p.cluster_nstrains[c]; p.v_dense[c] = 0;
             p.v_mode[c] = retry_wide ? MODE_RETRY_WIDE : 0;
         }
     }
@@ -1753,17 +1827,17 @@ void cluster_dedup_kernel(DedupParams p) {
 // over several chunks is listed once per chunk.
 struct UnitParams {
     const uint64_t* packed;
-    const uint32_t* cluster_seg_off;       // the plain view of cluster c sits at [seg0, seg0 + D) of the view arrays
+    const uint32_t* cluster_seg_off;       // the caller's: the plain view of cluster c sits at [seg0, seg0 + D) of the view arrays
     const uint32_t* v_nstr;                // [C] D
     const uint32_t* list_cluster;          // [n] clusters of this launch
-    const uint32_t* list_base;             // [n] where the cluster's pieces go in the view arrays (room: its units)
-    const uint64_t* v_word_off; const uint32_t* v_len; const uint32_t* v_ord;     // the plain view
-    uint64_t* u_word_off; uint32_t* u_len; uint32_t* u_sample; uint32_t* u_ord; uint32_t* u_bits;   // the pool
-    uint32_t* v_nseg; uint32_t* view_off;  // [C] rewritten when the cluster takes the unit view
+    const uint32_t* list_base;             // [n] where the cluster's pieces go in the pool (room: its units)
+    View view;                             // plain is read, the pool written; v_nseg and view_off are rewritten when the
+                                           // cluster takes the unit view
     uint32_t k;
     uint32_t tmp_off;                      // unit_class_kernel: a second stretch of the pool arrays, this far behind the first,
                                            // takes a cluster's pieces in the order they are found
 };
+PF_ARG_BLOCK(UnitParams);
 constexpr uint32_t UNIT_THREADS = 256;
 constexpr uint32_t UNIT_TAB = 4096;            // class-table slots per batch of unit positions
 constexpr uint32_t UNIT_PAIRS = 2048;          // (distinct sequence, unit) pairs per batch: half the table
@@ -1771,6 +1845,7 @@ constexpr uint32_t UNIT_PER_THREAD = UNIT_PAIRS / UNIT_THREADS;
 constexpr uint32_t UNIT_MAX_WORDS = 6;         // ceil((63 + PF_MAX_K) / 32)
 
 __global__ __launch_bounds__(UNIT_THREADS) void unit_class_kernel(UnitParams p) {
+    const ViewSegs& pool = p.view.pool;
     __shared__ uint64_t t_hash[UNIT_TAB];
     __shared__ uint32_t t_min[UNIT_TAB];                 // lowest pair index of the class = its first member
     __shared__ uint32_t d_len[DEDUP_MAX_D_WIDE], d_ord[DEDUP_MAX_D_WIDE];
@@ -1785,9 +1860,9 @@ __global__ __launch_bounds__(UNIT_THREADS) void unit_class_kernel(UnitParams p) 
     const uint32_t Dp = (D + 31) & ~31u, nchunks = Dp >> 5;
     uint32_t maxlen = 0;
     for (uint32_t d = tid; d < D; d += UNIT_THREADS) {
-        const uint64_t wo = p.v_word_off[seg0 + d];
-        const uint32_t len = p.v_len[seg0 + d];
-        d_len[d] = len; d_ord[d] = p.v_ord[seg0 + d]; d_wlo[d] = (uint32_t)wo; d_whi[d] = (uint32_t)(wo >> 32);
+        const uint64_t wo = p.view.plain.word_off[seg0 + d];
+        const uint32_t len = p.view.plain.len[seg0 + d];
+        d_len[d] = len; d_ord[d] = p.view.plain.ord[seg0 + d]; d_wlo[d] = (uint32_t)wo; d_whi[d] = (uint32_t)(wo >> 32);
         maxlen = max(maxlen, len);
     }
     for (uint32_t i = tid; i < nchunks; i += UNIT_THREADS) ch_cnt[i] = 0;
@@ -1890,11 +1965,11 @@ __global__ __launch_bounds__(UNIT_THREADS) void unit_class_kernel(UnitParams p) 
                         const uint32_t fi = t_min[my_slot[r]], fd = fi - (fi / Dp) * Dp;
                         atomicAdd(&ch_cnt[chunk], 1u);
                         const uint32_t at = tb + atomicAdd(&sh_npieces, 1u);
-                        p.u_word_off[at] = (((uint64_t)d_whi[fd] << 32) | d_wlo[fd]) + 2 * (uint64_t)u;
-                        p.u_len[at] = min(d_len[fd] - 64 * u, span);
-                        p.u_ord[at] = d_ord[fd] + 64 * u;
-                        p.u_sample[at] = chunk << 5;
-                        p.u_bits[at] = members;
+                        pool.word_off[at] = (((uint64_t)d_whi[fd] << 32) | d_wlo[fd]) + 2 * (uint64_t)u;
+                        pool.len[at] = min(d_len[fd] - 64 * u, span);
+                        pool.ord[at] = d_ord[fd] + 64 * u;
+                        pool.sample[at] = chunk << 5;
+                        pool.bits[at] = members;
                     }
                     if (same) todo = false;
                 }
@@ -1912,14 +1987,14 @@ __global__ __launch_bounds__(UNIT_THREADS) void unit_class_kernel(UnitParams p) 
         }
         __syncthreads();                                             // (the pieces written above: visible to the workgroup)
         for (uint32_t i = tid, n = sh_npieces; i < n; i += UNIT_THREADS) {
-            const uint32_t smp = p.u_sample[tb + i], chunk = smp >> 5;
+            const uint32_t smp = pool.sample[tb + i], chunk = smp >> 5;
             const uint32_t at = base + ch_base[chunk] + atomicAdd(&ch_cnt[chunk], 1u);
-            p.u_word_off[at] = p.u_word_off[tb + i]; p.u_len[at] = p.u_len[tb + i]; p.u_ord[at] = p.u_ord[tb + i];
-            p.u_sample[at] = smp; p.u_bits[at] = p.u_bits[tb + i];
+            pool.word_off[at] = pool.word_off[tb + i]; pool.len[at] = pool.len[tb + i]; pool.ord[at] = pool.ord[tb + i];
+            pool.sample[at] = smp; pool.bits[at] = pool.bits[tb + i];
         }
         __syncthreads();
     }
-    if (tid == 0) { p.view_off[c] = base | VIEW_IN_POOL; p.v_nseg[c] = ch_base[nchunks]; }
+    if (tid == 0) { p.view.view_off[c] = base | VIEW_IN_POOL; p.view.v_nseg[c] = ch_base[nchunks]; }
 }
 
 // The same for a cluster of at most 64 distinct sequences (every mode-1 cluster: the usual case), without a table: one
@@ -1931,6 +2006,7 @@ __global__ __launch_bounds__(UNIT_THREADS) void unit_class_kernel(UnitParams p) 
 constexpr uint32_t UNIT_SMALL_MAX_D = 64;
 template <int NW>     // 64-bit words a unit's 63 + k bases take: ceil((63 + k) / 32)
 __global__ __launch_bounds__(256) void unit_class_small_kernel(UnitParams p, uint32_t n) {
+    const ViewSegs& pool = p.view.pool;
     // One wave per cluster.  The wave's lanes are G = 4 .. 64 columns (the next power of two >= D) x 64 / G unit positions:
     // with lane = distinct sequence alone, a cluster of 8 alleles left 56 lanes idle and the kernel was bound by
     // instruction issue (9 000 wave-instructions per cluster, 0.7 ms per 50 000 clusters).  Classes inside a group of G
@@ -1948,7 +2024,7 @@ __global__ __launch_bounds__(256) void unit_class_small_kernel(UnitParams p, uin
     const uint64_t gmask = G == 64 ? ~0ull : (1ull << G) - 1;
     uint32_t len = 0, ordb = 0;
     uint64_t wo = 0;
-    if (d < D) { len = p.v_len[seg0 + d]; ordb = p.v_ord[seg0 + d]; wo = p.v_word_off[seg0 + d]; }
+    if (d < D) { len = p.view.plain.len[seg0 + d]; ordb = p.view.plain.ord[seg0 + d]; wo = p.view.plain.word_off[seg0 + d]; }
     uint32_t maxlen = len;
     for (int o = 32; o > 0; o >>= 1) maxlen = max(maxlen, __shfl_xor(maxlen, o));
     if (maxlen < k) return;
@@ -1986,13 +2062,13 @@ __global__ __launch_bounds__(256) void unit_class_small_kernel(UnitParams p, uin
                 if (lead) {
                     if (m0) {
                         const uint32_t at = base + i0 + (uint32_t)__popcll(b0 & below);
-                        p.u_word_off[at] = wo + 2 * (uint64_t)u; p.u_len[at] = nb; p.u_ord[at] = ordb + 64 * u;
-                        p.u_sample[at] = 0; p.u_bits[at] = m0;
+                        pool.word_off[at] = wo + 2 * (uint64_t)u; pool.len[at] = nb; pool.ord[at] = ordb + 64 * u;
+                        pool.sample[at] = 0; pool.bits[at] = m0;
                     }
                     if (m1) {
                         const uint32_t at = tb + i1 + (uint32_t)__popcll(b1 & below);
-                        p.u_word_off[at] = wo + 2 * (uint64_t)u; p.u_len[at] = nb; p.u_ord[at] = ordb + 64 * u;
-                        p.u_sample[at] = 32; p.u_bits[at] = m1;
+                        pool.word_off[at] = wo + 2 * (uint64_t)u; pool.len[at] = nb; pool.ord[at] = ordb + 64 * u;
+                        pool.sample[at] = 32; pool.bits[at] = m1;
                     }
                 }
                 i0 += (uint32_t)__popcll(b0); i1 += (uint32_t)__popcll(b1);
@@ -2003,11 +2079,11 @@ __global__ __launch_bounds__(256) void unit_class_small_kernel(UnitParams p, uin
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // this wave's stores above, before its loads below
             for (uint32_t j = lane; j < i1; j += 64) {
                 const uint32_t at = base + i0 + j;
-                p.u_word_off[at] = p.u_word_off[tb + j]; p.u_len[at] = p.u_len[tb + j]; p.u_ord[at] = p.u_ord[tb + j];
-                p.u_sample[at] = 32; p.u_bits[at] = p.u_bits[tb + j];
+                pool.word_off[at] = pool.word_off[tb + j]; pool.len[at] = pool.len[tb + j]; pool.ord[at] = pool.ord[tb + j];
+                pool.sample[at] = 32; pool.bits[at] = pool.bits[tb + j];
             }
         }
-        if (lane == 0) { p.view_off[c] = base | VIEW_IN_POOL; p.v_nseg[c] = i0 + i1; }
+        if (lane == 0) { p.view.view_off[c] = base | VIEW_IN_POOL; p.view.v_nseg[c] = i0 + i1; }
     }
 }
 
@@ -2032,60 +2108,40 @@ __global__ __launch_bounds__(256) void extra_csr_kernel(const uint32_t* extra_cl
 // slow-path rows -> a prebuilt table in an item's scratch slice (same layout the scan kernel leaves)
 // ---------------------------------------------------------------------------------------------
 struct ExtraParams {
-    const uint32_t* extra_ord;     // ordinals in the cluster's numbering (cluster_dedup_kernel's extra_dense)
-    const uint32_t* extra_bits;    // [n_extra][W]
-    const uint32_t* item_first;    // [n] first extra row of the item
-    const uint32_t* item_nslots;   // [n] rows of the item
-    const uint32_t* item_scratch;
-    uint64_t* tab_key; uint32_t* tab_ord; uint32_t* chunkbits; uint32_t* chunkmask; uint32_t* item_count;
+    ViewFacts vf;                  // extra_dense, extra_bits
+    Items items;                   // item_extra_first, item_nslots (rows of the item), item_scratch
+    SlotDump dump;
+    RowOpts opt;
     const uint32_t* work;          // [gridDim.x] item ids of this launch
-    uint32_t W, NS, KW;
 };
+PF_ARG_BLOCK(ExtraParams);
 __global__ void extra_fill_kernel(ExtraParams p) {
     const uint32_t item = p.work[blockIdx.x];
-    const uint32_t first = p.item_first[item], n = p.item_nslots[item], slice = p.item_scratch[item];
+    const uint32_t first = p.items.item_extra_first[item], n = p.items.item_nslots[item], slice = p.items.item_scratch[item];
     for (uint32_t e = threadIdx.x; e < n; e += blockDim.x) {
-        p.tab_key[((size_t)slice * p.KW) * p.NS + e] = KEY_EXTRA_FLAG | (uint64_t)(first + e);
-        for (uint32_t j = 1; j < p.KW; j++) p.tab_key[((size_t)slice * p.KW + j) * p.NS + e] = 0;
-        p.tab_ord[(size_t)slice * p.NS + e] = p.extra_ord[first + e];
-        for (uint32_t w = 0; w < p.W; w++)
-            p.chunkbits[((size_t)slice * p.W + w) * p.NS + e] = p.extra_bits[(size_t)(first + e) * p.W + w];
+        p.dump.tab_key[((size_t)slice * p.opt.KW) * p.opt.NS + e] = KEY_EXTRA_FLAG | (uint64_t)(first + e);
+        for (uint32_t j = 1; j < p.opt.KW; j++) p.dump.tab_key[((size_t)slice * p.opt.KW + j) * p.opt.NS + e] = 0;
+        p.dump.tab_ord[(size_t)slice * p.opt.NS + e] = p.vf.extra_dense[first + e];
+        for (uint32_t w = 0; w < p.opt.W; w++)
+            p.dump.chunkbits[((size_t)slice * p.opt.W + w) * p.opt.NS + e] = p.vf.extra_bits[(size_t)(first + e) * p.opt.W + w];
     }
-    if (threadIdx.x < 8) p.chunkmask[slice * 8 + threadIdx.x] = 0xFFFFFFFFu;
-    if (threadIdx.x == 0) p.item_count[item] = n;
+    if (threadIdx.x < 8) p.dump.chunkmask[slice * 8 + threadIdx.x] = 0xFFFFFFFFu;
+    if (threadIdx.x == 0) p.dump.item_count[item] = n;
 }
 
 // ---------------------------------------------------------------------------------------------
 // rows_kernel
 // ---------------------------------------------------------------------------------------------
 struct RowsParams {
-    const uint32_t* item_cluster; const uint32_t* item_nslots; const uint32_t* item_scratch;
-    const uint32_t* item_count; const uint32_t* item_is_extra;
-    const uint32_t* cluster_overflow;
-    const uint32_t* cluster_seg_off;                                   // caller's segments (for M)
-    const uint32_t* seg_sample; const uint32_t* seg_distinct;          // caller's sample column / distinct index
-    const uint32_t* v_mode; const uint32_t* v_nstr; const uint32_t* v_dense;
-    const uint32_t* cluster_nstrains; const uint32_t* cluster_npresab; const uint32_t* cluster_presab;
-    const uint64_t* cluster_ordinal;
-    const uint32_t* maf_lo; const uint32_t* maf_hi;
-    const uint32_t* tab_ord; const uint32_t* chunkbits; const uint32_t* chunkmask;
-    uint4* slot_hash;        // [slice][NS]
-    // mode 0 (sorted)
-    uint64_t* sorted_pair;   // [slice][NS]  ord << 32 | slot, ascending
-    uint32_t* kept_prefix;   // [slice][NS+1] exclusive prefix of keep flags in sorted order
-    // mode 1 (ordinal bitmaps)
-    uint4* bm4;              // [slice][DENSE_WORDS_BIG] per ordinal word {occupied, kept, ordinals before it, kept ones before it}:
-                             // one 16-byte record, because emit_kernel asks for all four at a random word per kept k-mer
-    uint2* bm2;              // [slice][DENSE_WORDS_BIG] {occupied, kept} of an item that is one of several of its cluster: what
-                             // bitmap_merge_kernel reads (it writes the cluster's records into the first item's bm4)
-    const uint32_t* item_nsib;   // [item] items of the item's cluster
-    uint32_t* mrows;         // [slice][DEDUP_MROWS]  M[d][Wp]: samples that carry distinct sequence d
-    uint32_t* item_unique;   // [item]
-    uint32_t* item_kept;     // [item]
+    CallerSegs cl;           // (the segments: for M)
+    ViewFacts vf;
+    Items items;
+    SlotDump dump;
+    RowScratch rs;
+    RowOpts opt;
     const uint32_t* work;    // [gridDim.x] item ids of this launch
-    uint32_t W, NS;
-    uint32_t consider_missing, patfilt, multiple_files;
 };
+PF_ARG_BLOCK(RowsParams);
 
 constexpr uint32_t ROWS_THREADS = 1024;
 constexpr uint32_t AT_SLOTS = 1024, AT_LIMIT = 768;   // distinct allele masks per item held in LDS (mode 1)
@@ -2142,29 +2198,29 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
     PF_PROF_BEGIN();
     const uint32_t tid = threadIdx.x;
     const uint32_t item = p.work[blockIdx.x];
-    const uint32_t c = p.item_cluster[item];
-    const uint32_t slice = p.item_scratch[item];
-    const uint32_t NS = p.NS, W = p.W;
-    if (p.cluster_overflow[c]) {
-        if (tid == 0) { p.item_unique[item] = 0; p.item_kept[item] = 0; }
+    const uint32_t c = p.items.item_cluster[item];
+    const uint32_t slice = p.items.item_scratch[item];
+    const uint32_t NS = p.opt.NS, W = p.opt.W;
+    if (p.vf.cluster_overflow[c]) {
+        if (tid == 0) { p.rs.item_unique[item] = 0; p.rs.item_kept[item] = 0; }
         return;
     }
-    const uint32_t ns = p.item_nslots[item];
-    const uint32_t mode = p.v_mode[c] & 3u;
-    const bool expand = mode == 1 && !p.item_is_extra[item];
-    const bool wide = mode == 2 && !p.item_is_extra[item];
-    const bool bitmaps = ranks_by_bitmap(mode, p.v_dense[c]);     // ranks from ordinal bitmaps; else sorted pairs
-    const uint32_t nstr = p.cluster_nstrains[c], npres = p.cluster_npresab[c];
+    const uint32_t ns = p.items.item_nslots[item];
+    const uint32_t mode = p.vf.v_mode[c] & 3u;
+    const bool expand = mode == 1 && !p.items.item_is_extra[item];
+    const bool wide = mode == 2 && !p.items.item_is_extra[item];
+    const bool bitmaps = ranks_by_bitmap(mode, p.vf.v_dense[c]);     // ranks from ordinal bitmaps; else sorted pairs
+    const uint32_t nstr = p.cl.cluster_nstrains[c], npres = p.cl.cluster_npresab[c];
     const uint32_t nchunks = (nstr + 31) >> 5;
     const uint32_t Wp = (W + 3) & ~3u;
-    const uint32_t* presab = p.cluster_presab + (size_t)c * W;
+    const uint32_t* presab = p.cl.cluster_presab + (size_t)c * W;
 
     uint64_t* pairs = reinterpret_cast<uint64_t*>(rsh);
     uint8_t* keepf = reinterpret_cast<uint8_t*>(rsh + 2 * SORT_MAX);
     uint32_t* M = rsh;
     uint32_t* occ = rsh + DEDUP_MROWS;
     uint32_t* keepbm = occ + DENSE_WORDS;
-    const uint32_t dense_words = bitmaps ? (p.v_dense[c] + 31) >> 5 : 0;
+    const uint32_t dense_words = bitmaps ? (p.vf.v_dense[c] + 31) >> 5 : 0;
     // more dense ordinals than two LDS bitmaps hold (a wide cluster of up to 1 048 576 windows over its distinct sequences):
     // ONE bitmap of DENSE_WIN words, per stretch of the ordinal space used twice -- occupied ordinals, then kept ones -- with
     // the slots' keep flags parked in slot_tag meanwhile.  (Such clusters sorted their (ordinal, slot) pairs per item and searched every
@@ -2174,7 +2230,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
     uint16_t* segd = reinterpret_cast<uint16_t*>(rsh);   // mode 2: (distinct index << 5 | sample & 31) per segment;
                                                          // lives where `pairs` will be, until the rows are evaluated
 
-    if (tid < 8) cmask[tid] = p.chunkmask[slice * 8 + tid];
+    if (tid < 8) cmask[tid] = p.dump.chunkmask[slice * 8 + tid];
     if (tid == 0) {
         sh_cnt = 0;
         uint32_t np = 0;
@@ -2191,21 +2247,21 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
     __syncthreads();
     if (expand) {
         // M[d] = samples whose sequence is distinct sequence d, from the caller's segment list
-        const uint32_t s0 = p.cluster_seg_off[c], s1 = p.cluster_seg_off[c + 1];
+        const uint32_t s0 = p.cl.cluster_seg_off[c], s1 = p.cl.cluster_seg_off[c + 1];
         for (uint32_t s = s0 + tid; s < s1; s += ROWS_THREADS) {
-            const uint32_t d = p.seg_distinct[s], smp = p.seg_sample[s];
+            const uint32_t d = p.cl.seg_distinct[s], smp = p.cl.seg_sample[s];
             atomicOr(&M[d * Wp + (smp >> 5)], 1u << (smp & 31));
         }
         __syncthreads();
-        const uint32_t mw = p.v_nstr[c] * Wp;
-        for (uint32_t i = tid; i < mw; i += ROWS_THREADS) p.mrows[(size_t)slice * DEDUP_MROWS + i] = M[i];
+        const uint32_t mw = p.vf.v_nstr[c] * Wp;
+        for (uint32_t i = tid; i < mw; i += ROWS_THREADS) p.rs.mrows[(size_t)slice * DEDUP_MROWS + i] = M[i];
         PF_PROF_STAMP(57);
     }
-    const uint64_t ordinal = p.cluster_ordinal[c];
-    const RowRule rule = row_rule(p, presab, nstr, npres, sh_npres, ordinal);
+    const uint64_t ordinal = p.cl.cluster_ordinal[c];
+    const RowRule rule = row_rule(p.opt, presab, nstr, npres, sh_npres, ordinal);
 
-    const uint32_t* ordp = p.tab_ord + (size_t)slice * NS;
-    const uint32_t* cb = p.chunkbits + (size_t)slice * W * NS;
+    const uint32_t* ordp = p.dump.tab_ord + (size_t)slice * NS;
+    const uint32_t* cb = p.dump.chunkbits + (size_t)slice * W * NS;
     const bool f0 = (cmask[0] & 1) != 0, f1 = (cmask[0] & 2) != 0;
 
     // presence row of one k-mer -> (128-bit row hash, keep flag).  The row comes either from the chunk words of
@@ -2257,12 +2313,12 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
         // segments is a copy of a distinct sequence of the mask.  Distinct masks are evaluated once (table keyed by a
         // 50-bit hash of the words, verified word for word against the slot that opened the entry), in rounds of up
         // to AT_LIMIT distinct masks: a mask that finds the table full waits for the next round.
-        const uint32_t s0 = p.cluster_seg_off[c], s1 = p.cluster_seg_off[c + 1], nsegs = s1 - s0;
-        const uint32_t D = p.v_nstr[c], nmw = (D + 31) >> 5;
+        const uint32_t s0 = p.cl.cluster_seg_off[c], s1 = p.cl.cluster_seg_off[c + 1], nsegs = s1 - s0;
+        const uint32_t D = p.vf.v_nstr[c], nmw = (D + 31) >> 5;
         // (the segments are sorted by sample: the first segment of a 32-sample word is the count of those before it)
         for (uint32_t s = tid; s < nsegs; s += ROWS_THREADS) {
-            const uint32_t smp = p.seg_sample[s0 + s];
-            segd[s] = (uint16_t)((p.seg_distinct[s0 + s] << 5) | (smp & 31u));
+            const uint32_t smp = p.cl.seg_sample[s0 + s];
+            segd[s] = (uint16_t)((p.cl.seg_distinct[s0 + s] << 5) | (smp & 31u));
             atomicAdd(&wstart[(smp >> 5) + 1], 1u);
         }
         // (every slot starts as waiting; step A, which asks for a slot's mask words anyway, asks for its ordinal with them and
@@ -2306,7 +2362,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
         const uint32_t RW = (nchunks + 3) & ~3u;
         const uint32_t cap = min(min(AT_LIMIT, (20480u - ((nsegs + 1) >> 1)) / nmw), 4u * (DENSE_WORDS_BIG / RW));
         auto row_of = [&](uint32_t e) -> uint32_t* {
-            return reinterpret_cast<uint32_t*>(p.bm4 + (size_t)slice * DENSE_WORDS_BIG) + (size_t)e * RW;
+            return reinterpret_cast<uint32_t*>(p.rs.bm4 + (size_t)slice * DENSE_WORDS_BIG) + (size_t)e * RW;
         };
         // one half-wave per mask: lane j gathers row word 32 r + j in round r, the 32 words of a round then go through
         // the row hash in order (eight blocks), every lane running it on the words read back from LDS (one broadcast
@@ -2400,7 +2456,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
         // (for clusters of three or more work items: there an allele's private k-mers are nearly all there is and its mask
         // comes back in every item -- 2 000 clusters of ~150 SURVEY alleles, ten items each: rows_kernel 6.2 -> 5.7 ms; with
         // related alleles, two items a cluster, the set-up cost what it saved: 1.40 -> 1.54 ms)
-        const bool singles = D <= SINGLE_MAX && m_base + D * RW <= 20480u && p.item_nsib[item] >= 3;
+        const bool singles = D <= SINGLE_MAX && m_base + D * RW <= 20480u && p.items.item_nsib[item] >= 3;
         if (singles) {
             uint32_t* Ms = rsh + m_base;
             for (uint32_t i = tid; i < D * RW; i += ROWS_THREADS) Ms[i] = 0;
@@ -2605,12 +2661,12 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
                 if (tag >= SINGLE_TAG && tag < SINGLE_TAG + SINGLE_MAX) {
                     const uint32_t dd = tag - SINGLE_TAG;
                     const bool kp = (single_keep[dd >> 5] >> (dd & 31u)) & 1u;
-                    if (kp) p.slot_hash[(size_t)slice * NS + i] = single_hash[dd];
+                    if (kp) p.rs.slot_hash[(size_t)slice * NS + i] = single_hash[dd];
                     slot_tag[i] = kp ? WIDE_KEEP : WIDE_DROP;
                     continue;
                 }
                 if (tag >= AT_SLOTS) continue;
-                if (at_keep[tag]) p.slot_hash[(size_t)slice * NS + i] = at_hash[tag];    // (emit_kernel reads kept k-mers' only)
+                if (at_keep[tag]) p.rs.slot_hash[(size_t)slice * NS + i] = at_hash[tag];    // (emit_kernel reads kept k-mers' only)
                 slot_tag[i] = at_keep[tag] ? WIDE_KEEP : WIDE_DROP;
             }
             __syncthreads();
@@ -2701,7 +2757,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
         // the kept k-mers of the item, (ordinal, slot) in any order, for emit_kernel -- which otherwise looks at every slot
         // of the table and finds out slot by slot, load after load, that most are empty or dropped
         if (bitmaps && keep && (o >> 5) < dense_words)
-            p.sorted_pair[(size_t)slice * NS + atomicAdd(&sh_cnt, 1u)] = ((uint64_t)o << 32) | i;
+            p.rs.sorted_pair[(size_t)slice * NS + atomicAdd(&sh_cnt, 1u)] = ((uint64_t)o << 32) | i;
     };
     if (wide) {
         // (hash and flag of every slot: round D above; here only the ordinals are read, five slots' at a time)
@@ -2739,7 +2795,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
             }
             if (found) { h = at_hash[a]; keep = at_keep[a] != 0; }
             else keep = row_eval(true, amask, i, h);          // table was full: evaluate this slot on its own
-            if (keep) p.slot_hash[(size_t)slice * NS + i] = h;
+            if (keep) p.rs.slot_hash[(size_t)slice * NS + i] = h;
             place(i, o, keep);
         }
     }
@@ -2763,11 +2819,11 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
         } else {
             keep = row_eval(false, 0, i, h);
         }
-        if (keep) p.slot_hash[(size_t)slice * NS + i] = h;
+        if (keep) p.rs.slot_hash[(size_t)slice * NS + i] = h;
         place(i, o, keep);
     }
     __syncthreads();
-    if (bitmaps && tid == 0) p.kept_prefix[(size_t)slice * (NS + 1)] = sh_cnt;
+    if (bitmaps && tid == 0) p.rs.kept_prefix[(size_t)slice * (NS + 1)] = sh_cnt;
     PF_PROF_STAMP(44);
 
     if (big) {
@@ -2775,7 +2831,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
         // the occupied ordinals of the stretch, then the kept ones -- with the counts of the stretches before it carried on
         constexpr uint32_t PWB = DENSE_WIN / ROWS_THREADS;           // 16 words per thread
         const size_t gb = (size_t)slice * DENSE_WORDS_BIG;
-        const bool alone = p.item_nsib[item] == 1;
+        const bool alone = p.items.item_nsib[item] == 1;
         uint32_t base_o = 0, base_k = 0;
         for (uint32_t w0 = 0; w0 < dense_words; w0 += DENSE_WIN) {
             for (int round = 0; round < 2; round++) {
@@ -2793,8 +2849,8 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
                 for (uint32_t j = 0; j < PWB; j++) sm += __popc(bigbm[tid * PWB + j]);
                 uint32_t tot;
                 uint32_t run = (round ? base_k : base_o) + block_exscan(sm, wave_tot, &tot);
-                uint32_t* rec = reinterpret_cast<uint32_t*>(p.bm4 + gb) + (round ? 1 : 0);      // .x / .y, and .z / .w two further on
-                uint32_t* rec2 = reinterpret_cast<uint32_t*>(p.bm2 + gb) + (round ? 1 : 0);
+                uint32_t* rec = reinterpret_cast<uint32_t*>(p.rs.bm4 + gb) + (round ? 1 : 0);      // .x / .y, and .z / .w two further on
+                uint32_t* rec2 = reinterpret_cast<uint32_t*>(p.rs.bm2 + gb) + (round ? 1 : 0);
 #pragma unroll
                 for (uint32_t j = 0; j < PWB; j++) {
                     const uint32_t w = w0 + tid * PWB + j;
@@ -2808,7 +2864,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
                 if (round) base_k += tot; else base_o += tot;
             }
         }
-        if (tid == 0) { p.item_unique[item] = base_o; p.item_kept[item] = base_k; }
+        if (tid == 0) { p.rs.item_unique[item] = base_o; p.rs.item_kept[item] = base_k; }
         PF_PROF_STAMP(45);
         return;
     }
@@ -2827,18 +2883,18 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
         uint32_t bo = block_exscan(so, wave_tot, &tot_o);
         uint32_t bk = block_exscan(sk, wave_tot, &tot_k);
         const size_t gb = (size_t)slice * DENSE_WORDS_BIG;
-        const bool alone = p.item_nsib[item] == 1;
+        const bool alone = p.items.item_nsib[item] == 1;
 #pragma unroll
         for (uint32_t j = 0; j < PW; j++) {
             const uint32_t w = tid * PW + j;
             if (w < dense_words) {
                 const uint32_t a = occ[w], b = keepbm[w];
-                if (alone) p.bm4[gb + w] = make_uint4(a, b, bo, bk);
-                else p.bm2[gb + w] = make_uint2(a, b);
+                if (alone) p.rs.bm4[gb + w] = make_uint4(a, b, bo, bk);
+                else p.rs.bm2[gb + w] = make_uint2(a, b);
                 bo += __popc(a); bk += __popc(b);
             }
         }
-        if (tid == 0) { p.item_unique[item] = tot_o; p.item_kept[item] = tot_k; }
+        if (tid == 0) { p.rs.item_unique[item] = tot_o; p.rs.item_kept[item] = tot_k; }
         PF_PROF_STAMP(45);
         return;
     }
@@ -2874,8 +2930,8 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
     }
     uint32_t total;
     const uint32_t base = block_exscan(sum, wave_tot, &total);
-    uint64_t* sp = p.sorted_pair + (size_t)slice * NS;
-    uint32_t* kp = p.kept_prefix + (size_t)slice * (NS + 1);
+    uint64_t* sp = p.rs.sorted_pair + (size_t)slice * NS;
+    uint32_t* kp = p.rs.kept_prefix + (size_t)slice * (NS + 1);
 #pragma unroll
     for (uint32_t j = 0; j < PER; j++) {
         const uint32_t r = tid * PER + j;
@@ -2883,8 +2939,8 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
     }
     if (tid == 0) {
         kp[n] = total;
-        p.item_unique[item] = n;
-        p.item_kept[item] = total;
+        p.rs.item_unique[item] = n;
+        p.rs.item_kept[item] = total;
     }
     PF_PROF_STAMP(46);
 }
@@ -2898,11 +2954,11 @@ __global__ __launch_bounds__(ROWS_THREADS) void rows_kernel(RowsParams p) {
 // (emit_kernel asked every sibling, four loads each, for every kept k-mer).  The result replaces the first item's arrays.
 struct BitmapMergeParams {
     const uint32_t* sub_cluster; const uint32_t* cluster_item0; const uint32_t* cluster_nitems;   // as BaseParams
-    const uint32_t* item_scratch; const uint32_t* cluster_overflow; const uint32_t* v_mode; const uint32_t* v_dense;
-    const uint32_t* item_fused;        // [item] nonzero: finished by finish_kernel, which keeps its bitmaps in LDS
-    uint4* bm4;                        // [slice][DENSE_WORDS_BIG] {occupied, kept, ordinals before, kept before} per ordinal word
-    const uint2* bm2;                  // [slice][DENSE_WORDS_BIG] the items' own {occupied, kept}
+    ViewFacts vf;
+    Items items;                       // item_compact nonzero: finished by finish_kernel, which keeps its bitmaps in LDS
+    RowScratch rs;                     // bm2 of every item -> bm4 of the cluster's first
 };
+PF_ARG_BLOCK(BitmapMergeParams);
 constexpr uint32_t BM_THREADS = 256, BM_WPT = 4, BM_SIB = 64;   // words per thread and round; sibling slices staged at a time
 __global__ __launch_bounds__(BM_THREADS) void bitmap_merge_kernel(BitmapMergeParams p) {
     // Round 3's form took one word per thread and round and walked the siblings in a loop whose every trip was two
@@ -2915,9 +2971,9 @@ __global__ __launch_bounds__(BM_THREADS) void bitmap_merge_kernel(BitmapMergePar
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t c = p.sub_cluster[blockIdx.x];
     const uint32_t i0 = p.cluster_item0[blockIdx.x], ni = p.cluster_nitems[blockIdx.x];
-    if (ni < 2 || p.item_fused[i0] || p.cluster_overflow[c] || !ranks_by_bitmap(p.v_mode[c] & 3u, p.v_dense[c])) return;
-    const uint32_t dense_words = (p.v_dense[c] + 31) >> 5;
-    const size_t g0 = (size_t)p.item_scratch[i0] * DENSE_WORDS_BIG;
+    if (ni < 2 || p.items.item_compact[i0] || p.vf.cluster_overflow[c] || !ranks_by_bitmap(p.vf.v_mode[c] & 3u, p.vf.v_dense[c])) return;
+    const uint32_t dense_words = (p.vf.v_dense[c] + 31) >> 5;
+    const size_t g0 = (size_t)p.items.item_scratch[i0] * DENSE_WORDS_BIG;
     uint32_t run_o = 0, run_k = 0;                       // ordinals / kept ordinals in the words before this round's
     constexpr uint32_t RW = BM_THREADS * BM_WPT;
     for (uint32_t w0 = 0; w0 < dense_words; w0 += RW) {
@@ -2929,7 +2985,7 @@ __global__ __launch_bounds__(BM_THREADS) void bitmap_merge_kernel(BitmapMergePar
         for (uint32_t q0 = 0; q0 < ni; q0 += BM_SIB) {
             const uint32_t nq = min(ni - q0, BM_SIB);
             __syncthreads();
-            if (tid < nq) sib_slice[tid] = p.item_scratch[i0 + q0 + tid];
+            if (tid < nq) sib_slice[tid] = p.items.item_scratch[i0 + q0 + tid];
             __syncthreads();
             for (uint32_t q = 0; q < nq; q += 8) {
                 uint2 v[8][BM_WPT];
@@ -2937,7 +2993,7 @@ __global__ __launch_bounds__(BM_THREADS) void bitmap_merge_kernel(BitmapMergePar
                 for (uint32_t u = 0; u < 8; u++) {
                     const size_t g = (size_t)sib_slice[min(q + u, nq - 1)] * DENSE_WORDS_BIG;
 #pragma unroll
-                    for (uint32_t j = 0; j < BM_WPT; j++) v[u][j] = p.bm2[g + min(wb + j, dense_words - 1)];
+                    for (uint32_t j = 0; j < BM_WPT; j++) v[u][j] = p.rs.bm2[g + min(wb + j, dense_words - 1)];
                 }
 #pragma unroll
                 for (uint32_t u = 0; u < 8; u++) {
@@ -2965,7 +3021,7 @@ __global__ __launch_bounds__(BM_THREADS) void bitmap_merge_kernel(BitmapMergePar
         }
 #pragma unroll
         for (uint32_t j = 0; j < BM_WPT; j++) {
-            if (wb + j < dense_words) p.bm4[g0 + wb + j] = make_uint4(o[j], k[j], bo, bk);
+            if (wb + j < dense_words) p.rs.bm4[g0 + wb + j] = make_uint4(o[j], k[j], bo, bk);
             bo += __popc(o[j]); bk += __popc(k[j]);
         }
         run_o += to; run_k += tk;
@@ -2979,12 +3035,12 @@ struct BaseParams {
     const uint32_t* sub_cluster;       // [n] batch-local cluster ids of this sub-batch
     const uint32_t* cluster_item0;     // [n] first item (absolute) of the cluster in this pass
     const uint32_t* cluster_nitems;    // [n]
-    const uint32_t* item_kept; const uint32_t* item_unique;
-    const uint32_t* cluster_overflow;
-    uint64_t* cluster_kmer_off; uint32_t* cluster_kmer_cnt; uint32_t* cluster_unique;
-    uint64_t* cursor;                  // [0] next free output index  [1] total unique  [2] total kept
+    ViewFacts vf;
+    RowScratch rs;                     // item_kept, item_unique
+    Outputs out;
     uint32_t n;
 };
+PF_ARG_BLOCK(BaseParams);
 __global__ __launch_bounds__(1024) void cluster_base_kernel(BaseParams p) {
     // (output room is CLAIMED -- one atomic add per 1 024 clusters -- not read and written back: the fused finish kernels of
     // the same sub-batch may be running beside this kernel on the context's second stream, and they claim theirs the same way)
@@ -2998,30 +3054,30 @@ __global__ __launch_bounds__(1024) void cluster_base_kernel(BaseParams p) {
         bool live = false;
         if (i < p.n) {
             c = p.sub_cluster[i];
-            live = !p.cluster_overflow[c];
+            live = !p.vf.cluster_overflow[c];
             if (live) {
                 const uint32_t i0 = p.cluster_item0[i], ni = p.cluster_nitems[i];
-                for (uint32_t q = 0; q < ni; q++) { kept += p.item_kept[i0 + q]; uniq += p.item_unique[i0 + q]; }
+                for (uint32_t q = 0; q < ni; q++) { kept += p.rs.item_kept[i0 + q]; uniq += p.rs.item_unique[i0 + q]; }
             }
         }
         uint32_t total;
         const uint32_t ex = block_exscan(kept, wave_tot, &total);
         if (tid == 0) {
-            sh_base = atomicAdd((unsigned long long*)&p.cursor[0], (unsigned long long)total);
-            if (total) atomicAdd((unsigned long long*)&p.cursor[2], (unsigned long long)total);
+            sh_base = atomicAdd((unsigned long long*)&p.out.cursor[0], (unsigned long long)total);
+            if (total) atomicAdd((unsigned long long*)&p.out.cursor[2], (unsigned long long)total);
         }
         __syncthreads();
         if (i < p.n && live) {
-            p.cluster_kmer_off[c] = sh_base + ex;
-            p.cluster_kmer_cnt[c] = kept;
-            p.cluster_unique[c] = uniq;
+            p.out.cluster_kmer_off[c] = sh_base + ex;
+            p.out.cluster_kmer_cnt[c] = kept;
+            p.out.cluster_unique[c] = uniq;
             uniq_sum += uniq;
         }
         __syncthreads();
     }
     // totals
     for (int d = 32; d > 0; d >>= 1) uniq_sum += __shfl_down(uniq_sum, d);
-    if ((tid & 63) == 0 && uniq_sum) atomicAdd((unsigned long long*)&p.cursor[1], (unsigned long long)uniq_sum);
+    if ((tid & 63) == 0 && uniq_sum) atomicAdd((unsigned long long*)&p.out.cursor[1], (unsigned long long)uniq_sum);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3189,29 +3245,17 @@ __global__ __launch_bounds__(256) void pattern_rehash_kernel(RehashParams p) {
 // emit_kernel
 // ---------------------------------------------------------------------------------------------
 struct EmitParams {
-    const uint32_t* item_cluster; const uint32_t* item_scratch; const uint32_t* item_unique;
-    const uint32_t* item_nslots;
-    const uint32_t* item_sib0;       // [item] first item of the same cluster (absolute)
-    const uint32_t* item_nsib;       // [item] items of that cluster
-    const uint32_t* cluster_overflow;
-    const uint32_t* v_mode; const uint32_t* v_dense;
-    const uint32_t* cluster_nstrains; const uint32_t* cluster_npresab; const uint32_t* cluster_presab;
-    const uint64_t* cluster_ordinal;
-    const uint64_t* cluster_kmer_off;
-    const uint64_t* tab_key; const uint32_t* tab_ord; const uint4* slot_hash;
- const uint64_t* sorted_pair; const uint32_t* kept_prefix;                                       // mode 0
-    uint32_t* kept_prefix_rw;        // (the same array: with bitmaps its words 1.. take the kept k-mers' output indices)
-    const uint4* bm4;                // ranks by bitmap: {occupied, kept, ordinals before, kept before} per ordinal word
-    uint32_t* slot_out;              // [slice][NS] mode 1: index of the slot's k-mer inside the cluster's output
-    uint64_t* out_key; uint32_t* out_pid; uint64_t* out_first;     // out_first: first_seen each k-mer offered
-    uint32_t* cluster_pattern; uint64_t* cluster_first;
+    CallerSegs cl;
+    ViewFacts vf;
+    Items items;
+    SlotDump dump;
+    RowScratch rs;
+    Outputs out;
     PatternTable pt;
-    uint64_t out_base;      // global index of out_key[0] (arena base)
-    uint64_t out_cap;       // entries in the arena
+    RowOpts opt;
     const uint32_t* work;   // [gridDim.x] item ids of this launch
-    uint32_t W, NS, KW;
-    uint32_t consider_missing, multiple_files;
 };
+PF_ARG_BLOCK(EmitParams);
 
 __device__ __forceinline__ uint32_t pair_lower_bound(const uint64_t* sp, uint32_t n, uint32_t ord) {
     uint32_t a = 0, b = n;
@@ -3244,36 +3288,36 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(EmitParams p) {
     PF_PROF_BEGIN();
     const uint32_t tid = threadIdx.x;
     const uint32_t item = p.work[blockIdx.x];
-    const uint32_t c = p.item_cluster[item];
-    if (p.cluster_overflow[c]) return;
-    const uint32_t slice = p.item_scratch[item];
-    const uint32_t NS = p.NS, W = p.W, KW = p.KW;
-    const uint32_t U = p.item_unique[item];
-    const uint32_t sib0 = p.item_sib0[item], nsib = p.item_nsib[item];
-    const uint64_t ordinal = p.cluster_ordinal[c];
-    const uint64_t obase = p.cluster_kmer_off[c] - p.out_base;
-    const uint32_t mode = p.v_mode[c] & 3u;
-    const bool sorted = !ranks_by_bitmap(mode, p.v_dense[c]);    // the item's k-mers sorted by ordinal (rows_kernel), or
+    const uint32_t c = p.items.item_cluster[item];
+    if (p.vf.cluster_overflow[c]) return;
+    const uint32_t slice = p.items.item_scratch[item];
+    const uint32_t NS = p.opt.NS, W = p.opt.W, KW = p.opt.KW;
+    const uint32_t U = p.rs.item_unique[item];
+    const uint32_t sib0 = p.items.item_sib0[item], nsib = p.items.item_nsib[item];
+    const uint64_t ordinal = p.cl.cluster_ordinal[c];
+    const uint64_t obase = p.out.cluster_kmer_off[c] - p.out.out_base;
+    const uint32_t mode = p.vf.v_mode[c] & 3u;
+    const bool sorted = !ranks_by_bitmap(mode, p.vf.v_dense[c]);    // the item's k-mers sorted by ordinal (rows_kernel), or
                                                                  // ordinal bitmaps
 
     if (item == sib0 && tid == 0) {
-        const uint4 h = own_row_hash(p.cluster_presab + (size_t)c * W, p.cluster_npresab[c], ordinal, p.multiple_files);
+        const uint4 h = own_row_hash(p.cl.cluster_presab + (size_t)c * W, p.cl.cluster_npresab[c], ordinal, p.opt.multiple_files);
         const uint64_t fs = ordinal << 32;
-        p.cluster_pattern[c] = pattern_insert(p.pt, h, fs);
-        p.cluster_first[c] = fs;
+        p.out.cluster_pattern[c] = pattern_insert(p.pt, h, fs);
+        p.out.cluster_first[c] = fs;
     }
 
-    const uint32_t ns = p.item_nslots[item];
-    const size_t gb0 = (size_t)p.item_scratch[sib0] * DENSE_WORDS_BIG;
-    const uint64_t* sp = p.sorted_pair + (size_t)slice * NS;
-    const uint32_t* kp = p.kept_prefix + (size_t)slice * (NS + 1);
-    uint32_t* sout = p.slot_out + (size_t)slice * NS;    // per entry (slot / sorted position): index of its k-mer in
+    const uint32_t ns = p.items.item_nslots[item];
+    const size_t gb0 = (size_t)p.items.item_scratch[sib0] * DENSE_WORDS_BIG;
+    const uint64_t* sp = p.rs.sorted_pair + (size_t)slice * NS;
+    const uint32_t* kp = p.rs.kept_prefix + (size_t)slice * (NS + 1);
+    uint32_t* sout = p.rs.slot_out + (size_t)slice * NS;    // per entry (slot / sorted position): index of its k-mer in
                                                          // the cluster's output, NONE when it is not kept
     // entries: the item's k-mers in ordinal order (sorted), or its KEPT k-mers in any order (bitmaps: rows_kernel left
     // their (ordinal, slot) pairs in sorted_pair and their number in kept_prefix[0]; kept_prefix[1 + i] takes entry i's
     // output index here)
     const uint32_t n_entries = sorted ? U : min(kp[0], ns);
-    uint32_t* kres = p.kept_prefix_rw + (size_t)slice * (NS + 1) + 1;
+    uint32_t* kres = p.rs.kept_prefix + (size_t)slice * (NS + 1) + 1;
     for (uint32_t i = tid; i < LT_SLOTS; i += EMIT_THREADS) { lt_lo[i] = EMPTY64; lt_hi[i] = EMPTY64; lt_first[i] = EMPTY64; }
     if (tid == 0) { lt_count = 0; ins_cnt[0] = 0; }
     // (ranks by bitmap: nobody reads a slot's output index -- pattern_rows_kernel and pass 3 go by entry, kres[] -- so the
@@ -3284,7 +3328,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(EmitParams p) {
     __syncthreads();
     PF_PROF_STAMP(32);
     auto row_id = [&](uint32_t slot, uint64_t& lo, uint64_t& hi) {
-        const uint4 h = p.slot_hash[(size_t)slice * NS + slot];
+        const uint4 h = p.rs.slot_hash[(size_t)slice * NS + slot];
         lo = ((uint64_t)h.x << 32) | h.y; hi = ((uint64_t)h.z << 32) | h.w;
         if (lo == EMPTY64) lo--;
         if (hi == EMPTY64) hi--;
@@ -3308,10 +3352,10 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(EmitParams p) {
                     for (uint32_t q = 0; q < nsib; q++) {
                         const uint32_t it = sib0 + q;
                         if (it == item) continue;
-                        const uint32_t sl = p.item_scratch[it];
-                        const uint32_t lb = pair_lower_bound(p.sorted_pair + (size_t)sl * NS, p.item_unique[it], ord);
+                        const uint32_t sl = p.items.item_scratch[it];
+                        const uint32_t lb = pair_lower_bound(p.rs.sorted_pair + (size_t)sl * NS, p.rs.item_unique[it], ord);
                         rank += lb;
-                        kept_before += p.kept_prefix[(size_t)sl * (NS + 1) + lb];
+                        kept_before += p.rs.kept_prefix[(size_t)sl * (NS + 1) + lb];
                     }
                     res = kept_before;
                     fs = (ordinal << 32) | (uint64_t)(rank + 1);
@@ -3325,7 +3369,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(EmitParams p) {
                 // the cluster's bitmaps: this item's own, or (several items) their union, which
                 // bitmap_merge_kernel left in the first item's place -- four loads that go out together
                 const size_t g2 = gb0 + (o >> 5);
-                const uint4 rec = p.bm4[g2];
+                const uint4 rec = p.rs.bm4[g2];
                 const uint32_t bo = rec.x, kw = rec.y, po = rec.z, pk = rec.w;
                 row_id(slot, lo, hi);                          // (and the row hash with them)
                 res = pk + __popc(kw & below);
@@ -3344,7 +3388,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(EmitParams p) {
         uint32_t ls = 0;
         if (st == 2) {
             const uint64_t o_idx = obase + res;
-            if (o_idx < p.out_cap) p.out_first[o_idx] = fs;
+            if (o_idx < p.out.out_cap) p.out.out_first[o_idx] = fs;
             if (sorted) row_id(slot, lo, hi);
             ls = (uint32_t)(lo ^ (hi >> 7)) & (LT_SLOTS - 1);
         }
@@ -3396,7 +3440,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(EmitParams p) {
         const uint32_t kb = sorted ? sout[i] : kres[i];
         if (kb == 0xFFFFFFFFu) continue;
         const uint64_t o_idx = obase + kb;
-        if (o_idx >= p.out_cap) { p.pt.counters[2] = 1; continue; }   // cannot happen: the arena holds every item's limit
+        if (o_idx >= p.out.out_cap) { p.pt.counters[2] = 1; continue; }   // cannot happen: the arena holds every item's limit
         const uint32_t slot = (uint32_t)sp[i];
         uint32_t pid = 0xFFFFFFFFu;
         bool found = false;
@@ -3416,10 +3460,10 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(EmitParams p) {
             }
         }
         // not in the local table (it was full): straight to the run-global table
-        if (!found) pid = pattern_insert(p.pt, lo, (uint32_t)(hi >> 32), p.out_first[o_idx]);
-        p.out_key[o_idx * KW] = p.tab_key[((size_t)slice * KW) * NS + slot];
-        for (uint32_t j = 1; j < KW; j++) p.out_key[o_idx * KW + j] = p.tab_key[((size_t)slice * KW + j) * NS + slot];
-        p.out_pid[o_idx] = pid;
+        if (!found) pid = pattern_insert(p.pt, lo, (uint32_t)(hi >> 32), p.out.out_first[o_idx]);
+        p.out.out_key[o_idx * KW] = p.dump.tab_key[((size_t)slice * KW) * NS + slot];
+        for (uint32_t j = 1; j < KW; j++) p.out.out_key[o_idx * KW + j] = p.dump.tab_key[((size_t)slice * KW + j) * NS + slot];
+        p.out.out_pid[o_idx] = pid;
     }
 #ifdef PF_PROF
     __syncthreads();
@@ -3477,6 +3521,7 @@ struct FinishParams {
     uint32_t W, NS, KW;
     uint32_t consider_missing, patfilt, multiple_files;
 };
+PF_ARG_BLOCK(FinishParams);
 
 // MULTI: the work item is the first of several key partitions of the cluster; the slot loops run over all of
 // them (the mask table, ordinal bitmaps and M are per cluster anyway) and slot tags are looked up again instead
@@ -3608,7 +3653,9 @@ __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(8,
     __syncthreads();
     PF_PROF_STAMP(1);
     PF_KO_FINISH_AT(1);
-    const RowRule rule = row_rule(p, presab, nstr, npres, sh_npres, ordinal);
+    // (the options group out of the flat block's fields)
+    const RowOpts opt{p.maf_lo, p.maf_hi, p.W, p.NS, p.KW, p.consider_missing, p.patfilt, p.multiple_files};
+    const RowRule rule = row_rule(opt, presab, nstr, npres, sh_npres, ordinal);
 
     auto row_word4 = [&](uint64_t amask, uint32_t ch, uint32_t (&wv)[4]) {
         wv[0] = wv[1] = wv[2] = wv[3] = 0;
@@ -3980,26 +4027,18 @@ __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(8,
     atomicAdd(&pf_prof[k], (unsigned long long)(n_ - prof_t_)); prof_t_ = n_; } } while (0)
 #endif
 struct PatRowsParams {
-    const uint32_t* item_cluster; const uint32_t* item_scratch; const uint32_t* item_unique;
-    const uint32_t* item_nslots; const uint32_t* item_is_extra;
-    const uint32_t* item_sib0; const uint32_t* item_nsib;
-    const uint32_t* cluster_overflow;
-    const uint32_t* v_mode; const uint32_t* v_nstr; const uint32_t* v_dense;
-    const uint32_t* cluster_seg_off; const uint32_t* seg_sample; const uint32_t* seg_distinct;   // caller's segments (mode 2)
-    const uint32_t* cluster_nstrains; const uint32_t* cluster_npresab; const uint32_t* cluster_presab;
-    const uint64_t* cluster_kmer_off;
-    const uint64_t* sorted_pair; const uint32_t* kept_prefix; const uint32_t* chunkbits; const uint32_t* chunkmask;
-    const uint32_t* slot_out; const uint32_t* mrows;
-    const uint32_t* out_pid; const uint64_t* out_first;
-    const uint32_t* cluster_pattern; const uint64_t* cluster_first;
-    const uint64_t* pat_first_seen;
-    uint32_t* pat_bits; uint32_t* pat_nan; uint32_t* pat_n;
-    uint64_t out_base, out_cap;
-    uint32_t pool;
+    CallerSegs cl;          // (the segments: mode 2)
+    ViewFacts vf;
+    Items items;
+    SlotDump dump;
+    RowScratch rs;
+    Outputs out;
+    PatternTable pt;
+    PatternPool pats;
+    RowOpts opt;
     const uint32_t* work;   // [gridDim.x] item ids of this launch
-    uint32_t W, NS;
-    uint32_t consider_missing;
 };
+PF_ARG_BLOCK(PatRowsParams);
 constexpr uint32_t PR_LIST = 2048;   // winners collected per round
 // 512 threads: three workgroups = 24 waves per CU (the 50 KiB of LDS allow three; with 256 threads that was 12 waves, with
 // 1024 two workgroups = 32 waves but longer barriers).  Phase 1 is three dependent global loads per slot and nothing else:
@@ -4026,52 +4065,52 @@ __global__ __launch_bounds__(PR_THREADS) void pattern_rows_kernel(PatRowsParams 
 
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
     const uint32_t item = p.work[blockIdx.x];
-    const uint32_t c = p.item_cluster[item];
-    if (p.cluster_overflow[c]) return;
-    const uint32_t slice = p.item_scratch[item];
-    const uint32_t NS = p.NS, W = p.W;
-    const uint32_t U = p.item_unique[item];
-    const uint32_t sib0 = p.item_sib0[item];
-    const uint32_t nstr = p.cluster_nstrains[c];
+    const uint32_t c = p.items.item_cluster[item];
+    if (p.vf.cluster_overflow[c]) return;
+    const uint32_t slice = p.items.item_scratch[item];
+    const uint32_t NS = p.opt.NS, W = p.opt.W;
+    const uint32_t U = p.rs.item_unique[item];
+    const uint32_t sib0 = p.items.item_sib0[item];
+    const uint32_t nstr = p.cl.cluster_nstrains[c];
     const uint32_t nchunks = (nstr + 31) >> 5;
-    const uint32_t* presab = p.cluster_presab + (size_t)c * W;
-    const uint64_t obase = p.cluster_kmer_off[c] - p.out_base;
-    const uint32_t* cb = p.chunkbits + (size_t)slice * W * NS;
-    const uint32_t* cm = p.chunkmask + slice * 8;
-    const uint32_t mode = p.v_mode[c] & 3u;
-    const uint32_t ns = p.item_nslots[item];
-    const bool expand = mode == 1 && !p.item_is_extra[item];
-    const bool wide = mode == 2 && !p.item_is_extra[item];
-    const uint32_t nmw = (p.v_nstr[c] + 31) >> 5;
+    const uint32_t* presab = p.cl.cluster_presab + (size_t)c * W;
+    const uint64_t obase = p.out.cluster_kmer_off[c] - p.out.out_base;
+    const uint32_t* cb = p.dump.chunkbits + (size_t)slice * W * NS;
+    const uint32_t* cm = p.dump.chunkmask + slice * 8;
+    const uint32_t mode = p.vf.v_mode[c] & 3u;
+    const uint32_t ns = p.items.item_nslots[item];
+    const bool expand = mode == 1 && !p.items.item_is_extra[item];
+    const bool wide = mode == 2 && !p.items.item_is_extra[item];
+    const uint32_t nmw = (p.vf.v_nstr[c] + 31) >> 5;
     const uint32_t Wp = (W + 3) & ~3u;
-    const uint32_t* M = p.mrows + (size_t)slice * DEDUP_MROWS;
-    const uint32_t* sout = p.slot_out + (size_t)slice * NS;
-    const uint64_t* sp = p.sorted_pair + (size_t)slice * NS;
+    const uint32_t* M = p.rs.mrows + (size_t)slice * DEDUP_MROWS;
+    const uint32_t* sout = p.rs.slot_out + (size_t)slice * NS;
+    const uint64_t* sp = p.rs.sorted_pair + (size_t)slice * NS;
 
     if (item == sib0 && tid == 0) {
-        const uint32_t pid = p.cluster_pattern[c];
-        if (pid < p.pool && p.pat_first_seen[pid] == p.cluster_first[c]) {
-            const uint32_t npres = p.cluster_npresab[c];
+        const uint32_t pid = p.out.cluster_pattern[c];
+        if (pid < p.pt.pool && p.pt.first_seen[pid] == p.out.cluster_first[c]) {
+            const uint32_t npres = p.cl.cluster_npresab[c];
             for (uint32_t w = 0; w < W; w++) {
-                p.pat_bits[(size_t)pid * W + w] = presab[w];
-                if (p.pat_nan) p.pat_nan[(size_t)pid * W + w] = 0;
+                p.pats.pat_bits[(size_t)pid * W + w] = presab[w];
+                if (p.pats.pat_nan) p.pats.pat_nan[(size_t)pid * W + w] = 0;
             }
-            p.pat_n[pid] = npres | 0x80000000u;
+            p.pats.pat_n[pid] = npres | 0x80000000u;
         }
     }
     // (through a lambda: called in place, the row loop below is scheduled differently and the kernel takes 58 VGPRs for 55)
-    auto nan_at = [&](uint32_t w) -> uint32_t { return nan_word(presab, nstr, nchunks, p.consider_missing, w); };
+    auto nan_at = [&](uint32_t w) -> uint32_t { return nan_word(presab, nstr, nchunks, p.opt.consider_missing, w); };
     if (expand) {
-        const uint32_t mw = min(p.v_nstr[c] * Wp, DEDUP_MROWS);
+        const uint32_t mw = min(p.vf.v_nstr[c] * Wp, DEDUP_MROWS);
         for (uint32_t i = tid; i < mw; i += blockDim.x) Ml[i] = M[i];
         __syncthreads();
     }
     if (wide) {
-        const uint32_t s0 = p.cluster_seg_off[c], s1 = p.cluster_seg_off[c + 1];
+        const uint32_t s0 = p.cl.cluster_seg_off[c], s1 = p.cl.cluster_seg_off[c + 1];
         for (uint32_t s = tid; s < s1 - s0; s += blockDim.x)
-            segd[s] = (uint16_t)((p.seg_distinct[s0 + s] << 5) | (p.seg_sample[s0 + s] & 31u));
+            segd[s] = (uint16_t)((p.cl.seg_distinct[s0 + s] << 5) | (p.cl.seg_sample[s0 + s] & 31u));
         for (uint32_t w = tid; w <= nchunks; w += blockDim.x)
-            wstart[w] = seg_lower_bound(p.seg_sample, s0, s1, w << 5) - s0;
+            wstart[w] = seg_lower_bound(p.cl.seg_sample, s0, s1, w << 5) - s0;
         if (lane == 0) mstage[wave][32] = 0;
         __syncthreads();
     }
@@ -4091,8 +4130,8 @@ __global__ __launch_bounds__(PR_THREADS) void pattern_rows_kernel(PatRowsParams 
     for (int dd = 1; dd < 64; dd <<= 1) sg_used = max(sg_used, (uint32_t)__shfl_xor(sg_used, dd));
     // entries = sorted positions, or (ranks by bitmap) the item's kept k-mers: (ordinal, slot) pairs from rows_kernel,
     // their output indices from emit_kernel
-    const bool sorted = !ranks_by_bitmap(mode, p.v_dense[c]);
-    const uint32_t* kres = p.kept_prefix + (size_t)slice * (NS + 1) + 1;
+    const bool sorted = !ranks_by_bitmap(mode, p.vf.v_dense[c]);
+    const uint32_t* kres = p.rs.kept_prefix + (size_t)slice * (NS + 1) + 1;
     const uint32_t total = sorted ? U : min(kres[-1], ns);
     const uint32_t stride = blockDim.x;
     const uint32_t rounds_total = (total + stride - 1) / stride;
@@ -4126,10 +4165,10 @@ __global__ __launch_bounds__(PR_THREADS) void pattern_rows_kernel(PatRowsParams 
 #pragma unroll
         for (uint32_t r = 0; r < PRR; r++) {
             const uint64_t o = obase + kb_[r];
-            ok_[r] = kb_[r] != 0xFFFFFFFFu && o < p.out_cap;
+            ok_[r] = kb_[r] != 0xFFFFFFFFu && o < p.out.out_cap;
             const uint64_t oc = ok_[r] ? o : 0;                  // (an arena holds at least one entry)
-            pid_[r] = p.out_pid[oc];                             // (unconditional: the loads of the four rounds go out together)
-            of_[r] = p.out_first[oc];
+            pid_[r] = p.out.out_pid[oc];                             // (unconditional: the loads of the four rounds go out together)
+            of_[r] = p.out.out_first[oc];
         }
 #pragma unroll
         for (uint32_t r = 0; r < PRR; r++) {
@@ -4137,10 +4176,10 @@ __global__ __launch_bounds__(PR_THREADS) void pattern_rows_kernel(PatRowsParams 
             if (!ok_[r]) pid_[r] = 0xFFFFFFFFu;
         }
 #pragma unroll
-        for (uint32_t r = 0; r < PRR; r++) pf_[r] = p.pat_first_seen[min(pid_[r], p.pool - 1)];
+        for (uint32_t r = 0; r < PRR; r++) pf_[r] = p.pt.first_seen[min(pid_[r], p.pt.pool - 1)];
 #pragma unroll
         for (uint32_t r = 0; r < PRR; r++) {
-            if (pid_[r] < p.pool && pf_[r] == of_[r]) {
+            if (pid_[r] < p.pt.pool && pf_[r] == of_[r]) {
                 const uint32_t at = atomicAdd(&l_count, 1u);
                 if (at < PR_LIST) { l_slot[at] = sl_[r]; l_pid[at] = pid_[r]; }
             }
@@ -4196,10 +4235,10 @@ __global__ __launch_bounds__(PR_THREADS) void pattern_rows_kernel(PatRowsParams 
                         v = cb[(size_t)w * NS + slot];
                     }
                 }
-                p.pat_bits[(size_t)pid * W + w] = v;
-                if (p.pat_nan) p.pat_nan[(size_t)pid * W + w] = nan_at(w);
+                p.pats.pat_bits[(size_t)pid * W + w] = v;
+                if (p.pats.pat_nan) p.pats.pat_nan[(size_t)pid * W + w] = nan_at(w);
             }
-            if (lane == 0) p.pat_n[pid] = nstr;
+            if (lane == 0) p.pats.pat_n[pid] = nstr;
         }
         __syncthreads();
     }
@@ -4288,13 +4327,14 @@ __device__ __forceinline__ void md5_block(uint32_t st[4], const uint32_t m[16]) 
 }
 
 struct Md5Params {
-    const uint32_t* pat_bits; const uint32_t* pat_nan; const uint32_t* pat_n;
+    PatternPool pats;
     uint8_t* pat_md5;
     const uint32_t* cluster_pattern;   // [n_clusters] the int pass: the clusters' own rows are the int64 rows
     uint32_t n_clusters;
     const uint32_t* range;   // device: {first id, one past the last id} of this launch, or null:
     uint32_t pid0, pid1, W;  // ... the range given here
 };
+PF_ARG_BLOCK(Md5Params);
 constexpr uint32_t MD5_THREADS = 256;
 
 // One lane per pattern, no LDS and no barriers: every lane reads its own row, four words (16 MD5 blocks) ahead of the
@@ -4320,11 +4360,11 @@ __global__ __launch_bounds__(MD5_THREADS) void md5_kernel(Md5Params p) {
         if (idx >= r1) continue;
         const uint32_t pid = FLOAT_ROWS ? idx : p.cluster_pattern[idx];
         if (!FLOAT_ROWS && (pid < p.pid0 || pid >= p.pid1)) continue;      // a row of an earlier batch (hashed then), or none
-        const uint32_t nk = p.pat_n[pid];
+        const uint32_t nk = p.pats.pat_n[pid];
         if (FLOAT_ROWS == ((nk >> 31) != 0)) continue;        // an int64 row is the int pass's, a float64 row the float pass's
         const uint32_t n = nk & 0x7FFFFFFFu;
-        const uint32_t* rb = p.pat_bits + (size_t)pid * W;
-        const uint32_t* rn = HAS_NAN ? p.pat_nan + (size_t)pid * W : nullptr;
+        const uint32_t* rb = p.pats.pat_bits + (size_t)pid * W;
+        const uint32_t* rn = HAS_NAN ? p.pats.pat_nan + (size_t)pid * W : nullptr;
         uint32_t st[4] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u};
         const uint64_t nbytes = (uint64_t)n * 8;
         const uint32_t full = n >> 3, rem = n & 7;            // whole 64-byte blocks = 8 elements each, and the rest
