@@ -18,6 +18,7 @@
 #include <condition_variable>
 #include <mutex>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <chrono>
 #include <cstdio>
@@ -32,10 +33,6 @@
 namespace {
 
 thread_local std::string g_err;
-
-struct Item {
-    uint32_t cluster, part, nparts, nslots, slice, sib0, nsib, extra_first, is_extra;
-};
 
 struct Arena {
     DevBuf key, pid, first;
@@ -72,22 +69,135 @@ struct PartModel {
     }
 };
 
-// host scratch of pf_submit, kept between calls (capacity persists: no allocation / page faults in steady state)
-struct SubmitScratch {
-    std::vector<Item> items;             // the work items of a pass
+// The owning groups of the submit path's device buffers.  Each states its members once besides their declaration (a table
+// or a list), sizes and releases them from that, and hands out the kernels' argument groups (pf_kernels.h) that point into
+// them.  A pf:: group is built at the launch that uses it and never kept across an ensure, which may move a buffer.
+// The scratch slices: what a work item (cluster x key partition) keeps while its sub-batch is in flight.
+struct Scratch {
+    DevBuf tab_key, tab_ord, chunkbits, chunkmask, slot_hash, sorted_pair, kept_prefix, bm4, bm2, mrows, slot_out, cmask_lo, cmask_hi;
+    struct Dims { uint64_t NS, KW, W; };  // table slots of a slice, key words, presence words: the context's
+    struct Slice { DevBuf Scratch::*buf; uint64_t per_slot, per_item; };   // bytes per table slot, and beside them per item
+    static std::array<Slice, 13> slices(uint64_t KW, uint64_t W) {
+        return {{{&Scratch::tab_key, 8 * KW, 0}, {&Scratch::tab_ord, 4, 0}, {&Scratch::chunkbits, 4 * W, 0}, {&Scratch::chunkmask, 0, 8 * 4},
+                 {&Scratch::slot_hash, 16, 0}, {&Scratch::sorted_pair, 8, 0}, {&Scratch::kept_prefix, 4, 4},
+                 {&Scratch::bm4, 0, pf::DENSE_WORDS_BIG * 16}, {&Scratch::bm2, 0, pf::DENSE_WORDS_BIG * 8}, {&Scratch::mrows, 0, pf::DEDUP_MROWS * 4},
+                 {&Scratch::slot_out, 4, 0}, {&Scratch::cmask_lo, 4, 0}, {&Scratch::cmask_hi, 4, 0}}};
+    }
+    // what max_items is sized by (28 bytes of margin: with chunkmask's 32 and kept_prefix's 4 the 64 it always had)
+    static uint64_t bytes_per_item(Dims d) {
+        uint64_t n = 28;
+        for (const Slice& s : slices(d.KW, d.W)) n += d.NS * s.per_slot + s.per_item;
+        return n;
+    }
+    int ensure(uint32_t items, Dims d) {  // (DevBuf::ensure: buffers that are large enough stay)
+        for (const Slice& s : slices(d.KW, d.W)) PFCHK((this->*s.buf).ensure(items * (d.NS * s.per_slot + s.per_item)));
+        return PF_OK;
+    }
+    void release() { for (const Slice& s : slices(0, 0)) (this->*s.buf).release(); }     // (which buffers, whatever their size)
+    pf::SlotDump slot_dump(uint32_t* item_count) const {       // (the key counts go beside the pass's items)
+        return pf::SlotDump{cmask_lo.as<uint32_t>(), cmask_hi.as<uint32_t>(), tab_key.as<uint64_t>(), tab_ord.as<uint32_t>(),
+                            chunkbits.as<uint32_t>(), chunkmask.as<uint32_t>(), item_count};
+    }
+    pf::RowScratch row_scratch(uint32_t* item_unique, uint32_t* item_kept) const {
+        return pf::RowScratch{slot_hash.as<uint4>(), sorted_pair.as<uint64_t>(), kept_prefix.as<uint32_t>(), bm4.as<uint4>(),
+                              bm2.as<uint2>(), mrows.as<uint32_t>(), slot_out.as<uint32_t>(), item_unique, item_kept};
+    }
+};
+// A host-planned pass: its work items by column, its work lists and the lists of its sub-batches as the host writes them
+// (capacity persists between calls: no allocation / page faults in steady state), each with its device view into the
+// staging block that one copy fills (staged_upload).
+struct Staged { std::vector<uint32_t> h; DevBuf d; };
+struct HostPass {
+    // compact = fused at all, binned = its cluster's windows are binned
+    enum Col { it_cluster, it_part, it_nparts, it_nslots, it_slice, it_sib0, it_nsib, it_extra_first, it_is_extra, it_compact, it_binned, N_COLS };
+    enum List { work_scan, work_extra, work_fin, work_fin2, work_fin3, work_fin5, work_rows, N_LISTS };   // of the sub-batches, concatenated
+    Staged col[N_COLS], list[N_LISTS];
+    Staged sub_cluster, sub_item0, sub_nitems;   // the general path's clusters, per sub-batch: cluster, first item, items
+    Staged bin_block;                    // the binned clusters: cluster | first item | partitions | first queue entry
+    std::vector<uint32_t> bin_cluster, bin_item0, bin_nparts, bin_base;   // ... its four stretches while they are built
     std::vector<uint8_t> fused;          // per item: 0 general path; 1 / 2 / 5 one item, fused small / large / huge class;
                                          // 3 the first of several partitions (fused large class), 4 the others
-    // the item columns that go up (Item's fields, plus compact = fused at all, binned = its cluster's windows are binned)
-    std::vector<uint32_t> it_cluster, it_part, it_nparts, it_nslots, it_slice, it_sib0, it_nsib, it_extra_first,
-        it_is_extra, it_compact, it_binned;
-    // the work lists of the pass's sub-batches, concatenated
-    std::vector<uint32_t> w_scan, w_extra, w_fin, w_fin2, w_fin3, w_fin5, w_rows;
-    // the general path's clusters, per sub-batch: cluster, first item, items
-    std::vector<uint32_t> sub_cluster, sub_item0, sub_nitems;
-    // the binned clusters: cluster, first item, partitions, first queue entry; the four as one upload block
-    std::vector<uint32_t> bin_cluster, bin_item0, bin_nparts, bin_base, bin_block;
-    std::vector<uint32_t> wide;          // a part's clusters for the wide dedup class
-    std::vector<uint32_t> count, plan;   // key counts read back for the key-partition estimate (host items, plan_kernel's)
+    DevBuf it_count, it_unique, it_kept; // [item] what the kernels count: keys in the table, k-mers, kept ones
+    size_t n_items() const { return fused.size(); }
+    void begin(size_t room) {            // room for so many items: push writes the columns by index, end cuts them to size
+        for (Staged& s : col) s.h.resize(room, 0);
+        for (Staged* s : {&sub_cluster, &sub_item0, &sub_nitems, &bin_block}) s->h.clear();
+        for (auto* v : {&bin_cluster, &bin_item0, &bin_nparts, &bin_base}) v->clear();
+        fused.clear(); fused.reserve(room);
+    }
+    void push(uint32_t cluster, uint32_t part, uint32_t nparts, uint32_t nslots, uint32_t slice, uint32_t sib0, uint32_t nsib,
+              uint32_t extra_first, uint32_t is_extra, uint8_t fuse, uint32_t binned) {
+        const uint32_t v[N_COLS] = {cluster, part, nparts, nslots, slice, sib0, nsib, extra_first, is_extra, fuse ? 1u : 0u, binned};
+        for (int k = 0; k < N_COLS; k++) col[k].h[fused.size()] = v[k];
+        fused.push_back(fuse);
+    }
+    void end() { for (Staged& s : col) s.h.resize(fused.size()); }
+    std::vector<Staged*> staged() {       // in the order they lie in the staging block
+        std::vector<Staged*> v = {&bin_block};
+        for (Staged& s : col) v.push_back(&s);
+        v.insert(v.end(), {&sub_cluster, &sub_item0, &sub_nitems});
+        for (Staged& s : list) v.push_back(&s);
+        return v;
+    }
+    pf::Items items() const {
+        auto p = [&](Col k) { return col[k].d.as<uint32_t>(); };
+        return pf::Items{p(it_cluster), p(it_part), p(it_nparts), p(it_nslots), p(it_slice), p(it_compact), p(it_binned),
+                         p(it_is_extra), p(it_extra_first), p(it_sib0), p(it_nsib)};
+    }
+};
+// Per batch: the scan view cluster_dedup_kernel builds and the per-cluster outputs.
+struct BatchBufs {
+    DevBuf cl_overflow, cl_kmer_off, cl_kmer_cnt, cl_unique, cl_pattern, cl_first, cl_rec, view_off, v_nseg, v_nstr, v_mode, v_dense;   // [C]
+    DevBuf v_word_off, v_len, v_sample, v_ord, v_bits, seg_distinct, extra_dense;       // [NSEG]; the last [n_extra]
+    DevBuf cursor, extra_off;            // sized apart: 64 bytes at pf_create; [C + 1] (+ 1) where the CSR is made
+    int ensure(uint32_t C, uint32_t NSEG, uint32_t n_extra) {
+        const size_t C1 = std::max(C, 1u), NSEG1 = std::max(NSEG, 1u), NEX1 = std::max(n_extra, 1u);
+        const std::pair<DevBuf*, size_t> bufs[] = {
+            {&cl_overflow, C1 * 4}, {&cl_kmer_off, C1 * 8}, {&cl_kmer_cnt, C1 * 4}, {&cl_unique, C1 * 4}, {&cl_pattern, C1 * 4},
+            {&cl_first, C1 * 8}, {&cl_rec, C1 * sizeof(pf::ClusterRec)}, {&v_word_off, NSEG1 * 8}, {&v_len, NSEG1 * 4},
+            {&v_sample, NSEG1 * 4}, {&v_ord, NSEG1 * 4}, {&v_bits, NSEG1 * 4}, {&view_off, C1 * 4}, {&seg_distinct, NSEG1 * 4},
+            {&v_nseg, C1 * 4}, {&v_nstr, C1 * 4}, {&v_mode, C1 * 4}, {&v_dense, C1 * 4}, {&extra_dense, NEX1 * 4}};
+        for (const auto& [buf, bytes] : bufs) PFCHK(buf->ensure(bytes));
+        return PF_OK;
+    }
+    pf::View view() const {              // (the plain entries: a launch adds its unit pool's)
+        pf::View v{};
+        v.plain = pf::ViewSegs{v_word_off.as<uint64_t>(), v_len.as<uint32_t>(), v_sample.as<uint32_t>(), v_ord.as<uint32_t>(),
+                               v_bits.as<uint32_t>()};
+        v.view_off = view_off.as<uint32_t>(); v.v_nseg = v_nseg.as<uint32_t>();
+        return v;
+    }
+    void dedup_outputs(pf::DedupParams& dp) const {    // what cluster_dedup_kernel writes, and the extra-row CSR it reads
+        dp.view = view(); dp.seg_distinct = seg_distinct.as<uint32_t>(); dp.extra_off = extra_off.as<uint32_t>();
+        dp.cl_overflow = cl_overflow.as<uint32_t>(); dp.cl_kmer_cnt = cl_kmer_cnt.as<uint32_t>(); dp.cl_unique = cl_unique.as<uint32_t>();
+        dp.cl_pattern = cl_pattern.as<uint32_t>(); dp.v_nstr = v_nstr.as<uint32_t>(); dp.v_mode = v_mode.as<uint32_t>();
+        dp.v_dense = v_dense.as<uint32_t>(); dp.extra_dense = extra_dense.as<uint32_t>();
+    }
+    pf::ViewFacts view_facts(const uint32_t* extra_bits) const {      // (the slow-path rows themselves are the caller's)
+        return pf::ViewFacts{v_nstr.as<uint32_t>(), v_mode.as<uint32_t>(), v_dense.as<uint32_t>(), cl_overflow.as<uint32_t>(),
+                             extra_off.as<uint32_t>(), extra_dense.as<uint32_t>(), extra_bits};
+    }
+    pf::Outputs outputs(const Arena& ar) const {   // (of the arena of the pass being launched)
+        return pf::Outputs{ar.key.as<uint64_t>(), ar.pid.as<uint32_t>(), ar.first.as<uint64_t>(), ar.base, ar.cap,
+                           cl_kmer_off.as<uint64_t>(), cl_kmer_cnt.as<uint32_t>(), cl_unique.as<uint32_t>(),
+                           cl_pattern.as<uint32_t>(), cl_first.as<uint64_t>(), cursor.as<uint64_t>()};
+    }
+};
+// The run-global pattern table (`cap` slots, a power of two) and the pool arrays indexed by pattern id (cap / 2 ids).
+struct PatternBufs {
+    DevBuf lo, val, first, bits, nan, n, md5, b64;   // (nan: only with consider_missing; b64: once a device renderer asked)
+    uint64_t cap = 0; uint32_t pool = 0;
+    pf::PatternPool pattern_pool() const { return pf::PatternPool{bits.as<uint32_t>(), nan.as<uint32_t>(), n.as<uint32_t>()}; }
+};
+// The caller's batch on the device (when it passes host pointers), and the per-batch gather lists
+struct CallerBufs {
+    DevBuf b_packed, b_seg_word_off, b_seg_len, b_seg_sample, b_seg_ord, b_cl_seg_off, b_cl_nstr, b_cl_npres, b_cl_presab,
+        b_cl_ordinal, b_extra_ord, b_extra_bits, b_seg_strand_off, b_literal, g_src_off, g_src_start, g_src_flags;
+};
+// host scratch of pf_submit besides the pass's (HostPass), kept between calls like it
+struct SubmitScratch {
+    // a part's clusters for the wide dedup class; key counts read back for the key-partition estimate (host items, plan_kernel's)
+    std::vector<uint32_t> wide, count, plan;
 };
 
 // kmers.tsv of target strains.  What the host renderer's measure pass leaves for its write pass, per sequence:
@@ -117,30 +227,24 @@ struct pf_ctx {
     uint32_t NS = 0, W = 0, max_items = 0;
     std::vector<uint32_t> maf_lo, maf_hi;
     DevBuf d_maf_lo, d_maf_hi;
-    // pattern table + pool
+    PatternBufs pats;              // pattern table + pool, its counters, and the kernels' view of both (sync_pattern_table)
+    DevBuf pt_counters;
     pf::PatternTable pt{};
-    DevBuf pt_lo, pt_val, pt_first, pt_counters, pat_bits, pat_nan, pat_n, pat_md5;
     PartModel part_model;
     uint64_t n_submits = 0;
     uint32_t n_patterns = 0;       // patterns allocated after the last submit
     uint32_t pid0 = 0;             // first pattern id of the last submit
-    // scratch slices
-    DevBuf tab_key, tab_ord, chunkbits, chunkmask, slot_hash, sorted_pair, kept_prefix;
-    // uploaded batch (when the caller passes host pointers)
-    DevBuf b_packed, b_seg_word_off, b_seg_len, b_seg_sample, b_seg_ord, b_cl_seg_off, b_cl_nstr, b_cl_npres,
-        b_cl_presab, b_cl_ordinal, b_extra_ord, b_extra_bits, b_seg_strand_off;
-    // per batch device arrays
-    DevBuf cl_rec, cl_overflow, cl_kmer_off, cl_kmer_cnt, cl_unique, cl_pattern, cl_first, cursor;
-    // scan view built by cluster_dedup_kernel
-    DevBuf v_word_off, v_len, v_sample, v_ord, seg_distinct, v_nseg, v_nstr, v_mode, v_dense, extra_off, extra_dense;
-    DevBuf bm4, bm2, mrows, slot_out, it_is_extra, cmask_lo, cmask_hi, it_compact;
+    Scratch scratch;                       // the scratch slices of max_items work items
+    Scratch::Dims dims() const { return {NS, (uint64_t)KW, W}; }
+    CallerBufs caller;
+    BatchBufs batch;
+    HostPass pass;                            // the host-planned pass being built or in flight
     DevBuf strand_bits, scan_desc, md5_list, wide_list;
-    DevBuf v_bits, view_off;
     // unit view (unit_class_kernel): one pool of view entries per part of a batch's first pass, and the list
     // {clusters, their places in the pool} that goes up with it
     struct UPool { DevBuf word_off, len, sample, ord, bits, list; PinBuf pin; };
-    DevBuf pat_b64, txt_dev, txt_meta;   // device-side rendering: base64 of every digest, the text, its per-row tables
-    uint32_t b64_done = 0;               // patterns whose base64 is in pat_b64
+    DevBuf txt_dev, txt_meta;              // device-side rendering (beside pats.b64): the text, its per-row tables
+    uint32_t b64_done = 0;               // patterns whose base64 is in pats.b64
     PinBuf txt_pins[2];                  // pinned host copies of the rendered text, used alternately so that a writer thread
                                          // may still be on the previous batch's
     int txt_slot = 0;
@@ -169,14 +273,12 @@ struct pf_ctx {
     pf_batch last{};                      // the last pf_submit's batch arrays as device pointers (valid until the next submit)
     uint32_t last_nseg = 0;
     uint64_t last_words = 0;              // words of last.packed: the batch's, or the buffer pf_submit_gather filled
-    DevBuf g_store, b_literal, g_src_off, g_src_start, g_src_flags;   // genomes resident in HBM + per-batch gather lists
+    DevBuf g_store;                       // genomes resident in HBM
     uint64_t g_words = 0;
     const pf_gather* pending_gather = nullptr;
     SubmitScratch hs;
     int n_cu = 256;
-    DevBuf it_binned, bin_lists, q_key, q_ord, q_bit, q_off;      // key-partition queues of binned clusters (bin_kernel)
-    DevBuf it_cluster, it_part, it_nparts, it_nslots, it_slice, it_sib0, it_nsib, it_extra_first, it_count,
-        it_unique, it_kept, work_scan, work_extra, work_fin, work_fin2, work_fin3, work_fin5, work_rows, sub_cluster, sub_item0, sub_nitems;
+    DevBuf q_key, q_ord, q_bit, q_off;    // key-partition queues of binned clusters (bin_kernel)
     std::vector<std::unique_ptr<Arena>> arenas;
     uint32_t n_passes = 0;                 // arenas the last pf_submit used (arenas[] itself only ever grows)
     DevBuf rp_order, rp_rlen, rp_rowoff;   // pf_render_pattern_rows: the id list, row lengths, row offsets
@@ -282,9 +384,9 @@ int fill_u64(pf_ctx* c, void* p, uint64_t v, uint64_t n) {
 }
 
 int reset_patterns(pf_ctx* c) {
-    PFCHK(fill_u64(c, c->pt_lo.p, pf::EMPTY64, c->pt.cap));
-    PFCHK(fill_u64(c, c->pt_val.p, pf::EMPTY64, c->pt.cap));
-    PFCHK(fill_u64(c, c->pt_first.p, pf::EMPTY64, c->pt.pool));
+    PFCHK(fill_u64(c, c->pats.lo.p, pf::EMPTY64, c->pats.cap));
+    PFCHK(fill_u64(c, c->pats.val.p, pf::EMPTY64, c->pats.cap));
+    PFCHK(fill_u64(c, c->pats.first.p, pf::EMPTY64, c->pats.pool));
     HIPCHK(hipMemsetAsync(c->pt_counters.p, 0, 16, c->stream));
     c->n_patterns = 0;
     c->pid0 = 0;
@@ -296,14 +398,14 @@ int reset_patterns(pf_ctx* c) {
 }
 
 // Upload many small uint32 arrays with ONE pinned-host -> device copy; each DevBuf becomes a view into stage_dev.
-int staged_upload(pf_ctx* c, std::vector<std::pair<DevBuf*, const std::vector<uint32_t>*>>& arrs) {
+int staged_upload(pf_ctx* c, const std::vector<Staged*>& arrs) {
     size_t total = 0;
     std::vector<size_t> off(arrs.size());
     for (size_t i = 0; i < arrs.size(); i++) {
         off[i] = total;
-        total += (std::max<size_t>(arrs[i].second->size(), 1) * 4 + 255) & ~(size_t)255;
+        total += (std::max<size_t>(arrs[i]->h.size(), 1) * 4 + 255) & ~(size_t)255;
     }
-    for (auto& a : arrs) if (!a.first->view) a.first->release();
+    for (Staged* a : arrs) if (!a->d.view) a->d.release();
     DevBuf& stage_dev = c->stage_devs[c->stage_slot];
     PinBuf& stage_pin = c->stage_pins[c->stage_slot];
     // several passes are queued without a host sync in between: the copy that last used this slot (two passes ago) has
@@ -312,23 +414,18 @@ int staged_upload(pf_ctx* c, std::vector<std::pair<DevBuf*, const std::vector<ui
     PFCHK(stage_dev.ensure(total));
     PFCHK(stage_pin.ensure(total));
     for (size_t i = 0; i < arrs.size(); i++) {
-        const auto& v = *arrs[i].second;
+        const auto& v = arrs[i]->h;
         if (!v.empty()) memcpy(stage_pin.as<char>() + off[i], v.data(), v.size() * 4);
-        arrs[i].first->p = (char*)stage_dev.p + off[i];
-        arrs[i].first->cap = 0;
-        arrs[i].first->view = true;
+        arrs[i]->d.p = (char*)stage_dev.p + off[i];
+        arrs[i]->d.cap = 0;
+        arrs[i]->d.view = true;
     }
     HIPCHK(hipMemcpyAsync(stage_dev.p, stage_pin.p, total, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->ev_stage[c->stage_slot], c->stream));
     return PF_OK;
 }
 
-// the run-global pattern table (`slots` = power of two) and the pool arrays indexed by pattern id (slots / 2 ids)
-struct PatternBufs {
-    DevBuf lo, val, first, bits, nan, n, md5, b64;
-    uint64_t cap = 0;
-    uint32_t pool = 0;
-};
+// a table of `slots` (a power of two) and its pool
 int alloc_pattern_bufs(pf_ctx* c, uint64_t slots, bool with_b64, PatternBufs& pb) {
     if (c->pt_slot_limit && slots > c->pt_slot_limit)
         return fail(PF_ERR_OOM, "pattern table of %llu slots refused (limit %llu set by pf_debug_limit_pattern_slots)",
@@ -346,23 +443,10 @@ int alloc_pattern_bufs(pf_ctx* c, uint64_t slots, bool with_b64, PatternBufs& pb
     if (with_b64) PFCHK(pb.b64.ensure(pool * 24));
     return PF_OK;
 }
-// the context takes the buffers over (its old ones, if any, are moved into `pb`, which frees them)
-void adopt_pattern_bufs(pf_ctx* c, PatternBufs& pb) {
-    std::swap(c->pt_lo, pb.lo); std::swap(c->pt_val, pb.val); std::swap(c->pt_first, pb.first);
-    std::swap(c->pat_bits, pb.bits); std::swap(c->pat_nan, pb.nan); std::swap(c->pat_n, pb.n);
-    std::swap(c->pat_md5, pb.md5); std::swap(c->pat_b64, pb.b64);
-    std::swap(c->pt.cap, pb.cap); std::swap(c->pt.pool, pb.pool);
-    c->pt.lo = c->pt_lo.as<uint64_t>();
-    c->pt.val = c->pt_val.as<uint64_t>();
-    c->pt.first_seen = c->pt_first.as<uint64_t>();
-}
-int alloc_patterns(pf_ctx* c, uint64_t slots) {
-    PatternBufs pb;
-    PFCHK(alloc_pattern_bufs(c, slots, false, pb));
-    PFCHK(c->pt_counters.ensure(16));
-    adopt_pattern_bufs(c, pb);
-    c->pt.counters = c->pt_counters.as<uint32_t>();
-    return PF_OK;
+// the kernels' view of the table, from its owner: after every change of c->pats
+void sync_pattern_table(pf_ctx* c) {
+    c->pt = pf::PatternTable{c->pats.lo.as<uint64_t>(), c->pats.val.as<uint64_t>(), c->pats.first.as<uint64_t>(),
+                             c->pt_counters.as<uint32_t>(), c->pats.cap, c->pats.pool};
 }
 
 // The reference's `patterns` is an unbounded set (panfeed.py:146-150): when a batch runs out of pattern ids (or
@@ -377,61 +461,45 @@ int grow_patterns(pf_ctx* c, uint64_t min_pool) {
     const uint32_t keep = c->n_patterns;            // ids of the batches that completed
     const size_t W = c->W;
     PatternBufs nb;
-    int rc = alloc_pattern_bufs(c, slots, c->pat_b64.p != nullptr, nb);
-    auto copy = [&](DevBuf& dst, DevBuf& src, size_t bytes) -> int {
+    int rc = alloc_pattern_bufs(c, slots, c->pats.b64.p != nullptr, nb);
+    auto copy = [&](DevBuf& dst, const DevBuf& src, size_t bytes) -> int {
         if (bytes && src.p) HIPCHK(hipMemcpyAsync(dst.p, src.p, bytes, hipMemcpyDeviceToDevice, c->stream));
         return PF_OK;
     };
     if (rc == PF_OK) rc = fill_u64(c, nb.lo.p, pf::EMPTY64, slots);
     if (rc == PF_OK) rc = fill_u64(c, nb.val.p, pf::EMPTY64, slots);
     if (rc == PF_OK) rc = fill_u64(c, nb.first.p, pf::EMPTY64, nb.pool);
-    if (rc == PF_OK) rc = copy(nb.first, c->pt_first, (size_t)keep * 8);
-    if (rc == PF_OK) rc = copy(nb.bits, c->pat_bits, (size_t)keep * W * 4);
-    if (rc == PF_OK && c->o.consider_missing) rc = copy(nb.nan, c->pat_nan, (size_t)keep * W * 4);
-    if (rc == PF_OK) rc = copy(nb.n, c->pat_n, (size_t)keep * 4);
-    if (rc == PF_OK) rc = copy(nb.md5, c->pat_md5, (size_t)keep * 16);
-    if (rc == PF_OK && nb.b64.p) rc = copy(nb.b64, c->pat_b64, (size_t)std::min(c->b64_done, keep) * 24);
+    const PatternBufs& ob = c->pats;
+    if (rc == PF_OK) rc = copy(nb.first, ob.first, (size_t)keep * 8);
+    if (rc == PF_OK) rc = copy(nb.bits, ob.bits, (size_t)keep * W * 4);
+    if (rc == PF_OK && c->o.consider_missing) rc = copy(nb.nan, ob.nan, (size_t)keep * W * 4);
+    if (rc == PF_OK) rc = copy(nb.n, ob.n, (size_t)keep * 4);
+    if (rc == PF_OK) rc = copy(nb.md5, ob.md5, (size_t)keep * 16);
+    if (rc == PF_OK && nb.b64.p) rc = copy(nb.b64, ob.b64, (size_t)std::min(c->b64_done, keep) * 24);
     if (rc == PF_OK) {
         pf::RehashParams rp{};
-        rp.old_lo = c->pt_lo.as<uint64_t>(); rp.old_val = c->pt_val.as<uint64_t>(); rp.old_cap = c->pt.cap;
+        rp.old_lo = ob.lo.as<uint64_t>(); rp.old_val = ob.val.as<uint64_t>(); rp.old_cap = ob.cap;
         rp.new_lo = nb.lo.as<uint64_t>(); rp.new_val = nb.val.as<uint64_t>(); rp.new_cap = slots; rp.keep_below = keep;
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((c->pt.cap + 255) / 256, 8192);
         hipLaunchKernelGGL(pf::pattern_rehash_kernel, dim3(blocks), dim3(256), 0, c->stream, rp);
         if (hipGetLastError() != hipSuccess) rc = fail(PF_ERR_HIP, "pattern_rehash_kernel launch failed");
     }
     if (rc == PF_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(PF_ERR_HIP, "growing the pattern table failed");
+    const uint32_t cnt[4] = {keep, 0, 0, 0};
     if (rc != PF_OK) {
         (void)hipStreamSynchronize(c->stream);       // nothing queued above may still touch nb's buffers when they go
         // the failed batch's additions are still in the old table: forget them, as the successful path does
-        const uint32_t cnt[4] = {keep, 0, 0, 0};
         (void)hipMemcpy(c->pt_counters.p, cnt, 16, hipMemcpyHostToDevice);
         return rc;
     }
-    adopt_pattern_bufs(c, nb);                       // nb now holds the old buffers
-    const uint32_t cnt[4] = {keep, 0, 0, 0};
+    std::swap(c->pats, nb);                          // nb now holds the old buffers, and frees them
+    sync_pattern_table(c);
     HIPCHK(hipMemcpy(c->pt_counters.p, cnt, 16, hipMemcpyHostToDevice));
     c->b64_done = std::min(c->b64_done, keep);
     c->n_grown++;
     return PF_OK;
 }
 
-// bytes of scratch one work item (cluster x key partition) keeps while its sub-batch is in flight
-uint64_t slice_bytes(const pf_ctx* c) {
-    return (uint64_t)c->NS * (8ull * c->KW + 4 + 4ull * c->W + 16 + 8 + 4 + 4 + 4 + 4) + (uint64_t)pf::DENSE_WORDS_BIG * 24 +
-           (uint64_t)pf::DEDUP_MROWS * 4 + 64;
-}
-// the scratch slices of `items` work items (DevBuf::ensure: buffers that are large enough stay)
-int alloc_scratch(pf_ctx* c, uint32_t items) {
-    const size_t NS = c->NS, S = items, W = c->W;
-    PFCHK(c->tab_key.ensure(S * NS * 8 * c->KW)); PFCHK(c->tab_ord.ensure(S * NS * 4));
-    PFCHK(c->chunkbits.ensure(S * NS * W * 4)); PFCHK(c->chunkmask.ensure(S * 8 * 4));
-    PFCHK(c->slot_hash.ensure(S * NS * 16)); PFCHK(c->sorted_pair.ensure(S * NS * 8));
-    PFCHK(c->kept_prefix.ensure(S * (NS + 1) * 4));
-    PFCHK(c->bm4.ensure(S * pf::DENSE_WORDS_BIG * 16)); PFCHK(c->bm2.ensure(S * pf::DENSE_WORDS_BIG * 8));
-    PFCHK(c->mrows.ensure(S * pf::DEDUP_MROWS * 4)); PFCHK(c->slot_out.ensure(S * NS * 4));
-    PFCHK(c->cmask_lo.ensure(S * NS * 4)); PFCHK(c->cmask_hi.ensure(S * NS * 4));
-    return PF_OK;
-}
 // A cluster asks for more work items than a sub-batch holds (a very divergent or very wide cluster; an overflow retry
 // multiplies its key partitions): the scratch is re-made for `need` items -- when that fits half of the device memory
 // that is free once the old scratch is gone -- instead of failing the run.  Nothing may be in flight: the caller's
@@ -440,20 +508,18 @@ int grow_scratch(pf_ctx* c, uint32_t need) {
     HIPCHK(hipStreamSynchronize(c->stream));
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t sb = slice_bytes(c);
+    const uint64_t sb = Scratch::bytes_per_item(c->dims());
     const uint64_t have = (uint64_t)c->max_items * sb;
     uint64_t want = std::max<uint64_t>(need, std::min<uint64_t>(2ull * c->max_items, 65536));
     if (want * sb > (free_b + have) / 2) want = need;
     if (want * sb > (free_b + have) / 2)
         return fail(PF_ERR_CAPACITY, "a cluster needs %u work items (%.1f GB of scratch); %.1f GB of device memory are free",
                     need, (double)need * sb / 1e9, (double)(free_b + have) / 1e9);
-    DevBuf* bufs[] = {&c->tab_key, &c->tab_ord, &c->chunkbits, &c->chunkmask, &c->slot_hash, &c->sorted_pair, &c->kept_prefix,
-                      &c->bm4, &c->bm2, &c->mrows, &c->slot_out, &c->cmask_lo, &c->cmask_hi};
-    for (DevBuf* b : bufs) b->release();          // (freed first: old and new need not fit side by side)
-    const int rc = alloc_scratch(c, (uint32_t)want);
+    c->scratch.release();                         // (freed first: old and new need not fit side by side)
+    const int rc = c->scratch.ensure((uint32_t)want, c->dims());
     if (rc != PF_OK) {                            // back to what it was; if even that fails the context is unusable
-        for (DevBuf* b : bufs) b->release();
-        if (alloc_scratch(c, c->max_items) != PF_OK) c->max_items = 0;
+        c->scratch.release();
+        if (c->scratch.ensure(c->max_items, c->dims()) != PF_OK) c->max_items = 0;
         return rc;
     }
     c->max_items = (uint32_t)want;
@@ -679,7 +745,7 @@ int pf_create(pf_ctx** out, int device, const pf_opts* o) {
         // work items of one launch = scratch slices resident at once; keep them within half of the free HBM
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b) {
-            const uint64_t fit = (free_b / 2) / slice_bytes(c);
+            const uint64_t fit = (free_b / 2) / Scratch::bytes_per_item(c->dims());
             if (c->max_items > fit) c->max_items = (uint32_t)std::max<uint64_t>(fit, 64);
         }
     }
@@ -708,9 +774,10 @@ int pf_create(pf_ctx** out, int device, const pf_opts* o) {
         uint64_t cap = o->pattern_capacity ? o->pattern_capacity : (1ull << 24);
         uint64_t p2 = 1024;
         while (p2 < cap) p2 <<= 1;
-        if (!guard(alloc_patterns(c, p2))) break;
+        if (!guard(alloc_pattern_bufs(c, p2, false, c->pats)) || !guard(c->pt_counters.ensure(16))) break;
+        sync_pattern_table(c);
         if (!guard(reset_patterns(c))) break;
-        if (!guard(c->cursor.ensure(64)) || !guard(alloc_scratch(c, c->max_items))) break;
+        if (!guard(c->batch.cursor.ensure(64)) || !guard(c->scratch.ensure(c->max_items, c->dims()))) break;
         e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) { rc = fail(PF_ERR_HIP, "pf_create sync: %s", hipGetErrorString(e)); break; }
     } while (0);
@@ -810,10 +877,10 @@ DPtrs dplan_ptrs(const pf_ctx::DPlan& plan) {
     const size_t n = plan.n;
     return DPtrs{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, b + 6 * n, b + 7 * n, b + 8 * n};
 }
-struct FinWork { const uint32_t* work; uint32_t n; };   // one class of the fused finish kernels in a launch
+struct FinWork { const uint32_t* work; uint32_t n; };   // a launch's stretch of a work list (one class of the fused finish kernels)
 // a host-planned pass: its sub-batches (one launch each) and their stretches of the work lists (off[s] to off[s + 1])
 struct Sub { uint32_t item0, nitems, cl0, ncl, pool, bin0, nbin; uint64_t q_total; };
-struct SubLists { uint32_t scan, extra, fin, fin2, fin3, fin5, rows; };
+struct SubLists { uint32_t at[HostPass::N_LISTS]; };     // by HostPass::List
 struct Pass { std::vector<Sub> subs; std::vector<SubLists> off; uint64_t arena_cap = 0; size_t NB = 0; };
 
 // What one submit_once call carries from stage to stage (what outlives the call is in pf_ctx).  The member functions
@@ -881,9 +948,9 @@ struct SubmitRun {
                     if (s > b->cluster_seg_off[i] && b->seg_sample[s] < b->seg_sample[s - 1])
                         return fail(PF_ERR_ARG, "segments of cluster %u are not sorted by sample", i);
                 }
-            if (!gth) PFCHK(upload(c, c->b_packed, b->packed, (size_t)b->n_words, &d.packed));
-            PFCHK(upload(c, c->b_seg_word_off, b->seg_word_off, NSEG, &d.seg_word_off));
-            PFCHK(upload(c, c->b_seg_len, b->seg_len, NSEG, &d.seg_len));
+            if (!gth) PFCHK(upload(c, c->caller.b_packed, b->packed, (size_t)b->n_words, &d.packed));
+            PFCHK(upload(c, c->caller.b_seg_word_off, b->seg_word_off, NSEG, &d.seg_word_off));
+            PFCHK(upload(c, c->caller.b_seg_len, b->seg_len, NSEG, &d.seg_len));
             if (gth) {
                 // the packed input is produced on the device: segments copied (or reverse-complemented) out of the
                 // resident genomes, plus the few the host packed itself (b->packed = the literal words)
@@ -898,33 +965,33 @@ struct SubmitRun {
                         return fail(PF_ERR_ARG, "segment %u: source range outside the resident genomes", s);
                     }
                 }
-                PFCHK(c->b_packed.ensure((size_t)std::max<uint64_t>(total_words, 4) * 8));
-                d.packed = c->b_packed.as<uint64_t>();
+                PFCHK(c->caller.b_packed.ensure((size_t)std::max<uint64_t>(total_words, 4) * 8));
+                d.packed = c->caller.b_packed.as<uint64_t>();
                 const uint64_t* lit; const uint64_t* so; const uint32_t* ss; const uint32_t* sf;
-                PFCHK(upload(c, c->b_literal, b->packed, (size_t)b->n_words, &lit));
-                PFCHK(upload(c, c->g_src_off, gth->src_off, NSEG, &so));
-                PFCHK(upload(c, c->g_src_start, gth->src_start, NSEG, &ss));
-                PFCHK(upload(c, c->g_src_flags, gth->src_flags, NSEG, &sf));
+                PFCHK(upload(c, c->caller.b_literal, b->packed, (size_t)b->n_words, &lit));
+                PFCHK(upload(c, c->caller.g_src_off, gth->src_off, NSEG, &so));
+                PFCHK(upload(c, c->caller.g_src_start, gth->src_start, NSEG, &ss));
+                PFCHK(upload(c, c->caller.g_src_flags, gth->src_flags, NSEG, &sf));
                 if (total_words >= 4)
-                    HIPCHK(hipMemsetAsync(c->b_packed.as<uint64_t>() + (total_words - 4), 0, 32, c->stream));
+                    HIPCHK(hipMemsetAsync(c->caller.b_packed.as<uint64_t>() + (total_words - 4), 0, 32, c->stream));
                 if (NSEG) {
                     pf::GatherParams gp{};
                     gp.store = c->g_store.as<uint64_t>(); gp.literal = lit; gp.src_off = so; gp.src_start = ss; gp.src_flags = sf;
-                    gp.seg_word_off = d.seg_word_off; gp.seg_len = d.seg_len; gp.packed = c->b_packed.as<uint64_t>(); gp.n_segs = NSEG;
+                    gp.seg_word_off = d.seg_word_off; gp.seg_len = d.seg_len; gp.packed = c->caller.b_packed.as<uint64_t>(); gp.n_segs = NSEG;
                     hipLaunchKernelGGL(pf::gather_segments_kernel, dim3((NSEG + 15) / 16), dim3(256), 0, c->stream, gp);
                     HIPCHK(hipGetLastError());
                 }
             }
-            PFCHK(upload(c, c->b_seg_sample, b->seg_sample, NSEG, &d.seg_sample));
-            PFCHK(upload(c, c->b_seg_ord, b->seg_ord_base, NSEG, &d.seg_ord_base));
-            PFCHK(upload(c, c->b_cl_seg_off, b->cluster_seg_off, (size_t)C + 1, &d.cluster_seg_off));
-            PFCHK(upload(c, c->b_cl_nstr, b->cluster_nstrains, C, &d.cluster_nstrains));
-            PFCHK(upload(c, c->b_cl_npres, b->cluster_npresab, C, &d.cluster_npresab));
-            PFCHK(upload(c, c->b_cl_presab, b->cluster_presab, (size_t)C * W, &d.cluster_presab));
-            PFCHK(upload(c, c->b_cl_ordinal, b->cluster_ordinal, C, &d.cluster_ordinal));
-            PFCHK(upload(c, c->b_extra_ord, b->extra_ord, b->n_extra, &d.extra_ord));
-            PFCHK(upload(c, c->b_extra_bits, b->extra_bits, (size_t)b->n_extra * W, &d.extra_bits));
-            if (b->seg_strand_off) PFCHK(upload(c, c->b_seg_strand_off, b->seg_strand_off, NSEG, &d.seg_strand_off));
+            PFCHK(upload(c, c->caller.b_seg_sample, b->seg_sample, NSEG, &d.seg_sample));
+            PFCHK(upload(c, c->caller.b_seg_ord, b->seg_ord_base, NSEG, &d.seg_ord_base));
+            PFCHK(upload(c, c->caller.b_cl_seg_off, b->cluster_seg_off, (size_t)C + 1, &d.cluster_seg_off));
+            PFCHK(upload(c, c->caller.b_cl_nstr, b->cluster_nstrains, C, &d.cluster_nstrains));
+            PFCHK(upload(c, c->caller.b_cl_npres, b->cluster_npresab, C, &d.cluster_npresab));
+            PFCHK(upload(c, c->caller.b_cl_presab, b->cluster_presab, (size_t)C * W, &d.cluster_presab));
+            PFCHK(upload(c, c->caller.b_cl_ordinal, b->cluster_ordinal, C, &d.cluster_ordinal));
+            PFCHK(upload(c, c->caller.b_extra_ord, b->extra_ord, b->n_extra, &d.extra_ord));
+            PFCHK(upload(c, c->caller.b_extra_bits, b->extra_bits, (size_t)b->n_extra * W, &d.extra_bits));
+            if (b->seg_strand_off) PFCHK(upload(c, c->caller.b_seg_strand_off, b->seg_strand_off, NSEG, &d.seg_strand_off));
             if (b->n_extra) h_extra_cluster.assign(b->extra_cluster, b->extra_cluster + b->n_extra);
         }
         // extras per cluster (CSR).  A batch that is in device memory already has its list checked and counted there
@@ -940,22 +1007,14 @@ struct SubmitRun {
             }
             for (uint32_t e = 0; e < b->n_extra; e++) ex_first[h_extra_cluster[e] + 1]++;
             for (uint32_t i = 0; i < C; i++) ex_first[i + 1] += ex_first[i];
-            PFCHK(upload_vec(c, c->extra_off, ex_first));
+            PFCHK(upload_vec(c, c->batch.extra_off, ex_first));
         }
         return PF_OK;
     }
     // ---- per batch outputs
     int ensure_batch_outputs() {
-        const size_t C1 = std::max(C, 1u), NSEG1 = std::max(NSEG, 1u), NEX1 = std::max(b->n_extra, 1u);
-        const std::pair<DevBuf*, size_t> bufs[] = {
-            {&c->cl_overflow, C1 * 4}, {&c->cl_kmer_off, C1 * 8}, {&c->cl_kmer_cnt, C1 * 4}, {&c->cl_unique, C1 * 4},
-            {&c->cl_pattern, C1 * 4}, {&c->cl_first, C1 * 8}, {&c->cl_rec, C1 * sizeof(pf::ClusterRec)},
-            {&c->v_word_off, NSEG1 * 8}, {&c->v_len, NSEG1 * 4}, {&c->v_sample, NSEG1 * 4}, {&c->v_ord, NSEG1 * 4},
-            {&c->v_bits, NSEG1 * 4}, {&c->view_off, C1 * 4}, {&c->seg_distinct, NSEG1 * 4}, {&c->v_nseg, C1 * 4},
-            {&c->v_nstr, C1 * 4}, {&c->v_mode, C1 * 4}, {&c->v_dense, C1 * 4}, {&c->extra_dense, NEX1 * 4}};
-        for (const auto& [buf, bytes] : bufs) PFCHK(buf->ensure(bytes));
-        // (cl_overflow / cl_kmer_cnt / cl_unique / cl_pattern get their start values from the dedup kernel)
-        HIPCHK(hipMemsetAsync(c->cursor.p, 0, 64, c->stream));
+        PFCHK(c->batch.ensure(C, NSEG, b->n_extra));   // (cl_overflow / cl_kmer_cnt / cl_unique / cl_pattern: start values from the dedup kernel)
+        HIPCHK(hipMemsetAsync(c->batch.cursor.p, 0, 64, c->stream));
         return PF_OK;
     }
     // ---- the device plan (plan_kernel) of part h: the simple clusters' work items laid out behind the part's dedup, a
@@ -970,7 +1029,7 @@ struct SubmitRun {
         PFCHK(plan.pin_out.ensure(64, true));
         const DPtrs q = dplan_ptrs(plan);
         pf::PlanParams pp{};
-        pp.rec = c->cl_rec.as<pf::ClusterRec>(); pp.plan_room = c->plan_room.as<uint32_t>(); pp.plan_arena = c->plan_arena.as<uint32_t>();
+        pp.rec = c->batch.cl_rec.as<pf::ClusterRec>(); pp.plan_room = c->plan_room.as<uint32_t>(); pp.plan_arena = c->plan_arena.as<uint32_t>();
         pp.c0 = c0; pp.c1 = c1; pp.NS = NS; pp.max_items = c->max_items;
         pp.it_cluster = q.it_cluster; pp.it_nslots = q.it_nslots; pp.w_scan = q.w_scan; pp.w_fin = q.w_fin; pp.w_fin2 = q.w_fin2;
         pp.w_fin5 = q.w_fin5; pp.unit_cluster = q.unit_cluster; pp.unit_base = q.unit_base; pp.blk = q.blk;
@@ -991,15 +1050,20 @@ struct SubmitRun {
             hipLaunchKernelGGL(pf::cluster_dedup_kernel<pf::DedupSmall>, dim3(n), dim3(pf::DEDUP_THREADS), 0, c->stream, dp);
             HIPCHK(hipGetLastError());
             PFCHK(mark_end(c));
-            hipLaunchKernelGGL(pf::cluster_ninst_kernel, dim3((n + 3) / 4), dim3(256), 0, c->stream, d.cluster_seg_off,
-                               d.seg_len, c->v_len.as<uint32_t>(), c->v_nseg.as<uint32_t>(), c->o.klength, c0, c1,
-                               (const uint32_t*)nullptr,
-                               c->v_mode.as<uint32_t>(), c->v_dense.as<uint32_t>(), c->v_nstr.as<uint32_t>(), c->cl_rec.as<pf::ClusterRec>(), pcls);
-            HIPCHK(hipGetLastError());
+            PFCHK(launch_ninst(c0, n, nullptr, pcls));
             if (use_plan) PFCHK(launch_plan(h, c0, c1));
-            HIPCHK(hipMemcpyAsync(rec + c0, c->cl_rec.as<pf::ClusterRec>() + c0, (size_t)n * sizeof(pf::ClusterRec), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(rec + c0, c->batch.cl_rec.as<pf::ClusterRec>() + c0, (size_t)n * sizeof(pf::ClusterRec), hipMemcpyDeviceToHost, c->stream));
         }
         HIPCHK(hipEventRecord(c->ev_part[h], c->stream));
+        return PF_OK;
+    }
+    // what the host (and plan_kernel, by `cls`) needs of the dedup pass, a record per cluster: `count` from `first` on, or `list`'s
+    int launch_ninst(uint32_t first, uint32_t count, const uint32_t* list, const pf::PlanClassify& cls) {
+        const pf::View v = view(nullptr); const pf::ViewFacts vf = view_facts();
+        hipLaunchKernelGGL(pf::cluster_ninst_kernel, dim3((count + 3) / 4), dim3(256), 0, c->stream, d.cluster_seg_off, d.seg_len,
+                           v.plain.len, v.v_nseg, c->o.klength, first, first + count, list, vf.v_mode, vf.v_dense, vf.v_nstr,
+                           c->batch.cl_rec.as<pf::ClusterRec>(), cls);
+        HIPCHK(hipGetLastError());
         return PF_OK;
     }
     // ---- identical segments -> scan view (mode 1) or the caller's list as it is (mode 0); then the strand bits
@@ -1015,8 +1079,8 @@ struct SubmitRun {
         rec = c->pin_dedup.as<pf::ClusterRec>();
         h_exfirst = reinterpret_cast<uint32_t*>(rec + C8);
         if (ex_on_device) {
-            PFCHK(c->extra_off.ensure(((size_t)C + 2) * 4));
-            uint32_t* exo = c->extra_off.as<uint32_t>();
+            PFCHK(c->batch.extra_off.ensure(((size_t)C + 2) * 4));
+            uint32_t* exo = c->batch.extra_off.as<uint32_t>();
             HIPCHK(hipMemsetAsync(exo + C + 1, 0, 4, c->stream));
             hipLaunchKernelGGL(pf::extra_csr_kernel, dim3(std::min<uint32_t>((std::max(C + 1, b->n_extra) + 255) / 256, 2048u)), dim3(256), 0,
                                c->stream, b->extra_cluster, b->n_extra, C, exo, exo + C + 1);
@@ -1033,16 +1097,9 @@ struct SubmitRun {
             dp.packed = d.packed; dp.seg_word_off = d.seg_word_off; dp.seg_len = d.seg_len;
             dp.seg_sample = d.seg_sample; dp.seg_ord_base = d.seg_ord_base;
             dp.cluster_seg_off = d.cluster_seg_off; dp.cluster_nstrains = d.cluster_nstrains;
-            dp.extra_off = c->extra_off.as<uint32_t>(); dp.extra_ord = d.extra_ord;
-            dp.view = view(nullptr);
-            dp.seg_distinct = c->seg_distinct.as<uint32_t>();
-            dp.cl_overflow = c->cl_overflow.as<uint32_t>(); dp.cl_kmer_cnt = c->cl_kmer_cnt.as<uint32_t>();
-            dp.cl_unique = c->cl_unique.as<uint32_t>(); dp.cl_pattern = c->cl_pattern.as<uint32_t>();
-            dp.v_nstr = c->v_nstr.as<uint32_t>();
-            dp.v_mode = c->v_mode.as<uint32_t>(); dp.v_dense = c->v_dense.as<uint32_t>();
-            dp.extra_dense = c->extra_dense.as<uint32_t>();
-            dp.k = c->o.klength; dp.W = W; dp.canon = c->o.canon;
-            dp.enable = (c->o.flags & PF_FLAG_NO_DEDUP) ? 0u : 1u;
+            dp.extra_ord = d.extra_ord;
+            c->batch.dedup_outputs(dp);
+            dp.k = c->o.klength; dp.W = W; dp.canon = c->o.canon; dp.enable = (c->o.flags & PF_FLAG_NO_DEDUP) ? 0u : 1u;
         }
         // ---- the device plan: the estimate's learned line is what this context knew when the batch came in (the host's
         // own estimate for the rest of the part reads the same sums: they change at the end of a submit only)
@@ -1061,7 +1118,7 @@ struct SubmitRun {
             }
             PFCHK(c->plan_room.ensure((size_t)C * 4));
             PFCHK(c->plan_arena.ensure((size_t)C * 4));
-            pcls.extra_off = c->extra_off.as<uint32_t>(); pcls.plan_room = c->plan_room.as<uint32_t>(); pcls.plan_arena = c->plan_arena.as<uint32_t>();
+            pcls.extra_off = c->batch.extra_off.as<uint32_t>(); pcls.plan_room = c->plan_room.as<uint32_t>(); pcls.plan_arena = c->plan_arena.as<uint32_t>();
             pcls.mult = c->o.canon ? 1u : 2u; pcls.NS = NS; pcls.W = W; pcls.unit_view = (c->o.flags & PF_FLAG_NO_UNIT_DEDUP) ? 0u : 1u;
             pcls.reg_ready = fit.ready ? 1u : 0u; pcls.share = share; pcls.reg_a = fit.a; pcls.reg_b = fit.b; pcls.reg_half_sd = fit.half_sd;
         }
@@ -1103,13 +1160,8 @@ struct SubmitRun {
         hipLaunchKernelGGL(pf::cluster_dedup_kernel<pf::DedupWide>, dim3(nw), dim3(pf::DEDUP_THREADS), 0, c->stream, dw);
         HIPCHK(hipGetLastError());
         PFCHK(mark_end(c));
-        hipLaunchKernelGGL(pf::cluster_ninst_kernel, dim3((nw + 3) / 4), dim3(256), 0, c->stream, d.cluster_seg_off,
-                           d.seg_len, c->v_len.as<uint32_t>(), c->v_nseg.as<uint32_t>(), c->o.klength, 0u, nw,
-                           c->wide_list.as<uint32_t>(),
-                           c->v_mode.as<uint32_t>(), c->v_dense.as<uint32_t>(), c->v_nstr.as<uint32_t>(), c->cl_rec.as<pf::ClusterRec>(),
-                           pf::PlanClassify{});        // (the wide class's clusters are the host's: no plan bits)
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(rec + c0, c->cl_rec.as<pf::ClusterRec>() + c0, (size_t)(c1 - c0) * sizeof(pf::ClusterRec), hipMemcpyDeviceToHost, c->stream));
+        PFCHK(launch_ninst(0, nw, c->wide_list.as<uint32_t>(), pf::PlanClassify{}));   // (the wide class's clusters are the host's: no plan bits)
+        HIPCHK(hipMemcpyAsync(rec + c0, c->batch.cl_rec.as<pf::ClusterRec>() + c0, (size_t)(c1 - c0) * sizeof(pf::ClusterRec), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         c->timing.n_wide_clusters += nw;
         return PF_OK;
@@ -1132,7 +1184,7 @@ struct SubmitRun {
             HIPCHK(hipMemcpyAsync(up.list.p, up.pin.p, (size_t)nu * 8, hipMemcpyHostToDevice, c->stream));
             q.list_cluster = up.list.as<uint32_t>(); q.list_base = up.list.as<uint32_t>() + nu;
         }
-        q.packed = d.packed; q.cluster_seg_off = d.cluster_seg_off; q.v_nstr = c->v_nstr.as<uint32_t>();
+        q.packed = d.packed; q.cluster_seg_off = d.cluster_seg_off; q.v_nstr = c->batch.v_nstr.as<uint32_t>();
         q.view = view(&up); q.k = c->o.klength; q.tmp_off = (uint32_t)R;
         PFCHK(mark_begin(c, TimeCat::dedup));
         if (nsmall) {
@@ -1155,52 +1207,26 @@ struct SubmitRun {
         PFCHK(mark_end(c));
         return PF_OK;
     }
-    // ---- the kernels' argument groups (pf_kernels.h), one builder each.  A group is built at the launch that uses it and
-    // never kept across a DevBuf::ensure, which may move a buffer (q_key, the arenas, the unit pools).
+    // ---- the kernels' argument groups (pf_kernels.h): the owning groups' own with what this batch adds, built at the launch
+    // that uses them and never kept across a DevBuf::ensure, which may move a buffer (q_key, the arenas, the unit pools).
     pf::CallerSegs caller_segs() const {
-        return pf::CallerSegs{d.cluster_seg_off, d.seg_sample, c->seg_distinct.as<uint32_t>(), d.cluster_nstrains,
+        return pf::CallerSegs{d.cluster_seg_off, d.seg_sample, c->batch.seg_distinct.as<uint32_t>(), d.cluster_nstrains,
                               d.cluster_npresab, d.cluster_presab, d.cluster_ordinal};
     }
     pf::View view(const pf_ctx::UPool* up) const {     // (the dedup pass has no pool yet)
-        pf::View v{};
-        v.plain = pf::ViewSegs{c->v_word_off.as<uint64_t>(), c->v_len.as<uint32_t>(), c->v_sample.as<uint32_t>(),
-                               c->v_ord.as<uint32_t>(), c->v_bits.as<uint32_t>()};
+        pf::View v = c->batch.view();
         if (up) v.pool = pf::ViewSegs{up->word_off.as<uint64_t>(), up->len.as<uint32_t>(), up->sample.as<uint32_t>(),
                                       up->ord.as<uint32_t>(), up->bits.as<uint32_t>()};
-        v.view_off = c->view_off.as<uint32_t>(); v.v_nseg = c->v_nseg.as<uint32_t>();
         return v;
     }
-    pf::ViewFacts view_facts() const {
-        return pf::ViewFacts{c->v_nstr.as<uint32_t>(), c->v_mode.as<uint32_t>(), c->v_dense.as<uint32_t>(), c->cl_overflow.as<uint32_t>(),
-                             c->extra_off.as<uint32_t>(), c->extra_dense.as<uint32_t>(), d.extra_bits};
-    }
-    // a host-planned pass's items (the staged upload) ...
-    pf::Items host_items() const {
-        return pf::Items{c->it_cluster.as<uint32_t>(), c->it_part.as<uint32_t>(), c->it_nparts.as<uint32_t>(), c->it_nslots.as<uint32_t>(),
-                         c->it_slice.as<uint32_t>(), c->it_compact.as<uint32_t>(), c->it_binned.as<uint32_t>(), c->it_is_extra.as<uint32_t>(),
-                         c->it_extra_first.as<uint32_t>(), c->it_sib0.as<uint32_t>(), c->it_nsib.as<uint32_t>()};
-    }
-    // ... and plan_kernel's, all "one partition, own slice, compact, nothing else": three constant arrays stand in
+    pf::ViewFacts view_facts() const { return c->batch.view_facts(d.extra_bits); }
+    pf::Outputs outputs() const { return c->batch.outputs(*ar); }
+    pf::SlotDump slot_dump(uint32_t* item_count) const { return c->scratch.slot_dump(item_count); }
+    pf::RowScratch row_scratch() const { return c->scratch.row_scratch(c->pass.it_unique.as<uint32_t>(), c->pass.it_kept.as<uint32_t>()); }
+    pf::PatternPool pattern_pool() const { return c->pats.pattern_pool(); }
+    // plan_kernel's items (the host's: HostPass::items()), all "one partition, own slice, compact, nothing else": constant arrays stand in
     static pf::Items planned_items(const uint32_t* cluster, const uint32_t* nslots, const uint32_t* zeros, const uint32_t* ones, const uint32_t* iota) {
         return pf::Items{cluster, zeros, ones, nslots, iota, ones, zeros, zeros, zeros, iota, ones};
-    }
-    pf::SlotDump slot_dump(uint32_t* item_count) const {       // (the key counts go beside the pass's items)
-        return pf::SlotDump{c->cmask_lo.as<uint32_t>(), c->cmask_hi.as<uint32_t>(), c->tab_key.as<uint64_t>(), c->tab_ord.as<uint32_t>(),
-                            c->chunkbits.as<uint32_t>(), c->chunkmask.as<uint32_t>(), item_count};
-    }
-    pf::RowScratch row_scratch() const {
-        return pf::RowScratch{c->slot_hash.as<uint4>(), c->sorted_pair.as<uint64_t>(), c->kept_prefix.as<uint32_t>(), c->bm4.as<uint4>(),
-                              c->bm2.as<uint2>(), c->mrows.as<uint32_t>(), c->slot_out.as<uint32_t>(), c->it_unique.as<uint32_t>(),
-                              c->it_kept.as<uint32_t>()};
-    }
-    pf::Outputs outputs() const {                              // (of the arena of the pass being launched)
-        return pf::Outputs{ar->key.as<uint64_t>(), ar->pid.as<uint32_t>(), ar->first.as<uint64_t>(), ar->base, ar->cap,
-                           c->cl_kmer_off.as<uint64_t>(), c->cl_kmer_cnt.as<uint32_t>(), c->cl_unique.as<uint32_t>(),
-                           c->cl_pattern.as<uint32_t>(), c->cl_first.as<uint64_t>(), c->cursor.as<uint64_t>()};
-    }
-    pf::PatternPool pattern_pool() const {
-        return pf::PatternPool{c->pat_bits.as<uint32_t>(), c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr,
-                               c->pat_n.as<uint32_t>()};
     }
     pf::RowOpts row_opts() const {
         return pf::RowOpts{c->d_maf_lo.as<uint32_t>(), c->d_maf_hi.as<uint32_t>(), W, NS, KW,
@@ -1280,13 +1306,13 @@ struct SubmitRun {
     // the cursor's next free index restarts at the arena's base (a host-planned pass queues its item upload first)
     int upload_cursor_start() {
         c->pin_small.as<uint64_t>()[arena_i & 15] = arena_base;
-        HIPCHK(hipMemcpyAsync(c->cursor.p, c->pin_small.as<uint64_t>() + (arena_i & 15), 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->batch.cursor.p, c->pin_small.as<uint64_t>() + (arena_i & 15), 8, hipMemcpyHostToDevice, c->stream));
         return PF_OK;
     }
     // a pass not waited for: its cursor comes back with the last pass's results
     int defer_pass() {
         const uint32_t pin = 16 + (arena_i & 31);
-        HIPCHK(hipMemcpyAsync(c->pin_small.as<uint64_t>() + pin, c->cursor.p, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->pin_small.as<uint64_t>() + pin, c->batch.cursor.p, 8, hipMemcpyDeviceToHost, c->stream));
         deferred.push_back(Deferred{ar, pin});
         arena_base += ar->cap;
         arena_i++;
@@ -1417,13 +1443,11 @@ struct SubmitRun {
     }
     // ---- items of this pass: the todo clusters' key partitions and extra-row items, cut into sub-batches
     int build_items(Pass& ps) {
-        SubmitScratch& hs = c->hs;
+        HostPass& hpass = c->pass;
         const uint32_t lim_full = pf::insert_limit(NS);
-        std::vector<Item>& items = hs.items;
-        items.clear(); hs.fused.clear();
-        items.reserve(todo.size() + 64); hs.fused.reserve(todo.size() + 64);
-        hs.it_binned.clear(); hs.bin_cluster.clear(); hs.bin_item0.clear(); hs.bin_nparts.clear(); hs.bin_base.clear();
-        hs.sub_cluster.clear(); hs.sub_item0.clear(); hs.sub_nitems.clear();
+        size_t room = 0;                   // (an item per key partition, and at most the slow-path items of the general path)
+        for (uint32_t ci : todo) room += nparts[ci] + (ex_first[ci + 1] - ex_first[ci] + lim_full - 1) / lim_full;
+        hpass.begin(room);
         Sub cur{0, 0, 0, 0, todo.empty() ? 0u : pool_of(todo[0]), 0, 0, 0};
         for (uint32_t ci : todo) {
             const uint32_t np = nparts[ci];
@@ -1459,71 +1483,56 @@ struct SubmitRun {
             if (cur.nitems + nit > c->max_items || (cur.nitems && pool_of(ci) != cur.pool) ||
                 (binned && cur.q_total + qn > BIN_MAX_ENTRIES)) {
                 ps.subs.push_back(cur);
-                cur = Sub{(uint32_t)items.size(), 0, (uint32_t)hs.sub_cluster.size(), 0, pool_of(ci), (uint32_t)hs.bin_cluster.size(), 0, 0};
+                cur = Sub{(uint32_t)hpass.n_items(), 0, (uint32_t)hpass.sub_cluster.h.size(), 0, pool_of(ci), (uint32_t)hpass.bin_cluster.size(), 0, 0};
             }
             if (!cur.nitems) cur.pool = pool_of(ci);
-            const uint32_t sib0 = (uint32_t)items.size();
+            const uint32_t sib0 = (uint32_t)hpass.n_items();
             // table size: a cluster that cannot overflow a small table gets one (less flush traffic)
             uint32_t ns = NS;
             const uint64_t inst = rec[ci].vinst * mult;
             if (np == 1 && NS > 4096 + pf::INSERT_SLACK && inst <= pf::insert_limit(4096)) ns = 4096;
             else if (np == 1 && NS > 6144 + pf::INSERT_SLACK && inst <= pf::insert_limit(6144)) ns = 6144;
-            for (uint32_t q = 0; q < np; q++) {
-                items.push_back(Item{ci, q, np, ns, cur.nitems + q, sib0, nit, 0, 0});
-                hs.fused.push_back(fused == 3 && q > 0 ? 4 : fused);
-            }
-            hs.it_binned.resize(items.size() + nex_items, 0);
+            for (uint32_t q = 0; q < np; q++)
+                hpass.push(ci, q, np, ns, cur.nitems + q, sib0, nit, 0, 0, fused == 3 && q > 0 ? 4 : fused, binned ? 1u : 0u);
             if (binned) {
-                for (uint32_t q = 0; q < np; q++) hs.it_binned[sib0 + q] = 1;
-                hs.bin_cluster.push_back(ci); hs.bin_item0.push_back(sib0); hs.bin_nparts.push_back(np);
-                hs.bin_base.push_back((uint32_t)cur.q_total);
+                hpass.bin_cluster.push_back(ci); hpass.bin_item0.push_back(sib0); hpass.bin_nparts.push_back(np);
+                hpass.bin_base.push_back((uint32_t)cur.q_total);
                 cur.q_total += qn; cur.nbin++;
                 c->timing.n_binned_clusters++;
             }
             for (uint32_t q = 0; q < nex_items; q++) {
                 const uint32_t first = ex_first[ci] + q * lim_full;
                 const uint32_t cnt = std::min(lim_full, ex_first[ci + 1] - first);
-                items.push_back(Item{ci, 0, 1, cnt, cur.nitems + np + q, sib0, nit, first, 1});
-                hs.fused.push_back(0);
+                hpass.push(ci, 0, 1, cnt, cur.nitems + np + q, sib0, nit, first, 1, 0, 0);
             }
             for (uint32_t q = 0; q < np; q++) ps.arena_cap += std::min<uint64_t>(pf::insert_limit(ns), inst);
             ps.arena_cap += nex;
             if (!fused) {
-                hs.sub_cluster.push_back(ci);
-                hs.sub_item0.push_back(sib0);
-                hs.sub_nitems.push_back(nit);
+                hpass.sub_cluster.h.push_back(ci); hpass.sub_item0.h.push_back(sib0); hpass.sub_nitems.h.push_back(nit);
                 cur.ncl++;
             }
             cur.nitems += nit;
             c->cluster_arena[ci] = arena_i;
         }
         if (cur.nitems) ps.subs.push_back(cur);
-        lap("  items");
+        hpass.end(); lap("  items");
         return PF_OK;
     }
-    // ---- item arrays and work lists of this pass, up in one staged copy
+    // ---- the work lists of this pass; items and lists up in one staged copy
     int build_work_lists(Pass& ps) {
-        SubmitScratch& hs = c->hs;
-        const std::vector<Item>& items = hs.items;
-        const size_t NI = items.size();
-        for (auto* v : {&hs.it_cluster, &hs.it_part, &hs.it_nparts, &hs.it_nslots, &hs.it_slice, &hs.it_sib0, &hs.it_nsib,
-                        &hs.it_extra_first, &hs.it_is_extra, &hs.it_compact})
-            v->resize(NI);
-        hs.it_binned.resize(NI, 0);
-        for (auto* v : {&hs.w_scan, &hs.w_extra, &hs.w_fin, &hs.w_fin2, &hs.w_fin3, &hs.w_rows, &hs.w_fin5}) { v->clear(); v->reserve(NI); }
-        for (size_t i = 0; i < NI; i++) {
-            hs.it_cluster[i] = items[i].cluster; hs.it_part[i] = items[i].part; hs.it_nparts[i] = items[i].nparts;
-            hs.it_nslots[i] = items[i].nslots; hs.it_slice[i] = items[i].slice; hs.it_sib0[i] = items[i].sib0;
-            hs.it_nsib[i] = items[i].nsib; hs.it_extra_first[i] = items[i].extra_first; hs.it_is_extra[i] = items[i].is_extra;
-            hs.it_compact[i] = hs.fused[i] ? 1 : 0;
-        }
-        lap("  arena + item columns");
-        for (DevBuf* v : {&c->it_count, &c->it_unique, &c->it_kept}) PFCHK(v->ensure(std::max<size_t>(NI, 1) * 4));
+        HostPass& hpass = c->pass;
+        const size_t NI = hpass.n_items();
+        const uint32_t* const it_cl = hpass.col[hpass.it_cluster].h.data();
+        const uint32_t* const it_extra = hpass.col[hpass.it_is_extra].h.data();
+        for (Staged& l : hpass.list) { l.h.clear(); l.h.reserve(NI); }
+        auto list = [&](HostPass::List l) -> std::vector<uint32_t>& { return hpass.list[l].h; };
+        lap("  arena");
+        for (DevBuf* v : {&hpass.it_count, &hpass.it_unique, &hpass.it_kept}) PFCHK(v->ensure(std::max<size_t>(NI, 1) * 4));
         // work lists per sub-batch, concatenated; heaviest items first inside each launch (the grid then drains evenly):
         // a coarse O(n) order by log2(scan instances) is enough
-        ps.off.assign(ps.subs.size() + 1, SubLists{0, 0, 0, 0, 0, 0, 0});
+        ps.off.assign(ps.subs.size() + 1, SubLists{});
         auto wclass = [&](uint32_t it) -> int {
-            const uint64_t w = rec[items[it].cluster].vinst;
+            const uint64_t w = rec[it_cl[it]].vinst;
             return w ? 63 - __builtin_clzll(w) : 0;
         };
         std::vector<uint32_t> tmp_scan, tmp_fin, tmp_fin2;
@@ -1542,79 +1551,71 @@ struct SubmitRun {
         };
         for (size_t s = 0; s < ps.subs.size(); s++) {
             for (uint32_t i = ps.subs[s].item0; i < ps.subs[s].item0 + ps.subs[s].nitems; i++) {
-                if (items[i].is_extra) hs.w_extra.push_back(i); else tmp_scan.push_back(i);
-                if (hs.fused[i] == 1) tmp_fin.push_back(i);
-                else if (hs.fused[i] == 2) tmp_fin2.push_back(i);
-                else if (hs.fused[i] == 3) hs.w_fin3.push_back(i);
-                else if (hs.fused[i] == 5) hs.w_fin5.push_back(i);
-                else if (hs.fused[i] == 0) hs.w_rows.push_back(i);
+                if (it_extra[i]) list(hpass.work_extra).push_back(i); else tmp_scan.push_back(i);
+                if (hpass.fused[i] == 1) tmp_fin.push_back(i);
+                else if (hpass.fused[i] == 2) tmp_fin2.push_back(i);
+                else if (hpass.fused[i] == 3) list(hpass.work_fin3).push_back(i);
+                else if (hpass.fused[i] == 5) list(hpass.work_fin5).push_back(i);
+                else if (hpass.fused[i] == 0) list(hpass.work_rows).push_back(i);
             }
-            append_by_weight(tmp_scan, hs.w_scan);
-            append_by_weight(tmp_fin, hs.w_fin);
-            append_by_weight(tmp_fin2, hs.w_fin2);
-            ps.off[s + 1] = SubLists{(uint32_t)hs.w_scan.size(), (uint32_t)hs.w_extra.size(), (uint32_t)hs.w_fin.size(),
-                                     (uint32_t)hs.w_fin2.size(), (uint32_t)hs.w_fin3.size(), (uint32_t)hs.w_fin5.size(),
-                                     (uint32_t)hs.w_rows.size()};
+            append_by_weight(tmp_scan, list(hpass.work_scan));
+            append_by_weight(tmp_fin, list(hpass.work_fin));
+            append_by_weight(tmp_fin2, list(hpass.work_fin2));
+            for (int l = 0; l < HostPass::N_LISTS; l++) ps.off[s + 1].at[l] = (uint32_t)hpass.list[l].h.size();
         }
-        // the four lists of the binned clusters travel as one block (cluster | first item | partitions | first entry)
-        ps.NB = hs.bin_cluster.size();
-        hs.bin_block.clear();
+        ps.NB = hpass.bin_cluster.size();      // the four lists of the binned clusters travel as one block
         if (ps.NB) {
-            for (auto* v : {&hs.bin_cluster, &hs.bin_item0, &hs.bin_nparts, &hs.bin_base}) hs.bin_block.insert(hs.bin_block.end(), v->begin(), v->end());
+            std::vector<uint32_t>& block = hpass.bin_block.h;
+            for (auto* v : {&hpass.bin_cluster, &hpass.bin_item0, &hpass.bin_nparts, &hpass.bin_base}) block.insert(block.end(), v->begin(), v->end());
             PFCHK(c->q_off.ensure(NI * (pf::BIN_CHUNKS + 1) * 4));
         }
-        std::vector<std::pair<DevBuf*, const std::vector<uint32_t>*>> arrs = {
-            {&c->bin_lists, &hs.bin_block},
-            {&c->it_cluster, &hs.it_cluster}, {&c->it_part, &hs.it_part}, {&c->it_nparts, &hs.it_nparts},
-            {&c->it_nslots, &hs.it_nslots}, {&c->it_slice, &hs.it_slice}, {&c->it_sib0, &hs.it_sib0}, {&c->it_nsib, &hs.it_nsib},
-            {&c->it_extra_first, &hs.it_extra_first}, {&c->it_is_extra, &hs.it_is_extra}, {&c->it_compact, &hs.it_compact},
-            {&c->it_binned, &hs.it_binned},
-            {&c->sub_cluster, &hs.sub_cluster}, {&c->sub_item0, &hs.sub_item0}, {&c->sub_nitems, &hs.sub_nitems},
-            {&c->work_scan, &hs.w_scan}, {&c->work_extra, &hs.w_extra}, {&c->work_fin, &hs.w_fin}, {&c->work_fin2, &hs.w_fin2},
-            {&c->work_fin3, &hs.w_fin3}, {&c->work_fin5, &hs.w_fin5}, {&c->work_rows, &hs.w_rows}};
         lap("  work lists");
-        return staged_upload(c, arrs);
+        return staged_upload(c, hpass.staged());
     }
     // ---- sub-batch s of a host-planned pass: extra-row fill, (bin and) scan, the fused finish beside or in line, then
     // the general path: rows -> cluster base (+ bitmap merge) -> emit -> pattern rows
     int launch_sub_batch(const Pass& ps, size_t s) {
         const Sub& sb = ps.subs[s];
         const SubLists &o0 = ps.off[s], &o1 = ps.off[s + 1];
-        const uint32_t n_scan = o1.scan - o0.scan, n_extra_items = o1.extra - o0.extra;
-        if (n_extra_items) {
+        const HostPass& hpass = c->pass;
+        uint32_t* const it_count = hpass.it_count.as<uint32_t>();
+        FinWork w[HostPass::N_LISTS];         // this sub-batch's stretch of every work list
+        for (int l = 0; l < HostPass::N_LISTS; l++) w[l] = FinWork{hpass.list[l].d.as<uint32_t>() + o0.at[l], o1.at[l] - o0.at[l]};
+        const FinWork w_scan = w[hpass.work_scan], w_extra = w[hpass.work_extra], w_rows = w[hpass.work_rows];
+        const uint32_t n_scan = w_scan.n, n_rows = w_rows.n;
+        if (w_extra.n) {
             pf::ExtraParams ep{};
-            ep.vf = view_facts(); ep.items = host_items(); ep.dump = slot_dump(c->it_count.as<uint32_t>()); ep.opt = row_opts();
-            ep.work = c->work_extra.as<uint32_t>() + o0.extra;
+            ep.vf = view_facts(); ep.items = hpass.items(); ep.dump = slot_dump(it_count); ep.opt = row_opts();
+            ep.work = w_extra.work;
             PFCHK(mark_begin(c, TimeCat::emit));
-            hipLaunchKernelGGL(pf::extra_fill_kernel, dim3(n_extra_items), dim3(256), 0, c->stream, ep);
+            hipLaunchKernelGGL(pf::extra_fill_kernel, dim3(w_extra.n), dim3(256), 0, c->stream, ep);
             HIPCHK(hipGetLastError());
             PFCHK(mark_end(c));
         }
         if (n_scan) {
-            pf::ScanParams sp = scan_params(host_items(), c->it_count.as<uint32_t>(), c->upool[sb.pool], c->work_scan.as<uint32_t>() + o0.scan);
+            pf::ScanParams sp = scan_params(hpass.items(), it_count, c->upool[sb.pool], w_scan.work);
             PFCHK(mark_begin(c, TimeCat::scan));
             if (sb.nbin) {
                 const size_t qcap = (size_t)sb.q_total + 64, NB = ps.NB;
                 PFCHK(c->q_key.ensure(qcap * 8 * KW)); PFCHK(c->q_ord.ensure(qcap * 4)); PFCHK(c->q_bit.ensure(qcap * 4));
                 sp.q_key = c->q_key.as<uint64_t>(); sp.q_ord = c->q_ord.as<uint32_t>(); sp.q_bit = c->q_bit.as<uint32_t>();
                 sp.q_stride = qcap; sp.q_off = c->q_off.as<uint32_t>();
-                sp.bin_cluster = c->bin_lists.as<uint32_t>() + sb.bin0; sp.bin_item0 = c->bin_lists.as<uint32_t>() + NB + sb.bin0;
-                sp.bin_nparts = c->bin_lists.as<uint32_t>() + 2 * NB + sb.bin0; sp.bin_base = c->bin_lists.as<uint32_t>() + 3 * NB + sb.bin0;
+                const uint32_t* const bin = hpass.bin_block.d.as<uint32_t>() + sb.bin0;
+                sp.bin_cluster = bin; sp.bin_item0 = bin + NB; sp.bin_nparts = bin + 2 * NB; sp.bin_base = bin + 3 * NB;
                 PFCHK(launch_bin(c, sp, sb.nbin));
             }
             PFCHK(launch_scan(c, sp, n_scan));
             PFCHK(mark_end(c));
             c->timing.scan_launches++;
         }
-        const uint32_t n_fin = o1.fin - o0.fin, n_fin2 = o1.fin2 - o0.fin2, n_fin3 = o1.fin3 - o0.fin3,
-                       n_fin5 = o1.fin5 - o0.fin5, n_rows = o1.rows - o0.rows;
         // A launch whose fused-finish workgroups do not fill the GPU while general-path items wait behind them (a batch
         // of many-allele clusters with a few dozen simple ones: two 1 024-thread workgroups took 0.4 ms each with the
         // other 250 CUs idle; any batch of a few hundred clusters): the finish kernels go to the context's second
         // stream and run BESIDE rows / emit / pattern rows -- they share nothing but atomically claimed output room
         // and the run-global pattern table.  (Not for full launches: two latency-bound kernels that each fill the GPU
         // take each other's wave slots -- five such pairings lost in rounds 2-3.)
-        const uint32_t n_fused_wg = n_fin + n_fin2 + n_fin3 + n_fin5;
+        const FinWork w_fin = w[hpass.work_fin], w_fin2 = w[hpass.work_fin2], w_fin3 = w[hpass.work_fin3], w_fin5 = w[hpass.work_fin5];
+        const uint32_t n_fused_wg = w_fin.n + w_fin2.n + w_fin3.n + w_fin5.n;
         const bool beside = n_fused_wg && n_rows && n_fused_wg <= 2u * (uint32_t)c->n_cu;
         if (n_fused_wg) {
             hipStream_t fs = c->stream;
@@ -1624,21 +1625,19 @@ struct SubmitRun {
                 fs = c->side;
                 c->timing.n_side_launches++;
             }
-            PFCHK(launch_fused_finish(finish_params(host_items(), c->it_count.as<uint32_t>()), fs, {c->work_fin5.as<uint32_t>() + o0.fin5, n_fin5},
-                                      {c->work_fin3.as<uint32_t>() + o0.fin3, n_fin3}, {c->work_fin2.as<uint32_t>() + o0.fin2, n_fin2},
-                                      {c->work_fin.as<uint32_t>() + o0.fin, n_fin}));
+            PFCHK(launch_fused_finish(finish_params(hpass.items(), it_count), fs, w_fin5, w_fin3, w_fin2, w_fin));
             if (beside) HIPCHK(hipEventRecord(c->ev_join, c->side));
         }
         if (!n_rows) return PF_OK;
         // the general path's four kernels read the same groups (nothing between here and the last launch resizes a buffer)
         const pf::CallerSegs cl = caller_segs();
         const pf::ViewFacts vf = view_facts();
-        const pf::Items items = host_items();
-        const pf::SlotDump dump = slot_dump(c->it_count.as<uint32_t>());
+        const pf::Items items = hpass.items();
+        const pf::SlotDump dump = slot_dump(it_count);
         const pf::RowScratch rs = row_scratch();
         const pf::Outputs out = outputs();
         const pf::RowOpts opt = row_opts();
-        const uint32_t* const work = c->work_rows.as<uint32_t>() + o0.rows;
+        const uint32_t* const work = w_rows.work;
         pf::RowsParams rp{};
         rp.cl = cl; rp.vf = vf; rp.items = items; rp.dump = dump; rp.rs = rs; rp.opt = opt; rp.work = work;
         PFCHK(mark_begin(c, TimeCat::rows));
@@ -1647,9 +1646,9 @@ struct SubmitRun {
         PFCHK(mark_end(c));
 
         pf::BaseParams bp{};
-        bp.sub_cluster = c->sub_cluster.as<uint32_t>() + sb.cl0;
-        bp.cluster_item0 = c->sub_item0.as<uint32_t>() + sb.cl0;
-        bp.cluster_nitems = c->sub_nitems.as<uint32_t>() + sb.cl0;
+        bp.sub_cluster = hpass.sub_cluster.d.as<uint32_t>() + sb.cl0;
+        bp.cluster_item0 = hpass.sub_item0.d.as<uint32_t>() + sb.cl0;
+        bp.cluster_nitems = hpass.sub_nitems.d.as<uint32_t>() + sb.cl0;
         bp.vf = vf; bp.rs = rs; bp.out = out;
         bp.n = sb.ncl;
         PFCHK(mark_begin(c, TimeCat::emit));
@@ -1683,7 +1682,8 @@ struct SubmitRun {
     // ---- the pass waited for (the last part's, or a re-run): who overflowed?  Read-back, learning, the next pass's clusters
     int finish_pass(const Pass& ps, uint32_t pass, bool rerun) {
         SubmitScratch& hs = c->hs;
-        const size_t NI = hs.items.size();
+        const HostPass& hpass = c->pass;
+        const size_t NI = hpass.n_items();
         PFCHK(c->pin_ovf.ensure((size_t)C * 4 + 64));
         uint32_t* const ovf = c->pin_ovf.as<uint32_t>();
         uint64_t* const cur3 = c->pin_small.as<uint64_t>() + 48;
@@ -1700,15 +1700,15 @@ struct SubmitRun {
         }
         if (learn) {
             hs.count.resize(NI);
-            HIPCHK(hipMemcpyAsync(hs.count.data(), c->it_count.p, NI * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(hs.count.data(), hpass.it_count.p, NI * 4, hipMemcpyDeviceToHost, c->stream));
         }
         if (learn_planned) {
             hs.plan.resize(2 * (size_t)learn_planned);
             HIPCHK(hipMemcpyAsync(hs.plan.data(), dplan_ptrs(c->dplan[pass]).it_cluster, (size_t)learn_planned * 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipMemcpyAsync(hs.plan.data() + learn_planned, c->dplan[pass].it_count.p, (size_t)learn_planned * 4, hipMemcpyDeviceToHost, c->stream));
         }
-        HIPCHK(hipMemcpyAsync(ovf, c->cl_overflow.p, (size_t)C * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(cur3, c->cursor.p, 24, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(ovf, c->batch.cl_overflow.p, (size_t)C * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(cur3, c->batch.cursor.p, 24, hipMemcpyDeviceToHost, c->stream));
         // (the pattern counters come along: when this was the last pass the MD5 launch needs no round trip of its own)
         HIPCHK(hipMemcpyAsync(cnt_pin, c->pt_counters.p, 12, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -1737,13 +1737,13 @@ struct SubmitRun {
             };
             for (uint32_t i = 0; i < learn_planned && looked < 4096; i++)
                 if (hs.plan[i] < C) look(hs.plan[i], hs.plan[learn_planned + i]);
+            auto col = [&](HostPass::Col k) { return hpass.col[k].h.data(); };
             if (learn)
                 for (size_t i = 0; i < NI && looked < 4096; i++) {
-                    const Item& it = hs.items[i];
-                    if (it.is_extra || it.part != 0) continue;
+                    if (col(hpass.it_is_extra)[i] || col(hpass.it_part)[i] != 0) continue;
                     uint64_t keys = 0;
-                    for (uint32_t q = 0; q < it.nparts; q++) keys += hs.count[i + q];
-                    look(it.cluster, keys);
+                    for (uint32_t q = 0; q < col(hpass.it_nparts)[i]; q++) keys += hs.count[i + q];
+                    look(col(hpass.it_cluster)[i], keys);
                 }
         }
         std::vector<uint32_t> next;
@@ -1762,7 +1762,7 @@ struct SubmitRun {
             }
         if (!next.empty()) {
             c->timing.n_retried += (uint32_t)next.size();
-            HIPCHK(hipMemsetAsync(c->cl_overflow.p, 0, (size_t)std::max(C, 1u) * 4, c->stream));
+            HIPCHK(hipMemsetAsync(c->batch.cl_overflow.p, 0, (size_t)std::max(C, 1u) * 4, c->stream));
         }
         todo.swap(next);
         return PF_OK;
@@ -1770,11 +1770,11 @@ struct SubmitRun {
     // ---- MD5 of the patterns this batch created, ids [pid0, pid1)
     int launch_md5(uint32_t pid1) {
         pf::Md5Params mp{};
-        mp.pats = pattern_pool(); mp.pat_md5 = c->pat_md5.as<uint8_t>();
+        mp.pats = pattern_pool(); mp.pat_md5 = c->pats.md5.as<uint8_t>();
         mp.pid0 = c->pid0; mp.pid1 = pid1; mp.W = W; mp.range = nullptr;
         // int64 rows are the clusters' own rows: the int pass goes by cluster (cl_pattern) and runs BESIDE the float pass, on
         // the side stream, instead of behind it
-        mp.cluster_pattern = c->cl_pattern.as<uint32_t>(); mp.n_clusters = C;
+        mp.cluster_pattern = c->batch.cl_pattern.as<uint32_t>(); mp.n_clusters = C;
         PFCHK(mark_begin(c, TimeCat::md5));
         // A small launch is spread over the chip: the float pass's workgroups (four waves, one per SIMD) number a few per
         // CU, and the dispatcher fills CUs with up to eight before it moves on -- a SIMD gets through its rows at one rate
@@ -1876,7 +1876,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         PFCHK(r.upload_cursor_start());
         r.lap("upload items");
         for (size_t s = 0; s < ps.subs.size(); s++) PFCHK(r.launch_sub_batch(ps, s));
-        c->timing.n_items += (uint32_t)c->hs.items.size();
+        c->timing.n_items += (uint32_t)c->pass.n_items();
         for (uint32_t ci : r.todo) c->timing.scan_packed_bytes += r.rec[ci].words * 8 * r.nparts[ci];
         r.lap("launch pass");
         if (pass + 1 < r.P) {
@@ -2000,10 +2000,10 @@ int pf_fetch(pf_ctx* c, pf_result* res) {
     const uint32_t C = c->n_clusters, W = c->W, KW = (uint32_t)c->KW;
     c->h_kmer_off.resize(C); c->h_kmer_cnt.resize(C); c->h_cl_pattern.resize(C); c->h_cl_unique.resize(C);
     if (C) {
-        HIPCHK(hipMemcpy(c->h_kmer_off.data(), c->cl_kmer_off.p, (size_t)C * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(c->h_kmer_cnt.data(), c->cl_kmer_cnt.p, (size_t)C * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(c->h_cl_pattern.data(), c->cl_pattern.p, (size_t)C * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(c->h_cl_unique.data(), c->cl_unique.p, (size_t)C * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c->h_kmer_off.data(), c->batch.cl_kmer_off.p, (size_t)C * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c->h_kmer_cnt.data(), c->batch.cl_kmer_cnt.p, (size_t)C * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c->h_cl_pattern.data(), c->batch.cl_pattern.p, (size_t)C * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c->h_cl_unique.data(), c->batch.cl_unique.p, (size_t)C * 4, hipMemcpyDeviceToHost));
     }
     // concatenate the used prefixes of the arenas; remap cluster offsets
     uint64_t total = 0;
@@ -2029,12 +2029,12 @@ int pf_fetch(pf_ctx* c, pf_result* res) {
     if (c->o.consider_missing) c->h_pat_nan.resize((size_t)p1 * W);
     if (p1 > p0) {
         const size_t n = p1 - p0;
-        HIPCHK(hipMemcpy(c->h_pat_bits.data() + (size_t)p0 * W, c->pat_bits.as<uint32_t>() + (size_t)p0 * W, n * W * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(c->h_pat_n.data() + p0, c->pat_n.as<uint32_t>() + p0, n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(c->h_pat_md5.data() + (size_t)p0 * 16, c->pat_md5.as<uint8_t>() + (size_t)p0 * 16, n * 16, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c->h_pat_bits.data() + (size_t)p0 * W, c->pats.bits.as<uint32_t>() + (size_t)p0 * W, n * W * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c->h_pat_n.data() + p0, c->pats.n.as<uint32_t>() + p0, n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c->h_pat_md5.data() + (size_t)p0 * 16, c->pats.md5.as<uint8_t>() + (size_t)p0 * 16, n * 16, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(c->h_first_seen.data() + p0, c->pt.first_seen + p0, n * 8, hipMemcpyDeviceToHost));
         if (c->o.consider_missing)
-            HIPCHK(hipMemcpy(c->h_pat_nan.data() + (size_t)p0 * W, c->pat_nan.as<uint32_t>() + (size_t)p0 * W, n * W * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(c->h_pat_nan.data() + (size_t)p0 * W, c->pats.nan.as<uint32_t>() + (size_t)p0 * W, n * W * 4, hipMemcpyDeviceToHost));
     }
     c->h_new_pid.resize(p1 - p0);
     std::iota(c->h_new_pid.begin(), c->h_new_pid.end(), p0);
@@ -2068,7 +2068,7 @@ int pf_export_patterns(pf_ctx* c, uint64_t* n, const uint8_t** md5, const uint64
     c->h_first_seen.resize(p1);
     if (p1) {
         HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpy(c->h_pat_md5.data(), c->pat_md5.p, (size_t)p1 * 16, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c->h_pat_md5.data(), c->pats.md5.p, (size_t)p1 * 16, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(c->h_first_seen.data(), c->pt.first_seen, (size_t)p1 * 8, hipMemcpyDeviceToHost));
     }
     *n = p1;
@@ -2083,7 +2083,7 @@ int pf_export_patterns_dev(pf_ctx* c, uint64_t cap, void* d_md5, void* d_first_s
     const uint64_t m = std::min<uint64_t>(cap, c->n_patterns);
     if (m) {
         if (!d_md5 || !d_first_seen) return fail(PF_ERR_ARG, "null destination");
-        HIPCHK(hipMemcpyAsync(d_md5, c->pat_md5.p, (size_t)m * 16, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_md5, c->pats.md5.p, (size_t)m * 16, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(d_first_seen, c->pt.first_seen, (size_t)m * 8, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
@@ -2648,7 +2648,7 @@ int pf_result_checksum(pf_ctx* c, uint64_t out[3]) {
     if (!C) return PF_OK;
     // where each cluster's k-mers stand: arena of the cluster + offset inside it
     std::vector<uint64_t> off(C);
-    HIPCHK(hipMemcpy(off.data(), c->cl_kmer_off.p, (size_t)C * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(off.data(), c->batch.cl_kmer_off.p, (size_t)C * 8, hipMemcpyDeviceToHost));
     std::vector<const uint64_t*> kp(C);
     std::vector<const uint32_t*> pp(C);
     for (uint32_t i = 0; i < C; i++) {
@@ -2665,8 +2665,8 @@ int pf_result_checksum(pf_ctx* c, uint64_t out[3]) {
         hipMemsetAsync(d_acc.p, 0, 24, c->stream) != hipSuccess) rc = fail(PF_ERR_HIP, "pf_result_checksum: copy failed");
     if (rc == PF_OK) {
         hipLaunchKernelGGL(pf::result_checksum_kernel, dim3(C), dim3(256), 0, c->stream,
-                           (const uint64_t* const*)d_kp.p, (const uint32_t* const*)d_pp.p, c->cl_kmer_cnt.as<uint32_t>(),
-                           c->cl_unique.as<uint32_t>(), c->cl_pattern.as<uint32_t>(), c->pat_md5.as<uint8_t>(), KW,
+                           (const uint64_t* const*)d_kp.p, (const uint32_t* const*)d_pp.p, c->batch.cl_kmer_cnt.as<uint32_t>(),
+                           c->batch.cl_unique.as<uint32_t>(), c->batch.cl_pattern.as<uint32_t>(), c->pats.md5.as<uint8_t>(), KW,
                            (unsigned long long*)d_acc.p);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
             hipMemcpy(out, d_acc.p, 24, hipMemcpyDeviceToHost) != hipSuccess)
@@ -3027,11 +3027,11 @@ int pf_genomes_upload(pf_ctx* c, uint32_t n, const char* const* ascii, const uin
 namespace {
 // base64 of every digest up to n_patterns, on the device (incremental)
 int ensure_b64_dev(pf_ctx* c) {
-    if (!c->pat_b64.p) PFCHK(c->pat_b64.ensure((size_t)c->pt.pool * 24));
+    if (!c->pats.b64.p) PFCHK(c->pats.b64.ensure((size_t)c->pt.pool * 24));
     const uint32_t p1 = c->n_patterns;
     if (c->b64_done < p1) {
         hipLaunchKernelGGL(pf::b64_kernel, dim3((p1 - c->b64_done + 255) / 256), dim3(256), 0, c->stream,
-                           c->pat_md5.as<uint8_t>(), c->b64_done, p1, c->pat_b64.as<char>());
+                           c->pats.md5.as<uint8_t>(), c->b64_done, p1, c->pats.b64.as<char>());
         HIPCHK(hipGetLastError());
         c->b64_done = p1;
     }
@@ -3045,8 +3045,8 @@ int text_pin(pf_ctx* c, size_t total) {
 // hashes_to_patterns rows on the device.  The lengths of n rows into d_len: of the patterns order[0 .. n) (a device
 // list), or of patterns pid0 .. pid0 + n without a list
 int hp_rowlen(pf_ctx* c, const uint32_t* order, uint32_t pid0, uint32_t n, uint32_t* d_len) {
-    hipLaunchKernelGGL(pf::hp_rowlen_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->pat_n.as<uint32_t>(),
-                       c->o.consider_missing ? c->pat_nan.as<uint32_t>() : (const uint32_t*)nullptr, c->W, pid0, order, n, d_len);
+    hipLaunchKernelGGL(pf::hp_rowlen_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->pats.n.as<uint32_t>(),
+                       c->o.consider_missing ? c->pats.nan.as<uint32_t>() : (const uint32_t*)nullptr, c->W, pid0, order, n, d_len);
     HIPCHK(hipGetLastError());
     return PF_OK;
 }
@@ -3054,9 +3054,9 @@ int hp_rowlen(pf_ctx* c, const uint32_t* order, uint32_t pid0, uint32_t n, uint3
 int hp_text(pf_ctx* c, const uint32_t* order, const uint64_t* row_off, uint32_t n, char* text) {
     pf::HpTextParams hpp{};
     hpp.order = order; hpp.row_off = row_off;
-    hpp.pat_bits = c->pat_bits.as<uint32_t>();
-    hpp.pat_nan = c->o.consider_missing ? c->pat_nan.as<uint32_t>() : nullptr;
-    hpp.pat_n = c->pat_n.as<uint32_t>(); hpp.b64 = c->pat_b64.as<char>();
+    hpp.pat_bits = c->pats.bits.as<uint32_t>();
+    hpp.pat_nan = c->o.consider_missing ? c->pats.nan.as<uint32_t>() : nullptr;
+    hpp.pat_n = c->pats.n.as<uint32_t>(); hpp.b64 = c->pats.b64.as<char>();
     hpp.text = text; hpp.n = n; hpp.W = c->W;
     hipLaunchKernelGGL(pf::hp_text_kernel, dim3(n), dim3(256), 0, c->stream, hpp);
     HIPCHK(hipGetLastError());
@@ -3117,8 +3117,8 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
     std::vector<uint64_t> koff(C);
     std::vector<uint32_t> kcnt(C);
     if (C) {
-        HIPCHK(hipMemcpyAsync(koff.data(), c->cl_kmer_off.p, (size_t)C * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(kcnt.data(), c->cl_kmer_cnt.p, (size_t)C * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(koff.data(), c->batch.cl_kmer_off.p, (size_t)C * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(kcnt.data(), c->batch.cl_kmer_cnt.p, (size_t)C * 4, hipMemcpyDeviceToHost, st));
     }
     const uint32_t p0 = c->pid0, p1 = c->n_patterns, P = want_hp ? p1 - p0 : 0;
     std::vector<uint64_t> fs(P);
@@ -3194,10 +3194,10 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
         pf::KhTextParams kp{};
         kp.text_off = (const uint64_t*)(dm + o_text); kp.name_off = (const uint32_t*)(dm + o_name); kp.names = dm + o_blob;
         kp.kmer_off = (const uint64_t*)(dm + o_koff); kp.kmer_cnt = (const uint32_t*)(dm + o_kcnt);
-        kp.cluster_pattern = c->cl_pattern.as<uint32_t>(); kp.cluster_arena = (const uint32_t*)(dm + o_arena);
+        kp.cluster_pattern = c->batch.cl_pattern.as<uint32_t>(); kp.cluster_arena = (const uint32_t*)(dm + o_arena);
         kp.block_cluster = (const uint32_t*)(dm + o_bc); kp.block_row0 = (const uint32_t*)(dm + o_br);
         for (size_t a = 0; a < c->n_passes; a++) { kp.arena_key[a] = c->arenas[a]->key.as<uint64_t>(); kp.arena_pid[a] = c->arenas[a]->pid.as<uint32_t>(); }
-        kp.b64 = c->pat_b64.as<char>(); kp.extra_keys = dm + o_extra; kp.text = c->txt_dev.as<char>();
+        kp.b64 = c->pats.b64.as<char>(); kp.extra_keys = dm + o_extra; kp.text = c->txt_dev.as<char>();
         kp.k = k; kp.KW = KW; kp.rows_per_block = rows_per_block;
         hipLaunchKernelGGL(pf::kh_text_kernel, dim3((uint32_t)blk_cluster.size()), dim3(256), 0, st, kp);
         HIPCHK(hipGetLastError());

@@ -72,6 +72,59 @@ def test_scratch_grows_for_a_cluster_of_more_items_than_max_items():
     eng.close()
 
 
+def test_failed_scratch_enlargement_leaves_the_context_usable():
+    """the failure branch of the growing scratch (pf_debug_limit_alloc stands in for a full device): the limit is the
+    largest buffer a batch of one-item clusters asked for -- the 3-item bm4 bitmaps, 3 x 32 768 x 16 = 1 572 864 bytes.  A
+    cluster of the many-allele batch then needs 8 work items (9 in some runs: the partitions a retry gets come from how far
+    the overflowing scan came); of the scratch re-made for them the tab_key and tab_ord fit, and the chunkbits (8 items x
+    9 600 slots x 7 words x 4 = 2 150 400 bytes, or 2 419 200; 806 400 at 3 items) is the request refused, the only one of
+    that batch above the limit: PF_ERR_OOM, nothing counted as grown.  The context has its 3-item scratch back:
+    the simple batch again, limit still set, gives the oracle's text; with the limit lifted the many-allele batch grows the
+    scratch and gives the oracle's too."""
+    import ctypes as C
+    import re
+    from panfeed_amd import _lib
+    from panfeed_amd.engine import Engine
+    S, k = 200, 31
+    few = _records(10, S, first=31000, flank=30, mean_len=500, min_len=200, max_len=900, n_rate=0.01, paralog_rate=0.03)
+    many = _records(5, S, first=777, flank=30, mean_len=900, min_len=600, max_len=1200, n_rate=0.0, paralog_rate=0.02,
+                    sub_rate=0.03, mean_alleles=60.0, allele_decay=1.0, allele_model="star")
+    (ek, ekh, ehp), _ = _oracle_texts(few + few + many, klength=k, canon=True)
+    L = _lib.load()
+    stats = (C.c_uint64 * 2)()
+    _lib.check(L.pf_debug_limit_alloc(0, stats))                  # clears the counters
+    eng = Engine(klength=k, max_strains=S + 24, max_items=3, pattern_capacity=4096)
+    outs = [eng.run(few)]
+    _lib.check(L.pf_debug_limit_alloc(0, stats))
+    largest = int(stats[0])
+    print("largest allocation of the simple batch:", largest)
+    assert largest > 0
+    try:
+        _lib.check(L.pf_debug_limit_alloc(largest, stats))
+        ordinal = eng.next_ordinal
+        with pytest.raises(_lib.PanfeedHipError) as ei:
+            eng.run(many)
+        eng.next_ordinal = ordinal                                # (the failed batch does not count)
+        _lib.check(L.pf_debug_limit_alloc(largest, stats))
+        refused = int(re.search(r"hipMalloc\((\d+)\)", str(ei.value)).group(1))
+        print("refused:", ei.value, "| largest request of the failed batch:", int(stats[0]))
+        assert ei.value.status == _lib.ERR_OOM
+        assert eng.timing()["n_scratch_grown"] == 0
+        # the scratch's chunkbits, 9 600 slots of a one-word key's table x W words per item (no other buffer has that size per
+        # item), re-made for the 8 or 9 items the cluster asks for: no other request of this batch was as large
+        assert refused in (8 * 9600 * eng.W * 4, 9 * 9600 * eng.W * 4) and largest < refused == int(stats[0])
+        outs.append(eng.run(few))
+    finally:
+        _lib.check(L.pf_debug_limit_alloc(0, None))
+    outs.append(eng.run(many))
+    t = eng.timing()
+    print("n_scratch_grown", t["n_scratch_grown"], "n_items", outs[-1].timing["n_items"])
+    assert t["n_scratch_grown"] >= 1 and outs[-1].timing["n_items"] > 3
+    assert "".join(o.kmers_to_hashes for o in outs) == ekh
+    assert "".join(o.hashes_to_patterns for o in outs) == ehp
+    eng.close()
+
+
 def test_fused_finish_beside_the_general_path():
     """a launch with a few simple clusters (fused finish) and a few of many distinct sequences (general path): the finish
     kernels run on the context's second stream beside rows / emit / pattern rows; output room is claimed atomically by both
