@@ -528,6 +528,37 @@ int pf_render_pattern_rows(pf_ctx* ctx, const uint32_t* pids, uint64_t n, const 
 int pf_gzip_members(const char* data, uint64_t n, int level, uint64_t chunk_bytes, char** out, uint64_t* out_n);
 
 /*
+ * gzip ON THE DEVICE (opt-in: larger files than pf_gzip_members' level 9 in less time; measured: profiles/gzip_device/).  The text is cut
+ * into independent chunks of pf_gzip_device_chunk_bytes() bytes; each becomes one complete gzip member (RFC 1952) of one
+ * deflate block -- stored, fixed or dynamic Huffman, the smallest by exact bit count -- with matches found through a
+ * hash table in LDS (one candidate per position, greedy parse, no match reaching before its chunk), its CRC32 computed on
+ * the device.  Any gzip reader gets back exactly the text; the same text gives the same bytes on every run.
+ * flags: 0 is the product setting; the others are test hooks.
+ */
+#define PF_GZ_FIXED_ONLY 1u     /* every block with the fixed codes */
+#define PF_GZ_DYNAMIC_ONLY 2u   /* every block with dynamic codes */
+#define PF_GZ_LITERALS_ONLY 4u  /* no match is accepted */
+uint32_t pf_gzip_device_chunk_bytes(void);
+/* Host text in, members out (malloc'd: pf_free_text): uploaded, encoded on the GPU, copied back.  n == 0 gives
+ * *out_n == 0.  For tests, tools and text rendered on the host. */
+int pf_gzip_device(pf_ctx* ctx, const char* data, uint64_t n, uint32_t flags, char** out, uint64_t* out_n);
+/* Device time of the last pf_gzip_device's kernels (encode, size scan, gather; hipEvent on the context's stream), ms. */
+int pf_gzip_device_last_ms(pf_ctx* ctx, float* ms);
+/* The same container and coder run serially on the host, with a plain one-candidate greedy matcher: no context, no GPU.
+ * Its bytes need not equal the device's; both decode to `data`. */
+int pf_gzip_host_model(const char* data, uint64_t n, uint32_t flags, char** out, uint64_t* out_n);
+/* Off by default.  While on, pf_render_device[_ex] hands out gzip members in place of text (*kh, *kh_bytes, *hp,
+ * *hp_bytes describe the compressed bytes) and so does pf_kmers_tsv_stream_next: every block of a range is encoded as it
+ * is produced and its compressed size read back before it is copied (the host-rendered sequences are in the device text
+ * and go the same way); a block's members decode to a block of the text, in order.  The stream's *total_bytes stays the
+ * text's size and *peak_text_bytes includes the encoder's buffers.  pf_device_text_chunk, pf_render_pattern_rows and the
+ * host renderers are not affected. */
+int pf_set_device_gzip(pf_ctx* ctx, int on, uint32_t flags);
+/* The text sizes behind the compressed bytes: out[0], out[1] = bytes of kmers_to_hashes / hashes_to_patterns text of the
+ * last pf_render_device[_ex]; out[2] = text bytes the open (or last) kmers.tsv stream has handed out so far. */
+int pf_device_gzip_text_bytes(pf_ctx* ctx, uint64_t out[3]);
+
+/*
  * Row filter of the downstream tools on the device: the rows of kmers_to_hashes.tsv whose
  * hashed_pattern is one of a set of hashes (/root/reference/panfeed/get_clusters.py:89-94, get_kmers.py:103-106:
  * `x[x['hashed_pattern'].isin(passing_hashes)]` over 100 000-row pandas chunks) and the rows of kmers.tsv whose cluster

@@ -148,9 +148,12 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_rowfilter_create", "pf_rowfilter_scan", "pf_rowfilter_stats", "pf_rowfilter_destroy",
            "pf_plotgrid_create", "pf_plotgrid_scan", "pf_plotgrid_finish", "pf_plotgrid_clusters", "pf_plotgrid_pvalues",
            "pf_plotgrid_set_significance", "pf_plotgrid_grids", "pf_plotgrid_stats", "pf_plotgrid_destroy",
-           "pf_py_str_addresses", "pf_pangenome_close_async", "pf_py_seqinfo_columns", "pf_py_release"]
+           "pf_py_str_addresses", "pf_pangenome_close_async", "pf_py_seqinfo_columns", "pf_py_release",
+           "pf_gzip_device_chunk_bytes", "pf_gzip_device", "pf_gzip_host_model", "pf_set_device_gzip",
+           "pf_device_gzip_text_bytes", "pf_gzip_device_last_ms"]
 
 RENDER_NO_PATTERN_ROWS = 1
+GZ_FIXED_ONLY, GZ_DYNAMIC_ONLY, GZ_LITERALS_ONLY = 1, 2, 4     # pf_gzip_device / pf_set_device_gzip test hooks; 0: the product
 GET_CTX = C.CFUNCTYPE(C.c_void_p, C.c_void_p)     # pf_pangenome_open_device_cb: the context, when the first genome needs it
 ERR_ARG, ERR_OOM, ERR_HIP, ERR_CAPACITY, ERR_STATE = -1, -2, -3, -4, -5
 
@@ -279,6 +282,13 @@ def _load_locked():
     L.pf_plotgrid_destroy.argtypes = [C.c_void_p]
     L.pf_plotgrid_destroy.restype = None
     L.pf_gzip_members.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pf_gzip_device_chunk_bytes.argtypes = []
+    L.pf_gzip_device_chunk_bytes.restype = C.c_uint32
+    L.pf_gzip_device.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pf_gzip_host_model.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pf_gzip_device_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.pf_set_device_gzip.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+    L.pf_device_gzip_text_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.pf_submit_gather.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Gather), C.POINTER(Result)]
     L.pf_records_free.argtypes = [C.c_void_p]
     L.pf_records_free.restype = None

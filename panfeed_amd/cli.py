@@ -61,6 +61,8 @@ def get_options(argv=None):
                    help="one output directory per gene cluster instead of one set of files")
     p.add_argument("--compress", action="store_true", default=False,
                    help="gzip the output files")
+    p.add_argument("--gpu-compress", action="store_true", default=False,
+                   help="gzip the output files on the GPU; implies --compress; much faster, somewhat larger files")
     p.add_argument("--cores", type=int, default=1,
                    help="accepted for compatibility; the GPU does the work of the worker processes")
     p.add_argument("-ql", "--queue-limit", type=int, default=3,
@@ -128,6 +130,11 @@ def main(argv=None, run=None):
     if os.path.exists(args.output):
         logger.error(f"Output directory {args.output} exists: remove it or choose another")
         return 1
+    more = {}
+    if args.gpu_compress:
+        more["device_gzip"] = True
+        if args.multiple_files:
+            logger.info("--gpu-compress with --multiple-files: the per-cluster files are compressed on the host")
     if run is None:
         from .pipeline import run_files as run
     from ._lib import PanfeedHipError
@@ -137,9 +144,9 @@ def main(argv=None, run=None):
                     canon=not args.non_canonical, consider_missing=args.consider_missing, patfilt=not args.no_filter,
                     maf=args.maf, upstream=args.upstream, downstream=args.downstream,
                     downstream_start_codon=args.downstream_start_codon, targets=tuple(sorted(targets)),
-                    genes=sorted(genes) if genes is not None else None, compress=args.compress,
+                    genes=sorted(genes) if genes is not None else None, compress=args.compress or args.gpu_compress,
                     multiple_files=args.multiple_files, batch_clusters=args.batch_clusters, device=args.device,
-                    raise_missing=args.stop_on_missing)
+                    raise_missing=args.stop_on_missing, **more)
     except PanfeedHipError as e:          # the reader's message under --stop-on-missing, or the library's error
         logger.error(str(e))
         return 1

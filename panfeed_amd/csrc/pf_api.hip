@@ -13,6 +13,7 @@
 #include "../../include/panfeed_hip.h"
 #include "pf_ingest.h"
 #include "pf_buf.h"
+#include "pf_deflate.h"
 
 #include <sys/stat.h>
 #include <condition_variable>
@@ -270,6 +271,22 @@ struct pf_ctx {
         hipEvent_t ev_prod[2] = {nullptr, nullptr};    // on `stream`: the range in buffer b is written
         hipEvent_t ev_copied[2] = {nullptr, nullptr};  // on `side`: the range in buffer b has left the device
     } kts;
+    // gzip on the device (pf_set_device_gzip): the encoder, and what the mode keeps -- the members of a render, the
+    // members of the stream's two blocks in flight (block j + 1 is encoded while block j is written out by the caller),
+    // the pinned cursor read-backs (0, 1: a render's two texts; 2, 3: the stream's blocks), the text sizes behind them
+    PfGzEncoder gz;
+    struct GzMode {
+        bool on = false, pending = false;
+        uint32_t flags = 0;
+        DevBuf render_members, block_members[2];
+        PinBuf pin_cursor;
+        hipEvent_t ev_copy = nullptr;
+        int pending_slot = 0;
+        uint64_t pending_text = 0;
+        uint64_t raw[3] = {0, 0, 0};
+        uint64_t block_bound = 0;
+        float encode_ms = 0.0f;                   // the last pf_gzip_device's encode, scan and gather launches (hipEvent)
+    } gzm;
     pf_batch last{};                      // the last pf_submit's batch arrays as device pointers (valid until the next submit)
     uint32_t last_nseg = 0;
     uint64_t last_words = 0;              // words of last.packed: the batch's, or the buffer pf_submit_gather filled
@@ -338,7 +355,7 @@ void kt_stream_end(pf_ctx* c) {
         (void)hipStreamSynchronize(c->stream);
     }
     for (int b = 0; b < 2; b++) { free(S.htext[b]); S.htext[b] = nullptr; }
-    S.active = false; c->kt_pref.valid = false;
+    S.active = false; c->kt_pref.valid = false; c->gzm.pending = false;
     S.hseqs.clear(); S.host = KtHostText{}; S.plan = KtPlan{};
 }
 
@@ -709,7 +726,7 @@ void pf_destroy(pf_ctx* c) {
     for (auto e : c->ev_stage) if (e) (void)hipEventDestroy(e);
     for (auto e : c->ev_part) if (e) (void)hipEventDestroy(e);
     for (auto e : {c->kts.ev_prod[0], c->kts.ev_prod[1], c->kts.ev_copied[0], c->kts.ev_copied[1], c->ev_t0, c->ev_t1,
-                   c->ev_fork, c->ev_join})
+                   c->ev_fork, c->ev_join, c->gzm.ev_copy})
         if (e) (void)hipEventDestroy(e);
     if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2508,6 +2525,68 @@ int kt_copy_block(pf_ctx* c, int slot) {
 }
 }  // namespace
 
+namespace {
+// Device gzip of the stream.  The block at (S.cur, S.cur_off) encoded on c->side behind its range's writing, its members
+// into block_members[slot] and their size on its way into the pinned cursor 2 + slot; the stream's position moves past
+// the block.  As with kt_copy_block, a range's last block marks the range's buffer free and range r + 2 is queued into it.
+int kt_gz_block(pf_ctx* c, int slot) {
+    pf_ctx::KtStream& S = c->kts;
+    pf_ctx::GzMode& G = c->gzm;
+    const KtPlan::Range& R = S.plan.ranges[S.cur];
+    const int b = (int)(S.cur & 1);
+    const char* buf = (b ? c->kt_text2 : c->kt_text).as<char>();
+    const uint64_t n = std::min<uint64_t>(KT_BLOCK, R.bytes - S.cur_off);
+    HIPCHK(hipStreamWaitEvent(c->side, S.ev_prod[b], 0));
+    PFCHK(c->gz.begin(c->side, 2 + slot));
+    PFCHK(c->gz.append(c->side, 2 + slot, buf + S.cur_off, n, G.flags, G.block_members[slot].as<char>(), G.block_bound));
+    PFCHK(c->gz.read_cursor(c->side, 2 + slot, G.pin_cursor.as<uint64_t>() + 2 + slot));
+    G.pending = true; G.pending_slot = slot; G.pending_text = n;
+    S.cur_off += n;
+    if (S.cur_off == R.bytes) {
+        HIPCHK(hipEventRecord(S.ev_copied[b], c->side));
+        if (S.cur + 2 < S.plan.ranges.size()) PFCHK(kt_produce(c, S.cur + 2));
+        S.cur++; S.cur_off = 0;
+    }
+    return PF_OK;
+}
+
+// the buffers of the stream's blocks in flight, for blocks of at most block_text bytes of text
+int kt_gz_buffers(pf_ctx* c, uint64_t block_text) {
+    pf_ctx::GzMode& G = c->gzm;
+    PFCHK(c->gz.ensure(c->n_cu));
+    G.block_bound = PfGzEncoder::bound(std::max<uint64_t>(block_text, 1));
+    for (int s = 0; s < 2; s++) {
+        PFCHK(G.block_members[s].ensure(G.block_bound, true));
+        PFCHK(c->kt_pins[s].ensure(G.block_bound, true));
+    }
+    if (!G.ev_copy) HIPCHK(hipEventCreateWithFlags(&G.ev_copy, hipEventDisableTiming));
+    return PF_OK;
+}
+
+// pf_kmers_tsv_stream_next under device gzip: the members of the next block of text
+int kt_gz_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
+    pf_ctx::KtStream& S = c->kts;
+    pf_ctx::GzMode& G = c->gzm;
+    if (!G.pending) {
+        if (S.cur >= S.plan.ranges.size()) { kt_stream_end(c); return PF_OK; }
+        PFCHK(kt_gz_block(c, 0));
+    }
+    HIPCHK(hipStreamSynchronize(c->side));                 // the block is encoded, its size has arrived
+    const int slot = G.pending_slot;
+    const uint64_t z = G.pin_cursor.as<uint64_t>()[2 + slot];
+    if (z > G.block_bound) return fail(PF_ERR_STATE, "device gzip: a block's members exceed their bound");
+    G.pending = false;
+    G.raw[2] += G.pending_text;
+    HIPCHK(hipMemcpyAsync(c->kt_pins[slot].p, G.block_members[slot].p, z, hipMemcpyDeviceToHost, c->side));
+    HIPCHK(hipEventRecord(G.ev_copy, c->side));
+    if (S.cur < S.plan.ranges.size()) PFCHK(kt_gz_block(c, slot ^ 1));      // the next block is encoded meanwhile
+    HIPCHK(hipEventSynchronize(G.ev_copy));
+    *ptr = c->kt_pins[slot].as<char>();
+    *nbytes = z;
+    return PF_OK;
+}
+}  // namespace
+
 // The same rows written by the GPU (kt_len_kernel / kt_text_kernel) for the sequences kt_layout gives it and by the host
 // renderer above for the others, which are copied to their places in the device text: the text of all n sequences, in
 // order, stays in device memory and is handed out block by block (pf_device_text_chunk).  It is the stream's plan with
@@ -2538,9 +2617,16 @@ int pf_kmers_tsv_stream_begin(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, 
     if (peak_text_bytes) *peak_text_bytes = 0;
     PFCHK(kt_open(c, seqs, n, budget_bytes));
     const KtPlan& P = c->kts.plan;
+    uint64_t peak = P.peak;
+    c->gzm.raw[2] = 0;
+    if (c->gzm.on) {                 // the encoder's buffers and the two blocks of members count as the text's memory
+        const int rc = kt_gz_buffers(c, std::min<uint64_t>(KT_BLOCK, P.max_range));
+        if (rc != PF_OK) { kt_stream_end(c); return rc; }
+        peak += c->gz.device_bytes() + 2 * c->gzm.block_bound;
+    }
     *total_bytes = P.total;
     *n_ranges = (uint32_t)P.ranges.size();
-    if (peak_text_bytes) *peak_text_bytes = P.peak;
+    if (peak_text_bytes) *peak_text_bytes = peak;
     return PF_OK;
 }
 
@@ -2550,6 +2636,7 @@ int pf_kmers_tsv_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
     pf_ctx::KtStream& S = c->kts;
     if (!S.active) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_next without an open pf_kmers_tsv_stream_begin");
     HIPCHK(hipSetDevice(c->device));
+    if (c->gzm.on) return kt_gz_next(c, ptr, nbytes);
     if (S.cur >= S.plan.ranges.size()) { kt_stream_end(c); return PF_OK; }
     if (!c->kt_pref.valid) PFCHK(kt_copy_block(c, 0));
     HIPCHK(hipStreamSynchronize(c->side));
@@ -3161,7 +3248,7 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
     const uint64_t hp_at = (kh_n + 255) & ~(uint64_t)255;          // the second text starts 256-byte aligned
     const uint64_t total = hp_at + hp_n + 16;
     PFCHK(c->txt_dev.ensure(total));
-    PFCHK(text_pin(c, total));
+    PFCHK(text_pin(c, c->gzm.on ? 16 : total));        // (under device gzip the block is sized once the members' sizes are known)
     char* txt_pin = c->txt_pins[c->txt_slot].as<char>();
     // ---- one block of tables for both kernels
     auto pad8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
@@ -3203,11 +3290,111 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
         HIPCHK(hipGetLastError());
     }
     if (P) PFCHK(hp_text(c, (const uint32_t*)(dm + o_order), (const uint64_t*)(dm + o_rowoff), P, c->txt_dev.as<char>() + hp_at));
+    if (c->gzm.on) {
+        // both texts through the encoder behind their kernels; the two compressed sizes come back, then only members
+        // cross to the host
+        pf_ctx::GzMode& G = c->gzm;
+        HIPCHK(hipStreamSynchronize(c->side));             // (the encoder's scratch is one: no block of a stream in flight)
+        const uint64_t b0 = PfGzEncoder::bound(kh_n), b1 = PfGzEncoder::bound(hp_n);
+        PFCHK(G.render_members.ensure(b0 + b1 + 16));
+        char* M = G.render_members.as<char>();
+        uint64_t* cur = G.pin_cursor.as<uint64_t>();
+        PFCHK(c->gz.begin(st, 0));
+        PFCHK(c->gz.append(st, 0, c->txt_dev.as<char>(), kh_n, G.flags, M, b0));
+        PFCHK(c->gz.read_cursor(st, 0, cur));
+        PFCHK(c->gz.begin(st, 1));
+        PFCHK(c->gz.append(st, 1, c->txt_dev.as<char>() + hp_at, hp_n, G.flags, M + b0, b1));
+        PFCHK(c->gz.read_cursor(st, 1, cur + 1));
+        HIPCHK(hipStreamSynchronize(st));
+        const uint64_t z0 = cur[0], z1 = cur[1], z1_at = (z0 + 255) & ~(uint64_t)255;
+        if (z0 > b0 || z1 > b1) return fail(PF_ERR_STATE, "device gzip: a text's members exceed their bound");
+        PFCHK(c->txt_pins[c->txt_slot].ensure(z1_at + z1 + 16));
+        char* pin = c->txt_pins[c->txt_slot].as<char>();
+        if (z0) HIPCHK(hipMemcpyAsync(pin, M, z0, hipMemcpyDeviceToHost, st));
+        if (z1) HIPCHK(hipMemcpyAsync(pin + z1_at, M + b0, z1, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        G.raw[0] = kh_n; G.raw[1] = hp_n;
+        *kh = pin; *kh_bytes = z0;
+        *hp = pin + z1_at; *hp_bytes = z1;
+        return PF_OK;
+    }
     if (kh_n) HIPCHK(hipMemcpyAsync(txt_pin, c->txt_dev.p, kh_n, hipMemcpyDeviceToHost, st));
     if (hp_n) HIPCHK(hipMemcpyAsync(txt_pin + hp_at, c->txt_dev.as<char>() + hp_at, hp_n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *kh = txt_pin; *kh_bytes = kh_n;
     *hp = txt_pin + hp_at; *hp_bytes = hp_n;
+    return PF_OK;
+}
+
+int pf_set_device_gzip(pf_ctx* c, int on, uint32_t flags) {
+    if (!c) return fail(PF_ERR_ARG, "pf_set_device_gzip: null argument");
+    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY)) return fail(PF_ERR_ARG, "pf_set_device_gzip: unknown flag");
+    HIPCHK(hipSetDevice(c->device));
+    kt_stream_end(c);                     // (an open stream would change its kind half way)
+    if (on) {
+        PFCHK(c->gz.ensure(c->n_cu));
+        PFCHK(c->gzm.pin_cursor.ensure(64, true));
+    }
+    c->gzm.on = on != 0; c->gzm.flags = flags;
+    return PF_OK;
+}
+
+int pf_device_gzip_text_bytes(pf_ctx* c, uint64_t out[3]) {
+    if (!c || !out) return fail(PF_ERR_ARG, "pf_device_gzip_text_bytes: null argument");
+    for (int i = 0; i < 3; i++) out[i] = c->gzm.raw[i];
+    return PF_OK;
+}
+
+int pf_gzip_device_last_ms(pf_ctx* c, float* ms) {
+    if (!c || !ms) return fail(PF_ERR_ARG, "pf_gzip_device_last_ms: null argument");
+    *ms = c->gzm.encode_ms;
+    return PF_OK;
+}
+
+int pf_gzip_device(pf_ctx* c, const char* data, uint64_t n, uint32_t flags, char** out, uint64_t* out_n) {
+    if (!c || (!data && n) || !out || !out_n) return fail(PF_ERR_ARG, "pf_gzip_device: null argument");
+    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY)) return fail(PF_ERR_ARG, "pf_gzip_device: unknown flag");
+    *out = nullptr; *out_n = 0;
+    if (!n) {
+        if (!(*out = (char*)malloc(1))) return fail(PF_ERR_OOM, "pf_gzip_device: out of memory");
+        return PF_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    PFCHK(c->gz.ensure(c->n_cu));
+    PFCHK(c->gzm.pin_cursor.ensure(64, true));
+    HIPCHK(hipStreamSynchronize(c->side));
+    hipStream_t st = c->stream;
+    DevBuf text, members;
+    const uint64_t cap = PfGzEncoder::bound(n);
+    PFCHK(text.ensure(n + 16, true));
+    PFCHK(members.ensure(cap, true));
+    uint64_t* cur = c->gzm.pin_cursor.as<uint64_t>();
+    HIPCHK(hipMemcpyAsync(text.p, data, n, hipMemcpyHostToDevice, st));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    PFCHK(get_event(c, &e0));
+    if (get_event(c, &e1) != PF_OK) { c->ev_pool.push_back(e0); return PF_ERR_HIP; }
+    // (the two events go back to the pool whichever step fails)
+    auto encode = [&]() -> int {
+        HIPCHK(hipEventRecord(e0, st));
+        PFCHK(c->gz.begin(st, 0));
+        PFCHK(c->gz.append(st, 0, text.as<char>(), n, flags, members.as<char>(), cap));
+        HIPCHK(hipEventRecord(e1, st));
+        PFCHK(c->gz.read_cursor(st, 0, cur));
+        HIPCHK(hipStreamSynchronize(st));
+        c->gzm.encode_ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&c->gzm.encode_ms, e0, e1));
+        return PF_OK;
+    };
+    const int enc_rc = encode();
+    c->ev_pool.push_back(e0); c->ev_pool.push_back(e1);
+    PFCHK(enc_rc);
+    const uint64_t z = cur[0];
+    if (z > cap) return fail(PF_ERR_STATE, "pf_gzip_device: the members exceed their bound");
+    char* buf = (char*)malloc(z ? z : 1);
+    if (!buf) return fail(PF_ERR_OOM, "pf_gzip_device: out of memory");
+    const hipError_t e = hipMemcpy(buf, members.p, z, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { free(buf); return fail(PF_ERR_HIP, "pf_gzip_device: copy failed: %s", hipGetErrorString(e)); }
+    *out = buf; *out_n = z;
     return PF_OK;
 }
 

@@ -1,0 +1,351 @@
+// pf_deflate.hip -- the deflate encoder on the device (format logic: pf_deflate.h) and the host model's entry point.
+//
+// gz_encode_kernel: one workgroup of 256 threads per chunk of CHUNK bytes (a grid of two workgroups per CU walks the
+// chunks).  The chunk's text is staged in LDS beside a hash table of 4 096 positions.  Matches are found in steps of 256
+// positions, one per thread.  The positions look their 4-byte hash up and go into the table eight at a time, in text
+// order, by atomicMax: a position's candidate is the largest position with its hash among the groups of eight before its
+// own, whatever order the lanes ran in -- the same text gives the same bytes.  The compares then run 256 wide.  One lane
+// walks the step's match lengths greedily (a match, or one literal, then the position behind it); the token starts it
+// lists become tokens, in parallel, in a stream in global memory, and the histograms are kept by LDS atomics.
+// The coding pass sorts the used symbols by rank counting, builds the two length-limited codes (one lane each), sums
+// the exact sizes of the three block types, and places the tokens' bits by wave prefix sums into a staging area that
+// takes the place of the text and the table; the member leaves LDS in whole words.
+// LDS: 48 KiB of text + table, 10 KiB of tables -- under 64 KiB, two workgroups per CU within its 160 KiB.
+// gz_scan_kernel / gz_gather_kernel: the member sizes summed from an append cursor, the members copied from their
+// worst-case slots to their places, contiguous, so that one copy takes them to the host.
+#include "pf_deflate.h"
+
+#include <cstdlib>
+#include <cstring>
+
+namespace pfgz {
+
+constexpr int THREADS = 256;
+constexpr uint32_t TEXT_WORDS = (CHUNK + 16) / 4, TAB_WORDS = 1u << HASH_BITS;
+static_assert(CHUNK == THREADS * CRC_SUB, "one CRC piece per thread");
+static_assert(SLOT_WORDS <= TEXT_WORDS + TAB_WORDS, "the staging area takes the place of the text and the table");
+static_assert(CHUNK <= 32768, "distances reach 32 768 at most, a stored block 65 535 bytes");
+
+struct EncParams {
+    const uint8_t* text; uint64_t n; uint32_t nchunks, flags;
+    uint8_t* slots; uint32_t* sizes; uint32_t* tokens;
+};
+
+__device__ inline uint32_t wave_inclusive_sum(uint32_t x, uint32_t lane) {
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(x, d, 64);
+        if (lane >= d) x += t;
+    }
+    return x;
+}
+
+__device__ inline uint32_t load4(const uint8_t* p) {
+    uint32_t w;
+    __builtin_memcpy(&w, p, 4);
+    return w;
+}
+
+// symbols tid and tid + 256 of a histogram of nsym entries into `sorted`, by ascending (frequency, symbol), the unused
+// ones left out; returns through *n_used (zeroed by the caller before the barrier in front of this)
+__device__ inline void rank_sort(const uint32_t* hist, uint32_t nsym, SymFreq* sorted, uint32_t* n_used, uint32_t tid) {
+    for (uint32_t s = tid; s < nsym; s += THREADS) {
+        const uint32_t f = hist[s];
+        if (!f) continue;
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < nsym; j++) {
+            const uint32_t g = hist[j];
+            rank += (g != 0 && (g < f || (g == f && j < s))) ? 1u : 0u;
+        }
+        sorted[rank] = SymFreq{f, s};
+        atomicAdd(n_used, 1u);
+    }
+}
+
+__global__ __launch_bounds__(THREADS, 2) void gz_encode_kernel(EncParams P) {
+    __shared__ uint32_t s_buf[TEXT_WORDS + TAB_WORDS];       // the text, the hash table; later the member's staging
+    __shared__ uint16_t s_mlen[2][THREADS], s_mdist[2][THREADS], s_tokpos[2][THREADS];
+    __shared__ uint32_t s_cnt[2], s_carry, s_nused[2], s_bits[3], s_wsum[2][4];
+    __shared__ uint32_t s_ll_hist[288], s_d_hist[32];
+    __shared__ Codes s_dyn;
+    __shared__ SymFreq s_sort_ll[288], s_sort_d[32];
+    __shared__ uint32_t s_crc[THREADS], s_crclen[THREADS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint8_t* s_text = reinterpret_cast<uint8_t*>(s_buf);
+    uint32_t* s_tab = s_buf + TEXT_WORDS;
+    uint32_t* tokens = P.tokens + (size_t)blockIdx.x * CHUNK;
+    const bool lit_only = (P.flags & PF_GZ_LITERALS_ONLY) != 0;
+
+    for (uint32_t chunk = blockIdx.x; chunk < P.nchunks; chunk += gridDim.x) {
+        const uint64_t start = (uint64_t)chunk * CHUNK;
+        const uint32_t n = (uint32_t)(P.n - start < CHUNK ? P.n - start : CHUNK);
+        const uint8_t* src = P.text + start;
+        uint8_t* slot = P.slots + (size_t)chunk * SLOT_BYTES;
+        // ---- stage the text, clear the table and the histograms
+        if ((reinterpret_cast<uintptr_t>(src) & 3) == 0) {
+            const uint32_t* src4 = reinterpret_cast<const uint32_t*>(src);
+            for (uint32_t i = tid; i < n / 4; i += THREADS) s_buf[i] = src4[i];
+            for (uint32_t i = (n & ~3u) + tid; i < n; i += THREADS) s_text[i] = src[i];
+        } else {
+            for (uint32_t i = tid; i < n; i += THREADS) s_text[i] = src[i];
+        }
+        for (uint32_t i = tid; i < TAB_WORDS; i += THREADS) s_tab[i] = 0;
+        for (uint32_t i = tid; i < 288; i += THREADS) { s_ll_hist[i] = i == 256 ? 1u : 0u; s_dyn.ll_len[i] = 0; }
+        if (tid < 32) { s_d_hist[tid] = 0; s_dyn.d_len[tid] = 0; }
+        if (tid == 0) { s_carry = 0; s_nused[0] = s_nused[1] = 0; s_bits[0] = s_bits[1] = s_bits[2] = 0; }
+        __syncthreads();
+
+        // ---- matches and the greedy parse, 256 positions a step
+        uint32_t ntok = 0;
+        for (uint32_t s0 = 0, par = 0; s0 < n; s0 += THREADS, par ^= 1) {
+            const uint32_t p = s0 + tid;
+            uint32_t L = 0, D = 0, cand = 0;
+            const bool hashed = p + 3 < n;
+            const uint32_t h = hashed ? hash4(load4(s_text + p)) : 0;
+            // look up, then insert, eight positions at a time in text order: a group's candidates are the positions of
+            // the groups before it, two positions of one group with the same hash leave the larger (atomicMax).  Between
+            // waves a barrier keeps that order; inside a wave the groups are eight masked sequences, kept apart by a
+            // wave-level fence and executed in the order they were issued.  Were the groups ever merged into one, a
+            // position would only lose the candidates of its own step's earlier groups: the bytes would still depend on
+            // the text alone and decode to it, and the files would grow (the row before, 60 to 230 bytes back, is these
+            // texts' nearest repeat) -- tools/gzip_device_bench.py's ratio against zlib level 1 shows it.
+            for (uint32_t w = 0; w < THREADS / 64; w++) {
+                if (wave == w)
+                    for (uint32_t g = 0; g < 8; g++) {
+                        if ((lane >> 3) == g && hashed) {
+                            cand = __hip_atomic_load(&s_tab[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            atomicMax(&s_tab[h], p + 1);
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    }
+                __syncthreads();
+            }
+            if (cand && p >= s_carry && !lit_only) {          // (a position inside the match carried in needs none)
+                const uint32_t c = cand - 1, maxl = min(MAX_MATCH, n - p);
+                uint32_t l = 0;
+                while (l + 4 <= maxl && load4(s_text + c + l) == load4(s_text + p + l)) l += 4;
+                while (l < maxl && s_text[c + l] == s_text[p + l]) l++;
+                if (match_ok(l, p - c)) { L = l; D = p - c; }
+            }
+            s_mlen[par][tid] = (uint16_t)L; s_mdist[par][tid] = (uint16_t)(D ? D - 1 : 0);
+            __syncthreads();
+            if (tid == 0) {
+                const uint32_t end = min(s0 + THREADS, n);
+                uint32_t q = max(s0, s_carry), cnt = 0;
+                while (q < end) {
+                    const uint32_t l = s_mlen[par][q - s0];
+                    s_tokpos[par][cnt++] = (uint16_t)(q - s0);
+                    q += l ? l : 1;
+                }
+                s_cnt[par] = cnt; s_carry = q;
+            }
+            __syncthreads();
+            const uint32_t cnt = s_cnt[par];
+            if (tid < cnt) {
+                const uint32_t q = s_tokpos[par][tid], l = s_mlen[par][q];
+                uint32_t tok;
+                if (l) {
+                    uint32_t eb, ev;
+                    const uint32_t d = s_mdist[par][q];
+                    tok = 0x80000000u | ((l - 3) << 16) | d;
+                    atomicAdd(&s_ll_hist[len_sym(l, &eb, &ev)], 1u);
+                    atomicAdd(&s_d_hist[dist_sym(d, &eb, &ev)], 1u);
+                } else {
+                    tok = s_text[s0 + q];
+                    atomicAdd(&s_ll_hist[tok], 1u);
+                }
+                tokens[ntok + tid] = tok;
+            }
+            ntok += cnt;
+        }
+        __syncthreads();
+
+        // ---- the chunk's CRC: a piece per thread, combined pairwise
+        {
+            const uint32_t at = tid * CRC_SUB, m = at < n ? min(CRC_SUB, n - at) : 0;
+            s_crc[tid] = m ? crc32_bytes(s_text + at, m) : 0;
+            s_crclen[tid] = m;
+        }
+        // ---- the dynamic codes: used symbols sorted by rank counting, then one lane per code
+        rank_sort(s_ll_hist, N_LL, s_sort_ll, &s_nused[0], tid);
+        rank_sort(s_d_hist, N_D, s_sort_d, &s_nused[1], tid);
+        __syncthreads();
+        for (uint32_t step = 1; step < THREADS; step <<= 1) {
+            if ((tid & (2 * step - 1)) == 0 && s_crclen[tid + step]) {
+                s_crc[tid] = s_crclen[tid] ? crc_combine(s_crc[tid], s_crc[tid + step], s_crclen[tid + step]) : s_crc[tid + step];
+                s_crclen[tid] += s_crclen[tid + step];
+            }
+            if (step == 1) {
+                if (tid == 0) { build_lengths(s_sort_ll, (int)s_nused[0], s_dyn.ll_len); canonical_codes(s_dyn.ll_len, N_LL, s_dyn.ll_code); }
+                if (tid == 64) { build_lengths(s_sort_d, (int)s_nused[1], s_dyn.d_len); canonical_codes(s_dyn.d_len, N_D, s_dyn.d_code); }
+            }
+            __syncthreads();
+        }
+        // ---- the exact sizes of the block types
+        {
+            uint32_t b[3] = {0, 0, 0};
+            for (uint32_t s = tid; s < N_LL; s += THREADS) ll_sym_bits(s, s_ll_hist[s], s_dyn, b);
+            if (tid < N_D) d_sym_bits(tid, s_d_hist[tid], s_dyn, b);
+            for (int k = 0; k < 3; k++) {
+                uint32_t v = wave_inclusive_sum(b[k], lane);
+                if (lane == 63 && v) atomicAdd(&s_bits[k], v);
+            }
+        }
+        __syncthreads();
+        uint32_t coded = 0;
+        const uint32_t bits[3] = {s_bits[0], s_bits[1], s_bits[2]};
+        const Mode mode = choose_mode(bits, n, P.flags, &coded);
+        const uint32_t crc = s_crc[0], mbytes = member_bytes(coded);
+        if (mode == STORED) {
+            // the member straight from the staged text: head, 01 LEN NLEN, the bytes, CRC32, ISIZE
+            if (tid < 23) {
+                const uint8_t head[15] = {0x1F, 0x8B, 8, 0, 0, 0, 0, 0, 0, 0xFF, 1, (uint8_t)n, (uint8_t)(n >> 8), (uint8_t)~n, (uint8_t)(~n >> 8)};
+                if (tid < 15) slot[tid] = head[tid];
+                else if (tid < 19) slot[15 + n + (tid - 15)] = (uint8_t)(crc >> (8 * (tid - 15)));
+                else slot[15 + n + (tid - 15)] = (uint8_t)(n >> (8 * (tid - 19)));
+            }
+            for (uint32_t i = tid; i < n; i += THREADS) slot[15 + i] = s_text[i];
+        } else {
+            __syncthreads();                                   // (the text's last readers: the CRC pieces, long done)
+            for (uint32_t i = tid; i < SLOT_WORDS; i += THREADS) s_buf[i] = 0;
+            if (mode == FIXED) {
+                for (uint32_t s = tid; s < 288; s += THREADS) { s_dyn.ll_len[s] = (uint8_t)fixed_ll_len(s); s_dyn.ll_code[s] = (uint16_t)fixed_ll_code(s); }
+                if (tid < 32) { s_dyn.d_len[tid] = 5; s_dyn.d_code[tid] = (uint16_t)bit_reverse(tid, 5); }
+            }
+            __syncthreads();
+            uint32_t base = 8 * MEMBER_HEAD + 3 + (mode == DYNAMIC ? DYN_HEADER_FIXED_BITS + bits[2] : 0);
+            if (tid == 0) {
+                put_member_head(s_buf);
+                put_bits(s_buf, 8 * MEMBER_HEAD, 1 | (uint32_t)mode << 1, 3);
+                if (mode == DYNAMIC) (void)put_dyn_header(s_buf, 8 * MEMBER_HEAD + 3, s_dyn);
+                put_member_tail(s_buf, coded, crc, n);
+            }
+            for (uint32_t r = 0, par = 0; r < ntok; r += THREADS, par ^= 1) {
+                uint64_t val = 0;
+                const uint32_t nb = r + tid < ntok ? token_bits(tokens[r + tid], s_dyn, &val) : 0;
+                const uint32_t incl = wave_inclusive_sum(nb, lane);
+                if (lane == 63) s_wsum[par][wave] = incl;
+                __syncthreads();
+                uint32_t before = 0, total = 0;
+                for (uint32_t w = 0; w < 4; w++) { const uint32_t x = s_wsum[par][w]; total += x; before += w < wave ? x : 0; }
+                // (the sizes are exact, so the tokens end where the count said; a bit past it would be a bug, never a write)
+                if (base + before + incl <= 8 * MEMBER_HEAD + coded) put_bits(s_buf, base + before + incl - nb, val, nb);
+                base += total;
+            }
+            if (tid == 0 && base + s_dyn.ll_len[256] <= 8 * MEMBER_HEAD + coded) put_bits(s_buf, base, s_dyn.ll_code[256], s_dyn.ll_len[256]);
+            __syncthreads();
+            uint32_t* slot4 = reinterpret_cast<uint32_t*>(slot);
+            for (uint32_t i = tid; i < (mbytes + 3) / 4; i += THREADS) slot4[i] = s_buf[i];
+        }
+        if (tid == 0) P.sizes[chunk] = mbytes;
+        __syncthreads();                                       // the next chunk's text goes where this one's member stood
+    }
+}
+
+// offs[i] = *cursor + the sizes before chunk i; *cursor advances by their sum.  One workgroup; thread 0 alone reads and
+// writes the cursor, the others get its value through LDS.
+__global__ __launch_bounds__(THREADS) void gz_scan_kernel(const uint32_t* sizes, uint32_t n, uint64_t* offs, uint64_t* cursor) {
+    __shared__ uint32_t s_w[4];
+    __shared__ uint64_t s_base;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) s_base = *cursor;
+    __syncthreads();
+    uint64_t base = s_base;
+    for (uint32_t r = 0; r < n; r += THREADS) {
+        const uint32_t v = r + tid < n ? sizes[r + tid] : 0, incl = wave_inclusive_sum(v, lane);
+        if (lane == 63) s_w[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < 4; w++) { total += s_w[w]; before += w < wave ? s_w[w] : 0; }
+        if (r + tid < n) offs[r + tid] = base + before + incl - v;
+        base += total;
+        __syncthreads();
+    }
+    if (tid == 0) *cursor = base;
+}
+
+// chunk i's member from its slot to members + offs[i]; a member that would pass `cap` is left out (the host sized the
+// buffer for the worst case: it never is).  The bytes up to the destination's next 16-byte boundary and the last few go
+// one by one, the rest in 16-byte units, stored aligned.
+__global__ __launch_bounds__(THREADS) void gz_gather_kernel(const uint8_t* slots, const uint32_t* sizes, const uint64_t* offs,
+                                                            uint8_t* members, uint64_t cap) {
+    const uint32_t chunk = blockIdx.x, m = sizes[chunk], tid = threadIdx.x;
+    const uint64_t at = offs[chunk];
+    if (at + m > cap) return;
+    const uint8_t* src = slots + (size_t)chunk * SLOT_BYTES;
+    uint8_t* dst = members + at;
+    const uint32_t head = min(m, (uint32_t)(-reinterpret_cast<uintptr_t>(dst) & 15));
+    if (tid < head) dst[tid] = src[tid];
+    const uint32_t nvec = (m - head) / 16, done = head + 16 * nvec;
+    for (uint32_t i = tid; i < nvec; i += THREADS) {
+        uint4 v;
+        __builtin_memcpy(&v, src + head + 16 * i, 16);
+        *reinterpret_cast<uint4*>(dst + head + 16 * i) = v;
+    }
+    if (done + tid < m) dst[done + tid] = src[done + tid];
+}
+
+}  // namespace pfgz
+
+int PfGzEncoder::ensure(int n_cu) {
+    const uint32_t grid = (uint32_t)std::max(1, n_cu) * 2;
+    const uint64_t nch = BLOCK / pfgz::CHUNK;
+    PFCHK(slots.ensure(nch * pfgz::SLOT_BYTES, true));
+    PFCHK(sizes.ensure(nch * 4, true));
+    PFCHK(offs.ensure(nch * 8, true));
+    PFCHK(tokens.ensure((uint64_t)grid * pfgz::CHUNK * 4, true));
+    if (!cursors.p) {
+        PFCHK(cursors.ensure(N_CURSORS * 8, true));
+        HIPCHK(hipMemset(cursors.p, 0, N_CURSORS * 8));
+    }
+    grid_cap = grid;
+    return PF_OK;
+}
+
+int PfGzEncoder::begin(hipStream_t st, int which) {
+    if (which < 0 || which >= N_CURSORS || !cursors.p) return fail(PF_ERR_STATE, "gzip encoder: no such cursor");
+    HIPCHK(hipMemsetAsync(cursors.as<uint64_t>() + which, 0, 8, st));
+    return PF_OK;
+}
+
+int PfGzEncoder::append(hipStream_t st, int which, const char* text, uint64_t n, uint32_t flags, char* members, uint64_t cap) {
+    if (which < 0 || which >= N_CURSORS || !grid_cap) return fail(PF_ERR_STATE, "gzip encoder: not set up");
+    for (uint64_t at = 0; at < n; at += BLOCK) {
+        const uint64_t m = std::min(BLOCK, n - at);
+        const uint32_t nch = (uint32_t)chunks(m);
+        pfgz::EncParams P{reinterpret_cast<const uint8_t*>(text) + at, m, nch, flags, slots.as<uint8_t>(), sizes.as<uint32_t>(),
+                          tokens.as<uint32_t>()};
+        hipLaunchKernelGGL(pfgz::gz_encode_kernel, dim3(std::min(nch, grid_cap)), dim3(pfgz::THREADS), 0, st, P);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(pfgz::gz_scan_kernel, dim3(1), dim3(pfgz::THREADS), 0, st, sizes.as<uint32_t>(), nch, offs.as<uint64_t>(),
+                           cursors.as<uint64_t>() + which);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(pfgz::gz_gather_kernel, dim3(nch), dim3(pfgz::THREADS), 0, st, slots.as<uint8_t>(), sizes.as<uint32_t>(),
+                           offs.as<uint64_t>(), reinterpret_cast<uint8_t*>(members), cap);
+        HIPCHK(hipGetLastError());
+    }
+    return PF_OK;
+}
+
+int PfGzEncoder::read_cursor(hipStream_t st, int which, uint64_t* host) {
+    HIPCHK(hipMemcpyAsync(host, cursors.as<uint64_t>() + which, 8, hipMemcpyDeviceToHost, st));
+    return PF_OK;
+}
+
+extern "C" {
+
+uint32_t pf_gzip_device_chunk_bytes(void) { return pfgz::CHUNK; }
+
+int pf_gzip_host_model(const char* data, uint64_t n, uint32_t flags, char** out, uint64_t* out_n) {
+    if ((!data && n) || !out || !out_n) return fail(PF_ERR_ARG, "pf_gzip_host_model: null argument");
+    *out = nullptr; *out_n = 0;
+    std::vector<uint8_t> members;
+    if (!pfgz::host_model(reinterpret_cast<const uint8_t*>(data), n, flags, members))
+        return fail(PF_ERR_STATE, "pf_gzip_host_model: a block's size differs from its count");
+    char* buf = (char*)malloc(members.size() ? members.size() : 1);
+    if (!buf) return fail(PF_ERR_OOM, "pf_gzip_host_model: out of memory");
+    if (!members.empty()) memcpy(buf, members.data(), members.size());
+    *out = buf; *out_n = members.size();
+    return PF_OK;
+}
+
+}  // extern "C"

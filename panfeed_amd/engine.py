@@ -99,6 +99,31 @@ class DeviceText:
         return bytes(out)
 
 
+class GzipMembers:
+    """complete gzip members the GPU made of a text (Engine(device_gzip=True)): `view` holds them (as long-lived as
+    the text it stands for would be), `text_bytes` is the size of the text they decode to -- None where the producer does
+    not know it per block (the stream's blocks: the stream reports its text bytes as a whole); len() is the compressed
+    size"""
+
+    def __init__(self, view, text_bytes=None):
+        self.view, self.text_bytes = view, None if text_bytes is None else int(text_bytes)
+
+    def __len__(self):
+        return len(self.view)
+
+    def __bytes__(self):
+        return bytes(self.view)
+
+
+def text_len(data):
+    """bytes of text `data` stands for: its own length, or what a GzipMembers decodes to"""
+    if not isinstance(data, GzipMembers):
+        return len(data)
+    if data.text_bytes is None:
+        raise ValueError("these gzip members' text size is not known")
+    return data.text_bytes
+
+
 def _view(ptr, n, dtype):
     if n == 0:
         return np.zeros(0, dtype=dtype)
@@ -115,6 +140,11 @@ class BatchOutput:
         self.per_cluster = []   # multiple_files: [(idx, kmers_tsv, kmers_to_hashes, hashes_to_patterns)]
         self.stats = {}
         self.timing = {}
+
+    @property
+    def gzip_members(self):
+        """whether kmers_to_hashes and hashes_to_patterns are gzip members (GzipMembers) instead of text"""
+        return isinstance(self.kmers_to_hashes, GzipMembers) and isinstance(self.hashes_to_patterns, GzipMembers)
 
 
 def _batch_stats(hb, res, patterns, **streamed):
@@ -134,7 +164,7 @@ class Engine:
     def __init__(self, klength=31, canon=True, consider_missing=False, patfilt=True, maf=0.01,
                  multiple_files=False, max_strains=1024, stroi=(), device=0, pattern_capacity=0,
                  max_items=0, dedup=True, unit_dedup=True, key_binning=True, device_plan=False,
-                 targets_text_budget=8 << 30):
+                 targets_text_budget=8 << 30, device_gzip=False, device_gzip_flags=0):
         self.L = _lib.load()
         # device memory a batch's kmers.tsv text may take when it is streamed to a targets_sink (stream_targets_device)
         self.targets_text_budget = int(targets_text_budget)
@@ -156,6 +186,11 @@ class Engine:
                       (0 if key_binning else _lib.FLAG_NO_KEY_BINNING) | (_lib.FLAG_DEVICE_PLAN if device_plan else 0))
         self.ctx = C.c_void_p()
         _lib.check(self.L.pf_create(C.byref(self.ctx), int(device), C.byref(o)))
+        # device_gzip: the texts the GPU writes (render_device, stream_targets_device) leave it as gzip members; the host
+        # renderers, and with them every --multiple-files run, are not affected
+        self.device_gzip = bool(device_gzip) and not self.multiple_files
+        if self.device_gzip:
+            _lib.check(self.L.pf_set_device_gzip(self.ctx, 1, int(device_gzip_flags)))
         self.next_ordinal = 0
         self._md5_b64 = {}      # pattern id -> 24-char hash string (patterns seen so far)
         self.n_patterns = 0
@@ -321,6 +356,7 @@ class Engine:
                     # target strains: their rows written by the GPU too (the next submit reuses the device's text
                     # block, so the rows come over now)
                     streamed, ranges, peak = 0, 0, 0
+                    self.stream_compressed = 0
                     if hb.n_targets and targets_sink is not None:
                         # in ranges of at most targets_text_budget bytes of device memory
                         streamed, ranges, peak = self.stream_targets_device(hb, targets_sink)
@@ -329,6 +365,8 @@ class Engine:
                         out.kmers_tsv = bytes(self.render_targets_device(hb)) if hb.n_targets else b""
                     out.stats = _batch_stats(hb, res, self.pattern_count(), kmers_tsv_streamed=streamed,
                                              kmers_tsv_ranges=ranges, kmers_tsv_peak_device_bytes=peak)
+                    if self.device_gzip:
+                        out.stats["compressed_bytes"] = len(texts[0]) + len(texts[1]) + self.stream_compressed
                     out.timing = self.timing()
                 else:
                     out = self._render(hb, self.fetch(), defer_patterns)
@@ -450,6 +488,10 @@ class Engine:
         _lib.check(self.L.pf_render_device_ex(self.ctx, names, extra, len(hb.extra_keys),
                                               _lib.RENDER_NO_PATTERN_ROWS if defer_patterns else 0,
                                               C.byref(kh), C.byref(kn), C.byref(hp), C.byref(hn)))
+        if self.device_gzip:
+            raw = (C.c_uint64 * 3)()
+            _lib.check(self.L.pf_device_gzip_text_bytes(self.ctx, raw))
+            return GzipMembers(_mem(kh, kn.value), raw[0]), GzipMembers(_mem(hp, hn.value), raw[1])
         return _mem(kh, kn.value), _mem(hp, hn.value)
 
     # ------------------------------------------------------------------ run-global patterns (multi-GPU)
@@ -497,6 +539,7 @@ class Engine:
         t0 = time.time()
         budget = self.targets_text_budget if budget is None else int(budget)
         streamed = 0
+        self.stream_compressed = 0
         # (the records and the strings they point to are read until the last block: the host renders its share of
         # every range when the range is written)
         with self._target_records(hb) as (arr, n):
@@ -509,8 +552,16 @@ class Engine:
                 _lib.check(self.L.pf_kmers_tsv_stream_next(self.ctx, C.byref(ptr), C.byref(nb)))
                 if not nb.value:
                     break
-                sink(_mem(ptr, nb.value))
-                streamed += int(nb.value)
+                if self.device_gzip:            # a block's members; the text bytes behind them are asked for below
+                    sink(GzipMembers(_mem(ptr, nb.value), None))
+                    self.stream_compressed += int(nb.value)
+                else:
+                    sink(_mem(ptr, nb.value))
+                    streamed += int(nb.value)
+            if self.device_gzip:
+                raw = (C.c_uint64 * 3)()
+                _lib.check(self.L.pf_device_gzip_text_bytes(self.ctx, raw))
+                streamed = int(raw[2])
         if streamed != int(total.value):
             raise _lib.PanfeedHipError(_lib.ERR_STATE, f"kmers.tsv stream: {streamed} bytes handed out of {total.value}")
         self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": time.time() - t1, "copy_s": 0.0}

@@ -5,7 +5,7 @@ import io
 import os
 
 from . import _lib
-from .engine import KMERS_TSV_HEADER, KMERS_TO_HASHES_HEADER, _mem, hashes_to_patterns_header
+from .engine import KMERS_TSV_HEADER, KMERS_TO_HASHES_HEADER, GzipMembers, _mem, hashes_to_patterns_header
 
 
 class ParallelGzipWriter:
@@ -66,9 +66,67 @@ class ParallelGzipWriter:
         self.close()
 
 
-def create_kmer_stroi(output, compress=False):
-    """kmers.tsv[.gz] with its header written (input.py:235-247)."""
-    if not compress:
+class MemberGzipWriter:
+    """A .gz file made of gzip members from two sources: `write(text)` compresses the text on the host into one member
+    (the header line; the batches that fell back to the host renderers), `write_members(view)` appends members that are
+    complete already -- the GPU's (Engine(device_gzip=True)) -- as they are.  The first write is the file's header, so an
+    output with no rows is still a valid gzip file.  `bytes_written` / `header_bytes` / `host_bytes`: the file's size, its
+    first member's, and that of the members compressed here behind the header."""
+
+    def __init__(self, path, compresslevel=9):
+        self.fh = open(path, "wb")
+        self.level = compresslevel
+        self.bytes_written = 0
+        self.header_bytes = None
+        self.host_bytes = 0
+        self.closed = False
+
+    def write(self, text):
+        import gzip
+        b = text.encode() if isinstance(text, str) else bytes(text)
+        if not b:
+            return 0
+        member = gzip.compress(b, compresslevel=self.level, mtime=0)
+        if self.header_bytes is None:
+            self.header_bytes = len(member)
+        else:
+            self.host_bytes += len(member)
+        self.fh.write(member)
+        self.bytes_written += len(member)
+        return len(text)
+
+    def write_members(self, view):
+        if len(view):
+            if self.header_bytes is None:
+                self.header_bytes = 0
+            self.fh.write(view)
+            self.bytes_written += len(view)
+
+    def flush(self):
+        self.fh.flush()
+
+    def close(self):
+        if self.closed:
+            return
+        if not self.bytes_written:              # nothing at all was written: an empty member
+            import gzip
+            self.fh.write(gzip.compress(b"", compresslevel=self.level, mtime=0))
+        self.fh.close()
+        self.closed = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def create_kmer_stroi(output, compress=False, device_gzip=False):
+    """kmers.tsv[.gz] with its header written (input.py:235-247).  device_gzip: a writer that also takes the GPU's
+    members."""
+    if device_gzip:
+        fh = MemberGzipWriter(os.path.join(output, "kmers.tsv.gz"))
+    elif not compress:
         fh = open(os.path.join(output, "kmers.tsv"), "w")
     else:
         fh = ParallelGzipWriter(os.path.join(output, "kmers.tsv.gz"), compresslevel=9)
@@ -77,9 +135,12 @@ def create_kmer_stroi(output, compress=False):
     return fh
 
 
-def create_hash_files(output, compress=False):
+def create_hash_files(output, compress=False, device_gzip=False):
     """(hashes_to_patterns, kmers_to_hashes) handles, no headers yet (input.py:249-259)."""
-    if not compress:
+    if device_gzip:
+        hash_pat = MemberGzipWriter(os.path.join(output, "hashes_to_patterns.tsv.gz"))
+        kmer_hash = MemberGzipWriter(os.path.join(output, "kmers_to_hashes.tsv.gz"))
+    elif not compress:
         hash_pat = open(os.path.join(output, "hashes_to_patterns.tsv"), "w")
         kmer_hash = open(os.path.join(output, "kmers_to_hashes.tsv"), "w")
     else:
@@ -119,8 +180,11 @@ def write_cluster_dir(output, idx, strains, kmers_tsv, kmers_to_hashes, hashes_t
 
 def write_text(fh, data):
     """`data` -- str, or the bytes-like text the GPU wrote -- into `fh`: a text file, a binary file or a
-    ParallelGzipWriter.  Bytes go straight into a text file's binary layer."""
-    if isinstance(data, str):
+    ParallelGzipWriter.  Bytes go straight into a text file's binary layer.  Gzip members the GPU made (a GzipMembers:
+    the batch output says what it carries, the bytes are not looked at) are appended by a MemberGzipWriter as they are."""
+    if isinstance(data, GzipMembers):
+        fh.write_members(data.view)
+    elif isinstance(data, str):
         fh.write(data.encode() if isinstance(fh, io.BufferedIOBase) else data)
     elif len(data):
         raw = getattr(fh, "buffer", None)

@@ -13,7 +13,7 @@ import threading
 import time
 
 from . import _lib
-from .engine import Engine, add_batch_stats
+from .engine import Engine, add_batch_stats, text_len
 from .native_input import Pangenome
 from .output import create_hash_files, create_kmer_stroi, write_cluster_dir, write_strain_headers, write_text
 
@@ -64,8 +64,9 @@ def settle_context(pg, eng, open_reader):
 class _FileRun:
     """What the steps of one `run_files` call share."""
 
-    def __init__(self, output, compress, multiple_files):
+    def __init__(self, output, compress, multiple_files, device_gzip=False):
         self.output, self.compress, self.multiple_files = output, compress, multiple_files
+        self.device_gzip = device_gzip and not multiple_files      # (per-cluster directories keep the host path)
         self.t_start = time.perf_counter()
         # where the wall time went: opening + parsing the inputs, creating the context, uploading the genomes, then the
         # overlapped stages of the batches (Engine.run_batches: read + pack on its thread, pf_submit = upload + kernels,
@@ -189,8 +190,8 @@ def _start_upload(run, pg, eng, resident, overlap):
 def _open_outputs(run, strains):
     run.strains = list(strains)
     if not run.multiple_files:
-        run.kmer_stroi = create_kmer_stroi(run.output, run.compress)
-        run.hash_pat, run.kmer_hash = create_hash_files(run.output, run.compress)
+        run.kmer_stroi = create_kmer_stroi(run.output, run.compress, run.device_gzip)
+        run.hash_pat, run.kmer_hash = create_hash_files(run.output, run.compress, run.device_gzip)
         write_strain_headers(run.hash_pat, run.kmer_hash, run.strains)
 
 
@@ -215,7 +216,9 @@ def _write_batches(run, eng, pg, stats, batch_clusters, device_text):
                 break
             add_batch_stats(stats, o)
             stats["patterns"] = o.stats.get("patterns", stats["patterns"])
-            stats["bytes"] += (len(o.kmers_tsv) + len(o.kmers_to_hashes) + len(o.hashes_to_patterns) +
+            if run.device_gzip:                 # the members the GPU made of this batch, by the encoder's own count
+                stats["compressed_bytes"] = stats.get("compressed_bytes", 0) + o.stats.get("compressed_bytes", 0)
+            stats["bytes"] += (text_len(o.kmers_tsv) + text_len(o.kmers_to_hashes) + text_len(o.hashes_to_patterns) +
                                o.stats.get("kmers_tsv_streamed", 0))
             q.put(o)
     finally:
@@ -224,6 +227,8 @@ def _write_batches(run, eng, pg, stats, batch_clusters, device_text):
         for fh in (run.kmer_stroi, run.kmer_hash, run.hash_pat):
             if fh is not None:
                 fh.close()
+                if run.device_gzip:             # and the members the host compressed behind the header (fallback batches)
+                    stats["compressed_bytes"] = stats.get("compressed_bytes", 0) + fh.host_bytes
     if run.write_err is not None:
         raise run.write_err
 
@@ -231,7 +236,8 @@ def _write_batches(run, eng, pg, stats, batch_clusters, device_text):
 def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon=True, consider_missing=False,
               patfilt=True, maf=0.01, upstream=0, downstream=0, downstream_start_codon=False, targets=(), genes=None,
               compress=False, multiple_files=False, batch_clusters=256, resident=True, device_text=True, device=0,
-              max_items=0, pattern_capacity=0, overlap=True, one_pass=True, raise_missing=False):
+              max_items=0, pattern_capacity=0, overlap=True, one_pass=True, raise_missing=False, device_gzip=False,
+              targets_text_budget=None):
     """One directory of outputs (`kmers.tsv`, `kmers_to_hashes.tsv`, `hashes_to_patterns.tsv`, `.gz` under
     `compress`; under `multiple_files` one such directory per gene cluster, `<output>/<cluster>/`, the pattern set
     starting empty in each: `panfeed.py:35-43,153-167`) from a panaroo table and a directory (or file of files) of GFFs.  Option names and meaning follow
@@ -239,8 +245,14 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
     `__main__.py:283-297`).  one_pass (with resident): the genomes go to the GPU as their files are read
     (pf_pangenome_open_device) instead of being read into host strings first and uploaded afterwards.  raise_missing
     (`--stop-on-missing`): a strain, contig or gene of the table that is not found is an error instead of a warning.
+    device_gzip (`--gpu-compress`): the `.gz` files are compressed on the GPU -- it implies `compress`; the text the GPU
+    writes leaves it as gzip members (larger files than `compress` writes, in less time -- profiles/gzip_device/ -- that read back as
+    the same text), `stats["bytes"]` keeps counting text and `stats["compressed_bytes"]` is what the files hold behind their
+    header members: the encoder's own count of every batch's members plus the members the host compressed.  Under `multiple_files` it changes nothing: the per-cluster directories keep the host's gzip.
+    targets_text_budget: device memory a batch's kmers.tsv text may take (default: the engine's).
     Returns a dict of counters."""
-    run = _FileRun(output, compress, multiple_files)
+    compress = bool(compress or device_gzip)
+    run = _FileRun(output, compress, multiple_files, bool(device_gzip))
     err = existing_output_error(output)
     if err is not None:
         raise err
@@ -249,7 +261,8 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
     make_engine = functools.partial(sized_engine, batch_clusters=batch_clusters, max_items=max_items, klength=klength,
                                     canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
                                     multiple_files=multiple_files, stroi=set(targets), device=device,
-                                    pattern_capacity=pattern_capacity)
+                                    pattern_capacity=pattern_capacity, device_gzip=run.device_gzip,
+                                    **({} if targets_text_budget is None else {"targets_text_budget": targets_text_budget}))
     open_reader = functools.partial(Pangenome, presence_absence, gffdir, fastadir, upstream, downstream,
                                     downstream_start_codon, targets=targets, genes=genes, raise_missing=raise_missing)
     n_peek = _peek_n_strains(presence_absence) if overlap else 0

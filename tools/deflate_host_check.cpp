@@ -1,0 +1,126 @@
+// deflate_host_check.cpp -- a stand-alone check of the gzip code that runs on the host, for a sanitizer build:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude \
+//       tools/deflate_host_check.cpp panfeed_amd/csrc/pf_gzip.cpp -lz -lpthread -o /tmp/deflate_host_check
+// It runs the device encoder's host model (csrc/pf_deflate.h: the format functions the kernel uses too) and the host
+// path's pf_gzip_members (csrc/pf_gzip.cpp) over the edge cases of tests/deflate_cases.py (cases 1-9, generated here),
+// under every flag set that applies, and inflates every result with zlib: it must be the input.  Exit status 0: all equal.
+#include "../panfeed_amd/csrc/pf_deflate.h"
+#include "../panfeed_amd/csrc/pf_host.h"
+
+#include <zlib.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <random>
+#include <string>
+
+extern "C" void pf_set_error_(const char* msg) { fprintf(stderr, "library error: %s\n", msg); }
+unsigned pf_host_threads(unsigned cap) { return cap < 4 ? cap : 4; }
+
+namespace {
+using Bytes = std::vector<uint8_t>;
+int failures = 0, checks = 0;
+
+// every member of a multi-member gzip stream, inflated and joined
+bool gunzip(const uint8_t* p, size_t n, Bytes& out) {
+    out.clear();
+    size_t at = 0;
+    while (at < n) {
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (inflateInit2(&zs, 15 + 16) != Z_OK) return false;
+        zs.next_in = const_cast<Bytef*>(p + at);
+        zs.avail_in = (uInt)(n - at);
+        int rc = Z_OK;
+        while (rc == Z_OK) {
+            uint8_t buf[65536];
+            zs.next_out = buf; zs.avail_out = sizeof buf;
+            rc = inflate(&zs, Z_NO_FLUSH);
+            out.insert(out.end(), buf, buf + (sizeof buf - zs.avail_out));
+        }
+        at += zs.total_in;
+        inflateEnd(&zs);
+        if (rc != Z_STREAM_END) return false;
+    }
+    return true;
+}
+
+void check(const std::string& name, const Bytes& data, uint32_t flags) {
+    Bytes members, back;
+    checks++;
+    bool ok = pfgz::host_model(data.data(), data.size(), flags, members) && gunzip(members.data(), members.size(), back) && back == data;
+    if (data.empty()) ok = ok && members.empty();
+    if (!ok) { failures++; fprintf(stderr, "FAIL host model %s flags %u\n", name.c_str(), flags); }
+    if (flags == 0 && !data.empty()) {
+        char* out = nullptr;
+        uint64_t out_n = 0;
+        checks++;
+        const int rc = pf_gzip_members(reinterpret_cast<const char*>(data.data()), data.size(), 9, 65536, &out, &out_n);
+        if (rc != 0 || !gunzip(reinterpret_cast<const uint8_t*>(out), out_n, back) || back != data) {
+            failures++; fprintf(stderr, "FAIL pf_gzip_members %s\n", name.c_str());
+        }
+        free(out);
+    }
+}
+
+Bytes random_bytes(uint32_t seed, size_t n) {
+    std::mt19937 rng(seed);
+    Bytes b(n);
+    for (auto& x : b) x = (uint8_t)rng();
+    return b;
+}
+}  // namespace
+
+int main() {
+    const uint32_t C = pfgz::CHUNK, ALL[3] = {0, PF_GZ_FIXED_ONLY, PF_GZ_DYNAMIC_ONLY};
+    auto all = [&](const std::string& name, const Bytes& d) { for (uint32_t f : ALL) check(name, d, f); };
+    for (size_t n = 0; n <= 4; n++) all("short", Bytes(n, 'q'));                                  // 1
+    Bytes every(512);
+    for (size_t i = 0; i < 512; i++) every[i] = (uint8_t)i;
+    all("all_bytes_twice", every);                                                               // 2
+    for (size_t n : {1u, 2u, 3u, 4u, 5u, 257u, 258u, 259u, 260u, 261u, 516u, 517u, C - 1, C, C + 1, 2 * C + 3}) {   // 3
+        all("run", Bytes(n, 'a'));
+        Bytes p2(n);
+        for (size_t i = 0; i < n; i++) p2[i] = i & 1 ? '\t' : '0';
+        all("period2", p2);
+    }
+    for (uint32_t L : {3u, 4u, 10u, 11u, 12u, 18u, 19u, 34u, 35u, 66u, 67u, 130u, 131u, 257u, 258u}) {           // 4
+        Bytes R = random_bytes(1000 + L, 300);
+        for (auto& x : R) if (x == 0xEE) x = 0x11;               // 0xEE is the byte absent from R
+        Bytes d = R;
+        d.push_back(0xEE);
+        d.insert(d.end(), R.begin(), R.begin() + L);
+        d.push_back((uint8_t)(R[L] + 1) == 0xEE ? (uint8_t)(R[L] + 2) : (uint8_t)(R[L] + 1));
+        all("length_edge", d);
+    }
+    for (uint32_t D : {1u, 2u, 3u, 4u, 5u, 7u, 9u, 13u, 17u, 25u, 33u, 49u, 65u, 97u, 129u, 193u, 257u, 385u, 513u, 769u, 1025u,
+                       1537u, 2049u, 3073u, 4097u, 6145u, 8193u, 12289u, 16385u, 24577u, 32768u}) {            // 5
+        if (D >= 8193 && D >= C - 16) continue;
+        Bytes d = random_bytes(2000 + D, D + 8);
+        for (uint32_t i = 0; i < 8; i++) d[D + i] = d[i];
+        all("distance_edge", d);
+    }
+    check("incompressible", random_bytes(3, 3 * C + 17), 0);                                      // 6
+    {                                                                                            // 7
+        uint64_t F[64] = {0, 1, 1};
+        for (int i = 3; i < 64; i++) F[i] = F[i - 1] + F[i - 2];
+        int m = 1;
+        while (F[m + 3] - 1 <= C) m++;
+        Bytes d;
+        for (int i = 1; i <= m; i++) d.insert(d.end(), (size_t)F[i], (uint8_t)i);
+        std::mt19937 rng(7);
+        for (size_t i = d.size(); i > 1; i--) std::swap(d[i - 1], d[rng() % i]);
+        check("fibonacci", d, PF_GZ_LITERALS_ONLY | PF_GZ_DYNAMIC_ONLY);
+        check("fibonacci", d, PF_GZ_DYNAMIC_ONLY);
+    }
+    {                                                                                            // 8
+        Bytes perm(every.begin(), every.begin() + 256);
+        std::mt19937 rng(8);
+        for (size_t i = 256; i > 1; i--) std::swap(perm[i - 1], perm[rng() % i]);
+        check("no_distance_symbol", perm, PF_GZ_DYNAMIC_ONLY);
+    }
+    check("one_literal_symbol", Bytes(64, 'a'), PF_GZ_LITERALS_ONLY | PF_GZ_DYNAMIC_ONLY);         // 9
+    printf("%d checks, %d failures\n", checks, failures);
+    return failures ? 1 : 0;
+}
