@@ -263,7 +263,11 @@ PF_HD void put_member_tail(uint32_t* words, uint32_t coded_bits, uint32_t crc, u
 }
 
 PF_HD uint32_t hash4(uint32_t w) { return (w * 2654435761u) >> (32 - HASH_BITS); }
-// a candidate's match is taken from 4 bytes on; 3 bytes only when near (a far 3-byte match costs more than 3 literals)
+// a candidate's match is taken from 4 bytes on; 3 bytes only when near (a far 3-byte match costs more than 3 literals).
+// As long as a candidate comes from an equal hash4 of four bytes, the 3-byte clause never holds: two words that differ
+// only in their top byte differ by d << 24, the odd multiplier keeps that product's top byte non-zero, so their hashes
+// differ in their top 8 bits -- a candidate agrees in 0, 1, 2 or at least 4 bytes, and length symbol 257 is never
+// emitted (tests/test_deflate_host_model.py checks both).  The clause is what a candidate from any other source would need.
 PF_HD bool match_ok(uint32_t len, uint32_t dist) { return len >= 4 || (len == 3 && dist <= 4096); }
 
 // ---- the serial host model: same chunking, same coder, one candidate per position from a hash table of the positions

@@ -4,6 +4,10 @@
 // It runs the device encoder's host model (csrc/pf_deflate.h: the format functions the kernel uses too) and the host
 // path's pf_gzip_members (csrc/pf_gzip.cpp) over the edge cases of tests/deflate_cases.py (cases 1-9, generated here),
 // under every flag set that applies, and inflates every result with zlib: it must be the input.  Exit status 0: all equal.
+// The cases that are built in Python only (wide_tokens, whose widest tokens put_bits writes into three words, and the
+// fibonacci text that reaches the code length limit) come from a file, given as the one argument:
+//   python tests/deflate_cases.py /tmp/deflate_cases.bin && /tmp/deflate_host_check /tmp/deflate_cases.bin
+// -- records of flags (u32), name length (u32), name, text length (u64), text, little-endian, for the built chunk size.
 #include "../panfeed_amd/csrc/pf_deflate.h"
 #include "../panfeed_amd/csrc/pf_host.h"
 
@@ -70,9 +74,28 @@ Bytes random_bytes(uint32_t seed, size_t n) {
     for (auto& x : b) x = (uint8_t)rng();
     return b;
 }
+
+// the records of a file written by tests/deflate_cases.py's dump_cases; false: the file is cut short or cannot be read
+bool check_file(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return false;
+    bool ok = true;
+    for (;;) {
+        uint32_t head[2];
+        uint64_t n;
+        if (fread(head, 4, 2, f) != 2) { ok = feof(f) != 0; break; }
+        std::string name(head[1], '\0');
+        if (head[1] > 256 || fread(&name[0], 1, head[1], f) != head[1] || fread(&n, 8, 1, f) != 1 || n > (1u << 28)) { ok = false; break; }
+        Bytes data((size_t)n);
+        if (fread(data.data(), 1, data.size(), f) != data.size()) { ok = false; break; }
+        check(name, data, head[0]);
+    }
+    fclose(f);
+    return ok;
+}
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
     const uint32_t C = pfgz::CHUNK, ALL[3] = {0, PF_GZ_FIXED_ONLY, PF_GZ_DYNAMIC_ONLY};
     auto all = [&](const std::string& name, const Bytes& d) { for (uint32_t f : ALL) check(name, d, f); };
     for (size_t n = 0; n <= 4; n++) all("short", Bytes(n, 'q'));                                  // 1
@@ -85,7 +108,7 @@ int main() {
         for (size_t i = 0; i < n; i++) p2[i] = i & 1 ? '\t' : '0';
         all("period2", p2);
     }
-    for (uint32_t L : {3u, 4u, 10u, 11u, 12u, 18u, 19u, 34u, 35u, 66u, 67u, 130u, 131u, 257u, 258u}) {           // 4
+    for (uint32_t L : {3u, 4u, 10u, 11u, 12u, 13u, 16u, 18u, 19u, 26u, 34u, 35u, 66u, 67u, 130u, 131u, 226u, 257u, 258u}) {   // 4
         Bytes R = random_bytes(1000 + L, 300);
         for (auto& x : R) if (x == 0xEE) x = 0x11;               // 0xEE is the byte absent from R
         Bytes d = R;
@@ -105,10 +128,10 @@ int main() {
     {                                                                                            // 7
         uint64_t F[64] = {0, 1, 1};
         for (int i = 3; i < 64; i++) F[i] = F[i - 1] + F[i - 2];
-        int m = 1;
-        while (F[m + 3] - 1 <= C) m++;
+        int m = 2;                                       // byte i occurs F(i) times from F(2) on: with the end-of-block
+        while (F[m + 3] - 2 <= C) m++;                   // symbol's one the weights are F(1), F(2), .. -- a chain
         Bytes d;
-        for (int i = 1; i <= m; i++) d.insert(d.end(), (size_t)F[i], (uint8_t)i);
+        for (int i = 2; i <= m; i++) d.insert(d.end(), (size_t)F[i], (uint8_t)i);
         std::mt19937 rng(7);
         for (size_t i = d.size(); i > 1; i--) std::swap(d[i - 1], d[rng() % i]);
         check("fibonacci", d, PF_GZ_LITERALS_ONLY | PF_GZ_DYNAMIC_ONLY);
@@ -121,6 +144,7 @@ int main() {
         check("no_distance_symbol", perm, PF_GZ_DYNAMIC_ONLY);
     }
     check("one_literal_symbol", Bytes(64, 'a'), PF_GZ_LITERALS_ONLY | PF_GZ_DYNAMIC_ONLY);         // 9
+    if (argc > 1 && !check_file(argv[1])) { failures++; fprintf(stderr, "FAIL reading %s\n", argv[1]); }
     printf("%d checks, %d failures\n", checks, failures);
     return failures ? 1 : 0;
 }
