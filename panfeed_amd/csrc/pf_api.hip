@@ -216,6 +216,63 @@ struct KtPlan {
     uint64_t total = 0, cap = 0, max_unit = 0, max_range = 0, peak = 0;   // peak: of two neighbouring ranges
 };
 
+// The text path's state.  The render of kmers_to_hashes / hashes_to_patterns on the device (beside pats.b64): the text
+// and its per-row tables; the pinned host copies of the rendered text, used alternately so that a writer thread may
+// still be on the previous batch's; pf_render_pattern_rows' id list, row lengths and row offsets.
+struct RenderText {
+    DevBuf dev, meta, rp_order, rp_rlen, rp_rowoff;
+    PinBuf pins[2];
+    int slot = 0;
+    uint32_t b64_done = 0;               // patterns whose base64 is in pats.b64
+    int next_pin(size_t bytes, char** pin) {     // the other pinned block, of at least `bytes`
+        PFCHK(pins[slot ^= 1].ensure(bytes));
+        *pin = pins[slot].as<char>();
+        return PF_OK;
+    }
+};
+// kmers.tsv written on the device: descriptors, tiles, and the text in ranges -- range r is written into text[r & 1]
+// while the range before it leaves through the pinned blocks.  pf_kmers_tsv_stream_begin / _next hand the ranges out in
+// order; pf_render_kmers_tsv_device writes the whole text as one range into text[0], where `bytes` of it stay for
+// pf_device_text_chunk.  Each begin ends the other's text.
+struct TargetText {
+    DevBuf seqs, tiles, prefix, tbytes, toff, text[2];
+    uint64_t bytes = 0;
+    PinBuf pins[2];
+    // the one block on its way, on `side`: n bytes from `off` of the text into pins[slot] -- or, a stream's block under
+    // device gzip, their members into GzMode::block_members[slot], the members' size into the slot's pinned cursor word
+    struct { bool valid = false; int slot = 0; uint64_t off = 0, n = 0; } flight;
+    struct Stream {
+        bool active = false;
+        std::vector<pf_target_seq> hseqs;      // the host-rendered sequences (the caller's strings, until the stream ends)
+        KtHostText host;                       // their one measurement
+        KtPlan plan;
+        pf::KtParams kp{};
+        uint32_t cur = 0;                      // the block to queue next: range cur, bytes from cur_off
+        uint64_t cur_off = 0, pin_bytes = 0;
+        char* htext[2] = {nullptr, nullptr};   // the host's share of the range being written into each buffer
+        hipEvent_t ev_prod[2] = {nullptr, nullptr};    // on `stream`: the range in buffer b is written
+        hipEvent_t ev_copied[2] = {nullptr, nullptr};  // on `side`: the range in buffer b has left the device
+    } stream;
+    void destroy_events() { for (auto e : {stream.ev_prod[0], stream.ev_prod[1], stream.ev_copied[0], stream.ev_copied[1]}) if (e) (void)hipEventDestroy(e); }
+};
+// gzip on the device (pf_set_device_gzip): the mode, the encoder, the members of a render and of the stream's two blocks
+// in flight (block j + 1 is encoded while block j is written out by the caller), the text sizes behind the members
+struct GzMode {
+    bool on = false;
+    uint32_t flags = 0;
+    PfGzEncoder enc;
+    DevBuf render_members, block_members[2];
+    uint64_t block_bound = 0;                 // bytes of each of block_members
+    hipEvent_t ev_copy = nullptr;             // on `side`: a block's members have arrived in pinned memory
+    uint64_t raw[3] = {0, 0, 0};              // text bytes of the last render's two texts, of the stream's blocks so far
+    float encode_ms = 0.0f;                   // the last pf_gzip_device's encode, scan and gather launches (hipEvent)
+    void destroy_events() { if (ev_copy) (void)hipEventDestroy(ev_copy); }
+};
+int gz_check_flags(uint32_t flags, const char* who) {
+    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY)) return fail(PF_ERR_ARG, "%s: unknown flag", who);
+    return PF_OK;
+}
+
 }  // namespace
 
 struct pf_ctx {
@@ -244,49 +301,9 @@ struct pf_ctx {
     // unit view (unit_class_kernel): one pool of view entries per part of a batch's first pass, and the list
     // {clusters, their places in the pool} that goes up with it
     struct UPool { DevBuf word_off, len, sample, ord, bits, list; PinBuf pin; };
-    DevBuf txt_dev, txt_meta;              // device-side rendering (beside pats.b64): the text, its per-row tables
-    uint32_t b64_done = 0;               // patterns whose base64 is in pats.b64
-    PinBuf txt_pins[2];                  // pinned host copies of the rendered text, used alternately so that a writer thread
-                                         // may still be on the previous batch's
-    int txt_slot = 0;
-    // kmers.tsv written on the device: descriptors, tiles, and the text in ranges -- range r is written into kt_text (r
-    // even) or kt_text2 (r odd) while the range before it leaves through the pinned blocks.  pf_kmers_tsv_stream_begin /
-    // _next hand the ranges out in order; pf_render_kmers_tsv_device writes the whole text as one range into kt_text,
-    // where kt_bytes of it stay for pf_device_text_chunk.  Each begin ends the other's text.
-    DevBuf kt_seqs, kt_tiles, kt_prefix, kt_tbytes, kt_toff, kt_text, kt_text2;
-    uint64_t kt_bytes = 0;
-    uint32_t kt_host_seqs = 0;
-    PinBuf kt_pins[2];
-    struct { bool valid = false; int slot = 0; uint64_t off = 0, n = 0; } kt_pref;   // the block on its way, on `side`, into
-                                                                                     // kt_pins[slot]: n bytes from `off` of the text
-    struct KtStream {
-        bool active = false;
-        std::vector<pf_target_seq> hseqs;      // the host-rendered sequences (the caller's strings, until the stream ends)
-        KtHostText host;                       // their one measurement
-        KtPlan plan;
-        pf::KtParams kp{};
-        uint32_t cur = 0;                      // the block to hand out next: range cur, bytes from cur_off
-        uint64_t cur_off = 0, pin_bytes = 0;
-        char* htext[2] = {nullptr, nullptr};   // the host's share of the range being written into each buffer
-        hipEvent_t ev_prod[2] = {nullptr, nullptr};    // on `stream`: the range in buffer b is written
-        hipEvent_t ev_copied[2] = {nullptr, nullptr};  // on `side`: the range in buffer b has left the device
-    } kts;
-    // gzip on the device (pf_set_device_gzip): the encoder, and what the mode keeps -- the members of a render, the
-    // members of the stream's two blocks in flight (block j + 1 is encoded while block j is written out by the caller),
-    // the pinned cursor read-backs (0, 1: a render's two texts; 2, 3: the stream's blocks), the text sizes behind them
-    PfGzEncoder gz;
-    struct GzMode {
-        bool on = false, pending = false;
-        uint32_t flags = 0;
-        DevBuf render_members, block_members[2];
-        PinBuf pin_cursor;
-        hipEvent_t ev_copy = nullptr;
-        int pending_slot = 0;
-        uint64_t pending_text = 0;
-        uint64_t raw[3] = {0, 0, 0};
-        uint64_t block_bound = 0;
-        float encode_ms = 0.0f;                   // the last pf_gzip_device's encode, scan and gather launches (hipEvent)
-    } gzm;
+    RenderText txt;                        // the text path: the render's state,
+    TargetText kt;                         // the target text's (kmers.tsv) with its stream,
+    GzMode gz;                             // and the gzip mode
     pf_batch last{};                      // the last pf_submit's batch arrays as device pointers (valid until the next submit)
     uint32_t last_nseg = 0;
     uint64_t last_words = 0;              // words of last.packed: the batch's, or the buffer pf_submit_gather filled
@@ -298,7 +315,6 @@ struct pf_ctx {
     DevBuf q_key, q_ord, q_bit, q_off;    // key-partition queues of binned clusters (bin_kernel)
     std::vector<std::unique_ptr<Arena>> arenas;
     uint32_t n_passes = 0;                 // arenas the last pf_submit used (arenas[] itself only ever grows)
-    DevBuf rp_order, rp_rlen, rp_rowoff;   // pf_render_pattern_rows: the id list, row lengths, row offsets
     uint32_t n_grown = 0;                  // times the pattern table / pool were enlarged
     uint32_t n_scratch_grown = 0;          // times the scratch slices were re-made for a cluster of more items than max_items
     uint64_t pt_slot_limit = 0;            // test hook (pf_debug_limit_pattern_slots): allocations above it fail as if out of memory
@@ -349,13 +365,13 @@ namespace {
 // the end of a kmers.tsv stream (its last block handed out, a new one begun, the next pf_submit, pf_destroy): nothing of
 // it is in flight afterwards, its host text is freed
 void kt_stream_end(pf_ctx* c) {
-    pf_ctx::KtStream& S = c->kts;
+    TargetText::Stream& S = c->kt.stream;
     if (S.active) {
         (void)hipStreamSynchronize(c->side);
         (void)hipStreamSynchronize(c->stream);
     }
     for (int b = 0; b < 2; b++) { free(S.htext[b]); S.htext[b] = nullptr; }
-    S.active = false; c->kt_pref.valid = false; c->gzm.pending = false;
+    S.active = false; c->kt.flight.valid = false;
     S.hseqs.clear(); S.host = KtHostText{}; S.plan = KtPlan{};
 }
 
@@ -407,7 +423,7 @@ int reset_patterns(pf_ctx* c) {
     HIPCHK(hipMemsetAsync(c->pt_counters.p, 0, 16, c->stream));
     c->n_patterns = 0;
     c->pid0 = 0;
-    c->b64_done = 0;
+    c->txt.b64_done = 0;
     c->pt_stale = false;
     c->h_pat_bits.clear(); c->h_pat_nan.clear(); c->h_pat_n.clear(); c->h_pat_md5.clear(); c->h_first_seen.clear();
     c->h_b64.clear();
@@ -492,7 +508,7 @@ int grow_patterns(pf_ctx* c, uint64_t min_pool) {
     if (rc == PF_OK && c->o.consider_missing) rc = copy(nb.nan, ob.nan, (size_t)keep * W * 4);
     if (rc == PF_OK) rc = copy(nb.n, ob.n, (size_t)keep * 4);
     if (rc == PF_OK) rc = copy(nb.md5, ob.md5, (size_t)keep * 16);
-    if (rc == PF_OK && nb.b64.p) rc = copy(nb.b64, ob.b64, (size_t)std::min(c->b64_done, keep) * 24);
+    if (rc == PF_OK && nb.b64.p) rc = copy(nb.b64, ob.b64, (size_t)std::min(c->txt.b64_done, keep) * 24);
     if (rc == PF_OK) {
         pf::RehashParams rp{};
         rp.old_lo = ob.lo.as<uint64_t>(); rp.old_val = ob.val.as<uint64_t>(); rp.old_cap = ob.cap;
@@ -512,7 +528,7 @@ int grow_patterns(pf_ctx* c, uint64_t min_pool) {
     std::swap(c->pats, nb);                          // nb now holds the old buffers, and frees them
     sync_pattern_table(c);
     HIPCHK(hipMemcpy(c->pt_counters.p, cnt, 16, hipMemcpyHostToDevice));
-    c->b64_done = std::min(c->b64_done, keep);
+    c->txt.b64_done = std::min(c->txt.b64_done, keep);
     c->n_grown++;
     return PF_OK;
 }
@@ -725,8 +741,8 @@ void pf_destroy(pf_ctx* c) {
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     for (auto e : c->ev_stage) if (e) (void)hipEventDestroy(e);
     for (auto e : c->ev_part) if (e) (void)hipEventDestroy(e);
-    for (auto e : {c->kts.ev_prod[0], c->kts.ev_prod[1], c->kts.ev_copied[0], c->kts.ev_copied[1], c->ev_t0, c->ev_t1,
-                   c->ev_fork, c->ev_join, c->gzm.ev_copy})
+    c->kt.destroy_events(); c->gz.destroy_events();
+    for (auto e : {c->ev_t0, c->ev_t1, c->ev_fork, c->ev_join})
         if (e) (void)hipEventDestroy(e);
     if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1840,7 +1856,7 @@ struct SubmitRun {
         c->n_clusters = C; c->last = d; c->last_nseg = NSEG;
         c->last_words = gth ? gth->n_words : b->n_words;
         if (!c->n_strand_words) c->last.seg_strand_off = nullptr;
-        c->kt_bytes = 0; c->kt_pref.valid = false;
+        c->kt.bytes = 0; c->kt.flight.valid = false;
         pf_result res{};
         res.n_instances = total_inst; res.n_unique = c->counters.n_unique; res.n_kept = c->counters.n_kept;   // (the last pass's cursor)
         res.n_new_patterns = pid1 - c->pid0; res.n_patterns = pid1; res.W = W; res.key_words = KW;
@@ -2343,22 +2359,22 @@ int kt_layout(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, KtLayout& L) {
     pf::KtParams& kp = L.kp;
     L.tbytes.assign(NT, 0);
     if (NT) {
-        PFCHK(c->kt_seqs.ensure(ks.size() * sizeof(pf::KtSeq)));
-        PFCHK(c->kt_tiles.ensure((size_t)NT * 8));
-        PFCHK(c->kt_prefix.ensure(prefix.size() + 16));
-        PFCHK(c->kt_tbytes.ensure((size_t)NT * 4));
-        PFCHK(c->kt_toff.ensure((size_t)NT * 8));
-        HIPCHK(hipMemcpyAsync(c->kt_seqs.p, ks.data(), ks.size() * sizeof(pf::KtSeq), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->kt_tiles.p, tiles.data(), (size_t)NT * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->kt_prefix.p, prefix.data(), prefix.size(), hipMemcpyHostToDevice, c->stream));
-        kp.seqs = c->kt_seqs.as<pf::KtSeq>(); kp.tiles = c->kt_tiles.as<uint2>(); kp.prefix = c->kt_prefix.as<char>();
+        PFCHK(c->kt.seqs.ensure(ks.size() * sizeof(pf::KtSeq)));
+        PFCHK(c->kt.tiles.ensure((size_t)NT * 8));
+        PFCHK(c->kt.prefix.ensure(prefix.size() + 16));
+        PFCHK(c->kt.tbytes.ensure((size_t)NT * 4));
+        PFCHK(c->kt.toff.ensure((size_t)NT * 8));
+        HIPCHK(hipMemcpyAsync(c->kt.seqs.p, ks.data(), ks.size() * sizeof(pf::KtSeq), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->kt.tiles.p, tiles.data(), (size_t)NT * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->kt.prefix.p, prefix.data(), prefix.size(), hipMemcpyHostToDevice, c->stream));
+        kp.seqs = c->kt.seqs.as<pf::KtSeq>(); kp.tiles = c->kt.tiles.as<uint2>(); kp.prefix = c->kt.prefix.as<char>();
         kp.packed = c->last.packed; kp.seg_word_off = c->last.seg_word_off; kp.seg_strand_off = c->last.seg_strand_off;
         kp.strand_bits = c->strand_bits.as<uint64_t>();
-        kp.tile_bytes = c->kt_tbytes.as<uint32_t>(); kp.tile_off = c->kt_toff.as<uint64_t>();
+        kp.tile_bytes = c->kt.tbytes.as<uint32_t>(); kp.tile_off = c->kt.toff.as<uint64_t>();
         kp.k = k; kp.canon = canon ? 1u : 0u;
         hipLaunchKernelGGL(pf::kt_len_kernel, dim3(NT), dim3(pf::KT_ROWS), 0, c->stream, kp);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(L.tbytes.data(), c->kt_tbytes.p, (size_t)NT * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(L.tbytes.data(), c->kt.tbytes.p, (size_t)NT * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     return PF_OK;
@@ -2417,15 +2433,14 @@ void kt_plan(const KtLayout& L, const std::vector<uint64_t>& hsizes, uint64_t bu
 namespace {
 constexpr uint64_t KT_BLOCK = 64ull << 20;    // bytes per block a stream hands out (DeviceText.chunks' default too)
 
-// range r of the open text written into its buffer (kt_text for even r, kt_text2 for odd) on c->stream: its tiles by
-// kt_text_kernel, its host-rendered sequences written by the host now, from their one measurement, and copied up.  From
-// r = 2 on the buffer's range before (r - 2) must have left the device first: c->stream waits for that range's last
-// copy on c->side.
+// range r of the open text written into its buffer (text[r & 1]) on c->stream: its tiles by kt_text_kernel, its
+// host-rendered sequences written by the host now, from their one measurement, and copied up.  From r = 2 on the
+// buffer's range before (r - 2) must have left the device first: c->stream waits for that range's last copy on c->side.
 int kt_produce(pf_ctx* c, uint32_t r) {
-    pf_ctx::KtStream& S = c->kts;
+    TargetText::Stream& S = c->kt.stream;
     const KtPlan::Range& R = S.plan.ranges[r];
     const int b = (int)(r & 1);
-    char* buf = (b ? c->kt_text2 : c->kt_text).as<char>();
+    char* buf = c->kt.text[b].as<char>();
     if (r >= 2) {
         HIPCHK(hipEventSynchronize(S.ev_prod[b]));          // (its host text has been copied up: free it)
         free(S.htext[b]); S.htext[b] = nullptr;
@@ -2452,13 +2467,16 @@ int kt_produce(pf_ctx* c, uint32_t r) {
     return PF_OK;
 }
 
-// What the two device texts share: the layout, the host's share measured, the plan within `budget`, the buffers, and
-// the first two ranges on their way (there is only one when the text fits the budget).  The stream is open afterwards;
-// a failure leaves none.
-int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget) {
+// What the two device texts share: the checks of their arguments and of the context's state, the layout, the host's
+// share measured, the plan within `budget`, the buffers, and the first two ranges on their way (there is only one when
+// the text fits the budget).  The stream is open afterwards; a failure leaves none.
+int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget, bool outputs_given, const char* who) {
+    if (!c || !outputs_given || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
+    if (!c->have_batch) return fail(PF_ERR_STATE, "%s without a successful pf_submit", who);
+    HIPCHK(hipSetDevice(c->device));
     kt_stream_end(c);
-    c->kt_bytes = 0; c->kt_pref.valid = false;     // (pf_device_text_chunk's text is gone: the buffers are reused)
-    pf_ctx::KtStream& S = c->kts;
+    c->kt.bytes = 0;                               // (pf_device_text_chunk's text is gone: the buffers are reused)
+    TargetText::Stream& S = c->kt.stream;
     S.active = true;
     struct Guard { pf_ctx* c; bool ok; ~Guard() { if (!ok) kt_stream_end(c); } } guard{c, false};
     KtLayout L;
@@ -2479,12 +2497,9 @@ int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget) {
                     (unsigned long long)P.max_unit, (unsigned long long)(2 * (P.max_unit + 64)));
     // ---- the buffers, the events, the first two ranges on their way
     const uint32_t NR = (uint32_t)P.ranges.size(), NT = (uint32_t)L.tiles.size();
-    if (NR <= 1) PFCHK(c->kt_text.ensure((size_t)P.total + 64));
-    else {
-        PFCHK(c->kt_text.ensure((size_t)P.max_range + 64, true));
-        PFCHK(c->kt_text2.ensure((size_t)P.max_range + 64, true));
-    }
-    if (NT) HIPCHK(hipMemcpyAsync(c->kt_toff.p, P.toff.data(), (size_t)NT * 8, hipMemcpyHostToDevice, c->stream));
+    if (NR <= 1) PFCHK(c->kt.text[0].ensure((size_t)P.total + 64));
+    else for (DevBuf& t : c->kt.text) PFCHK(t.ensure((size_t)P.max_range + 64, true));
+    if (NT) HIPCHK(hipMemcpyAsync(c->kt.toff.p, P.toff.data(), (size_t)NT * 8, hipMemcpyHostToDevice, c->stream));
     for (int b = 0; b < 2; b++) {
         if (!S.ev_prod[b]) HIPCHK(hipEventCreateWithFlags(&S.ev_prod[b], hipEventDisableTiming));
         if (!S.ev_copied[b]) HIPCHK(hipEventCreateWithFlags(&S.ev_copied[b], hipEventDisableTiming));
@@ -2493,7 +2508,6 @@ int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget) {
     S.cur = 0; S.cur_off = 0;
     S.pin_bytes = std::max<uint64_t>(1, std::min(KT_BLOCK, P.max_range));
     for (uint32_t r = 0; r < std::min(NR, 2u); r++) PFCHK(kt_produce(c, r));
-    c->kt_host_seqs = (uint32_t)S.hseqs.size();
     guard.ok = true;
     return PF_OK;
 }
@@ -2501,46 +2515,29 @@ int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget) {
 // n bytes at src, which start at byte `off` of the text, on their way into pinned slot `slot` (of `block` bytes) on
 // c->side: the one block in flight that pf_device_text_chunk or pf_kmers_tsv_stream_next picks up next
 int kt_prefetch(pf_ctx* c, int slot, const char* src, uint64_t off, uint64_t n, uint64_t block) {
-    PFCHK(c->kt_pins[slot].ensure(block, true));
-    if (n) HIPCHK(hipMemcpyAsync(c->kt_pins[slot].p, src, n, hipMemcpyDeviceToHost, c->side));
-    c->kt_pref.valid = true; c->kt_pref.slot = slot; c->kt_pref.off = off; c->kt_pref.n = n;
+    PFCHK(c->kt.pins[slot].ensure(block, true));
+    if (n) HIPCHK(hipMemcpyAsync(c->kt.pins[slot].p, src, n, hipMemcpyDeviceToHost, c->side));
+    c->kt.flight = {true, slot, off, n};
     return PF_OK;
 }
 
-// the copy of the block at (S.cur, S.cur_off) into pinned slot `slot`, queued on c->side behind its range's writing; the
-// last block of range r also marks the range's buffer free, and range r + 2 is queued into it
-int kt_copy_block(pf_ctx* c, int slot) {
-    pf_ctx::KtStream& S = c->kts;
+// The stream's block at (S.cur, S.cur_off) queued on c->side behind its range's writing, and the stream's position moved
+// past it.  Plain: its copy into pinned slot `slot`.  Device gzip: its encode into block_members[slot], the members'
+// size on its way into the slot's pinned cursor word.  The last block of range r also marks the range's buffer free, and
+// range r + 2 is queued into it.
+int kt_block(pf_ctx* c, int slot) {
+    TargetText::Stream& S = c->kt.stream;
+    GzMode& G = c->gz;
     const KtPlan::Range& R = S.plan.ranges[S.cur];
     const int b = (int)(S.cur & 1);
-    const char* buf = (b ? c->kt_text2 : c->kt_text).as<char>();
-    const uint64_t n = std::min<uint64_t>(S.pin_bytes, R.bytes - S.cur_off);
+    const char* src = c->kt.text[b].as<char>() + S.cur_off;
+    const uint64_t off = R.base + S.cur_off, n = std::min<uint64_t>(S.pin_bytes, R.bytes - S.cur_off);
     HIPCHK(hipStreamWaitEvent(c->side, S.ev_prod[b], 0));
-    PFCHK(kt_prefetch(c, slot, buf + S.cur_off, R.base + S.cur_off, n, S.pin_bytes));
-    if (S.cur_off + n == R.bytes) {
-        HIPCHK(hipEventRecord(S.ev_copied[b], c->side));
-        if (S.cur + 2 < S.plan.ranges.size()) PFCHK(kt_produce(c, S.cur + 2));
-    }
-    return PF_OK;
-}
-}  // namespace
-
-namespace {
-// Device gzip of the stream.  The block at (S.cur, S.cur_off) encoded on c->side behind its range's writing, its members
-// into block_members[slot] and their size on its way into the pinned cursor 2 + slot; the stream's position moves past
-// the block.  As with kt_copy_block, a range's last block marks the range's buffer free and range r + 2 is queued into it.
-int kt_gz_block(pf_ctx* c, int slot) {
-    pf_ctx::KtStream& S = c->kts;
-    pf_ctx::GzMode& G = c->gzm;
-    const KtPlan::Range& R = S.plan.ranges[S.cur];
-    const int b = (int)(S.cur & 1);
-    const char* buf = (b ? c->kt_text2 : c->kt_text).as<char>();
-    const uint64_t n = std::min<uint64_t>(KT_BLOCK, R.bytes - S.cur_off);
-    HIPCHK(hipStreamWaitEvent(c->side, S.ev_prod[b], 0));
-    PFCHK(c->gz.begin(c->side, 2 + slot));
-    PFCHK(c->gz.append(c->side, 2 + slot, buf + S.cur_off, n, G.flags, G.block_members[slot].as<char>(), G.block_bound));
-    PFCHK(c->gz.read_cursor(c->side, 2 + slot, G.pin_cursor.as<uint64_t>() + 2 + slot));
-    G.pending = true; G.pending_slot = slot; G.pending_text = n;
+    if (G.on) {
+        PFCHK(G.enc.encode(c->side, slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, src, n, G.flags,
+                           G.block_members[slot].as<char>(), G.block_bound));
+        c->kt.flight = {true, slot, off, n};
+    } else PFCHK(kt_prefetch(c, slot, src, off, n, S.pin_bytes));
     S.cur_off += n;
     if (S.cur_off == R.bytes) {
         HIPCHK(hipEventRecord(S.ev_copied[b], c->side));
@@ -2550,39 +2547,16 @@ int kt_gz_block(pf_ctx* c, int slot) {
     return PF_OK;
 }
 
-// the buffers of the stream's blocks in flight, for blocks of at most block_text bytes of text
+// the buffers of the stream's blocks in flight under device gzip, for blocks of at most block_text bytes of text
 int kt_gz_buffers(pf_ctx* c, uint64_t block_text) {
-    pf_ctx::GzMode& G = c->gzm;
-    PFCHK(c->gz.ensure(c->n_cu));
+    GzMode& G = c->gz;
+    PFCHK(G.enc.ensure(c->n_cu));
     G.block_bound = PfGzEncoder::bound(std::max<uint64_t>(block_text, 1));
     for (int s = 0; s < 2; s++) {
         PFCHK(G.block_members[s].ensure(G.block_bound, true));
-        PFCHK(c->kt_pins[s].ensure(G.block_bound, true));
+        PFCHK(c->kt.pins[s].ensure(G.block_bound, true));
     }
     if (!G.ev_copy) HIPCHK(hipEventCreateWithFlags(&G.ev_copy, hipEventDisableTiming));
-    return PF_OK;
-}
-
-// pf_kmers_tsv_stream_next under device gzip: the members of the next block of text
-int kt_gz_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
-    pf_ctx::KtStream& S = c->kts;
-    pf_ctx::GzMode& G = c->gzm;
-    if (!G.pending) {
-        if (S.cur >= S.plan.ranges.size()) { kt_stream_end(c); return PF_OK; }
-        PFCHK(kt_gz_block(c, 0));
-    }
-    HIPCHK(hipStreamSynchronize(c->side));                 // the block is encoded, its size has arrived
-    const int slot = G.pending_slot;
-    const uint64_t z = G.pin_cursor.as<uint64_t>()[2 + slot];
-    if (z > G.block_bound) return fail(PF_ERR_STATE, "device gzip: a block's members exceed their bound");
-    G.pending = false;
-    G.raw[2] += G.pending_text;
-    HIPCHK(hipMemcpyAsync(c->kt_pins[slot].p, G.block_members[slot].p, z, hipMemcpyDeviceToHost, c->side));
-    HIPCHK(hipEventRecord(G.ev_copy, c->side));
-    if (S.cur < S.plan.ranges.size()) PFCHK(kt_gz_block(c, slot ^ 1));      // the next block is encoded meanwhile
-    HIPCHK(hipEventSynchronize(G.ev_copy));
-    *ptr = c->kt_pins[slot].as<char>();
-    *nbytes = z;
     return PF_OK;
 }
 }  // namespace
@@ -2590,17 +2564,14 @@ int kt_gz_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
 // The same rows written by the GPU (kt_len_kernel / kt_text_kernel) for the sequences kt_layout gives it and by the host
 // renderer above for the others, which are copied to their places in the device text: the text of all n sequences, in
 // order, stays in device memory and is handed out block by block (pf_device_text_chunk).  It is the stream's plan with
-// no budget -- one range, written into kt_text -- and no stream is left open: the caller's seqs die with the call.
+// no budget -- one range, written into text[0] -- and no stream is left open: the caller's seqs die with the call.
 int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t* nbytes) {
-    if (!c || !nbytes || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
-    if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_kmers_tsv_device without a successful pf_submit");
-    HIPCHK(hipSetDevice(c->device));
-    PFCHK(kt_open(c, seqs, n, ~0ull));
-    const uint64_t total = c->kts.plan.total;
+    PFCHK(kt_open(c, seqs, n, ~0ull, nbytes != nullptr, "pf_render_kmers_tsv_device"));
+    const uint64_t total = c->kt.stream.plan.total;
     const hipError_t text_written = hipStreamSynchronize(c->stream);
     kt_stream_end(c);
     HIPCHK(text_written);
-    c->kt_bytes = total;
+    c->kt.bytes = total;
     *nbytes = total;
     return PF_OK;
 }
@@ -2610,19 +2581,17 @@ int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n,
 // r leaves the device.  A batch whose text fits the budget is one range, the single-buffer path's work.
 int pf_kmers_tsv_stream_begin(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget_bytes,
                               uint64_t* total_bytes, uint32_t* n_ranges, uint64_t* peak_text_bytes) {
-    if (!c || !total_bytes || !n_ranges || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
-    if (!c->have_batch) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_begin without a successful pf_submit");
-    HIPCHK(hipSetDevice(c->device));
-    *total_bytes = 0; *n_ranges = 0;
+    if (total_bytes) *total_bytes = 0;
+    if (n_ranges) *n_ranges = 0;
     if (peak_text_bytes) *peak_text_bytes = 0;
-    PFCHK(kt_open(c, seqs, n, budget_bytes));
-    const KtPlan& P = c->kts.plan;
+    PFCHK(kt_open(c, seqs, n, budget_bytes, total_bytes && n_ranges, "pf_kmers_tsv_stream_begin"));
+    const KtPlan& P = c->kt.stream.plan;
     uint64_t peak = P.peak;
-    c->gzm.raw[2] = 0;
-    if (c->gzm.on) {                 // the encoder's buffers and the two blocks of members count as the text's memory
+    c->gz.raw[2] = 0;
+    if (c->gz.on) {                  // the encoder's buffers and the two blocks of members count as the text's memory
         const int rc = kt_gz_buffers(c, std::min<uint64_t>(KT_BLOCK, P.max_range));
         if (rc != PF_OK) { kt_stream_end(c); return rc; }
-        peak += c->gz.device_bytes() + 2 * c->gzm.block_bound;
+        peak += c->gz.enc.device_bytes() + 2 * c->gz.block_bound;
     }
     *total_bytes = P.total;
     *n_ranges = (uint32_t)P.ranges.size();
@@ -2630,23 +2599,36 @@ int pf_kmers_tsv_stream_begin(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, 
     return PF_OK;
 }
 
+// The next block of the open stream: its text, or under device gzip its members.  While the caller holds block j, block
+// j + 1 is already queued: its copy into the other pinned slot, or its encode into the other block of members.
 int pf_kmers_tsv_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
     if (!c || !ptr || !nbytes) return fail(PF_ERR_ARG, "null argument");
     *ptr = nullptr; *nbytes = 0;
-    pf_ctx::KtStream& S = c->kts;
+    TargetText::Stream& S = c->kt.stream;
+    GzMode& G = c->gz;
     if (!S.active) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_next without an open pf_kmers_tsv_stream_begin");
     HIPCHK(hipSetDevice(c->device));
-    if (c->gzm.on) return kt_gz_next(c, ptr, nbytes);
-    if (S.cur >= S.plan.ranges.size()) { kt_stream_end(c); return PF_OK; }
-    if (!c->kt_pref.valid) PFCHK(kt_copy_block(c, 0));
-    HIPCHK(hipStreamSynchronize(c->side));
-    const int slot = c->kt_pref.slot;
-    const uint64_t n = c->kt_pref.n;
-    c->kt_pref.valid = false;
-    S.cur_off += n;
-    if (S.cur_off == S.plan.ranges[S.cur].bytes) { S.cur++; S.cur_off = 0; }
-    if (S.cur < S.plan.ranges.size()) PFCHK(kt_copy_block(c, slot ^ 1));      // the next block on its way meanwhile
-    *ptr = c->kt_pins[slot].as<char>();
+    if (!c->kt.flight.valid) {
+        if (S.cur >= S.plan.ranges.size()) { kt_stream_end(c); return PF_OK; }
+        PFCHK(kt_block(c, 0));
+    }
+    HIPCHK(hipStreamSynchronize(c->side));                 // the block has arrived (gzip: is encoded, its size has arrived)
+    const int slot = c->kt.flight.slot;
+    uint64_t n = c->kt.flight.n;
+    hipEvent_t arrival = nullptr;                          // what else the hand-out waits for, once the next block is queued
+    if (G.on) {
+        // only the members cross to the host: their copy goes behind the encode and before the next block's, which runs
+        // while they arrive
+        const uint64_t text = n;
+        PFCHK(G.enc.member_bytes(slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, &n));
+        G.raw[2] += text;
+        HIPCHK(hipMemcpyAsync(c->kt.pins[slot].p, G.block_members[slot].p, n, hipMemcpyDeviceToHost, c->side));
+        HIPCHK(hipEventRecord(arrival = G.ev_copy, c->side));
+    }
+    c->kt.flight.valid = false;
+    if (S.cur < S.plan.ranges.size()) PFCHK(kt_block(c, slot ^ 1));      // the next block on its way meanwhile
+    if (arrival) HIPCHK(hipEventSynchronize(arrival));
+    *ptr = c->kt.pins[slot].as<char>();
     *nbytes = n;
     return PF_OK;
 }
@@ -2655,25 +2637,26 @@ int pf_kmers_tsv_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
 // remains), in pinned host memory; the block after it is already on its way when the call returns.
 int pf_device_text_chunk(pf_ctx* c, uint64_t offset, uint64_t max_bytes, const char** ptr, uint64_t* nbytes) {
     if (!c || !ptr || !nbytes || !max_bytes) return fail(PF_ERR_ARG, "null argument");
-    if (offset > c->kt_bytes) return fail(PF_ERR_ARG, "offset beyond the text");
+    TargetText& T = c->kt;
+    if (offset > T.bytes) return fail(PF_ERR_ARG, "offset beyond the text");
     HIPCHK(hipSetDevice(c->device));
-    const uint64_t n = std::min<uint64_t>(max_bytes, c->kt_bytes - offset);
-    const char* text = c->kt_text.as<char>();
+    const uint64_t n = std::min<uint64_t>(max_bytes, T.bytes - offset);
+    const char* text = T.text[0].as<char>();
     if (!n) {                                         // (nothing to copy, and the block in flight, if any, stays)
-        PFCHK(c->kt_pins[0].ensure(max_bytes, true));
-        *ptr = c->kt_pins[0].as<char>(); *nbytes = 0;
+        PFCHK(T.pins[0].ensure(max_bytes, true));
+        *ptr = T.pins[0].as<char>(); *nbytes = 0;
         return PF_OK;
     }
-    if (!(c->kt_pref.valid && c->kt_pref.off == offset && c->kt_pref.n == n)) {
+    if (!(T.flight.valid && T.flight.off == offset && T.flight.n == n)) {
         HIPCHK(hipStreamSynchronize(c->side));        // (a block in flight that nobody asked for)
         PFCHK(kt_prefetch(c, 0, text + offset, offset, n, max_bytes));
     }
     HIPCHK(hipStreamSynchronize(c->side));            // requested by the call before, or just now: wait for it
-    const int slot = c->kt_pref.slot;
-    c->kt_pref.valid = false;
+    const int slot = T.flight.slot;
+    T.flight.valid = false;
     const uint64_t next = offset + n;
-    if (next < c->kt_bytes) PFCHK(kt_prefetch(c, slot ^ 1, text + next, next, std::min<uint64_t>(max_bytes, c->kt_bytes - next), max_bytes));
-    *ptr = c->kt_pins[slot].as<char>();
+    if (next < T.bytes) PFCHK(kt_prefetch(c, slot ^ 1, text + next, next, std::min<uint64_t>(max_bytes, T.bytes - next), max_bytes));
+    *ptr = T.pins[slot].as<char>();
     *nbytes = n;
     return PF_OK;
 }
@@ -3116,18 +3099,13 @@ namespace {
 int ensure_b64_dev(pf_ctx* c) {
     if (!c->pats.b64.p) PFCHK(c->pats.b64.ensure((size_t)c->pt.pool * 24));
     const uint32_t p1 = c->n_patterns;
-    if (c->b64_done < p1) {
-        hipLaunchKernelGGL(pf::b64_kernel, dim3((p1 - c->b64_done + 255) / 256), dim3(256), 0, c->stream,
-                           c->pats.md5.as<uint8_t>(), c->b64_done, p1, c->pats.b64.as<char>());
+    if (c->txt.b64_done < p1) {
+        hipLaunchKernelGGL(pf::b64_kernel, dim3((p1 - c->txt.b64_done + 255) / 256), dim3(256), 0, c->stream,
+                           c->pats.md5.as<uint8_t>(), c->txt.b64_done, p1, c->pats.b64.as<char>());
         HIPCHK(hipGetLastError());
-        c->b64_done = p1;
+        c->txt.b64_done = p1;
     }
     return PF_OK;
-}
-// pinned host block `slot` of the rendered text, at least `total` bytes
-int text_pin(pf_ctx* c, size_t total) {
-    c->txt_slot ^= 1;
-    return c->txt_pins[c->txt_slot].ensure(total);
 }
 // hashes_to_patterns rows on the device.  The lengths of n rows into d_len: of the patterns order[0 .. n) (a device
 // list), or of patterns pid0 .. pid0 + n without a list
@@ -3162,23 +3140,23 @@ int pf_render_pattern_rows(pf_ctx* c, const uint32_t* pids, uint64_t n, const ch
     hipStream_t st = c->stream;
     const uint32_t P = (uint32_t)n;
     PFCHK(ensure_b64_dev(c));
-    PFCHK(c->rp_order.ensure((size_t)P * 4));
-    PFCHK(c->rp_rlen.ensure((size_t)P * 4));
-    PFCHK(c->rp_rowoff.ensure(((size_t)P + 1) * 8));
-    HIPCHK(hipMemcpyAsync(c->rp_order.p, pids, (size_t)P * 4, hipMemcpyHostToDevice, st));
-    PFCHK(hp_rowlen(c, c->rp_order.as<uint32_t>(), 0u, P, c->rp_rlen.as<uint32_t>()));
+    PFCHK(c->txt.rp_order.ensure((size_t)P * 4));
+    PFCHK(c->txt.rp_rlen.ensure((size_t)P * 4));
+    PFCHK(c->txt.rp_rowoff.ensure(((size_t)P + 1) * 8));
+    HIPCHK(hipMemcpyAsync(c->txt.rp_order.p, pids, (size_t)P * 4, hipMemcpyHostToDevice, st));
+    PFCHK(hp_rowlen(c, c->txt.rp_order.as<uint32_t>(), 0u, P, c->txt.rp_rlen.as<uint32_t>()));
     std::vector<uint32_t> rlen(P);
-    HIPCHK(hipMemcpyAsync(rlen.data(), c->rp_rlen.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rlen.data(), c->txt.rp_rlen.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     std::vector<uint64_t> row_off((size_t)P + 1, 0);
     for (uint32_t i = 0; i < P; i++) row_off[i + 1] = row_off[i] + rlen[i];
     const uint64_t total = row_off[P];
-    PFCHK(c->txt_dev.ensure(total + 16));
-    PFCHK(text_pin(c, total + 16));
-    HIPCHK(hipMemcpyAsync(c->rp_rowoff.p, row_off.data(), ((size_t)P + 1) * 8, hipMemcpyHostToDevice, st));
-    PFCHK(hp_text(c, c->rp_order.as<uint32_t>(), c->rp_rowoff.as<uint64_t>(), P, c->txt_dev.as<char>()));
-    char* pin = c->txt_pins[c->txt_slot].as<char>();
-    HIPCHK(hipMemcpyAsync(pin, c->txt_dev.p, total, hipMemcpyDeviceToHost, st));
+    PFCHK(c->txt.dev.ensure(total + 16));
+    char* pin;
+    PFCHK(c->txt.next_pin(total + 16, &pin));
+    HIPCHK(hipMemcpyAsync(c->txt.rp_rowoff.p, row_off.data(), ((size_t)P + 1) * 8, hipMemcpyHostToDevice, st));
+    PFCHK(hp_text(c, c->txt.rp_order.as<uint32_t>(), c->txt.rp_rowoff.as<uint64_t>(), P, c->txt.dev.as<char>()));
+    HIPCHK(hipMemcpyAsync(pin, c->txt.dev.p, total, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *text = pin; *nbytes = total;
     return PF_OK;
@@ -3189,16 +3167,18 @@ int pf_render_device(pf_ctx* c, const char* const* names, const char* extra_keys
     return pf_render_device_ex(c, names, extra_keys, n_extra, 0, kh, kh_bytes, hp, hp_bytes);
 }
 
-int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra, uint32_t flags,
-                        const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes) {
-    if (!c || !kh || !kh_bytes || !hp || !hp_bytes) return fail(PF_ERR_ARG, "pf_render_device: null argument");
-    const bool want_hp = !(flags & PF_RENDER_NO_PATTERN_ROWS);
-    if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_device needs a successful pf_submit");
-    if (c->o.multiple_files) return fail(PF_ERR_ARG, "pf_render_device writes one pair of texts per batch; use the host renderers under multiple_files");
-    HIPCHK(hipSetDevice(c->device));
-    const uint32_t C = c->n_clusters, KW = (uint32_t)c->KW, k = c->o.klength;
-    if (C && !names) return fail(PF_ERR_ARG, "pf_render_device: cluster names missing");
-    if (c->n_passes > pf::TEXT_MAX_ARENAS) return fail(PF_ERR_CAPACITY, "pf_render_device: too many passes (%u)", c->n_passes);
+namespace {
+// pf_render_device's host layout: the counts come down, then rows per cluster and workgroups per cluster
+// (kmers_to_hashes), the new patterns in first-seen order (hashes_to_patterns), and the one block of tables (`meta`, with
+// the o_* offsets into it) both kernels read
+struct RenderLayout {
+    uint32_t C = 0, P = 0, n_blocks = 0, rows_per_block = 256;
+    uint64_t kh_n = 0, hp_n = 0, hp_at = 0;        // the two texts' bytes; the second starts 256-byte aligned
+    size_t o_text = 0, o_koff = 0, o_rowoff = 0, o_name = 0, o_kcnt = 0, o_arena = 0, o_bc = 0, o_br = 0, o_order = 0, o_blob = 0, o_extra = 0;
+    std::vector<char> meta;
+};
+int render_layout(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra, bool want_hp, RenderLayout& L) {
+    const uint32_t C = L.C = c->n_clusters, k = c->o.klength;
     hipStream_t st = c->stream;
     // ---- small per-cluster / per-pattern arrays to the host: counts and the first-seen order
     std::vector<uint64_t> koff(C);
@@ -3207,7 +3187,7 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
         HIPCHK(hipMemcpyAsync(koff.data(), c->batch.cl_kmer_off.p, (size_t)C * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(kcnt.data(), c->batch.cl_kmer_cnt.p, (size_t)C * 4, hipMemcpyDeviceToHost, st));
     }
-    const uint32_t p0 = c->pid0, p1 = c->n_patterns, P = want_hp ? p1 - p0 : 0;
+    const uint32_t p0 = c->pid0, p1 = c->n_patterns, P = L.P = want_hp ? p1 - p0 : 0;
     std::vector<uint64_t> fs(P);
     std::vector<uint32_t> rlen(P);
     DevBuf d_rlen;
@@ -3223,173 +3203,186 @@ int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_k
     std::vector<uint64_t> text_off(C + 1, 0);
     std::vector<uint32_t> name_off(C + 1, 0), arena_of(C), blk_cluster, blk_row0;
     std::string blob;
-    uint32_t rows_per_block = 256;
     for (uint32_t i = 0; i < C; i++) {
-        const uint32_t L = (uint32_t)strlen(names[i]);
-        blob.append(names[i], L);
+        const uint32_t len = (uint32_t)strlen(names[i]);
+        blob.append(names[i], len);
         name_off[i + 1] = (uint32_t)blob.size();
-        const uint64_t head = pf::kh_head_len(L), rowlen = pf::kh_row_len(L, k);
-        if (head + rowlen > pf::TEXT_TILE) return fail(PF_ERR_ARG, "cluster name too long for the text kernel (%u bytes)", L);
-        rows_per_block = std::min<uint32_t>(rows_per_block, (uint32_t)((pf::TEXT_TILE - head) / rowlen));
+        const uint64_t head = pf::kh_head_len(len), rowlen = pf::kh_row_len(len, k);
+        if (head + rowlen > pf::TEXT_TILE) return fail(PF_ERR_ARG, "cluster name too long for the text kernel (%u bytes)", len);
+        L.rows_per_block = std::min<uint32_t>(L.rows_per_block, (uint32_t)((pf::TEXT_TILE - head) / rowlen));
         text_off[i + 1] = text_off[i] + head + (uint64_t)kcnt[i] * rowlen;
         const uint32_t a = c->cluster_arena[i];
         arena_of[i] = a;
         koff[i] = kcnt[i] ? koff[i] - c->arenas[a]->base : 0;
     }
     for (uint32_t i = 0; i < C; i++)
-        for (uint32_t r = 0; r < kcnt[i] + 1; r += rows_per_block) { blk_cluster.push_back(i); blk_row0.push_back(r); }
+        for (uint32_t r = 0; r < kcnt[i] + 1; r += L.rows_per_block) { blk_cluster.push_back(i); blk_row0.push_back(r); }
+    L.n_blocks = (uint32_t)blk_cluster.size();
     // ---- hashes_to_patterns layout: new patterns in first-seen order
     std::vector<uint32_t> order(P);
     std::iota(order.begin(), order.end(), 0u);
     std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return fs[x] < fs[y]; });
     std::vector<uint64_t> row_off(P + 1, 0);
     for (uint32_t i = 0; i < P; i++) { row_off[i + 1] = row_off[i] + rlen[order[i]]; order[i] += p0; }
-    const uint64_t kh_n = text_off[C], hp_n = row_off[P];
-    const uint64_t hp_at = (kh_n + 255) & ~(uint64_t)255;          // the second text starts 256-byte aligned
-    const uint64_t total = hp_at + hp_n + 16;
-    PFCHK(c->txt_dev.ensure(total));
-    PFCHK(text_pin(c, c->gzm.on ? 16 : total));        // (under device gzip the block is sized once the members' sizes are known)
-    char* txt_pin = c->txt_pins[c->txt_slot].as<char>();
+    L.kh_n = text_off[C]; L.hp_n = row_off[P];
+    L.hp_at = (L.kh_n + 255) & ~(uint64_t)255;
     // ---- one block of tables for both kernels
     auto pad8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
     size_t o = 0;
-    const size_t o_text = o; o += pad8((size_t)(C + 1) * 8);
-    const size_t o_koff = o; o += pad8((size_t)C * 8);
-    const size_t o_rowoff = o; o += pad8((size_t)(P + 1) * 8);
-    const size_t o_name = o; o += pad8((size_t)(C + 1) * 4);
-    const size_t o_kcnt = o; o += pad8((size_t)C * 4);
-    const size_t o_arena = o; o += pad8((size_t)C * 4);
-    const size_t o_bc = o; o += pad8(blk_cluster.size() * 4);
-    const size_t o_br = o; o += pad8(blk_row0.size() * 4);
-    const size_t o_order = o; o += pad8((size_t)P * 4);
-    const size_t o_blob = o; o += pad8(blob.size() + 1);
-    const size_t o_extra = o; o += pad8((size_t)n_extra * k + 1);
-    std::vector<char> meta(o, 0);
-    memcpy(&meta[o_text], text_off.data(), (size_t)(C + 1) * 8);
-    if (C) memcpy(&meta[o_koff], koff.data(), (size_t)C * 8);
-    memcpy(&meta[o_rowoff], row_off.data(), (size_t)(P + 1) * 8);
-    memcpy(&meta[o_name], name_off.data(), (size_t)(C + 1) * 4);
-    if (C) { memcpy(&meta[o_kcnt], kcnt.data(), (size_t)C * 4); memcpy(&meta[o_arena], arena_of.data(), (size_t)C * 4); }
-    if (!blk_cluster.empty()) { memcpy(&meta[o_bc], blk_cluster.data(), blk_cluster.size() * 4); memcpy(&meta[o_br], blk_row0.data(), blk_row0.size() * 4); }
-    if (P) memcpy(&meta[o_order], order.data(), (size_t)P * 4);
-    if (!blob.empty()) memcpy(&meta[o_blob], blob.data(), blob.size());
-    if (n_extra && extra_keys) memcpy(&meta[o_extra], extra_keys, (size_t)n_extra * k);
-    PFCHK(c->txt_meta.ensure(o));
-    HIPCHK(hipMemcpyAsync(c->txt_meta.p, meta.data(), o, hipMemcpyHostToDevice, st));
-    const char* dm = c->txt_meta.as<char>();
-    if (!blk_cluster.empty()) {
+    L.o_text = o; o += pad8((size_t)(C + 1) * 8);
+    L.o_koff = o; o += pad8((size_t)C * 8);
+    L.o_rowoff = o; o += pad8((size_t)(P + 1) * 8);
+    L.o_name = o; o += pad8((size_t)(C + 1) * 4);
+    L.o_kcnt = o; o += pad8((size_t)C * 4);
+    L.o_arena = o; o += pad8((size_t)C * 4);
+    L.o_bc = o; o += pad8(blk_cluster.size() * 4);
+    L.o_br = o; o += pad8(blk_row0.size() * 4);
+    L.o_order = o; o += pad8((size_t)P * 4);
+    L.o_blob = o; o += pad8(blob.size() + 1);
+    L.o_extra = o; o += pad8((size_t)n_extra * k + 1);
+    std::vector<char>& meta = L.meta;
+    meta.assign(o, 0);
+    memcpy(&meta[L.o_text], text_off.data(), (size_t)(C + 1) * 8);
+    if (C) memcpy(&meta[L.o_koff], koff.data(), (size_t)C * 8);
+    memcpy(&meta[L.o_rowoff], row_off.data(), (size_t)(P + 1) * 8);
+    memcpy(&meta[L.o_name], name_off.data(), (size_t)(C + 1) * 4);
+    if (C) { memcpy(&meta[L.o_kcnt], kcnt.data(), (size_t)C * 4); memcpy(&meta[L.o_arena], arena_of.data(), (size_t)C * 4); }
+    if (!blk_cluster.empty()) { memcpy(&meta[L.o_bc], blk_cluster.data(), blk_cluster.size() * 4); memcpy(&meta[L.o_br], blk_row0.data(), blk_row0.size() * 4); }
+    if (P) memcpy(&meta[L.o_order], order.data(), (size_t)P * 4);
+    if (!blob.empty()) memcpy(&meta[L.o_blob], blob.data(), blob.size());
+    if (n_extra && extra_keys) memcpy(&meta[L.o_extra], extra_keys, (size_t)n_extra * k);
+    return PF_OK;
+}
+
+// the tables up and the two launches: kmers_to_hashes from txt.dev on, hashes_to_patterns from txt.dev + hp_at
+int render_launch(pf_ctx* c, const RenderLayout& L) {
+    hipStream_t st = c->stream;
+    PFCHK(c->txt.dev.ensure(L.hp_at + L.hp_n + 16));
+    PFCHK(c->txt.meta.ensure(L.meta.size()));
+    HIPCHK(hipMemcpyAsync(c->txt.meta.p, L.meta.data(), L.meta.size(), hipMemcpyHostToDevice, st));
+    const char* dm = c->txt.meta.as<char>();
+    if (L.n_blocks) {
         pf::KhTextParams kp{};
-        kp.text_off = (const uint64_t*)(dm + o_text); kp.name_off = (const uint32_t*)(dm + o_name); kp.names = dm + o_blob;
-        kp.kmer_off = (const uint64_t*)(dm + o_koff); kp.kmer_cnt = (const uint32_t*)(dm + o_kcnt);
-        kp.cluster_pattern = c->batch.cl_pattern.as<uint32_t>(); kp.cluster_arena = (const uint32_t*)(dm + o_arena);
-        kp.block_cluster = (const uint32_t*)(dm + o_bc); kp.block_row0 = (const uint32_t*)(dm + o_br);
+        kp.text_off = (const uint64_t*)(dm + L.o_text); kp.name_off = (const uint32_t*)(dm + L.o_name); kp.names = dm + L.o_blob;
+        kp.kmer_off = (const uint64_t*)(dm + L.o_koff); kp.kmer_cnt = (const uint32_t*)(dm + L.o_kcnt);
+        kp.cluster_pattern = c->batch.cl_pattern.as<uint32_t>(); kp.cluster_arena = (const uint32_t*)(dm + L.o_arena);
+        kp.block_cluster = (const uint32_t*)(dm + L.o_bc); kp.block_row0 = (const uint32_t*)(dm + L.o_br);
         for (size_t a = 0; a < c->n_passes; a++) { kp.arena_key[a] = c->arenas[a]->key.as<uint64_t>(); kp.arena_pid[a] = c->arenas[a]->pid.as<uint32_t>(); }
-        kp.b64 = c->pats.b64.as<char>(); kp.extra_keys = dm + o_extra; kp.text = c->txt_dev.as<char>();
-        kp.k = k; kp.KW = KW; kp.rows_per_block = rows_per_block;
-        hipLaunchKernelGGL(pf::kh_text_kernel, dim3((uint32_t)blk_cluster.size()), dim3(256), 0, st, kp);
+        kp.b64 = c->pats.b64.as<char>(); kp.extra_keys = dm + L.o_extra; kp.text = c->txt.dev.as<char>();
+        kp.k = c->o.klength; kp.KW = (uint32_t)c->KW; kp.rows_per_block = L.rows_per_block;
+        hipLaunchKernelGGL(pf::kh_text_kernel, dim3(L.n_blocks), dim3(256), 0, st, kp);
         HIPCHK(hipGetLastError());
     }
-    if (P) PFCHK(hp_text(c, (const uint32_t*)(dm + o_order), (const uint64_t*)(dm + o_rowoff), P, c->txt_dev.as<char>() + hp_at));
-    if (c->gzm.on) {
-        // both texts through the encoder behind their kernels; the two compressed sizes come back, then only members
-        // cross to the host
-        pf_ctx::GzMode& G = c->gzm;
+    if (L.P) PFCHK(hp_text(c, (const uint32_t*)(dm + L.o_order), (const uint64_t*)(dm + L.o_rowoff), L.P, c->txt.dev.as<char>() + L.hp_at));
+    return PF_OK;
+}
+
+// The hand-out of a render: two spans of device text, written on c->stream, leave through one pinned block, the second
+// at a 256-aligned offset -- as they are, or under device gzip as their members: both texts go through the encoder behind
+// their kernels, the two compressed sizes come back, then only members cross to the host.
+struct Span { const char* p; uint64_t n; };
+int render_handout(pf_ctx* c, Span text0, Span text1, Span* out0, Span* out1) {
+    hipStream_t st = c->stream;
+    GzMode& G = c->gz;
+    if (G.on) {
         HIPCHK(hipStreamSynchronize(c->side));             // (the encoder's scratch is one: no block of a stream in flight)
-        const uint64_t b0 = PfGzEncoder::bound(kh_n), b1 = PfGzEncoder::bound(hp_n);
+        const uint64_t b0 = PfGzEncoder::bound(text0.n), b1 = PfGzEncoder::bound(text1.n);
         PFCHK(G.render_members.ensure(b0 + b1 + 16));
         char* M = G.render_members.as<char>();
-        uint64_t* cur = G.pin_cursor.as<uint64_t>();
-        PFCHK(c->gz.begin(st, 0));
-        PFCHK(c->gz.append(st, 0, c->txt_dev.as<char>(), kh_n, G.flags, M, b0));
-        PFCHK(c->gz.read_cursor(st, 0, cur));
-        PFCHK(c->gz.begin(st, 1));
-        PFCHK(c->gz.append(st, 1, c->txt_dev.as<char>() + hp_at, hp_n, G.flags, M + b0, b1));
-        PFCHK(c->gz.read_cursor(st, 1, cur + 1));
+        PFCHK(G.enc.encode(st, PfGzEncoder::RENDER_KMERS_TO_HASHES, text0.p, text0.n, G.flags, M, b0));
+        PFCHK(G.enc.encode(st, PfGzEncoder::RENDER_HASHES_TO_PATTERNS, text1.p, text1.n, G.flags, M + b0, b1));
         HIPCHK(hipStreamSynchronize(st));
-        const uint64_t z0 = cur[0], z1 = cur[1], z1_at = (z0 + 255) & ~(uint64_t)255;
-        if (z0 > b0 || z1 > b1) return fail(PF_ERR_STATE, "device gzip: a text's members exceed their bound");
-        PFCHK(c->txt_pins[c->txt_slot].ensure(z1_at + z1 + 16));
-        char* pin = c->txt_pins[c->txt_slot].as<char>();
-        if (z0) HIPCHK(hipMemcpyAsync(pin, M, z0, hipMemcpyDeviceToHost, st));
-        if (z1) HIPCHK(hipMemcpyAsync(pin + z1_at, M + b0, z1, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        G.raw[0] = kh_n; G.raw[1] = hp_n;
-        *kh = pin; *kh_bytes = z0;
-        *hp = pin + z1_at; *hp_bytes = z1;
-        return PF_OK;
+        G.raw[0] = text0.n; G.raw[1] = text1.n;
+        text0.p = M; text1.p = M + b0;
+        PFCHK(G.enc.member_bytes(PfGzEncoder::RENDER_KMERS_TO_HASHES, &text0.n));
+        PFCHK(G.enc.member_bytes(PfGzEncoder::RENDER_HASHES_TO_PATTERNS, &text1.n));
     }
-    if (kh_n) HIPCHK(hipMemcpyAsync(txt_pin, c->txt_dev.p, kh_n, hipMemcpyDeviceToHost, st));
-    if (hp_n) HIPCHK(hipMemcpyAsync(txt_pin + hp_at, c->txt_dev.as<char>() + hp_at, hp_n, hipMemcpyDeviceToHost, st));
+    const uint64_t at1 = (text0.n + 255) & ~(uint64_t)255;
+    char* pin;
+    PFCHK(c->txt.next_pin(at1 + text1.n + 16, &pin));
+    if (text0.n) HIPCHK(hipMemcpyAsync(pin, text0.p, text0.n, hipMemcpyDeviceToHost, st));
+    if (text1.n) HIPCHK(hipMemcpyAsync(pin + at1, text1.p, text1.n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    *kh = txt_pin; *kh_bytes = kh_n;
-    *hp = txt_pin + hp_at; *hp_bytes = hp_n;
+    *out0 = Span{pin, text0.n}; *out1 = Span{pin + at1, text1.n};
+    return PF_OK;
+}
+}  // namespace
+
+int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra, uint32_t flags,
+                        const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes) {
+    if (!c || !kh || !kh_bytes || !hp || !hp_bytes) return fail(PF_ERR_ARG, "pf_render_device: null argument");
+    if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_device needs a successful pf_submit");
+    if (c->o.multiple_files) return fail(PF_ERR_ARG, "pf_render_device writes one pair of texts per batch; use the host renderers under multiple_files");
+    HIPCHK(hipSetDevice(c->device));
+    if (c->n_clusters && !names) return fail(PF_ERR_ARG, "pf_render_device: cluster names missing");
+    if (c->n_passes > pf::TEXT_MAX_ARENAS) return fail(PF_ERR_CAPACITY, "pf_render_device: too many passes (%u)", c->n_passes);
+    RenderLayout L;
+    PFCHK(render_layout(c, names, extra_keys, n_extra, !(flags & PF_RENDER_NO_PATTERN_ROWS), L));
+    PFCHK(render_launch(c, L));
+    Span out0, out1;
+    PFCHK(render_handout(c, Span{c->txt.dev.as<char>(), L.kh_n}, Span{c->txt.dev.as<char>() + L.hp_at, L.hp_n}, &out0, &out1));
+    *kh = out0.p; *kh_bytes = out0.n;
+    *hp = out1.p; *hp_bytes = out1.n;
     return PF_OK;
 }
 
 int pf_set_device_gzip(pf_ctx* c, int on, uint32_t flags) {
     if (!c) return fail(PF_ERR_ARG, "pf_set_device_gzip: null argument");
-    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY)) return fail(PF_ERR_ARG, "pf_set_device_gzip: unknown flag");
+    PFCHK(gz_check_flags(flags, "pf_set_device_gzip"));
     HIPCHK(hipSetDevice(c->device));
     kt_stream_end(c);                     // (an open stream would change its kind half way)
-    if (on) {
-        PFCHK(c->gz.ensure(c->n_cu));
-        PFCHK(c->gzm.pin_cursor.ensure(64, true));
-    }
-    c->gzm.on = on != 0; c->gzm.flags = flags;
+    if (on) PFCHK(c->gz.enc.ensure(c->n_cu));
+    c->gz.on = on != 0; c->gz.flags = flags;
     return PF_OK;
 }
 
 int pf_device_gzip_text_bytes(pf_ctx* c, uint64_t out[3]) {
     if (!c || !out) return fail(PF_ERR_ARG, "pf_device_gzip_text_bytes: null argument");
-    for (int i = 0; i < 3; i++) out[i] = c->gzm.raw[i];
+    for (int i = 0; i < 3; i++) out[i] = c->gz.raw[i];
     return PF_OK;
 }
 
 int pf_gzip_device_last_ms(pf_ctx* c, float* ms) {
     if (!c || !ms) return fail(PF_ERR_ARG, "pf_gzip_device_last_ms: null argument");
-    *ms = c->gzm.encode_ms;
+    *ms = c->gz.encode_ms;
     return PF_OK;
 }
 
 int pf_gzip_device(pf_ctx* c, const char* data, uint64_t n, uint32_t flags, char** out, uint64_t* out_n) {
     if (!c || (!data && n) || !out || !out_n) return fail(PF_ERR_ARG, "pf_gzip_device: null argument");
-    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY)) return fail(PF_ERR_ARG, "pf_gzip_device: unknown flag");
+    PFCHK(gz_check_flags(flags, "pf_gzip_device"));
     *out = nullptr; *out_n = 0;
     if (!n) {
         if (!(*out = (char*)malloc(1))) return fail(PF_ERR_OOM, "pf_gzip_device: out of memory");
         return PF_OK;
     }
     HIPCHK(hipSetDevice(c->device));
-    PFCHK(c->gz.ensure(c->n_cu));
-    PFCHK(c->gzm.pin_cursor.ensure(64, true));
+    PfGzEncoder& enc = c->gz.enc;
+    constexpr PfGzEncoder::Cursor W = PfGzEncoder::RENDER_KMERS_TO_HASHES;      // (a render's: neither is on its way now)
+    PFCHK(enc.ensure(c->n_cu));
     HIPCHK(hipStreamSynchronize(c->side));
     hipStream_t st = c->stream;
     DevBuf text, members;
     const uint64_t cap = PfGzEncoder::bound(n);
     PFCHK(text.ensure(n + 16, true));
     PFCHK(members.ensure(cap, true));
-    uint64_t* cur = c->gzm.pin_cursor.as<uint64_t>();
     HIPCHK(hipMemcpyAsync(text.p, data, n, hipMemcpyHostToDevice, st));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     PFCHK(get_event(c, &e0));
     if (get_event(c, &e1) != PF_OK) { c->ev_pool.push_back(e0); return PF_ERR_HIP; }
     // (the two events go back to the pool whichever step fails)
     auto encode = [&]() -> int {
-        HIPCHK(hipEventRecord(e0, st));
-        PFCHK(c->gz.begin(st, 0));
-        PFCHK(c->gz.append(st, 0, text.as<char>(), n, flags, members.as<char>(), cap));
-        HIPCHK(hipEventRecord(e1, st));
-        PFCHK(c->gz.read_cursor(st, 0, cur));
+        PFCHK(enc.encode(st, W, text.as<char>(), n, flags, members.as<char>(), cap, e0, e1));
         HIPCHK(hipStreamSynchronize(st));
-        c->gzm.encode_ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&c->gzm.encode_ms, e0, e1));
+        c->gz.encode_ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&c->gz.encode_ms, e0, e1));
         return PF_OK;
     };
     const int enc_rc = encode();
     c->ev_pool.push_back(e0); c->ev_pool.push_back(e1);
     PFCHK(enc_rc);
-    const uint64_t z = cur[0];
-    if (z > cap) return fail(PF_ERR_STATE, "pf_gzip_device: the members exceed their bound");
+    uint64_t z = 0;
+    PFCHK(enc.member_bytes(W, &z));
     char* buf = (char*)malloc(z ? z : 1);
     if (!buf) return fail(PF_ERR_OOM, "pf_gzip_device: out of memory");
     const hipError_t e = hipMemcpy(buf, members.p, z, hipMemcpyDeviceToHost);

@@ -363,22 +363,25 @@ inline bool host_model(const uint8_t* data, uint64_t n, uint32_t flags, std::vec
 #if defined(__HIPCC__)
 #include "pf_buf.h"
 // The device encoder: its buffers (worst-case slots, member sizes and offsets, the token streams of the resident
-// workgroups, append cursors) and the launches.  One per context; every call is stream-ordered on the stream given.
+// workgroups, append cursors and their pinned read-backs) and the launches.  One per context; every call is
+// stream-ordered on the stream given.
 struct PfGzEncoder {
     static constexpr uint64_t BLOCK = 64ull << 20;       // text bytes per launch: the product's block size
-    static constexpr int N_CURSORS = 4;
+    // one append cursor per text that may be on its way at once: a render's two texts, the stream's two blocks
+    enum Cursor { RENDER_KMERS_TO_HASHES, RENDER_HASHES_TO_PATTERNS, STREAM_BLOCK0, STREAM_BLOCK1, N_CURSORS };
     DevBuf slots, sizes, offs, tokens, cursors;
+    PinBuf pin; uint64_t caps[N_CURSORS] = {};           // per cursor: its value read back, the bytes its last encode's members may take
     uint32_t grid_cap = 0;                               // resident workgroups the token streams are sized for
     static uint64_t chunks(uint64_t n) { return (n + pfgz::CHUNK - 1) / pfgz::CHUNK; }
     static uint64_t bound(uint64_t n) { return chunks(n) * pfgz::SLOT_BYTES; }       // of the members of n bytes of text
     uint64_t device_bytes() const { return slots.cap + sizes.cap + offs.cap + tokens.cap + cursors.cap; }
     int ensure(int n_cu);
-    // cursor `which` back to zero
-    int begin(hipStream_t st, int which);
-    // the members of text[0 .. n) (device memory) appended at members + cursor, which advances; members holds cap bytes
-    int append(hipStream_t st, int which, const char* text, uint64_t n, uint32_t flags, char* members, uint64_t cap);
-    // the cursor's value on its way into *host (pinned memory)
-    int read_cursor(hipStream_t st, int which, uint64_t* host);
-    void release() { for (DevBuf* b : {&slots, &sizes, &offs, &tokens, &cursors}) b->release(); }
+    // On `st`: cursor w back to zero, the members of text[0 .. n) (device memory) written from `members` on, which holds
+    // cap bytes, and the cursor -- their size -- on its way into w's pinned word.  t0 / t1, where given, are recorded
+    // around the cursor's reset and the launches.
+    int encode(hipStream_t st, Cursor w, const char* text, uint64_t n, uint32_t flags, char* members, uint64_t cap,
+               hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+    // once the caller has synchronised with that encode: the bytes of its members; PF_ERR_STATE if they exceed its cap
+    int member_bytes(Cursor w, uint64_t* z) const;
 };
 #endif

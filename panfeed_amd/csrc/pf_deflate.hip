@@ -297,18 +297,18 @@ int PfGzEncoder::ensure(int n_cu) {
         PFCHK(cursors.ensure(N_CURSORS * 8, true));
         HIPCHK(hipMemset(cursors.p, 0, N_CURSORS * 8));
     }
+    PFCHK(pin.ensure(64, true));
     grid_cap = grid;
     return PF_OK;
 }
 
-int PfGzEncoder::begin(hipStream_t st, int which) {
-    if (which < 0 || which >= N_CURSORS || !cursors.p) return fail(PF_ERR_STATE, "gzip encoder: no such cursor");
-    HIPCHK(hipMemsetAsync(cursors.as<uint64_t>() + which, 0, 8, st));
-    return PF_OK;
-}
-
-int PfGzEncoder::append(hipStream_t st, int which, const char* text, uint64_t n, uint32_t flags, char* members, uint64_t cap) {
-    if (which < 0 || which >= N_CURSORS || !grid_cap) return fail(PF_ERR_STATE, "gzip encoder: not set up");
+int PfGzEncoder::encode(hipStream_t st, Cursor w, const char* text, uint64_t n, uint32_t flags, char* members, uint64_t cap,
+                        hipEvent_t t0, hipEvent_t t1) {
+    if (!grid_cap || !cursors.p) return fail(PF_ERR_STATE, "gzip encoder: not set up");
+    uint64_t* cursor = cursors.as<uint64_t>() + w;
+    caps[w] = cap;
+    if (t0) HIPCHK(hipEventRecord(t0, st));
+    HIPCHK(hipMemsetAsync(cursor, 0, 8, st));
     for (uint64_t at = 0; at < n; at += BLOCK) {
         const uint64_t m = std::min(BLOCK, n - at);
         const uint32_t nch = (uint32_t)chunks(m);
@@ -317,17 +317,20 @@ int PfGzEncoder::append(hipStream_t st, int which, const char* text, uint64_t n,
         hipLaunchKernelGGL(pfgz::gz_encode_kernel, dim3(std::min(nch, grid_cap)), dim3(pfgz::THREADS), 0, st, P);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(pfgz::gz_scan_kernel, dim3(1), dim3(pfgz::THREADS), 0, st, sizes.as<uint32_t>(), nch, offs.as<uint64_t>(),
-                           cursors.as<uint64_t>() + which);
+                           cursor);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(pfgz::gz_gather_kernel, dim3(nch), dim3(pfgz::THREADS), 0, st, slots.as<uint8_t>(), sizes.as<uint32_t>(),
                            offs.as<uint64_t>(), reinterpret_cast<uint8_t*>(members), cap);
         HIPCHK(hipGetLastError());
     }
+    if (t1) HIPCHK(hipEventRecord(t1, st));
+    HIPCHK(hipMemcpyAsync(pin.as<uint64_t>() + w, cursor, 8, hipMemcpyDeviceToHost, st));
     return PF_OK;
 }
 
-int PfGzEncoder::read_cursor(hipStream_t st, int which, uint64_t* host) {
-    HIPCHK(hipMemcpyAsync(host, cursors.as<uint64_t>() + which, 8, hipMemcpyDeviceToHost, st));
+int PfGzEncoder::member_bytes(Cursor w, uint64_t* z) const {
+    *z = pin.as<uint64_t>()[w];
+    if (*z > caps[w]) return fail(PF_ERR_STATE, "device gzip: a text's members exceed their bound");
     return PF_OK;
 }
 

@@ -158,41 +158,12 @@ def test_unit_order_at_the_seams_of_the_plan(canon):
     twice, one range, ranges at the smallest budget and the host renderer all give the oracle's bytes"""
     import re
 
-    import numpy as np
-    from oracle import oracle as po
+    import seam_batch
     from panfeed_amd import _lib
-    from panfeed_amd.classes import Seqinfo
     from panfeed_amd.engine import Engine
     from panfeed_amd.packing import build_batch_native
-    rng = np.random.default_rng(31)
-    comp = bytes.maketrans(b"ACGTN", b"TGCAN")
-
-    def seq(n, n_at=None):
-        s = bytearray(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), n).tobytes())
-        if n_at is not None:
-            s[n_at] = ord("N")
-        return bytes(s)
-    k = 31
-    seqs = [seq(20),                 # no window: the batch's first sequence drops out
-            seq(400, 200),           # host-rendered
-            seq(1000),               # 970 windows: 4 tiles canonical, 8 not
-            seq(25),                 # no window, between a device unit and a host unit
-            seq(300, 150),           # host next to host
-            seq(200, 199),           # ... its last base an 'N'
-            seq(159),                # 129 windows: 258 rows when not canonical, a tile seam after row 256
-            seq(31),                 # exactly one window
-            seq(100, 50),            # host-rendered, the last text of the batch
-            seq(10)]                 # no window: the batch's last sequence
-    names = [f"s{i:02d}" for i in range(1, 11)]
-    gs = {nm: [Seqinfo(s.decode(), s.translate(comp).decode(), f"{nm}_g", f"{nm}_c", 100 + i, 100 + i + len(s) - 1,
-                       -1 if i % 2 else 1, i)]
-          for i, (nm, s) in enumerate(zip(names, seqs))}
-    recs = [(gs, "grp1", np.ones(10, dtype=np.int64))]
-    stroi = set(names)
-    run = po.OracleRun(klength=k, stroi=stroi, canon=canon)
-    run.feed(recs)
-    ek = run.texts()[0].encode()
-    assert 100_000 < len(ek) < 400_000
+    k = seam_batch.K
+    recs, stroi, ek = seam_batch.build(canon)
     eng = Engine(klength=k, canon=canon, max_strains=32, stroi=stroi)
     try:
         hb = build_batch_native(recs, k, canon, eng.W, stroi=stroi, first_ordinal=0)
