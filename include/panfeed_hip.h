@@ -547,6 +547,23 @@ int pf_gzip_device_last_ms(pf_ctx* ctx, float* ms);
 /* The same container and coder run serially on the host, with a plain one-candidate greedy matcher: no context, no GPU.
  * Its bytes need not equal the device's; both decode to `data`. */
 int pf_gzip_host_model(const char* data, uint64_t n, uint32_t flags, char** out, uint64_t* out_n);
+/*
+ * gunzip ON THE DEVICE, for files made of small members such as pf_gzip_device writes: every member at most
+ * pf_gzip_device_chunk_bytes() of text (its ISIZE) and at most a ninth more than that compressed, with the plain 10-byte
+ * header (CM = 8, FLG = 0).  Inside such a member all of RFC 1951 is taken: stored, fixed and dynamic blocks, several
+ * blocks, the run codes 16 / 17 / 18.  Where members start is found without decoding: the first member's first eight
+ * header bytes (up to MTIME) are the signature, every place they stand at is a candidate, a member's tail is the 8 bytes before the next one.  One wave
+ * inflates one member; every member is verified on the device (it ends exactly at its tail, gives exactly ISIZE bytes,
+ * its CRC32 matches).  *taken = 0 with PF_OK: not a run of such members, or a member failed a check -- pf_last_error()
+ * names the first such member and why; nothing is repaired, the caller reads the file another way.
+ * Host bytes in, text out (malloc'd: pf_free_text).  n == 0 gives *out_n == 0, *taken = 1.  Device memory: the members
+ * and the text of at most 256 MiB of text at a time.
+ */
+int pf_gunzip_device(pf_ctx* ctx, const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken);
+/* Device time of the last pf_gunzip_device's inflate kernels (hipEvent on the context's stream), ms. */
+int pf_gunzip_device_last_ms(pf_ctx* ctx, float* ms);
+/* The same format functions run serially on the host: no context, no GPU. */
+int pf_gunzip_host_model(const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken);
 /* Off by default.  While on, pf_render_device[_ex] hands out gzip members in place of text (*kh, *kh_bytes, *hp,
  * *hp_bytes describe the compressed bytes) and so does pf_kmers_tsv_stream_next: every block of a range is encoded as it
  * is produced and its compressed size read back before it is copied (the host-rendered sequences are in the device text
@@ -575,6 +592,23 @@ int pf_rowfilter_create(int device, int first_field, const char* const* keys, co
 int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const uint64_t** line_begin,
                       const uint64_t** line_end, uint64_t* n_lines, uint64_t* consumed);
 int pf_rowfilter_stats(pf_rowfilter* f, uint64_t* bytes_scanned, float* device_ms);
+/*
+ * The same filter over a file of small gzip members (see pf_gunzip_device), inflated on the device and scanned where
+ * the inflate left the text.  pf_rowfilter_members_begin starts a file (header = 1: its first line is no row; it is kept
+ * for pf_rowfilter_members_header, valid until the next begin).  pf_rowfilter_scan_members takes a block of the
+ * COMPRESSED file that starts at a member start: the whole members in it are uploaded and inflated behind the unfinished
+ * line the call before left on the device, the complete lines are scanned, the candidates' lines are gathered on the
+ * device and checked against the exact keys on the host.  *lines: the matching lines joined, in file order (valid until
+ * the next call); *consumed: the compressed bytes of the members taken -- the caller puts members[consumed:] in front
+ * of its next block.  last = 1: the block ends the file; once all of it is consumed, a final line without a newline is
+ * given one.  *taken = 0 with PF_OK: as pf_gunzip_device; nothing is carried over then.
+ */
+int pf_rowfilter_members_begin(pf_rowfilter* f, int header);
+int pf_rowfilter_members_header(pf_rowfilter* f, const char** line, uint64_t* nbytes);
+int pf_rowfilter_scan_members(pf_rowfilter* f, const char* members, uint64_t nbytes, int last, const char** lines,
+                              uint64_t* lines_bytes, uint64_t* n_lines, uint64_t* consumed, int* taken);
+/* Members and text bytes inflated by this filter, its inflate kernels' ms, the decoder's device bytes (any may be NULL). */
+int pf_rowfilter_gunzip_stats(pf_rowfilter* f, uint64_t* members, uint64_t* text_bytes, float* inflate_ms, uint64_t* device_bytes);
 void pf_rowfilter_destroy(pf_rowfilter* f);
 
 /*

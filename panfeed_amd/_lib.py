@@ -150,7 +150,9 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_plotgrid_set_significance", "pf_plotgrid_grids", "pf_plotgrid_stats", "pf_plotgrid_destroy",
            "pf_py_str_addresses", "pf_pangenome_close_async", "pf_py_seqinfo_columns", "pf_py_release",
            "pf_gzip_device_chunk_bytes", "pf_gzip_device", "pf_gzip_host_model", "pf_set_device_gzip",
-           "pf_device_gzip_text_bytes", "pf_gzip_device_last_ms"]
+           "pf_device_gzip_text_bytes", "pf_gzip_device_last_ms",
+           "pf_gunzip_device", "pf_gunzip_device_last_ms", "pf_gunzip_host_model",
+           "pf_rowfilter_members_begin", "pf_rowfilter_members_header", "pf_rowfilter_scan_members", "pf_rowfilter_gunzip_stats"]
 
 RENDER_NO_PATTERN_ROWS = 1
 GZ_FIXED_ONLY, GZ_DYNAMIC_ONLY, GZ_LITERALS_ONLY = 1, 2, 4     # pf_gzip_device / pf_set_device_gzip test hooks; 0: the product
@@ -289,6 +291,15 @@ def _load_locked():
     L.pf_gzip_device_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.pf_set_device_gzip.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
     L.pf_device_gzip_text_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.pf_gunzip_device.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.pf_gunzip_device_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.pf_gunzip_host_model.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.pf_rowfilter_members_begin.argtypes = [C.c_void_p, C.c_int]
+    L.pf_rowfilter_members_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pf_rowfilter_scan_members.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.pf_rowfilter_gunzip_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float),
+                                            C.POINTER(C.c_uint64)]
     L.pf_submit_gather.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Gather), C.POINTER(Result)]
     L.pf_records_free.argtypes = [C.c_void_p]
     L.pf_records_free.restype = None

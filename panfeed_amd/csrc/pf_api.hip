@@ -266,6 +266,8 @@ struct GzMode {
     hipEvent_t ev_copy = nullptr;             // on `side`: a block's members have arrived in pinned memory
     uint64_t raw[3] = {0, 0, 0};              // text bytes of the last render's two texts, of the stream's blocks so far
     float encode_ms = 0.0f;                   // the last pf_gzip_device's encode, scan and gather launches (hipEvent)
+    PfGzDecoder dec;
+    float decode_ms = 0.0f;                   // the last pf_gunzip_device's inflate launches (hipEvent)
     void destroy_events() { if (ev_copy) (void)hipEventDestroy(ev_copy); }
 };
 int gz_check_flags(uint32_t flags, const char* who) {
@@ -3388,6 +3390,70 @@ int pf_gzip_device(pf_ctx* c, const char* data, uint64_t n, uint32_t flags, char
     const hipError_t e = hipMemcpy(buf, members.p, z, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { free(buf); return fail(PF_ERR_HIP, "pf_gzip_device: copy failed: %s", hipGetErrorString(e)); }
     *out = buf; *out_n = z;
+    return PF_OK;
+}
+
+int pf_gunzip_device_last_ms(pf_ctx* c, float* ms) {
+    if (!c || !ms) return fail(PF_ERR_ARG, "pf_gunzip_device_last_ms: null argument");
+    *ms = c->gz.decode_ms;
+    return PF_OK;
+}
+
+int pf_gunzip_device(pf_ctx* c, const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken) {
+    if (!c || (!members && n) || !out || !out_n || !taken) return fail(PF_ERR_ARG, "pf_gunzip_device: null argument");
+    *out = nullptr; *out_n = 0; *taken = 0;
+    c->gz.decode_ms = 0.f;
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(members);
+    std::vector<pfgz::MemberRef> ms;
+    uint64_t consumed = 0;
+    if (!pfgz::list_members(bytes, n, true, ms, &consumed)) {
+        (void)fail(PF_OK, "pf_gunzip_device: not taken: member 0: %s", pfgz::inf_status_name(pfgz::INF_BAD_HEAD));
+        return PF_OK;
+    }
+    const int64_t bad = pfgz::first_refused(ms);
+    if (bad >= 0) {
+        (void)fail(PF_OK, "pf_gunzip_device: not taken: member %lld: %s", (long long)bad, pfgz::inf_status_name(ms[(size_t)bad].status));
+        return PF_OK;
+    }
+    uint64_t total = 0;
+    for (const auto& m : ms) total += m.isize;
+    std::unique_ptr<char, void (*)(void*)> buf((char*)malloc(total ? total : 1), free);
+    if (!buf) return fail(PF_ERR_OOM, "pf_gunzip_device: out of memory");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    DevBuf text;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    PFCHK(get_event(c, &e0));
+    if (get_event(c, &e1) != PF_OK) { c->ev_pool.push_back(e0); return PF_ERR_HIP; }
+    // a call of the decoder per MAX_MEMBERS members (so at most MAX_TEXT bytes of text on the device at a time)
+    auto decode = [&]() -> int {
+        uint64_t at = 0;
+        for (size_t i = 0; i < ms.size(); i += PfGzDecoder::MAX_MEMBERS) {
+            const uint32_t k = (uint32_t)std::min<size_t>(PfGzDecoder::MAX_MEMBERS, ms.size() - i);
+            uint64_t part = 0;
+            for (uint32_t j = 0; j < k; j++) part += ms[i + j].isize;
+            PFCHK(text.ensure(part + 16));
+            PFCHK(c->gz.dec.decode(st, bytes, ms.data() + i, k, text.as<uint8_t>(), part, e0, e1));
+            HIPCHK(hipStreamSynchronize(st));
+            float t = 0.f;
+            HIPCHK(hipEventElapsedTime(&t, e0, e1));
+            c->gz.decode_ms += t;
+            uint32_t status = 0;
+            const int64_t r = c->gz.dec.first_refused(&status);
+            if (r >= 0) {
+                (void)fail(PF_OK, "pf_gunzip_device: not taken: member %lld: %s", (long long)(i + (size_t)r), pfgz::inf_status_name(status));
+                return 1;
+            }
+            if (part) HIPCHK(hipMemcpy(buf.get() + at, text.p, part, hipMemcpyDeviceToHost));
+            at += part;
+        }
+        return PF_OK;
+    };
+    const int rc = decode();
+    c->ev_pool.push_back(e0); c->ev_pool.push_back(e1);
+    if (rc == 1) return PF_OK;                  // not taken
+    PFCHK(rc);
+    *out = buf.release(); *out_n = total; *taken = 1;
     return PF_OK;
 }
 

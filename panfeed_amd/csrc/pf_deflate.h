@@ -1,9 +1,12 @@
-// pf_deflate.h -- internal: gzip (RFC 1952) members with deflate (RFC 1951) blocks, written by the GPU.
+// pf_deflate.h -- internal: gzip (RFC 1952) members with deflate (RFC 1951) blocks, written and read by the GPU.
 //
 // The format logic is written once, as host+device functions: length / distance symbols and their extra bits, the fixed
 // codes, the length-limited code builder, the canonical code assignment, the dynamic block header, the bit writer, CRC32
 // and its combination.  pf_deflate.hip runs them in the encoder kernel; host_model() below runs the same functions
 // serially, with a plain one-candidate greedy matcher, so that the format can be tested without a GPU.
+//
+// The decoder's side stands behind the encoder's: bit reader, decode tables, the dynamic header with its run codes, stored
+// blocks, several blocks per member -- inflate_blocks(), run by the decoder kernel and by host_inflate_model().
 //
 // Container: the text is cut into chunks of CHUNK bytes; every chunk becomes one complete gzip member holding one final
 // deflate block -- stored, fixed or dynamic, whichever is smallest by exact bit count.  No match reaches before its chunk.
@@ -19,6 +22,8 @@
 #else
 #define PF_HD inline
 #endif
+
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -358,6 +363,310 @@ inline bool host_model(const uint8_t* data, uint64_t n, uint32_t flags, std::vec
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The decoder's side: all of RFC 1951 for a member of at most CHUNK bytes of text and SLOT_BYTES compressed bytes.
+// inflate_blocks() below is the one place that reads a deflate stream; it is a template over the sink that takes the
+// tokens (Out): pf_deflate.hip's sink spreads a match copy over a wave, host_inflate_model()'s writes byte by byte.
+// Every bound is checked here, before the sink is called: no read past the payload's last byte, no write past ISIZE,
+// no distance before the member's first byte, no symbol 286 / 287, no distance symbol 30 / 31.  Every loop iteration
+// takes at least one input bit or gives at least one output byte, so any stream ends its decode.
+enum InfStatus : uint32_t {
+    INF_OK = 0,
+    INF_NOT_DECODED,        // (another member of the call was refused before this one was looked at)
+    INF_BAD_HEAD,           // not ID1 ID2 CM=8 FLG=0, or a member shorter than its frame
+    INF_TOO_LARGE,          // ISIZE over CHUNK or more than SLOT_BYTES compressed
+    INF_TRUNCATED,          // the payload ended inside a block
+    INF_BAD_BLOCK_TYPE,     // BTYPE 3
+    INF_BAD_STORED,         // LEN != ~NLEN
+    INF_BAD_CODE,           // an over-subscribed or incomplete code, no end-of-block code, a bit pattern without a symbol
+    INF_BAD_LENGTHS,        // the dynamic header: HLIT / HDIST out of range, a repeat without a length before it or past the end
+    INF_BAD_SYMBOL,         // length symbol 286 / 287, distance symbol 30 / 31
+    INF_BAD_DISTANCE,       // a match that starts before the member's first byte
+    INF_TOO_MUCH_TEXT,      // the stream gives more than ISIZE bytes
+    INF_TOO_LITTLE_TEXT,    // the final block ended before ISIZE bytes
+    INF_NOT_AT_TAIL,        // the final block ended before the member's tail
+    INF_BAD_CRC,
+    INF_N_STATUS
+};
+inline const char* inf_status_name(uint32_t s) {
+    static const char* const names[INF_N_STATUS] = {"ok", "not decoded", "bad header", "too large", "truncated", "block type 3",
+        "stored LEN / NLEN", "bad code", "bad code lengths", "bad symbol", "distance before the start", "more text than ISIZE",
+        "less text than ISIZE", "ends before its tail", "CRC32 differs"};
+    return s < INF_N_STATUS ? names[s] : "?";
+}
+
+// bits from p[0 .. n), least significant first; a read past the end gives zeros and sets `over`
+struct BitReader {
+    const uint8_t* p; uint32_t n, pos; uint64_t buf; uint32_t cnt; bool over;
+};
+PF_HD BitReader bit_reader(const uint8_t* p, uint32_t n) { return BitReader{p, n, 0, 0, 0, false}; }
+PF_HD void refill(BitReader& r) {
+    while (r.cnt <= 56 && r.pos < r.n) { r.buf |= (uint64_t)r.p[r.pos++] << r.cnt; r.cnt += 8; }
+}
+PF_HD uint32_t take_bits(BitReader& r, uint32_t nb) {            // nb <= 32
+    if (r.cnt < nb) {
+        refill(r);
+        if (r.cnt < nb) { r.over = true; r.buf = 0; r.cnt = 0; return 0; }
+    }
+    const uint32_t v = (uint32_t)(r.buf & ((1ull << nb) - 1));
+    r.buf >>= nb; r.cnt -= nb;
+    return v;
+}
+PF_HD uint32_t byte_pos(const BitReader& r) { return r.pos - (r.cnt >> 3); }     // of the first byte no bit was taken from
+
+// symbol -> first length / distance (the extra bits: len_sym_extra, dist_sym_extra)
+PF_HD uint32_t len_base(uint32_t sym) {
+    if (sym < 265) return sym - 254;
+    if (sym == 285) return 258;
+    const uint32_t e = (sym - 261) / 4;
+    return 3 + ((4 + (sym - 261) % 4) << e);
+}
+PF_HD uint32_t dist_base(uint32_t sym) { return sym < 4 ? sym + 1 : 1 + ((2 + (sym & 1)) << (sym / 2 - 1)); }
+
+// a canonical code for decoding: count[b] = codes of b bits, sym[] = the coded symbols by (length, symbol)
+struct DecodeTables {
+    uint16_t ll_count[MAX_BITS + 1], ll_sym[288], d_count[MAX_BITS + 1], d_sym[32];
+    uint8_t lens[288 + 32];
+};
+struct CodeCounts { uint32_t c[MAX_BITS + 1]; };     // a block's counts, kept by the decode loop in registers
+
+// Tables of the code with these lengths.  INF_BAD_CODE for an over-subscribed code and for an incomplete one, except
+// the two incomplete codes RFC 1951 allows where `allow_one` says so: one symbol of one bit, and no symbol at all (a
+// block without matches; using such a code is an error where it is used).
+PF_HD uint32_t build_decode(const uint8_t* len, uint32_t n, uint16_t* count, uint16_t* sym, bool allow_one) {
+    uint32_t cnt[MAX_BITS + 1], offs[MAX_BITS + 2];
+    for (uint32_t b = 0; b <= MAX_BITS; b++) cnt[b] = 0;
+    for (uint32_t s = 0; s < n; s++) cnt[len[s] & 15]++;
+    int32_t left = 1;
+    for (uint32_t b = 1; b <= MAX_BITS; b++) {
+        left = left * 2 - (int32_t)cnt[b];
+        if (left < 0) return INF_BAD_CODE;
+    }
+    const uint32_t coded = n - cnt[0];
+    if (left > 0 && !(allow_one && (coded == 0 || (coded == 1 && cnt[1] == 1)))) return INF_BAD_CODE;
+    offs[1] = 0;
+    for (uint32_t b = 1; b <= MAX_BITS; b++) offs[b + 1] = offs[b] + cnt[b];
+    for (uint32_t s = 0; s < n; s++) if (len[s] & 15) sym[offs[len[s] & 15]++] = (uint16_t)s;
+    count[0] = 0;
+    for (uint32_t b = 1; b <= MAX_BITS; b++) count[b] = (uint16_t)cnt[b];
+    return INF_OK;
+}
+PF_HD CodeCounts load_counts(const uint16_t* count) {
+    CodeCounts k;
+    for (uint32_t b = 0; b <= MAX_BITS; b++) k.c[b] = count[b];
+    return k;
+}
+// the next symbol, or -1: no code of up to MAX_BITS bits starts this way, or the payload ended (r.over)
+PF_HD int32_t decode_sym(BitReader& r, const CodeCounts& k, const uint16_t* sym) {
+    if (r.cnt < MAX_BITS) refill(r);
+    uint32_t bits = (uint32_t)r.buf, code = 0, first = 0, index = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (uint32_t b = 1; b <= MAX_BITS; b++) {
+        code |= bits & 1; bits >>= 1;
+        const uint32_t c = k.c[b];
+        if (code < first + c) {
+            if (b > r.cnt) { r.over = true; r.buf = 0; r.cnt = 0; return -1; }
+            r.buf >>= b; r.cnt -= b;
+            return sym[index + (code - first)];
+        }
+        index += c; first = (first + c) << 1; code <<= 1;
+    }
+    if (r.cnt < MAX_BITS) r.over = true;
+    return -1;
+}
+
+PF_HD uint32_t fixed_tables(DecodeTables& T) {
+    for (uint32_t s = 0; s < 288; s++) T.lens[s] = (uint8_t)fixed_ll_len(s);
+    for (uint32_t s = 0; s < 32; s++) T.lens[288 + s] = 5;
+    const uint32_t a = build_decode(T.lens, 288, T.ll_count, T.ll_sym, false);
+    return a ? a : build_decode(T.lens + 288, 32, T.d_count, T.d_sym, false);
+}
+
+// the dynamic header behind BTYPE: HLIT, HDIST, HCLEN, the code-length code, the lengths with the run codes 16 / 17 / 18
+// (every caller reads the header, so that the reader's state stays the same for all; only the leader writes T)
+PF_HD uint32_t dynamic_tables(BitReader& r, DecodeTables& T, bool leader) {
+    const uint8_t order[N_CL] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+    const uint32_t hlit = take_bits(r, 5) + 257, hdist = take_bits(r, 5) + 1, hclen = take_bits(r, 4) + 4;
+    if (r.over) return INF_TRUNCATED;
+    if (hlit > N_LL || hdist > N_D) return INF_BAD_LENGTHS;
+    uint8_t cl[N_CL];
+    for (uint32_t i = 0; i < N_CL; i++) cl[i] = 0;
+    for (uint32_t i = 0; i < hclen; i++) cl[order[i]] = (uint8_t)take_bits(r, 3);
+    if (r.over) return INF_TRUNCATED;
+    uint16_t cl_count[MAX_BITS + 1], cl_sym[N_CL];
+    if (build_decode(cl, N_CL, cl_count, cl_sym, false)) return INF_BAD_CODE;
+    const CodeCounts k = load_counts(cl_count);
+    const uint32_t total = hlit + hdist;
+    uint32_t prev = 0;
+    for (uint32_t i = 0; i < total;) {
+        const int32_t s = decode_sym(r, k, cl_sym);
+        if (s < 0) return r.over ? INF_TRUNCATED : INF_BAD_CODE;
+        if (s < 16) { if (leader) T.lens[i] = (uint8_t)s; i++; prev = (uint32_t)s; continue; }
+        uint32_t rep, v = 0;
+        if (s == 16) { if (i == 0) return INF_BAD_LENGTHS; v = prev; rep = 3 + take_bits(r, 2); }
+        else if (s == 17) rep = 3 + take_bits(r, 3);
+        else rep = 11 + take_bits(r, 7);
+        if (r.over) return INF_TRUNCATED;
+        if (i + rep > total) return INF_BAD_LENGTHS;
+        if (leader) for (uint32_t j = 0; j < rep; j++) T.lens[i + j] = (uint8_t)v;
+        i += rep; prev = v;
+    }
+    if (!leader) return INF_OK;
+    if (T.lens[256] == 0) return INF_BAD_CODE;                     // a block cannot end without this code
+    // (the distance lengths first: they stand behind the literal / length ones, whose table is not lens[])
+    const uint32_t a = build_decode(T.lens + hlit, hdist, T.d_count, T.d_sym, true);
+    return a ? a : build_decode(T.lens, hlit, T.ll_count, T.ll_sym, true);
+}
+
+// The blocks of one member's payload, p[0 .. n), into a sink that holds at most `isize` bytes.  Out has
+//   bool leader()                      whether this caller writes the shared tables (the device: one lane of the wave)
+//   void sync()                        after the leader's writes, before anyone reads them
+//   uint32_t share(v)                  the leader's v
+//   void literal(o, byte)              text[o] = byte
+//   void copy(o, dist, len)            text[o + i] = text[o - dist + i], i = 0 .. len - 1, as if byte by byte
+//   void stored(o, src, len)           text[o + i] = src[i]
+// *produced: the bytes given.  INF_OK: the final block ended with exactly isize bytes given and exactly at p + n.
+template <class Out>
+PF_HD uint32_t inflate_blocks(const uint8_t* p, uint32_t n, uint32_t isize, DecodeTables& T, Out& out, uint32_t* produced) {
+    BitReader r = bit_reader(p, n);
+    uint32_t o = 0, bfinal = 0;
+    *produced = 0;
+    do {
+        bfinal = take_bits(r, 1);
+        const uint32_t btype = take_bits(r, 2);
+        if (r.over) return INF_TRUNCATED;
+        if (btype == 3) return INF_BAD_BLOCK_TYPE;
+        if (btype == 0) {
+            (void)take_bits(r, r.cnt & 7);
+            const uint32_t len = take_bits(r, 16), nlen = take_bits(r, 16);
+            if (r.over) return INF_TRUNCATED;
+            if (len != (~nlen & 0xFFFFu)) return INF_BAD_STORED;
+            const uint32_t at = byte_pos(r);
+            if (len > n - at) return INF_TRUNCATED;
+            if (len > isize - o) return INF_TOO_MUCH_TEXT;
+            out.stored(o, p + at, len);
+            o += len; *produced = o;
+            r.pos = at + len; r.buf = 0; r.cnt = 0;
+            continue;
+        }
+        uint32_t st = INF_OK;
+        if (btype == 1) { if (out.leader()) st = fixed_tables(T); }
+        else st = dynamic_tables(r, T, out.leader());
+        out.sync();
+        st = out.share(st);                    // (every caller asks: the leader's lane must be there to answer)
+        if (st) return st;
+        const CodeCounts kl = load_counts(T.ll_count), kd = load_counts(T.d_count);
+        for (;;) {
+            const int32_t s = decode_sym(r, kl, T.ll_sym);
+            if (s < 0) return r.over ? INF_TRUNCATED : INF_BAD_CODE;
+            if (s < 256) {
+                if (o >= isize) return INF_TOO_MUCH_TEXT;
+                out.literal(o, (uint8_t)s);
+                o++; *produced = o;
+                continue;
+            }
+            if (s == 256) break;
+            if (s >= (int32_t)N_LL) return INF_BAD_SYMBOL;
+            const uint32_t len = len_base((uint32_t)s) + take_bits(r, len_sym_extra((uint32_t)s));
+            const int32_t ds = decode_sym(r, kd, T.d_sym);
+            if (ds < 0) return r.over ? INF_TRUNCATED : INF_BAD_CODE;
+            if (ds >= (int32_t)N_D) return INF_BAD_SYMBOL;
+            const uint32_t dist = dist_base((uint32_t)ds) + take_bits(r, dist_sym_extra((uint32_t)ds));
+            if (r.over) return INF_TRUNCATED;
+            if (dist > o) return INF_BAD_DISTANCE;
+            if (len > isize - o) return INF_TOO_MUCH_TEXT;
+            out.copy(o, dist, len);
+            o += len; *produced = o;
+        }
+        out.sync();                    // (the next block's tables take this one's place)
+    } while (!bfinal);
+    if (o != isize) return INF_TOO_LITTLE_TEXT;
+    return byte_pos(r) == n ? INF_OK : INF_NOT_AT_TAIL;
+}
+
+// ---- where members start, without decoding: the first member's ID1 ID2 CM FLG MTIME are the signature, every place
+// they stand at is a candidate, a member's tail is the 8 bytes before the next candidate (or the end).  XFL and OS are
+// left out of the signature: a file of this project's starts with the header line's member, which zlib wrote with its
+// own XFL and OS, and goes on with the device's (both write MTIME = 0).  Eight bytes: a false candidate inside compressed
+// bytes comes once in 2^64 positions, and is refused by the checks of the member it cuts in two.
+constexpr uint32_t MEMBER_SIG = 8;
+struct MemberRef {
+    uint64_t at;             // of the member's head in the bytes given
+    uint32_t size, isize, crc, status;      // whole member's bytes; from its tail; INF_OK or why it is not taken
+};
+inline bool member_head_ok(const uint8_t* p, uint64_t n) { return n >= MEMBER_HEAD && p[0] == 0x1F && p[1] == 0x8B && p[2] == 8 && p[3] == 0; }
+inline uint32_t le32(const uint8_t* p) { return p[0] | p[1] << 8 | p[2] << 16 | (uint32_t)p[3] << 24; }
+// the members of p[0 .. n): those that end before another candidate, and with `last` the one that ends at n too.
+// *consumed: the bytes of the members listed.  false: p does not start with a head this decoder takes.
+inline bool list_members(const uint8_t* p, uint64_t n, bool last, std::vector<MemberRef>& out, uint64_t* consumed) {
+    out.clear(); *consumed = 0;
+    if (!n) return true;
+    if (!member_head_ok(p, n)) return false;
+    std::vector<uint64_t> starts(1, 0);
+    for (uint64_t at = 1; at + MEMBER_HEAD <= n;) {
+        const void* hit = memmem(p + at, (size_t)(n - at), p, MEMBER_SIG);
+        if (!hit) break;
+        at = (uint64_t)(static_cast<const uint8_t*>(hit) - p);
+        starts.push_back(at);
+        at++;
+    }
+    if (last) starts.push_back(n);
+    for (size_t i = 0; i + 1 < starts.size(); i++) {
+        MemberRef m{starts[i], 0, 0, 0, INF_OK};
+        const uint64_t size = starts[i + 1] - starts[i];
+        if (size < MEMBER_HEAD + MEMBER_TAIL) m.status = INF_BAD_HEAD;
+        else if (size > SLOT_BYTES) m.status = INF_TOO_LARGE;
+        else {
+            m.size = (uint32_t)size;
+            m.crc = le32(p + starts[i + 1] - 8); m.isize = le32(p + starts[i + 1] - 4);
+            if (m.isize > CHUNK) m.status = INF_TOO_LARGE;
+        }
+        out.push_back(m);
+    }
+    *consumed = starts.back();
+    return true;
+}
+inline int64_t first_refused(const std::vector<MemberRef>& ms) {
+    for (size_t i = 0; i < ms.size(); i++) if (ms[i].status != INF_OK) return (int64_t)i;
+    return -1;
+}
+
+struct HostSink {
+    uint8_t* w;
+    bool leader() const { return true; }
+    void sync() {}
+    uint32_t share(uint32_t v) const { return v; }
+    void literal(uint32_t o, uint8_t b) { w[o] = b; }
+    void copy(uint32_t o, uint32_t dist, uint32_t len) { for (uint32_t i = 0; i < len; i++) w[o + i] = w[o - dist + i]; }
+    void stored(uint32_t o, const uint8_t* src, uint32_t len) { if (len) memcpy(w + o, src, len); }
+};
+
+// The serial host model of the device decoder: the same functions, one member after the other, each from a buffer of
+// exactly its payload into one of exactly ISIZE bytes (a sanitizer build sees any step past either).  false: "not
+// taken", *first_bad / *status name the first member refused (a head that is not taken: member 0, INF_BAD_HEAD).
+inline bool host_inflate_model(const uint8_t* p, uint64_t n, std::vector<uint8_t>& text, uint64_t* first_bad, uint32_t* status) {
+    text.clear(); *first_bad = 0; *status = INF_OK;
+    std::vector<MemberRef> ms;
+    uint64_t consumed = 0;
+    if (!list_members(p, n, true, ms, &consumed)) { *status = INF_BAD_HEAD; return false; }
+    const int64_t bad = first_refused(ms);
+    if (bad >= 0) { *first_bad = (uint64_t)bad; *status = ms[(size_t)bad].status; return false; }
+    DecodeTables T;
+    for (size_t i = 0; i < ms.size(); i++) {
+        const std::vector<uint8_t> payload(p + ms[i].at + MEMBER_HEAD, p + ms[i].at + ms[i].size - MEMBER_TAIL);
+        std::vector<uint8_t> window(ms[i].isize);
+        HostSink sink{window.data()};
+        uint32_t produced = 0;
+        uint32_t st = inflate_blocks(payload.data(), (uint32_t)payload.size(), ms[i].isize, T, sink, &produced);
+        if (!st && crc32_bytes(window.data(), ms[i].isize) != ms[i].crc) st = INF_BAD_CRC;
+        if (st) { *first_bad = i; *status = st; text.clear(); return false; }
+        text.insert(text.end(), window.begin(), window.end());
+    }
+    return true;
+}
+
 }  // namespace pfgz
 
 #if defined(__HIPCC__)
@@ -383,5 +692,27 @@ struct PfGzEncoder {
                hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
     // once the caller has synchronised with that encode: the bytes of its members; PF_ERR_STATE if they exceed its cap
     int member_bytes(Cursor w, uint64_t* z) const;
+};
+// The device decoder: members in, text out, one wave per member (gz_inflate_kernel).  Its buffers hold the members of one
+// call, MAX_MEMBERS at most, each of SLOT_BYTES at most: device_bytes() <= MAX_MEMBERS * (SLOT_BYTES + 48) + slack; the
+// text buffer is the caller's.  Every call is stream-ordered on the stream given.
+namespace pfgz {
+struct DecMember { uint64_t src, dst; uint32_t csize, isize, crc, pad; };     // payload offset in the upload, text offset
+struct DecResult { uint32_t status, produced, crc, pad; };                   // an InfStatus, the bytes given, the CRC32 found
+}
+struct PfGzDecoder {
+    static constexpr uint64_t MAX_TEXT = 256ull << 20;        // text bytes per call: the row filter's block
+    static constexpr uint32_t MAX_MEMBERS = (uint32_t)(MAX_TEXT / pfgz::CHUNK);
+    DevBuf members, desc, results;
+    PinBuf pin;                                              // the results, read back
+    std::vector<pfgz::DecMember> desc_host;
+    uint32_t n_last = 0;
+    uint64_t device_bytes() const { return members.cap + desc.cap + results.cap; }
+    // On `st`: the n members ms[] (listed over `bytes`, host memory, all with status INF_OK) uploaded and inflated
+    // into text[0 .. sum of their ISIZE), which must fit text_cap; their results on the way into pinned memory.
+    int decode(hipStream_t st, const uint8_t* bytes, const pfgz::MemberRef* ms, uint32_t n, uint8_t* text, uint64_t text_cap,
+               hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+    // once the caller has synchronised with that decode: the first member that failed a check and its status, or -1
+    int64_t first_refused(uint32_t* status) const;
 };
 #endif

@@ -1,4 +1,4 @@
-// pf_deflate.hip -- the deflate encoder on the device (format logic: pf_deflate.h) and the host model's entry point.
+// pf_deflate.hip -- the deflate encoder and decoder on the device (format logic: pf_deflate.h) and the host models' entry points.
 //
 // gz_encode_kernel: one workgroup of 256 threads per chunk of CHUNK bytes (a grid of two workgroups per CU walks the
 // chunks).  The chunk's text is staged in LDS beside a hash table of 4 096 positions.  Matches are found in steps of 256
@@ -284,6 +284,79 @@ __global__ __launch_bounds__(THREADS) void gz_gather_kernel(const uint8_t* slots
     if (done + tid < m) dst[done + tid] = src[done + tid];
 }
 
+// ---- the decoder.  gz_inflate_kernel: one wave (a workgroup of 64 threads) per member.  A member is a serial bit chain, so
+// the wave's lanes all read the same bits (inflate_blocks, pf_deflate.h) and keep the same state; what the wave shares out
+// is a token's work: a match's or a stored block's bytes go one per lane.  The member's text is built in a CHUNK-byte
+// window in LDS: a match reads bytes that other lanes of the wave wrote a moment before, and in LDS the wave's accesses
+// are served in the order they were issued -- a fence in front of every match copy keeps the compiler to that order and
+// waits for the writes; nothing of this has to become visible through the caches of global memory.  The CRC32 is taken
+// from the window, a piece per lane, the pieces combined by shuffles, and the text leaves in 16-byte stores.
+// LDS: 32 KiB + 32 B of window, 1.3 KiB of tables -- four workgroups per CU within its 160 KiB; more waves per CU would
+// need the window in HBM, and then every match would wait on a round trip through L2 for bytes its own wave just wrote.
+// No wave waits for another: there is no barrier between workgroups, no flag, no loop without a bound.
+constexpr uint32_t WIN_WORDS = CHUNK / 4 + 8;       // (the copy out reads up to four words past a 16-byte unit's first)
+
+struct DecParams { const uint8_t* members; const DecMember* m; uint32_t n; uint8_t* text; DecResult* res; };
+
+struct WaveSink {
+    uint8_t* w; uint32_t lane;
+    __device__ bool leader() const { return lane == 0; }
+    __device__ void sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __builtin_amdgcn_wave_barrier(); }
+    __device__ uint32_t share(uint32_t v) const { return (uint32_t)__shfl((int)v, 0, 64); }
+    __device__ void literal(uint32_t o, uint8_t b) { if (lane == 0) w[o] = b; }
+    // byte o + i is byte o - dist + i mod dist: the bytes [o - dist, o) are all there before the copy starts, which is
+    // what the byte-serial copy of an overlapping match (dist < len) comes to
+    __device__ void copy(uint32_t o, uint32_t dist, uint32_t len) {
+        sync();
+        const uint8_t* from = w + o - dist;
+        if (dist >= len) { for (uint32_t i = lane; i < len; i += 64) w[o + i] = from[i]; }
+        else { for (uint32_t i = lane; i < len; i += 64) w[o + i] = from[i % dist]; }
+    }
+    __device__ void stored(uint32_t o, const uint8_t* src, uint32_t len) { for (uint32_t i = lane; i < len; i += 64) w[o + i] = src[i]; }
+};
+
+__global__ __launch_bounds__(64) void gz_inflate_kernel(DecParams P) {
+    __shared__ uint32_t s_win[WIN_WORDS];
+    __shared__ DecodeTables s_T;
+    const uint32_t lane = threadIdx.x, mi = blockIdx.x;
+    if (mi >= P.n) return;
+    const DecMember m = P.m[mi];
+    uint8_t* win = reinterpret_cast<uint8_t*>(s_win);
+    WaveSink sink{win, lane};
+    uint32_t produced = 0;
+    uint32_t st = m.isize <= CHUNK ? inflate_blocks(P.members + m.src, m.csize, m.isize, s_T, sink, &produced) : (uint32_t)INF_TOO_LARGE;
+    sink.sync();
+    uint32_t crc = 0;
+    if (st == INF_OK) {
+        const uint32_t piece = (m.isize + 63) / 64, at = lane * piece;
+        uint32_t len = at < m.isize ? min(piece, m.isize - at) : 0;
+        crc = len ? crc32_bytes(win + at, len) : 0;
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t oc = (uint32_t)__shfl_down((int)crc, d, 64), ol = (uint32_t)__shfl_down((int)len, d, 64);
+            if ((lane & (2 * d - 1)) == 0 && ol) { crc = len ? crc_combine(crc, oc, ol) : oc; len += ol; }
+        }
+        crc = (uint32_t)__shfl((int)crc, 0, 64);
+        if (crc != m.crc) st = INF_BAD_CRC;
+    }
+    if (lane == 0) P.res[mi] = DecResult{st, produced, crc, 0};
+    if (st != INF_OK) return;
+    // the text to its place: single bytes up to the destination's next 16-byte boundary, 16-byte units, single bytes
+    uint8_t* dst = P.text + m.dst;
+    const uint32_t head = min(m.isize, (uint32_t)(-reinterpret_cast<uintptr_t>(dst) & 15));
+    if (lane < head) dst[lane] = win[lane];
+    const uint32_t nvec = (m.isize - head) / 16, done = head + 16 * nvec;
+    for (uint32_t v = lane; v < nvec; v += 64) {
+        const uint32_t s = head + 16 * v, wi = s >> 2, sh = 8 * (s & 3);
+        uint32_t x[5];
+        for (int k = 0; k < 5; k++) x[k] = s_win[wi + k];
+        uint4 o;
+        o.x = (uint32_t)((((uint64_t)x[1] << 32) | x[0]) >> sh); o.y = (uint32_t)((((uint64_t)x[2] << 32) | x[1]) >> sh);
+        o.z = (uint32_t)((((uint64_t)x[3] << 32) | x[2]) >> sh); o.w = (uint32_t)((((uint64_t)x[4] << 32) | x[3]) >> sh);
+        *reinterpret_cast<uint4*>(dst + s) = o;
+    }
+    if (done + lane < m.isize) dst[done + lane] = win[done + lane];
+}
+
 }  // namespace pfgz
 
 int PfGzEncoder::ensure(int n_cu) {
@@ -334,6 +407,44 @@ int PfGzEncoder::member_bytes(Cursor w, uint64_t* z) const {
     return PF_OK;
 }
 
+int PfGzDecoder::decode(hipStream_t st, const uint8_t* bytes, const pfgz::MemberRef* ms, uint32_t n, uint8_t* text, uint64_t text_cap,
+                        hipEvent_t t0, hipEvent_t t1) {
+    if (n > MAX_MEMBERS) return fail(PF_ERR_ARG, "gzip decoder: more than %u members in a call", MAX_MEMBERS);
+    n_last = n;
+    if (!n) return PF_OK;
+    const uint64_t lo = ms[0].at, hi = ms[n - 1].at + ms[n - 1].size;
+    desc_host.resize(n);
+    uint64_t dst = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (ms[i].status != pfgz::INF_OK || ms[i].size < pfgz::MEMBER_HEAD + pfgz::MEMBER_TAIL || ms[i].at + ms[i].size > hi || ms[i].at < lo)
+            return fail(PF_ERR_ARG, "gzip decoder: member %u was not listed as taken", i);
+        desc_host[i] = pfgz::DecMember{ms[i].at - lo + pfgz::MEMBER_HEAD, dst, ms[i].size - pfgz::MEMBER_HEAD - pfgz::MEMBER_TAIL, ms[i].isize,
+                                       ms[i].crc, 0};
+        dst += ms[i].isize;
+    }
+    if (dst > text_cap) return fail(PF_ERR_ARG, "gzip decoder: the members' text exceeds its buffer");
+    PFCHK(members.ensure(hi - lo + 16));
+    PFCHK(desc.ensure((size_t)n * sizeof(pfgz::DecMember)));
+    PFCHK(results.ensure((size_t)n * sizeof(pfgz::DecResult)));
+    PFCHK(pin.ensure((size_t)n * sizeof(pfgz::DecResult)));
+    HIPCHK(hipMemcpyAsync(members.p, bytes + lo, hi - lo, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(desc.p, desc_host.data(), (size_t)n * sizeof(pfgz::DecMember), hipMemcpyHostToDevice, st));
+    if (t0) HIPCHK(hipEventRecord(t0, st));
+    pfgz::DecParams P{members.as<uint8_t>(), desc.as<pfgz::DecMember>(), n, text, results.as<pfgz::DecResult>()};
+    hipLaunchKernelGGL(pfgz::gz_inflate_kernel, dim3(n), dim3(64), 0, st, P);
+    HIPCHK(hipGetLastError());
+    if (t1) HIPCHK(hipEventRecord(t1, st));
+    HIPCHK(hipMemcpyAsync(pin.p, results.p, (size_t)n * sizeof(pfgz::DecResult), hipMemcpyDeviceToHost, st));
+    return PF_OK;
+}
+
+int64_t PfGzDecoder::first_refused(uint32_t* status) const {
+    const pfgz::DecResult* r = pin.as<pfgz::DecResult>();
+    for (uint32_t i = 0; i < n_last; i++)
+        if (r[i].status != pfgz::INF_OK) { *status = r[i].status; return i; }
+    return -1;
+}
+
 extern "C" {
 
 uint32_t pf_gzip_device_chunk_bytes(void) { return pfgz::CHUNK; }
@@ -348,6 +459,23 @@ int pf_gzip_host_model(const char* data, uint64_t n, uint32_t flags, char** out,
     if (!buf) return fail(PF_ERR_OOM, "pf_gzip_host_model: out of memory");
     if (!members.empty()) memcpy(buf, members.data(), members.size());
     *out = buf; *out_n = members.size();
+    return PF_OK;
+}
+
+int pf_gunzip_host_model(const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken) {
+    if ((!members && n) || !out || !out_n || !taken) return fail(PF_ERR_ARG, "pf_gunzip_host_model: null argument");
+    *out = nullptr; *out_n = 0; *taken = 0;
+    std::vector<uint8_t> text;
+    uint64_t bad = 0;
+    uint32_t status = 0;
+    if (!pfgz::host_inflate_model(reinterpret_cast<const uint8_t*>(members), n, text, &bad, &status)) {
+        (void)fail(PF_OK, "pf_gunzip_host_model: not taken: member %llu: %s", (unsigned long long)bad, pfgz::inf_status_name(status));
+        return PF_OK;
+    }
+    char* buf = (char*)malloc(text.size() ? text.size() : 1);
+    if (!buf) return fail(PF_ERR_OOM, "pf_gunzip_host_model: out of memory");
+    if (!text.empty()) memcpy(buf, text.data(), text.size());
+    *out = buf; *out_n = text.size(); *taken = 1;
     return PF_OK;
 }
 

@@ -16,6 +16,7 @@
 
 #include "../../include/panfeed_hip.h"
 #include "pf_buf.h"
+#include "pf_deflate.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -133,6 +134,52 @@ __global__ __launch_bounds__(256) void rowfilter_kernel(RfParams p) {
     }
 }
 
+// ---- the scan of text that never was on the host (pf_rowfilter_scan_members): where its complete lines end, and the
+// candidates' lines gathered into one buffer for the host's exact check
+// out[0] = bytes of complete lines of text[0 .. total), out[1] = total; with `last`, a final line without a newline is
+// given one first (the buffer has room for it).  One workgroup; it walks back from the end 4 096 bytes a step until a
+// step holds a newline.
+__global__ __launch_bounds__(256) void rf_tail_kernel(unsigned char* text, uint64_t total, int last, uint64_t* out) {
+    __shared__ unsigned long long s_best;
+    const uint32_t tid = threadIdx.x;
+    if (last && total && text[total - 1] != '\n') {       // (every thread reads the same byte: the branch is uniform)
+        if (tid == 0) { text[total] = '\n'; out[0] = total + 1; out[1] = total + 1; }
+        return;
+    }
+    if (tid == 0) s_best = 0;
+    __syncthreads();
+    for (uint64_t end = total; end > 0; end = end > 4096 ? end - 4096 : 0) {
+        const uint64_t lo = end > 4096 ? end - 4096 : 0;
+        const uint64_t a = lo + 16ull * tid, b = a + 16 < end ? a + 16 : end;
+        for (uint64_t i = b; i > a; i--)
+            if (text[i - 1] == '\n') { atomicMax(&s_best, (unsigned long long)i); break; }
+        __syncthreads();
+        const unsigned long long best = s_best;
+        __syncthreads();                              // (nobody adds to it for the next step before all have read it)
+        if (best) break;
+    }
+    if (tid == 0) { out[0] = s_best; out[1] = total; }
+}
+
+// candidate k's line, [b, e) with its newline, as pf_rowfilter_scan finds it on the host
+__global__ __launch_bounds__(256) void rf_extent_kernel(const unsigned char* text, uint64_t n, const uint64_t* pos, uint64_t cnt,
+                                                         int first_field, uint64_t* begin, uint64_t* end) {
+    const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (k >= cnt) return;
+    const uint64_t q = pos[k] < n ? pos[k] : n - 1;
+    uint64_t b = q, e = q;
+    if (first_field) { while (e < n && text[e] != '\n') e++; }
+    else { while (b > 0 && text[b - 1] != '\n') b--; }
+    begin[k] = b; end[k] = e + 1 <= n ? e + 1 : n;
+}
+
+// line k to lines + off[k]; a workgroup of 64 per line
+__global__ __launch_bounds__(64) void rf_gather_kernel(const unsigned char* text, const uint64_t* begin, const uint64_t* end,
+                                                        const uint64_t* off, unsigned char* lines) {
+    const uint64_t k = blockIdx.x, b = begin[k], m = end[k] - b;
+    for (uint64_t i = threadIdx.x; i < m; i += 64) lines[off[k] + i] = text[b + i];
+}
+
 }  // namespace
 
 struct pf_rowfilter {
@@ -150,7 +197,57 @@ struct pf_rowfilter {
     uint64_t bytes_scanned = 0;
     float device_ms = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
+    // pf_rowfilter_scan_members: the decoder, the unfinished line carried from one call to the next (device), the
+    // candidates' lines (extents and offsets on the device, the gathered bytes on both sides), the kept lines
+    PfGzDecoder dec;
+    DevBuf d_carry, d_ext, d_lines, d_tail;
+    uint64_t carry_n = 0;
+    bool want_header = false;
+    std::string header, raw_lines, lines;
+    uint64_t gz_members = 0, gz_text_bytes = 0;
+    float gz_ms = 0;
 };
+
+namespace {
+
+// The text is on the device -- d_text[0 .. n), complete lines, the buffer reaching to the next multiple of 16 bytes -- scan
+// it: the candidates' positions, sorted.  On the filter's stream, behind whatever put the text there.
+int rf_scan_device(pf_rowfilter* f, uint64_t n, std::vector<uint64_t>& pos) {
+    // room for the candidates: the filter keeps few rows, so the room is a guess (a position per 64 bytes of text, a
+    // million at least) and the kernel is run again with what it asked for should the guess be too small -- counting
+    // the lines of the block on the host to size it for the worst case cost more than the kernel itself
+    const size_t guess = std::max<size_t>((size_t)1 << 20, (size_t)(n / 64));
+    PFCHK(f->d_out.ensure(guess * 8, true));
+    unsigned long long cnt = 0;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        HIPCHK(hipMemsetAsync(f->d_count.p, 0, 8, f->stream));
+        RfParams p{};
+        p.text = f->d_text.as<unsigned char>(); p.n = n; p.set = f->d_set.as<uint64_t>(); p.cap = f->cap;
+        p.first_field = f->first_field;
+        p.out = f->d_out.as<uint64_t>(); p.count = f->d_count.as<unsigned long long>(); p.out_cap = f->d_out.cap / 8;
+        const uint64_t nvec = (n + 15) / 16;
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((nvec + 255) / 256, 256 * 16);
+        HIPCHK(hipEventRecord(f->e0, f->stream));
+        hipLaunchKernelGGL(rowfilter_kernel, dim3(blocks), dim3(256), 0, f->stream, p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(f->e1, f->stream));
+        HIPCHK(hipMemcpyAsync(&cnt, f->d_count.p, 8, hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(hipStreamSynchronize(f->stream));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, f->e0, f->e1) == hipSuccess) f->device_ms += ms;
+        if (cnt <= f->d_out.cap / 8) break;
+        // more candidates than room (the kernel counted them all and kept what fitted): again, with room for all
+        PFCHK(f->d_out.ensure(((size_t)cnt + (size_t)cnt / 8) * 8, true));
+    }
+    f->bytes_scanned += n;
+    if (cnt > f->d_out.cap / 8) return fail(PF_ERR_STATE, "pf_rowfilter_scan: more candidates than room, twice");
+    pos.resize((size_t)cnt);
+    if (cnt) HIPCHK(hipMemcpy(pos.data(), f->d_out.p, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+    std::sort(pos.begin(), pos.end());
+    return PF_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -219,11 +316,6 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
     const size_t padded = (n + 15) / 16 * 16 + 16;
     if (padded > f->d_text.cap) PFCHK(f->d_text.ensure(padded + padded / 8, true));
     if (padded > f->pin.cap) PFCHK(f->pin.ensure(padded + padded / 8, true));
-    // room for the candidates: the filter keeps few rows, so the room is a guess (a position per 64 bytes of text, a
-    // million at least) and the kernel is run again with what it asked for should the guess be too small -- counting
-    // the lines of the block on the host to size it for the worst case cost more than the kernel itself
-    const size_t guess = std::max<size_t>((size_t)1 << 20, (size_t)(n / 64));
-    PFCHK(f->d_out.ensure(guess * 8, true));
     {   // the block into pinned memory on a few threads (one memcpy of 256 MB is slower than the rest of the call)
         char* const pin = f->pin.as<char>();
         const unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(8, n >> 22));
@@ -238,32 +330,8 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
         memset(pin + n, 0, padded - n);
     }
     HIPCHK(hipMemcpyAsync(f->d_text.p, f->pin.p, padded, hipMemcpyHostToDevice, f->stream));
-    unsigned long long cnt = 0;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        HIPCHK(hipMemsetAsync(f->d_count.p, 0, 8, f->stream));
-        RfParams p{};
-        p.text = f->d_text.as<unsigned char>(); p.n = n; p.set = f->d_set.as<uint64_t>(); p.cap = f->cap;
-        p.first_field = f->first_field;
-        p.out = f->d_out.as<uint64_t>(); p.count = f->d_count.as<unsigned long long>(); p.out_cap = f->d_out.cap / 8;
-        const uint64_t nvec = (n + 15) / 16;
-        const uint32_t blocks = (uint32_t)std::min<uint64_t>((nvec + 255) / 256, 256 * 16);
-        HIPCHK(hipEventRecord(f->e0, f->stream));
-        hipLaunchKernelGGL(rowfilter_kernel, dim3(blocks), dim3(256), 0, f->stream, p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(f->e1, f->stream));
-        HIPCHK(hipMemcpyAsync(&cnt, f->d_count.p, 8, hipMemcpyDeviceToHost, f->stream));
-        HIPCHK(hipStreamSynchronize(f->stream));
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, f->e0, f->e1) == hipSuccess) f->device_ms += ms;
-        if (cnt <= f->d_out.cap / 8) break;
-        // more candidates than room (the kernel counted them all and kept what fitted): again, with room for all
-        PFCHK(f->d_out.ensure(((size_t)cnt + (size_t)cnt / 8) * 8, true));
-    }
-    f->bytes_scanned += n;
-    if (cnt > f->d_out.cap / 8) return fail(PF_ERR_STATE, "pf_rowfilter_scan: more candidates than room, twice");
-    std::vector<uint64_t> pos((size_t)cnt);
-    if (cnt) HIPCHK(hipMemcpy(pos.data(), f->d_out.p, (size_t)cnt * 8, hipMemcpyDeviceToHost));
-    std::sort(pos.begin(), pos.end());
+    std::vector<uint64_t> pos;
+    PFCHK(rf_scan_device(f, n, pos));
     // exact check of every candidate (a 64-bit hash collision must not add a row), then the line's extent
     for (uint64_t q : pos) {
         uint64_t b, e;
@@ -291,6 +359,158 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
         f->end.push_back(e + 1 <= n ? e + 1 : n);          // the '\n' is part of the line
     }
     *line_begin = f->begin.data(); *line_end = f->end.data(); *n_lines = f->begin.size();
+    return PF_OK;
+}
+
+int pf_rowfilter_members_begin(pf_rowfilter* f, int header) {
+    if (!f) return fail(PF_ERR_ARG, "pf_rowfilter_members_begin: null argument");
+    f->carry_n = 0; f->want_header = header != 0; f->header.clear();
+    return PF_OK;
+}
+
+int pf_rowfilter_members_header(pf_rowfilter* f, const char** line, uint64_t* nbytes) {
+    if (!f || !line || !nbytes) return fail(PF_ERR_ARG, "pf_rowfilter_members_header: null argument");
+    *line = f->header.data(); *nbytes = f->header.size();
+    return PF_OK;
+}
+
+int pf_rowfilter_scan_members(pf_rowfilter* f, const char* members, uint64_t nbytes, int last, const char** lines,
+                              uint64_t* lines_bytes, uint64_t* n_lines, uint64_t* consumed, int* taken) {
+    if (!f || !lines || !lines_bytes || !n_lines || !consumed || !taken || (nbytes && !members))
+        return fail(PF_ERR_ARG, "pf_rowfilter_scan_members: null argument");
+    HIPCHK(hipSetDevice(f->device));
+    f->lines.clear();
+    *lines = f->lines.data(); *lines_bytes = 0; *n_lines = 0; *consumed = 0; *taken = 0;
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(members);
+    // (whatever refuses the block leaves no line carried: the caller starts over another way)
+    auto refuse = [&](uint64_t member, uint32_t status) {
+        f->carry_n = 0;
+        (void)fail(PF_OK, "pf_rowfilter_scan_members: not taken: member %llu of the block: %s", (unsigned long long)member,
+                   pfgz::inf_status_name(status));
+        return PF_OK;
+    };
+    std::vector<pfgz::MemberRef> ms;
+    uint64_t listed = 0;
+    if (!pfgz::list_members(bytes, nbytes, last != 0, ms, &listed)) return refuse(0, pfgz::INF_BAD_HEAD);
+    // a member this decoder takes would have ended by now
+    if (ms.empty() && !last && nbytes >= pfgz::SLOT_BYTES + pfgz::MEMBER_HEAD) return refuse(0, pfgz::INF_TOO_LARGE);
+    if (ms.empty() && !last) { *taken = 1; return PF_OK; }            // no whole member yet: the caller reads on
+    // at most the decoder's call: the rest is the caller's to give again
+    uint64_t text_n = 0;
+    size_t take = 0;
+    while (take < ms.size() && take < PfGzDecoder::MAX_MEMBERS) {
+        if (ms[take].status != pfgz::INF_OK) return refuse(take, ms[take].status);
+        if (take && text_n + ms[take].isize > PfGzDecoder::MAX_TEXT) break;
+        text_n += ms[take].isize; take++;
+    }
+    const bool all = take == ms.size();
+    const uint64_t used = all ? listed : ms[take].at;
+    const bool end = last && all;
+    // the device text: the line carried over, then the members' text; room for a final newline and the scan's 16-byte reads
+    uint64_t total = f->carry_n + text_n;
+    const size_t padded = (total + 1 + 15) / 16 * 16 + 16;
+    if (padded > f->d_text.cap) PFCHK(f->d_text.ensure(padded + padded / 8, true));
+    PFCHK(f->d_tail.ensure(16, true));
+    if (f->carry_n) HIPCHK(hipMemcpyAsync(f->d_text.p, f->d_carry.p, f->carry_n, hipMemcpyDeviceToDevice, f->stream));
+    PFCHK(f->dec.decode(f->stream, bytes, ms.data(), (uint32_t)take, f->d_text.as<uint8_t>() + f->carry_n, text_n, f->e0, f->e1));
+    hipLaunchKernelGGL(rf_tail_kernel, dim3(1), dim3(256), 0, f->stream, f->d_text.as<unsigned char>(), total, end ? 1 : 0,
+                       f->d_tail.as<uint64_t>());
+    HIPCHK(hipGetLastError());
+    uint64_t tail[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(tail, f->d_tail.p, 16, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(hipStreamSynchronize(f->stream));
+    if (take) {
+        float ms_ = 0;
+        if (hipEventElapsedTime(&ms_, f->e0, f->e1) == hipSuccess) f->gz_ms += ms_;
+        uint32_t status = 0;
+        const int64_t bad = f->dec.first_refused(&status);
+        if (bad >= 0) return refuse((uint64_t)bad, status);
+    }
+    const uint64_t n = tail[0];
+    total = tail[1];
+    uint64_t skip = 0;                                  // the header line's bytes: no candidate of it is a row
+    if (f->want_header) {
+        std::string front((size_t)std::min<uint64_t>(n, 1 << 16), '\0');
+        if (!front.empty()) HIPCHK(hipMemcpy(&front[0], f->d_text.p, front.size(), hipMemcpyDeviceToHost));
+        const size_t nl = front.find('\n');
+        if (nl == std::string::npos) {
+            if (!(end && total == 0)) return refuse(0, pfgz::INF_NOT_DECODED);      // (a header line over 64 KiB or over a call's text)
+        } else {
+            f->header.assign(front, 0, nl + 1);
+            skip = nl + 1;
+        }
+        f->want_header = false;
+    }
+    f->gz_members += take; f->gz_text_bytes += text_n;
+    if (n && !f->keys.empty()) {
+        std::vector<uint64_t> pos;
+        PFCHK(rf_scan_device(f, n, pos));
+        const uint64_t cnt = pos.size();
+        if (cnt) {
+            // the candidates' lines: extents on the device, offsets by the host, one gather, one copy down
+            PFCHK(f->d_ext.ensure((size_t)cnt * 24, true));
+            uint64_t* const d_begin = f->d_ext.as<uint64_t>(), *const d_end = d_begin + cnt, *const d_off = d_end + cnt;
+            HIPCHK(hipMemcpyAsync(f->d_out.p, pos.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, f->stream));
+            hipLaunchKernelGGL(rf_extent_kernel, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, f->stream,
+                               f->d_text.as<const unsigned char>(), n, f->d_out.as<const uint64_t>(), cnt, f->first_field, d_begin, d_end);
+            HIPCHK(hipGetLastError());
+            std::vector<uint64_t> ext((size_t)cnt * 2), off((size_t)cnt);
+            HIPCHK(hipMemcpyAsync(ext.data(), d_begin, (size_t)cnt * 16, hipMemcpyDeviceToHost, f->stream));
+            HIPCHK(hipStreamSynchronize(f->stream));
+            uint64_t sum = 0;
+            for (uint64_t k = 0; k < cnt; k++) { off[k] = sum; sum += ext[cnt + k] - ext[k]; }
+            PFCHK(f->d_lines.ensure(sum + 16));
+            HIPCHK(hipMemcpyAsync(d_off, off.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, f->stream));
+            hipLaunchKernelGGL(rf_gather_kernel, dim3((uint32_t)cnt), dim3(64), 0, f->stream, f->d_text.as<const unsigned char>(), d_begin,
+                               d_end, d_off, f->d_lines.as<unsigned char>());
+            HIPCHK(hipGetLastError());
+            f->raw_lines.resize((size_t)sum);
+            if (sum) HIPCHK(hipMemcpyAsync(&f->raw_lines[0], f->d_lines.p, (size_t)sum, hipMemcpyDeviceToHost, f->stream));
+            HIPCHK(hipStreamSynchronize(f->stream));
+            // exact check of every candidate (a 64-bit hash collision must not add a row)
+            uint64_t kept = 0;
+            std::string key;
+            for (uint64_t k = 0; k < cnt; k++) {
+                if (ext[k] < skip) continue;
+                const char* b = f->raw_lines.data() + off[k];
+                const char* e = b + (ext[cnt + k] - ext[k]);            // behind the newline
+                const char* t = e > b && e[-1] == '\n' ? e - 1 : e;     // the line without it
+                if (f->first_field) {
+                    const char* q = b;
+                    while (q < t && *q != '\t') q++;
+                    key.assign(b, (size_t)(q - b));
+                } else {
+                    const char* q = t;
+                    while (q > b && q[-1] != '\t') q--;
+                    key.assign(q, (size_t)(t - q));
+                }
+#ifdef PF_WEAK_HASH
+                if (!f->keys.count(key)) rf_wh_rowfilter_rejects++;
+#endif
+                if (!f->keys.count(key)) continue;
+                f->lines.append(b, (size_t)(e - b));
+                kept++;
+            }
+            *n_lines = kept;
+        }
+    }
+    // the unfinished line stays on the device for the next call
+    f->carry_n = total - n;
+    if (f->carry_n) {
+        PFCHK(f->d_carry.ensure(f->carry_n));
+        HIPCHK(hipMemcpyAsync(f->d_carry.p, f->d_text.as<char>() + n, f->carry_n, hipMemcpyDeviceToDevice, f->stream));
+        HIPCHK(hipStreamSynchronize(f->stream));
+    }
+    *lines = f->lines.data(); *lines_bytes = f->lines.size(); *consumed = used; *taken = 1;
+    return PF_OK;
+}
+
+int pf_rowfilter_gunzip_stats(pf_rowfilter* f, uint64_t* members, uint64_t* text_bytes, float* inflate_ms, uint64_t* device_bytes) {
+    if (!f) return fail(PF_ERR_ARG, "pf_rowfilter_gunzip_stats: null argument");
+    if (members) *members = f->gz_members;
+    if (text_bytes) *text_bytes = f->gz_text_bytes;
+    if (inflate_ms) *inflate_ms = f->gz_ms;
+    if (device_bytes) *device_bytes = f->dec.device_bytes();
     return PF_OK;
 }
 

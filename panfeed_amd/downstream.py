@@ -28,10 +28,21 @@ from . import _lib
 logger = logging.getLogger("panfeed")
 
 BLOCK_BYTES = 256 << 20
+# the device gunzip route reads COMPRESSED bytes: an eighth of the text block, which these texts' ratio of 6 to 8 makes
+# about one block of text a call (a call takes 256 MiB of text at most and hands the rest back)
+GZ_BLOCK_DIVISOR = 8
+GZ_HEAD = b"\x1f\x8b\x08\x00"          # ID1 ID2 CM=8 FLG=0: the only header the device decoder takes
+
+
+class NotTaken(RuntimeError):
+    """device_gunzip=True and the file is not one the device decoder takes"""
 
 
 class RowFilter:
     """rows of a TSV whose first (`first_field=True`) or last field is one of `keys`, filtered on the device"""
+
+    device_gunzip_files = 0         # files, over all filters, that went the device gunzip route to their end
+    fallback_files = 0              # and files the automatic mode began there and read again through gzip
 
     def __init__(self, keys, first_field, device=0):
         self.L = _lib.load()
@@ -39,6 +50,7 @@ class RowFilter:
         arr = (C.c_char_p * max(len(ks), 1))(*ks)
         lens = (C.c_uint32 * max(len(ks), 1))(*[len(k) for k in ks])
         self.h = C.c_void_p()
+        self.fallbacks = 0              # files the automatic mode began on the device and read again through gzip
         _lib.check(self.L.pf_rowfilter_create(int(device), 1 if first_field else 0, arr, lens, len(ks), C.byref(self.h)))
 
     def close(self):
@@ -51,7 +63,11 @@ class RowFilter:
     def stats(self):
         n, ms = C.c_uint64(), C.c_float()
         _lib.check(self.L.pf_rowfilter_stats(self.h, C.byref(n), C.byref(ms)))
-        return {"bytes_scanned": int(n.value), "device_ms": float(ms.value)}
+        gm, gt, gms, gdev = C.c_uint64(), C.c_uint64(), C.c_float(), C.c_uint64()
+        _lib.check(self.L.pf_rowfilter_gunzip_stats(self.h, C.byref(gm), C.byref(gt), C.byref(gms), C.byref(gdev)))
+        return {"bytes_scanned": int(n.value), "device_ms": float(ms.value),
+                "members_inflated": int(gm.value), "text_bytes_inflated": int(gt.value), "inflate_ms": float(gms.value),
+                "inflate_device_bytes": int(gdev.value), "gunzip_fallbacks": self.fallbacks}
 
     def scan_block(self, data, n=None):
         """(matching lines of the complete lines of `data` (bytes, or the first n bytes of a bytearray), joined; number of
@@ -69,10 +85,65 @@ class RowFilter:
         del ptr, view
         return got, int(used.value)
 
-    def filter_file(self, path, block_bytes=None):
-        """(header line, matching data lines) of a TSV file (.gz read through gzip, as pandas does by the name).  The file
-        is read block by block straight into one buffer; what follows a block's last complete line is moved to the front
-        for the next block."""
+    def scan_members(self, data, last):
+        """(matching lines of the text of the whole gzip members in `data` (bytes of the compressed file from a member
+        start on), joined; compressed bytes consumed; whether the device decoder took them)"""
+        lines, nb, cnt, used, taken = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
+        _lib.check(self.L.pf_rowfilter_scan_members(self.h, data, len(data), 1 if last else 0, C.byref(lines), C.byref(nb),
+                                                    C.byref(cnt), C.byref(used), C.byref(taken)))
+        got = C.string_at(lines, nb.value) if nb.value else b""
+        return got, int(used.value), bool(taken.value)
+
+    def _filter_members(self, path, block_bytes):
+        """filter_file's device gunzip route: (header, rows), or None with the library's reason logged when a block was
+        not taken.  Blocks of the compressed file go up as they are; what follows a block's last whole member is put in
+        front of the next block."""
+        block = max(1, block_bytes or BLOCK_BYTES // GZ_BLOCK_DIVISOR)
+        out = []
+        _lib.check(self.L.pf_rowfilter_members_begin(self.h, 1))
+        with open(path, "rb") as fh:
+            carry, eof = b"", False
+            while True:
+                if not eof:
+                    chunk = fh.read(block)
+                    eof = len(chunk) < block
+                    carry = carry + chunk if carry else chunk
+                got, used, taken = self.scan_members(carry, eof)
+                if not taken:
+                    logger.debug("%s: %s", path, self.L.pf_last_error().decode(errors="replace"))
+                    return None
+                out.append(got)
+                carry = carry[used:]
+                if eof and not carry:
+                    break
+        line, n = C.c_void_p(), C.c_uint64()
+        _lib.check(self.L.pf_rowfilter_members_header(self.h, C.byref(line), C.byref(n)))
+        return (C.string_at(line, n.value) if n.value else b""), b"".join(out)
+
+    def filter_file(self, path, block_bytes=None, device_gunzip=None):
+        """(header line, matching data lines) of a TSV file.  A .gz file made of small members with the plain gzip header
+        (--gpu-compress writes such) is inflated on the device and scanned there: device_gunzip=None tries that for a
+        name ending in .gz whose first bytes are such a header, and reads the whole file again through gzip, as pandas
+        does by the name, when a block is not taken; False never tries; True raises NotTaken instead of reading again.
+        block_bytes then counts compressed bytes.  Otherwise the file is read block by block straight into one buffer;
+        what follows a block's last complete line is moved to the front for the next block."""
+        if device_gunzip is None:
+            device_gunzip = False
+            if str(path).endswith(".gz"):
+                with open(path, "rb") as fh:
+                    device_gunzip = fh.read(10)[:4] == GZ_HEAD
+            auto = True
+        else:
+            auto = False
+        if device_gunzip:
+            got = self._filter_members(path, block_bytes)
+            if got is not None:
+                RowFilter.device_gunzip_files += 1
+                return got
+            if not auto:
+                raise NotTaken(f"{path}: {self.L.pf_last_error().decode(errors='replace')}")
+            self.fallbacks += 1
+            RowFilter.fallback_files += 1
         out = []
 
         def scan(buf, n):
@@ -131,6 +202,8 @@ def _options(description, kmers):
         p.add_argument("--clusters-per-iteration", type=int, default=15)
     p.add_argument("-v", action="count", default=0)
     p.add_argument("--device", type=int, default=0, help="GPU the row filter runs on")
+    p.add_argument("--host-gunzip", action="store_true", default=False,
+                   help="inflate .gz inputs on the host (by default files of small members, as --gpu-compress writes, are inflated on the GPU)")
     return p
 
 
@@ -171,7 +244,7 @@ def get_clusters(argv=None, out=None):
     a, passing = _associations(args)
     f = RowFilter(passing, first_field=False, device=args.device)
     try:
-        header, rows = f.filter_file(args.kmers_to_hashes)
+        header, rows = f.filter_file(args.kmers_to_hashes, device_gunzip=False if args.host_gunzip else None)
     finally:
         f.close()
     h = _table(header, rows)
@@ -187,7 +260,7 @@ def get_kmers(argv=None, out=None):
     a, passing = _associations(args, index_name="hashed_pattern")
     f = RowFilter(passing, first_field=False, device=args.device)
     try:
-        header, rows = f.filter_file(args.kmers_to_hashes)
+        header, rows = f.filter_file(args.kmers_to_hashes, device_gunzip=False if args.host_gunzip else None)
     finally:
         f.close()
     h = _table(header, rows).set_index("hashed_pattern")
@@ -208,7 +281,7 @@ def get_kmers(argv=None, out=None):
         # for a NaN cell when the bunch is a list of the column's unique() values -- such rows are dropped, not matched)
         fk = RowFilter([lit for c in bunch if c is not _NAN_KEY for lit in literal[_key(c)]], first_field=True, device=args.device)
         try:
-            kheader, krows = fk.filter_file(args.kmers)
+            kheader, krows = fk.filter_file(args.kmers, device_gunzip=False if args.host_gunzip else None)
         finally:
             fk.close()
         k = _table(kheader, krows).set_index(["cluster", "k-mer"])
