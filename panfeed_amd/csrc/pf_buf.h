@@ -1,5 +1,5 @@
-// pf_buf.h -- internal: the error helpers and the owners of device and pinned host memory that the library's two
-// translation units with device code (pf_api.hip, pf_rowfilter.hip) share.  Not part of the C ABI (include/panfeed_hip.h).
+// pf_buf.h -- internal: the error helpers and the owners of device and pinned host memory that the library's three
+// translation units with device code (pf_api.hip, pf_rowfilter.hip, pf_deflate.hip) share.  Not part of the C ABI (include/panfeed_hip.h).
 // A buffer frees itself when its owner goes; what is freed early on purpose says so where it happens.
 #pragma once
 #include <hip/hip_runtime.h>

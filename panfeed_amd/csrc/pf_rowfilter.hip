@@ -23,6 +23,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <string_view>
 #include <unordered_set>
 #include <thread>
 #include <vector>
@@ -114,23 +115,27 @@ __device__ __forceinline__ uint32_t rf_newlines(uint32_t w) {
     return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
 }
 
+// line_end(at) for every '\n' of the 16 bytes at text + 16 * v, in their order.  The caller sees to v < ceil(n / 16) and to a
+// buffer that reaches to the next multiple of 16 bytes, padded with zeros, and tests `at` against its own bound
+template <class F> __device__ __forceinline__ void rf_each_newline(const unsigned char* text, uint64_t v, F&& line_end) {
+    const uint4 w = reinterpret_cast<const uint4*>(text)[v];
+    const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        uint32_t m = rf_newlines(ws[q]);
+        while (m) {
+            const int b = (__ffs((int)m) - 1) >> 3;
+            m &= m - 1;
+            line_end(v * 16 + q * 4 + b);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void rowfilter_kernel(RfParams p) {
     const uint64_t nvec = (p.n + 15) / 16;
     for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < nvec; v += (uint64_t)gridDim.x * blockDim.x) {
-        // the block's buffer is padded to a multiple of 16 bytes with zeros
-        const uint4 w = reinterpret_cast<const uint4*>(p.text)[v];
-        const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
         if (v == 0 && p.first_field) rf_line(p, -1);     // the line that starts the block
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            uint32_t m = rf_newlines(ws[q]);
-            while (m) {
-                const int b = (__ffs((int)m) - 1) >> 3;
-                m &= m - 1;
-                const uint64_t at = v * 16 + q * 4 + b;
-                if (at < p.n) rf_line(p, (int64_t)at);
-            }
-        }
+        rf_each_newline(p.text, v, [&](uint64_t at) { if (at < p.n) rf_line(p, (int64_t)at); });
     }
 }
 
@@ -161,16 +166,21 @@ __global__ __launch_bounds__(256) void rf_tail_kernel(unsigned char* text, uint6
     if (tid == 0) { out[0] = s_best; out[1] = total; }
 }
 
-// candidate k's line, [b, e) with its newline, as pf_rowfilter_scan finds it on the host
-__global__ __launch_bounds__(256) void rf_extent_kernel(const unsigned char* text, uint64_t n, const uint64_t* pos, uint64_t cnt,
-                                                         int first_field, uint64_t* begin, uint64_t* end) {
-    const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (k >= cnt) return;
-    const uint64_t q = pos[k] < n ? pos[k] : n - 1;
+// the line of text[0 .. n) at a candidate's position -- its start (first_field) or its '\n' --: [*begin, *end), the
+// newline part of it.  For the host's exact check of the plain route and, on the device, for the member route's gather
+__host__ __device__ inline void rf_line_extent(const unsigned char* text, uint64_t n, uint64_t pos, int first_field,
+                                               uint64_t* begin, uint64_t* end) {
+    const uint64_t q = pos < n ? pos : n - 1;
     uint64_t b = q, e = q;
     if (first_field) { while (e < n && text[e] != '\n') e++; }
     else { while (b > 0 && text[b - 1] != '\n') b--; }
-    begin[k] = b; end[k] = e + 1 <= n ? e + 1 : n;
+    *begin = b; *end = e + 1 <= n ? e + 1 : n;
+}
+
+__global__ __launch_bounds__(256) void rf_extent_kernel(const unsigned char* text, uint64_t n, const uint64_t* pos, uint64_t cnt,
+                                                         int first_field, uint64_t* begin, uint64_t* end) {
+    const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (k < cnt) rf_line_extent(text, n, pos[k], first_field, &begin[k], &end[k]);
 }
 
 // line k to lines + off[k]; a workgroup of 64 per line
@@ -180,23 +190,74 @@ __global__ __launch_bounds__(64) void rf_gather_kernel(const unsigned char* text
     for (uint64_t i = threadIdx.x; i < m; i += 64) lines[off[k] + i] = text[b + i];
 }
 
+// ---- what the row filter and the plot grid (below) own alike.  A block's text -- complete lines only, the caller carries
+// the rest over -- on the device and the pinned buffer host text goes through.  The scans read 16 bytes at a time: d_text
+// reaches to the next multiple of 16 bytes and 16 more; a buffer that is re-made gets an eighth more
+struct BlockText {
+    DevBuf d_text;
+    PinBuf pin;
+    static uint64_t complete_lines(const char* text, uint64_t n) { while (n && text[n - 1] != '\n') n--; return n; }
+    static size_t padded(uint64_t bytes) { return (bytes + 15) / 16 * 16 + 16; }
+    int reserve(uint64_t bytes, bool pinned_too = false) {
+        const size_t want = padded(bytes);
+        auto grow = [want](auto& buf) -> int { return want > buf.cap ? buf.ensure(want + want / 8, true) : PF_OK; };
+        if (int rc = grow(d_text)) return rc;
+        return pinned_too ? grow(pin) : PF_OK;
+    }
+    int upload(hipStream_t stream, const char* text, uint64_t n) {
+        PFCHK(reserve(n, true));
+        // into pinned memory on a few threads (one memcpy of 256 MB is slower than the rest of the call)
+        char* const to = pin.as<char>();
+        const unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(8, n >> 22));
+        std::vector<std::thread> th;
+        const uint64_t step = (n + nt - 1) / nt;
+        for (unsigned t = 1; t < nt; t++) {
+            const uint64_t a = t * step, b = std::min<uint64_t>(n, a + step);
+            if (a < b) th.emplace_back([=] { memcpy(to + a, text + a, (size_t)(b - a)); });
+        }
+        memcpy(to, text, (size_t)std::min<uint64_t>(n, step));
+        for (auto& t : th) t.join();
+        memset(to + n, 0, padded(n) - n);
+        HIPCHK(hipMemcpyAsync(d_text.p, pin.p, padded(n), hipMemcpyHostToDevice, stream));
+        return PF_OK;
+    }
+};
+
+// A stream and the two events that bracket what is timed on it.  Its owner declares it last, so that it goes first: the
+// stream is synchronised and destroyed before the buffers its work may still use are freed.
+struct TimedStream {
+    hipStream_t stream = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    TimedStream() = default; TimedStream(const TimedStream&) = delete;
+    ~TimedStream() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    int create() { HIPCHK(hipStreamCreate(&stream)); HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); return PF_OK; }
+    template <class F> int timed(F&& work) {          // e0 and e1 recorded around what `work` puts on the stream
+        HIPCHK(hipEventRecord(e0, stream)); PFCHK(work()); HIPCHK(hipEventRecord(e1, stream));
+        return PF_OK;
+    }
+    // once the caller has synchronised with the stream: the time between the two events, added to *ms
+    void add_elapsed(float* ms) const { float t = 0; if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) *ms += t; }
+};
+
 }  // namespace
 
 struct pf_rowfilter {
     int device = 0;
     int first_field = 0;
-    hipStream_t stream = nullptr;
     std::unordered_set<std::string> keys;
+    std::string key;                           // a candidate's key field, for the look-up in keys
     DevBuf d_set;                              // the keys' hashes (uint64), cap slots
     uint64_t cap = 0;
-    DevBuf d_text;                             // the block, padded
-    PinBuf pin;                                // its pinned host copy
+    BlockText text;                            // the block
     DevBuf d_out;                              // candidate positions (uint64)
     DevBuf d_count;
     std::vector<uint64_t> begin, end;          // result of the last scan
     uint64_t bytes_scanned = 0;
     float device_ms = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     // pf_rowfilter_scan_members: the decoder, the unfinished line carried from one call to the next (device), the
     // candidates' lines (extents and offsets on the device, the gathered bytes on both sides), the kept lines
     PfGzDecoder dec;
@@ -206,6 +267,7 @@ struct pf_rowfilter {
     std::string header, raw_lines, lines;
     uint64_t gz_members = 0, gz_text_bytes = 0;
     float gz_ms = 0;
+    TimedStream ts;
 };
 
 namespace {
@@ -220,21 +282,20 @@ int rf_scan_device(pf_rowfilter* f, uint64_t n, std::vector<uint64_t>& pos) {
     PFCHK(f->d_out.ensure(guess * 8, true));
     unsigned long long cnt = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
-        HIPCHK(hipMemsetAsync(f->d_count.p, 0, 8, f->stream));
+        HIPCHK(hipMemsetAsync(f->d_count.p, 0, 8, f->ts.stream));
         RfParams p{};
-        p.text = f->d_text.as<unsigned char>(); p.n = n; p.set = f->d_set.as<uint64_t>(); p.cap = f->cap;
+        p.text = f->text.d_text.as<unsigned char>(); p.n = n; p.set = f->d_set.as<uint64_t>(); p.cap = f->cap;
         p.first_field = f->first_field;
         p.out = f->d_out.as<uint64_t>(); p.count = f->d_count.as<unsigned long long>(); p.out_cap = f->d_out.cap / 8;
         const uint64_t nvec = (n + 15) / 16;
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((nvec + 255) / 256, 256 * 16);
-        HIPCHK(hipEventRecord(f->e0, f->stream));
-        hipLaunchKernelGGL(rowfilter_kernel, dim3(blocks), dim3(256), 0, f->stream, p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(f->e1, f->stream));
-        HIPCHK(hipMemcpyAsync(&cnt, f->d_count.p, 8, hipMemcpyDeviceToHost, f->stream));
-        HIPCHK(hipStreamSynchronize(f->stream));
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, f->e0, f->e1) == hipSuccess) f->device_ms += ms;
+        PFCHK(f->ts.timed([&]() -> int {
+            hipLaunchKernelGGL(rowfilter_kernel, dim3(blocks), dim3(256), 0, f->ts.stream, p);
+            HIPCHK(hipGetLastError()); return PF_OK;
+        }));
+        HIPCHK(hipMemcpyAsync(&cnt, f->d_count.p, 8, hipMemcpyDeviceToHost, f->ts.stream));
+        HIPCHK(hipStreamSynchronize(f->ts.stream));
+        f->ts.add_elapsed(&f->device_ms);
         if (cnt <= f->d_out.cap / 8) break;
         // more candidates than room (the kernel counted them all and kept what fitted): again, with room for all
         PFCHK(f->d_out.ensure(((size_t)cnt + (size_t)cnt / 8) * 8, true));
@@ -247,19 +308,157 @@ int rf_scan_device(pf_rowfilter* f, uint64_t n, std::vector<uint64_t>& pos) {
     return PF_OK;
 }
 
+// ---- the host's exact check (a 64-bit hash collision must not add a row): the key field of the line [b, t), t at its newline
+std::string_view rf_key_field(const char* b, const char* t, int first_field) {
+    const char* q = first_field ? b : t;
+    if (first_field) while (q < t && *q != '\t') q++;
+    else while (q > b && q[-1] != '\t') q--;
+    return first_field ? std::string_view(b, (size_t)(q - b)) : std::string_view(q, (size_t)(t - q));
+}
+
+// and whether the line [b, e), with its newline, is a row: that field is one of the keys
+bool rf_keep(pf_rowfilter* f, const char* b, const char* e) {
+    const std::string_view key = rf_key_field(b, e > b && e[-1] == '\n' ? e - 1 : e, f->first_field);
+    f->key.assign(key.data(), key.size());
+    const bool keep = f->keys.count(f->key) != 0;
+#ifdef PF_WEAK_HASH
+    if (!keep) rf_wh_rowfilter_rejects++;
+#endif
+    return keep;
+}
+
+// ---- pf_rowfilter_scan_members, stage by stage.  *refused, with PF_OK: the block is not one for this route, "not taken"
+struct RfMembers {
+    const uint8_t* bytes; uint64_t nbytes; bool last;     // the call's arguments
+    std::vector<pfgz::MemberRef> ms;                     // plan: the members listed; how many of them this call takes,
+    size_t take = 0; uint64_t text_n = 0, used = 0;      // their text's bytes, the compressed bytes they use up; whether the
+    bool end = false, none_yet = false;                  // file's text ends with them; no whole member yet: the caller reads on
+    uint64_t total = 0, n = 0;     // inflate: d_text[0 .. total) is the carried line and the members' text, [0 .. n) its complete lines
+    uint64_t skip = 0;             // header: the header line's bytes: no candidate of it is a row
+    std::vector<uint64_t> ext, off;     // candidates: their lines' begins, then ends, in d_text; their offsets in raw_lines
+};
+
+// (whatever refuses the block leaves no line carried: the caller starts over another way)
+int rf_refuse(pf_rowfilter* f, uint64_t member, uint32_t status, bool* refused) {
+    f->carry_n = 0; *refused = true;
+    return fail(PF_OK, "pf_rowfilter_scan_members: not taken: member %llu of the block: %s", (unsigned long long)member,
+                pfgz::inf_status_name(status));
+}
+
+int rf_members_plan(pf_rowfilter* f, RfMembers& c, bool* refused) {
+    uint64_t listed = 0;
+    if (!pfgz::list_members(c.bytes, c.nbytes, c.last, c.ms, &listed)) return rf_refuse(f, 0, pfgz::INF_BAD_HEAD, refused);
+    const bool none = c.ms.empty() && !c.last;
+    // a member this decoder takes would have ended by now
+    if (none && c.nbytes >= pfgz::SLOT_BYTES + pfgz::MEMBER_HEAD) return rf_refuse(f, 0, pfgz::INF_TOO_LARGE, refused);
+    if (none) { c.none_yet = true; return PF_OK; }
+    // at most the decoder's call: the rest is the caller's to give again
+    while (c.take < c.ms.size() && c.take < PfGzDecoder::MAX_MEMBERS) {
+        if (c.ms[c.take].status != pfgz::INF_OK) return rf_refuse(f, c.take, c.ms[c.take].status, refused);
+        if (c.take && c.text_n + c.ms[c.take].isize > PfGzDecoder::MAX_TEXT) break;
+        c.text_n += c.ms[c.take].isize; c.take++;
+    }
+    const bool all = c.take == c.ms.size();
+    c.used = all ? listed : c.ms[c.take].at;
+    c.end = c.last && all;
+    return PF_OK;
+}
+
+// the device text: the line carried over, then the members' text; room for a final newline.  Where its complete lines end
+int rf_members_inflate(pf_rowfilter* f, RfMembers& c, bool* refused) {
+    hipStream_t st = f->ts.stream;
+    c.total = f->carry_n + c.text_n;
+    PFCHK(f->text.reserve(c.total + 1));
+    PFCHK(f->d_tail.ensure(16, true));
+    unsigned char* const text = f->text.d_text.as<unsigned char>();
+    if (f->carry_n) HIPCHK(hipMemcpyAsync(text, f->d_carry.p, f->carry_n, hipMemcpyDeviceToDevice, st));
+    PFCHK(f->dec.decode(st, c.bytes, c.ms.data(), (uint32_t)c.take, text + f->carry_n, c.text_n, f->ts.e0, f->ts.e1));
+    hipLaunchKernelGGL(rf_tail_kernel, dim3(1), dim3(256), 0, st, text, c.total, c.end ? 1 : 0, f->d_tail.as<uint64_t>());
+    HIPCHK(hipGetLastError());
+    uint64_t tail[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(tail, f->d_tail.p, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (c.take) {
+        f->ts.add_elapsed(&f->gz_ms);
+        uint32_t status = 0;
+        const int64_t bad = f->dec.first_refused(&status);
+        if (bad >= 0) return rf_refuse(f, (uint64_t)bad, status, refused);
+    }
+    c.n = tail[0]; c.total = tail[1];
+    return PF_OK;
+}
+
+// the first call's first line is the header line
+int rf_members_header(pf_rowfilter* f, RfMembers& c, bool* refused) {
+    if (!f->want_header) return PF_OK;
+    std::string front((size_t)std::min<uint64_t>(c.n, 1 << 16), '\0');
+    if (!front.empty()) HIPCHK(hipMemcpy(&front[0], f->text.d_text.p, front.size(), hipMemcpyDeviceToHost));
+    const size_t nl = front.find('\n');
+    // (no line end: a header line over 64 KiB or over a call's text -- unless the file is empty)
+    if (nl == std::string::npos && !(c.end && c.total == 0)) return rf_refuse(f, 0, pfgz::INF_NOT_DECODED, refused);
+    if (nl != std::string::npos) { f->header.assign(front, 0, nl + 1); c.skip = nl + 1; }
+    f->want_header = false;
+    return PF_OK;
+}
+
+// the candidates' lines: extents on the device, offsets by the host, one gather, one copy down into raw_lines
+int rf_members_candidates(pf_rowfilter* f, RfMembers& c) {
+    if (!c.n || f->keys.empty()) return PF_OK;
+    hipStream_t st = f->ts.stream;
+    std::vector<uint64_t> pos;
+    PFCHK(rf_scan_device(f, c.n, pos));
+    const uint64_t cnt = pos.size();
+    if (!cnt) return PF_OK;
+    const unsigned char* const text = f->text.d_text.as<const unsigned char>();
+    PFCHK(f->d_ext.ensure((size_t)cnt * 24, true));
+    uint64_t* const d_begin = f->d_ext.as<uint64_t>(), *const d_end = d_begin + cnt, *const d_off = d_end + cnt;
+    HIPCHK(hipMemcpyAsync(f->d_out.p, pos.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(rf_extent_kernel, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st, text, c.n,
+                       f->d_out.as<const uint64_t>(), cnt, f->first_field, d_begin, d_end);
+    HIPCHK(hipGetLastError());
+    c.ext.resize((size_t)cnt * 2); c.off.resize((size_t)cnt);
+    HIPCHK(hipMemcpyAsync(c.ext.data(), d_begin, (size_t)cnt * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    uint64_t sum = 0;
+    for (uint64_t k = 0; k < cnt; k++) { c.off[k] = sum; sum += c.ext[cnt + k] - c.ext[k]; }
+    PFCHK(f->d_lines.ensure(sum + 16));
+    HIPCHK(hipMemcpyAsync(d_off, c.off.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(rf_gather_kernel, dim3((uint32_t)cnt), dim3(64), 0, st, text, d_begin, d_end, d_off,
+                       f->d_lines.as<unsigned char>());
+    HIPCHK(hipGetLastError());
+    f->raw_lines.resize((size_t)sum);
+    if (sum) HIPCHK(hipMemcpyAsync(&f->raw_lines[0], f->d_lines.p, (size_t)sum, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return PF_OK;
+}
+
+// the candidates that are rows, appended to lines; how many
+uint64_t rf_members_keep(pf_rowfilter* f, const RfMembers& c) {
+    const uint64_t cnt = c.off.size(); uint64_t kept = 0;
+    for (uint64_t k = 0; k < cnt; k++) {
+        if (c.ext[k] < c.skip) continue;
+        const char* b = f->raw_lines.data() + c.off[k];
+        const char* e = b + (c.ext[cnt + k] - c.ext[k]);
+        if (rf_keep(f, b, e)) { f->lines.append(b, (size_t)(e - b)); kept++; }
+    }
+    return kept;
+}
+
+// the unfinished line stays on the device for the next call
+int rf_members_save_carry(pf_rowfilter* f, const RfMembers& c) {
+    f->carry_n = c.total - c.n;
+    if (!f->carry_n) return PF_OK;
+    PFCHK(f->d_carry.ensure(f->carry_n));
+    HIPCHK(hipMemcpyAsync(f->d_carry.p, f->text.d_text.as<char>() + c.n, f->carry_n, hipMemcpyDeviceToDevice, f->ts.stream));
+    HIPCHK(hipStreamSynchronize(f->ts.stream));
+    return PF_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
-void pf_rowfilter_destroy(pf_rowfilter* f) {
-    if (!f) return;
-    (void)hipSetDevice(f->device);
-    if (f->stream) (void)hipStreamSynchronize(f->stream);
-    if (f->e0) (void)hipEventDestroy(f->e0);
-    if (f->e1) (void)hipEventDestroy(f->e1);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
-    delete f;
-}
+void pf_rowfilter_destroy(pf_rowfilter* f) { if (f) { (void)hipSetDevice(f->device); delete f; } }
 
 int pf_rowfilter_create(int device, int first_field, const char* const* keys, const uint32_t* key_len, uint64_t n_keys,
                         pf_rowfilter** out) {
@@ -269,7 +468,7 @@ int pf_rowfilter_create(int device, int first_field, const char* const* keys, co
     HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_rowfilter_create: no such device");
     HIPCHK(hipSetDevice(device));
-    pf_rowfilter* f = new pf_rowfilter();
+    std::unique_ptr<pf_rowfilter, void (*)(pf_rowfilter*)> f(new pf_rowfilter(), pf_rowfilter_destroy);
     f->device = device;
     f->first_field = first_field ? 1 : 0;
     std::vector<uint64_t> table;
@@ -286,18 +485,11 @@ int pf_rowfilter_create(int device, int first_field, const char* const* keys, co
         table[slot] = h;
     }
     f->cap = cap;
-    int rc = PF_OK;
-    do {
-        if (hipStreamCreate(&f->stream) != hipSuccess || hipEventCreate(&f->e0) != hipSuccess || hipEventCreate(&f->e1) != hipSuccess ||
-            f->d_set.ensure(cap * 8, true) != PF_OK || f->d_count.ensure(8, true) != PF_OK) {
-            rc = fail(PF_ERR_HIP, "pf_rowfilter_create: device allocation failed");
-            break;
-        }
-        if (hipMemcpy(f->d_set.p, table.data(), cap * 8, hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(PF_ERR_HIP, "pf_rowfilter_create: upload failed");
-    } while (0);
-    if (rc != PF_OK) { pf_rowfilter_destroy(f); return rc; }
-    *out = f;
+    if (f->ts.create() != PF_OK || f->d_set.ensure(cap * 8, true) != PF_OK || f->d_count.ensure(8, true) != PF_OK)
+        return fail(PF_ERR_HIP, "pf_rowfilter_create: device allocation failed");
+    if (hipMemcpy(f->d_set.p, table.data(), cap * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(PF_ERR_HIP, "pf_rowfilter_create: upload failed");
+    *out = f.release();
     return PF_OK;
 }
 
@@ -307,56 +499,16 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
         return fail(PF_ERR_ARG, "pf_rowfilter_scan: null argument");
     HIPCHK(hipSetDevice(f->device));
     f->begin.clear(); f->end.clear();
-    *line_begin = nullptr; *line_end = nullptr; *n_lines = 0; *consumed = 0;
-    // complete lines only: the caller carries the rest over to its next block
-    uint64_t n = nbytes;
-    while (n && text[n - 1] != '\n') n--;
-    *consumed = n;
+    *line_begin = nullptr; *line_end = nullptr; *n_lines = 0;
+    const uint64_t n = *consumed = BlockText::complete_lines(text, nbytes);
     if (!n || f->keys.empty()) return PF_OK;
-    const size_t padded = (n + 15) / 16 * 16 + 16;
-    if (padded > f->d_text.cap) PFCHK(f->d_text.ensure(padded + padded / 8, true));
-    if (padded > f->pin.cap) PFCHK(f->pin.ensure(padded + padded / 8, true));
-    {   // the block into pinned memory on a few threads (one memcpy of 256 MB is slower than the rest of the call)
-        char* const pin = f->pin.as<char>();
-        const unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(8, n >> 22));
-        std::vector<std::thread> th;
-        const uint64_t step = (n + nt - 1) / nt;
-        for (unsigned t = 1; t < nt; t++) {
-            const uint64_t a = t * step, b = std::min<uint64_t>(n, a + step);
-            if (a < b) th.emplace_back([=] { memcpy(pin + a, text + a, (size_t)(b - a)); });
-        }
-        memcpy(pin, text, (size_t)std::min<uint64_t>(n, step));
-        for (auto& t : th) t.join();
-        memset(pin + n, 0, padded - n);
-    }
-    HIPCHK(hipMemcpyAsync(f->d_text.p, f->pin.p, padded, hipMemcpyHostToDevice, f->stream));
+    PFCHK(f->text.upload(f->ts.stream, text, n));
     std::vector<uint64_t> pos;
     PFCHK(rf_scan_device(f, n, pos));
-    // exact check of every candidate (a 64-bit hash collision must not add a row), then the line's extent
     for (uint64_t q : pos) {
         uint64_t b, e;
-        std::string key;
-        if (f->first_field) {
-            b = q;
-            const char* nl = (const char*)memchr(text + b, '\n', (size_t)(n - b));
-            e = nl ? (uint64_t)(nl - text) : n;
-            uint64_t t = b;
-            while (t < e && text[t] != '\t') t++;
-            key.assign(text + b, (size_t)(t - b));
-        } else {
-            e = q;
-            b = e;
-            while (b > 0 && text[b - 1] != '\n') b--;
-            uint64_t t = e;
-            while (t > b && text[t - 1] != '\t') t--;
-            key.assign(text + t, (size_t)(e - t));
-        }
-#ifdef PF_WEAK_HASH
-        if (!f->keys.count(key)) rf_wh_rowfilter_rejects++;
-#endif
-        if (!f->keys.count(key)) continue;
-        f->begin.push_back(b);
-        f->end.push_back(e + 1 <= n ? e + 1 : n);          // the '\n' is part of the line
+        rf_line_extent(reinterpret_cast<const unsigned char*>(text), n, q, f->first_field, &b, &e);
+        if (rf_keep(f, text + b, text + e)) { f->begin.push_back(b); f->end.push_back(e); }
     }
     *line_begin = f->begin.data(); *line_end = f->end.data(); *n_lines = f->begin.size();
     return PF_OK;
@@ -381,127 +533,18 @@ int pf_rowfilter_scan_members(pf_rowfilter* f, const char* members, uint64_t nby
     HIPCHK(hipSetDevice(f->device));
     f->lines.clear();
     *lines = f->lines.data(); *lines_bytes = 0; *n_lines = 0; *consumed = 0; *taken = 0;
-    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(members);
-    // (whatever refuses the block leaves no line carried: the caller starts over another way)
-    auto refuse = [&](uint64_t member, uint32_t status) {
-        f->carry_n = 0;
-        (void)fail(PF_OK, "pf_rowfilter_scan_members: not taken: member %llu of the block: %s", (unsigned long long)member,
-                   pfgz::inf_status_name(status));
-        return PF_OK;
-    };
-    std::vector<pfgz::MemberRef> ms;
-    uint64_t listed = 0;
-    if (!pfgz::list_members(bytes, nbytes, last != 0, ms, &listed)) return refuse(0, pfgz::INF_BAD_HEAD);
-    // a member this decoder takes would have ended by now
-    if (ms.empty() && !last && nbytes >= pfgz::SLOT_BYTES + pfgz::MEMBER_HEAD) return refuse(0, pfgz::INF_TOO_LARGE);
-    if (ms.empty() && !last) { *taken = 1; return PF_OK; }            // no whole member yet: the caller reads on
-    // at most the decoder's call: the rest is the caller's to give again
-    uint64_t text_n = 0;
-    size_t take = 0;
-    while (take < ms.size() && take < PfGzDecoder::MAX_MEMBERS) {
-        if (ms[take].status != pfgz::INF_OK) return refuse(take, ms[take].status);
-        if (take && text_n + ms[take].isize > PfGzDecoder::MAX_TEXT) break;
-        text_n += ms[take].isize; take++;
-    }
-    const bool all = take == ms.size();
-    const uint64_t used = all ? listed : ms[take].at;
-    const bool end = last && all;
-    // the device text: the line carried over, then the members' text; room for a final newline and the scan's 16-byte reads
-    uint64_t total = f->carry_n + text_n;
-    const size_t padded = (total + 1 + 15) / 16 * 16 + 16;
-    if (padded > f->d_text.cap) PFCHK(f->d_text.ensure(padded + padded / 8, true));
-    PFCHK(f->d_tail.ensure(16, true));
-    if (f->carry_n) HIPCHK(hipMemcpyAsync(f->d_text.p, f->d_carry.p, f->carry_n, hipMemcpyDeviceToDevice, f->stream));
-    PFCHK(f->dec.decode(f->stream, bytes, ms.data(), (uint32_t)take, f->d_text.as<uint8_t>() + f->carry_n, text_n, f->e0, f->e1));
-    hipLaunchKernelGGL(rf_tail_kernel, dim3(1), dim3(256), 0, f->stream, f->d_text.as<unsigned char>(), total, end ? 1 : 0,
-                       f->d_tail.as<uint64_t>());
-    HIPCHK(hipGetLastError());
-    uint64_t tail[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(tail, f->d_tail.p, 16, hipMemcpyDeviceToHost, f->stream));
-    HIPCHK(hipStreamSynchronize(f->stream));
-    if (take) {
-        float ms_ = 0;
-        if (hipEventElapsedTime(&ms_, f->e0, f->e1) == hipSuccess) f->gz_ms += ms_;
-        uint32_t status = 0;
-        const int64_t bad = f->dec.first_refused(&status);
-        if (bad >= 0) return refuse((uint64_t)bad, status);
-    }
-    const uint64_t n = tail[0];
-    total = tail[1];
-    uint64_t skip = 0;                                  // the header line's bytes: no candidate of it is a row
-    if (f->want_header) {
-        std::string front((size_t)std::min<uint64_t>(n, 1 << 16), '\0');
-        if (!front.empty()) HIPCHK(hipMemcpy(&front[0], f->d_text.p, front.size(), hipMemcpyDeviceToHost));
-        const size_t nl = front.find('\n');
-        if (nl == std::string::npos) {
-            if (!(end && total == 0)) return refuse(0, pfgz::INF_NOT_DECODED);      // (a header line over 64 KiB or over a call's text)
-        } else {
-            f->header.assign(front, 0, nl + 1);
-            skip = nl + 1;
-        }
-        f->want_header = false;
-    }
-    f->gz_members += take; f->gz_text_bytes += text_n;
-    if (n && !f->keys.empty()) {
-        std::vector<uint64_t> pos;
-        PFCHK(rf_scan_device(f, n, pos));
-        const uint64_t cnt = pos.size();
-        if (cnt) {
-            // the candidates' lines: extents on the device, offsets by the host, one gather, one copy down
-            PFCHK(f->d_ext.ensure((size_t)cnt * 24, true));
-            uint64_t* const d_begin = f->d_ext.as<uint64_t>(), *const d_end = d_begin + cnt, *const d_off = d_end + cnt;
-            HIPCHK(hipMemcpyAsync(f->d_out.p, pos.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, f->stream));
-            hipLaunchKernelGGL(rf_extent_kernel, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, f->stream,
-                               f->d_text.as<const unsigned char>(), n, f->d_out.as<const uint64_t>(), cnt, f->first_field, d_begin, d_end);
-            HIPCHK(hipGetLastError());
-            std::vector<uint64_t> ext((size_t)cnt * 2), off((size_t)cnt);
-            HIPCHK(hipMemcpyAsync(ext.data(), d_begin, (size_t)cnt * 16, hipMemcpyDeviceToHost, f->stream));
-            HIPCHK(hipStreamSynchronize(f->stream));
-            uint64_t sum = 0;
-            for (uint64_t k = 0; k < cnt; k++) { off[k] = sum; sum += ext[cnt + k] - ext[k]; }
-            PFCHK(f->d_lines.ensure(sum + 16));
-            HIPCHK(hipMemcpyAsync(d_off, off.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, f->stream));
-            hipLaunchKernelGGL(rf_gather_kernel, dim3((uint32_t)cnt), dim3(64), 0, f->stream, f->d_text.as<const unsigned char>(), d_begin,
-                               d_end, d_off, f->d_lines.as<unsigned char>());
-            HIPCHK(hipGetLastError());
-            f->raw_lines.resize((size_t)sum);
-            if (sum) HIPCHK(hipMemcpyAsync(&f->raw_lines[0], f->d_lines.p, (size_t)sum, hipMemcpyDeviceToHost, f->stream));
-            HIPCHK(hipStreamSynchronize(f->stream));
-            // exact check of every candidate (a 64-bit hash collision must not add a row)
-            uint64_t kept = 0;
-            std::string key;
-            for (uint64_t k = 0; k < cnt; k++) {
-                if (ext[k] < skip) continue;
-                const char* b = f->raw_lines.data() + off[k];
-                const char* e = b + (ext[cnt + k] - ext[k]);            // behind the newline
-                const char* t = e > b && e[-1] == '\n' ? e - 1 : e;     // the line without it
-                if (f->first_field) {
-                    const char* q = b;
-                    while (q < t && *q != '\t') q++;
-                    key.assign(b, (size_t)(q - b));
-                } else {
-                    const char* q = t;
-                    while (q > b && q[-1] != '\t') q--;
-                    key.assign(q, (size_t)(t - q));
-                }
-#ifdef PF_WEAK_HASH
-                if (!f->keys.count(key)) rf_wh_rowfilter_rejects++;
-#endif
-                if (!f->keys.count(key)) continue;
-                f->lines.append(b, (size_t)(e - b));
-                kept++;
-            }
-            *n_lines = kept;
-        }
-    }
-    // the unfinished line stays on the device for the next call
-    f->carry_n = total - n;
-    if (f->carry_n) {
-        PFCHK(f->d_carry.ensure(f->carry_n));
-        HIPCHK(hipMemcpyAsync(f->d_carry.p, f->d_text.as<char>() + n, f->carry_n, hipMemcpyDeviceToDevice, f->stream));
-        HIPCHK(hipStreamSynchronize(f->stream));
-    }
-    *lines = f->lines.data(); *lines_bytes = f->lines.size(); *consumed = used; *taken = 1;
+    RfMembers c{reinterpret_cast<const uint8_t*>(members), nbytes, last != 0};
+    bool refused = false;
+    PFCHK(rf_members_plan(f, c, &refused));
+    if (refused || c.none_yet) { *taken = !refused; return PF_OK; }        // (none yet: taken, and the caller reads on)
+    PFCHK(rf_members_inflate(f, c, &refused));
+    if (!refused) PFCHK(rf_members_header(f, c, &refused));
+    if (refused) return PF_OK;
+    f->gz_members += c.take; f->gz_text_bytes += c.text_n;
+    PFCHK(rf_members_candidates(f, c));
+    *n_lines = rf_members_keep(f, c);
+    PFCHK(rf_members_save_carry(f, c));
+    *lines = f->lines.data(); *lines_bytes = f->lines.size(); *consumed = c.used; *taken = 1;
     return PF_OK;
 }
 
@@ -708,19 +751,8 @@ __device__ void pg_line(const PgScanParams& p, uint64_t s) {
 __global__ __launch_bounds__(256) void pg_scan_kernel(PgScanParams p) {
     const uint64_t nvec = (p.n + 15) / 16;
     for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < nvec; v += (uint64_t)gridDim.x * blockDim.x) {
-        const uint4 w = reinterpret_cast<const uint4*>(p.text)[v];
-        const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
         if (v == 0) pg_line(p, 0);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            uint32_t m = rf_newlines(ws[q]);
-            while (m) {
-                const int b = (__ffs((int)m) - 1) >> 3;
-                m &= m - 1;
-                const uint64_t at = v * 16 + q * 4 + b;
-                if (at + 1 < p.n) pg_line(p, at + 1);
-            }
-        }
+        rf_each_newline(p.text, v, [&](uint64_t at) { if (at + 1 < p.n) pg_line(p, at + 1); });
     }
 }
 
@@ -810,8 +842,6 @@ inline uint32_t pg_blocks(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, s
 
 struct pf_plotgrid {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     float device_ms = 0;
     int32_t col[6] = {};
     int32_t max_col = 0;
@@ -833,8 +863,7 @@ struct pf_plotgrid {
     uint64_t n_rec = 0;
     DevBuf d_chk;                               // PgCheck
     DevBuf d_ctr;                               // [0] records [1] checks [2] lines ; err as [3]
-    DevBuf d_text;                              // the block, padded
-    PinBuf pin;                                 // its pinned host copy
+    BlockText text;                             // the block
     uint64_t bytes_scanned = 0, lines = 0;
     // after pf_plotgrid_finish
     int finished = 0;
@@ -848,6 +877,7 @@ struct pf_plotgrid {
     DevBuf d_key, d_cnt;                       // the grids' cells
     DevBuf d_slot_item;
     DevBuf d_item;                             // off[n] | min[n] | width[n], packed in one buffer
+    TimedStream ts;
 };
 
 namespace {
@@ -865,8 +895,8 @@ int pg_tab_reserve(pf_plotgrid* g, pf_plotgrid::Tab& t, uint64_t more, uint64_t 
         if (want >= ((uint64_t)1 << 47)) return fail(PF_ERR_CAPACITY, "pf_plotgrid: name arena over 2^47 bytes");
         DevBuf a;
         PFCHK(a.ensure(want, true));
-        if (t.used) HIPCHK(hipMemcpyAsync(a.p, t.arena.p, t.used, hipMemcpyDeviceToDevice, g->stream));
-        HIPCHK(hipStreamSynchronize(g->stream));
+        if (t.used) HIPCHK(hipMemcpyAsync(a.p, t.arena.p, t.used, hipMemcpyDeviceToDevice, g->ts.stream));
+        HIPCHK(hipStreamSynchronize(g->ts.stream));
         std::swap(t.arena, a);                  // (the old arena goes at the end of this block)
     }
     uint64_t cap = std::max<uint64_t>(t.cap, 1024);
@@ -876,20 +906,20 @@ int pg_tab_reserve(pf_plotgrid* g, pf_plotgrid::Tab& t, uint64_t more, uint64_t 
     DevBuf hash, str;
     PFCHK(hash.ensure(cap * 8, true));
     PFCHK(str.ensure(cap * 8, true));
-    HIPCHK(hipMemsetAsync(hash.p, 0, cap * 8, g->stream));
+    HIPCHK(hipMemsetAsync(hash.p, 0, cap * 8, g->ts.stream));
     if (t.hash.p) {
         DevBuf remap;
         PFCHK(remap.ensure(t.cap * 4, true));
         PgTable n = pg_view(t);
         n.hash = hash.as<ull>(); n.str = str.as<ull>(); n.cap = cap;
-        hipLaunchKernelGGL(pg_rehash_kernel, dim3(pg_blocks(t.cap)), dim3(256), 0, g->stream, pg_view(t), n, remap.as<uint32_t>());
+        hipLaunchKernelGGL(pg_rehash_kernel, dim3(pg_blocks(t.cap)), dim3(256), 0, g->ts.stream, pg_view(t), n, remap.as<uint32_t>());
         HIPCHK(hipGetLastError());
         if (g->n_rec) {
-            hipLaunchKernelGGL(pg_remap_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->stream, g->d_rec.as<PgRecord>(), g->n_rec,
+            hipLaunchKernelGGL(pg_remap_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->ts.stream, g->d_rec.as<PgRecord>(), g->n_rec,
                                (const uint32_t*)remap.p, field);
             HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipStreamSynchronize(g->stream));
+        HIPCHK(hipStreamSynchronize(g->ts.stream));
     }
     std::swap(t.hash, hash); std::swap(t.str, str);   // (the old ones go on return)
     t.cap = cap;
@@ -919,15 +949,7 @@ int pg_tab_list(pf_plotgrid* g, pf_plotgrid::Tab& t, std::vector<uint32_t>& slot
 
 extern "C" {
 
-void pf_plotgrid_destroy(pf_plotgrid* g) {
-    if (!g) return;
-    (void)hipSetDevice(g->device);
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    if (g->e0) (void)hipEventDestroy(g->e0);
-    if (g->e1) (void)hipEventDestroy(g->e1);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;
-}
+void pf_plotgrid_destroy(pf_plotgrid* g) { if (g) { (void)hipSetDevice(g->device); delete g; } }
 
 int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* strain_len, uint32_t n_strains,
                        const int32_t* columns, int zoom, int64_t start, int64_t stop, pf_plotgrid** out) {
@@ -974,9 +996,7 @@ int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* s
         ids[slot] = i;
     }
     g->strain_cap = cap;
-    HIPCHK(hipStreamCreate(&g->stream));
-    HIPCHK(hipEventCreate(&g->e0));
-    HIPCHK(hipEventCreate(&g->e1));
+    PFCHK(g->ts.create());
     PFCHK(g->d_strain_hash.ensure(cap * 8, true));
     PFCHK(g->d_strain_id.ensure(cap * 4, true));
     PFCHK(g->d_strain_bytes.ensure(std::max<size_t>(bytes.size(), 1), true));
@@ -999,47 +1019,28 @@ int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t
     if (!g || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_plotgrid_scan: null argument");
     if (g->finished) return fail(PF_ERR_STATE, "pf_plotgrid_scan: after pf_plotgrid_finish");
     HIPCHK(hipSetDevice(g->device));
-    *consumed = 0;
-    uint64_t n = nbytes;
-    while (n && text[n - 1] != '\n') n--;
-    *consumed = n;
+    const uint64_t n = *consumed = BlockText::complete_lines(text, nbytes);
     if (!n) return PF_OK;
     if (n >= ((uint64_t)1 << 32)) return fail(PF_ERR_ARG, "pf_plotgrid_scan: a block of 4 GiB or more");
     // every row needs max_col tabs and a newline: at most this many rows pass
     const uint64_t rows = n / ((uint64_t)g->max_col + 1) + 1;
-    const size_t padded = (n + 15) / 16 * 16 + 16;
-    if (padded > g->d_text.cap) PFCHK(g->d_text.ensure(padded + padded / 8, true));
-    if (padded > g->pin.cap) PFCHK(g->pin.ensure(padded + padded / 8, true));
     PFCHK(g->d_chk.ensure(rows * sizeof(PgCheck), true));
     if (g->n_rec + rows > g->d_rec.cap / sizeof(PgRecord)) {
         const uint64_t want = std::max<uint64_t>((g->n_rec + rows) * 3 / 2, 1 << 16);
         DevBuf r;
         PFCHK(r.ensure(want * sizeof(PgRecord), true));
-        if (g->n_rec) HIPCHK(hipMemcpyAsync(r.p, g->d_rec.p, g->n_rec * sizeof(PgRecord), hipMemcpyDeviceToDevice, g->stream));
-        HIPCHK(hipStreamSynchronize(g->stream));
+        if (g->n_rec) HIPCHK(hipMemcpyAsync(r.p, g->d_rec.p, g->n_rec * sizeof(PgRecord), hipMemcpyDeviceToDevice, g->ts.stream));
+        HIPCHK(hipStreamSynchronize(g->ts.stream));
         std::swap(g->d_rec, r);                 // (the old records go at the end of this block)
     }
     if (int rc = pg_tab_reserve(g, g->cl, rows, n, 0)) return rc;
     if (int rc = pg_tab_reserve(g, g->pv, rows, n, 1)) return rc;
-    {
-        char* const pin = g->pin.as<char>();
-        const unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(8, n >> 22));
-        std::vector<std::thread> th;
-        const uint64_t step = (n + nt - 1) / nt;
-        for (unsigned t = 1; t < nt; t++) {
-            const uint64_t a = t * step, b = std::min<uint64_t>(n, a + step);
-            if (a < b) th.emplace_back([=] { memcpy(pin + a, text + a, (size_t)(b - a)); });
-        }
-        memcpy(pin, text, (size_t)std::min<uint64_t>(n, step));
-        for (auto& t : th) t.join();
-        memset(pin + n, 0, padded - n);
-    }
-    HIPCHK(hipMemcpyAsync(g->d_text.p, g->pin.p, padded, hipMemcpyHostToDevice, g->stream));
+    PFCHK(g->text.upload(g->ts.stream, text, n));
     unsigned long long* const d_ctr = g->d_ctr.as<ull>();
     unsigned long long ctr[4] = {g->n_rec, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(d_ctr, ctr, 3 * 8, hipMemcpyHostToDevice, g->stream));   // records continue; checks, lines restart
+    HIPCHK(hipMemcpyAsync(d_ctr, ctr, 3 * 8, hipMemcpyHostToDevice, g->ts.stream));   // records continue; checks, lines restart
     PgScanParams p{};
-    p.text = g->d_text.as<unsigned char>(); p.n = n;
+    p.text = g->text.d_text.as<unsigned char>(); p.n = n;
     for (int q = 0; q < 6; q++) p.col[q] = g->col[q];
     p.max_col = g->max_col;
     p.strain_hash = g->d_strain_hash.as<ull>(); p.strain_id = g->d_strain_id.as<uint32_t>(); p.strain_cap = g->strain_cap;
@@ -1048,25 +1049,25 @@ int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t
     p.zoom = g->zoom; p.start = g->start; p.stop = g->stop;
     p.rec = g->d_rec.as<PgRecord>(); p.n_rec = d_ctr; p.chk = g->d_chk.as<PgCheck>(); p.n_chk = d_ctr + 1; p.n_lines = d_ctr + 2;
     p.err = (unsigned int*)(d_ctr + 3);
-    HIPCHK(hipEventRecord(g->e0, g->stream));
-    hipLaunchKernelGGL(pg_scan_kernel, dim3(pg_blocks((n + 15) / 16)), dim3(256), 0, g->stream, p);
-    HIPCHK(hipGetLastError());
-    unsigned long long n_chk = 0;
-    HIPCHK(hipMemcpyAsync(&n_chk, d_ctr + 1, 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    if (n_chk) {
-        hipLaunchKernelGGL(pg_check_kernel, dim3(pg_blocks(n_chk)), dim3(256), 0, g->stream, g->d_text.as<const unsigned char>(),
-                           g->d_chk.as<const PgCheck>(), (uint64_t)n_chk, pg_view(g->cl), pg_view(g->pv), (unsigned int*)(d_ctr + 3));
+    PFCHK(g->ts.timed([&]() -> int {
+        hipLaunchKernelGGL(pg_scan_kernel, dim3(pg_blocks((n + 15) / 16)), dim3(256), 0, g->ts.stream, p);
         HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventRecord(g->e1, g->stream));
-    HIPCHK(hipMemcpyAsync(ctr, d_ctr, 4 * 8, hipMemcpyDeviceToHost, g->stream));
+        unsigned long long n_chk = 0;
+        HIPCHK(hipMemcpyAsync(&n_chk, d_ctr + 1, 8, hipMemcpyDeviceToHost, g->ts.stream));
+        HIPCHK(hipStreamSynchronize(g->ts.stream));
+        if (n_chk) {
+            hipLaunchKernelGGL(pg_check_kernel, dim3(pg_blocks(n_chk)), dim3(256), 0, g->ts.stream, p.text, g->d_chk.as<const PgCheck>(),
+                               (uint64_t)n_chk, pg_view(g->cl), pg_view(g->pv), (unsigned int*)(d_ctr + 3));
+            HIPCHK(hipGetLastError());
+        }
+        return PF_OK;
+    }));
+    HIPCHK(hipMemcpyAsync(ctr, d_ctr, 4 * 8, hipMemcpyDeviceToHost, g->ts.stream));
     unsigned long long tc[2][2];
-    HIPCHK(hipMemcpyAsync(tc[0], g->cl.ctr.p, 16, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(tc[1], g->pv.ctr.p, 16, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, g->e0, g->e1) == hipSuccess) g->device_ms += ms;
+    HIPCHK(hipMemcpyAsync(tc[0], g->cl.ctr.p, 16, hipMemcpyDeviceToHost, g->ts.stream));
+    HIPCHK(hipMemcpyAsync(tc[1], g->pv.ctr.p, 16, hipMemcpyDeviceToHost, g->ts.stream));
+    HIPCHK(hipStreamSynchronize(g->ts.stream));
+    g->ts.add_elapsed(&g->device_ms);
     g->cl.used = tc[0][0]; g->cl.count = tc[0][1];
     g->pv.used = tc[1][0]; g->pv.count = tc[1][1];
     g->n_rec = ctr[0];
@@ -1097,10 +1098,10 @@ int pf_plotgrid_finish(pf_plotgrid* g, uint32_t* n_clusters, uint64_t* n_pvalues
         HIPCHK(hipMemcpy(mx.p, init.data(), cap * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemset(cnt.p, 0, cap * 8));
         if (g->n_rec) {
-            hipLaunchKernelGGL(pg_stats_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->stream, g->d_rec.as<const PgRecord>(),
+            hipLaunchKernelGGL(pg_stats_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->ts.stream, g->d_rec.as<const PgRecord>(),
                                g->n_rec, mn.as<int>(), mx.as<int>(), cnt.as<ull>());
             HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(g->stream));
+            HIPCHK(hipStreamSynchronize(g->ts.stream));
         }
         std::vector<int> hmn(cap), hmx(cap);
         std::vector<unsigned long long> hc(cap);
@@ -1180,31 +1181,30 @@ int pf_plotgrid_grids(pf_plotgrid* g, const uint32_t* ids, uint32_t n, uint64_t*
     std::vector<uint32_t> iwidth(n);
     for (uint32_t i = 0; i < n; i++) { imin[i] = (int32_t)(int64_t)item[n + i]; iwidth[i] = (uint32_t)item[2 * (size_t)n + i]; }
     char* dit = g->d_item.as<char>();
-    HIPCHK(hipMemcpyAsync(dit, item.data(), (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    HIPCHK(hipMemcpyAsync(dit + (size_t)n * 8, imin.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-    HIPCHK(hipMemcpyAsync(dit + (size_t)n * 12, iwidth.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(dit, item.data(), (size_t)n * 8, hipMemcpyHostToDevice, g->ts.stream));
+    HIPCHK(hipMemcpyAsync(dit + (size_t)n * 8, imin.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->ts.stream));
+    HIPCHK(hipMemcpyAsync(dit + (size_t)n * 12, iwidth.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->ts.stream));
     unsigned long long* const d_err = g->d_ctr.as<ull>() + 3;
-    HIPCHK(hipMemcpyAsync(g->d_slot_item.p, slot_item.data(), cap * 4, hipMemcpyHostToDevice, g->stream));
-    HIPCHK(hipMemsetAsync(g->d_key.p, 0, cells * 8, g->stream));
-    HIPCHK(hipMemsetAsync(g->d_cnt.p, 0, cells * 8, g->stream));
-    HIPCHK(hipMemsetAsync(d_err, 0, 8, g->stream));
+    HIPCHK(hipMemcpyAsync(g->d_slot_item.p, slot_item.data(), cap * 4, hipMemcpyHostToDevice, g->ts.stream));
+    HIPCHK(hipMemsetAsync(g->d_key.p, 0, cells * 8, g->ts.stream));
+    HIPCHK(hipMemsetAsync(g->d_cnt.p, 0, cells * 8, g->ts.stream));
+    HIPCHK(hipMemsetAsync(d_err, 0, 8, g->ts.stream));
     PgGridParams p{};
     p.rec = g->d_rec.as<PgRecord>(); p.n = g->n_rec; p.slot_item = g->d_slot_item.as<int32_t>();
     p.item_off = (const uint64_t*)dit; p.item_min = (const int32_t*)(dit + (size_t)n * 8);
     p.item_width = (const uint32_t*)(dit + (size_t)n * 12);
     p.n_strains = g->n_strains; p.sig_key = g->d_sig.as<ull>(); p.key = g->d_key.as<ull>(); p.cnt = g->d_cnt.as<ull>();
     p.err = (unsigned int*)d_err;
-    HIPCHK(hipEventRecord(g->e0, g->stream));
-    hipLaunchKernelGGL(pg_grid_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->stream, p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(g->e1, g->stream));
+    PFCHK(g->ts.timed([&]() -> int {
+        hipLaunchKernelGGL(pg_grid_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->ts.stream, p);
+        HIPCHK(hipGetLastError()); return PF_OK;
+    }));
     unsigned long long err = 0;
-    HIPCHK(hipMemcpyAsync(key_out, g->d_key.p, cells * 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(cnt_out, g->d_cnt.p, cells * 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, g->e0, g->e1) == hipSuccess) g->device_ms += ms;
+    HIPCHK(hipMemcpyAsync(key_out, g->d_key.p, cells * 8, hipMemcpyDeviceToHost, g->ts.stream));
+    HIPCHK(hipMemcpyAsync(cnt_out, g->d_cnt.p, cells * 8, hipMemcpyDeviceToHost, g->ts.stream));
+    HIPCHK(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, g->ts.stream));
+    HIPCHK(hipStreamSynchronize(g->ts.stream));
+    g->ts.add_elapsed(&g->device_ms);
     if (err) return fail(PF_ERR_STATE, "pf_plotgrid_grids: a record outside its cluster's grid");
     return PF_OK;
 }

@@ -6,7 +6,8 @@ output:
 
 What costs time in them is streaming `kmers_to_hashes.tsv` (one row per kept k-mer of the whole pangenome) and
 `kmers.tsv` through pandas in 100 000-row chunks only to keep the few rows whose hash / cluster is in a set.  Here that
-row filter runs on the GPU over the raw text (`RowFilter` -> pf_rowfilter_scan, csrc/pf_rowfilter.hip); the small
+row filter runs on the GPU over the raw text (`RowFilter` -> pf_rowfilter_scan, or pf_rowfilter_scan_members for a
+device-gzipped file, csrc/pf_rowfilter.hip); the small
 tables that remain (the associations, the kept rows) go through the same pandas statements as the reference's, so the
 printed tables are the same bytes.  There is no CPU fallback for the filter.
 
@@ -232,6 +233,16 @@ def _ordered_unique(series):
     return list(dict.fromkeys(_key(v) for v in series.tolist()))
 
 
+def _filtered(keys, first_field, path, args):
+    """(header line, matching data lines) of one table by a filter of its own; .gz inputs go the device gunzip route when
+    they are files it takes, unless --host-gunzip"""
+    f = RowFilter(keys, first_field=first_field, device=args.device)
+    try:
+        return f.filter_file(path, device_gunzip=False if args.host_gunzip else None)
+    finally:
+        f.close()
+
+
 def _first_fields(rows):
     """the literal first field of every line of `rows` (bytes), in order"""
     return [ln.split(b"\t", 1)[0] for ln in rows.split(b"\n") if ln]
@@ -242,11 +253,7 @@ def get_clusters(argv=None, out=None):
     out = out or sys.stdout
     args = _options("Indicate which genes clusters have significantly associated patterns", False).parse_args(argv)
     a, passing = _associations(args)
-    f = RowFilter(passing, first_field=False, device=args.device)
-    try:
-        header, rows = f.filter_file(args.kmers_to_hashes, device_gunzip=False if args.host_gunzip else None)
-    finally:
-        f.close()
+    header, rows = _filtered(passing, False, args.kmers_to_hashes, args)
     h = _table(header, rows)
     for c in _ordered_unique(h["cluster"]):
         print(c, file=out)
@@ -258,11 +265,7 @@ def get_kmers(argv=None, out=None):
     out = out or sys.stdout
     args = _options("Annotate association results with positional information", True).parse_args(argv)
     a, passing = _associations(args, index_name="hashed_pattern")
-    f = RowFilter(passing, first_field=False, device=args.device)
-    try:
-        header, rows = f.filter_file(args.kmers_to_hashes, device_gunzip=False if args.host_gunzip else None)
-    finally:
-        f.close()
+    header, rows = _filtered(passing, False, args.kmers_to_hashes, args)
     h = _table(header, rows).set_index("hashed_pattern")
     clusters = _ordered_unique(h["cluster"])
     # The device filter compares the TEXT of a row's cluster field, the reference the values pandas parsed on both sides
@@ -279,11 +282,7 @@ def get_kmers(argv=None, out=None):
         bunch = clusters[idx: idx + args.clusters_per_iteration]
         # (a NaN among the bunch selects nothing: the reference's `x['cluster'].isin(bunch)`, get_kmers.py:131-134, is False
         # for a NaN cell when the bunch is a list of the column's unique() values -- such rows are dropped, not matched)
-        fk = RowFilter([lit for c in bunch if c is not _NAN_KEY for lit in literal[_key(c)]], first_field=True, device=args.device)
-        try:
-            kheader, krows = fk.filter_file(args.kmers, device_gunzip=False if args.host_gunzip else None)
-        finally:
-            fk.close()
+        kheader, krows = _filtered([lit for c in bunch if c is not _NAN_KEY for lit in literal[_key(c)]], True, args.kmers, args)
         k = _table(kheader, krows).set_index(["cluster", "k-mer"])
         how = "left" if args.only_passing else "right"                      # get_kmers.py:137-141
         t = b.reset_index().set_index(["cluster", "k-mer"]).join(k, how=how)

@@ -1,7 +1,6 @@
 """The row filter over device-gzipped files (RowFilter.filter_file -> pf_rowfilter_scan_members: the members inflated on the
 GPU, the text scanned where the inflate left it) and the two downstream tools over such files, against the same filter
 over the plain text and against the N4 golden outputs."""
-import ctypes as C
 import gzip
 import io
 import json
@@ -14,7 +13,7 @@ from conftest import GOLDEN, all_cases
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import deflate_cases as dc  # noqa: E402
-import inflate_cases as ic  # noqa: E402
+from device_gz_files import member_sizes, write_device_gz  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -33,36 +32,6 @@ def eng():
 def chunk_bytes():
     from panfeed_amd import _lib
     return int(_lib.load().pf_gzip_device_chunk_bytes())
-
-
-def device_gzip(eng, data):
-    from panfeed_amd import _lib
-    out, n = C.c_void_p(), C.c_uint64()
-    _lib.check(eng.L.pf_gzip_device(eng.ctx, data, len(data), 0, C.byref(out), C.byref(n)))
-    try:
-        return C.string_at(out, n.value) if n.value else b""
-    finally:
-        eng.L.pf_free_text(out)
-
-
-def write_device_gz(eng, path, header, rows):
-    """as --gpu-compress writes it: the header line's member from the host, the rows' members from the device"""
-    from panfeed_amd.output import MemberGzipWriter
-    with MemberGzipWriter(str(path)) as w:
-        w.write(header)
-        w.write_members(device_gzip(eng, rows))
-    with gzip.open(path, "rb") as fh:
-        assert fh.read() == header + rows
-
-
-def member_sizes(raw):
-    at, sizes = 0, []
-    while at < len(raw):
-        nxt = raw.find(ic.HEAD[:8], at + 1)
-        nxt = len(raw) if nxt < 0 else nxt
-        sizes.append(nxt - at)
-        at = nxt
-    return sizes
 
 
 def field(line, first_field):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import text_tables as tt
+from device_gz_files import member_sizes, write_device_gz
 
 pytestmark = pytest.mark.gpu
 
@@ -81,16 +82,21 @@ def test_rowfilter_byte_sweep(first_field, with_empty_key):
     _same_lines(got, exp)
 
 
-@pytest.mark.parametrize("first_field", MODES, ids=MODE_IDS)
-def test_rowfilter_field_limits(first_field):
-    """fields and keys of 4 094 and 4 095 bytes match, of 4 096 bytes never; a line of 100 000 bytes with a short key field"""
+def _field_limit_case():
+    """(keys, text): fields and keys of 4 094, 4 095 and 4 096 bytes; lines of 100 000 bytes with short key fields"""
     sizes = (4094, 4095, 4096)
     keys = [b"k" * n for n in sizes] + [b"ab"]
     lines = []
     for n in sizes:
         lines += [b"k" * n + b"\tx\tother", b"other\tx\t" + b"k" * n, b"k" * n, b"k" * (n - 1) + b"j\tx\t" + b"k" * (n - 1) + b"j"]
     lines += [b"ab\t" + b"w" * 100_000 + b"\tab", b"zz\t" + b"w" * 100_000 + b"\tzz", b"w" * 100_000]
-    text = b"".join(ln + b"\n" for ln in lines)
+    return keys, b"".join(ln + b"\n" for ln in lines)
+
+
+@pytest.mark.parametrize("first_field", MODES, ids=MODE_IDS)
+def test_rowfilter_field_limits(first_field):
+    """fields and keys of 4 094 and 4 095 bytes match, of 4 096 bytes never; a line of 100 000 bytes with a short key field"""
+    keys, text = _field_limit_case()
     exp = tt.filter_rows(text, keys, first_field)
     assert exp.count(b"\n") == 5 and (b"k" * 4096) not in exp
     got, used = _scan(text, keys, first_field)
@@ -169,6 +175,129 @@ def test_rowfilter_key_sets(first_field):
         exp = tt.filter_rows(text, keys, first_field)
         assert _scan(text, keys, first_field) == (exp, len(text)), keys
     assert tt.filter_rows(text, [b"ab\t1", b"\t"], first_field) == b""
+
+
+# ------------------------------------------------------------------------------------------------ row filter, member route
+# The same models through pf_rowfilter_scan_members: the text device-gzipped behind the header line's member, as
+# --gpu-compress writes it, inflated on the GPU and scanned where the inflate left it.
+@pytest.fixture(scope="module")
+def eng():
+    from panfeed_amd.engine import Engine
+    e = Engine(klength=21, max_strains=32)
+    yield e
+    e.close()
+
+
+def _chunk_bytes():
+    from panfeed_amd import _lib
+    return int(_lib.load().pf_gzip_device_chunk_bytes())
+
+
+def _member_file(eng, tmp_path, text, name="table.tsv.gz"):
+    """(path, member sizes) of HEADER + text, device-gzipped"""
+    p = tmp_path / name
+    write_device_gz(eng, p, HEADER, text)
+    return str(p), member_sizes(p.read_bytes())
+
+
+def _filter_members(path, sizes, keys, first_field, whole_members_per_call=None, times=1):
+    """filter_file by the device gunzip route alone, `times` times on one filter: every member inflated on the device"""
+    from panfeed_amd.downstream import RowFilter
+    block = None if whole_members_per_call is None else whole_members_per_call * max(sizes) + 1
+    f = RowFilter(keys, first_field=first_field)
+    try:
+        got = [f.filter_file(path, block_bytes=block, device_gunzip=True) for _ in range(times)]
+        st = f.stats()
+    finally:
+        f.close()
+    assert st["members_inflated"] == times * len(sizes) and st["gunzip_fallbacks"] == 0
+    return got[0] if times == 1 else got
+
+
+def _on_both_blockings(path, sizes, keys, first_field, exp):
+    """the default block (the whole file in one call) and one whole member a call (lines carried on the device)"""
+    for per_call in (None, 1):
+        header, rows = _filter_members(path, sizes, keys, first_field, per_call)
+        assert header == HEADER
+        _same_lines(rows, exp)
+
+
+def _model_text(which):
+    if which == "byte-sweep":
+        return tt.rowfilter_byte_sweep_text(), [[tt.SWEEP_KEY], [tt.SWEEP_KEY, b""]]
+    text, C_ = tt.rowfilter_alignment_text(), _chunk_bytes()
+    text *= -(-(2 * C_ + 1) // len(text))                       # three members of text at least
+    return text, [list(tt.RF_KEYS), list(tt.RF_KEYS) + [b""]]
+
+
+@pytest.mark.parametrize("which", ["alignment", "byte-sweep"])
+def test_member_route_on_the_model_texts(eng, tmp_path, which):
+    text, key_lists = _model_text(which)
+    path, sizes = _member_file(eng, tmp_path, text)
+    C_ = _chunk_bytes()
+    assert len(sizes) == 1 + -(-len(text) // C_)
+    if which == "alignment":
+        # a line lies across a seam between two members: it is carried from one call to the next
+        assert len(sizes) >= 1 + 3 and any(text[k * C_ - 1:k * C_] != b"\n" for k in range(1, len(sizes) - 1))
+    for first_field in MODES:
+        for keys in key_lists:
+            exp = tt.filter_rows(text, keys, first_field)
+            if which == "alignment":
+                assert exp.count(b"\n") > 60
+            else:
+                assert exp.count(b"\n") == (0 if first_field else 4 * 254 + 8)
+            _on_both_blockings(path, sizes, keys, first_field, exp)
+
+
+@pytest.mark.parametrize("first_field", MODES, ids=MODE_IDS)
+def test_member_route_header_only(eng, tmp_path, first_field):
+    path, sizes = _member_file(eng, tmp_path, b"")
+    assert len(sizes) == 1
+    assert _filter_members(path, sizes, list(tt.RF_KEYS) + [b""], first_field) == (HEADER, b"")
+
+
+@pytest.mark.parametrize("first_field", MODES, ids=MODE_IDS)
+def test_member_route_field_limits(eng, tmp_path, first_field):
+    """the lines of test_rowfilter_field_limits: those of 100 000 bytes lie across several members, so the carried line
+    and the walk to a candidate's line start cross member seams"""
+    keys, text = _field_limit_case()
+    path, sizes = _member_file(eng, tmp_path, text)
+    assert len(sizes) > 1 + 3 * 100_000 // _chunk_bytes()
+    exp = tt.filter_rows(text, keys, first_field)
+    assert exp.count(b"\n") == 5 and (b"k" * 4096) not in exp
+    _on_both_blockings(path, sizes, keys, first_field, exp)
+
+
+def test_member_route_more_candidates_than_room(eng, tmp_path):
+    """2^20 + 5 matching lines in one call, about 2 MiB of text in 64 members: the scan runs a second time with the room
+    the first asked for, and every candidate's line is gathered; the same filter again"""
+    n = 2 ** 20 + 5
+    text = b"a\n" * n + b"b\nab\t1\n\tq\n"
+    path, sizes = _member_file(eng, tmp_path, text)
+    assert len(sizes) == 1 + -(-len(text) // _chunk_bytes())
+    for header, rows in _filter_members(path, sizes, [b"a"], True, times=2):
+        assert header == HEADER and len(rows) == 2 * n and rows == b"a\n" * n
+
+
+def test_member_route_unfinished_member_over_a_slot_is_refused_at_once():
+    """a block, not the file's last, that holds no whole member: short of a slot's bytes and a head it is taken with
+    nothing consumed (the caller reads on); from that size on a member this decoder takes would have ended, and the
+    block is refused there and then -- not taken, as one whole-file member of gzip's is -- not when the file ends"""
+    import inflate_cases as ic
+
+    from panfeed_amd import _lib
+    from panfeed_amd.downstream import RowFilter
+    limit = ic.slot_bytes(_chunk_bytes()) + len(ic.HEAD)
+    data = ic.HEAD + b"\x55" * limit                         # (no second member head in it)
+    f = RowFilter([b"a"], first_field=True)
+    try:
+        _lib.check(f.L.pf_rowfilter_members_begin(f.h, 1))
+        assert f.scan_members(data[:limit - 1], False) == (b"", 0, True)
+        assert f.scan_members(data[:limit], False) == (b"", 0, False)
+        assert b"not taken" in f.L.pf_last_error()
+        assert f.scan_members(data, False) == (b"", 0, False)
+    finally:
+        f.close()
 
 
 # ------------------------------------------------------------------------------------------------ plot scan

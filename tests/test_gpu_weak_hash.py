@@ -2,7 +2,7 @@
 
 Five places are exact only because a content hash is followed by a compare of the content: the dedup pass's group table
 (cluster_dedup_kernel, both size classes), the unit-class table (unit_class_kernel), the mask table of rows_kernel's mode 2,
-the row filter's candidates (pf_rowfilter_scan) and the plot grid's name tables (pg_scan_kernel / pg_check_kernel).  With
+the row filter's candidates (pf_rowfilter_scan and pf_rowfilter_scan_members) and the plot grid's name tables (pg_scan_kernel / pg_check_kernel).  With
 64-bit hashes no input reaches those compares with two contents under one hash.  libpanfeed_hip_weakhash.so (built by
 build() beside the shipped library, -DPF_WEAK_HASH) ANDs exactly those hashes with a mask; tests/weakhash_worker.py runs
 it ONCE, in a process of its own, over tests/weak_hash_cases.py, and this module asserts run by run:
@@ -189,6 +189,28 @@ def test_rowfilter_candidates_are_verified(worker, tmp_path, mask, fixture):
     print("rowfilter", hex(mask), got["counters"])
     assert got["counters"]["rowfilter"] > 0
     assert got["counters"]["strain"] == 0
+
+
+@pytest.mark.parametrize("mask", ww.ROWFILTER_MASKS, ids=[f"{m:#x}" for m in ww.ROWFILTER_MASKS])
+def test_rowfilter_routes_verify_their_candidates_alike(worker, tmp_path, mask):
+    """kmers_to_hashes.tsv of the first fixture as a plain file (pf_rowfilter_scan) and device-gzipped
+    (pf_rowfilter_scan_members) under a masked key hash: both routes keep the rows the shipped library keeps of the plain
+    file, and both reject the same number of candidates -- the plain route never scans the header line, the member route
+    passes over the header's candidates before it counts"""
+    res = _results(worker)
+    got = res["rowfilter_routes"][f"{mask:#x}"]
+    paths, _ = ww.n4_files(str(tmp_path), N4[0])
+    plain = paths["kmers_to_hashes.tsv"]
+    shipped = ww.route_rows(plain, ww.route_keys(plain))
+    print("rowfilter routes", hex(mask), got)
+    n_data = sum(1 for _ in open(plain, "rb")) - 1
+    assert 0 < shipped["n_rows"] < n_data
+    for route in ("plain", "members"):
+        assert {k: got[route][k] for k in shipped} == shipped, route
+    if mask == 0:
+        # every data line is a candidate; those whose key is none of the keys are rejected by the bytes
+        assert got["plain"]["rejects"] == n_data - shipped["n_rows"] > 0
+    assert got["plain"]["rejects"] == got["members"]["rejects"]
 
 
 @pytest.mark.parametrize("mask", ww.ROWFILTER_MASKS, ids=[f"{m:#x}" for m in ww.ROWFILTER_MASKS])

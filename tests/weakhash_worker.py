@@ -4,7 +4,7 @@
 
 Points panfeed_amd._lib.LIB_PATH at libpanfeed_hip_weakhash.so before anything loads the library, checks that
 pf_version() names the variant, goes through every run of tests/weak_hash_cases.py (and the row filter and plot grid
-runs below) and writes OUTDIR/results.json: per run the digests of the three texts, the Timing fields and the counters of
+runs below, the row filter's two routes -- plain text and device-gzipped members -- among them) and writes OUTDIR/results.json: per run the digests of the three texts, the Timing fields and the counters of
 pf_debug_weakhash_counts.  Asserts nothing about the results: the test module does, run by run.
 """
 import ctypes as C
@@ -20,6 +20,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
 import weak_hash_cases as wc  # noqa: E402
+from device_gz_files import write_device_gz  # noqa: E402
 
 VARIANT = "libpanfeed_hip_weakhash.so"
 VERSION_WORD = "weak-hash"
@@ -84,6 +85,25 @@ def n4_run(paths, run):
     return {"rc": int(rc or 0), "lines": digest("\n".join(sorted(out.getvalue().splitlines())))}
 
 
+def route_keys(path):
+    """every third of the distinct hashed_patterns of a kmers_to_hashes.tsv: the keys of route_rows, which keep some rows
+    and leave the others to be rejected when every row is a candidate"""
+    with open(path, "rb") as fh:
+        lines = fh.read().split(b"\n")[1:-1]
+    return sorted({ln.split(b"\t")[-1] for ln in lines})[::3]
+
+
+def route_rows(path, keys, device_gunzip=None):
+    """(header, rows) of one fresh last-field filter over the file, as digests, and the number of rows"""
+    from panfeed_amd.downstream import RowFilter
+    f = RowFilter(keys, first_field=False)
+    try:
+        header, rows = f.filter_file(path, device_gunzip=device_gunzip)
+    finally:
+        f.close()
+    return {"header": digest(header), "rows": digest(rows), "n_rows": rows.count(b"\n")}
+
+
 def plot_run(outdir, two_clusters):
     """the grids of weak_hash_cases.plot_table, or the error the scan stops with"""
     import numpy as np
@@ -137,7 +157,7 @@ def main():
         return dict(zip(wc.COUNTERS, [int(x) for x in buf]))
 
     from panfeed_amd.engine import Engine  # noqa: F401  (HIP initialised by the first engine, after the path was set)
-    results = {"version": version, "runs": {}, "rowfilter": {}, "plot": {}, "seconds": {}}
+    results = {"version": version, "runs": {}, "rowfilter": {}, "rowfilter_routes": {}, "plot": {}, "seconds": {}}
     t_all = time.time()
     for case in wc.cases():
         t0 = time.time()
@@ -156,6 +176,27 @@ def main():
             counters()
             got = [n4_run(paths, r) for r in runs]
             results["rowfilter"][f"{i}-{mask:#x}"] = {"runs": got, "counters": counters()}
+    # the first fixture's kmers_to_hashes.tsv by the row filter's two routes: the plain file (pf_rowfilter_scan) and the same
+    # text device-gzipped (pf_rowfilter_scan_members), the file written before any hash is masked
+    set_mask(None, wc.CONTROL)
+    plain = os.path.join(outdir, "n4_0", "kmers_to_hashes.tsv")
+    with open(plain, "rb") as fh:
+        text = fh.read()
+    cut = text.index(b"\n") + 1
+    eng = Engine(klength=21, max_strains=32)
+    try:
+        write_device_gz(eng, plain + ".gz", text[:cut], text[cut:])
+    finally:
+        eng.close()
+    keys = route_keys(plain)
+    for mask in ROWFILTER_MASKS:
+        set_mask(None, mask)
+        counters()
+        got = {}
+        for route, path, kw in (("plain", plain, {}), ("members", plain + ".gz", {"device_gunzip": True})):
+            got[route] = route_rows(path, keys, **kw)
+            got[route]["rejects"] = counters()["rowfilter"]
+        results["rowfilter_routes"][f"{mask:#x}"] = got
     for mask in ROWFILTER_MASKS:
         set_mask(None, mask)
         counters()
