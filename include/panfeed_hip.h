@@ -612,6 +612,55 @@ int pf_rowfilter_gunzip_stats(pf_rowfilter* f, uint64_t* members, uint64_t* text
 void pf_rowfilter_destroy(pf_rowfilter* f);
 
 /*
+ * panfeed-get-kmers' join on the device: /root/reference/panfeed/get_kmers.py:131-141.  The rows of
+ * kmers.tsv whose cluster is a selected one come out as `cluster \t k-mer \t <text> \t <fields 2..10> \n`, in file order,
+ * where <text> is what the host rendered for the row's (cluster, k-mer) -- one of two renderings -- or `empty_text` for a
+ * row that has no key.  Clusters and keys are looked up by 64-bit hash and verified by their bytes on the device.
+ * create: the selected clusters, each with the number (< n_bunches) of the bunch it is joined in; the keys with their two
+ * texts.  A cluster or key field of 4 096 bytes or more matches nothing (as in the row filter); a key that comes twice is
+ * an error.
+ * survey: one pass for all bunches.  Blocks as pf_rowfilter_scan takes them (or blocks of members, as
+ * pf_rowfilter_scan_members: the three *_members* calls mirror the row filter's); pf_kmerjoin_counters then gives five
+ * numbers per bunch (valid until the next call): rows, rows without a key, output bytes under rendering 0 and under
+ * rendering 1, and the OR of the rows' plainness flags (PF_KJ_*).  A flagged row is one that pandas' read_csv -> to_csv
+ * might not print as it stands; the caller joins such a bunch another way.
+ * join: the rows of one bunch of a block, in rendering `mode` 0 or 1; mode 2 keeps, as they stand, the rows that have a
+ * key.  *out_bytes = the bytes of text made; pf_kmerjoin_next_text hands them out piece by piece through pinned memory
+ * (*nbytes = 0: no more; a piece is valid until the call after the next).  A row that would have been flagged is
+ * PF_ERR_STATE here.
+ * stats (either may be NULL): stats[0] bytes scanned, [1] rows written, [2] raw rows kept (mode 2), [3] members and
+ * [4] text bytes inflated, [5] the decoder's device bytes, [6] look-ups whose hash was equal and whose bytes were not
+ * (above zero only under a weakened hash, in practice), [7] rows written with the empty text; ms[0] survey kernels, [1] join kernels, [2] inflate.
+ */
+#define PF_KJ_TABS 1u      /* not exactly 10 tabs */
+#define PF_KJ_BYTES 2u     /* a byte below 0x20 other than tab, of 0x80 or above, or a double quote */
+#define PF_KJ_INT 4u       /* one of the six integer fields is not canonical decimal of at most 18 digits */
+#define PF_KJ_EMPTY 8u     /* one of the five text fields is empty */
+#define PF_KJ_NA 16u       /* a text field is one of pandas' default NA strings */
+#define PF_KJ_NUMERIC 32u  /* a text field has only bytes of 0123456789+-.eE */
+#define PF_KJ_WORD 64u     /* a text field is, ignoring case and a sign, inf, infinity, nan, true or false */
+#define PF_KJ_LONG 128u    /* a row of more than 65 536 bytes, or a field of 4 096 bytes or more */
+typedef struct pf_kmerjoin pf_kmerjoin;
+int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* cluster_len, const uint32_t* cluster_bunch,
+                       uint64_t n_clusters, uint32_t n_bunches, const char* const* key_cluster, const uint32_t* key_cluster_len,
+                       const char* const* key_kmer, const uint32_t* key_kmer_len, const char* const* text0, const uint32_t* text0_len,
+                       const char* const* text1, const uint32_t* text1_len, uint64_t n_keys, const char* empty_text,
+                       uint32_t empty_len, pf_kmerjoin** out);
+int pf_kmerjoin_survey(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint64_t* consumed);
+int pf_kmerjoin_members_begin(pf_kmerjoin* j, int header);
+int pf_kmerjoin_members_header(pf_kmerjoin* j, const char** line, uint64_t* nbytes);
+int pf_kmerjoin_survey_members(pf_kmerjoin* j, const char* members, uint64_t nbytes, int last, uint64_t* consumed, int* taken);
+int pf_kmerjoin_reset_counters(pf_kmerjoin* j);
+int pf_kmerjoin_counters(pf_kmerjoin* j, const uint64_t** counters, uint32_t* n_bunches);
+int pf_kmerjoin_join(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint32_t bunch, int mode, uint64_t* out_bytes,
+                     uint64_t* consumed);
+int pf_kmerjoin_join_members(pf_kmerjoin* j, const char* members, uint64_t nbytes, int last, uint32_t bunch, int mode,
+                             uint64_t* out_bytes, uint64_t* consumed, int* taken);
+int pf_kmerjoin_next_text(pf_kmerjoin* j, const char** piece, uint64_t* nbytes);
+int pf_kmerjoin_stats(pf_kmerjoin* j, uint64_t stats[8], float ms[3]);
+void pf_kmerjoin_destroy(pf_kmerjoin* j);
+
+/*
  * panfeed-plot's per-cluster grids on the device, over the annotated k-mer table that
  * panfeed-get-kmers writes.  Replaces /root/reference/panfeed/plot.py:195-222 (the whole table in one pandas frame, the
  * `isin` strain filter at :200, the base letter / scalar at :209-222) and the three pivot_tables per cluster at

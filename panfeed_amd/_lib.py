@@ -152,7 +152,10 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_gzip_device_chunk_bytes", "pf_gzip_device", "pf_gzip_host_model", "pf_set_device_gzip",
            "pf_device_gzip_text_bytes", "pf_gzip_device_last_ms",
            "pf_gunzip_device", "pf_gunzip_device_last_ms", "pf_gunzip_host_model",
-           "pf_rowfilter_members_begin", "pf_rowfilter_members_header", "pf_rowfilter_scan_members", "pf_rowfilter_gunzip_stats"]
+           "pf_rowfilter_members_begin", "pf_rowfilter_members_header", "pf_rowfilter_scan_members", "pf_rowfilter_gunzip_stats",
+           "pf_kmerjoin_create", "pf_kmerjoin_survey", "pf_kmerjoin_members_begin", "pf_kmerjoin_members_header",
+           "pf_kmerjoin_survey_members", "pf_kmerjoin_reset_counters", "pf_kmerjoin_counters", "pf_kmerjoin_join",
+           "pf_kmerjoin_join_members", "pf_kmerjoin_next_text", "pf_kmerjoin_stats", "pf_kmerjoin_destroy"]
 
 RENDER_NO_PATTERN_ROWS = 1
 GZ_FIXED_ONLY, GZ_DYNAMIC_ONLY, GZ_LITERALS_ONLY = 1, 2, 4     # pf_gzip_device / pf_set_device_gzip test hooks; 0: the product
@@ -300,6 +303,22 @@ def _load_locked():
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     L.pf_rowfilter_gunzip_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float),
                                             C.POINTER(C.c_uint64)]
+    strs, u32s, u64p = C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(C.c_uint64)
+    L.pf_kmerjoin_create.argtypes = [C.c_int, strs, u32s, u32s, C.c_uint64, C.c_uint32, strs, u32s, strs, u32s, strs, u32s,
+                                     strs, u32s, C.c_uint64, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.pf_kmerjoin_survey.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, u64p]
+    L.pf_kmerjoin_members_begin.argtypes = [C.c_void_p, C.c_int]
+    L.pf_kmerjoin_members_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), u64p]
+    L.pf_kmerjoin_survey_members.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, u64p, C.POINTER(C.c_int)]
+    L.pf_kmerjoin_reset_counters.argtypes = [C.c_void_p]
+    L.pf_kmerjoin_counters.argtypes = [C.c_void_p, C.POINTER(u64p), C.POINTER(C.c_uint32)]
+    L.pf_kmerjoin_join.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_int, u64p, u64p]
+    L.pf_kmerjoin_join_members.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_uint32, C.c_int, u64p, u64p,
+                                           C.POINTER(C.c_int)]
+    L.pf_kmerjoin_next_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), u64p]
+    L.pf_kmerjoin_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pf_kmerjoin_destroy.argtypes = [C.c_void_p]
+    L.pf_kmerjoin_destroy.restype = None
     L.pf_submit_gather.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Gather), C.POINTER(Result)]
     L.pf_records_free.argtypes = [C.c_void_p]
     L.pf_records_free.restype = None

@@ -1220,6 +1220,627 @@ int pf_plotgrid_stats(pf_plotgrid* g, uint64_t* bytes_scanned, uint64_t* lines, 
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------------------------------------------------
+// panfeed-get-kmers' join: /root/reference/panfeed/get_kmers.py:131-141 on the device.
+//
+// The reference parses every kmers.tsv row of a bunch of clusters and joins the small table of passing (cluster, k-mer)
+// pairs to it (`how="right"`: every row comes out, in file order, with the table's columns or empty fields in front of
+// its own).  Here the host renders the table's columns as text once per key (downstream.rendered_texts) and the device
+// does the per-row work: find the row's cluster in a table of the selected clusters, its (cluster, k-mer) in a table of
+// the keys -- both open addressing on rf_hash values, both verified by bytes HERE, since a written row never reaches the
+// host before it is output -- and write  cluster \t k-mer \t <text> \t <fields 2..10 as they stand> \n.
+//
+// Two kinds of pass over blocks of complete lines.  Every thread owns 256 bytes (16 vectors of 16) and the lines whose
+// preceding newline lies in them.
+//   survey   all bunches at once: per bunch, rows, rows without a key, output bytes under either rendering, and the OR
+//            of the rows' plainness flags (KJ_*): a flagged row is one pandas' read_csv -> to_csv might not print as it
+//            stands, and its bunch goes through pandas
+//   join     one bunch: kj_plan_kernel counts each thread's rows and output bytes, kj_tiles_kernel makes the tiles' sums
+//            exclusive prefixes, kj_place_kernel gives every row a record (source, destination, the four pieces) in file
+//            order, kj_write_kernel copies: a wave per group of 16 consecutive rows, lanes striding over a row's bytes.
+//            mode 2 keeps the raw rows that have a key instead (--only-passing: pandas joins those few).
+// A row of more than KJ_MAX_LINE bytes, or with a field of RF_MAX_FIELD bytes or more, is a flag (KJ_LONG), never a fault.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t KJ_MAX_LINE = 1u << 16;
+constexpr uint32_t KJ_TILE_VECS = 4096;          // vectors of a workgroup: 256 threads x 16
+constexpr uint32_t KJ_GROUP = 16;                // rows of a wave's step in the writer
+constexpr uint64_t KJ_PIECE = 32ull << 20;       // bytes of output handed out at a time
+enum : uint32_t { KJ_TABS = 1, KJ_BYTES = 2, KJ_INT = 4, KJ_EMPTY = 8, KJ_NA = 16, KJ_NUMERIC = 32, KJ_WORD = 64, KJ_LONG = 128 };
+enum { KJ_ROWS = 0, KJ_UNMATCHED = 1, KJ_BYTES0 = 2, KJ_BYTES1 = 3, KJ_FLAGS = 4, KJ_COUNTERS = 5 };
+
+struct KjCluster { uint32_t off, len, bunch; };
+struct KjKey { uint32_t cl_off, cl_len, km_off, km_len, t_off[2], t_len[2]; };
+struct KjRec { uint64_t src, dst; uint32_t len0, f1, mid, f10, len10, t_off, t_len, raw; };
+
+struct KjParams {
+    const unsigned char* text;   // the block, complete lines, zero-padded to the next multiple of 16 bytes
+    uint64_t n, begin;           // lines that start in [begin, n)
+    const unsigned long long* chash; const uint32_t* cslot; uint64_t ccap; const KjCluster* clusters;
+    const unsigned long long* khash; const uint32_t* kslot; uint64_t kcap; const KjKey* keys;
+    const unsigned char* arena;  // the clusters', keys' and texts' bytes
+    uint32_t empty_off, empty_len;
+    int32_t bunch;               // join: the bunch whose rows are written
+    int mode;                    // join: rendering 0 / 1, or 2: the raw rows that have a key
+    unsigned long long* counters;        // survey: KJ_COUNTERS per bunch
+    unsigned long long* rejects;         // look-ups whose hash was equal and whose bytes were not
+    unsigned long long* unmatched;       // join: rows written with the empty text
+    uint2* thr;                          // join: per thread, rows and output bytes
+    unsigned long long* tile;            // join: per tile, rows and bytes (then their exclusive prefixes), and the totals behind
+    KjRec* rec;
+    unsigned char* out;
+    unsigned int* err;
+};
+
+__device__ __forceinline__ bool kj_same(const unsigned char* a, const unsigned char* b, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) if (a[i] != b[i]) return false;
+    return true;
+}
+
+// the bunch of the line at s by its first field, -1 if that is no selected cluster; *len0 = the field's length
+__device__ int32_t kj_cluster(const KjParams& p, uint64_t s, uint32_t* len0, uint64_t* hash) {
+    uint64_t h = 0xCBF29CE484222325ull, e = s;
+    while (e - s < RF_MAX_FIELD && p.text[e] != '\t' && p.text[e] != '\n') { h = rf_hash_step(h, p.text[e]); e++; }
+    if (e - s >= RF_MAX_FIELD) return -1;                      // (as the row filter: a field this long matches nothing)
+    *len0 = (uint32_t)(e - s); *hash = h;
+    const uint64_t hf = rf_hash_fin(h);
+    uint64_t slot = hf & (p.ccap - 1);
+    for (uint64_t probes = 0; probes < p.ccap; probes++) {
+        const unsigned long long cur = p.chash[slot];
+        if (cur == 0) return -1;
+        if (cur == hf) {
+            const KjCluster c = p.clusters[p.cslot[slot]];
+            if (c.len == *len0 && kj_same(p.arena + c.off, p.text + s, c.len)) return (int32_t)c.bunch;
+            atomicAdd(p.rejects, 1ull);
+        }
+        slot = (slot + 1) & (p.ccap - 1);
+    }
+    return -1;
+}
+
+// the key of (cluster, k-mer), -1 if there is none; h = the unfinished hash of the cluster's bytes
+__device__ int64_t kj_key(const KjParams& p, uint64_t h, const unsigned char* cl, uint32_t cl_len, const unsigned char* km, uint32_t km_len) {
+    h = rf_hash_step(h, '\t');
+    for (uint32_t i = 0; i < km_len; i++) h = rf_hash_step(h, km[i]);
+    const uint64_t hf = rf_hash_fin(h);
+    uint64_t slot = hf & (p.kcap - 1);
+    for (uint64_t probes = 0; probes < p.kcap; probes++) {
+        const unsigned long long cur = p.khash[slot];
+        if (cur == 0) return -1;
+        if (cur == hf) {
+            const uint32_t id = p.kslot[slot];
+            const KjKey k = p.keys[id];
+            if (k.cl_len == cl_len && k.km_len == km_len && kj_same(p.arena + k.cl_off, cl, cl_len) && kj_same(p.arena + k.km_off, km, km_len))
+                return id;
+            atomicAdd(p.rejects, 1ull);
+        }
+        slot = (slot + 1) & (p.kcap - 1);
+    }
+    return -1;
+}
+
+__device__ __forceinline__ unsigned char kj_lower(unsigned char c) { return (c >= 'A' && c <= 'Z') ? c + 32 : c; }
+
+// s[0 .. n) is one of the strings of `list` (each ended by a 0, the list by another), case folded or not
+__device__ bool kj_in_list(const char* list, const unsigned char* s, uint32_t n, bool fold) {
+    while (*list) {
+        uint32_t i = 0;
+        while (list[i] && i < n && (unsigned char)list[i] == (fold ? kj_lower(s[i]) : s[i])) i++;
+        if (!list[i] && i == n) return true;
+        while (list[i]) i++;
+        list += i + 1;
+    }
+    return false;
+}
+
+// pandas' default NA strings but the empty one, and the words its parsers read as a float or a bool
+__device__ const char kj_na_strings[] = "#N/A\0#N/A N/A\0#NA\0-1.#IND\0-1.#QNAN\0-NaN\0-nan\0001.#IND\0001.#QNAN\0<NA>\0N/A\0NA\0NULL\0NaN\0None\0n/a\0nan\0null\0";
+__device__ const char kj_words[] = "inf\0infinity\0nan\0true\0false\0";
+
+// the plainness flags of field `idx` of a row
+__device__ uint32_t kj_field_flags(const unsigned char* s, uint32_t n, uint32_t idx) {
+    if (idx > 10) return 0;                                    // (KJ_TABS says it)
+    uint32_t f = n >= RF_MAX_FIELD ? KJ_LONG : 0;
+    if (idx >= 4 && idx <= 9) {                                // canonical decimal: -?(0|[1-9][0-9]{0,17}), no -0
+        uint32_t i = (n && s[0] == '-') ? 1 : 0;
+        const uint32_t digits = n - i;
+        bool ok = digits >= 1 && digits <= 18 && !(digits > 1 && s[i] == '0') && !(i && s[i] == '0');
+        for (; ok && i < n; i++) ok = s[i] >= '0' && s[i] <= '9';
+        return f | (ok ? 0 : KJ_INT);
+    }
+    if (!n) return f | KJ_EMPTY;
+    bool numeric = true;
+    for (uint32_t i = 0; numeric && i < n; i++) {
+        const unsigned char c = s[i];
+        numeric = (c >= '0' && c <= '9') || c == '+' || c == '-' || c == '.' || c == 'e' || c == 'E';
+    }
+    if (numeric) f |= KJ_NUMERIC;
+    if (n <= 9) {
+        if (kj_in_list(kj_na_strings, s, n, false)) f |= KJ_NA;
+        const uint32_t sign = (s[0] == '+' || s[0] == '-') ? 1 : 0;
+        if (kj_in_list(kj_words, s + sign, n - sign, true)) f |= KJ_WORD;
+    }
+    return f;
+}
+
+struct KjWalk { uint32_t len, f1, end9, f10, flags; };     // len without the newline; field 1's start, field 9's end, field 10's start
+
+// the line at s (text[n - 1] is a newline).  FLAGS: all plainness flags; otherwise KJ_TABS and KJ_LONG only
+template <bool FLAGS> __device__ void kj_walk(const unsigned char* t, uint64_t s, KjWalk& w) {
+    uint32_t tabs = 0, fb = 0, flags = 0, i = 0;
+    w.f1 = w.end9 = w.f10 = 0;
+    for (;; i++) {
+        if (i >= KJ_MAX_LINE) { flags |= KJ_LONG; break; }
+        const unsigned char c = t[s + i];
+        if (c == '\t' || c == '\n') {
+            if (FLAGS) flags |= kj_field_flags(t + s + fb, i - fb, tabs);
+            else if (i - fb >= RF_MAX_FIELD) flags |= KJ_LONG;
+            if (tabs == 0) w.f1 = i + 1;
+            if (tabs == 9) { w.end9 = i; w.f10 = i + 1; }
+            if (c == '\n') break;
+            tabs++; fb = i + 1;
+        } else if (FLAGS && (c < 0x20 || c >= 0x80 || c == '"')) flags |= KJ_BYTES;
+    }
+    if (tabs != 10) flags |= KJ_TABS;
+    w.len = i; w.flags = flags;
+}
+
+// line_start(s) for every line of [begin, n) whose preceding newline -- or, for the line at 0, the block's start -- is in
+// this thread's 16 vectors, in file order
+template <class F> __device__ __forceinline__ void kj_each_line(const KjParams& p, F&& line_start) {
+    const uint64_t nvec = (p.n + 15) / 16;
+    const uint64_t v0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+    if (v0 == 0 && p.begin == 0 && p.n) line_start(0);
+    for (uint64_t v = v0; v < v0 + 16 && v < nvec; v++)
+        rf_each_newline(p.text, v, [&](uint64_t at) { if (at + 1 < p.n && at + 1 >= p.begin) line_start(at + 1); });
+}
+
+__global__ __launch_bounds__(256) void kj_survey_kernel(KjParams p) {
+    // the workgroup's 64 KiB of text are nearly always rows of one bunch: that bunch's counters are kept in LDS
+    __shared__ unsigned long long s_cnt[KJ_COUNTERS];
+    __shared__ int s_bunch;
+    if (threadIdx.x < KJ_COUNTERS) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_bunch = -1;
+    __syncthreads();
+    kj_each_line(p, [&](uint64_t s) {
+        uint32_t len0; uint64_t h;
+        const int32_t bunch = kj_cluster(p, s, &len0, &h);
+        if (bunch < 0) return;
+        KjWalk w;
+        kj_walk<true>(p.text, s, w);
+        uint64_t bytes[2] = {0, 0};
+        bool unmatched = false;
+        if (!(w.flags & (KJ_TABS | KJ_LONG))) {
+            const int64_t id = kj_key(p, h, p.text + s, len0, p.text + s + w.f10, w.len - w.f10);
+            unmatched = id < 0;
+            const uint64_t fixed = (uint64_t)len0 + (w.len - w.f10) + (w.end9 - w.f1) + 4;
+            for (int r = 0; r < 2; r++) bytes[r] = fixed + (id < 0 ? p.empty_len : p.keys[id].t_len[r]);
+        }
+        int mine = s_bunch;
+        if (mine < 0) { const int old = atomicCAS(&s_bunch, -1, bunch); mine = old < 0 ? bunch : old; }
+        unsigned long long* const c = mine == bunch ? s_cnt : p.counters + (uint64_t)bunch * KJ_COUNTERS;
+        atomicAdd(&c[KJ_ROWS], 1ull);
+        if (unmatched) atomicAdd(&c[KJ_UNMATCHED], 1ull);
+        atomicAdd(&c[KJ_BYTES0], (unsigned long long)bytes[0]);
+        atomicAdd(&c[KJ_BYTES1], (unsigned long long)bytes[1]);
+        if (w.flags) atomicOr(&c[KJ_FLAGS], (unsigned long long)w.flags);
+    });
+    __syncthreads();
+    if (threadIdx.x < KJ_COUNTERS && s_bunch >= 0 && s_cnt[threadIdx.x]) {
+        unsigned long long* const c = p.counters + (uint64_t)s_bunch * KJ_COUNTERS + threadIdx.x;
+        if (threadIdx.x == KJ_FLAGS) atomicOr(c, s_cnt[threadIdx.x]); else atomicAdd(c, s_cnt[threadIdx.x]);
+    }
+}
+
+// the row of this join's output the line at s makes, if it makes one (its dst is the caller's); *keyed: it has a key
+__device__ bool kj_row(const KjParams& p, uint64_t s, KjRec& r, bool* keyed) {
+    uint32_t len0; uint64_t h;
+    if (kj_cluster(p, s, &len0, &h) != p.bunch) return false;
+    KjWalk w;
+    kj_walk<false>(p.text, s, w);
+    if (w.flags) { atomicOr(p.err, w.flags); return false; }       // not the file the survey saw
+    const int64_t id = kj_key(p, h, p.text + s, len0, p.text + s + w.f10, w.len - w.f10);
+    *keyed = id >= 0;
+    r.src = s; r.f1 = w.f1; r.mid = w.end9 - w.f1; r.f10 = w.f10; r.len10 = w.len - w.f10;
+    if (p.mode == 2) {
+        if (id < 0) return false;
+        r.raw = 1; r.len0 = w.len + 1; r.t_off = 0; r.t_len = 0;
+        return true;
+    }
+    r.raw = 0; r.len0 = len0;
+    r.t_off = id < 0 ? p.empty_off : p.keys[id].t_off[p.mode];
+    r.t_len = id < 0 ? p.empty_len : p.keys[id].t_len[p.mode];
+    return true;
+}
+
+__device__ __forceinline__ uint32_t kj_out_len(const KjRec& r) { return r.raw ? r.len0 : r.len0 + r.len10 + r.t_len + r.mid + 4; }
+
+// an exclusive prefix sum over the workgroup's 256 threads of (a, b); the totals to all
+__device__ void kj_block_exscan(unsigned long long& a, unsigned long long& b, unsigned long long* tot_a, unsigned long long* tot_b) {
+    __shared__ unsigned long long sa[256], sb[256];
+    const uint32_t t = threadIdx.x;
+    const unsigned long long a0 = a, b0 = b;
+    sa[t] = a; sb[t] = b;
+    __syncthreads();
+    for (uint32_t d = 1; d < 256; d <<= 1) {
+        const unsigned long long xa = t >= d ? sa[t - d] : 0, xb = t >= d ? sb[t - d] : 0;
+        __syncthreads();
+        sa[t] += xa; sb[t] += xb;
+        __syncthreads();
+    }
+    a = sa[t] - a0; b = sb[t] - b0;
+    *tot_a = sa[255]; *tot_b = sb[255];
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void kj_plan_kernel(KjParams p) {
+    unsigned long long rows = 0, bytes = 0, unmatched = 0;
+    kj_each_line(p, [&](uint64_t s) {
+        KjRec r; bool keyed;
+        if (kj_row(p, s, r, &keyed)) { rows++; bytes += kj_out_len(r); unmatched += !keyed; }
+    });
+    if (unmatched) atomicAdd(p.unmatched, unmatched);
+    p.thr[(uint64_t)blockIdx.x * 256 + threadIdx.x] = make_uint2((uint32_t)rows, (uint32_t)bytes);
+    unsigned long long ta, tb;
+    kj_block_exscan(rows, bytes, &ta, &tb);
+    if (threadIdx.x == 0) { p.tile[2 * (uint64_t)blockIdx.x] = ta; p.tile[2 * (uint64_t)blockIdx.x + 1] = tb; }
+}
+
+// tile[2 i], tile[2 i + 1] -> their exclusive prefixes; the totals to tile[2 n], tile[2 n + 1].  One workgroup
+__global__ __launch_bounds__(256) void kj_tiles_kernel(unsigned long long* tile, uint64_t n) {
+    const uint64_t per = (n + 255) / 256, lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
+    unsigned long long a = 0, b = 0;
+    for (uint64_t i = lo; i < hi; i++) { a += tile[2 * i]; b += tile[2 * i + 1]; }
+    unsigned long long ta, tb;
+    kj_block_exscan(a, b, &ta, &tb);
+    for (uint64_t i = lo; i < hi; i++) {
+        const unsigned long long xa = tile[2 * i], xb = tile[2 * i + 1];
+        tile[2 * i] = a; tile[2 * i + 1] = b;
+        a += xa; b += xb;
+    }
+    if (threadIdx.x == 0) { tile[2 * n] = ta; tile[2 * n + 1] = tb; }
+}
+
+__global__ __launch_bounds__(256) void kj_place_kernel(KjParams p, uint64_t n_rows, uint64_t n_bytes) {
+    const uint2 mine = p.thr[(uint64_t)blockIdx.x * 256 + threadIdx.x];
+    unsigned long long row = mine.x, at = mine.y, ta, tb;
+    kj_block_exscan(row, at, &ta, &tb);
+    row += p.tile[2 * (uint64_t)blockIdx.x]; at += p.tile[2 * (uint64_t)blockIdx.x + 1];
+    kj_each_line(p, [&](uint64_t s) {
+        KjRec r; bool keyed;
+        if (!kj_row(p, s, r, &keyed)) return;
+        r.dst = at;
+        const uint32_t len = kj_out_len(r);
+        if (row < n_rows && at + len <= n_bytes) p.rec[row] = r; else atomicOr(p.err, 0x80000000u);
+        row++; at += len;
+    });
+}
+
+__global__ __launch_bounds__(256) void kj_write_kernel(KjParams p, uint64_t n_rows) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t g = wave * KJ_GROUP; g < n_rows; g += n_waves * KJ_GROUP) {
+        for (uint64_t k = g; k < g + KJ_GROUP && k < n_rows; k++) {
+            const KjRec r = p.rec[k];
+            const unsigned char* const src = p.text + r.src;
+            unsigned char* const dst = p.out + r.dst;
+            if (r.raw) { for (uint32_t i = lane; i < r.len0; i += 64) dst[i] = src[i]; continue; }
+            // cluster \t k-mer \t text \t fields 1..9 \n
+            const uint32_t e0 = r.len0, e1 = e0 + 1 + r.len10, e2 = e1 + 1 + r.t_len, e3 = e2 + 1 + r.mid;
+            for (uint32_t i = lane; i <= e3; i += 64) {
+                unsigned char c;
+                if (i < e0) c = src[i];
+                else if (i == e0 || i == e1 || i == e2) c = '\t';
+                else if (i < e1) c = src[r.f10 + (i - e0 - 1)];
+                else if (i < e2) c = p.arena[r.t_off + (i - e1 - 1)];
+                else if (i < e3) c = src[r.f1 + (i - e2 - 1)];
+                else c = '\n';
+                dst[i] = c;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+struct pf_kmerjoin {
+    pf_rowfilter rf;                             // the block's text, the member stages' state, the stream: the row filter's own
+    uint32_t n_bunches = 0;
+    uint64_t ccap = 0, kcap = 0;
+    uint32_t empty_off = 0, empty_len = 0;
+    DevBuf d_chash, d_cslot, d_clusters, d_khash, d_kslot, d_keys, d_arena, d_counters, d_misc;     // d_misc: rejects, err, unmatched
+    DevBuf d_thr, d_tile, d_rec, d_out;
+    PinBuf pin[2];
+    std::vector<uint64_t> counters;
+    uint64_t out_bytes = 0, out_pos = 0, flying = 0;      // the join's text: its bytes, those handed out or on their way, the piece on its way
+    int cur = 0;
+    uint64_t bytes_scanned = 0, rows_written = 0, raw_rows = 0;
+    float survey_ms = 0, write_ms = 0;
+};
+
+namespace {
+
+KjParams kj_params(pf_kmerjoin* j, uint64_t n, uint64_t begin) {
+    KjParams p{};
+    p.text = j->rf.text.d_text.as<unsigned char>(); p.n = n; p.begin = begin;
+    p.chash = j->d_chash.as<unsigned long long>(); p.cslot = j->d_cslot.as<uint32_t>(); p.ccap = j->ccap; p.clusters = j->d_clusters.as<KjCluster>();
+    p.khash = j->d_khash.as<unsigned long long>(); p.kslot = j->d_kslot.as<uint32_t>(); p.kcap = j->kcap; p.keys = j->d_keys.as<KjKey>();
+    p.arena = j->d_arena.as<unsigned char>(); p.empty_off = j->empty_off; p.empty_len = j->empty_len;
+    p.counters = j->d_counters.as<unsigned long long>();
+    p.rejects = j->d_misc.as<unsigned long long>(); p.err = reinterpret_cast<unsigned int*>(j->d_misc.as<unsigned long long>() + 1);
+    p.unmatched = j->d_misc.as<unsigned long long>() + 2;
+    return p;
+}
+
+inline uint32_t kj_tiles(uint64_t n) { return (uint32_t)(((n + 15) / 16 + KJ_TILE_VECS - 1) / KJ_TILE_VECS); }
+
+// the survey of d_text[begin .. n)
+int kj_survey_device(pf_kmerjoin* j, uint64_t n, uint64_t begin) {
+    if (n <= begin) return PF_OK;
+    TimedStream& ts = j->rf.ts;
+    const KjParams p = kj_params(j, n, begin);
+    PFCHK(ts.timed([&]() -> int {
+        hipLaunchKernelGGL(kj_survey_kernel, dim3(kj_tiles(n)), dim3(256), 0, ts.stream, p);
+        HIPCHK(hipGetLastError()); return PF_OK;
+    }));
+    HIPCHK(hipStreamSynchronize(ts.stream));
+    ts.add_elapsed(&j->survey_ms);
+    j->bytes_scanned += n - begin;
+    return PF_OK;
+}
+
+// the join of d_text[begin .. n) for one bunch: the text in d_out[0 .. out_bytes), ready to be handed out
+int kj_join_device(pf_kmerjoin* j, uint64_t n, uint64_t begin, uint32_t bunch, int mode) {
+    j->out_bytes = j->out_pos = j->flying = 0;
+    if (n <= begin) return PF_OK;
+    if (bunch >= j->n_bunches || mode < 0 || mode > 2) return fail(PF_ERR_ARG, "pf_kmerjoin_join: no such bunch or mode");
+    TimedStream& ts = j->rf.ts;
+    const uint32_t tiles = kj_tiles(n);
+    PFCHK(j->d_thr.ensure((size_t)tiles * 256 * sizeof(uint2)));
+    PFCHK(j->d_tile.ensure(((size_t)tiles + 1) * 16));
+    KjParams p = kj_params(j, n, begin);
+    p.bunch = (int32_t)bunch; p.mode = mode;
+    p.thr = j->d_thr.as<uint2>(); p.tile = j->d_tile.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(p.err, 0, 4, ts.stream));
+    float ms = 0;
+    PFCHK(ts.timed([&]() -> int {
+        hipLaunchKernelGGL(kj_plan_kernel, dim3(tiles), dim3(256), 0, ts.stream, p);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(kj_tiles_kernel, dim3(1), dim3(256), 0, ts.stream, p.tile, (uint64_t)tiles);
+        HIPCHK(hipGetLastError()); return PF_OK;
+    }));
+    uint64_t totals[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(totals, p.tile + 2 * (uint64_t)tiles, 16, hipMemcpyDeviceToHost, ts.stream));
+    HIPCHK(hipStreamSynchronize(ts.stream));
+    ts.add_elapsed(&ms);
+    j->bytes_scanned += n - begin;
+    const uint64_t n_rows = totals[0], n_bytes = totals[1];
+    unsigned int err = 0;
+    if (n_rows) {
+        PFCHK(j->d_rec.ensure((size_t)n_rows * sizeof(KjRec)));
+        PFCHK(j->d_out.ensure((size_t)n_bytes));
+        p.rec = j->d_rec.as<KjRec>(); p.out = j->d_out.as<unsigned char>();
+        PFCHK(ts.timed([&]() -> int {
+            hipLaunchKernelGGL(kj_place_kernel, dim3(tiles), dim3(256), 0, ts.stream, p, n_rows, n_bytes);
+            HIPCHK(hipGetLastError());
+            const uint64_t groups = (n_rows + KJ_GROUP - 1) / KJ_GROUP;
+            hipLaunchKernelGGL(kj_write_kernel, dim3((uint32_t)std::min<uint64_t>((groups + 3) / 4, 256 * 32)), dim3(256), 0, ts.stream, p, n_rows);
+            HIPCHK(hipGetLastError()); return PF_OK;
+        }));
+    }
+    HIPCHK(hipMemcpyAsync(&err, p.err, 4, hipMemcpyDeviceToHost, ts.stream));
+    HIPCHK(hipStreamSynchronize(ts.stream));
+    if (n_rows) ts.add_elapsed(&ms);
+    j->write_ms += ms;
+    if (err) return fail(PF_ERR_STATE, "pf_kmerjoin_join: a row of the bunch is not one the survey passed (flags 0x%x): the file has changed", err);
+    j->out_bytes = n_bytes;
+    if (mode == 2) j->raw_rows += n_rows; else j->rows_written += n_rows;
+    return PF_OK;
+}
+
+// the row filter's member stages for a block of members: the text in rf.text.d_text, lines of [c.skip, c.n) for `work`
+template <class F> int kj_members(pf_kmerjoin* j, const char* members, uint64_t nbytes, int last, uint64_t* consumed, int* taken, F&& work) {
+    pf_rowfilter* f = &j->rf;
+    *consumed = 0; *taken = 0;
+    RfMembers c{reinterpret_cast<const uint8_t*>(members), nbytes, last != 0};
+    bool refused = false;
+    PFCHK(rf_members_plan(f, c, &refused));
+    if (refused || c.none_yet) { *taken = !refused; return PF_OK; }
+    PFCHK(rf_members_inflate(f, c, &refused));
+    if (!refused) PFCHK(rf_members_header(f, c, &refused));
+    if (refused) return PF_OK;
+    f->gz_members += c.take; f->gz_text_bytes += c.text_n;
+    PFCHK(work(c.n, c.skip));
+    PFCHK(rf_members_save_carry(f, c));
+    *consumed = c.used; *taken = 1;
+    return PF_OK;
+}
+
+template <class T> int kj_upload(DevBuf& d, const std::vector<T>& v) {
+    PFCHK(d.ensure(std::max<size_t>(v.size() * sizeof(T), 16), true));
+    if (!v.empty()) HIPCHK(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return PF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pf_kmerjoin_destroy(pf_kmerjoin* j) {
+    if (!j) return;
+    (void)hipSetDevice(j->rf.device);
+    if (j->rf.ts.stream) (void)hipStreamSynchronize(j->rf.ts.stream);      // (a piece of text may be on its way down)
+    delete j;
+}
+
+int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* cluster_len, const uint32_t* cluster_bunch,
+                       uint64_t n_clusters, uint32_t n_bunches, const char* const* key_cluster, const uint32_t* key_cluster_len,
+                       const char* const* key_kmer, const uint32_t* key_kmer_len, const char* const* text0, const uint32_t* text0_len,
+                       const char* const* text1, const uint32_t* text1_len, uint64_t n_keys, const char* empty_text,
+                       uint32_t empty_len, pf_kmerjoin** out) {
+    if (!out || (n_clusters && (!clusters || !cluster_len || !cluster_bunch)) || (empty_len && !empty_text) ||
+        (n_keys && (!key_cluster || !key_cluster_len || !key_kmer || !key_kmer_len || !text0 || !text0_len || !text1 || !text1_len)))
+        return fail(PF_ERR_ARG, "pf_kmerjoin_create: null argument");
+    *out = nullptr;
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_kmerjoin_create: no such device");
+    HIPCHK(hipSetDevice(device));
+    std::unique_ptr<pf_kmerjoin, void (*)(pf_kmerjoin*)> j(new pf_kmerjoin(), pf_kmerjoin_destroy);
+    j->rf.device = device; j->rf.first_field = 1;
+    j->n_bunches = std::max<uint32_t>(n_bunches, 1);
+    std::string arena;
+    auto put = [&arena](const char* s, uint32_t n) { const size_t at = arena.size(); arena.append(s, n); return (uint32_t)at; };
+    auto room = [](uint64_t n) { uint64_t cap = 1024; while (cap < 4 * (n + 1)) cap <<= 1; return cap; };
+    auto insert = [](std::vector<unsigned long long>& hash, std::vector<uint32_t>& slot_id, uint64_t h, uint32_t id) {
+        uint64_t slot = h & (hash.size() - 1);                 // (equal hashes take slots of their own: the bytes tell them apart)
+        while (hash[slot] != RF_EMPTY) slot = (slot + 1) & (hash.size() - 1);
+        hash[slot] = h; slot_id[slot] = id;
+    };
+    j->empty_off = put(empty_text, empty_len); j->empty_len = empty_len;
+    // the selected clusters (one that comes twice keeps its first bunch)
+    std::vector<KjCluster> cl;
+    std::vector<unsigned long long> chash(j->ccap = room(n_clusters), RF_EMPTY);
+    std::vector<uint32_t> cslot(j->ccap, 0);
+    std::unordered_set<std::string> seen;
+    for (uint64_t i = 0; i < n_clusters; i++) {
+        if (cluster_len[i] >= RF_MAX_FIELD || cluster_bunch[i] >= j->n_bunches) continue;      // cannot match, as in the row filter
+        if (!seen.emplace(clusters[i], cluster_len[i]).second) continue;
+        insert(chash, cslot, rf_hash(clusters[i], cluster_len[i]), (uint32_t)cl.size());
+        cl.push_back(KjCluster{put(clusters[i], cluster_len[i]), cluster_len[i], cluster_bunch[i]});
+    }
+    // the keys: the hash runs over cluster, a tab, k-mer
+    std::vector<KjKey> keys;
+    std::vector<unsigned long long> khash(j->kcap = room(n_keys), RF_EMPTY);
+    std::vector<uint32_t> kslot(j->kcap, 0);
+    seen.clear();
+    for (uint64_t i = 0; i < n_keys; i++) {
+        if (key_cluster_len[i] >= RF_MAX_FIELD || key_kmer_len[i] >= RF_MAX_FIELD) continue;
+        // (a thread's rows -- 17 at most, of KJ_MAX_LINE bytes and a text each -- are counted in 32 bits)
+        if (text0_len[i] >= (1u << 24) || text1_len[i] >= (1u << 24)) return fail(PF_ERR_CAPACITY, "pf_kmerjoin_create: a key's text takes 16 MiB or more");
+        std::string both(key_cluster[i], key_cluster_len[i]);
+        both.push_back('\t'); both.append(key_kmer[i], key_kmer_len[i]);
+        if (!seen.insert(both).second) return fail(PF_ERR_ARG, "pf_kmerjoin_create: key %llu comes twice", (unsigned long long)i);
+        insert(khash, kslot, rf_hash(both.data(), both.size()), (uint32_t)keys.size());
+        KjKey k{};
+        k.cl_off = put(key_cluster[i], key_cluster_len[i]); k.cl_len = key_cluster_len[i];
+        k.km_off = put(key_kmer[i], key_kmer_len[i]); k.km_len = key_kmer_len[i];
+        k.t_off[0] = put(text0[i], text0_len[i]); k.t_len[0] = text0_len[i];
+        k.t_off[1] = put(text1[i], text1_len[i]); k.t_len[1] = text1_len[i];
+        keys.push_back(k);
+    }
+    if (arena.size() >= (1ull << 32)) return fail(PF_ERR_CAPACITY, "pf_kmerjoin_create: the keys and their texts take 4 GiB or more");
+    j->counters.assign((size_t)j->n_bunches * KJ_COUNTERS, 0);
+    PFCHK(j->rf.ts.create());
+    PFCHK(kj_upload(j->d_chash, chash)); PFCHK(kj_upload(j->d_cslot, cslot)); PFCHK(kj_upload(j->d_clusters, cl));
+    PFCHK(kj_upload(j->d_khash, khash)); PFCHK(kj_upload(j->d_kslot, kslot)); PFCHK(kj_upload(j->d_keys, keys));
+    PFCHK(kj_upload(j->d_arena, std::vector<char>(arena.begin(), arena.end())));
+    PFCHK(kj_upload(j->d_counters, j->counters));
+    PFCHK(kj_upload(j->d_misc, std::vector<uint64_t>(3, 0)));
+    *out = j.release();
+    return PF_OK;
+}
+
+int pf_kmerjoin_survey(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint64_t* consumed) {
+    if (!j || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_kmerjoin_survey: null argument");
+    HIPCHK(hipSetDevice(j->rf.device));
+    const uint64_t n = *consumed = BlockText::complete_lines(text, nbytes);
+    if (!n) return PF_OK;
+    PFCHK(j->rf.text.upload(j->rf.ts.stream, text, n));
+    return kj_survey_device(j, n, 0);
+}
+
+int pf_kmerjoin_members_begin(pf_kmerjoin* j, int header) {
+    if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_members_begin: null argument");
+    return pf_rowfilter_members_begin(&j->rf, header);
+}
+
+int pf_kmerjoin_members_header(pf_kmerjoin* j, const char** line, uint64_t* nbytes) {
+    if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_members_header: null argument");
+    return pf_rowfilter_members_header(&j->rf, line, nbytes);
+}
+
+int pf_kmerjoin_survey_members(pf_kmerjoin* j, const char* members, uint64_t nbytes, int last, uint64_t* consumed, int* taken) {
+    if (!j || !consumed || !taken || (nbytes && !members)) return fail(PF_ERR_ARG, "pf_kmerjoin_survey_members: null argument");
+    HIPCHK(hipSetDevice(j->rf.device));
+    return kj_members(j, members, nbytes, last, consumed, taken, [j](uint64_t n, uint64_t skip) { return kj_survey_device(j, n, skip); });
+}
+
+int pf_kmerjoin_reset_counters(pf_kmerjoin* j) {
+    if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_reset_counters: null argument");
+    HIPCHK(hipSetDevice(j->rf.device));
+    HIPCHK(hipMemset(j->d_counters.p, 0, j->counters.size() * 8));
+    return PF_OK;
+}
+
+int pf_kmerjoin_counters(pf_kmerjoin* j, const uint64_t** counters, uint32_t* n_bunches) {
+    if (!j || !counters || !n_bunches) return fail(PF_ERR_ARG, "pf_kmerjoin_counters: null argument");
+    HIPCHK(hipSetDevice(j->rf.device));
+    HIPCHK(hipMemcpy(j->counters.data(), j->d_counters.p, j->counters.size() * 8, hipMemcpyDeviceToHost));
+    *counters = j->counters.data(); *n_bunches = j->n_bunches;
+    return PF_OK;
+}
+
+int pf_kmerjoin_join(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint32_t bunch, int mode, uint64_t* out_bytes, uint64_t* consumed) {
+    if (!j || !out_bytes || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_kmerjoin_join: null argument");
+    HIPCHK(hipSetDevice(j->rf.device));
+    *out_bytes = 0; j->out_bytes = j->out_pos = j->flying = 0;
+    const uint64_t n = *consumed = BlockText::complete_lines(text, nbytes);
+    if (!n) return PF_OK;
+    PFCHK(j->rf.text.upload(j->rf.ts.stream, text, n));
+    PFCHK(kj_join_device(j, n, 0, bunch, mode));
+    *out_bytes = j->out_bytes;
+    return PF_OK;
+}
+
+int pf_kmerjoin_join_members(pf_kmerjoin* j, const char* members, uint64_t nbytes, int last, uint32_t bunch, int mode,
+                             uint64_t* out_bytes, uint64_t* consumed, int* taken) {
+    if (!j || !out_bytes || !consumed || !taken || (nbytes && !members)) return fail(PF_ERR_ARG, "pf_kmerjoin_join_members: null argument");
+    HIPCHK(hipSetDevice(j->rf.device));
+    *out_bytes = 0; j->out_bytes = j->out_pos = j->flying = 0;
+    PFCHK(kj_members(j, members, nbytes, last, consumed, taken,
+                     [j, bunch, mode](uint64_t n, uint64_t skip) { return kj_join_device(j, n, skip, bunch, mode); }));
+    *out_bytes = j->out_bytes;
+    return PF_OK;
+}
+
+int pf_kmerjoin_next_text(pf_kmerjoin* j, const char** piece, uint64_t* nbytes) {
+    if (!j || !piece || !nbytes) return fail(PF_ERR_ARG, "pf_kmerjoin_next_text: null argument");
+    HIPCHK(hipSetDevice(j->rf.device));
+    *piece = nullptr; *nbytes = 0;
+    hipStream_t st = j->rf.ts.stream;
+    auto start = [&]() -> int {                    // the next piece on its way into pin[cur]
+        j->flying = std::min<uint64_t>(KJ_PIECE, j->out_bytes - j->out_pos);
+        if (!j->flying) return PF_OK;
+        PFCHK(j->pin[j->cur].ensure((size_t)std::min<uint64_t>(KJ_PIECE, j->out_bytes), true));
+        HIPCHK(hipMemcpyAsync(j->pin[j->cur].p, j->d_out.as<char>() + j->out_pos, (size_t)j->flying, hipMemcpyDeviceToHost, st));
+        j->out_pos += j->flying;
+        return PF_OK;
+    };
+    if (!j->flying) PFCHK(start());
+    if (!j->flying) return PF_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    *piece = j->pin[j->cur].as<char>(); *nbytes = j->flying;
+    j->cur ^= 1;
+    return start();                                // (into the other buffer, while the caller writes this one)
+}
+
+int pf_kmerjoin_stats(pf_kmerjoin* j, uint64_t stats[8], float ms[3]) {
+    if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_stats: null argument");
+    HIPCHK(hipSetDevice(j->rf.device));
+    if (stats) {
+        uint64_t misc[3] = {0, 0, 0};                          // rejects, err, unmatched
+        HIPCHK(hipMemcpy(misc, j->d_misc.p, sizeof misc, hipMemcpyDeviceToHost));
+        stats[0] = j->bytes_scanned; stats[1] = j->rows_written; stats[2] = j->raw_rows; stats[3] = j->rf.gz_members;
+        stats[4] = j->rf.gz_text_bytes; stats[5] = j->rf.dec.device_bytes(); stats[6] = misc[0]; stats[7] = misc[2];
+    }
+    if (ms) { ms[0] = j->survey_ms; ms[1] = j->write_ms; ms[2] = j->rf.gz_ms; }
+    return PF_OK;
+}
+
+}  // extern "C"
+
 #ifdef PF_WEAK_HASH
 extern "C" {
 // weak-hash test build only (not part of the ABI): this file's share of pf_debug_set_hash_mask / pf_debug_weakhash_counts

@@ -11,6 +11,13 @@ device-gzipped file, csrc/pf_rowfilter.hip); the small
 tables that remain (the associations, the kept rows) go through the same pandas statements as the reference's, so the
 printed tables are the same bytes.  There is no CPU fallback for the filter.
 
+panfeed-get-kmers' second step, the join of every kmers.tsv row of a bunch of clusters to the small table of passing
+(cluster, k-mer) pairs, runs on the GPU as well (`KmerJoin` -> pf_kmerjoin_*): pandas renders the small table's columns
+as text once per key (`rendered_texts`), one survey pass over kmers.tsv counts every bunch's rows and tells whether
+pandas could print any of them other than as they stand, and one pass per bunch writes the annotated rows on the device.
+A bunch the survey flags, and a run whose table the device cannot take, goes through the pandas statements of the
+reference (`--host-join` sends everything there).
+
 One thing the reference leaves to chance is kept out of the comparison: it iterates over Python `set`s of cluster
 names, so the order of its printed clusters / blocks changes with PYTHONHASHSEED.  Here clusters come in order of their
 first appearance in kmers_to_hashes.tsv.
@@ -158,6 +165,206 @@ class RowFilter:
         return header, b"".join(out)
 
 
+KJ_FLAG_NAMES = ((1, "not 10 tabs"), (2, "a control, non-ASCII or quote byte"), (4, "an integer field that is not canonical decimal"),
+                 (8, "an empty text field"), (16, "an NA string"), (32, "a text field of number characters only"),
+                 (64, "inf / nan / true / false"), (128, "a row over 65 536 or a field of 4 096 bytes or more"))
+KJ_RAW = 2                          # KmerJoin.join_file's mode: the rows that have a key, as they stand
+
+
+def _gz_members_file(path):
+    """whether the file is a .gz whose first bytes are the only header the device decoder takes"""
+    if not str(path).endswith(".gz"):
+        return False
+    with open(path, "rb") as fh:
+        return fh.read(10)[:4] == GZ_HEAD
+
+
+class KmerJoin:
+    """the rows of kmers.tsv whose cluster is a selected one, annotated with the rendered text of their (cluster, k-mer)
+    on the device.  clusters: (literal bytes, bunch number) pairs; keys: (cluster bytes, k-mer bytes) pairs with their two
+    renderings text0 / text1; empty: the text of a row that has no key"""
+
+    device_bunches = 0              # bunches, over all joins, written by the device
+    host_bunches = 0                # bunches the survey flagged: joined by pandas
+    host_runs = 0                   # runs whose table the device route refused: every bunch joined by pandas
+    device_gunzip_files = 0         # passes over a file that went the device gunzip route to their end
+    fallback_files = 0              # and passes the automatic mode began there and read again through gzip
+    last_stats = None               # stats() of the last run's join, with the survey's rows and unmatched rows over all bunches
+
+    def __init__(self, clusters, n_bunches, keys, text0, text1, empty, device=0):
+        self.L = _lib.load()
+        self.h = C.c_void_p()
+        self.n_bunches = max(int(n_bunches), 1)
+        self.members = {}               # path -> whether the survey went the device gunzip route to the end
+
+        def strs(items):
+            n = max(len(items), 1)
+            return (C.c_char_p * n)(*items), (C.c_uint32 * n)(*[len(x) for x in items])
+
+        cl, cl_len = strs([c for c, _ in clusters])
+        bunch = (C.c_uint32 * max(len(clusters), 1))(*[b for _, b in clusters])
+        kc, kc_len = strs([c for c, _ in keys])
+        kk, kk_len = strs([k for _, k in keys])
+        t0, t0_len = strs(list(text0))
+        t1, t1_len = strs(list(text1))
+        _lib.check(self.L.pf_kmerjoin_create(int(device), cl, cl_len, bunch, len(clusters), self.n_bunches, kc, kc_len, kk, kk_len,
+                                             t0, t0_len, t1, t1_len, len(keys), empty, len(empty), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.L.pf_kmerjoin_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    def stats(self):
+        st, ms = (C.c_uint64 * 8)(), (C.c_float * 3)()
+        _lib.check(self.L.pf_kmerjoin_stats(self.h, st, ms))
+        return {"bytes_scanned": int(st[0]), "rows_written": int(st[1]), "raw_rows": int(st[2]), "members_inflated": int(st[3]),
+                "text_bytes_inflated": int(st[4]), "inflate_device_bytes": int(st[5]), "hash_rejects": int(st[6]),
+                "unmatched_written": int(st[7]),
+                "survey_ms": float(ms[0]), "write_ms": float(ms[1]), "inflate_ms": float(ms[2])}
+
+    def counters(self):
+        """per bunch: rows, unmatched rows, output bytes under either rendering, plainness flags"""
+        p, n = C.POINTER(C.c_uint64)(), C.c_uint32()
+        _lib.check(self.L.pf_kmerjoin_counters(self.h, C.byref(p), C.byref(n)))
+        return [{"rows": int(p[5 * i]), "unmatched": int(p[5 * i + 1]), "bytes": (int(p[5 * i + 2]), int(p[5 * i + 3])),
+                 "flags": int(p[5 * i + 4])} for i in range(n.value)]
+
+    def _drain(self, write):
+        """hand the text the last join call made to write(), piece by piece"""
+        piece, n = C.c_void_p(), C.c_uint64()
+        while True:
+            _lib.check(self.L.pf_kmerjoin_next_text(self.h, C.byref(piece), C.byref(n)))
+            if not n.value:
+                return
+            write(memoryview((C.c_char * n.value).from_address(piece.value)))
+
+    def _pass_members(self, path, block_bytes, call, write):
+        """one pass over a file of device members; False, with the library's reason logged, when a block was not taken"""
+        block = max(1, block_bytes or BLOCK_BYTES // GZ_BLOCK_DIVISOR)
+        _lib.check(self.L.pf_kmerjoin_members_begin(self.h, 1))
+        with open(path, "rb") as fh:
+            carry, eof = b"", False
+            while True:
+                if not eof:
+                    chunk = fh.read(block)
+                    eof = len(chunk) < block
+                    carry = carry + chunk if carry else chunk
+                used, taken = C.c_uint64(), C.c_int()
+                call(carry, len(carry), 1 if eof else 0, used, taken)
+                if not taken.value:
+                    logger.debug("%s: %s", path, self.L.pf_last_error().decode(errors="replace"))
+                    return False
+                if write:
+                    self._drain(write)
+                carry = carry[used.value:]
+                if eof and not carry:
+                    return True
+
+    def _pass_plain(self, path, block_bytes, call, write):
+        def scan(buf, n):
+            used = C.c_uint64()
+            call((C.c_char * len(buf)).from_buffer(buf), n, used)
+            if write:
+                self._drain(write)
+            return int(used.value)
+
+        with open_table(path) as fh:
+            fh.readline()                            # the header line
+            scan_lines(fh, scan, block_bytes)
+
+    def survey_file(self, path, block_bytes=None, device_gunzip=None):
+        """one pass over kmers.tsv for all bunches: counters().  device_gunzip as RowFilter.filter_file's"""
+        auto = device_gunzip is None
+        if auto:
+            device_gunzip = _gz_members_file(path)
+        self.members[path] = False
+        if device_gunzip:
+            def call(data, n, last, used, taken):
+                _lib.check(self.L.pf_kmerjoin_survey_members(self.h, data, n, last, C.byref(used), C.byref(taken)))
+            if self._pass_members(path, block_bytes, call, None):
+                KmerJoin.device_gunzip_files += 1
+                self.members[path] = True
+                return self.counters()
+            if not auto:
+                raise NotTaken(f"{path}: {self.L.pf_last_error().decode(errors='replace')}")
+            KmerJoin.fallback_files += 1
+            _lib.check(self.L.pf_kmerjoin_reset_counters(self.h))
+        self._pass_plain(path, block_bytes, lambda ptr, n, used: _lib.check(self.L.pf_kmerjoin_survey(self.h, ptr, n, C.byref(used))), None)
+        return self.counters()
+
+    def join_file(self, path, bunch, mode, write, block_bytes=None):
+        """one pass over kmers.tsv for one bunch: its annotated rows (mode 0 / 1: the rendering) or its raw rows that have
+        a key (KJ_RAW) go to write(), in file order.  The file goes the way the survey found for it."""
+        if self.members.get(path):
+            def call(data, n, last, used, taken):
+                out_n = C.c_uint64()
+                _lib.check(self.L.pf_kmerjoin_join_members(self.h, data, n, last, bunch, mode, C.byref(out_n), C.byref(used), C.byref(taken)))
+            if not self._pass_members(path, block_bytes, call, write):
+                raise NotTaken(f"{path}: {self.L.pf_last_error().decode(errors='replace')} (the survey pass took the file)")
+            KmerJoin.device_gunzip_files += 1
+            return
+
+        def call(ptr, n, used):
+            out_n = C.c_uint64()
+            _lib.check(self.L.pf_kmerjoin_join(self.h, ptr, n, bunch, mode, C.byref(out_n), C.byref(used)))
+        self._pass_plain(path, block_bytes, call, write)
+
+
+def _isnan(v):
+    return isinstance(v, float) and v != v
+
+
+def rendered_texts(B, other_columns):
+    """What the device join prints for the columns of B (indexed by cluster, k-mer), taken from pandas itself: B is
+    joined (`how="right"`) to a probe frame of one row per key and one dummy integer column, printed, and the key and
+    dummy fields are cut off each line -- once as it is (text0) and once with a probe row that has no key in B, which
+    makes pandas promote B's integer columns to float and its bool columns to object as an unmatched kmers.tsv row does
+    (text1).  Keys that hold a NaN match no plain row and are left out.
+    -> dict(keys, text0, text1, empty, header), or a str: why the device route cannot take this table"""
+    keys = [k for k in B.index.tolist() if not (_isnan(k[0]) or _isnan(k[1]))]
+    if len(set(keys)) != len(keys):
+        return "the table has a (cluster, k-mer) twice"
+    if not all(isinstance(c, str) and isinstance(k, str) for c, k in keys):
+        return "a cluster or k-mer of the table is not text"
+    clash = set(B.columns) & (set(other_columns) | {"cluster", "k-mer"})
+    if clash:
+        return f"column {sorted(clash)[0]!r} is in both tables"
+    dummy = "probe"
+    while dummy in B.columns:
+        dummy += "_"
+    nokey = "!"
+    while any(c == nokey for c, _ in keys):
+        nokey += "!"
+    texts = []
+    for extra in ([], [(nokey, nokey)]):
+        probe_keys = keys + extra
+        if not probe_keys:
+            texts.append(([], None))
+            continue
+        probe = pd.DataFrame({dummy: 0}, index=pd.MultiIndex.from_tuples(probe_keys, names=["cluster", "k-mer"]))
+        lines = B.join(probe, how="right").to_csv(sep="\t", header=True).split("\n")
+        if len(lines) != len(probe_keys) + 2 or lines[-1] != "" or not lines[0].endswith("\t" + dummy):
+            return "the table's text has line breaks of its own"
+        got = []
+        for (c, k), line in zip(probe_keys, lines[1:]):
+            prefix = f"{c}\t{k}\t"
+            if not (line.startswith(prefix) and line.endswith("\t0") and len(line) >= len(prefix) + 2):
+                return f"pandas does not print the key ({c!r}, {k!r}) as it stands"
+            got.append(line[len(prefix):-2].encode())
+        texts.append((got, lines[0]))
+    (text0, _), (text1, header) = texts
+    empty = text1.pop()
+    if empty != b"\t" * (len(B.columns) - 1):
+        return "the text of a row without a key is not empty fields"
+    if max([len(t) for t in text0 + text1] + [0]) >= 1 << 20:
+        return "a key's text is 1 MiB or more"
+    header = header[:-len(dummy)] + "\t".join(other_columns) + "\n"
+    return {"keys": keys, "text0": text0, "text1": text1, "empty": empty, "header": header}
+
+
 def open_table(path):
     """a TSV file for reading bytes (.gz through gzip, as pandas does by the name)"""
     return (gzip.open if str(path).endswith(".gz") else open)(path, "rb")
@@ -200,7 +407,11 @@ def _options(description, kmers):
     p.add_argument("-o", "--output", default=None)
     if kmers:
         p.add_argument("--only-passing", action="store_true", default=False)
-        p.add_argument("--clusters-per-iteration", type=int, default=15)
+        p.add_argument("--clusters-per-iteration", type=int, default=15,
+                       help="clusters joined per pass over kmers.tsv (memory does not grow with it: a value as large as the "
+                            "number of clusters makes the whole run two passes over the file, one survey and one join)")
+        p.add_argument("--host-join", action="store_true", default=False,
+                       help="join kmers.tsv to the associations in pandas, bunch by bunch (by default the GPU looks the rows up and writes them)")
     p.add_argument("-v", action="count", default=0)
     p.add_argument("--device", type=int, default=0, help="GPU the row filter runs on")
     p.add_argument("--host-gunzip", action="store_true", default=False,
@@ -276,19 +487,91 @@ def get_kmers(argv=None, out=None):
     literal = {}
     for val, lit in zip(h["cluster"].tolist(), _first_fields(rows)):
         literal.setdefault(_key(val), {})[lit] = None
-    first = True
     b = a.join(h, how="inner") if clusters else None                       # get_kmers.py:136
-    for idx in range(0, len(clusters), args.clusters_per_iteration):
-        bunch = clusters[idx: idx + args.clusters_per_iteration]
-        # (a NaN among the bunch selects nothing: the reference's `x['cluster'].isin(bunch)`, get_kmers.py:131-134, is False
-        # for a NaN cell when the bunch is a list of the column's unique() values -- such rows are dropped, not matched)
-        kheader, krows = _filtered([lit for c in bunch if c is not _NAN_KEY for lit in literal[_key(c)]], True, args.kmers, args)
-        k = _table(kheader, krows).set_index(["cluster", "k-mer"])
-        how = "left" if args.only_passing else "right"                      # get_kmers.py:137-141
-        t = b.reset_index().set_index(["cluster", "k-mer"]).join(k, how=how)
-        t.to_csv(out, sep="\t", header=first)
-        first = False
+    bunches = [clusters[idx: idx + args.clusters_per_iteration] for idx in range(0, len(clusters), args.clusters_per_iteration)]
+    # (a NaN among the bunch selects nothing: the reference's `x['cluster'].isin(bunch)`, get_kmers.py:131-134, is False
+    # for a NaN cell when the bunch is a list of the column's unique() values -- such rows are dropped, not matched)
+    bunch_keys = [[lit for c in bunch if c is not _NAN_KEY for lit in literal[_key(c)]] for bunch in bunches]
+    join, plan = (None, None) if args.host_join or not bunches else _device_join(args, b, bunch_keys)
+    first = True
+    try:
+        for n, keys in enumerate(bunch_keys):
+            if join is not None and not plan[n]["flags"]:
+                first = _device_bunch(args, join, plan, n, b, out, first)
+                KmerJoin.device_bunches += 1
+                continue
+            if join is not None:
+                KmerJoin.host_bunches += 1
+                logger.debug("bunch %d goes through pandas: %s", n, ", ".join(t for f, t in KJ_FLAG_NAMES if plan[n]["flags"] & f))
+            kheader, krows = _filtered(keys, True, args.kmers, args)
+            k = _table(kheader, krows).set_index(["cluster", "k-mer"])
+            how = "left" if args.only_passing else "right"                      # get_kmers.py:137-141
+            t = b.reset_index().set_index(["cluster", "k-mer"]).join(k, how=how)
+            t.to_csv(out, sep="\t", header=first)
+            first = False
+    finally:
+        if join is not None:
+            KmerJoin.last_stats = dict(join.stats(), rows=sum(c["rows"] for c in plan), unmatched=sum(c["unmatched"] for c in plan))
+            join.close()
     return 0
+
+
+def _device_join(args, b, bunch_keys):
+    """(a KmerJoin over the run's table, the survey's counters per bunch), or (None, None) with the reason logged when the
+    device route cannot take the run"""
+    from .engine import KMERS_TSV_HEADER
+    columns = KMERS_TSV_HEADER.rstrip("\n").split("\t")
+    with open_table(args.kmers) as fh:
+        header = fh.readline()
+    texts = "kmers.tsv does not have the header panfeed writes" if header != KMERS_TSV_HEADER.encode() else None
+    if texts is None:
+        B = b.reset_index().set_index(["cluster", "k-mer"])
+        texts = rendered_texts(B, columns[1:10])
+    if not isinstance(texts, str):
+        literals = {lit for keys in bunch_keys for lit in keys}
+        if not all(c.encode() in literals for c, _ in texts["keys"]):
+            texts = "a cluster of the table is not printed as kmers_to_hashes spells it"
+    if isinstance(texts, str):
+        logger.debug("the join goes through pandas: %s", texts)
+        KmerJoin.host_runs += 1
+        return None, None
+    join = KmerJoin([(lit, n) for n, keys in enumerate(bunch_keys) for lit in keys], len(bunch_keys),
+                    [(c.encode(), k.encode()) for c, k in texts["keys"]], texts["text0"], texts["text1"], texts["empty"],
+                    device=args.device)
+    try:
+        plan = join.survey_file(args.kmers, device_gunzip=False if args.host_gunzip else None)
+    except BaseException:
+        join.close()
+        raise
+    join.header = texts["header"]
+    return join, plan
+
+
+def _writer(out):
+    """bytes -> out: to its .buffer when it has one that takes UTF-8 as it is"""
+    raw = getattr(out, "buffer", None)
+    if raw is not None and str(getattr(out, "encoding", "")).lower().replace("-", "").replace("_", "") == "utf8":
+        out.flush()
+        return raw.write
+    return lambda piece: out.write(bytes(piece).decode())
+
+
+def _device_bunch(args, join, plan, n, b, out, first):
+    """one bunch by the device route; -> `first` for the next bunch"""
+    if not args.only_passing:
+        if first:
+            out.write(join.header)
+        # (an unmatched row makes pandas promote the table's integer columns: the survey counted them)
+        join.join_file(args.kmers, n, 1 if plan[n]["unmatched"] else 0, _writer(out))
+        return False
+    # how="left" stays a pandas join, over the rows of the bunch that have a key only: a left join drops the others
+    kept = []
+    join.join_file(args.kmers, n, KJ_RAW, lambda piece: kept.append(bytes(piece)))
+    from .engine import KMERS_TSV_HEADER
+    k = _table(KMERS_TSV_HEADER.encode(), b"".join(kept)).set_index(["cluster", "k-mer"])
+    t = b.reset_index().set_index(["cluster", "k-mer"]).join(k, how="left")
+    t.to_csv(out, sep="\t", header=first)
+    return False
 
 
 def main_get_clusters():

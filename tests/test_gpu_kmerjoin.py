@@ -1,0 +1,312 @@
+"""panfeed-get-kmers' device join (downstream.KmerJoin -> pf_kmerjoin_*): the survey, plan, place and write kernels of
+csrc/pf_rowfilter.hip against the host route (--host-join: the reference's pandas statements) and against the model of
+tests/join_tables.py.  No expected text comes from the device route itself."""
+import gzip
+import io
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+from conftest import GOLDEN, REPO, all_cases
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import join_tables as jt  # noqa: E402
+from device_gz_files import write_device_gz  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+with gzip.open(os.path.join(GOLDEN, "n4.json.gz"), "rb") as _fh:
+    FIX = json.loads(_fh.read().decode())["fixtures"]
+CASES = {c["name"]: c for c in all_cases()}
+RUNS = [(f["case"], i) for f in FIX for i, r in enumerate(f["runs"]) if r["tool"] == "get_kmers"]
+WORKER_TIMEOUT_S = 240
+
+
+def _get_kmers(argv):
+    from panfeed_amd import downstream
+    out = io.StringIO()
+    rc = 0
+    try:
+        rc = downstream.get_kmers(argv, out=out)
+    except SystemExit as e:
+        rc = int(e.code or 0)
+    return out.getvalue(), rc
+
+
+def _routes():
+    from panfeed_amd.downstream import KmerJoin
+    return KmerJoin.device_bunches, KmerJoin.host_bunches, KmerJoin.host_runs
+
+
+def _moved(before):
+    return tuple(b - a for a, b in zip(before, _routes()))
+
+
+def _golden_files(tmp_path, fx, write=None):
+    """the fixture's three files; write(path, text bytes) -> path makes each of the two tables (default: plain)"""
+    exp = CASES[fx["case"]]["expect"]
+    paths = {}
+    for name in ("kmers.tsv", "kmers_to_hashes.tsv"):
+        if write is None:
+            (tmp_path / name).write_text(exp[name])
+            paths[name] = str(tmp_path / name)
+        else:
+            paths[name] = write(str(tmp_path / name), exp[name].encode())
+    (tmp_path / "assoc.tsv").write_text(fx["associations"])
+    return paths, str(tmp_path / "assoc.tsv")
+
+
+def _n_bunches(run):
+    el = run["stdout"].splitlines()
+    n_clusters = len({ln.split("\t")[0] for ln in el[1:]})
+    cpi = int(run["args"][run["args"].index("--clusters-per-iteration") + 1]) if "--clusters-per-iteration" in run["args"] else 15
+    return n_clusters, cpi
+
+
+def _same_as_reference(got, run):
+    """the comparison of test_gpu_n4.py"""
+    gl, el = got.splitlines(), run["stdout"].splitlines()
+    assert gl[:1] == el[:1]
+    assert sorted(gl[1:]) == sorted(el[1:])
+    n_clusters, cpi = _n_bunches(run)
+    if n_clusters <= cpi and "--only-passing" not in run["args"]:
+        assert got == run["stdout"]
+
+
+@pytest.mark.parametrize("case,i", RUNS, ids=[f"{c}-{i}" for c, i in RUNS])
+def test_golden_runs_go_the_device_route(tmp_path, case, i):
+    fx = next(f for f in FIX if f["case"] == case)
+    run = fx["runs"][i]
+    paths, pa = _golden_files(tmp_path, fx)
+    argv = ["-a", pa, "-p", paths["kmers_to_hashes.tsv"], "-k", paths["kmers.tsv"]] + run["args"]
+    before = _routes()
+    got, rc = _get_kmers(argv)
+    device, host, refused = _moved(before)
+    assert rc == run["rc"]
+    _same_as_reference(got, run)
+    assert host == 0 and refused == 0
+    assert (device > 0) == bool(run["stdout"])
+    if "--only-passing" in run["args"] and run["stdout"]:
+        from panfeed_amd.downstream import KmerJoin
+        st = KmerJoin.last_stats
+        print(st)
+        assert st["rows_written"] == 0 and st["raw_rows"] == st["rows"] - st["unmatched"]
+        kmers_rows = len(jt.rows_of(CASES[case]["expect"]["kmers.tsv"].encode()))
+        assert (st["rows"] > 0) == (kmers_rows > 0)     # (two of the golden cases have no target strain: kmers.tsv is its header)
+        if kmers_rows:
+            assert 0 < st["raw_rows"] < st["rows"]      # fewer raw rows came down than the bunches hold
+        before = _routes()
+        assert _get_kmers(argv + ["--host-join"])[0] == got
+        assert _moved(before) == (0, 0, 0)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from panfeed_amd.engine import Engine
+    e = Engine(klength=21, max_strains=32)
+    yield e
+    e.close()
+
+
+def _write_host_gz(path, text):
+    from panfeed_amd.output import ParallelGzipWriter
+    w = ParallelGzipWriter(path + ".gz", chunk_bytes=65536)
+    w.write(text.decode())
+    w.close()
+    return path + ".gz"
+
+
+@pytest.mark.parametrize("how", ["blocks", "host_gz", "device_gz"])
+def test_golden_runs_over_small_blocks_and_gzip_inputs(tmp_path, eng, how):
+    from panfeed_amd import downstream
+    from panfeed_amd.downstream import KmerJoin
+    fx = FIX[0]
+
+    def device_gz(path, text):
+        cut = text.index(b"\n") + 1
+        write_device_gz(eng, path + ".gz", text[:cut], text[cut:])
+        return path + ".gz"
+
+    paths, pa = _golden_files(tmp_path, fx, {"blocks": None, "host_gz": _write_host_gz, "device_gz": device_gz}[how])
+    old = downstream.BLOCK_BYTES
+    try:
+        for blk in (257, 4096) if how == "blocks" else (4096, old):
+            downstream.BLOCK_BYTES = blk
+            for run in (r for r in fx["runs"] if r["tool"] == "get_kmers" and r["stdout"]):
+                before, gz_before = _routes(), (KmerJoin.device_gunzip_files, KmerJoin.fallback_files)
+                got, rc = _get_kmers(["-a", pa, "-p", paths["kmers_to_hashes.tsv"], "-k", paths["kmers.tsv"]] + run["args"])
+                assert rc == 0
+                _same_as_reference(got, run)
+                device, host, refused = _moved(before)
+                assert device > 0 and host == 0 and refused == 0, (blk, run["args"])
+                st = KmerJoin.last_stats
+                if how == "device_gz":
+                    assert KmerJoin.device_gunzip_files > gz_before[0] and KmerJoin.fallback_files == gz_before[1]
+                    assert st["members_inflated"] > 0 and st["text_bytes_inflated"] >= len(CASES[fx["case"]]["expect"]["kmers.tsv"])
+                else:
+                    assert KmerJoin.device_gunzip_files == gz_before[0] and st["members_inflated"] == 0
+    finally:
+        downstream.BLOCK_BYTES = old
+
+
+def _handmade_files(tmp_path, t):
+    (tmp_path / "assoc.tsv").write_text(t["assoc"])
+    (tmp_path / "kh.tsv").write_bytes(t["kh"])
+    (tmp_path / "kmers.tsv").write_bytes(t["kmers"])
+    return ["-a", str(tmp_path / "assoc.tsv"), "-p", str(tmp_path / "kh.tsv"), "-k", str(tmp_path / "kmers.tsv")]
+
+
+def _against_model_and_host(tmp_path, t, args, threshold=0.5, per=15):
+    """the device route's text; it equals the model's and the host route's, and the bunches went the way the model says"""
+    argv = _handmade_files(tmp_path, t) + ["-t", str(threshold), "--clusters-per-iteration", str(per)] + args
+    model, routes = jt.join_model(str(tmp_path / "assoc.tsv"), t["kh"], t["kmers"], threshold=threshold, per_iteration=per,
+                                  only_passing="--only-passing" in args)
+    before = _routes()
+    got, rc = _get_kmers(argv)
+    moved = _moved(before)
+    host, rc_host = _get_kmers(argv + ["--host-join"])
+    assert rc == 0 == rc_host
+    assert got == model
+    assert got == host
+    assert moved == (sum(routes), len(routes) - sum(routes), 0)
+    return got, routes
+
+
+@pytest.mark.parametrize("per", [1, 2, 15])
+@pytest.mark.parametrize("int_column", [False, True], ids=["text_columns", "int_column"])
+@pytest.mark.parametrize("args", [[], ["--only-passing"]], ids=["right", "left"])
+def test_handmade_table(tmp_path, per, int_column, args):
+    """rows at every offset of a vector, a last row without its newline, clusters and k-mers that are prefixes of one
+    another, a k-mer under another cluster only, bunches with every / no row unmatched, both renderings, more than 256
+    rows in a block with texts of 0 to 300 bytes"""
+    t = jt.handmade(int_column=int_column)
+    assert not t["kmers"].endswith(b"\n") and len(jt.rows_of(t["kmers"])) > 256
+    assert jt.vector_places(t["kmers"]) == (set(range(16)), set(range(16)))
+    got, routes = _against_model_and_host(tmp_path, t, args, per=per)
+    assert all(routes) and len(routes) == {1: 6, 2: 3, 15: 1}[per]
+    from panfeed_amd.downstream import KmerJoin
+    st = KmerJoin.last_stats
+    rows = len(got.splitlines()) - 1
+    if args:
+        assert st["rows_written"] == 0 and 0 < st["raw_rows"] == st["rows"] - st["unmatched"]
+    else:      # selected and absent from kmers.tsv: no row; every written row is counted, the unmatched ones as such
+        assert st["rows_written"] == rows == st["rows"] and st["unmatched_written"] == st["unmatched"] > 0
+
+
+def test_handmade_table_in_many_blocks(tmp_path):
+    """blocks of 300 bytes: every row is a block's first or last at some point, and rows are carried over"""
+    from panfeed_amd import downstream
+    old = downstream.BLOCK_BYTES
+    try:
+        downstream.BLOCK_BYTES = 300
+        _against_model_and_host(tmp_path, jt.handmade(rows_per_cluster=20), [], per=2)
+    finally:
+        downstream.BLOCK_BYTES = old
+
+
+@pytest.mark.parametrize("n", [4095, 4096])
+def test_long_fields(tmp_path, n):
+    """a strain of 4 095 bytes is a field like any other; one of 4 096 sends its bunch through pandas"""
+    t = jt.handmade(rows_per_cluster=6)
+    rows = t["kmers"].split(b"\n")
+    rows[2] = jt.kmers_row("g", "ACG", 1, strain="s" * n)
+    t["kmers"] = b"\n".join(rows)
+    _, routes = _against_model_and_host(tmp_path, t, [], per=1)
+    assert routes == [n == 4095] + [True] * 5
+
+
+def test_empty_key_table(tmp_path):
+    """the only passing rows of kmers_to_hashes have an empty k-mer: clusters are selected, no key is left, every row
+    comes out with empty fields"""
+    t = jt.handmade(rows_per_cluster=6)
+    t["kh"] = jt.KH_HEADER + b"g\t\tH1\nfull\t\tH5\n"
+    got, routes = _against_model_and_host(tmp_path, t, [], per=15)
+    assert routes == [True] and len(got.splitlines()) == 13
+
+
+def test_no_selected_cluster(tmp_path):
+    got, routes = _against_model_and_host(tmp_path, jt.handmade(rows_per_cluster=6), [], threshold=1e-30)
+    assert got == "" and routes == []
+
+
+FLAGGED = {jt.TABS: ("g", "s1", "gene", "NODE_1", "1", "5", "36", "0", "31", "1"),
+           jt.BYTES: ("g", "caf\u00e9", "gene", "NODE_1", "1", "5", "36", "0", "31", "1", "ACG"),
+           jt.INT: ("g", "s1", "gene", "NODE_1", "1", "007", "36", "0", "31", "1", "ACG"),
+           jt.EMPTY: ("g", "s1", "", "NODE_1", "1", "5", "36", "0", "31", "1", "ACG"),
+           jt.NA: ("g", "NA", "gene", "NODE_1", "1", "5", "36", "0", "31", "1", "ACG"),
+           jt.NUMERIC: ("g", "123", "gene", "NODE_1", "1", "5", "36", "0", "31", "1", "ACG"),
+           jt.WORD: ("g", "s1", "gene", "True", "1", "5", "36", "0", "31", "1", "ACG"),
+           jt.LONG: ("g", "s1", "g" * 4096, "NODE_1", "1", "5", "36", "0", "31", "1", "ACG")}
+
+
+@pytest.mark.parametrize("flag", sorted(FLAGGED), ids=[str(f) for f in sorted(FLAGGED)])
+def test_a_flagged_bunch_goes_through_pandas(tmp_path, flag):
+    """one row of cluster g sets exactly this flag: that bunch is joined by pandas, the other five by the device, and the
+    text is the host route's"""
+    row = "\t".join(FLAGGED[flag]).encode()
+    assert jt.plainness(row) == flag
+    t = jt.handmade(rows_per_cluster=6)
+    rows = t["kmers"].split(b"\n")
+    rows.insert(3, row)
+    t["kmers"] = b"\n".join(rows)
+    _, routes = _against_model_and_host(tmp_path, t, [], per=1)
+    assert routes == [False] + [True] * 5
+
+
+def test_out_of_memory_fails_cleanly(tmp_path):
+    """pf_debug_limit_alloc below the join's output buffer and above everything else (the row filter's candidate buffer
+    over kmers_to_hashes.tsv is 8 MiB; texts of up to 200 000 bytes make the 50 KB of kmers.tsv 13 MB of output): the run
+    fails as out of memory, the join closes, and with the limit lifted a fresh run gives the expected text"""
+    from panfeed_amd import _lib
+    limit = 9 << 20
+    t = jt.handmade(long_notes=200000, rows_per_cluster=100)
+    argv = _handmade_files(tmp_path, t) + ["-t", "0.5"]
+    model, routes = jt.join_model(str(tmp_path / "assoc.tsv"), t["kh"], t["kmers"], threshold=0.5)
+    assert routes == [True] and len(model) > limit and 8 * len(t["kmers"]) + 3 * len(t["assoc"]) < limit
+    L = _lib.load()
+    try:
+        _lib.check(L.pf_debug_limit_alloc(limit, None))
+        with pytest.raises(_lib.PanfeedHipError) as ei:
+            _get_kmers(argv)
+        assert ei.value.status == _lib.ERR_OOM
+    finally:
+        _lib.check(L.pf_debug_limit_alloc(0, None))
+    got, rc = _get_kmers(argv)
+    assert rc == 0 and got == model
+
+
+@pytest.fixture(scope="module")
+def weak(tmp_path_factory):
+    """the weak-hash variant's results: one fresh child with its own time limit, never restarted"""
+    out = tmp_path_factory.mktemp("kmerjoin_weakhash")
+    try:
+        p = subprocess.run([sys.executable, os.path.join(REPO, "tests", "kmerjoin_weakhash_worker.py"), str(out)], capture_output=True,
+                           text=True, timeout=WORKER_TIMEOUT_S)
+    except subprocess.TimeoutExpired as e:
+        return {"error": f"kmerjoin_weakhash_worker.py did not finish in {WORKER_TIMEOUT_S} s:\n{(e.stderr or b'')[-4000:]}"}
+    if p.returncode != 0:
+        return {"error": f"kmerjoin_weakhash_worker.py exited with {p.returncode}:\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}"}
+    with open(os.path.join(str(out), "results.json")) as fh:
+        return json.load(fh)
+
+
+@pytest.mark.parametrize("mask", ["0x0", "0x7", "0xffffffffffffffff"])
+def test_keys_are_verified_by_bytes_under_a_weak_hash(weak, tmp_path, mask):
+    """with the text site's hash masked to nothing or to three bits, every look-up meets other clusters' and keys' slots:
+    the bytes decide, the text is the shipped library's, and the join counts the compares that failed; with the hash
+    whole it counts none"""
+    if "error" in weak:
+        pytest.fail(weak["error"], pytrace=False)
+    t = jt.handmade()
+    argv = _handmade_files(tmp_path, t) + ["-t", "0.5", "--clusters-per-iteration", "2"]
+    shipped, rc = _get_kmers(argv)
+    from panfeed_amd.downstream import KmerJoin
+    assert rc == 0 and KmerJoin.last_stats["hash_rejects"] == 0
+    got = weak[mask]
+    print(mask, {k: v for k, v in got.items() if k != "text"})
+    assert got["text"] == shipped
+    assert got["routes"] == [3, 0, 0]
+    assert (got["hash_rejects"] > 0) == (mask != "0xffffffffffffffff")
