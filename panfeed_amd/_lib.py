@@ -348,6 +348,12 @@ def load_pydll():
     return _pydll
 
 
+def c_strings(items):
+    """(char* array, uint32 array of their lengths) for a list of bytes objects; arrays of one unused element for none"""
+    n = max(len(items), 1)
+    return (C.c_char_p * n)(*items), (C.c_uint32 * n)(*[len(x) for x in items])
+
+
 def check(status):
     if status != 0:
         raise PanfeedHipError(status, load().pf_last_error().decode(errors="replace"))

@@ -17,6 +17,7 @@
 #include "../../include/panfeed_hip.h"
 #include "pf_buf.h"
 #include "pf_deflate.h"
+#include "pf_host.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -243,38 +244,171 @@ struct TimedStream {
     void add_elapsed(float* ms) const { float t = 0; if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) *ms += t; }
 };
 
+// ---- TextFeed::members, stage by stage: what a call's plan, inflate and header stages find out
+struct RfMembers {
+    const uint8_t* bytes; uint64_t nbytes; bool last;     // the call's arguments
+    std::vector<pfgz::MemberRef> ms;                     // plan: the members listed; how many of them this call takes,
+    size_t take = 0; uint64_t text_n = 0, used = 0;      // their text's bytes, the compressed bytes they use up; whether the
+    bool end = false, none_yet = false;                  // file's text ends with them; no whole member yet: the caller reads on
+    uint64_t total = 0, n = 0;     // inflate: d_text[0 .. total) is the carried line and the members' text, [0 .. n) its complete lines
+    uint64_t skip = 0;             // header: the header line's bytes: no line of it is a row
+    bool refused = false;          // any of them: the block is not one for this route, "not taken"
+};
+
+// Complete lines of a table's text on the device, text.d_text[0 .. n), for the row filter, the plot grid and the k-mer join
+// alike.  A block comes as host text (plain) or as whole gzip members of the compressed file, inflated where they land
+// (members): then the unfinished line is carried over on the device and the file's first line, the header line, is kept
+// apart.  One stream, the owner's work included.  The owner declares the feed last (see TimedStream).
+struct TextFeed {
+    int device = 0;
+    BlockText text;                            // the block
+    PfGzDecoder dec;
+    DevBuf d_carry, d_tail;                    // the unfinished line carried from one members call to the next; rf_tail_kernel's answer
+    uint64_t carry_n = 0;
+    bool want_header = false;
+    std::string header;
+    uint64_t gz_members = 0, gz_text_bytes = 0;
+    float gz_ms = 0;
+    TimedStream ts;
+
+    // the complete lines of host text: *n bytes of them, uploaded unless there are none.  `before(*n)`: what the owner has to
+    // check and reserve for a block of that many bytes in front of the upload
+    int plain(const char* t, uint64_t nbytes, uint64_t* n) { return plain(t, nbytes, n, [](uint64_t) { return PF_OK; }); }
+    template <class F> int plain(const char* t, uint64_t nbytes, uint64_t* n, F&& before) {
+        *n = BlockText::complete_lines(t, nbytes);
+        if (!*n) return PF_OK;
+        PFCHK(before(*n));
+        return text.upload(ts.stream, t, *n);
+    }
+
+    // a file of members starts: nothing carried; with `with_header`, its first line is not a row
+    int members_begin(int with_header) { carry_n = 0; want_header = with_header != 0; header.clear(); return PF_OK; }
+    // that line, with its newline, once a members call has seen it (the messages are the row filter's for every owner)
+    int header_line(const char** line, uint64_t* nbytes) const {
+        if (!line || !nbytes) return fail(PF_ERR_ARG, "pf_rowfilter_members_header: null argument");
+        *line = header.data(); *nbytes = header.size();
+        return PF_OK;
+    }
+
+    // A block of the compressed file from a member start on.  *taken = 0, with PF_OK and the reason as the error text:
+    // the block is not one for this route.  Else
+    // `work(n, skip)` has scanned the lines of d_text[skip .. n) and *consumed compressed bytes are used up; none of them,
+    // and no work, while the block holds no whole member yet: the caller reads on
+    template <class F> int members(const char* bytes, uint64_t nbytes, int last, uint64_t* consumed, int* taken, F&& work) {
+        *consumed = 0; *taken = 0;
+        RfMembers c{reinterpret_cast<const uint8_t*>(bytes), nbytes, last != 0};
+        PFCHK(plan(c));
+        if (c.refused || c.none_yet) { *taken = !c.refused; return PF_OK; }
+        PFCHK(inflate(c));
+        if (!c.refused) PFCHK(peel_header(c));
+        if (c.refused) return PF_OK;
+        gz_members += c.take; gz_text_bytes += c.text_n;
+        PFCHK(work(c.n, c.skip));
+        PFCHK(save_carry(c));
+        *consumed = c.used; *taken = 1;
+        return PF_OK;
+    }
+
+private:
+    // (whatever refuses the block leaves no line carried: the caller starts over another way)
+    int refuse(RfMembers& c, uint64_t member, uint32_t status) {
+        carry_n = 0; c.refused = true;
+        return fail(PF_OK, "pf_rowfilter_scan_members: not taken: member %llu of the block: %s", (unsigned long long)member,
+                    pfgz::inf_status_name(status));
+    }
+
+    int plan(RfMembers& c) {
+        uint64_t listed = 0;
+        if (!pfgz::list_members(c.bytes, c.nbytes, c.last, c.ms, &listed)) return refuse(c, 0, pfgz::INF_BAD_HEAD);
+        const bool none = c.ms.empty() && !c.last;
+        // a member this decoder takes would have ended by now
+        if (none && c.nbytes >= pfgz::SLOT_BYTES + pfgz::MEMBER_HEAD) return refuse(c, 0, pfgz::INF_TOO_LARGE);
+        if (none) { c.none_yet = true; return PF_OK; }
+        // at most the decoder's call: the rest is the caller's to give again
+        while (c.take < c.ms.size() && c.take < PfGzDecoder::MAX_MEMBERS) {
+            if (c.ms[c.take].status != pfgz::INF_OK) return refuse(c, c.take, c.ms[c.take].status);
+            if (c.take && c.text_n + c.ms[c.take].isize > PfGzDecoder::MAX_TEXT) break;
+            c.text_n += c.ms[c.take].isize; c.take++;
+        }
+        const bool all = c.take == c.ms.size();
+        c.used = all ? listed : c.ms[c.take].at;
+        c.end = c.last && all;
+        return PF_OK;
+    }
+
+    // the device text: the line carried over, then the members' text; room for a final newline.  Where its complete lines end
+    int inflate(RfMembers& c) {
+        hipStream_t st = ts.stream;
+        c.total = carry_n + c.text_n;
+        PFCHK(text.reserve(c.total + 1));
+        PFCHK(d_tail.ensure(16, true));
+        unsigned char* const to = text.d_text.as<unsigned char>();
+        if (carry_n) HIPCHK(hipMemcpyAsync(to, d_carry.p, carry_n, hipMemcpyDeviceToDevice, st));
+        PFCHK(dec.decode(st, c.bytes, c.ms.data(), (uint32_t)c.take, to + carry_n, c.text_n, ts.e0, ts.e1));
+        hipLaunchKernelGGL(rf_tail_kernel, dim3(1), dim3(256), 0, st, to, c.total, c.end ? 1 : 0, d_tail.as<uint64_t>());
+        HIPCHK(hipGetLastError());
+        uint64_t tail[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(tail, d_tail.p, 16, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (c.take) {
+            ts.add_elapsed(&gz_ms);
+            uint32_t status = 0;
+            const int64_t bad = dec.first_refused(&status);
+            if (bad >= 0) return refuse(c, (uint64_t)bad, status);
+        }
+        c.n = tail[0]; c.total = tail[1];
+        return PF_OK;
+    }
+
+    // the first call's first line is the header line
+    int peel_header(RfMembers& c) {
+        if (!want_header) return PF_OK;
+        std::string front((size_t)std::min<uint64_t>(c.n, 1 << 16), '\0');
+        if (!front.empty()) HIPCHK(hipMemcpy(&front[0], text.d_text.p, front.size(), hipMemcpyDeviceToHost));
+        const size_t nl = front.find('\n');
+        // (no line end: a header line over 64 KiB or over a call's text -- unless the file is empty)
+        if (nl == std::string::npos && !(c.end && c.total == 0)) return refuse(c, 0, pfgz::INF_NOT_DECODED);
+        if (nl != std::string::npos) { header.assign(front, 0, nl + 1); c.skip = nl + 1; }
+        want_header = false;
+        return PF_OK;
+    }
+
+    // the unfinished line stays on the device for the next call
+    int save_carry(const RfMembers& c) {
+        carry_n = c.total - c.n;
+        if (!carry_n) return PF_OK;
+        PFCHK(d_carry.ensure(carry_n));
+        HIPCHK(hipMemcpyAsync(d_carry.p, text.d_text.as<char>() + c.n, carry_n, hipMemcpyDeviceToDevice, ts.stream));
+        HIPCHK(hipStreamSynchronize(ts.stream));
+        return PF_OK;
+    }
+};
+
 }  // namespace
 
 struct pf_rowfilter {
-    int device = 0;
     int first_field = 0;
     std::unordered_set<std::string> keys;
     std::string key;                           // a candidate's key field, for the look-up in keys
     DevBuf d_set;                              // the keys' hashes (uint64), cap slots
     uint64_t cap = 0;
-    BlockText text;                            // the block
     DevBuf d_out;                              // candidate positions (uint64)
     DevBuf d_count;
     std::vector<uint64_t> begin, end;          // result of the last scan
     uint64_t bytes_scanned = 0;
     float device_ms = 0;
-    // pf_rowfilter_scan_members: the decoder, the unfinished line carried from one call to the next (device), the
-    // candidates' lines (extents and offsets on the device, the gathered bytes on both sides), the kept lines
-    PfGzDecoder dec;
-    DevBuf d_carry, d_ext, d_lines, d_tail;
-    uint64_t carry_n = 0;
-    bool want_header = false;
-    std::string header, raw_lines, lines;
-    uint64_t gz_members = 0, gz_text_bytes = 0;
-    float gz_ms = 0;
-    TimedStream ts;
+    // pf_rowfilter_scan_members: the candidates' lines (extents and offsets on the device, the bytes on both sides), the kept lines
+    DevBuf d_ext, d_lines;
+    std::string raw_lines, lines;
+    TextFeed feed;
 };
 
 namespace {
 
-// The text is on the device -- d_text[0 .. n), complete lines, the buffer reaching to the next multiple of 16 bytes -- scan
-// it: the candidates' positions, sorted.  On the filter's stream, behind whatever put the text there.
+// The text is on the device -- the feed's d_text[0 .. n), complete lines -- scan it: the candidates' positions, sorted.  On
+// the feed's stream, behind whatever put the text there.
 int rf_scan_device(pf_rowfilter* f, uint64_t n, std::vector<uint64_t>& pos) {
+    TimedStream& ts = f->feed.ts;
     // room for the candidates: the filter keeps few rows, so the room is a guess (a position per 64 bytes of text, a
     // million at least) and the kernel is run again with what it asked for should the guess be too small -- counting
     // the lines of the block on the host to size it for the worst case cost more than the kernel itself
@@ -282,20 +416,20 @@ int rf_scan_device(pf_rowfilter* f, uint64_t n, std::vector<uint64_t>& pos) {
     PFCHK(f->d_out.ensure(guess * 8, true));
     unsigned long long cnt = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
-        HIPCHK(hipMemsetAsync(f->d_count.p, 0, 8, f->ts.stream));
+        HIPCHK(hipMemsetAsync(f->d_count.p, 0, 8, ts.stream));
         RfParams p{};
-        p.text = f->text.d_text.as<unsigned char>(); p.n = n; p.set = f->d_set.as<uint64_t>(); p.cap = f->cap;
+        p.text = f->feed.text.d_text.as<unsigned char>(); p.n = n; p.set = f->d_set.as<uint64_t>(); p.cap = f->cap;
         p.first_field = f->first_field;
         p.out = f->d_out.as<uint64_t>(); p.count = f->d_count.as<unsigned long long>(); p.out_cap = f->d_out.cap / 8;
         const uint64_t nvec = (n + 15) / 16;
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((nvec + 255) / 256, 256 * 16);
-        PFCHK(f->ts.timed([&]() -> int {
-            hipLaunchKernelGGL(rowfilter_kernel, dim3(blocks), dim3(256), 0, f->ts.stream, p);
+        PFCHK(ts.timed([&]() -> int {
+            hipLaunchKernelGGL(rowfilter_kernel, dim3(blocks), dim3(256), 0, ts.stream, p);
             HIPCHK(hipGetLastError()); return PF_OK;
         }));
-        HIPCHK(hipMemcpyAsync(&cnt, f->d_count.p, 8, hipMemcpyDeviceToHost, f->ts.stream));
-        HIPCHK(hipStreamSynchronize(f->ts.stream));
-        f->ts.add_elapsed(&f->device_ms);
+        HIPCHK(hipMemcpyAsync(&cnt, f->d_count.p, 8, hipMemcpyDeviceToHost, ts.stream));
+        HIPCHK(hipStreamSynchronize(ts.stream));
+        ts.add_elapsed(&f->device_ms);
         if (cnt <= f->d_out.cap / 8) break;
         // more candidates than room (the kernel counted them all and kept what fitted): again, with room for all
         PFCHK(f->d_out.ensure(((size_t)cnt + (size_t)cnt / 8) * 8, true));
@@ -327,102 +461,29 @@ bool rf_keep(pf_rowfilter* f, const char* b, const char* e) {
     return keep;
 }
 
-// ---- pf_rowfilter_scan_members, stage by stage.  *refused, with PF_OK: the block is not one for this route, "not taken"
-struct RfMembers {
-    const uint8_t* bytes; uint64_t nbytes; bool last;     // the call's arguments
-    std::vector<pfgz::MemberRef> ms;                     // plan: the members listed; how many of them this call takes,
-    size_t take = 0; uint64_t text_n = 0, used = 0;      // their text's bytes, the compressed bytes they use up; whether the
-    bool end = false, none_yet = false;                  // file's text ends with them; no whole member yet: the caller reads on
-    uint64_t total = 0, n = 0;     // inflate: d_text[0 .. total) is the carried line and the members' text, [0 .. n) its complete lines
-    uint64_t skip = 0;             // header: the header line's bytes: no candidate of it is a row
-    std::vector<uint64_t> ext, off;     // candidates: their lines' begins, then ends, in d_text; their offsets in raw_lines
-};
-
-// (whatever refuses the block leaves no line carried: the caller starts over another way)
-int rf_refuse(pf_rowfilter* f, uint64_t member, uint32_t status, bool* refused) {
-    f->carry_n = 0; *refused = true;
-    return fail(PF_OK, "pf_rowfilter_scan_members: not taken: member %llu of the block: %s", (unsigned long long)member,
-                pfgz::inf_status_name(status));
-}
-
-int rf_members_plan(pf_rowfilter* f, RfMembers& c, bool* refused) {
-    uint64_t listed = 0;
-    if (!pfgz::list_members(c.bytes, c.nbytes, c.last, c.ms, &listed)) return rf_refuse(f, 0, pfgz::INF_BAD_HEAD, refused);
-    const bool none = c.ms.empty() && !c.last;
-    // a member this decoder takes would have ended by now
-    if (none && c.nbytes >= pfgz::SLOT_BYTES + pfgz::MEMBER_HEAD) return rf_refuse(f, 0, pfgz::INF_TOO_LARGE, refused);
-    if (none) { c.none_yet = true; return PF_OK; }
-    // at most the decoder's call: the rest is the caller's to give again
-    while (c.take < c.ms.size() && c.take < PfGzDecoder::MAX_MEMBERS) {
-        if (c.ms[c.take].status != pfgz::INF_OK) return rf_refuse(f, c.take, c.ms[c.take].status, refused);
-        if (c.take && c.text_n + c.ms[c.take].isize > PfGzDecoder::MAX_TEXT) break;
-        c.text_n += c.ms[c.take].isize; c.take++;
-    }
-    const bool all = c.take == c.ms.size();
-    c.used = all ? listed : c.ms[c.take].at;
-    c.end = c.last && all;
-    return PF_OK;
-}
-
-// the device text: the line carried over, then the members' text; room for a final newline.  Where its complete lines end
-int rf_members_inflate(pf_rowfilter* f, RfMembers& c, bool* refused) {
-    hipStream_t st = f->ts.stream;
-    c.total = f->carry_n + c.text_n;
-    PFCHK(f->text.reserve(c.total + 1));
-    PFCHK(f->d_tail.ensure(16, true));
-    unsigned char* const text = f->text.d_text.as<unsigned char>();
-    if (f->carry_n) HIPCHK(hipMemcpyAsync(text, f->d_carry.p, f->carry_n, hipMemcpyDeviceToDevice, st));
-    PFCHK(f->dec.decode(st, c.bytes, c.ms.data(), (uint32_t)c.take, text + f->carry_n, c.text_n, f->ts.e0, f->ts.e1));
-    hipLaunchKernelGGL(rf_tail_kernel, dim3(1), dim3(256), 0, st, text, c.total, c.end ? 1 : 0, f->d_tail.as<uint64_t>());
-    HIPCHK(hipGetLastError());
-    uint64_t tail[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(tail, f->d_tail.p, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (c.take) {
-        f->ts.add_elapsed(&f->gz_ms);
-        uint32_t status = 0;
-        const int64_t bad = f->dec.first_refused(&status);
-        if (bad >= 0) return rf_refuse(f, (uint64_t)bad, status, refused);
-    }
-    c.n = tail[0]; c.total = tail[1];
-    return PF_OK;
-}
-
-// the first call's first line is the header line
-int rf_members_header(pf_rowfilter* f, RfMembers& c, bool* refused) {
-    if (!f->want_header) return PF_OK;
-    std::string front((size_t)std::min<uint64_t>(c.n, 1 << 16), '\0');
-    if (!front.empty()) HIPCHK(hipMemcpy(&front[0], f->text.d_text.p, front.size(), hipMemcpyDeviceToHost));
-    const size_t nl = front.find('\n');
-    // (no line end: a header line over 64 KiB or over a call's text -- unless the file is empty)
-    if (nl == std::string::npos && !(c.end && c.total == 0)) return rf_refuse(f, 0, pfgz::INF_NOT_DECODED, refused);
-    if (nl != std::string::npos) { f->header.assign(front, 0, nl + 1); c.skip = nl + 1; }
-    f->want_header = false;
-    return PF_OK;
-}
-
-// the candidates' lines: extents on the device, offsets by the host, one gather, one copy down into raw_lines
-int rf_members_candidates(pf_rowfilter* f, RfMembers& c) {
-    if (!c.n || f->keys.empty()) return PF_OK;
-    hipStream_t st = f->ts.stream;
+// ---- the work of pf_rowfilter_scan_members on the feed's d_text[0 .. n).  The candidates' lines: extents on the device
+// (ext: their begins, then their ends), offsets in raw_lines by the host (off), one gather, one copy down into raw_lines
+int rf_members_candidates(pf_rowfilter* f, uint64_t n, std::vector<uint64_t>& ext, std::vector<uint64_t>& off) {
+    if (!n || f->keys.empty()) return PF_OK;
+    hipStream_t st = f->feed.ts.stream;
     std::vector<uint64_t> pos;
-    PFCHK(rf_scan_device(f, c.n, pos));
+    PFCHK(rf_scan_device(f, n, pos));
     const uint64_t cnt = pos.size();
     if (!cnt) return PF_OK;
-    const unsigned char* const text = f->text.d_text.as<const unsigned char>();
+    const unsigned char* const text = f->feed.text.d_text.as<const unsigned char>();
     PFCHK(f->d_ext.ensure((size_t)cnt * 24, true));
     uint64_t* const d_begin = f->d_ext.as<uint64_t>(), *const d_end = d_begin + cnt, *const d_off = d_end + cnt;
     HIPCHK(hipMemcpyAsync(f->d_out.p, pos.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(rf_extent_kernel, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st, text, c.n,
+    hipLaunchKernelGGL(rf_extent_kernel, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st, text, n,
                        f->d_out.as<const uint64_t>(), cnt, f->first_field, d_begin, d_end);
     HIPCHK(hipGetLastError());
-    c.ext.resize((size_t)cnt * 2); c.off.resize((size_t)cnt);
-    HIPCHK(hipMemcpyAsync(c.ext.data(), d_begin, (size_t)cnt * 16, hipMemcpyDeviceToHost, st));
+    ext.resize((size_t)cnt * 2); off.resize((size_t)cnt);
+    HIPCHK(hipMemcpyAsync(ext.data(), d_begin, (size_t)cnt * 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     uint64_t sum = 0;
-    for (uint64_t k = 0; k < cnt; k++) { c.off[k] = sum; sum += c.ext[cnt + k] - c.ext[k]; }
+    for (uint64_t k = 0; k < cnt; k++) { off[k] = sum; sum += ext[cnt + k] - ext[k]; }
     PFCHK(f->d_lines.ensure(sum + 16));
-    HIPCHK(hipMemcpyAsync(d_off, c.off.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_off, off.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(rf_gather_kernel, dim3((uint32_t)cnt), dim3(64), 0, st, text, d_begin, d_end, d_off,
                        f->d_lines.as<unsigned char>());
     HIPCHK(hipGetLastError());
@@ -432,33 +493,23 @@ int rf_members_candidates(pf_rowfilter* f, RfMembers& c) {
     return PF_OK;
 }
 
-// the candidates that are rows, appended to lines; how many
-uint64_t rf_members_keep(pf_rowfilter* f, const RfMembers& c) {
-    const uint64_t cnt = c.off.size(); uint64_t kept = 0;
+// the candidates behind the header line's `skip` bytes that are rows, appended to lines; how many
+uint64_t rf_members_keep(pf_rowfilter* f, uint64_t skip, const std::vector<uint64_t>& ext, const std::vector<uint64_t>& off) {
+    const uint64_t cnt = off.size(); uint64_t kept = 0;
     for (uint64_t k = 0; k < cnt; k++) {
-        if (c.ext[k] < c.skip) continue;
-        const char* b = f->raw_lines.data() + c.off[k];
-        const char* e = b + (c.ext[cnt + k] - c.ext[k]);
+        if (ext[k] < skip) continue;
+        const char* b = f->raw_lines.data() + off[k];
+        const char* e = b + (ext[cnt + k] - ext[k]);
         if (rf_keep(f, b, e)) { f->lines.append(b, (size_t)(e - b)); kept++; }
     }
     return kept;
-}
-
-// the unfinished line stays on the device for the next call
-int rf_members_save_carry(pf_rowfilter* f, const RfMembers& c) {
-    f->carry_n = c.total - c.n;
-    if (!f->carry_n) return PF_OK;
-    PFCHK(f->d_carry.ensure(f->carry_n));
-    HIPCHK(hipMemcpyAsync(f->d_carry.p, f->text.d_text.as<char>() + c.n, f->carry_n, hipMemcpyDeviceToDevice, f->ts.stream));
-    HIPCHK(hipStreamSynchronize(f->ts.stream));
-    return PF_OK;
 }
 
 }  // namespace
 
 extern "C" {
 
-void pf_rowfilter_destroy(pf_rowfilter* f) { if (f) { (void)hipSetDevice(f->device); delete f; } }
+void pf_rowfilter_destroy(pf_rowfilter* f) { if (f) { (void)hipSetDevice(f->feed.device); delete f; } }
 
 int pf_rowfilter_create(int device, int first_field, const char* const* keys, const uint32_t* key_len, uint64_t n_keys,
                         pf_rowfilter** out) {
@@ -469,23 +520,16 @@ int pf_rowfilter_create(int device, int first_field, const char* const* keys, co
     if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_rowfilter_create: no such device");
     HIPCHK(hipSetDevice(device));
     std::unique_ptr<pf_rowfilter, void (*)(pf_rowfilter*)> f(new pf_rowfilter(), pf_rowfilter_destroy);
-    f->device = device;
+    f->feed.device = device;
     f->first_field = first_field ? 1 : 0;
-    std::vector<uint64_t> table;
-    uint64_t cap = 1024;
-    while (cap < 4 * (n_keys + 1)) cap <<= 1;
-    table.assign(cap, RF_EMPTY);
+    const uint64_t cap = f->cap = pf_table_room(n_keys, 4);
+    std::vector<uint64_t> table(cap, RF_EMPTY);
     for (uint64_t i = 0; i < n_keys; i++) {
         if (key_len[i] >= RF_MAX_FIELD) continue;        // cannot match: the kernel gives up on fields this long
-        auto ins = f->keys.emplace(keys[i], key_len[i]);
-        if (!ins.second) continue;
-        const uint64_t h = rf_hash(keys[i], key_len[i]);
-        uint64_t slot = h & (cap - 1);
-        while (table[slot] != RF_EMPTY && table[slot] != h) slot = (slot + 1) & (cap - 1);
-        table[slot] = h;
+        if (!f->keys.emplace(keys[i], key_len[i]).second) continue;
+        pf_table_insert(table, rf_hash(keys[i], key_len[i]), [](uint64_t) { return true; });     // a set: equal hashes share a slot
     }
-    f->cap = cap;
-    if (f->ts.create() != PF_OK || f->d_set.ensure(cap * 8, true) != PF_OK || f->d_count.ensure(8, true) != PF_OK)
+    if (f->feed.ts.create() != PF_OK || f->d_set.ensure(cap * 8, true) != PF_OK || f->d_count.ensure(8, true) != PF_OK)
         return fail(PF_ERR_HIP, "pf_rowfilter_create: device allocation failed");
     if (hipMemcpy(f->d_set.p, table.data(), cap * 8, hipMemcpyHostToDevice) != hipSuccess)
         return fail(PF_ERR_HIP, "pf_rowfilter_create: upload failed");
@@ -497,12 +541,14 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
                       const uint64_t** line_end, uint64_t* n_lines, uint64_t* consumed) {
     if (!f || !line_begin || !line_end || !n_lines || !consumed || (nbytes && !text))
         return fail(PF_ERR_ARG, "pf_rowfilter_scan: null argument");
-    HIPCHK(hipSetDevice(f->device));
+    HIPCHK(hipSetDevice(f->feed.device));
     f->begin.clear(); f->end.clear();
     *line_begin = nullptr; *line_end = nullptr; *n_lines = 0;
-    const uint64_t n = *consumed = BlockText::complete_lines(text, nbytes);
-    if (!n || f->keys.empty()) return PF_OK;
-    PFCHK(f->text.upload(f->ts.stream, text, n));
+    // (without keys no line is a row: the block's lines are counted and stay where they are)
+    if (f->keys.empty()) { *consumed = BlockText::complete_lines(text, nbytes); return PF_OK; }
+    PFCHK(f->feed.plain(text, nbytes, consumed));
+    const uint64_t n = *consumed;
+    if (!n) return PF_OK;
     std::vector<uint64_t> pos;
     PFCHK(rf_scan_device(f, n, pos));
     for (uint64_t q : pos) {
@@ -516,44 +562,37 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
 
 int pf_rowfilter_members_begin(pf_rowfilter* f, int header) {
     if (!f) return fail(PF_ERR_ARG, "pf_rowfilter_members_begin: null argument");
-    f->carry_n = 0; f->want_header = header != 0; f->header.clear();
-    return PF_OK;
+    return f->feed.members_begin(header);
 }
 
 int pf_rowfilter_members_header(pf_rowfilter* f, const char** line, uint64_t* nbytes) {
-    if (!f || !line || !nbytes) return fail(PF_ERR_ARG, "pf_rowfilter_members_header: null argument");
-    *line = f->header.data(); *nbytes = f->header.size();
-    return PF_OK;
+    if (!f) return fail(PF_ERR_ARG, "pf_rowfilter_members_header: null argument");
+    return f->feed.header_line(line, nbytes);
 }
 
 int pf_rowfilter_scan_members(pf_rowfilter* f, const char* members, uint64_t nbytes, int last, const char** lines,
                               uint64_t* lines_bytes, uint64_t* n_lines, uint64_t* consumed, int* taken) {
     if (!f || !lines || !lines_bytes || !n_lines || !consumed || !taken || (nbytes && !members))
         return fail(PF_ERR_ARG, "pf_rowfilter_scan_members: null argument");
-    HIPCHK(hipSetDevice(f->device));
+    HIPCHK(hipSetDevice(f->feed.device));
     f->lines.clear();
-    *lines = f->lines.data(); *lines_bytes = 0; *n_lines = 0; *consumed = 0; *taken = 0;
-    RfMembers c{reinterpret_cast<const uint8_t*>(members), nbytes, last != 0};
-    bool refused = false;
-    PFCHK(rf_members_plan(f, c, &refused));
-    if (refused || c.none_yet) { *taken = !refused; return PF_OK; }        // (none yet: taken, and the caller reads on)
-    PFCHK(rf_members_inflate(f, c, &refused));
-    if (!refused) PFCHK(rf_members_header(f, c, &refused));
-    if (refused) return PF_OK;
-    f->gz_members += c.take; f->gz_text_bytes += c.text_n;
-    PFCHK(rf_members_candidates(f, c));
-    *n_lines = rf_members_keep(f, c);
-    PFCHK(rf_members_save_carry(f, c));
-    *lines = f->lines.data(); *lines_bytes = f->lines.size(); *consumed = c.used; *taken = 1;
+    *lines = f->lines.data(); *lines_bytes = 0; *n_lines = 0;
+    PFCHK(f->feed.members(members, nbytes, last, consumed, taken, [&](uint64_t n, uint64_t skip) -> int {
+        std::vector<uint64_t> ext, off;
+        PFCHK(rf_members_candidates(f, n, ext, off));
+        *n_lines = rf_members_keep(f, skip, ext, off);
+        return PF_OK;
+    }));
+    *lines = f->lines.data(); *lines_bytes = f->lines.size();      // (nothing, unless the block was taken and had rows)
     return PF_OK;
 }
 
 int pf_rowfilter_gunzip_stats(pf_rowfilter* f, uint64_t* members, uint64_t* text_bytes, float* inflate_ms, uint64_t* device_bytes) {
     if (!f) return fail(PF_ERR_ARG, "pf_rowfilter_gunzip_stats: null argument");
-    if (members) *members = f->gz_members;
-    if (text_bytes) *text_bytes = f->gz_text_bytes;
-    if (inflate_ms) *inflate_ms = f->gz_ms;
-    if (device_bytes) *device_bytes = f->dec.device_bytes();
+    if (members) *members = f->feed.gz_members;
+    if (text_bytes) *text_bytes = f->feed.gz_text_bytes;
+    if (inflate_ms) *inflate_ms = f->feed.gz_ms;
+    if (device_bytes) *device_bytes = f->feed.dec.device_bytes();
     return PF_OK;
 }
 
@@ -841,7 +880,6 @@ inline uint32_t pg_blocks(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, s
 }  // namespace
 
 struct pf_plotgrid {
-    int device = 0;
     float device_ms = 0;
     int32_t col[6] = {};
     int32_t max_col = 0;
@@ -863,7 +901,6 @@ struct pf_plotgrid {
     uint64_t n_rec = 0;
     DevBuf d_chk;                               // PgCheck
     DevBuf d_ctr;                               // [0] records [1] checks [2] lines ; err as [3]
-    BlockText text;                             // the block
     uint64_t bytes_scanned = 0, lines = 0;
     // after pf_plotgrid_finish
     int finished = 0;
@@ -877,7 +914,7 @@ struct pf_plotgrid {
     DevBuf d_key, d_cnt;                       // the grids' cells
     DevBuf d_slot_item;
     DevBuf d_item;                             // off[n] | min[n] | width[n], packed in one buffer
-    TimedStream ts;
+    TextFeed feed;                             // the block (host text only: pf_plotgrid_scan)
 };
 
 namespace {
@@ -895,8 +932,8 @@ int pg_tab_reserve(pf_plotgrid* g, pf_plotgrid::Tab& t, uint64_t more, uint64_t 
         if (want >= ((uint64_t)1 << 47)) return fail(PF_ERR_CAPACITY, "pf_plotgrid: name arena over 2^47 bytes");
         DevBuf a;
         PFCHK(a.ensure(want, true));
-        if (t.used) HIPCHK(hipMemcpyAsync(a.p, t.arena.p, t.used, hipMemcpyDeviceToDevice, g->ts.stream));
-        HIPCHK(hipStreamSynchronize(g->ts.stream));
+        if (t.used) HIPCHK(hipMemcpyAsync(a.p, t.arena.p, t.used, hipMemcpyDeviceToDevice, g->feed.ts.stream));
+        HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
         std::swap(t.arena, a);                  // (the old arena goes at the end of this block)
     }
     uint64_t cap = std::max<uint64_t>(t.cap, 1024);
@@ -906,20 +943,20 @@ int pg_tab_reserve(pf_plotgrid* g, pf_plotgrid::Tab& t, uint64_t more, uint64_t 
     DevBuf hash, str;
     PFCHK(hash.ensure(cap * 8, true));
     PFCHK(str.ensure(cap * 8, true));
-    HIPCHK(hipMemsetAsync(hash.p, 0, cap * 8, g->ts.stream));
+    HIPCHK(hipMemsetAsync(hash.p, 0, cap * 8, g->feed.ts.stream));
     if (t.hash.p) {
         DevBuf remap;
         PFCHK(remap.ensure(t.cap * 4, true));
         PgTable n = pg_view(t);
         n.hash = hash.as<ull>(); n.str = str.as<ull>(); n.cap = cap;
-        hipLaunchKernelGGL(pg_rehash_kernel, dim3(pg_blocks(t.cap)), dim3(256), 0, g->ts.stream, pg_view(t), n, remap.as<uint32_t>());
+        hipLaunchKernelGGL(pg_rehash_kernel, dim3(pg_blocks(t.cap)), dim3(256), 0, g->feed.ts.stream, pg_view(t), n, remap.as<uint32_t>());
         HIPCHK(hipGetLastError());
         if (g->n_rec) {
-            hipLaunchKernelGGL(pg_remap_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->ts.stream, g->d_rec.as<PgRecord>(), g->n_rec,
+            hipLaunchKernelGGL(pg_remap_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->feed.ts.stream, g->d_rec.as<PgRecord>(), g->n_rec,
                                (const uint32_t*)remap.p, field);
             HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipStreamSynchronize(g->ts.stream));
+        HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
     }
     std::swap(t.hash, hash); std::swap(t.str, str);   // (the old ones go on return)
     t.cap = cap;
@@ -949,7 +986,7 @@ int pg_tab_list(pf_plotgrid* g, pf_plotgrid::Tab& t, std::vector<uint32_t>& slot
 
 extern "C" {
 
-void pf_plotgrid_destroy(pf_plotgrid* g) { if (g) { (void)hipSetDevice(g->device); delete g; } }
+void pf_plotgrid_destroy(pf_plotgrid* g) { if (g) { (void)hipSetDevice(g->feed.device); delete g; } }
 
 int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* strain_len, uint32_t n_strains,
                        const int32_t* columns, int zoom, int64_t start, int64_t stop, pf_plotgrid** out) {
@@ -961,7 +998,7 @@ int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* s
     if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_plotgrid_create: no such device");
     HIPCHK(hipSetDevice(device));
     std::unique_ptr<pf_plotgrid, void (*)(pf_plotgrid*)> g(new pf_plotgrid(), pf_plotgrid_destroy);
-    g->device = device;
+    g->feed.device = device;
     g->zoom = zoom ? 1 : 0;
     g->start = start; g->stop = stop;
     g->n_strains = n_strains;
@@ -971,8 +1008,7 @@ int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* s
         g->max_col = std::max(g->max_col, columns[q]);
     }
     // the strain set: distinct names (a repeated phenotype name keeps its first id)
-    uint64_t cap = 1024;
-    while (cap < 2 * ((uint64_t)n_strains + 1)) cap <<= 1;
+    const uint64_t cap = pf_table_room(n_strains, 2);
     std::vector<unsigned long long> hs(cap, 0);
     std::vector<uint32_t> ids(cap, 0);
     std::string bytes;
@@ -981,22 +1017,14 @@ int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* s
         if (strain_len[i] > 0xFFFF) return fail(PF_ERR_ARG, "pf_plotgrid_create: strain name over 65535 bytes");
         str[i] = ((uint64_t)bytes.size() << 16) | strain_len[i];
         bytes.append(strains[i], strain_len[i]);
-        const uint64_t h = rf_hash(strains[i], strain_len[i]);
-        uint64_t slot = h & (cap - 1);
-        bool dup = false;
-        while (hs[slot]) {
-            if (hs[slot] == h) {
-                const uint64_t o = str[ids[slot]];
-                if ((o & 0xFFFF) == strain_len[i] && !memcmp(bytes.data() + (o >> 16), strains[i], strain_len[i])) { dup = true; break; }
-            }
-            slot = (slot + 1) & (cap - 1);
-        }
-        if (dup) continue;
-        hs[slot] = h;
-        ids[slot] = i;
+        const int64_t slot = pf_table_insert(hs, rf_hash(strains[i], strain_len[i]), [&](uint64_t at) {
+            const uint64_t o = str[ids[at]];
+            return (o & 0xFFFF) == strain_len[i] && !memcmp(bytes.data() + (o >> 16), strains[i], strain_len[i]);
+        });
+        if (slot >= 0) ids[slot] = i;
     }
     g->strain_cap = cap;
-    PFCHK(g->ts.create());
+    PFCHK(g->feed.ts.create());
     PFCHK(g->d_strain_hash.ensure(cap * 8, true));
     PFCHK(g->d_strain_id.ensure(cap * 4, true));
     PFCHK(g->d_strain_bytes.ensure(std::max<size_t>(bytes.size(), 1), true));
@@ -1018,29 +1046,31 @@ int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* s
 int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t* consumed) {
     if (!g || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_plotgrid_scan: null argument");
     if (g->finished) return fail(PF_ERR_STATE, "pf_plotgrid_scan: after pf_plotgrid_finish");
-    HIPCHK(hipSetDevice(g->device));
-    const uint64_t n = *consumed = BlockText::complete_lines(text, nbytes);
+    HIPCHK(hipSetDevice(g->feed.device));
+    // room for what a block of n bytes may add, made in front of its upload
+    PFCHK(g->feed.plain(text, nbytes, consumed, [g](uint64_t n) -> int {
+        if (n >= ((uint64_t)1 << 32)) return fail(PF_ERR_ARG, "pf_plotgrid_scan: a block of 4 GiB or more");
+        // every row needs max_col tabs and a newline: at most this many rows pass
+        const uint64_t rows = n / ((uint64_t)g->max_col + 1) + 1;
+        PFCHK(g->d_chk.ensure(rows * sizeof(PgCheck), true));
+        if (g->n_rec + rows > g->d_rec.cap / sizeof(PgRecord)) {
+            const uint64_t want = std::max<uint64_t>((g->n_rec + rows) * 3 / 2, 1 << 16);
+            DevBuf r;
+            PFCHK(r.ensure(want * sizeof(PgRecord), true));
+            if (g->n_rec) HIPCHK(hipMemcpyAsync(r.p, g->d_rec.p, g->n_rec * sizeof(PgRecord), hipMemcpyDeviceToDevice, g->feed.ts.stream));
+            HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
+            std::swap(g->d_rec, r);                 // (the old records go at the end of this block)
+        }
+        PFCHK(pg_tab_reserve(g, g->cl, rows, n, 0));
+        return pg_tab_reserve(g, g->pv, rows, n, 1);
+    }));
+    const uint64_t n = *consumed;
     if (!n) return PF_OK;
-    if (n >= ((uint64_t)1 << 32)) return fail(PF_ERR_ARG, "pf_plotgrid_scan: a block of 4 GiB or more");
-    // every row needs max_col tabs and a newline: at most this many rows pass
-    const uint64_t rows = n / ((uint64_t)g->max_col + 1) + 1;
-    PFCHK(g->d_chk.ensure(rows * sizeof(PgCheck), true));
-    if (g->n_rec + rows > g->d_rec.cap / sizeof(PgRecord)) {
-        const uint64_t want = std::max<uint64_t>((g->n_rec + rows) * 3 / 2, 1 << 16);
-        DevBuf r;
-        PFCHK(r.ensure(want * sizeof(PgRecord), true));
-        if (g->n_rec) HIPCHK(hipMemcpyAsync(r.p, g->d_rec.p, g->n_rec * sizeof(PgRecord), hipMemcpyDeviceToDevice, g->ts.stream));
-        HIPCHK(hipStreamSynchronize(g->ts.stream));
-        std::swap(g->d_rec, r);                 // (the old records go at the end of this block)
-    }
-    if (int rc = pg_tab_reserve(g, g->cl, rows, n, 0)) return rc;
-    if (int rc = pg_tab_reserve(g, g->pv, rows, n, 1)) return rc;
-    PFCHK(g->text.upload(g->ts.stream, text, n));
     unsigned long long* const d_ctr = g->d_ctr.as<ull>();
     unsigned long long ctr[4] = {g->n_rec, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(d_ctr, ctr, 3 * 8, hipMemcpyHostToDevice, g->ts.stream));   // records continue; checks, lines restart
+    HIPCHK(hipMemcpyAsync(d_ctr, ctr, 3 * 8, hipMemcpyHostToDevice, g->feed.ts.stream));   // records continue; checks, lines restart
     PgScanParams p{};
-    p.text = g->text.d_text.as<unsigned char>(); p.n = n;
+    p.text = g->feed.text.d_text.as<unsigned char>(); p.n = n;
     for (int q = 0; q < 6; q++) p.col[q] = g->col[q];
     p.max_col = g->max_col;
     p.strain_hash = g->d_strain_hash.as<ull>(); p.strain_id = g->d_strain_id.as<uint32_t>(); p.strain_cap = g->strain_cap;
@@ -1049,25 +1079,25 @@ int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t
     p.zoom = g->zoom; p.start = g->start; p.stop = g->stop;
     p.rec = g->d_rec.as<PgRecord>(); p.n_rec = d_ctr; p.chk = g->d_chk.as<PgCheck>(); p.n_chk = d_ctr + 1; p.n_lines = d_ctr + 2;
     p.err = (unsigned int*)(d_ctr + 3);
-    PFCHK(g->ts.timed([&]() -> int {
-        hipLaunchKernelGGL(pg_scan_kernel, dim3(pg_blocks((n + 15) / 16)), dim3(256), 0, g->ts.stream, p);
+    PFCHK(g->feed.ts.timed([&]() -> int {
+        hipLaunchKernelGGL(pg_scan_kernel, dim3(pg_blocks((n + 15) / 16)), dim3(256), 0, g->feed.ts.stream, p);
         HIPCHK(hipGetLastError());
         unsigned long long n_chk = 0;
-        HIPCHK(hipMemcpyAsync(&n_chk, d_ctr + 1, 8, hipMemcpyDeviceToHost, g->ts.stream));
-        HIPCHK(hipStreamSynchronize(g->ts.stream));
+        HIPCHK(hipMemcpyAsync(&n_chk, d_ctr + 1, 8, hipMemcpyDeviceToHost, g->feed.ts.stream));
+        HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
         if (n_chk) {
-            hipLaunchKernelGGL(pg_check_kernel, dim3(pg_blocks(n_chk)), dim3(256), 0, g->ts.stream, p.text, g->d_chk.as<const PgCheck>(),
+            hipLaunchKernelGGL(pg_check_kernel, dim3(pg_blocks(n_chk)), dim3(256), 0, g->feed.ts.stream, p.text, g->d_chk.as<const PgCheck>(),
                                (uint64_t)n_chk, pg_view(g->cl), pg_view(g->pv), (unsigned int*)(d_ctr + 3));
             HIPCHK(hipGetLastError());
         }
         return PF_OK;
     }));
-    HIPCHK(hipMemcpyAsync(ctr, d_ctr, 4 * 8, hipMemcpyDeviceToHost, g->ts.stream));
+    HIPCHK(hipMemcpyAsync(ctr, d_ctr, 4 * 8, hipMemcpyDeviceToHost, g->feed.ts.stream));
     unsigned long long tc[2][2];
-    HIPCHK(hipMemcpyAsync(tc[0], g->cl.ctr.p, 16, hipMemcpyDeviceToHost, g->ts.stream));
-    HIPCHK(hipMemcpyAsync(tc[1], g->pv.ctr.p, 16, hipMemcpyDeviceToHost, g->ts.stream));
-    HIPCHK(hipStreamSynchronize(g->ts.stream));
-    g->ts.add_elapsed(&g->device_ms);
+    HIPCHK(hipMemcpyAsync(tc[0], g->cl.ctr.p, 16, hipMemcpyDeviceToHost, g->feed.ts.stream));
+    HIPCHK(hipMemcpyAsync(tc[1], g->pv.ctr.p, 16, hipMemcpyDeviceToHost, g->feed.ts.stream));
+    HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
+    g->feed.ts.add_elapsed(&g->device_ms);
     g->cl.used = tc[0][0]; g->cl.count = tc[0][1];
     g->pv.used = tc[1][0]; g->pv.count = tc[1][1];
     g->n_rec = ctr[0];
@@ -1083,7 +1113,7 @@ int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t
 
 int pf_plotgrid_finish(pf_plotgrid* g, uint32_t* n_clusters, uint64_t* n_pvalues, uint64_t* n_records) {
     if (!g || !n_clusters || !n_pvalues || !n_records) return fail(PF_ERR_ARG, "pf_plotgrid_finish: null argument");
-    HIPCHK(hipSetDevice(g->device));
+    HIPCHK(hipSetDevice(g->feed.device));
     if (!g->finished) {
         if (int rc = pg_tab_list(g, g->cl, g->cl_slot, g->cl_names, g->cl_off)) return rc;
         if (int rc = pg_tab_list(g, g->pv, g->pv_slot, g->pv_texts, g->pv_off)) return rc;
@@ -1098,10 +1128,10 @@ int pf_plotgrid_finish(pf_plotgrid* g, uint32_t* n_clusters, uint64_t* n_pvalues
         HIPCHK(hipMemcpy(mx.p, init.data(), cap * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemset(cnt.p, 0, cap * 8));
         if (g->n_rec) {
-            hipLaunchKernelGGL(pg_stats_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->ts.stream, g->d_rec.as<const PgRecord>(),
+            hipLaunchKernelGGL(pg_stats_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->feed.ts.stream, g->d_rec.as<const PgRecord>(),
                                g->n_rec, mn.as<int>(), mx.as<int>(), cnt.as<ull>());
             HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(g->ts.stream));
+            HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
         }
         std::vector<int> hmn(cap), hmx(cap);
         std::vector<unsigned long long> hc(cap);
@@ -1141,7 +1171,7 @@ int pf_plotgrid_pvalues(pf_plotgrid* g, const char** texts, const uint64_t** tex
 int pf_plotgrid_set_significance(pf_plotgrid* g, const uint64_t* keys) {
     if (!g || (!keys && !g->pv_slot.empty())) return fail(PF_ERR_ARG, "pf_plotgrid_set_significance: null argument");
     if (!g->finished) return fail(PF_ERR_STATE, "pf_plotgrid_set_significance: before pf_plotgrid_finish");
-    HIPCHK(hipSetDevice(g->device));
+    HIPCHK(hipSetDevice(g->feed.device));
     const uint64_t cap = std::max<uint64_t>(g->pv.cap, 1);
     std::vector<unsigned long long> by_slot(cap, 0);
     for (size_t i = 0; i < g->pv_slot.size(); i++) by_slot[g->pv_slot[i]] = keys[i];
@@ -1155,7 +1185,7 @@ int pf_plotgrid_grids(pf_plotgrid* g, const uint32_t* ids, uint32_t n, uint64_t*
     if (!g || (n && (!ids || !key_out || !cnt_out))) return fail(PF_ERR_ARG, "pf_plotgrid_grids: null argument");
     if (!g->finished || !g->sig_set) return fail(PF_ERR_STATE, "pf_plotgrid_grids: before pf_plotgrid_set_significance");
     if (!n) return PF_OK;
-    HIPCHK(hipSetDevice(g->device));
+    HIPCHK(hipSetDevice(g->feed.device));
     const uint64_t cap = std::max<uint64_t>(g->cl.cap, 1);
     std::vector<int32_t> slot_item(cap, -1);
     std::vector<uint64_t> item(3 * (size_t)n);
@@ -1181,30 +1211,30 @@ int pf_plotgrid_grids(pf_plotgrid* g, const uint32_t* ids, uint32_t n, uint64_t*
     std::vector<uint32_t> iwidth(n);
     for (uint32_t i = 0; i < n; i++) { imin[i] = (int32_t)(int64_t)item[n + i]; iwidth[i] = (uint32_t)item[2 * (size_t)n + i]; }
     char* dit = g->d_item.as<char>();
-    HIPCHK(hipMemcpyAsync(dit, item.data(), (size_t)n * 8, hipMemcpyHostToDevice, g->ts.stream));
-    HIPCHK(hipMemcpyAsync(dit + (size_t)n * 8, imin.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->ts.stream));
-    HIPCHK(hipMemcpyAsync(dit + (size_t)n * 12, iwidth.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->ts.stream));
+    HIPCHK(hipMemcpyAsync(dit, item.data(), (size_t)n * 8, hipMemcpyHostToDevice, g->feed.ts.stream));
+    HIPCHK(hipMemcpyAsync(dit + (size_t)n * 8, imin.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->feed.ts.stream));
+    HIPCHK(hipMemcpyAsync(dit + (size_t)n * 12, iwidth.data(), (size_t)n * 4, hipMemcpyHostToDevice, g->feed.ts.stream));
     unsigned long long* const d_err = g->d_ctr.as<ull>() + 3;
-    HIPCHK(hipMemcpyAsync(g->d_slot_item.p, slot_item.data(), cap * 4, hipMemcpyHostToDevice, g->ts.stream));
-    HIPCHK(hipMemsetAsync(g->d_key.p, 0, cells * 8, g->ts.stream));
-    HIPCHK(hipMemsetAsync(g->d_cnt.p, 0, cells * 8, g->ts.stream));
-    HIPCHK(hipMemsetAsync(d_err, 0, 8, g->ts.stream));
+    HIPCHK(hipMemcpyAsync(g->d_slot_item.p, slot_item.data(), cap * 4, hipMemcpyHostToDevice, g->feed.ts.stream));
+    HIPCHK(hipMemsetAsync(g->d_key.p, 0, cells * 8, g->feed.ts.stream));
+    HIPCHK(hipMemsetAsync(g->d_cnt.p, 0, cells * 8, g->feed.ts.stream));
+    HIPCHK(hipMemsetAsync(d_err, 0, 8, g->feed.ts.stream));
     PgGridParams p{};
     p.rec = g->d_rec.as<PgRecord>(); p.n = g->n_rec; p.slot_item = g->d_slot_item.as<int32_t>();
     p.item_off = (const uint64_t*)dit; p.item_min = (const int32_t*)(dit + (size_t)n * 8);
     p.item_width = (const uint32_t*)(dit + (size_t)n * 12);
     p.n_strains = g->n_strains; p.sig_key = g->d_sig.as<ull>(); p.key = g->d_key.as<ull>(); p.cnt = g->d_cnt.as<ull>();
     p.err = (unsigned int*)d_err;
-    PFCHK(g->ts.timed([&]() -> int {
-        hipLaunchKernelGGL(pg_grid_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->ts.stream, p);
+    PFCHK(g->feed.ts.timed([&]() -> int {
+        hipLaunchKernelGGL(pg_grid_kernel, dim3(pg_blocks(g->n_rec)), dim3(256), 0, g->feed.ts.stream, p);
         HIPCHK(hipGetLastError()); return PF_OK;
     }));
     unsigned long long err = 0;
-    HIPCHK(hipMemcpyAsync(key_out, g->d_key.p, cells * 8, hipMemcpyDeviceToHost, g->ts.stream));
-    HIPCHK(hipMemcpyAsync(cnt_out, g->d_cnt.p, cells * 8, hipMemcpyDeviceToHost, g->ts.stream));
-    HIPCHK(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, g->ts.stream));
-    HIPCHK(hipStreamSynchronize(g->ts.stream));
-    g->ts.add_elapsed(&g->device_ms);
+    HIPCHK(hipMemcpyAsync(key_out, g->d_key.p, cells * 8, hipMemcpyDeviceToHost, g->feed.ts.stream));
+    HIPCHK(hipMemcpyAsync(cnt_out, g->d_cnt.p, cells * 8, hipMemcpyDeviceToHost, g->feed.ts.stream));
+    HIPCHK(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, g->feed.ts.stream));
+    HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
+    g->feed.ts.add_elapsed(&g->device_ms);
     if (err) return fail(PF_ERR_STATE, "pf_plotgrid_grids: a record outside its cluster's grid");
     return PF_OK;
 }
@@ -1545,7 +1575,6 @@ __global__ __launch_bounds__(256) void kj_write_kernel(KjParams p, uint64_t n_ro
 }  // namespace
 
 struct pf_kmerjoin {
-    pf_rowfilter rf;                             // the block's text, the member stages' state, the stream: the row filter's own
     uint32_t n_bunches = 0;
     uint64_t ccap = 0, kcap = 0;
     uint32_t empty_off = 0, empty_len = 0;
@@ -1557,13 +1586,14 @@ struct pf_kmerjoin {
     int cur = 0;
     uint64_t bytes_scanned = 0, rows_written = 0, raw_rows = 0;
     float survey_ms = 0, write_ms = 0;
+    TextFeed feed;                               // (its stream goes first: a piece of text may be on its way down into pin)
 };
 
 namespace {
 
 KjParams kj_params(pf_kmerjoin* j, uint64_t n, uint64_t begin) {
     KjParams p{};
-    p.text = j->rf.text.d_text.as<unsigned char>(); p.n = n; p.begin = begin;
+    p.text = j->feed.text.d_text.as<unsigned char>(); p.n = n; p.begin = begin;
     p.chash = j->d_chash.as<unsigned long long>(); p.cslot = j->d_cslot.as<uint32_t>(); p.ccap = j->ccap; p.clusters = j->d_clusters.as<KjCluster>();
     p.khash = j->d_khash.as<unsigned long long>(); p.kslot = j->d_kslot.as<uint32_t>(); p.kcap = j->kcap; p.keys = j->d_keys.as<KjKey>();
     p.arena = j->d_arena.as<unsigned char>(); p.empty_off = j->empty_off; p.empty_len = j->empty_len;
@@ -1578,7 +1608,7 @@ inline uint32_t kj_tiles(uint64_t n) { return (uint32_t)(((n + 15) / 16 + KJ_TIL
 // the survey of d_text[begin .. n)
 int kj_survey_device(pf_kmerjoin* j, uint64_t n, uint64_t begin) {
     if (n <= begin) return PF_OK;
-    TimedStream& ts = j->rf.ts;
+    TimedStream& ts = j->feed.ts;
     const KjParams p = kj_params(j, n, begin);
     PFCHK(ts.timed([&]() -> int {
         hipLaunchKernelGGL(kj_survey_kernel, dim3(kj_tiles(n)), dim3(256), 0, ts.stream, p);
@@ -1595,7 +1625,7 @@ int kj_join_device(pf_kmerjoin* j, uint64_t n, uint64_t begin, uint32_t bunch, i
     j->out_bytes = j->out_pos = j->flying = 0;
     if (n <= begin) return PF_OK;
     if (bunch >= j->n_bunches || mode < 0 || mode > 2) return fail(PF_ERR_ARG, "pf_kmerjoin_join: no such bunch or mode");
-    TimedStream& ts = j->rf.ts;
+    TimedStream& ts = j->feed.ts;
     const uint32_t tiles = kj_tiles(n);
     PFCHK(j->d_thr.ensure((size_t)tiles * 256 * sizeof(uint2)));
     PFCHK(j->d_tile.ensure(((size_t)tiles + 1) * 16));
@@ -1639,24 +1669,6 @@ int kj_join_device(pf_kmerjoin* j, uint64_t n, uint64_t begin, uint32_t bunch, i
     return PF_OK;
 }
 
-// the row filter's member stages for a block of members: the text in rf.text.d_text, lines of [c.skip, c.n) for `work`
-template <class F> int kj_members(pf_kmerjoin* j, const char* members, uint64_t nbytes, int last, uint64_t* consumed, int* taken, F&& work) {
-    pf_rowfilter* f = &j->rf;
-    *consumed = 0; *taken = 0;
-    RfMembers c{reinterpret_cast<const uint8_t*>(members), nbytes, last != 0};
-    bool refused = false;
-    PFCHK(rf_members_plan(f, c, &refused));
-    if (refused || c.none_yet) { *taken = !refused; return PF_OK; }
-    PFCHK(rf_members_inflate(f, c, &refused));
-    if (!refused) PFCHK(rf_members_header(f, c, &refused));
-    if (refused) return PF_OK;
-    f->gz_members += c.take; f->gz_text_bytes += c.text_n;
-    PFCHK(work(c.n, c.skip));
-    PFCHK(rf_members_save_carry(f, c));
-    *consumed = c.used; *taken = 1;
-    return PF_OK;
-}
-
 template <class T> int kj_upload(DevBuf& d, const std::vector<T>& v) {
     PFCHK(d.ensure(std::max<size_t>(v.size() * sizeof(T), 16), true));
     if (!v.empty()) HIPCHK(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
@@ -1667,12 +1679,7 @@ template <class T> int kj_upload(DevBuf& d, const std::vector<T>& v) {
 
 extern "C" {
 
-void pf_kmerjoin_destroy(pf_kmerjoin* j) {
-    if (!j) return;
-    (void)hipSetDevice(j->rf.device);
-    if (j->rf.ts.stream) (void)hipStreamSynchronize(j->rf.ts.stream);      // (a piece of text may be on its way down)
-    delete j;
-}
+void pf_kmerjoin_destroy(pf_kmerjoin* j) { if (j) { (void)hipSetDevice(j->feed.device); delete j; } }
 
 int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* cluster_len, const uint32_t* cluster_bunch,
                        uint64_t n_clusters, uint32_t n_bunches, const char* const* key_cluster, const uint32_t* key_cluster_len,
@@ -1688,20 +1695,17 @@ int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* 
     if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_kmerjoin_create: no such device");
     HIPCHK(hipSetDevice(device));
     std::unique_ptr<pf_kmerjoin, void (*)(pf_kmerjoin*)> j(new pf_kmerjoin(), pf_kmerjoin_destroy);
-    j->rf.device = device; j->rf.first_field = 1;
+    j->feed.device = device;
     j->n_bunches = std::max<uint32_t>(n_bunches, 1);
     std::string arena;
     auto put = [&arena](const char* s, uint32_t n) { const size_t at = arena.size(); arena.append(s, n); return (uint32_t)at; };
-    auto room = [](uint64_t n) { uint64_t cap = 1024; while (cap < 4 * (n + 1)) cap <<= 1; return cap; };
     auto insert = [](std::vector<unsigned long long>& hash, std::vector<uint32_t>& slot_id, uint64_t h, uint32_t id) {
-        uint64_t slot = h & (hash.size() - 1);                 // (equal hashes take slots of their own: the bytes tell them apart)
-        while (hash[slot] != RF_EMPTY) slot = (slot + 1) & (hash.size() - 1);
-        hash[slot] = h; slot_id[slot] = id;
+        slot_id[pf_table_insert(hash, h, [](uint64_t) { return false; })] = id;     // (equal hashes take slots of their own: the bytes tell them apart)
     };
     j->empty_off = put(empty_text, empty_len); j->empty_len = empty_len;
     // the selected clusters (one that comes twice keeps its first bunch)
     std::vector<KjCluster> cl;
-    std::vector<unsigned long long> chash(j->ccap = room(n_clusters), RF_EMPTY);
+    std::vector<unsigned long long> chash(j->ccap = pf_table_room(n_clusters, 4), RF_EMPTY);
     std::vector<uint32_t> cslot(j->ccap, 0);
     std::unordered_set<std::string> seen;
     for (uint64_t i = 0; i < n_clusters; i++) {
@@ -1712,7 +1716,7 @@ int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* 
     }
     // the keys: the hash runs over cluster, a tab, k-mer
     std::vector<KjKey> keys;
-    std::vector<unsigned long long> khash(j->kcap = room(n_keys), RF_EMPTY);
+    std::vector<unsigned long long> khash(j->kcap = pf_table_room(n_keys, 4), RF_EMPTY);
     std::vector<uint32_t> kslot(j->kcap, 0);
     seen.clear();
     for (uint64_t i = 0; i < n_keys; i++) {
@@ -1732,7 +1736,7 @@ int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* 
     }
     if (arena.size() >= (1ull << 32)) return fail(PF_ERR_CAPACITY, "pf_kmerjoin_create: the keys and their texts take 4 GiB or more");
     j->counters.assign((size_t)j->n_bunches * KJ_COUNTERS, 0);
-    PFCHK(j->rf.ts.create());
+    PFCHK(j->feed.ts.create());
     PFCHK(kj_upload(j->d_chash, chash)); PFCHK(kj_upload(j->d_cslot, cslot)); PFCHK(kj_upload(j->d_clusters, cl));
     PFCHK(kj_upload(j->d_khash, khash)); PFCHK(kj_upload(j->d_kslot, kslot)); PFCHK(kj_upload(j->d_keys, keys));
     PFCHK(kj_upload(j->d_arena, std::vector<char>(arena.begin(), arena.end())));
@@ -1744,39 +1748,37 @@ int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* 
 
 int pf_kmerjoin_survey(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint64_t* consumed) {
     if (!j || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_kmerjoin_survey: null argument");
-    HIPCHK(hipSetDevice(j->rf.device));
-    const uint64_t n = *consumed = BlockText::complete_lines(text, nbytes);
-    if (!n) return PF_OK;
-    PFCHK(j->rf.text.upload(j->rf.ts.stream, text, n));
-    return kj_survey_device(j, n, 0);
+    HIPCHK(hipSetDevice(j->feed.device));
+    PFCHK(j->feed.plain(text, nbytes, consumed));
+    return kj_survey_device(j, *consumed, 0);
 }
 
 int pf_kmerjoin_members_begin(pf_kmerjoin* j, int header) {
     if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_members_begin: null argument");
-    return pf_rowfilter_members_begin(&j->rf, header);
+    return j->feed.members_begin(header);
 }
 
 int pf_kmerjoin_members_header(pf_kmerjoin* j, const char** line, uint64_t* nbytes) {
     if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_members_header: null argument");
-    return pf_rowfilter_members_header(&j->rf, line, nbytes);
+    return j->feed.header_line(line, nbytes);
 }
 
 int pf_kmerjoin_survey_members(pf_kmerjoin* j, const char* members, uint64_t nbytes, int last, uint64_t* consumed, int* taken) {
     if (!j || !consumed || !taken || (nbytes && !members)) return fail(PF_ERR_ARG, "pf_kmerjoin_survey_members: null argument");
-    HIPCHK(hipSetDevice(j->rf.device));
-    return kj_members(j, members, nbytes, last, consumed, taken, [j](uint64_t n, uint64_t skip) { return kj_survey_device(j, n, skip); });
+    HIPCHK(hipSetDevice(j->feed.device));
+    return j->feed.members(members, nbytes, last, consumed, taken, [j](uint64_t n, uint64_t skip) { return kj_survey_device(j, n, skip); });
 }
 
 int pf_kmerjoin_reset_counters(pf_kmerjoin* j) {
     if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_reset_counters: null argument");
-    HIPCHK(hipSetDevice(j->rf.device));
+    HIPCHK(hipSetDevice(j->feed.device));
     HIPCHK(hipMemset(j->d_counters.p, 0, j->counters.size() * 8));
     return PF_OK;
 }
 
 int pf_kmerjoin_counters(pf_kmerjoin* j, const uint64_t** counters, uint32_t* n_bunches) {
     if (!j || !counters || !n_bunches) return fail(PF_ERR_ARG, "pf_kmerjoin_counters: null argument");
-    HIPCHK(hipSetDevice(j->rf.device));
+    HIPCHK(hipSetDevice(j->feed.device));
     HIPCHK(hipMemcpy(j->counters.data(), j->d_counters.p, j->counters.size() * 8, hipMemcpyDeviceToHost));
     *counters = j->counters.data(); *n_bunches = j->n_bunches;
     return PF_OK;
@@ -1784,12 +1786,10 @@ int pf_kmerjoin_counters(pf_kmerjoin* j, const uint64_t** counters, uint32_t* n_
 
 int pf_kmerjoin_join(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint32_t bunch, int mode, uint64_t* out_bytes, uint64_t* consumed) {
     if (!j || !out_bytes || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_kmerjoin_join: null argument");
-    HIPCHK(hipSetDevice(j->rf.device));
+    HIPCHK(hipSetDevice(j->feed.device));
     *out_bytes = 0; j->out_bytes = j->out_pos = j->flying = 0;
-    const uint64_t n = *consumed = BlockText::complete_lines(text, nbytes);
-    if (!n) return PF_OK;
-    PFCHK(j->rf.text.upload(j->rf.ts.stream, text, n));
-    PFCHK(kj_join_device(j, n, 0, bunch, mode));
+    PFCHK(j->feed.plain(text, nbytes, consumed));
+    PFCHK(kj_join_device(j, *consumed, 0, bunch, mode));
     *out_bytes = j->out_bytes;
     return PF_OK;
 }
@@ -1797,19 +1797,19 @@ int pf_kmerjoin_join(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint32_t
 int pf_kmerjoin_join_members(pf_kmerjoin* j, const char* members, uint64_t nbytes, int last, uint32_t bunch, int mode,
                              uint64_t* out_bytes, uint64_t* consumed, int* taken) {
     if (!j || !out_bytes || !consumed || !taken || (nbytes && !members)) return fail(PF_ERR_ARG, "pf_kmerjoin_join_members: null argument");
-    HIPCHK(hipSetDevice(j->rf.device));
+    HIPCHK(hipSetDevice(j->feed.device));
     *out_bytes = 0; j->out_bytes = j->out_pos = j->flying = 0;
-    PFCHK(kj_members(j, members, nbytes, last, consumed, taken,
-                     [j, bunch, mode](uint64_t n, uint64_t skip) { return kj_join_device(j, n, skip, bunch, mode); }));
+    PFCHK(j->feed.members(members, nbytes, last, consumed, taken,
+                           [j, bunch, mode](uint64_t n, uint64_t skip) { return kj_join_device(j, n, skip, bunch, mode); }));
     *out_bytes = j->out_bytes;
     return PF_OK;
 }
 
 int pf_kmerjoin_next_text(pf_kmerjoin* j, const char** piece, uint64_t* nbytes) {
     if (!j || !piece || !nbytes) return fail(PF_ERR_ARG, "pf_kmerjoin_next_text: null argument");
-    HIPCHK(hipSetDevice(j->rf.device));
+    HIPCHK(hipSetDevice(j->feed.device));
     *piece = nullptr; *nbytes = 0;
-    hipStream_t st = j->rf.ts.stream;
+    hipStream_t st = j->feed.ts.stream;
     auto start = [&]() -> int {                    // the next piece on its way into pin[cur]
         j->flying = std::min<uint64_t>(KJ_PIECE, j->out_bytes - j->out_pos);
         if (!j->flying) return PF_OK;
@@ -1828,14 +1828,14 @@ int pf_kmerjoin_next_text(pf_kmerjoin* j, const char** piece, uint64_t* nbytes) 
 
 int pf_kmerjoin_stats(pf_kmerjoin* j, uint64_t stats[8], float ms[3]) {
     if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_stats: null argument");
-    HIPCHK(hipSetDevice(j->rf.device));
+    HIPCHK(hipSetDevice(j->feed.device));
     if (stats) {
         uint64_t misc[3] = {0, 0, 0};                          // rejects, err, unmatched
         HIPCHK(hipMemcpy(misc, j->d_misc.p, sizeof misc, hipMemcpyDeviceToHost));
-        stats[0] = j->bytes_scanned; stats[1] = j->rows_written; stats[2] = j->raw_rows; stats[3] = j->rf.gz_members;
-        stats[4] = j->rf.gz_text_bytes; stats[5] = j->rf.dec.device_bytes(); stats[6] = misc[0]; stats[7] = misc[2];
+        stats[0] = j->bytes_scanned; stats[1] = j->rows_written; stats[2] = j->raw_rows; stats[3] = j->feed.gz_members;
+        stats[4] = j->feed.gz_text_bytes; stats[5] = j->feed.dec.device_bytes(); stats[6] = misc[0]; stats[7] = misc[2];
     }
-    if (ms) { ms[0] = j->survey_ms; ms[1] = j->write_ms; ms[2] = j->rf.gz_ms; }
+    if (ms) { ms[0] = j->survey_ms; ms[1] = j->write_ms; ms[2] = j->feed.gz_ms; }
     return PF_OK;
 }
 

@@ -6,8 +6,7 @@ output:
 
 What costs time in them is streaming `kmers_to_hashes.tsv` (one row per kept k-mer of the whole pangenome) and
 `kmers.tsv` through pandas in 100 000-row chunks only to keep the few rows whose hash / cluster is in a set.  Here that
-row filter runs on the GPU over the raw text (`RowFilter` -> pf_rowfilter_scan, or pf_rowfilter_scan_members for a
-device-gzipped file, csrc/pf_rowfilter.hip); the small
+row filter runs on the GPU over the raw text (`RowFilter` -> pf_rowfilter_scan, csrc/pf_rowfilter.hip); the small
 tables that remain (the associations, the kept rows) go through the same pandas statements as the reference's, so the
 printed tables are the same bytes.  There is no CPU fallback for the filter.
 
@@ -17,6 +16,10 @@ as text once per key (`rendered_texts`), one survey pass over kmers.tsv counts e
 pandas could print any of them other than as they stand, and one pass per bunch writes the annotated rows on the device.
 A bunch the survey flags, and a run whose table the device cannot take, goes through the pandas statements of the
 reference (`--host-join` sends everything there).
+
+Both read a table the same two ways, written once here: a device-gzipped file goes up compressed and is inflated where
+it lands (`pass_member_file` -> pf_*_members), any other is read block by block through the host (`scan_lines`);
+`route_file` chooses, and falls back to the second when the device decoder does not take a block.
 
 One thing the reference leaves to chance is kept out of the comparison: it iterates over Python `set`s of cluster
 names, so the order of its printed clusters / blocks changes with PYTHONHASHSEED.  Here clusters come in order of their
@@ -46,6 +49,66 @@ class NotTaken(RuntimeError):
     """device_gunzip=True and the file is not one the device decoder takes"""
 
 
+def _last_error():
+    return _lib.load().pf_last_error().decode(errors="replace")
+
+
+def _gz_members_file(path):
+    """whether the file is a .gz whose first bytes are the only header the device decoder takes"""
+    if not str(path).endswith(".gz"):
+        return False
+    with open(path, "rb") as fh:
+        return fh.read(10)[:4] == GZ_HEAD
+
+
+def pass_member_file(path, block_bytes, begin, call, after=None, reason=_last_error):
+    """One pass over a file of gzip members through a device text feed (TextFeed, csrc/pf_rowfilter.hip): begin(), then
+    blocks of the COMPRESSED file go to call(data, last) -> (compressed bytes used, whether the block was taken) as they
+    are, what follows a block's last whole member put in front of the next block; `last` from the read that met the end
+    of the file on; after() behind every call that was taken.  -> whether the file went through to its end: False, with
+    reason() -- the library's -- logged, as soon as a block is not taken."""
+    block = max(1, block_bytes or BLOCK_BYTES // GZ_BLOCK_DIVISOR)
+    begin()
+    with open(path, "rb") as fh:
+        carry, eof = b"", False
+        while True:
+            if not eof:
+                chunk = fh.read(block)
+                eof = len(chunk) < block
+                carry = carry + chunk if carry else chunk
+            used, taken = call(carry, eof)
+            if not taken:
+                logger.debug("%s: %s", path, reason())
+                return False
+            if after:
+                after()
+            carry = carry[used:]
+            if eof and not carry:
+                return True
+
+
+def route_file(path, device_gunzip, members, host, counts, again=None, reason=_last_error):
+    """A file by the device gunzip route, members(), or through gzip as pandas reads it by the name, host(); -> what that
+    returned.  device_gunzip=None tries members() for a .gz of the header the device decoder takes and, when it returns
+    None -- a block was not taken --, runs again() (what the owner undoes before the file is read once more) and host();
+    True tries members() whatever the file and raises NotTaken instead; False never tries.  `counts`: the owner's class,
+    whose device_gunzip_files or fallback_files moves."""
+    auto = device_gunzip is None
+    if auto:
+        device_gunzip = _gz_members_file(path)
+    if device_gunzip:
+        got = members()
+        if got is not None:
+            counts.device_gunzip_files += 1
+            return got
+        if not auto:
+            raise NotTaken(f"{path}: {reason()}")
+        counts.fallback_files += 1
+        if again:
+            again()
+    return host()
+
+
 class RowFilter:
     """rows of a TSV whose first (`first_field=True`) or last field is one of `keys`, filtered on the device"""
 
@@ -55,8 +118,7 @@ class RowFilter:
     def __init__(self, keys, first_field, device=0):
         self.L = _lib.load()
         ks = [k.encode() if isinstance(k, str) else bytes(k) for k in keys]
-        arr = (C.c_char_p * max(len(ks), 1))(*ks)
-        lens = (C.c_uint32 * max(len(ks), 1))(*[len(k) for k in ks])
+        arr, lens = _lib.c_strings(ks)
         self.h = C.c_void_p()
         self.fallbacks = 0              # files the automatic mode began on the device and read again through gzip
         _lib.check(self.L.pf_rowfilter_create(int(device), 1 if first_field else 0, arr, lens, len(ks), C.byref(self.h)))
@@ -103,55 +165,21 @@ class RowFilter:
         return got, int(used.value), bool(taken.value)
 
     def _filter_members(self, path, block_bytes):
-        """filter_file's device gunzip route: (header, rows), or None with the library's reason logged when a block was
-        not taken.  Blocks of the compressed file go up as they are; what follows a block's last whole member is put in
-        front of the next block."""
-        block = max(1, block_bytes or BLOCK_BYTES // GZ_BLOCK_DIVISOR)
+        """filter_file's device gunzip route: (header, rows), or None when a block was not taken"""
         out = []
-        _lib.check(self.L.pf_rowfilter_members_begin(self.h, 1))
-        with open(path, "rb") as fh:
-            carry, eof = b"", False
-            while True:
-                if not eof:
-                    chunk = fh.read(block)
-                    eof = len(chunk) < block
-                    carry = carry + chunk if carry else chunk
-                got, used, taken = self.scan_members(carry, eof)
-                if not taken:
-                    logger.debug("%s: %s", path, self.L.pf_last_error().decode(errors="replace"))
-                    return None
-                out.append(got)
-                carry = carry[used:]
-                if eof and not carry:
-                    break
+
+        def call(data, last):
+            got, used, taken = self.scan_members(data, last)
+            out.append(got)
+            return used, taken
+
+        if not pass_member_file(path, block_bytes, lambda: _lib.check(self.L.pf_rowfilter_members_begin(self.h, 1)), call):
+            return None
         line, n = C.c_void_p(), C.c_uint64()
         _lib.check(self.L.pf_rowfilter_members_header(self.h, C.byref(line), C.byref(n)))
         return (C.string_at(line, n.value) if n.value else b""), b"".join(out)
 
-    def filter_file(self, path, block_bytes=None, device_gunzip=None):
-        """(header line, matching data lines) of a TSV file.  A .gz file made of small members with the plain gzip header
-        (--gpu-compress writes such) is inflated on the device and scanned there: device_gunzip=None tries that for a
-        name ending in .gz whose first bytes are such a header, and reads the whole file again through gzip, as pandas
-        does by the name, when a block is not taken; False never tries; True raises NotTaken instead of reading again.
-        block_bytes then counts compressed bytes.  Otherwise the file is read block by block straight into one buffer;
-        what follows a block's last complete line is moved to the front for the next block."""
-        if device_gunzip is None:
-            device_gunzip = False
-            if str(path).endswith(".gz"):
-                with open(path, "rb") as fh:
-                    device_gunzip = fh.read(10)[:4] == GZ_HEAD
-            auto = True
-        else:
-            auto = False
-        if device_gunzip:
-            got = self._filter_members(path, block_bytes)
-            if got is not None:
-                RowFilter.device_gunzip_files += 1
-                return got
-            if not auto:
-                raise NotTaken(f"{path}: {self.L.pf_last_error().decode(errors='replace')}")
-            self.fallbacks += 1
-            RowFilter.fallback_files += 1
+    def _filter_host(self, path, block_bytes):
         out = []
 
         def scan(buf, n):
@@ -164,19 +192,22 @@ class RowFilter:
             scan_lines(fh, scan, block_bytes)
         return header, b"".join(out)
 
+    def _fell_back(self):
+        self.fallbacks += 1
+
+    def filter_file(self, path, block_bytes=None, device_gunzip=None):
+        """(header line, matching data lines) of a TSV file.  A .gz file made of small members with the plain gzip header
+        (--gpu-compress writes such) is inflated on the device and scanned there, as device_gunzip says (route_file);
+        block_bytes then counts compressed bytes.  Otherwise the file is read block by block straight into one buffer;
+        what follows a block's last complete line is moved to the front for the next block."""
+        return route_file(path, device_gunzip, lambda: self._filter_members(path, block_bytes),
+                          lambda: self._filter_host(path, block_bytes), RowFilter, self._fell_back)
+
 
 KJ_FLAG_NAMES = ((1, "not 10 tabs"), (2, "a control, non-ASCII or quote byte"), (4, "an integer field that is not canonical decimal"),
                  (8, "an empty text field"), (16, "an NA string"), (32, "a text field of number characters only"),
                  (64, "inf / nan / true / false"), (128, "a row over 65 536 or a field of 4 096 bytes or more"))
 KJ_RAW = 2                          # KmerJoin.join_file's mode: the rows that have a key, as they stand
-
-
-def _gz_members_file(path):
-    """whether the file is a .gz whose first bytes are the only header the device decoder takes"""
-    if not str(path).endswith(".gz"):
-        return False
-    with open(path, "rb") as fh:
-        return fh.read(10)[:4] == GZ_HEAD
 
 
 class KmerJoin:
@@ -196,11 +227,7 @@ class KmerJoin:
         self.h = C.c_void_p()
         self.n_bunches = max(int(n_bunches), 1)
         self.members = {}               # path -> whether the survey went the device gunzip route to the end
-
-        def strs(items):
-            n = max(len(items), 1)
-            return (C.c_char_p * n)(*items), (C.c_uint32 * n)(*[len(x) for x in items])
-
+        strs = _lib.c_strings
         cl, cl_len = strs([c for c, _ in clusters])
         bunch = (C.c_uint32 * max(len(clusters), 1))(*[b for _, b in clusters])
         kc, kc_len = strs([c for c, _ in keys])
@@ -241,27 +268,16 @@ class KmerJoin:
                 return
             write(memoryview((C.c_char * n.value).from_address(piece.value)))
 
-    def _pass_members(self, path, block_bytes, call, write):
-        """one pass over a file of device members; False, with the library's reason logged, when a block was not taken"""
-        block = max(1, block_bytes or BLOCK_BYTES // GZ_BLOCK_DIVISOR)
-        _lib.check(self.L.pf_kmerjoin_members_begin(self.h, 1))
-        with open(path, "rb") as fh:
-            carry, eof = b"", False
-            while True:
-                if not eof:
-                    chunk = fh.read(block)
-                    eof = len(chunk) < block
-                    carry = carry + chunk if carry else chunk
-                used, taken = C.c_uint64(), C.c_int()
-                call(carry, len(carry), 1 if eof else 0, used, taken)
-                if not taken.value:
-                    logger.debug("%s: %s", path, self.L.pf_last_error().decode(errors="replace"))
-                    return False
-                if write:
-                    self._drain(write)
-                carry = carry[used.value:]
-                if eof and not carry:
-                    return True
+    def _pass_members(self, path, block_bytes, fn, args, write):
+        """one pass over a file of device members, fn(handle, block, its bytes, last, *args, &used, &taken) a block; False
+        when a block was not taken"""
+        def call(data, last):
+            used, taken = C.c_uint64(), C.c_int()
+            _lib.check(fn(self.h, data, len(data), 1 if last else 0, *args, C.byref(used), C.byref(taken)))
+            return used.value, taken.value
+
+        return pass_member_file(path, block_bytes, lambda: _lib.check(self.L.pf_kmerjoin_members_begin(self.h, 1)), call,
+                                (lambda: self._drain(write)) if write else None)
 
     def _pass_plain(self, path, block_bytes, call, write):
         def scan(buf, n):
@@ -277,32 +293,24 @@ class KmerJoin:
 
     def survey_file(self, path, block_bytes=None, device_gunzip=None):
         """one pass over kmers.tsv for all bunches: counters().  device_gunzip as RowFilter.filter_file's"""
-        auto = device_gunzip is None
-        if auto:
-            device_gunzip = _gz_members_file(path)
+        def members():
+            self.members[path] = self._pass_members(path, block_bytes, self.L.pf_kmerjoin_survey_members, (), None)
+            return True if self.members[path] else None
+
+        def host():
+            self._pass_plain(path, block_bytes, lambda ptr, n, used: _lib.check(self.L.pf_kmerjoin_survey(self.h, ptr, n, C.byref(used))), None)
+            return True
+
         self.members[path] = False
-        if device_gunzip:
-            def call(data, n, last, used, taken):
-                _lib.check(self.L.pf_kmerjoin_survey_members(self.h, data, n, last, C.byref(used), C.byref(taken)))
-            if self._pass_members(path, block_bytes, call, None):
-                KmerJoin.device_gunzip_files += 1
-                self.members[path] = True
-                return self.counters()
-            if not auto:
-                raise NotTaken(f"{path}: {self.L.pf_last_error().decode(errors='replace')}")
-            KmerJoin.fallback_files += 1
-            _lib.check(self.L.pf_kmerjoin_reset_counters(self.h))
-        self._pass_plain(path, block_bytes, lambda ptr, n, used: _lib.check(self.L.pf_kmerjoin_survey(self.h, ptr, n, C.byref(used))), None)
+        # (a survey that stopped half way has counted rows: they go before the file is read again)
+        route_file(path, device_gunzip, members, host, KmerJoin, lambda: _lib.check(self.L.pf_kmerjoin_reset_counters(self.h)))
         return self.counters()
 
     def join_file(self, path, bunch, mode, write, block_bytes=None):
         """one pass over kmers.tsv for one bunch: its annotated rows (mode 0 / 1: the rendering) or its raw rows that have
         a key (KJ_RAW) go to write(), in file order.  The file goes the way the survey found for it."""
         if self.members.get(path):
-            def call(data, n, last, used, taken):
-                out_n = C.c_uint64()
-                _lib.check(self.L.pf_kmerjoin_join_members(self.h, data, n, last, bunch, mode, C.byref(out_n), C.byref(used), C.byref(taken)))
-            if not self._pass_members(path, block_bytes, call, write):
+            if not self._pass_members(path, block_bytes, self.L.pf_kmerjoin_join_members, (bunch, mode, C.byref(C.c_uint64())), write):
                 raise NotTaken(f"{path}: {self.L.pf_last_error().decode(errors='replace')} (the survey pass took the file)")
             KmerJoin.device_gunzip_files += 1
             return

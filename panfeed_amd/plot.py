@@ -200,8 +200,7 @@ class GridBuilder:
         self._lib = _lib
         self.L = _lib.load()
         names = [str(s).encode() for s in strains]
-        arr = (C.c_char_p * max(len(names), 1))(*names)
-        lens = (C.c_uint32 * max(len(names), 1))(*[len(s) for s in names])
+        arr, lens = _lib.c_strings(names)
         cols = (C.c_int32 * 6)(*columns)
         zoom = start is not None
         self.h = C.c_void_p()

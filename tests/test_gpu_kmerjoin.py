@@ -152,6 +152,83 @@ def test_golden_runs_over_small_blocks_and_gzip_inputs(tmp_path, eng, how):
         downstream.BLOCK_BYTES = old
 
 
+FEED_BLOCK = 4096 // 8          # compressed bytes a read: what the device_gz case above makes of its smaller BLOCK_BYTES
+
+
+@pytest.fixture(scope="module")
+def feed_file(tmp_path_factory, eng):
+    """the first fixture's kmers.tsv, plain and device-gzipped: (its bytes, the plain path, the .gz path).  Read FEED_BLOCK
+    compressed bytes at a time a member straddles calls, and the members' cut lies inside a line"""
+    from device_gz_files import member_sizes
+    text = CASES[FIX[0]["case"]]["expect"]["kmers.tsv"].encode()
+    d = tmp_path_factory.mktemp("feed")
+    plain, gz = str(d / "kmers.tsv"), str(d / "kmers.tsv.gz")
+    with open(plain, "wb") as fh:
+        fh.write(text)
+    cut = text.index(b"\n") + 1
+    write_device_gz(eng, gz, text[:cut], text[cut:])
+    chunk = eng.L.pf_gzip_device_chunk_bytes()
+    with open(gz, "rb") as fh:
+        sizes = member_sizes(fh.read())
+    assert len(sizes) >= 3 and max(sizes) > 2 * FEED_BLOCK and len(text) > cut + chunk and text[cut + chunk - 1:cut + chunk] != b"\n"
+    return text, plain, gz
+
+
+def _feed_counts(st):
+    return st["members_inflated"], st["text_bytes_inflated"]
+
+
+def test_the_row_filter_and_the_join_run_the_same_feed(feed_file):
+    """one process, the two owners of a device text feed by turns over the same member file: the same members and text
+    bytes inflated a pass, all of the file's, and the same header line peeled off"""
+    import ctypes as C
+    from panfeed_amd import _lib
+    from panfeed_amd.downstream import KmerJoin, RowFilter
+    text, _plain, gz = feed_file
+    header = text[:text.index(b"\n") + 1]
+    cluster = text[len(header):].split(b"\t", 1)[0]
+    rf, kj = RowFilter([cluster], first_field=True), KmerJoin([(cluster, 0)], 1, [], [], [], b"")
+    try:
+        seen = [_feed_counts(rf.stats()), _feed_counts(kj.stats())]
+        for _turn in range(2):
+            got_header, rows = rf.filter_file(gz, block_bytes=FEED_BLOCK, device_gunzip=True)
+            assert got_header == header and rows and all(ln.split(b"\t", 1)[0] == cluster for ln in rows.splitlines())
+            plan = kj.survey_file(gz, block_bytes=FEED_BLOCK, device_gunzip=True)
+            assert plan[0]["rows"] == len(rows.splitlines())
+            line, n = C.c_void_p(), C.c_uint64()
+            _lib.check(kj.L.pf_kmerjoin_members_header(kj.h, C.byref(line), C.byref(n)))
+            assert C.string_at(line, n.value) == header
+            now = [_feed_counts(rf.stats()), _feed_counts(kj.stats())]
+            passes = [tuple(b - a for a, b in zip(before, after)) for before, after in zip(seen, now)]
+            print(passes)
+            assert passes[0] == passes[1] and passes[0][0] >= 3 and passes[0][1] == len(text)
+            seen = now
+            _lib.check(kj.L.pf_kmerjoin_reset_counters(kj.h))
+    finally:
+        rf.close()
+        kj.close()
+
+
+def test_a_join_without_clusters_or_keys_surveys_by_both_routes(feed_file):
+    """the join's handle is a feed and its own tables, nothing of a row filter: with no cluster and no key it reads the whole
+    file either way and finds no row"""
+    from panfeed_amd.downstream import KmerJoin
+    text, plain, gz = feed_file
+    body = len(text) - (text.index(b"\n") + 1)
+    kj = KmerJoin([], 0, [], [], [], b"")
+    try:
+        scanned = 0
+        for path, route in ((gz, True), (plain, False), (gz, False)):
+            plan = kj.survey_file(path, block_bytes=FEED_BLOCK if route else 4096, device_gunzip=route)
+            assert plan == [{"rows": 0, "unmatched": 0, "bytes": (0, 0), "flags": 0}], (path, route)
+            st = kj.stats()
+            assert st["bytes_scanned"] - scanned == body, (path, route)
+            scanned = st["bytes_scanned"]
+        assert st["members_inflated"] >= 3 and st["text_bytes_inflated"] == len(text) and st["rows_written"] == 0
+    finally:
+        kj.close()
+
+
 def _handmade_files(tmp_path, t):
     (tmp_path / "assoc.tsv").write_text(t["assoc"])
     (tmp_path / "kh.tsv").write_bytes(t["kh"])

@@ -1,6 +1,7 @@
 """The text-table models without a GPU: the case lists of tests/text_tables.py reach every class of the classifier (so
 that thinning a list cannot quietly lose an edge), the pure-Python models agree with pandas where pandas reads a table
-the same way, the block reader under both scanners (`scan_lines`) shows its consumer every byte once, and the ordered
+the same way, the block reader under both scanners (`scan_lines`) shows its consumer every byte once, as does the pass
+over a file of gzip members (`pass_member_file`), `route_file` chooses between the two as it says, and the ordered
 64-bit keys of the plot grids order doubles as IEEE does."""
 import gzip
 import io
@@ -230,6 +231,125 @@ def test_scan_lines_header_only_long_line_and_gzip(tmp_path):
     for block in (1, 13, 64, 1 << 16):
         with open_table(str(p)) as fh:
             assert b"".join(_shown(fh, block)) == LADDER + b"unterminated\n", block
+
+
+# ------------------------------------------------------------------------------------------------ the member-file pass
+REC = 7                                                       # the stub's "members": records of REC bytes, b"<nnnnn>"
+MEMBER_FILE = b"".join(b"<%05d>" % i for i in range(6))
+
+
+class MemberStub:
+    """a stand-in for a device text feed: takes the whole records at the front of a block once it holds `need` of them (or
+    the file ends), and keeps what it was shown and what it used up; at call number `refuse_at` it takes nothing"""
+
+    def __init__(self, need=1, refuse_at=None):
+        self.need, self.refuse_at = need, refuse_at
+        self.begun, self.lasts, self.used, self.after, self.reasons = 0, [], [], 0, 0
+
+    def begin(self):
+        assert not self.lasts
+        self.begun += 1
+
+    def call(self, data, last):
+        self.lasts.append(last)
+        if len(self.lasts) == self.refuse_at:
+            return 0, False
+        whole = len(data) // REC
+        if last:
+            assert len(data) == whole * REC                    # the end of the file is the end of a record
+        used = whole * REC if last or whole >= self.need else 0
+        assert all(data[i:i + 1] == b"<" and data[i + REC - 1:i + REC] == b">" for i in range(0, used, REC))
+        self.used.append(data[:used])
+        return used, True
+
+    def ran_after(self):
+        self.after += 1
+
+    def reason(self):
+        self.reasons += 1
+        return "the stub's reason"
+
+    def run(self, path, block):
+        from panfeed_amd.downstream import pass_member_file
+        return pass_member_file(path, block, self.begin, self.call, self.ran_after, self.reason)
+
+
+@pytest.fixture(scope="module")
+def member_file(tmp_path_factory):
+    p = tmp_path_factory.mktemp("member_file") / "records.gz"
+    p.write_bytes(MEMBER_FILE)
+    return str(p)
+
+
+# (REC and 2 * REC put every / every other record boundary exactly at a block's end; 1 and REC - 1 make calls that hold no
+# whole record yet, as does every `need` above 1: used == 0, taken, while more of the file remains)
+@pytest.mark.parametrize("need", [1, 2, 4])
+@pytest.mark.parametrize("block", [1, REC - 1, REC, REC + 1, 2 * REC, len(MEMBER_FILE)])
+def test_member_file_pass_shows_every_byte_once(member_file, block, need):
+    s = MemberStub(need)
+    assert s.run(member_file, block) is True
+    assert s.begun == 1 and b"".join(s.used) == MEMBER_FILE and s.reasons == 0
+    # read number i is short, and the end of the file known, when i blocks are more than the file
+    first_last = len(MEMBER_FILE) // block + 1
+    assert s.lasts == [i >= first_last for i in range(1, len(s.lasts) + 1)] and s.lasts[-1] is True
+    assert s.after == len(s.lasts)
+    if block < REC * need:
+        assert b"" in s.used[:-1]                              # some call took nothing yet, and the pass read on
+
+
+@pytest.mark.parametrize("block", [1, REC, REC + 1, len(MEMBER_FILE)])
+@pytest.mark.parametrize("k", [1, 2, "final"])
+def test_member_file_pass_stops_at_a_block_not_taken(member_file, block, k):
+    whole = MemberStub()
+    assert whole.run(member_file, block)
+    k = len(whole.lasts) if k == "final" else k
+    s = MemberStub(refuse_at=k)
+    assert s.run(member_file, block) is False
+    assert len(s.lasts) == k and s.reasons == 1 and s.after == k - 1
+    assert s.lasts == whole.lasts[:k] and s.used == whole.used[:k - 1]
+
+
+class RouteStub:
+    """the two routes and the owner's counters of a route_file call"""
+    device_gunzip_files = fallback_files = 0
+
+    def __init__(self, taken):
+        self.taken, self.log = taken, []
+
+    def run(self, path, device_gunzip):
+        from panfeed_amd.downstream import route_file
+        return route_file(path, device_gunzip, lambda: self.log.append("members") or ("members" if self.taken else None),
+                          lambda: self.log.append("host") or "host", self, lambda: self.log.append("again"), lambda: "the stub's reason")
+
+    def counts(self):
+        return self.device_gunzip_files, self.fallback_files
+
+
+def test_route_decision(tmp_path):
+    from panfeed_amd.downstream import GZ_HEAD, NotTaken
+    device_gz, host_gz, plain = (str(tmp_path / n) for n in ("device.tsv.gz", "host.tsv.gz", "plain.tsv"))
+    (tmp_path / "device.tsv.gz").write_bytes(GZ_HEAD + bytes(6))
+    (tmp_path / "host.tsv.gz").write_bytes(b"\x1f\x8b\x08\x08" + bytes(6))  # FLG = FNAME: a header the device does not take
+    (tmp_path / "plain.tsv").write_bytes(GZ_HEAD + bytes(6))                # the name decides first
+    # automatic: the member route where the file looks like one for it; not taken -> undo, host route, one fallback
+    r = RouteStub(taken=True)
+    assert r.run(device_gz, None) == "members" and r.log == ["members"] and r.counts() == (1, 0)
+    r = RouteStub(taken=False)
+    assert r.run(device_gz, None) == "host" and r.log == ["members", "again", "host"] and r.counts() == (0, 1)
+    for path in (host_gz, plain):
+        r = RouteStub(taken=True)
+        assert r.run(path, None) == "host" and r.log == ["host"] and r.counts() == (0, 0)
+    # forced: whatever the file; not taken -> NotTaken with the reason, and the host route is never called
+    r = RouteStub(taken=True)
+    assert r.run(plain, True) == "members" and r.log == ["members"] and r.counts() == (1, 0)
+    r = RouteStub(taken=False)
+    with pytest.raises(NotTaken, match="the stub's reason"):
+        r.run(device_gz, True)
+    assert r.log == ["members"] and r.counts() == (0, 0)
+    # False never calls the member route
+    r = RouteStub(taken=True)
+    assert r.run(device_gz, False) == "host" and r.log == ["host"] and r.counts() == (0, 0)
+    assert RouteStub.device_gunzip_files == 0 and RouteStub.fallback_files == 0   # (the stubs counted on themselves)
 
 
 # ------------------------------------------------------------------------------------------------ ordered keys
