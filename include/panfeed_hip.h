@@ -661,6 +661,51 @@ int pf_kmerjoin_stats(pf_kmerjoin* j, uint64_t stats[8], float ms[3]);
 void pf_kmerjoin_destroy(pf_kmerjoin* j);
 
 /*
+ * The associations filter on the device: the first step of both downstream tools,
+ * /root/reference/panfeed/get_clusters.py:76-88 and /root/reference/panfeed/get_kmers.py:93-106
+ * (`a = pd.read_csv(associations, sep='\t', index_col=0); a = a[a[column] <= threshold]`), as one pass over the file's
+ * text.  It keeps, as they stand and in file order, the data lines whose cell in field `pvalue_field` MAY be <= the
+ * threshold: a superset, decided on an approximation of the cell's number against thr_hi, the threshold widened by the
+ * caller (threshold + |threshold| * 2^-30); a cell whose magnitude is outside 1e-300 .. 1e300 keeps its row, an NA cell drops
+ * it.  Over ALL data lines it ORs, per column of the header's n_fields, the class of every cell (PF_AF_INT ...) -- what
+ * tells the dtype pandas would have inferred from the whole file -- and the rows' flags (PF_AF_ROW_*).  The caller parses
+ * the kept lines alone and takes the file through pandas whole when a flag, an ODD cell or a mix of classes says so.
+ * create (get_clusters.py:76-84, get_kmers.py:93-101: the column and the threshold): pvalue_field < n_fields.
+ * scan (get_clusters.py:76, get_kmers.py:93: the file's text): a block of data lines that starts at a line start, as
+ * pf_rowfilter_scan takes it; *out_bytes = the bytes of kept lines, *consumed = the bytes of complete lines.
+ * members_begin / members_header / scan_members (the same lines, for a .gz of device-made members): as the row
+ * filter's three calls; the header line is peeled off by the feed.
+ * next_lines (get_clusters.py:85-88, get_kmers.py:102-106: the rows that stay): the kept lines of the last scan piece by
+ * piece, as pf_kmerjoin_next_text (*nbytes = 0: no more; a piece is valid until the call after the next).
+ * columns (the dtypes read_csv infers at get_clusters.py:76 / get_kmers.py:93): n_fields words of class bits, the OR of
+ * the rows' flags, counters[0] data lines and counters[1] kept lines so far (the pointer is valid until the next call).
+ * stats (either may be NULL): stats[0] bytes scanned, [1] members and [2] text bytes inflated, [3] the decoder's device
+ * bytes; ms[0] the filter's kernels, ms[1] inflate.
+ */
+#define PF_AF_INT 1u         /* [+-]?[0-9]{1,18} */
+#define PF_AF_FLOAT 2u       /* [+-]?([0-9]+\.?[0-9]*|\.[0-9]+)([eE][+-]?[0-9]+)? that is neither INT nor ODD */
+#define PF_AF_NA 4u          /* the empty cell or one of pandas' default NA strings */
+#define PF_AF_ODD 8u         /* inf / infinity / nan / true / false with an optional sign in any case (and no NA string), a space at
+                                either end, an integer of more than 18 digits, a number of more than 18 integer digits or more than
+                                5 exponent digits or whose exponent plus integer digits exceed 300 */
+#define PF_AF_TEXT 16u       /* everything else */
+#define PF_AF_ROW_FIELDS 1u  /* not as many fields as the header */
+#define PF_AF_ROW_EMPTY 2u   /* an empty line */
+#define PF_AF_ROW_BYTES 4u   /* a byte below 0x20 other than tab and newline, or a double quote */
+#define PF_AF_ROW_LONG 8u    /* a row of more than 65 536 bytes, or a field of 4 096 bytes or more */
+typedef struct pf_assocfilter pf_assocfilter;
+int pf_assocfilter_create(int device, uint32_t pvalue_field, uint32_t n_fields, double thr_hi, pf_assocfilter** out);
+int pf_assocfilter_scan(pf_assocfilter* f, const char* text, uint64_t nbytes, uint64_t* out_bytes, uint64_t* consumed);
+int pf_assocfilter_members_begin(pf_assocfilter* f, int header);
+int pf_assocfilter_members_header(pf_assocfilter* f, const char** line, uint64_t* nbytes);
+int pf_assocfilter_scan_members(pf_assocfilter* f, const char* members, uint64_t nbytes, int last, uint64_t* out_bytes,
+                                uint64_t* consumed, int* taken);
+int pf_assocfilter_next_lines(pf_assocfilter* f, const char** piece, uint64_t* nbytes);
+int pf_assocfilter_columns(pf_assocfilter* f, const uint32_t** class_bits, uint32_t* n_fields, uint32_t* row_flags, uint64_t counters[2]);
+int pf_assocfilter_stats(pf_assocfilter* f, uint64_t stats[4], float ms[2]);
+void pf_assocfilter_destroy(pf_assocfilter* f);
+
+/*
  * panfeed-plot's per-cluster grids on the device, over the annotated k-mer table that
  * panfeed-get-kmers writes.  Replaces /root/reference/panfeed/plot.py:195-222 (the whole table in one pandas frame, the
  * `isin` strain filter at :200, the base letter / scalar at :209-222) and the three pivot_tables per cluster at

@@ -155,7 +155,10 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_rowfilter_members_begin", "pf_rowfilter_members_header", "pf_rowfilter_scan_members", "pf_rowfilter_gunzip_stats",
            "pf_kmerjoin_create", "pf_kmerjoin_survey", "pf_kmerjoin_members_begin", "pf_kmerjoin_members_header",
            "pf_kmerjoin_survey_members", "pf_kmerjoin_reset_counters", "pf_kmerjoin_counters", "pf_kmerjoin_join",
-           "pf_kmerjoin_join_members", "pf_kmerjoin_next_text", "pf_kmerjoin_stats", "pf_kmerjoin_destroy"]
+           "pf_kmerjoin_join_members", "pf_kmerjoin_next_text", "pf_kmerjoin_stats", "pf_kmerjoin_destroy",
+           "pf_assocfilter_create", "pf_assocfilter_scan", "pf_assocfilter_members_begin", "pf_assocfilter_members_header",
+           "pf_assocfilter_scan_members", "pf_assocfilter_next_lines", "pf_assocfilter_columns", "pf_assocfilter_stats",
+           "pf_assocfilter_destroy"]
 
 RENDER_NO_PATTERN_ROWS = 1
 GZ_FIXED_ONLY, GZ_DYNAMIC_ONLY, GZ_LITERALS_ONLY = 1, 2, 4     # pf_gzip_device / pf_set_device_gzip test hooks; 0: the product
@@ -319,6 +322,17 @@ def _load_locked():
     L.pf_kmerjoin_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.pf_kmerjoin_destroy.argtypes = [C.c_void_p]
     L.pf_kmerjoin_destroy.restype = None
+    L.pf_assocfilter_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_void_p)]
+    L.pf_assocfilter_scan.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, u64p, u64p]
+    L.pf_assocfilter_members_begin.argtypes = [C.c_void_p, C.c_int]
+    L.pf_assocfilter_members_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), u64p]
+    L.pf_assocfilter_scan_members.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, u64p, u64p, C.POINTER(C.c_int)]
+    L.pf_assocfilter_next_lines.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), u64p]
+    L.pf_assocfilter_columns.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                         C.c_void_p]
+    L.pf_assocfilter_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pf_assocfilter_destroy.argtypes = [C.c_void_p]
+    L.pf_assocfilter_destroy.restype = None
     L.pf_submit_gather.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Gather), C.POINTER(Result)]
     L.pf_records_free.argtypes = [C.c_void_p]
     L.pf_records_free.restype = None

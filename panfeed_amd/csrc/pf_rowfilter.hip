@@ -1417,8 +1417,8 @@ template <bool FLAGS> __device__ void kj_walk(const unsigned char* t, uint64_t s
 }
 
 // line_start(s) for every line of [begin, n) whose preceding newline -- or, for the line at 0, the block's start -- is in
-// this thread's 16 vectors, in file order
-template <class F> __device__ __forceinline__ void kj_each_line(const KjParams& p, F&& line_start) {
+// this thread's 16 vectors, in file order.  P: the join's parameters or the associations filter's -- text, n and begin
+template <class P, class F> __device__ __forceinline__ void kj_each_line(const P& p, F&& line_start) {
     const uint64_t nvec = (p.n + 15) / 16;
     const uint64_t v0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
     if (v0 == 0 && p.begin == 0 && p.n) line_start(0);
@@ -1572,6 +1572,34 @@ __global__ __launch_bounds__(256) void kj_write_kernel(KjParams p, uint64_t n_ro
     }
 }
 
+// The text a pass wrote on the device, d_out[0 .. bytes), handed out piece by piece through two pinned buffers: the k-mer
+// join's rows and the associations filter's kept lines
+struct KjHandout {
+    DevBuf d_out;
+    PinBuf pin[2];
+    uint64_t bytes = 0, pos = 0, flying = 0;      // the text's bytes, those handed out or on their way, the piece on its way
+    int cur = 0;
+    void reset() { bytes = pos = flying = 0; }
+    // *nbytes = 0: no more; a piece is valid until the call after the next
+    int next(hipStream_t st, const char** piece, uint64_t* nbytes) {
+        *piece = nullptr; *nbytes = 0;
+        auto start = [&]() -> int {                    // the next piece on its way into pin[cur]
+            flying = std::min<uint64_t>(KJ_PIECE, bytes - pos);
+            if (!flying) return PF_OK;
+            PFCHK(pin[cur].ensure((size_t)std::min<uint64_t>(KJ_PIECE, bytes), true));
+            HIPCHK(hipMemcpyAsync(pin[cur].p, d_out.as<char>() + pos, (size_t)flying, hipMemcpyDeviceToHost, st));
+            pos += flying;
+            return PF_OK;
+        };
+        if (!flying) PFCHK(start());
+        if (!flying) return PF_OK;
+        HIPCHK(hipStreamSynchronize(st));
+        *piece = pin[cur].as<char>(); *nbytes = flying;
+        cur ^= 1;
+        return start();                                // (into the other buffer, while the caller writes this one)
+    }
+};
+
 }  // namespace
 
 struct pf_kmerjoin {
@@ -1579,11 +1607,9 @@ struct pf_kmerjoin {
     uint64_t ccap = 0, kcap = 0;
     uint32_t empty_off = 0, empty_len = 0;
     DevBuf d_chash, d_cslot, d_clusters, d_khash, d_kslot, d_keys, d_arena, d_counters, d_misc;     // d_misc: rejects, err, unmatched
-    DevBuf d_thr, d_tile, d_rec, d_out;
-    PinBuf pin[2];
+    DevBuf d_thr, d_tile, d_rec;
     std::vector<uint64_t> counters;
-    uint64_t out_bytes = 0, out_pos = 0, flying = 0;      // the join's text: its bytes, those handed out or on their way, the piece on its way
-    int cur = 0;
+    KjHandout out;                               // the join's text
     uint64_t bytes_scanned = 0, rows_written = 0, raw_rows = 0;
     float survey_ms = 0, write_ms = 0;
     TextFeed feed;                               // (its stream goes first: a piece of text may be on its way down into pin)
@@ -1620,9 +1646,9 @@ int kj_survey_device(pf_kmerjoin* j, uint64_t n, uint64_t begin) {
     return PF_OK;
 }
 
-// the join of d_text[begin .. n) for one bunch: the text in d_out[0 .. out_bytes), ready to be handed out
+// the join of d_text[begin .. n) for one bunch: the text in out.d_out[0 .. out.bytes), ready to be handed out
 int kj_join_device(pf_kmerjoin* j, uint64_t n, uint64_t begin, uint32_t bunch, int mode) {
-    j->out_bytes = j->out_pos = j->flying = 0;
+    j->out.reset();
     if (n <= begin) return PF_OK;
     if (bunch >= j->n_bunches || mode < 0 || mode > 2) return fail(PF_ERR_ARG, "pf_kmerjoin_join: no such bunch or mode");
     TimedStream& ts = j->feed.ts;
@@ -1649,8 +1675,8 @@ int kj_join_device(pf_kmerjoin* j, uint64_t n, uint64_t begin, uint32_t bunch, i
     unsigned int err = 0;
     if (n_rows) {
         PFCHK(j->d_rec.ensure((size_t)n_rows * sizeof(KjRec)));
-        PFCHK(j->d_out.ensure((size_t)n_bytes));
-        p.rec = j->d_rec.as<KjRec>(); p.out = j->d_out.as<unsigned char>();
+        PFCHK(j->out.d_out.ensure((size_t)n_bytes));
+        p.rec = j->d_rec.as<KjRec>(); p.out = j->out.d_out.as<unsigned char>();
         PFCHK(ts.timed([&]() -> int {
             hipLaunchKernelGGL(kj_place_kernel, dim3(tiles), dim3(256), 0, ts.stream, p, n_rows, n_bytes);
             HIPCHK(hipGetLastError());
@@ -1664,7 +1690,7 @@ int kj_join_device(pf_kmerjoin* j, uint64_t n, uint64_t begin, uint32_t bunch, i
     if (n_rows) ts.add_elapsed(&ms);
     j->write_ms += ms;
     if (err) return fail(PF_ERR_STATE, "pf_kmerjoin_join: a row of the bunch is not one the survey passed (flags 0x%x): the file has changed", err);
-    j->out_bytes = n_bytes;
+    j->out.bytes = n_bytes;
     if (mode == 2) j->raw_rows += n_rows; else j->rows_written += n_rows;
     return PF_OK;
 }
@@ -1787,10 +1813,10 @@ int pf_kmerjoin_counters(pf_kmerjoin* j, const uint64_t** counters, uint32_t* n_
 int pf_kmerjoin_join(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint32_t bunch, int mode, uint64_t* out_bytes, uint64_t* consumed) {
     if (!j || !out_bytes || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_kmerjoin_join: null argument");
     HIPCHK(hipSetDevice(j->feed.device));
-    *out_bytes = 0; j->out_bytes = j->out_pos = j->flying = 0;
+    *out_bytes = 0; j->out.reset();
     PFCHK(j->feed.plain(text, nbytes, consumed));
     PFCHK(kj_join_device(j, *consumed, 0, bunch, mode));
-    *out_bytes = j->out_bytes;
+    *out_bytes = j->out.bytes;
     return PF_OK;
 }
 
@@ -1798,32 +1824,17 @@ int pf_kmerjoin_join_members(pf_kmerjoin* j, const char* members, uint64_t nbyte
                              uint64_t* out_bytes, uint64_t* consumed, int* taken) {
     if (!j || !out_bytes || !consumed || !taken || (nbytes && !members)) return fail(PF_ERR_ARG, "pf_kmerjoin_join_members: null argument");
     HIPCHK(hipSetDevice(j->feed.device));
-    *out_bytes = 0; j->out_bytes = j->out_pos = j->flying = 0;
+    *out_bytes = 0; j->out.reset();
     PFCHK(j->feed.members(members, nbytes, last, consumed, taken,
                            [j, bunch, mode](uint64_t n, uint64_t skip) { return kj_join_device(j, n, skip, bunch, mode); }));
-    *out_bytes = j->out_bytes;
+    *out_bytes = j->out.bytes;
     return PF_OK;
 }
 
 int pf_kmerjoin_next_text(pf_kmerjoin* j, const char** piece, uint64_t* nbytes) {
     if (!j || !piece || !nbytes) return fail(PF_ERR_ARG, "pf_kmerjoin_next_text: null argument");
     HIPCHK(hipSetDevice(j->feed.device));
-    *piece = nullptr; *nbytes = 0;
-    hipStream_t st = j->feed.ts.stream;
-    auto start = [&]() -> int {                    // the next piece on its way into pin[cur]
-        j->flying = std::min<uint64_t>(KJ_PIECE, j->out_bytes - j->out_pos);
-        if (!j->flying) return PF_OK;
-        PFCHK(j->pin[j->cur].ensure((size_t)std::min<uint64_t>(KJ_PIECE, j->out_bytes), true));
-        HIPCHK(hipMemcpyAsync(j->pin[j->cur].p, j->d_out.as<char>() + j->out_pos, (size_t)j->flying, hipMemcpyDeviceToHost, st));
-        j->out_pos += j->flying;
-        return PF_OK;
-    };
-    if (!j->flying) PFCHK(start());
-    if (!j->flying) return PF_OK;
-    HIPCHK(hipStreamSynchronize(st));
-    *piece = j->pin[j->cur].as<char>(); *nbytes = j->flying;
-    j->cur ^= 1;
-    return start();                                // (into the other buffer, while the caller writes this one)
+    return j->out.next(j->feed.ts.stream, piece, nbytes);
 }
 
 int pf_kmerjoin_stats(pf_kmerjoin* j, uint64_t stats[8], float ms[3]) {
@@ -1836,6 +1847,343 @@ int pf_kmerjoin_stats(pf_kmerjoin* j, uint64_t stats[8], float ms[3]) {
         stats[4] = j->feed.gz_text_bytes; stats[5] = j->feed.dec.device_bytes(); stats[6] = misc[0]; stats[7] = misc[2];
     }
     if (ms) { ms[0] = j->survey_ms; ms[1] = j->write_ms; ms[2] = j->feed.gz_ms; }
+    return PF_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The associations filter: the first step of both downstream tools,
+//   /root/reference/panfeed/get_clusters.py:76-88, /root/reference/panfeed/get_kmers.py:93-106
+//     a = pd.read_csv(associations, sep='\t', index_col=0);  a = a[a[column] <= threshold]
+// as one pass over the file's text, a third owner of the TextFeed.  The host parses with pandas only the lines this pass
+// keeps; that the table comes out as from the whole file rests on two things the pass finds out:
+//   the kept lines   every data line whose p-value cell MAY satisfy value <= threshold, as it stands, in file order.  The
+//                    decision is a superset: the cell's text becomes a double within 2^-48 of the decimal it spells (see
+//                    af_value) and the row is dropped only above thr_hi, the threshold widened by 2^-30; pandas decides
+//                    exactly on what is left
+//   the classes      per column, the OR over ALL data rows of each cell's class (AF_INT ...): they tell the dtype pandas
+//                    would have inferred for the column from the whole file, and so how to_csv prints the kept rows
+// and the OR of the rows' flags (AF_ROW_*): a flagged table, one with an AF_ODD cell or one whose classes pandas would mix
+// goes through pandas whole (the routing is the caller's).
+// Kernels: af_plan_kernel walks every line once -- classes, flags, keep or drop, per-thread rows and bytes --,
+// kj_tiles_kernel, af_place_kernel (the walk of the p-value cell alone) and the raw rows of kj_write_kernel.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+enum : uint32_t { AF_INT = PF_AF_INT, AF_FLOAT = PF_AF_FLOAT, AF_NA = PF_AF_NA, AF_ODD = PF_AF_ODD, AF_TEXT = PF_AF_TEXT };
+enum : uint32_t { AF_ROW_FIELDS = PF_AF_ROW_FIELDS, AF_ROW_EMPTY = PF_AF_ROW_EMPTY, AF_ROW_BYTES = PF_AF_ROW_BYTES, AF_ROW_LONG = PF_AF_ROW_LONG };
+constexpr uint32_t AF_LDS_COLS = 256;            // columns whose class bits a workgroup gathers in LDS; the rest go to HBM
+constexpr uint32_t AF_DIGITS = 17;               // digits of a number's text that count, leading zeros among them, as in pandas
+constexpr uint32_t AF_INT_DIGITS = 18;           // an integer of more digits may not fit int64
+constexpr uint32_t AF_EXP_DIGITS = 5;
+constexpr int32_t AF_DECADES = 300;              // |value| within 1e-300 .. 1e300 is decided here
+
+struct AfParams {
+    const unsigned char* text;   // the block, complete lines
+    uint64_t n, begin;           // lines that start in [begin, n)
+    uint32_t pvalue_field, n_fields;
+    double thr_hi;
+    unsigned int* cols;          // n_fields words of class bits
+    unsigned int* flags;         // [0] the OR of the rows' flags, [1] a place kernel that found other rows than the plan
+    unsigned long long* rows;    // data lines
+    uint2* thr; unsigned long long* tile; KjRec* rec;
+};
+
+// One cell, byte by byte: the number grammar  [+-]?([0-9]+\.?[0-9]*|\.[0-9]+)([eE][+-]?[0-9]+)?  and what its value needs.
+// st: 0 nothing yet, 1 sign, 2 integer digits, 3 behind the point with a digit somewhere, 4 a point and no digit yet, 6 e,
+// 7 the exponent's sign, 8 exponent digits, 9 no number; a number ends in 2, 3 or 8
+struct AfCell {
+    uint32_t st = 0, n_int = 0, taken = 0, sig = 0, n_exp = 0, len = 0;
+    int32_t adj = 0, ex = 0;
+    bool neg = false, eneg = false;
+    unsigned char first = 0, last = 0;
+    uint64_t m = 0;
+    __device__ __forceinline__ void step(unsigned char c) {
+        if (!len) first = c;
+        last = c; len++;
+        const uint32_t d = (uint32_t)c - '0';
+        if (d < 10) {
+            const bool take = taken < AF_DIGITS;
+            if (st <= 2) { st = 2; n_int++; if (!take) adj++; }
+            else if (st == 3 || st == 4) { st = 3; if (take) adj--; }
+            else if (st >= 6 && st <= 8) { st = 8; n_exp++; if (ex < 100000) ex = ex * 10 + (int32_t)d; return; }
+            else { st = 9; return; }
+            if (take) { m = m * 10 + d; taken++; if (m) sig++; }
+        } else if (c == '+' || c == '-') {
+            if (st == 0) { st = 1; neg = c == '-'; } else if (st == 6) { st = 7; eneg = c == '-'; } else st = 9;
+        } else if (c == '.') {
+            st = st == 2 ? 3 : st <= 1 ? 4 : 9;
+        } else if (c == 'e' || c == 'E') {
+            st = (st == 2 || st == 3) ? 6 : 9;
+        } else st = 9;
+    }
+};
+
+// the class of a finished cell; s: its bytes.  AF_ODD: a cell pandas may read otherwise in a subset of the file than in the
+// whole -- a word of kj_words, a space at either end, an integer of more than 18 digits, and a number its float parser
+// may refuse or overflow (more than 18 integer digits, more than 5 exponent digits, 1e300 or more by its exponent)
+__device__ uint32_t af_class(const AfCell& c, const unsigned char* s) {
+    if (!c.len) return AF_NA;
+    if (c.first == ' ' || c.last == ' ') return AF_ODD;
+    if (c.st == 2) return c.n_int <= AF_INT_DIGITS ? AF_INT : AF_ODD;
+    if (c.st == 3 || c.st == 8)
+        return (c.n_int > AF_INT_DIGITS || c.n_exp > AF_EXP_DIGITS || (!c.eneg && c.ex + (int32_t)c.n_int > AF_DECADES)) ? AF_ODD : AF_FLOAT;
+    if (c.len <= 9) {
+        if (kj_in_list(kj_na_strings, s, c.len, false)) return AF_NA;
+        const uint32_t sign = (s[0] == '+' || s[0] == '-') ? 1 : 0;
+        if (kj_in_list(kj_words, s + sign, c.len - sign, true)) return AF_ODD;
+    }
+    return AF_TEXT;
+}
+
+// Whether a p-value cell of class AF_INT or AF_FLOAT may be <= the threshold.  Its value as pandas' parser takes it is
+// m * 10^e: m the first 17 digits of the text (leading zeros count, an integer digit behind them raises e, a fraction digit
+// behind them is dropped).  m = 0 is exactly +-0.  Else m has `sig` digits and |value| lies in [10^(sig-1+e), 10^(sig+e)):
+// outside 1e-300 .. 1e300 the row is undecided and kept.  Inside, v = double(m) times at most nine of 10^(+-2^k):
+// the conversion rounds once (m < 10^17 has up to 57 bits), every factor is within 2^-53 of its power and every product rounds
+// once, no product leaves the normal range (they move from m >= 1 towards the result monotonically): |v / (m 10^e) - 1| <=
+// (1 + 2 * 9) * 2^-53 < 2^-48.  The row is dropped only if v > thr_hi
+__device__ bool af_keep(const AfCell& c, double thr_hi) {
+    double v = 0.0;
+    if (c.m) {
+        const int32_t e = c.adj + (c.eneg ? -c.ex : c.ex), lo = (int32_t)c.sig - 1 + e;
+        if (lo < -AF_DECADES || lo + 1 > AF_DECADES) return true;
+        v = (double)(long long)c.m;
+        const uint32_t a = (uint32_t)(e < 0 ? -e : e);
+        const double up[9] = {1e1, 1e2, 1e4, 1e8, 1e16, 1e32, 1e64, 1e128, 1e256};
+        const double dn[9] = {1e-1, 1e-2, 1e-4, 1e-8, 1e-16, 1e-32, 1e-64, 1e-128, 1e-256};
+#pragma unroll
+        for (int b = 0; b < 9; b++) if ((a >> b) & 1) v *= e < 0 ? dn[b] : up[b];
+    }
+    return (c.neg ? -v : v) <= thr_hi;
+}
+
+struct AfRow { uint32_t len, flags; bool keep; };       // len with the newline
+
+// the line at s (text[n - 1] is a newline), read a 32-bit word every four bytes.  SURVEY: every cell's class goes to
+// col(field, class) and the row's flags are found; otherwise the p-value cell alone is looked at
+template <bool SURVEY, class C> __device__ void af_walk(const AfParams& p, uint64_t s, AfRow& r, C&& col) {
+    const uint32_t* const words = reinterpret_cast<const uint32_t*>(p.text);
+    uint32_t word = words[s >> 2];
+    uint32_t field = 0, fb = 0, flags = 0, i = 0;
+    AfCell cell;
+    r.keep = false;
+    for (;; i++) {
+        if (i >= KJ_MAX_LINE) { flags |= AF_ROW_LONG; break; }
+        const uint64_t pos = s + i;
+        if (i && !(pos & 3)) word = words[pos >> 2];
+        const unsigned char c = (unsigned char)(word >> ((pos & 3) * 8));
+        if (c == '\t' || c == '\n') {
+            if (i - fb >= RF_MAX_FIELD) flags |= AF_ROW_LONG;
+            if (SURVEY || field == p.pvalue_field) {
+                const uint32_t cls = af_class(cell, p.text + s + fb);
+                if (SURVEY && field < p.n_fields) col(field, cls);
+                if (field == p.pvalue_field) r.keep = (cls & (AF_INT | AF_FLOAT)) && af_keep(cell, p.thr_hi);
+            }
+            if (c == '\n') break;
+            field++; fb = i + 1; cell = AfCell();
+        } else {
+            if (SURVEY && (c < 0x20 || c == '"')) flags |= AF_ROW_BYTES;
+            if (SURVEY || field == p.pvalue_field) cell.step(c);
+        }
+    }
+    if (field + 1 != p.n_fields) flags |= AF_ROW_FIELDS;
+    if (i == 0) flags |= AF_ROW_EMPTY;
+    if (flags & AF_ROW_LONG) r.keep = false;
+    r.len = i + 1; r.flags = flags;
+}
+
+__global__ __launch_bounds__(256) void af_plan_kernel(AfParams p) {
+    __shared__ unsigned int s_cols[AF_LDS_COLS];
+    __shared__ unsigned int s_flags;
+    __shared__ unsigned long long s_lines;
+    for (uint32_t k = threadIdx.x; k < AF_LDS_COLS; k += 256) s_cols[k] = 0;
+    if (threadIdx.x == 0) { s_flags = 0; s_lines = 0; }
+    __syncthreads();
+    unsigned long long rows = 0, bytes = 0, lines = 0;
+    uint32_t flags = 0;
+    // (a bit once set stays set: a stale look can only cost an atomic, never lose a bit)
+    auto col = [&](uint32_t field, uint32_t cls) {
+        unsigned int* const at = field < AF_LDS_COLS ? &s_cols[field] : &p.cols[field];
+        if ((*at & cls) != cls) atomicOr(at, cls);
+    };
+    kj_each_line(p, [&](uint64_t s) {
+        AfRow r;
+        af_walk<true>(p, s, r, col);
+        lines++; flags |= r.flags;
+        if (r.keep) { rows++; bytes += r.len; }
+    });
+    p.thr[(uint64_t)blockIdx.x * 256 + threadIdx.x] = make_uint2((uint32_t)rows, (uint32_t)bytes);
+    if (flags) atomicOr(&s_flags, flags);
+    if (lines) atomicAdd(&s_lines, lines);
+    unsigned long long ta, tb;
+    kj_block_exscan(rows, bytes, &ta, &tb);
+    if (threadIdx.x == 0) {
+        p.tile[2 * (uint64_t)blockIdx.x] = ta; p.tile[2 * (uint64_t)blockIdx.x + 1] = tb;
+        if (s_flags) atomicOr(&p.flags[0], s_flags);
+        if (s_lines) atomicAdd(p.rows, s_lines);
+    }
+    for (uint32_t k = threadIdx.x; k < AF_LDS_COLS && k < p.n_fields; k += 256)
+        if (s_cols[k] & ~p.cols[k]) atomicOr(&p.cols[k], s_cols[k]);
+}
+
+__global__ __launch_bounds__(256) void af_place_kernel(AfParams p, uint64_t n_rows, uint64_t n_bytes) {
+    const uint2 mine = p.thr[(uint64_t)blockIdx.x * 256 + threadIdx.x];
+    unsigned long long row = mine.x, at = mine.y, ta, tb;
+    kj_block_exscan(row, at, &ta, &tb);
+    row += p.tile[2 * (uint64_t)blockIdx.x]; at += p.tile[2 * (uint64_t)blockIdx.x + 1];
+    kj_each_line(p, [&](uint64_t s) {
+        AfRow w;
+        af_walk<false>(p, s, w, [](uint32_t, uint32_t) {});
+        if (!w.keep) return;
+        KjRec r{};
+        r.src = s; r.dst = at; r.len0 = w.len; r.raw = 1;
+        if (row < n_rows && at + w.len <= n_bytes) p.rec[row] = r; else atomicOr(&p.flags[1], 1u);
+        row++; at += w.len;
+    });
+}
+
+}  // namespace
+
+struct pf_assocfilter {
+    uint32_t pvalue_field = 0, n_fields = 0;
+    double thr_hi = 0;
+    DevBuf d_cols, d_misc;                       // d_misc: data lines (8 bytes), the rows' flags and the place kernel's complaint (4 each)
+    DevBuf d_thr, d_tile, d_rec;
+    std::vector<uint32_t> cols;
+    KjHandout out;                               // the kept lines of the last scan
+    uint64_t bytes_scanned = 0, kept = 0;
+    float device_ms = 0;
+    TextFeed feed;                               // (its stream goes first: a piece of text may be on its way down into pin)
+};
+
+namespace {
+
+// the scan of d_text[begin .. n): the kept lines in out.d_out[0 .. out.bytes), ready to be handed out
+int af_scan_device(pf_assocfilter* f, uint64_t n, uint64_t begin) {
+    f->out.reset();
+    if (n <= begin) return PF_OK;
+    TimedStream& ts = f->feed.ts;
+    const uint32_t tiles = kj_tiles(n);
+    PFCHK(f->d_thr.ensure((size_t)tiles * 256 * sizeof(uint2)));
+    PFCHK(f->d_tile.ensure(((size_t)tiles + 1) * 16));
+    AfParams p{};
+    p.text = f->feed.text.d_text.as<unsigned char>(); p.n = n; p.begin = begin;
+    p.pvalue_field = f->pvalue_field; p.n_fields = f->n_fields; p.thr_hi = f->thr_hi;
+    p.cols = f->d_cols.as<unsigned int>();
+    p.rows = f->d_misc.as<unsigned long long>(); p.flags = reinterpret_cast<unsigned int*>(f->d_misc.as<unsigned long long>() + 1);
+    p.thr = f->d_thr.as<uint2>(); p.tile = f->d_tile.as<unsigned long long>();
+    PFCHK(ts.timed([&]() -> int {
+        hipLaunchKernelGGL(af_plan_kernel, dim3(tiles), dim3(256), 0, ts.stream, p);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(kj_tiles_kernel, dim3(1), dim3(256), 0, ts.stream, p.tile, (uint64_t)tiles);
+        HIPCHK(hipGetLastError()); return PF_OK;
+    }));
+    uint64_t totals[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(totals, p.tile + 2 * (uint64_t)tiles, 16, hipMemcpyDeviceToHost, ts.stream));
+    HIPCHK(hipStreamSynchronize(ts.stream));
+    ts.add_elapsed(&f->device_ms);
+    f->bytes_scanned += n - begin;
+    const uint64_t n_rows = totals[0], n_bytes = totals[1];
+    if (!n_rows) return PF_OK;
+    PFCHK(f->d_rec.ensure((size_t)n_rows * sizeof(KjRec)));
+    PFCHK(f->out.d_out.ensure((size_t)n_bytes));
+    p.rec = f->d_rec.as<KjRec>();
+    KjParams w{};                                 // the writer's share: raw rows, text -> out by the records
+    w.text = p.text; w.rec = p.rec; w.out = f->out.d_out.as<unsigned char>();
+    PFCHK(ts.timed([&]() -> int {
+        hipLaunchKernelGGL(af_place_kernel, dim3(tiles), dim3(256), 0, ts.stream, p, n_rows, n_bytes);
+        HIPCHK(hipGetLastError());
+        const uint64_t groups = (n_rows + KJ_GROUP - 1) / KJ_GROUP;
+        hipLaunchKernelGGL(kj_write_kernel, dim3((uint32_t)std::min<uint64_t>((groups + 3) / 4, 256 * 32)), dim3(256), 0, ts.stream, w, n_rows);
+        HIPCHK(hipGetLastError()); return PF_OK;
+    }));
+    unsigned int err = 0;
+    HIPCHK(hipMemcpyAsync(&err, p.flags + 1, 4, hipMemcpyDeviceToHost, ts.stream));
+    HIPCHK(hipStreamSynchronize(ts.stream));
+    ts.add_elapsed(&f->device_ms);
+    if (err) return fail(PF_ERR_STATE, "pf_assocfilter_scan: the place pass found other rows than the plan pass");
+    f->out.bytes = n_bytes; f->kept += n_rows;
+    return PF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pf_assocfilter_destroy(pf_assocfilter* f) { if (f) { (void)hipSetDevice(f->feed.device); delete f; } }
+
+int pf_assocfilter_create(int device, uint32_t pvalue_field, uint32_t n_fields, double thr_hi, pf_assocfilter** out) {
+    if (!out) return fail(PF_ERR_ARG, "pf_assocfilter_create: null argument");
+    *out = nullptr;
+    if (!n_fields || pvalue_field >= n_fields) return fail(PF_ERR_ARG, "pf_assocfilter_create: the p-value field is not one of the header's");
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_assocfilter_create: no such device");
+    HIPCHK(hipSetDevice(device));
+    std::unique_ptr<pf_assocfilter, void (*)(pf_assocfilter*)> f(new pf_assocfilter(), pf_assocfilter_destroy);
+    f->feed.device = device;
+    f->pvalue_field = pvalue_field; f->n_fields = n_fields; f->thr_hi = thr_hi;
+    f->cols.assign(n_fields, 0);
+    PFCHK(f->feed.ts.create());
+    PFCHK(kj_upload(f->d_cols, f->cols));
+    PFCHK(kj_upload(f->d_misc, std::vector<uint64_t>(2, 0)));
+    *out = f.release();
+    return PF_OK;
+}
+
+int pf_assocfilter_scan(pf_assocfilter* f, const char* text, uint64_t nbytes, uint64_t* out_bytes, uint64_t* consumed) {
+    if (!f || !out_bytes || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_assocfilter_scan: null argument");
+    HIPCHK(hipSetDevice(f->feed.device));
+    *out_bytes = 0; f->out.reset();
+    PFCHK(f->feed.plain(text, nbytes, consumed));
+    PFCHK(af_scan_device(f, *consumed, 0));
+    *out_bytes = f->out.bytes;
+    return PF_OK;
+}
+
+int pf_assocfilter_members_begin(pf_assocfilter* f, int header) {
+    if (!f) return fail(PF_ERR_ARG, "pf_assocfilter_members_begin: null argument");
+    return f->feed.members_begin(header);
+}
+
+int pf_assocfilter_members_header(pf_assocfilter* f, const char** line, uint64_t* nbytes) {
+    if (!f) return fail(PF_ERR_ARG, "pf_assocfilter_members_header: null argument");
+    return f->feed.header_line(line, nbytes);
+}
+
+int pf_assocfilter_scan_members(pf_assocfilter* f, const char* members, uint64_t nbytes, int last, uint64_t* out_bytes,
+                                uint64_t* consumed, int* taken) {
+    if (!f || !out_bytes || !consumed || !taken || (nbytes && !members)) return fail(PF_ERR_ARG, "pf_assocfilter_scan_members: null argument");
+    HIPCHK(hipSetDevice(f->feed.device));
+    *out_bytes = 0; f->out.reset();
+    PFCHK(f->feed.members(members, nbytes, last, consumed, taken, [f](uint64_t n, uint64_t skip) { return af_scan_device(f, n, skip); }));
+    *out_bytes = f->out.bytes;
+    return PF_OK;
+}
+
+int pf_assocfilter_next_lines(pf_assocfilter* f, const char** piece, uint64_t* nbytes) {
+    if (!f || !piece || !nbytes) return fail(PF_ERR_ARG, "pf_assocfilter_next_lines: null argument");
+    HIPCHK(hipSetDevice(f->feed.device));
+    return f->out.next(f->feed.ts.stream, piece, nbytes);
+}
+
+int pf_assocfilter_columns(pf_assocfilter* f, const uint32_t** class_bits, uint32_t* n_fields, uint32_t* row_flags, uint64_t counters[2]) {
+    if (!f || !class_bits || !n_fields || !row_flags || !counters) return fail(PF_ERR_ARG, "pf_assocfilter_columns: null argument");
+    HIPCHK(hipSetDevice(f->feed.device));
+    uint64_t misc[2] = {0, 0};
+    HIPCHK(hipMemcpy(f->cols.data(), f->d_cols.p, f->cols.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(misc, f->d_misc.p, sizeof misc, hipMemcpyDeviceToHost));
+    *class_bits = f->cols.data(); *n_fields = f->n_fields; *row_flags = (uint32_t)(misc[1] & 0xFFFFFFFFu);
+    counters[0] = misc[0]; counters[1] = f->kept;
+    return PF_OK;
+}
+
+int pf_assocfilter_stats(pf_assocfilter* f, uint64_t stats[4], float ms[2]) {
+    if (!f) return fail(PF_ERR_ARG, "pf_assocfilter_stats: null argument");
+    if (stats) { stats[0] = f->bytes_scanned; stats[1] = f->feed.gz_members; stats[2] = f->feed.gz_text_bytes; stats[3] = f->feed.dec.device_bytes(); }
+    if (ms) { ms[0] = f->device_ms; ms[1] = f->feed.gz_ms; }
     return PF_OK;
 }
 

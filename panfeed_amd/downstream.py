@@ -17,7 +17,14 @@ pandas could print any of them other than as they stand, and one pass per bunch 
 A bunch the survey flags, and a run whose table the device cannot take, goes through the pandas statements of the
 reference (`--host-join` sends everything there).
 
-Both read a table the same two ways, written once here: a device-gzipped file goes up compressed and is inflated where
+Both tools begin by thresholding the associations table (`_associations`).  That too is one pass on the GPU
+(`AssocFilter` -> pf_assocfilter_*): it keeps the lines whose p-value may pass -- a superset, pandas makes the exact
+comparison on what is left -- and tells, per column, which classes of cells the WHOLE file holds, so that the few kept
+lines are parsed with the dtypes pandas would have inferred from all of them (`assoc_plan`).  A table the pass flags, or
+whose classes pandas would mix, goes through the reference's two statements whole (`--host-associations` sends every
+table there).
+
+All three read a table the same two ways, written once here: a device-gzipped file goes up compressed and is inflated where
 it lands (`pass_member_file` -> pf_*_members), any other is read block by block through the host (`scan_lines`);
 `route_file` chooses, and falls back to the second when the device decoder does not take a block.
 
@@ -321,6 +328,162 @@ class KmerJoin:
         self._pass_plain(path, block_bytes, call, write)
 
 
+AF_INT, AF_FLOAT, AF_NA, AF_ODD, AF_TEXT = 1, 2, 4, 8, 16
+AF_FLAG_NAMES = ((1, "a row with another number of fields than the header"), (2, "an empty line"),
+                 (4, "a control byte or a quote"), (8, "a row over 65 536 or a field of 4 096 bytes or more"))
+AF_MARGIN = 2.0 ** -30              # the device drops a row only above threshold + |threshold| * AF_MARGIN
+
+
+class AssocFilter:
+    """the data lines of an associations table whose cell in field `pvalue_field` may be <= threshold, kept on the device
+    as they stand, with the classes of all cells per column and the rows' flags"""
+
+    device_files = 0                # tables, over all filters, whose kept lines alone went to pandas
+    host_files = 0                  # tables that went through pandas whole
+    device_gunzip_files = 0         # passes over a file that went the device gunzip route to their end
+    fallback_files = 0              # and passes the automatic mode began there and read again through gzip
+    last_stats = None               # stats() of the last table that had a device pass
+
+    def __init__(self, pvalue_field, n_fields, threshold, device=0):
+        self.L = _lib.load()
+        self.h = C.c_void_p()
+        self.args = (int(device), int(pvalue_field), int(n_fields), float(threshold) + abs(float(threshold)) * AF_MARGIN)
+        self.header = None              # the header line the device gunzip route peeled off
+        self._create()
+
+    def _create(self):
+        self.close()
+        _lib.check(self.L.pf_assocfilter_create(*self.args, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.L.pf_assocfilter_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    def stats(self):
+        st, ms = (C.c_uint64 * 4)(), (C.c_float * 2)()
+        _lib.check(self.L.pf_assocfilter_stats(self.h, st, ms))
+        c = self.columns()
+        return {"bytes_scanned": int(st[0]), "rows": c["rows"], "kept": c["kept"], "members_inflated": int(st[1]),
+                "text_bytes_inflated": int(st[2]), "inflate_device_bytes": int(st[3]), "device_ms": float(ms[0]),
+                "inflate_ms": float(ms[1])}
+
+    def columns(self):
+        """over all lines scanned so far: the class bits of every column, the OR of the rows' flags, data and kept lines"""
+        bits, n, flags, cnt = C.POINTER(C.c_uint32)(), C.c_uint32(), C.c_uint32(), (C.c_uint64 * 2)()
+        _lib.check(self.L.pf_assocfilter_columns(self.h, C.byref(bits), C.byref(n), C.byref(flags), cnt))
+        return {"classes": [int(bits[i]) for i in range(n.value)], "flags": int(flags.value), "rows": int(cnt[0]), "kept": int(cnt[1])}
+
+    def _drain(self, out):
+        piece, n = C.c_void_p(), C.c_uint64()
+        while True:
+            _lib.check(self.L.pf_assocfilter_next_lines(self.h, C.byref(piece), C.byref(n)))
+            if not n.value:
+                return
+            out.append(C.string_at(piece, n.value))
+
+    def scan_block(self, data, n=None):
+        """(kept lines of the complete lines of `data` (bytes, or the first n bytes of a bytearray), joined; bytes consumed)"""
+        kept, used, out = C.c_uint64(), C.c_uint64(), []
+        if isinstance(data, bytearray):
+            n = len(data) if n is None else n
+            ptr = (C.c_char * len(data)).from_buffer(data)          # no copy
+        else:
+            n, ptr = len(data), data
+        _lib.check(self.L.pf_assocfilter_scan(self.h, ptr, n, C.byref(kept), C.byref(used)))
+        del ptr
+        self._drain(out)
+        return b"".join(out), int(used.value)
+
+    def scan_members(self, data, last):
+        """(kept lines of the text of the whole gzip members in `data`, joined; compressed bytes consumed; whether the
+        device decoder took them)"""
+        kept, used, taken, out = C.c_uint64(), C.c_uint64(), C.c_int(), []
+        _lib.check(self.L.pf_assocfilter_scan_members(self.h, data, len(data), 1 if last else 0, C.byref(kept), C.byref(used),
+                                                      C.byref(taken)))
+        if taken.value:
+            self._drain(out)
+        return b"".join(out), int(used.value), bool(taken.value)
+
+    def _filter_members(self, path, block_bytes):
+        out = []
+
+        def call(data, last):
+            got, used, taken = self.scan_members(data, last)
+            out.append(got)
+            return used, taken
+
+        if not pass_member_file(path, block_bytes, lambda: _lib.check(self.L.pf_assocfilter_members_begin(self.h, 1)), call):
+            return None
+        line, n = C.c_void_p(), C.c_uint64()
+        _lib.check(self.L.pf_assocfilter_members_header(self.h, C.byref(line), C.byref(n)))
+        self.header = C.string_at(line, n.value) if n.value else b""
+        return b"".join(out)
+
+    def _filter_host(self, path, block_bytes):
+        out = []
+
+        def scan(buf, n):
+            got, used = self.scan_block(buf, n)
+            out.append(got)
+            return used
+
+        with open_table(path) as fh:
+            fh.readline()                            # the header line
+            scan_lines(fh, scan, block_bytes)
+        return b"".join(out)
+
+    def filter_file(self, path, block_bytes=None, device_gunzip=None):
+        """the kept data lines of a table file, joined; columns() then speaks of the whole file.  device_gunzip as
+        RowFilter.filter_file's (a pass that stopped half way has ORed classes in: the filter is made anew before the file
+        is read again)"""
+        return route_file(path, device_gunzip, lambda: self._filter_members(path, block_bytes),
+                          lambda: self._filter_host(path, block_bytes), AssocFilter, self._create)
+
+
+def assoc_header(line):
+    """the column names of an associations table's header line (bytes), the index column's first; None for a header the
+    device route leaves to pandas: no line, a name twice, an empty name, a quote or control byte, a byte-order mark, text
+    that is not UTF-8"""
+    if not line.endswith(b"\n"):
+        return None
+    try:
+        text = line[:-1].decode()
+    except UnicodeDecodeError:
+        return None
+    names = text.split("\t")
+    if len(set(names)) != len(names) or "" in names or any(ord(ch) < 0x20 and ch != "\t" or ch == '"' for ch in text):
+        return None
+    if text.startswith("\ufeff"):
+        return None
+    return names
+
+
+def assoc_plan(names, pvalue_field, classes, flags, rows):
+    """What the classes of a whole table's cells and its rows' flags say: (dtype per column name, None) -- the dtypes
+    pandas infers from the whole file, to be forced on the kept lines --, or (None, why the table goes through pandas
+    whole)."""
+    if flags:
+        return None, ", ".join(t for f, t in AF_FLAG_NAMES if flags & f)
+    dtypes = {}
+    for i, (name, c) in enumerate(zip(names, classes)):
+        if c & AF_ODD:
+            return None, f"column {name!r} holds a cell pandas may read otherwise in a part of the file"
+        if c & AF_TEXT and c & (AF_INT | AF_FLOAT):
+            return None, f"column {name!r} mixes text and numbers"
+        if c & AF_TEXT and i == pvalue_field:
+            return None, f"column {name!r} holds text"
+        dtypes[name] = object if c & AF_TEXT else "int64" if c == AF_INT and rows else "float64"
+    return dtypes, None
+
+
+def assoc_table(header, kept, dtypes):
+    """the kept lines as pandas reads them under the whole file's dtypes"""
+    return pd.read_csv(io.BytesIO(header + kept), sep="\t", index_col=0, dtype=dtypes)
+
+
 def _isnan(v):
     return isinstance(v, float) and v != v
 
@@ -420,6 +583,9 @@ def _options(description, kmers):
                             "number of clusters makes the whole run two passes over the file, one survey and one join)")
         p.add_argument("--host-join", action="store_true", default=False,
                        help="join kmers.tsv to the associations in pandas, bunch by bunch (by default the GPU looks the rows up and writes them)")
+    p.add_argument("--host-associations", action="store_true", default=False,
+                   help="read the whole associations table with pandas (by default the GPU keeps the lines that may pass the "
+                        "threshold and pandas reads those)")
     p.add_argument("-v", action="count", default=0)
     p.add_argument("--device", type=int, default=0, help="GPU the row filter runs on")
     p.add_argument("--host-gunzip", action="store_true", default=False,
@@ -427,18 +593,64 @@ def _options(description, kmers):
     return p
 
 
-def _associations(args, index_name=None):
-    """the filtered associations table and the passing hashes (get_clusters.py:76-88, get_kmers.py:93-106)"""
-    a = pd.read_csv(args.associations, sep="\t", index_col=0)
+def _missing_column(args):
+    logger.warning(f"Associations file does not have the {args.column} column")
+    sys.exit(1)
+
+
+def _passing(a, args, index_name):
+    """the reference's statements on a table as read_csv made it: (the filtered table, the passing hashes)"""
     if index_name:
         a.index.name = index_name
     if args.column not in a.columns:
-        logger.warning(f"Associations file does not have the {args.column} column")
-        sys.exit(1)
+        _missing_column(args)
     a = a[a[args.column] <= args.threshold]
     if args.output is not None:
         a.to_csv(args.output, sep="\t")
     return a, [str(x) for x in a.index.unique()]
+
+
+def _device_scan(args, field, names):
+    """one device pass over the associations file: (kept lines, AssocFilter.columns(), the header line if the device
+    peeled it off)"""
+    f = AssocFilter(field, len(names), args.threshold, device=args.device)
+    try:
+        kept = f.filter_file(args.associations, device_gunzip=False if args.host_gunzip else None)
+        cols = f.columns()
+        AssocFilter.last_stats = f.stats()
+        return kept, cols, f.header
+    finally:
+        f.close()
+
+
+def _associations(args, index_name=None, scan=_device_scan):
+    """the filtered associations table and the passing hashes (get_clusters.py:76-88, get_kmers.py:93-106).  The file goes
+    through the device filter (`scan`) and pandas reads the kept lines under the dtypes of the whole file; it reads the
+    whole file, as the reference does, when the pass says the two could differ or --host-associations asks for it"""
+    a, why = None, "--host-associations"
+    if not getattr(args, "host_associations", False):
+        with open_table(args.associations) as fh:
+            header = fh.readline()
+        names = assoc_header(header)
+        if names is None:
+            why = "the header line is not plain"
+        elif args.column not in names[1:]:
+            _missing_column(args)
+        else:
+            field = names.index(args.column)
+            kept, cols, peeled = scan(args, field, names)
+            dtypes, why = assoc_plan(names, field, cols["classes"], cols["flags"], cols["rows"])
+            if peeled is not None and peeled != header:
+                dtypes, why = None, "the header line the device peeled off is not the file's first line"
+            if dtypes is not None:
+                a = assoc_table(header, kept, dtypes)
+    if a is None:
+        logger.debug("the associations go through pandas whole: %s", why)
+        AssocFilter.host_files += 1
+        a = pd.read_csv(args.associations, sep="\t", index_col=0)
+    else:
+        AssocFilter.device_files += 1
+    return _passing(a, args, index_name)
 
 
 _NAN_KEY = float("nan")      # ONE object for every NaN a column holds (tolist() makes a new one per cell, and nan != nan)
