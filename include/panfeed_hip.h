@@ -631,6 +631,15 @@ void pf_rowfilter_destroy(pf_rowfilter* f);
  * stats (either may be NULL): stats[0] bytes scanned, [1] rows written, [2] raw rows kept (mode 2), [3] members and
  * [4] text bytes inflated, [5] the decoder's device bytes, [6] look-ups whose hash was equal and whose bytes were not
  * (above zero only under a weakened hash, in practice), [7] rows written with the empty text; ms[0] survey kernels, [1] join kernels, [2] inflate.
+ * set_gzip (off by default): while on, the text of a join call in mode 0 or 1 leaves as gzip members, as pf_gzip_device
+ * makes them, and pf_kmerjoin_next_text hands out the members' bytes in place of the text.  The call's text is encoded on
+ * the join's stream in slices of at most 64 MiB, a slice when the one before is handed out: the encoder (made on first use)
+ * and the slice's members take device memory for 64 MiB of text at most, whatever the call wrote, and only members go to the
+ * host.  A member never spans two join calls (a call's last member may be short); a call that wrote no row hands out none;
+ * mode 2 stays text.  *out_bytes stays the bytes of TEXT made.  flags: pf_gzip_device's test hooks.  Switching drops what
+ * is left of the last call's text.
+ * gzip_stats (any may be NULL): text bytes encoded, member bytes made, the encoder's kernels' ms, the device bytes of the
+ * encoder and the members' buffer.
  */
 #define PF_KJ_TABS 1u      /* not exactly 10 tabs */
 #define PF_KJ_BYTES 2u     /* a byte below 0x20 other than tab, of 0x80 or above, or a double quote */
@@ -658,6 +667,8 @@ int pf_kmerjoin_join_members(pf_kmerjoin* j, const char* members, uint64_t nbyte
                              uint64_t* out_bytes, uint64_t* consumed, int* taken);
 int pf_kmerjoin_next_text(pf_kmerjoin* j, const char** piece, uint64_t* nbytes);
 int pf_kmerjoin_stats(pf_kmerjoin* j, uint64_t stats[8], float ms[3]);
+int pf_kmerjoin_set_gzip(pf_kmerjoin* j, int on, uint32_t flags);
+int pf_kmerjoin_gzip_stats(pf_kmerjoin* j, uint64_t* text_bytes, uint64_t* member_bytes, float* encode_ms, uint64_t* device_bytes);
 void pf_kmerjoin_destroy(pf_kmerjoin* j);
 
 /*
@@ -724,11 +735,21 @@ void pf_assocfilter_destroy(pf_assocfilter* f);
  * pf_plotgrid_grids: the grids of n clusters (ids), one after the other, n_strains x (max - min + 1) cells each,
  * strain-major: key_out = the largest key of the cell's rows (0: none but NaN), cnt_out = rows << 32 | sum of the
  * rows' base letters (with one row: its letter; 0 for an empty k-mer).  Integer atomics only: the same bits every run.
+ * members_begin / members_header / scan_members / gunzip_stats: the same scan over a .gz of small gzip members -- what
+ * panfeed-get-kmers --gz-output writes -- as the row filter's four calls: blocks of the COMPRESSED file from a member start
+ * on, inflated on the device behind the line the call before left unfinished and scanned where they land; the header line
+ * (members_begin's header = 1) is peeled off by the feed and is no row.  Room for records and names is made from the
+ * INFLATED bytes, and those stay under 4 GiB a call (a call inflates 256 MiB of text at most).  *taken = 0 with PF_OK: as
+ * pf_gunzip_device; the grid's records and tables are then as they were before the call.
  */
 typedef struct pf_plotgrid pf_plotgrid;
 int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* strain_len, uint32_t n_strains,
                        const int32_t* columns, int zoom, int64_t start, int64_t stop, pf_plotgrid** out);
 int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t* consumed);
+int pf_plotgrid_members_begin(pf_plotgrid* g, int header);
+int pf_plotgrid_members_header(pf_plotgrid* g, const char** line, uint64_t* nbytes);
+int pf_plotgrid_scan_members(pf_plotgrid* g, const char* members, uint64_t nbytes, int last, uint64_t* consumed, int* taken);
+int pf_plotgrid_gunzip_stats(pf_plotgrid* g, uint64_t* members, uint64_t* text_bytes, float* inflate_ms, uint64_t* device_bytes);
 int pf_plotgrid_finish(pf_plotgrid* g, uint32_t* n_clusters, uint64_t* n_pvalues, uint64_t* n_records);
 int pf_plotgrid_clusters(pf_plotgrid* g, const char** names, const uint64_t** name_off, const int32_t** min_pos,
                          const int32_t** max_pos, const uint64_t** rows);

@@ -158,7 +158,9 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_kmerjoin_join_members", "pf_kmerjoin_next_text", "pf_kmerjoin_stats", "pf_kmerjoin_destroy",
            "pf_assocfilter_create", "pf_assocfilter_scan", "pf_assocfilter_members_begin", "pf_assocfilter_members_header",
            "pf_assocfilter_scan_members", "pf_assocfilter_next_lines", "pf_assocfilter_columns", "pf_assocfilter_stats",
-           "pf_assocfilter_destroy"]
+           "pf_assocfilter_destroy",
+           "pf_kmerjoin_set_gzip", "pf_kmerjoin_gzip_stats",
+           "pf_plotgrid_members_begin", "pf_plotgrid_members_header", "pf_plotgrid_scan_members", "pf_plotgrid_gunzip_stats"]
 
 RENDER_NO_PATTERN_ROWS = 1
 GZ_FIXED_ONLY, GZ_DYNAMIC_ONLY, GZ_LITERALS_ONLY = 1, 2, 4     # pf_gzip_device / pf_set_device_gzip test hooks; 0: the product
@@ -287,6 +289,11 @@ def _load_locked():
     L.pf_plotgrid_grids.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.pf_plotgrid_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_float)]
+    L.pf_plotgrid_members_begin.argtypes = [C.c_void_p, C.c_int]
+    L.pf_plotgrid_members_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pf_plotgrid_scan_members.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.pf_plotgrid_gunzip_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_uint64)]
     L.pf_plotgrid_destroy.argtypes = [C.c_void_p]
     L.pf_plotgrid_destroy.restype = None
     L.pf_gzip_members.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -320,6 +327,8 @@ def _load_locked():
                                            C.POINTER(C.c_int)]
     L.pf_kmerjoin_next_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), u64p]
     L.pf_kmerjoin_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pf_kmerjoin_set_gzip.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+    L.pf_kmerjoin_gzip_stats.argtypes = [C.c_void_p, u64p, u64p, C.POINTER(C.c_float), u64p]
     L.pf_kmerjoin_destroy.argtypes = [C.c_void_p]
     L.pf_kmerjoin_destroy.restype = None
     L.pf_assocfilter_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_void_p)]

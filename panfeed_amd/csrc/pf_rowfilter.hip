@@ -648,7 +648,7 @@ struct PgCheck {              // one row that passed the strain filter: its fiel
 
 struct PgScanParams {
     const unsigned char* text;
-    uint64_t n;
+    uint64_t n, begin;        // lines that start in [begin, n)
     int32_t col[6];           // cluster, strain, gene_start, k-mer, strand, p-value
     int32_t max_col;
     const unsigned long long* strain_hash;   // static set: hash, strain id
@@ -790,8 +790,8 @@ __device__ void pg_line(const PgScanParams& p, uint64_t s) {
 __global__ __launch_bounds__(256) void pg_scan_kernel(PgScanParams p) {
     const uint64_t nvec = (p.n + 15) / 16;
     for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < nvec; v += (uint64_t)gridDim.x * blockDim.x) {
-        if (v == 0) pg_line(p, 0);
-        rf_each_newline(p.text, v, [&](uint64_t at) { if (at + 1 < p.n) pg_line(p, at + 1); });
+        if (v == 0 && p.begin == 0) pg_line(p, 0);
+        rf_each_newline(p.text, v, [&](uint64_t at) { if (at + 1 < p.n && at + 1 >= p.begin) pg_line(p, at + 1); });
     }
 }
 
@@ -914,7 +914,7 @@ struct pf_plotgrid {
     DevBuf d_key, d_cnt;                       // the grids' cells
     DevBuf d_slot_item;
     DevBuf d_item;                             // off[n] | min[n] | width[n], packed in one buffer
-    TextFeed feed;                             // the block (host text only: pf_plotgrid_scan)
+    TextFeed feed;                             // the block: host text (pf_plotgrid_scan) or gzip members (pf_plotgrid_scan_members)
 };
 
 namespace {
@@ -979,6 +979,76 @@ int pg_tab_list(pf_plotgrid* g, pf_plotgrid::Tab& t, std::vector<uint32_t>& slot
         bytes.append(arena, (size_t)(st[i] >> 16), (size_t)(st[i] & 0xFFFF));
         off.push_back(bytes.size());
     }
+    return PF_OK;
+}
+
+// a block's text is addressed in 32 bits (PgCheck) -- the inflated text, for a block of members
+int pg_block_fits(uint64_t n) {
+    return n >= ((uint64_t)1 << 32) ? fail(PF_ERR_ARG, "pf_plotgrid_scan: a block of 4 GiB or more") : PF_OK;
+}
+
+// The scan of the feed's d_text[skip .. n), complete lines, for the plain route and the member route alike: room for what
+// a block of that many bytes may add, pg_scan_kernel, pg_check_kernel, the counters read back.  On the feed's stream, behind
+// whatever put the text there.
+int pg_scan_device(pf_plotgrid* g, uint64_t n, uint64_t skip) {
+    if (n <= skip) return PF_OK;
+    PFCHK(pg_block_fits(n));
+    const uint64_t bytes = n - skip;
+    // every row needs max_col tabs and a newline: at most this many rows pass
+    const uint64_t rows = bytes / ((uint64_t)g->max_col + 1) + 1;
+    PFCHK(g->d_chk.ensure(rows * sizeof(PgCheck), true));
+    if (g->n_rec + rows > g->d_rec.cap / sizeof(PgRecord)) {
+        const uint64_t want = std::max<uint64_t>((g->n_rec + rows) * 3 / 2, 1 << 16);
+        DevBuf r;
+        PFCHK(r.ensure(want * sizeof(PgRecord), true));
+        if (g->n_rec) HIPCHK(hipMemcpyAsync(r.p, g->d_rec.p, g->n_rec * sizeof(PgRecord), hipMemcpyDeviceToDevice, g->feed.ts.stream));
+        HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
+        std::swap(g->d_rec, r);                 // (the old records go at the end of this block)
+    }
+    PFCHK(pg_tab_reserve(g, g->cl, rows, bytes, 0));
+    PFCHK(pg_tab_reserve(g, g->pv, rows, bytes, 1));
+    unsigned long long* const d_ctr = g->d_ctr.as<ull>();
+    unsigned long long ctr[4] = {g->n_rec, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(d_ctr, ctr, 3 * 8, hipMemcpyHostToDevice, g->feed.ts.stream));   // records continue; checks, lines restart
+    PgScanParams p{};
+    p.text = g->feed.text.d_text.as<unsigned char>(); p.n = n; p.begin = skip;
+    for (int q = 0; q < 6; q++) p.col[q] = g->col[q];
+    p.max_col = g->max_col;
+    p.strain_hash = g->d_strain_hash.as<ull>(); p.strain_id = g->d_strain_id.as<uint32_t>(); p.strain_cap = g->strain_cap;
+    p.strain_bytes = g->d_strain_bytes.as<unsigned char>(); p.strain_str = g->d_strain_str.as<uint64_t>();
+    p.clusters = pg_view(g->cl); p.pvalues = pg_view(g->pv);
+    p.zoom = g->zoom; p.start = g->start; p.stop = g->stop;
+    p.rec = g->d_rec.as<PgRecord>(); p.n_rec = d_ctr; p.chk = g->d_chk.as<PgCheck>(); p.n_chk = d_ctr + 1; p.n_lines = d_ctr + 2;
+    p.err = (unsigned int*)(d_ctr + 3);
+    PFCHK(g->feed.ts.timed([&]() -> int {
+        hipLaunchKernelGGL(pg_scan_kernel, dim3(pg_blocks((n + 15) / 16)), dim3(256), 0, g->feed.ts.stream, p);
+        HIPCHK(hipGetLastError());
+        unsigned long long n_chk = 0;
+        HIPCHK(hipMemcpyAsync(&n_chk, d_ctr + 1, 8, hipMemcpyDeviceToHost, g->feed.ts.stream));
+        HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
+        if (n_chk) {
+            hipLaunchKernelGGL(pg_check_kernel, dim3(pg_blocks(n_chk)), dim3(256), 0, g->feed.ts.stream, p.text, g->d_chk.as<const PgCheck>(),
+                               (uint64_t)n_chk, pg_view(g->cl), pg_view(g->pv), (unsigned int*)(d_ctr + 3));
+            HIPCHK(hipGetLastError());
+        }
+        return PF_OK;
+    }));
+    HIPCHK(hipMemcpyAsync(ctr, d_ctr, 4 * 8, hipMemcpyDeviceToHost, g->feed.ts.stream));
+    unsigned long long tc[2][2];
+    HIPCHK(hipMemcpyAsync(tc[0], g->cl.ctr.p, 16, hipMemcpyDeviceToHost, g->feed.ts.stream));
+    HIPCHK(hipMemcpyAsync(tc[1], g->pv.ctr.p, 16, hipMemcpyDeviceToHost, g->feed.ts.stream));
+    HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
+    g->feed.ts.add_elapsed(&g->device_ms);
+    g->cl.used = tc[0][0]; g->cl.count = tc[0][1];
+    g->pv.used = tc[1][0]; g->pv.count = tc[1][1];
+    g->n_rec = ctr[0];
+    g->lines += ctr[2];
+    g->bytes_scanned += bytes;
+    const unsigned err = (unsigned)(ctr[3] & 0xFFFFFFFFu);
+    if (err & (PG_ERR_CLUSTER | PG_ERR_PVALUE))
+        return fail(PF_ERR_CAPACITY, "pf_plotgrid_scan: two different cluster names or p-value texts share a 64-bit hash");
+    if (err & PG_ERR_LONG) return fail(PF_ERR_ARG, "pf_plotgrid_scan: a cluster name or p-value field over 4095 bytes");
+    if (err & PG_ERR_RANGE) return fail(PF_ERR_ARG, "pf_plotgrid_scan: a gene_start outside the 32-bit range");
     return PF_OK;
 }
 
@@ -1047,67 +1117,35 @@ int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t
     if (!g || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_plotgrid_scan: null argument");
     if (g->finished) return fail(PF_ERR_STATE, "pf_plotgrid_scan: after pf_plotgrid_finish");
     HIPCHK(hipSetDevice(g->feed.device));
-    // room for what a block of n bytes may add, made in front of its upload
-    PFCHK(g->feed.plain(text, nbytes, consumed, [g](uint64_t n) -> int {
-        if (n >= ((uint64_t)1 << 32)) return fail(PF_ERR_ARG, "pf_plotgrid_scan: a block of 4 GiB or more");
-        // every row needs max_col tabs and a newline: at most this many rows pass
-        const uint64_t rows = n / ((uint64_t)g->max_col + 1) + 1;
-        PFCHK(g->d_chk.ensure(rows * sizeof(PgCheck), true));
-        if (g->n_rec + rows > g->d_rec.cap / sizeof(PgRecord)) {
-            const uint64_t want = std::max<uint64_t>((g->n_rec + rows) * 3 / 2, 1 << 16);
-            DevBuf r;
-            PFCHK(r.ensure(want * sizeof(PgRecord), true));
-            if (g->n_rec) HIPCHK(hipMemcpyAsync(r.p, g->d_rec.p, g->n_rec * sizeof(PgRecord), hipMemcpyDeviceToDevice, g->feed.ts.stream));
-            HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
-            std::swap(g->d_rec, r);                 // (the old records go at the end of this block)
-        }
-        PFCHK(pg_tab_reserve(g, g->cl, rows, n, 0));
-        return pg_tab_reserve(g, g->pv, rows, n, 1);
-    }));
-    const uint64_t n = *consumed;
-    if (!n) return PF_OK;
-    unsigned long long* const d_ctr = g->d_ctr.as<ull>();
-    unsigned long long ctr[4] = {g->n_rec, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(d_ctr, ctr, 3 * 8, hipMemcpyHostToDevice, g->feed.ts.stream));   // records continue; checks, lines restart
-    PgScanParams p{};
-    p.text = g->feed.text.d_text.as<unsigned char>(); p.n = n;
-    for (int q = 0; q < 6; q++) p.col[q] = g->col[q];
-    p.max_col = g->max_col;
-    p.strain_hash = g->d_strain_hash.as<ull>(); p.strain_id = g->d_strain_id.as<uint32_t>(); p.strain_cap = g->strain_cap;
-    p.strain_bytes = g->d_strain_bytes.as<unsigned char>(); p.strain_str = g->d_strain_str.as<uint64_t>();
-    p.clusters = pg_view(g->cl); p.pvalues = pg_view(g->pv);
-    p.zoom = g->zoom; p.start = g->start; p.stop = g->stop;
-    p.rec = g->d_rec.as<PgRecord>(); p.n_rec = d_ctr; p.chk = g->d_chk.as<PgCheck>(); p.n_chk = d_ctr + 1; p.n_lines = d_ctr + 2;
-    p.err = (unsigned int*)(d_ctr + 3);
-    PFCHK(g->feed.ts.timed([&]() -> int {
-        hipLaunchKernelGGL(pg_scan_kernel, dim3(pg_blocks((n + 15) / 16)), dim3(256), 0, g->feed.ts.stream, p);
-        HIPCHK(hipGetLastError());
-        unsigned long long n_chk = 0;
-        HIPCHK(hipMemcpyAsync(&n_chk, d_ctr + 1, 8, hipMemcpyDeviceToHost, g->feed.ts.stream));
-        HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
-        if (n_chk) {
-            hipLaunchKernelGGL(pg_check_kernel, dim3(pg_blocks(n_chk)), dim3(256), 0, g->feed.ts.stream, p.text, g->d_chk.as<const PgCheck>(),
-                               (uint64_t)n_chk, pg_view(g->cl), pg_view(g->pv), (unsigned int*)(d_ctr + 3));
-            HIPCHK(hipGetLastError());
-        }
-        return PF_OK;
-    }));
-    HIPCHK(hipMemcpyAsync(ctr, d_ctr, 4 * 8, hipMemcpyDeviceToHost, g->feed.ts.stream));
-    unsigned long long tc[2][2];
-    HIPCHK(hipMemcpyAsync(tc[0], g->cl.ctr.p, 16, hipMemcpyDeviceToHost, g->feed.ts.stream));
-    HIPCHK(hipMemcpyAsync(tc[1], g->pv.ctr.p, 16, hipMemcpyDeviceToHost, g->feed.ts.stream));
-    HIPCHK(hipStreamSynchronize(g->feed.ts.stream));
-    g->feed.ts.add_elapsed(&g->device_ms);
-    g->cl.used = tc[0][0]; g->cl.count = tc[0][1];
-    g->pv.used = tc[1][0]; g->pv.count = tc[1][1];
-    g->n_rec = ctr[0];
-    g->lines += ctr[2];
-    g->bytes_scanned += n;
-    const unsigned err = (unsigned)(ctr[3] & 0xFFFFFFFFu);
-    if (err & (PG_ERR_CLUSTER | PG_ERR_PVALUE))
-        return fail(PF_ERR_CAPACITY, "pf_plotgrid_scan: two different cluster names or p-value texts share a 64-bit hash");
-    if (err & PG_ERR_LONG) return fail(PF_ERR_ARG, "pf_plotgrid_scan: a cluster name or p-value field over 4095 bytes");
-    if (err & PG_ERR_RANGE) return fail(PF_ERR_ARG, "pf_plotgrid_scan: a gene_start outside the 32-bit range");
+    // (a block this scan cannot take is turned away in front of its upload)
+    PFCHK(g->feed.plain(text, nbytes, consumed, [](uint64_t n) { return pg_block_fits(n); }));
+    return pg_scan_device(g, *consumed, 0);
+}
+
+int pf_plotgrid_members_begin(pf_plotgrid* g, int header) {
+    if (!g) return fail(PF_ERR_ARG, "pf_plotgrid_members_begin: null argument");
+    return g->feed.members_begin(header);
+}
+
+int pf_plotgrid_members_header(pf_plotgrid* g, const char** line, uint64_t* nbytes) {
+    if (!g) return fail(PF_ERR_ARG, "pf_plotgrid_members_header: null argument");
+    return g->feed.header_line(line, nbytes);
+}
+
+int pf_plotgrid_scan_members(pf_plotgrid* g, const char* members, uint64_t nbytes, int last, uint64_t* consumed, int* taken) {
+    if (!g || !consumed || !taken || (nbytes && !members)) return fail(PF_ERR_ARG, "pf_plotgrid_scan_members: null argument");
+    if (g->finished) return fail(PF_ERR_STATE, "pf_plotgrid_scan_members: after pf_plotgrid_finish");
+    HIPCHK(hipSetDevice(g->feed.device));
+    // (the feed calls the scan only once the block is taken: a block that is not leaves records and tables as they were)
+    return g->feed.members(members, nbytes, last, consumed, taken, [g](uint64_t n, uint64_t skip) { return pg_scan_device(g, n, skip); });
+}
+
+int pf_plotgrid_gunzip_stats(pf_plotgrid* g, uint64_t* members, uint64_t* text_bytes, float* inflate_ms, uint64_t* device_bytes) {
+    if (!g) return fail(PF_ERR_ARG, "pf_plotgrid_gunzip_stats: null argument");
+    if (members) *members = g->feed.gz_members;
+    if (text_bytes) *text_bytes = g->feed.gz_text_bytes;
+    if (inflate_ms) *inflate_ms = g->feed.gz_ms;
+    if (device_bytes) *device_bytes = g->feed.dec.device_bytes();
     return PF_OK;
 }
 
@@ -1612,10 +1650,23 @@ struct pf_kmerjoin {
     KjHandout out;                               // the join's text
     uint64_t bytes_scanned = 0, rows_written = 0, raw_rows = 0;
     float survey_ms = 0, write_ms = 0;
+    // pf_kmerjoin_set_gzip: the text of a mode 0 / 1 call leaves as gzip members.  The encoder is made on first use; a call's
+    // text is encoded a slice of at most PfGzEncoder::BLOCK bytes at a time, slice by slice as its members are handed out,
+    // so the encoder's buffers and gz.d_out, the slice's members, take PfGzEncoder::bound(BLOCK) bytes each at most
+    bool gz_on = false, gz_now = false;          // the switch; whether the last join call's text is one to encode
+    uint32_t gz_flags = 0;
+    PfGzEncoder enc;
+    KjHandout gz;                                // the members of the slice out.d_out[gz_at - its bytes .. gz_at)
+    uint64_t gz_at = 0;                          // text bytes of the call encoded so far
+    uint64_t gz_text_bytes = 0, gz_member_bytes = 0;
+    float gz_ms = 0;
     TextFeed feed;                               // (its stream goes first: a piece of text may be on its way down into pin)
 };
 
 namespace {
+
+// nothing of an earlier join call is left to hand out
+void kj_reset_out(pf_kmerjoin* j) { j->out.reset(); j->gz.reset(); j->gz_at = 0; j->gz_now = false; }
 
 KjParams kj_params(pf_kmerjoin* j, uint64_t n, uint64_t begin) {
     KjParams p{};
@@ -1648,7 +1699,7 @@ int kj_survey_device(pf_kmerjoin* j, uint64_t n, uint64_t begin) {
 
 // the join of d_text[begin .. n) for one bunch: the text in out.d_out[0 .. out.bytes), ready to be handed out
 int kj_join_device(pf_kmerjoin* j, uint64_t n, uint64_t begin, uint32_t bunch, int mode) {
-    j->out.reset();
+    kj_reset_out(j);
     if (n <= begin) return PF_OK;
     if (bunch >= j->n_bunches || mode < 0 || mode > 2) return fail(PF_ERR_ARG, "pf_kmerjoin_join: no such bunch or mode");
     TimedStream& ts = j->feed.ts;
@@ -1691,8 +1742,34 @@ int kj_join_device(pf_kmerjoin* j, uint64_t n, uint64_t begin, uint32_t bunch, i
     j->write_ms += ms;
     if (err) return fail(PF_ERR_STATE, "pf_kmerjoin_join: a row of the bunch is not one the survey passed (flags 0x%x): the file has changed", err);
     j->out.bytes = n_bytes;
+    j->gz_now = j->gz_on && mode != 2;            // (the raw rows go to pandas: they stay text)
     if (mode == 2) j->raw_rows += n_rows; else j->rows_written += n_rows;
     return PF_OK;
+}
+
+// With the switch on: the next piece of the members of the last join call's text.  A slice's members are handed out to
+// their end, then the next slice is encoded in their place (the pieces handed out are in pinned memory by then)
+int kj_next_members(pf_kmerjoin* j, const char** piece, uint64_t* nbytes) {
+    TimedStream& ts = j->feed.ts;
+    constexpr PfGzEncoder::Cursor W = PfGzEncoder::STREAM_BLOCK0;
+    for (;;) {
+        PFCHK(j->gz.next(ts.stream, piece, nbytes));
+        if (*nbytes || j->gz_at >= j->out.bytes) return PF_OK;
+        const uint64_t m = std::min<uint64_t>(PfGzEncoder::BLOCK, j->out.bytes - j->gz_at), cap = PfGzEncoder::bound(m);
+        if (!j->enc.grid_cap) {
+            int n_cu = 0;
+            HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, j->feed.device));
+            PFCHK(j->enc.ensure(n_cu > 0 ? n_cu : 256));
+        }
+        // (a buffer that is re-made gets a quarter more, up to what a whole slice may take)
+        if (cap > j->gz.d_out.cap) PFCHK(j->gz.d_out.ensure((size_t)std::min<uint64_t>(PfGzEncoder::bound(PfGzEncoder::BLOCK), cap + cap / 4), true));
+        j->gz.reset();
+        PFCHK(j->enc.encode(ts.stream, W, j->out.d_out.as<char>() + j->gz_at, m, j->gz_flags, j->gz.d_out.as<char>(), cap, ts.e0, ts.e1));
+        HIPCHK(hipStreamSynchronize(ts.stream));
+        ts.add_elapsed(&j->gz_ms);
+        PFCHK(j->enc.member_bytes(W, &j->gz.bytes));
+        j->gz_at += m; j->gz_text_bytes += m; j->gz_member_bytes += j->gz.bytes;
+    }
 }
 
 template <class T> int kj_upload(DevBuf& d, const std::vector<T>& v) {
@@ -1813,7 +1890,7 @@ int pf_kmerjoin_counters(pf_kmerjoin* j, const uint64_t** counters, uint32_t* n_
 int pf_kmerjoin_join(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint32_t bunch, int mode, uint64_t* out_bytes, uint64_t* consumed) {
     if (!j || !out_bytes || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_kmerjoin_join: null argument");
     HIPCHK(hipSetDevice(j->feed.device));
-    *out_bytes = 0; j->out.reset();
+    *out_bytes = 0; kj_reset_out(j);
     PFCHK(j->feed.plain(text, nbytes, consumed));
     PFCHK(kj_join_device(j, *consumed, 0, bunch, mode));
     *out_bytes = j->out.bytes;
@@ -1824,7 +1901,7 @@ int pf_kmerjoin_join_members(pf_kmerjoin* j, const char* members, uint64_t nbyte
                              uint64_t* out_bytes, uint64_t* consumed, int* taken) {
     if (!j || !out_bytes || !consumed || !taken || (nbytes && !members)) return fail(PF_ERR_ARG, "pf_kmerjoin_join_members: null argument");
     HIPCHK(hipSetDevice(j->feed.device));
-    *out_bytes = 0; j->out.reset();
+    *out_bytes = 0; kj_reset_out(j);
     PFCHK(j->feed.members(members, nbytes, last, consumed, taken,
                            [j, bunch, mode](uint64_t n, uint64_t skip) { return kj_join_device(j, n, skip, bunch, mode); }));
     *out_bytes = j->out.bytes;
@@ -1834,7 +1911,24 @@ int pf_kmerjoin_join_members(pf_kmerjoin* j, const char* members, uint64_t nbyte
 int pf_kmerjoin_next_text(pf_kmerjoin* j, const char** piece, uint64_t* nbytes) {
     if (!j || !piece || !nbytes) return fail(PF_ERR_ARG, "pf_kmerjoin_next_text: null argument");
     HIPCHK(hipSetDevice(j->feed.device));
-    return j->out.next(j->feed.ts.stream, piece, nbytes);
+    return j->gz_now ? kj_next_members(j, piece, nbytes) : j->out.next(j->feed.ts.stream, piece, nbytes);
+}
+
+int pf_kmerjoin_set_gzip(pf_kmerjoin* j, int on, uint32_t flags) {
+    if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_set_gzip: null argument");
+    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY)) return fail(PF_ERR_ARG, "pf_kmerjoin_set_gzip: unknown flag");
+    kj_reset_out(j);                              // (a text half handed out would change its kind)
+    j->gz_on = on != 0; j->gz_flags = flags;
+    return PF_OK;
+}
+
+int pf_kmerjoin_gzip_stats(pf_kmerjoin* j, uint64_t* text_bytes, uint64_t* member_bytes, float* encode_ms, uint64_t* device_bytes) {
+    if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_gzip_stats: null argument");
+    if (text_bytes) *text_bytes = j->gz_text_bytes;
+    if (member_bytes) *member_bytes = j->gz_member_bytes;
+    if (encode_ms) *encode_ms = j->gz_ms;
+    if (device_bytes) *device_bytes = j->enc.device_bytes() + j->gz.d_out.cap;
+    return PF_OK;
 }
 
 int pf_kmerjoin_stats(pf_kmerjoin* j, uint64_t stats[8], float ms[3]) {

@@ -28,6 +28,11 @@ All three read a table the same two ways, written once here: a device-gzipped fi
 it lands (`pass_member_file` -> pf_*_members), any other is read block by block through the host (`scan_lines`);
 `route_file` chooses, and falls back to the second when the device decoder does not take a block.
 
+panfeed-get-kmers --gz-output writes the annotated table as such a file itself: the device join's rows are gzipped where
+they were written (pf_kmerjoin_set_gzip) and only the members come to the host; text made on the host -- the header line,
+a bunch or a run that went through pandas -- goes into the same file as small members (output.SmallMemberGzipWriter), so
+that panfeed-plot reads all of it on the device.
+
 One thing the reference leaves to chance is kept out of the comparison: it iterates over Python `set`s of cluster
 names, so the order of its printed clusters / blocks changes with PYTHONHASHSEED.  Here clusters come in order of their
 first appearance in kmers_to_hashes.tsv.
@@ -254,10 +259,19 @@ class KmerJoin:
     def stats(self):
         st, ms = (C.c_uint64 * 8)(), (C.c_float * 3)()
         _lib.check(self.L.pf_kmerjoin_stats(self.h, st, ms))
+        gt, gm, gms, gdev = C.c_uint64(), C.c_uint64(), C.c_float(), C.c_uint64()
+        _lib.check(self.L.pf_kmerjoin_gzip_stats(self.h, C.byref(gt), C.byref(gm), C.byref(gms), C.byref(gdev)))
         return {"bytes_scanned": int(st[0]), "rows_written": int(st[1]), "raw_rows": int(st[2]), "members_inflated": int(st[3]),
                 "text_bytes_inflated": int(st[4]), "inflate_device_bytes": int(st[5]), "hash_rejects": int(st[6]),
                 "unmatched_written": int(st[7]),
-                "survey_ms": float(ms[0]), "write_ms": float(ms[1]), "inflate_ms": float(ms[2])}
+                "survey_ms": float(ms[0]), "write_ms": float(ms[1]), "inflate_ms": float(ms[2]),
+                "gzip_text_bytes": int(gt.value), "gzip_member_bytes": int(gm.value), "gzip_ms": float(gms.value),
+                "gzip_device_bytes": int(gdev.value)}
+
+    def set_gzip(self, on, flags=0):
+        """while on, join_file's write() gets gzip members of the annotated rows (modes 0 and 1; KJ_RAW stays text).  flags:
+        the device encoder's test hooks (_lib.GZ_*)"""
+        _lib.check(self.L.pf_kmerjoin_set_gzip(self.h, 1 if on else 0, int(flags)))
 
     def counters(self):
         """per bunch: rows, unmatched rows, output bytes under either rendering, plainness flags"""
@@ -583,6 +597,9 @@ def _options(description, kmers):
                             "number of clusters makes the whole run two passes over the file, one survey and one join)")
         p.add_argument("--host-join", action="store_true", default=False,
                        help="join kmers.tsv to the associations in pandas, bunch by bunch (by default the GPU looks the rows up and writes them)")
+        p.add_argument("--gz-output", default=None, metavar="PATH",
+                       help="write the annotated table to PATH (ending in .gz) as small gzip members, compressed on the GPU where "
+                            "the GPU wrote the rows, in place of printing it; panfeed-plot inflates such a file on the GPU")
     p.add_argument("--host-associations", action="store_true", default=False,
                    help="read the whole associations table with pandas (by default the GPU keeps the lines that may pass the "
                         "threshold and pandas reads those)")
@@ -694,7 +711,10 @@ def get_clusters(argv=None, out=None):
 def get_kmers(argv=None, out=None):
     """panfeed-get-kmers: association results joined with the k-mers' clusters and positions"""
     out = out or sys.stdout
-    args = _options("Annotate association results with positional information", True).parse_args(argv)
+    parser = _options("Annotate association results with positional information", True)
+    args = parser.parse_args(argv)
+    if args.gz_output is not None and not args.gz_output.endswith(".gz"):
+        parser.error("--gz-output: the path must end in .gz (the downstream tools choose the device route by that suffix)")
     a, passing = _associations(args, index_name="hashed_pattern")
     header, rows = _filtered(passing, False, args.kmers_to_hashes, args)
     h = _table(header, rows).set_index("hashed_pattern")
@@ -714,7 +734,11 @@ def get_kmers(argv=None, out=None):
     bunch_keys = [[lit for c in bunch if c is not _NAN_KEY for lit in literal[_key(c)]] for bunch in bunches]
     join, plan = (None, None) if args.host_join or not bunches else _device_join(args, b, bunch_keys)
     first = True
+    sink = None
     try:
+        if args.gz_output is not None:               # (the table goes there and nothing to `out`)
+            from .output import SmallMemberGzipWriter
+            out = sink = SmallMemberGzipWriter(args.gz_output, _lib.load().pf_gzip_device_chunk_bytes())
         for n, keys in enumerate(bunch_keys):
             if join is not None and not plan[n]["flags"]:
                 first = _device_bunch(args, join, plan, n, b, out, first)
@@ -730,6 +754,8 @@ def get_kmers(argv=None, out=None):
             t.to_csv(out, sep="\t", header=first)
             first = False
     finally:
+        if sink is not None:
+            sink.close()
         if join is not None:
             KmerJoin.last_stats = dict(join.stats(), rows=sum(c["rows"] for c in plan), unmatched=sum(c["unmatched"] for c in plan))
             join.close()
@@ -759,6 +785,8 @@ def _device_join(args, b, bunch_keys):
                     [(c.encode(), k.encode()) for c, k in texts["keys"]], texts["text0"], texts["text1"], texts["empty"],
                     device=args.device)
     try:
+        if args.gz_output is not None:
+            join.set_gzip(True)
         plan = join.survey_file(args.kmers, device_gunzip=False if args.host_gunzip else None)
     except BaseException:
         join.close()
@@ -767,8 +795,11 @@ def _device_join(args, b, bunch_keys):
     return join, plan
 
 
-def _writer(out):
-    """bytes -> out: to its .buffer when it has one that takes UTF-8 as it is"""
+def _writer(out, members=False):
+    """bytes -> out: to its .buffer when it has one that takes UTF-8 as it is; `members`: they are gzip members for a
+    writer of such"""
+    if members:
+        return out.write_members
     raw = getattr(out, "buffer", None)
     if raw is not None and str(getattr(out, "encoding", "")).lower().replace("-", "").replace("_", "") == "utf8":
         out.flush()
@@ -782,7 +813,7 @@ def _device_bunch(args, join, plan, n, b, out, first):
         if first:
             out.write(join.header)
         # (an unmatched row makes pandas promote the table's integer columns: the survey counted them)
-        join.join_file(args.kmers, n, 1 if plan[n]["unmatched"] else 0, _writer(out))
+        join.join_file(args.kmers, n, 1 if plan[n]["unmatched"] else 0, _writer(out, members=args.gz_output is not None))
         return False
     # how="left" stays a pandas join, over the rows of the bunch that have a key only: a left join drops the others
     kept = []

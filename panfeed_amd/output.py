@@ -121,6 +121,80 @@ class MemberGzipWriter:
         self.close()
 
 
+class SmallMemberGzipWriter:
+    """A .gz file every member of which the device decoder takes (pf_gunzip_device): panfeed-get-kmers --gz-output's.
+    `write_members(view)` appends the GPU's members as they are; `write(text)` takes text made on the host -- the header
+    line, what pandas printed -- and compresses it into members of at most `chunk_bytes` of text each, the file's first
+    line in a member of its own.  Every member starts with the same eight bytes (FLG = 0, MTIME = 0), which is how the
+    decoder finds them.  Host text is held back until a member's worth has gathered, and goes out in front of the next
+    members or at close; a file nothing was written to is one empty member."""
+
+    def __init__(self, path, chunk_bytes, compresslevel=6):
+        self.fh = open(path, "wb")
+        self.chunk, self.level = int(chunk_bytes), compresslevel
+        self.held = b""                          # host text not yet in a member
+        self.first_line = True                   # the file's first line has not gone out yet
+        self.bytes_written = self.text_bytes = self.host_members = 0
+        self.closed = False
+
+    def _member(self, text):
+        import gzip
+        member = gzip.compress(bytes(text), compresslevel=self.level, mtime=0)
+        self.fh.write(member)
+        self.bytes_written += len(member)
+        self.text_bytes += len(text)
+        self.host_members += 1
+
+    def _emit(self, everything):
+        data, at = memoryview(self.held), 0
+        if self.first_line and data.nbytes:
+            nl = self.held.find(b"\n")
+            if nl < 0 and not everything:
+                return
+            at = nl + 1 if nl >= 0 else data.nbytes
+            for a in range(0, at, self.chunk):   # (a first line over a member's size takes several)
+                self._member(data[a:min(at, a + self.chunk)])
+            self.first_line = False
+        while data.nbytes - at >= (1 if everything else self.chunk):
+            self._member(data[at:at + self.chunk])
+            at += self.chunk
+        self.held = bytes(data[at:])
+
+    def write(self, text):
+        b = text.encode() if isinstance(text, str) else bytes(text)
+        if b:
+            self.held = self.held + b if self.held else b
+            if self.first_line or len(self.held) >= self.chunk:
+                self._emit(False)
+        return len(text)
+
+    def write_members(self, view):
+        if len(view):
+            self._emit(True)
+            self.first_line = False
+            self.fh.write(view)
+            self.bytes_written += len(view)
+
+    def flush(self):
+        self.fh.flush()
+
+    def close(self):
+        if self.closed:
+            return
+        self._emit(True)
+        if not self.bytes_written:
+            import gzip
+            self.fh.write(gzip.compress(b"", compresslevel=self.level, mtime=0))
+        self.fh.close()
+        self.closed = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 def create_kmer_stroi(output, compress=False, device_gzip=False):
     """kmers.tsv[.gz] with its header written (input.py:235-247).  device_gzip: a writer that also takes the GPU's
     members."""

@@ -3,7 +3,8 @@
 Options, defaults, refusals (their order and exit status) and output file names are the reference's (`plot.py:35-136`,
 `:145-158`, `:165-167`, `:196-198`), plus `--device` as the downstream tools have.  What the reference does with one
 pandas frame of the whole annotated table and three `pivot_table`s per cluster (`:195-305`) is done here by
-`pf_plotgrid_*` (csrc/pf_rowfilter.hip): the table streams through the GPU in blocks of complete lines, and every
+`pf_plotgrid_*` (csrc/pf_rowfilter.hip): the table streams through the GPU in blocks of complete lines -- a `.gz` of small
+members, as `panfeed-get-kmers --gz-output` writes it, goes up compressed and is inflated there -- and every
 cluster's grid (largest significance, row count, the one row's letter) is built there with integer atomics.  What is
 left on the host is small and goes through the reference's own pandas / numpy statements: the phenotype, the parse of
 the distinct p-value texts and their -log10, the order of the strains, the hybrid normalisation.  Rendering is
@@ -71,6 +72,9 @@ def get_options(argv=None):
     parser.add_argument("-v", action="count", default=0, help="Increase verbosity level")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     parser.add_argument("--device", type=int, default=0, help="GPU the grids are built on")
+    parser.add_argument("--host-gunzip", action="store_true", default=False,
+                        help="inflate a .gz table on the host (by default a file of small members, as panfeed-get-kmers "
+                             "--gz-output writes, is inflated on the GPU)")
     return parser.parse_args(argv)
 
 
@@ -195,18 +199,28 @@ for _b, _v in BASE2INT.items():
 class GridBuilder:
     """pf_plotgrid: the annotated table streamed through the device, then grids for batches of clusters"""
 
+    device_gunzip_files = 0         # files, over all builders, that went the device gunzip route to their end
+    fallback_files = 0              # and files the automatic mode began there and read again through gzip
+
     def __init__(self, strains, columns, start=None, stop=None, device=0):
         from . import _lib
         self._lib = _lib
         self.L = _lib.load()
         names = [str(s).encode() for s in strains]
-        arr, lens = _lib.c_strings(names)
-        cols = (C.c_int32 * 6)(*columns)
         zoom = start is not None
+        self.args = (int(device), names, tuple(columns), 1 if zoom else 0, int(start) if zoom else 0, int(stop) if zoom else 0)
         self.h = C.c_void_p()
-        _lib.check(self.L.pf_plotgrid_create(int(device), arr, lens, len(names), cols, 1 if zoom else 0,
-                                             int(start) if zoom else 0, int(stop) if zoom else 0, C.byref(self.h)))
+        self.fallbacks = 0              # files the automatic mode began on the device and read again through gzip
+        self._create()
         self.n_strains = len(names)
+
+    def _create(self):
+        """a fresh handle: an empty grid"""
+        self.close()
+        device, names, columns, zoom, start, stop = self.args
+        arr, lens = self._lib.c_strings(names)
+        self._lib.check(self.L.pf_plotgrid_create(device, arr, lens, len(names), (C.c_int32 * 6)(*columns), zoom, start, stop,
+                                                  C.byref(self.h)))
 
     def close(self):
         if self.h:
@@ -215,7 +229,19 @@ class GridBuilder:
 
     __del__ = close
 
-    def scan_file(self, path, block_bytes=None):
+    def _scan_members(self, path, block_bytes):
+        """scan_file's device gunzip route: True, or None when a block was not taken"""
+        from .downstream import GZ_BLOCK_DIVISOR, pass_member_file
+
+        def call(data, last):
+            used, taken = C.c_uint64(), C.c_int()
+            self._lib.check(self.L.pf_plotgrid_scan_members(self.h, data, len(data), 1 if last else 0, C.byref(used), C.byref(taken)))
+            return used.value, taken.value
+
+        return pass_member_file(path, block_bytes or BLOCK_BYTES // GZ_BLOCK_DIVISOR,
+                                lambda: self._lib.check(self.L.pf_plotgrid_members_begin(self.h, 1)), call) or None
+
+    def _scan_host(self, path, block_bytes):
         from .downstream import open_table, scan_lines
 
         def scan(buf, n):
@@ -228,6 +254,21 @@ class GridBuilder:
         with open_table(path) as fh:
             fh.readline()
             scan_lines(fh, scan, block_bytes or BLOCK_BYTES)
+        return True
+
+    def _fell_back(self):
+        """a file refused part-way has left rows in the grid: it starts over on an empty one"""
+        self.fallbacks += 1
+        self._create()
+
+    def scan_file(self, path, block_bytes=None, device_gunzip=None):
+        """The data lines of the annotated table into the grid.  A .gz made of small members with the plain gzip header is
+        inflated on the device and scanned there, as device_gunzip says (downstream.route_file: None tries it for such a
+        file and reads the file again through gzip when a block is not taken, True raises NotTaken then, False never
+        tries); block_bytes then counts compressed bytes.  Any other file is read block by block through the host."""
+        from .downstream import route_file
+        route_file(path, device_gunzip, lambda: self._scan_members(path, block_bytes), lambda: self._scan_host(path, block_bytes),
+                   GridBuilder, self._fell_back)
 
     def finish(self):
         nc, npv, nr = C.c_uint32(), C.c_uint64(), C.c_uint64()
@@ -275,8 +316,12 @@ class GridBuilder:
     def stats(self):
         b, ln, r, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
         self._lib.check(self.L.pf_plotgrid_stats(self.h, C.byref(b), C.byref(ln), C.byref(r), C.byref(ms)))
+        gm, gt, gms, gdev = C.c_uint64(), C.c_uint64(), C.c_float(), C.c_uint64()
+        self._lib.check(self.L.pf_plotgrid_gunzip_stats(self.h, C.byref(gm), C.byref(gt), C.byref(gms), C.byref(gdev)))
         return {"bytes_scanned": int(b.value), "lines": int(ln.value), "records": int(r.value),
-                "device_ms": float(ms.value)}
+                "device_ms": float(ms.value),
+                "members_inflated": int(gm.value), "text_bytes_inflated": int(gt.value), "inflate_ms": float(gms.value),
+                "inflate_device_bytes": int(gdev.value), "gunzip_fallbacks": self.fallbacks}
 
 
 def _figure(gene, key, cnt, ph, names, ids_of, mn, mx, threshold, minimum_pvalue, alpha, xticks, nucleotides):
@@ -331,11 +376,11 @@ def _figure(gene, key, cnt, ph, names, ids_of, mn, mx, threshold, minimum_pvalue
 
 
 def _figures(kmers, ph, columns, threshold=1, start=None, stop=None, minimum_pvalue=1e-10, nucleotides=False,
-             alpha=0, xticks=200, device=0, block_bytes=None, grid_budget=None):
+             alpha=0, xticks=200, device=0, block_bytes=None, grid_budget=None, device_gunzip=None):
     strains = list(dict.fromkeys(ph.index))
     gb = GridBuilder(strains, columns, start, stop, device)
     try:
-        gb.scan_file(kmers, block_bytes)
+        gb.scan_file(kmers, block_bytes, device_gunzip)
         gb.finish()
         gb.set_significance(significance_of(gb.pvalue_texts))
         ids_of = {s: i for i, s in enumerate(strains)}
@@ -371,14 +416,15 @@ def _figures(kmers, ph, columns, threshold=1, start=None, stop=None, minimum_pva
 
 def cluster_figures(kmers, phenotype, column="lrt-pvalue", threshold=1, start=None, stop=None, phenotype_column=None,
                     sample=None, minimum_pvalue=1e-10, nucleotides=False, alpha=0, xticks=200, device=0,
-                    block_bytes=None, grid_budget=None):
-    """One ClusterFigure per cluster of the annotated table `kmers` (panfeed-get-kmers' output; .gz read through gzip)
-    that has rows in the zoom, in sorted() order.  `phenotype` is the phenotype TSV's path.  Raises Refusal where the
-    reference exits with status 1."""
+                    block_bytes=None, grid_budget=None, device_gunzip=None):
+    """One ClusterFigure per cluster of the annotated table `kmers` (panfeed-get-kmers' output; a .gz of small members, as
+    its --gz-output writes, is inflated on the GPU, any other .gz read through gzip: device_gunzip as
+    GridBuilder.scan_file's) that has rows in the zoom, in sorted() order.  `phenotype` is the phenotype TSV's path.
+    Raises Refusal where the reference exits with status 1."""
     ph = read_phenotype(phenotype, phenotype_column, sample)
     columns = table_columns(kmers, column)
     yield from _figures(kmers, ph, columns, threshold, start, stop, minimum_pvalue, nucleotides, alpha, xticks, device,
-                        block_bytes, grid_budget)
+                        block_bytes, grid_budget, device_gunzip)
 
 
 def _colormaps():
@@ -473,7 +519,8 @@ def plot(argv=None):
         matplotlib.use("Agg")
     cmap1, cmap2 = _colormaps()
     for fig in _figures(args.kmers, ph, columns, args.threshold, args.start, args.stop, args.minimum_pvalue,
-                        args.nucleotides, args.alpha, args.xticks, args.device):
+                        args.nucleotides, args.alpha, args.xticks, args.device,
+                        device_gunzip=False if args.host_gunzip else None):
         render(fig, args, cmap1, cmap2)
     render_legend(args, cmap2)
     return 0
