@@ -520,6 +520,22 @@ int pf_render_device_ex(pf_ctx* ctx, const char* const* names, const char* extra
  * __main__.py:67-81).  *text points into the context's pinned memory, valid until the call after the next one of
  * this function / pf_render_device. */
 int pf_render_pattern_rows(pf_ctx* ctx, const uint32_t* pids, uint64_t n, const char** text, uint64_t* nbytes);
+/* The same rows (the bytes pf_render_pattern_rows gives for the same ids: any ids of the pool, in this order, repeats
+ * allowed) as a stream, in device memory of two slices of text plus 8 bytes per row (the ids and the row lengths; the
+ * host keeps 12 bytes per row), whatever the size of the text: the text is cut at row boundaries into slices
+ * of at most slice_bytes (0, or more than 64 MiB: 64 MiB; a row longer than slice_bytes is a slice of its own), written
+ * into two device buffers used alternately.  begin checks the ids (one at or beyond pf_pattern_count is PF_ERR_ARG),
+ * copies them (pids need not outlive the call) and measures every row; *total_text_bytes: the text's size, *n_slices:
+ * the slices.  PF_ERR_STATE while a kmers.tsv stream or another stream of pattern rows of the context has not reached
+ * its end: the streams share their buffers.  Ends the text of pf_render_kmers_tsv_device. */
+int pf_pattern_rows_stream_begin(pf_ctx* ctx, const uint32_t* pids, uint64_t n, uint64_t slice_bytes,
+                                 uint64_t* total_text_bytes, uint32_t* n_slices);
+/* The next slice in pinned host memory owned by the context, valid until the next call; the slice after it has been
+ * queued on the context's stream already (rows, encode, copy).  Under pf_set_device_gzip the slice's gzip members are
+ * handed out in its place, and out[2] of pf_device_gzip_text_bytes counts the text behind them.  *nbytes == 0 at the end
+ * (the stream is then over).  A pf_submit, pf_reset_patterns, a kmers.tsv text begun or pf_set_device_gzip ends the
+ * stream: the next call is PF_ERR_STATE.  (pf_merge_patterns only reads the pool and leaves the stream alone.) */
+int pf_pattern_rows_stream_next(pf_ctx* ctx, const char** ptr, uint64_t* nbytes);
 
 /* Parallel gzip of a block of output text (the reference: gzip.open(..., "wt", compresslevel=9),
  * /root/reference/panfeed/input.py:239-241,255-258 -- one core).  `data` is cut at line ends into chunks of about
@@ -572,7 +588,8 @@ int pf_gunzip_host_model(const char* members, uint64_t n, char** out, uint64_t* 
  * host renderers are not affected. */
 int pf_set_device_gzip(pf_ctx* ctx, int on, uint32_t flags);
 /* The text sizes behind the compressed bytes: out[0], out[1] = bytes of kmers_to_hashes / hashes_to_patterns text of the
- * last pf_render_device[_ex]; out[2] = text bytes the open (or last) kmers.tsv stream has handed out so far. */
+ * last pf_render_device[_ex]; out[2] = text bytes the open (or last) kmers.tsv or pattern-row stream has handed out so
+ * far. */
 int pf_device_gzip_text_bytes(pf_ctx* ctx, uint64_t out[3]);
 
 /*

@@ -140,6 +140,7 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_dev_upload", "pf_dev_download", "pf_synth_expand", "pf_pack_acgt", "pf_b64_digest",
            "pf_render_kmers_to_hashes", "pf_render_hashes_to_patterns", "pf_render_kmers_tsv", "pf_render_kmers_tsv_device", "pf_device_text_chunk", "pf_free_text",
            "pf_kmers_tsv_stream_begin", "pf_kmers_tsv_stream_next",
+           "pf_pattern_rows_stream_begin", "pf_pattern_rows_stream_next",
            "pf_pack_records", "pf_packed_view", "pf_packed_free",
            "pf_pangenome_open", "pf_pangenome_open_device", "pf_pangenome_open_device_cb", "pf_debug_open_hostsink", "pf_pangenome_close", "pf_pangenome_info", "pf_pangenome_strain",
            "pf_pangenome_take_log", "pf_pangenome_next", "pf_records_free", "pf_pangenome_contigs",
@@ -269,6 +270,9 @@ def _load_locked():
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_uint64)]
     L.pf_render_pattern_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pf_pattern_rows_stream_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_uint32)]
+    L.pf_pattern_rows_stream_next.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pf_pangenome_weights.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     L.pf_pangenome_set_range.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     L.pf_rowfilter_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]

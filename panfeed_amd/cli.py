@@ -1,4 +1,5 @@
-"""`python -m panfeed_amd`: the `panfeed` command (the reference's `panfeed/__main__.py`) on one GPU.
+"""`python -m panfeed_amd`: the `panfeed` command (the reference's `panfeed/__main__.py`) on one GPU, or with `--gpus N`
+on N of them.
 
 Option names, short forms, defaults and meanings are the reference's (`__main__.py:86-222`); so are the refusals, their
 order and their exit status (`__main__.py:234-242`, `input.py:213-216`).  The run itself is `pipeline.run_files`: the
@@ -7,7 +8,11 @@ native reader, the GPU, a writer thread.  Two options are added: `--device` (as 
 worker processes).  One refusal is new: `-k` outside 1..PF_MAX_K, before any file is read or the GPU touched.
 
 Unlike the reference, no `<output>/fastas/` directory is made (the reader splits the GFFs' `##FASTA` sections in
-memory), so none is left behind.  A run on more than one GPU is `sharded.run_files_sharded` under torchrun.
+memory), so none is left behind.
+
+`--gpus N` (N > 1) is `sharded.run_files_sharded` with one rank per GPU: this process touches no GPU and starts the ranks
+as fresh child processes (`rank.launch`).  With `WORLD_SIZE` and `RANK` in the environment -- a launcher of the user's
+own -- the command is one rank of that world.  `PANFEED_SHARED_GPU=1` rehearses the control flow on one GPU.
 """
 import argparse
 import logging
@@ -25,8 +30,11 @@ BATCH_CLUSTERS = 256    # pipeline.run_files' default
 def get_options(argv=None):
     p = argparse.ArgumentParser(
         prog="panfeed",
-        description="Gene-cluster-specific k-mers and their presence/absence patterns over a pangenome, on one AMD GPU. "
-                    "For a run over several GPUs use panfeed_amd.sharded.run_files_sharded under torchrun.")
+        description="Gene-cluster-specific k-mers and their presence/absence patterns over a pangenome, on one AMD GPU, or "
+                    "with --gpus N on N of them (the files are the same).  Under a launcher such as torchrun, which sets "
+                    "WORLD_SIZE and RANK, the command is one rank of that world.  PANFEED_SHARED_GPU=1 runs every rank on "
+                    "--device with host collectives: a rehearsal that exercises control flow only, never a multi-GPU "
+                    "measurement.")
     p.add_argument("-g", "--gff", required=True,
                    help="GFF files: a directory of them, or a file naming one path per line (the sequences come from "
                         "each GFF's ##FASTA section unless -f is given; file names must match the table's strain columns)")
@@ -70,6 +78,8 @@ def get_options(argv=None):
     p.add_argument("--stop-on-missing", action="store_true", default=False,
                    help="fail when a strain, contig or gene of the table is not found (default: warn and go on)")
     p.add_argument("--device", type=int, default=0, help="GPU to run on (default: %(default)d)")
+    p.add_argument("--gpus", type=int, default=None,
+                   help="GPUs to run on, one process (rank) each, devices 0..N-1 (default: one GPU, --device)")
     p.add_argument("--batch-clusters", type=int, default=BATCH_CLUSTERS,
                    help="gene clusters per GPU batch (default: %(default)d)")
     p.add_argument("-v", action="count", default=0, help="more log output (-v: debug)")
@@ -96,9 +106,11 @@ def read_names(path):
         return {line.rstrip("\n") for line in fh}
 
 
-def main(argv=None, run=None):
-    """the panfeed command; returns the exit status.  run: what does the work (default pipeline.run_files; tests
-    pass their own)"""
+def main(argv=None, run=None, launch=None, rank_entry=None):
+    """the panfeed command; returns the exit status.  run: what does the work on one GPU (default pipeline.run_files);
+    launch: what starts the ranks of `--gpus N` (default rank.launch); rank_entry: what this process does as one rank of
+    a launcher's world (default rank.run_rank).  Tests pass their own."""
+    from . import rank as rank_mod
     args = get_options(argv)
     set_logging(args.v)
     k = args.kmer_length
@@ -127,17 +139,52 @@ def main(argv=None, run=None):
     if args.genes is not None:
         logger.debug(f"Reading gene clusters ({args.genes})")
         genes = read_names(args.genes)
-    if os.path.exists(args.output):
+    as_rank = rank_mod.launched()         # (rank 0 creates the directory: the ranks look together, in run_files_sharded)
+    if os.path.exists(args.output) and not as_rank:
         logger.error(f"Output directory {args.output} exists: remove it or choose another")
         return 1
+    many = as_rank or (args.gpus is not None and args.gpus != 1)
+    if args.gpus is not None and args.gpus < 1:
+        logger.error("--gpus must be at least 1")
+        return 2
+    if many and args.device != 0 and not rank_mod.shared_gpu():
+        logger.error("--device cannot be combined with a run on several GPUs: rank r runs on GPU r")
+        return 2
+    if many and not as_rank and not rank_mod.shared_gpu():
+        import torch                      # (counting the devices does not initialise the GPU)
+        ndev = torch.cuda.device_count()
+        if ndev < args.gpus:
+            logger.error(f"--gpus {args.gpus}: {ndev} device{'s' if ndev != 1 else ''} on this machine -- one rank per GPU; "
+                         "nothing was run (PANFEED_SHARED_GPU=1 rehearses the control flow on one GPU)")
+            return 2
     more = {}
     if args.gpu_compress:
         more["device_gzip"] = True
         if args.multiple_files:
             logger.info("--gpu-compress with --multiple-files: the per-cluster files are compressed on the host")
+    from ._lib import PanfeedHipError
+    if many:
+        options = dict(fastadir=args.fasta, klength=k, canon=not args.non_canonical, consider_missing=args.consider_missing,
+                       patfilt=not args.no_filter, maf=args.maf, upstream=args.upstream, downstream=args.downstream,
+                       downstream_start_codon=args.downstream_start_codon, targets=tuple(sorted(targets)),
+                       genes=sorted(genes) if genes is not None else None, compress=args.compress or args.gpu_compress,
+                       multiple_files=args.multiple_files, batch_clusters=args.batch_clusters, gpu=args.device,
+                       raise_missing=args.stop_on_missing, **more)
+        if not as_rank:
+            logger.info(f"Extracting k-mers on {args.gpus} GPUs" +
+                        (" (PANFEED_SHARED_GPU=1: a rehearsal on one)" if rank_mod.shared_gpu() else ""))
+            return (launch or rank_mod.launch)(args.gpus, args.presence_absence, args.gff, args.output, verbose=args.v,
+                                               **options)
+        logger.info(f"Extracting k-mers as rank {os.environ['RANK']} of {os.environ['WORLD_SIZE']}")
+        try:
+            stats = (rank_entry or rank_mod.run_rank)(args.presence_absence, args.gff, args.output, **options)
+        except (PanfeedHipError, FileExistsError, RuntimeError) as e:
+            logger.error(str(e))
+            return 1
+        rank_mod.report(stats or {}, args.output)
+        return 0
     if run is None:
         from .pipeline import run_files as run
-    from ._lib import PanfeedHipError
     logger.info("Extracting k-mers")
     try:
         stats = run(args.presence_absence, args.gff, args.output, fastadir=args.fasta, klength=k,

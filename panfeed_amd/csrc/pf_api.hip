@@ -270,6 +270,23 @@ struct GzMode {
     float decode_ms = 0.0f;                   // the last pf_gunzip_device's inflate launches (hipEvent)
     void destroy_events() { if (ev_copy) (void)hipEventDestroy(ev_copy); }
 };
+// hashes_to_patterns rows of a list of patterns as a stream (pf_pattern_rows_stream_begin / _next): the ids and their row
+// lengths on the device, the text cut into slices at row boundaries.  Slice i is written into TargetText::text[i & 1] and
+// leaves through TargetText::pins[i & 1] -- as it is, or as its members from GzMode::block_members[i & 1] -- all on the
+// context's stream.  These are the kmers.tsv stream's buffers and cursors: one of the two streams is open at a time.
+struct PatternRowStream {
+    bool active = false;
+    DevBuf order, rlen, rowoff[2];            // the ids, their row lengths; a slice's row offsets (from the slice's start)
+    PinBuf pin_rowoff[2];
+    std::vector<uint64_t> row_off;            // of the whole text, n + 1
+    std::vector<uint64_t> cut;                // slice i holds rows [cut[i], cut[i + 1])
+    uint32_t queued = 0, handed = 0;          // slices queued on the stream, slices handed out
+    // on `stream`: slice i's text has arrived in pinned memory, or under device gzip is encoded and its size has arrived
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    uint32_t n_slices() const { return cut.empty() ? 0u : (uint32_t)cut.size() - 1; }
+    uint64_t bytes(uint32_t i) const { return row_off[cut[i + 1]] - row_off[cut[i]]; }
+    void destroy_events() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+};
 int gz_check_flags(uint32_t flags, const char* who) {
     if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY)) return fail(PF_ERR_ARG, "%s: unknown flag", who);
     return PF_OK;
@@ -305,7 +322,8 @@ struct pf_ctx {
     struct UPool { DevBuf word_off, len, sample, ord, bits, list; PinBuf pin; };
     RenderText txt;                        // the text path: the render's state,
     TargetText kt;                         // the target text's (kmers.tsv) with its stream,
-    GzMode gz;                             // and the gzip mode
+    GzMode gz;                             // the gzip mode,
+    PatternRowStream pr;                   // and the stream of pattern rows
     pf_batch last{};                      // the last pf_submit's batch arrays as device pointers (valid until the next submit)
     uint32_t last_nseg = 0;
     uint64_t last_words = 0;              // words of last.packed: the batch's, or the buffer pf_submit_gather filled
@@ -375,6 +393,15 @@ void kt_stream_end(pf_ctx* c) {
     for (int b = 0; b < 2; b++) { free(S.htext[b]); S.htext[b] = nullptr; }
     S.active = false; c->kt.flight.valid = false;
     S.hseqs.clear(); S.host = KtHostText{}; S.plan = KtPlan{};
+}
+// the end of a pattern-row stream (its last slice handed out, the next pf_submit, a kmers.tsv text begun, pf_destroy):
+// nothing of it is in flight afterwards
+void pr_stream_end(pf_ctx* c) {
+    PatternRowStream& S = c->pr;
+    if (S.active) (void)hipStreamSynchronize(c->stream);
+    S.active = false;
+    S.row_off.clear(); S.cut.clear();
+    S.queued = S.handed = 0;
 }
 
 int get_event(pf_ctx* c, hipEvent_t* ev) {
@@ -739,11 +766,12 @@ void pf_destroy(pf_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     kt_stream_end(c);                     // (before its pinned blocks go)
+    pr_stream_end(c);
     for (auto& e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     for (auto e : c->ev_stage) if (e) (void)hipEventDestroy(e);
     for (auto e : c->ev_part) if (e) (void)hipEventDestroy(e);
-    c->kt.destroy_events(); c->gz.destroy_events();
+    c->kt.destroy_events(); c->gz.destroy_events(); c->pr.destroy_events();
     for (auto e : {c->ev_t0, c->ev_t1, c->ev_fork, c->ev_join})
         if (e) (void)hipEventDestroy(e);
     if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
@@ -824,6 +852,7 @@ int pf_create(pf_ctx** out, int device, const pf_opts* o) {
 int pf_reset_patterns(pf_ctx* c) {
     if (!c) return fail(PF_ERR_ARG, "null context");
     HIPCHK(hipSetDevice(c->device));
+    pr_stream_end(c);                     // (its rows were measured in the pool that goes now)
     PFCHK(reset_patterns(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     return PF_OK;
@@ -1872,7 +1901,8 @@ struct SubmitRun {
 
 int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* counters, uint64_t* need, bool rerun) {
     c->have_batch = false;
-    kt_stream_end(c);                     // a kmers.tsv stream of the batch before is over
+    kt_stream_end(c);                     // a kmers.tsv stream of the batch before is over,
+    pr_stream_end(c);                     // and so is a stream of pattern rows
     // whatever way this call ends, nothing it queued is still reading the caller's arrays or the pinned staging
     // blocks afterwards (the successful path has waited already; an error return may come with work in flight)
     struct Drain { hipStream_t s, s2; ~Drain() { (void)hipStreamSynchronize(s2); (void)hipStreamSynchronize(s); } } drain{c->stream, c->side};
@@ -2477,6 +2507,7 @@ int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget, b
     if (!c->have_batch) return fail(PF_ERR_STATE, "%s without a successful pf_submit", who);
     HIPCHK(hipSetDevice(c->device));
     kt_stream_end(c);
+    pr_stream_end(c);                              // (a stream of pattern rows has these buffers)
     c->kt.bytes = 0;                               // (pf_device_text_chunk's text is gone: the buffers are reused)
     TargetText::Stream& S = c->kt.stream;
     S.active = true;
@@ -2561,6 +2592,18 @@ int kt_gz_buffers(pf_ctx* c, uint64_t block_text) {
     if (!G.ev_copy) HIPCHK(hipEventCreateWithFlags(&G.ev_copy, hipEventDisableTiming));
     return PF_OK;
 }
+
+// Device gzip, a block of `text` bytes whose encode into block_members[slot] the caller has synchronised with: only the
+// members cross to the host.  *n: their size; their copy into the slot's pinned block is queued on st with ev_copy behind
+// it, for the caller to wait for once the next block is on its way.
+int gz_block_down(pf_ctx* c, int slot, uint64_t text, hipStream_t st, uint64_t* n) {
+    GzMode& G = c->gz;
+    PFCHK(G.enc.member_bytes(slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, n));
+    G.raw[2] += text;
+    HIPCHK(hipMemcpyAsync(c->kt.pins[slot].p, G.block_members[slot].p, *n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(G.ev_copy, st));
+    return PF_OK;
+}
 }  // namespace
 
 // The same rows written by the GPU (kt_len_kernel / kt_text_kernel) for the sequences kt_layout gives it and by the host
@@ -2619,13 +2662,9 @@ int pf_kmers_tsv_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
     uint64_t n = c->kt.flight.n;
     hipEvent_t arrival = nullptr;                          // what else the hand-out waits for, once the next block is queued
     if (G.on) {
-        // only the members cross to the host: their copy goes behind the encode and before the next block's, which runs
-        // while they arrive
-        const uint64_t text = n;
-        PFCHK(G.enc.member_bytes(slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, &n));
-        G.raw[2] += text;
-        HIPCHK(hipMemcpyAsync(c->kt.pins[slot].p, G.block_members[slot].p, n, hipMemcpyDeviceToHost, c->side));
-        HIPCHK(hipEventRecord(arrival = G.ev_copy, c->side));
+        // their copy goes behind the encode and before the next block's, which runs while they arrive
+        PFCHK(gz_block_down(c, slot, n, c->side, &n));
+        arrival = G.ev_copy;
     }
     c->kt.flight.valid = false;
     if (S.cur < S.plan.ranges.size()) PFCHK(kt_block(c, slot ^ 1));      // the next block on its way meanwhile
@@ -3164,6 +3203,118 @@ int pf_render_pattern_rows(pf_ctx* c, const uint32_t* pids, uint64_t n, const ch
     return PF_OK;
 }
 
+namespace {
+// slice i of the open pattern-row stream queued on c->stream: its row offsets up, its rows written into text[i & 1], then
+// their copy into the slot's pinned block -- or, under device gzip, their encode into the slot's block of members
+int pr_produce(pf_ctx* c, uint32_t i) {
+    PatternRowStream& S = c->pr;
+    GzMode& G = c->gz;
+    hipStream_t st = c->stream;
+    const int slot = (int)(i & 1);
+    const uint64_t r0 = S.cut[i], rows = S.cut[i + 1] - r0, bytes = S.bytes(i);
+    uint64_t* ro = S.pin_rowoff[slot].as<uint64_t>();       // (the slot's slice before, i - 2, has been handed out)
+    for (uint64_t j = 0; j <= rows; j++) ro[j] = S.row_off[r0 + j] - S.row_off[r0];
+    HIPCHK(hipMemcpyAsync(S.rowoff[slot].p, ro, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, st));
+    char* text = c->kt.text[slot].as<char>();
+    PFCHK(hp_text(c, S.order.as<uint32_t>() + r0, S.rowoff[slot].as<uint64_t>(), (uint32_t)rows, text));
+    if (G.on)
+        PFCHK(G.enc.encode(st, slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, text, bytes, G.flags,
+                           G.block_members[slot].as<char>(), G.block_bound));
+    else HIPCHK(hipMemcpyAsync(c->kt.pins[slot].p, text, (size_t)bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(S.ev[slot], st));
+    S.queued = i + 1;
+    return PF_OK;
+}
+}  // namespace
+
+int pf_pattern_rows_stream_begin(pf_ctx* c, const uint32_t* pids, uint64_t n, uint64_t slice_bytes, uint64_t* total_text_bytes,
+                                 uint32_t* n_slices) {
+    if (!c || !total_text_bytes || !n_slices || (n && !pids)) return fail(PF_ERR_ARG, "pf_pattern_rows_stream_begin: null argument");
+    *total_text_bytes = 0; *n_slices = 0;
+    PatternRowStream& S = c->pr;
+    if (S.active || c->kt.stream.active)
+        return fail(PF_ERR_STATE, "pf_pattern_rows_stream_begin: a stream of this context (%s) is not at its end",
+                    S.active ? "pattern rows" : "kmers.tsv");
+    if (n > 0x7FFFFFFFull) return fail(PF_ERR_ARG, "pf_pattern_rows_stream_begin: too many rows in one stream");
+    for (uint64_t i = 0; i < n; i++)
+        if (pids[i] >= c->n_patterns) return fail(PF_ERR_ARG, "pf_pattern_rows_stream_begin: pattern id %u out of range (%u patterns)", pids[i], c->n_patterns);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const uint32_t P = (uint32_t)n;
+    const uint64_t cap = slice_bytes && slice_bytes < PfGzEncoder::BLOCK ? slice_bytes : PfGzEncoder::BLOCK;
+    S.active = true;
+    struct Guard { pf_ctx* c; bool ok; ~Guard() { if (!ok) pr_stream_end(c); } } guard{c, false};
+    c->gz.raw[2] = 0;
+    c->kt.bytes = 0;                               // (pf_device_text_chunk's text is gone: the buffers are reused)
+    c->kt.flight.valid = false;
+    HIPCHK(hipStreamSynchronize(c->side));         // (a block of that text that nobody asked for)
+    S.row_off.assign((size_t)P + 1, 0);
+    S.cut.assign(1, 0);
+    uint64_t max_bytes = 0, max_rows = 0;
+    if (P) {
+        // ---- the ids up, every row's length down: one launch
+        PFCHK(ensure_b64_dev(c));
+        PFCHK(S.order.ensure((size_t)P * 4));
+        PFCHK(S.rlen.ensure((size_t)P * 4));
+        HIPCHK(hipMemcpyAsync(S.order.p, pids, (size_t)P * 4, hipMemcpyHostToDevice, st));
+        PFCHK(hp_rowlen(c, S.order.as<uint32_t>(), 0u, P, S.rlen.as<uint32_t>()));
+        std::vector<uint32_t> rlen(P);
+        HIPCHK(hipMemcpyAsync(rlen.data(), S.rlen.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        // ---- the slices: cut between rows, a slice of at most `cap` bytes or of one row
+        uint64_t first = 0;
+        for (uint32_t i = 0; i < P; i++) {
+            if (i > first && S.row_off[i] - S.row_off[first] + rlen[i] > cap) { S.cut.push_back(i); first = i; }
+            S.row_off[i + 1] = S.row_off[i] + rlen[i];
+        }
+        S.cut.push_back(P);
+        for (uint32_t s = 0; s < S.n_slices(); s++) {
+            max_bytes = std::max(max_bytes, S.bytes(s));
+            max_rows = std::max(max_rows, S.cut[s + 1] - S.cut[s]);
+        }
+        // ---- the buffers of two slices, the events, the first slice on its way
+        if (c->gz.on) PFCHK(kt_gz_buffers(c, max_bytes));
+        for (int b = 0; b < 2; b++) {
+            PFCHK(c->kt.text[b].ensure((size_t)max_bytes + 64, true));
+            if (!c->gz.on) PFCHK(c->kt.pins[b].ensure((size_t)max_bytes, true));
+            PFCHK(S.rowoff[b].ensure((size_t)(max_rows + 1) * 8));
+            PFCHK(S.pin_rowoff[b].ensure((size_t)(max_rows + 1) * 8));
+            if (!S.ev[b]) HIPCHK(hipEventCreateWithFlags(&S.ev[b], hipEventDisableTiming));
+        }
+        PFCHK(pr_produce(c, 0));
+    }
+    *total_text_bytes = S.row_off[P];
+    *n_slices = S.n_slices();
+    guard.ok = true;
+    return PF_OK;
+}
+
+int pf_pattern_rows_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
+    if (!c || !ptr || !nbytes) return fail(PF_ERR_ARG, "pf_pattern_rows_stream_next: null argument");
+    *ptr = nullptr; *nbytes = 0;
+    PatternRowStream& S = c->pr;
+    if (!S.active) return fail(PF_ERR_STATE, "pf_pattern_rows_stream_next without an open pf_pattern_rows_stream_begin");
+    HIPCHK(hipSetDevice(c->device));
+    const uint32_t i = S.handed;
+    if (i >= S.n_slices()) { pr_stream_end(c); return PF_OK; }
+    struct Guard { pf_ctx* c; bool ok; ~Guard() { if (!ok) pr_stream_end(c); } } guard{c, false};
+    const int slot = (int)(i & 1);
+    HIPCHK(hipEventSynchronize(S.ev[slot]));       // the slice has arrived (gzip: is encoded, its size has arrived)
+    uint64_t n = S.bytes(i);
+    hipEvent_t arrival = nullptr;                  // what else the hand-out waits for, once the next slice is queued
+    if (c->gz.on) {
+        PFCHK(gz_block_down(c, slot, n, c->stream, &n));
+        arrival = c->gz.ev_copy;
+    }
+    S.handed = i + 1;
+    if (S.queued < S.n_slices()) PFCHK(pr_produce(c, S.queued));      // the next slice on its way meanwhile
+    if (arrival) HIPCHK(hipEventSynchronize(arrival));
+    *ptr = c->kt.pins[slot].as<char>();
+    *nbytes = n;
+    guard.ok = true;
+    return PF_OK;
+}
+
 int pf_render_device(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra,
                      const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes) {
     return pf_render_device_ex(c, names, extra_keys, n_extra, 0, kh, kh_bytes, hp, hp_bytes);
@@ -3333,6 +3484,7 @@ int pf_set_device_gzip(pf_ctx* c, int on, uint32_t flags) {
     PFCHK(gz_check_flags(flags, "pf_set_device_gzip"));
     HIPCHK(hipSetDevice(c->device));
     kt_stream_end(c);                     // (an open stream would change its kind half way)
+    pr_stream_end(c);
     if (on) PFCHK(c->gz.enc.ensure(c->n_cu));
     c->gz.on = on != 0; c->gz.flags = flags;
     return PF_OK;

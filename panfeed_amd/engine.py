@@ -260,7 +260,8 @@ class Engine:
         res = self.fetch()
         return self._render(hb, res)
 
-    def run_stream(self, records, batch_clusters=256, prefetch=2, defer_patterns=False, device_text=False):
+    def run_stream(self, records, batch_clusters=256, prefetch=2, defer_patterns=False, device_text=False,
+                   targets_sink=None):
         """Generator over BatchOutput: packs batch i+1 (host threads, pf_pack_records) while the GPU works on
         batch i and the caller writes batch i-1 -- the reference's reader / workers / writer pipeline
         (__main__.py:39-81,299-344) with the GPU in the workers' place and a deterministic order
@@ -277,7 +278,8 @@ class Engine:
                     return
                 yield build_batch_native(chunk, self.k, self.canon, self.W, stroi=self.stroi, first_ordinal=ordinal)
                 ordinal += len(chunk)
-        return self.run_batches(host_batches(), prefetch, device_text, defer_patterns=defer_patterns)
+        return self.run_batches(host_batches(), prefetch, device_text, defer_patterns=defer_patterns,
+                                targets_sink=targets_sink)
 
     def run_pangenome(self, pangenome, batch_clusters=256, prefetch=2, device_text=False, defer_patterns=False,
                       before_first_submit=None, targets_sink=None):
@@ -519,6 +521,34 @@ class Engine:
             _lib.check(self.L.pf_render_pattern_rows(self.ctx, part.ctypes.data_as(C.c_void_p), len(part),
                                                      C.byref(txt), C.byref(nb)))
             yield _take(txt, nb.value)
+
+    def stream_pattern_rows(self, pids, sink, slice_bytes=0):
+        """the same rows (the bytes of `render_pattern_rows(pids)`) handed to `sink` slice by slice as they leave the
+        device (pf_pattern_rows_stream_begin / _next): a memoryview of pinned memory, or under device_gzip a GzipMembers
+        of the slice's members, valid during the call; slice i + 1 is written (and encoded) while the sink has slice i.
+        Device memory: two slices of at most `slice_bytes` (0: 64 MiB) plus 8 bytes per row (the ids, the row lengths),
+        whatever the size of the text.  Returns (text bytes, bytes handed out, slices)."""
+        pids = np.ascontiguousarray(pids, dtype=np.uint32)
+        total, slices = C.c_uint64(), C.c_uint32()
+        _lib.check(self.L.pf_pattern_rows_stream_begin(self.ctx, pids.ctypes.data_as(C.c_void_p), len(pids),
+                                                       int(slice_bytes), C.byref(total), C.byref(slices)))
+        ptr, nb = C.c_void_p(), C.c_uint64()
+        handed = 0
+        while True:
+            _lib.check(self.L.pf_pattern_rows_stream_next(self.ctx, C.byref(ptr), C.byref(nb)))
+            if not nb.value:
+                break
+            view = _mem(ptr, nb.value)
+            sink(GzipMembers(view, None) if self.device_gzip else view)
+            handed += int(nb.value)
+        text = handed
+        if self.device_gzip:
+            raw = (C.c_uint64 * 3)()
+            _lib.check(self.L.pf_device_gzip_text_bytes(self.ctx, raw))
+            text = int(raw[2])
+        if text != int(total.value):
+            raise _lib.PanfeedHipError(_lib.ERR_STATE, f"pattern-row stream: {text} bytes handed out of {total.value}")
+        return text, handed, int(slices.value)
 
     def render_targets_device(self, hb):
         """kmers.tsv rows of every target sequence of `hb` (the last submit), written on the device

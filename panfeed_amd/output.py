@@ -127,13 +127,15 @@ class SmallMemberGzipWriter:
     line, what pandas printed -- and compresses it into members of at most `chunk_bytes` of text each, the file's first
     line in a member of its own.  Every member starts with the same eight bytes (FLG = 0, MTIME = 0), which is how the
     decoder finds them.  Host text is held back until a member's worth has gathered, and goes out in front of the next
-    members or at close; a file nothing was written to is one empty member."""
+    members or at close; a file nothing was written to is one empty member.  part: the file is a piece of such a file
+    (a rank's share of a sharded run's, sharded.ShardWriter) -- its first line is a line like any other, and a part nothing
+    was written to stays empty."""
 
-    def __init__(self, path, chunk_bytes, compresslevel=6):
+    def __init__(self, path, chunk_bytes, compresslevel=6, part=False):
         self.fh = open(path, "wb")
-        self.chunk, self.level = int(chunk_bytes), compresslevel
+        self.chunk, self.level, self.part = int(chunk_bytes), compresslevel, bool(part)
         self.held = b""                          # host text not yet in a member
-        self.first_line = True                   # the file's first line has not gone out yet
+        self.first_line = not self.part          # the file's first line has not gone out yet
         self.bytes_written = self.text_bytes = self.host_members = 0
         self.closed = False
 
@@ -182,7 +184,7 @@ class SmallMemberGzipWriter:
         if self.closed:
             return
         self._emit(True)
-        if not self.bytes_written:
+        if not self.bytes_written and not self.part:
             import gzip
             self.fh.write(gzip.compress(b"", compresslevel=self.level, mtime=0))
         self.fh.close()
