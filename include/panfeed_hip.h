@@ -265,6 +265,18 @@ int pf_debug_limit_alloc(uint64_t max_bytes, uint64_t stats[2]);
  * context's own for a batch of host arrays and for pf_submit_gather; for a batch with on_device = 1 it is the caller's
  * `packed`, which the context does not own: read it only while the caller keeps that buffer alive. */
 int pf_debug_read_words(pf_ctx* ctx, int which, uint64_t first, uint64_t n, uint64_t* out);
+/* Test hook, read-only: how the host (or, under PF_FLAG_DEVICE_PLAN, cluster_ninst_kernel) routed every cluster of the
+ * last pf_submit after the dedup pass.  n_clusters must be that batch's.  Each array may be NULL; each has n_clusters
+ * elements.  route[c] = class | mode << 3 | first << 5: `class` is the finish class of the cluster's last, successful
+ * attempt (1: fused small, 2: fused large, 3: fused large over several key partitions, 5: fused huge, 0: the general path
+ * of rows_kernel and emit_kernel), `mode` its view (0: every copy, 1: distinct sequences, 2: the wide class) and `first`
+ * the class of its first attempt (equal to `class` unless a scan overflowed its table).  nparts[c] and nslots[c] are the
+ * key partitions and the table slots per partition of the last attempt, attempts[c] how many attempts the cluster took.
+ * For a host-planned cluster these are what the item builder computed; for a device-planned one the class and table bits
+ * the kernel left in its record, read back with the records the host fetches anyway.  Nothing is recorded on the device
+ * for this hook and the package never calls it. */
+int pf_debug_cluster_routes(pf_ctx* ctx, uint32_t n_clusters, uint8_t* route, uint32_t* nparts, uint32_t* nslots,
+                            uint32_t* attempts);
 
 /* Device buffers for callers that keep batches resident (bench.py, tests): plain hipMalloc /
  * hipMemcpy / hipFree on the context's device. */

@@ -136,7 +136,7 @@ FLAG_DEVICE_PLAN = 8
 # every symbol include/panfeed_hip.h declares
 EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_destroy", "pf_reset_patterns",
            "pf_submit", "pf_fetch", "pf_get_timing", "pf_export_patterns", "pf_export_patterns_dev",
-           "pf_merge_patterns", "pf_merge_patterns_padded", "pf_pattern_count", "pf_debug_limit_pattern_slots", "pf_debug_limit_alloc", "pf_debug_read_words", "pf_result_checksum", "pf_dev_alloc", "pf_dev_free",
+           "pf_merge_patterns", "pf_merge_patterns_padded", "pf_pattern_count", "pf_debug_limit_pattern_slots", "pf_debug_limit_alloc", "pf_debug_read_words", "pf_debug_cluster_routes", "pf_result_checksum", "pf_dev_alloc", "pf_dev_free",
            "pf_dev_upload", "pf_dev_download", "pf_synth_expand", "pf_pack_acgt", "pf_b64_digest",
            "pf_render_kmers_to_hashes", "pf_render_hashes_to_patterns", "pf_render_kmers_tsv", "pf_render_kmers_tsv_device", "pf_device_text_chunk", "pf_free_text",
            "pf_kmers_tsv_stream_begin", "pf_kmers_tsv_stream_next",
@@ -215,6 +215,7 @@ def _load_locked():
     L.pf_debug_limit_pattern_slots.argtypes = [C.c_void_p, C.c_uint64]
     L.pf_debug_limit_alloc.argtypes = [C.c_uint64, C.POINTER(C.c_uint64)]
     L.pf_debug_read_words.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.pf_debug_cluster_routes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pf_result_checksum.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.pf_merge_patterns_padded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
                                            C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]

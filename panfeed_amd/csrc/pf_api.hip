@@ -368,6 +368,8 @@ struct pf_ctx {
     uint32_t n_clusters = 0;
     uint64_t n_strand_words = 0;
     std::vector<uint32_t> cluster_arena;   // arena index per cluster
+    struct Route { uint32_t nparts, nslots, attempts; uint8_t cls, first, mode; };
+    std::vector<Route> routes;             // per cluster, for pf_debug_cluster_routes (host bookkeeping only)
     pf_result counters{};
     pf_timing timing{};
     std::vector<EvPair> events;
@@ -979,6 +981,12 @@ struct SubmitRun {
         t_host0 = t;
     }
     uint32_t part_begin(uint32_t h) const { return h ? part_end[h - 1] : 0; }
+    // an attempt's route, for pf_debug_cluster_routes
+    void note_route(uint32_t ci, uint32_t cls, uint32_t np, uint32_t ns) {
+        pf_ctx::Route& rt = c->routes[ci];
+        if (!rt.attempts++) rt.first = (uint8_t)cls;
+        rt.cls = (uint8_t)cls; rt.mode = (uint8_t)(rec[ci].mode & 3u); rt.nparts = np; rt.nslots = ns;
+    }
 
     // ---- batch arrays on the device
     int upload_batch() {
@@ -1468,7 +1476,11 @@ struct SubmitRun {
             if (rec[i].ninst * mult >= 0xFFFFFFF0ull) return fail(PF_ERR_ARG, "cluster %u has too many k-mer instances", i);
             total_inst += rec[i].ninst * mult;
             c->timing.n_dedup_clusters += rec[i].mode ? 1u : 0u;
-            if (rec[i].pad & pf::PLAN_PLANNED) continue;          // laid out by plan_kernel: one key partition
+            if (rec[i].pad & pf::PLAN_PLANNED) {                  // laid out by plan_kernel: one key partition
+                const uint32_t nsi = (rec[i].pad >> pf::PLAN_NS_SHIFT) & 15u;
+                note_route(i, (rec[i].pad >> pf::PLAN_CLS_SHIFT) & 15u, 1, nsi == 1 ? 4096u : nsi == 2 ? 6144u : NS);
+                continue;
+            }
             nparts[i] = first_nparts(rec[i]);
         }
         // the host-planned clusters' unit view.  A cluster's pieces number at most the units of its plain view: that is
@@ -1556,6 +1568,7 @@ struct SubmitRun {
             const uint64_t inst = rec[ci].vinst * mult;
             if (np == 1 && NS > 4096 + pf::INSERT_SLACK && inst <= pf::insert_limit(4096)) ns = 4096;
             else if (np == 1 && NS > 6144 + pf::INSERT_SLACK && inst <= pf::insert_limit(6144)) ns = 6144;
+            note_route(ci, fused, np, ns);
             for (uint32_t q = 0; q < np; q++)
                 hpass.push(ci, q, np, ns, cur.nitems + q, sib0, nit, 0, 0, fused == 3 && q > 0 ? 4 : fused, binned ? 1u : 0u);
             if (binned) {
@@ -1927,6 +1940,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
     c->pid0 = c->n_patterns;
     if (!rerun) c->n_submits++;
     c->cluster_arena.assign(r.C, 0);
+    c->routes.assign(r.C, pf_ctx::Route{});
     r.nparts.assign(r.C, 1);
     c->counters = pf_result{};
     // host-planned passes: the parts' (what plan_kernel left of them, queued back to back), then the re-runs
@@ -2036,6 +2050,21 @@ int pf_debug_read_words(pf_ctx* c, int which, uint64_t first, uint64_t n, uint64
     if (first > bound || n > bound - first) return fail(PF_ERR_ARG, "pf_debug_read_words: words [%llu, +%llu) outside the %llu held",
                                                         (unsigned long long)first, (unsigned long long)n, (unsigned long long)bound);
     if (n) HIPCHK(hipMemcpy(out, src + first, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return PF_OK;
+}
+
+int pf_debug_cluster_routes(pf_ctx* c, uint32_t n_clusters, uint8_t* route, uint32_t* nparts, uint32_t* nslots, uint32_t* attempts) {
+    if (!c) return fail(PF_ERR_ARG, "pf_debug_cluster_routes: null context");
+    if (!c->have_batch) return fail(PF_ERR_STATE, "pf_debug_cluster_routes without a successful pf_submit");
+    if (n_clusters != c->n_clusters || c->routes.size() != n_clusters)
+        return fail(PF_ERR_ARG, "pf_debug_cluster_routes: %u clusters asked for, the last batch had %u", n_clusters, c->n_clusters);
+    for (uint32_t i = 0; i < n_clusters; i++) {
+        const pf_ctx::Route& rt = c->routes[i];
+        if (route) route[i] = (uint8_t)((rt.cls & 7u) | ((rt.mode & 3u) << 3) | ((rt.first & 7u) << 5));
+        if (nparts) nparts[i] = rt.nparts;
+        if (nslots) nslots[i] = rt.nslots;
+        if (attempts) attempts[i] = rt.attempts;
+    }
     return PF_OK;
 }
 
