@@ -384,6 +384,23 @@ private:
     }
 };
 
+// What the feed's owners' entry points pf_*_members_begin, pf_*_members_header and pf_*_gunzip_stats do, each under its own
+// name `fn`.  H: an owner, a handle with a `feed`
+template <class H> int feed_members_begin(H* h, const char* fn, int header) {
+    return h ? h->feed.members_begin(header) : fail(PF_ERR_ARG, "%s: null argument", fn);
+}
+template <class H> int feed_members_header(H* h, const char* fn, const char** line, uint64_t* nbytes) {
+    return h ? h->feed.header_line(line, nbytes) : fail(PF_ERR_ARG, "%s: null argument", fn);
+}
+template <class H> int feed_gunzip_stats(H* h, const char* fn, uint64_t* members, uint64_t* text_bytes, float* inflate_ms, uint64_t* device_bytes) {
+    if (!h) return fail(PF_ERR_ARG, "%s: null argument", fn);
+    if (members) *members = h->feed.gz_members;
+    if (text_bytes) *text_bytes = h->feed.gz_text_bytes;
+    if (inflate_ms) *inflate_ms = h->feed.gz_ms;
+    if (device_bytes) *device_bytes = h->feed.dec.device_bytes();
+    return PF_OK;
+}
+
 }  // namespace
 
 struct pf_rowfilter {
@@ -560,14 +577,10 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
     return PF_OK;
 }
 
-int pf_rowfilter_members_begin(pf_rowfilter* f, int header) {
-    if (!f) return fail(PF_ERR_ARG, "pf_rowfilter_members_begin: null argument");
-    return f->feed.members_begin(header);
-}
+int pf_rowfilter_members_begin(pf_rowfilter* f, int header) { return feed_members_begin(f, "pf_rowfilter_members_begin", header); }
 
 int pf_rowfilter_members_header(pf_rowfilter* f, const char** line, uint64_t* nbytes) {
-    if (!f) return fail(PF_ERR_ARG, "pf_rowfilter_members_header: null argument");
-    return f->feed.header_line(line, nbytes);
+    return feed_members_header(f, "pf_rowfilter_members_header", line, nbytes);
 }
 
 int pf_rowfilter_scan_members(pf_rowfilter* f, const char* members, uint64_t nbytes, int last, const char** lines,
@@ -588,12 +601,7 @@ int pf_rowfilter_scan_members(pf_rowfilter* f, const char* members, uint64_t nby
 }
 
 int pf_rowfilter_gunzip_stats(pf_rowfilter* f, uint64_t* members, uint64_t* text_bytes, float* inflate_ms, uint64_t* device_bytes) {
-    if (!f) return fail(PF_ERR_ARG, "pf_rowfilter_gunzip_stats: null argument");
-    if (members) *members = f->feed.gz_members;
-    if (text_bytes) *text_bytes = f->feed.gz_text_bytes;
-    if (inflate_ms) *inflate_ms = f->feed.gz_ms;
-    if (device_bytes) *device_bytes = f->feed.dec.device_bytes();
-    return PF_OK;
+    return feed_gunzip_stats(f, "pf_rowfilter_gunzip_stats", members, text_bytes, inflate_ms, device_bytes);
 }
 
 int pf_rowfilter_stats(pf_rowfilter* f, uint64_t* bytes_scanned, float* device_ms) {
@@ -1122,14 +1130,10 @@ int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t
     return pg_scan_device(g, *consumed, 0);
 }
 
-int pf_plotgrid_members_begin(pf_plotgrid* g, int header) {
-    if (!g) return fail(PF_ERR_ARG, "pf_plotgrid_members_begin: null argument");
-    return g->feed.members_begin(header);
-}
+int pf_plotgrid_members_begin(pf_plotgrid* g, int header) { return feed_members_begin(g, "pf_plotgrid_members_begin", header); }
 
 int pf_plotgrid_members_header(pf_plotgrid* g, const char** line, uint64_t* nbytes) {
-    if (!g) return fail(PF_ERR_ARG, "pf_plotgrid_members_header: null argument");
-    return g->feed.header_line(line, nbytes);
+    return feed_members_header(g, "pf_plotgrid_members_header", line, nbytes);
 }
 
 int pf_plotgrid_scan_members(pf_plotgrid* g, const char* members, uint64_t nbytes, int last, uint64_t* consumed, int* taken) {
@@ -1141,12 +1145,7 @@ int pf_plotgrid_scan_members(pf_plotgrid* g, const char* members, uint64_t nbyte
 }
 
 int pf_plotgrid_gunzip_stats(pf_plotgrid* g, uint64_t* members, uint64_t* text_bytes, float* inflate_ms, uint64_t* device_bytes) {
-    if (!g) return fail(PF_ERR_ARG, "pf_plotgrid_gunzip_stats: null argument");
-    if (members) *members = g->feed.gz_members;
-    if (text_bytes) *text_bytes = g->feed.gz_text_bytes;
-    if (inflate_ms) *inflate_ms = g->feed.gz_ms;
-    if (device_bytes) *device_bytes = g->feed.dec.device_bytes();
-    return PF_OK;
+    return feed_gunzip_stats(g, "pf_plotgrid_gunzip_stats", members, text_bytes, inflate_ms, device_bytes);
 }
 
 int pf_plotgrid_finish(pf_plotgrid* g, uint32_t* n_clusters, uint64_t* n_pvalues, uint64_t* n_records) {
@@ -1289,6 +1288,211 @@ int pf_plotgrid_stats(pf_plotgrid* g, uint64_t* bytes_scanned, uint64_t* lines, 
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The row pack: "select some lines of a block and write them, packed and in file order, into one device buffer", for the
+// k-mer join and the associations filter (both below).  Every thread owns 256 bytes of the text (16 vectors of 16) and the
+// lines whose preceding newline lies in them; a workgroup's 64 KiB are a tile.  A client brings two kernels of its own:
+//   plan     counts each thread's selected rows and their output bytes and ends in row_plan: the counts to thr, the
+//            workgroup's sums to tile.  row_tiles_kernel then makes the tiles' sums exclusive prefixes
+//   place    finds the same rows again through row_place, which gives every one a record (RowRec: source, destination, its
+//            pieces) at its place in file order -- or raises the client's complaint bit: the two passes disagree
+// and row_write_kernel copies by the records: a wave per group of 16 consecutive rows, lanes striding over a row's bytes.
+// RowPack owns the buffers and runs the sequence; RowHandout brings the text to the host.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t ROW_TILE_VECS = 4096;         // vectors of a workgroup: 256 threads x 16
+constexpr uint32_t ROW_GROUP = 16;               // rows of a wave's step in the writer
+constexpr uint64_t ROW_PIECE = 32ull << 20;      // bytes of output handed out at a time
+
+// a row of the output: text[src ..) as it stands, len0 bytes (raw), or  field 0 \t field 10 \t arena text \t fields 1..9 \n
+struct RowRec { uint64_t src, dst; uint32_t len0, f1, mid, f10, len10, t_off, t_len, raw; };
+
+__device__ __forceinline__ uint32_t row_out_len(const RowRec& r) { return r.raw ? r.len0 : r.len0 + r.len10 + r.t_len + r.mid + 4; }
+
+// what the pack's own code reads of a client's parameters: the client's parameter struct begins with it
+struct RowSpan {
+    const unsigned char* text;   // the block, complete lines, zero-padded to the next multiple of 16 bytes
+    uint64_t n, begin;           // lines that start in [begin, n)
+    uint2* thr;                  // per thread, rows and output bytes
+    unsigned long long* tile;    // per tile, rows and bytes (then their exclusive prefixes), and the totals behind
+    RowRec* rec;
+    unsigned char* out;
+    const unsigned char* arena;  // the bytes a record's t_off speaks of (none where all rows are raw)
+};
+
+inline uint32_t row_tiles(uint64_t n) { return (uint32_t)(((n + 15) / 16 + ROW_TILE_VECS - 1) / ROW_TILE_VECS); }
+
+// line_start(s) for every line of [begin, n) whose preceding newline -- or, for the line at 0, the block's start -- is in
+// this thread's 16 vectors, in file order
+template <class F> __device__ __forceinline__ void row_each_line(const RowSpan& p, F&& line_start) {
+    const uint64_t nvec = (p.n + 15) / 16;
+    const uint64_t v0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+    if (v0 == 0 && p.begin == 0 && p.n) line_start(0);
+    for (uint64_t v = v0; v < v0 + 16 && v < nvec; v++)
+        rf_each_newline(p.text, v, [&](uint64_t at) { if (at + 1 < p.n && at + 1 >= p.begin) line_start(at + 1); });
+}
+
+// an exclusive prefix sum over the workgroup's 256 threads of (a, b); the totals to all
+__device__ void row_block_exscan(unsigned long long& a, unsigned long long& b, unsigned long long* tot_a, unsigned long long* tot_b) {
+    __shared__ unsigned long long sa[256], sb[256];
+    const uint32_t t = threadIdx.x;
+    const unsigned long long a0 = a, b0 = b;
+    sa[t] = a; sb[t] = b;
+    __syncthreads();
+    for (uint32_t d = 1; d < 256; d <<= 1) {
+        const unsigned long long xa = t >= d ? sa[t - d] : 0, xb = t >= d ? sb[t - d] : 0;
+        __syncthreads();
+        sa[t] += xa; sb[t] += xb;
+        __syncthreads();
+    }
+    a = sa[t] - a0; b = sb[t] - b0;
+    *tot_a = sa[255]; *tot_b = sb[255];
+    __syncthreads();
+}
+
+// the end of a client's plan kernel: this thread's selected rows and their output bytes to thr, the workgroup's to tile
+// (whatever the workgroup wrote to LDS before is visible to all behind it)
+__device__ __forceinline__ void row_plan(const RowSpan& p, unsigned long long rows, unsigned long long bytes) {
+    p.thr[(uint64_t)blockIdx.x * 256 + threadIdx.x] = make_uint2((uint32_t)rows, (uint32_t)bytes);
+    unsigned long long ta, tb;
+    row_block_exscan(rows, bytes, &ta, &tb);
+    if (threadIdx.x == 0) { p.tile[2 * (uint64_t)blockIdx.x] = ta; p.tile[2 * (uint64_t)blockIdx.x + 1] = tb; }
+}
+
+// tile[2 i], tile[2 i + 1] -> their exclusive prefixes; the totals to tile[2 n], tile[2 n + 1].  One workgroup
+__global__ __launch_bounds__(256) void row_tiles_kernel(unsigned long long* tile, uint64_t n) {
+    const uint64_t per = (n + 255) / 256, lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
+    unsigned long long a = 0, b = 0;
+    for (uint64_t i = lo; i < hi; i++) { a += tile[2 * i]; b += tile[2 * i + 1]; }
+    unsigned long long ta, tb;
+    row_block_exscan(a, b, &ta, &tb);
+    for (uint64_t i = lo; i < hi; i++) {
+        const unsigned long long xa = tile[2 * i], xb = tile[2 * i + 1];
+        tile[2 * i] = a; tile[2 * i + 1] = b;
+        a += xa; b += xb;
+    }
+    if (threadIdx.x == 0) { tile[2 * n] = ta; tile[2 * n + 1] = tb; }
+}
+
+// the body of a client's place kernel: the thread's first row and byte from thr and tile, then row(s, r) -> whether the line
+// at s is a selected row, r all of its record but dst.  A row the plan left no room for raises `bit` of *err instead
+template <class F> __device__ __forceinline__ void row_place(const RowSpan& p, uint64_t n_rows, uint64_t n_bytes, unsigned int* err,
+                                                             unsigned int bit, F&& row) {
+    const uint2 mine = p.thr[(uint64_t)blockIdx.x * 256 + threadIdx.x];
+    unsigned long long k = mine.x, at = mine.y, ta, tb;
+    row_block_exscan(k, at, &ta, &tb);
+    k += p.tile[2 * (uint64_t)blockIdx.x]; at += p.tile[2 * (uint64_t)blockIdx.x + 1];
+    row_each_line(p, [&](uint64_t s) {
+        RowRec r;
+        if (!row(s, r)) return;
+        r.dst = at;
+        const uint32_t len = row_out_len(r);
+        if (k < n_rows && at + len <= n_bytes) p.rec[k] = r; else atomicOr(err, bit);
+        k++; at += len;
+    });
+}
+
+__global__ __launch_bounds__(256) void row_write_kernel(RowSpan p, uint64_t n_rows) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t g = wave * ROW_GROUP; g < n_rows; g += n_waves * ROW_GROUP) {
+        for (uint64_t k = g; k < g + ROW_GROUP && k < n_rows; k++) {
+            const RowRec r = p.rec[k];
+            const unsigned char* const src = p.text + r.src;
+            unsigned char* const dst = p.out + r.dst;
+            if (r.raw) { for (uint32_t i = lane; i < r.len0; i += 64) dst[i] = src[i]; continue; }
+            // cluster \t k-mer \t text \t fields 1..9 \n
+            const uint32_t e0 = r.len0, e1 = e0 + 1 + r.len10, e2 = e1 + 1 + r.t_len, e3 = e2 + 1 + r.mid;
+            for (uint32_t i = lane; i <= e3; i += 64) {
+                unsigned char c;
+                if (i < e0) c = src[i];
+                else if (i == e0 || i == e1 || i == e2) c = '\t';
+                else if (i < e1) c = src[r.f10 + (i - e0 - 1)];
+                else if (i < e2) c = p.arena[r.t_off + (i - e1 - 1)];
+                else if (i < e3) c = src[r.f1 + (i - e2 - 1)];
+                else c = '\n';
+                dst[i] = c;
+            }
+        }
+    }
+}
+
+// The text a pass wrote on the device, d_out[0 .. bytes), handed out piece by piece through two pinned buffers
+struct RowHandout {
+    DevBuf d_out;
+    PinBuf pin[2];
+    uint64_t bytes = 0, pos = 0, flying = 0;      // the text's bytes, those handed out or on their way, the piece on its way
+    int cur = 0;
+    void reset() { bytes = pos = flying = 0; }
+    // *nbytes = 0: no more; a piece is valid until the call after the next
+    int next(hipStream_t st, const char** piece, uint64_t* nbytes) {
+        *piece = nullptr; *nbytes = 0;
+        auto start = [&]() -> int {                    // the next piece on its way into pin[cur]
+            flying = std::min<uint64_t>(ROW_PIECE, bytes - pos);
+            if (!flying) return PF_OK;
+            PFCHK(pin[cur].ensure((size_t)std::min<uint64_t>(ROW_PIECE, bytes), true));
+            HIPCHK(hipMemcpyAsync(pin[cur].p, d_out.as<char>() + pos, (size_t)flying, hipMemcpyDeviceToHost, st));
+            pos += flying;
+            return PF_OK;
+        };
+        if (!flying) PFCHK(start());
+        if (!flying) return PF_OK;
+        HIPCHK(hipStreamSynchronize(st));
+        *piece = pin[cur].as<char>(); *nbytes = flying;
+        cur ^= 1;
+        return start();                                // (into the other buffer, while the caller writes this one)
+    }
+};
+
+// The pack's buffers and its sequence on the client's stream.  run(): p holds the client's text, n and begin; plan(tiles)
+// and place(tiles) launch the client's two kernels with p, which has its thr and tile by the first and its rec and out by
+// the second.  The plan, the tile sums and the totals are waited for, their time added to *plan_ms; with rows, the place and
+// the writer are put on the stream inside the timed bracket and NOT waited for: the client reads its complaint word behind
+// them, synchronises once for both and then has the bracket's time from ts.add_elapsed.  out.bytes stays 0: the client
+// sets it once the call has succeeded
+struct RowPack {
+    DevBuf d_thr, d_tile, d_rec;
+    RowHandout out;
+    template <class Plan, class Place>
+    int run(TimedStream& ts, RowSpan& p, float* plan_ms, uint64_t* n_rows, uint64_t* n_bytes, Plan&& plan, Place&& place) {
+        const uint32_t tiles = row_tiles(p.n);
+        PFCHK(d_thr.ensure((size_t)tiles * 256 * sizeof(uint2)));
+        PFCHK(d_tile.ensure(((size_t)tiles + 1) * 16));
+        p.thr = d_thr.as<uint2>(); p.tile = d_tile.as<unsigned long long>();
+        PFCHK(ts.timed([&]() -> int {
+            plan(tiles);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(row_tiles_kernel, dim3(1), dim3(256), 0, ts.stream, p.tile, (uint64_t)tiles);
+            HIPCHK(hipGetLastError()); return PF_OK;
+        }));
+        uint64_t totals[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(totals, p.tile + 2 * (uint64_t)tiles, 16, hipMemcpyDeviceToHost, ts.stream));
+        HIPCHK(hipStreamSynchronize(ts.stream));
+        ts.add_elapsed(plan_ms);
+        *n_rows = totals[0]; *n_bytes = totals[1];
+        if (!*n_rows) return PF_OK;
+        PFCHK(d_rec.ensure((size_t)*n_rows * sizeof(RowRec)));
+        PFCHK(out.d_out.ensure((size_t)*n_bytes));
+        p.rec = d_rec.as<RowRec>(); p.out = out.d_out.as<unsigned char>();
+        return ts.timed([&]() -> int {
+            place(tiles);
+            HIPCHK(hipGetLastError());
+            const uint64_t groups = (*n_rows + ROW_GROUP - 1) / ROW_GROUP;
+            hipLaunchKernelGGL(row_write_kernel, dim3((uint32_t)std::min<uint64_t>((groups + 3) / 4, 256 * 32)), dim3(256), 0, ts.stream, p, *n_rows);
+            HIPCHK(hipGetLastError()); return PF_OK;
+        });
+    }
+};
+
+template <class T> int dev_upload(DevBuf& d, const std::vector<T>& v) {
+    PFCHK(d.ensure(std::max<size_t>(v.size() * sizeof(T), 16), true));
+    if (!v.empty()) HIPCHK(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return PF_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------
 // panfeed-get-kmers' join: /root/reference/panfeed/get_kmers.py:131-141 on the device.
 //
 // The reference parses every kmers.tsv row of a bunch of clusters and joins the small table of passing (cluster, k-mer)
@@ -1298,46 +1502,34 @@ int pf_plotgrid_stats(pf_plotgrid* g, uint64_t* bytes_scanned, uint64_t* lines, 
 // the keys -- both open addressing on rf_hash values, both verified by bytes HERE, since a written row never reaches the
 // host before it is output -- and write  cluster \t k-mer \t <text> \t <fields 2..10 as they stand> \n.
 //
-// Two kinds of pass over blocks of complete lines.  Every thread owns 256 bytes (16 vectors of 16) and the lines whose
-// preceding newline lies in them.
+// Two kinds of pass over blocks of complete lines, both by the row pack's division of the text (row_each_line).
 //   survey   all bunches at once: per bunch, rows, rows without a key, output bytes under either rendering, and the OR
 //            of the rows' plainness flags (KJ_*): a flagged row is one pandas' read_csv -> to_csv might not print as it
 //            stands, and its bunch goes through pandas
-//   join     one bunch: kj_plan_kernel counts each thread's rows and output bytes, kj_tiles_kernel makes the tiles' sums
-//            exclusive prefixes, kj_place_kernel gives every row a record (source, destination, the four pieces) in file
-//            order, kj_write_kernel copies: a wave per group of 16 consecutive rows, lanes striding over a row's bytes.
-//            mode 2 keeps the raw rows that have a key instead (--only-passing: pandas joins those few).
+//   join     one bunch, a client of the row pack: kj_plan_kernel counts each thread's rows of the bunch and their output
+//            bytes (kj_row, row_plan), kj_place_kernel makes their records (kj_row, row_place); row_tiles_kernel and
+//            row_write_kernel are the pack's.  mode 2 keeps the raw rows that have a key instead (--only-passing: pandas
+//            joins those few).
 // A row of more than KJ_MAX_LINE bytes, or with a field of RF_MAX_FIELD bytes or more, is a flag (KJ_LONG), never a fault.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
 
 constexpr uint32_t KJ_MAX_LINE = 1u << 16;
-constexpr uint32_t KJ_TILE_VECS = 4096;          // vectors of a workgroup: 256 threads x 16
-constexpr uint32_t KJ_GROUP = 16;                // rows of a wave's step in the writer
-constexpr uint64_t KJ_PIECE = 32ull << 20;       // bytes of output handed out at a time
 enum : uint32_t { KJ_TABS = 1, KJ_BYTES = 2, KJ_INT = 4, KJ_EMPTY = 8, KJ_NA = 16, KJ_NUMERIC = 32, KJ_WORD = 64, KJ_LONG = 128 };
 enum { KJ_ROWS = 0, KJ_UNMATCHED = 1, KJ_BYTES0 = 2, KJ_BYTES1 = 3, KJ_FLAGS = 4, KJ_COUNTERS = 5 };
 
 struct KjCluster { uint32_t off, len, bunch; };
 struct KjKey { uint32_t cl_off, cl_len, km_off, km_len, t_off[2], t_len[2]; };
-struct KjRec { uint64_t src, dst; uint32_t len0, f1, mid, f10, len10, t_off, t_len, raw; };
 
-struct KjParams {
-    const unsigned char* text;   // the block, complete lines, zero-padded to the next multiple of 16 bytes
-    uint64_t n, begin;           // lines that start in [begin, n)
+struct KjParams : RowSpan {      // (arena: the clusters', keys' and texts' bytes)
     const unsigned long long* chash; const uint32_t* cslot; uint64_t ccap; const KjCluster* clusters;
     const unsigned long long* khash; const uint32_t* kslot; uint64_t kcap; const KjKey* keys;
-    const unsigned char* arena;  // the clusters', keys' and texts' bytes
     uint32_t empty_off, empty_len;
     int32_t bunch;               // join: the bunch whose rows are written
     int mode;                    // join: rendering 0 / 1, or 2: the raw rows that have a key
     unsigned long long* counters;        // survey: KJ_COUNTERS per bunch
     unsigned long long* rejects;         // look-ups whose hash was equal and whose bytes were not
     unsigned long long* unmatched;       // join: rows written with the empty text
-    uint2* thr;                          // join: per thread, rows and output bytes
-    unsigned long long* tile;            // join: per tile, rows and bytes (then their exclusive prefixes), and the totals behind
-    KjRec* rec;
-    unsigned char* out;
     unsigned int* err;
 };
 
@@ -1454,16 +1646,6 @@ template <bool FLAGS> __device__ void kj_walk(const unsigned char* t, uint64_t s
     w.len = i; w.flags = flags;
 }
 
-// line_start(s) for every line of [begin, n) whose preceding newline -- or, for the line at 0, the block's start -- is in
-// this thread's 16 vectors, in file order.  P: the join's parameters or the associations filter's -- text, n and begin
-template <class P, class F> __device__ __forceinline__ void kj_each_line(const P& p, F&& line_start) {
-    const uint64_t nvec = (p.n + 15) / 16;
-    const uint64_t v0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
-    if (v0 == 0 && p.begin == 0 && p.n) line_start(0);
-    for (uint64_t v = v0; v < v0 + 16 && v < nvec; v++)
-        rf_each_newline(p.text, v, [&](uint64_t at) { if (at + 1 < p.n && at + 1 >= p.begin) line_start(at + 1); });
-}
-
 __global__ __launch_bounds__(256) void kj_survey_kernel(KjParams p) {
     // the workgroup's 64 KiB of text are nearly always rows of one bunch: that bunch's counters are kept in LDS
     __shared__ unsigned long long s_cnt[KJ_COUNTERS];
@@ -1471,7 +1653,7 @@ __global__ __launch_bounds__(256) void kj_survey_kernel(KjParams p) {
     if (threadIdx.x < KJ_COUNTERS) s_cnt[threadIdx.x] = 0;
     if (threadIdx.x == 0) s_bunch = -1;
     __syncthreads();
-    kj_each_line(p, [&](uint64_t s) {
+    row_each_line(p, [&](uint64_t s) {
         uint32_t len0; uint64_t h;
         const int32_t bunch = kj_cluster(p, s, &len0, &h);
         if (bunch < 0) return;
@@ -1501,8 +1683,8 @@ __global__ __launch_bounds__(256) void kj_survey_kernel(KjParams p) {
     }
 }
 
-// the row of this join's output the line at s makes, if it makes one (its dst is the caller's); *keyed: it has a key
-__device__ bool kj_row(const KjParams& p, uint64_t s, KjRec& r, bool* keyed) {
+// the row of this join's output the line at s makes, if it makes one (its dst is the pack's); *keyed: it has a key
+__device__ bool kj_row(const KjParams& p, uint64_t s, RowRec& r, bool* keyed) {
     uint32_t len0; uint64_t h;
     if (kj_cluster(p, s, &len0, &h) != p.bunch) return false;
     KjWalk w;
@@ -1522,121 +1704,19 @@ __device__ bool kj_row(const KjParams& p, uint64_t s, KjRec& r, bool* keyed) {
     return true;
 }
 
-__device__ __forceinline__ uint32_t kj_out_len(const KjRec& r) { return r.raw ? r.len0 : r.len0 + r.len10 + r.t_len + r.mid + 4; }
-
-// an exclusive prefix sum over the workgroup's 256 threads of (a, b); the totals to all
-__device__ void kj_block_exscan(unsigned long long& a, unsigned long long& b, unsigned long long* tot_a, unsigned long long* tot_b) {
-    __shared__ unsigned long long sa[256], sb[256];
-    const uint32_t t = threadIdx.x;
-    const unsigned long long a0 = a, b0 = b;
-    sa[t] = a; sb[t] = b;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {
-        const unsigned long long xa = t >= d ? sa[t - d] : 0, xb = t >= d ? sb[t - d] : 0;
-        __syncthreads();
-        sa[t] += xa; sb[t] += xb;
-        __syncthreads();
-    }
-    a = sa[t] - a0; b = sb[t] - b0;
-    *tot_a = sa[255]; *tot_b = sb[255];
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(256) void kj_plan_kernel(KjParams p) {
     unsigned long long rows = 0, bytes = 0, unmatched = 0;
-    kj_each_line(p, [&](uint64_t s) {
-        KjRec r; bool keyed;
-        if (kj_row(p, s, r, &keyed)) { rows++; bytes += kj_out_len(r); unmatched += !keyed; }
+    row_each_line(p, [&](uint64_t s) {
+        RowRec r; bool keyed;
+        if (kj_row(p, s, r, &keyed)) { rows++; bytes += row_out_len(r); unmatched += !keyed; }
     });
     if (unmatched) atomicAdd(p.unmatched, unmatched);
-    p.thr[(uint64_t)blockIdx.x * 256 + threadIdx.x] = make_uint2((uint32_t)rows, (uint32_t)bytes);
-    unsigned long long ta, tb;
-    kj_block_exscan(rows, bytes, &ta, &tb);
-    if (threadIdx.x == 0) { p.tile[2 * (uint64_t)blockIdx.x] = ta; p.tile[2 * (uint64_t)blockIdx.x + 1] = tb; }
-}
-
-// tile[2 i], tile[2 i + 1] -> their exclusive prefixes; the totals to tile[2 n], tile[2 n + 1].  One workgroup
-__global__ __launch_bounds__(256) void kj_tiles_kernel(unsigned long long* tile, uint64_t n) {
-    const uint64_t per = (n + 255) / 256, lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-    unsigned long long a = 0, b = 0;
-    for (uint64_t i = lo; i < hi; i++) { a += tile[2 * i]; b += tile[2 * i + 1]; }
-    unsigned long long ta, tb;
-    kj_block_exscan(a, b, &ta, &tb);
-    for (uint64_t i = lo; i < hi; i++) {
-        const unsigned long long xa = tile[2 * i], xb = tile[2 * i + 1];
-        tile[2 * i] = a; tile[2 * i + 1] = b;
-        a += xa; b += xb;
-    }
-    if (threadIdx.x == 0) { tile[2 * n] = ta; tile[2 * n + 1] = tb; }
+    row_plan(p, rows, bytes);
 }
 
 __global__ __launch_bounds__(256) void kj_place_kernel(KjParams p, uint64_t n_rows, uint64_t n_bytes) {
-    const uint2 mine = p.thr[(uint64_t)blockIdx.x * 256 + threadIdx.x];
-    unsigned long long row = mine.x, at = mine.y, ta, tb;
-    kj_block_exscan(row, at, &ta, &tb);
-    row += p.tile[2 * (uint64_t)blockIdx.x]; at += p.tile[2 * (uint64_t)blockIdx.x + 1];
-    kj_each_line(p, [&](uint64_t s) {
-        KjRec r; bool keyed;
-        if (!kj_row(p, s, r, &keyed)) return;
-        r.dst = at;
-        const uint32_t len = kj_out_len(r);
-        if (row < n_rows && at + len <= n_bytes) p.rec[row] = r; else atomicOr(p.err, 0x80000000u);
-        row++; at += len;
-    });
+    row_place(p, n_rows, n_bytes, p.err, 0x80000000u, [&](uint64_t s, RowRec& r) { bool keyed; return kj_row(p, s, r, &keyed); });
 }
-
-__global__ __launch_bounds__(256) void kj_write_kernel(KjParams p, uint64_t n_rows) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    for (uint64_t g = wave * KJ_GROUP; g < n_rows; g += n_waves * KJ_GROUP) {
-        for (uint64_t k = g; k < g + KJ_GROUP && k < n_rows; k++) {
-            const KjRec r = p.rec[k];
-            const unsigned char* const src = p.text + r.src;
-            unsigned char* const dst = p.out + r.dst;
-            if (r.raw) { for (uint32_t i = lane; i < r.len0; i += 64) dst[i] = src[i]; continue; }
-            // cluster \t k-mer \t text \t fields 1..9 \n
-            const uint32_t e0 = r.len0, e1 = e0 + 1 + r.len10, e2 = e1 + 1 + r.t_len, e3 = e2 + 1 + r.mid;
-            for (uint32_t i = lane; i <= e3; i += 64) {
-                unsigned char c;
-                if (i < e0) c = src[i];
-                else if (i == e0 || i == e1 || i == e2) c = '\t';
-                else if (i < e1) c = src[r.f10 + (i - e0 - 1)];
-                else if (i < e2) c = p.arena[r.t_off + (i - e1 - 1)];
-                else if (i < e3) c = src[r.f1 + (i - e2 - 1)];
-                else c = '\n';
-                dst[i] = c;
-            }
-        }
-    }
-}
-
-// The text a pass wrote on the device, d_out[0 .. bytes), handed out piece by piece through two pinned buffers: the k-mer
-// join's rows and the associations filter's kept lines
-struct KjHandout {
-    DevBuf d_out;
-    PinBuf pin[2];
-    uint64_t bytes = 0, pos = 0, flying = 0;      // the text's bytes, those handed out or on their way, the piece on its way
-    int cur = 0;
-    void reset() { bytes = pos = flying = 0; }
-    // *nbytes = 0: no more; a piece is valid until the call after the next
-    int next(hipStream_t st, const char** piece, uint64_t* nbytes) {
-        *piece = nullptr; *nbytes = 0;
-        auto start = [&]() -> int {                    // the next piece on its way into pin[cur]
-            flying = std::min<uint64_t>(KJ_PIECE, bytes - pos);
-            if (!flying) return PF_OK;
-            PFCHK(pin[cur].ensure((size_t)std::min<uint64_t>(KJ_PIECE, bytes), true));
-            HIPCHK(hipMemcpyAsync(pin[cur].p, d_out.as<char>() + pos, (size_t)flying, hipMemcpyDeviceToHost, st));
-            pos += flying;
-            return PF_OK;
-        };
-        if (!flying) PFCHK(start());
-        if (!flying) return PF_OK;
-        HIPCHK(hipStreamSynchronize(st));
-        *piece = pin[cur].as<char>(); *nbytes = flying;
-        cur ^= 1;
-        return start();                                // (into the other buffer, while the caller writes this one)
-    }
-};
 
 }  // namespace
 
@@ -1645,9 +1725,8 @@ struct pf_kmerjoin {
     uint64_t ccap = 0, kcap = 0;
     uint32_t empty_off = 0, empty_len = 0;
     DevBuf d_chash, d_cslot, d_clusters, d_khash, d_kslot, d_keys, d_arena, d_counters, d_misc;     // d_misc: rejects, err, unmatched
-    DevBuf d_thr, d_tile, d_rec;
     std::vector<uint64_t> counters;
-    KjHandout out;                               // the join's text
+    RowPack pack;                                // pack.out: the join's text
     uint64_t bytes_scanned = 0, rows_written = 0, raw_rows = 0;
     float survey_ms = 0, write_ms = 0;
     // pf_kmerjoin_set_gzip: the text of a mode 0 / 1 call leaves as gzip members.  The encoder is made on first use; a call's
@@ -1656,7 +1735,7 @@ struct pf_kmerjoin {
     bool gz_on = false, gz_now = false;          // the switch; whether the last join call's text is one to encode
     uint32_t gz_flags = 0;
     PfGzEncoder enc;
-    KjHandout gz;                                // the members of the slice out.d_out[gz_at - its bytes .. gz_at)
+    RowHandout gz;                               // the members of the slice pack.out.d_out[gz_at - its bytes .. gz_at)
     uint64_t gz_at = 0;                          // text bytes of the call encoded so far
     uint64_t gz_text_bytes = 0, gz_member_bytes = 0;
     float gz_ms = 0;
@@ -1666,7 +1745,7 @@ struct pf_kmerjoin {
 namespace {
 
 // nothing of an earlier join call is left to hand out
-void kj_reset_out(pf_kmerjoin* j) { j->out.reset(); j->gz.reset(); j->gz_at = 0; j->gz_now = false; }
+void kj_reset_out(pf_kmerjoin* j) { j->pack.out.reset(); j->gz.reset(); j->gz_at = 0; j->gz_now = false; }
 
 KjParams kj_params(pf_kmerjoin* j, uint64_t n, uint64_t begin) {
     KjParams p{};
@@ -1680,15 +1759,13 @@ KjParams kj_params(pf_kmerjoin* j, uint64_t n, uint64_t begin) {
     return p;
 }
 
-inline uint32_t kj_tiles(uint64_t n) { return (uint32_t)(((n + 15) / 16 + KJ_TILE_VECS - 1) / KJ_TILE_VECS); }
-
 // the survey of d_text[begin .. n)
 int kj_survey_device(pf_kmerjoin* j, uint64_t n, uint64_t begin) {
     if (n <= begin) return PF_OK;
     TimedStream& ts = j->feed.ts;
     const KjParams p = kj_params(j, n, begin);
     PFCHK(ts.timed([&]() -> int {
-        hipLaunchKernelGGL(kj_survey_kernel, dim3(kj_tiles(n)), dim3(256), 0, ts.stream, p);
+        hipLaunchKernelGGL(kj_survey_kernel, dim3(row_tiles(n)), dim3(256), 0, ts.stream, p);
         HIPCHK(hipGetLastError()); return PF_OK;
     }));
     HIPCHK(hipStreamSynchronize(ts.stream));
@@ -1697,51 +1774,28 @@ int kj_survey_device(pf_kmerjoin* j, uint64_t n, uint64_t begin) {
     return PF_OK;
 }
 
-// the join of d_text[begin .. n) for one bunch: the text in out.d_out[0 .. out.bytes), ready to be handed out
+// the join of d_text[begin .. n) for one bunch: the text in pack.out.d_out[0 .. pack.out.bytes), ready to be handed out
 int kj_join_device(pf_kmerjoin* j, uint64_t n, uint64_t begin, uint32_t bunch, int mode) {
     kj_reset_out(j);
     if (n <= begin) return PF_OK;
     if (bunch >= j->n_bunches || mode < 0 || mode > 2) return fail(PF_ERR_ARG, "pf_kmerjoin_join: no such bunch or mode");
     TimedStream& ts = j->feed.ts;
-    const uint32_t tiles = kj_tiles(n);
-    PFCHK(j->d_thr.ensure((size_t)tiles * 256 * sizeof(uint2)));
-    PFCHK(j->d_tile.ensure(((size_t)tiles + 1) * 16));
     KjParams p = kj_params(j, n, begin);
     p.bunch = (int32_t)bunch; p.mode = mode;
-    p.thr = j->d_thr.as<uint2>(); p.tile = j->d_tile.as<unsigned long long>();
-    HIPCHK(hipMemsetAsync(p.err, 0, 4, ts.stream));
+    HIPCHK(hipMemsetAsync(p.err, 0, 4, ts.stream));      // (kj_row complains in either pass: the word is this call's alone)
     float ms = 0;
-    PFCHK(ts.timed([&]() -> int {
-        hipLaunchKernelGGL(kj_plan_kernel, dim3(tiles), dim3(256), 0, ts.stream, p);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(kj_tiles_kernel, dim3(1), dim3(256), 0, ts.stream, p.tile, (uint64_t)tiles);
-        HIPCHK(hipGetLastError()); return PF_OK;
-    }));
-    uint64_t totals[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(totals, p.tile + 2 * (uint64_t)tiles, 16, hipMemcpyDeviceToHost, ts.stream));
-    HIPCHK(hipStreamSynchronize(ts.stream));
-    ts.add_elapsed(&ms);
+    uint64_t n_rows = 0, n_bytes = 0;
+    PFCHK(j->pack.run(ts, p, &ms, &n_rows, &n_bytes,
+                      [&](uint32_t tiles) { hipLaunchKernelGGL(kj_plan_kernel, dim3(tiles), dim3(256), 0, ts.stream, p); },
+                      [&](uint32_t tiles) { hipLaunchKernelGGL(kj_place_kernel, dim3(tiles), dim3(256), 0, ts.stream, p, n_rows, n_bytes); }));
     j->bytes_scanned += n - begin;
-    const uint64_t n_rows = totals[0], n_bytes = totals[1];
-    unsigned int err = 0;
-    if (n_rows) {
-        PFCHK(j->d_rec.ensure((size_t)n_rows * sizeof(KjRec)));
-        PFCHK(j->out.d_out.ensure((size_t)n_bytes));
-        p.rec = j->d_rec.as<KjRec>(); p.out = j->out.d_out.as<unsigned char>();
-        PFCHK(ts.timed([&]() -> int {
-            hipLaunchKernelGGL(kj_place_kernel, dim3(tiles), dim3(256), 0, ts.stream, p, n_rows, n_bytes);
-            HIPCHK(hipGetLastError());
-            const uint64_t groups = (n_rows + KJ_GROUP - 1) / KJ_GROUP;
-            hipLaunchKernelGGL(kj_write_kernel, dim3((uint32_t)std::min<uint64_t>((groups + 3) / 4, 256 * 32)), dim3(256), 0, ts.stream, p, n_rows);
-            HIPCHK(hipGetLastError()); return PF_OK;
-        }));
-    }
+    unsigned int err = 0;                                  // (read even when no row was placed: the plan may have complained)
     HIPCHK(hipMemcpyAsync(&err, p.err, 4, hipMemcpyDeviceToHost, ts.stream));
     HIPCHK(hipStreamSynchronize(ts.stream));
     if (n_rows) ts.add_elapsed(&ms);
     j->write_ms += ms;
     if (err) return fail(PF_ERR_STATE, "pf_kmerjoin_join: a row of the bunch is not one the survey passed (flags 0x%x): the file has changed", err);
-    j->out.bytes = n_bytes;
+    j->pack.out.bytes = n_bytes;
     j->gz_now = j->gz_on && mode != 2;            // (the raw rows go to pandas: they stay text)
     if (mode == 2) j->raw_rows += n_rows; else j->rows_written += n_rows;
     return PF_OK;
@@ -1754,8 +1808,8 @@ int kj_next_members(pf_kmerjoin* j, const char** piece, uint64_t* nbytes) {
     constexpr PfGzEncoder::Cursor W = PfGzEncoder::STREAM_BLOCK0;
     for (;;) {
         PFCHK(j->gz.next(ts.stream, piece, nbytes));
-        if (*nbytes || j->gz_at >= j->out.bytes) return PF_OK;
-        const uint64_t m = std::min<uint64_t>(PfGzEncoder::BLOCK, j->out.bytes - j->gz_at), cap = PfGzEncoder::bound(m);
+        if (*nbytes || j->gz_at >= j->pack.out.bytes) return PF_OK;
+        const uint64_t m = std::min<uint64_t>(PfGzEncoder::BLOCK, j->pack.out.bytes - j->gz_at), cap = PfGzEncoder::bound(m);
         if (!j->enc.grid_cap) {
             int n_cu = 0;
             HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, j->feed.device));
@@ -1764,18 +1818,12 @@ int kj_next_members(pf_kmerjoin* j, const char** piece, uint64_t* nbytes) {
         // (a buffer that is re-made gets a quarter more, up to what a whole slice may take)
         if (cap > j->gz.d_out.cap) PFCHK(j->gz.d_out.ensure((size_t)std::min<uint64_t>(PfGzEncoder::bound(PfGzEncoder::BLOCK), cap + cap / 4), true));
         j->gz.reset();
-        PFCHK(j->enc.encode(ts.stream, W, j->out.d_out.as<char>() + j->gz_at, m, j->gz_flags, j->gz.d_out.as<char>(), cap, ts.e0, ts.e1));
+        PFCHK(j->enc.encode(ts.stream, W, j->pack.out.d_out.as<char>() + j->gz_at, m, j->gz_flags, j->gz.d_out.as<char>(), cap, ts.e0, ts.e1));
         HIPCHK(hipStreamSynchronize(ts.stream));
         ts.add_elapsed(&j->gz_ms);
         PFCHK(j->enc.member_bytes(W, &j->gz.bytes));
         j->gz_at += m; j->gz_text_bytes += m; j->gz_member_bytes += j->gz.bytes;
     }
-}
-
-template <class T> int kj_upload(DevBuf& d, const std::vector<T>& v) {
-    PFCHK(d.ensure(std::max<size_t>(v.size() * sizeof(T), 16), true));
-    if (!v.empty()) HIPCHK(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return PF_OK;
 }
 
 }  // namespace
@@ -1840,11 +1888,11 @@ int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* 
     if (arena.size() >= (1ull << 32)) return fail(PF_ERR_CAPACITY, "pf_kmerjoin_create: the keys and their texts take 4 GiB or more");
     j->counters.assign((size_t)j->n_bunches * KJ_COUNTERS, 0);
     PFCHK(j->feed.ts.create());
-    PFCHK(kj_upload(j->d_chash, chash)); PFCHK(kj_upload(j->d_cslot, cslot)); PFCHK(kj_upload(j->d_clusters, cl));
-    PFCHK(kj_upload(j->d_khash, khash)); PFCHK(kj_upload(j->d_kslot, kslot)); PFCHK(kj_upload(j->d_keys, keys));
-    PFCHK(kj_upload(j->d_arena, std::vector<char>(arena.begin(), arena.end())));
-    PFCHK(kj_upload(j->d_counters, j->counters));
-    PFCHK(kj_upload(j->d_misc, std::vector<uint64_t>(3, 0)));
+    PFCHK(dev_upload(j->d_chash, chash)); PFCHK(dev_upload(j->d_cslot, cslot)); PFCHK(dev_upload(j->d_clusters, cl));
+    PFCHK(dev_upload(j->d_khash, khash)); PFCHK(dev_upload(j->d_kslot, kslot)); PFCHK(dev_upload(j->d_keys, keys));
+    PFCHK(dev_upload(j->d_arena, std::vector<char>(arena.begin(), arena.end())));
+    PFCHK(dev_upload(j->d_counters, j->counters));
+    PFCHK(dev_upload(j->d_misc, std::vector<uint64_t>(3, 0)));
     *out = j.release();
     return PF_OK;
 }
@@ -1856,14 +1904,10 @@ int pf_kmerjoin_survey(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint64
     return kj_survey_device(j, *consumed, 0);
 }
 
-int pf_kmerjoin_members_begin(pf_kmerjoin* j, int header) {
-    if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_members_begin: null argument");
-    return j->feed.members_begin(header);
-}
+int pf_kmerjoin_members_begin(pf_kmerjoin* j, int header) { return feed_members_begin(j, "pf_kmerjoin_members_begin", header); }
 
 int pf_kmerjoin_members_header(pf_kmerjoin* j, const char** line, uint64_t* nbytes) {
-    if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_members_header: null argument");
-    return j->feed.header_line(line, nbytes);
+    return feed_members_header(j, "pf_kmerjoin_members_header", line, nbytes);
 }
 
 int pf_kmerjoin_survey_members(pf_kmerjoin* j, const char* members, uint64_t nbytes, int last, uint64_t* consumed, int* taken) {
@@ -1893,7 +1937,7 @@ int pf_kmerjoin_join(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint32_t
     *out_bytes = 0; kj_reset_out(j);
     PFCHK(j->feed.plain(text, nbytes, consumed));
     PFCHK(kj_join_device(j, *consumed, 0, bunch, mode));
-    *out_bytes = j->out.bytes;
+    *out_bytes = j->pack.out.bytes;
     return PF_OK;
 }
 
@@ -1904,14 +1948,14 @@ int pf_kmerjoin_join_members(pf_kmerjoin* j, const char* members, uint64_t nbyte
     *out_bytes = 0; kj_reset_out(j);
     PFCHK(j->feed.members(members, nbytes, last, consumed, taken,
                            [j, bunch, mode](uint64_t n, uint64_t skip) { return kj_join_device(j, n, skip, bunch, mode); }));
-    *out_bytes = j->out.bytes;
+    *out_bytes = j->pack.out.bytes;
     return PF_OK;
 }
 
 int pf_kmerjoin_next_text(pf_kmerjoin* j, const char** piece, uint64_t* nbytes) {
     if (!j || !piece || !nbytes) return fail(PF_ERR_ARG, "pf_kmerjoin_next_text: null argument");
     HIPCHK(hipSetDevice(j->feed.device));
-    return j->gz_now ? kj_next_members(j, piece, nbytes) : j->out.next(j->feed.ts.stream, piece, nbytes);
+    return j->gz_now ? kj_next_members(j, piece, nbytes) : j->pack.out.next(j->feed.ts.stream, piece, nbytes);
 }
 
 int pf_kmerjoin_set_gzip(pf_kmerjoin* j, int on, uint32_t flags) {
@@ -1960,8 +2004,9 @@ int pf_kmerjoin_stats(pf_kmerjoin* j, uint64_t stats[8], float ms[3]) {
 //                    would have inferred for the column from the whole file, and so how to_csv prints the kept rows
 // and the OR of the rows' flags (AF_ROW_*): a flagged table, one with an AF_ODD cell or one whose classes pandas would mix
 // goes through pandas whole (the routing is the caller's).
-// Kernels: af_plan_kernel walks every line once -- classes, flags, keep or drop, per-thread rows and bytes --,
-// kj_tiles_kernel, af_place_kernel (the walk of the p-value cell alone) and the raw rows of kj_write_kernel.
+// Kernels: the second client of the row pack.  af_plan_kernel walks every line once -- classes, flags, keep or drop,
+// per-thread rows and bytes -- and ends in row_plan; af_place_kernel is the walk of the p-value cell alone under row_place;
+// row_tiles_kernel between them and row_write_kernel behind them, all rows raw, are the pack's.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -1973,15 +2018,12 @@ constexpr uint32_t AF_INT_DIGITS = 18;           // an integer of more digits ma
 constexpr uint32_t AF_EXP_DIGITS = 5;
 constexpr int32_t AF_DECADES = 300;              // |value| within 1e-300 .. 1e300 is decided here
 
-struct AfParams {
-    const unsigned char* text;   // the block, complete lines
-    uint64_t n, begin;           // lines that start in [begin, n)
+struct AfParams : RowSpan {      // (no arena: every kept line is a raw row)
     uint32_t pvalue_field, n_fields;
     double thr_hi;
     unsigned int* cols;          // n_fields words of class bits
     unsigned int* flags;         // [0] the OR of the rows' flags, [1] a place kernel that found other rows than the plan
     unsigned long long* rows;    // data lines
-    uint2* thr; unsigned long long* tile; KjRec* rec;
 };
 
 // One cell, byte by byte: the number grammar  [+-]?([0-9]+\.?[0-9]*|\.[0-9]+)([eE][+-]?[0-9]+)?  and what its value needs.
@@ -2102,19 +2144,16 @@ __global__ __launch_bounds__(256) void af_plan_kernel(AfParams p) {
         unsigned int* const at = field < AF_LDS_COLS ? &s_cols[field] : &p.cols[field];
         if ((*at & cls) != cls) atomicOr(at, cls);
     };
-    kj_each_line(p, [&](uint64_t s) {
+    row_each_line(p, [&](uint64_t s) {
         AfRow r;
         af_walk<true>(p, s, r, col);
         lines++; flags |= r.flags;
         if (r.keep) { rows++; bytes += r.len; }
     });
-    p.thr[(uint64_t)blockIdx.x * 256 + threadIdx.x] = make_uint2((uint32_t)rows, (uint32_t)bytes);
     if (flags) atomicOr(&s_flags, flags);
     if (lines) atomicAdd(&s_lines, lines);
-    unsigned long long ta, tb;
-    kj_block_exscan(rows, bytes, &ta, &tb);
+    row_plan(p, rows, bytes);
     if (threadIdx.x == 0) {
-        p.tile[2 * (uint64_t)blockIdx.x] = ta; p.tile[2 * (uint64_t)blockIdx.x + 1] = tb;
         if (s_flags) atomicOr(&p.flags[0], s_flags);
         if (s_lines) atomicAdd(p.rows, s_lines);
     }
@@ -2123,18 +2162,13 @@ __global__ __launch_bounds__(256) void af_plan_kernel(AfParams p) {
 }
 
 __global__ __launch_bounds__(256) void af_place_kernel(AfParams p, uint64_t n_rows, uint64_t n_bytes) {
-    const uint2 mine = p.thr[(uint64_t)blockIdx.x * 256 + threadIdx.x];
-    unsigned long long row = mine.x, at = mine.y, ta, tb;
-    kj_block_exscan(row, at, &ta, &tb);
-    row += p.tile[2 * (uint64_t)blockIdx.x]; at += p.tile[2 * (uint64_t)blockIdx.x + 1];
-    kj_each_line(p, [&](uint64_t s) {
+    row_place(p, n_rows, n_bytes, &p.flags[1], 1u, [&](uint64_t s, RowRec& r) {
         AfRow w;
         af_walk<false>(p, s, w, [](uint32_t, uint32_t) {});
-        if (!w.keep) return;
-        KjRec r{};
-        r.src = s; r.dst = at; r.len0 = w.len; r.raw = 1;
-        if (row < n_rows && at + w.len <= n_bytes) p.rec[row] = r; else atomicOr(&p.flags[1], 1u);
-        row++; at += w.len;
+        if (!w.keep) return false;
+        r = RowRec{};
+        r.src = s; r.len0 = w.len; r.raw = 1;
+        return true;
     });
 }
 
@@ -2144,9 +2178,8 @@ struct pf_assocfilter {
     uint32_t pvalue_field = 0, n_fields = 0;
     double thr_hi = 0;
     DevBuf d_cols, d_misc;                       // d_misc: data lines (8 bytes), the rows' flags and the place kernel's complaint (4 each)
-    DevBuf d_thr, d_tile, d_rec;
     std::vector<uint32_t> cols;
-    KjHandout out;                               // the kept lines of the last scan
+    RowPack pack;                                // pack.out: the kept lines of the last scan
     uint64_t bytes_scanned = 0, kept = 0;
     float device_ms = 0;
     TextFeed feed;                               // (its stream goes first: a piece of text may be on its way down into pin)
@@ -2154,51 +2187,28 @@ struct pf_assocfilter {
 
 namespace {
 
-// the scan of d_text[begin .. n): the kept lines in out.d_out[0 .. out.bytes), ready to be handed out
+// the scan of d_text[begin .. n): the kept lines in pack.out.d_out[0 .. pack.out.bytes), ready to be handed out
 int af_scan_device(pf_assocfilter* f, uint64_t n, uint64_t begin) {
-    f->out.reset();
+    f->pack.out.reset();
     if (n <= begin) return PF_OK;
     TimedStream& ts = f->feed.ts;
-    const uint32_t tiles = kj_tiles(n);
-    PFCHK(f->d_thr.ensure((size_t)tiles * 256 * sizeof(uint2)));
-    PFCHK(f->d_tile.ensure(((size_t)tiles + 1) * 16));
     AfParams p{};
     p.text = f->feed.text.d_text.as<unsigned char>(); p.n = n; p.begin = begin;
     p.pvalue_field = f->pvalue_field; p.n_fields = f->n_fields; p.thr_hi = f->thr_hi;
     p.cols = f->d_cols.as<unsigned int>();
     p.rows = f->d_misc.as<unsigned long long>(); p.flags = reinterpret_cast<unsigned int*>(f->d_misc.as<unsigned long long>() + 1);
-    p.thr = f->d_thr.as<uint2>(); p.tile = f->d_tile.as<unsigned long long>();
-    PFCHK(ts.timed([&]() -> int {
-        hipLaunchKernelGGL(af_plan_kernel, dim3(tiles), dim3(256), 0, ts.stream, p);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(kj_tiles_kernel, dim3(1), dim3(256), 0, ts.stream, p.tile, (uint64_t)tiles);
-        HIPCHK(hipGetLastError()); return PF_OK;
-    }));
-    uint64_t totals[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(totals, p.tile + 2 * (uint64_t)tiles, 16, hipMemcpyDeviceToHost, ts.stream));
-    HIPCHK(hipStreamSynchronize(ts.stream));
-    ts.add_elapsed(&f->device_ms);
+    uint64_t n_rows = 0, n_bytes = 0;
+    PFCHK(f->pack.run(ts, p, &f->device_ms, &n_rows, &n_bytes,
+                      [&](uint32_t tiles) { hipLaunchKernelGGL(af_plan_kernel, dim3(tiles), dim3(256), 0, ts.stream, p); },
+                      [&](uint32_t tiles) { hipLaunchKernelGGL(af_place_kernel, dim3(tiles), dim3(256), 0, ts.stream, p, n_rows, n_bytes); }));
     f->bytes_scanned += n - begin;
-    const uint64_t n_rows = totals[0], n_bytes = totals[1];
-    if (!n_rows) return PF_OK;
-    PFCHK(f->d_rec.ensure((size_t)n_rows * sizeof(KjRec)));
-    PFCHK(f->out.d_out.ensure((size_t)n_bytes));
-    p.rec = f->d_rec.as<KjRec>();
-    KjParams w{};                                 // the writer's share: raw rows, text -> out by the records
-    w.text = p.text; w.rec = p.rec; w.out = f->out.d_out.as<unsigned char>();
-    PFCHK(ts.timed([&]() -> int {
-        hipLaunchKernelGGL(af_place_kernel, dim3(tiles), dim3(256), 0, ts.stream, p, n_rows, n_bytes);
-        HIPCHK(hipGetLastError());
-        const uint64_t groups = (n_rows + KJ_GROUP - 1) / KJ_GROUP;
-        hipLaunchKernelGGL(kj_write_kernel, dim3((uint32_t)std::min<uint64_t>((groups + 3) / 4, 256 * 32)), dim3(256), 0, ts.stream, w, n_rows);
-        HIPCHK(hipGetLastError()); return PF_OK;
-    }));
+    if (!n_rows) return PF_OK;                      // (only the place pass complains, and the word is never cleared)
     unsigned int err = 0;
     HIPCHK(hipMemcpyAsync(&err, p.flags + 1, 4, hipMemcpyDeviceToHost, ts.stream));
     HIPCHK(hipStreamSynchronize(ts.stream));
     ts.add_elapsed(&f->device_ms);
     if (err) return fail(PF_ERR_STATE, "pf_assocfilter_scan: the place pass found other rows than the plan pass");
-    f->out.bytes = n_bytes; f->kept += n_rows;
+    f->pack.out.bytes = n_bytes; f->kept += n_rows;
     return PF_OK;
 }
 
@@ -2221,8 +2231,8 @@ int pf_assocfilter_create(int device, uint32_t pvalue_field, uint32_t n_fields, 
     f->pvalue_field = pvalue_field; f->n_fields = n_fields; f->thr_hi = thr_hi;
     f->cols.assign(n_fields, 0);
     PFCHK(f->feed.ts.create());
-    PFCHK(kj_upload(f->d_cols, f->cols));
-    PFCHK(kj_upload(f->d_misc, std::vector<uint64_t>(2, 0)));
+    PFCHK(dev_upload(f->d_cols, f->cols));
+    PFCHK(dev_upload(f->d_misc, std::vector<uint64_t>(2, 0)));
     *out = f.release();
     return PF_OK;
 }
@@ -2230,37 +2240,33 @@ int pf_assocfilter_create(int device, uint32_t pvalue_field, uint32_t n_fields, 
 int pf_assocfilter_scan(pf_assocfilter* f, const char* text, uint64_t nbytes, uint64_t* out_bytes, uint64_t* consumed) {
     if (!f || !out_bytes || !consumed || (nbytes && !text)) return fail(PF_ERR_ARG, "pf_assocfilter_scan: null argument");
     HIPCHK(hipSetDevice(f->feed.device));
-    *out_bytes = 0; f->out.reset();
+    *out_bytes = 0; f->pack.out.reset();
     PFCHK(f->feed.plain(text, nbytes, consumed));
     PFCHK(af_scan_device(f, *consumed, 0));
-    *out_bytes = f->out.bytes;
+    *out_bytes = f->pack.out.bytes;
     return PF_OK;
 }
 
-int pf_assocfilter_members_begin(pf_assocfilter* f, int header) {
-    if (!f) return fail(PF_ERR_ARG, "pf_assocfilter_members_begin: null argument");
-    return f->feed.members_begin(header);
-}
+int pf_assocfilter_members_begin(pf_assocfilter* f, int header) { return feed_members_begin(f, "pf_assocfilter_members_begin", header); }
 
 int pf_assocfilter_members_header(pf_assocfilter* f, const char** line, uint64_t* nbytes) {
-    if (!f) return fail(PF_ERR_ARG, "pf_assocfilter_members_header: null argument");
-    return f->feed.header_line(line, nbytes);
+    return feed_members_header(f, "pf_assocfilter_members_header", line, nbytes);
 }
 
 int pf_assocfilter_scan_members(pf_assocfilter* f, const char* members, uint64_t nbytes, int last, uint64_t* out_bytes,
                                 uint64_t* consumed, int* taken) {
     if (!f || !out_bytes || !consumed || !taken || (nbytes && !members)) return fail(PF_ERR_ARG, "pf_assocfilter_scan_members: null argument");
     HIPCHK(hipSetDevice(f->feed.device));
-    *out_bytes = 0; f->out.reset();
+    *out_bytes = 0; f->pack.out.reset();
     PFCHK(f->feed.members(members, nbytes, last, consumed, taken, [f](uint64_t n, uint64_t skip) { return af_scan_device(f, n, skip); }));
-    *out_bytes = f->out.bytes;
+    *out_bytes = f->pack.out.bytes;
     return PF_OK;
 }
 
 int pf_assocfilter_next_lines(pf_assocfilter* f, const char** piece, uint64_t* nbytes) {
     if (!f || !piece || !nbytes) return fail(PF_ERR_ARG, "pf_assocfilter_next_lines: null argument");
     HIPCHK(hipSetDevice(f->feed.device));
-    return f->out.next(f->feed.ts.stream, piece, nbytes);
+    return f->pack.out.next(f->feed.ts.stream, piece, nbytes);
 }
 
 int pf_assocfilter_columns(pf_assocfilter* f, const uint32_t** class_bits, uint32_t* n_fields, uint32_t* row_flags, uint64_t counters[2]) {

@@ -24,9 +24,11 @@ lines are parsed with the dtypes pandas would have inferred from all of them (`a
 whose classes pandas would mix, goes through the reference's two statements whole (`--host-associations` sends every
 table there).
 
-All three read a table the same two ways, written once here: a device-gzipped file goes up compressed and is inflated where
-it lands (`pass_member_file` -> pf_*_members), any other is read block by block through the host (`scan_lines`);
-`route_file` chooses, and falls back to the second when the device decoder does not take a block.
+All three, and panfeed-plot's `plot.GridBuilder`, read a table the same two ways, written once here: a device-gzipped
+file goes up compressed and is inflated where it lands (`pass_member_file` -> pf_*_members), any other is read block by
+block through the host (`scan_lines`); `route_file` chooses, and falls back to the second when the device decoder does not
+take a block.  What the four wrap around that -- the handle's life, the pointer to a block, the pass either way with the
+call's own arguments and what drains its output, the header line -- is `DeviceTable`, their base.
 
 panfeed-get-kmers --gz-output writes the annotated table as such a file itself: the device join's rows are gzipped where
 they were written (pf_kmerjoin_set_gzip) and only the members come to the host; text made on the host -- the header line,
@@ -43,8 +45,6 @@ import gzip
 import io
 import logging
 import sys
-
-import pandas as pd
 
 from . import _lib
 
@@ -121,26 +121,95 @@ def route_file(path, device_gunzip, members, host, counts, again=None, reason=_l
     return host()
 
 
-class RowFilter:
+class DeviceTable:
+    """What the four owners of a device text feed -- RowFilter, KmerJoin, AssocFilter here, plot.GridBuilder -- are alike: the
+    life of the handle and the pass over a table file either way.  The counters route_file moves stay on each subclass:
+    it does `counts.x += 1` on the class it is given, and one inherited from here would be all four's."""
+
+    entry = None                    # the owner's entry points by name: create, destroy, members_begin, members_header
+
+    def __init__(self):
+        self.L = _lib.load()
+        self.h = C.c_void_p()
+        self._create_fn, self._destroy_fn, self._begin_fn, self._header_fn = (getattr(self.L, name) for name in self.entry)
+
+    def _create(self, *args):
+        """a fresh handle, create(*args, &handle), in place of the one there may be"""
+        self.close()
+        _lib.check(self._create_fn(*args, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self._destroy_fn(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    @staticmethod
+    def _pointer(data, n=None):
+        """(what ctypes passes for `data`, the bytes of it that count): bytes as they are, a bytearray -- its first n bytes
+        count -- without a copy.  The export holds the bytearray's size: the caller drops the pointer (`del`) before
+        anything may resize the buffer, as scan_lines' buf.extend does"""
+        if isinstance(data, bytearray):
+            return (C.c_char * len(data)).from_buffer(data), len(data) if n is None else n
+        return data, len(data)
+
+    def _members_pass(self, path, block_bytes, fn, args=(), drain=None):
+        """one pass over a file of device members, fn(handle, block, its bytes, last, *args, &used, &taken) a block, then
+        drain() if the block was taken (pass_member_file's `after`); False when one was not"""
+        def call(data, last):
+            used, taken = C.c_uint64(), C.c_int()
+            _lib.check(fn(self.h, data, len(data), 1 if last else 0, *args, C.byref(used), C.byref(taken)))
+            return used.value, taken.value
+
+        return pass_member_file(path, block_bytes, lambda: _lib.check(self._begin_fn(self.h, 1)), call, drain)
+
+    def _plain_pass(self, path, block_bytes, fn, args=(), drain=None):
+        """one pass over a table file through the host, fn(handle, block, its bytes, *args, &used) a block of lines, then
+        drain(block) -- the block for a drain whose output speaks of it --; -> the header line, which is no block's"""
+        def scan(buf, n):
+            used = C.c_uint64()
+            ptr, n = self._pointer(buf, n)
+            _lib.check(fn(self.h, ptr, n, *args, C.byref(used)))
+            del ptr
+            if drain:
+                drain(buf)
+            return int(used.value)
+
+        with open_table(path) as fh:
+            header = fh.readline()
+            scan_lines(fh, scan, block_bytes)
+        return header
+
+    def _drain(self, next_fn, sink):
+        """the text the last call left on the device to sink(a view of it), piece by piece: next_fn(handle, &piece, &bytes)"""
+        piece, n = C.c_void_p(), C.c_uint64()
+        while True:
+            _lib.check(next_fn(self.h, C.byref(piece), C.byref(n)))
+            if not n.value:
+                return
+            sink(memoryview((C.c_char * n.value).from_address(piece.value)))
+
+    def _header(self):
+        """the header line the members pass peeled off"""
+        line, n = C.c_void_p(), C.c_uint64()
+        _lib.check(self._header_fn(self.h, C.byref(line), C.byref(n)))
+        return C.string_at(line, n.value) if n.value else b""
+
+
+class RowFilter(DeviceTable):
     """rows of a TSV whose first (`first_field=True`) or last field is one of `keys`, filtered on the device"""
 
+    entry = ("pf_rowfilter_create", "pf_rowfilter_destroy", "pf_rowfilter_members_begin", "pf_rowfilter_members_header")
     device_gunzip_files = 0         # files, over all filters, that went the device gunzip route to their end
     fallback_files = 0              # and files the automatic mode began there and read again through gzip
 
     def __init__(self, keys, first_field, device=0):
-        self.L = _lib.load()
+        super().__init__()
         ks = [k.encode() if isinstance(k, str) else bytes(k) for k in keys]
         arr, lens = _lib.c_strings(ks)
-        self.h = C.c_void_p()
         self.fallbacks = 0              # files the automatic mode began on the device and read again through gzip
-        _lib.check(self.L.pf_rowfilter_create(int(device), 1 if first_field else 0, arr, lens, len(ks), C.byref(self.h)))
-
-    def close(self):
-        if self.h:
-            self.L.pf_rowfilter_destroy(self.h)
-            self.h = C.c_void_p()
-
-    __del__ = close
+        self._create(int(device), 1 if first_field else 0, arr, lens, len(ks))
 
     def stats(self):
         n, ms = C.c_uint64(), C.c_float()
@@ -151,21 +220,21 @@ class RowFilter:
                 "members_inflated": int(gm.value), "text_bytes_inflated": int(gt.value), "inflate_ms": float(gms.value),
                 "inflate_device_bytes": int(gdev.value), "gunzip_fallbacks": self.fallbacks}
 
+    @staticmethod
+    def _rows(data, b, e, cnt):
+        """the lines data[b[i]:e[i]] of pf_rowfilter_scan's answer, joined (the view goes with the call)"""
+        view = memoryview(data)
+        return b"".join(view[b[i]:e[i]] for i in range(cnt.value))
+
     def scan_block(self, data, n=None):
         """(matching lines of the complete lines of `data` (bytes, or the first n bytes of a bytearray), joined; number of
         bytes consumed)"""
         b, e = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
         cnt, used = C.c_uint64(), C.c_uint64()
-        if isinstance(data, bytearray):
-            n = len(data) if n is None else n
-            ptr = (C.c_char * len(data)).from_buffer(data)          # no copy
-        else:
-            n, ptr = len(data), data
+        ptr, n = self._pointer(data, n)
         _lib.check(self.L.pf_rowfilter_scan(self.h, ptr, n, C.byref(b), C.byref(e), C.byref(cnt), C.byref(used)))
-        view = memoryview(data)
-        got = b"".join(view[b[i]:e[i]] for i in range(cnt.value))
-        del ptr, view
-        return got, int(used.value)
+        del ptr
+        return self._rows(data, b, e, cnt), int(used.value)
 
     def scan_members(self, data, last):
         """(matching lines of the text of the whole gzip members in `data` (bytes of the compressed file from a member
@@ -176,34 +245,6 @@ class RowFilter:
         got = C.string_at(lines, nb.value) if nb.value else b""
         return got, int(used.value), bool(taken.value)
 
-    def _filter_members(self, path, block_bytes):
-        """filter_file's device gunzip route: (header, rows), or None when a block was not taken"""
-        out = []
-
-        def call(data, last):
-            got, used, taken = self.scan_members(data, last)
-            out.append(got)
-            return used, taken
-
-        if not pass_member_file(path, block_bytes, lambda: _lib.check(self.L.pf_rowfilter_members_begin(self.h, 1)), call):
-            return None
-        line, n = C.c_void_p(), C.c_uint64()
-        _lib.check(self.L.pf_rowfilter_members_header(self.h, C.byref(line), C.byref(n)))
-        return (C.string_at(line, n.value) if n.value else b""), b"".join(out)
-
-    def _filter_host(self, path, block_bytes):
-        out = []
-
-        def scan(buf, n):
-            got, used = self.scan_block(buf, n)
-            out.append(got)
-            return used
-
-        with open_table(path) as fh:
-            header = fh.readline()
-            scan_lines(fh, scan, block_bytes)
-        return header, b"".join(out)
-
     def _fell_back(self):
         self.fallbacks += 1
 
@@ -212,8 +253,19 @@ class RowFilter:
         (--gpu-compress writes such) is inflated on the device and scanned there, as device_gunzip says (route_file);
         block_bytes then counts compressed bytes.  Otherwise the file is read block by block straight into one buffer;
         what follows a block's last complete line is moved to the front for the next block."""
-        return route_file(path, device_gunzip, lambda: self._filter_members(path, block_bytes),
-                          lambda: self._filter_host(path, block_bytes), RowFilter, self._fell_back)
+        def members():                               # (header, rows), or None when a block was not taken
+            out, lines, nb, cnt = [], C.c_void_p(), C.c_uint64(), C.c_uint64()
+            took = self._members_pass(path, block_bytes, self.L.pf_rowfilter_scan_members, (C.byref(lines), C.byref(nb), C.byref(cnt)),
+                                      lambda: out.append(C.string_at(lines, nb.value) if nb.value else b""))
+            return (self._header(), b"".join(out)) if took else None
+
+        def host():
+            out, b, e, cnt = [], C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.c_uint64()
+            header = self._plain_pass(path, block_bytes, self.L.pf_rowfilter_scan, (C.byref(b), C.byref(e), C.byref(cnt)),
+                                      lambda buf: out.append(self._rows(buf, b, e, cnt)))
+            return header, b"".join(out)
+
+        return route_file(path, device_gunzip, members, host, RowFilter, self._fell_back)
 
 
 KJ_FLAG_NAMES = ((1, "not 10 tabs"), (2, "a control, non-ASCII or quote byte"), (4, "an integer field that is not canonical decimal"),
@@ -222,7 +274,7 @@ KJ_FLAG_NAMES = ((1, "not 10 tabs"), (2, "a control, non-ASCII or quote byte"), 
 KJ_RAW = 2                          # KmerJoin.join_file's mode: the rows that have a key, as they stand
 
 
-class KmerJoin:
+class KmerJoin(DeviceTable):
     """the rows of kmers.tsv whose cluster is a selected one, annotated with the rendered text of their (cluster, k-mer)
     on the device.  clusters: (literal bytes, bunch number) pairs; keys: (cluster bytes, k-mer bytes) pairs with their two
     renderings text0 / text1; empty: the text of a row that has no key"""
@@ -233,10 +285,10 @@ class KmerJoin:
     device_gunzip_files = 0         # passes over a file that went the device gunzip route to their end
     fallback_files = 0              # and passes the automatic mode began there and read again through gzip
     last_stats = None               # stats() of the last run's join, with the survey's rows and unmatched rows over all bunches
+    entry = ("pf_kmerjoin_create", "pf_kmerjoin_destroy", "pf_kmerjoin_members_begin", "pf_kmerjoin_members_header")
 
     def __init__(self, clusters, n_bunches, keys, text0, text1, empty, device=0):
-        self.L = _lib.load()
-        self.h = C.c_void_p()
+        super().__init__()
         self.n_bunches = max(int(n_bunches), 1)
         self.members = {}               # path -> whether the survey went the device gunzip route to the end
         strs = _lib.c_strings
@@ -246,15 +298,8 @@ class KmerJoin:
         kk, kk_len = strs([k for _, k in keys])
         t0, t0_len = strs(list(text0))
         t1, t1_len = strs(list(text1))
-        _lib.check(self.L.pf_kmerjoin_create(int(device), cl, cl_len, bunch, len(clusters), self.n_bunches, kc, kc_len, kk, kk_len,
-                                             t0, t0_len, t1, t1_len, len(keys), empty, len(empty), C.byref(self.h)))
-
-    def close(self):
-        if self.h:
-            self.L.pf_kmerjoin_destroy(self.h)
-            self.h = C.c_void_p()
-
-    __del__ = close
+        self._create(int(device), cl, cl_len, bunch, len(clusters), self.n_bunches, kc, kc_len, kk, kk_len, t0, t0_len, t1, t1_len,
+                     len(keys), empty, len(empty))
 
     def stats(self):
         st, ms = (C.c_uint64 * 8)(), (C.c_float * 3)()
@@ -280,46 +325,14 @@ class KmerJoin:
         return [{"rows": int(p[5 * i]), "unmatched": int(p[5 * i + 1]), "bytes": (int(p[5 * i + 2]), int(p[5 * i + 3])),
                  "flags": int(p[5 * i + 4])} for i in range(n.value)]
 
-    def _drain(self, write):
-        """hand the text the last join call made to write(), piece by piece"""
-        piece, n = C.c_void_p(), C.c_uint64()
-        while True:
-            _lib.check(self.L.pf_kmerjoin_next_text(self.h, C.byref(piece), C.byref(n)))
-            if not n.value:
-                return
-            write(memoryview((C.c_char * n.value).from_address(piece.value)))
-
-    def _pass_members(self, path, block_bytes, fn, args, write):
-        """one pass over a file of device members, fn(handle, block, its bytes, last, *args, &used, &taken) a block; False
-        when a block was not taken"""
-        def call(data, last):
-            used, taken = C.c_uint64(), C.c_int()
-            _lib.check(fn(self.h, data, len(data), 1 if last else 0, *args, C.byref(used), C.byref(taken)))
-            return used.value, taken.value
-
-        return pass_member_file(path, block_bytes, lambda: _lib.check(self.L.pf_kmerjoin_members_begin(self.h, 1)), call,
-                                (lambda: self._drain(write)) if write else None)
-
-    def _pass_plain(self, path, block_bytes, call, write):
-        def scan(buf, n):
-            used = C.c_uint64()
-            call((C.c_char * len(buf)).from_buffer(buf), n, used)
-            if write:
-                self._drain(write)
-            return int(used.value)
-
-        with open_table(path) as fh:
-            fh.readline()                            # the header line
-            scan_lines(fh, scan, block_bytes)
-
     def survey_file(self, path, block_bytes=None, device_gunzip=None):
         """one pass over kmers.tsv for all bunches: counters().  device_gunzip as RowFilter.filter_file's"""
         def members():
-            self.members[path] = self._pass_members(path, block_bytes, self.L.pf_kmerjoin_survey_members, (), None)
+            self.members[path] = self._members_pass(path, block_bytes, self.L.pf_kmerjoin_survey_members)
             return True if self.members[path] else None
 
         def host():
-            self._pass_plain(path, block_bytes, lambda ptr, n, used: _lib.check(self.L.pf_kmerjoin_survey(self.h, ptr, n, C.byref(used))), None)
+            self._plain_pass(path, block_bytes, self.L.pf_kmerjoin_survey)
             return True
 
         self.members[path] = False
@@ -330,16 +343,17 @@ class KmerJoin:
     def join_file(self, path, bunch, mode, write, block_bytes=None):
         """one pass over kmers.tsv for one bunch: its annotated rows (mode 0 / 1: the rendering) or its raw rows that have
         a key (KJ_RAW) go to write(), in file order.  The file goes the way the survey found for it."""
-        if self.members.get(path):
-            if not self._pass_members(path, block_bytes, self.L.pf_kmerjoin_join_members, (bunch, mode, C.byref(C.c_uint64())), write):
-                raise NotTaken(f"{path}: {self.L.pf_last_error().decode(errors='replace')} (the survey pass took the file)")
-            KmerJoin.device_gunzip_files += 1
-            return
+        args = (bunch, mode, C.byref(C.c_uint64()))
 
-        def call(ptr, n, used):
-            out_n = C.c_uint64()
-            _lib.check(self.L.pf_kmerjoin_join(self.h, ptr, n, bunch, mode, C.byref(out_n), C.byref(used)))
-        self._pass_plain(path, block_bytes, call, write)
+        def drain(_block=None):                      # the text the block's join call made, piece by piece
+            self._drain(self.L.pf_kmerjoin_next_text, write)
+
+        if not self.members.get(path):
+            self._plain_pass(path, block_bytes, self.L.pf_kmerjoin_join, args, drain)
+        elif self._members_pass(path, block_bytes, self.L.pf_kmerjoin_join_members, args, drain):
+            KmerJoin.device_gunzip_files += 1
+        else:
+            raise NotTaken(f"{path}: {self.L.pf_last_error().decode(errors='replace')} (the survey pass took the file)")
 
 
 AF_INT, AF_FLOAT, AF_NA, AF_ODD, AF_TEXT = 1, 2, 4, 8, 16
@@ -348,7 +362,7 @@ AF_FLAG_NAMES = ((1, "a row with another number of fields than the header"), (2,
 AF_MARGIN = 2.0 ** -30              # the device drops a row only above threshold + |threshold| * AF_MARGIN
 
 
-class AssocFilter:
+class AssocFilter(DeviceTable):
     """the data lines of an associations table whose cell in field `pvalue_field` may be <= threshold, kept on the device
     as they stand, with the classes of all cells per column and the rows' flags"""
 
@@ -357,24 +371,13 @@ class AssocFilter:
     device_gunzip_files = 0         # passes over a file that went the device gunzip route to their end
     fallback_files = 0              # and passes the automatic mode began there and read again through gzip
     last_stats = None               # stats() of the last table that had a device pass
+    entry = ("pf_assocfilter_create", "pf_assocfilter_destroy", "pf_assocfilter_members_begin", "pf_assocfilter_members_header")
 
     def __init__(self, pvalue_field, n_fields, threshold, device=0):
-        self.L = _lib.load()
-        self.h = C.c_void_p()
+        super().__init__()
         self.args = (int(device), int(pvalue_field), int(n_fields), float(threshold) + abs(float(threshold)) * AF_MARGIN)
         self.header = None              # the header line the device gunzip route peeled off
-        self._create()
-
-    def _create(self):
-        self.close()
-        _lib.check(self.L.pf_assocfilter_create(*self.args, C.byref(self.h)))
-
-    def close(self):
-        if self.h:
-            self.L.pf_assocfilter_destroy(self.h)
-            self.h = C.c_void_p()
-
-    __del__ = close
+        self._create(*self.args)
 
     def stats(self):
         st, ms = (C.c_uint64 * 4)(), (C.c_float * 2)()
@@ -390,25 +393,17 @@ class AssocFilter:
         _lib.check(self.L.pf_assocfilter_columns(self.h, C.byref(bits), C.byref(n), C.byref(flags), cnt))
         return {"classes": [int(bits[i]) for i in range(n.value)], "flags": int(flags.value), "rows": int(cnt[0]), "kept": int(cnt[1])}
 
-    def _drain(self, out):
-        piece, n = C.c_void_p(), C.c_uint64()
-        while True:
-            _lib.check(self.L.pf_assocfilter_next_lines(self.h, C.byref(piece), C.byref(n)))
-            if not n.value:
-                return
-            out.append(C.string_at(piece, n.value))
+    def _take(self, out):
+        """the kept lines of the last scan call, appended to `out`"""
+        self._drain(self.L.pf_assocfilter_next_lines, lambda piece: out.append(bytes(piece)))
 
     def scan_block(self, data, n=None):
         """(kept lines of the complete lines of `data` (bytes, or the first n bytes of a bytearray), joined; bytes consumed)"""
         kept, used, out = C.c_uint64(), C.c_uint64(), []
-        if isinstance(data, bytearray):
-            n = len(data) if n is None else n
-            ptr = (C.c_char * len(data)).from_buffer(data)          # no copy
-        else:
-            n, ptr = len(data), data
+        ptr, n = self._pointer(data, n)
         _lib.check(self.L.pf_assocfilter_scan(self.h, ptr, n, C.byref(kept), C.byref(used)))
         del ptr
-        self._drain(out)
+        self._take(out)
         return b"".join(out), int(used.value)
 
     def scan_members(self, data, last):
@@ -418,43 +413,28 @@ class AssocFilter:
         _lib.check(self.L.pf_assocfilter_scan_members(self.h, data, len(data), 1 if last else 0, C.byref(kept), C.byref(used),
                                                       C.byref(taken)))
         if taken.value:
-            self._drain(out)
+            self._take(out)
         return b"".join(out), int(used.value), bool(taken.value)
-
-    def _filter_members(self, path, block_bytes):
-        out = []
-
-        def call(data, last):
-            got, used, taken = self.scan_members(data, last)
-            out.append(got)
-            return used, taken
-
-        if not pass_member_file(path, block_bytes, lambda: _lib.check(self.L.pf_assocfilter_members_begin(self.h, 1)), call):
-            return None
-        line, n = C.c_void_p(), C.c_uint64()
-        _lib.check(self.L.pf_assocfilter_members_header(self.h, C.byref(line), C.byref(n)))
-        self.header = C.string_at(line, n.value) if n.value else b""
-        return b"".join(out)
-
-    def _filter_host(self, path, block_bytes):
-        out = []
-
-        def scan(buf, n):
-            got, used = self.scan_block(buf, n)
-            out.append(got)
-            return used
-
-        with open_table(path) as fh:
-            fh.readline()                            # the header line
-            scan_lines(fh, scan, block_bytes)
-        return b"".join(out)
 
     def filter_file(self, path, block_bytes=None, device_gunzip=None):
         """the kept data lines of a table file, joined; columns() then speaks of the whole file.  device_gunzip as
         RowFilter.filter_file's (a pass that stopped half way has ORed classes in: the filter is made anew before the file
         is read again)"""
-        return route_file(path, device_gunzip, lambda: self._filter_members(path, block_bytes),
-                          lambda: self._filter_host(path, block_bytes), AssocFilter, self._create)
+        args = (C.byref(C.c_uint64()),)
+
+        def members():                               # the kept lines, or None when a block was not taken
+            out = []
+            if not self._members_pass(path, block_bytes, self.L.pf_assocfilter_scan_members, args, lambda: self._take(out)):
+                return None
+            self.header = self._header()
+            return b"".join(out)
+
+        def host():
+            out = []
+            self._plain_pass(path, block_bytes, self.L.pf_assocfilter_scan, args, lambda _block: self._take(out))
+            return b"".join(out)
+
+        return route_file(path, device_gunzip, members, host, AssocFilter, lambda: self._create(*self.args))
 
 
 def assoc_header(line):
@@ -495,6 +475,7 @@ def assoc_plan(names, pvalue_field, classes, flags, rows):
 
 def assoc_table(header, kept, dtypes):
     """the kept lines as pandas reads them under the whole file's dtypes"""
+    import pandas as pd
     return pd.read_csv(io.BytesIO(header + kept), sep="\t", index_col=0, dtype=dtypes)
 
 
@@ -509,6 +490,7 @@ def rendered_texts(B, other_columns):
     makes pandas promote B's integer columns to float and its bool columns to object as an unmatched kmers.tsv row does
     (text1).  Keys that hold a NaN match no plain row and are left out.
     -> dict(keys, text0, text1, empty, header), or a str: why the device route cannot take this table"""
+    import pandas as pd
     keys = [k for k in B.index.tolist() if not (_isnan(k[0]) or _isnan(k[1]))]
     if len(set(keys)) != len(keys):
         return "the table has a (cluster, k-mer) twice"
@@ -578,6 +560,7 @@ def scan_lines(fh, scan, block_bytes=None):
 
 
 def _table(header, rows):
+    import pandas as pd
     return pd.read_csv(io.BytesIO(header + rows), sep="\t")
 
 
@@ -644,6 +627,7 @@ def _associations(args, index_name=None, scan=_device_scan):
     """the filtered associations table and the passing hashes (get_clusters.py:76-88, get_kmers.py:93-106).  The file goes
     through the device filter (`scan`) and pandas reads the kept lines under the dtypes of the whole file; it reads the
     whole file, as the reference does, when the pass says the two could differ or --host-associations asks for it"""
+    import pandas as pd
     a, why = None, "--host-associations"
     if not getattr(args, "host_associations", False):
         with open_table(args.associations) as fh:

@@ -23,7 +23,8 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import __version__
+from . import __version__, _lib
+from .downstream import GZ_BLOCK_DIVISOR, DeviceTable, open_table, route_file
 
 logger = logging.getLogger("panfeed")
 
@@ -134,7 +135,6 @@ def read_phenotype(path, phenotype_column=None, sample=None):
 
 def table_columns(path, column):
     """the column indices (cluster, strain, gene_start, k-mer, strand, `column`) from the table's header line"""
-    from .downstream import open_table
     with open_table(path) as fh:
         header = fh.readline().rstrip(b"\r\n").decode().split("\t")
     if column not in header:
@@ -196,88 +196,50 @@ for _b, _v in BASE2INT.items():
     _SCALAR[ord(_b)] = _v
 
 
-class GridBuilder:
+class GridBuilder(DeviceTable):
     """pf_plotgrid: the annotated table streamed through the device, then grids for batches of clusters"""
 
+    entry = ("pf_plotgrid_create", "pf_plotgrid_destroy", "pf_plotgrid_members_begin", "pf_plotgrid_members_header")
     device_gunzip_files = 0         # files, over all builders, that went the device gunzip route to their end
     fallback_files = 0              # and files the automatic mode began there and read again through gzip
 
     def __init__(self, strains, columns, start=None, stop=None, device=0):
-        from . import _lib
-        self._lib = _lib
-        self.L = _lib.load()
+        super().__init__()
         names = [str(s).encode() for s in strains]
         zoom = start is not None
-        self.args = (int(device), names, tuple(columns), 1 if zoom else 0, int(start) if zoom else 0, int(stop) if zoom else 0)
-        self.h = C.c_void_p()
+        arr, lens = _lib.c_strings(names)
+        self.args = (int(device), arr, lens, len(names), (C.c_int32 * 6)(*columns), 1 if zoom else 0, int(start) if zoom else 0,
+                     int(stop) if zoom else 0)
         self.fallbacks = 0              # files the automatic mode began on the device and read again through gzip
-        self._create()
+        self._create(*self.args)        # (and again, for an empty grid: _fell_back)
         self.n_strains = len(names)
-
-    def _create(self):
-        """a fresh handle: an empty grid"""
-        self.close()
-        device, names, columns, zoom, start, stop = self.args
-        arr, lens = self._lib.c_strings(names)
-        self._lib.check(self.L.pf_plotgrid_create(device, arr, lens, len(names), (C.c_int32 * 6)(*columns), zoom, start, stop,
-                                                  C.byref(self.h)))
-
-    def close(self):
-        if self.h:
-            self.L.pf_plotgrid_destroy(self.h)
-            self.h = C.c_void_p()
-
-    __del__ = close
-
-    def _scan_members(self, path, block_bytes):
-        """scan_file's device gunzip route: True, or None when a block was not taken"""
-        from .downstream import GZ_BLOCK_DIVISOR, pass_member_file
-
-        def call(data, last):
-            used, taken = C.c_uint64(), C.c_int()
-            self._lib.check(self.L.pf_plotgrid_scan_members(self.h, data, len(data), 1 if last else 0, C.byref(used), C.byref(taken)))
-            return used.value, taken.value
-
-        return pass_member_file(path, block_bytes or BLOCK_BYTES // GZ_BLOCK_DIVISOR,
-                                lambda: self._lib.check(self.L.pf_plotgrid_members_begin(self.h, 1)), call) or None
-
-    def _scan_host(self, path, block_bytes):
-        from .downstream import open_table, scan_lines
-
-        def scan(buf, n):
-            used = C.c_uint64()
-            ptr = (C.c_char * len(buf)).from_buffer(buf)
-            self._lib.check(self.L.pf_plotgrid_scan(self.h, ptr, n, C.byref(used)))
-            del ptr
-            return int(used.value)
-
-        with open_table(path) as fh:
-            fh.readline()
-            scan_lines(fh, scan, block_bytes or BLOCK_BYTES)
-        return True
 
     def _fell_back(self):
         """a file refused part-way has left rows in the grid: it starts over on an empty one"""
         self.fallbacks += 1
-        self._create()
+        self._create(*self.args)
 
     def scan_file(self, path, block_bytes=None, device_gunzip=None):
         """The data lines of the annotated table into the grid.  A .gz made of small members with the plain gzip header is
         inflated on the device and scanned there, as device_gunzip says (downstream.route_file: None tries it for such a
         file and reads the file again through gzip when a block is not taken, True raises NotTaken then, False never
         tries); block_bytes then counts compressed bytes.  Any other file is read block by block through the host."""
-        from .downstream import route_file
-        route_file(path, device_gunzip, lambda: self._scan_members(path, block_bytes), lambda: self._scan_host(path, block_bytes),
-                   GridBuilder, self._fell_back)
+        def members():                               # True, or None when a block was not taken
+            return self._members_pass(path, block_bytes or BLOCK_BYTES // GZ_BLOCK_DIVISOR, self.L.pf_plotgrid_scan_members) or None
+
+        def host():
+            self._plain_pass(path, block_bytes or BLOCK_BYTES, self.L.pf_plotgrid_scan)
+            return True
+
+        route_file(path, device_gunzip, members, host, GridBuilder, self._fell_back)
 
     def finish(self):
         nc, npv, nr = C.c_uint32(), C.c_uint64(), C.c_uint64()
-        self._lib.check(self.L.pf_plotgrid_finish(self.h, C.byref(nc), C.byref(npv), C.byref(nr)))
+        _lib.check(self.L.pf_plotgrid_finish(self.h, C.byref(nc), C.byref(npv), C.byref(nr)))
         nc, npv = int(nc.value), int(npv.value)
         names, off = C.c_void_p(), C.POINTER(C.c_uint64)()
         mn, mx, rows = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_uint64)()
-        self._lib.check(self.L.pf_plotgrid_clusters(self.h, C.byref(names), C.byref(off), C.byref(mn), C.byref(mx),
-                                                    C.byref(rows)))
+        _lib.check(self.L.pf_plotgrid_clusters(self.h, C.byref(names), C.byref(off), C.byref(mn), C.byref(mx), C.byref(rows)))
         offs = np.ctypeslib.as_array(off, (nc + 1,)).copy() if nc else np.zeros(1, np.uint64)
         raw = C.string_at(names, int(offs[-1])) if nc else b""
         self.clusters = [raw[offs[i]:offs[i + 1]].decode() for i in range(nc)]
@@ -285,7 +247,7 @@ class GridBuilder:
         self.max = np.ctypeslib.as_array(mx, (nc,)).copy() if nc else np.zeros(0, np.int32)
         self.rows = np.ctypeslib.as_array(rows, (nc,)).copy() if nc else np.zeros(0, np.uint64)
         texts, toff = C.c_void_p(), C.POINTER(C.c_uint64)()
-        self._lib.check(self.L.pf_plotgrid_pvalues(self.h, C.byref(texts), C.byref(toff)))
+        _lib.check(self.L.pf_plotgrid_pvalues(self.h, C.byref(texts), C.byref(toff)))
         to = np.ctypeslib.as_array(toff, (npv + 1,)).copy() if npv else np.zeros(1, np.uint64)
         raw = C.string_at(texts, int(to[-1])) if npv else b""
         self.pvalue_texts = [raw[to[i]:to[i + 1]] for i in range(npv)]
@@ -293,7 +255,7 @@ class GridBuilder:
 
     def set_significance(self, sig):
         keys = np.ascontiguousarray(_keys(sig), dtype=np.uint64)
-        self._lib.check(self.L.pf_plotgrid_set_significance(self.h, keys.ctypes.data if len(keys) else None))
+        _lib.check(self.L.pf_plotgrid_set_significance(self.h, keys.ctypes.data if len(keys) else None))
 
     def width(self, i):
         return int(self.max[i]) - int(self.min[i]) + 1
@@ -305,7 +267,7 @@ class GridBuilder:
         key = np.empty(cells, np.uint64)
         cnt = np.empty(cells, np.uint64)
         idarr = np.asarray(ids, dtype=np.uint32)
-        self._lib.check(self.L.pf_plotgrid_grids(self.h, idarr.ctypes.data, len(ids), key.ctypes.data, cnt.ctypes.data))
+        _lib.check(self.L.pf_plotgrid_grids(self.h, idarr.ctypes.data, len(ids), key.ctypes.data, cnt.ctypes.data))
         out, o = [], 0
         for w in widths:
             n = w * self.n_strains
@@ -315,9 +277,9 @@ class GridBuilder:
 
     def stats(self):
         b, ln, r, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
-        self._lib.check(self.L.pf_plotgrid_stats(self.h, C.byref(b), C.byref(ln), C.byref(r), C.byref(ms)))
+        _lib.check(self.L.pf_plotgrid_stats(self.h, C.byref(b), C.byref(ln), C.byref(r), C.byref(ms)))
         gm, gt, gms, gdev = C.c_uint64(), C.c_uint64(), C.c_float(), C.c_uint64()
-        self._lib.check(self.L.pf_plotgrid_gunzip_stats(self.h, C.byref(gm), C.byref(gt), C.byref(gms), C.byref(gdev)))
+        _lib.check(self.L.pf_plotgrid_gunzip_stats(self.h, C.byref(gm), C.byref(gt), C.byref(gms), C.byref(gdev)))
         return {"bytes_scanned": int(b.value), "lines": int(ln.value), "records": int(r.value),
                 "device_ms": float(ms.value),
                 "members_inflated": int(gm.value), "text_bytes_inflated": int(gt.value), "inflate_ms": float(gms.value),

@@ -284,6 +284,106 @@ def test_handmade_table_in_many_blocks(tmp_path):
         downstream.BLOCK_BYTES = old
 
 
+TILE, SPAN = 1 << 16, 256      # bytes of the text a workgroup and a thread of the join's plan and place kernels own
+
+
+def _tile_end_table():
+    """kmers.tsv of about 200 KB: rows of cluster `sel` (bunch 0; its k-mer ACG is a key, TTT is not) placed by the byte among
+    rows of `oth` (bunch 1) and `zz` (not selected).  The plain route's block is the body and the member route's the whole
+    file, so every placement is made twice, for a block that starts 0 and len(header) bytes in front of the body"""
+    head = len(jt.KMERS_HEADER)
+    rows, at = [], 0
+
+    def put(cluster, length=None):                   # a row, of exactly `length` bytes with its newline if given
+        nonlocal at
+        i = len(rows)
+        row = jt.kmers_row(cluster, "ACG" if i % 2 else "TTT", i, strain="s" if length else None)
+        if length:
+            row = jt.kmers_row(cluster, "ACG" if i % 2 else "TTT", i, strain="s" * (length - len(row)))
+        rows.append(row)
+        at += len(row) + 1
+
+    def fill_to(target):                             # rows of the other bunch and of no bunch, up to exactly `target`
+        while at < target:
+            put(("oth", "zz")[len(rows) % 2], None if target - at >= 400 else target - at)
+        assert at == target
+
+    for _ in range(3):                               # three rows of the bunch in the first thread's 256 bytes
+        put("sel")
+    # at a multiple of 256, of 16 and of 4, each for the block that is the body and for the one with the header in front
+    for target in (4096, 8192 - head, 12288 + 16, 16384 + 16 - head, 20480 + 4, 24576 + 4 - head):
+        fill_to(target)
+        put("sel")
+    fill_to(TILE - 150)
+    put("sel", 150)                                  # ends at the first tile end: behind the header it straddles it
+    put("sel")                                       # starts at it
+    fill_to(2 * TILE - head)
+    put("sel", 150)                                  # behind the header it starts at the second tile end; alone it straddles it
+    fill_to(3 * TILE + 1000)                         # (no row of the bunch in the third tile)
+    for _ in range(3):
+        put("sel")
+    return jt.KMERS_HEADER, b"".join(r + b"\n" for r in rows)
+
+
+def _assert_line_starts(body, shift):
+    """the places test_rows_of_a_bunch_at_tile_ends is about, in a block that begins `shift` bytes in front of the body"""
+    from collections import Counter
+    every, at = [], shift
+    for row in body.split(b"\n")[:-1]:
+        every.append((at, len(row) + 1, row.startswith(b"sel\t")))
+        at += len(row) + 1
+    sel = [(b, n) for b, n, mine in every if mine]
+    assert ((at + 15) // 16 + 4095) // 4096 == 4                           # four tiles, ends at 65 536, 131 072 and 196 608
+    assert any(b % TILE == 0 for b, _ in sel)                              # at a tile end
+    assert any(b % SPAN == 0 and b % TILE for b, _ in sel)                 # at the start of a thread's span
+    assert any(b % 16 == 0 and b % SPAN for b, _ in sel)
+    assert any(b % 4 == 0 and b % 16 for b, _ in sel)
+    assert any(b < t < b + n - 1 for b, n in sel for t in (TILE, 2 * TILE, 3 * TILE))       # a tile end in its middle
+    # a line is its owner's by the newline in front of it (the block's first by its start)
+    own_sel = Counter(max(b - 1, 0) // SPAN for b, _ in sel)
+    own_any = {max(b - 1, 0) // SPAN for b, _, _ in every}
+    assert max(own_sel.values()) >= 2 and own_any - set(own_sel)
+    assert set(range(4)) - {span * SPAN // TILE for span in own_sel}       # a whole tile without a row of the bunch
+
+
+def test_rows_of_a_bunch_at_tile_ends(tmp_path, eng):
+    """One block of four tiles, by both routes and in the three modes: rows of the bunch that start at a tile end, at the
+    start of a thread's span, at a multiple of 16 and of 4, one with a tile end in its middle, a thread with three of them,
+    threads and a whole tile with none.  The join's place pass puts every row where the plan pass counted it; the text is the
+    model's and the same by both routes"""
+    from panfeed_amd import _lib
+    from panfeed_amd.downstream import KJ_RAW, KmerJoin
+    header, body = _tile_end_table()
+    for shift in (0, len(header)):
+        _assert_line_starts(body, shift)
+    plain, gz = str(tmp_path / "kmers.tsv"), str(tmp_path / "kmers.tsv.gz")
+    with open(plain, "wb") as fh:
+        fh.write(header + body)
+    write_device_gz(eng, gz, header, body)
+    block = 1 << 18
+    assert len(header + body) <= block
+    rows, key = jt.rows_of(header + body), (b"sel", b"ACG")
+    want = {0: jt.join_rows(rows, {b"sel"}, {key: b"t0"}, b""), 1: jt.join_rows(rows, {b"sel"}, {key: b"t1.0"}, b""),
+            KJ_RAW: jt.kept_rows(rows, {b"sel"}, {key})}
+    assert 0 < len(want[KJ_RAW]) < len(want[0]) < len(want[1])
+    kj = KmerJoin([(b"sel", 0), (b"oth", 1)], 2, [key], [b"t0"], [b"t1.0"], b"")
+    try:
+        got = {}
+        for path, route in ((plain, False), (gz, True)):
+            plan = kj.survey_file(path, block_bytes=block, device_gunzip=route)
+            assert plan[0]["flags"] == 0 and plan[0]["rows"] == len(want[0].splitlines()) and bool(kj.members[path]) == route
+            for mode in (0, 1, KJ_RAW):
+                out = []
+                kj.join_file(path, 0, mode, lambda piece: out.append(bytes(piece)), block_bytes=block)
+                got[route, mode] = b"".join(out)
+                assert got[route, mode] == want[mode], (route, mode)
+            _lib.check(kj.L.pf_kmerjoin_reset_counters(kj.h))       # (the next survey counts from nothing)
+        assert all(got[False, mode] == got[True, mode] for mode in (0, 1, KJ_RAW))
+        assert kj.stats()["members_inflated"] >= 4 * 4                    # four passes over the members of four tiles of text
+    finally:
+        kj.close()
+
+
 @pytest.mark.parametrize("n", [4095, 4096])
 def test_long_fields(tmp_path, n):
     """a strain of 4 095 bytes is a field like any other; one of 4 096 sends its bunch through pandas"""
