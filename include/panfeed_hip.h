@@ -511,13 +511,21 @@ int pf_kmers_tsv_stream_begin(pf_ctx* ctx, const pf_target_seq* seqs, uint32_t n
 /* The next block of that text (at most 64 MiB) in pinned host memory owned by the context, valid until the next call;
  * the block after it is already being copied.  *nbytes == 0 at the end (the stream is then over). */
 int pf_kmers_tsv_stream_next(pf_ctx* ctx, const char** ptr, uint64_t* nbytes);
+/* Where the rows of each of the n target sequences given to the last pf_render_kmers_tsv_device or
+ * pf_kmers_tsv_stream_begin end in the whole text: ends[i] is the offset just behind sequence i's rows (a sequence with
+ * no window repeats the end before it; ends[n - 1] is the text's size).  The caller cuts the text where its sequences
+ * change cluster (panfeed.py:104-110, 225-226 under multiple_files).  Valid until the next pf_submit or the next of
+ * those two calls, also after the stream has ended.  n must be that call's n (else PF_ERR_ARG); PF_ERR_STATE when
+ * there is no such text. */
+int pf_kmers_tsv_seq_ends(pf_ctx* ctx, uint64_t* ends, uint32_t n);
 
 /* The bodies of kmers_to_hashes.tsv and hashes_to_patterns.tsv of the last pf_submit written ON THE DEVICE
  * (panfeed.py:177,208 and :181-187,217-223): rows assembled in LDS, coalesced stores, one copy to pinned host memory.
  * No pf_fetch needed; the k-mer keys and pattern rows never cross PCIe, only the text does.  names: cluster names in
  * batch order; extra_keys: n_extra * klength bytes, the k-mer text of the batch's slow-path rows (NULL if none).
  * *kh / *hp point into pinned memory owned by the context (two blocks used alternately): valid until the call after
- * the next one, so that a writer thread can still be on the previous batch.  Not under multiple_files. */
+ * the next one, so that a writer thread can still be on the previous batch.  Not under multiple_files
+ * (PF_ERR_ARG): pf_render_device_clusters is the call for that. */
 int pf_render_device(pf_ctx* ctx, const char* const* names, const char* extra_keys, uint64_t n_extra,
                      const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes);
 /* Same with flags: PF_RENDER_NO_PATTERN_ROWS leaves hashes_to_patterns.tsv out (*hp_bytes = 0) -- a rank of a
@@ -525,6 +533,17 @@ int pf_render_device(pf_ctx* ctx, const char* const* names, const char* extra_ke
 #define PF_RENDER_NO_PATTERN_ROWS 1u
 int pf_render_device_ex(pf_ctx* ctx, const char* const* names, const char* extra_keys, uint64_t n_extra, uint32_t flags,
                         const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes);
+/* pf_render_device for a context made with multiple_files (panfeed.py:35-43, 159-167: one directory per gene cluster):
+ * the same two bodies, written by the same kernels in one pair of launches, plus where to cut them into the clusters'
+ * files.  kh_end / hp_end: caller arrays of n_clusters entries.  kh_end[i] is the offset just behind cluster i's rows in
+ * *kh; hp_end[i] the offset just behind the rows of the patterns first seen in cluster i in *hp (the pattern set
+ * starts empty in every cluster, and a batch's new patterns in first-seen order stand cluster by cluster).  A cluster
+ * without rows repeats the end before it; the last ends are *kh_bytes and *hp_bytes.  Bodies only: the files' header
+ * lines are the caller's.  Pinned-block lifetime and errors as pf_render_device (PF_ERR_CAPACITY: too many passes,
+ * PF_ERR_ARG: an over-long cluster name -- the host renderers take such a batch); PF_ERR_ARG without multiple_files. */
+int pf_render_device_clusters(pf_ctx* ctx, const char* const* names, const char* extra_keys, uint64_t n_extra,
+                              const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes,
+                              uint64_t* kh_end, uint64_t* hp_end);
 /* Rows of hashes_to_patterns.tsv ("hash\tv0\tv1...\n", panfeed.py:181-187, 217-223) for ANY patterns of the
  * run-global pool, in the order given, written on the device: pids[n] are pattern ids (< pf_pattern_count).  The
  * multi-GPU driver calls it after pf_merge_patterns with the ids whose first_seen is the global minimum of their

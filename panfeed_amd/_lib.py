@@ -139,7 +139,7 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_merge_patterns", "pf_merge_patterns_padded", "pf_pattern_count", "pf_debug_limit_pattern_slots", "pf_debug_limit_alloc", "pf_debug_read_words", "pf_debug_cluster_routes", "pf_result_checksum", "pf_dev_alloc", "pf_dev_free",
            "pf_dev_upload", "pf_dev_download", "pf_synth_expand", "pf_pack_acgt", "pf_b64_digest",
            "pf_render_kmers_to_hashes", "pf_render_hashes_to_patterns", "pf_render_kmers_tsv", "pf_render_kmers_tsv_device", "pf_device_text_chunk", "pf_free_text",
-           "pf_kmers_tsv_stream_begin", "pf_kmers_tsv_stream_next",
+           "pf_kmers_tsv_stream_begin", "pf_kmers_tsv_stream_next", "pf_kmers_tsv_seq_ends", "pf_render_device_clusters",
            "pf_pattern_rows_stream_begin", "pf_pattern_rows_stream_next",
            "pf_pack_records", "pf_packed_view", "pf_packed_free",
            "pf_pangenome_open", "pf_pangenome_open_device", "pf_pangenome_open_device_cb", "pf_debug_open_hostsink", "pf_pangenome_close", "pf_pangenome_info", "pf_pangenome_strain",
@@ -270,6 +270,10 @@ def _load_locked():
     L.pf_render_device_ex.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_char_p, C.c_uint64, C.c_uint32,
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_uint64)]
+    L.pf_render_device_clusters.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                            C.c_void_p, C.c_void_p]
+    L.pf_kmers_tsv_seq_ends.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.pf_render_pattern_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pf_pattern_rows_stream_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
                                                C.POINTER(C.c_uint32)]

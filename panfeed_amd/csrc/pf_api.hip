@@ -212,6 +212,7 @@ struct KtHostText {
 struct KtPlan {
     struct Range { uint32_t t0, t1, h0, h1; uint64_t base, bytes; };   // tiles [t0, t1), host sequences [h0, h1)
     std::vector<uint64_t> toff, hoff;
+    std::vector<uint64_t> seq_end;       // per sequence given: the offset just behind its rows (no window: the end before)
     std::vector<Range> ranges;
     uint64_t total = 0, cap = 0, max_unit = 0, max_range = 0, peak = 0;   // peak: of two neighbouring ranges
 };
@@ -241,6 +242,10 @@ struct TargetText {
     // the one block on its way, on `side`: n bytes from `off` of the text into pins[slot] -- or, a stream's block under
     // device gzip, their members into GzMode::block_members[slot], the members' size into the slot's pinned cursor word
     struct { bool valid = false; int slot = 0; uint64_t off = 0, n = 0; } flight;
+    // pf_kmers_tsv_seq_ends: the offset behind every sequence's rows in the last text planned (kt_plan), kept beyond the
+    // stream's end; gone with the next pf_submit
+    std::vector<uint64_t> seq_end;
+    bool have_seq_end = false;
     struct Stream {
         bool active = false;
         std::vector<pf_target_seq> hseqs;      // the host-rendered sequences (the caller's strings, until the stream ends)
@@ -1914,6 +1919,7 @@ struct SubmitRun {
 
 int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* counters, uint64_t* need, bool rerun) {
     c->have_batch = false;
+    c->kt.have_seq_end = false;
     kt_stream_end(c);                     // a kmers.tsv stream of the batch before is over,
     pr_stream_end(c);                     // and so is a stream of pattern rows
     // whatever way this call ends, nothing it queued is still reading the caller's arrays or the pinned staging
@@ -2458,7 +2464,7 @@ int kt_host_sso(pf_ctx* c, std::vector<uint32_t>& sso) {
 void kt_plan(const KtLayout& L, const std::vector<uint64_t>& hsizes, uint64_t budget, KtPlan& P) {
     const size_t NT = L.tiles.size(), NH = L.host_idx.size();
     P = KtPlan{};
-    P.toff.resize(NT); P.hoff.resize(NH);
+    P.toff.resize(NT); P.hoff.resize(NH); P.seq_end.resize(L.on_dev.size());
     const uint64_t all = std::accumulate(L.tbytes.begin(), L.tbytes.end(), (uint64_t)0) + std::accumulate(hsizes.begin(), hsizes.end(), (uint64_t)0);
     P.cap = all + 64 <= budget ? all : (budget / 2 > 64 ? budget / 2 - 64 : 0);
     KtPlan::Range cur{0, 0, 0, 0, 0, 0};
@@ -2481,6 +2487,7 @@ void kt_plan(const KtLayout& L, const std::vector<uint64_t>& hsizes, uint64_t bu
             unit(hsizes[hi], P.hoff[hi]);
             cur.h1 = (uint32_t)++hi;
         }
+        P.seq_end[i] = cur.base + cur.bytes;
     }
     if (cur.bytes) P.ranges.push_back(cur);
     P.total = cur.base + cur.bytes;
@@ -2538,6 +2545,7 @@ int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget, b
     kt_stream_end(c);
     pr_stream_end(c);                              // (a stream of pattern rows has these buffers)
     c->kt.bytes = 0;                               // (pf_device_text_chunk's text is gone: the buffers are reused)
+    c->kt.have_seq_end = false;
     TargetText::Stream& S = c->kt.stream;
     S.active = true;
     struct Guard { pf_ctx* c; bool ok; ~Guard() { if (!ok) kt_stream_end(c); } } guard{c, false};
@@ -2570,6 +2578,8 @@ int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget, b
     S.cur = 0; S.cur_off = 0;
     S.pin_bytes = std::max<uint64_t>(1, std::min(KT_BLOCK, P.max_range));
     for (uint32_t r = 0; r < std::min(NR, 2u); r++) PFCHK(kt_produce(c, r));
+    c->kt.seq_end.swap(S.plan.seq_end);            // (the plan goes with the stream; the ends stay until the next submit)
+    c->kt.have_seq_end = true;
     guard.ok = true;
     return PF_OK;
 }
@@ -2700,6 +2710,16 @@ int pf_kmers_tsv_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
     if (arrival) HIPCHK(hipEventSynchronize(arrival));
     *ptr = c->kt.pins[slot].as<char>();
     *nbytes = n;
+    return PF_OK;
+}
+
+int pf_kmers_tsv_seq_ends(pf_ctx* c, uint64_t* ends, uint32_t n) {
+    if (!c || (n && !ends)) return fail(PF_ERR_ARG, "pf_kmers_tsv_seq_ends: null argument");
+    if (!c->have_batch || !c->kt.have_seq_end)
+        return fail(PF_ERR_STATE, "pf_kmers_tsv_seq_ends without a pf_render_kmers_tsv_device or pf_kmers_tsv_stream_begin since the last pf_submit");
+    if ((size_t)n != c->kt.seq_end.size())
+        return fail(PF_ERR_ARG, "pf_kmers_tsv_seq_ends: %u sequences asked for, the text was planned for %zu", n, c->kt.seq_end.size());
+    if (n) memcpy(ends, c->kt.seq_end.data(), (size_t)n * 8);
     return PF_OK;
 }
 
@@ -3358,6 +3378,9 @@ struct RenderLayout {
     uint64_t kh_n = 0, hp_n = 0, hp_at = 0;        // the two texts' bytes; the second starts 256-byte aligned
     size_t o_text = 0, o_koff = 0, o_rowoff = 0, o_name = 0, o_kcnt = 0, o_arena = 0, o_bc = 0, o_br = 0, o_order = 0, o_blob = 0, o_extra = 0;
     std::vector<char> meta;
+    // multiple_files (cluster_ends asked for): per cluster, the offset behind its rows in each text
+    bool cluster_ends = false;
+    std::vector<uint64_t> kh_end, hp_end;
 };
 int render_layout(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra, bool want_hp, RenderLayout& L) {
     const uint32_t C = L.C = c->n_clusters, k = c->o.klength;
@@ -3379,6 +3402,8 @@ int render_layout(pf_ctx* c, const char* const* names, const char* extra_keys, u
         HIPCHK(hipMemcpyAsync(fs.data(), c->pt.first_seen + p0, (size_t)P * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(rlen.data(), d_rlen.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
     }
+    uint64_t ord0 = 0;                             // the batch's first ordinal: first_seen >> 32 counts from it
+    if (L.cluster_ends && C) HIPCHK(hipMemcpyAsync(&ord0, c->last.cluster_ordinal, 8, hipMemcpyDeviceToHost, st));
     PFCHK(ensure_b64_dev(c));
     HIPCHK(hipStreamSynchronize(st));
     // ---- kmers_to_hashes layout: rows per cluster, workgroups per cluster
@@ -3405,7 +3430,21 @@ int render_layout(pf_ctx* c, const char* const* names, const char* extra_keys, u
     std::iota(order.begin(), order.end(), 0u);
     std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return fs[x] < fs[y]; });
     std::vector<uint64_t> row_off(P + 1, 0);
-    for (uint32_t i = 0; i < P; i++) { row_off[i + 1] = row_off[i] + rlen[order[i]]; order[i] += p0; }
+    if (L.cluster_ends) {
+        // the new patterns in first-seen order (ordinal << 32 | rank) stand cluster by cluster: cut where the ordinal changes
+        L.kh_end.assign(text_off.begin() + 1, text_off.end());
+        L.hp_end.assign(C, 0);
+        uint32_t ci = 0;
+        for (uint32_t i = 0; i < P; i++) {
+            const uint64_t at = (uint32_t)((fs[order[i]] >> 32) - ord0);     // (the ordinal's low 32 bits are in first_seen)
+            if (at >= C || at < ci) return fail(PF_ERR_STATE, "a pattern's first_seen names no cluster of this batch");
+            for (; ci < at; ci++) L.hp_end[ci] = row_off[i];
+            row_off[i + 1] = row_off[i] + rlen[order[i]];
+        }
+        for (; ci < C; ci++) L.hp_end[ci] = row_off[P];
+        for (uint32_t i = 0; i < P; i++) order[i] += p0;
+    } else
+        for (uint32_t i = 0; i < P; i++) { row_off[i + 1] = row_off[i] + rlen[order[i]]; order[i] += p0; }
     L.kh_n = text_off[C]; L.hp_n = row_off[P];
     L.hp_at = (L.kh_n + 255) & ~(uint64_t)255;
     // ---- one block of tables for both kernels
@@ -3490,21 +3529,47 @@ int render_handout(pf_ctx* c, Span text0, Span text1, Span* out0, Span* out1) {
 }
 }  // namespace
 
-int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra, uint32_t flags,
-                        const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes) {
-    if (!c || !kh || !kh_bytes || !hp || !hp_bytes) return fail(PF_ERR_ARG, "pf_render_device: null argument");
+namespace {
+// pf_render_device_ex and pf_render_device_clusters behind their own checks: the layout (L.cluster_ends set by the
+// caller), the two launches, the hand-out
+int render_device(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra, bool want_hp, RenderLayout& L,
+                  const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes) {
     if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_device needs a successful pf_submit");
-    if (c->o.multiple_files) return fail(PF_ERR_ARG, "pf_render_device writes one pair of texts per batch; use the host renderers under multiple_files");
     HIPCHK(hipSetDevice(c->device));
     if (c->n_clusters && !names) return fail(PF_ERR_ARG, "pf_render_device: cluster names missing");
     if (c->n_passes > pf::TEXT_MAX_ARENAS) return fail(PF_ERR_CAPACITY, "pf_render_device: too many passes (%u)", c->n_passes);
-    RenderLayout L;
-    PFCHK(render_layout(c, names, extra_keys, n_extra, !(flags & PF_RENDER_NO_PATTERN_ROWS), L));
+    PFCHK(render_layout(c, names, extra_keys, n_extra, want_hp, L));
     PFCHK(render_launch(c, L));
     Span out0, out1;
     PFCHK(render_handout(c, Span{c->txt.dev.as<char>(), L.kh_n}, Span{c->txt.dev.as<char>() + L.hp_at, L.hp_n}, &out0, &out1));
     *kh = out0.p; *kh_bytes = out0.n;
     *hp = out1.p; *hp_bytes = out1.n;
+    return PF_OK;
+}
+}  // namespace
+
+int pf_render_device_ex(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra, uint32_t flags,
+                        const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes) {
+    if (!c || !kh || !kh_bytes || !hp || !hp_bytes) return fail(PF_ERR_ARG, "pf_render_device: null argument");
+    if (c->have_batch && c->o.multiple_files) return fail(PF_ERR_ARG, "pf_render_device writes one pair of texts per batch; pf_render_device_clusters says where to cut them under multiple_files");
+    RenderLayout L;
+    return render_device(c, names, extra_keys, n_extra, !(flags & PF_RENDER_NO_PATTERN_ROWS), L, kh, kh_bytes, hp, hp_bytes);
+}
+
+int pf_render_device_clusters(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra,
+                              const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes,
+                              uint64_t* kh_end, uint64_t* hp_end) {
+    if (!c || !kh || !kh_bytes || !hp || !hp_bytes) return fail(PF_ERR_ARG, "pf_render_device_clusters: null argument");
+    if (!c->o.multiple_files) return fail(PF_ERR_ARG, "pf_render_device_clusters is for a context made with multiple_files; pf_render_device otherwise");
+    if (c->have_batch && c->n_clusters && (!kh_end || !hp_end)) return fail(PF_ERR_ARG, "pf_render_device_clusters: null argument");
+    if (c->gz.on) return fail(PF_ERR_STATE, "pf_render_device_clusters hands out text, not gzip members: the clusters' files are cut from it");
+    RenderLayout L;
+    L.cluster_ends = true;
+    PFCHK(render_device(c, names, extra_keys, n_extra, true, L, kh, kh_bytes, hp, hp_bytes));
+    if (c->n_clusters) {
+        memcpy(kh_end, L.kh_end.data(), (size_t)c->n_clusters * 8);
+        memcpy(hp_end, L.hp_end.data(), (size_t)c->n_clusters * 8);
+    }
     return PF_OK;
 }
 

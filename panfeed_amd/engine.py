@@ -137,7 +137,9 @@ class BatchOutput:
         self.kmers_tsv = ""
         self.kmers_to_hashes = ""
         self.hashes_to_patterns = ""
-        self.per_cluster = []   # multiple_files: [(idx, kmers_tsv, kmers_to_hashes, hashes_to_patterns)]
+        # multiple_files: [(idx, kmers_tsv, kmers_to_hashes, hashes_to_patterns)], str or slices of the device-written
+        # bodies; kmers_tsv None: the rows went to run_batches' cluster_targets_sink
+        self.per_cluster = []
         self.stats = {}
         self.timing = {}
 
@@ -152,6 +154,15 @@ def _batch_stats(hb, res, patterns, **streamed):
     return {"clusters": int(hb.n_clusters), "instances": int(hb.n_instances), **streamed,
             "device_instances": int(res.n_instances), "unique_kmers": int(res.n_unique), "kept_kmers": int(res.n_kept),
             "new_patterns": int(res.n_new_patterns), "patterns": int(patterns)}
+
+
+def _cut(view, ends):
+    """`view` cut at the offsets `ends` (non-decreasing, the last one its length): one slice per end, no copy"""
+    parts, prev = [], 0
+    for e in ends:
+        parts.append(view[prev:int(e)])
+        prev = int(e)
+    return parts
 
 
 def add_batch_stats(totals, out, keys=("clusters", "instances", "kept_kmers", "device_ms")):
@@ -187,7 +198,8 @@ class Engine:
         self.ctx = C.c_void_p()
         _lib.check(self.L.pf_create(C.byref(self.ctx), int(device), C.byref(o)))
         # device_gzip: the texts the GPU writes (render_device, stream_targets_device) leave it as gzip members; the host
-        # renderers, and with them every --multiple-files run, are not affected
+        # renderers are not affected, nor is a --multiple-files run: its device text is cut into the clusters' files, whose
+        # gzip stays the host's
         self.device_gzip = bool(device_gzip) and not self.multiple_files
         if self.device_gzip:
             _lib.check(self.L.pf_set_device_gzip(self.ctx, 1, int(device_gzip_flags)))
@@ -261,7 +273,7 @@ class Engine:
         return self._render(hb, res)
 
     def run_stream(self, records, batch_clusters=256, prefetch=2, defer_patterns=False, device_text=False,
-                   targets_sink=None):
+                   targets_sink=None, cluster_targets_sink=None):
         """Generator over BatchOutput: packs batch i+1 (host threads, pf_pack_records) while the GPU works on
         batch i and the caller writes batch i-1 -- the reference's reader / workers / writer pipeline
         (__main__.py:39-81,299-344) with the GPU in the workers' place and a deterministic order
@@ -279,10 +291,10 @@ class Engine:
                 yield build_batch_native(chunk, self.k, self.canon, self.W, stroi=self.stroi, first_ordinal=ordinal)
                 ordinal += len(chunk)
         return self.run_batches(host_batches(), prefetch, device_text, defer_patterns=defer_patterns,
-                                targets_sink=targets_sink)
+                                targets_sink=targets_sink, cluster_targets_sink=cluster_targets_sink)
 
     def run_pangenome(self, pangenome, batch_clusters=256, prefetch=2, device_text=False, defer_patterns=False,
-                      before_first_submit=None, targets_sink=None):
+                      before_first_submit=None, targets_sink=None, cluster_targets_sink=None):
         """run_stream fed by the native reader (native_input.Pangenome): table rows -> records -> packed batches
         without leaving the library, then the GPU; yields BatchOutput in table order."""
         if tuple(sorted(pangenome.targets)) != tuple(sorted(self.stroi or ())):
@@ -290,14 +302,17 @@ class Engine:
         return self.run_batches(pangenome.batches(self.k, self.canon, self.W, max_clusters=batch_clusters,
                                                   first_ordinal=self.next_ordinal), prefetch, device_text,
                                 defer_patterns=defer_patterns, before_first_submit=before_first_submit,
-                                targets_sink=targets_sink)
+                                targets_sink=targets_sink, cluster_targets_sink=cluster_targets_sink)
 
     def run_batches(self, host_batches, prefetch=2, device_text=False, defer_patterns=False, before_first_submit=None,
-                    targets_sink=None):
+                    targets_sink=None, cluster_targets_sink=None):
         """GPU over an iterator of HostBatch, the next ones being prepared on one host thread meanwhile.
         device_text: kmers_to_hashes / hashes_to_patterns of a batch without target-strain rows come back as
         memoryviews of text the GPU wrote (render_device; valid until the batch after the next one has been rendered)
-        instead of str; batches with kmers.tsv rows and --multiple-files runs keep the host renderers.
+        instead of str.  Under multiple_files the same two bodies come with their cluster boundaries
+        (render_device_clusters): `out.per_cluster[i] = (idx, kt, kh_i, hp_i)` holds slices of them, and
+        `out.stats["device_cluster_files"]` says for how many of the batch's clusters (0: the batch fell back to the host
+        renderers).
         defer_patterns: leave hashes_to_patterns empty -- a rank of a sharded run renders its pattern rows after the
         run-global merge (`render_pattern_rows`).
         before_first_submit: called once, right before the first pf_submit (pipeline.run_files joins the thread that
@@ -308,7 +323,11 @@ class Engine:
         samples = 150 GB), which neither a host buffer nor one device buffer should hold: the GPU writes them in ranges of
         at most `targets_text_budget` bytes of device memory (stream_targets_device); `out.stats["kmers_tsv_streamed"]`
         says how many bytes went, `"kmers_tsv_ranges"` / `"kmers_tsv_peak_device_bytes"` in how many ranges and with how
-        much device memory at most."""
+        much device memory at most.
+        cluster_targets_sink (multiple_files): called as `sink(idx, block)` with the kmers.tsv rows of cluster `idx` -- at
+        least once for every cluster of a batch, in order, with an empty block where a cluster has no target row -- instead
+        of the rows standing in `out.per_cluster` (their place holds None).  With device_text the rows are streamed within
+        `targets_text_budget` like targets_sink's and cut at the cluster ends as they arrive (output.ClusterSplitter)."""
         from concurrent.futures import ThreadPoolExecutor
         it = iter(host_batches)
         # where the wall time of this run goes (seconds; bench.py's end-to-end leg): the packer thread's busy time
@@ -344,15 +363,17 @@ class Engine:
                 st["submit_s"] += t1 - t0
                 st["batches"] += 1
                 texts = None
-                if device_text and not self.multiple_files:
+                if device_text:
                     try:
-                        texts = self.render_device(hb, defer_patterns)
+                        texts = self.render_device_clusters(hb) if self.multiple_files else self.render_device(hb, defer_patterns)
                     except _lib.PanfeedHipError as e:
                         # a batch the text kernels cannot lay out (too many passes, an over-long cluster name)
                         # goes through the host renderers instead
                         if e.status not in (_lib.ERR_CAPACITY, _lib.ERR_ARG):
                             raise
-                if texts is not None:
+                if texts is not None and self.multiple_files:
+                    out = self._cluster_output(hb, res, texts, cluster_targets_sink)
+                elif texts is not None:
                     out = BatchOutput()
                     out.kmers_to_hashes, out.hashes_to_patterns = texts
                     # target strains: their rows written by the GPU too (the next submit reuses the device's text
@@ -377,9 +398,45 @@ class Engine:
                         out.stats["kmers_tsv_streamed"] = len(out.kmers_tsv)
                         targets_sink(out.kmers_tsv)
                         out.kmers_tsv = ""
+                    if self.multiple_files:
+                        out.stats["device_cluster_files"] = 0
+                        if cluster_targets_sink is not None:
+                            out.stats["kmers_tsv_streamed"] = len(out.kmers_tsv)
+                            for i, (idx, kt, kh, hp) in enumerate(out.per_cluster):
+                                cluster_targets_sink(idx, kt.encode())
+                                out.per_cluster[i] = (idx, None, kh, hp)
+                            out.kmers_tsv = ""
                 st["text_s"] += time.perf_counter() - t1
                 st["device_ms"] += out.timing.get("total_ms", 0.0)
                 yield out
+
+    def _cluster_output(self, hb, res, texts, cluster_targets_sink):
+        """the BatchOutput of a multiple_files batch whose text the device wrote: `texts` of render_device_clusters"""
+        kh, hp, kh_end, hp_end = texts
+        n_cl = hb.n_clusters
+        out = BatchOutput()
+        out.kmers_to_hashes, out.hashes_to_patterns = kh, hp
+        streamed, ranges, peak = 0, 0, 0
+        self.stream_compressed = 0
+        out.kmers_tsv = b""
+        if cluster_targets_sink is not None:
+            kt_parts = [None] * n_cl
+            if hb.n_targets:
+                streamed, ranges, peak = self.stream_targets_device(hb, cluster_targets_sink, cluster_sink=True)
+            else:
+                for idx in hb.idx:
+                    cluster_targets_sink(idx, b"")
+        elif hb.n_targets:
+            # (the next submit reuses the device's text block, so the rows come over now)
+            out.kmers_tsv = bytes(self.render_targets_device(hb))
+            kt_parts = _cut(memoryview(out.kmers_tsv), self.target_cluster_ends(hb))
+        else:
+            kt_parts = [b""] * n_cl
+        out.per_cluster = list(zip(hb.idx, kt_parts, _cut(kh, kh_end), _cut(hp, hp_end)))
+        out.stats = _batch_stats(hb, res, self.pattern_count(), kmers_tsv_streamed=streamed, kmers_tsv_ranges=ranges,
+                                 kmers_tsv_peak_device_bytes=peak, device_cluster_files=n_cl)
+        out.timing = self.timing()
+        return out
 
     def result_checksum(self):
         """(k-mer rows, cluster rows, kept) checksums of the last submit, computed on the device (pf_result_checksum)"""
@@ -496,6 +553,34 @@ class Engine:
             return GzipMembers(_mem(kh, kn.value), raw[0]), GzipMembers(_mem(hp, hn.value), raw[1])
         return _mem(kh, kn.value), _mem(hp, hn.value)
 
+    def render_device_clusters(self, hb):
+        """render_device for an engine made with multiple_files (pf_render_device_clusters): (kmers_to_hashes body,
+        hashes_to_patterns body, kh_end, hp_end) of the last submit -- the two memoryviews over pinned host memory (valid
+        until the render after the next one) and, per cluster of `hb`, the offset just behind its rows in each (uint64
+        arrays; a cluster without rows repeats the end before it).  Bodies only: the headers are the writer's."""
+        n_cl = hb.n_clusters
+        names = (C.c_char_p * max(n_cl, 1))(*[s.encode() for s in hb.idx])
+        extra = "".join(hb.extra_keys).encode("latin-1") if hb.extra_keys else None
+        kh, kn, hp, hn = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        kh_end, hp_end = np.zeros(max(n_cl, 1), dtype=np.uint64), np.zeros(max(n_cl, 1), dtype=np.uint64)
+        _lib.check(self.L.pf_render_device_clusters(self.ctx, names, extra, len(hb.extra_keys), C.byref(kh), C.byref(kn),
+                                                    C.byref(hp), C.byref(hn), kh_end.ctypes.data, hp_end.ctypes.data))
+        return _mem(kh, kn.value), _mem(hp, hn.value), kh_end[:n_cl], hp_end[:n_cl]
+
+    def target_cluster_ends(self, hb):
+        """per cluster of `hb`, the offset just behind its rows in the kmers.tsv text last written on the device for `hb`
+        (render_targets_device, or a stream_targets_device under way or over): the library's per-sequence ends
+        (pf_kmers_tsv_seq_ends) at the places where the sequences' cluster index changes.  A cluster without target rows
+        repeats the end before it."""
+        n = hb.n_targets
+        ends = np.zeros(max(n, 1), dtype=np.uint64)
+        _lib.check(self.L.pf_kmers_tsv_seq_ends(self.ctx, ends.ctypes.data, n))
+        ci = self._target_clusters
+        if len(ci) != n or (n > 1 and bool(np.any(ci[1:] < ci[:-1]))):
+            raise ValueError("the target sequences of the batch do not stand cluster by cluster")
+        upto = np.searchsorted(ci, np.arange(hb.n_clusters), side="right")      # sequences of clusters 0 .. i
+        return np.where(upto > 0, ends[np.maximum(upto, 1) - 1], 0).astype(np.uint64)
+
     # ------------------------------------------------------------------ run-global patterns (multi-GPU)
     def export_patterns(self):
         """(md5 uint8 [n,16], first_seen uint64 [n]) of every pattern this engine holds, as numpy arrays"""
@@ -561,11 +646,13 @@ class Engine:
         self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": time.time() - t1, "copy_s": 0.0}
         return DeviceText(self, nb.value)
 
-    def stream_targets_device(self, hb, sink, budget=None):
+    def stream_targets_device(self, hb, sink, budget=None, cluster_sink=False):
         """kmers.tsv rows of every target sequence of `hb` (the last submit), written on the device in ranges that take
         at most `budget` bytes of device memory (default: targets_text_budget) and handed to `sink` block by block (a
         memoryview of pinned memory, valid during the call) -- pf_kmers_tsv_stream_begin / _next.  The blocks joined are
-        the bytes of `render_targets_device(hb)`.  Returns (bytes, ranges, peak device text bytes)."""
+        the bytes of `render_targets_device(hb)`.  cluster_sink: `sink` is a cluster sink, `sink(idx, block)` -- the blocks are
+        cut at the cluster ends as they arrive, and every cluster of `hb` gets at least one call (output.ClusterSplitter).
+        Returns (bytes, ranges, peak device text bytes)."""
         t0 = time.time()
         budget = self.targets_text_budget if budget is None else int(budget)
         streamed = 0
@@ -578,6 +665,10 @@ class Engine:
             _lib.check(self.L.pf_kmers_tsv_stream_begin(self.ctx, arr, n, budget, C.byref(total), C.byref(ranges),
                                                         C.byref(peak)))
             ptr, nb = C.c_void_p(), C.c_uint64()
+            splitter = None
+            if cluster_sink:
+                from .output import ClusterSplitter
+                sink = splitter = ClusterSplitter(self.target_cluster_ends(hb), hb.idx, sink)
             while True:
                 _lib.check(self.L.pf_kmers_tsv_stream_next(self.ctx, C.byref(ptr), C.byref(nb)))
                 if not nb.value:
@@ -592,6 +683,8 @@ class Engine:
                 raw = (C.c_uint64 * 3)()
                 _lib.check(self.L.pf_device_gzip_text_bytes(self.ctx, raw))
                 streamed = int(raw[2])
+            if splitter is not None:
+                splitter.close()
         if streamed != int(total.value):
             raise _lib.PanfeedHipError(_lib.ERR_STATE, f"kmers.tsv stream: {streamed} bytes handed out of {total.value}")
         self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": time.time() - t1, "copy_s": 0.0}
@@ -659,6 +752,7 @@ class Engine:
         n = len(metas) if metas is not None else hb.n_targets
         rec = np.zeros(max(n, 1), dtype=TS)
         arr = C.cast(rec.ctypes.data, C.POINTER(_lib.TargetSeq))
+        self._target_clusters = np.zeros(0, dtype=np.int64)     # the sequences' cluster indices (target_cluster_ends)
         if not n:
             yield arr, 0
             return
@@ -677,6 +771,7 @@ class Engine:
 
         (t_so, t_si, t_ss, t_sn, t_ao, t_ap, t_au, akeys), (ci, strains, seqs) = self._target_columns(hb, metas)
         rec["cluster"] = block(list(hb.idx))[0][ci]
+        self._target_clusters = np.asarray(ci, dtype=np.int64)
         # names repeat (a strain, a contig): one copy each
         for field, values in (("strain", [str(x) for x in strains]), ("id", [str(s.id) for s in seqs]),
                               ("chromosome", [str(s.chromosome) for s in seqs])):

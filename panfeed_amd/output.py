@@ -240,18 +240,93 @@ def write_strain_headers(hash_pat, kmer_hash, strains):
 
 def write_cluster_dir(output, idx, strains, kmers_tsv, kmers_to_hashes, hashes_to_patterns, compress=False):
     """--multiple-files: the three files of gene cluster `idx`, headers and all, in `<output>/<idx>/`
-    (panfeed.py:38-43, 159-167)"""
+    (panfeed.py:38-43, 159-167).  The bodies: str, or the bytes-like text the GPU wrote (slices of a batch's device
+    text).  kmers_tsv None: `kmers.tsv` has been written already, by a ClusterKmersFiles sink."""
     path = os.path.join(output, idx)
     os.makedirs(path, exist_ok=True)
-    ks = create_kmer_stroi(path, compress)
-    ks.write(kmers_tsv)
-    ks.close()
+    if kmers_tsv is not None:
+        ks = create_kmer_stroi(path, compress)
+        write_text(ks, kmers_tsv)
+        ks.close()
     hash_pat, kmer_hash = create_hash_files(path, compress)
     write_strain_headers(hash_pat, kmer_hash, strains)
-    hash_pat.write(hashes_to_patterns)
-    kmer_hash.write(kmers_to_hashes)
+    write_text(hash_pat, hashes_to_patterns)
+    write_text(kmer_hash, kmers_to_hashes)
     hash_pat.close()
     kmer_hash.close()
+
+
+def write_cluster_dirs(output, strains, out, compress=False):
+    """write_cluster_dir for every cluster of a multiple_files batch (`out`: its BatchOutput)"""
+    for idx, kt, kh, hp in out.per_cluster:
+        write_cluster_dir(output, idx, strains, kt, kh, hp, compress)
+
+
+class ClusterSplitter:
+    """Cuts a text that arrives block by block (a batch's kmers.tsv rows as they leave the device) into its clusters'
+    shares: `ends[i]` is the offset just behind cluster `names[i]`'s bytes in the whole text (non-decreasing).  Call it
+    with every block, in order, then `close()`: `sink(name, piece)` is called at least once for every cluster, in order,
+    with an empty piece where a cluster has no byte.  Blocks and ends fall wherever they fall; a piece is a slice of the
+    block it came in, valid as long as that is."""
+
+    def __init__(self, ends, names, sink):
+        self.ends, self.names, self.sink = [int(e) for e in ends], list(names), sink
+        if len(self.ends) != len(self.names) or any(b < a for a, b in zip(self.ends, self.ends[1:])):
+            raise ValueError("one end per cluster, non-decreasing")
+        self.at = 0             # bytes taken so far
+        self.cluster = 0        # the cluster the next byte belongs to, if it has any left
+        self.called = False     # whether that cluster has had a call
+
+    def _next_cluster(self):
+        if not self.called:
+            self.sink(self.names[self.cluster], b"")
+        self.cluster += 1
+        self.called = False
+
+    def __call__(self, block):
+        view = memoryview(block)
+        off, n = 0, len(view)
+        while off < n:
+            while self.cluster < len(self.ends) and self.ends[self.cluster] <= self.at:
+                self._next_cluster()
+            if self.cluster == len(self.ends):
+                raise ValueError(f"{n - off} bytes of text behind the last cluster's end")
+            take = min(n - off, self.ends[self.cluster] - self.at)
+            self.sink(self.names[self.cluster], view[off:off + take])
+            self.called = True
+            off += take
+            self.at += take
+
+    def close(self):
+        if self.ends and self.at != self.ends[-1]:
+            raise ValueError(f"the text ended at byte {self.at}, the last cluster's end is {self.ends[-1]}")
+        while self.cluster < len(self.ends):
+            self._next_cluster()
+
+
+class ClusterKmersFiles:
+    """A cluster_targets_sink (Engine.run_batches) that writes `<output>/<idx>/kmers.tsv[.gz]`: the file is made, header
+    first, at a cluster's first call and closed when the next cluster's first call comes, or by `close()` -- the calls of
+    one cluster stand together.  `bytes`: the rows written so far."""
+
+    def __init__(self, output, compress=False):
+        self.output, self.compress = output, compress
+        self.idx, self.fh = None, None
+        self.bytes = 0
+
+    def __call__(self, idx, block):
+        if self.fh is None or idx != self.idx:
+            self.close()
+            path = os.path.join(self.output, idx)
+            os.makedirs(path, exist_ok=True)
+            self.idx, self.fh = idx, create_kmer_stroi(path, self.compress)
+        write_text(self.fh, block)
+        self.bytes += len(block)
+
+    def close(self):
+        if self.fh is not None:
+            self.fh.close()
+            self.fh = None
 
 
 def write_text(fh, data):

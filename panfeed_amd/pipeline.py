@@ -15,7 +15,8 @@ import time
 from . import _lib
 from .engine import Engine, add_batch_stats, text_len
 from .native_input import Pangenome
-from .output import create_hash_files, create_kmer_stroi, write_cluster_dir, write_strain_headers, write_text
+from .output import (ClusterKmersFiles, create_hash_files, create_kmer_stroi, write_cluster_dirs, write_strain_headers,
+                     write_text)
 
 
 # ---------------------------------------------------------------------- the start-up both file pipelines share
@@ -66,7 +67,7 @@ class _FileRun:
 
     def __init__(self, output, compress, multiple_files, device_gzip=False):
         self.output, self.compress, self.multiple_files = output, compress, multiple_files
-        self.device_gzip = device_gzip and not multiple_files      # (per-cluster directories keep the host path)
+        self.device_gzip = device_gzip and not multiple_files      # (per-cluster files keep the host's gzip)
         self.t_start = time.perf_counter()
         # where the wall time went: opening + parsing the inputs, creating the context, uploading the genomes, then the
         # overlapped stages of the batches (Engine.run_batches: read + pack on its thread, pf_submit = upload + kernels,
@@ -116,8 +117,7 @@ class _FileRun:
             write_text(self.kmer_hash, o.kmers_to_hashes)
             write_text(self.hash_pat, o.hashes_to_patterns)
             return
-        for idx, kt, kh, hp in o.per_cluster:
-            write_cluster_dir(self.output, idx, self.strains, kt, kh, hp, self.compress)
+        write_cluster_dirs(self.output, self.strains, o, self.compress)
 
     def writer(self, q, slots):
         while True:
@@ -206,16 +206,25 @@ def _write_batches(run, eng, pg, stats, batch_clusters, device_text):
     try:
         # (target strains' rows go to kmers.tsv block by block as they leave the device, from this thread: the file is
         # the writer thread's only when a batch's rows come as one object -- the host renderers' path)
+        # (under multiple_files each cluster's rows into its own directory's kmers.tsv, cut at the cluster ends)
         sink = (lambda blk: write_text(run.kmer_stroi, blk)) if (device_text and not run.multiple_files) else None
+        cluster_sink = ClusterKmersFiles(run.output, run.compress) if (device_text and run.multiple_files) else None
         batches = eng.run_pangenome(pg, batch_clusters=batch_clusters, device_text=device_text,
-                                    before_first_submit=run.wait_for_genomes, targets_sink=sink)
+                                    before_first_submit=run.wait_for_genomes, targets_sink=sink,
+                                    cluster_targets_sink=cluster_sink)
         while True:
             slots.acquire()
-            o = next(batches, None)
+            try:
+                o = next(batches, None)
+            finally:
+                if cluster_sink is not None:
+                    cluster_sink.close()        # the batch's last kmers.tsv
             if o is None:
                 break
             add_batch_stats(stats, o)
             stats["patterns"] = o.stats.get("patterns", stats["patterns"])
+            if run.multiple_files:              # the clusters whose files are cut from text the GPU wrote
+                stats["device_cluster_files"] = stats.get("device_cluster_files", 0) + o.stats.get("device_cluster_files", 0)
             if run.device_gzip:                 # the members the GPU made of this batch, by the encoder's own count
                 stats["compressed_bytes"] = stats.get("compressed_bytes", 0) + o.stats.get("compressed_bytes", 0)
             stats["bytes"] += (text_len(o.kmers_tsv) + text_len(o.kmers_to_hashes) + text_len(o.hashes_to_patterns) +
@@ -248,7 +257,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
     device_gzip (`--gpu-compress`): the `.gz` files are compressed on the GPU -- it implies `compress`; the text the GPU
     writes leaves it as gzip members (larger files than `compress` writes, in less time -- profiles/gzip_device/ -- that read back as
     the same text), `stats["bytes"]` keeps counting text and `stats["compressed_bytes"]` is what the files hold behind their
-    header members: the encoder's own count of every batch's members plus the members the host compressed.  Under `multiple_files` it changes nothing: the per-cluster directories keep the host's gzip.
+    header members: the encoder's own count of every batch's members plus the members the host compressed.  Under `multiple_files` it changes nothing: the per-cluster files are cut from text the GPU wrote (device_text) and keep the host's gzip.
     targets_text_budget: device memory a batch's kmers.tsv text may take (default: the engine's).
     Returns a dict of counters."""
     compress = bool(compress or device_gzip)

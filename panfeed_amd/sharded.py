@@ -18,7 +18,7 @@ run-global `patterns` set and the three file handles, panfeed.py:146-150, 179-18
   sequence of gzip members and so is the concatenation; under `device_gzip` the members are the GPU's, or small ones
   made on the host, and the file is one the device decoder takes.
 * `--multiple-files`: the pattern set restarts in every cluster (panfeed.py:165): no exchange at all, every rank writes
-  its clusters' directories.
+  its clusters' directories, cut from its batches' device text like a single-GPU run's.
 
 `PatternSource` is the little a rank needs from its engine after the shard has run; `Engine` provides it, and the CPU
 tests drive the same merge / assembly code with a stand-in.
@@ -30,7 +30,7 @@ import shutil
 import numpy as np
 
 from .engine import KMERS_TO_HASHES_HEADER, KMERS_TSV_HEADER, add_batch_stats, hashes_to_patterns_header, text_len
-from .output import ParallelGzipWriter, SmallMemberGzipWriter, write_cluster_dir, write_text
+from .output import ClusterKmersFiles, ParallelGzipWriter, SmallMemberGzipWriter, write_cluster_dirs, write_text
 
 FILES = ("kmers.tsv", "kmers_to_hashes.tsv", "hashes_to_patterns.tsv")
 
@@ -341,11 +341,18 @@ def _drive(eng, make_batches, output, strains, rank, world, dist, device, compre
     clusters written until then stay."""
     stats = {"rank": rank, "clusters": 0, "instances": 0, "kept_kmers": 0, "range": list(rng), "device_ms": 0.0}
     if multiple_files:
+        # a cluster's kmers.tsv rows go into its directory as they leave the device, its other two files when the batch
+        # is handed over (slices of the device text, or the host renderers' strings)
+        kmers_files = ClusterKmersFiles(output, compress)
+
         def each(o):
-            for idx, kt, kh, hp in o.per_cluster:
-                write_cluster_dir(output, idx, list(strains), kt, kh, hp, compress)
+            kmers_files.close()
+            write_cluster_dirs(output, list(strains), o, compress)
             add_batch_stats(stats, o, ("clusters", "instances"))
-        _shard_batches(make_batches(), each, dist, device)
+        try:
+            _shard_batches(make_batches(cluster_targets_sink=kmers_files), each, dist, device)
+        finally:
+            kmers_files.close()
         _barrier(dist, device)
         return stats
     stats.update(kmers_tsv_streamed=0, kmers_tsv_ranges=0, kmers_tsv_peak_device_bytes=0)
