@@ -511,6 +511,18 @@ int pf_kmers_tsv_stream_begin(pf_ctx* ctx, const pf_target_seq* seqs, uint32_t n
 /* The next block of that text (at most 64 MiB) in pinned host memory owned by the context, valid until the next call;
  * the block after it is already being copied.  *nbytes == 0 at the end (the stream is then over). */
 int pf_kmers_tsv_stream_next(pf_ctx* ctx, const char** ptr, uint64_t* nbytes);
+/* Under pf_set_device_gzip, between pf_kmers_tsv_stream_begin and the first pf_kmers_tsv_stream_next: text offsets behind
+ * which a gzip member must end (non-decreasing, none past the text's size, else PF_ERR_ARG; repeats, 0 and the text's
+ * size say nothing new and are dropped) -- the ends of the clusters' rows under multiple_files, so that each cluster's
+ * file is made of whole members.  Every block ends on a member boundary anyway; the cuts add boundaries inside blocks.
+ * Without this call the stream is as before.  PF_ERR_STATE: no open stream, no device gzip, or a block already queued. */
+int pf_kmers_tsv_stream_cuts(pf_ctx* ctx, const uint64_t* cuts, uint64_t n);
+/* The block pf_kmers_tsv_stream_next handed out last, under device gzip: *text_off, *text_bytes -- the text behind its
+ * members; *n_cuts -- the cuts that lie strictly inside that text; cut_text[i] / cut_member[i] (caller arrays of `cap`
+ * entries; PF_ERR_ARG if there are more cuts) -- their text offsets, ascending, and the offset in the block's members
+ * behind which the members of the text before the cut end.  PF_ERR_STATE without such a block. */
+int pf_kmers_tsv_stream_block_cuts(pf_ctx* ctx, uint64_t* text_off, uint64_t* text_bytes, uint64_t* cut_text, uint64_t* cut_member,
+                                   uint64_t cap, uint64_t* n_cuts);
 /* Where the rows of each of the n target sequences given to the last pf_render_kmers_tsv_device or
  * pf_kmers_tsv_stream_begin end in the whole text: ends[i] is the offset just behind sequence i's rows (a sequence with
  * no window repeats the end before it; ends[n - 1] is the text's size).  The caller cuts the text where its sequences
@@ -544,6 +556,15 @@ int pf_render_device_ex(pf_ctx* ctx, const char* const* names, const char* extra
 int pf_render_device_clusters(pf_ctx* ctx, const char* const* names, const char* extra_keys, uint64_t n_extra,
                               const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes,
                               uint64_t* kh_end, uint64_t* hp_end);
+/* pf_render_device_clusters under pf_set_device_gzip (PF_ERR_STATE without it, PF_ERR_ARG without multiple_files): the
+ * same two bodies from the same pair of launches, encoded so that no gzip member holds rows of two clusters, and handed
+ * out as members.  kh_end[i] / hp_end[i]: the offset just behind cluster i's members in *kh / *hp -- a cluster's piece
+ * is a complete gzip file's body, appended behind the header line's member as it is; a cluster without rows repeats the
+ * end before it.  kh_text_end / hp_text_end: the text offsets pf_render_device_clusters gives (the text sizes behind
+ * the pieces).  All four: caller arrays of n_clusters entries. */
+int pf_render_device_cluster_members(pf_ctx* ctx, const char* const* names, const char* extra_keys, uint64_t n_extra,
+                                     const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes,
+                                     uint64_t* kh_end, uint64_t* hp_end, uint64_t* kh_text_end, uint64_t* hp_text_end);
 /* Rows of hashes_to_patterns.tsv ("hash\tv0\tv1...\n", panfeed.py:181-187, 217-223) for ANY patterns of the
  * run-global pool, in the order given, written on the device: pids[n] are pattern ids (< pf_pattern_count).  The
  * multi-GPU driver calls it after pf_merge_patterns with the ids whose first_seen is the global minimum of their
@@ -589,11 +610,21 @@ uint32_t pf_gzip_device_chunk_bytes(void);
 /* Host text in, members out (malloc'd: pf_free_text): uploaded, encoded on the GPU, copied back.  n == 0 gives
  * *out_n == 0.  For tests, tools and text rendered on the host. */
 int pf_gzip_device(pf_ctx* ctx, const char* data, uint64_t n, uint32_t flags, char** out, uint64_t* out_n);
+/* The same for a text made of segments, one behind the other: seg_end[0 .. n_seg) are the offsets behind them
+ * (non-decreasing, the last one n; n_seg == 0 needs n == 0; else PF_ERR_ARG).  No member holds bytes of two segments:
+ * every segment is cut into chunks from its own start, an empty one has no member, and the bytes of a segment's members
+ * are those pf_gzip_device gives for the segment's text alone.  member_end[i] (caller array of n_seg entries): the
+ * offset in *out behind segment i's members. */
+int pf_gzip_device_segments(pf_ctx* ctx, const char* data, uint64_t n, const uint64_t* seg_end, uint64_t n_seg, uint32_t flags,
+                            char** out, uint64_t* out_n, uint64_t* member_end);
 /* Device time of the last pf_gzip_device's kernels (encode, size scan, gather; hipEvent on the context's stream), ms. */
 int pf_gzip_device_last_ms(pf_ctx* ctx, float* ms);
 /* The same container and coder run serially on the host, with a plain one-candidate greedy matcher: no context, no GPU.
  * Its bytes need not equal the device's; both decode to `data`. */
 int pf_gzip_host_model(const char* data, uint64_t n, uint32_t flags, char** out, uint64_t* out_n);
+/* and over segments, as pf_gzip_device_segments cuts them: the same chunk plan, the same refusals */
+int pf_gzip_host_model_segments(const char* data, uint64_t n, const uint64_t* seg_end, uint64_t n_seg, uint32_t flags, char** out,
+                                uint64_t* out_n, uint64_t* member_end);
 /*
  * gunzip ON THE DEVICE, for files made of small members such as pf_gzip_device writes: every member at most
  * pf_gzip_device_chunk_bytes() of text (its ISIZE) and at most a ninth more than that compressed, with the plain 10-byte
@@ -616,7 +647,8 @@ int pf_gunzip_host_model(const char* members, uint64_t n, char** out, uint64_t* 
  * is produced and its compressed size read back before it is copied (the host-rendered sequences are in the device text
  * and go the same way); a block's members decode to a block of the text, in order.  The stream's *total_bytes stays the
  * text's size and *peak_text_bytes includes the encoder's buffers.  pf_device_text_chunk, pf_render_pattern_rows and the
- * host renderers are not affected. */
+ * host renderers are not affected.  Under multiple_files the render call is pf_render_device_cluster_members (its
+ * members end where a cluster's rows end) and the stream takes the clusters' ends through pf_kmers_tsv_stream_cuts. */
 int pf_set_device_gzip(pf_ctx* ctx, int on, uint32_t flags);
 /* The text sizes behind the compressed bytes: out[0], out[1] = bytes of kmers_to_hashes / hashes_to_patterns text of the
  * last pf_render_device[_ex]; out[2] = text bytes the open (or last) kmers.tsv or pattern-row stream has handed out so

@@ -161,7 +161,9 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_assocfilter_scan_members", "pf_assocfilter_next_lines", "pf_assocfilter_columns", "pf_assocfilter_stats",
            "pf_assocfilter_destroy",
            "pf_kmerjoin_set_gzip", "pf_kmerjoin_gzip_stats",
-           "pf_plotgrid_members_begin", "pf_plotgrid_members_header", "pf_plotgrid_scan_members", "pf_plotgrid_gunzip_stats"]
+           "pf_plotgrid_members_begin", "pf_plotgrid_members_header", "pf_plotgrid_scan_members", "pf_plotgrid_gunzip_stats",
+           "pf_gzip_device_segments", "pf_gzip_host_model_segments", "pf_render_device_cluster_members",
+           "pf_kmers_tsv_stream_cuts", "pf_kmers_tsv_stream_block_cuts"]
 
 RENDER_NO_PATTERN_ROWS = 1
 GZ_FIXED_ONLY, GZ_DYNAMIC_ONLY, GZ_LITERALS_ONLY = 1, 2, 4     # pf_gzip_device / pf_set_device_gzip test hooks; 0: the product
@@ -310,6 +312,16 @@ def _load_locked():
     L.pf_gzip_device_chunk_bytes.restype = C.c_uint32
     L.pf_gzip_device.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pf_gzip_host_model.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pf_gzip_device_segments.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_uint64), C.c_void_p]
+    L.pf_gzip_host_model_segments.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_uint64), C.c_void_p]
+    L.pf_render_device_cluster_members.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p),
+                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pf_kmers_tsv_stream_cuts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.pf_kmers_tsv_stream_block_cuts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
+                                                 C.c_uint64, C.POINTER(C.c_uint64)]
     L.pf_gzip_device_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.pf_set_device_gzip.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
     L.pf_device_gzip_text_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]

@@ -3,8 +3,8 @@ on N of them.
 
 Option names, short forms, defaults and meanings are the reference's (`__main__.py:86-222`); so are the refusals, their
 order and their exit status (`__main__.py:234-242`, `input.py:213-216`).  The run itself is `pipeline.run_files`: the
-native reader, the GPU, a writer thread.  Two options are added: `--device` (as the downstream tools have) and
-`--batch-clusters`.  `--cores` and `-ql/--queue-limit` are accepted and change nothing (the GPU takes the place of the
+native reader, the GPU, a writer thread.  Options added: `--device` (as the downstream tools have),
+`--batch-clusters`, `--gpu-compress` and, for `--multiple-files`, `--gpu-compress-clusters`.  `--cores` and `-ql/--queue-limit` are accepted and change nothing (the GPU takes the place of the
 worker processes).  One refusal is new: `-k` outside 1..PF_MAX_K, before any file is read or the GPU touched.
 
 Unlike the reference, no `<output>/fastas/` directory is made (the reader splits the GFFs' `##FASTA` sections in
@@ -71,6 +71,8 @@ def get_options(argv=None):
                    help="gzip the output files")
     p.add_argument("--gpu-compress", action="store_true", default=False,
                    help="gzip the output files on the GPU; implies --compress; much faster, somewhat larger files")
+    p.add_argument("--gpu-compress-clusters", action="store_true", default=False,
+                   help="with --multiple-files: gzip the per-cluster files on the GPU; implies --compress")
     p.add_argument("--cores", type=int, default=1,
                    help="accepted for compatibility; the GPU does the work of the worker processes")
     p.add_argument("-ql", "--queue-limit", type=int, default=3,
@@ -129,6 +131,10 @@ def main(argv=None, run=None, launch=None, rank_entry=None):
     if args.batch_clusters < 1:
         logger.error("--batch-clusters must be at least 1")
         return 2
+    if args.gpu_compress_clusters and not args.multiple_files:
+        logger.error("--gpu-compress-clusters is for the per-cluster files of --multiple-files; --gpu-compress compresses the "
+                     "one set of files on the GPU")
+        return 2
     if args.targets is not None:
         logger.debug(f"Reading target strains ({args.targets})")
         targets = read_names(args.targets)
@@ -161,13 +167,16 @@ def main(argv=None, run=None, launch=None, rank_entry=None):
     if args.gpu_compress:
         more["device_gzip"] = True
         if args.multiple_files:
-            logger.info("--gpu-compress with --multiple-files: the per-cluster files are compressed on the host")
+            logger.info("--gpu-compress with --multiple-files: the per-cluster files are compressed on the host; "
+                        "--gpu-compress-clusters compresses them on the GPU")
+    if args.gpu_compress_clusters:
+        more["device_gzip_clusters"] = True
     from ._lib import PanfeedHipError
     if many:
         options = dict(fastadir=args.fasta, klength=k, canon=not args.non_canonical, consider_missing=args.consider_missing,
                        patfilt=not args.no_filter, maf=args.maf, upstream=args.upstream, downstream=args.downstream,
                        downstream_start_codon=args.downstream_start_codon, targets=tuple(sorted(targets)),
-                       genes=sorted(genes) if genes is not None else None, compress=args.compress or args.gpu_compress,
+                       genes=sorted(genes) if genes is not None else None, compress=args.compress or args.gpu_compress or args.gpu_compress_clusters,
                        multiple_files=args.multiple_files, batch_clusters=args.batch_clusters, gpu=args.device,
                        raise_missing=args.stop_on_missing, **more)
         if not as_rank:
@@ -191,7 +200,7 @@ def main(argv=None, run=None, launch=None, rank_entry=None):
                     canon=not args.non_canonical, consider_missing=args.consider_missing, patfilt=not args.no_filter,
                     maf=args.maf, upstream=args.upstream, downstream=args.downstream,
                     downstream_start_codon=args.downstream_start_codon, targets=tuple(sorted(targets)),
-                    genes=sorted(genes) if genes is not None else None, compress=args.compress or args.gpu_compress,
+                    genes=sorted(genes) if genes is not None else None, compress=args.compress or args.gpu_compress or args.gpu_compress_clusters,
                     multiple_files=args.multiple_files, batch_clusters=args.batch_clusters, device=args.device,
                     raise_missing=args.stop_on_missing, **more)
     except PanfeedHipError as e:          # the reader's message under --stop-on-missing, or the library's error

@@ -257,6 +257,12 @@ struct TargetText {
         char* htext[2] = {nullptr, nullptr};   // the host's share of the range being written into each buffer
         hipEvent_t ev_prod[2] = {nullptr, nullptr};    // on `stream`: the range in buffer b is written
         hipEvent_t ev_copied[2] = {nullptr, nullptr};  // on `side`: the range in buffer b has left the device
+        // device gzip with cuts (pf_kmers_tsv_stream_cuts): the text offsets inside the text behind which a member must
+        // end, ascending and distinct; per slot the block encoded into it -- its text, its cuts [lo, hi) and their
+        // places in its text -- and, once handed out, behind which member byte each of them lies
+        std::vector<uint64_t> cuts;
+        struct Block { uint64_t off = 0, n = 0; size_t lo = 0, hi = 0; std::vector<uint64_t> seg_end, member_end; } blk[2];
+        int handed = -1;                               // the slot of the block handed out last
     } stream;
     void destroy_events() { for (auto e : {stream.ev_prod[0], stream.ev_prod[1], stream.ev_copied[0], stream.ev_copied[1]}) if (e) (void)hipEventDestroy(e); }
 };
@@ -400,6 +406,7 @@ void kt_stream_end(pf_ctx* c) {
     for (int b = 0; b < 2; b++) { free(S.htext[b]); S.htext[b] = nullptr; }
     S.active = false; c->kt.flight.valid = false;
     S.hseqs.clear(); S.host = KtHostText{}; S.plan = KtPlan{};
+    S.cuts.clear(); S.handed = -1;
 }
 // the end of a pattern-row stream (its last slice handed out, the next pf_submit, a kmers.tsv text begun, pf_destroy):
 // nothing of it is in flight afterwards
@@ -2606,8 +2613,16 @@ int kt_block(pf_ctx* c, int slot) {
     const uint64_t off = R.base + S.cur_off, n = std::min<uint64_t>(S.pin_bytes, R.bytes - S.cur_off);
     HIPCHK(hipStreamWaitEvent(c->side, S.ev_prod[b], 0));
     if (G.on) {
-        PFCHK(G.enc.encode(c->side, slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, src, n, G.flags,
-                           G.block_members[slot].as<char>(), G.block_bound));
+        // the block's segments: what lies between the cuts inside it (none: one segment, the block as a whole)
+        TargetText::Stream::Block& B = S.blk[slot];
+        B.off = off; B.n = n;
+        B.lo = (size_t)(std::upper_bound(S.cuts.begin(), S.cuts.end(), off) - S.cuts.begin());
+        B.hi = (size_t)(std::lower_bound(S.cuts.begin(), S.cuts.end(), off + n) - S.cuts.begin());
+        B.seg_end.clear();
+        for (size_t i = B.lo; i < B.hi; i++) B.seg_end.push_back(S.cuts[i] - off);
+        if (n) B.seg_end.push_back(n);
+        PFCHK(G.enc.encode_segments(c->side, slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, src, n, B.seg_end.data(),
+                                    B.seg_end.size(), G.flags, G.block_members[slot].as<char>(), G.block_bound));
         c->kt.flight = {true, slot, off, n};
     } else PFCHK(kt_prefetch(c, slot, src, off, n, S.pin_bytes));
     S.cur_off += n;
@@ -2620,10 +2635,10 @@ int kt_block(pf_ctx* c, int slot) {
 }
 
 // the buffers of the stream's blocks in flight under device gzip, for blocks of at most block_text bytes of text
-int kt_gz_buffers(pf_ctx* c, uint64_t block_text) {
+int kt_gz_buffers(pf_ctx* c, uint64_t block_text, uint64_t n_cuts = 0) {
     GzMode& G = c->gz;
     PFCHK(G.enc.ensure(c->n_cu));
-    G.block_bound = PfGzEncoder::bound(std::max<uint64_t>(block_text, 1));
+    G.block_bound = PfGzEncoder::bound_segments(std::max<uint64_t>(block_text, 1), n_cuts);     // (every cut may add a short chunk)
     for (int s = 0; s < 2; s++) {
         PFCHK(G.block_members[s].ensure(G.block_bound, true));
         PFCHK(c->kt.pins[s].ensure(G.block_bound, true));
@@ -2638,6 +2653,11 @@ int kt_gz_buffers(pf_ctx* c, uint64_t block_text) {
 int gz_block_down(pf_ctx* c, int slot, uint64_t text, hipStream_t st, uint64_t* n) {
     GzMode& G = c->gz;
     PFCHK(G.enc.member_bytes(slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, n));
+    if (c->kt.stream.active && !c->kt.stream.cuts.empty()) {      // (the kmers.tsv stream's cuts: their places came with the size)
+        TargetText::Stream::Block& B = c->kt.stream.blk[slot];
+        B.member_end.resize(B.seg_end.size());
+        if (!B.seg_end.empty()) PFCHK(G.enc.segment_ends(slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, B.member_end.data()));
+    }
     G.raw[2] += text;
     HIPCHK(hipMemcpyAsync(c->kt.pins[slot].p, G.block_members[slot].p, *n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(G.ev_copy, st));
@@ -2708,8 +2728,41 @@ int pf_kmers_tsv_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
     c->kt.flight.valid = false;
     if (S.cur < S.plan.ranges.size()) PFCHK(kt_block(c, slot ^ 1));      // the next block on its way meanwhile
     if (arrival) HIPCHK(hipEventSynchronize(arrival));
+    S.handed = slot;
     *ptr = c->kt.pins[slot].as<char>();
     *nbytes = n;
+    return PF_OK;
+}
+
+int pf_kmers_tsv_stream_cuts(pf_ctx* c, const uint64_t* cuts, uint64_t n) {
+    if (!c || (n && !cuts)) return fail(PF_ERR_ARG, "pf_kmers_tsv_stream_cuts: null argument");
+    TargetText::Stream& S = c->kt.stream;
+    if (!S.active) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_cuts without an open pf_kmers_tsv_stream_begin");
+    if (!c->gz.on) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_cuts: the stream hands out text, which is cut anywhere; the cuts are for pf_set_device_gzip");
+    if (c->kt.flight.valid || S.cur || S.cur_off || S.handed >= 0)
+        return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_cuts: the stream's first block is on its way already");
+    std::vector<uint64_t> in;
+    for (uint64_t i = 0; i < n; i++) {
+        if ((i && cuts[i] < cuts[i - 1]) || cuts[i] > S.plan.total) return fail(PF_ERR_ARG, "pf_kmers_tsv_stream_cuts: the offsets must not decrease nor pass the text's end");
+        if (cuts[i] && cuts[i] < S.plan.total && (in.empty() || in.back() != cuts[i])) in.push_back(cuts[i]);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    PFCHK(kt_gz_buffers(c, std::min<uint64_t>(KT_BLOCK, S.plan.max_range), in.size()));
+    S.cuts.swap(in);
+    return PF_OK;
+}
+
+int pf_kmers_tsv_stream_block_cuts(pf_ctx* c, uint64_t* text_off, uint64_t* text_bytes, uint64_t* cut_text, uint64_t* cut_member,
+                                   uint64_t cap, uint64_t* n_cuts) {
+    if (!c || !text_off || !text_bytes || !n_cuts) return fail(PF_ERR_ARG, "pf_kmers_tsv_stream_block_cuts: null argument");
+    TargetText::Stream& S = c->kt.stream;
+    if (!S.active || S.handed < 0 || !c->gz.on) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_block_cuts without a block of members handed out");
+    const TargetText::Stream::Block& B = S.blk[S.handed];
+    const uint64_t k = B.hi - B.lo;
+    *text_off = B.off; *text_bytes = B.n; *n_cuts = k;
+    if (k > cap || (k && (!cut_text || !cut_member))) return fail(PF_ERR_ARG, "pf_kmers_tsv_stream_block_cuts: %llu cuts inside the block, room for %llu", (unsigned long long)k, (unsigned long long)cap);
+    if (k && B.member_end.size() != k + 1) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_block_cuts: the block's member offsets are missing");
+    for (uint64_t i = 0; i < k; i++) { cut_text[i] = S.cuts[B.lo + i]; cut_member[i] = B.member_end[i]; }
     return PF_OK;
 }
 
@@ -3502,21 +3555,31 @@ int render_launch(pf_ctx* c, const RenderLayout& L) {
 // at a 256-aligned offset -- as they are, or under device gzip as their members: both texts go through the encoder behind
 // their kernels, the two compressed sizes come back, then only members cross to the host.
 struct Span { const char* p; uint64_t n; };
-int render_handout(pf_ctx* c, Span text0, Span text1, Span* out0, Span* out1) {
+// (under device gzip) where the members of each text must end: n text offsets per text, and where the offsets behind
+// each segment's members go
+struct MemberCuts { uint64_t n; const uint64_t* end0; const uint64_t* end1; uint64_t* member_end0; uint64_t* member_end1; };
+int render_handout(pf_ctx* c, Span text0, Span text1, Span* out0, Span* out1, const MemberCuts* cuts = nullptr) {
     hipStream_t st = c->stream;
     GzMode& G = c->gz;
     if (G.on) {
         HIPCHK(hipStreamSynchronize(c->side));             // (the encoder's scratch is one: no block of a stream in flight)
-        const uint64_t b0 = PfGzEncoder::bound(text0.n), b1 = PfGzEncoder::bound(text1.n);
+        const uint64_t one0 = text0.n, one1 = text1.n, nseg0 = cuts ? cuts->n : (one0 ? 1 : 0), nseg1 = cuts ? cuts->n : (one1 ? 1 : 0);
+        const uint64_t* end0 = cuts ? cuts->end0 : &one0;
+        const uint64_t* end1 = cuts ? cuts->end1 : &one1;
+        const uint64_t b0 = PfGzEncoder::bound_segments(text0.n, cuts ? cuts->n : 0), b1 = PfGzEncoder::bound_segments(text1.n, cuts ? cuts->n : 0);
         PFCHK(G.render_members.ensure(b0 + b1 + 16));
         char* M = G.render_members.as<char>();
-        PFCHK(G.enc.encode(st, PfGzEncoder::RENDER_KMERS_TO_HASHES, text0.p, text0.n, G.flags, M, b0));
-        PFCHK(G.enc.encode(st, PfGzEncoder::RENDER_HASHES_TO_PATTERNS, text1.p, text1.n, G.flags, M + b0, b1));
+        PFCHK(G.enc.encode_segments(st, PfGzEncoder::RENDER_KMERS_TO_HASHES, text0.p, text0.n, end0, nseg0, G.flags, M, b0));
+        PFCHK(G.enc.encode_segments(st, PfGzEncoder::RENDER_HASHES_TO_PATTERNS, text1.p, text1.n, end1, nseg1, G.flags, M + b0, b1));
         HIPCHK(hipStreamSynchronize(st));
         G.raw[0] = text0.n; G.raw[1] = text1.n;
         text0.p = M; text1.p = M + b0;
         PFCHK(G.enc.member_bytes(PfGzEncoder::RENDER_KMERS_TO_HASHES, &text0.n));
         PFCHK(G.enc.member_bytes(PfGzEncoder::RENDER_HASHES_TO_PATTERNS, &text1.n));
+        if (cuts && cuts->n) {
+            PFCHK(G.enc.segment_ends(PfGzEncoder::RENDER_KMERS_TO_HASHES, cuts->member_end0));
+            PFCHK(G.enc.segment_ends(PfGzEncoder::RENDER_HASHES_TO_PATTERNS, cuts->member_end1));
+        }
     }
     const uint64_t at1 = (text0.n + 255) & ~(uint64_t)255;
     char* pin;
@@ -3533,7 +3596,8 @@ namespace {
 // pf_render_device_ex and pf_render_device_clusters behind their own checks: the layout (L.cluster_ends set by the
 // caller), the two launches, the hand-out
 int render_device(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra, bool want_hp, RenderLayout& L,
-                  const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes) {
+                  const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes, uint64_t* kh_member_end = nullptr,
+                  uint64_t* hp_member_end = nullptr) {
     if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_device needs a successful pf_submit");
     HIPCHK(hipSetDevice(c->device));
     if (c->n_clusters && !names) return fail(PF_ERR_ARG, "pf_render_device: cluster names missing");
@@ -3541,7 +3605,10 @@ int render_device(pf_ctx* c, const char* const* names, const char* extra_keys, u
     PFCHK(render_layout(c, names, extra_keys, n_extra, want_hp, L));
     PFCHK(render_launch(c, L));
     Span out0, out1;
-    PFCHK(render_handout(c, Span{c->txt.dev.as<char>(), L.kh_n}, Span{c->txt.dev.as<char>() + L.hp_at, L.hp_n}, &out0, &out1));
+    // (members cut at the clusters' ends: the ends render_layout has just computed)
+    const MemberCuts cuts{c->n_clusters, L.kh_end.data(), L.hp_end.data(), kh_member_end, hp_member_end};
+    PFCHK(render_handout(c, Span{c->txt.dev.as<char>(), L.kh_n}, Span{c->txt.dev.as<char>() + L.hp_at, L.hp_n}, &out0, &out1,
+                         kh_member_end ? &cuts : nullptr));
     *kh = out0.p; *kh_bytes = out0.n;
     *hp = out1.p; *hp_bytes = out1.n;
     return PF_OK;
@@ -3569,6 +3636,25 @@ int pf_render_device_clusters(pf_ctx* c, const char* const* names, const char* e
     if (c->n_clusters) {
         memcpy(kh_end, L.kh_end.data(), (size_t)c->n_clusters * 8);
         memcpy(hp_end, L.hp_end.data(), (size_t)c->n_clusters * 8);
+    }
+    return PF_OK;
+}
+
+int pf_render_device_cluster_members(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra,
+                                     const char** kh, uint64_t* kh_bytes, const char** hp, uint64_t* hp_bytes,
+                                     uint64_t* kh_end, uint64_t* hp_end, uint64_t* kh_text_end, uint64_t* hp_text_end) {
+    if (!c || !kh || !kh_bytes || !hp || !hp_bytes) return fail(PF_ERR_ARG, "pf_render_device_cluster_members: null argument");
+    if (!c->o.multiple_files) return fail(PF_ERR_ARG, "pf_render_device_cluster_members is for a context made with multiple_files");
+    if (!c->gz.on) return fail(PF_ERR_STATE, "pf_render_device_cluster_members hands out gzip members: pf_set_device_gzip first, or pf_render_device_clusters for text");
+    if (c->have_batch && c->n_clusters && (!kh_end || !hp_end || !kh_text_end || !hp_text_end))
+        return fail(PF_ERR_ARG, "pf_render_device_cluster_members: null argument");
+    RenderLayout L;
+    L.cluster_ends = true;
+    uint64_t none = 0;              // (a batch without clusters: no segment, nothing to report)
+    PFCHK(render_device(c, names, extra_keys, n_extra, true, L, kh, kh_bytes, hp, hp_bytes, kh_end ? kh_end : &none, hp_end ? hp_end : &none));
+    if (c->n_clusters) {
+        memcpy(kh_text_end, L.kh_end.data(), (size_t)c->n_clusters * 8);
+        memcpy(hp_text_end, L.hp_end.data(), (size_t)c->n_clusters * 8);
     }
     return PF_OK;
 }
@@ -3635,6 +3721,36 @@ int pf_gzip_device(pf_ctx* c, const char* data, uint64_t n, uint32_t flags, char
     if (!buf) return fail(PF_ERR_OOM, "pf_gzip_device: out of memory");
     const hipError_t e = hipMemcpy(buf, members.p, z, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { free(buf); return fail(PF_ERR_HIP, "pf_gzip_device: copy failed: %s", hipGetErrorString(e)); }
+    *out = buf; *out_n = z;
+    return PF_OK;
+}
+
+int pf_gzip_device_segments(pf_ctx* c, const char* data, uint64_t n, const uint64_t* seg_end, uint64_t n_seg, uint32_t flags,
+                            char** out, uint64_t* out_n, uint64_t* member_end) {
+    if (!c || (!data && n) || (!seg_end && n_seg) || (!member_end && n_seg) || !out || !out_n)
+        return fail(PF_ERR_ARG, "pf_gzip_device_segments: null argument");
+    PFCHK(gz_check_flags(flags, "pf_gzip_device_segments"));
+    *out = nullptr; *out_n = 0;
+    HIPCHK(hipSetDevice(c->device));
+    PfGzEncoder& enc = c->gz.enc;
+    constexpr PfGzEncoder::Cursor W = PfGzEncoder::RENDER_KMERS_TO_HASHES;      // (a render's: neither is on its way now)
+    PFCHK(enc.ensure(c->n_cu));
+    HIPCHK(hipStreamSynchronize(c->side));
+    hipStream_t st = c->stream;
+    DevBuf text, members;
+    const uint64_t cap = PfGzEncoder::bound_segments(n, n_seg);
+    PFCHK(text.ensure(n + 16, true));
+    PFCHK(members.ensure(cap + 16, true));
+    if (n) HIPCHK(hipMemcpyAsync(text.p, data, n, hipMemcpyHostToDevice, st));
+    PFCHK(enc.encode_segments(st, W, text.as<char>(), n, seg_end, n_seg, flags, members.as<char>(), cap));
+    HIPCHK(hipStreamSynchronize(st));
+    uint64_t z = 0;
+    PFCHK(enc.member_bytes(W, &z));
+    if (n_seg) PFCHK(enc.segment_ends(W, member_end));
+    char* buf = (char*)malloc(z ? z : 1);
+    if (!buf) return fail(PF_ERR_OOM, "pf_gzip_device_segments: out of memory");
+    const hipError_t e = z ? hipMemcpy(buf, members.p, z, hipMemcpyDeviceToHost) : hipSuccess;
+    if (e != hipSuccess) { free(buf); return fail(PF_ERR_HIP, "pf_gzip_device_segments: copy failed: %s", hipGetErrorString(e)); }
     *out = buf; *out_n = z;
     return PF_OK;
 }

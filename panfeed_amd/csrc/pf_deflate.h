@@ -10,6 +10,8 @@
 //
 // Container: the text is cut into chunks of CHUNK bytes; every chunk becomes one complete gzip member holding one final
 // deflate block -- stored, fixed or dynamic, whichever is smallest by exact bit count.  No match reaches before its chunk.
+// A text made of segments (several files' bodies, one behind the other) is cut segment by segment, each from its own
+// start, so that no member holds bytes of two segments: chunk_plan() below.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -351,16 +353,50 @@ inline void host_model_chunk(const uint8_t* text, uint32_t n, uint32_t flags, st
     for (uint32_t i = 0; i < nbytes; i++) out.push_back((uint8_t)(words[i >> 2] >> (8 * (i & 3))));
 }
 
-// the members of `data`; false: a chunk's size did not come out as counted (a bug)
-inline bool host_model(const uint8_t* data, uint64_t n, uint32_t flags, std::vector<uint8_t>& out) {
-    out.clear();
-    for (uint64_t at = 0; at < n; at += CHUNK) {
-        std::vector<uint8_t> one;
-        host_model_chunk(data + at, (uint32_t)std::min<uint64_t>(CHUNK, n - at), flags, one);
-        if (one.empty()) return false;
-        out.insert(out.end(), one.begin(), one.end());
+// ---- the chunk plan.  A text may be cut into segments (the per-cluster files' bodies, one behind the other): a member
+// never holds bytes of two segments.  Every segment is cut into chunks of CHUNK bytes counted from its own start, its
+// last one shorter; an empty segment has no chunk.  One segment over the whole text gives the plain container above.
+struct ChunkDesc { uint64_t start; uint32_t len, segment; };      // text offset, bytes (1 .. CHUNK), index into seg_end
+static_assert(sizeof(ChunkDesc) == 16, "the kernels read the plan as it stands in host memory");
+// the chunks of text[0 .. n) under segment ends seg_end[0 .. n_seg): non-decreasing offsets, the last one n (no segment:
+// no text).  false: the ends are not such a list.
+inline bool chunk_plan(const uint64_t* seg_end, uint64_t n_seg, uint64_t n, std::vector<ChunkDesc>& plan) {
+    plan.clear();
+    if (n_seg > 0xFFFFFFFFull || (n_seg ? seg_end[n_seg - 1] != n : n != 0)) return false;
+    uint64_t at = 0;
+    for (uint64_t s = 0; s < n_seg; s++) {
+        if (seg_end[s] < at) return false;
+        for (; at < seg_end[s]; at += std::min<uint64_t>(CHUNK, seg_end[s] - at))
+            plan.push_back(ChunkDesc{at, (uint32_t)std::min<uint64_t>(CHUNK, seg_end[s] - at), (uint32_t)s});
     }
     return true;
+}
+inline uint64_t plan_chunks(uint64_t n, uint64_t n_seg) { return (n + CHUNK - 1) / CHUNK + n_seg; }     // never fewer than the plan holds
+
+// The members of `data` under a plan, and behind which byte of them every segment's members end (member_end[n_seg],
+// may be null).  0: done; 1: the ends are no plan; 2: a chunk's size did not come out as counted (a bug).
+inline int host_model_segments(const uint8_t* data, uint64_t n, const uint64_t* seg_end, uint64_t n_seg, uint32_t flags,
+                               std::vector<uint8_t>& out, uint64_t* member_end) {
+    out.clear();
+    std::vector<ChunkDesc> plan;
+    if (!chunk_plan(seg_end, n_seg, n, plan)) return 1;
+    size_t c = 0;
+    for (uint64_t s = 0; s < n_seg; s++) {
+        for (; c < plan.size() && plan[c].segment == s; c++) {
+            std::vector<uint8_t> one;
+            host_model_chunk(data + plan[c].start, plan[c].len, flags, one);
+            if (one.empty()) return 2;
+            out.insert(out.end(), one.begin(), one.end());
+        }
+        if (member_end) member_end[s] = out.size();
+    }
+    return 0;
+}
+
+// the members of `data`; false: a chunk's size did not come out as counted (a bug)
+inline bool host_model(const uint8_t* data, uint64_t n, uint32_t flags, std::vector<uint8_t>& out) {
+    const uint64_t end = n;
+    return host_model_segments(data, n, &end, n ? 1 : 0, flags, out, nullptr) == 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -678,20 +714,38 @@ struct PfGzEncoder {
     static constexpr uint64_t BLOCK = 64ull << 20;       // text bytes per launch: the product's block size
     // one append cursor per text that may be on its way at once: a render's two texts, the stream's two blocks
     enum Cursor { RENDER_KMERS_TO_HASHES, RENDER_HASHES_TO_PATTERNS, STREAM_BLOCK0, STREAM_BLOCK1, N_CURSORS };
-    DevBuf slots, sizes, offs, tokens, cursors;
-    PinBuf pin; uint64_t caps[N_CURSORS] = {};           // per cursor: its value read back, the bytes its last encode's members may take
+    DevBuf slots, sizes, offs, tokens;                   // of one launch: BLOCK / CHUNK chunks
+    // per cursor: the chunk plan of its last encode (pinned, and on the device), the cursor with the member offset of
+    // every segment's first chunk behind it (on the device, and read back in one copy)
+    PinBuf plan_pin[N_CURSORS], seg_pin[N_CURSORS];
+    DevBuf plan_dev[N_CURSORS], seg_dev[N_CURSORS];
+    uint64_t caps[N_CURSORS] = {}, n_segs[N_CURSORS] = {};      // the bytes the last encode's members may take, its segments
     uint32_t grid_cap = 0;                               // resident workgroups the token streams are sized for
+    std::vector<pfgz::ChunkDesc> plan;                   // (scratch of encode_segments)
     static uint64_t chunks(uint64_t n) { return (n + pfgz::CHUNK - 1) / pfgz::CHUNK; }
-    static uint64_t bound(uint64_t n) { return chunks(n) * pfgz::SLOT_BYTES; }       // of the members of n bytes of text
-    uint64_t device_bytes() const { return slots.cap + sizes.cap + offs.cap + tokens.cap + cursors.cap; }
+    static uint64_t bound(uint64_t n) { return chunks(n) * pfgz::SLOT_BYTES; }       // of the members of n bytes of text in one segment
+    // of the members of n bytes in n_seg segments: every segment may end in a short chunk of its own
+    static uint64_t bound_segments(uint64_t n, uint64_t n_seg) { return pfgz::plan_chunks(n, n_seg) * pfgz::SLOT_BYTES; }
+    uint64_t device_bytes() const {
+        uint64_t b = slots.cap + sizes.cap + offs.cap + tokens.cap;
+        for (int w = 0; w < N_CURSORS; w++) b += plan_dev[w].cap + seg_dev[w].cap;
+        return b;
+    }
     int ensure(int n_cu);
     // On `st`: cursor w back to zero, the members of text[0 .. n) (device memory) written from `members` on, which holds
     // cap bytes, and the cursor -- their size -- on its way into w's pinned word.  t0 / t1, where given, are recorded
     // around the cursor's reset and the launches.
     int encode(hipStream_t st, Cursor w, const char* text, uint64_t n, uint32_t flags, char* members, uint64_t cap,
                hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+    // The same with members that end wherever a segment does: seg_end[0 .. n_seg) as pfgz::chunk_plan takes them
+    // (PF_ERR_ARG otherwise).  A launch takes BLOCK / CHUNK chunks of the plan; cap must hold the plan's worst case
+    // (bound_segments), or PF_ERR_ARG.  The offsets of the segments' first members travel back with the cursor.
+    int encode_segments(hipStream_t st, Cursor w, const char* text, uint64_t n, const uint64_t* seg_end, uint64_t n_seg, uint32_t flags,
+                        char* members, uint64_t cap, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
     // once the caller has synchronised with that encode: the bytes of its members; PF_ERR_STATE if they exceed its cap
     int member_bytes(Cursor w, uint64_t* z) const;
+    // and the offset behind every segment's members, member_end[n_seg of that encode]
+    int segment_ends(Cursor w, uint64_t* member_end) const;
 };
 // The device decoder: members in, text out, one wave per member (gz_inflate_kernel).  Its buffers hold the members of one
 // call, MAX_MEMBERS at most, each of SLOT_BYTES at most: device_bytes() <= MAX_MEMBERS * (SLOT_BYTES + 48) + slack; the

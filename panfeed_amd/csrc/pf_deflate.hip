@@ -1,7 +1,9 @@
 // pf_deflate.hip -- the deflate encoder and decoder on the device (format logic: pf_deflate.h) and the host models' entry points.
 //
-// gz_encode_kernel: one workgroup of 256 threads per chunk of CHUNK bytes (a grid of two workgroups per CU walks the
-// chunks).  The chunk's text is staged in LDS beside a hash table of 4 096 positions.  Matches are found in steps of 256
+// gz_encode_kernel: one workgroup of 256 threads per chunk of at most CHUNK bytes (a grid of two workgroups per CU walks
+// the chunks).  The chunks come from a plan in device memory (pfgz::chunk_plan): a chunk starts at any byte and may be
+// followed by another segment's text, of which nothing is staged -- every read of the text is a read of the chunk's own
+// bytes in LDS.  The chunk's text is staged in LDS beside a hash table of 4 096 positions.  Matches are found in steps of 256
 // positions, one per thread.  The positions look their 4-byte hash up and go into the table eight at a time, in text
 // order, by atomicMax: a position's candidate is the largest position with its hash among the groups of eight before its
 // own, whatever order the lanes ran in -- the same text gives the same bytes.  The compares then run 256 wide.  One lane
@@ -11,8 +13,9 @@
 // the exact sizes of the three block types, and places the tokens' bits by wave prefix sums into a staging area that
 // takes the place of the text and the table; the member leaves LDS in whole words.
 // LDS: 48 KiB of text + table, 10 KiB of tables -- under 64 KiB, two workgroups per CU within its 160 KiB.
-// gz_scan_kernel / gz_gather_kernel: the member sizes summed from an append cursor, the members copied from their
-// worst-case slots to their places, contiguous, so that one copy takes them to the host.
+// gz_scan_kernel / gz_gather_kernel: the member sizes summed from an append cursor, the offset of every segment's first
+// member noted behind the cursor, the members copied from their worst-case slots to their places, contiguous, so that one
+// copy takes them to the host.
 #include "pf_deflate.h"
 
 #include <cstdlib>
@@ -27,7 +30,7 @@ static_assert(SLOT_WORDS <= TEXT_WORDS + TAB_WORDS, "the staging area takes the 
 static_assert(CHUNK <= 32768, "distances reach 32 768 at most, a stored block 65 535 bytes");
 
 struct EncParams {
-    const uint8_t* text; uint64_t n; uint32_t nchunks, flags;
+    const uint8_t* text; const ChunkDesc* plan; uint32_t nchunks, flags;      // the launch's chunks: plan[0 .. nchunks)
     uint8_t* slots; uint32_t* sizes; uint32_t* tokens;
 };
 
@@ -76,17 +79,27 @@ __global__ __launch_bounds__(THREADS, 2) void gz_encode_kernel(EncParams P) {
     const bool lit_only = (P.flags & PF_GZ_LITERALS_ONLY) != 0;
 
     for (uint32_t chunk = blockIdx.x; chunk < P.nchunks; chunk += gridDim.x) {
-        const uint64_t start = (uint64_t)chunk * CHUNK;
-        const uint32_t n = (uint32_t)(P.n - start < CHUNK ? P.n - start : CHUNK);
-        const uint8_t* src = P.text + start;
+        const ChunkDesc d = P.plan[chunk];
+        const uint32_t n = min(d.len, CHUNK);
+        const uint8_t* src = P.text + d.start;
         uint8_t* slot = P.slots + (size_t)chunk * SLOT_BYTES;
-        // ---- stage the text, clear the table and the histograms
-        if ((reinterpret_cast<uintptr_t>(src) & 3) == 0) {
-            const uint32_t* src4 = reinterpret_cast<const uint32_t*>(src);
-            for (uint32_t i = tid; i < n / 4; i += THREADS) s_buf[i] = src4[i];
-            for (uint32_t i = (n & ~3u) + tid; i < n; i += THREADS) s_text[i] = src[i];
-        } else {
-            for (uint32_t i = tid; i < n; i += THREADS) s_text[i] = src[i];
+        // ---- stage the text, clear the table and the histograms.  Whole words come from aligned loads: a chunk that
+        // starts `a` bytes behind a word boundary takes every staged word from two neighbouring words of the text (the
+        // text's buffer starts on a word boundary, so the first of them is the buffer's own; the last word taken this
+        // way is the last that lies wholly inside the chunk), and its last few bytes one by one
+        {
+            const uint32_t a = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3);
+            uint32_t nw = n / 4;
+            if (a == 0) {
+                const uint32_t* src4 = reinterpret_cast<const uint32_t*>(src);
+                for (uint32_t i = tid; i < nw; i += THREADS) s_buf[i] = src4[i];
+            } else {
+                const uint32_t* src4 = reinterpret_cast<const uint32_t*>(src - a);
+                const uint32_t sh = 8 * a;
+                nw = n + a >= 8 ? (n + a - 8) / 4 + 1 : 0;
+                for (uint32_t i = tid; i < nw; i += THREADS) s_buf[i] = (src4[i] >> sh) | (src4[i + 1] << (32 - sh));
+            }
+            for (uint32_t i = 4 * nw + tid; i < n; i += THREADS) s_text[i] = src[i];
         }
         for (uint32_t i = tid; i < TAB_WORDS; i += THREADS) s_tab[i] = 0;
         for (uint32_t i = tid; i < 288; i += THREADS) { s_ll_hist[i] = i == 256 ? 1u : 0u; s_dyn.ll_len[i] = 0; }
@@ -242,8 +255,10 @@ __global__ __launch_bounds__(THREADS, 2) void gz_encode_kernel(EncParams P) {
 }
 
 // offs[i] = *cursor + the sizes before chunk i; *cursor advances by their sum.  One workgroup; thread 0 alone reads and
-// writes the cursor, the others get its value through LDS.
-__global__ __launch_bounds__(THREADS) void gz_scan_kernel(const uint32_t* sizes, uint32_t n, uint64_t* offs, uint64_t* cursor) {
+// writes the cursor, the others get its value through LDS.  seg_first[s] = the offset of segment s's first chunk: chunk i
+// is one if chunk i - 1 is another segment's (for the launch's first chunk the host says: first0).
+__global__ __launch_bounds__(THREADS) void gz_scan_kernel(const uint32_t* sizes, const ChunkDesc* plan, uint32_t n, uint32_t first0,
+                                                          uint64_t* offs, uint64_t* cursor, uint64_t* seg_first) {
     __shared__ uint32_t s_w[4];
     __shared__ uint64_t s_base;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -256,7 +271,11 @@ __global__ __launch_bounds__(THREADS) void gz_scan_kernel(const uint32_t* sizes,
         __syncthreads();
         uint32_t before = 0, total = 0;
         for (uint32_t w = 0; w < 4; w++) { total += s_w[w]; before += w < wave ? s_w[w] : 0; }
-        if (r + tid < n) offs[r + tid] = base + before + incl - v;
+        if (r + tid < n) {
+            const uint32_t i = r + tid, seg = plan[i].segment;
+            offs[i] = base + before + incl - v;
+            if (i ? plan[i - 1].segment != seg : first0 != 0) seg_first[seg] = base + before + incl - v;
+        }
         base += total;
         __syncthreads();
     }
@@ -366,44 +385,82 @@ int PfGzEncoder::ensure(int n_cu) {
     PFCHK(sizes.ensure(nch * 4, true));
     PFCHK(offs.ensure(nch * 8, true));
     PFCHK(tokens.ensure((uint64_t)grid * pfgz::CHUNK * 4, true));
-    if (!cursors.p) {
-        PFCHK(cursors.ensure(N_CURSORS * 8, true));
-        HIPCHK(hipMemset(cursors.p, 0, N_CURSORS * 8));
+    for (int w = 0; w < N_CURSORS; w++) {                 // (a one-segment text of a launch; a longer plan grows them)
+        PFCHK(plan_dev[w].ensure(nch * sizeof(pfgz::ChunkDesc), true));
+        PFCHK(plan_pin[w].ensure(nch * sizeof(pfgz::ChunkDesc), true));
+        PFCHK(seg_dev[w].ensure(64, true));
+        PFCHK(seg_pin[w].ensure(64, true));
     }
-    PFCHK(pin.ensure(64, true));
     grid_cap = grid;
     return PF_OK;
 }
 
 int PfGzEncoder::encode(hipStream_t st, Cursor w, const char* text, uint64_t n, uint32_t flags, char* members, uint64_t cap,
                         hipEvent_t t0, hipEvent_t t1) {
-    if (!grid_cap || !cursors.p) return fail(PF_ERR_STATE, "gzip encoder: not set up");
-    uint64_t* cursor = cursors.as<uint64_t>() + w;
-    caps[w] = cap;
+    const uint64_t end = n;
+    return encode_segments(st, w, text, n, &end, n ? 1 : 0, flags, members, cap, t0, t1);
+}
+
+int PfGzEncoder::encode_segments(hipStream_t st, Cursor w, const char* text, uint64_t n, const uint64_t* seg_end, uint64_t n_seg,
+                                 uint32_t flags, char* members, uint64_t cap, hipEvent_t t0, hipEvent_t t1) {
+    if (!grid_cap) return fail(PF_ERR_STATE, "gzip encoder: not set up");
+    if (!pfgz::chunk_plan(seg_end, n_seg, n, plan))
+        return fail(PF_ERR_ARG, "gzip encoder: the segment ends must not decrease and the last must be the text's size");
+    // every chunk of the plan may fill its slot: the members' buffer holds them all, or nothing is launched
+    if (plan.size() * (uint64_t)pfgz::SLOT_BYTES > cap)
+        return fail(PF_ERR_ARG, "gzip encoder: %zu chunks in %llu segments do not fit a buffer of %llu bytes", plan.size(),
+                    (unsigned long long)n_seg, (unsigned long long)cap);
+    const size_t plan_bytes = plan.size() * sizeof(pfgz::ChunkDesc), seg_bytes = (size_t)(1 + n_seg) * 8;
+    PFCHK(plan_dev[w].ensure(plan_bytes));
+    PFCHK(plan_pin[w].ensure(plan_bytes));
+    PFCHK(seg_dev[w].ensure(seg_bytes));
+    PFCHK(seg_pin[w].ensure(seg_bytes));
+    caps[w] = cap; n_segs[w] = n_seg;
+    uint64_t* cursor = seg_dev[w].as<uint64_t>();
+    uint64_t* seg_first = cursor + 1;
+    const pfgz::ChunkDesc* dplan = plan_dev[w].as<pfgz::ChunkDesc>();
+    if (plan_bytes) {
+        memcpy(plan_pin[w].p, plan.data(), plan_bytes);
+        HIPCHK(hipMemcpyAsync(plan_dev[w].p, plan_pin[w].p, plan_bytes, hipMemcpyHostToDevice, st));
+    }
     if (t0) HIPCHK(hipEventRecord(t0, st));
     HIPCHK(hipMemsetAsync(cursor, 0, 8, st));
-    for (uint64_t at = 0; at < n; at += BLOCK) {
-        const uint64_t m = std::min(BLOCK, n - at);
-        const uint32_t nch = (uint32_t)chunks(m);
-        pfgz::EncParams P{reinterpret_cast<const uint8_t*>(text) + at, m, nch, flags, slots.as<uint8_t>(), sizes.as<uint32_t>(),
+    if (n_seg) HIPCHK(hipMemsetAsync(seg_first, 0xFF, (size_t)n_seg * 8, st));      // (a segment without a chunk keeps this)
+    const size_t per_launch = (size_t)(BLOCK / pfgz::CHUNK);
+    for (size_t c0 = 0; c0 < plan.size(); c0 += per_launch) {
+        const uint32_t nch = (uint32_t)std::min(per_launch, plan.size() - c0);
+        const uint32_t first0 = c0 == 0 || plan[c0 - 1].segment != plan[c0].segment;
+        pfgz::EncParams P{reinterpret_cast<const uint8_t*>(text), dplan + c0, nch, flags, slots.as<uint8_t>(), sizes.as<uint32_t>(),
                           tokens.as<uint32_t>()};
         hipLaunchKernelGGL(pfgz::gz_encode_kernel, dim3(std::min(nch, grid_cap)), dim3(pfgz::THREADS), 0, st, P);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(pfgz::gz_scan_kernel, dim3(1), dim3(pfgz::THREADS), 0, st, sizes.as<uint32_t>(), nch, offs.as<uint64_t>(),
-                           cursor);
+        hipLaunchKernelGGL(pfgz::gz_scan_kernel, dim3(1), dim3(pfgz::THREADS), 0, st, sizes.as<uint32_t>(), dplan + c0, nch, first0,
+                           offs.as<uint64_t>(), cursor, seg_first);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(pfgz::gz_gather_kernel, dim3(nch), dim3(pfgz::THREADS), 0, st, slots.as<uint8_t>(), sizes.as<uint32_t>(),
                            offs.as<uint64_t>(), reinterpret_cast<uint8_t*>(members), cap);
         HIPCHK(hipGetLastError());
     }
     if (t1) HIPCHK(hipEventRecord(t1, st));
-    HIPCHK(hipMemcpyAsync(pin.as<uint64_t>() + w, cursor, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(seg_pin[w].p, cursor, seg_bytes, hipMemcpyDeviceToHost, st));
     return PF_OK;
 }
 
 int PfGzEncoder::member_bytes(Cursor w, uint64_t* z) const {
-    *z = pin.as<uint64_t>()[w];
+    if (!seg_pin[w].p) return fail(PF_ERR_STATE, "gzip encoder: not set up");
+    *z = seg_pin[w].as<uint64_t>()[0];
     if (*z > caps[w]) return fail(PF_ERR_STATE, "device gzip: a text's members exceed their bound");
+    return PF_OK;
+}
+
+int PfGzEncoder::segment_ends(Cursor w, uint64_t* member_end) const {
+    uint64_t next = 0;
+    PFCHK(member_bytes(w, &next));
+    const uint64_t* first = seg_pin[w].as<uint64_t>() + 1;
+    for (uint64_t i = n_segs[w]; i-- > 0;) {
+        member_end[i] = next;
+        if (first[i] != ~0ull) next = first[i];
+    }
     return PF_OK;
 }
 
@@ -457,6 +514,22 @@ int pf_gzip_host_model(const char* data, uint64_t n, uint32_t flags, char** out,
         return fail(PF_ERR_STATE, "pf_gzip_host_model: a block's size differs from its count");
     char* buf = (char*)malloc(members.size() ? members.size() : 1);
     if (!buf) return fail(PF_ERR_OOM, "pf_gzip_host_model: out of memory");
+    if (!members.empty()) memcpy(buf, members.data(), members.size());
+    *out = buf; *out_n = members.size();
+    return PF_OK;
+}
+
+int pf_gzip_host_model_segments(const char* data, uint64_t n, const uint64_t* seg_end, uint64_t n_seg, uint32_t flags, char** out,
+                                uint64_t* out_n, uint64_t* member_end) {
+    if ((!data && n) || (!seg_end && n_seg) || (!member_end && n_seg) || !out || !out_n)
+        return fail(PF_ERR_ARG, "pf_gzip_host_model_segments: null argument");
+    *out = nullptr; *out_n = 0;
+    std::vector<uint8_t> members;
+    const int rc = pfgz::host_model_segments(reinterpret_cast<const uint8_t*>(data), n, seg_end, n_seg, flags, members, member_end);
+    if (rc == 1) return fail(PF_ERR_ARG, "pf_gzip_host_model_segments: the segment ends must not decrease and the last must be n");
+    if (rc) return fail(PF_ERR_STATE, "pf_gzip_host_model_segments: a block's size differs from its count");
+    char* buf = (char*)malloc(members.size() ? members.size() : 1);
+    if (!buf) return fail(PF_ERR_OOM, "pf_gzip_host_model_segments: out of memory");
     if (!members.empty()) memcpy(buf, members.data(), members.size());
     *out = buf; *out_n = members.size();
     return PF_OK;

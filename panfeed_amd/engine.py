@@ -175,7 +175,7 @@ class Engine:
     def __init__(self, klength=31, canon=True, consider_missing=False, patfilt=True, maf=0.01,
                  multiple_files=False, max_strains=1024, stroi=(), device=0, pattern_capacity=0,
                  max_items=0, dedup=True, unit_dedup=True, key_binning=True, device_plan=False,
-                 targets_text_budget=8 << 30, device_gzip=False, device_gzip_flags=0):
+                 targets_text_budget=8 << 30, device_gzip=False, device_gzip_flags=0, device_gzip_clusters=False):
         self.L = _lib.load()
         # device memory a batch's kmers.tsv text may take when it is streamed to a targets_sink (stream_targets_device)
         self.targets_text_budget = int(targets_text_budget)
@@ -201,7 +201,10 @@ class Engine:
         # renderers are not affected, nor is a --multiple-files run: its device text is cut into the clusters' files, whose
         # gzip stays the host's
         self.device_gzip = bool(device_gzip) and not self.multiple_files
-        if self.device_gzip:
+        # device_gzip_clusters (multiple_files only): the per-cluster files' bodies leave the GPU as gzip members that end
+        # where a cluster's rows end (render_device_cluster_members, stream_targets_device's cluster sink)
+        self.device_gzip_clusters = bool(device_gzip_clusters) and self.multiple_files
+        if self.device_gzip or self.device_gzip_clusters:
             _lib.check(self.L.pf_set_device_gzip(self.ctx, 1, int(device_gzip_flags)))
         self.next_ordinal = 0
         self._md5_b64 = {}      # pattern id -> 24-char hash string (patterns seen so far)
@@ -312,7 +315,8 @@ class Engine:
         instead of str.  Under multiple_files the same two bodies come with their cluster boundaries
         (render_device_clusters): `out.per_cluster[i] = (idx, kt, kh_i, hp_i)` holds slices of them, and
         `out.stats["device_cluster_files"]` says for how many of the batch's clusters (0: the batch fell back to the host
-        renderers).
+        renderers).  With device_gzip_clusters those slices are GzipMembers (render_device_cluster_members) and
+        `out.stats["compressed_bytes"]` is the encoder's count of the batch's members.
         defer_patterns: leave hashes_to_patterns empty -- a rank of a sharded run renders its pattern rows after the
         run-global merge (`render_pattern_rows`).
         before_first_submit: called once, right before the first pf_submit (pipeline.run_files joins the thread that
@@ -365,7 +369,10 @@ class Engine:
                 texts = None
                 if device_text:
                     try:
-                        texts = self.render_device_clusters(hb) if self.multiple_files else self.render_device(hb, defer_patterns)
+                        if self.device_gzip_clusters:
+                            texts = self.render_device_cluster_members(hb)
+                        else:
+                            texts = self.render_device_clusters(hb) if self.multiple_files else self.render_device(hb, defer_patterns)
                     except _lib.PanfeedHipError as e:
                         # a batch the text kernels cannot lay out (too many passes, an over-long cluster name)
                         # goes through the host renderers instead
@@ -411,11 +418,20 @@ class Engine:
                 yield out
 
     def _cluster_output(self, hb, res, texts, cluster_targets_sink):
-        """the BatchOutput of a multiple_files batch whose text the device wrote: `texts` of render_device_clusters"""
-        kh, hp, kh_end, hp_end = texts
+        """the BatchOutput of a multiple_files batch whose text the device wrote: `texts` of render_device_clusters, or
+        of render_device_cluster_members -- the clusters' pieces are then GzipMembers that carry their text sizes"""
         n_cl = hb.n_clusters
         out = BatchOutput()
-        out.kmers_to_hashes, out.hashes_to_patterns = kh, hp
+        if self.device_gzip_clusters:
+            kh, hp, kh_end, hp_end, kh_text_end, hp_text_end = texts
+            kh_parts, hp_parts = ([GzipMembers(piece, size) for piece, size in zip(_cut(m, ends), np.diff(text_ends, prepend=np.uint64(0)))]
+                                  for m, ends, text_ends in ((kh, kh_end, kh_text_end), (hp, hp_end, hp_text_end)))
+            out.kmers_to_hashes = GzipMembers(kh, kh_text_end[-1] if n_cl else 0)
+            out.hashes_to_patterns = GzipMembers(hp, hp_text_end[-1] if n_cl else 0)
+        else:
+            kh, hp, kh_end, hp_end = texts
+            kh_parts, hp_parts = _cut(kh, kh_end), _cut(hp, hp_end)
+            out.kmers_to_hashes, out.hashes_to_patterns = kh, hp
         streamed, ranges, peak = 0, 0, 0
         self.stream_compressed = 0
         out.kmers_tsv = b""
@@ -432,9 +448,11 @@ class Engine:
             kt_parts = _cut(memoryview(out.kmers_tsv), self.target_cluster_ends(hb))
         else:
             kt_parts = [b""] * n_cl
-        out.per_cluster = list(zip(hb.idx, kt_parts, _cut(kh, kh_end), _cut(hp, hp_end)))
+        out.per_cluster = list(zip(hb.idx, kt_parts, kh_parts, hp_parts))
         out.stats = _batch_stats(hb, res, self.pattern_count(), kmers_tsv_streamed=streamed, kmers_tsv_ranges=ranges,
                                  kmers_tsv_peak_device_bytes=peak, device_cluster_files=n_cl)
+        if self.device_gzip_clusters:          # the members the GPU made of this batch, by the encoder's own count
+            out.stats["compressed_bytes"] = len(kh) + len(hp) + self.stream_compressed
         out.timing = self.timing()
         return out
 
@@ -567,6 +585,20 @@ class Engine:
                                                     C.byref(hp), C.byref(hn), kh_end.ctypes.data, hp_end.ctypes.data))
         return _mem(kh, kn.value), _mem(hp, hn.value), kh_end[:n_cl], hp_end[:n_cl]
 
+    def render_device_cluster_members(self, hb):
+        """render_device_clusters for an engine made with device_gzip_clusters (pf_render_device_cluster_members): the
+        two bodies as gzip members no one of which holds rows of two clusters -- (kh members, hp members, kh_end, hp_end,
+        kh_text_end, hp_text_end): per cluster of `hb` the offset just behind its members in each view, and behind its
+        rows in the text they decode to.  A cluster's piece is a gzip file's body as it stands."""
+        n_cl = hb.n_clusters
+        names = (C.c_char_p * max(n_cl, 1))(*[s.encode() for s in hb.idx])
+        extra = "".join(hb.extra_keys).encode("latin-1") if hb.extra_keys else None
+        kh, kn, hp, hn = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        ends = [np.zeros(max(n_cl, 1), dtype=np.uint64) for _ in range(4)]
+        _lib.check(self.L.pf_render_device_cluster_members(self.ctx, names, extra, len(hb.extra_keys), C.byref(kh), C.byref(kn),
+                                                           C.byref(hp), C.byref(hn), *[e.ctypes.data for e in ends]))
+        return (_mem(kh, kn.value), _mem(hp, hn.value)) + tuple(e[:n_cl] for e in ends)
+
     def target_cluster_ends(self, hb):
         """per cluster of `hb`, the offset just behind its rows in the kmers.tsv text last written on the device for `hb`
         (render_targets_device, or a stream_targets_device under way or over): the library's per-sequence ends
@@ -652,6 +684,8 @@ class Engine:
         memoryview of pinned memory, valid during the call) -- pf_kmers_tsv_stream_begin / _next.  The blocks joined are
         the bytes of `render_targets_device(hb)`.  cluster_sink: `sink` is a cluster sink, `sink(idx, block)` -- the blocks are
         cut at the cluster ends as they arrive, and every cluster of `hb` gets at least one call (output.ClusterSplitter).
+        Under device_gzip_clusters the stream is told the cluster ends (pf_kmers_tsv_stream_cuts), so that members end
+        there, and the cluster sink gets GzipMembers of whole members with their text sizes (output.ClusterMemberSplitter).
         Returns (bytes, ranges, peak device text bytes)."""
         t0 = time.time()
         budget = self.targets_text_budget if budget is None else int(budget)
@@ -666,20 +700,36 @@ class Engine:
                                                         C.byref(peak)))
             ptr, nb = C.c_void_p(), C.c_uint64()
             splitter = None
-            if cluster_sink:
+            gzip_on = self.device_gzip or self.device_gzip_clusters
+            if cluster_sink and gzip_on:
+                # members must end where a cluster's rows end: the stream is told the ends, and says of every block where
+                # they fell in its members
+                from .output import ClusterMemberSplitter
+                ends = np.ascontiguousarray(self.target_cluster_ends(hb), dtype=np.uint64)
+                _lib.check(self.L.pf_kmers_tsv_stream_cuts(self.ctx, ends.ctypes.data if len(ends) else None, len(ends)))
+                splitter = ClusterMemberSplitter(ends, hb.idx, sink)
+                cut_text, cut_member = (np.zeros(max(len(ends), 1), dtype=np.uint64) for _ in range(2))
+                t_off, t_n, n_cuts = C.c_uint64(), C.c_uint64(), C.c_uint64()
+
+                def sink(block):
+                    _lib.check(self.L.pf_kmers_tsv_stream_block_cuts(self.ctx, C.byref(t_off), C.byref(t_n), cut_text.ctypes.data,
+                                                                     cut_member.ctypes.data, len(cut_text), C.byref(n_cuts)))
+                    k = int(n_cuts.value)
+                    splitter(block.view, t_off.value, t_n.value, zip(cut_text[:k].tolist(), cut_member[:k].tolist()))
+            elif cluster_sink:
                 from .output import ClusterSplitter
                 sink = splitter = ClusterSplitter(self.target_cluster_ends(hb), hb.idx, sink)
             while True:
                 _lib.check(self.L.pf_kmers_tsv_stream_next(self.ctx, C.byref(ptr), C.byref(nb)))
                 if not nb.value:
                     break
-                if self.device_gzip:            # a block's members; the text bytes behind them are asked for below
+                if gzip_on:                     # a block's members; the text bytes behind them are asked for below
                     sink(GzipMembers(_mem(ptr, nb.value), None))
                     self.stream_compressed += int(nb.value)
                 else:
                     sink(_mem(ptr, nb.value))
                     streamed += int(nb.value)
-            if self.device_gzip:
+            if gzip_on:
                 raw = (C.c_uint64 * 3)()
                 _lib.check(self.L.pf_device_gzip_text_bytes(self.ctx, raw))
                 streamed = int(raw[2])

@@ -5,7 +5,7 @@ import io
 import os
 
 from . import _lib
-from .engine import KMERS_TSV_HEADER, KMERS_TO_HASHES_HEADER, GzipMembers, _mem, hashes_to_patterns_header
+from .engine import KMERS_TSV_HEADER, KMERS_TO_HASHES_HEADER, GzipMembers, _mem, hashes_to_patterns_header, text_len
 
 
 class ParallelGzipWriter:
@@ -238,28 +238,33 @@ def write_strain_headers(hash_pat, kmer_hash, strains):
     kmer_hash.flush()
 
 
-def write_cluster_dir(output, idx, strains, kmers_tsv, kmers_to_hashes, hashes_to_patterns, compress=False):
+def write_cluster_dir(output, idx, strains, kmers_tsv, kmers_to_hashes, hashes_to_patterns, compress=False, device_gzip=False):
     """--multiple-files: the three files of gene cluster `idx`, headers and all, in `<output>/<idx>/`
     (panfeed.py:38-43, 159-167).  The bodies: str, or the bytes-like text the GPU wrote (slices of a batch's device
-    text).  kmers_tsv None: `kmers.tsv` has been written already, by a ClusterKmersFiles sink."""
+    text).  kmers_tsv None: `kmers.tsv` has been written already, by a ClusterKmersFiles sink.
+    device_gzip: `.gz` files made of members (MemberGzipWriter) -- the header line is a member the host makes, a body that
+    is a GzipMembers (Engine(device_gzip_clusters=True)) is appended as it is, a body that is text becomes a member made
+    here.  Returns the bytes of those host-made members behind the headers (0 without device_gzip)."""
     path = os.path.join(output, idx)
     os.makedirs(path, exist_ok=True)
+    files = []
     if kmers_tsv is not None:
-        ks = create_kmer_stroi(path, compress)
+        ks = create_kmer_stroi(path, compress, device_gzip)
         write_text(ks, kmers_tsv)
-        ks.close()
-    hash_pat, kmer_hash = create_hash_files(path, compress)
+        files.append(ks)
+    hash_pat, kmer_hash = create_hash_files(path, compress, device_gzip)
     write_strain_headers(hash_pat, kmer_hash, strains)
     write_text(hash_pat, hashes_to_patterns)
     write_text(kmer_hash, kmers_to_hashes)
-    hash_pat.close()
-    kmer_hash.close()
+    files += [hash_pat, kmer_hash]
+    for fh in files:
+        fh.close()
+    return sum(fh.host_bytes for fh in files) if device_gzip else 0
 
 
-def write_cluster_dirs(output, strains, out, compress=False):
-    """write_cluster_dir for every cluster of a multiple_files batch (`out`: its BatchOutput)"""
-    for idx, kt, kh, hp in out.per_cluster:
-        write_cluster_dir(output, idx, strains, kt, kh, hp, compress)
+def write_cluster_dirs(output, strains, out, compress=False, device_gzip=False):
+    """write_cluster_dir for every cluster of a multiple_files batch (`out`: its BatchOutput); returns their sum"""
+    return sum(write_cluster_dir(output, idx, strains, kt, kh, hp, compress, device_gzip) for idx, kt, kh, hp in out.per_cluster)
 
 
 class ClusterSplitter:
@@ -304,28 +309,85 @@ class ClusterSplitter:
             self._next_cluster()
 
 
+class ClusterMemberSplitter:
+    """ClusterSplitter for a text that arrives as gzip members (the kmers.tsv stream under device gzip, told the clusters'
+    ends by pf_kmers_tsv_stream_cuts): a member cannot be cut, so every block comes with the places where the ends fall
+    in it.  Call it with every block, in order -- `(members, text_off, text_bytes, cuts)`: the block's members, the text
+    they decode to as an offset into the whole text and a size, and `(text offset, member offset)` of every cluster end
+    strictly inside that text, ascending -- then `close()`.  `sink(name, GzipMembers(piece, text bytes))` is called with
+    whole members only, at least once for every cluster, in order, with an empty piece where a cluster has no byte.
+    ValueError where the pieces do not add up: a block out of place, a cut outside its block, a piece over a cluster's
+    end, text missing at the close."""
+
+    def __init__(self, ends, names, sink):
+        self.ends, self.names, self.sink = [int(e) for e in ends], list(names), sink
+        if len(self.ends) != len(self.names) or any(b < a for a, b in zip(self.ends, self.ends[1:])):
+            raise ValueError("one end per cluster, non-decreasing")
+        self.at = 0             # text bytes taken so far
+        self.cluster = 0        # the cluster the next byte belongs to, if it has any left
+        self.called = False     # whether that cluster has had a call
+
+    def _next_cluster(self):
+        if not self.called:
+            self.sink(self.names[self.cluster], GzipMembers(memoryview(b""), 0))
+        self.cluster += 1
+        self.called = False
+
+    def __call__(self, members, text_off, text_bytes, cuts=()):
+        view = memoryview(members)
+        text_off, text_bytes = int(text_off), int(text_bytes)
+        if text_off != self.at:
+            raise ValueError(f"a block of the text from byte {text_off}, the text so far ends at byte {self.at}")
+        points = [(text_off, 0)] + [(int(t), int(m)) for t, m in cuts] + [(text_off + text_bytes, len(view))]
+        for (t0, m0), (t1, m1) in zip(points, points[1:]):
+            if t1 < t0 or m1 < m0 or (t1 == t0) != (m1 == m0):
+                raise ValueError(f"text bytes {t0}..{t1} in member bytes {m0}..{m1} of a block of {len(view)}: not a piece")
+            if t1 == t0:
+                continue
+            while self.cluster < len(self.ends) and self.ends[self.cluster] <= t0:
+                self._next_cluster()
+            if self.cluster == len(self.ends):
+                raise ValueError(f"{t1 - t0} bytes of text behind the last cluster's end")
+            if t1 > self.ends[self.cluster]:
+                raise ValueError(f"members of text bytes {t0}..{t1} pass the end of cluster {self.names[self.cluster]} "
+                                 f"at byte {self.ends[self.cluster]}")
+            self.sink(self.names[self.cluster], GzipMembers(view[m0:m1], t1 - t0))
+            self.called = True
+        self.at = text_off + text_bytes
+
+    def close(self):
+        if self.ends and self.at != self.ends[-1]:
+            raise ValueError(f"the text ended at byte {self.at}, the last cluster's end is {self.ends[-1]}")
+        while self.cluster < len(self.ends):
+            self._next_cluster()
+
+
 class ClusterKmersFiles:
     """A cluster_targets_sink (Engine.run_batches) that writes `<output>/<idx>/kmers.tsv[.gz]`: the file is made, header
     first, at a cluster's first call and closed when the next cluster's first call comes, or by `close()` -- the calls of
-    one cluster stand together.  `bytes`: the rows written so far."""
+    one cluster stand together.  `bytes`: the rows written so far.  device_gzip: the files are MemberGzipWriters -- a
+    block that is a GzipMembers is appended as it is, text becomes a member made here; `host_bytes`: the bytes of those
+    host-made members behind the headers, in the files closed so far."""
 
-    def __init__(self, output, compress=False):
-        self.output, self.compress = output, compress
+    def __init__(self, output, compress=False, device_gzip=False):
+        self.output, self.compress, self.device_gzip = output, compress, device_gzip
         self.idx, self.fh = None, None
-        self.bytes = 0
+        self.bytes = self.host_bytes = 0
 
     def __call__(self, idx, block):
         if self.fh is None or idx != self.idx:
             self.close()
             path = os.path.join(self.output, idx)
             os.makedirs(path, exist_ok=True)
-            self.idx, self.fh = idx, create_kmer_stroi(path, self.compress)
+            self.idx, self.fh = idx, create_kmer_stroi(path, self.compress, self.device_gzip)
         write_text(self.fh, block)
-        self.bytes += len(block)
+        self.bytes += text_len(block)
 
     def close(self):
         if self.fh is not None:
             self.fh.close()
+            if self.device_gzip:
+                self.host_bytes += self.fh.host_bytes
             self.fh = None
 
 

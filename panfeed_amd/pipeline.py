@@ -65,9 +65,11 @@ def settle_context(pg, eng, open_reader):
 class _FileRun:
     """What the steps of one `run_files` call share."""
 
-    def __init__(self, output, compress, multiple_files, device_gzip=False):
+    def __init__(self, output, compress, multiple_files, device_gzip=False, device_gzip_clusters=False):
         self.output, self.compress, self.multiple_files = output, compress, multiple_files
-        self.device_gzip = device_gzip and not multiple_files      # (per-cluster files keep the host's gzip)
+        self.device_gzip = device_gzip and not multiple_files      # (per-cluster files keep the host's gzip under this switch)
+        self.device_gzip_clusters = device_gzip_clusters and multiple_files     # (they have their own)
+        self.host_member_bytes = 0                      # per-cluster files: the members the writer thread compressed behind the headers
         self.t_start = time.perf_counter()
         # where the wall time went: opening + parsing the inputs, creating the context, uploading the genomes, then the
         # overlapped stages of the batches (Engine.run_batches: read + pack on its thread, pf_submit = upload + kernels,
@@ -117,7 +119,7 @@ class _FileRun:
             write_text(self.kmer_hash, o.kmers_to_hashes)
             write_text(self.hash_pat, o.hashes_to_patterns)
             return
-        write_cluster_dirs(self.output, self.strains, o, self.compress)
+        self.host_member_bytes += write_cluster_dirs(self.output, self.strains, o, self.compress, self.device_gzip_clusters)
 
     def writer(self, q, slots):
         while True:
@@ -208,7 +210,8 @@ def _write_batches(run, eng, pg, stats, batch_clusters, device_text):
         # the writer thread's only when a batch's rows come as one object -- the host renderers' path)
         # (under multiple_files each cluster's rows into its own directory's kmers.tsv, cut at the cluster ends)
         sink = (lambda blk: write_text(run.kmer_stroi, blk)) if (device_text and not run.multiple_files) else None
-        cluster_sink = ClusterKmersFiles(run.output, run.compress) if (device_text and run.multiple_files) else None
+        cluster_sink = (ClusterKmersFiles(run.output, run.compress, run.device_gzip_clusters)
+                        if (device_text and run.multiple_files) else None)
         batches = eng.run_pangenome(pg, batch_clusters=batch_clusters, device_text=device_text,
                                     before_first_submit=run.wait_for_genomes, targets_sink=sink,
                                     cluster_targets_sink=cluster_sink)
@@ -225,7 +228,7 @@ def _write_batches(run, eng, pg, stats, batch_clusters, device_text):
             stats["patterns"] = o.stats.get("patterns", stats["patterns"])
             if run.multiple_files:              # the clusters whose files are cut from text the GPU wrote
                 stats["device_cluster_files"] = stats.get("device_cluster_files", 0) + o.stats.get("device_cluster_files", 0)
-            if run.device_gzip:                 # the members the GPU made of this batch, by the encoder's own count
+            if run.device_gzip or run.device_gzip_clusters:     # the members the GPU made of this batch, by the encoder's own count
                 stats["compressed_bytes"] = stats.get("compressed_bytes", 0) + o.stats.get("compressed_bytes", 0)
             stats["bytes"] += (text_len(o.kmers_tsv) + text_len(o.kmers_to_hashes) + text_len(o.hashes_to_patterns) +
                                o.stats.get("kmers_tsv_streamed", 0))
@@ -238,6 +241,9 @@ def _write_batches(run, eng, pg, stats, batch_clusters, device_text):
                 fh.close()
                 if run.device_gzip:             # and the members the host compressed behind the header (fallback batches)
                     stats["compressed_bytes"] = stats.get("compressed_bytes", 0) + fh.host_bytes
+        if run.device_gzip_clusters:            # the same for the per-cluster files: what their two writers compressed
+            stats["compressed_bytes"] = (stats.get("compressed_bytes", 0) + run.host_member_bytes +
+                                         (cluster_sink.host_bytes if cluster_sink is not None else 0))
     if run.write_err is not None:
         raise run.write_err
 
@@ -246,7 +252,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
               patfilt=True, maf=0.01, upstream=0, downstream=0, downstream_start_codon=False, targets=(), genes=None,
               compress=False, multiple_files=False, batch_clusters=256, resident=True, device_text=True, device=0,
               max_items=0, pattern_capacity=0, overlap=True, one_pass=True, raise_missing=False, device_gzip=False,
-              targets_text_budget=None):
+              targets_text_budget=None, device_gzip_clusters=False):
     """One directory of outputs (`kmers.tsv`, `kmers_to_hashes.tsv`, `hashes_to_patterns.tsv`, `.gz` under
     `compress`; under `multiple_files` one such directory per gene cluster, `<output>/<cluster>/`, the pattern set
     starting empty in each: `panfeed.py:35-43,153-167`) from a panaroo table and a directory (or file of files) of GFFs.  Option names and meaning follow
@@ -258,10 +264,15 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
     writes leaves it as gzip members (larger files than `compress` writes, in less time -- profiles/gzip_device/ -- that read back as
     the same text), `stats["bytes"]` keeps counting text and `stats["compressed_bytes"]` is what the files hold behind their
     header members: the encoder's own count of every batch's members plus the members the host compressed.  Under `multiple_files` it changes nothing: the per-cluster files are cut from text the GPU wrote (device_text) and keep the host's gzip.
+    device_gzip_clusters (`--gpu-compress-clusters`): the per-cluster files of `multiple_files` compressed on the GPU -- it
+    implies `compress` and changes nothing without `multiple_files`; every cluster's bodies leave the GPU as gzip members
+    that end where the cluster's rows end and are appended behind the header line's member as they are;
+    `stats["compressed_bytes"]` as above.
     targets_text_budget: device memory a batch's kmers.tsv text may take (default: the engine's).
     Returns a dict of counters."""
-    compress = bool(compress or device_gzip)
-    run = _FileRun(output, compress, multiple_files, bool(device_gzip))
+    device_gzip_clusters = bool(device_gzip_clusters and multiple_files)
+    compress = bool(compress or device_gzip or device_gzip_clusters)
+    run = _FileRun(output, compress, multiple_files, bool(device_gzip), device_gzip_clusters)
     err = existing_output_error(output)
     if err is not None:
         raise err
@@ -271,6 +282,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
                                     canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
                                     multiple_files=multiple_files, stroi=set(targets), device=device,
                                     pattern_capacity=pattern_capacity, device_gzip=run.device_gzip,
+                                    device_gzip_clusters=run.device_gzip_clusters,
                                     **({} if targets_text_budget is None else {"targets_text_budget": targets_text_budget}))
     open_reader = functools.partial(Pangenome, presence_absence, gffdir, fastadir, upstream, downstream,
                                     downstream_start_codon, targets=targets, genes=genes, raise_missing=raise_missing)

@@ -192,10 +192,11 @@ def _bind_device(device):
 def run_records_sharded(records, output, strains, rank, world, dist=None, device=None, klength=31, canon=True,
                         consider_missing=False, patfilt=True, maf=0.01, targets=(), compress=False,
                         multiple_files=False, batch_clusters=256, weights=None, method="owner", gpu=0,
-                        max_items=0, pattern_capacity=0, dedup=True, device_gzip=False, targets_text_budget=None):
+                        max_items=0, pattern_capacity=0, dedup=True, device_gzip=False, targets_text_budget=None,
+                        device_gzip_clusters=False):
     """One rank of a sharded run over in-memory reference-shaped records (the tuples input.py:468 yields; every rank
     is given the same list).  Returns a dict of counters; the files are complete once rank 0 returns.  device_gzip,
-    targets_text_budget: as in `run_files_sharded`; where either is given the batches' texts are written on the device
+    device_gzip_clusters, targets_text_budget: as in `run_files_sharded`; where either is given the batches' texts are written on the device
     (the members and the ranges are the device's), else by the host renderers as before."""
     from .distributed import shard_range
     from .engine import Engine
@@ -203,18 +204,18 @@ def run_records_sharded(records, output, strains, rank, world, dist=None, device
     records = list(records)
     start, stop = shard_range(len(records), rank, world, weights)
     max_strains = max([len(strains)] + [max(len(r[0]), len(r[2])) for r in records] + [1])
-    compress, device_gzip = _gzip_modes(compress, device_gzip, multiple_files)
+    compress, device_gzip, device_gzip_clusters = _gzip_modes(compress, device_gzip, multiple_files, device_gzip_clusters)
     eng = Engine(klength=klength, canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
                  multiple_files=multiple_files, max_strains=(max_strains + 31) // 32 * 32, stroi=set(targets) if targets else (),
                  device=gpu, max_items=max_items, pattern_capacity=pattern_capacity, dedup=dedup, device_gzip=device_gzip,
-                 **_budget(targets_text_budget))
+                 device_gzip_clusters=device_gzip_clusters, **_budget(targets_text_budget))
     try:
         eng.next_ordinal = start                          # global ordinals: first_seen is unique over the run
         batches = functools.partial(eng.run_stream, records[start:stop], batch_clusters=batch_clusters,
                                     defer_patterns=not multiple_files,
-                                    device_text=device_gzip or targets_text_budget is not None)
+                                    device_text=device_gzip or device_gzip_clusters or targets_text_budget is not None)
         return _drive(eng, batches, output, strains, rank, world, dist, device, compress, multiple_files, method,
-                      (start, stop), device_gzip)
+                      (start, stop), device_gzip, device_gzip_clusters)
     finally:
         eng.close()
 
@@ -223,12 +224,15 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
                       canon=True, consider_missing=False, patfilt=True, maf=0.01, upstream=0, downstream=0,
                       downstream_start_codon=False, targets=(), genes=None, compress=False, multiple_files=False,
                       batch_clusters=256, resident=True, device_text=True, method="owner", gpu=0, max_items=0,
-                      pattern_capacity=0, device_gzip=False, raise_missing=False, targets_text_budget=None):
+                      pattern_capacity=0, device_gzip=False, raise_missing=False, targets_text_budget=None,
+                      device_gzip_clusters=False):
     """`pipeline.run_files` on N GPUs: every rank opens the pangenome, takes its range of the processing order
     (balanced by the number of gene entries per table row) and writes its parts; rank 0 assembles.  Option names as
     in the reference's CLI (`__main__.py:86-186`).
     device_gzip (`--gpu-compress`): implies `compress`; the text a rank's GPU writes leaves it as gzip members, and the
     assembled files are ones the device decoder takes (under `multiple_files` the host's gzip stays, as on one GPU).
+    device_gzip_clusters (`--gpu-compress-clusters`): with `multiple_files`, the per-cluster files compressed on each
+    rank's GPU, as in `pipeline.run_files`; implies `compress`.
     raise_missing (`--stop-on-missing`): the reader's; a rank that fails in its shard makes every rank fail before the
     pattern exchange, `.parts/` is removed, and so is the output directory where that leaves it empty (under
     `multiple_files` the clusters written until then stay, and the directory with them).  targets_text_budget: device memory a batch's kmers.tsv text may take (default: the engine's) --
@@ -238,7 +242,7 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
     from .pipeline import _peek_n_strains, existing_output_error, settle_context, sized_engine
     _bind_device(device)
     targets = tuple(targets or ())
-    compress, device_gzip = _gzip_modes(compress, device_gzip, multiple_files)
+    compress, device_gzip, device_gzip_clusters = _gzip_modes(compress, device_gzip, multiple_files, device_gzip_clusters)
     err = existing_output_error(output)
     _barrier(dist, device)                                        # every rank has looked before rank 0 creates it
     if err is not None:
@@ -250,7 +254,7 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
                                     canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
                                     multiple_files=multiple_files, stroi=set(targets), device=gpu,
                                     pattern_capacity=pattern_capacity, device_gzip=device_gzip,
-                                    **_budget(targets_text_budget))
+                                    device_gzip_clusters=device_gzip_clusters, **_budget(targets_text_budget))
     open_reader = functools.partial(Pangenome, presence_absence, gffdir, fastadir, upstream, downstream,
                                     downstream_start_codon, targets=targets, genes=genes, raise_missing=raise_missing)
     # every rank reads every genome (a cluster's sequences come from all of them): with resident genomes the files go to
@@ -278,7 +282,7 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
                                     defer_patterns=not multiple_files)
         try:
             stats = _drive(eng, batches, output, pg.strains, rank, world, dist, device, compress, multiple_files, method,
-                           (start, stop), device_gzip)
+                           (start, stop), device_gzip, device_gzip_clusters)
         except Exception:
             if rank == 0:                                 # (made above: it goes again where the failed run left it empty,
                 try:                                      # so that the command can be run again)
@@ -294,10 +298,12 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
             eng.close()
 
 
-def _gzip_modes(compress, device_gzip, multiple_files):
-    """(compress, device_gzip) as a run uses them: device_gzip implies compress; per-cluster directories keep the host's
-    gzip"""
-    return bool(compress or device_gzip), bool(device_gzip) and not multiple_files
+def _gzip_modes(compress, device_gzip, multiple_files, device_gzip_clusters=False):
+    """(compress, device_gzip, device_gzip_clusters) as a run uses them: either device switch implies compress;
+    per-cluster directories keep the host's gzip under device_gzip and have the device's under device_gzip_clusters,
+    which means nothing without them"""
+    clusters = bool(device_gzip_clusters) and bool(multiple_files)
+    return bool(compress or device_gzip or clusters), bool(device_gzip) and not multiple_files, clusters
 
 
 def _budget(targets_text_budget):
@@ -335,7 +341,7 @@ def _shard_batches(batches, each, dist, device, after_failure=None):
 
 
 def _drive(eng, make_batches, output, strains, rank, world, dist, device, compress, multiple_files, method, rng,
-           device_gzip=False):
+           device_gzip=False, device_gzip_clusters=False):
     """`make_batches(targets_sink=...)`: the engine's generator of BatchOutput over this rank's range.  A run in which a
     rank's shard failed assembles nothing and leaves no `.parts/` behind; under `multiple_files` the directories of the
     clusters written until then stay."""
@@ -343,16 +349,22 @@ def _drive(eng, make_batches, output, strains, rank, world, dist, device, compre
     if multiple_files:
         # a cluster's kmers.tsv rows go into its directory as they leave the device, its other two files when the batch
         # is handed over (slices of the device text, or the host renderers' strings)
-        kmers_files = ClusterKmersFiles(output, compress)
+        kmers_files = ClusterKmersFiles(output, compress, device_gzip_clusters)
+        if device_gzip_clusters:
+            stats["compressed_bytes"] = 0     # the GPU's members by the encoder's count, and the host's behind the headers
 
         def each(o):
             kmers_files.close()
-            write_cluster_dirs(output, list(strains), o, compress)
+            host = write_cluster_dirs(output, list(strains), o, compress, device_gzip_clusters)
             add_batch_stats(stats, o, ("clusters", "instances"))
+            if device_gzip_clusters:
+                stats["compressed_bytes"] += o.stats.get("compressed_bytes", 0) + host
         try:
             _shard_batches(make_batches(cluster_targets_sink=kmers_files), each, dist, device)
         finally:
             kmers_files.close()
+        if device_gzip_clusters:
+            stats["compressed_bytes"] += kmers_files.host_bytes
         _barrier(dist, device)
         return stats
     stats.update(kmers_tsv_streamed=0, kmers_tsv_ranges=0, kmers_tsv_peak_device_bytes=0)

@@ -4,6 +4,7 @@
 // It runs the device encoder's host model (csrc/pf_deflate.h: the format functions the kernel uses too) and the host
 // path's pf_gzip_members (csrc/pf_gzip.cpp) over the edge cases of tests/deflate_cases.py (cases 1-9, generated here),
 // under every flag set that applies, and inflates every result with zlib: it must be the input.  Exit status 0: all equal.
+// Case 10 is the segmented container (chunk_plan, host_model_segments) over the segment shapes of tests/deflate_segments.py.
 // The cases that are built in Python only (wide_tokens, whose widest tokens put_bits writes into three words, and the
 // fibonacci text that reaches the code length limit) come from a file, given as the one argument:
 //   python tests/deflate_cases.py /tmp/deflate_cases.bin && /tmp/deflate_host_check /tmp/deflate_cases.bin
@@ -65,6 +66,43 @@ void check(const std::string& name, const Bytes& data, uint32_t flags) {
             failures++; fprintf(stderr, "FAIL pf_gzip_members %s\n", name.c_str());
         }
         free(out);
+    }
+}
+
+// the host model over segments: every segment's members are those of its text alone, member_end their running sum, the
+// whole inflates to the text; lens: the segments' lengths
+void check_segments(const std::string& name, const Bytes& data, const std::vector<uint64_t>& lens, uint32_t flags) {
+    std::vector<uint64_t> ends, member_end(lens.size() + 1);
+    uint64_t at = 0;
+    for (uint64_t l : lens) ends.push_back(at += l);
+    Bytes members, want, back;
+    checks++;
+    bool ok = at == data.size() &&
+              pfgz::host_model_segments(data.data(), data.size(), ends.data(), ends.size(), flags, members, member_end.data()) == 0;
+    at = 0;
+    for (size_t i = 0; ok && i < lens.size(); i++) {
+        Bytes one;
+        ok = pfgz::host_model(data.data() + at, lens[i], flags, one);
+        want.insert(want.end(), one.begin(), one.end());
+        ok = ok && member_end[i] == want.size();
+        at += lens[i];
+    }
+    ok = ok && members == want && gunzip(members.data(), members.size(), back) && back == data;
+    if (!ok) { failures++; fprintf(stderr, "FAIL host model segments %s flags %u\n", name.c_str(), flags); }
+}
+// ends that are no plan are refused, nothing is read through them
+void check_refusals() {
+    const Bytes d(10, 'x');
+    Bytes members;
+    uint64_t member_end[3];
+    const uint64_t decreasing[3] = {5, 3, 10}, short_of_n[2] = {4, 9}, past_n[2] = {4, 11};
+    checks++;
+    if (pfgz::host_model_segments(d.data(), 10, decreasing, 3, 0, members, member_end) != 1 ||
+        pfgz::host_model_segments(d.data(), 10, short_of_n, 2, 0, members, member_end) != 1 ||
+        pfgz::host_model_segments(d.data(), 10, past_n, 2, 0, members, member_end) != 1 ||
+        pfgz::host_model_segments(d.data(), 10, nullptr, 0, 0, members, member_end) != 1 ||
+        pfgz::host_model_segments(d.data(), 0, nullptr, 0, 0, members, member_end) != 0 || !members.empty()) {
+        failures++; fprintf(stderr, "FAIL host model segments: refusals\n");
     }
 }
 
@@ -144,6 +182,20 @@ int main(int argc, char** argv) {
         check("no_distance_symbol", perm, PF_GZ_DYNAMIC_ONLY);
     }
     check("one_literal_symbol", Bytes(64, 'a'), PF_GZ_LITERALS_ONLY | PF_GZ_DYNAMIC_ONLY);         // 9
+    {                                                                                            // 10: segments
+        const std::vector<std::vector<uint64_t>> shapes = {{0}, {1}, {C}, {C + 1}, {0, 5, 0, 0, C - 1, 1, C, C + 1, 2 * C + 3, 0},
+                                                           std::vector<uint64_t>(2100, 40)};
+        for (const auto& lens : shapes) {
+            uint64_t n = 0;
+            for (uint64_t l : lens) n += l;
+            Bytes d((size_t)n);                          // rows of a few repeating fields, then bytes no code shortens
+            for (size_t i = 0; i < d.size(); i++) d[i] = "ACGTTGCA\tgroup_12\tq83hdkPZ\n"[(i * 7 + i / 29) % 27];
+            const Bytes noise = random_bytes(10, std::min<size_t>(4096, d.size() / 2));
+            std::copy(noise.begin(), noise.end(), d.begin() + (d.size() - noise.size()) / 3);
+            for (uint32_t f : {0u, PF_GZ_FIXED_ONLY, PF_GZ_DYNAMIC_ONLY, PF_GZ_LITERALS_ONLY}) check_segments("segments", d, lens, f);
+        }
+        check_refusals();
+    }
     if (argc > 1 && !check_file(argv[1])) { failures++; fprintf(stderr, "FAIL reading %s\n", argv[1]); }
     printf("%d checks, %d failures\n", checks, failures);
     return failures ? 1 : 0;
