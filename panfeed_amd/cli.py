@@ -172,11 +172,13 @@ def main(argv=None, run=None, launch=None, rank_entry=None):
     if args.gpu_compress_clusters:
         more["device_gzip_clusters"] = True
     from ._lib import PanfeedHipError
+    from .engine import gzip_modes
+    compress = gzip_modes(args.compress, args.gpu_compress, args.multiple_files, args.gpu_compress_clusters)[0]
     if many:
         options = dict(fastadir=args.fasta, klength=k, canon=not args.non_canonical, consider_missing=args.consider_missing,
                        patfilt=not args.no_filter, maf=args.maf, upstream=args.upstream, downstream=args.downstream,
                        downstream_start_codon=args.downstream_start_codon, targets=tuple(sorted(targets)),
-                       genes=sorted(genes) if genes is not None else None, compress=args.compress or args.gpu_compress or args.gpu_compress_clusters,
+                       genes=sorted(genes) if genes is not None else None, compress=compress,
                        multiple_files=args.multiple_files, batch_clusters=args.batch_clusters, gpu=args.device,
                        raise_missing=args.stop_on_missing, **more)
         if not as_rank:
@@ -200,7 +202,7 @@ def main(argv=None, run=None, launch=None, rank_entry=None):
                     canon=not args.non_canonical, consider_missing=args.consider_missing, patfilt=not args.no_filter,
                     maf=args.maf, upstream=args.upstream, downstream=args.downstream,
                     downstream_start_codon=args.downstream_start_codon, targets=tuple(sorted(targets)),
-                    genes=sorted(genes) if genes is not None else None, compress=args.compress or args.gpu_compress or args.gpu_compress_clusters,
+                    genes=sorted(genes) if genes is not None else None, compress=compress,
                     multiple_files=args.multiple_files, batch_clusters=args.batch_clusters, device=args.device,
                     raise_missing=args.stop_on_missing, **more)
     except PanfeedHipError as e:          # the reader's message under --stop-on-missing, or the library's error

@@ -5,6 +5,7 @@ ctypes, and renders the three TSV bodies exactly as the reference writes them
 One ``Engine`` = one panfeed run on one GPU: it owns the run-global pattern set
 (panfeed.py:149-150) in device memory, so clusters must be fed in processing order.
 """
+import collections
 import contextlib
 import ctypes as C
 import time
@@ -148,6 +149,12 @@ class BatchOutput:
         """whether kmers_to_hashes and hashes_to_patterns are gzip members (GzipMembers) instead of text"""
         return isinstance(self.kmers_to_hashes, GzipMembers) and isinstance(self.hashes_to_patterns, GzipMembers)
 
+    @property
+    def text_bytes(self):
+        """bytes of text the batch stands for: its three bodies and the kmers.tsv rows that went to a sink"""
+        return (text_len(self.kmers_tsv) + text_len(self.kmers_to_hashes) + text_len(self.hashes_to_patterns) +
+                self.stats.get("kmers_tsv_streamed", 0))
+
 
 def _batch_stats(hb, res, patterns, **streamed):
     """the counters of one batch (BatchOutput.stats); `streamed`: the kmers_tsv_* counters of a device-text batch"""
@@ -165,10 +172,31 @@ def _cut(view, ends):
     return parts
 
 
+def _cut_members(view, ends, text_ends):
+    """gzip members cut at `ends`, where the text they decode to is cut at `text_ends`: (the whole, its pieces), each a
+    GzipMembers that carries its text size"""
+    pieces = [GzipMembers(piece, size) for piece, size in zip(_cut(view, ends), np.diff(text_ends, prepend=np.uint64(0)))]
+    return GzipMembers(view, text_ends[-1] if len(text_ends) else 0), pieces
+
+
+# the two bodies of a batch the device wrote (views, or GzipMembers) and, under multiple_files, each one's pieces per cluster
+BatchBodies = collections.namedtuple("BatchBodies", "kh hp kh_parts hp_parts")
+
+
 def add_batch_stats(totals, out, keys=("clusters", "instances", "kept_kmers", "device_ms")):
-    """add a finished batch's counters (and its device time) to the totals a run reports"""
+    """add a finished batch's counters to the totals a run reports; "device_ms": its device time, "bytes": the text it
+    stands for"""
     for key in keys:
-        totals[key] += out.timing.get("total_ms", 0.0) if key == "device_ms" else out.stats.get(key, 0)
+        totals[key] = totals.get(key, 0) + (out.timing.get("total_ms", 0.0) if key == "device_ms" else
+                                            out.text_bytes if key == "bytes" else out.stats.get(key, 0))
+
+
+def gzip_modes(compress, device_gzip, multiple_files, device_gzip_clusters=False):
+    """(compress, device_gzip, device_gzip_clusters) as a run uses them: either device switch implies compress;
+    per-cluster directories keep the host's gzip under device_gzip and have the device's under device_gzip_clusters,
+    which means nothing without them"""
+    clusters = bool(device_gzip_clusters) and bool(multiple_files)
+    return bool(compress or device_gzip or clusters), bool(device_gzip) and not multiple_files, clusters
 
 
 class Engine:
@@ -200,10 +228,9 @@ class Engine:
         # device_gzip: the texts the GPU writes (render_device, stream_targets_device) leave it as gzip members; the host
         # renderers are not affected, nor is a --multiple-files run: its device text is cut into the clusters' files, whose
         # gzip stays the host's
-        self.device_gzip = bool(device_gzip) and not self.multiple_files
         # device_gzip_clusters (multiple_files only): the per-cluster files' bodies leave the GPU as gzip members that end
         # where a cluster's rows end (render_device_cluster_members, stream_targets_device's cluster sink)
-        self.device_gzip_clusters = bool(device_gzip_clusters) and self.multiple_files
+        _, self.device_gzip, self.device_gzip_clusters = gzip_modes(False, device_gzip, self.multiple_files, device_gzip_clusters)
         if self.device_gzip or self.device_gzip_clusters:
             _lib.check(self.L.pf_set_device_gzip(self.ctx, 1, int(device_gzip_flags)))
         self.next_ordinal = 0
@@ -339,6 +366,7 @@ class Engine:
         # the text stage (device text + its copy to the host, or pf_fetch + the host renderers)
         st = self.stages = {"pack_busy_s": 0.0, "pack_wait_s": 0.0, "submit_s": 0.0, "device_ms": 0.0, "text_s": 0.0,
                             "batches": 0}
+        sink = cluster_targets_sink if self.multiple_files else targets_sink      # (each mode has its own; the other's is not used)
 
         def pack_next():
             t0 = time.perf_counter()
@@ -366,94 +394,92 @@ class Engine:
                 t1 = time.perf_counter()
                 st["submit_s"] += t1 - t0
                 st["batches"] += 1
-                texts = None
-                if device_text:
-                    try:
-                        if self.device_gzip_clusters:
-                            texts = self.render_device_cluster_members(hb)
-                        else:
-                            texts = self.render_device_clusters(hb) if self.multiple_files else self.render_device(hb, defer_patterns)
-                    except _lib.PanfeedHipError as e:
-                        # a batch the text kernels cannot lay out (too many passes, an over-long cluster name)
-                        # goes through the host renderers instead
-                        if e.status not in (_lib.ERR_CAPACITY, _lib.ERR_ARG):
-                            raise
-                if texts is not None and self.multiple_files:
-                    out = self._cluster_output(hb, res, texts, cluster_targets_sink)
-                elif texts is not None:
-                    out = BatchOutput()
-                    out.kmers_to_hashes, out.hashes_to_patterns = texts
-                    # target strains: their rows written by the GPU too (the next submit reuses the device's text
-                    # block, so the rows come over now)
-                    streamed, ranges, peak = 0, 0, 0
-                    self.stream_compressed = 0
-                    if hb.n_targets and targets_sink is not None:
-                        # in ranges of at most targets_text_budget bytes of device memory
-                        streamed, ranges, peak = self.stream_targets_device(hb, targets_sink)
-                        out.kmers_tsv = b""
-                    else:
-                        out.kmers_tsv = bytes(self.render_targets_device(hb)) if hb.n_targets else b""
-                    out.stats = _batch_stats(hb, res, self.pattern_count(), kmers_tsv_streamed=streamed,
-                                             kmers_tsv_ranges=ranges, kmers_tsv_peak_device_bytes=peak)
-                    if self.device_gzip:
-                        out.stats["compressed_bytes"] = len(texts[0]) + len(texts[1]) + self.stream_compressed
-                    out.timing = self.timing()
-                else:
-                    out = self._render(hb, self.fetch(), defer_patterns)
-                    if targets_sink is not None and out.kmers_tsv and not self.multiple_files:
-                        # (the rows of this batch must not overtake, or be overtaken by, the streamed rows of its neighbours)
-                        out.stats["kmers_tsv_streamed"] = len(out.kmers_tsv)
-                        targets_sink(out.kmers_tsv)
-                        out.kmers_tsv = ""
-                    if self.multiple_files:
-                        out.stats["device_cluster_files"] = 0
-                        if cluster_targets_sink is not None:
-                            out.stats["kmers_tsv_streamed"] = len(out.kmers_tsv)
-                            for i, (idx, kt, kh, hp) in enumerate(out.per_cluster):
-                                cluster_targets_sink(idx, kt.encode())
-                                out.per_cluster[i] = (idx, None, kh, hp)
-                            out.kmers_tsv = ""
+                out = self._batch_text(hb, res, device_text, defer_patterns, sink)
                 st["text_s"] += time.perf_counter() - t1
                 st["device_ms"] += out.timing.get("total_ms", 0.0)
                 yield out
 
-    def _cluster_output(self, hb, res, texts, cluster_targets_sink):
-        """the BatchOutput of a multiple_files batch whose text the device wrote: `texts` of render_device_clusters, or
-        of render_device_cluster_members -- the clusters' pieces are then GzipMembers that carry their text sizes"""
-        n_cl = hb.n_clusters
-        out = BatchOutput()
-        if self.device_gzip_clusters:
-            kh, hp, kh_end, hp_end, kh_text_end, hp_text_end = texts
-            kh_parts, hp_parts = ([GzipMembers(piece, size) for piece, size in zip(_cut(m, ends), np.diff(text_ends, prepend=np.uint64(0)))]
-                                  for m, ends, text_ends in ((kh, kh_end, kh_text_end), (hp, hp_end, hp_text_end)))
-            out.kmers_to_hashes = GzipMembers(kh, kh_text_end[-1] if n_cl else 0)
-            out.hashes_to_patterns = GzipMembers(hp, hp_text_end[-1] if n_cl else 0)
-        else:
-            kh, hp, kh_end, hp_end = texts
-            kh_parts, hp_parts = _cut(kh, kh_end), _cut(hp, hp_end)
-            out.kmers_to_hashes, out.hashes_to_patterns = kh, hp
-        streamed, ranges, peak = 0, 0, 0
-        self.stream_compressed = 0
-        out.kmers_tsv = b""
-        if cluster_targets_sink is not None:
-            kt_parts = [None] * n_cl
-            if hb.n_targets:
-                streamed, ranges, peak = self.stream_targets_device(hb, cluster_targets_sink, cluster_sink=True)
+    # ------------------------------------------------------------------ the text stage of one batch
+    def _batch_text(self, hb, res, device_text, defer_patterns, sink):
+        """the BatchOutput of the batch just submitted: its text written by the device (device_text), or -- without it,
+        or for a batch the text kernels cannot lay out (too many passes, an over-long cluster name) -- by the host
+        renderers.  sink: the run's targets_sink, or under multiple_files its cluster_targets_sink."""
+        if device_text:
+            try:
+                bodies = self._device_bodies(hb, defer_patterns)
+            except _lib.PanfeedHipError as e:
+                if e.status not in (_lib.ERR_CAPACITY, _lib.ERR_ARG):
+                    raise
             else:
-                for idx in hb.idx:
-                    cluster_targets_sink(idx, b"")
+                return self._device_batch(hb, res, bodies, sink)
+            # pf_fetch mirrors the digests of this batch's new patterns only: those of the batches the device rendered
+            # were never fetched, and the host's kmers_to_hashes rows name them -- the whole pool's digests come over first
+            self.export_patterns()
+        return self._host_batch(hb, defer_patterns, sink)
+
+    def _device_bodies(self, hb, defer_patterns):
+        """kmers_to_hashes and hashes_to_patterns of the last submit by the render call of the engine's mode"""
+        if self.device_gzip_clusters:       # the clusters' pieces are GzipMembers that carry their text sizes
+            kh, hp, kh_end, hp_end, kh_text_end, hp_text_end = self.render_device_cluster_members(hb)
+            (kh, kh_parts), (hp, hp_parts) = _cut_members(kh, kh_end, kh_text_end), _cut_members(hp, hp_end, hp_text_end)
+            return BatchBodies(kh, hp, kh_parts, hp_parts)
+        if self.multiple_files:
+            kh, hp, kh_end, hp_end = self.render_device_clusters(hb)
+            return BatchBodies(kh, hp, _cut(kh, kh_end), _cut(hp, hp_end))
+        return BatchBodies(*self.render_device(hb, defer_patterns), None, None)
+
+    def _device_rows(self, hb, sink):
+        """the kmers.tsv rows of a device-text batch, written by the GPU too (the next submit reuses the device's text
+        block, so the rows come over now): streamed to `sink` in ranges of at most targets_text_budget bytes of device
+        memory, or gathered.  Returns (kmers_tsv, its per-cluster pieces under multiple_files -- None each where they went
+        to the sink --, streamed, ranges, peak, compressed)."""
+        per_cluster = self.multiple_files
+        text, parts, counts, compressed = b"", None, (0, 0, 0), 0
+        if sink is not None and hb.n_targets:
+            counts = self.stream_targets_device(hb, sink, cluster_sink=True) if per_cluster else self.stream_targets_device(hb, sink)
+            compressed = self.stream_compressed
+        elif sink is not None and per_cluster:
+            for idx in hb.idx:
+                sink(idx, b"")
         elif hb.n_targets:
-            # (the next submit reuses the device's text block, so the rows come over now)
-            out.kmers_tsv = bytes(self.render_targets_device(hb))
-            kt_parts = _cut(memoryview(out.kmers_tsv), self.target_cluster_ends(hb))
-        else:
-            kt_parts = [b""] * n_cl
-        out.per_cluster = list(zip(hb.idx, kt_parts, kh_parts, hp_parts))
+            text = bytes(self.render_targets_device(hb))
+        if per_cluster and sink is not None:
+            parts = [None] * hb.n_clusters
+        elif per_cluster:
+            parts = _cut(memoryview(text), self.target_cluster_ends(hb)) if hb.n_targets else [b""] * hb.n_clusters
+        return (text, parts) + tuple(counts) + (compressed,)
+
+    def _device_batch(self, hb, res, bodies, sink):
+        """the BatchOutput of a batch whose text the device wrote"""
+        out = BatchOutput()
+        out.kmers_to_hashes, out.hashes_to_patterns = bodies.kh, bodies.hp
+        out.kmers_tsv, kt_parts, streamed, ranges, peak, compressed = self._device_rows(hb, sink)
+        more = {}
+        if self.multiple_files:
+            out.per_cluster = list(zip(hb.idx, kt_parts, bodies.kh_parts, bodies.hp_parts))
+            more["device_cluster_files"] = hb.n_clusters
         out.stats = _batch_stats(hb, res, self.pattern_count(), kmers_tsv_streamed=streamed, kmers_tsv_ranges=ranges,
-                                 kmers_tsv_peak_device_bytes=peak, device_cluster_files=n_cl)
-        if self.device_gzip_clusters:          # the members the GPU made of this batch, by the encoder's own count
-            out.stats["compressed_bytes"] = len(kh) + len(hp) + self.stream_compressed
+                                 kmers_tsv_peak_device_bytes=peak, **more)
+        if self.device_gzip or self.device_gzip_clusters:      # the members the GPU made of this batch, by the encoder's own count
+            out.stats["compressed_bytes"] = len(bodies.kh) + len(bodies.hp) + compressed
         out.timing = self.timing()
+        return out
+
+    def _host_batch(self, hb, defer_patterns, sink):
+        """the BatchOutput of a batch by the host renderers; its kmers.tsv rows go to `sink` now (the rows of this batch
+        must not overtake, or be overtaken by, the streamed rows of its neighbours)"""
+        out = self._render(hb, self.fetch(), defer_patterns)
+        if self.multiple_files:
+            out.stats["device_cluster_files"] = 0
+        if sink is not None and (self.multiple_files or out.kmers_tsv):
+            out.stats["kmers_tsv_streamed"] = len(out.kmers_tsv)
+            if self.multiple_files:
+                for i, (idx, kt, kh, hp) in enumerate(out.per_cluster):
+                    sink(idx, kt.encode())
+                    out.per_cluster[i] = (idx, None, kh, hp)
+            else:
+                sink(out.kmers_tsv)
+            out.kmers_tsv = ""
         return out
 
     def result_checksum(self):
@@ -554,50 +580,43 @@ class Engine:
         out.timing = self.timing()
         return out
 
+    def _render_call(self, fn, hb, flags=(), n_ends=0):
+        """one render of the last submit's two bodies on the device by `fn` (pf_render_device_ex after `flags`, or one
+        of its per-cluster kin with `n_ends` arrays of per-cluster ends behind the texts): the two memoryviews, then the
+        ends, one uint64 per cluster of `hb` in each"""
+        n_cl = hb.n_clusters
+        names = (C.c_char_p * max(n_cl, 1))(*[s.encode() for s in hb.idx])
+        extra = "".join(hb.extra_keys).encode("latin-1") if hb.extra_keys else None
+        kh, kn, hp, hn = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        ends = [np.zeros(max(n_cl, 1), dtype=np.uint64) for _ in range(n_ends)]
+        _lib.check(fn(self.ctx, names, extra, len(hb.extra_keys), *flags, C.byref(kh), C.byref(kn), C.byref(hp), C.byref(hn),
+                      *[e.ctypes.data for e in ends]))
+        return (_mem(kh, kn.value), _mem(hp, hn.value)) + tuple(e[:n_cl] for e in ends)
+
     def render_device(self, hb, defer_patterns=False):
         """(kmers_to_hashes body, hashes_to_patterns body) of the last submit as memoryviews over pinned host memory,
         the text having been written by the GPU (pf_render_device): no pf_fetch, no bytes -> str; valid until the
         render after the next one.  kmers.tsv rows (target strains) still come from `_render` / `_render_targets`."""
-        C_ = hb.n_clusters
-        names = (C.c_char_p * max(C_, 1))(*[s.encode() for s in hb.idx])
-        extra = "".join(hb.extra_keys).encode("latin-1") if hb.extra_keys else None
-        kh, kn, hp, hn = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
-        _lib.check(self.L.pf_render_device_ex(self.ctx, names, extra, len(hb.extra_keys),
-                                              _lib.RENDER_NO_PATTERN_ROWS if defer_patterns else 0,
-                                              C.byref(kh), C.byref(kn), C.byref(hp), C.byref(hn)))
+        kh, hp = self._render_call(self.L.pf_render_device_ex, hb, (_lib.RENDER_NO_PATTERN_ROWS if defer_patterns else 0,))
         if self.device_gzip:
             raw = (C.c_uint64 * 3)()
             _lib.check(self.L.pf_device_gzip_text_bytes(self.ctx, raw))
-            return GzipMembers(_mem(kh, kn.value), raw[0]), GzipMembers(_mem(hp, hn.value), raw[1])
-        return _mem(kh, kn.value), _mem(hp, hn.value)
+            return GzipMembers(kh, raw[0]), GzipMembers(hp, raw[1])
+        return kh, hp
 
     def render_device_clusters(self, hb):
         """render_device for an engine made with multiple_files (pf_render_device_clusters): (kmers_to_hashes body,
         hashes_to_patterns body, kh_end, hp_end) of the last submit -- the two memoryviews over pinned host memory (valid
         until the render after the next one) and, per cluster of `hb`, the offset just behind its rows in each (uint64
         arrays; a cluster without rows repeats the end before it).  Bodies only: the headers are the writer's."""
-        n_cl = hb.n_clusters
-        names = (C.c_char_p * max(n_cl, 1))(*[s.encode() for s in hb.idx])
-        extra = "".join(hb.extra_keys).encode("latin-1") if hb.extra_keys else None
-        kh, kn, hp, hn = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
-        kh_end, hp_end = np.zeros(max(n_cl, 1), dtype=np.uint64), np.zeros(max(n_cl, 1), dtype=np.uint64)
-        _lib.check(self.L.pf_render_device_clusters(self.ctx, names, extra, len(hb.extra_keys), C.byref(kh), C.byref(kn),
-                                                    C.byref(hp), C.byref(hn), kh_end.ctypes.data, hp_end.ctypes.data))
-        return _mem(kh, kn.value), _mem(hp, hn.value), kh_end[:n_cl], hp_end[:n_cl]
+        return self._render_call(self.L.pf_render_device_clusters, hb, n_ends=2)
 
     def render_device_cluster_members(self, hb):
         """render_device_clusters for an engine made with device_gzip_clusters (pf_render_device_cluster_members): the
         two bodies as gzip members no one of which holds rows of two clusters -- (kh members, hp members, kh_end, hp_end,
         kh_text_end, hp_text_end): per cluster of `hb` the offset just behind its members in each view, and behind its
         rows in the text they decode to.  A cluster's piece is a gzip file's body as it stands."""
-        n_cl = hb.n_clusters
-        names = (C.c_char_p * max(n_cl, 1))(*[s.encode() for s in hb.idx])
-        extra = "".join(hb.extra_keys).encode("latin-1") if hb.extra_keys else None
-        kh, kn, hp, hn = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
-        ends = [np.zeros(max(n_cl, 1), dtype=np.uint64) for _ in range(4)]
-        _lib.check(self.L.pf_render_device_cluster_members(self.ctx, names, extra, len(hb.extra_keys), C.byref(kh), C.byref(kn),
-                                                           C.byref(hp), C.byref(hn), *[e.ctypes.data for e in ends]))
-        return (_mem(kh, kn.value), _mem(hp, hn.value)) + tuple(e[:n_cl] for e in ends)
+        return self._render_call(self.L.pf_render_device_cluster_members, hb, n_ends=4)
 
     def target_cluster_ends(self, hb):
         """per cluster of `hb`, the offset just behind its rows in the kmers.tsv text last written on the device for `hb`
@@ -699,46 +718,51 @@ class Engine:
             _lib.check(self.L.pf_kmers_tsv_stream_begin(self.ctx, arr, n, budget, C.byref(total), C.byref(ranges),
                                                         C.byref(peak)))
             ptr, nb = C.c_void_p(), C.c_uint64()
-            splitter = None
             gzip_on = self.device_gzip or self.device_gzip_clusters
-            if cluster_sink and gzip_on:
-                # members must end where a cluster's rows end: the stream is told the ends, and says of every block where
-                # they fell in its members
-                from .output import ClusterMemberSplitter
-                ends = np.ascontiguousarray(self.target_cluster_ends(hb), dtype=np.uint64)
-                _lib.check(self.L.pf_kmers_tsv_stream_cuts(self.ctx, ends.ctypes.data if len(ends) else None, len(ends)))
-                splitter = ClusterMemberSplitter(ends, hb.idx, sink)
-                cut_text, cut_member = (np.zeros(max(len(ends), 1), dtype=np.uint64) for _ in range(2))
-                t_off, t_n, n_cuts = C.c_uint64(), C.c_uint64(), C.c_uint64()
-
-                def sink(block):
-                    _lib.check(self.L.pf_kmers_tsv_stream_block_cuts(self.ctx, C.byref(t_off), C.byref(t_n), cut_text.ctypes.data,
-                                                                     cut_member.ctypes.data, len(cut_text), C.byref(n_cuts)))
-                    k = int(n_cuts.value)
-                    splitter(block.view, t_off.value, t_n.value, zip(cut_text[:k].tolist(), cut_member[:k].tolist()))
-            elif cluster_sink:
-                from .output import ClusterSplitter
-                sink = splitter = ClusterSplitter(self.target_cluster_ends(hb), hb.idx, sink)
+            take, close = self._cluster_blocks(hb, sink, gzip_on) if cluster_sink else (sink, None)
             while True:
                 _lib.check(self.L.pf_kmers_tsv_stream_next(self.ctx, C.byref(ptr), C.byref(nb)))
                 if not nb.value:
                     break
                 if gzip_on:                     # a block's members; the text bytes behind them are asked for below
-                    sink(GzipMembers(_mem(ptr, nb.value), None))
+                    take(GzipMembers(_mem(ptr, nb.value), None))
                     self.stream_compressed += int(nb.value)
                 else:
-                    sink(_mem(ptr, nb.value))
+                    take(_mem(ptr, nb.value))
                     streamed += int(nb.value)
             if gzip_on:
                 raw = (C.c_uint64 * 3)()
                 _lib.check(self.L.pf_device_gzip_text_bytes(self.ctx, raw))
                 streamed = int(raw[2])
-            if splitter is not None:
-                splitter.close()
+            if close is not None:
+                close()
         if streamed != int(total.value):
             raise _lib.PanfeedHipError(_lib.ERR_STATE, f"kmers.tsv stream: {streamed} bytes handed out of {total.value}")
         self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": time.time() - t1, "copy_s": 0.0}
         return streamed, int(ranges.value), int(peak.value)
+
+    def _cluster_blocks(self, hb, sink, gzip_on):
+        """(take, close) for the blocks of the kmers.tsv stream just begun for `hb` where `sink` is a cluster sink: a
+        splitter of the output module that cuts them at the clusters' ends.  Text can be cut anywhere
+        (output.ClusterSplitter takes the blocks as they are); members must end where a cluster's rows end, so under
+        gzip_on the stream is told the ends and asked of every block where they fell in its members
+        (output.ClusterMemberSplitter)."""
+        from . import output
+        ends = np.ascontiguousarray(self.target_cluster_ends(hb), dtype=np.uint64)
+        if not gzip_on:
+            splitter = output.ClusterSplitter(ends, hb.idx, sink)
+            return splitter, splitter.close
+        _lib.check(self.L.pf_kmers_tsv_stream_cuts(self.ctx, ends.ctypes.data if len(ends) else None, len(ends)))
+        splitter = output.ClusterMemberSplitter(ends, hb.idx, sink)
+        cut_text, cut_member = (np.zeros(max(len(ends), 1), dtype=np.uint64) for _ in range(2))
+        t_off, t_n, n_cuts = C.c_uint64(), C.c_uint64(), C.c_uint64()
+
+        def take(block):
+            _lib.check(self.L.pf_kmers_tsv_stream_block_cuts(self.ctx, C.byref(t_off), C.byref(t_n), cut_text.ctypes.data,
+                                                             cut_member.ctypes.data, len(cut_text), C.byref(n_cuts)))
+            k = int(n_cuts.value)
+            splitter(block.view, t_off.value, t_n.value, zip(cut_text[:k].tolist(), cut_member[:k].tolist()))
+        return take, splitter.close
 
     def _render_targets(self, hb, metas, owned=False):
         """kmers.tsv rows of `metas` (packing.SeqMeta, in order) through pf_render_kmers_tsv: str, or the library's own

@@ -8,30 +8,72 @@ from . import _lib
 from .engine import KMERS_TSV_HEADER, KMERS_TO_HASHES_HEADER, GzipMembers, _mem, hashes_to_patterns_header, text_len
 
 
-class ParallelGzipWriter:
-    """Text handle over a .gz file, like gzip.open(path, "wt", compresslevel=9) (input.py:239-241, 255-258), whose
-    deflate work is done by the library's host threads: what is written is buffered, cut at line ends into chunks
-    and compressed as independent gzip members (pf_gzip_members).  Reads back as the same text with any gzip reader."""
+class _GzipWriter:
+    """What the writers of .gz files share: `write` takes str or bytes-like text (`_take` gets its bytes, never empty),
+    `close` is done once -- the rest of the text goes out (`_finish`), and a file that needs it (`_is_empty`) gets one
+    empty member, so that it is a valid gzip stream --, `with` closes.  MTIME: of the members made here (None: the time
+    of writing, like gzip.open's)."""
+    MTIME = 0
 
-    def __init__(self, path, compresslevel=9, buffer_bytes=64 << 20, chunk_bytes=4 << 20):
-        self.L = _lib.load()
+    def __init__(self, path, compresslevel):
         self.fh = open(path, "wb")
-        self.level, self.buffer_bytes, self.chunk_bytes = compresslevel, buffer_bytes, chunk_bytes
-        self.parts, self.pending = [], 0
-        self.wrote = False
+        self.level = compresslevel
         self.closed = False
+
+    def _compress(self, data):
+        import gzip
+        return gzip.compress(bytes(data), compresslevel=self.level, mtime=self.MTIME)
 
     def write(self, text):
         b = text.encode() if isinstance(text, str) else bytes(text)
-        if not b:
-            return 0
+        if b:
+            self._take(b)
+        return len(text)
+
+    def flush(self):
+        # a flush of the reference's GzipFile only empties Python-side buffers into the deflate stream; members are
+        # cut when enough text has gathered, so nothing is forced out here except at close
+        self.fh.flush()
+
+    def _finish(self):
+        pass
+
+    def close(self):
+        if self.closed:
+            return
+        self._finish()
+        if self._is_empty():
+            self.fh.write(self._compress(b""))
+        self.fh.close()
+        self.closed = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class ParallelGzipWriter(_GzipWriter):
+    """Text handle over a .gz file, like gzip.open(path, "wt", compresslevel=9) (input.py:239-241, 255-258), whose
+    deflate work is done by the library's host threads: what is written is buffered, cut at line ends into chunks
+    and compressed as independent gzip members (pf_gzip_members).  Reads back as the same text with any gzip reader."""
+    MTIME = None
+
+    def __init__(self, path, compresslevel=9, buffer_bytes=64 << 20, chunk_bytes=4 << 20):
+        super().__init__(path, compresslevel)
+        self.L = _lib.load()
+        self.buffer_bytes, self.chunk_bytes = buffer_bytes, chunk_bytes
+        self.parts, self.pending = [], 0
+        self.wrote = False
+
+    def _take(self, b):
         self.parts.append(b)
         self.pending += len(b)
         if self.pending >= self.buffer_bytes:
-            self._emit()
-        return len(text)
+            self._finish()
 
-    def _emit(self):
+    def _finish(self):
         data = b"".join(self.parts)
         self.parts, self.pending = [], 0
         if not data:
@@ -44,29 +86,11 @@ class ParallelGzipWriter:
             self.L.pf_free_text(out)
         self.wrote = True
 
-    def flush(self):
-        # a flush of the reference's GzipFile only empties Python-side buffers into the deflate stream; members are
-        # cut when enough text has gathered, so nothing is forced out here except at close
-        self.fh.flush()
-
-    def close(self):
-        if self.closed:
-            return
-        self._emit()
-        if not self.wrote:                      # an empty file is still a valid (empty) gzip stream
-            import gzip
-            self.fh.write(gzip.compress(b"", compresslevel=self.level))
-        self.fh.close()
-        self.closed = True
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+    def _is_empty(self):
+        return not self.wrote
 
 
-class MemberGzipWriter:
+class MemberGzipWriter(_GzipWriter):
     """A .gz file made of gzip members from two sources: `write(text)` compresses the text on the host into one member
     (the header line; the batches that fell back to the host renderers), `write_members(view)` appends members that are
     complete already -- the GPU's (Engine(device_gzip=True)) -- as they are.  The first write is the file's header, so an
@@ -74,26 +98,19 @@ class MemberGzipWriter:
     first member's, and that of the members compressed here behind the header."""
 
     def __init__(self, path, compresslevel=9):
-        self.fh = open(path, "wb")
-        self.level = compresslevel
+        super().__init__(path, compresslevel)
         self.bytes_written = 0
         self.header_bytes = None
         self.host_bytes = 0
-        self.closed = False
 
-    def write(self, text):
-        import gzip
-        b = text.encode() if isinstance(text, str) else bytes(text)
-        if not b:
-            return 0
-        member = gzip.compress(b, compresslevel=self.level, mtime=0)
+    def _take(self, b):
+        member = self._compress(b)
         if self.header_bytes is None:
             self.header_bytes = len(member)
         else:
             self.host_bytes += len(member)
         self.fh.write(member)
         self.bytes_written += len(member)
-        return len(text)
 
     def write_members(self, view):
         if len(view):
@@ -102,26 +119,11 @@ class MemberGzipWriter:
             self.fh.write(view)
             self.bytes_written += len(view)
 
-    def flush(self):
-        self.fh.flush()
-
-    def close(self):
-        if self.closed:
-            return
-        if not self.bytes_written:              # nothing at all was written: an empty member
-            import gzip
-            self.fh.write(gzip.compress(b"", compresslevel=self.level, mtime=0))
-        self.fh.close()
-        self.closed = True
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+    def _is_empty(self):
+        return not self.bytes_written
 
 
-class SmallMemberGzipWriter:
+class SmallMemberGzipWriter(_GzipWriter):
     """A .gz file every member of which the device decoder takes (pf_gunzip_device): panfeed-get-kmers --gz-output's.
     `write_members(view)` appends the GPU's members as they are; `write(text)` takes text made on the host -- the header
     line, what pandas printed -- and compresses it into members of at most `chunk_bytes` of text each, the file's first
@@ -132,16 +134,14 @@ class SmallMemberGzipWriter:
     was written to stays empty."""
 
     def __init__(self, path, chunk_bytes, compresslevel=6, part=False):
-        self.fh = open(path, "wb")
-        self.chunk, self.level, self.part = int(chunk_bytes), compresslevel, bool(part)
+        super().__init__(path, compresslevel)
+        self.chunk, self.part = int(chunk_bytes), bool(part)
         self.held = b""                          # host text not yet in a member
         self.first_line = not self.part          # the file's first line has not gone out yet
         self.bytes_written = self.text_bytes = self.host_members = 0
-        self.closed = False
 
     def _member(self, text):
-        import gzip
-        member = gzip.compress(bytes(text), compresslevel=self.level, mtime=0)
+        member = self._compress(text)
         self.fh.write(member)
         self.bytes_written += len(member)
         self.text_bytes += len(text)
@@ -162,13 +162,10 @@ class SmallMemberGzipWriter:
             at += self.chunk
         self.held = bytes(data[at:])
 
-    def write(self, text):
-        b = text.encode() if isinstance(text, str) else bytes(text)
-        if b:
-            self.held = self.held + b if self.held else b
-            if self.first_line or len(self.held) >= self.chunk:
-                self._emit(False)
-        return len(text)
+    def _take(self, b):
+        self.held = self.held + b if self.held else b
+        if self.first_line or len(self.held) >= self.chunk:
+            self._emit(False)
 
     def write_members(self, view):
         if len(view):
@@ -177,35 +174,27 @@ class SmallMemberGzipWriter:
             self.fh.write(view)
             self.bytes_written += len(view)
 
-    def flush(self):
-        self.fh.flush()
-
-    def close(self):
-        if self.closed:
-            return
+    def _finish(self):
         self._emit(True)
-        if not self.bytes_written and not self.part:
-            import gzip
-            self.fh.write(gzip.compress(b"", compresslevel=self.level, mtime=0))
-        self.fh.close()
-        self.closed = True
 
-    def __enter__(self):
-        return self
+    def _is_empty(self):
+        return not self.bytes_written and not self.part
 
-    def __exit__(self, *a):
-        self.close()
+
+def _create(output, name, compress, device_gzip):
+    """the file `name` of an output directory: `name`.gz under device_gzip -- a writer that also takes the GPU's members --
+    or under compress, else a text file"""
+    if device_gzip:
+        return MemberGzipWriter(os.path.join(output, name + ".gz"))
+    if compress:
+        return ParallelGzipWriter(os.path.join(output, name + ".gz"), compresslevel=9)
+    return open(os.path.join(output, name), "w")
 
 
 def create_kmer_stroi(output, compress=False, device_gzip=False):
     """kmers.tsv[.gz] with its header written (input.py:235-247).  device_gzip: a writer that also takes the GPU's
     members."""
-    if device_gzip:
-        fh = MemberGzipWriter(os.path.join(output, "kmers.tsv.gz"))
-    elif not compress:
-        fh = open(os.path.join(output, "kmers.tsv"), "w")
-    else:
-        fh = ParallelGzipWriter(os.path.join(output, "kmers.tsv.gz"), compresslevel=9)
+    fh = _create(output, "kmers.tsv", compress, device_gzip)
     fh.write(KMERS_TSV_HEADER)
     fh.flush()
     return fh
@@ -213,16 +202,8 @@ def create_kmer_stroi(output, compress=False, device_gzip=False):
 
 def create_hash_files(output, compress=False, device_gzip=False):
     """(hashes_to_patterns, kmers_to_hashes) handles, no headers yet (input.py:249-259)."""
-    if device_gzip:
-        hash_pat = MemberGzipWriter(os.path.join(output, "hashes_to_patterns.tsv.gz"))
-        kmer_hash = MemberGzipWriter(os.path.join(output, "kmers_to_hashes.tsv.gz"))
-    elif not compress:
-        hash_pat = open(os.path.join(output, "hashes_to_patterns.tsv"), "w")
-        kmer_hash = open(os.path.join(output, "kmers_to_hashes.tsv"), "w")
-    else:
-        hash_pat = ParallelGzipWriter(os.path.join(output, "hashes_to_patterns.tsv.gz"), compresslevel=9)
-        kmer_hash = ParallelGzipWriter(os.path.join(output, "kmers_to_hashes.tsv.gz"), compresslevel=9)
-    return hash_pat, kmer_hash
+    return (_create(output, "hashes_to_patterns.tsv", compress, device_gzip),
+            _create(output, "kmers_to_hashes.tsv", compress, device_gzip))
 
 
 def write_headers(hash_pat, kmer_hash, genepres):
@@ -267,26 +248,41 @@ def write_cluster_dirs(output, strains, out, compress=False, device_gzip=False):
     return sum(write_cluster_dir(output, idx, strains, kt, kh, hp, compress, device_gzip) for idx, kt, kh, hp in out.per_cluster)
 
 
-class ClusterSplitter:
+class _ClusterCursor:
+    """What the two splitters share: `ends[i]` is the offset just behind cluster `names[i]`'s bytes in the whole text
+    (non-decreasing); the cluster the next byte belongs to, and whether it has had a call; `close()` checks that the
+    text reached the last end and gives every cluster left its call -- with `_empty()` where it has no byte."""
+
+    def __init__(self, ends, names, sink):
+        self.ends, self.names, self.sink = [int(e) for e in ends], list(names), sink
+        if len(self.ends) != len(self.names) or any(b < a for a, b in zip(self.ends, self.ends[1:])):
+            raise ValueError("one end per cluster, non-decreasing")
+        self.at = 0             # text bytes taken so far
+        self.cluster = 0        # the cluster the next byte belongs to, if it has any left
+        self.called = False     # whether that cluster has had a call
+
+    def _next_cluster(self):
+        if not self.called:
+            self.sink(self.names[self.cluster], self._empty())
+        self.cluster += 1
+        self.called = False
+
+    def close(self):
+        if self.ends and self.at != self.ends[-1]:
+            raise ValueError(f"the text ended at byte {self.at}, the last cluster's end is {self.ends[-1]}")
+        while self.cluster < len(self.ends):
+            self._next_cluster()
+
+
+class ClusterSplitter(_ClusterCursor):
     """Cuts a text that arrives block by block (a batch's kmers.tsv rows as they leave the device) into its clusters'
     shares: `ends[i]` is the offset just behind cluster `names[i]`'s bytes in the whole text (non-decreasing).  Call it
     with every block, in order, then `close()`: `sink(name, piece)` is called at least once for every cluster, in order,
     with an empty piece where a cluster has no byte.  Blocks and ends fall wherever they fall; a piece is a slice of the
     block it came in, valid as long as that is."""
 
-    def __init__(self, ends, names, sink):
-        self.ends, self.names, self.sink = [int(e) for e in ends], list(names), sink
-        if len(self.ends) != len(self.names) or any(b < a for a, b in zip(self.ends, self.ends[1:])):
-            raise ValueError("one end per cluster, non-decreasing")
-        self.at = 0             # bytes taken so far
-        self.cluster = 0        # the cluster the next byte belongs to, if it has any left
-        self.called = False     # whether that cluster has had a call
-
-    def _next_cluster(self):
-        if not self.called:
-            self.sink(self.names[self.cluster], b"")
-        self.cluster += 1
-        self.called = False
+    def _empty(self):
+        return b""
 
     def __call__(self, block):
         view = memoryview(block)
@@ -302,14 +298,8 @@ class ClusterSplitter:
             off += take
             self.at += take
 
-    def close(self):
-        if self.ends and self.at != self.ends[-1]:
-            raise ValueError(f"the text ended at byte {self.at}, the last cluster's end is {self.ends[-1]}")
-        while self.cluster < len(self.ends):
-            self._next_cluster()
 
-
-class ClusterMemberSplitter:
+class ClusterMemberSplitter(_ClusterCursor):
     """ClusterSplitter for a text that arrives as gzip members (the kmers.tsv stream under device gzip, told the clusters'
     ends by pf_kmers_tsv_stream_cuts): a member cannot be cut, so every block comes with the places where the ends fall
     in it.  Call it with every block, in order -- `(members, text_off, text_bytes, cuts)`: the block's members, the text
@@ -319,19 +309,8 @@ class ClusterMemberSplitter:
     ValueError where the pieces do not add up: a block out of place, a cut outside its block, a piece over a cluster's
     end, text missing at the close."""
 
-    def __init__(self, ends, names, sink):
-        self.ends, self.names, self.sink = [int(e) for e in ends], list(names), sink
-        if len(self.ends) != len(self.names) or any(b < a for a, b in zip(self.ends, self.ends[1:])):
-            raise ValueError("one end per cluster, non-decreasing")
-        self.at = 0             # text bytes taken so far
-        self.cluster = 0        # the cluster the next byte belongs to, if it has any left
-        self.called = False     # whether that cluster has had a call
-
-    def _next_cluster(self):
-        if not self.called:
-            self.sink(self.names[self.cluster], GzipMembers(memoryview(b""), 0))
-        self.cluster += 1
-        self.called = False
+    def _empty(self):
+        return GzipMembers(memoryview(b""), 0)
 
     def __call__(self, members, text_off, text_bytes, cuts=()):
         view = memoryview(members)
@@ -354,12 +333,6 @@ class ClusterMemberSplitter:
             self.sink(self.names[self.cluster], GzipMembers(view[m0:m1], t1 - t0))
             self.called = True
         self.at = text_off + text_bytes
-
-    def close(self):
-        if self.ends and self.at != self.ends[-1]:
-            raise ValueError(f"the text ended at byte {self.at}, the last cluster's end is {self.ends[-1]}")
-        while self.cluster < len(self.ends):
-            self._next_cluster()
 
 
 class ClusterKmersFiles:

@@ -13,7 +13,7 @@ import threading
 import time
 
 from . import _lib
-from .engine import Engine, add_batch_stats, text_len
+from .engine import Engine, add_batch_stats, gzip_modes
 from .native_input import Pangenome
 from .output import (ClusterKmersFiles, create_hash_files, create_kmer_stroi, write_cluster_dirs, write_strain_headers,
                      write_text)
@@ -66,9 +66,10 @@ class _FileRun:
     """What the steps of one `run_files` call share."""
 
     def __init__(self, output, compress, multiple_files, device_gzip=False, device_gzip_clusters=False):
-        self.output, self.compress, self.multiple_files = output, compress, multiple_files
-        self.device_gzip = device_gzip and not multiple_files      # (per-cluster files keep the host's gzip under this switch)
-        self.device_gzip_clusters = device_gzip_clusters and multiple_files     # (they have their own)
+        self.output, self.multiple_files = output, multiple_files
+        # (per-cluster files keep the host's gzip under device_gzip: they have a switch of their own)
+        self.compress, self.device_gzip, self.device_gzip_clusters = gzip_modes(compress, device_gzip, multiple_files,
+                                                                                device_gzip_clusters)
         self.host_member_bytes = 0                      # per-cluster files: the members the writer thread compressed behind the headers
         self.t_start = time.perf_counter()
         # where the wall time went: opening + parsing the inputs, creating the context, uploading the genomes, then the
@@ -209,9 +210,16 @@ def _write_batches(run, eng, pg, stats, batch_clusters, device_text):
         # (target strains' rows go to kmers.tsv block by block as they leave the device, from this thread: the file is
         # the writer thread's only when a batch's rows come as one object -- the host renderers' path)
         # (under multiple_files each cluster's rows into its own directory's kmers.tsv, cut at the cluster ends)
-        sink = (lambda blk: write_text(run.kmer_stroi, blk)) if (device_text and not run.multiple_files) else None
-        cluster_sink = (ClusterKmersFiles(run.output, run.compress, run.device_gzip_clusters)
-                        if (device_text and run.multiple_files) else None)
+        sink = cluster_sink = None
+        if device_text and run.multiple_files:
+            cluster_sink = ClusterKmersFiles(run.output, run.compress, run.device_gzip_clusters)
+        elif device_text:
+            sink = functools.partial(write_text, run.kmer_stroi)
+        # what a batch adds to the run's counters: "bytes" its text; the clusters whose files are cut from text the GPU
+        # wrote; under device gzip the members the GPU made of it, by the encoder's own count
+        keys = (("clusters", "instances", "kept_kmers", "device_ms", "bytes") +
+                (("device_cluster_files",) if run.multiple_files else ()) +
+                (("compressed_bytes",) if run.device_gzip or run.device_gzip_clusters else ()))
         batches = eng.run_pangenome(pg, batch_clusters=batch_clusters, device_text=device_text,
                                     before_first_submit=run.wait_for_genomes, targets_sink=sink,
                                     cluster_targets_sink=cluster_sink)
@@ -224,14 +232,8 @@ def _write_batches(run, eng, pg, stats, batch_clusters, device_text):
                     cluster_sink.close()        # the batch's last kmers.tsv
             if o is None:
                 break
-            add_batch_stats(stats, o)
+            add_batch_stats(stats, o, keys)
             stats["patterns"] = o.stats.get("patterns", stats["patterns"])
-            if run.multiple_files:              # the clusters whose files are cut from text the GPU wrote
-                stats["device_cluster_files"] = stats.get("device_cluster_files", 0) + o.stats.get("device_cluster_files", 0)
-            if run.device_gzip or run.device_gzip_clusters:     # the members the GPU made of this batch, by the encoder's own count
-                stats["compressed_bytes"] = stats.get("compressed_bytes", 0) + o.stats.get("compressed_bytes", 0)
-            stats["bytes"] += (text_len(o.kmers_tsv) + text_len(o.kmers_to_hashes) + text_len(o.hashes_to_patterns) +
-                               o.stats.get("kmers_tsv_streamed", 0))
             q.put(o)
     finally:
         q.put(None)
@@ -270,9 +272,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
     `stats["compressed_bytes"]` as above.
     targets_text_budget: device memory a batch's kmers.tsv text may take (default: the engine's).
     Returns a dict of counters."""
-    device_gzip_clusters = bool(device_gzip_clusters and multiple_files)
-    compress = bool(compress or device_gzip or device_gzip_clusters)
-    run = _FileRun(output, compress, multiple_files, bool(device_gzip), device_gzip_clusters)
+    run = _FileRun(output, compress, multiple_files, device_gzip, device_gzip_clusters)
     err = existing_output_error(output)
     if err is not None:
         raise err

@@ -29,7 +29,8 @@ import shutil
 
 import numpy as np
 
-from .engine import KMERS_TO_HASHES_HEADER, KMERS_TSV_HEADER, add_batch_stats, hashes_to_patterns_header, text_len
+from .engine import (KMERS_TO_HASHES_HEADER, KMERS_TSV_HEADER, add_batch_stats, gzip_modes, hashes_to_patterns_header,
+                     text_len)
 from .output import ClusterKmersFiles, ParallelGzipWriter, SmallMemberGzipWriter, write_cluster_dirs, write_text
 
 FILES = ("kmers.tsv", "kmers_to_hashes.tsv", "hashes_to_patterns.tsv")
@@ -204,7 +205,7 @@ def run_records_sharded(records, output, strains, rank, world, dist=None, device
     records = list(records)
     start, stop = shard_range(len(records), rank, world, weights)
     max_strains = max([len(strains)] + [max(len(r[0]), len(r[2])) for r in records] + [1])
-    compress, device_gzip, device_gzip_clusters = _gzip_modes(compress, device_gzip, multiple_files, device_gzip_clusters)
+    compress, device_gzip, device_gzip_clusters = gzip_modes(compress, device_gzip, multiple_files, device_gzip_clusters)
     eng = Engine(klength=klength, canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
                  multiple_files=multiple_files, max_strains=(max_strains + 31) // 32 * 32, stroi=set(targets) if targets else (),
                  device=gpu, max_items=max_items, pattern_capacity=pattern_capacity, dedup=dedup, device_gzip=device_gzip,
@@ -242,7 +243,7 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
     from .pipeline import _peek_n_strains, existing_output_error, settle_context, sized_engine
     _bind_device(device)
     targets = tuple(targets or ())
-    compress, device_gzip, device_gzip_clusters = _gzip_modes(compress, device_gzip, multiple_files, device_gzip_clusters)
+    compress, device_gzip, device_gzip_clusters = gzip_modes(compress, device_gzip, multiple_files, device_gzip_clusters)
     err = existing_output_error(output)
     _barrier(dist, device)                                        # every rank has looked before rank 0 creates it
     if err is not None:
@@ -296,14 +297,6 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
         pg.close()
         if eng is not None:
             eng.close()
-
-
-def _gzip_modes(compress, device_gzip, multiple_files, device_gzip_clusters=False):
-    """(compress, device_gzip, device_gzip_clusters) as a run uses them: either device switch implies compress;
-    per-cluster directories keep the host's gzip under device_gzip and have the device's under device_gzip_clusters,
-    which means nothing without them"""
-    clusters = bool(device_gzip_clusters) and bool(multiple_files)
-    return bool(compress or device_gzip or clusters), bool(device_gzip) and not multiple_files, clusters
 
 
 def _budget(targets_text_budget):
@@ -367,14 +360,15 @@ def _drive(eng, make_batches, output, strains, rank, world, dist, device, compre
             stats["compressed_bytes"] += kmers_files.host_bytes
         _barrier(dist, device)
         return stats
-    stats.update(kmers_tsv_streamed=0, kmers_tsv_ranges=0, kmers_tsv_peak_device_bytes=0)
+    stats.update(kmers_tsv_streamed=0, kmers_tsv_ranges=0, kmers_tsv_peak_device_bytes=0, bytes=0)
     writer = ShardWriter(output, rank, compress, device_gzip)
+    kmers_tsv, kmers_to_hashes = writer.sink("kmers.tsv"), writer.sink("kmers_to_hashes.tsv")
 
     def each(o):
-        writer.write_batch(o.kmers_tsv, o.kmers_to_hashes)
-        writer.bytes += o.stats.get("kmers_tsv_streamed", 0)
+        kmers_tsv(o.kmers_tsv)                            # (what a sink takes is counted by the batch: "bytes")
+        kmers_to_hashes(o.kmers_to_hashes)
         add_batch_stats(stats, o, ("clusters", "instances", "kept_kmers", "device_ms", "kmers_tsv_streamed",
-                                   "kmers_tsv_ranges"))
+                                   "kmers_tsv_ranges", "bytes"))
         stats["kmers_tsv_peak_device_bytes"] = max(stats["kmers_tsv_peak_device_bytes"],
                                                    o.stats.get("kmers_tsv_peak_device_bytes", 0))
 
@@ -386,7 +380,7 @@ def _drive(eng, make_batches, output, strains, rank, world, dist, device, compre
     try:
         # a batch's kmers.tsv rows go into the part block by block as they leave the device (or, from a batch that fell
         # back to the host renderers, as one text, in its place)
-        _shard_batches(make_batches(targets_sink=writer.sink("kmers.tsv")), each, dist, device, drop_parts)
+        _shard_batches(make_batches(targets_sink=kmers_tsv), each, dist, device, drop_parts)
         stats["local_patterns"] = eng.pattern_count()
         stats["pattern_rows"], stats["patterns"] = finish_shard(eng, writer, dist, device, method)
     finally:
@@ -395,5 +389,5 @@ def _drive(eng, make_batches, output, strains, rank, world, dist, device, compre
     if rank == 0:
         assemble(output, world, strains, compress, device_gzip=device_gzip)
     _barrier(dist, device)
-    stats["bytes"] = writer.bytes
+    stats["bytes"] += writer.bytes                        # the pattern rows, behind the batches' text
     return stats
