@@ -606,6 +606,11 @@ int pf_gzip_members(const char* data, uint64_t n, int level, uint64_t chunk_byte
 #define PF_GZ_FIXED_ONLY 1u     /* every block with the fixed codes */
 #define PF_GZ_DYNAMIC_ONLY 2u   /* every block with dynamic codes */
 #define PF_GZ_LITERALS_ONLY 4u  /* no match is accepted */
+/* Not a test hook: every member leaves as a BGZF member (SAM specification 4.1: the 18-byte head with FLG = 4 and the BC
+ * subfield, BSIZE = the member's size - 1) -- the same member, 8 bytes longer.  Offsets, member_end[] and sizes count the
+ * framed members.  The 28-byte end-of-file member is the file writer's to append.  Taken by pf_gzip_device[_segments],
+ * pf_gzip_host_model[_segments] and pf_set_device_gzip; pf_kmerjoin_set_gzip refuses it. */
+#define PF_GZ_BGZF 8u
 uint32_t pf_gzip_device_chunk_bytes(void);
 /* Host text in, members out (malloc'd: pf_free_text): uploaded, encoded on the GPU, copied back.  n == 0 gives
  * *out_n == 0.  For tests, tools and text rendered on the host. */
@@ -642,6 +647,20 @@ int pf_gunzip_device(pf_ctx* ctx, const char* members, uint64_t n, char** out, u
 int pf_gunzip_device_last_ms(pf_ctx* ctx, float* ms);
 /* The same format functions run serially on the host: no context, no GPU. */
 int pf_gunzip_host_model(const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken);
+/*
+ * The same for BGZF, what bgzip and htslib write: a chain of members of at most 65 536 bytes, of at most 65 536 bytes of
+ * text each, every one with the 18-byte head FLG = 4, XLEN = 6, 'B' 'C' 02 00 BSIZE.  Only that head is taken: any other
+ * extra field (XLEN != 6, another or a second subfield) is "not taken".  The members are found by their BSIZE chain;
+ * a head in the chain that is not such a head (a plain gzip member among them: mixed files are not supported), a BSIZE
+ * smaller than a frame or past the end, an ISIZE over 65 536 are "not taken" before anything is decoded.  The end marker
+ * is a member of no text; a file without it is taken, as gzip reads it.  Members of more than
+ * pf_gzip_device_chunk_bytes() of text are inflated by a kernel with a 64 KiB window in LDS (two workgroups per CU), the
+ * others by pf_gunzip_device's (four).  Large gzip members, such as the 4 MiB ones of pf_gzip_members, are not taken by
+ * either call: one wave inflates one member, and a member of megabytes would take it most of a second.
+ * Results, refusals, memory and pf_gunzip_device_last_ms as for pf_gunzip_device.
+ */
+int pf_gunzip_device_bgzf(pf_ctx* ctx, const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken);
+int pf_gunzip_host_model_bgzf(const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken);
 /* Off by default.  While on, pf_render_device[_ex] hands out gzip members in place of text (*kh, *kh_bytes, *hp,
  * *hp_bytes describe the compressed bytes) and so does pf_kmers_tsv_stream_next: every block of a range is encoded as it
  * is produced and its compressed size read back before it is copied (the host-rendered sequences are in the device text
@@ -682,6 +701,9 @@ int pf_rowfilter_stats(pf_rowfilter* f, uint64_t* bytes_scanned, float* device_m
  * the next call); *consumed: the compressed bytes of the members taken -- the caller puts members[consumed:] in front
  * of its next block.  last = 1: the block ends the file; once all of it is consumed, a final line without a newline is
  * given one.  *taken = 0 with PF_OK: as pf_gunzip_device; nothing is carried over then.
+ * A block whose first head is a BGZF head (see pf_gunzip_device_bgzf) has its members listed by their BSIZE chain and is
+ * taken in the same way, by this and by every other owner of the feed -- pf_assocfilter_scan_members,
+ * pf_kmerjoin_survey_members / _join_members, pf_plotgrid_scan_members: there is no entry point of its own for BGZF.
  */
 int pf_rowfilter_members_begin(pf_rowfilter* f, int header);
 int pf_rowfilter_members_header(pf_rowfilter* f, const char** line, uint64_t* nbytes);

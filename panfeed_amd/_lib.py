@@ -163,10 +163,12 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_kmerjoin_set_gzip", "pf_kmerjoin_gzip_stats",
            "pf_plotgrid_members_begin", "pf_plotgrid_members_header", "pf_plotgrid_scan_members", "pf_plotgrid_gunzip_stats",
            "pf_gzip_device_segments", "pf_gzip_host_model_segments", "pf_render_device_cluster_members",
-           "pf_kmers_tsv_stream_cuts", "pf_kmers_tsv_stream_block_cuts"]
+           "pf_kmers_tsv_stream_cuts", "pf_kmers_tsv_stream_block_cuts",
+           "pf_gunzip_device_bgzf", "pf_gunzip_host_model_bgzf"]
 
 RENDER_NO_PATTERN_ROWS = 1
 GZ_FIXED_ONLY, GZ_DYNAMIC_ONLY, GZ_LITERALS_ONLY = 1, 2, 4     # pf_gzip_device / pf_set_device_gzip test hooks; 0: the product
+GZ_BGZF = 8                                                    # PF_GZ_BGZF: the members leave as BGZF members (no test hook)
 GET_CTX = C.CFUNCTYPE(C.c_void_p, C.c_void_p)     # pf_pangenome_open_device_cb: the context, when the first genome needs it
 ERR_ARG, ERR_OOM, ERR_HIP, ERR_CAPACITY, ERR_STATE = -1, -2, -3, -4, -5
 
@@ -328,6 +330,8 @@ def _load_locked():
     L.pf_gunzip_device.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     L.pf_gunzip_device_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.pf_gunzip_host_model.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.pf_gunzip_device_bgzf.argtypes = L.pf_gunzip_device.argtypes
+    L.pf_gunzip_host_model_bgzf.argtypes = L.pf_gunzip_host_model.argtypes
     L.pf_rowfilter_members_begin.argtypes = [C.c_void_p, C.c_int]
     L.pf_rowfilter_members_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pf_rowfilter_scan_members.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),

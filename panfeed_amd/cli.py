@@ -71,6 +71,9 @@ def get_options(argv=None):
                    help="gzip the output files")
     p.add_argument("--gpu-compress", action="store_true", default=False,
                    help="gzip the output files on the GPU; implies --compress; much faster, somewhat larger files")
+    p.add_argument("--bgzf", action="store_true", default=False,
+                   help="with --gpu-compress: write the three files as BGZF, the multi-member gzip that bgzip and htslib "
+                        "read and write (not with --multiple-files or on several GPUs)")
     p.add_argument("--gpu-compress-clusters", action="store_true", default=False,
                    help="with --multiple-files: gzip the per-cluster files on the GPU; implies --compress")
     p.add_argument("--cores", type=int, default=1,
@@ -135,6 +138,14 @@ def main(argv=None, run=None, launch=None, rank_entry=None):
         logger.error("--gpu-compress-clusters is for the per-cluster files of --multiple-files; --gpu-compress compresses the "
                      "one set of files on the GPU")
         return 2
+    if args.bgzf:
+        if not args.gpu_compress:
+            logger.error("--bgzf frames the members --gpu-compress makes: give --gpu-compress with it")
+            return 2
+        if args.multiple_files or rank_mod.launched() or (args.gpus is not None and args.gpus != 1):
+            logger.error("--bgzf is for the three files of a run on one GPU: --multiple-files, --gpus N and a launched rank "
+                         "are deliberately out of its scope; nothing was run")
+            return 2
     if args.targets is not None:
         logger.debug(f"Reading target strains ({args.targets})")
         targets = read_names(args.targets)
@@ -171,6 +182,8 @@ def main(argv=None, run=None, launch=None, rank_entry=None):
                         "--gpu-compress-clusters compresses them on the GPU")
     if args.gpu_compress_clusters:
         more["device_gzip_clusters"] = True
+    if args.bgzf:
+        more["bgzf"] = True
     from ._lib import PanfeedHipError
     from .engine import gzip_modes
     compress = gzip_modes(args.compress, args.gpu_compress, args.multiple_files, args.gpu_compress_clusters)[0]

@@ -299,7 +299,7 @@ struct PatternRowStream {
     void destroy_events() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
 int gz_check_flags(uint32_t flags, const char* who) {
-    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY)) return fail(PF_ERR_ARG, "%s: unknown flag", who);
+    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY | PF_GZ_BGZF)) return fail(PF_ERR_ARG, "%s: unknown flag", who);
     return PF_OK;
 }
 
@@ -3761,41 +3761,42 @@ int pf_gunzip_device_last_ms(pf_ctx* c, float* ms) {
     return PF_OK;
 }
 
-int pf_gunzip_device(pf_ctx* c, const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken) {
-    if (!c || (!members && n) || !out || !out_n || !taken) return fail(PF_ERR_ARG, "pf_gunzip_device: null argument");
+// pf_gunzip_device and pf_gunzip_device_bgzf, each under its own name `fn`: the members listed by signature, or by the BSIZE chain
+static int gunzip_device(pf_ctx* c, const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken, bool bgzf, const char* fn) {
+    if (!c || (!members && n) || !out || !out_n || !taken) return fail(PF_ERR_ARG, "%s: null argument", fn);
     *out = nullptr; *out_n = 0; *taken = 0;
     c->gz.decode_ms = 0.f;
     const uint8_t* bytes = reinterpret_cast<const uint8_t*>(members);
     std::vector<pfgz::MemberRef> ms;
     uint64_t consumed = 0;
-    if (!pfgz::list_members(bytes, n, true, ms, &consumed)) {
-        (void)fail(PF_OK, "pf_gunzip_device: not taken: member 0: %s", pfgz::inf_status_name(pfgz::INF_BAD_HEAD));
+    if (!(bgzf ? pfgz::list_members_bgzf(bytes, n, true, ms, &consumed) : pfgz::list_members(bytes, n, true, ms, &consumed))) {
+        (void)fail(PF_OK, "%s: not taken: member 0: %s", fn, pfgz::inf_status_name(pfgz::INF_BAD_HEAD));
         return PF_OK;
     }
     const int64_t bad = pfgz::first_refused(ms);
     if (bad >= 0) {
-        (void)fail(PF_OK, "pf_gunzip_device: not taken: member %lld: %s", (long long)bad, pfgz::inf_status_name(ms[(size_t)bad].status));
+        (void)fail(PF_OK, "%s: not taken: member %lld: %s", fn, (long long)bad, pfgz::inf_status_name(ms[(size_t)bad].status));
         return PF_OK;
     }
     uint64_t total = 0;
     for (const auto& m : ms) total += m.isize;
     std::unique_ptr<char, void (*)(void*)> buf((char*)malloc(total ? total : 1), free);
-    if (!buf) return fail(PF_ERR_OOM, "pf_gunzip_device: out of memory");
+    if (!buf) return fail(PF_ERR_OOM, "%s: out of memory", fn);
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     DevBuf text;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     PFCHK(get_event(c, &e0));
     if (get_event(c, &e1) != PF_OK) { c->ev_pool.push_back(e0); return PF_ERR_HIP; }
-    // a call of the decoder per MAX_MEMBERS members (so at most MAX_TEXT bytes of text on the device at a time)
+    // a call of the decoder per MAX_MEMBERS members and MAX_TEXT bytes of text (what is on the device at a time)
     auto decode = [&]() -> int {
         uint64_t at = 0;
-        for (size_t i = 0; i < ms.size(); i += PfGzDecoder::MAX_MEMBERS) {
-            const uint32_t k = (uint32_t)std::min<size_t>(PfGzDecoder::MAX_MEMBERS, ms.size() - i);
+        for (size_t i = 0, k = 0; i < ms.size(); i += k) {
             uint64_t part = 0;
-            for (uint32_t j = 0; j < k; j++) part += ms[i + j].isize;
+            for (k = 0; i + k < ms.size() && k < PfGzDecoder::MAX_MEMBERS && (!k || part + ms[i + k].isize <= PfGzDecoder::MAX_TEXT); k++)
+                part += ms[i + k].isize;
             PFCHK(text.ensure(part + 16));
-            PFCHK(c->gz.dec.decode(st, bytes, ms.data() + i, k, text.as<uint8_t>(), part, e0, e1));
+            PFCHK(c->gz.dec.decode(st, bytes, ms.data() + i, (uint32_t)k, text.as<uint8_t>(), part, e0, e1));
             HIPCHK(hipStreamSynchronize(st));
             float t = 0.f;
             HIPCHK(hipEventElapsedTime(&t, e0, e1));
@@ -3803,7 +3804,7 @@ int pf_gunzip_device(pf_ctx* c, const char* members, uint64_t n, char** out, uin
             uint32_t status = 0;
             const int64_t r = c->gz.dec.first_refused(&status);
             if (r >= 0) {
-                (void)fail(PF_OK, "pf_gunzip_device: not taken: member %lld: %s", (long long)(i + (size_t)r), pfgz::inf_status_name(status));
+                (void)fail(PF_OK, "%s: not taken: member %lld: %s", fn, (long long)(i + (size_t)r), pfgz::inf_status_name(status));
                 return 1;
             }
             if (part) HIPCHK(hipMemcpy(buf.get() + at, text.p, part, hipMemcpyDeviceToHost));
@@ -3817,6 +3818,14 @@ int pf_gunzip_device(pf_ctx* c, const char* members, uint64_t n, char** out, uin
     PFCHK(rc);
     *out = buf.release(); *out_n = total; *taken = 1;
     return PF_OK;
+}
+
+int pf_gunzip_device(pf_ctx* c, const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken) {
+    return gunzip_device(c, members, n, out, out_n, taken, false, "pf_gunzip_device");
+}
+
+int pf_gunzip_device_bgzf(pf_ctx* c, const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken) {
+    return gunzip_device(c, members, n, out, out_n, taken, true, "pf_gunzip_device_bgzf");
 }
 
 #ifdef PF_PROF

@@ -12,6 +12,15 @@
 // deflate block -- stored, fixed or dynamic, whichever is smallest by exact bit count.  No match reaches before its chunk.
 // A text made of segments (several files' bodies, one behind the other) is cut segment by segment, each from its own
 // start, so that no member holds bytes of two segments: chunk_plan() below.
+//
+// BGZF (SAM specification 4.1; what bgzip and htslib write) is the second container, read and written: a chain of
+// independent gzip members of at most 65 536 bytes, of at most 65 536 bytes of text each, whose 18-byte head carries the
+// member's size -- FLG = 4, XLEN = 6, the one extra subfield 'B' 'C' 02 00 BSIZE, BSIZE = the member's size - 1 -- and that
+// ends with a 28-byte member of no text.  Only that head is taken as BGZF: any other extra field (XLEN != 6, another or a
+// second subfield) is "not taken", and such a file goes the host's way.  A file is one container or the other: a head of the
+// other kind inside a chain is refused.  list_members_bgzf() walks the BSIZE chain; the encoder's members become BGZF under
+// PF_GZ_BGZF by 8 more bytes of head each (bgzf_frame), applied where the members are sized and gathered -- the end marker
+// is the host writer's to append.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -46,6 +55,13 @@ constexpr uint32_t MEMBER_HEAD = 10, MEMBER_TAIL = 8;
 constexpr uint32_t SLOT_BYTES = (CHUNK + CHUNK / 8 + 256 + 15) & ~15u;
 constexpr uint32_t SLOT_WORDS = SLOT_BYTES / 4;
 constexpr uint32_t MAX_CODED_BITS = (SLOT_BYTES - MEMBER_HEAD - MEMBER_TAIL - 16) * 8;
+// BGZF: the head with its BC subfield, what it adds to the plain head, the most a member and its text may be
+constexpr uint32_t BGZF_HEAD = 18, BGZF_EXTRA = BGZF_HEAD - MEMBER_HEAD, BGZF_MAX_MEMBER = 65536, BGZF_MAX_TEXT = 65536;
+// the largest member the encoder makes is SLOT_BYTES - 16 (MAX_CODED_BITS; a stored one is CHUNK + 23): framed, it still
+// fits its slot's share of every bound and BSIZE
+static_assert(SLOT_BYTES - 16 + BGZF_EXTRA <= SLOT_BYTES, "a framed member stays within the per-chunk bound");
+static_assert(SLOT_BYTES - 16 + BGZF_EXTRA <= BGZF_MAX_MEMBER, "a framed member's size - 1 fits BSIZE");
+static_assert(CHUNK + 5 + MEMBER_HEAD + MEMBER_TAIL <= SLOT_BYTES - 16, "a stored member is no larger than a coded one may be");
 
 enum Mode : uint32_t { STORED = 0, FIXED = 1, DYNAMIC = 2 };
 
@@ -269,6 +285,19 @@ PF_HD void put_member_tail(uint32_t* words, uint32_t coded_bits, uint32_t crc, u
     put_bits(words, at + 32, n, 32);
 }
 
+// BGZF: byte i (< BGZF_HEAD) of the head of a member of `framed` bytes whose plain head is plain[0 .. MEMBER_HEAD): the
+// plain head with FLG = 4, then XLEN = 6, 'B' 'C', SLEN = 2, BSIZE = framed - 1
+PF_HD uint8_t bgzf_head_byte(const uint8_t* plain, uint32_t framed, uint32_t i) {
+    const uint64_t extra = 0x0000000243420006ull | (uint64_t)(framed - 1) << 48;      // (bytes 06 00 'B' 'C' 02 00 lo hi, in a register)
+    return i == 3 ? 4 : i < MEMBER_HEAD ? plain[i] : (uint8_t)(extra >> (8 * (i - MEMBER_HEAD)));
+}
+// the end-of-file member (SAM specification 4.1): an empty fixed block under the head as bgzip writes it
+constexpr uint32_t BGZF_EOF_BYTES = 28;
+inline const uint8_t* bgzf_eof() {
+    static const uint8_t eof[BGZF_EOF_BYTES] = {0x1F, 0x8B, 8, 4, 0, 0, 0, 0, 0, 0xFF, 6, 0, 'B', 'C', 2, 0, 0x1B, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    return eof;
+}
+
 PF_HD uint32_t hash4(uint32_t w) { return (w * 2654435761u) >> (32 - HASH_BITS); }
 // a candidate's match is taken from 4 bytes on; 3 bytes only when near (a far 3-byte match costs more than 3 literals).
 // As long as a candidate comes from an equal hash4 of four bytes, the 3-byte clause never holds: two words that differ
@@ -350,7 +379,15 @@ inline void host_model_chunk(const uint8_t* text, uint32_t n, uint32_t flags, st
     }
     put_member_tail(words.data(), coded, crc, n);
     const uint32_t nbytes = member_bytes(coded);
-    for (uint32_t i = 0; i < nbytes; i++) out.push_back((uint8_t)(words[i >> 2] >> (8 * (i & 3))));
+    auto byte = [&](uint32_t i) { return (uint8_t)(words[i >> 2] >> (8 * (i & 3))); };
+    uint32_t from = 0;
+    if (flags & PF_GZ_BGZF) {                // the same member behind the longer head, as gz_gather_kernel frames it
+        uint8_t plain[MEMBER_HEAD];
+        for (uint32_t i = 0; i < MEMBER_HEAD; i++) plain[i] = byte(i);
+        for (uint32_t i = 0; i < BGZF_HEAD; i++) out.push_back(bgzf_head_byte(plain, nbytes + BGZF_EXTRA, i));
+        from = MEMBER_HEAD;
+    }
+    for (uint32_t i = from; i < nbytes; i++) out.push_back(byte(i));
 }
 
 // ---- the chunk plan.  A text may be cut into segments (the per-cluster files' bodies, one behind the other): a member
@@ -409,9 +446,9 @@ inline bool host_model(const uint8_t* data, uint64_t n, uint32_t flags, std::vec
 enum InfStatus : uint32_t {
     INF_OK = 0,
     INF_NOT_DECODED,        // (another member of the call was refused before this one was looked at)
-    INF_BAD_HEAD,           // not ID1 ID2 CM=8 FLG=0, or a member shorter than its frame
-    INF_TOO_LARGE,          // ISIZE over CHUNK or more than SLOT_BYTES compressed
-    INF_TRUNCATED,          // the payload ended inside a block
+    INF_BAD_HEAD,           // not ID1 ID2 CM=8 FLG=0 (BGZF: not FLG=4 with the one BC subfield), or a member shorter than its frame
+    INF_TOO_LARGE,          // ISIZE over CHUNK or more than SLOT_BYTES compressed (BGZF: ISIZE over 65 536)
+    INF_TRUNCATED,          // the payload ended inside a block (BGZF: the file ended inside a member)
     INF_BAD_BLOCK_TYPE,     // BTYPE 3
     INF_BAD_STORED,         // LEN != ~NLEN
     INF_BAD_CODE,           // an over-subscribed or incomplete code, no end-of-block code, a bit pattern without a symbol
@@ -631,6 +668,7 @@ constexpr uint32_t MEMBER_SIG = 8;
 struct MemberRef {
     uint64_t at;             // of the member's head in the bytes given
     uint32_t size, isize, crc, status;      // whole member's bytes; from its tail; INF_OK or why it is not taken
+    uint32_t head = MEMBER_HEAD;            // the bytes in front of its payload: MEMBER_HEAD, or BGZF_HEAD
 };
 inline bool member_head_ok(const uint8_t* p, uint64_t n) { return n >= MEMBER_HEAD && p[0] == 0x1F && p[1] == 0x8B && p[2] == 8 && p[3] == 0; }
 inline uint32_t le32(const uint8_t* p) { return p[0] | p[1] << 8 | p[2] << 16 | (uint32_t)p[3] << 24; }
@@ -669,6 +707,47 @@ inline int64_t first_refused(const std::vector<MemberRef>& ms) {
     return -1;
 }
 
+// ---- BGZF: the same list by the BSIZE chain, no signature search.  A head is taken as BGZF only in the shape bgzip and
+// htslib write it: FLG = 4, XLEN = 6, the single subfield BC of two bytes (MTIME, XFL and OS are free).
+inline bool bgzf_head_ok(const uint8_t* p, uint64_t n) {
+    return n >= BGZF_HEAD && p[0] == 0x1F && p[1] == 0x8B && p[2] == 8 && p[3] == 4 && p[10] == 6 && p[11] == 0 && p[12] == 'B' &&
+           p[13] == 'C' && p[14] == 2 && p[15] == 0;
+}
+// The members of p[0 .. n) in the order of the chain.  A member that runs past n ends the list when !last (the caller
+// reads on) and is INF_TRUNCATED with `last`; a head in the chain that is no BGZF head, or a BSIZE too small for a frame,
+// is INF_BAD_HEAD; an ISIZE over BGZF_MAX_TEXT is INF_TOO_LARGE.  The list ends with the first member refused.  The end
+// marker is a member of no text like any other, and a file without it is taken.  *consumed: the bytes of the members
+// listed as taken.  false: p does not start with a BGZF head (with !last and fewer bytes than a head: an empty list).
+inline bool list_members_bgzf(const uint8_t* p, uint64_t n, bool last, std::vector<MemberRef>& out, uint64_t* consumed) {
+    out.clear(); *consumed = 0;
+    uint64_t at = 0;
+    while (at < n) {
+        MemberRef m{at, 0, 0, 0, INF_OK, BGZF_HEAD};
+        const uint64_t left = n - at;
+        if (left < BGZF_HEAD && !last) break;
+        if (!bgzf_head_ok(p + at, left)) {
+            if (at == 0) return false;
+            m.status = left < BGZF_HEAD ? INF_TRUNCATED : INF_BAD_HEAD;
+        } else {
+            const uint32_t size = (p[at + 16] | (uint32_t)p[at + 17] << 8) + 1;
+            if (size < BGZF_HEAD + MEMBER_TAIL) m.status = INF_BAD_HEAD;
+            else if (size > left) {
+                if (!last) break;
+                m.status = INF_TRUNCATED;
+            } else {
+                m.size = size;
+                m.crc = le32(p + at + size - 8); m.isize = le32(p + at + size - 4);
+                if (m.isize > BGZF_MAX_TEXT) m.status = INF_TOO_LARGE;
+            }
+        }
+        out.push_back(m);
+        if (m.status != INF_OK) break;
+        at += m.size;
+    }
+    *consumed = at;
+    return true;
+}
+
 struct HostSink {
     uint8_t* w;
     bool leader() const { return true; }
@@ -682,16 +761,13 @@ struct HostSink {
 // The serial host model of the device decoder: the same functions, one member after the other, each from a buffer of
 // exactly its payload into one of exactly ISIZE bytes (a sanitizer build sees any step past either).  false: "not
 // taken", *first_bad / *status name the first member refused (a head that is not taken: member 0, INF_BAD_HEAD).
-inline bool host_inflate_model(const uint8_t* p, uint64_t n, std::vector<uint8_t>& text, uint64_t* first_bad, uint32_t* status) {
-    text.clear(); *first_bad = 0; *status = INF_OK;
-    std::vector<MemberRef> ms;
-    uint64_t consumed = 0;
-    if (!list_members(p, n, true, ms, &consumed)) { *status = INF_BAD_HEAD; return false; }
+inline bool host_inflate_listed(const uint8_t* p, const std::vector<MemberRef>& ms, std::vector<uint8_t>& text, uint64_t* first_bad,
+                                uint32_t* status) {
     const int64_t bad = first_refused(ms);
     if (bad >= 0) { *first_bad = (uint64_t)bad; *status = ms[(size_t)bad].status; return false; }
     DecodeTables T;
     for (size_t i = 0; i < ms.size(); i++) {
-        const std::vector<uint8_t> payload(p + ms[i].at + MEMBER_HEAD, p + ms[i].at + ms[i].size - MEMBER_TAIL);
+        const std::vector<uint8_t> payload(p + ms[i].at + ms[i].head, p + ms[i].at + ms[i].size - MEMBER_TAIL);
         std::vector<uint8_t> window(ms[i].isize);
         HostSink sink{window.data()};
         uint32_t produced = 0;
@@ -701,6 +777,21 @@ inline bool host_inflate_model(const uint8_t* p, uint64_t n, std::vector<uint8_t
         text.insert(text.end(), window.begin(), window.end());
     }
     return true;
+}
+inline bool host_inflate_model(const uint8_t* p, uint64_t n, std::vector<uint8_t>& text, uint64_t* first_bad, uint32_t* status) {
+    text.clear(); *first_bad = 0; *status = INF_OK;
+    std::vector<MemberRef> ms;
+    uint64_t consumed = 0;
+    if (!list_members(p, n, true, ms, &consumed)) { *status = INF_BAD_HEAD; return false; }
+    return host_inflate_listed(p, ms, text, first_bad, status);
+}
+// the same for a BGZF file: the members by their BSIZE chain, a window of up to BGZF_MAX_TEXT bytes
+inline bool host_inflate_model_bgzf(const uint8_t* p, uint64_t n, std::vector<uint8_t>& text, uint64_t* first_bad, uint32_t* status) {
+    text.clear(); *first_bad = 0; *status = INF_OK;
+    std::vector<MemberRef> ms;
+    uint64_t consumed = 0;
+    if (!list_members_bgzf(p, n, true, ms, &consumed)) { *status = INF_BAD_HEAD; return false; }
+    return host_inflate_listed(p, ms, text, first_bad, status);
 }
 
 }  // namespace pfgz
@@ -747,9 +838,10 @@ struct PfGzEncoder {
     // and the offset behind every segment's members, member_end[n_seg of that encode]
     int segment_ends(Cursor w, uint64_t* member_end) const;
 };
-// The device decoder: members in, text out, one wave per member (gz_inflate_kernel).  Its buffers hold the members of one
-// call, MAX_MEMBERS at most, each of SLOT_BYTES at most: device_bytes() <= MAX_MEMBERS * (SLOT_BYTES + 48) + slack; the
-// text buffer is the caller's.  Every call is stream-ordered on the stream given.
+// The device decoder: members in, text out, one wave per member (gz_inflate_kernel; gz_inflate64_kernel for the BGZF members
+// of more than CHUNK bytes of text).  Its buffers hold the members of one call, MAX_MEMBERS at most, and are sized from the
+// members given: device_bytes() <= their bytes + 52 per member + slack (members of this project's own: at most
+// MAX_MEMBERS * (SLOT_BYTES + 52)); the text buffer is the caller's.  Every call is stream-ordered on the stream given.
 namespace pfgz {
 struct DecMember { uint64_t src, dst; uint32_t csize, isize, crc, pad; };     // payload offset in the upload, text offset
 struct DecResult { uint32_t status, produced, crc, pad; };                   // an InfStatus, the bytes given, the CRC32 found
@@ -757,13 +849,16 @@ struct DecResult { uint32_t status, produced, crc, pad; };                   // 
 struct PfGzDecoder {
     static constexpr uint64_t MAX_TEXT = 256ull << 20;        // text bytes per call: the row filter's block
     static constexpr uint32_t MAX_MEMBERS = (uint32_t)(MAX_TEXT / pfgz::CHUNK);
-    DevBuf members, desc, results;
+    DevBuf members, desc, results;                           // (desc: the descriptors, then the two kernels' member indices)
     PinBuf pin;                                              // the results, read back
     std::vector<pfgz::DecMember> desc_host;
+    std::vector<uint32_t> index_host;                        // the members of at most CHUNK bytes of text, then the larger ones
     uint32_t n_last = 0;
+    bool large_ready = false;                                // gz_inflate64_kernel's dynamic LDS limit is raised (once, on the decoder's device)
     uint64_t device_bytes() const { return members.cap + desc.cap + results.cap; }
-    // On `st`: the n members ms[] (listed over `bytes`, host memory, all with status INF_OK) uploaded and inflated
-    // into text[0 .. sum of their ISIZE), which must fit text_cap; their results on the way into pinned memory.
+    // On `st`: the n members ms[] (listed over `bytes`, host memory, all with status INF_OK, each with its own head
+    // length: MEMBER_HEAD or BGZF_HEAD) uploaded and inflated into text[0 .. sum of their ISIZE), which must fit text_cap;
+    // their results on the way into pinned memory.
     int decode(hipStream_t st, const uint8_t* bytes, const pfgz::MemberRef* ms, uint32_t n, uint8_t* text, uint64_t text_cap,
                hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
     // once the caller has synchronised with that decode: the first member that failed a check and its status, or -1

@@ -15,7 +15,8 @@
 // LDS: 48 KiB of text + table, 10 KiB of tables -- under 64 KiB, two workgroups per CU within its 160 KiB.
 // gz_scan_kernel / gz_gather_kernel: the member sizes summed from an append cursor, the offset of every segment's first
 // member noted behind the cursor, the members copied from their worst-case slots to their places, contiguous, so that one
-// copy takes them to the host.
+// copy takes them to the host.  Under PF_GZ_BGZF these two also make every member a BGZF member, 8 bytes of head longer.
+// gz_inflate_kernel / gz_inflate64_kernel: the decoder, one wave per member, further down with its own comment.
 #include "pf_deflate.h"
 
 #include <cstdlib>
@@ -257,8 +258,10 @@ __global__ __launch_bounds__(THREADS, 2) void gz_encode_kernel(EncParams P) {
 // offs[i] = *cursor + the sizes before chunk i; *cursor advances by their sum.  One workgroup; thread 0 alone reads and
 // writes the cursor, the others get its value through LDS.  seg_first[s] = the offset of segment s's first chunk: chunk i
 // is one if chunk i - 1 is another segment's (for the launch's first chunk the host says: first0).
+// `frame`: the bytes the gather adds to every member's head (BGZF_EXTRA under PF_GZ_BGZF, else 0): every offset, every
+// segment's first and the cursor then count the framed members.
 __global__ __launch_bounds__(THREADS) void gz_scan_kernel(const uint32_t* sizes, const ChunkDesc* plan, uint32_t n, uint32_t first0,
-                                                          uint64_t* offs, uint64_t* cursor, uint64_t* seg_first) {
+                                                          uint64_t* offs, uint64_t* cursor, uint64_t* seg_first, uint32_t frame) {
     __shared__ uint32_t s_w[4];
     __shared__ uint64_t s_base;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -266,7 +269,7 @@ __global__ __launch_bounds__(THREADS) void gz_scan_kernel(const uint32_t* sizes,
     __syncthreads();
     uint64_t base = s_base;
     for (uint32_t r = 0; r < n; r += THREADS) {
-        const uint32_t v = r + tid < n ? sizes[r + tid] : 0, incl = wave_inclusive_sum(v, lane);
+        const uint32_t v = r + tid < n ? sizes[r + tid] + frame : 0, incl = wave_inclusive_sum(v, lane);
         if (lane == 63) s_w[wave] = incl;
         __syncthreads();
         uint32_t before = 0, total = 0;
@@ -284,16 +287,26 @@ __global__ __launch_bounds__(THREADS) void gz_scan_kernel(const uint32_t* sizes,
 
 // chunk i's member from its slot to members + offs[i]; a member that would pass `cap` is left out (the host sized the
 // buffer for the worst case: it never is).  The bytes up to the destination's next 16-byte boundary and the last few go
-// one by one, the rest in 16-byte units, stored aligned.
+// one by one, the rest in 16-byte units, stored aligned.  `frame` (BGZF_EXTRA under PF_GZ_BGZF, else 0): the member leaves
+// as a BGZF member of m + frame bytes -- the 18-byte head made of the slot's plain one (bgzf_head_byte), then the slot's
+// bytes from MEMBER_HEAD on, each `frame` bytes further back; the bytes that go one by one then cover that head.
 __global__ __launch_bounds__(THREADS) void gz_gather_kernel(const uint8_t* slots, const uint32_t* sizes, const uint64_t* offs,
-                                                            uint8_t* members, uint64_t cap) {
-    const uint32_t chunk = blockIdx.x, m = sizes[chunk], tid = threadIdx.x;
+                                                            uint8_t* members, uint64_t cap, uint32_t frame) {
+    const uint32_t chunk = blockIdx.x, m = sizes[chunk] + frame, tid = threadIdx.x;
     const uint64_t at = offs[chunk];
     if (at + m > cap) return;
     const uint8_t* src = slots + (size_t)chunk * SLOT_BYTES;
     uint8_t* dst = members + at;
-    const uint32_t head = min(m, (uint32_t)(-reinterpret_cast<uintptr_t>(dst) & 15));
-    if (tid < head) dst[tid] = src[tid];
+    uint32_t head = (uint32_t)(-reinterpret_cast<uintptr_t>(dst) & 15);
+    if (frame) {
+        while (head < BGZF_HEAD) head += 16;                   // (at most 33 bytes: fewer than the threads)
+        head = min(m, head);
+        if (tid < head) dst[tid] = tid < BGZF_HEAD ? bgzf_head_byte(src, m, tid) : src[tid - frame];
+    } else {
+        head = min(m, head);
+        if (tid < head) dst[tid] = src[tid];
+    }
+    src -= frame;                                              // (read at BGZF_HEAD and beyond only: src[MEMBER_HEAD ..] of the slot)
     const uint32_t nvec = (m - head) / 16, done = head + 16 * nvec;
     for (uint32_t i = tid; i < nvec; i += THREADS) {
         uint4 v;
@@ -313,9 +326,23 @@ __global__ __launch_bounds__(THREADS) void gz_gather_kernel(const uint8_t* slots
 // LDS: 32 KiB + 32 B of window, 1.3 KiB of tables -- four workgroups per CU within its 160 KiB; more waves per CU would
 // need the window in HBM, and then every match would wait on a round trip through L2 for bytes its own wave just wrote.
 // No wave waits for another: there is no barrier between workgroups, no flag, no loop without a bound.
+//
+// gz_inflate64_kernel: the same wave-per-member decode for the BGZF members of more than CHUNK bytes of text -- up to
+// BGZF_MAX_TEXT = 65 536, what bgzip cuts a file into.  The member's whole text again stays in LDS while it is decoded:
+// text offsets run to 65 535, a distance of 32 768 may reach from the window's second half into its first, a stored
+// block may fill the member.  Its window of 64 KiB + 32 B and the tables are 66 592 bytes, over the 64 KiB a kernel
+// may declare, so the LDS is dynamic and the limit is raised once per decoder (hipFuncSetAttribute).  Occupancy: two such
+// workgroups fit a CU's 160 KiB, against four of gz_inflate_kernel -- half the resident waves for members of twice the
+// text, so that per CU as many bytes are in flight; a third workgroup would need the window cut or kept in HBM.  So
+// members of at most CHUNK bytes of text -- bgzip's last block of a file, the end marker, this project's own BGZF members
+// -- keep the kernel of four per CU, and only the larger ones come here: two launches over one descriptor list, each
+// with the list of its members' indices (`idx`; none: the launch's workgroup i takes member i).
 constexpr uint32_t WIN_WORDS = CHUNK / 4 + 8;       // (the copy out reads up to four words past a 16-byte unit's first)
+constexpr uint32_t WIN64_WORDS = BGZF_MAX_TEXT / 4 + 8;
+constexpr uint32_t INFLATE64_LDS = WIN64_WORDS * 4 + (uint32_t)sizeof(DecodeTables);
+static_assert(WIN64_WORDS * 4 % 16 == 0 && 2 * INFLATE64_LDS <= 160 * 1024, "the tables stand aligned behind the window; two workgroups per CU");
 
-struct DecParams { const uint8_t* members; const DecMember* m; uint32_t n; uint8_t* text; DecResult* res; };
+struct DecParams { const uint8_t* members; const DecMember* m; const uint32_t* idx; uint32_t n; uint8_t* text; DecResult* res; };
 
 struct WaveSink {
     uint8_t* w; uint32_t lane;
@@ -334,16 +361,14 @@ struct WaveSink {
     __device__ void stored(uint32_t o, const uint8_t* src, uint32_t len) { for (uint32_t i = lane; i < len; i += 64) w[o + i] = src[i]; }
 };
 
-__global__ __launch_bounds__(64) void gz_inflate_kernel(DecParams P) {
-    __shared__ uint32_t s_win[WIN_WORDS];
-    __shared__ DecodeTables s_T;
-    const uint32_t lane = threadIdx.x, mi = blockIdx.x;
-    if (mi >= P.n) return;
+// one member by one wave: s_win holds MAX_TEXT bytes and the copy-out's slack, a member of more text is INF_TOO_LARGE
+template <uint32_t MAX_TEXT>
+__device__ __forceinline__ void inflate_member(const DecParams& P, uint32_t mi, uint32_t* s_win, DecodeTables& s_T, uint32_t lane) {
     const DecMember m = P.m[mi];
     uint8_t* win = reinterpret_cast<uint8_t*>(s_win);
     WaveSink sink{win, lane};
     uint32_t produced = 0;
-    uint32_t st = m.isize <= CHUNK ? inflate_blocks(P.members + m.src, m.csize, m.isize, s_T, sink, &produced) : (uint32_t)INF_TOO_LARGE;
+    uint32_t st = m.isize <= MAX_TEXT ? inflate_blocks(P.members + m.src, m.csize, m.isize, s_T, sink, &produced) : (uint32_t)INF_TOO_LARGE;
     sink.sync();
     uint32_t crc = 0;
     if (st == INF_OK) {
@@ -374,6 +399,19 @@ __global__ __launch_bounds__(64) void gz_inflate_kernel(DecParams P) {
         *reinterpret_cast<uint4*>(dst + s) = o;
     }
     if (done + lane < m.isize) dst[done + lane] = win[done + lane];
+}
+
+__global__ __launch_bounds__(64) void gz_inflate_kernel(DecParams P) {
+    __shared__ uint32_t s_win[WIN_WORDS];
+    __shared__ DecodeTables s_T;
+    if (blockIdx.x >= P.n) return;
+    inflate_member<CHUNK>(P, P.idx ? P.idx[blockIdx.x] : blockIdx.x, s_win, s_T, threadIdx.x);
+}
+
+__global__ __launch_bounds__(64) void gz_inflate64_kernel(DecParams P) {
+    extern __shared__ __align__(16) uint32_t s_dyn64[];          // WIN64_WORDS of window, then the tables: INFLATE64_LDS bytes
+    if (blockIdx.x >= P.n) return;
+    inflate_member<BGZF_MAX_TEXT>(P, P.idx[blockIdx.x], s_dyn64, *reinterpret_cast<DecodeTables*>(s_dyn64 + WIN64_WORDS), threadIdx.x);
 }
 
 }  // namespace pfgz
@@ -427,6 +465,7 @@ int PfGzEncoder::encode_segments(hipStream_t st, Cursor w, const char* text, uin
     HIPCHK(hipMemsetAsync(cursor, 0, 8, st));
     if (n_seg) HIPCHK(hipMemsetAsync(seg_first, 0xFF, (size_t)n_seg * 8, st));      // (a segment without a chunk keeps this)
     const size_t per_launch = (size_t)(BLOCK / pfgz::CHUNK);
+    const uint32_t frame = flags & PF_GZ_BGZF ? pfgz::BGZF_EXTRA : 0;       // (the encode kernel's members are the same either way)
     for (size_t c0 = 0; c0 < plan.size(); c0 += per_launch) {
         const uint32_t nch = (uint32_t)std::min(per_launch, plan.size() - c0);
         const uint32_t first0 = c0 == 0 || plan[c0 - 1].segment != plan[c0].segment;
@@ -435,10 +474,10 @@ int PfGzEncoder::encode_segments(hipStream_t st, Cursor w, const char* text, uin
         hipLaunchKernelGGL(pfgz::gz_encode_kernel, dim3(std::min(nch, grid_cap)), dim3(pfgz::THREADS), 0, st, P);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(pfgz::gz_scan_kernel, dim3(1), dim3(pfgz::THREADS), 0, st, sizes.as<uint32_t>(), dplan + c0, nch, first0,
-                           offs.as<uint64_t>(), cursor, seg_first);
+                           offs.as<uint64_t>(), cursor, seg_first, frame);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(pfgz::gz_gather_kernel, dim3(nch), dim3(pfgz::THREADS), 0, st, slots.as<uint8_t>(), sizes.as<uint32_t>(),
-                           offs.as<uint64_t>(), reinterpret_cast<uint8_t*>(members), cap);
+                           offs.as<uint64_t>(), reinterpret_cast<uint8_t*>(members), cap, frame);
         HIPCHK(hipGetLastError());
     }
     if (t1) HIPCHK(hipEventRecord(t1, st));
@@ -471,25 +510,47 @@ int PfGzDecoder::decode(hipStream_t st, const uint8_t* bytes, const pfgz::Member
     if (!n) return PF_OK;
     const uint64_t lo = ms[0].at, hi = ms[n - 1].at + ms[n - 1].size;
     desc_host.resize(n);
+    index_host.resize(n);
     uint64_t dst = 0;
+    uint32_t n_small = 0, n_large = 0;
     for (uint32_t i = 0; i < n; i++) {
-        if (ms[i].status != pfgz::INF_OK || ms[i].size < pfgz::MEMBER_HEAD + pfgz::MEMBER_TAIL || ms[i].at + ms[i].size > hi || ms[i].at < lo)
+        const uint32_t head = ms[i].head;
+        if (ms[i].status != pfgz::INF_OK || (head != pfgz::MEMBER_HEAD && head != pfgz::BGZF_HEAD) || ms[i].size < head + pfgz::MEMBER_TAIL ||
+            ms[i].at + ms[i].size > hi || ms[i].at < lo || ms[i].isize > pfgz::BGZF_MAX_TEXT)
             return fail(PF_ERR_ARG, "gzip decoder: member %u was not listed as taken", i);
-        desc_host[i] = pfgz::DecMember{ms[i].at - lo + pfgz::MEMBER_HEAD, dst, ms[i].size - pfgz::MEMBER_HEAD - pfgz::MEMBER_TAIL, ms[i].isize,
-                                       ms[i].crc, 0};
+        desc_host[i] = pfgz::DecMember{ms[i].at - lo + head, dst, ms[i].size - head - pfgz::MEMBER_TAIL, ms[i].isize, ms[i].crc, 0};
         dst += ms[i].isize;
+        // the members of at most CHUNK bytes of text from the front of the index list, the larger ones from its end
+        if (ms[i].isize <= pfgz::CHUNK) index_host[n_small++] = i;
+        else index_host[n - ++n_large] = i;
     }
     if (dst > text_cap) return fail(PF_ERR_ARG, "gzip decoder: the members' text exceeds its buffer");
+    if (n_large && !large_ready) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(pfgz::gz_inflate64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)pfgz::INFLATE64_LDS));
+        large_ready = true;
+    }
+    const size_t desc_bytes = (size_t)n * sizeof(pfgz::DecMember), index_bytes = n_large ? (size_t)n * 4 : 0;
     PFCHK(members.ensure(hi - lo + 16));
-    PFCHK(desc.ensure((size_t)n * sizeof(pfgz::DecMember)));
+    PFCHK(desc.ensure(desc_bytes + index_bytes));
     PFCHK(results.ensure((size_t)n * sizeof(pfgz::DecResult)));
     PFCHK(pin.ensure((size_t)n * sizeof(pfgz::DecResult)));
     HIPCHK(hipMemcpyAsync(members.p, bytes + lo, hi - lo, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(desc.p, desc_host.data(), (size_t)n * sizeof(pfgz::DecMember), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(desc.p, desc_host.data(), desc_bytes, hipMemcpyHostToDevice, st));
+    const uint32_t* index = reinterpret_cast<const uint32_t*>(desc.as<char>() + desc_bytes);
+    if (index_bytes) HIPCHK(hipMemcpyAsync(desc.as<char>() + desc_bytes, index_host.data(), index_bytes, hipMemcpyHostToDevice, st));
     if (t0) HIPCHK(hipEventRecord(t0, st));
-    pfgz::DecParams P{members.as<uint8_t>(), desc.as<pfgz::DecMember>(), n, text, results.as<pfgz::DecResult>()};
-    hipLaunchKernelGGL(pfgz::gz_inflate_kernel, dim3(n), dim3(64), 0, st, P);
-    HIPCHK(hipGetLastError());
+    // (a call without larger members is one launch over the descriptors as they stand, without an index list)
+    pfgz::DecParams P{members.as<uint8_t>(), desc.as<pfgz::DecMember>(), n_large ? index : nullptr, n_small, text, results.as<pfgz::DecResult>()};
+    if (n_small) {
+        hipLaunchKernelGGL(pfgz::gz_inflate_kernel, dim3(n_small), dim3(64), 0, st, P);
+        HIPCHK(hipGetLastError());
+    }
+    if (n_large) {
+        P.idx = index + n_small; P.n = n_large;
+        hipLaunchKernelGGL(pfgz::gz_inflate64_kernel, dim3(n_large), dim3(64), pfgz::INFLATE64_LDS, st, P);
+        HIPCHK(hipGetLastError());
+    }
     if (t1) HIPCHK(hipEventRecord(t1, st));
     HIPCHK(hipMemcpyAsync(pin.p, results.p, (size_t)n * sizeof(pfgz::DecResult), hipMemcpyDeviceToHost, st));
     return PF_OK;
@@ -547,6 +608,23 @@ int pf_gunzip_host_model(const char* members, uint64_t n, char** out, uint64_t* 
     }
     char* buf = (char*)malloc(text.size() ? text.size() : 1);
     if (!buf) return fail(PF_ERR_OOM, "pf_gunzip_host_model: out of memory");
+    if (!text.empty()) memcpy(buf, text.data(), text.size());
+    *out = buf; *out_n = text.size(); *taken = 1;
+    return PF_OK;
+}
+
+int pf_gunzip_host_model_bgzf(const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken) {
+    if ((!members && n) || !out || !out_n || !taken) return fail(PF_ERR_ARG, "pf_gunzip_host_model_bgzf: null argument");
+    *out = nullptr; *out_n = 0; *taken = 0;
+    std::vector<uint8_t> text;
+    uint64_t bad = 0;
+    uint32_t status = 0;
+    if (!pfgz::host_inflate_model_bgzf(reinterpret_cast<const uint8_t*>(members), n, text, &bad, &status)) {
+        (void)fail(PF_OK, "pf_gunzip_host_model_bgzf: not taken: member %llu: %s", (unsigned long long)bad, pfgz::inf_status_name(status));
+        return PF_OK;
+    }
+    char* buf = (char*)malloc(text.size() ? text.size() : 1);
+    if (!buf) return fail(PF_ERR_OOM, "pf_gunzip_host_model_bgzf: out of memory");
     if (!text.empty()) memcpy(buf, text.data(), text.size());
     *out = buf; *out_n = text.size(); *taken = 1;
     return PF_OK;

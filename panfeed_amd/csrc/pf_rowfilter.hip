@@ -319,10 +319,14 @@ private:
 
     int plan(RfMembers& c) {
         uint64_t listed = 0;
-        if (!pfgz::list_members(c.bytes, c.nbytes, c.last, c.ms, &listed)) return refuse(c, 0, pfgz::INF_BAD_HEAD);
+        // the block's first head says which container it is: a BGZF head (FLG = 4 with the one BC subfield) has the
+        // members listed by their BSIZE chain, anything else by the signature search, as ever
+        const bool bgzf = pfgz::bgzf_head_ok(c.bytes, c.nbytes);
+        if (!(bgzf ? pfgz::list_members_bgzf(c.bytes, c.nbytes, c.last, c.ms, &listed) : pfgz::list_members(c.bytes, c.nbytes, c.last, c.ms, &listed)))
+            return refuse(c, 0, pfgz::INF_BAD_HEAD);
         const bool none = c.ms.empty() && !c.last;
         // a member this decoder takes would have ended by now
-        if (none && c.nbytes >= pfgz::SLOT_BYTES + pfgz::MEMBER_HEAD) return refuse(c, 0, pfgz::INF_TOO_LARGE);
+        if (none && c.nbytes >= (bgzf ? pfgz::BGZF_MAX_MEMBER : pfgz::SLOT_BYTES + pfgz::MEMBER_HEAD)) return refuse(c, 0, pfgz::INF_TOO_LARGE);
         if (none) { c.none_yet = true; return PF_OK; }
         // at most the decoder's call: the rest is the caller's to give again
         while (c.take < c.ms.size() && c.take < PfGzDecoder::MAX_MEMBERS) {

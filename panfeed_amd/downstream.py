@@ -54,7 +54,8 @@ BLOCK_BYTES = 256 << 20
 # the device gunzip route reads COMPRESSED bytes: an eighth of the text block, which these texts' ratio of 6 to 8 makes
 # about one block of text a call (a call takes 256 MiB of text at most and hands the rest back)
 GZ_BLOCK_DIVISOR = 8
-GZ_HEAD = b"\x1f\x8b\x08\x00"          # ID1 ID2 CM=8 FLG=0: the only header the device decoder takes
+GZ_HEAD = b"\x1f\x8b\x08\x00"          # ID1 ID2 CM=8 FLG=0: the plain header the device decoder takes
+BGZF_HEAD = b"\x1f\x8b\x08\x04"        # and FLG=4 with the one extra subfield BC of two bytes: BGZF, what bgzip writes
 
 
 class NotTaken(RuntimeError):
@@ -71,6 +72,15 @@ def _gz_members_file(path):
         return False
     with open(path, "rb") as fh:
         return fh.read(10)[:4] == GZ_HEAD
+
+
+def _bgzf_file(path):
+    """whether the file is a .gz that starts with a BGZF head: 1f 8b 08 04, and BC 02 00 at bytes 12 to 15"""
+    if not str(path).endswith(".gz"):
+        return False
+    with open(path, "rb") as fh:
+        head = fh.read(18)
+    return len(head) == 18 and head[:4] == BGZF_HEAD and head[12:16] == b"BC\x02\x00"
 
 
 def pass_member_file(path, block_bytes, begin, call, after=None, reason=_last_error):
@@ -101,13 +111,13 @@ def pass_member_file(path, block_bytes, begin, call, after=None, reason=_last_er
 
 def route_file(path, device_gunzip, members, host, counts, again=None, reason=_last_error):
     """A file by the device gunzip route, members(), or through gzip as pandas reads it by the name, host(); -> what that
-    returned.  device_gunzip=None tries members() for a .gz of the header the device decoder takes and, when it returns
+    returned.  device_gunzip=None tries members() for a .gz of a header the device decoder takes (plain, or BGZF) and, when it returns
     None -- a block was not taken --, runs again() (what the owner undoes before the file is read once more) and host();
     True tries members() whatever the file and raises NotTaken instead; False never tries.  `counts`: the owner's class,
     whose device_gunzip_files or fallback_files moves."""
     auto = device_gunzip is None
     if auto:
-        device_gunzip = _gz_members_file(path)
+        device_gunzip = _gz_members_file(path) or _bgzf_file(path)
     if device_gunzip:
         got = members()
         if got is not None:
@@ -589,7 +599,8 @@ def _options(description, kmers):
     p.add_argument("-v", action="count", default=0)
     p.add_argument("--device", type=int, default=0, help="GPU the row filter runs on")
     p.add_argument("--host-gunzip", action="store_true", default=False,
-                   help="inflate .gz inputs on the host (by default files of small members, as --gpu-compress writes, are inflated on the GPU)")
+                   help="inflate .gz inputs on the host (by default files of small members, as --gpu-compress writes, and BGZF files, "
+                        "as bgzip or --gpu-compress --bgzf write, are inflated on the GPU)")
     return p
 
 

@@ -203,7 +203,7 @@ class Engine:
     def __init__(self, klength=31, canon=True, consider_missing=False, patfilt=True, maf=0.01,
                  multiple_files=False, max_strains=1024, stroi=(), device=0, pattern_capacity=0,
                  max_items=0, dedup=True, unit_dedup=True, key_binning=True, device_plan=False,
-                 targets_text_budget=8 << 30, device_gzip=False, device_gzip_flags=0, device_gzip_clusters=False):
+                 targets_text_budget=8 << 30, device_gzip=False, device_gzip_flags=0, device_gzip_clusters=False, bgzf=False):
         self.L = _lib.load()
         # device memory a batch's kmers.tsv text may take when it is streamed to a targets_sink (stream_targets_device)
         self.targets_text_budget = int(targets_text_budget)
@@ -231,8 +231,14 @@ class Engine:
         # device_gzip_clusters (multiple_files only): the per-cluster files' bodies leave the GPU as gzip members that end
         # where a cluster's rows end (render_device_cluster_members, stream_targets_device's cluster sink)
         _, self.device_gzip, self.device_gzip_clusters = gzip_modes(False, device_gzip, self.multiple_files, device_gzip_clusters)
+        # bgzf (with device_gzip, not for multiple_files): those members are BGZF members (PF_GZ_BGZF), for a file that
+        # output.BgzfMemberWriter writes
+        self.bgzf = bool(bgzf)
+        if self.bgzf and not self.device_gzip:
+            self.close()
+            raise ValueError("bgzf is for device_gzip without multiple_files")
         if self.device_gzip or self.device_gzip_clusters:
-            _lib.check(self.L.pf_set_device_gzip(self.ctx, 1, int(device_gzip_flags)))
+            _lib.check(self.L.pf_set_device_gzip(self.ctx, 1, int(device_gzip_flags) | (_lib.GZ_BGZF if self.bgzf else 0)))
         self.next_ordinal = 0
         self._md5_b64 = {}      # pattern id -> 24-char hash string (patterns seen so far)
         self.n_patterns = 0

@@ -123,6 +123,51 @@ class MemberGzipWriter(_GzipWriter):
         return not self.bytes_written
 
 
+BGZF_BLOCK = 65280                   # text bytes per host-made BGZF member: bgzip's, so that a stored member still fits BSIZE
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")      # SAM specification 4.1
+
+
+def bgzf_member(text, level):
+    """one BGZF member of at most BGZF_BLOCK bytes of text: raw deflate by zlib under the 18-byte head (MTIME = 0, the one
+    subfield BC, BSIZE = the member's size - 1)"""
+    import struct
+    import zlib
+    z = zlib.compressobj(level, zlib.DEFLATED, -15)
+    body = z.compress(text) + z.flush()
+    size = 18 + len(body) + 8
+    if len(text) > BGZF_BLOCK or size > 65536:
+        raise ValueError("a BGZF member holds at most 65 536 bytes")
+    return (bytes([0x1F, 0x8B, 8, 4, 0, 0, 0, 0, 0, 0xFF]) + struct.pack("<H2sHH", 6, b"BC", 2, size - 1) + body
+            + struct.pack("<II", zlib.crc32(text), len(text)))
+
+
+class BgzfMemberWriter(MemberGzipWriter):
+    """MemberGzipWriter's file as BGZF (Engine(device_gzip=True, bgzf=True)): `write(text)` cuts host text into blocks of
+    at most BGZF_BLOCK bytes and writes each as a BGZF member, `write_members(view)` appends the GPU's members, which are
+    BGZF members under PF_GZ_BGZF, as they are, and `close` appends the 28-byte end-of-file member: htslib's readers and
+    this project's device decoder walk the file by its BSIZE chain."""
+
+    def _take(self, b):
+        data = memoryview(b)
+        n = 0
+        for at in range(0, data.nbytes, BGZF_BLOCK):
+            member = bgzf_member(bytes(data[at:at + BGZF_BLOCK]), self.level)
+            self.fh.write(member)
+            n += len(member)
+        if self.header_bytes is None:
+            self.header_bytes = n
+        else:
+            self.host_bytes += n
+        self.bytes_written += n
+
+    def _finish(self):
+        self.fh.write(BGZF_EOF)
+        self.bytes_written += len(BGZF_EOF)
+
+    def _is_empty(self):
+        return False                     # (the end marker is a member: the file is a valid gzip stream as it is)
+
+
 class SmallMemberGzipWriter(_GzipWriter):
     """A .gz file every member of which the device decoder takes (pf_gunzip_device): panfeed-get-kmers --gz-output's.
     `write_members(view)` appends the GPU's members as they are; `write(text)` takes text made on the host -- the header
@@ -181,29 +226,29 @@ class SmallMemberGzipWriter(_GzipWriter):
         return not self.bytes_written and not self.part
 
 
-def _create(output, name, compress, device_gzip):
-    """the file `name` of an output directory: `name`.gz under device_gzip -- a writer that also takes the GPU's members --
-    or under compress, else a text file"""
+def _create(output, name, compress, device_gzip, bgzf=False):
+    """the file `name` of an output directory: `name`.gz under device_gzip -- a writer that also takes the GPU's members,
+    BGZF ones under bgzf -- or under compress, else a text file"""
     if device_gzip:
-        return MemberGzipWriter(os.path.join(output, name + ".gz"))
+        return (BgzfMemberWriter if bgzf else MemberGzipWriter)(os.path.join(output, name + ".gz"))
     if compress:
         return ParallelGzipWriter(os.path.join(output, name + ".gz"), compresslevel=9)
     return open(os.path.join(output, name), "w")
 
 
-def create_kmer_stroi(output, compress=False, device_gzip=False):
+def create_kmer_stroi(output, compress=False, device_gzip=False, bgzf=False):
     """kmers.tsv[.gz] with its header written (input.py:235-247).  device_gzip: a writer that also takes the GPU's
-    members."""
-    fh = _create(output, "kmers.tsv", compress, device_gzip)
+    members; bgzf: as BGZF."""
+    fh = _create(output, "kmers.tsv", compress, device_gzip, bgzf)
     fh.write(KMERS_TSV_HEADER)
     fh.flush()
     return fh
 
 
-def create_hash_files(output, compress=False, device_gzip=False):
+def create_hash_files(output, compress=False, device_gzip=False, bgzf=False):
     """(hashes_to_patterns, kmers_to_hashes) handles, no headers yet (input.py:249-259)."""
-    return (_create(output, "hashes_to_patterns.tsv", compress, device_gzip),
-            _create(output, "kmers_to_hashes.tsv", compress, device_gzip))
+    return (_create(output, "hashes_to_patterns.tsv", compress, device_gzip, bgzf),
+            _create(output, "kmers_to_hashes.tsv", compress, device_gzip, bgzf))
 
 
 def write_headers(hash_pat, kmer_hash, genepres):

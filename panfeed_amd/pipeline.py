@@ -65,8 +65,8 @@ def settle_context(pg, eng, open_reader):
 class _FileRun:
     """What the steps of one `run_files` call share."""
 
-    def __init__(self, output, compress, multiple_files, device_gzip=False, device_gzip_clusters=False):
-        self.output, self.multiple_files = output, multiple_files
+    def __init__(self, output, compress, multiple_files, device_gzip=False, device_gzip_clusters=False, bgzf=False):
+        self.output, self.multiple_files, self.bgzf = output, multiple_files, bool(bgzf)
         # (per-cluster files keep the host's gzip under device_gzip: they have a switch of their own)
         self.compress, self.device_gzip, self.device_gzip_clusters = gzip_modes(compress, device_gzip, multiple_files,
                                                                                 device_gzip_clusters)
@@ -193,8 +193,8 @@ def _start_upload(run, pg, eng, resident, overlap):
 def _open_outputs(run, strains):
     run.strains = list(strains)
     if not run.multiple_files:
-        run.kmer_stroi = create_kmer_stroi(run.output, run.compress, run.device_gzip)
-        run.hash_pat, run.kmer_hash = create_hash_files(run.output, run.compress, run.device_gzip)
+        run.kmer_stroi = create_kmer_stroi(run.output, run.compress, run.device_gzip, run.bgzf)
+        run.hash_pat, run.kmer_hash = create_hash_files(run.output, run.compress, run.device_gzip, run.bgzf)
         write_strain_headers(run.hash_pat, run.kmer_hash, run.strains)
 
 
@@ -254,7 +254,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
               patfilt=True, maf=0.01, upstream=0, downstream=0, downstream_start_codon=False, targets=(), genes=None,
               compress=False, multiple_files=False, batch_clusters=256, resident=True, device_text=True, device=0,
               max_items=0, pattern_capacity=0, overlap=True, one_pass=True, raise_missing=False, device_gzip=False,
-              targets_text_budget=None, device_gzip_clusters=False):
+              targets_text_budget=None, device_gzip_clusters=False, bgzf=False):
     """One directory of outputs (`kmers.tsv`, `kmers_to_hashes.tsv`, `hashes_to_patterns.tsv`, `.gz` under
     `compress`; under `multiple_files` one such directory per gene cluster, `<output>/<cluster>/`, the pattern set
     starting empty in each: `panfeed.py:35-43,153-167`) from a panaroo table and a directory (or file of files) of GFFs.  Option names and meaning follow
@@ -270,9 +270,14 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
     implies `compress` and changes nothing without `multiple_files`; every cluster's bodies leave the GPU as gzip members
     that end where the cluster's rows end and are appended behind the header line's member as they are;
     `stats["compressed_bytes"]` as above.
+    bgzf (`--bgzf`, with device_gzip, not for multiple_files: ValueError): the three files are BGZF -- the GPU's members
+    leave it as BGZF members, host text is written in BGZF members of at most 65 280 bytes, every file ends with the
+    end-of-file member; htslib's readers take them, and so does the device gunzip route of the downstream tools.
     targets_text_budget: device memory a batch's kmers.tsv text may take (default: the engine's).
     Returns a dict of counters."""
-    run = _FileRun(output, compress, multiple_files, device_gzip, device_gzip_clusters)
+    run = _FileRun(output, compress, multiple_files, device_gzip, device_gzip_clusters, bgzf)
+    if run.bgzf and not run.device_gzip:
+        raise ValueError("bgzf is for device_gzip without multiple_files")
     err = existing_output_error(output)
     if err is not None:
         raise err
@@ -282,7 +287,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
                                     canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
                                     multiple_files=multiple_files, stroi=set(targets), device=device,
                                     pattern_capacity=pattern_capacity, device_gzip=run.device_gzip,
-                                    device_gzip_clusters=run.device_gzip_clusters,
+                                    device_gzip_clusters=run.device_gzip_clusters, bgzf=run.bgzf,
                                     **({} if targets_text_budget is None else {"targets_text_budget": targets_text_budget}))
     open_reader = functools.partial(Pangenome, presence_absence, gffdir, fastadir, upstream, downstream,
                                     downstream_start_codon, targets=targets, genes=genes, raise_missing=raise_missing)

@@ -75,7 +75,7 @@ def get_options(argv=None):
     parser.add_argument("--device", type=int, default=0, help="GPU the grids are built on")
     parser.add_argument("--host-gunzip", action="store_true", default=False,
                         help="inflate a .gz table on the host (by default a file of small members, as panfeed-get-kmers "
-                             "--gz-output writes, is inflated on the GPU)")
+                             "--gz-output writes, or a bgzip'd file (BGZF) is inflated on the GPU)")
     return parser.parse_args(argv)
 
 
