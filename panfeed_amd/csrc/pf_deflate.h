@@ -443,6 +443,11 @@ inline bool host_model(const uint8_t* data, uint64_t n, uint32_t flags, std::vec
 // Every bound is checked here, before the sink is called: no read past the payload's last byte, no write past ISIZE,
 // no distance before the member's first byte, no symbol 286 / 287, no distance symbol 30 / 31.  Every loop iteration
 // takes at least one input bit or gives at least one output byte, so any stream ends its decode.
+// "bad code" against "truncated": decode_sym looks at MAX_BITS bits at once.  A bit pattern that no code has is
+// INF_BAD_CODE where at least MAX_BITS bits of payload are left from its first bit on (two or more whole bytes behind the
+// byte it starts in always are); within the payload's last MAX_BITS - 1 bits it cannot be told from a longer code cut
+// short and is INF_TRUNCATED -- also for a lone distance code's unused bit and for a block without distance codes, where
+// no longer code exists.  Either way the member is not taken (tests/inflate_edges.py pins both answers).
 enum InfStatus : uint32_t {
     INF_OK = 0,
     INF_NOT_DECODED,        // (another member of the call was refused before this one was looked at)
