@@ -728,7 +728,8 @@ void pf_rowfilter_destroy(pf_rowfilter* f);
  * might not print as it stands; the caller joins such a bunch another way.
  * join: the rows of one bunch of a block, in rendering `mode` 0 or 1; mode 2 keeps, as they stand, the rows that have a
  * key.  *out_bytes = the bytes of text made; pf_kmerjoin_next_text hands them out piece by piece through pinned memory
- * (*nbytes = 0: no more; a piece is valid until the call after the next).  A row that would have been flagged is
+ * (*nbytes = 0: no more; a piece is valid until the next call: that call starts the copy of the piece behind its own
+ * into the buffer this one lies in, as pf_kmers_tsv_stream_next does).  A row that would have been flagged is
  * PF_ERR_STATE here.
  * stats (either may be NULL): stats[0] bytes scanned, [1] rows written, [2] raw rows kept (mode 2), [3] members and
  * [4] text bytes inflated, [5] the decoder's device bytes, [6] look-ups whose hash was equal and whose bytes were not
@@ -789,7 +790,7 @@ void pf_kmerjoin_destroy(pf_kmerjoin* j);
  * members_begin / members_header / scan_members (the same lines, for a .gz of device-made members): as the row
  * filter's three calls; the header line is peeled off by the feed.
  * next_lines (get_clusters.py:85-88, get_kmers.py:102-106: the rows that stay): the kept lines of the last scan piece by
- * piece, as pf_kmerjoin_next_text (*nbytes = 0: no more; a piece is valid until the call after the next).
+ * piece, as pf_kmerjoin_next_text (*nbytes = 0: no more; a piece is valid until the next call).
  * columns (the dtypes read_csv infers at get_clusters.py:76 / get_kmers.py:93): n_fields words of class bits, the OR of
  * the rows' flags, counters[0] data lines and counters[1] kept lines so far (the pointer is valid until the next call).
  * stats (either may be NULL): stats[0] bytes scanned, [1] members and [2] text bytes inflated, [3] the decoder's device

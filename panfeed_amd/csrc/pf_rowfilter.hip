@@ -1428,7 +1428,8 @@ struct RowHandout {
     uint64_t bytes = 0, pos = 0, flying = 0;      // the text's bytes, those handed out or on their way, the piece on its way
     int cur = 0;
     void reset() { bytes = pos = flying = 0; }
-    // *nbytes = 0: no more; a piece is valid until the call after the next
+    // *nbytes = 0: no more; a piece is valid until the next call, which returns the other buffer and starts the copy of the
+    // piece behind it into this one
     int next(hipStream_t st, const char** piece, uint64_t* nbytes) {
         *piece = nullptr; *nbytes = 0;
         auto start = [&]() -> int {                    // the next piece on its way into pin[cur]
