@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <new>
 #include <numeric>
 #include <thread>
 #include <string>
@@ -45,7 +46,7 @@ struct Arena {
 // what a timed stretch of the stream counts towards (pf_timing); the extra-row fill counts as emit
 enum class TimeCat { scan, rows, emit, dedup, pattern_rows, md5, finish };
 
-struct EvPair { hipEvent_t a, b; TimeCat cat; };
+struct EvPair { HipEvent a, b; TimeCat cat; };
 
 // What this context has seen of its clusters of many distinct sequences: g = new k-mers per further sequence against
 // L = windows of one sequence, as running sums for the line g = a + b L (related alleles: a few tens whatever L is;
@@ -254,9 +255,9 @@ struct TargetText {
         pf::KtParams kp{};
         uint32_t cur = 0;                      // the block to queue next: range cur, bytes from cur_off
         uint64_t cur_off = 0, pin_bytes = 0;
-        char* htext[2] = {nullptr, nullptr};   // the host's share of the range being written into each buffer
-        hipEvent_t ev_prod[2] = {nullptr, nullptr};    // on `stream`: the range in buffer b is written
-        hipEvent_t ev_copied[2] = {nullptr, nullptr};  // on `side`: the range in buffer b has left the device
+        std::unique_ptr<char[]> htext[2];      // the host's share of the range being written into each buffer
+        HipEvent ev_prod[2];                   // on `stream`: the range in buffer b is written
+        HipEvent ev_copied[2];                 // on `side`: the range in buffer b has left the device
         // device gzip with cuts (pf_kmers_tsv_stream_cuts): the text offsets inside the text behind which a member must
         // end, ascending and distinct; per slot the block encoded into it -- its text, its cuts [lo, hi) and their
         // places in its text -- and, once handed out, behind which member byte each of them lies
@@ -264,7 +265,6 @@ struct TargetText {
         struct Block { uint64_t off = 0, n = 0; size_t lo = 0, hi = 0; std::vector<uint64_t> seg_end, member_end; } blk[2];
         int handed = -1;                               // the slot of the block handed out last
     } stream;
-    void destroy_events() { for (auto e : {stream.ev_prod[0], stream.ev_prod[1], stream.ev_copied[0], stream.ev_copied[1]}) if (e) (void)hipEventDestroy(e); }
 };
 // gzip on the device (pf_set_device_gzip): the mode, the encoder, the members of a render and of the stream's two blocks
 // in flight (block j + 1 is encoded while block j is written out by the caller), the text sizes behind the members
@@ -274,12 +274,11 @@ struct GzMode {
     PfGzEncoder enc;
     DevBuf render_members, block_members[2];
     uint64_t block_bound = 0;                 // bytes of each of block_members
-    hipEvent_t ev_copy = nullptr;             // on `side`: a block's members have arrived in pinned memory
+    HipEvent ev_copy;                         // on `side`: a block's members have arrived in pinned memory
     uint64_t raw[3] = {0, 0, 0};              // text bytes of the last render's two texts, of the stream's blocks so far
     float encode_ms = 0.0f;                   // the last pf_gzip_device's encode, scan and gather launches (hipEvent)
     PfGzDecoder dec;
     float decode_ms = 0.0f;                   // the last pf_gunzip_device's inflate launches (hipEvent)
-    void destroy_events() { if (ev_copy) (void)hipEventDestroy(ev_copy); }
 };
 // hashes_to_patterns rows of a list of patterns as a stream (pf_pattern_rows_stream_begin / _next): the ids and their row
 // lengths on the device, the text cut into slices at row boundaries.  Slice i is written into TargetText::text[i & 1] and
@@ -293,10 +292,9 @@ struct PatternRowStream {
     std::vector<uint64_t> cut;                // slice i holds rows [cut[i], cut[i + 1])
     uint32_t queued = 0, handed = 0;          // slices queued on the stream, slices handed out
     // on `stream`: slice i's text has arrived in pinned memory, or under device gzip is encoded and its size has arrived
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    HipEvent ev[2];
     uint32_t n_slices() const { return cut.empty() ? 0u : (uint32_t)cut.size() - 1; }
     uint64_t bytes(uint32_t i) const { return row_off[cut[i + 1]] - row_off[cut[i]]; }
-    void destroy_events() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
 int gz_check_flags(uint32_t flags, const char* who) {
     if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY | PF_GZ_BGZF)) return fail(PF_ERR_ARG, "%s: unknown flag", who);
@@ -307,9 +305,9 @@ int gz_check_flags(uint32_t flags, const char* who) {
 
 struct pf_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t side = nullptr;            // the fused finish kernels of a SMALL launch run here, beside the general path's kernels
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    HipStream stream;
+    HipStream side;                        // the fused finish kernels of a SMALL launch run here, beside the general path's kernels
+    HipEvent ev_fork, ev_join;
     pf_opts o{};
     int KW = 1;
     uint32_t NS = 0, W = 0, max_items = 0;
@@ -364,14 +362,14 @@ struct pf_ctx {
                                    // hipMemcpyAsync a staged, blocking copy)
     static constexpr int MAX_PARTS = 8;
     UPool upool[2 * MAX_PARTS];            // [2 h]: the device-planned clusters of part h, [2 h + 1]: the host-planned rest
-    hipEvent_t ev_part[MAX_PARTS] = {};    // a part's dedup results have arrived in pinned memory
+    HipEvent ev_part[MAX_PARTS];           // a part's dedup results have arrived in pinned memory
     // plan_kernel's output per part: item arrays, work lists, unit-view list (one device block), its 40-byte summary in
     // pinned memory; and the constant item arrays (zeros | ones | 0, 1, 2, ...) every device-planned pass shares
     struct DPlan { DevBuf block, it_count, out; PinBuf pin_out; uint32_t n = 0; };
     DPlan dplan[MAX_PARTS];
     DevBuf dp_const, plan_room, plan_arena;
     uint32_t dp_const_n = 0;
-    hipEvent_t ev_stage[2] = {nullptr, nullptr};   // a staging slot's upload has left the pinned block
+    HipEvent ev_stage[2];                  // a staging slot's upload has left the pinned block
 
     // last batch bookkeeping
     bool have_batch = false;
@@ -384,8 +382,8 @@ struct pf_ctx {
     pf_result counters{};
     pf_timing timing{};
     std::vector<EvPair> events;
-    std::vector<hipEvent_t> ev_pool;
-    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+    std::vector<HipEvent> ev_pool;
+    HipEvent ev_t0, ev_t1;
     // host result storage
     std::vector<uint64_t> h_kmer_off, h_kmer_key, h_first_seen, h_strand;
     std::vector<uint32_t> h_kmer_cnt, h_cl_pattern, h_cl_unique, h_kmer_pid, h_new_pid, h_pat_bits, h_pat_nan, h_pat_n;
@@ -403,7 +401,7 @@ void kt_stream_end(pf_ctx* c) {
         (void)hipStreamSynchronize(c->side);
         (void)hipStreamSynchronize(c->stream);
     }
-    for (int b = 0; b < 2; b++) { free(S.htext[b]); S.htext[b] = nullptr; }
+    for (auto& t : S.htext) t.reset();
     S.active = false; c->kt.flight.valid = false;
     S.hseqs.clear(); S.host = KtHostText{}; S.plan = KtPlan{};
     S.cuts.clear(); S.handed = -1;
@@ -418,10 +416,9 @@ void pr_stream_end(pf_ctx* c) {
     S.queued = S.handed = 0;
 }
 
-int get_event(pf_ctx* c, hipEvent_t* ev) {
-    if (!c->ev_pool.empty()) { *ev = c->ev_pool.back(); c->ev_pool.pop_back(); return PF_OK; }
-    HIPCHK(hipEventCreate(ev));
-    return PF_OK;
+int get_event(pf_ctx* c, HipEvent* ev) {
+    if (!c->ev_pool.empty()) { *ev = std::move(c->ev_pool.back()); c->ev_pool.pop_back(); return PF_OK; }
+    return ev->ensure();
 }
 // a timed stretch of one category on `s` (the context's stream unless the launches go to the side stream); the pairs are
 // read after the batch's last synchronisation, when both streams have drained
@@ -430,7 +427,7 @@ int mark_begin(pf_ctx* c, TimeCat cat, hipStream_t s = nullptr) {
     PFCHK(get_event(c, &e.a));
     PFCHK(get_event(c, &e.b));
     HIPCHK(hipEventRecord(e.a, s ? s : c->stream));
-    c->events.push_back(e);
+    c->events.push_back(std::move(e));
     return PF_OK;
 }
 int mark_end(pf_ctx* c, hipStream_t s = nullptr) {
@@ -778,19 +775,14 @@ int pf_device_count(void) {
 void pf_destroy(pf_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
+    // Both streams are idle before any member goes, so the order in which pf_ctx declares its buffers, events and streams
+    // does not matter to their owners.  (`side` by name as well: the stream ends wait for it only while a stream is open,
+    // and a block of a rendered text that nobody asked for may be on its way into a pinned block without one.)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    kt_stream_end(c);                     // (before its pinned blocks go)
+    kt_stream_end(c);
     pr_stream_end(c);
-    for (auto& e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    for (auto e : c->ev_stage) if (e) (void)hipEventDestroy(e);
-    for (auto e : c->ev_part) if (e) (void)hipEventDestroy(e);
-    c->kt.destroy_events(); c->gz.destroy_events(); c->pr.destroy_events();
-    for (auto e : {c->ev_t0, c->ev_t1, c->ev_fork, c->ev_join})
-        if (e) (void)hipEventDestroy(e);
-    if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;                             // (the buffers go with it)
+    if (c->side) (void)hipStreamSynchronize(c->side);
+    delete c;
 }
 
 int pf_create(pf_ctx** out, int device, const pf_opts* o) {
@@ -810,7 +802,10 @@ int pf_create(pf_ctx** out, int device, const pf_opts* o) {
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(PF_ERR_ARG, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
 
-    pf_ctx* c = new pf_ctx();
+    // (a step that fails leaves no context behind, and its error text is the one pf_last_error returns afterwards)
+    struct Unmake { void operator()(pf_ctx* c) const { const std::string keep = g_err; pf_destroy(c); g_err = keep; } };
+    std::unique_ptr<pf_ctx, Unmake> held(new pf_ctx());
+    pf_ctx* const c = held.get();
     c->device = device;
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     c->o = *o;
@@ -830,36 +825,24 @@ int pf_create(pf_ctx** out, int device, const pf_opts* o) {
     c->maf_hi.assign(o->maf_hi, o->maf_hi + o->max_strains + 1);
     c->o.maf_lo = c->maf_lo.data();
     c->o.maf_hi = c->maf_hi.data();
-    int rc = PF_OK;
-    auto guard = [&](int r) { if (r != PF_OK && rc == PF_OK) rc = r; return r == PF_OK; };
-    do {
-        hipError_t e = hipStreamCreate(&c->stream);
-        if (e != hipSuccess) { rc = fail(PF_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); break; }
-        if (hipStreamCreate(&c->side) != hipSuccess || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) { rc = fail(PF_ERR_HIP, "hipStreamCreate (side) failed"); break; }
-        bool ev_ok = true;
-        for (auto& ev : c->ev_part) ev_ok = ev_ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
-        for (auto& ev : c->ev_stage) ev_ok = ev_ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
-        if (!ev_ok ||
-            c->pin_small.ensure(512, true) != PF_OK ||
-            hipEventCreate(&c->ev_t0) != hipSuccess || hipEventCreate(&c->ev_t1) != hipSuccess) {
-            rc = fail(PF_ERR_HIP, "hipEventCreate failed"); break;
-        }
-        if (!guard(scan_attr(c))) break;
-        if (!guard(upload_vec(c, c->d_maf_lo, c->maf_lo))) break;
-        if (!guard(upload_vec(c, c->d_maf_hi, c->maf_hi))) break;
-        uint64_t cap = o->pattern_capacity ? o->pattern_capacity : (1ull << 24);
-        uint64_t p2 = 1024;
-        while (p2 < cap) p2 <<= 1;
-        if (!guard(alloc_pattern_bufs(c, p2, false, c->pats)) || !guard(c->pt_counters.ensure(16))) break;
-        sync_pattern_table(c);
-        if (!guard(reset_patterns(c))) break;
-        if (!guard(c->batch.cursor.ensure(64)) || !guard(c->scratch.ensure(c->max_items, c->dims()))) break;
-        e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { rc = fail(PF_ERR_HIP, "pf_create sync: %s", hipGetErrorString(e)); break; }
-    } while (0);
-    if (rc != PF_OK) { std::string keep = g_err; pf_destroy(c); g_err = keep; return rc; }
-    *out = c;
+    PFCHK(c->stream.create()); PFCHK(c->side.create());
+    PFCHK(c->ev_fork.ensure(hipEventDisableTiming)); PFCHK(c->ev_join.ensure(hipEventDisableTiming));
+    for (HipEvent& ev : c->ev_part) PFCHK(ev.ensure(hipEventDisableTiming));
+    for (HipEvent& ev : c->ev_stage) PFCHK(ev.ensure(hipEventDisableTiming));
+    PFCHK(c->pin_small.ensure(512, true));
+    PFCHK(c->ev_t0.ensure()); PFCHK(c->ev_t1.ensure());
+    PFCHK(scan_attr(c));
+    PFCHK(upload_vec(c, c->d_maf_lo, c->maf_lo)); PFCHK(upload_vec(c, c->d_maf_hi, c->maf_hi));
+    uint64_t cap = o->pattern_capacity ? o->pattern_capacity : (1ull << 24);
+    uint64_t p2 = 1024;
+    while (p2 < cap) p2 <<= 1;
+    PFCHK(alloc_pattern_bufs(c, p2, false, c->pats)); PFCHK(c->pt_counters.ensure(16));
+    sync_pattern_table(c);
+    PFCHK(reset_patterns(c));
+    PFCHK(c->batch.cursor.ensure(64)); PFCHK(c->scratch.ensure(c->max_items, c->dims()));
+    if (const hipError_t e = hipStreamSynchronize(c->stream); e != hipSuccess)
+        return fail(PF_ERR_HIP, "pf_create sync: %s", hipGetErrorString(e));
+    *out = held.release();
     return PF_OK;
 }
 
@@ -1939,7 +1922,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
         return fail(PF_ERR_ARG, "cluster arrays missing");
     if (b->n_extra && (!b->extra_cluster || !b->extra_ord || !b->extra_bits))
         return fail(PF_ERR_ARG, "extra arrays missing");
-    for (auto& e : c->events) { c->ev_pool.push_back(e.a); c->ev_pool.push_back(e.b); }
+    for (auto& e : c->events) { c->ev_pool.push_back(std::move(e.a)); c->ev_pool.push_back(std::move(e.b)); }
     c->events.clear();
     c->timing = pf_timing{};
     SubmitRun r(c, b, gth);
@@ -2518,7 +2501,7 @@ int kt_produce(pf_ctx* c, uint32_t r) {
     char* buf = c->kt.text[b].as<char>();
     if (r >= 2) {
         HIPCHK(hipEventSynchronize(S.ev_prod[b]));          // (its host text has been copied up: free it)
-        free(S.htext[b]); S.htext[b] = nullptr;
+        S.htext[b].reset();
         HIPCHK(hipStreamWaitEvent(c->stream, S.ev_copied[b], 0));
     }
     if (R.t1 > R.t0) {
@@ -2530,11 +2513,12 @@ int kt_produce(pf_ctx* c, uint32_t r) {
     if (R.h1 > R.h0) {
         const uint64_t* hsize = S.host.size.data();
         const uint64_t hbytes = std::accumulate(hsize + R.h0, hsize + R.h1, (uint64_t)0);
-        if (!(S.htext[b] = (char*)malloc(hbytes + 1))) return fail(PF_ERR_OOM, "malloc(%llu) failed", (unsigned long long)hbytes);
-        PFCHK(kt_host_write(c, S.hseqs.data(), S.host, R.h0, R.h1, S.htext[b]));
+        S.htext[b].reset(new (std::nothrow) char[hbytes + 1]);
+        if (!S.htext[b]) return fail(PF_ERR_OOM, "malloc(%llu) failed", (unsigned long long)hbytes);
+        PFCHK(kt_host_write(c, S.hseqs.data(), S.host, R.h0, R.h1, S.htext[b].get()));
         uint64_t at = 0;
         for (uint32_t j = R.h0; j < R.h1; j++) {
-            if (hsize[j]) HIPCHK(hipMemcpyAsync(buf + (S.plan.hoff[j] - R.base), S.htext[b] + at, (size_t)hsize[j], hipMemcpyHostToDevice, c->stream));
+            if (hsize[j]) HIPCHK(hipMemcpyAsync(buf + (S.plan.hoff[j] - R.base), S.htext[b].get() + at, (size_t)hsize[j], hipMemcpyHostToDevice, c->stream));
             at += hsize[j];
         }
     }
@@ -2577,10 +2561,7 @@ int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget, b
     if (NR <= 1) PFCHK(c->kt.text[0].ensure((size_t)P.total + 64));
     else for (DevBuf& t : c->kt.text) PFCHK(t.ensure((size_t)P.max_range + 64, true));
     if (NT) HIPCHK(hipMemcpyAsync(c->kt.toff.p, P.toff.data(), (size_t)NT * 8, hipMemcpyHostToDevice, c->stream));
-    for (int b = 0; b < 2; b++) {
-        if (!S.ev_prod[b]) HIPCHK(hipEventCreateWithFlags(&S.ev_prod[b], hipEventDisableTiming));
-        if (!S.ev_copied[b]) HIPCHK(hipEventCreateWithFlags(&S.ev_copied[b], hipEventDisableTiming));
-    }
+    for (int b = 0; b < 2; b++) { PFCHK(S.ev_prod[b].ensure(hipEventDisableTiming)); PFCHK(S.ev_copied[b].ensure(hipEventDisableTiming)); }
     S.kp = L.kp;
     S.cur = 0; S.cur_off = 0;
     S.pin_bytes = std::max<uint64_t>(1, std::min(KT_BLOCK, P.max_range));
@@ -2643,7 +2624,7 @@ int kt_gz_buffers(pf_ctx* c, uint64_t block_text, uint64_t n_cuts = 0) {
         PFCHK(G.block_members[s].ensure(G.block_bound, true));
         PFCHK(c->kt.pins[s].ensure(G.block_bound, true));
     }
-    if (!G.ev_copy) HIPCHK(hipEventCreateWithFlags(&G.ev_copy, hipEventDisableTiming));
+    PFCHK(G.ev_copy.ensure(hipEventDisableTiming));
     return PF_OK;
 }
 
@@ -2911,11 +2892,10 @@ int pf_submit_gather(pf_ctx* c, const pf_batch* b, const pf_gather* g, pf_result
 // genome on the host (read, upper-casing copy into contig strings, copy into pinned blocks) before the same pack.
 namespace {
 struct IngestSlot {
-    char* pin = nullptr; size_t cap = 0;
-    bool own = false;         // its blocks are its own (a file larger than the ring's slots), not parts of the ring's two blocks
+    RegBuf pin;               // its blocks are views into the ring's two blocks, or its own (a file larger than the ring's slots)
     DevBuf dev, dpieces;
     PinBuf pin_pieces;
-    hipEvent_t ev = nullptr;
+    HipEvent ev;
     bool held = false;        // a reader thread is filling it
     bool inflight = false;    // its copy / kernel may not have finished (ev)
 };
@@ -2926,7 +2906,7 @@ struct Ingest {
     void* user = nullptr;
     std::once_flag once;
     bool setup_ok = false;
-    char* ring_pin = nullptr;
+    RegBuf ring_pin;
     DevBuf ring_dev;
     std::mutex mu;
     std::condition_variable cv;
@@ -2951,25 +2931,21 @@ int ingest_acquire(void* self, size_t bytes, char** host, uint32_t* slot) {
             IngestSlot& s = I->slots[i];
             if (s.held) continue;
             if (s.inflight && hipEventQuery(s.ev) == hipSuccess) s.inflight = false;
-            if (!s.inflight) { if (pick < 0 || (s.cap >= bytes && I->slots[pick].cap < bytes)) pick = (int)i; }
+            if (!s.inflight) { if (pick < 0 || (s.pin.cap >= bytes && I->slots[pick].pin.cap < bytes)) pick = (int)i; }
             else if (waitable < 0) waitable = (int)i;
         }
         if (pick >= 0) {
             IngestSlot& s = I->slots[pick];
             s.held = true;
-            if (s.cap < bytes) {
+            if (s.pin.cap < bytes) {
                 lk.unlock();                                   // (the slot is ours: nobody else looks at it while it is held)
-                if (s.pin && s.own) { (void)hipHostUnregister(s.pin); free(s.pin); }
-                s.pin = nullptr; s.cap = 0; s.own = true;
-                const size_t want = bytes + bytes / 4 + 4096;
-                bool ok = posix_memalign((void**)&s.pin, 4096, want) == 0 && s.pin;
-                if (ok && hipHostRegister(s.pin, want, hipHostRegisterDefault) != hipSuccess) { (void)hipGetLastError(); free(s.pin); s.pin = nullptr; ok = false; }
-                ok = ok && s.dev.ensure(want) == PF_OK;
+                const size_t want = bytes + bytes / 4 + 4096;  // (a block of its own, with its own device twin)
+                const bool ok = s.pin.ensure(want) == PF_OK && s.dev.ensure(want) == PF_OK;
+                if (!ok) s.pin.release();
                 lk.lock();
                 if (!ok) { s.held = false; I->cv.notify_all(); return I->failed(PF_ERR_OOM, "no pinned / device block of " + std::to_string(want) + " bytes for a genome's text"); }
-                s.cap = want;
             }
-            *host = s.pin; *slot = (uint32_t)pick;
+            *host = s.pin.p; *slot = (uint32_t)pick;
             return PF_OK;
         }
         if (waitable >= 0) {                                    // every free block is still on its way to the device
@@ -2997,8 +2973,8 @@ int ingest_submit(void* self, uint32_t slot, size_t text_bytes, const pf_ingest_
     if (hipSetDevice(I->c->device) != hipSuccess) return done(I->failed(PF_ERR_HIP, "hipSetDevice failed"));
     // the pieces travel behind the text in the same block when there is room (one copy instead of two per file)
     const size_t tail = (text_bytes + 63) & ~(size_t)63;
-    const bool inline_pieces = tail + (size_t)n * sizeof(pf::TextPiece) <= s.cap;
-    pf::TextPiece* const pcs = inline_pieces ? reinterpret_cast<pf::TextPiece*>(s.pin + tail) : nullptr;
+    const bool inline_pieces = tail + (size_t)n * sizeof(pf::TextPiece) <= s.pin.cap;
+    pf::TextPiece* const pcs = inline_pieces ? reinterpret_cast<pf::TextPiece*>(s.pin.p + tail) : nullptr;
     if (!inline_pieces && (size_t)n * sizeof(pf::TextPiece) > s.pin_pieces.cap &&
         s.pin_pieces.ensure(((size_t)n + n / 2 + 64) * sizeof(pf::TextPiece), true) != PF_OK)
         return done(I->failed(PF_ERR_OOM, "ingest pieces: " + g_err));
@@ -3021,12 +2997,12 @@ int ingest_submit(void* self, uint32_t slot, size_t text_bytes, const pf_ingest_
     const pf::TextPiece* dpcs;
     if (getenv("PF_DEBUG_INGEST_SKIP_UPLOAD")) return done(PF_OK);        // (timing experiment: the reader alone; nothing reaches the store)
     if (inline_pieces) {
-        if (hipMemcpyAsync((char*)s.dev.p + lo, s.pin + lo, tail + (size_t)n * sizeof(pf::TextPiece) - lo, hipMemcpyHostToDevice, st) != hipSuccess)
+        if (hipMemcpyAsync((char*)s.dev.p + lo, s.pin.p + lo, tail + (size_t)n * sizeof(pf::TextPiece) - lo, hipMemcpyHostToDevice, st) != hipSuccess)
             return done(I->failed(PF_ERR_HIP, "ingest: upload of a genome's text failed"));
         dpcs = reinterpret_cast<const pf::TextPiece*>((char*)s.dev.p + tail);
     } else {
         if (s.dpieces.ensure((size_t)n * sizeof(pf::TextPiece)) != PF_OK) return done(I->failed(PF_ERR_OOM, "device block for ingest pieces"));
-        if (hipMemcpyAsync((char*)s.dev.p + lo, s.pin + lo, text_bytes - lo, hipMemcpyHostToDevice, st) != hipSuccess ||
+        if (hipMemcpyAsync((char*)s.dev.p + lo, s.pin.p + lo, text_bytes - lo, hipMemcpyHostToDevice, st) != hipSuccess ||
             hipMemcpyAsync(s.dpieces.p, s.pin_pieces.p, (size_t)n * sizeof(pf::TextPiece), hipMemcpyHostToDevice, st) != hipSuccess)
             return done(I->failed(PF_ERR_HIP, "ingest: upload of a genome's text failed"));
         dpcs = (const pf::TextPiece*)s.dpieces.p;
@@ -3070,24 +3046,20 @@ int ingest_setup(Ingest* I) {
     // slots as reader threads, plus a few, are never all busy -- and 64 slots of 10 MB were 0.6 GB to allocate and page-lock
     // in front of the first upload)
     I->slots.resize(std::max<size_t>(4, std::min<size_t>((size_t)nt / 2 + 4, (size_t)o->n_genomes + 1)));
-    for (auto& s : I->slots)
-        if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) return fail(PF_ERR_HIP, "hipEventCreate failed");
+    for (auto& s : I->slots) PFCHK(s.ev.ensure(hipEventDisableTiming));
     // the ring's blocks: ONE page-locked allocation and ONE device allocation, cut into slots that hold the largest file (an
     // allocation per slot was 2 x 32 calls into the driver, one after the other, in front of the first upload).  Ordinary
-    // memory, page-locked where it lies (hipHostRegister): the reader only COPIES the FASTA text into these blocks -- it
+    // memory, page-locked where it lies (RegBuf): the reader only COPIES the FASTA text into these blocks -- it
     // parses in its threads' own buffers.
     const size_t slot_bytes = (std::min<size_t>(biggest, 256u << 20) + 64 + (64u << 10) + 4095) & ~(size_t)4095;   // (+ room for the pieces)
     const size_t total = slot_bytes * I->slots.size();
-    if (posix_memalign((void**)&I->ring_pin, 4096, total) == 0 && I->ring_pin) {
-        if (hipHostRegister(I->ring_pin, total, hipHostRegisterDefault) != hipSuccess) { (void)hipGetLastError(); free(I->ring_pin); I->ring_pin = nullptr; }
-    } else I->ring_pin = nullptr;
-    if (I->ring_pin && I->ring_dev.ensure(total) == PF_OK) {
+    if (I->ring_pin.ensure(total) == PF_OK && I->ring_dev.ensure(total) == PF_OK) {
         for (size_t i = 0; i < I->slots.size(); i++) {
             IngestSlot& s = I->slots[i];
-            s.pin = I->ring_pin + i * slot_bytes; s.cap = slot_bytes; s.own = false;
+            s.pin.p = I->ring_pin.p + i * slot_bytes; s.pin.cap = slot_bytes; s.pin.view = true;
             s.dev.p = (char*)I->ring_dev.p + i * slot_bytes; s.dev.cap = 0; s.dev.view = true;
         }
-    } else if (I->ring_pin) { (void)hipHostUnregister(I->ring_pin); free(I->ring_pin); I->ring_pin = nullptr; I->ring_dev.release(); }   // (slots then allocate their own)
+    } else { I->ring_pin.release(); I->ring_dev.release(); }   // (slots then allocate their own)
     return PF_OK;
 }
 // every callback starts here: PF_OK once the set-up has succeeded (it runs once, on whichever reader thread comes first)
@@ -3125,12 +3097,7 @@ int pf_pangenome_open_device_cb(const pf_pangenome_opts* o, pf_ctx* (*get_ctx)(v
         (void)hipSetDevice(c->device);
         if (hipStreamSynchronize(c->stream) != hipSuccess && rc == PF_OK) rc = fail(PF_ERR_HIP, "the genomes' upload failed");
     }
-    lap("last uploads");
-    if (I.ring_pin) { (void)hipHostUnregister(I.ring_pin); free(I.ring_pin); }
-    for (auto& s : I.slots) {
-        if (s.pin && s.own) { (void)hipHostUnregister(s.pin); free(s.pin); }
-        if (s.ev) (void)hipEventDestroy(s.ev);
-    }
+    lap("last uploads");                  // (the stream is idle: the ring, the slots' own blocks and their events go with I)
     if (rc != PF_OK) {
         if (P) pf_pangenome_close(P);
         if (c) c->g_store.release();
@@ -3199,42 +3166,35 @@ int pf_genomes_upload(pf_ctx* c, uint32_t n, const char* const* ascii, const uin
     }
     PinBuf pin[2];
     DevBuf dasc[2], dpieces[2];
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int rc = PF_OK;
-    do {
-        for (int q = 0; q < 2 && rc == PF_OK; q++) {
-            if ((rc = pin[q].ensure(BLOCK, true)) != PF_OK) break;
-            if ((rc = dasc[q].ensure(BLOCK)) != PF_OK) break;
-            if (hipEventCreateWithFlags(&ev[q], hipEventDisableTiming) != hipSuccess) { rc = fail(PF_ERR_HIP, "hipEventCreate failed"); break; }
-        }
-        if (rc != PF_OK) break;
-        for (size_t bi = 0; bi < blks.size() && rc == PF_OK; bi++) {
-            Blk& bk = blks[bi];
-            if (bk.pieces.empty()) continue;
-            const int q = (int)(bi & 1);
-            if (hipEventSynchronize(ev[q]) != hipSuccess) { rc = fail(PF_ERR_HIP, "hipEventSynchronize failed"); break; }   // the slot's last block has left it
-            // the block's pieces into the pinned block, on the host threads (padding bases are 'A')
-            char* dst = pin[q].as<char>();
-            parallel_for(bk.fill, [&](uint64_t a, uint64_t e) {          // every thread takes a byte range of the block
-                for (const Src& sp : bk.src) {
-                    const uint64_t lo = std::max<uint64_t>(a, sp.at), hi = std::min<uint64_t>(e, sp.at + sp.n);
-                    if (lo < hi) memcpy(dst + lo, sp.p + (lo - sp.at), hi - lo);
-                }
-            });
-            for (const Src& sp : bk.src) { const size_t padded = (sp.n + 31) / 32 * 32; memset(dst + sp.at + sp.n, 'A', padded - sp.n); }
-            if ((rc = dpieces[q].ensure(bk.pieces.size() * sizeof(pf::PackPiece))) != PF_OK) break;
-            if (hipMemcpyAsync(dasc[q].p, pin[q].p, bk.fill, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                hipMemcpyAsync(dpieces[q].p, bk.pieces.data(), bk.pieces.size() * sizeof(pf::PackPiece), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-                rc = fail(PF_ERR_HIP, "genome upload failed"); break;
+    HipEvent ev[2];
+    // (declared after the staging buffers, it goes before them: however this call ends, the stream is idle when they are freed)
+    struct Idle { hipStream_t s; bool done; ~Idle() { if (!done) (void)hipStreamSynchronize(s); } } idle{c->stream, false};
+    for (int q = 0; q < 2; q++) { PFCHK(pin[q].ensure(BLOCK, true)); PFCHK(dasc[q].ensure(BLOCK)); PFCHK(ev[q].ensure(hipEventDisableTiming)); }
+    for (size_t bi = 0; bi < blks.size(); bi++) {
+        Blk& bk = blks[bi];
+        if (bk.pieces.empty()) continue;
+        const int q = (int)(bi & 1);
+        if (hipEventSynchronize(ev[q]) != hipSuccess) return fail(PF_ERR_HIP, "hipEventSynchronize failed");   // the slot's last block has left it
+        // the block's pieces into the pinned block, on the host threads (padding bases are 'A')
+        char* dst = pin[q].as<char>();
+        parallel_for(bk.fill, [&](uint64_t a, uint64_t e) {          // every thread takes a byte range of the block
+            for (const Src& sp : bk.src) {
+                const uint64_t lo = std::max<uint64_t>(a, sp.at), hi = std::min<uint64_t>(e, sp.at + sp.n);
+                if (lo < hi) memcpy(dst + lo, sp.p + (lo - sp.at), hi - lo);
             }
-            hipLaunchKernelGGL(pf::genome_pack_kernel, dim3(bk.blocks), dim3(256), 0, c->stream, (const uint8_t*)dasc[q].p,
-                               (const pf::PackPiece*)dpieces[q].p, (uint32_t)bk.pieces.size(), c->g_store.as<uint64_t>());
-            if (hipGetLastError() != hipSuccess || hipEventRecord(ev[q], c->stream) != hipSuccess) { rc = fail(PF_ERR_HIP, "genome_pack_kernel launch failed"); break; }
-        }
-    } while (0);
-    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == PF_OK) rc = fail(PF_ERR_HIP, "genome upload failed");
-    for (auto e : ev) if (e) (void)hipEventDestroy(e);
-    return rc;                            // (the staging buffers go now, after the sync)
+        });
+        for (const Src& sp : bk.src) { const size_t padded = (sp.n + 31) / 32 * 32; memset(dst + sp.at + sp.n, 'A', padded - sp.n); }
+        PFCHK(dpieces[q].ensure(bk.pieces.size() * sizeof(pf::PackPiece)));
+        if (hipMemcpyAsync(dasc[q].p, pin[q].p, bk.fill, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(dpieces[q].p, bk.pieces.data(), bk.pieces.size() * sizeof(pf::PackPiece), hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return fail(PF_ERR_HIP, "genome upload failed");
+        hipLaunchKernelGGL(pf::genome_pack_kernel, dim3(bk.blocks), dim3(256), 0, c->stream, (const uint8_t*)dasc[q].p,
+                           (const pf::PackPiece*)dpieces[q].p, (uint32_t)bk.pieces.size(), c->g_store.as<uint64_t>());
+        if (hipGetLastError() != hipSuccess || hipEventRecord(ev[q], c->stream) != hipSuccess) return fail(PF_ERR_HIP, "genome_pack_kernel launch failed");
+    }
+    idle.done = true;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(PF_ERR_HIP, "genome upload failed");
+    return PF_OK;
 }
 
 namespace {
@@ -3381,7 +3341,7 @@ int pf_pattern_rows_stream_begin(pf_ctx* c, const uint32_t* pids, uint64_t n, ui
             if (!c->gz.on) PFCHK(c->kt.pins[b].ensure((size_t)max_bytes, true));
             PFCHK(S.rowoff[b].ensure((size_t)(max_rows + 1) * 8));
             PFCHK(S.pin_rowoff[b].ensure((size_t)(max_rows + 1) * 8));
-            if (!S.ev[b]) HIPCHK(hipEventCreateWithFlags(&S.ev[b], hipEventDisableTiming));
+            PFCHK(S.ev[b].ensure(hipEventDisableTiming));
         }
         PFCHK(pr_produce(c, 0));
     }
@@ -3701,9 +3661,8 @@ int pf_gzip_device(pf_ctx* c, const char* data, uint64_t n, uint32_t flags, char
     PFCHK(text.ensure(n + 16, true));
     PFCHK(members.ensure(cap, true));
     HIPCHK(hipMemcpyAsync(text.p, data, n, hipMemcpyHostToDevice, st));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    PFCHK(get_event(c, &e0));
-    if (get_event(c, &e1) != PF_OK) { c->ev_pool.push_back(e0); return PF_ERR_HIP; }
+    HipEvent e0, e1;
+    PFCHK(get_event(c, &e0)); PFCHK(get_event(c, &e1));
     // (the two events go back to the pool whichever step fails)
     auto encode = [&]() -> int {
         PFCHK(enc.encode(st, W, text.as<char>(), n, flags, members.as<char>(), cap, e0, e1));
@@ -3713,7 +3672,7 @@ int pf_gzip_device(pf_ctx* c, const char* data, uint64_t n, uint32_t flags, char
         return PF_OK;
     };
     const int enc_rc = encode();
-    c->ev_pool.push_back(e0); c->ev_pool.push_back(e1);
+    c->ev_pool.push_back(std::move(e0)); c->ev_pool.push_back(std::move(e1));
     PFCHK(enc_rc);
     uint64_t z = 0;
     PFCHK(enc.member_bytes(W, &z));
@@ -3785,9 +3744,8 @@ static int gunzip_device(pf_ctx* c, const char* members, uint64_t n, char** out,
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     DevBuf text;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    PFCHK(get_event(c, &e0));
-    if (get_event(c, &e1) != PF_OK) { c->ev_pool.push_back(e0); return PF_ERR_HIP; }
+    HipEvent e0, e1;
+    PFCHK(get_event(c, &e0)); PFCHK(get_event(c, &e1));
     // a call of the decoder per MAX_MEMBERS members and MAX_TEXT bytes of text (what is on the device at a time)
     auto decode = [&]() -> int {
         uint64_t at = 0;
@@ -3813,7 +3771,7 @@ static int gunzip_device(pf_ctx* c, const char* members, uint64_t n, char** out,
         return PF_OK;
     };
     const int rc = decode();
-    c->ev_pool.push_back(e0); c->ev_pool.push_back(e1);
+    c->ev_pool.push_back(std::move(e0)); c->ev_pool.push_back(std::move(e1));
     if (rc == 1) return PF_OK;                  // not taken
     PFCHK(rc);
     *out = buf.release(); *out_n = total; *taken = 1;

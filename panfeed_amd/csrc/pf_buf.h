@@ -1,6 +1,9 @@
-// pf_buf.h -- internal: the error helpers and the owners of device and pinned host memory that the library's three
-// translation units with device code (pf_api.hip, pf_rowfilter.hip, pf_deflate.hip) share.  Not part of the C ABI (include/panfeed_hip.h).
-// A buffer frees itself when its owner goes; what is freed early on purpose says so where it happens.
+// pf_buf.h -- internal: the error helpers and the owners of what the library's three translation units with device code
+// (pf_api.hip, pf_rowfilter.hip, pf_deflate.hip) take from the HIP runtime: device memory (DevBuf), pinned host memory
+// (PinBuf), ordinary host memory page-locked where it lies (RegBuf), events (HipEvent), streams (HipStream; TimedStream with
+// the two events that time it).  Not part of the C ABI (include/panfeed_hip.h).  A buffer frees itself when its owner goes,
+// an event is destroyed and a stream synchronised, then destroyed, with theirs -- nowhere else is one of them created,
+// registered or let go; what is freed early on purpose says so where it happens.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +13,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <utility>
 
 extern "C" void pf_set_error_(const char* msg);   // pf_api.hip: the text pf_last_error returns on this thread
@@ -123,6 +127,71 @@ struct PinBuf {
     }
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// Ordinary host memory, 4096-aligned and page-locked where it lies (hipHostRegister) -- or a view into another RegBuf's
+// block, which is never freed.  A block that is too small is re-made at exactly `bytes`; a failure leaves nothing behind,
+// and no sticky HIP error either.
+struct RegBuf {
+    char* p = nullptr; size_t cap = 0; bool view = false;
+    RegBuf() = default; RegBuf(const RegBuf&) = delete; RegBuf& operator=(const RegBuf&) = delete;
+    RegBuf(RegBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)), view(std::exchange(o.view, false)) {}
+    RegBuf& operator=(RegBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(view, o.view); return *this; }
+    ~RegBuf() { release(); }
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return PF_OK;
+        release();
+        void* q = nullptr;
+        if (posix_memalign(&q, 4096, bytes) != 0 || !q) return fail(PF_ERR_OOM, "posix_memalign(%zu) failed", bytes);
+        if (hipHostRegister(q, bytes, hipHostRegisterDefault) != hipSuccess) { (void)hipGetLastError(); free(q); return fail(PF_ERR_OOM, "hipHostRegister(%zu) failed", bytes); }
+        p = static_cast<char*>(q); cap = bytes;
+        return PF_OK;
+    }
+    void release() { if (p && !view) { (void)hipHostUnregister(p); free(p); } p = nullptr; cap = 0; view = false; }
+};
+
+// An event: made on first use with the flags its site asks for, destroyed with its owner; passed to HIP as it is.
+struct HipEvent {
+    hipEvent_t e = nullptr;
+    HipEvent() = default; HipEvent(const HipEvent&) = delete; HipEvent& operator=(const HipEvent&) = delete;
+    HipEvent(HipEvent&& o) noexcept : e(std::exchange(o.e, nullptr)) {}
+    HipEvent& operator=(HipEvent&& o) noexcept { std::swap(e, o.e); return *this; }
+    ~HipEvent() { if (e) (void)hipEventDestroy(e); }
+    int ensure(unsigned flags = hipEventDefault) {
+        if (e || (flags == hipEventDefault ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, flags)) == hipSuccess) return PF_OK;
+        e = nullptr;
+        return fail(PF_ERR_HIP, "hipEventCreate failed");
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+// A stream: synchronised, then destroyed, with its owner; passed to HIP as it is.
+struct HipStream {
+    hipStream_t s = nullptr;
+    HipStream() = default; HipStream(const HipStream&) = delete; HipStream& operator=(const HipStream&) = delete;
+    HipStream(HipStream&& o) noexcept : s(std::exchange(o.s, nullptr)) {}
+    HipStream& operator=(HipStream&& o) noexcept { std::swap(s, o.s); return *this; }
+    ~HipStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    int create() {
+        const hipError_t r = hipStreamCreate(&s);
+        if (r != hipSuccess) { s = nullptr; return fail(PF_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(r)); }
+        return PF_OK;
+    }
+    operator hipStream_t() const { return s; }
+};
+
+// A stream and the two events that bracket what is timed on it.  Its owner declares it last, so that it goes first: the
+// stream is synchronised and destroyed before the buffers its work may still use are freed.
+struct TimedStream {
+    HipEvent e0, e1;
+    HipStream stream;                                 // (its own last member likewise: it goes before the events recorded on it)
+    int create() { PFCHK(stream.create()); PFCHK(e0.ensure()); PFCHK(e1.ensure()); return PF_OK; }
+    template <class F> int timed(F&& work) {          // e0 and e1 recorded around what `work` puts on the stream
+        HIPCHK(hipEventRecord(e0, stream)); PFCHK(work()); HIPCHK(hipEventRecord(e1, stream));
+        return PF_OK;
+    }
+    // once the caller has synchronised with the stream: the time between the two events, added to *ms
+    void add_elapsed(float* ms) const { float t = 0; if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) *ms += t; }
 };
 
 }  // namespace

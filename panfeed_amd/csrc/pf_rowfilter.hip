@@ -224,26 +224,6 @@ struct BlockText {
     }
 };
 
-// A stream and the two events that bracket what is timed on it.  Its owner declares it last, so that it goes first: the
-// stream is synchronised and destroyed before the buffers its work may still use are freed.
-struct TimedStream {
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    TimedStream() = default; TimedStream(const TimedStream&) = delete;
-    ~TimedStream() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    int create() { HIPCHK(hipStreamCreate(&stream)); HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); return PF_OK; }
-    template <class F> int timed(F&& work) {          // e0 and e1 recorded around what `work` puts on the stream
-        HIPCHK(hipEventRecord(e0, stream)); PFCHK(work()); HIPCHK(hipEventRecord(e1, stream));
-        return PF_OK;
-    }
-    // once the caller has synchronised with the stream: the time between the two events, added to *ms
-    void add_elapsed(float* ms) const { float t = 0; if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) *ms += t; }
-};
-
 // ---- TextFeed::members, stage by stage: what a call's plan, inflate and header stages find out
 struct RfMembers {
     const uint8_t* bytes; uint64_t nbytes; bool last;     // the call's arguments
@@ -404,6 +384,19 @@ template <class H> int feed_gunzip_stats(H* h, const char* fn, uint64_t* members
     if (device_bytes) *device_bytes = h->feed.dec.device_bytes();
     return PF_OK;
 }
+// ... and what their pf_*_create and pf_*_destroy share.  Create: the device checked and made current, the handle made --
+// destroyed again should the rest of its create fail -- and its feed's stream and events.  Destroy: on the handle's device
+template <class H> using FeedHandle = std::unique_ptr<H, void (*)(H*)>;
+template <class H> void feed_destroy(H* h) { if (h) { (void)hipSetDevice(h->feed.device); delete h; } }
+template <class H> int feed_create(int device, const char* fn, FeedHandle<H>& h) {
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "%s: no such device", fn);
+    HIPCHK(hipSetDevice(device));
+    h.reset(new H());
+    h->feed.device = device;
+    return h->feed.ts.create();
+}
 
 }  // namespace
 
@@ -530,18 +523,13 @@ uint64_t rf_members_keep(pf_rowfilter* f, uint64_t skip, const std::vector<uint6
 
 extern "C" {
 
-void pf_rowfilter_destroy(pf_rowfilter* f) { if (f) { (void)hipSetDevice(f->feed.device); delete f; } }
+void pf_rowfilter_destroy(pf_rowfilter* f) { feed_destroy(f); }
 
 int pf_rowfilter_create(int device, int first_field, const char* const* keys, const uint32_t* key_len, uint64_t n_keys,
                         pf_rowfilter** out) {
     if (!out || (n_keys && (!keys || !key_len))) return fail(PF_ERR_ARG, "pf_rowfilter_create: null argument");
     *out = nullptr;
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_rowfilter_create: no such device");
-    HIPCHK(hipSetDevice(device));
-    std::unique_ptr<pf_rowfilter, void (*)(pf_rowfilter*)> f(new pf_rowfilter(), pf_rowfilter_destroy);
-    f->feed.device = device;
+    FeedHandle<pf_rowfilter> f(nullptr, pf_rowfilter_destroy); PFCHK(feed_create(device, "pf_rowfilter_create", f));
     f->first_field = first_field ? 1 : 0;
     const uint64_t cap = f->cap = pf_table_room(n_keys, 4);
     std::vector<uint64_t> table(cap, RF_EMPTY);
@@ -550,7 +538,7 @@ int pf_rowfilter_create(int device, int first_field, const char* const* keys, co
         if (!f->keys.emplace(keys[i], key_len[i]).second) continue;
         pf_table_insert(table, rf_hash(keys[i], key_len[i]), [](uint64_t) { return true; });     // a set: equal hashes share a slot
     }
-    if (f->feed.ts.create() != PF_OK || f->d_set.ensure(cap * 8, true) != PF_OK || f->d_count.ensure(8, true) != PF_OK)
+    if (f->d_set.ensure(cap * 8, true) != PF_OK || f->d_count.ensure(8, true) != PF_OK)
         return fail(PF_ERR_HIP, "pf_rowfilter_create: device allocation failed");
     if (hipMemcpy(f->d_set.p, table.data(), cap * 8, hipMemcpyHostToDevice) != hipSuccess)
         return fail(PF_ERR_HIP, "pf_rowfilter_create: upload failed");
@@ -1068,19 +1056,14 @@ int pg_scan_device(pf_plotgrid* g, uint64_t n, uint64_t skip) {
 
 extern "C" {
 
-void pf_plotgrid_destroy(pf_plotgrid* g) { if (g) { (void)hipSetDevice(g->feed.device); delete g; } }
+void pf_plotgrid_destroy(pf_plotgrid* g) { feed_destroy(g); }
 
 int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* strain_len, uint32_t n_strains,
                        const int32_t* columns, int zoom, int64_t start, int64_t stop, pf_plotgrid** out) {
     if (!out || !columns || (n_strains && (!strains || !strain_len))) return fail(PF_ERR_ARG, "pf_plotgrid_create: null argument");
     *out = nullptr;
     if (n_strains >= (1u << 24)) return fail(PF_ERR_ARG, "pf_plotgrid_create: at most 2^24 - 1 phenotype strains");
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_plotgrid_create: no such device");
-    HIPCHK(hipSetDevice(device));
-    std::unique_ptr<pf_plotgrid, void (*)(pf_plotgrid*)> g(new pf_plotgrid(), pf_plotgrid_destroy);
-    g->feed.device = device;
+    FeedHandle<pf_plotgrid> g(nullptr, pf_plotgrid_destroy); PFCHK(feed_create(device, "pf_plotgrid_create", g));
     g->zoom = zoom ? 1 : 0;
     g->start = start; g->stop = stop;
     g->n_strains = n_strains;
@@ -1106,7 +1089,6 @@ int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* s
         if (slot >= 0) ids[slot] = i;
     }
     g->strain_cap = cap;
-    PFCHK(g->feed.ts.create());
     PFCHK(g->d_strain_hash.ensure(cap * 8, true));
     PFCHK(g->d_strain_id.ensure(cap * 4, true));
     PFCHK(g->d_strain_bytes.ensure(std::max<size_t>(bytes.size(), 1), true));
@@ -1835,7 +1817,7 @@ int kj_next_members(pf_kmerjoin* j, const char** piece, uint64_t* nbytes) {
 
 extern "C" {
 
-void pf_kmerjoin_destroy(pf_kmerjoin* j) { if (j) { (void)hipSetDevice(j->feed.device); delete j; } }
+void pf_kmerjoin_destroy(pf_kmerjoin* j) { feed_destroy(j); }
 
 int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* cluster_len, const uint32_t* cluster_bunch,
                        uint64_t n_clusters, uint32_t n_bunches, const char* const* key_cluster, const uint32_t* key_cluster_len,
@@ -1846,12 +1828,7 @@ int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* 
         (n_keys && (!key_cluster || !key_cluster_len || !key_kmer || !key_kmer_len || !text0 || !text0_len || !text1 || !text1_len)))
         return fail(PF_ERR_ARG, "pf_kmerjoin_create: null argument");
     *out = nullptr;
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_kmerjoin_create: no such device");
-    HIPCHK(hipSetDevice(device));
-    std::unique_ptr<pf_kmerjoin, void (*)(pf_kmerjoin*)> j(new pf_kmerjoin(), pf_kmerjoin_destroy);
-    j->feed.device = device;
+    FeedHandle<pf_kmerjoin> j(nullptr, pf_kmerjoin_destroy); PFCHK(feed_create(device, "pf_kmerjoin_create", j));
     j->n_bunches = std::max<uint32_t>(n_bunches, 1);
     std::string arena;
     auto put = [&arena](const char* s, uint32_t n) { const size_t at = arena.size(); arena.append(s, n); return (uint32_t)at; };
@@ -1892,7 +1869,6 @@ int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* 
     }
     if (arena.size() >= (1ull << 32)) return fail(PF_ERR_CAPACITY, "pf_kmerjoin_create: the keys and their texts take 4 GiB or more");
     j->counters.assign((size_t)j->n_bunches * KJ_COUNTERS, 0);
-    PFCHK(j->feed.ts.create());
     PFCHK(dev_upload(j->d_chash, chash)); PFCHK(dev_upload(j->d_cslot, cslot)); PFCHK(dev_upload(j->d_clusters, cl));
     PFCHK(dev_upload(j->d_khash, khash)); PFCHK(dev_upload(j->d_kslot, kslot)); PFCHK(dev_upload(j->d_keys, keys));
     PFCHK(dev_upload(j->d_arena, std::vector<char>(arena.begin(), arena.end())));
@@ -2221,21 +2197,15 @@ int af_scan_device(pf_assocfilter* f, uint64_t n, uint64_t begin) {
 
 extern "C" {
 
-void pf_assocfilter_destroy(pf_assocfilter* f) { if (f) { (void)hipSetDevice(f->feed.device); delete f; } }
+void pf_assocfilter_destroy(pf_assocfilter* f) { feed_destroy(f); }
 
 int pf_assocfilter_create(int device, uint32_t pvalue_field, uint32_t n_fields, double thr_hi, pf_assocfilter** out) {
     if (!out) return fail(PF_ERR_ARG, "pf_assocfilter_create: null argument");
     *out = nullptr;
     if (!n_fields || pvalue_field >= n_fields) return fail(PF_ERR_ARG, "pf_assocfilter_create: the p-value field is not one of the header's");
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(PF_ERR_ARG, "pf_assocfilter_create: no such device");
-    HIPCHK(hipSetDevice(device));
-    std::unique_ptr<pf_assocfilter, void (*)(pf_assocfilter*)> f(new pf_assocfilter(), pf_assocfilter_destroy);
-    f->feed.device = device;
+    FeedHandle<pf_assocfilter> f(nullptr, pf_assocfilter_destroy); PFCHK(feed_create(device, "pf_assocfilter_create", f));
     f->pvalue_field = pvalue_field; f->n_fields = n_fields; f->thr_hi = thr_hi;
     f->cols.assign(n_fields, 0);
-    PFCHK(f->feed.ts.create());
     PFCHK(dev_upload(f->d_cols, f->cols));
     PFCHK(dev_upload(f->d_misc, std::vector<uint64_t>(2, 0)));
     *out = f.release();
