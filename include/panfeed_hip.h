@@ -531,6 +531,35 @@ int pf_kmers_tsv_stream_block_cuts(pf_ctx* ctx, uint64_t* text_off, uint64_t* te
  * there is no such text. */
 int pf_kmers_tsv_seq_ends(pf_ctx* ctx, uint64_t* ends, uint32_t n);
 
+/* Rows of passing patterns only.  pf_set_passing_hashes turns the filter on with the n digests at md5 (16 bytes each, the
+ * bytes whose base64 the files print; repeats count once; n = 0 is allowed: no row passes).  While it is on, the text of
+ * pf_render_kmers_tsv_device and of pf_kmers_tsv_stream_begin / _next -- its size, ranges, budget check, peak, the
+ * offsets of pf_kmers_tsv_seq_ends (a sequence none of whose rows are kept repeats the end before it) and of
+ * pf_kmers_tsv_stream_cuts / _block_cuts -- is the unfiltered text with exactly those rows kept, in their order, whose
+ * (cluster, k-mer) pair is a kept k-mer of the last pf_submit with a pattern digest in the set: the pairs
+ * kmers_to_hashes.tsv lists with such a hash.  The GPU decides before a byte of a dropped row is written.
+ * pf_render_kmers_tsv (the host renderer), kmers_to_hashes and hashes_to_patterns are not affected.
+ * pf_clear_passing_hashes turns the filter off and frees what it held.  Both are PF_ERR_STATE while a kmers.tsv
+ * stream is open. */
+int pf_set_passing_hashes(pf_ctx* ctx, const uint8_t* md5, uint64_t n);
+int pf_clear_passing_hashes(pf_ctx* ctx);
+/* While the filter is on, after every pf_submit and before the batch's first kmers.tsv text (else that text's call is
+ * PF_ERR_STATE): the batch's cluster names (n_clusters NUL-terminated strings, batch order; a pf_target_seq's `cluster`
+ * is looked up among them, an unknown one is PF_ERR_ARG) and the text of its slow-path rows, as pf_render_device takes
+ * them (klength bytes each, back to back; NULL without such rows).  Both are copied.  PF_ERR_STATE without a
+ * successful pf_submit or while a kmers.tsv stream is open. */
+int pf_passing_batch_names(pf_ctx* ctx, const char* const* cluster_names, const char* extra_keys, uint64_t n_extra);
+/* out[0] digests in the set, [1] kept k-mers marked as passing for the last filtered text, [2] rows that text
+ * considered, [3] rows it kept, [4] lookups since that text's marking whose slot hash matched and whose bytes did not,
+ * [5] device bytes the filter holds (its tables are not part of a stream's text budget). */
+int pf_passing_stats(pf_ctx* ctx, uint64_t out[6]);
+/* Milliseconds (hipEvent) of the last filtered text's mark and index kernel. */
+int pf_passing_mark_ms(pf_ctx* ctx, float* ms);
+/* Test hook: the passing set's and the batch index's lookups keep only the low `bits` bits of their slot hash (64: all
+ * of it, the product; 0: one chain), so that the compare-and-reject branch runs in the shipped library.  The value is a
+ * kernel argument.  PF_ERR_ARG above 64, PF_ERR_STATE while a kmers.tsv stream is open. */
+int pf_debug_passing_hash_bits(pf_ctx* ctx, uint32_t bits);
+
 /* The bodies of kmers_to_hashes.tsv and hashes_to_patterns.tsv of the last pf_submit written ON THE DEVICE
  * (panfeed.py:177,208 and :181-187,217-223): rows assembled in LDS, coalesced stores, one copy to pinned host memory.
  * No pf_fetch needed; the k-mer keys and pattern rows never cross PCIe, only the text does.  names: cluster names in

@@ -76,6 +76,17 @@ def get_options(argv=None):
                         "read and write (not with --multiple-files or on several GPUs)")
     p.add_argument("--gpu-compress-clusters", action="store_true", default=False,
                    help="with --multiple-files: gzip the per-cluster files on the GPU; implies --compress")
+    p.add_argument("--passing-hashes", metavar="FILE", default=None,
+                   help="write only the kmers.tsv rows of passing patterns: those whose (cluster, k-mer) kmers_to_hashes.tsv "
+                        "lists with one of the hashed_pattern values of FILE (one per line); decided on the GPU before a "
+                        "dropped row is written; the other two files are not affected (not on several GPUs)")
+    p.add_argument("--passing-associations", metavar="FILE", default=None,
+                   help="the same, with the passing hashes taken from an associations table as panfeed-get-kmers takes "
+                        "them: the rows whose --passing-column is at most --passing-threshold")
+    p.add_argument("--passing-threshold", type=float, default=None,
+                   help="with --passing-associations (default: 1)")
+    p.add_argument("--passing-column", default=None,
+                   help="with --passing-associations (default: lrt-pvalue)")
     p.add_argument("--cores", type=int, default=1,
                    help="accepted for compatibility; the GPU does the work of the worker processes")
     p.add_argument("-ql", "--queue-limit", type=int, default=3,
@@ -111,10 +122,51 @@ def read_names(path):
         return {line.rstrip("\n") for line in fh}
 
 
-def main(argv=None, run=None, launch=None, rank_entry=None):
+def is_hashed_pattern(text):
+    """whether `text` is a hashed_pattern as the files print it: the 24 base64 characters of a 16-byte digest"""
+    import binascii
+    if len(text) != 24:
+        return False
+    try:
+        d = binascii.a2b_base64(text)
+    except (binascii.Error, ValueError):
+        return False
+    return len(d) == 16 and binascii.b2a_base64(d)[:24].decode() == text
+
+
+def passing_hashes(values, source):
+    """the hashed_pattern values among `values` (strings), in order and once each; a blank one is skipped, any other that
+    is no such digest matches nothing: their number is logged once, as a warning"""
+    good, bad = {}, 0
+    for v in values:
+        v = v.rstrip("\r\n")
+        if not v.strip():
+            continue
+        if is_hashed_pattern(v):
+            good[v] = None
+        else:
+            bad += 1
+    if bad:
+        logger.warning(f"{bad} entr{'y' if bad == 1 else 'ies'} of {source} {'is' if bad == 1 else 'are'} not a "
+                       "hashed_pattern (24 base64 characters of a 16-byte digest) and match nothing")
+    return list(good)
+
+
+def associations_hashes(path, threshold, column, device):
+    """the passing hashes of an associations table, as the downstream tools take them (downstream._associations: the same
+    device pass, the same fallbacks; a missing column ends the command with status 1 and the tools' message)"""
+    import argparse
+    from . import downstream
+    ns = argparse.Namespace(associations=path, threshold=threshold, column=column, output=None, device=device,
+                            host_gunzip=False, host_associations=False)
+    return downstream._associations(ns, index_name="hashed_pattern")[1]
+
+
+def main(argv=None, run=None, launch=None, rank_entry=None, associations=None):
     """the panfeed command; returns the exit status.  run: what does the work on one GPU (default pipeline.run_files);
     launch: what starts the ranks of `--gpus N` (default rank.launch); rank_entry: what this process does as one rank of
-    a launcher's world (default rank.run_rank).  Tests pass their own."""
+    a launcher's world (default rank.run_rank); associations: what reads the passing hashes of --passing-associations
+    (default associations_hashes).  Tests pass their own."""
     from . import rank as rank_mod
     args = get_options(argv)
     set_logging(args.v)
@@ -146,6 +198,17 @@ def main(argv=None, run=None, launch=None, rank_entry=None):
             logger.error("--bgzf is for the three files of a run on one GPU: --multiple-files, --gpus N and a launched rank "
                          "are deliberately out of its scope; nothing was run")
             return 2
+    if args.passing_hashes is not None and args.passing_associations is not None:
+        logger.error("--passing-hashes and --passing-associations both name the passing patterns: give one of them")
+        return 2
+    if args.passing_associations is None and (args.passing_threshold is not None or args.passing_column is not None):
+        logger.error("--passing-threshold and --passing-column belong to --passing-associations: give it with them")
+        return 2
+    passing_on = args.passing_hashes is not None or args.passing_associations is not None
+    if passing_on and (rank_mod.launched() or (args.gpus is not None and args.gpus != 1)):
+        logger.error("--passing-hashes / --passing-associations filter the kmers.tsv of a run on one GPU: --gpus N and a "
+                     "launched rank are deliberately out of their scope; nothing was run")
+        return 2
     if args.targets is not None:
         logger.debug(f"Reading target strains ({args.targets})")
         targets = read_names(args.targets)
@@ -184,6 +247,23 @@ def main(argv=None, run=None, launch=None, rank_entry=None):
         more["device_gzip_clusters"] = True
     if args.bgzf:
         more["bgzf"] = True
+    if passing_on:
+        if args.passing_hashes is not None:
+            logger.debug(f"Reading passing hashes ({args.passing_hashes})")
+            with open(args.passing_hashes) as fh:
+                more["passing_hashes"] = passing_hashes(fh, args.passing_hashes)
+        else:
+            try:
+                found = (associations or associations_hashes)(
+                    args.passing_associations, 1 if args.passing_threshold is None else args.passing_threshold,
+                    "lrt-pvalue" if args.passing_column is None else args.passing_column, args.device)
+            except SystemExit as e:        # (the tools' way out of a missing column: their message has been logged)
+                return e.code if isinstance(e.code, int) else 1
+            more["passing_hashes"] = passing_hashes(found, args.passing_associations)
+        if not targets:
+            logger.info("No target strains: the passing patterns have no kmers.tsv rows to choose among")
+        else:
+            logger.info(f"kmers.tsv will hold the rows of {len(more['passing_hashes'])} passing patterns only")
     from ._lib import PanfeedHipError
     from .engine import gzip_modes
     compress = gzip_modes(args.compress, args.gpu_compress, args.multiple_files, args.gpu_compress_clusters)[0]
@@ -225,5 +305,7 @@ def main(argv=None, run=None, launch=None, rank_entry=None):
     for line in (stats.get("log") or "").splitlines():
         logger.warning(line)
     logger.info(f"{stats.get('clusters', 0)} gene clusters, {stats.get('instances', 0)} k-mer instances, "
-                f"{stats.get('patterns', 0)} patterns written to {args.output}")
+                f"{stats.get('patterns', 0)} patterns written to {args.output}" +
+                (f"; {stats.get('kmers_rows_kept', 0)} of {stats.get('kmers_rows_considered', 0)} kmers.tsv rows kept "
+                 "(passing patterns only)" if passing_on else ""))
     return 0

@@ -29,6 +29,8 @@
 #include <numeric>
 #include <thread>
 #include <string>
+#include <unordered_map>
+#include <unordered_set>
 #include <atomic>
 #include <vector>
 
@@ -236,6 +238,7 @@ struct RenderText {
 // while the range before it leaves through the pinned blocks.  pf_kmers_tsv_stream_begin / _next hand the ranges out in
 // order; pf_render_kmers_tsv_device writes the whole text as one range into text[0], where `bytes` of it stay for
 // pf_device_text_chunk.  Each begin ends the other's text.
+struct KtHostFilter;
 struct TargetText {
     DevBuf seqs, tiles, prefix, tbytes, toff, text[2];
     uint64_t bytes = 0;
@@ -253,6 +256,9 @@ struct TargetText {
         KtHostText host;                       // their one measurement
         KtPlan plan;
         pf::KtParams kp{};
+        bool filter = false;                   // the text is the filtered one: kf beside kp, hfilter for the host's share
+        pf::KtFilter kf{};
+        std::unique_ptr<KtHostFilter> hfilter;
         uint32_t cur = 0;                      // the block to queue next: range cur, bytes from cur_off
         uint64_t cur_off = 0, pin_bytes = 0;
         std::unique_ptr<char[]> htext[2];      // the host's share of the range being written into each buffer
@@ -303,6 +309,39 @@ int gz_check_flags(uint32_t flags, const char* who) {
 
 }  // namespace
 
+namespace {
+// Rows of passing patterns only (pf_set_passing_hashes).  The set: the caller's distinct digests and their table on the
+// device.  Per batch: the clusters' names and the slow-path rows' text (pf_passing_batch_names), and what the text's
+// opening (kt_filter_prepare) leaves -- the marks of the kept k-mers of the clusters that own a target sequence, the
+// index of the passing ones, the row kernels' keep bits -- with the counts pf_passing_stats reports.
+struct PassingRows {
+    bool on = false;
+    uint32_t bits = 64;                       // pf_debug_passing_hash_bits
+    std::vector<uint8_t> digests;             // n x 16, distinct
+    DevBuf set;                               // pf::PassSlot [set_mask + 1]
+    uint64_t set_mask = 0;
+    bool have_names = false;                  // since the last pf_submit
+    std::unordered_map<std::string, uint32_t> name_idx;
+    std::string extra;                        // klength bytes per slow-path row of the batch
+    DevBuf ref, hsh, mark, counters, mark_cluster, mark_off, koff, arena_of, seq_cluster, keep_bits, tile_rows;
+    uint64_t marked = 0, considered = 0, kept = 0;
+    float mark_ms = 0.0f;                     // the last text's mark and index kernel (hipEvent)
+    HipEvent ev0, ev1;
+    uint64_t device_bytes() const {
+        uint64_t n = 0;
+        for (const DevBuf* b : {&set, &ref, &hsh, &mark, &counters, &mark_cluster, &mark_off, &koff, &arena_of, &seq_cluster, &keep_bits, &tile_rows}) n += b->cap;
+        return n;
+    }
+};
+// the host's statement of the filter for the sequences it renders: per such sequence the text of its cluster's passing
+// k-mers (built from the marks and keys of those clusters only), and the rows it looked at and kept
+struct KtHostFilter {
+    std::vector<std::unordered_set<std::string>> sets;     // per cluster that owns a host-rendered sequence
+    std::vector<uint32_t> seq_set;                         // per host-rendered sequence: its cluster's set
+    std::atomic<uint64_t> considered{0}, kept{0};
+};
+}  // namespace
+
 struct pf_ctx {
     int device = 0;
     HipStream stream;
@@ -333,6 +372,7 @@ struct pf_ctx {
     TargetText kt;                         // the target text's (kmers.tsv) with its stream,
     GzMode gz;                             // the gzip mode,
     PatternRowStream pr;                   // and the stream of pattern rows
+    PassingRows passing;                   // the filter of kmers.tsv rows (pf_set_passing_hashes)
     pf_batch last{};                      // the last pf_submit's batch arrays as device pointers (valid until the next submit)
     uint32_t last_nseg = 0;
     uint64_t last_words = 0;              // words of last.packed: the batch's, or the buffer pf_submit_gather filled
@@ -405,6 +445,7 @@ void kt_stream_end(pf_ctx* c) {
     S.active = false; c->kt.flight.valid = false;
     S.hseqs.clear(); S.host = KtHostText{}; S.plan = KtPlan{};
     S.cuts.clear(); S.handed = -1;
+    S.filter = false; S.hfilter.reset();
 }
 // the end of a pattern-row stream (its last slice handed out, the next pf_submit, a kmers.tsv text begun, pf_destroy):
 // nothing of it is in flight afterwards
@@ -708,6 +749,24 @@ struct RowWrite {
     void ch(char x) { *w++ = x; }
     void num(long long v) { w = put_i64(w, v); }
     void revcomp(const char* last, uint32_t k) { for (uint32_t q = 0; q < k; q++) w[q] = *(last - q); w += k; }   // complement letters, backwards
+};
+
+// Under the passing-rows filter: a row gathered until its line end, then handed on as one piece if its k-mer -- the k
+// bytes before the line end -- is among the cluster's passing k-mers
+template <class Inner>
+struct RowFilter {
+    Inner& in; const std::unordered_set<std::string>& set; uint32_t k;
+    std::string row; uint64_t seen = 0, kept = 0;
+    void text(const char* p, size_t l) { row.append(p, l); }
+    void num(long long v) { char t[24]; row.append(t, (size_t)(put_i64(t, v) - t)); }
+    void revcomp(const char* last, uint32_t n) { for (uint32_t q = 0; q < n; q++) row.push_back(*(last - q)); }
+    void ch(char x) {
+        row.push_back(x);
+        if (x != '\n') return;
+        seen++;
+        if (row.size() > k && set.count(row.substr(row.size() - 1 - k, k))) { kept++; in.text(row.data(), row.size()); }
+        row.clear();
+    }
 };
 
 // The rows of target sequence s, in order, field by field into `out` (two rows per window in non-canonical mode).
@@ -1910,6 +1969,7 @@ struct SubmitRun {
 int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* counters, uint64_t* need, bool rerun) {
     c->have_batch = false;
     c->kt.have_seq_end = false;
+    c->passing.have_names = false;
     kt_stream_end(c);                     // a kmers.tsv stream of the batch before is over,
     pr_stream_end(c);                     // and so is a stream of pattern rows
     // whatever way this call ends, nothing it queued is still reading the caller's arrays or the pinned staging
@@ -2283,7 +2343,7 @@ int pf_render_hashes_to_patterns(pf_ctx* c, char** out, uint64_t* nbytes) {
 namespace {
 // Measure: which strand every window of the n target sequences uses, taken once from the device's strand bits, and with
 // that the exact size of every sequence's rows -- no worst-case sizing, no compaction afterwards.
-int kt_host_measure(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, const uint32_t* seg_strand_off, KtHostText& M) {
+int kt_host_measure(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, const uint32_t* seg_strand_off, KtHostText& M, KtHostFilter* F = nullptr) {
     if (!c || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
     if (!c->have_batch) return fail(PF_ERR_STATE, "pf_render_kmers_tsv without a successful pf_submit");
     HIPCHK(hipSetDevice(c->device));
@@ -2316,7 +2376,11 @@ int kt_host_measure(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, const uint
                 }
             }
             RowCount cnt;
-            if (!kt_host_rows(s, k, canon, rcflag, cnt)) bad = true;
+            if (F) {                                   // the filtered text: only the kept rows count
+                RowFilter<RowCount> f{cnt, F->sets[F->seq_set[i]], k};
+                if (!kt_host_rows(s, k, canon, rcflag, f)) bad = true;
+                F->considered += f.seen; F->kept += f.kept;
+            } else if (!kt_host_rows(s, k, canon, rcflag, cnt)) bad = true;
             M.size[i] = cnt.n;
         }
     });
@@ -2326,7 +2390,7 @@ int kt_host_measure(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, const uint
 }
 
 // Write: the rows of the measured sequences [i0, i1), back to back from dst on, each sequence at its exact place
-int kt_host_write(pf_ctx* c, const pf_target_seq* seqs, const KtHostText& M, uint32_t i0, uint32_t i1, char* dst) {
+int kt_host_write(pf_ctx* c, const pf_target_seq* seqs, const KtHostText& M, uint32_t i0, uint32_t i1, char* dst, const KtHostFilter* F = nullptr) {
     const uint32_t k = c->o.klength;
     const bool canon = c->o.canon != 0;
     std::vector<uint64_t> off((size_t)(i1 - i0) + 1, 0);
@@ -2335,7 +2399,11 @@ int kt_host_write(pf_ctx* c, const pf_target_seq* seqs, const KtHostText& M, uin
     parallel_for(i1 - i0, [&](uint64_t a, uint64_t b) {
         for (uint64_t j = a; j < b; j++) {
             RowWrite wr{dst + off[j]};
-            kt_host_rows(seqs[i0 + j], k, canon, canon ? M.rcflags.data() + M.fl_off[i0 + j] : nullptr, wr);
+            const uint8_t* rcflag = canon ? M.rcflags.data() + M.fl_off[i0 + j] : nullptr;
+            if (F) {
+                RowFilter<RowWrite> f{wr, F->sets[F->seq_set[i0 + j]], k};
+                kt_host_rows(seqs[i0 + j], k, canon, rcflag, f);
+            } else kt_host_rows(seqs[i0 + j], k, canon, rcflag, wr);
             if ((uint64_t)(wr.w - (dst + off[j])) != M.size[i0 + j]) bad = true;
         }
     });
@@ -2370,7 +2438,156 @@ struct KtLayout {
     std::vector<uint32_t> host_idx;     // sequences left to the host renderer
     std::vector<uint8_t> on_dev;
     pf::KtParams kp{};
+    // under the passing-rows filter: the kernels' second argument, the kept rows of every tile, the candidate rows of the
+    // device's sequences, and the host's sets
+    bool filter = false;
+    pf::KtFilter kf{};
+    std::vector<uint32_t> trows;
+    uint64_t dev_rows = 0;
+    std::unique_ptr<KtHostFilter> hfilter;
 };
+
+// The passing set's table from the digests the context holds, at the hash width in force
+int passing_build_set(pf_ctx* c) {
+    PassingRows& F = c->passing;
+    const uint64_t n = F.digests.size() / 16;
+    uint64_t cap = 16;
+    while (cap < 2 * n + 2) cap <<= 1;
+    std::vector<pf::PassSlot> slots(cap, pf::PassSlot{0, 0, 0, 0});
+    for (uint64_t i = 0; i < n; i++) {
+        uint64_t d[2];
+        memcpy(d, F.digests.data() + i * 16, 16);
+        const uint64_t h = pf::pass_digest_hash(d[0], d[1], F.bits);
+        uint64_t at = h & (cap - 1);
+        while (slots[at].used) at = (at + 1) & (cap - 1);
+        slots[at] = pf::PassSlot{d[0], d[1], h, 1};
+    }
+    HIPCHK(hipSetDevice(c->device));
+    PFCHK(F.set.ensure(cap * sizeof(pf::PassSlot)));
+    HIPCHK(hipMemcpy(F.set.p, slots.data(), cap * sizeof(pf::PassSlot), hipMemcpyHostToDevice));
+    F.set_mask = cap - 1;
+    return PF_OK;
+}
+
+// Mark and index, once per text: the kept k-mers of the clusters that own one of the text's sequences are marked by
+// their patterns' digests (pass_mark_kernel), the passing ones entered into the batch index the row kernels probe.  For
+// the clusters of the host-rendered sequences the marks and keys come down and become the text of their passing k-mers.
+// all_cl: the cluster of every sequence that has a window (~0u: none); dev_cl: of the device-written ones, in order.
+int kt_filter_prepare(pf_ctx* c, const std::vector<uint32_t>& all_cl, const std::vector<uint32_t>& dev_cl, KtLayout& L) {
+    PassingRows& F = c->passing;
+    const uint32_t C = c->n_clusters, KW = (uint32_t)c->KW, k = c->o.klength, NT = (uint32_t)L.tiles.size();
+    hipStream_t st = c->stream;
+    std::vector<uint64_t> koff(C);
+    std::vector<uint32_t> kcnt(C), arena_of(C);
+    if (C) {
+        HIPCHK(hipMemcpyAsync(koff.data(), c->batch.cl_kmer_off.p, (size_t)C * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(kcnt.data(), c->batch.cl_kmer_cnt.p, (size_t)C * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    std::vector<uint8_t> owns(C, 0);
+    for (uint32_t cl : all_cl) if (cl != ~0u) owns[cl] = 1;
+    std::vector<uint32_t> mcl, mark_of(C, ~0u);
+    std::vector<uint64_t> moff{0};
+    for (uint32_t i = 0; i < C; i++) {
+        const uint32_t a = c->cluster_arena[i];
+        arena_of[i] = a;
+        koff[i] = kcnt[i] ? koff[i] - c->arenas[a]->base : 0;
+        if (!owns[i]) continue;
+        mark_of[i] = (uint32_t)mcl.size();
+        mcl.push_back(i);
+        moff.push_back(moff.back() + kcnt[i]);
+    }
+    const uint64_t M = moff.back();
+    uint64_t cap = 64;
+    while (cap < 2 * M + 2) cap <<= 1;
+    if ((M + 255) / 256 > 0x7FFFFFFFull) return fail(PF_ERR_CAPACITY, "passing rows: %llu kept k-mers to mark", (unsigned long long)M);
+    PFCHK(F.ref.ensure(cap * 8)); PFCHK(F.hsh.ensure(cap * 8)); PFCHK(F.mark.ensure(std::max<uint64_t>(M, 1)));
+    PFCHK(F.counters.ensure(16));
+    PFCHK(F.mark_cluster.ensure(std::max<size_t>(mcl.size(), 1) * 4)); PFCHK(F.mark_off.ensure(moff.size() * 8));
+    PFCHK(F.koff.ensure(std::max<size_t>(C, 1) * 8)); PFCHK(F.arena_of.ensure(std::max<size_t>(C, 1) * 4));
+    PFCHK(F.seq_cluster.ensure(std::max<size_t>(dev_cl.size(), 1) * 4));
+    PFCHK(F.keep_bits.ensure(std::max<size_t>(NT, 1) * (pf::KT_ROWS / 64) * 8)); PFCHK(F.tile_rows.ensure(std::max<size_t>(NT, 1) * 4));
+    if (!mcl.empty()) HIPCHK(hipMemcpyAsync(F.mark_cluster.p, mcl.data(), mcl.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(F.mark_off.p, moff.data(), moff.size() * 8, hipMemcpyHostToDevice, st));
+    if (C) {
+        HIPCHK(hipMemcpyAsync(F.koff.p, koff.data(), (size_t)C * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(F.arena_of.p, arena_of.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
+    }
+    if (!dev_cl.empty()) HIPCHK(hipMemcpyAsync(F.seq_cluster.p, dev_cl.data(), dev_cl.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(F.counters.p, 0, 16, st));
+    PFCHK(fill_u64(c, F.ref.p, pf::EMPTY64, cap));
+    PFCHK(F.ev0.ensure()); PFCHK(F.ev1.ensure());
+    HIPCHK(hipEventRecord(F.ev0, st));
+    if (M) {
+        pf::PassMarkParams mp{};
+        mp.mark_cluster = F.mark_cluster.as<uint32_t>(); mp.mark_off = F.mark_off.as<uint64_t>();
+        mp.n_mark = (uint32_t)mcl.size(); mp.n_patterns = c->n_patterns;
+        mp.kmer_off = F.koff.as<uint64_t>(); mp.cluster_arena = F.arena_of.as<uint32_t>();
+        for (size_t a = 0; a < c->n_passes; a++) { mp.arena_key[a] = c->arenas[a]->key.as<uint64_t>(); mp.arena_pid[a] = c->arenas[a]->pid.as<uint32_t>(); }
+        mp.md5 = c->pats.md5.as<uint8_t>();
+        mp.set = F.set.as<pf::PassSlot>(); mp.set_mask = F.set_mask;
+        mp.ref = F.ref.as<uint64_t>(); mp.hsh = F.hsh.as<uint64_t>(); mp.mask = cap - 1;
+        mp.mark = F.mark.as<uint8_t>(); mp.counters = F.counters.as<unsigned long long>();
+        mp.KW = KW; mp.bits = F.bits;
+        hipLaunchKernelGGL(pf::pass_mark_kernel, dim3((uint32_t)((M + 255) / 256)), dim3(256), 0, st, mp);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(F.ev1, st));
+    uint64_t cnt[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(cnt, F.counters.p, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));            // (the vectors above have gone up; the marks are written)
+    F.marked = cnt[0];
+    F.mark_ms = 0.0f;
+    (void)hipEventElapsedTime(&F.mark_ms, F.ev0, F.ev1);
+    pf::KtFilter& kf = L.kf;
+    kf.seq_cluster = F.seq_cluster.as<uint32_t>();
+    kf.ref = F.ref.as<uint64_t>(); kf.hsh = F.hsh.as<uint64_t>(); kf.mask = cap - 1;
+    kf.kmer_off = F.koff.as<uint64_t>(); kf.cluster_arena = F.arena_of.as<uint32_t>();
+    for (size_t a = 0; a < c->n_passes; a++) kf.arena_key[a] = c->arenas[a]->key.as<uint64_t>();
+    kf.keep_bits = F.keep_bits.as<uint64_t>(); kf.tile_rows = F.tile_rows.as<uint32_t>();
+    kf.counters = F.counters.as<unsigned long long>();
+    kf.KW = KW; kf.bits = F.bits;
+    // ---- the host's share: the passing k-mers, as text, of the clusters whose sequences it renders
+    L.hfilter.reset(new KtHostFilter);
+    KtHostFilter& H = *L.hfilter;
+    std::vector<uint32_t> set_of(C, ~0u);
+    std::vector<uint8_t> marks;
+    std::vector<uint64_t> keys;
+    for (uint32_t i : L.host_idx) {
+        const uint32_t cl = all_cl[i];
+        if (set_of[cl] == ~0u) {
+            set_of[cl] = (uint32_t)H.sets.size();
+            H.sets.emplace_back();
+            std::unordered_set<std::string>& set = H.sets.back();
+            const uint32_t n = kcnt[cl];
+            if (n) {
+                marks.resize(n); keys.resize((size_t)n * KW);
+                HIPCHK(hipMemcpy(marks.data(), F.mark.as<uint8_t>() + moff[mark_of[cl]], n, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(keys.data(), c->arenas[arena_of[cl]]->key.as<uint64_t>() + koff[cl] * KW, (size_t)n * KW * 8, hipMemcpyDeviceToHost));
+            }
+            std::string t(k, 'A');
+            for (uint32_t j = 0; j < n; j++) {
+                if (!marks[j]) continue;
+                const uint64_t* key = keys.data() + (size_t)j * KW;
+                if (key[0] >> 63) {
+                    const uint64_t e = (uint32_t)key[0];
+                    if ((e + 1) * k > F.extra.size()) return fail(PF_ERR_STATE, "passing rows: a slow-path row's text was not given (pf_passing_batch_names)");
+                    t.assign(F.extra, (size_t)e * k, k);
+                } else {
+                    for (uint32_t q = 0; q < k; q++) {
+                        const uint32_t b0 = 2 * (k - 1 - q), b1 = b0 + 1;
+                        const uint32_t code = (uint32_t)((key[KW - 1 - b0 / 63] >> (b0 % 63)) & 1) | ((uint32_t)((key[KW - 1 - b1 / 63] >> (b1 % 63)) & 1) << 1);
+                        t[q] = "ACGT"[code];
+                    }
+                }
+                set.insert(t);
+            }
+        }
+        H.seq_set.push_back(set_of[cl]);
+    }
+    return PF_OK;
+}
+
 int kt_layout(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, KtLayout& L) {
     const uint32_t k = c->o.klength;
     const bool canon = c->o.canon != 0;
@@ -2382,10 +2599,24 @@ int kt_layout(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, KtLayout& L) {
     L.on_dev.assign(n, 0);
     std::string prefix;
     auto digits = [](long long v) { return len_i64(v); };
+    PassingRows& F = c->passing;
+    L.filter = F.on;
+    std::vector<uint32_t> all_cl, dev_cl;
+    if (L.filter) {
+        if (!F.have_names) return fail(PF_ERR_STATE, "the passing-rows filter is on: pf_passing_batch_names must follow pf_submit before a kmers.tsv text");
+        if (c->n_passes > pf::TEXT_MAX_ARENAS) return fail(PF_ERR_CAPACITY, "passing rows: the batch took %u passes, the filter's kernels read %u arenas", c->n_passes, pf::TEXT_MAX_ARENAS);
+        if ((uint32_t)c->KW > pf::PASS_MAX_KW) return fail(PF_ERR_ARG, "passing rows: keys of %d words", c->KW);
+        all_cl.assign(n, ~0u);
+    }
     for (uint32_t i = 0; i < n; i++) {
         const pf_target_seq& s = seqs[i];
         const long long nk = (long long)s.len - k + 1;
         if (nk <= 0) continue;                   // no window, no row (panfeed.py:59,64)
+        if (L.filter) {
+            const auto it = F.name_idx.find(s.cluster);
+            if (it == F.name_idx.end()) return fail(PF_ERR_ARG, "passing rows: target sequence %u names cluster '%s', which is not of the last batch", i, s.cluster);
+            all_cl[i] = it->second;
+        }
         bool dev = s.n_segs == 1 && s.n_ambig == 0 && s.seg_start[0] == 0 && s.seg_nwin[0] == (uint64_t)nk &&
                    s.seg_index[0] < c->last_nseg && (uint64_t)nk * reps < 0xFFFFFF00ull;
         size_t plen = 0;
@@ -2400,6 +2631,7 @@ int kt_layout(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, KtLayout& L) {
         }
         if (!dev) { L.host_idx.push_back(i); continue; }
         L.on_dev[i] = 1;
+        if (L.filter) { dev_cl.push_back(all_cl[i]); L.dev_rows += (uint64_t)nk * reps; }
         pf::KtSeq q{};
         q.base = s.strand > 0 ? s.start : s.end; q.offset = s.offset; q.strand = s.strand;
         q.seg = s.seg_index[0]; q.nk = (uint32_t)nk; q.prefix_off = (uint32_t)prefix.size(); q.prefix_len = (uint32_t)plen;
@@ -2415,6 +2647,7 @@ int kt_layout(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, KtLayout& L) {
     const uint32_t NT = (uint32_t)tiles.size();
     pf::KtParams& kp = L.kp;
     L.tbytes.assign(NT, 0);
+    if (L.filter) { L.trows.assign(NT, 0); PFCHK(kt_filter_prepare(c, all_cl, dev_cl, L)); }
     if (NT) {
         PFCHK(c->kt.seqs.ensure(ks.size() * sizeof(pf::KtSeq)));
         PFCHK(c->kt.tiles.ensure((size_t)NT * 8));
@@ -2429,8 +2662,10 @@ int kt_layout(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, KtLayout& L) {
         kp.strand_bits = c->strand_bits.as<uint64_t>();
         kp.tile_bytes = c->kt.tbytes.as<uint32_t>(); kp.tile_off = c->kt.toff.as<uint64_t>();
         kp.k = k; kp.canon = canon ? 1u : 0u;
-        hipLaunchKernelGGL(pf::kt_len_kernel, dim3(NT), dim3(pf::KT_ROWS), 0, c->stream, kp);
+        if (L.filter) hipLaunchKernelGGL(pf::kt_len_passing_kernel, dim3(NT), dim3(pf::KT_ROWS), 0, c->stream, kp, L.kf);
+        else hipLaunchKernelGGL(pf::kt_len_kernel, dim3(NT), dim3(pf::KT_ROWS), 0, c->stream, kp);
         HIPCHK(hipGetLastError());
+        if (L.filter) HIPCHK(hipMemcpyAsync(L.trows.data(), c->passing.tile_rows.p, (size_t)NT * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(L.tbytes.data(), c->kt.tbytes.p, (size_t)NT * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
@@ -2507,7 +2742,8 @@ int kt_produce(pf_ctx* c, uint32_t r) {
     if (R.t1 > R.t0) {
         pf::KtParams kp = S.kp;
         kp.text = buf; kp.tile_first = R.t0; kp.text_base = R.base;
-        hipLaunchKernelGGL(pf::kt_text_kernel, dim3(R.t1 - R.t0), dim3(pf::KT_ROWS), 0, c->stream, kp);
+        if (S.filter) hipLaunchKernelGGL(pf::kt_text_passing_kernel, dim3(R.t1 - R.t0), dim3(pf::KT_ROWS), 0, c->stream, kp, S.kf);
+        else hipLaunchKernelGGL(pf::kt_text_kernel, dim3(R.t1 - R.t0), dim3(pf::KT_ROWS), 0, c->stream, kp);
         HIPCHK(hipGetLastError());
     }
     if (R.h1 > R.h0) {
@@ -2515,7 +2751,7 @@ int kt_produce(pf_ctx* c, uint32_t r) {
         const uint64_t hbytes = std::accumulate(hsize + R.h0, hsize + R.h1, (uint64_t)0);
         S.htext[b].reset(new (std::nothrow) char[hbytes + 1]);
         if (!S.htext[b]) return fail(PF_ERR_OOM, "malloc(%llu) failed", (unsigned long long)hbytes);
-        PFCHK(kt_host_write(c, S.hseqs.data(), S.host, R.h0, R.h1, S.htext[b].get()));
+        PFCHK(kt_host_write(c, S.hseqs.data(), S.host, R.h0, R.h1, S.htext[b].get(), S.hfilter.get()));
         uint64_t at = 0;
         for (uint32_t j = R.h0; j < R.h1; j++) {
             if (hsize[j]) HIPCHK(hipMemcpyAsync(buf + (S.plan.hoff[j] - R.base), S.htext[b].get() + at, (size_t)hsize[j], hipMemcpyHostToDevice, c->stream));
@@ -2542,13 +2778,18 @@ int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget, b
     struct Guard { pf_ctx* c; bool ok; ~Guard() { if (!ok) kt_stream_end(c); } } guard{c, false};
     KtLayout L;
     PFCHK(kt_layout(c, seqs, n, L));
+    S.filter = L.filter; S.kf = L.kf; S.hfilter = std::move(L.hfilter);
     // ---- the host's share: measured here, written range by range
     S.hseqs.resize(L.host_idx.size());
     for (size_t j = 0; j < L.host_idx.size(); j++) S.hseqs[j] = seqs[L.host_idx[j]];
     if (!S.hseqs.empty()) {
         std::vector<uint32_t> sso;
         PFCHK(kt_host_sso(c, sso));
-        PFCHK(kt_host_measure(c, S.hseqs.data(), (uint32_t)S.hseqs.size(), sso.empty() ? nullptr : sso.data(), S.host));
+        PFCHK(kt_host_measure(c, S.hseqs.data(), (uint32_t)S.hseqs.size(), sso.empty() ? nullptr : sso.data(), S.host, S.hfilter.get()));
+    }
+    if (S.filter) {
+        c->passing.considered = L.dev_rows + S.hfilter->considered;
+        c->passing.kept = std::accumulate(L.trows.begin(), L.trows.end(), (uint64_t)0) + S.hfilter->kept;
     }
     const KtPlan& P = S.plan;
     kt_plan(L, S.host.size, budget, S.plan);
@@ -2754,6 +2995,76 @@ int pf_kmers_tsv_seq_ends(pf_ctx* c, uint64_t* ends, uint32_t n) {
     if ((size_t)n != c->kt.seq_end.size())
         return fail(PF_ERR_ARG, "pf_kmers_tsv_seq_ends: %u sequences asked for, the text was planned for %zu", n, c->kt.seq_end.size());
     if (n) memcpy(ends, c->kt.seq_end.data(), (size_t)n * 8);
+    return PF_OK;
+}
+
+int pf_set_passing_hashes(pf_ctx* c, const uint8_t* md5, uint64_t n) {
+    if (!c || (n && !md5)) return fail(PF_ERR_ARG, "pf_set_passing_hashes: null argument");
+    if (c->kt.stream.active) return fail(PF_ERR_STATE, "pf_set_passing_hashes while a kmers.tsv stream is open");
+    PassingRows& F = c->passing;
+    std::vector<std::array<uint8_t, 16>> d(n);
+    if (n) memcpy(d.data(), md5, n * 16);
+    std::sort(d.begin(), d.end());
+    d.erase(std::unique(d.begin(), d.end()), d.end());
+    F.digests.resize(d.size() * 16);
+    if (!d.empty()) memcpy(F.digests.data(), d.data(), d.size() * 16);
+    PFCHK(passing_build_set(c));
+    F.on = true;
+    F.marked = F.considered = F.kept = 0;
+    return PF_OK;
+}
+
+int pf_clear_passing_hashes(pf_ctx* c) {
+    if (!c) return fail(PF_ERR_ARG, "pf_clear_passing_hashes: null argument");
+    if (c->kt.stream.active) return fail(PF_ERR_STATE, "pf_clear_passing_hashes while a kmers.tsv stream is open");
+    PassingRows& F = c->passing;
+    F.on = false;
+    F.digests.clear();
+    for (DevBuf* b : {&F.set, &F.ref, &F.hsh, &F.mark, &F.counters, &F.mark_cluster, &F.mark_off, &F.koff, &F.arena_of, &F.seq_cluster, &F.keep_bits, &F.tile_rows}) b->release();
+    F.marked = F.considered = F.kept = 0;
+    return PF_OK;
+}
+
+int pf_passing_batch_names(pf_ctx* c, const char* const* cluster_names, const char* extra_keys, uint64_t n_extra) {
+    if (!c || (c->n_clusters && !cluster_names) || (n_extra && !extra_keys)) return fail(PF_ERR_ARG, "pf_passing_batch_names: null argument");
+    if (!c->have_batch) return fail(PF_ERR_STATE, "pf_passing_batch_names without a successful pf_submit");
+    if (c->kt.stream.active) return fail(PF_ERR_STATE, "pf_passing_batch_names while a kmers.tsv stream is open");
+    PassingRows& F = c->passing;
+    F.name_idx.clear();
+    for (uint32_t i = 0; i < c->n_clusters; i++) {
+        if (!cluster_names[i]) return fail(PF_ERR_ARG, "pf_passing_batch_names: null name");
+        F.name_idx.emplace(cluster_names[i], i);
+    }
+    F.extra.assign(extra_keys ? extra_keys : "", (size_t)n_extra * c->o.klength);
+    F.have_names = true;
+    return PF_OK;
+}
+
+int pf_passing_stats(pf_ctx* c, uint64_t out[6]) {
+    if (!c || !out) return fail(PF_ERR_ARG, "pf_passing_stats: null argument");
+    PassingRows& F = c->passing;
+    uint64_t cnt[2] = {0, 0};
+    if (F.on && F.counters.p) {
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy(cnt, F.counters.p, 16, hipMemcpyDeviceToHost));
+    }
+    out[0] = F.digests.size() / 16; out[1] = F.marked; out[2] = F.considered; out[3] = F.kept; out[4] = cnt[1];
+    out[5] = F.device_bytes();
+    return PF_OK;
+}
+
+int pf_passing_mark_ms(pf_ctx* c, float* ms) {
+    if (!c || !ms) return fail(PF_ERR_ARG, "pf_passing_mark_ms: null argument");
+    *ms = c->passing.mark_ms;
+    return PF_OK;
+}
+
+int pf_debug_passing_hash_bits(pf_ctx* c, uint32_t bits) {
+    if (!c || bits > 64) return fail(PF_ERR_ARG, "pf_debug_passing_hash_bits: 0 .. 64 bits");
+    if (c->kt.stream.active) return fail(PF_ERR_STATE, "pf_debug_passing_hash_bits while a kmers.tsv stream is open");
+    c->passing.bits = bits;
+    if (c->passing.on) PFCHK(passing_build_set(c));
     return PF_OK;
 }
 

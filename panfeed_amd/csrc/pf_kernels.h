@@ -4982,18 +4982,162 @@ __device__ __forceinline__ bool kt_row(const KtParams& p, const KtSeq& s, uint32
 __device__ __forceinline__ uint32_t kt_row_len(const KtParams& p, const KtSeq& s, const KtRow& r) {
     return s.prefix_len + kt_dec_len(r.ts) + kt_dec_len(r.te) + kt_dec_len(r.gs) + kt_dec_len(r.ge) + kt_dec_len(r.us) + 5 + p.k + 1;
 }
-__global__ __launch_bounds__(KT_ROWS) void kt_len_kernel(KtParams p) {
+// ---------------------------------------------------------------------------------------------
+// Rows of passing patterns only (pf_set_passing_hashes): the set of passing digests, the batch's index of passing
+// (cluster, k-mer) pairs, and the row kernels' probe of it
+// ---------------------------------------------------------------------------------------------
+// The passing set: open addressing, linear probing, at most half full (pf_api.hip builds it on the host).  A slot keeps its
+// digest's hash beside the 16 bytes: a probe compares the bytes only where the hashes agree, and counts every such
+// comparison that fails.  `bits` (pf_debug_passing_hash_bits) keeps only the low bits of every hash, here and in the batch
+// index below -- 64 in the product; with few bits the chains grow long and the byte comparisons decide.
+struct PassSlot { uint64_t d0, d1, h, used; };
+__host__ __device__ inline uint64_t pass_hash_mask(uint32_t bits) { return bits >= 64 ? ~0ull : (1ull << bits) - 1ull; }
+__host__ __device__ inline uint64_t pass_mix64(uint64_t x) {
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull; x ^= x >> 27; x *= 0x94d049bb133111ebull; x ^= x >> 31;
+    return x;
+}
+__host__ __device__ inline uint64_t pass_digest_hash(uint64_t d0, uint64_t d1, uint32_t bits) {
+    return pass_mix64(d0 ^ pass_mix64(d1)) & pass_hash_mask(bits);
+}
+__device__ __forceinline__ bool pass_set_has(const PassSlot* slots, uint64_t mask, uint64_t d0, uint64_t d1, uint32_t bits,
+                                             uint32_t& unequal) {
+    const uint64_t h = pass_digest_hash(d0, d1, bits);
+    for (uint64_t i = h & mask;; i = (i + 1) & mask) {             // (a free slot ends every chain: the table is half empty)
+        const PassSlot s = slots[i];
+        if (!s.used) return false;
+        if (s.h != h) continue;
+        if (s.d0 == d0 && s.d1 == d1) return true;
+        unequal++;
+    }
+}
+// The batch index: a slot names a kept k-mer -- cluster << 32 | its place among the cluster's kept k-mers -- and keeps
+// the hash of (cluster, key words).  A probe reads the named key from the arena and compares every word.
+constexpr uint32_t PASS_MAX_KW = 4;              // k <= 126
+__device__ __forceinline__ uint64_t pass_key_hash(uint32_t cluster, const uint64_t* kw, uint32_t KW, uint32_t bits) {
+    uint64_t h = pass_mix64(cluster + 0x9e3779b97f4a7c15ull);
+#pragma unroll
+    for (uint32_t w = 0; w < PASS_MAX_KW; w++) if (w < KW) h = pass_mix64(h ^ kw[w]);
+    return h & pass_hash_mask(bits);
+}
+struct PassMarkParams {
+    const uint32_t* mark_cluster;    // [n_mark] the clusters that own a target sequence
+    const uint64_t* mark_off;        // [n_mark + 1] first mark of each: the kept k-mers of those clusters, back to back
+    uint32_t n_mark, n_patterns;
+    const uint64_t* kmer_off; const uint32_t* cluster_arena;          // [C] as KhTextParams has them
+    const uint64_t* arena_key[TEXT_MAX_ARENAS]; const uint32_t* arena_pid[TEXT_MAX_ARENAS];
+    const uint8_t* md5;              // the pattern table's digests
+    const PassSlot* set; uint64_t set_mask;
+    uint64_t* ref; uint64_t* hsh; uint64_t mask;                      // the batch index: [mask + 1], ref = EMPTY64
+    uint8_t* mark;                   // [mark_off[n_mark]] out: 1 = the k-mer's pattern passes
+    unsigned long long* counters;    // [0] k-mers marked  [1] hashes equal, bytes not (set and index probes)
+    uint32_t KW, bits;
+};
+// one thread per kept k-mer of the marked clusters: its pattern's digest looked up in the passing set, the mark written,
+// a passing fast-path key entered into the batch index.  The kept k-mers of a cluster are distinct, so an entry never
+// meets its equal: it takes the first free slot of its chain.  A slow-path key (k0 >> 63: a window with a letter other
+// than A/C/G/T) gets its mark -- the host needs it for the sequences it renders -- and no entry: no device-written row
+// can ask for it.
+__global__ __launch_bounds__(256) void pass_mark_kernel(PassMarkParams p) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= p.mark_off[p.n_mark]) return;
+    uint32_t lo = 0, hi = p.n_mark;                                   // mark_off[lo] <= g < mark_off[hi]
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (p.mark_off[mid] <= g) lo = mid; else hi = mid; }
+    const uint32_t c = p.mark_cluster[lo], r = (uint32_t)(g - p.mark_off[lo]), a = p.cluster_arena[c];
+    const uint64_t j = p.kmer_off[c] + r;
+    const uint64_t* key = p.arena_key[a] + j * p.KW;
+    const uint32_t pid = p.arena_pid[a][j];
+    uint32_t unequal = 0;
+    bool pass = false;
+    if (pid < p.n_patterns) {
+        const uint64_t* d = reinterpret_cast<const uint64_t*>(p.md5 + (size_t)pid * 16);
+        pass = pass_set_has(p.set, p.set_mask, d[0], d[1], p.bits, unequal);
+    }
+    p.mark[g] = pass ? 1 : 0;
+    if (pass) atomicAdd(&p.counters[0], 1ull);
+    if (unequal) atomicAdd(&p.counters[1], (unsigned long long)unequal);
+    if (!pass || (key[0] >> 63)) return;
+    uint64_t kw[PASS_MAX_KW] = {0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t w = 0; w < PASS_MAX_KW; w++) if (w < p.KW) kw[w] = key[w];
+    const uint64_t h = pass_key_hash(c, kw, p.KW, p.bits), val = ((uint64_t)c << 32) | r;
+    for (uint64_t i = h & p.mask;; i = (i + 1) & p.mask) {            // (the index has room for every marked k-mer twice over)
+        if (p.ref[i] != EMPTY64) continue;
+        if (atomicCAS((unsigned long long*)&p.ref[i], (unsigned long long)EMPTY64, (unsigned long long)val) == EMPTY64) { p.hsh[i] = h; break; }
+    }
+}
+// what the filtered row kernels get beside KtParams
+struct KtFilter {
+    const uint32_t* seq_cluster;     // [device-written sequences] the cluster of KtParams::seqs[i]
+    const uint64_t* ref; const uint64_t* hsh; uint64_t mask;          // the batch index
+    const uint64_t* kmer_off; const uint32_t* cluster_arena;
+    const uint64_t* arena_key[TEXT_MAX_ARENAS];
+    uint64_t* keep_bits;             // [tiles][KT_ROWS / 64] kt_len_kernel out, kt_text_kernel in: the rows kept
+    uint32_t* tile_rows;             // [tiles] kt_len_kernel out: how many
+    unsigned long long* counters;    // PassMarkParams::counters
+    uint32_t KW, bits;
+};
+// The key of the k-mer row r prints, from the packed bases and the strand it is printed from, laid out as the arena's
+// keys are (kh_text_kernel: bit b of the 2k-bit value in 63-bit word KW - 1 - b / 63 at bit b % 63), looked up in the
+// batch index under the sequence's cluster
+__device__ __forceinline__ bool kt_row_passes(const KtParams& p, const KtFilter& f, const KtSeq& s, uint32_t cluster, const KtRow& r,
+                                              uint32_t& unequal) {
+    const uint64_t* words = p.packed + p.seg_word_off[s.seg];
+    const uint32_t k = p.k, KW = f.KW;
+    uint64_t kw[PASS_MAX_KW] = {0, 0, 0, 0};
+    for (uint32_t q = 0; q < k; q++) {
+        const uint32_t i = r.rc ? r.pos + k - 1 - q : r.pos + q;
+        uint32_t code = (uint32_t)(words[i >> 5] >> (62 - 2 * (i & 31))) & 3u;
+        if (r.rc) code = 3u - code;
+        const uint32_t b0 = 2 * (k - 1 - q), b1 = b0 + 1;
+        const uint32_t i0 = KW - 1 - b0 / 63, i1 = KW - 1 - b1 / 63;
+        const uint64_t v0 = (uint64_t)(code & 1u) << (b0 % 63), v1 = (uint64_t)(code >> 1) << (b1 % 63);
+#pragma unroll
+        for (uint32_t w = 0; w < PASS_MAX_KW; w++) kw[w] |= (i0 == w ? v0 : 0ull) | (i1 == w ? v1 : 0ull);
+    }
+    const uint64_t h = pass_key_hash(cluster, kw, KW, f.bits);
+    for (uint64_t i = h & f.mask;; i = (i + 1) & f.mask) {
+        const uint64_t rf = f.ref[i];
+        if (rf == EMPTY64) return false;
+        if (f.hsh[i] != h) continue;
+        bool eq = (uint32_t)(rf >> 32) == cluster;
+        if (eq) {
+            const uint64_t* key = f.arena_key[f.cluster_arena[cluster]] + (f.kmer_off[cluster] + (uint32_t)rf) * KW;
+#pragma unroll
+            for (uint32_t w = 0; w < PASS_MAX_KW; w++) if (w < KW) eq = eq && key[w] == kw[w];
+        }
+        if (eq) return true;
+        unequal++;
+    }
+}
+
+// FILTER: a row whose (cluster, k-mer) is not in the batch index has length 0 -- kt_len decides (the tile's keep bits),
+// kt_text reads the decision; a tile may come out empty.  Without FILTER these are the kernels as they were.
+template <bool FILTER>
+__device__ __forceinline__ void kt_len(const KtParams& p, const KtFilter& f) {
     __shared__ uint32_t wsum[KT_ROWS / 64];
+    __shared__ uint32_t wrows[FILTER ? KT_ROWS / 64 : 1];
     const uint2 t = p.tiles[blockIdx.x];
     const KtSeq s = p.seqs[t.x];
     KtRow r;
-    uint32_t len = kt_row(p, s, t.y + threadIdx.x, r) ? kt_row_len(p, s, r) : 0u;
+    bool have = kt_row(p, s, t.y + threadIdx.x, r);
+    if constexpr (FILTER) {
+        uint32_t unequal = 0;
+        if (have) have = kt_row_passes(p, f, s, f.seq_cluster[t.x], r, unequal);
+        if (unequal) atomicAdd(&f.counters[1], (unsigned long long)unequal);
+        const uint64_t kept = __ballot(have);
+        if ((threadIdx.x & 63) == 0) { f.keep_bits[(size_t)blockIdx.x * (KT_ROWS / 64) + (threadIdx.x >> 6)] = kept; wrows[threadIdx.x >> 6] = (uint32_t)__popcll(kept); }
+    }
+    uint32_t len = have ? kt_row_len(p, s, r) : 0u;
     for (int d = 32; d > 0; d >>= 1) len += __shfl_down(len, d);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = len;
     __syncthreads();
-    if (threadIdx.x == 0) { uint32_t a = 0; for (uint32_t i = 0; i < KT_ROWS / 64; i++) a += wsum[i]; p.tile_bytes[blockIdx.x] = a; }
+    if (threadIdx.x == 0) {
+        uint32_t a = 0; for (uint32_t i = 0; i < KT_ROWS / 64; i++) a += wsum[i]; p.tile_bytes[blockIdx.x] = a;
+        if constexpr (FILTER) { uint32_t n = 0; for (uint32_t i = 0; i < KT_ROWS / 64; i++) n += wrows[i]; f.tile_rows[blockIdx.x] = n; }
+    }
 }
-__global__ __launch_bounds__(KT_ROWS) void kt_text_kernel(KtParams p) {
+template <bool FILTER>
+__device__ __forceinline__ void kt_text(const KtParams& p, const KtFilter& f) {
     __shared__ __align__(16) char tile[KT_TILE + 32];
     __shared__ uint32_t wsum[KT_ROWS / 64 + 1];
     const uint32_t ti = p.tile_first + blockIdx.x;
@@ -5001,7 +5145,8 @@ __global__ __launch_bounds__(KT_ROWS) void kt_text_kernel(KtParams p) {
     const KtSeq s = p.seqs[t.x];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     KtRow r;
-    const bool have = kt_row(p, s, t.y + threadIdx.x, r);
+    bool have = kt_row(p, s, t.y + threadIdx.x, r);
+    if constexpr (FILTER) have = have && ((f.keep_bits[(size_t)ti * (KT_ROWS / 64) + wave] >> lane) & 1ull);
     const uint32_t len = have ? kt_row_len(p, s, r) : 0u;
     uint32_t x = len;
     for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d); if ((int)lane >= d) x += y; }
@@ -5035,6 +5180,10 @@ __global__ __launch_bounds__(KT_ROWS) void kt_text_kernel(KtParams p) {
     __syncthreads();
     tile_store(tile, mis, p.text + gbase, min(total, KT_TILE));
 }
+__global__ __launch_bounds__(KT_ROWS) void kt_len_kernel(KtParams p) { kt_len<false>(p, KtFilter{}); }
+__global__ __launch_bounds__(KT_ROWS) void kt_text_kernel(KtParams p) { kt_text<false>(p, KtFilter{}); }
+__global__ __launch_bounds__(KT_ROWS) void kt_len_passing_kernel(KtParams p, KtFilter f) { kt_len<true>(p, f); }
+__global__ __launch_bounds__(KT_ROWS) void kt_text_passing_kernel(KtParams p, KtFilter f) { kt_text<true>(p, f); }
 
 struct HpTextParams {
     const uint32_t* order;           // [n] new pattern ids in first-seen order

@@ -5,6 +5,7 @@ ctypes, and renders the three TSV bodies exactly as the reference writes them
 One ``Engine`` = one panfeed run on one GPU: it owns the run-global pattern set
 (panfeed.py:149-150) in device memory, so clusters must be fed in processing order.
 """
+import binascii
 import collections
 import contextlib
 import ctypes as C
@@ -37,6 +38,41 @@ def _mem(ptr, n):
 def _take(ptr, n):
     """n bytes at `ptr` as `bytes` (ctypes.string_at takes a C int: texts beyond 2 GiB need this)"""
     return bytes(_mem(ptr, n))
+
+
+def passing_digests(hashes):
+    """the 16-byte digests of `hashes`, an iterable of 24-character `hashed_pattern` strings (as the files print them) or
+    of 16-byte values: a sorted list without repeats.  Anything else is a ValueError."""
+    out = set()
+    for h in hashes:
+        if isinstance(h, str) and len(h) == 24:
+            try:
+                d = binascii.a2b_base64(h)
+            except (binascii.Error, ValueError):
+                d = b""
+            if len(d) != 16 or binascii.b2a_base64(d)[:24].decode() != h:
+                raise ValueError(f"not a hashed_pattern: {h!r}")
+        elif isinstance(h, (bytes, bytearray, memoryview, np.ndarray)) and len(bytes(h)) == 16:
+            d = bytes(h)
+        else:
+            raise ValueError(f"a passing hash is 24 base64 characters or 16 bytes, not {h!r}")
+        out.add(d)
+    return sorted(out)
+
+
+def filter_passing_rows(kmers_tsv, kmers_to_hashes, passing):
+    """The host's statement of the passing-rows filter, on text alone: the rows of the kmers.tsv body `kmers_tsv` whose
+    (cluster, k-mer) stands in a k-mer row of the kmers_to_hashes body with a hash in `passing` (a set of 24-character
+    strings).  Returns (text, rows considered, rows kept)."""
+    pairs = set()
+    for line in kmers_to_hashes.split("\n"):
+        if line:
+            idx, kmer, h = line.rsplit("\t", 2)
+            if kmer and h in passing:
+                pairs.add((idx, kmer))
+    rows = kmers_tsv.split("\n")[:-1]
+    kept = [r for r in rows if (r.split("\t", 1)[0], r.rsplit("\t", 1)[1]) in pairs]
+    return "".join(r + "\n" for r in kept), len(rows), len(kept)
 
 
 # pf_batch's array fields, under the names HostBatch gives them too: Engine.submit_host_batch hands them over by host
@@ -203,7 +239,8 @@ class Engine:
     def __init__(self, klength=31, canon=True, consider_missing=False, patfilt=True, maf=0.01,
                  multiple_files=False, max_strains=1024, stroi=(), device=0, pattern_capacity=0,
                  max_items=0, dedup=True, unit_dedup=True, key_binning=True, device_plan=False,
-                 targets_text_budget=8 << 30, device_gzip=False, device_gzip_flags=0, device_gzip_clusters=False, bgzf=False):
+                 targets_text_budget=8 << 30, device_gzip=False, device_gzip_flags=0, device_gzip_clusters=False, bgzf=False,
+                 passing_hashes=None):
         self.L = _lib.load()
         # device memory a batch's kmers.tsv text may take when it is streamed to a targets_sink (stream_targets_device)
         self.targets_text_budget = int(targets_text_budget)
@@ -239,6 +276,15 @@ class Engine:
             raise ValueError("bgzf is for device_gzip without multiple_files")
         if self.device_gzip or self.device_gzip_clusters:
             _lib.check(self.L.pf_set_device_gzip(self.ctx, 1, int(device_gzip_flags) | (_lib.GZ_BGZF if self.bgzf else 0)))
+        # passing_hashes (None: off; an empty iterable: on, no row passes): kmers.tsv holds the rows of passing patterns
+        # only -- those whose (cluster, k-mer) kmers_to_hashes lists with one of these hashes
+        self.passing = None
+        if passing_hashes is not None:
+            try:
+                self.set_passing_hashes(passing_hashes)
+            except Exception:
+                self.close()
+                raise
         self.next_ordinal = 0
         self._md5_b64 = {}      # pattern id -> 24-char hash string (patterns seen so far)
         self.n_patterns = 0
@@ -253,6 +299,39 @@ class Engine:
             self.close()
         except Exception:
             pass
+
+    # ------------------------------------------------------------------ rows of passing patterns only
+    def set_passing_hashes(self, hashes):
+        """turn the passing-rows filter on (pf_set_passing_hashes) with `hashes` (see passing_digests); None: off"""
+        if hashes is None:
+            _lib.check(self.L.pf_clear_passing_hashes(self.ctx))
+            self.passing = None
+            return
+        digests = passing_digests(hashes)
+        blob = b"".join(digests)
+        _lib.check(self.L.pf_set_passing_hashes(self.ctx, blob if blob else None, len(digests)))
+        self.passing = frozenset(binascii.b2a_base64(d)[:24].decode() for d in digests)
+
+    def passing_stats(self):
+        """pf_passing_stats: (digests, kept k-mers marked, rows considered, rows kept, hash equal and bytes not, device bytes)"""
+        out = (C.c_uint64 * 6)()
+        _lib.check(self.L.pf_passing_stats(self.ctx, out))
+        return tuple(int(x) for x in out)
+
+    def _passing_names(self, hb):
+        """before a filtered kmers.tsv text of `hb`: the batch's names and slow-path rows for the library's filter"""
+        if self.passing is None:
+            return
+        names = (C.c_char_p * max(hb.n_clusters, 1))(*[s.encode() for s in hb.idx])
+        extra = "".join(hb.extra_keys).encode("latin-1") if hb.extra_keys else None
+        _lib.check(self.L.pf_passing_batch_names(self.ctx, names, extra, len(hb.extra_keys)))
+
+    def _passing_rows(self, hb):
+        """what the filtered device text of `hb` adds to the batch's counters"""
+        if self.passing is None:
+            return {}
+        st = self.passing_stats() if hb.n_targets else (0,) * 6
+        return {"kmers_rows_considered": st[2], "kmers_rows_kept": st[3], "passing_digests": len(self.passing)}
 
     # ------------------------------------------------------------------ device calls
     def submit_host_batch(self, hb):
@@ -464,6 +543,7 @@ class Engine:
         if self.multiple_files:
             out.per_cluster = list(zip(hb.idx, kt_parts, bodies.kh_parts, bodies.hp_parts))
             more["device_cluster_files"] = hb.n_clusters
+        more.update(self._passing_rows(hb))
         out.stats = _batch_stats(hb, res, self.pattern_count(), kmers_tsv_streamed=streamed, kmers_tsv_ranges=ranges,
                                  kmers_tsv_peak_device_bytes=peak, **more)
         if self.device_gzip or self.device_gzip_clusters:      # the members the GPU made of this batch, by the encoder's own count
@@ -565,7 +645,18 @@ class Engine:
             self.L.pf_free_text(buf)
         # kmers.tsv body (panfeed.py:90-107): one row per window of the target strains' sequences
         kt_by_cluster = [[] for _ in range(C_)]
-        if hb.n_targets:
+        considered = kept = 0
+        if hb.n_targets and self.passing is not None:
+            # the filter's second, independent statement: the host renderer's rows (pf_render_kmers_tsv knows no filter)
+            # against the pairs the fetched k-mers and digests put into kmers_to_hashes
+            by_cl = {}
+            for meta in hb.targets:
+                by_cl.setdefault(meta.cluster if self.multiple_files else 0, []).append(meta)
+            for ci, metas in by_cl.items():
+                text, n_rows, n_kept = filter_passing_rows(self._render_targets(hb, metas), kh_all, self.passing)
+                kt_by_cluster[ci].append(text)
+                considered, kept = considered + n_rows, kept + n_kept
+        elif hb.n_targets:
             if self.multiple_files:
                 by_cl = {}
                 for meta in hb.targets:
@@ -583,6 +674,8 @@ class Engine:
         out.hashes_to_patterns = hp_all
         out.kmers_tsv = "".join("".join(x) for x in kt_by_cluster)
         out.stats = _batch_stats(hb, res, res.n_patterns)
+        if self.passing is not None:
+            out.stats.update(kmers_rows_considered=considered, kmers_rows_kept=kept, passing_digests=len(self.passing))
         out.timing = self.timing()
         return out
 
@@ -697,6 +790,7 @@ class Engine:
         (pf_render_kmers_tsv_device): a DeviceText.  Same bytes as `_render_targets(hb, hb.targets)`."""
         t0 = time.time()
         nb = C.c_uint64()
+        self._passing_names(hb)
         with self._target_records(hb) as (arr, n):
             t1 = time.time()
             _lib.check(self.L.pf_render_kmers_tsv_device(self.ctx, arr, n, C.byref(nb)))
@@ -718,6 +812,7 @@ class Engine:
         self.stream_compressed = 0
         # (the records and the strings they point to are read until the last block: the host renders its share of
         # every range when the range is written)
+        self._passing_names(hb)
         with self._target_records(hb) as (arr, n):
             total, ranges, peak = C.c_uint64(), C.c_uint32(), C.c_uint64()
             t1 = time.time()

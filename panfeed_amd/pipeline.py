@@ -219,7 +219,10 @@ def _write_batches(run, eng, pg, stats, batch_clusters, device_text):
         # wrote; under device gzip the members the GPU made of it, by the encoder's own count
         keys = (("clusters", "instances", "kept_kmers", "device_ms", "bytes") +
                 (("device_cluster_files",) if run.multiple_files else ()) +
-                (("compressed_bytes",) if run.device_gzip or run.device_gzip_clusters else ()))
+                (("compressed_bytes",) if run.device_gzip or run.device_gzip_clusters else ()) +
+                (("kmers_rows_considered", "kmers_rows_kept") if eng.passing is not None else ()))
+        if eng.passing is not None:
+            stats.update(kmers_rows_considered=0, kmers_rows_kept=0, passing_digests=len(eng.passing))
         batches = eng.run_pangenome(pg, batch_clusters=batch_clusters, device_text=device_text,
                                     before_first_submit=run.wait_for_genomes, targets_sink=sink,
                                     cluster_targets_sink=cluster_sink)
@@ -254,7 +257,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
               patfilt=True, maf=0.01, upstream=0, downstream=0, downstream_start_codon=False, targets=(), genes=None,
               compress=False, multiple_files=False, batch_clusters=256, resident=True, device_text=True, device=0,
               max_items=0, pattern_capacity=0, overlap=True, one_pass=True, raise_missing=False, device_gzip=False,
-              targets_text_budget=None, device_gzip_clusters=False, bgzf=False):
+              targets_text_budget=None, device_gzip_clusters=False, bgzf=False, passing_hashes=None):
     """One directory of outputs (`kmers.tsv`, `kmers_to_hashes.tsv`, `hashes_to_patterns.tsv`, `.gz` under
     `compress`; under `multiple_files` one such directory per gene cluster, `<output>/<cluster>/`, the pattern set
     starting empty in each: `panfeed.py:35-43,153-167`) from a panaroo table and a directory (or file of files) of GFFs.  Option names and meaning follow
@@ -274,6 +277,10 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
     leave it as BGZF members, host text is written in BGZF members of at most 65 280 bytes, every file ends with the
     end-of-file member; htslib's readers take them, and so does the device gunzip route of the downstream tools.
     targets_text_budget: device memory a batch's kmers.tsv text may take (default: the engine's).
+    passing_hashes (`--passing-hashes` / `--passing-associations`; None: off): an iterable of `hashed_pattern` strings or
+    16-byte digests -- kmers.tsv holds only the rows whose (cluster, k-mer) kmers_to_hashes.tsv lists with one of them,
+    decided on the GPU before a dropped row is written; the other two files are not affected.  `stats` gains
+    `kmers_rows_considered`, `kmers_rows_kept` and `passing_digests`.
     Returns a dict of counters."""
     run = _FileRun(output, compress, multiple_files, device_gzip, device_gzip_clusters, bgzf)
     if run.bgzf and not run.device_gzip:
@@ -288,6 +295,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
                                     multiple_files=multiple_files, stroi=set(targets), device=device,
                                     pattern_capacity=pattern_capacity, device_gzip=run.device_gzip,
                                     device_gzip_clusters=run.device_gzip_clusters, bgzf=run.bgzf,
+                                    **({} if passing_hashes is None else {"passing_hashes": list(passing_hashes)}),
                                     **({} if targets_text_budget is None else {"targets_text_budget": targets_text_budget}))
     open_reader = functools.partial(Pangenome, presence_absence, gffdir, fastadir, upstream, downstream,
                                     downstream_start_codon, targets=targets, genes=genes, raise_missing=raise_missing)
