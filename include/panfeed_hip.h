@@ -559,6 +559,13 @@ int pf_passing_mark_ms(pf_ctx* ctx, float* ms);
  * of it, the product; 0: one chain), so that the compare-and-reject branch runs in the shipped library.  The value is a
  * kernel argument.  PF_ERR_ARG above 64, PF_ERR_STATE while a kmers.tsv stream is open. */
 int pf_debug_passing_hash_bits(pf_ctx* ctx, uint32_t bits);
+/* Test hook, read-only: slots [first, first + n) of the filter's device tables as they stand, after the stream's work
+ * (hipMemcpy).  which = 0: the passing set, four words a slot (d0, d1, h, used); 1: the batch index's ref (cluster << 32 |
+ * place, ~0 = free) and 2: its hsh, one word a slot, as the last filtered kmers.tsv text of the last pf_submit left
+ * them.  *slots (may be NULL): the table's size.  May be called after that text has been opened, a stream open or not.
+ * PF_ERR_ARG outside the table; PF_ERR_STATE with the filter off, or for 1 and 2 with no such text since the last
+ * pf_submit, pf_set_passing_hashes or pf_debug_passing_hash_bits.  The package never calls it. */
+int pf_debug_passing_tables(pf_ctx* ctx, int which, uint64_t first, uint64_t n, uint64_t* out, uint64_t* slots);
 
 /* The bodies of kmers_to_hashes.tsv and hashes_to_patterns.tsv of the last pf_submit written ON THE DEVICE
  * (panfeed.py:177,208 and :181-187,217-223): rows assembled in LDS, coalesced stores, one copy to pinned host memory.

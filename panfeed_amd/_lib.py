@@ -166,7 +166,7 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_kmers_tsv_stream_cuts", "pf_kmers_tsv_stream_block_cuts",
            "pf_gunzip_device_bgzf", "pf_gunzip_host_model_bgzf",
            "pf_set_passing_hashes", "pf_clear_passing_hashes", "pf_passing_batch_names", "pf_passing_stats",
-           "pf_passing_mark_ms", "pf_debug_passing_hash_bits"]
+           "pf_passing_mark_ms", "pf_debug_passing_hash_bits", "pf_debug_passing_tables"]
 
 RENDER_NO_PATTERN_ROWS = 1
 GZ_FIXED_ONLY, GZ_DYNAMIC_ONLY, GZ_LITERALS_ONLY = 1, 2, 4     # pf_gzip_device / pf_set_device_gzip test hooks; 0: the product
@@ -250,6 +250,7 @@ def _load_locked():
     L.pf_passing_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.pf_passing_mark_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.pf_debug_passing_hash_bits.argtypes = [C.c_void_p, C.c_uint32]
+    L.pf_debug_passing_tables.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
     L.pf_render_kmers_tsv.argtypes = [C.c_void_p, C.POINTER(TargetSeq), C.c_uint32, C.c_void_p,
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pf_pack_records.argtypes = [C.POINTER(PackIn), C.POINTER(C.c_void_p)]

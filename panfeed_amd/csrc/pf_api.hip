@@ -325,6 +325,7 @@ struct PassingRows {
     std::string extra;                        // klength bytes per slow-path row of the batch
     DevBuf ref, hsh, mark, counters, mark_cluster, mark_off, koff, arena_of, seq_cluster, keep_bits, tile_rows;
     uint64_t marked = 0, considered = 0, kept = 0;
+    uint64_t index_slots = 0;                 // ref / hsh of the last filtered text (0: none since the set or the batch changed)
     float mark_ms = 0.0f;                     // the last text's mark and index kernel (hipEvent)
     HipEvent ev0, ev1;
     uint64_t device_bytes() const {
@@ -1970,6 +1971,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
     c->have_batch = false;
     c->kt.have_seq_end = false;
     c->passing.have_names = false;
+    c->passing.index_slots = 0;
     kt_stream_end(c);                     // a kmers.tsv stream of the batch before is over,
     pr_stream_end(c);                     // and so is a stream of pattern rows
     // whatever way this call ends, nothing it queued is still reading the caller's arrays or the pinned staging
@@ -2542,6 +2544,7 @@ int kt_filter_prepare(pf_ctx* c, const std::vector<uint32_t>& all_cl, const std:
     pf::KtFilter& kf = L.kf;
     kf.seq_cluster = F.seq_cluster.as<uint32_t>();
     kf.ref = F.ref.as<uint64_t>(); kf.hsh = F.hsh.as<uint64_t>(); kf.mask = cap - 1;
+    F.index_slots = cap;
     kf.kmer_off = F.koff.as<uint64_t>(); kf.cluster_arena = F.arena_of.as<uint32_t>();
     for (size_t a = 0; a < c->n_passes; a++) kf.arena_key[a] = c->arenas[a]->key.as<uint64_t>();
     kf.keep_bits = F.keep_bits.as<uint64_t>(); kf.tile_rows = F.tile_rows.as<uint32_t>();
@@ -3011,6 +3014,7 @@ int pf_set_passing_hashes(pf_ctx* c, const uint8_t* md5, uint64_t n) {
     PFCHK(passing_build_set(c));
     F.on = true;
     F.marked = F.considered = F.kept = 0;
+    F.index_slots = 0;
     return PF_OK;
 }
 
@@ -3022,6 +3026,7 @@ int pf_clear_passing_hashes(pf_ctx* c) {
     F.digests.clear();
     for (DevBuf* b : {&F.set, &F.ref, &F.hsh, &F.mark, &F.counters, &F.mark_cluster, &F.mark_off, &F.koff, &F.arena_of, &F.seq_cluster, &F.keep_bits, &F.tile_rows}) b->release();
     F.marked = F.considered = F.kept = 0;
+    F.index_slots = 0;
     return PF_OK;
 }
 
@@ -3064,7 +3069,26 @@ int pf_debug_passing_hash_bits(pf_ctx* c, uint32_t bits) {
     if (!c || bits > 64) return fail(PF_ERR_ARG, "pf_debug_passing_hash_bits: 0 .. 64 bits");
     if (c->kt.stream.active) return fail(PF_ERR_STATE, "pf_debug_passing_hash_bits while a kmers.tsv stream is open");
     c->passing.bits = bits;
+    c->passing.index_slots = 0;
     if (c->passing.on) PFCHK(passing_build_set(c));
+    return PF_OK;
+}
+
+int pf_debug_passing_tables(pf_ctx* c, int which, uint64_t first, uint64_t n, uint64_t* out, uint64_t* slots) {
+    if (!c || (n && !out)) return fail(PF_ERR_ARG, "pf_debug_passing_tables: null argument");
+    if (which < 0 || which > 2) return fail(PF_ERR_ARG, "pf_debug_passing_tables: which must be 0 (the passing set), 1 (the index's ref) or 2 (its hsh)");
+    PassingRows& F = c->passing;
+    if (!F.on) return fail(PF_ERR_STATE, "pf_debug_passing_tables: the passing-rows filter is off");
+    if (which != 0 && (!c->have_batch || !F.index_slots))
+        return fail(PF_ERR_STATE, "pf_debug_passing_tables: no filtered kmers.tsv text since the last pf_submit, pf_set_passing_hashes or pf_debug_passing_hash_bits");
+    const uint64_t bound = which == 0 ? F.set_mask + 1 : F.index_slots, words = which == 0 ? sizeof(pf::PassSlot) / 8 : 1;
+    if (slots) *slots = bound;
+    if (first > bound || n > bound - first) return fail(PF_ERR_ARG, "pf_debug_passing_tables: slots [%llu, +%llu) outside the %llu held",
+                                                        (unsigned long long)first, (unsigned long long)n, (unsigned long long)bound);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint64_t* src = which == 0 ? F.set.as<uint64_t>() : which == 1 ? F.ref.as<uint64_t>() : F.hsh.as<uint64_t>();
+    if (n) HIPCHK(hipMemcpy(out, src + first * words, (size_t)(n * words) * 8, hipMemcpyDeviceToHost));
     return PF_OK;
 }
 
