@@ -234,43 +234,56 @@ struct RenderText {
         return PF_OK;
     }
 };
-// kmers.tsv written on the device: descriptors, tiles, and the text in ranges -- range r is written into text[r & 1]
-// while the range before it leaves through the pinned blocks.  pf_kmers_tsv_stream_begin / _next hand the ranges out in
-// order; pf_render_kmers_tsv_device writes the whole text as one range into text[0], where `bytes` of it stay for
-// pf_device_text_chunk.  Each begin ends the other's text.
-struct KtHostFilter;
-struct TargetText {
-    DevBuf seqs, tiles, prefix, tbytes, toff, text[2];
-    uint64_t bytes = 0;
+// A device text handed out in blocks (pf_kmers_tsv_stream_*, pf_pattern_rows_stream_*): the only owner of what a text in
+// flight needs.  Range r is written into text[r & 1] on `stream` while the range before it leaves through the pinned
+// blocks on `side`: as it is, or under device gzip as its members from GzMode::block_members.  One text is open at a
+// time, and `kind` says whose: its producer writes the ranges and keeps only what its text needs beyond that.
+struct TextStream {
+    enum Kind { NONE, KMERS_TSV, PATTERN_ROWS };
+    struct Range { uint64_t base, bytes; };
+    struct Producer {
+        Kind kind;
+        int (*write)(pf_ctx*, uint32_t r, char* buf, int b);   // range r into buf (text[b]), queued on `stream`
+        void (*drop)(pf_ctx*);                                 // the stream has ended: its host state goes
+    };
+    Kind kind = NONE;
+    Producer by{};
+    DevBuf text[2];
     PinBuf pins[2];
+    uint64_t kept = 0;                     // bytes of text[0] that pf_render_kmers_tsv_device left for pf_device_text_chunk
     // the one block on its way, on `side`: n bytes from `off` of the text into pins[slot] -- or, a stream's block under
     // device gzip, their members into GzMode::block_members[slot], the members' size into the slot's pinned cursor word
     struct { bool valid = false; int slot = 0; uint64_t off = 0, n = 0; } flight;
+    std::vector<Range> ranges;
+    uint32_t cur = 0;                      // the block to queue next: range cur, bytes from cur_off
+    uint64_t cur_off = 0, pin_bytes = 0;
+    HipEvent ev_prod[2];                   // on `stream`: the range in buffer b is written
+    HipEvent ev_copied[2];                 // on `side`: the range in buffer b has left the device
+    // device gzip with cuts (pf_kmers_tsv_stream_cuts): the text offsets inside the text behind which a member must
+    // end, ascending and distinct; per slot the block encoded into it -- its text, its cuts [lo, hi) and their
+    // places in its text -- and, once handed out, behind which member byte each of them lies
+    std::vector<uint64_t> cuts;
+    struct Block { uint64_t off = 0, n = 0; size_t lo = 0, hi = 0; std::vector<uint64_t> seg_end, member_end; } blk[2];
+    int handed = -1;                       // the slot of the block handed out last
+};
+// kmers.tsv written on the device: descriptors and tiles, and what the stream's kmers.tsv producer keeps while its text
+// is open.  pf_kmers_tsv_stream_begin / _next hand the ranges out in order; pf_render_kmers_tsv_device writes the whole
+// text as one range into the stream's text[0], where `kept` bytes of it stay for pf_device_text_chunk.
+struct KtHostFilter;
+struct TargetText {
+    DevBuf seqs, tiles, prefix, tbytes, toff;
     // pf_kmers_tsv_seq_ends: the offset behind every sequence's rows in the last text planned (kt_plan), kept beyond the
     // stream's end; gone with the next pf_submit
     std::vector<uint64_t> seq_end;
     bool have_seq_end = false;
-    struct Stream {
-        bool active = false;
-        std::vector<pf_target_seq> hseqs;      // the host-rendered sequences (the caller's strings, until the stream ends)
-        KtHostText host;                       // their one measurement
-        KtPlan plan;
-        pf::KtParams kp{};
-        bool filter = false;                   // the text is the filtered one: kf beside kp, hfilter for the host's share
-        pf::KtFilter kf{};
-        std::unique_ptr<KtHostFilter> hfilter;
-        uint32_t cur = 0;                      // the block to queue next: range cur, bytes from cur_off
-        uint64_t cur_off = 0, pin_bytes = 0;
-        std::unique_ptr<char[]> htext[2];      // the host's share of the range being written into each buffer
-        HipEvent ev_prod[2];                   // on `stream`: the range in buffer b is written
-        HipEvent ev_copied[2];                 // on `side`: the range in buffer b has left the device
-        // device gzip with cuts (pf_kmers_tsv_stream_cuts): the text offsets inside the text behind which a member must
-        // end, ascending and distinct; per slot the block encoded into it -- its text, its cuts [lo, hi) and their
-        // places in its text -- and, once handed out, behind which member byte each of them lies
-        std::vector<uint64_t> cuts;
-        struct Block { uint64_t off = 0, n = 0; size_t lo = 0, hi = 0; std::vector<uint64_t> seg_end, member_end; } blk[2];
-        int handed = -1;                               // the slot of the block handed out last
-    } stream;
+    std::vector<pf_target_seq> hseqs;      // the host-rendered sequences (the caller's strings, until the stream ends)
+    KtHostText host;                       // their one measurement
+    KtPlan plan;
+    pf::KtParams kp{};
+    bool filter = false;                   // the text is the filtered one: kf beside kp, hfilter for the host's share
+    pf::KtFilter kf{};
+    std::unique_ptr<KtHostFilter> hfilter;
+    std::unique_ptr<char[]> htext[2];      // the host's share of the range being written into each buffer
 };
 // gzip on the device (pf_set_device_gzip): the mode, the encoder, the members of a render and of the stream's two blocks
 // in flight (block j + 1 is encoded while block j is written out by the caller), the text sizes behind the members
@@ -286,21 +299,14 @@ struct GzMode {
     PfGzDecoder dec;
     float decode_ms = 0.0f;                   // the last pf_gunzip_device's inflate launches (hipEvent)
 };
-// hashes_to_patterns rows of a list of patterns as a stream (pf_pattern_rows_stream_begin / _next): the ids and their row
-// lengths on the device, the text cut into slices at row boundaries.  Slice i is written into TargetText::text[i & 1] and
-// leaves through TargetText::pins[i & 1] -- as it is, or as its members from GzMode::block_members[i & 1] -- all on the
-// context's stream.  These are the kmers.tsv stream's buffers and cursors: one of the two streams is open at a time.
-struct PatternRowStream {
-    bool active = false;
+// hashes_to_patterns rows of a list of patterns (pf_pattern_rows_stream_begin / _next), the stream's other producer: the
+// ids and their row lengths on the device, the text cut into slices at row boundaries.  A slice is a range of the stream
+// and one block of it.
+struct PatternRows {
     DevBuf order, rlen, rowoff[2];            // the ids, their row lengths; a slice's row offsets (from the slice's start)
     PinBuf pin_rowoff[2];
     std::vector<uint64_t> row_off;            // of the whole text, n + 1
     std::vector<uint64_t> cut;                // slice i holds rows [cut[i], cut[i + 1])
-    uint32_t queued = 0, handed = 0;          // slices queued on the stream, slices handed out
-    // on `stream`: slice i's text has arrived in pinned memory, or under device gzip is encoded and its size has arrived
-    HipEvent ev[2];
-    uint32_t n_slices() const { return cut.empty() ? 0u : (uint32_t)cut.size() - 1; }
-    uint64_t bytes(uint32_t i) const { return row_off[cut[i + 1]] - row_off[cut[i]]; }
 };
 int gz_check_flags(uint32_t flags, const char* who) {
     if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY | PF_GZ_BGZF)) return fail(PF_ERR_ARG, "%s: unknown flag", who);
@@ -370,9 +376,10 @@ struct pf_ctx {
     // {clusters, their places in the pool} that goes up with it
     struct UPool { DevBuf word_off, len, sample, ord, bits, list; PinBuf pin; };
     RenderText txt;                        // the text path: the render's state,
-    TargetText kt;                         // the target text's (kmers.tsv) with its stream,
-    GzMode gz;                             // the gzip mode,
-    PatternRowStream pr;                   // and the stream of pattern rows
+    TextStream ts;                         // the one text handed out in blocks, and its two producers:
+    TargetText kt;                         // the target text's (kmers.tsv)
+    PatternRows pr;                        // and the pattern rows';
+    GzMode gz;                             // the gzip mode
     PassingRows passing;                   // the filter of kmers.tsv rows (pf_set_passing_hashes)
     pf_batch last{};                      // the last pf_submit's batch arrays as device pointers (valid until the next submit)
     uint32_t last_nseg = 0;
@@ -434,29 +441,19 @@ struct pf_ctx {
 
 namespace {
 
-// the end of a kmers.tsv stream (its last block handed out, a new one begun, the next pf_submit, pf_destroy): nothing of
-// it is in flight afterwards, its host text is freed
-void kt_stream_end(pf_ctx* c) {
-    TargetText::Stream& S = c->kt.stream;
-    if (S.active) {
-        (void)hipStreamSynchronize(c->side);
-        (void)hipStreamSynchronize(c->stream);
-    }
-    for (auto& t : S.htext) t.reset();
-    S.active = false; c->kt.flight.valid = false;
-    S.hseqs.clear(); S.host = KtHostText{}; S.plan = KtPlan{};
-    S.cuts.clear(); S.handed = -1;
-    S.filter = false; S.hfilter.reset();
+// the end of the open stream (its last block handed out, a kmers.tsv text begun, the next pf_submit, pf_set_device_gzip,
+// pf_destroy): nothing of it is in flight afterwards, its producer's host state is freed.  `only`: a stream of that kind
+void ts_end(pf_ctx* c, TextStream::Kind only = TextStream::NONE) {
+    TextStream& S = c->ts;
+    if (S.kind == TextStream::NONE || (only != TextStream::NONE && S.kind != only)) return;
+    (void)hipStreamSynchronize(c->side);
+    (void)hipStreamSynchronize(c->stream);
+    S.by.drop(c);
+    S.kind = TextStream::NONE; S.flight.valid = false;
+    S.ranges.clear(); S.cuts.clear(); S.handed = -1;
 }
-// the end of a pattern-row stream (its last slice handed out, the next pf_submit, a kmers.tsv text begun, pf_destroy):
-// nothing of it is in flight afterwards
-void pr_stream_end(pf_ctx* c) {
-    PatternRowStream& S = c->pr;
-    if (S.active) (void)hipStreamSynchronize(c->stream);
-    S.active = false;
-    S.row_off.clear(); S.cut.clear();
-    S.queued = S.handed = 0;
-}
+// a stream being opened ends with the step that fails
+struct EndUnlessOpen { pf_ctx* c; bool ok = false; ~EndUnlessOpen() { if (!ok) ts_end(c); } };
 
 int get_event(pf_ctx* c, HipEvent* ev) {
     if (!c->ev_pool.empty()) { *ev = std::move(c->ev_pool.back()); c->ev_pool.pop_back(); return PF_OK; }
@@ -839,8 +836,7 @@ void pf_destroy(pf_ctx* c) {
     // does not matter to their owners.  (`side` by name as well: the stream ends wait for it only while a stream is open,
     // and a block of a rendered text that nobody asked for may be on its way into a pinned block without one.)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    kt_stream_end(c);
-    pr_stream_end(c);
+    ts_end(c);
     if (c->side) (void)hipStreamSynchronize(c->side);
     delete c;
 }
@@ -909,7 +905,7 @@ int pf_create(pf_ctx** out, int device, const pf_opts* o) {
 int pf_reset_patterns(pf_ctx* c) {
     if (!c) return fail(PF_ERR_ARG, "null context");
     HIPCHK(hipSetDevice(c->device));
-    pr_stream_end(c);                     // (its rows were measured in the pool that goes now)
+    ts_end(c, TextStream::PATTERN_ROWS);  // (its rows were measured in the pool that goes now)
     PFCHK(reset_patterns(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     return PF_OK;
@@ -1955,7 +1951,7 @@ struct SubmitRun {
         c->n_clusters = C; c->last = d; c->last_nseg = NSEG;
         c->last_words = gth ? gth->n_words : b->n_words;
         if (!c->n_strand_words) c->last.seg_strand_off = nullptr;
-        c->kt.bytes = 0; c->kt.flight.valid = false;
+        c->ts.kept = 0; c->ts.flight.valid = false;
         pf_result res{};
         res.n_instances = total_inst; res.n_unique = c->counters.n_unique; res.n_kept = c->counters.n_kept;   // (the last pass's cursor)
         res.n_new_patterns = pid1 - c->pid0; res.n_patterns = pid1; res.W = W; res.key_words = KW;
@@ -1972,8 +1968,7 @@ int submit_once(pf_ctx* c, const pf_batch* b, const pf_gather* gth, pf_result* c
     c->kt.have_seq_end = false;
     c->passing.have_names = false;
     c->passing.index_slots = 0;
-    kt_stream_end(c);                     // a kmers.tsv stream of the batch before is over,
-    pr_stream_end(c);                     // and so is a stream of pattern rows
+    ts_end(c);                            // a stream of the batch before, of either text, is over
     // whatever way this call ends, nothing it queued is still reading the caller's arrays or the pinned staging
     // blocks afterwards (the successful path has waited already; an error return may come with work in flight)
     struct Drain { hipStream_t s, s2; ~Drain() { (void)hipStreamSynchronize(s2); (void)hipStreamSynchronize(s); } } drain{c->stream, c->side};
@@ -2729,19 +2724,55 @@ void kt_plan(const KtLayout& L, const std::vector<uint64_t>& hsizes, uint64_t bu
 namespace {
 constexpr uint64_t KT_BLOCK = 64ull << 20;    // bytes per block a stream hands out (DeviceText.chunks' default too)
 
-// range r of the open text written into its buffer (text[r & 1]) on c->stream: its tiles by kt_text_kernel, its
-// host-rendered sequences written by the host now, from their one measurement, and copied up.  From r = 2 on the
-// buffer's range before (r - 2) must have left the device first: c->stream waits for that range's last copy on c->side.
-int kt_produce(pf_ctx* c, uint32_t r) {
-    TargetText::Stream& S = c->kt.stream;
-    const KtPlan::Range& R = S.plan.ranges[r];
+// Range r of the open stream written into its buffer (text[r & 1]) on c->stream, by the stream's producer.  From r = 2
+// on the buffer's range before (r - 2) must be done with: the host waits until that range was written, so that the
+// producer may reuse the host memory it was uploaded from, and c->stream waits for that range's last copy on c->side.
+int ts_produce(pf_ctx* c, uint32_t r) {
+    TextStream& S = c->ts;
     const int b = (int)(r & 1);
-    char* buf = c->kt.text[b].as<char>();
     if (r >= 2) {
-        HIPCHK(hipEventSynchronize(S.ev_prod[b]));          // (its host text has been copied up: free it)
-        S.htext[b].reset();
+        HIPCHK(hipEventSynchronize(S.ev_prod[b]));
         HIPCHK(hipStreamWaitEvent(c->stream, S.ev_copied[b], 0));
     }
+    PFCHK(S.by.write(c, r, S.text[b].as<char>(), b));
+    HIPCHK(hipEventRecord(S.ev_prod[b], c->stream));
+    return PF_OK;
+}
+
+// A text begun: a stream that is open ends, pf_device_text_chunk's text is gone (the buffers are reused) with the block of
+// it that nobody asked for, and the stream is `by`'s from here on.
+int ts_begin(pf_ctx* c, const TextStream::Producer& by) {
+    TextStream& S = c->ts;
+    ts_end(c);
+    if (S.flight.valid) HIPCHK(hipStreamSynchronize(c->side));
+    S.kept = 0; S.flight.valid = false;
+    S.kind = by.kind; S.by = by;
+    return PF_OK;
+}
+
+// The stream begun takes its ranges: the buffers (one range: all of it in text[0]; several: two of the largest), the
+// events, the position at the start, blocks of at most pin_bytes, and the first two ranges on their way.
+int ts_open(pf_ctx* c, std::vector<TextStream::Range> ranges, uint64_t pin_bytes) {
+    TextStream& S = c->ts;
+    S.ranges.swap(ranges);
+    const uint32_t NR = (uint32_t)S.ranges.size();
+    uint64_t max_range = 0;
+    for (const TextStream::Range& R : S.ranges) max_range = std::max(max_range, R.bytes);
+    if (NR <= 1) PFCHK(S.text[0].ensure((size_t)max_range + 64));
+    else for (DevBuf& t : S.text) PFCHK(t.ensure((size_t)max_range + 64, true));
+    for (int b = 0; b < 2; b++) { PFCHK(S.ev_prod[b].ensure(hipEventDisableTiming)); PFCHK(S.ev_copied[b].ensure(hipEventDisableTiming)); }
+    S.cur = 0; S.cur_off = 0;
+    S.pin_bytes = std::max<uint64_t>(1, pin_bytes);
+    for (uint32_t r = 0; r < std::min(NR, 2u); r++) PFCHK(ts_produce(c, r));
+    return PF_OK;
+}
+
+// The kmers.tsv producer.  Range r: its tiles by kt_text_kernel, its host-rendered sequences written by the host now, from
+// their one measurement, and copied up (the text of the buffer's range before has been: it is freed).
+int kt_write(pf_ctx* c, uint32_t r, char* buf, int b) {
+    TargetText& S = c->kt;
+    const KtPlan::Range& R = S.plan.ranges[r];
+    S.htext[b].reset();
     if (R.t1 > R.t0) {
         pf::KtParams kp = S.kp;
         kp.text = buf; kp.tile_first = R.t0; kp.text_base = R.base;
@@ -2761,24 +2792,26 @@ int kt_produce(pf_ctx* c, uint32_t r) {
             at += hsize[j];
         }
     }
-    HIPCHK(hipEventRecord(S.ev_prod[b], c->stream));
     return PF_OK;
+}
+void kt_drop(pf_ctx* c) {
+    TargetText& S = c->kt;
+    for (auto& t : S.htext) t.reset();
+    S.hseqs.clear(); S.host = KtHostText{}; S.plan = KtPlan{};
+    S.filter = false; S.hfilter.reset();
 }
 
 // What the two device texts share: the checks of their arguments and of the context's state, the layout, the host's
-// share measured, the plan within `budget`, the buffers, and the first two ranges on their way (there is only one when
-// the text fits the budget).  The stream is open afterwards; a failure leaves none.
+// share measured, the plan within `budget`, and the stream opened over the plan's ranges (there is only one when the
+// text fits the budget).  The stream is open afterwards, whatever stream was before is not; a failure leaves none.
 int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget, bool outputs_given, const char* who) {
     if (!c || !outputs_given || (n && !seqs)) return fail(PF_ERR_ARG, "null argument");
     if (!c->have_batch) return fail(PF_ERR_STATE, "%s without a successful pf_submit", who);
     HIPCHK(hipSetDevice(c->device));
-    kt_stream_end(c);
-    pr_stream_end(c);                              // (a stream of pattern rows has these buffers)
-    c->kt.bytes = 0;                               // (pf_device_text_chunk's text is gone: the buffers are reused)
     c->kt.have_seq_end = false;
-    TargetText::Stream& S = c->kt.stream;
-    S.active = true;
-    struct Guard { pf_ctx* c; bool ok; ~Guard() { if (!ok) kt_stream_end(c); } } guard{c, false};
+    EndUnlessOpen guard{c};
+    PFCHK(ts_begin(c, {TextStream::KMERS_TSV, kt_write, kt_drop}));
+    TargetText& S = c->kt;
     KtLayout L;
     PFCHK(kt_layout(c, seqs, n, L));
     S.filter = L.filter; S.kf = L.kf; S.hfilter = std::move(L.hfilter);
@@ -2800,16 +2833,13 @@ int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget, b
         return fail(PF_ERR_ARG, "kmers.tsv budget of %llu bytes is too small for this batch: its largest tile or host-rendered "
                     "sequence is %llu bytes, the smallest budget that works is %llu", (unsigned long long)budget,
                     (unsigned long long)P.max_unit, (unsigned long long)(2 * (P.max_unit + 64)));
-    // ---- the buffers, the events, the first two ranges on their way
-    const uint32_t NR = (uint32_t)P.ranges.size(), NT = (uint32_t)L.tiles.size();
-    if (NR <= 1) PFCHK(c->kt.text[0].ensure((size_t)P.total + 64));
-    else for (DevBuf& t : c->kt.text) PFCHK(t.ensure((size_t)P.max_range + 64, true));
+    // ---- the tiles' places up, and the stream over the plan's ranges
+    const uint32_t NT = (uint32_t)L.tiles.size();
     if (NT) HIPCHK(hipMemcpyAsync(c->kt.toff.p, P.toff.data(), (size_t)NT * 8, hipMemcpyHostToDevice, c->stream));
-    for (int b = 0; b < 2; b++) { PFCHK(S.ev_prod[b].ensure(hipEventDisableTiming)); PFCHK(S.ev_copied[b].ensure(hipEventDisableTiming)); }
     S.kp = L.kp;
-    S.cur = 0; S.cur_off = 0;
-    S.pin_bytes = std::max<uint64_t>(1, std::min(KT_BLOCK, P.max_range));
-    for (uint32_t r = 0; r < std::min(NR, 2u); r++) PFCHK(kt_produce(c, r));
+    std::vector<TextStream::Range> ranges;
+    for (const KtPlan::Range& R : P.ranges) ranges.push_back({R.base, R.bytes});
+    PFCHK(ts_open(c, std::move(ranges), std::min(KT_BLOCK, P.max_range)));
     c->kt.seq_end.swap(S.plan.seq_end);            // (the plan goes with the stream; the ends stay until the next submit)
     c->kt.have_seq_end = true;
     guard.ok = true;
@@ -2817,11 +2847,12 @@ int kt_open(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t budget, b
 }
 
 // n bytes at src, which start at byte `off` of the text, on their way into pinned slot `slot` (of `block` bytes) on
-// c->side: the one block in flight that pf_device_text_chunk or pf_kmers_tsv_stream_next picks up next
-int kt_prefetch(pf_ctx* c, int slot, const char* src, uint64_t off, uint64_t n, uint64_t block) {
-    PFCHK(c->kt.pins[slot].ensure(block, true));
-    if (n) HIPCHK(hipMemcpyAsync(c->kt.pins[slot].p, src, n, hipMemcpyDeviceToHost, c->side));
-    c->kt.flight = {true, slot, off, n};
+// c->side: the one block in flight that pf_device_text_chunk or a stream's next picks up next
+int ts_prefetch(pf_ctx* c, int slot, const char* src, uint64_t off, uint64_t n, uint64_t block) {
+    TextStream& S = c->ts;
+    PFCHK(S.pins[slot].ensure(block, true));
+    if (n) HIPCHK(hipMemcpyAsync(S.pins[slot].p, src, n, hipMemcpyDeviceToHost, c->side));
+    S.flight = {true, slot, off, n};
     return PF_OK;
 }
 
@@ -2829,17 +2860,17 @@ int kt_prefetch(pf_ctx* c, int slot, const char* src, uint64_t off, uint64_t n, 
 // past it.  Plain: its copy into pinned slot `slot`.  Device gzip: its encode into block_members[slot], the members'
 // size on its way into the slot's pinned cursor word.  The last block of range r also marks the range's buffer free, and
 // range r + 2 is queued into it.
-int kt_block(pf_ctx* c, int slot) {
-    TargetText::Stream& S = c->kt.stream;
+int ts_block(pf_ctx* c, int slot) {
+    TextStream& S = c->ts;
     GzMode& G = c->gz;
-    const KtPlan::Range& R = S.plan.ranges[S.cur];
+    const TextStream::Range& R = S.ranges[S.cur];
     const int b = (int)(S.cur & 1);
-    const char* src = c->kt.text[b].as<char>() + S.cur_off;
+    const char* src = S.text[b].as<char>() + S.cur_off;
     const uint64_t off = R.base + S.cur_off, n = std::min<uint64_t>(S.pin_bytes, R.bytes - S.cur_off);
     HIPCHK(hipStreamWaitEvent(c->side, S.ev_prod[b], 0));
     if (G.on) {
         // the block's segments: what lies between the cuts inside it (none: one segment, the block as a whole)
-        TargetText::Stream::Block& B = S.blk[slot];
+        TextStream::Block& B = S.blk[slot];
         B.off = off; B.n = n;
         B.lo = (size_t)(std::upper_bound(S.cuts.begin(), S.cuts.end(), off) - S.cuts.begin());
         B.hi = (size_t)(std::lower_bound(S.cuts.begin(), S.cuts.end(), off + n) - S.cuts.begin());
@@ -2848,44 +2879,74 @@ int kt_block(pf_ctx* c, int slot) {
         if (n) B.seg_end.push_back(n);
         PFCHK(G.enc.encode_segments(c->side, slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, src, n, B.seg_end.data(),
                                     B.seg_end.size(), G.flags, G.block_members[slot].as<char>(), G.block_bound));
-        c->kt.flight = {true, slot, off, n};
-    } else PFCHK(kt_prefetch(c, slot, src, off, n, S.pin_bytes));
+        S.flight = {true, slot, off, n};
+    } else PFCHK(ts_prefetch(c, slot, src, off, n, S.pin_bytes));
     S.cur_off += n;
     if (S.cur_off == R.bytes) {
         HIPCHK(hipEventRecord(S.ev_copied[b], c->side));
-        if (S.cur + 2 < S.plan.ranges.size()) PFCHK(kt_produce(c, S.cur + 2));
+        if (S.cur + 2 < S.ranges.size()) PFCHK(ts_produce(c, S.cur + 2));
         S.cur++; S.cur_off = 0;
     }
     return PF_OK;
 }
 
-// the buffers of the stream's blocks in flight under device gzip, for blocks of at most block_text bytes of text
-int kt_gz_buffers(pf_ctx* c, uint64_t block_text, uint64_t n_cuts = 0) {
+// The open stream is to be handed out: the count of its text bytes starts, and under device gzip the buffers of its two
+// blocks in flight are there, for blocks of at most pin_bytes of text with n_cuts cuts among them
+int ts_hand_out(pf_ctx* c, uint64_t n_cuts = 0) {
     GzMode& G = c->gz;
+    G.raw[2] = 0;
+    if (!G.on) return PF_OK;
     PFCHK(G.enc.ensure(c->n_cu));
-    G.block_bound = PfGzEncoder::bound_segments(std::max<uint64_t>(block_text, 1), n_cuts);     // (every cut may add a short chunk)
+    G.block_bound = PfGzEncoder::bound_segments(c->ts.pin_bytes, n_cuts);     // (every cut may add a short chunk)
     for (int s = 0; s < 2; s++) {
         PFCHK(G.block_members[s].ensure(G.block_bound, true));
-        PFCHK(c->kt.pins[s].ensure(G.block_bound, true));
+        PFCHK(c->ts.pins[s].ensure(G.block_bound, true));
     }
     PFCHK(G.ev_copy.ensure(hipEventDisableTiming));
     return PF_OK;
 }
 
 // Device gzip, a block of `text` bytes whose encode into block_members[slot] the caller has synchronised with: only the
-// members cross to the host.  *n: their size; their copy into the slot's pinned block is queued on st with ev_copy behind
-// it, for the caller to wait for once the next block is on its way.
-int gz_block_down(pf_ctx* c, int slot, uint64_t text, hipStream_t st, uint64_t* n) {
+// members cross to the host.  *n: their size; their copy into the slot's pinned block is queued on c->side with ev_copy
+// behind it, for the caller to wait for once the next block is on its way.
+int gz_block_down(pf_ctx* c, int slot, uint64_t text, uint64_t* n) {
+    TextStream& S = c->ts;
     GzMode& G = c->gz;
-    PFCHK(G.enc.member_bytes(slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, n));
-    if (c->kt.stream.active && !c->kt.stream.cuts.empty()) {      // (the kmers.tsv stream's cuts: their places came with the size)
-        TargetText::Stream::Block& B = c->kt.stream.blk[slot];
+    const PfGzEncoder::Cursor w = slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0;
+    PFCHK(G.enc.member_bytes(w, n));
+    if (!S.cuts.empty()) {                                 // (the stream's cuts: their places came with the size)
+        TextStream::Block& B = S.blk[slot];
         B.member_end.resize(B.seg_end.size());
-        if (!B.seg_end.empty()) PFCHK(G.enc.segment_ends(slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, B.member_end.data()));
+        if (!B.seg_end.empty()) PFCHK(G.enc.segment_ends(w, B.member_end.data()));
     }
     G.raw[2] += text;
-    HIPCHK(hipMemcpyAsync(c->kt.pins[slot].p, G.block_members[slot].p, *n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(G.ev_copy, st));
+    HIPCHK(hipMemcpyAsync(S.pins[slot].p, G.block_members[slot].p, *n, hipMemcpyDeviceToHost, c->side));
+    HIPCHK(hipEventRecord(G.ev_copy, c->side));
+    return PF_OK;
+}
+
+// The next block of the open stream: its text, or under device gzip its members.  While the caller holds block j, block
+// j + 1 is already queued: its copy into the other pinned slot, or its encode into the other block of members.  A step
+// that fails leaves the stream open as it stands, of either producer: whatever begins or ends a stream next ends it.
+int ts_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
+    TextStream& S = c->ts;
+    GzMode& G = c->gz;
+    HIPCHK(hipSetDevice(c->device));
+    if (!S.flight.valid) {
+        if (S.cur >= S.ranges.size()) { ts_end(c); return PF_OK; }
+        PFCHK(ts_block(c, 0));
+    }
+    HIPCHK(hipStreamSynchronize(c->side));                 // the block has arrived (gzip: is encoded, its size has arrived)
+    const int slot = S.flight.slot;
+    uint64_t n = S.flight.n;
+    // their copy goes behind the encode and before the next block's, which runs while they arrive
+    if (G.on) PFCHK(gz_block_down(c, slot, n, &n));
+    S.flight.valid = false;
+    if (S.cur < S.ranges.size()) PFCHK(ts_block(c, slot ^ 1));      // the next block on its way meanwhile
+    if (G.on) HIPCHK(hipEventSynchronize(G.ev_copy));
+    S.handed = slot;
+    *ptr = S.pins[slot].as<char>();
+    *nbytes = n;
     return PF_OK;
 }
 }  // namespace
@@ -2896,11 +2957,11 @@ int gz_block_down(pf_ctx* c, int slot, uint64_t text, hipStream_t st, uint64_t* 
 // no budget -- one range, written into text[0] -- and no stream is left open: the caller's seqs die with the call.
 int pf_render_kmers_tsv_device(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, uint64_t* nbytes) {
     PFCHK(kt_open(c, seqs, n, ~0ull, nbytes != nullptr, "pf_render_kmers_tsv_device"));
-    const uint64_t total = c->kt.stream.plan.total;
+    const uint64_t total = c->kt.plan.total;
     const hipError_t text_written = hipStreamSynchronize(c->stream);
-    kt_stream_end(c);
+    ts_end(c);
     HIPCHK(text_written);
-    c->kt.bytes = total;
+    c->ts.kept = total;
     *nbytes = total;
     return PF_OK;
 }
@@ -2914,65 +2975,39 @@ int pf_kmers_tsv_stream_begin(pf_ctx* c, const pf_target_seq* seqs, uint32_t n, 
     if (n_ranges) *n_ranges = 0;
     if (peak_text_bytes) *peak_text_bytes = 0;
     PFCHK(kt_open(c, seqs, n, budget_bytes, total_bytes && n_ranges, "pf_kmers_tsv_stream_begin"));
-    const KtPlan& P = c->kt.stream.plan;
+    const KtPlan& P = c->kt.plan;
     uint64_t peak = P.peak;
-    c->gz.raw[2] = 0;
-    if (c->gz.on) {                  // the encoder's buffers and the two blocks of members count as the text's memory
-        const int rc = kt_gz_buffers(c, std::min<uint64_t>(KT_BLOCK, P.max_range));
-        if (rc != PF_OK) { kt_stream_end(c); return rc; }
-        peak += c->gz.enc.device_bytes() + 2 * c->gz.block_bound;
-    }
+    if (const int rc = ts_hand_out(c); rc != PF_OK) { ts_end(c); return rc; }
+    // the encoder's buffers and the two blocks of members count as the text's memory
+    if (c->gz.on) peak += c->gz.enc.device_bytes() + 2 * c->gz.block_bound;
     *total_bytes = P.total;
     *n_ranges = (uint32_t)P.ranges.size();
     if (peak_text_bytes) *peak_text_bytes = peak;
     return PF_OK;
 }
 
-// The next block of the open stream: its text, or under device gzip its members.  While the caller holds block j, block
-// j + 1 is already queued: its copy into the other pinned slot, or its encode into the other block of members.
 int pf_kmers_tsv_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
     if (!c || !ptr || !nbytes) return fail(PF_ERR_ARG, "null argument");
     *ptr = nullptr; *nbytes = 0;
-    TargetText::Stream& S = c->kt.stream;
-    GzMode& G = c->gz;
-    if (!S.active) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_next without an open pf_kmers_tsv_stream_begin");
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->kt.flight.valid) {
-        if (S.cur >= S.plan.ranges.size()) { kt_stream_end(c); return PF_OK; }
-        PFCHK(kt_block(c, 0));
-    }
-    HIPCHK(hipStreamSynchronize(c->side));                 // the block has arrived (gzip: is encoded, its size has arrived)
-    const int slot = c->kt.flight.slot;
-    uint64_t n = c->kt.flight.n;
-    hipEvent_t arrival = nullptr;                          // what else the hand-out waits for, once the next block is queued
-    if (G.on) {
-        // their copy goes behind the encode and before the next block's, which runs while they arrive
-        PFCHK(gz_block_down(c, slot, n, c->side, &n));
-        arrival = G.ev_copy;
-    }
-    c->kt.flight.valid = false;
-    if (S.cur < S.plan.ranges.size()) PFCHK(kt_block(c, slot ^ 1));      // the next block on its way meanwhile
-    if (arrival) HIPCHK(hipEventSynchronize(arrival));
-    S.handed = slot;
-    *ptr = c->kt.pins[slot].as<char>();
-    *nbytes = n;
-    return PF_OK;
+    if (c->ts.kind != TextStream::KMERS_TSV) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_next without an open pf_kmers_tsv_stream_begin");
+    return ts_next(c, ptr, nbytes);
 }
 
 int pf_kmers_tsv_stream_cuts(pf_ctx* c, const uint64_t* cuts, uint64_t n) {
     if (!c || (n && !cuts)) return fail(PF_ERR_ARG, "pf_kmers_tsv_stream_cuts: null argument");
-    TargetText::Stream& S = c->kt.stream;
-    if (!S.active) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_cuts without an open pf_kmers_tsv_stream_begin");
+    TextStream& S = c->ts;
+    if (S.kind != TextStream::KMERS_TSV) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_cuts without an open pf_kmers_tsv_stream_begin");
     if (!c->gz.on) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_cuts: the stream hands out text, which is cut anywhere; the cuts are for pf_set_device_gzip");
-    if (c->kt.flight.valid || S.cur || S.cur_off || S.handed >= 0)
+    if (S.flight.valid || S.cur || S.cur_off || S.handed >= 0)
         return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_cuts: the stream's first block is on its way already");
+    const uint64_t total = c->kt.plan.total;
     std::vector<uint64_t> in;
     for (uint64_t i = 0; i < n; i++) {
-        if ((i && cuts[i] < cuts[i - 1]) || cuts[i] > S.plan.total) return fail(PF_ERR_ARG, "pf_kmers_tsv_stream_cuts: the offsets must not decrease nor pass the text's end");
-        if (cuts[i] && cuts[i] < S.plan.total && (in.empty() || in.back() != cuts[i])) in.push_back(cuts[i]);
+        if ((i && cuts[i] < cuts[i - 1]) || cuts[i] > total) return fail(PF_ERR_ARG, "pf_kmers_tsv_stream_cuts: the offsets must not decrease nor pass the text's end");
+        if (cuts[i] && cuts[i] < total && (in.empty() || in.back() != cuts[i])) in.push_back(cuts[i]);
     }
     HIPCHK(hipSetDevice(c->device));
-    PFCHK(kt_gz_buffers(c, std::min<uint64_t>(KT_BLOCK, S.plan.max_range), in.size()));
+    PFCHK(ts_hand_out(c, in.size()));
     S.cuts.swap(in);
     return PF_OK;
 }
@@ -2980,9 +3015,9 @@ int pf_kmers_tsv_stream_cuts(pf_ctx* c, const uint64_t* cuts, uint64_t n) {
 int pf_kmers_tsv_stream_block_cuts(pf_ctx* c, uint64_t* text_off, uint64_t* text_bytes, uint64_t* cut_text, uint64_t* cut_member,
                                    uint64_t cap, uint64_t* n_cuts) {
     if (!c || !text_off || !text_bytes || !n_cuts) return fail(PF_ERR_ARG, "pf_kmers_tsv_stream_block_cuts: null argument");
-    TargetText::Stream& S = c->kt.stream;
-    if (!S.active || S.handed < 0 || !c->gz.on) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_block_cuts without a block of members handed out");
-    const TargetText::Stream::Block& B = S.blk[S.handed];
+    TextStream& S = c->ts;
+    if (S.kind != TextStream::KMERS_TSV || S.handed < 0 || !c->gz.on) return fail(PF_ERR_STATE, "pf_kmers_tsv_stream_block_cuts without a block of members handed out");
+    const TextStream::Block& B = S.blk[S.handed];
     const uint64_t k = B.hi - B.lo;
     *text_off = B.off; *text_bytes = B.n; *n_cuts = k;
     if (k > cap || (k && (!cut_text || !cut_member))) return fail(PF_ERR_ARG, "pf_kmers_tsv_stream_block_cuts: %llu cuts inside the block, room for %llu", (unsigned long long)k, (unsigned long long)cap);
@@ -3003,7 +3038,7 @@ int pf_kmers_tsv_seq_ends(pf_ctx* c, uint64_t* ends, uint32_t n) {
 
 int pf_set_passing_hashes(pf_ctx* c, const uint8_t* md5, uint64_t n) {
     if (!c || (n && !md5)) return fail(PF_ERR_ARG, "pf_set_passing_hashes: null argument");
-    if (c->kt.stream.active) return fail(PF_ERR_STATE, "pf_set_passing_hashes while a kmers.tsv stream is open");
+    if (c->ts.kind == TextStream::KMERS_TSV) return fail(PF_ERR_STATE, "pf_set_passing_hashes while a kmers.tsv stream is open");
     PassingRows& F = c->passing;
     std::vector<std::array<uint8_t, 16>> d(n);
     if (n) memcpy(d.data(), md5, n * 16);
@@ -3020,7 +3055,7 @@ int pf_set_passing_hashes(pf_ctx* c, const uint8_t* md5, uint64_t n) {
 
 int pf_clear_passing_hashes(pf_ctx* c) {
     if (!c) return fail(PF_ERR_ARG, "pf_clear_passing_hashes: null argument");
-    if (c->kt.stream.active) return fail(PF_ERR_STATE, "pf_clear_passing_hashes while a kmers.tsv stream is open");
+    if (c->ts.kind == TextStream::KMERS_TSV) return fail(PF_ERR_STATE, "pf_clear_passing_hashes while a kmers.tsv stream is open");
     PassingRows& F = c->passing;
     F.on = false;
     F.digests.clear();
@@ -3033,7 +3068,7 @@ int pf_clear_passing_hashes(pf_ctx* c) {
 int pf_passing_batch_names(pf_ctx* c, const char* const* cluster_names, const char* extra_keys, uint64_t n_extra) {
     if (!c || (c->n_clusters && !cluster_names) || (n_extra && !extra_keys)) return fail(PF_ERR_ARG, "pf_passing_batch_names: null argument");
     if (!c->have_batch) return fail(PF_ERR_STATE, "pf_passing_batch_names without a successful pf_submit");
-    if (c->kt.stream.active) return fail(PF_ERR_STATE, "pf_passing_batch_names while a kmers.tsv stream is open");
+    if (c->ts.kind == TextStream::KMERS_TSV) return fail(PF_ERR_STATE, "pf_passing_batch_names while a kmers.tsv stream is open");
     PassingRows& F = c->passing;
     F.name_idx.clear();
     for (uint32_t i = 0; i < c->n_clusters; i++) {
@@ -3067,7 +3102,7 @@ int pf_passing_mark_ms(pf_ctx* c, float* ms) {
 
 int pf_debug_passing_hash_bits(pf_ctx* c, uint32_t bits) {
     if (!c || bits > 64) return fail(PF_ERR_ARG, "pf_debug_passing_hash_bits: 0 .. 64 bits");
-    if (c->kt.stream.active) return fail(PF_ERR_STATE, "pf_debug_passing_hash_bits while a kmers.tsv stream is open");
+    if (c->ts.kind == TextStream::KMERS_TSV) return fail(PF_ERR_STATE, "pf_debug_passing_hash_bits while a kmers.tsv stream is open");
     c->passing.bits = bits;
     c->passing.index_slots = 0;
     if (c->passing.on) PFCHK(passing_build_set(c));
@@ -3096,10 +3131,10 @@ int pf_debug_passing_tables(pf_ctx* c, int which, uint64_t first, uint64_t n, ui
 // remains), in pinned host memory; the block after it is already on its way when the call returns.
 int pf_device_text_chunk(pf_ctx* c, uint64_t offset, uint64_t max_bytes, const char** ptr, uint64_t* nbytes) {
     if (!c || !ptr || !nbytes || !max_bytes) return fail(PF_ERR_ARG, "null argument");
-    TargetText& T = c->kt;
-    if (offset > T.bytes) return fail(PF_ERR_ARG, "offset beyond the text");
+    TextStream& T = c->ts;
+    if (offset > T.kept) return fail(PF_ERR_ARG, "offset beyond the text");
     HIPCHK(hipSetDevice(c->device));
-    const uint64_t n = std::min<uint64_t>(max_bytes, T.bytes - offset);
+    const uint64_t n = std::min<uint64_t>(max_bytes, T.kept - offset);
     const char* text = T.text[0].as<char>();
     if (!n) {                                         // (nothing to copy, and the block in flight, if any, stays)
         PFCHK(T.pins[0].ensure(max_bytes, true));
@@ -3108,13 +3143,13 @@ int pf_device_text_chunk(pf_ctx* c, uint64_t offset, uint64_t max_bytes, const c
     }
     if (!(T.flight.valid && T.flight.off == offset && T.flight.n == n)) {
         HIPCHK(hipStreamSynchronize(c->side));        // (a block in flight that nobody asked for)
-        PFCHK(kt_prefetch(c, 0, text + offset, offset, n, max_bytes));
+        PFCHK(ts_prefetch(c, 0, text + offset, offset, n, max_bytes));
     }
     HIPCHK(hipStreamSynchronize(c->side));            // requested by the call before, or just now: wait for it
     const int slot = T.flight.slot;
     T.flight.valid = false;
     const uint64_t next = offset + n;
-    if (next < T.bytes) PFCHK(kt_prefetch(c, slot ^ 1, text + next, next, std::min<uint64_t>(max_bytes, T.bytes - next), max_bytes));
+    if (next < T.kept) PFCHK(ts_prefetch(c, slot ^ 1, text + next, next, std::min<uint64_t>(max_bytes, T.kept - next), max_bytes));
     *ptr = T.pins[slot].as<char>();
     *nbytes = n;
     return PF_OK;
@@ -3567,28 +3602,40 @@ int hp_text(pf_ctx* c, const uint32_t* order, const uint64_t* row_off, uint32_t 
 }
 }  // namespace
 
+namespace {
+// The rows of the patterns pids[0 .. n) measured (one launch, and c->stream idle afterwards): the ids checked, then up
+// in `order`, every row's length through `rlen` and down, row i's offset in their text in row_off[i], the text's size
+// in row_off[n]
+int hp_measure(pf_ctx* c, const char* who, const uint32_t* pids, uint32_t n, DevBuf& order, DevBuf& rlen, std::vector<uint64_t>& row_off) {
+    row_off.assign((size_t)n + 1, 0);
+    if (!n) return PF_OK;
+    for (uint32_t i = 0; i < n; i++)
+        if (pids[i] >= c->n_patterns) return fail(PF_ERR_ARG, "%s: pattern id %u out of range (%u patterns)", who, pids[i], c->n_patterns);
+    PFCHK(ensure_b64_dev(c));
+    PFCHK(order.ensure((size_t)n * 4));
+    PFCHK(rlen.ensure((size_t)n * 4));
+    HIPCHK(hipMemcpyAsync(order.p, pids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    PFCHK(hp_rowlen(c, order.as<uint32_t>(), 0u, n, rlen.as<uint32_t>()));
+    std::vector<uint32_t> len(n);
+    HIPCHK(hipMemcpyAsync(len.data(), rlen.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < n; i++) row_off[i + 1] = row_off[i] + len[i];
+    return PF_OK;
+}
+}  // namespace
+
 int pf_render_pattern_rows(pf_ctx* c, const uint32_t* pids, uint64_t n, const char** text, uint64_t* nbytes) {
     if (!c || !text || !nbytes || (n && !pids)) return fail(PF_ERR_ARG, "pf_render_pattern_rows: null argument");
     HIPCHK(hipSetDevice(c->device));
     *text = nullptr; *nbytes = 0;
     if (!n) return PF_OK;
     if (n > 0x7FFFFFFFull) return fail(PF_ERR_ARG, "pf_render_pattern_rows: too many rows in one call");
-    for (uint64_t i = 0; i < n; i++)
-        if (pids[i] >= c->n_patterns) return fail(PF_ERR_ARG, "pf_render_pattern_rows: pattern id %u out of range (%u patterns)", pids[i], c->n_patterns);
     hipStream_t st = c->stream;
     const uint32_t P = (uint32_t)n;
-    PFCHK(ensure_b64_dev(c));
-    PFCHK(c->txt.rp_order.ensure((size_t)P * 4));
-    PFCHK(c->txt.rp_rlen.ensure((size_t)P * 4));
-    PFCHK(c->txt.rp_rowoff.ensure(((size_t)P + 1) * 8));
-    HIPCHK(hipMemcpyAsync(c->txt.rp_order.p, pids, (size_t)P * 4, hipMemcpyHostToDevice, st));
-    PFCHK(hp_rowlen(c, c->txt.rp_order.as<uint32_t>(), 0u, P, c->txt.rp_rlen.as<uint32_t>()));
-    std::vector<uint32_t> rlen(P);
-    HIPCHK(hipMemcpyAsync(rlen.data(), c->txt.rp_rlen.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<uint64_t> row_off((size_t)P + 1, 0);
-    for (uint32_t i = 0; i < P; i++) row_off[i + 1] = row_off[i] + rlen[i];
+    std::vector<uint64_t> row_off;
+    PFCHK(hp_measure(c, "pf_render_pattern_rows", pids, P, c->txt.rp_order, c->txt.rp_rlen, row_off));
     const uint64_t total = row_off[P];
+    PFCHK(c->txt.rp_rowoff.ensure(((size_t)P + 1) * 8));
     PFCHK(c->txt.dev.ensure(total + 16));
     char* pin;
     PFCHK(c->txt.next_pin(total + 16, &pin));
@@ -3601,87 +3648,56 @@ int pf_render_pattern_rows(pf_ctx* c, const uint32_t* pids, uint64_t n, const ch
 }
 
 namespace {
-// slice i of the open pattern-row stream queued on c->stream: its row offsets up, its rows written into text[i & 1], then
-// their copy into the slot's pinned block -- or, under device gzip, their encode into the slot's block of members
-int pr_produce(pf_ctx* c, uint32_t i) {
-    PatternRowStream& S = c->pr;
-    GzMode& G = c->gz;
-    hipStream_t st = c->stream;
-    const int slot = (int)(i & 1);
-    const uint64_t r0 = S.cut[i], rows = S.cut[i + 1] - r0, bytes = S.bytes(i);
-    uint64_t* ro = S.pin_rowoff[slot].as<uint64_t>();       // (the slot's slice before, i - 2, has been handed out)
+// The pattern-row producer.  Range r is slice r: its row offsets up (the pinned block they go up from is free: the
+// buffer's slice before has been written), its rows written into the buffer by hp_text_kernel.
+int pr_write(pf_ctx* c, uint32_t r, char* buf, int b) {
+    PatternRows& S = c->pr;
+    const uint64_t r0 = S.cut[r], rows = S.cut[r + 1] - r0;
+    uint64_t* ro = S.pin_rowoff[b].as<uint64_t>();
     for (uint64_t j = 0; j <= rows; j++) ro[j] = S.row_off[r0 + j] - S.row_off[r0];
-    HIPCHK(hipMemcpyAsync(S.rowoff[slot].p, ro, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, st));
-    char* text = c->kt.text[slot].as<char>();
-    PFCHK(hp_text(c, S.order.as<uint32_t>() + r0, S.rowoff[slot].as<uint64_t>(), (uint32_t)rows, text));
-    if (G.on)
-        PFCHK(G.enc.encode(st, slot ? PfGzEncoder::STREAM_BLOCK1 : PfGzEncoder::STREAM_BLOCK0, text, bytes, G.flags,
-                           G.block_members[slot].as<char>(), G.block_bound));
-    else HIPCHK(hipMemcpyAsync(c->kt.pins[slot].p, text, (size_t)bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(S.ev[slot], st));
-    S.queued = i + 1;
-    return PF_OK;
+    HIPCHK(hipMemcpyAsync(S.rowoff[b].p, ro, (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    return hp_text(c, S.order.as<uint32_t>() + r0, S.rowoff[b].as<uint64_t>(), (uint32_t)rows, buf);
 }
+void pr_drop(pf_ctx* c) { c->pr.row_off.clear(); c->pr.cut.clear(); }
 }  // namespace
 
 int pf_pattern_rows_stream_begin(pf_ctx* c, const uint32_t* pids, uint64_t n, uint64_t slice_bytes, uint64_t* total_text_bytes,
                                  uint32_t* n_slices) {
     if (!c || !total_text_bytes || !n_slices || (n && !pids)) return fail(PF_ERR_ARG, "pf_pattern_rows_stream_begin: null argument");
     *total_text_bytes = 0; *n_slices = 0;
-    PatternRowStream& S = c->pr;
-    if (S.active || c->kt.stream.active)
+    PatternRows& S = c->pr;
+    if (c->ts.kind != TextStream::NONE)
         return fail(PF_ERR_STATE, "pf_pattern_rows_stream_begin: a stream of this context (%s) is not at its end",
-                    S.active ? "pattern rows" : "kmers.tsv");
+                    c->ts.kind == TextStream::PATTERN_ROWS ? "pattern rows" : "kmers.tsv");
     if (n > 0x7FFFFFFFull) return fail(PF_ERR_ARG, "pf_pattern_rows_stream_begin: too many rows in one stream");
-    for (uint64_t i = 0; i < n; i++)
-        if (pids[i] >= c->n_patterns) return fail(PF_ERR_ARG, "pf_pattern_rows_stream_begin: pattern id %u out of range (%u patterns)", pids[i], c->n_patterns);
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
     const uint32_t P = (uint32_t)n;
     const uint64_t cap = slice_bytes && slice_bytes < PfGzEncoder::BLOCK ? slice_bytes : PfGzEncoder::BLOCK;
-    S.active = true;
-    struct Guard { pf_ctx* c; bool ok; ~Guard() { if (!ok) pr_stream_end(c); } } guard{c, false};
-    c->gz.raw[2] = 0;
-    c->kt.bytes = 0;                               // (pf_device_text_chunk's text is gone: the buffers are reused)
-    c->kt.flight.valid = false;
-    HIPCHK(hipStreamSynchronize(c->side));         // (a block of that text that nobody asked for)
-    S.row_off.assign((size_t)P + 1, 0);
+    std::vector<uint64_t> row_off;
+    PFCHK(hp_measure(c, "pf_pattern_rows_stream_begin", pids, P, S.order, S.rlen, row_off));
+    EndUnlessOpen guard{c};
+    PFCHK(ts_begin(c, {TextStream::PATTERN_ROWS, pr_write, pr_drop}));
+    // ---- the slices: cut between rows, a slice of at most `cap` bytes or of one row; each is a range and one block
+    S.row_off.swap(row_off);
     S.cut.assign(1, 0);
+    std::vector<TextStream::Range> ranges;
     uint64_t max_bytes = 0, max_rows = 0;
-    if (P) {
-        // ---- the ids up, every row's length down: one launch
-        PFCHK(ensure_b64_dev(c));
-        PFCHK(S.order.ensure((size_t)P * 4));
-        PFCHK(S.rlen.ensure((size_t)P * 4));
-        HIPCHK(hipMemcpyAsync(S.order.p, pids, (size_t)P * 4, hipMemcpyHostToDevice, st));
-        PFCHK(hp_rowlen(c, S.order.as<uint32_t>(), 0u, P, S.rlen.as<uint32_t>()));
-        std::vector<uint32_t> rlen(P);
-        HIPCHK(hipMemcpyAsync(rlen.data(), S.rlen.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        // ---- the slices: cut between rows, a slice of at most `cap` bytes or of one row
-        uint64_t first = 0;
-        for (uint32_t i = 0; i < P; i++) {
-            if (i > first && S.row_off[i] - S.row_off[first] + rlen[i] > cap) { S.cut.push_back(i); first = i; }
-            S.row_off[i + 1] = S.row_off[i] + rlen[i];
+    for (uint32_t i = 1; i <= P; i++)
+        if (i == P || S.row_off[i + 1] - S.row_off[S.cut.back()] > cap) {
+            const uint64_t first = S.cut.back();
+            ranges.push_back({S.row_off[first], S.row_off[i] - S.row_off[first]});
+            max_bytes = std::max(max_bytes, ranges.back().bytes);
+            max_rows = std::max(max_rows, i - first);
+            S.cut.push_back(i);
         }
-        S.cut.push_back(P);
-        for (uint32_t s = 0; s < S.n_slices(); s++) {
-            max_bytes = std::max(max_bytes, S.bytes(s));
-            max_rows = std::max(max_rows, S.cut[s + 1] - S.cut[s]);
-        }
-        // ---- the buffers of two slices, the events, the first slice on its way
-        if (c->gz.on) PFCHK(kt_gz_buffers(c, max_bytes));
-        for (int b = 0; b < 2; b++) {
-            PFCHK(c->kt.text[b].ensure((size_t)max_bytes + 64, true));
-            if (!c->gz.on) PFCHK(c->kt.pins[b].ensure((size_t)max_bytes, true));
-            PFCHK(S.rowoff[b].ensure((size_t)(max_rows + 1) * 8));
-            PFCHK(S.pin_rowoff[b].ensure((size_t)(max_rows + 1) * 8));
-            PFCHK(S.ev[b].ensure(hipEventDisableTiming));
-        }
-        PFCHK(pr_produce(c, 0));
+    for (int b = 0; b < 2 && P; b++) {
+        PFCHK(S.rowoff[b].ensure((size_t)(max_rows + 1) * 8));
+        PFCHK(S.pin_rowoff[b].ensure((size_t)(max_rows + 1) * 8));
     }
+    PFCHK(ts_open(c, std::move(ranges), max_bytes));
+    PFCHK(ts_hand_out(c));
     *total_text_bytes = S.row_off[P];
-    *n_slices = S.n_slices();
+    *n_slices = (uint32_t)S.cut.size() - 1;
     guard.ok = true;
     return PF_OK;
 }
@@ -3689,27 +3705,8 @@ int pf_pattern_rows_stream_begin(pf_ctx* c, const uint32_t* pids, uint64_t n, ui
 int pf_pattern_rows_stream_next(pf_ctx* c, const char** ptr, uint64_t* nbytes) {
     if (!c || !ptr || !nbytes) return fail(PF_ERR_ARG, "pf_pattern_rows_stream_next: null argument");
     *ptr = nullptr; *nbytes = 0;
-    PatternRowStream& S = c->pr;
-    if (!S.active) return fail(PF_ERR_STATE, "pf_pattern_rows_stream_next without an open pf_pattern_rows_stream_begin");
-    HIPCHK(hipSetDevice(c->device));
-    const uint32_t i = S.handed;
-    if (i >= S.n_slices()) { pr_stream_end(c); return PF_OK; }
-    struct Guard { pf_ctx* c; bool ok; ~Guard() { if (!ok) pr_stream_end(c); } } guard{c, false};
-    const int slot = (int)(i & 1);
-    HIPCHK(hipEventSynchronize(S.ev[slot]));       // the slice has arrived (gzip: is encoded, its size has arrived)
-    uint64_t n = S.bytes(i);
-    hipEvent_t arrival = nullptr;                  // what else the hand-out waits for, once the next slice is queued
-    if (c->gz.on) {
-        PFCHK(gz_block_down(c, slot, n, c->stream, &n));
-        arrival = c->gz.ev_copy;
-    }
-    S.handed = i + 1;
-    if (S.queued < S.n_slices()) PFCHK(pr_produce(c, S.queued));      // the next slice on its way meanwhile
-    if (arrival) HIPCHK(hipEventSynchronize(arrival));
-    *ptr = c->kt.pins[slot].as<char>();
-    *nbytes = n;
-    guard.ok = true;
-    return PF_OK;
+    if (c->ts.kind != TextStream::PATTERN_ROWS) return fail(PF_ERR_STATE, "pf_pattern_rows_stream_next without an open pf_pattern_rows_stream_begin");
+    return ts_next(c, ptr, nbytes);
 }
 
 int pf_render_device(pf_ctx* c, const char* const* names, const char* extra_keys, uint64_t n_extra,
@@ -3958,8 +3955,7 @@ int pf_set_device_gzip(pf_ctx* c, int on, uint32_t flags) {
     if (!c) return fail(PF_ERR_ARG, "pf_set_device_gzip: null argument");
     PFCHK(gz_check_flags(flags, "pf_set_device_gzip"));
     HIPCHK(hipSetDevice(c->device));
-    kt_stream_end(c);                     // (an open stream would change its kind half way)
-    pr_stream_end(c);
+    ts_end(c);                            // (an open stream would change its kind half way)
     if (on) PFCHK(c->gz.enc.ensure(c->n_cu));
     c->gz.on = on != 0; c->gz.flags = flags;
     return PF_OK;

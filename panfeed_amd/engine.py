@@ -767,23 +767,34 @@ class Engine:
         total, slices = C.c_uint64(), C.c_uint32()
         _lib.check(self.L.pf_pattern_rows_stream_begin(self.ctx, pids.ctypes.data_as(C.c_void_p), len(pids),
                                                        int(slice_bytes), C.byref(total), C.byref(slices)))
+        text, handed = self._drain_stream(self.L.pf_pattern_rows_stream_next, sink, self.device_gzip, total.value,
+                                          "pattern-row stream")
+        return text, handed, int(slices.value)
+
+    def _drain_stream(self, next_block, take, gzip_on, total, what, close=None):
+        """the blocks of the device text stream just begun, from `next_block` (a *_stream_next entry point) until it
+        hands out none, each given to `take` as a memoryview of pinned memory, or under gzip_on as a GzipMembers of its
+        members (the text bytes behind them are the library's count); `close`, where given, is called after the last.
+        Returns (text bytes, bytes handed out); text bytes other than `total` are an error."""
         ptr, nb = C.c_void_p(), C.c_uint64()
         handed = 0
         while True:
-            _lib.check(self.L.pf_pattern_rows_stream_next(self.ctx, C.byref(ptr), C.byref(nb)))
+            _lib.check(next_block(self.ctx, C.byref(ptr), C.byref(nb)))
             if not nb.value:
                 break
             view = _mem(ptr, nb.value)
-            sink(GzipMembers(view, None) if self.device_gzip else view)
+            take(GzipMembers(view, None) if gzip_on else view)
             handed += int(nb.value)
         text = handed
-        if self.device_gzip:
+        if gzip_on:
             raw = (C.c_uint64 * 3)()
             _lib.check(self.L.pf_device_gzip_text_bytes(self.ctx, raw))
             text = int(raw[2])
-        if text != int(total.value):
-            raise _lib.PanfeedHipError(_lib.ERR_STATE, f"pattern-row stream: {text} bytes handed out of {total.value}")
-        return text, handed, int(slices.value)
+        if close is not None:
+            close()
+        if text != int(total):
+            raise _lib.PanfeedHipError(_lib.ERR_STATE, f"{what}: {text} bytes handed out of {total}")
+        return text, handed
 
     def render_targets_device(self, hb):
         """kmers.tsv rows of every target sequence of `hb` (the last submit), written on the device
@@ -808,7 +819,6 @@ class Engine:
         Returns (bytes, ranges, peak device text bytes)."""
         t0 = time.time()
         budget = self.targets_text_budget if budget is None else int(budget)
-        streamed = 0
         self.stream_compressed = 0
         # (the records and the strings they point to are read until the last block: the host renders its share of
         # every range when the range is written)
@@ -818,27 +828,13 @@ class Engine:
             t1 = time.time()
             _lib.check(self.L.pf_kmers_tsv_stream_begin(self.ctx, arr, n, budget, C.byref(total), C.byref(ranges),
                                                         C.byref(peak)))
-            ptr, nb = C.c_void_p(), C.c_uint64()
             gzip_on = self.device_gzip or self.device_gzip_clusters
             take, close = self._cluster_blocks(hb, sink, gzip_on) if cluster_sink else (sink, None)
-            while True:
-                _lib.check(self.L.pf_kmers_tsv_stream_next(self.ctx, C.byref(ptr), C.byref(nb)))
-                if not nb.value:
-                    break
-                if gzip_on:                     # a block's members; the text bytes behind them are asked for below
-                    take(GzipMembers(_mem(ptr, nb.value), None))
-                    self.stream_compressed += int(nb.value)
-                else:
-                    take(_mem(ptr, nb.value))
-                    streamed += int(nb.value)
-            if gzip_on:
-                raw = (C.c_uint64 * 3)()
-                _lib.check(self.L.pf_device_gzip_text_bytes(self.ctx, raw))
-                streamed = int(raw[2])
-            if close is not None:
-                close()
-        if streamed != int(total.value):
-            raise _lib.PanfeedHipError(_lib.ERR_STATE, f"kmers.tsv stream: {streamed} bytes handed out of {total.value}")
+
+            def counted(block):
+                take(block)
+                self.stream_compressed += len(block) if gzip_on else 0
+            streamed, _ = self._drain_stream(self.L.pf_kmers_tsv_stream_next, counted, gzip_on, total.value, "kmers.tsv stream", close)
         self.render_targets_timing = {"marshal_s": t1 - t0, "render_s": time.time() - t1, "copy_s": 0.0}
         return streamed, int(ranges.value), int(peak.value)
 
