@@ -697,6 +697,24 @@ int pf_gunzip_host_model(const char* members, uint64_t n, char** out, uint64_t* 
  */
 int pf_gunzip_device_bgzf(pf_ctx* ctx, const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken);
 int pf_gunzip_host_model_bgzf(const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken);
+/*
+ * LARGE gzip members on the device, parallel inside a member: what gzip, pigz and Python's gzip.open write (one member a
+ * file, any RFC 1952 head: FEXTRA, FNAME, FCOMMENT, FHCRC are skipped) and the 4 MiB zlib members of pf_gzip_members.  The
+ * member's payload is cut every piece_bytes (0: 32 KiB; else at least 64); from every cut on, a wave looks for the next
+ * dynamic block's header by trial; every found start is decoded once without the text before it (back-references into it
+ * stay markers), the windows are chained in order, and every live piece is decoded again as bytes to its place, its CRC32
+ * taken; CRC32 and ISIZE are checked against the member's tail.  Not taken: a reserved FLG bit or CM != 8, a damaged or
+ * truncated member, a piece of more than 256 MiB of text or of more than 1 536 * piece_bytes compressed bytes (a member
+ * of fixed or stored blocks only is one piece).  Every member of the buffer goes this route, one after the other.
+ * pieces (may be NULL): [0] starts found, [1] live pieces, [2] starts dropped (false or redundant), [3] members taken.
+ * Results and refusals as for pf_gunzip_device; pf_gunzip_device_last_ms: the four passes' device time.  Device memory:
+ * under 1 536 * piece_bytes + 2 048 * 96 KiB and the text of a call, 256 MiB at most.
+ * pf_gunzip_host_model_large: the same find, marker, chain and byte steps run serially on the host: no context, no GPU.
+ */
+int pf_gunzip_device_large(pf_ctx* ctx, const char* members, uint64_t n, uint32_t piece_bytes, char** out, uint64_t* out_n, int* taken,
+                           uint64_t* pieces);
+int pf_gunzip_host_model_large(const char* members, uint64_t n, uint32_t piece_bytes, char** out, uint64_t* out_n, int* taken,
+                               uint64_t* pieces);
 /* Off by default.  While on, pf_render_device[_ex] hands out gzip members in place of text (*kh, *kh_bytes, *hp,
  * *hp_bytes describe the compressed bytes) and so does pf_kmers_tsv_stream_next: every block of a range is encoded as it
  * is produced and its compressed size read back before it is copied (the host-rendered sequences are in the device text
@@ -747,6 +765,20 @@ int pf_rowfilter_scan_members(pf_rowfilter* f, const char* members, uint64_t nby
                               uint64_t* lines_bytes, uint64_t* n_lines, uint64_t* consumed, int* taken);
 /* Members and text bytes inflated by this filter, its inflate kernels' ms, the decoder's device bytes (any may be NULL). */
 int pf_rowfilter_gunzip_stats(pf_rowfilter* f, uint64_t* members, uint64_t* text_bytes, float* inflate_ms, uint64_t* device_bytes);
+/*
+ * The large-member route (see pf_gunzip_device_large) behind pf_rowfilter_scan_members, off by default: while on, a
+ * block the small-member kernels do not take -- any other RFC 1952 head, a member over their size limits -- is tried as
+ * a large member from its first byte on; the members that follow it under the same first eight bytes are decoded beside
+ * it in the same call, up to the next one the small-member kernels take.  A member may span calls: a call with last = 0 takes the
+ * pieces whose end it can confirm and reports *consumed up to the byte that holds the next block; one that can confirm
+ * nothing yet consumes nothing and is taken (the caller reads on).  With last = 1 the member must end at its tail.
+ * piece_bytes: 0 for the default of 32 KiB of compressed bytes, else at least 64.  Setting it forgets an open member;
+ * so does pf_rowfilter_members_begin.  pf_rowfilter_large_stats: pieces[4] as pf_gunzip_device_large's, ms[4] the device
+ * time of the find, marker, chain and byte passes (either may be NULL).  The other owners of the feed have the same two
+ * calls: pf_kmerjoin_*, pf_assocfilter_*, pf_plotgrid_*.
+ */
+int pf_rowfilter_set_large_members(pf_rowfilter* f, int on, uint32_t piece_bytes);
+int pf_rowfilter_large_stats(pf_rowfilter* f, uint64_t* pieces, float* ms);
 void pf_rowfilter_destroy(pf_rowfilter* f);
 
 /*
@@ -796,6 +828,8 @@ int pf_kmerjoin_create(int device, const char* const* clusters, const uint32_t* 
                        uint32_t empty_len, pf_kmerjoin** out);
 int pf_kmerjoin_survey(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint64_t* consumed);
 int pf_kmerjoin_members_begin(pf_kmerjoin* j, int header);
+int pf_kmerjoin_set_large_members(pf_kmerjoin* j, int on, uint32_t piece_bytes);
+int pf_kmerjoin_large_stats(pf_kmerjoin* j, uint64_t* pieces, float* ms);
 int pf_kmerjoin_members_header(pf_kmerjoin* j, const char** line, uint64_t* nbytes);
 int pf_kmerjoin_survey_members(pf_kmerjoin* j, const char* members, uint64_t nbytes, int last, uint64_t* consumed, int* taken);
 int pf_kmerjoin_reset_counters(pf_kmerjoin* j);
@@ -847,6 +881,8 @@ typedef struct pf_assocfilter pf_assocfilter;
 int pf_assocfilter_create(int device, uint32_t pvalue_field, uint32_t n_fields, double thr_hi, pf_assocfilter** out);
 int pf_assocfilter_scan(pf_assocfilter* f, const char* text, uint64_t nbytes, uint64_t* out_bytes, uint64_t* consumed);
 int pf_assocfilter_members_begin(pf_assocfilter* f, int header);
+int pf_assocfilter_set_large_members(pf_assocfilter* f, int on, uint32_t piece_bytes);
+int pf_assocfilter_large_stats(pf_assocfilter* f, uint64_t* pieces, float* ms);
 int pf_assocfilter_members_header(pf_assocfilter* f, const char** line, uint64_t* nbytes);
 int pf_assocfilter_scan_members(pf_assocfilter* f, const char* members, uint64_t nbytes, int last, uint64_t* out_bytes,
                                 uint64_t* consumed, int* taken);
@@ -886,6 +922,8 @@ int pf_plotgrid_create(int device, const char* const* strains, const uint32_t* s
                        const int32_t* columns, int zoom, int64_t start, int64_t stop, pf_plotgrid** out);
 int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t* consumed);
 int pf_plotgrid_members_begin(pf_plotgrid* g, int header);
+int pf_plotgrid_set_large_members(pf_plotgrid* g, int on, uint32_t piece_bytes);
+int pf_plotgrid_large_stats(pf_plotgrid* g, uint64_t* pieces, float* ms);
 int pf_plotgrid_members_header(pf_plotgrid* g, const char** line, uint64_t* nbytes);
 int pf_plotgrid_scan_members(pf_plotgrid* g, const char* members, uint64_t nbytes, int last, uint64_t* consumed, int* taken);
 int pf_plotgrid_gunzip_stats(pf_plotgrid* g, uint64_t* members, uint64_t* text_bytes, float* inflate_ms, uint64_t* device_bytes);

@@ -165,6 +165,9 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
            "pf_gzip_device_segments", "pf_gzip_host_model_segments", "pf_render_device_cluster_members",
            "pf_kmers_tsv_stream_cuts", "pf_kmers_tsv_stream_block_cuts",
            "pf_gunzip_device_bgzf", "pf_gunzip_host_model_bgzf",
+           "pf_gunzip_device_large", "pf_gunzip_host_model_large",
+           "pf_rowfilter_set_large_members", "pf_rowfilter_large_stats", "pf_kmerjoin_set_large_members", "pf_kmerjoin_large_stats",
+           "pf_assocfilter_set_large_members", "pf_assocfilter_large_stats", "pf_plotgrid_set_large_members", "pf_plotgrid_large_stats",
            "pf_set_passing_hashes", "pf_clear_passing_hashes", "pf_passing_batch_names", "pf_passing_stats",
            "pf_passing_mark_ms", "pf_debug_passing_hash_bits", "pf_debug_passing_tables"]
 
@@ -341,6 +344,12 @@ def _load_locked():
     L.pf_gunzip_host_model.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     L.pf_gunzip_device_bgzf.argtypes = L.pf_gunzip_device.argtypes
     L.pf_gunzip_host_model_bgzf.argtypes = L.pf_gunzip_host_model.argtypes
+    L.pf_gunzip_device_large.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+    L.pf_gunzip_host_model_large.argtypes = L.pf_gunzip_device_large.argtypes[1:]
+    for owner in ("rowfilter", "kmerjoin", "assocfilter", "plotgrid"):
+        getattr(L, f"pf_{owner}_set_large_members").argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+        getattr(L, f"pf_{owner}_large_stats").argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
     L.pf_rowfilter_members_begin.argtypes = [C.c_void_p, C.c_int]
     L.pf_rowfilter_members_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pf_rowfilter_scan_members.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),

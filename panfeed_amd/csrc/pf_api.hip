@@ -298,6 +298,7 @@ struct GzMode {
     float encode_ms = 0.0f;                   // the last pf_gzip_device's encode, scan and gather launches (hipEvent)
     PfGzDecoder dec;
     float decode_ms = 0.0f;                   // the last pf_gunzip_device's inflate launches (hipEvent)
+    PfGzLarge large;                          // pf_gunzip_device_large's passes
 };
 // hashes_to_patterns rows of a list of patterns (pf_pattern_rows_stream_begin / _next), the stream's other producer: the
 // ids and their row lengths on the device, the text cut into slices at row boundaries.  A slice is a range of the stream
@@ -4115,6 +4116,49 @@ int pf_gunzip_device(pf_ctx* c, const char* members, uint64_t n, char** out, uin
 
 int pf_gunzip_device_bgzf(pf_ctx* c, const char* members, uint64_t n, char** out, uint64_t* out_n, int* taken) {
     return gunzip_device(c, members, n, out, out_n, taken, true, "pf_gunzip_device_bgzf");
+}
+
+// The whole buffer by the large-member route, every member alone, call after call as a text feed gives them (last = 1:
+// all the bytes are there), the text of each call copied out behind it
+int pf_gunzip_device_large(pf_ctx* c, const char* members, uint64_t n, uint32_t piece_bytes, char** out, uint64_t* out_n, int* taken,
+                           uint64_t* pieces) {
+    if (!c || (!members && n) || !out || !out_n || !taken) return fail(PF_ERR_ARG, "pf_gunzip_device_large: null argument");
+    *out = nullptr; *out_n = 0; *taken = 0;
+    if (piece_bytes && piece_bytes < pfgz::PIECE_MIN) return fail(PF_ERR_ARG, "pf_gunzip_device_large: piece_bytes is 0 or at least %u", pfgz::PIECE_MIN);
+    HIPCHK(hipSetDevice(c->device));
+    PfGzLarge& be = c->gz.large;
+    be.st = c->stream;
+    DevBuf text;
+    be.place = [&](uint64_t text_n, uint8_t** dst) -> int { PFCHK(text.ensure(text_n + 16)); *dst = text.as<uint8_t>(); return PF_OK; };
+    std::vector<char> all;
+    pfgz::LargeState s;
+    pfgz::LargeStats stats;
+    const float before = be.ms[0] + be.ms[1] + be.ms[2] + be.ms[3];
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(members);
+    uint32_t status = pfgz::INF_OK;
+    bool ok = true;
+    for (uint64_t at = 0; at < n && ok;) {
+        pfgz::LargeOut o;
+        PFCHK(pfgz::large_call(be, s, stats, bytes + at, n - at, true, piece_bytes, o));
+        if (!o.taken || !o.consumed) { ok = false; status = o.status ? o.status : (uint32_t)pfgz::INF_NOT_DECODED; break; }
+        const size_t had = all.size();
+        all.resize(had + o.text_n);
+        if (o.text_n) HIPCHK(hipMemcpy(all.data() + had, text.p, o.text_n, hipMemcpyDeviceToHost));
+        at += o.consumed;
+    }
+    if (ok && s.open) { ok = false; status = pfgz::INF_TRUNCATED; }
+    be.place = nullptr;
+    c->gz.decode_ms = be.ms[0] + be.ms[1] + be.ms[2] + be.ms[3] - before;
+    if (pieces) { pieces[0] = stats.found; pieces[1] = stats.live; pieces[2] = stats.dropped; pieces[3] = stats.members; }
+    if (!ok) {
+        (void)fail(PF_OK, "pf_gunzip_device_large: not taken: member %llu: %s", (unsigned long long)stats.members, pfgz::inf_status_name(status));
+        return PF_OK;
+    }
+    char* buf = (char*)malloc(all.size() ? all.size() : 1);
+    if (!buf) return fail(PF_ERR_OOM, "pf_gunzip_device_large: out of memory");
+    if (!all.empty()) memcpy(buf, all.data(), all.size());
+    *out = buf; *out_n = all.size(); *taken = 1;
+    return PF_OK;
 }
 
 #ifdef PF_PROF

@@ -30,13 +30,16 @@
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define PF_HD __host__ __device__ inline
+#define PF_HD_M __host__ __device__
 #else
 #define PF_HD inline
+#define PF_HD_M
 #endif
 
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <vector>
 
 namespace pfgz {
@@ -598,20 +601,33 @@ PF_HD uint32_t dynamic_tables(BitReader& r, DecodeTables& T, bool leader) {
     return a ? a : build_decode(T.lens, hlit, T.ll_count, T.ll_sym, true);
 }
 
-// The blocks of one member's payload, p[0 .. n), into a sink that holds at most `isize` bytes.  Out has
+// The blocks of a deflate stream from the reader's place on, into a sink.  Out has
 //   bool leader()                      whether this caller writes the shared tables (the device: one lane of the wave)
 //   void sync()                        after the leader's writes, before anyone reads them
 //   uint32_t share(v)                  the leader's v
 //   void literal(o, byte)              text[o] = byte
 //   void copy(o, dist, len)            text[o + i] = text[o - dist + i], i = 0 .. len - 1, as if byte by byte
 //   void stored(o, src, len)           text[o + i] = src[i]
-// *produced: the bytes given.  INF_OK: the final block ended with exactly isize bytes given and exactly at p + n.
-template <class Out>
-PF_HD uint32_t inflate_blocks(const uint8_t* p, uint32_t n, uint32_t isize, DecodeTables& T, Out& out, uint32_t* produced) {
-    BitReader r = bit_reader(p, n);
+// and Stop has  bool at(uint64_t bit): asked behind every block that is not the final one, with the bit the next block
+// starts at; true ends the run there.  `hist`: the bytes of text that stand before o = 0 (a match may reach that far back);
+// `cap`: the most bytes the run may give.  *produced: the bytes given.  INF_OK: the run ended behind a block, *why says
+// which way (RUN_AT_STOP / RUN_FINAL) and the reader stands behind that block's last bit.
+enum RunEnd : uint32_t { RUN_NONE = 0, RUN_AT_STOP, RUN_FINAL };
+struct NoStop { PF_HD_M bool at(uint64_t) { return false; } };
+PF_HD uint64_t bit_pos(const BitReader& r) { return (uint64_t)r.pos * 8 - r.cnt; }     // of the next bit to take
+// a reader of p[0 .. n) that stands at bit `bit` (< 8 n)
+PF_HD BitReader bit_reader_at(const uint8_t* p, uint32_t n, uint64_t bit) {
+    BitReader r{p, n, (uint32_t)(bit >> 3), 0, 0, false};
+    (void)take_bits(r, (uint32_t)(bit & 7));
+    return r;
+}
+template <class Out, class Stop>
+PF_HD uint32_t inflate_run(BitReader& r, uint32_t hist, uint32_t cap, DecodeTables& T, Out& out, Stop& stop, uint32_t* produced, uint32_t* why) {
+    const uint8_t* const p = r.p;
+    const uint32_t n = r.n;
     uint32_t o = 0, bfinal = 0;
-    *produced = 0;
-    do {
+    *produced = 0; *why = RUN_NONE;
+    for (;;) {
         bfinal = take_bits(r, 1);
         const uint32_t btype = take_bits(r, 2);
         if (r.over) return INF_TRUNCATED;
@@ -623,44 +639,57 @@ PF_HD uint32_t inflate_blocks(const uint8_t* p, uint32_t n, uint32_t isize, Deco
             if (len != (~nlen & 0xFFFFu)) return INF_BAD_STORED;
             const uint32_t at = byte_pos(r);
             if (len > n - at) return INF_TRUNCATED;
-            if (len > isize - o) return INF_TOO_MUCH_TEXT;
+            if (len > cap - o) return INF_TOO_MUCH_TEXT;
             out.stored(o, p + at, len);
             o += len; *produced = o;
             r.pos = at + len; r.buf = 0; r.cnt = 0;
-            continue;
-        }
-        uint32_t st = INF_OK;
-        if (btype == 1) { if (out.leader()) st = fixed_tables(T); }
-        else st = dynamic_tables(r, T, out.leader());
-        out.sync();
-        st = out.share(st);                    // (every caller asks: the leader's lane must be there to answer)
-        if (st) return st;
-        const CodeCounts kl = load_counts(T.ll_count), kd = load_counts(T.d_count);
-        for (;;) {
-            const int32_t s = decode_sym(r, kl, T.ll_sym);
-            if (s < 0) return r.over ? INF_TRUNCATED : INF_BAD_CODE;
-            if (s < 256) {
-                if (o >= isize) return INF_TOO_MUCH_TEXT;
-                out.literal(o, (uint8_t)s);
-                o++; *produced = o;
-                continue;
+        } else {
+            uint32_t st = INF_OK;
+            if (btype == 1) { if (out.leader()) st = fixed_tables(T); }
+            else st = dynamic_tables(r, T, out.leader());
+            out.sync();
+            st = out.share(st);                    // (every caller asks: the leader's lane must be there to answer)
+            if (st) return st;
+            const CodeCounts kl = load_counts(T.ll_count), kd = load_counts(T.d_count);
+            for (;;) {
+                const int32_t s = decode_sym(r, kl, T.ll_sym);
+                if (s < 0) return r.over ? INF_TRUNCATED : INF_BAD_CODE;
+                if (s < 256) {
+                    if (o >= cap) return INF_TOO_MUCH_TEXT;
+                    out.literal(o, (uint8_t)s);
+                    o++; *produced = o;
+                    continue;
+                }
+                if (s == 256) break;
+                if (s >= (int32_t)N_LL) return INF_BAD_SYMBOL;
+                const uint32_t len = len_base((uint32_t)s) + take_bits(r, len_sym_extra((uint32_t)s));
+                const int32_t ds = decode_sym(r, kd, T.d_sym);
+                if (ds < 0) return r.over ? INF_TRUNCATED : INF_BAD_CODE;
+                if (ds >= (int32_t)N_D) return INF_BAD_SYMBOL;
+                const uint32_t dist = dist_base((uint32_t)ds) + take_bits(r, dist_sym_extra((uint32_t)ds));
+                if (r.over) return INF_TRUNCATED;
+                if (dist > o && dist - o > hist) return INF_BAD_DISTANCE;
+                if (len > cap - o) return INF_TOO_MUCH_TEXT;
+                out.copy(o, dist, len);
+                o += len; *produced = o;
             }
-            if (s == 256) break;
-            if (s >= (int32_t)N_LL) return INF_BAD_SYMBOL;
-            const uint32_t len = len_base((uint32_t)s) + take_bits(r, len_sym_extra((uint32_t)s));
-            const int32_t ds = decode_sym(r, kd, T.d_sym);
-            if (ds < 0) return r.over ? INF_TRUNCATED : INF_BAD_CODE;
-            if (ds >= (int32_t)N_D) return INF_BAD_SYMBOL;
-            const uint32_t dist = dist_base((uint32_t)ds) + take_bits(r, dist_sym_extra((uint32_t)ds));
-            if (r.over) return INF_TRUNCATED;
-            if (dist > o) return INF_BAD_DISTANCE;
-            if (len > isize - o) return INF_TOO_MUCH_TEXT;
-            out.copy(o, dist, len);
-            o += len; *produced = o;
+            out.sync();                    // (the next block's tables take this one's place)
         }
-        out.sync();                    // (the next block's tables take this one's place)
-    } while (!bfinal);
-    if (o != isize) return INF_TOO_LITTLE_TEXT;
+        if (bfinal) { *why = RUN_FINAL; return INF_OK; }
+        if (stop.at(bit_pos(r))) { *why = RUN_AT_STOP; return INF_OK; }
+    }
+}
+
+// The blocks of one member's payload, p[0 .. n), into a sink that holds at most `isize` bytes: the run from the payload's
+// first bit to its final block.  INF_OK: that block ended with exactly isize bytes given and exactly at p + n.
+template <class Out>
+PF_HD uint32_t inflate_blocks(const uint8_t* p, uint32_t n, uint32_t isize, DecodeTables& T, Out& out, uint32_t* produced) {
+    BitReader r = bit_reader(p, n);
+    NoStop never;
+    uint32_t why = RUN_NONE;
+    const uint32_t st = inflate_run(r, 0, isize, T, out, never, produced, &why);
+    if (st) return st;
+    if (*produced != isize) return INF_TOO_LITTLE_TEXT;
     return byte_pos(r) == n ? INF_OK : INF_NOT_AT_TAIL;
 }
 
@@ -799,6 +828,344 @@ inline bool host_inflate_model_bgzf(const uint8_t* p, uint64_t n, std::vector<ui
     return host_inflate_listed(p, ms, text, first_bad, status);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Large members: a decoder that is parallel inside a member, for the files other writers make (one whole-file member
+// from gzip / pigz / Python's gzip.open, 4 MiB zlib members).  A deflate stream can be entered at a block boundary without
+// what stands before it, and a dynamic block's header is signature enough to find boundaries by trial:
+//   find    the payload is cut every piece_bytes; from each cut on, bit offsets are tried until one holds BTYPE = 2 and a
+//           header dynamic_tables() takes whole (block_start_ok) -- a found start -- or the next cut comes.  The payload's
+//           first bit is a start.  Stored and fixed blocks are not looked for: they are decoded inside the piece they
+//           fall in.
+//   marker  every found start is decoded without the text before it, into a window of WINDOW 16-bit entries: a byte, or
+//           MARK | j, "byte j of the unknown WINDOW bytes before this piece".  The run ends where a block ends exactly at
+//           a later found start, behind the final block, with the data, or at PIECE_TEXT_CAP bytes of text.
+//   chain   piece 0 is live; the next live piece is the start the live one ended at; found starts a live piece steps
+//           over are dropped (false, or redundant).  In that order each live piece's last window becomes bytes by looking
+//           its markers up in the window before it.
+//   bytes   every live piece is decoded again, as bytes, with the window before it preset, to its place in the text, and
+//           its CRC32 taken; the host combines the CRCs and checks them and the length against the member's tail.
+// large_call() below is that sequence for one call, written once for the serial host backend (HostLarge: the host model)
+// and the device's (PfGzLarge, pf_deflate.hip).  A member may span calls: LargeState carries it.
+constexpr uint32_t WINDOW = 32768, WMASK = WINDOW - 1, MARK = 0x8000;
+constexpr uint32_t PIECE_DEFAULT = 32768, PIECE_MIN = 64;
+constexpr uint32_t PIECE_TEXT_CAP = 256u << 20;       // a piece of more text (a member without a findable block start in it
+                                                      // for that long) is INF_TOO_LARGE: the member is not taken
+constexpr uint32_t MAX_PIECES = 2048;                 // starts of a call: every one has a ring with the backend
+constexpr uint32_t MAX_CUTS = MAX_PIECES / 4 * 3;     // cuts of a call, which reads MAX_CUTS * piece_bytes at most; the other
+                                                      // quarter of the starts is room for the payloads of members side by side
+constexpr uint64_t LARGE_MAX_TEXT = 256ull << 20;     // text taken per call (PfGzDecoder::MAX_TEXT)
+
+// The RFC 1952 head at p[0 .. n): INF_OK and *head = its bytes; INF_TRUNCATED: it runs past n; INF_BAD_HEAD: not
+// ID1 ID2 CM = 8, or a reserved FLG bit.  FEXTRA, FNAME, FCOMMENT and FHCRC are skipped.
+inline uint32_t parse_head(const uint8_t* p, uint64_t n, uint64_t* head) {
+    *head = 0;
+    if (n >= 1 && p[0] != 0x1F) return INF_BAD_HEAD;
+    if (n >= 2 && p[1] != 0x8B) return INF_BAD_HEAD;
+    if (n >= 3 && p[2] != 8) return INF_BAD_HEAD;
+    if (n >= 4 && (p[3] & 0xE0)) return INF_BAD_HEAD;
+    if (n < MEMBER_HEAD) return INF_TRUNCATED;
+    const uint32_t flg = p[3];
+    uint64_t at = MEMBER_HEAD;
+    if (flg & 4) {                                   // FEXTRA
+        if (at + 2 > n) return INF_TRUNCATED;
+        at += 2 + (p[at] | (uint64_t)p[at + 1] << 8);
+        if (at > n) return INF_TRUNCATED;
+    }
+    for (uint32_t bit : {8u, 16u}) {                 // FNAME, FCOMMENT: to their zero byte
+        if (!(flg & bit)) continue;
+        const void* z = at < n ? memchr(p + at, 0, (size_t)(n - at)) : nullptr;
+        if (!z) return INF_TRUNCATED;
+        at = (uint64_t)(static_cast<const uint8_t*>(z) - p) + 1;
+    }
+    if (flg & 2) at += 2;                            // FHCRC
+    if (at > n) return INF_TRUNCATED;
+    *head = at;
+    return INF_OK;
+}
+
+// whether a dynamic block may start at bit `bit` of p[0 .. n): BTYPE = 2 (either BFINAL) and a header that passes
+// everything dynamic_tables checks.  T is the caller's scratch.  Reads no byte outside p[0 .. n), ends for any input.
+PF_HD bool block_start_ok(const uint8_t* p, uint32_t n, uint64_t bit, DecodeTables& T) {
+    if ((bit >> 3) >= n) return false;
+    BitReader r = bit_reader_at(p, n, bit);
+    const uint32_t head = take_bits(r, 3);
+    if (r.over || (head >> 1) != 2) return false;
+    return dynamic_tables(r, T, true) == INF_OK;
+}
+
+// what the marker pass leaves of a piece, and the stop rule it runs under: a block that ends at a found start behind
+// the piece's own (starts[] ascending)
+struct PieceResult { uint32_t status, produced, why, next; uint64_t end_bit; };
+struct StopAtStart {
+    const uint64_t* starts; uint32_t n, k;
+    PF_HD_M bool at(uint64_t bit) { while (k < n && starts[k] < bit) k++; return k < n && starts[k] == bit; }
+};
+struct StopAtBit { uint64_t bit; PF_HD_M bool at(uint64_t b) { return b == bit; } };
+// a live piece for the byte pass: where it starts and must end, the text before it that exists, its text's place and size
+struct LivePiece { uint64_t start_bit, end_bit, dst; uint32_t piece, hist, produced, why; };
+struct ByteResult { uint32_t status, produced, crc, pad; };
+
+// A window of WINDOW entries as a ring (entry of text offset o: w[o & WMASK]; the entries of the WINDOW bytes before o = 0
+// stand in it when the run starts), and the text itself where `text` is given.  The serial form; the wave's is in
+// pf_deflate.hip.
+template <class E> struct HostRing {
+    E* w; uint8_t* text;
+    bool leader() const { return true; }
+    void sync() {}
+    uint32_t share(uint32_t v) const { return v; }
+    void put(uint32_t o, E v) { w[o & WMASK] = v; if (text) text[o] = (uint8_t)v; }
+    void literal(uint32_t o, uint8_t b) { put(o, b); }
+    void copy(uint32_t o, uint32_t dist, uint32_t len) { for (uint32_t i = 0; i < len; i++) put(o + i, w[(o + i - dist) & WMASK]); }
+    void stored(uint32_t o, const uint8_t* src, uint32_t len) { for (uint32_t i = 0; i < len; i++) put(o + i, src[i]); }
+};
+
+// the marker pass's run of one piece: ring[WINDOW] of 16-bit entries, left as the run ends
+template <class Sink>
+PF_HD PieceResult marker_run(const uint8_t* p, uint32_t n, const uint64_t* starts, uint32_t n_starts, uint32_t i, DecodeTables& T, Sink& sink) {
+    BitReader r = bit_reader_at(p, n, starts[i]);
+    StopAtStart stop{starts, n_starts, i + 1};
+    PieceResult R{INF_OK, 0, RUN_NONE, 0, 0};
+    R.status = inflate_run(r, WINDOW, PIECE_TEXT_CAP, T, sink, stop, &R.produced, &R.why);
+    if (R.status == INF_TOO_MUCH_TEXT) R.status = INF_TOO_LARGE;
+    if (R.status == INF_OK) { R.end_bit = bit_pos(r); R.next = stop.k; }
+    return R;
+}
+// the byte pass's run of one live piece: ring[WINDOW] of bytes preset with the window before it, text to text[0 .. produced)
+template <class Sink>
+PF_HD ByteResult byte_run(const uint8_t* p, uint32_t n, const LivePiece& L, DecodeTables& T, Sink& sink) {
+    BitReader r = bit_reader_at(p, n, L.start_bit);
+    StopAtBit stop{L.end_bit};
+    ByteResult B{INF_OK, 0, 0, 0};
+    uint32_t why = RUN_NONE;
+    B.status = inflate_run(r, L.hist, L.produced, T, sink, stop, &B.produced, &why);
+    // (the same bits under the same rule: anything else than the marker pass's end is a bug, and refuses the member)
+    if (B.status == INF_OK && (B.produced != L.produced || why != L.why || bit_pos(r) != L.end_bit)) B.status = INF_NOT_DECODED;
+    return B;
+}
+// entry j of the window a piece leaves (the WINDOW bytes before its end), from its ring and the window before it
+// (`before` null: no text stands before the piece -- a member's first -- and what a marker stands for is never looked at)
+PF_HD uint8_t chain_byte(const uint16_t* ring, uint32_t produced, const uint8_t* before, uint32_t j) {
+    const uint16_t e = ring[(produced + j) & WMASK];
+    return e & MARK ? (before ? before[e & WMASK] : (uint8_t)0) : (uint8_t)e;
+}
+// a chain of live pieces starts with the call's first piece and with every piece that has no text before it: the chains
+// of members decoded side by side are independent of one another
+PF_HD bool chain_starts(const LivePiece* live, uint32_t i) { return i == 0 || live[i].hist == 0; }
+
+// an open member between calls, and the route's counters
+struct LargeState {
+    bool open = false;
+    uint32_t bit0 = 0, hist = 0, crc = 0;      // the next block's bit in the first carried byte; bytes in the window; running CRC32
+    uint64_t len = 0;                          // running text length
+    uint8_t sig[MEMBER_SIG] = {0, 0, 0, 0, 0, 0, 0, 0};      // its head's first bytes: the members that follow it are found under them
+};
+struct LargeStats { uint64_t found = 0, live = 0, dropped = 0, members = 0; };
+struct LargeOut {
+    bool taken = false, none_yet = false, member_end = false;
+    uint32_t status = INF_OK;
+    uint64_t consumed = 0, text_n = 0;
+};
+
+// One call of the large-member route over bytes[0 .. n), which start at a member's head (!s.open) or with the byte that
+// holds an open member's next block (s.open).  The backend B runs the passes:
+//   int begin(bytes, limit)                                 the bytes the passes may look at, bytes[0 .. limit)
+//   int find(cuts[], n_cuts, piece_bytes, hit[])            hit[k]: the start found from cuts[k] on, or ~0
+//   int marker(starts[], n_starts, results[])               (the rings stay with the backend)
+//   int bytes_pass(live[], n_live, text_n, results[])       chain and byte pass: the text, the window carried
+// Each returns PF_OK or an error of the library's; "not taken" is out.taken = false with out.status.  out.none_yet: nothing
+// could be confirmed yet, nothing is consumed, the caller reads on (only with !last).  The state moves only with a call
+// that consumes bytes.  A call may take several members, one behind the other, where their heads can be found beforehand.
+template <class B>
+int large_call(B& be, LargeState& s, LargeStats& stats, const uint8_t* bytes, uint64_t n, bool last, uint32_t piece_bytes, LargeOut& out) {
+    out = LargeOut{};
+    auto refuse = [&](uint32_t st) { out.taken = false; out.status = st; s = LargeState{}; return 0; };
+    auto read_on = [&]() { out.taken = true; out.none_yet = true; return 0; };
+    if (piece_bytes == 0) piece_bytes = PIECE_DEFAULT;
+    LargeState t = s;
+    uint64_t start_bit = t.bit0;
+    if (!t.open) {
+        uint64_t head = 0;
+        const uint32_t st = parse_head(bytes, n, &head);
+        if (st == INF_TRUNCATED && !last) return read_on();
+        if (st) return refuse(st);
+        t = LargeState{};
+        t.open = true; start_bit = head * 8;
+        memcpy(t.sig, bytes, MEMBER_SIG);
+    }
+    const uint64_t first = start_bit >> 3;
+    const uint64_t limit = std::min<uint64_t>(n, first + (uint64_t)MAX_CUTS * piece_bytes);     // (< 4 GiB: the readers' offsets are 32-bit)
+    if (limit >= (1ull << 32) || first >= limit) return first >= limit && !last ? read_on() : refuse(first >= limit ? INF_TRUNCATED : INF_TOO_LARGE);
+    const bool cut_short = limit < n, end_here = last && !cut_short;
+    { const int rc = be.begin(bytes, limit); if (rc) return rc; }
+    // find: the cuts' hits, and -- members side by side -- the payload's first bit of every member whose head stands in these
+    // bytes under the signature of the call's first member, open or not (list_members' search; a false candidate is a false
+    // start like any other)
+    // A call has MAX_PIECES starts at most -- the backend's rings are sized by it: the cuts come first, then as many members'
+    // payloads as still fit (the chain ends in front of a member whose payload is no start; the next call begins there)
+    std::vector<uint64_t> cuts, hit, starts(1, start_bit), payloads, heads;
+    for (uint64_t c = first + piece_bytes; c < limit; c += piece_bytes) cuts.push_back(c);
+    const size_t room = MAX_PIECES - 1 - std::min<size_t>(MAX_PIECES - 1, cuts.size());
+    if (limit > MEMBER_SIG)
+        for (uint64_t c = s.open ? 0 : 1; c + MEMBER_HEAD <= limit;) {
+            const void* m = memmem(bytes + c, (size_t)(limit - c), t.sig, MEMBER_SIG);
+            if (!m) break;
+            c = (uint64_t)(static_cast<const uint8_t*>(m) - bytes);
+            uint64_t head = 0;
+            if (parse_head(bytes + c, limit - c, &head) == INF_OK && c + head < limit) { heads.push_back(c); if (payloads.size() < room) payloads.push_back((c + head) * 8); }
+            c++;
+        }
+    hit.assign(cuts.size(), ~0ull);
+    if (!cuts.empty()) { const int rc = be.find(cuts.data(), (uint32_t)cuts.size(), piece_bytes, hit.data()); if (rc) return rc; }
+    for (uint64_t h : hit) if (h != ~0ull) starts.push_back(h);
+    starts.insert(starts.end(), payloads.begin(), payloads.end());
+    std::sort(starts.begin(), starts.end());
+    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
+    if (starts.size() > MAX_PIECES) return refuse(INF_TOO_LARGE);          // (cannot be: 1 + the cuts + the payloads that fit)
+    // marker
+    std::vector<PieceResult> res(starts.size());
+    { const int rc = be.marker(starts.data(), (uint32_t)starts.size(), res.data()); if (rc) return rc; }
+    // the live chain: what is confirmed and fits the call.  Behind a member's tail the chain goes on with the member whose
+    // payload starts there, if its first bit is a start of this call
+    struct Ended { size_t n_live; uint64_t tail; };            // a member that ends in this call: its last live piece, its tail's place
+    std::vector<LivePiece> live;
+    std::vector<Ended> ended;
+    uint64_t text_n = 0, consumed = 0, member_len = t.len;
+    uint32_t at = 0, next_bit0 = 0;
+    bool member_end = false;
+    for (;;) {
+        const PieceResult& R = res[at];
+        if (R.status == INF_TRUNCATED && !end_here) break;                    // its end is not in these bytes yet
+        if (R.status != INF_OK) { if (ended.empty()) return refuse(R.status); break; }      // (a later member: in a call of its own)
+        if (!live.empty() && text_n + R.produced > LARGE_MAX_TEXT) break;
+        const uint64_t tail = (R.end_bit + 7) >> 3;
+        if (R.why == RUN_FINAL && tail + MEMBER_TAIL > n) {
+            if (!last || !ended.empty()) break;
+            return refuse(INF_TRUNCATED);
+        }
+        live.push_back(LivePiece{starts[at], R.end_bit, text_n, at, (uint32_t)std::min<uint64_t>(WINDOW, member_len), R.produced, R.why});
+        text_n += R.produced; member_len += R.produced;
+        member_end = R.why == RUN_FINAL;
+        if (member_end) {
+            consumed = tail + MEMBER_TAIL; next_bit0 = 0; member_len = 0;
+            ended.push_back(Ended{live.size(), tail});
+            uint64_t head = 0;
+            if (consumed >= limit || parse_head(bytes + consumed, limit - consumed, &head) != INF_OK) break;
+            // (a member within the small-member kernels' limits, as list_members sizes it, is theirs: the call ends here)
+            const auto after = std::upper_bound(heads.begin(), heads.end(), consumed);
+            const uint64_t ends = after != heads.end() ? *after : end_here ? n : 0;        // (0: not known)
+            if (ends >= consumed + MEMBER_HEAD + MEMBER_TAIL && bytes[consumed + 3] == 0 && ends - consumed <= SLOT_BYTES && le32(bytes + ends - 4) <= CHUNK) break;
+            const auto next = std::lower_bound(starts.begin(), starts.end(), (consumed + head) * 8);
+            if (next == starts.end() || *next != (consumed + head) * 8) break;
+            at = (uint32_t)(next - starts.begin());
+            continue;
+        }
+        if (R.next >= starts.size()) return refuse(INF_NOT_DECODED);           // (a run that stopped at a start names it)
+        consumed = starts[R.next] >> 3; next_bit0 = (uint32_t)(starts[R.next] & 7);
+        at = R.next;
+    }
+    if (live.empty()) {
+        // nothing confirmed: with more bytes to come the caller reads on, unless this call already looked as far as one may
+        if (cut_short || last) return refuse(cut_short ? INF_TOO_LARGE : INF_TRUNCATED);
+        return read_on();
+    }
+    // chain and byte pass, then every ended member's CRC32 and length against its tail
+    std::vector<ByteResult> br(live.size());
+    { const int rc = be.bytes_pass(live.data(), (uint32_t)live.size(), text_n, br.data()); if (rc) return rc; }
+    size_t e = 0;
+    for (size_t i = 0; i < live.size(); i++) {
+        if (br[i].status != INF_OK) return refuse(br[i].status);
+        t.crc = crc_combine(t.crc, br[i].crc, live[i].produced);
+        t.len += live[i].produced;
+        if (e < ended.size() && ended[e].n_live == i + 1) {
+            const uint8_t* tail = bytes + ended[e].tail;
+            if (le32(tail) != t.crc) return refuse(INF_BAD_CRC);
+            if (le32(tail + 4) != (uint32_t)t.len) return refuse(t.len > le32(tail + 4) ? INF_TOO_MUCH_TEXT : INF_TOO_LITTLE_TEXT);
+            stats.members++; e++;
+            const LargeState ended_one = t;
+            t = LargeState{};
+            if (i + 1 < live.size()) { t.open = true; memcpy(t.sig, ended_one.sig, MEMBER_SIG); }
+        }
+    }
+    if (t.open) { t.bit0 = next_bit0; t.hist = (uint32_t)std::min<uint64_t>(WINDOW, t.len); }
+    uint64_t found = 0;                        // the found starts up to where the call's text ends: the rest is found again
+    for (uint64_t b : starts) if (b < live.back().end_bit) found++;
+    stats.found += found; stats.live += live.size(); stats.dropped += found - live.size();
+    s = t;
+    out.taken = true; out.member_end = !t.open; out.consumed = consumed; out.text_n = text_n;
+    return 0;
+}
+
+// The serial backend: the host model.  Every pass reads from a heap copy of exactly the bytes a call may look at, and a
+// live piece's text goes to a buffer of exactly its size (a sanitizer build sees any step past either).
+struct HostLarge {
+    std::vector<uint16_t> rings;               // of the call's found starts, WINDOW entries each
+    std::vector<uint8_t> window = std::vector<uint8_t>(WINDOW, 0), text;     // the window carried; the call's text
+    std::vector<uint8_t> data;                 // a heap copy of exactly the bytes the call may look at
+    uint64_t limit = 0;
+    int begin(const uint8_t* bytes, uint64_t n) { data.assign(bytes, bytes + n); limit = n; return 0; }
+    int find(const uint64_t* cuts, uint32_t n_cuts, uint32_t piece_bytes, uint64_t* hit) {
+        DecodeTables T;
+        for (uint32_t k = 0; k < n_cuts; k++) {
+            const uint64_t end = std::min<uint64_t>(limit, cuts[k] + piece_bytes) * 8;
+            for (uint64_t bit = cuts[k] * 8; bit < end; bit++)
+                if (block_start_ok(data.data(), (uint32_t)limit, bit, T)) { hit[k] = bit; break; }
+        }
+        return 0;
+    }
+    int marker(const uint64_t* starts, uint32_t n_starts, PieceResult* res) {
+        DecodeTables T;
+        rings.assign((size_t)n_starts * WINDOW, 0);
+        for (uint32_t i = 0; i < n_starts; i++) {
+            uint16_t* ring = rings.data() + (size_t)i * WINDOW;
+            for (uint32_t j = 0; j < WINDOW; j++) ring[j] = (uint16_t)(MARK | j);
+            HostRing<uint16_t> sink{ring, nullptr};
+            res[i] = marker_run(data.data(), (uint32_t)limit, starts, n_starts, i, T, sink);
+        }
+        return 0;
+    }
+    int bytes_pass(const LivePiece* live, uint32_t n_live, uint64_t text_n, ByteResult* br) {
+        DecodeTables T;
+        text.assign((size_t)text_n, 0);
+        std::vector<uint8_t> before(window), after(WINDOW), ring(WINDOW);
+        for (uint32_t i = 0; i < n_live; i++) {
+            const uint16_t* marks = rings.data() + (size_t)live[i].piece * WINDOW;
+            for (uint32_t j = 0; j < WINDOW; j++) after[j] = chain_byte(marks, live[i].produced, live[i].hist ? before.data() : nullptr, j);
+            ring = before;
+            std::vector<uint8_t> piece(live[i].produced);
+            HostRing<uint8_t> sink{ring.data(), piece.data()};
+            br[i] = byte_run(data.data(), (uint32_t)limit, live[i], T, sink);
+            br[i].crc = crc32_bytes(piece.data(), live[i].produced);
+            // (the chain's window and the byte pass's own must be the same bytes)
+            if (br[i].status == INF_OK)
+                for (uint32_t j = 0; j < WINDOW; j++) if (ring[(live[i].produced + j) & WMASK] != after[j] && WINDOW - j <= live[i].hist + live[i].produced) br[i].status = INF_NOT_DECODED;
+            if (!piece.empty()) memcpy(text.data() + live[i].dst, piece.data(), piece.size());
+            before.swap(after);
+        }
+        window = before;
+        return 0;
+    }
+};
+
+// a whole file of gzip members by the large-member route, each member alone, call after call as a feed would; false: "not
+// taken", *member / *status name the member refused
+inline bool host_inflate_large(const uint8_t* p, uint64_t n, uint32_t piece_bytes, std::vector<uint8_t>& text, LargeStats& stats,
+                               uint64_t* member, uint32_t* status) {
+    text.clear(); *member = 0; *status = INF_OK;
+    HostLarge be;
+    LargeState s;
+    for (uint64_t at = 0; at < n;) {
+        LargeOut o;
+        if (large_call(be, s, stats, p + at, n - at, true, piece_bytes, o) || !o.taken || !o.consumed) {
+            *member = stats.members; *status = o.status ? o.status : (uint32_t)INF_NOT_DECODED; text.clear();
+            return false;
+        }
+        text.insert(text.end(), be.text.begin(), be.text.end());
+        at += o.consumed;
+    }
+    if (s.open) { *member = stats.members; *status = INF_TRUNCATED; text.clear(); return false; }
+    return true;
+}
+
 }  // namespace pfgz
 
 #if defined(__HIPCC__)
@@ -868,5 +1235,27 @@ struct PfGzDecoder {
                hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
     // once the caller has synchronised with that decode: the first member that failed a check and its status, or -1
     int64_t first_refused(uint32_t* status) const;
+};
+// The device backend of pfgz::large_call: the find, marker, chain and byte passes as separate launches in stream order, no
+// workgroup waiting for another.  Device memory per call, whatever the file's size: the bytes the call looks at
+// (MAX_CUTS * piece_bytes at most: 48 MiB at the default piece), per start (MAX_PIECES at most) a ring of 64 KiB and 48 bytes
+// of results, per live piece a window of 32 KiB, one carried window -- under MAX_PIECES * 96 KiB + the bytes = 240 MiB at the
+// default piece; the text buffer is the caller's (`place`), LARGE_MAX_TEXT at most.
+struct PfGzLarge {
+    hipStream_t st = nullptr;
+    // asked before the byte pass: room for text_n bytes of text; -> where they go (device memory)
+    std::function<int(uint64_t text_n, uint8_t** dst)> place;
+    DevBuf data, d_cuts, d_hits, d_starts, d_res, rings, wins, d_live, d_br, window;
+    HipEvent e0, e1, e2;
+    float ms[4] = {0, 0, 0, 0};               // device time of the find, marker, chain and byte passes
+    uint32_t limit = 0;
+    bool ready = false;                       // the carried window exists, gz_marker_kernel's dynamic LDS limit is raised
+    uint64_t device_bytes() const {
+        return data.cap + d_cuts.cap + d_hits.cap + d_starts.cap + d_res.cap + rings.cap + wins.cap + d_live.cap + d_br.cap + window.cap;
+    }
+    int begin(const uint8_t* bytes, uint64_t n);
+    int find(const uint64_t* cuts, uint32_t n_cuts, uint32_t piece_bytes, uint64_t* hit);
+    int marker(const uint64_t* starts, uint32_t n_starts, pfgz::PieceResult* res);
+    int bytes_pass(const pfgz::LivePiece* live, uint32_t n_live, uint64_t text_n, pfgz::ByteResult* br);
 };
 #endif

@@ -414,6 +414,124 @@ __global__ __launch_bounds__(64) void gz_inflate64_kernel(DecParams P) {
     inflate_member<BGZF_MAX_TEXT>(P, P.idx[blockIdx.x], s_dyn64, *reinterpret_cast<DecodeTables*>(s_dyn64 + WIN64_WORDS), threadIdx.x);
 }
 
+// ---- large members (pf_deflate.h: large_call): the four passes.  Every loop is bounded by the input's bits or by a cap on
+// the output stated where it is passed; every offset into a ring is masked, every text write stands under inflate_run's
+// cap, which is the piece's own size.
+//
+// gz_find_kernel: one wave per cut, a lane per bit offset, 64 offsets at a time, until one lane's offset holds a dynamic
+// block's header (block_start_ok) or the next cut comes.  The tables a lane builds to judge a header are its own (scratch).
+__global__ __launch_bounds__(64) void gz_find_kernel(const uint8_t* p, uint32_t n, const uint64_t* cuts, uint32_t n_cuts, uint32_t piece_bytes,
+                                                      uint64_t* hit) {
+    const uint32_t k = blockIdx.x, lane = threadIdx.x;
+    if (k >= n_cuts) return;
+    DecodeTables T;
+    const uint64_t from = cuts[k] * 8, end = min((uint64_t)n, cuts[k] + piece_bytes) * 8;
+    uint64_t found = ~0ull;
+    for (uint64_t base = from; base < end; base += 64) {
+        const uint64_t bit = base + lane;
+        const bool ok = bit < end && block_start_ok(p, n, bit, T);
+        const uint64_t m = __ballot(ok);
+        if (m) { found = base + (uint64_t)(__ffsll((long long)m) - 1); break; }
+    }
+    if (lane == 0) hit[k] = found;
+}
+
+// the wave's form of HostRing: a match copy spread over the lanes.  In the ring a copy's sources never stand where an
+// earlier lane's destination does: a source WINDOW - d entries before a destination (distances near WINDOW) is read by a
+// lower lane index than the one that writes it, in the same or an earlier step of the loop
+template <class E> struct WaveRing {
+    E* w; uint8_t* text; uint32_t lane;
+    __device__ bool leader() const { return lane == 0; }
+    __device__ void sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __builtin_amdgcn_wave_barrier(); }
+    __device__ uint32_t share(uint32_t v) const { return (uint32_t)__shfl((int)v, 0, 64); }
+    __device__ void put(uint32_t o, E v) { w[o & WMASK] = v; if (text) text[o] = (uint8_t)v; }
+    __device__ void literal(uint32_t o, uint8_t b) { if (lane == 0) put(o, b); }
+    __device__ void copy(uint32_t o, uint32_t dist, uint32_t len) {
+        sync();
+        for (uint32_t i = lane; i < len; i += 64) put(o + i, w[(o - dist + (dist >= len ? i : i % dist)) & WMASK]);
+    }
+    // (a stored block may be longer than the ring: only its last WINDOW bytes stay in it)
+    __device__ void stored(uint32_t o, const uint8_t* src, uint32_t len) {
+        for (uint32_t i = lane; i < len; i += 64) {
+            if (len - i <= WINDOW) w[(o + i) & WMASK] = src[i];
+            if (text) text[o + i] = src[i];
+        }
+    }
+};
+
+// gz_marker_kernel: one wave per found start decodes without the text before it; its ring of WINDOW 16-bit entries (64 KiB
+// of LDS, with the tables over what a kernel may declare: dynamic, two workgroups per CU as gz_inflate64_kernel) goes out
+// as it stands when the run ends
+constexpr uint32_t MARKER_LDS = WINDOW * 2 + (uint32_t)sizeof(DecodeTables);
+static_assert(WINDOW * 2 % 16 == 0 && 2 * MARKER_LDS <= 160 * 1024, "the tables stand aligned behind the ring; two workgroups per CU");
+__global__ __launch_bounds__(64) void gz_marker_kernel(const uint8_t* p, uint32_t n, const uint64_t* starts, uint32_t n_starts, PieceResult* res,
+                                                        uint32_t* rings) {
+    extern __shared__ __align__(16) uint32_t s_dynm[];           // WINDOW entries, then the tables: MARKER_LDS bytes
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n_starts) return;
+    for (uint32_t j = lane; j < WINDOW / 2; j += 64) s_dynm[j] = (MARK | (2 * j)) | (MARK | (2 * j + 1)) << 16;
+    WaveRing<uint16_t> sink{reinterpret_cast<uint16_t*>(s_dynm), nullptr, lane};
+    sink.sync();
+    const PieceResult R = marker_run(p, n, starts, n_starts, i, *reinterpret_cast<DecodeTables*>(s_dynm + WINDOW / 2), sink);
+    sink.sync();
+    if (lane == 0) res[i] = R;
+    if (R.status != INF_OK) return;
+    uint32_t* out = rings + (size_t)i * (WINDOW / 2);
+    for (uint32_t j = lane; j < WINDOW / 2; j += 64) out[j] = s_dynm[j];
+}
+
+// gz_chain_kernel: one workgroup per chain -- per member whose first piece is in the call (chain_starts) -- walks its live
+// pieces in order, WINDOW bytes a step: wins[0] is the window carried into the call, wins[i + 1] the one live piece i
+// leaves.  A chain's first piece with no text before it reads no window, so no workgroup reads what another writes.
+__global__ __launch_bounds__(1024) void gz_chain_kernel(const LivePiece* live, uint32_t n_live, const uint16_t* rings, uint8_t* wins) {
+    __shared__ uint32_t s_from;
+    if (threadIdx.x == 0) {
+        uint32_t chain = 0, from = n_live;
+        for (uint32_t i = 0; i < n_live; i++)
+            if (chain_starts(live, i) && chain++ == blockIdx.x) { from = i; break; }
+        s_from = from;
+    }
+    __syncthreads();
+    for (uint32_t i = s_from; i < n_live && (i == s_from || !chain_starts(live, i)); i++) {
+        const uint16_t* ring = rings + (size_t)live[i].piece * WINDOW;
+        const uint8_t* before = live[i].hist ? wins + (size_t)i * WINDOW : nullptr;
+        uint8_t* after = wins + (size_t)(i + 1) * WINDOW;
+        for (uint32_t j = threadIdx.x; j < WINDOW; j += 1024) after[j] = chain_byte(ring, live[i].produced, before, j);
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
+// gz_bytes_kernel: one wave per live piece decodes it again as bytes -- the window before it preset in LDS (32 KiB and the
+// tables: four workgroups per CU, as gz_inflate_kernel), the text to its place as it is made -- and takes its CRC32
+__global__ __launch_bounds__(64) void gz_bytes_kernel(const uint8_t* p, uint32_t n, const LivePiece* live, uint32_t n_live, const uint8_t* wins,
+                                                       uint8_t* text, ByteResult* br) {
+    __shared__ __align__(16) uint32_t s_ring[WINDOW / 4];
+    __shared__ DecodeTables s_T;
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n_live) return;
+    const LivePiece L = live[i];
+    const uint4* before = reinterpret_cast<const uint4*>(wins + (size_t)i * WINDOW);
+    for (uint32_t j = lane; j < WINDOW / 16; j += 64) reinterpret_cast<uint4*>(s_ring)[j] = before[j];
+    uint8_t* dst = text + L.dst;
+    WaveRing<uint8_t> sink{reinterpret_cast<uint8_t*>(s_ring), dst, lane};
+    sink.sync();
+    ByteResult B = byte_run(p, n, L, s_T, sink);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");           // (the lanes read back what other lanes wrote)
+    __builtin_amdgcn_wave_barrier();
+    if (B.status == INF_OK) {
+        const uint32_t piece = (L.produced + 63) / 64, at = lane * piece;
+        uint32_t len = at < L.produced ? min(piece, L.produced - at) : 0;
+        uint32_t crc = len ? crc32_bytes(dst + at, len) : 0;
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t oc = (uint32_t)__shfl_down((int)crc, d, 64), ol = (uint32_t)__shfl_down((int)len, d, 64);
+            if ((lane & (2 * d - 1)) == 0 && ol) { crc = len ? crc_combine(crc, oc, ol) : oc; len += ol; }
+        }
+        B.crc = crc;
+    }
+    if (lane == 0) br[i] = B;
+}
+
 }  // namespace pfgz
 
 int PfGzEncoder::ensure(int n_cu) {
@@ -563,9 +681,108 @@ int64_t PfGzDecoder::first_refused(uint32_t* status) const {
     return -1;
 }
 
+// ---- the large-member route's passes on the device: each uploads what it needs, launches, and reads its small answer
+// back behind a synchronisation -- the host decides between them (pfgz::large_call)
+int PfGzLarge::begin(const uint8_t* bytes, uint64_t n) {
+    if (n >= (1ull << 32)) return fail(PF_ERR_ARG, "gzip decoder: a call over 4 GiB of compressed bytes");
+    if (!ready) {
+        PFCHK(window.ensure(pfgz::WINDOW, true));
+        HIPCHK(hipMemsetAsync(window.p, 0, pfgz::WINDOW, st));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(pfgz::gz_marker_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)pfgz::MARKER_LDS));
+        PFCHK(e0.ensure()); PFCHK(e1.ensure()); PFCHK(e2.ensure());
+        ready = true;
+    }
+    limit = (uint32_t)n;
+    PFCHK(data.ensure(n + 16));
+    HIPCHK(hipMemcpyAsync(data.p, bytes, n, hipMemcpyHostToDevice, st));
+    return PF_OK;
+}
+
+int PfGzLarge::find(const uint64_t* cuts, uint32_t n_cuts, uint32_t piece_bytes, uint64_t* hit) {
+    PFCHK(d_cuts.ensure((size_t)n_cuts * 8));
+    PFCHK(d_hits.ensure((size_t)n_cuts * 8));
+    HIPCHK(hipMemcpyAsync(d_cuts.p, cuts, (size_t)n_cuts * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(e0, st));
+    hipLaunchKernelGGL(pfgz::gz_find_kernel, dim3(n_cuts), dim3(64), 0, st, data.as<uint8_t>(), limit, d_cuts.as<uint64_t>(), n_cuts, piece_bytes,
+                       d_hits.as<uint64_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, st));
+    HIPCHK(hipMemcpyAsync(hit, d_hits.p, (size_t)n_cuts * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float t = 0;
+    if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) ms[0] += t;
+    return PF_OK;
+}
+
+int PfGzLarge::marker(const uint64_t* starts, uint32_t n_starts, pfgz::PieceResult* res) {
+    PFCHK(d_starts.ensure((size_t)n_starts * 8));
+    PFCHK(d_res.ensure((size_t)n_starts * sizeof(pfgz::PieceResult)));
+    PFCHK(rings.ensure((size_t)n_starts * pfgz::WINDOW * 2));
+    HIPCHK(hipMemcpyAsync(d_starts.p, starts, (size_t)n_starts * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(e0, st));
+    hipLaunchKernelGGL(pfgz::gz_marker_kernel, dim3(n_starts), dim3(64), pfgz::MARKER_LDS, st, data.as<uint8_t>(), limit, d_starts.as<uint64_t>(),
+                       n_starts, d_res.as<pfgz::PieceResult>(), rings.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, st));
+    HIPCHK(hipMemcpyAsync(res, d_res.p, (size_t)n_starts * sizeof(pfgz::PieceResult), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float t = 0;
+    if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) ms[1] += t;
+    return PF_OK;
+}
+
+int PfGzLarge::bytes_pass(const pfgz::LivePiece* live, uint32_t n_live, uint64_t text_n, pfgz::ByteResult* br) {
+    uint8_t* text = nullptr;
+    PFCHK(place(text_n, &text));
+    PFCHK(d_live.ensure((size_t)n_live * sizeof(pfgz::LivePiece)));
+    PFCHK(d_br.ensure((size_t)n_live * sizeof(pfgz::ByteResult)));
+    PFCHK(wins.ensure((size_t)(n_live + 1) * pfgz::WINDOW));
+    HIPCHK(hipMemcpyAsync(d_live.p, live, (size_t)n_live * sizeof(pfgz::LivePiece), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(wins.p, window.p, pfgz::WINDOW, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipEventRecord(e0, st));
+    uint32_t n_chains = 0;
+    for (uint32_t i = 0; i < n_live; i++) n_chains += pfgz::chain_starts(live, i) ? 1 : 0;
+    hipLaunchKernelGGL(pfgz::gz_chain_kernel, dim3(n_chains), dim3(1024), 0, st, d_live.as<pfgz::LivePiece>(), n_live, rings.as<uint16_t>(), wins.as<uint8_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, st));
+    hipLaunchKernelGGL(pfgz::gz_bytes_kernel, dim3(n_live), dim3(64), 0, st, data.as<uint8_t>(), limit, d_live.as<pfgz::LivePiece>(), n_live,
+                       wins.as<uint8_t>(), text, d_br.as<pfgz::ByteResult>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e2, st));
+    HIPCHK(hipMemcpyAsync(window.p, wins.as<uint8_t>() + (size_t)n_live * pfgz::WINDOW, pfgz::WINDOW, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(br, d_br.p, (size_t)n_live * sizeof(pfgz::ByteResult), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float t = 0;
+    if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) ms[2] += t;
+    if (hipEventElapsedTime(&t, e1, e2) == hipSuccess) ms[3] += t;
+    return PF_OK;
+}
+
 extern "C" {
 
 uint32_t pf_gzip_device_chunk_bytes(void) { return pfgz::CHUNK; }
+
+int pf_gunzip_host_model_large(const char* members, uint64_t n, uint32_t piece_bytes, char** out, uint64_t* out_n, int* taken, uint64_t* pieces) {
+    if ((!members && n) || !out || !out_n || !taken) return fail(PF_ERR_ARG, "pf_gunzip_host_model_large: null argument");
+    *out = nullptr; *out_n = 0; *taken = 0;
+    if (piece_bytes && piece_bytes < pfgz::PIECE_MIN) return fail(PF_ERR_ARG, "pf_gunzip_host_model_large: piece_bytes is 0 or at least %u", pfgz::PIECE_MIN);
+    std::vector<uint8_t> text;
+    pfgz::LargeStats stats;
+    uint64_t bad = 0;
+    uint32_t status = 0;
+    const bool ok = pfgz::host_inflate_large(reinterpret_cast<const uint8_t*>(members), n, piece_bytes, text, stats, &bad, &status);
+    if (pieces) { pieces[0] = stats.found; pieces[1] = stats.live; pieces[2] = stats.dropped; pieces[3] = stats.members; }
+    if (!ok) {
+        (void)fail(PF_OK, "pf_gunzip_host_model_large: not taken: member %llu: %s", (unsigned long long)bad, pfgz::inf_status_name(status));
+        return PF_OK;
+    }
+    char* buf = (char*)malloc(text.size() ? text.size() : 1);
+    if (!buf) return fail(PF_ERR_OOM, "pf_gunzip_host_model_large: out of memory");
+    if (!text.empty()) memcpy(buf, text.data(), text.size());
+    *out = buf; *out_n = text.size(); *taken = 1;
+    return PF_OK;
+}
 
 int pf_gzip_host_model(const char* data, uint64_t n, uint32_t flags, char** out, uint64_t* out_n) {
     if ((!data && n) || !out || !out_n) return fail(PF_ERR_ARG, "pf_gzip_host_model: null argument");

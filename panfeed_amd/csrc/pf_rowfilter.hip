@@ -233,6 +233,7 @@ struct RfMembers {
     uint64_t total = 0, n = 0;     // inflate: d_text[0 .. total) is the carried line and the members' text, [0 .. n) its complete lines
     uint64_t skip = 0;             // header: the header line's bytes: no line of it is a row
     bool refused = false;          // any of them: the block is not one for this route, "not taken"
+    bool go_large = false;         // plan, inflate: not for the small-member kernels -- with the feed's switch on, the large-member route's
 };
 
 // Complete lines of a table's text on the device, text.d_text[0 .. n), for the row filter, the plot grid and the k-mer join
@@ -249,6 +250,13 @@ struct TextFeed {
     std::string header;
     uint64_t gz_members = 0, gz_text_bytes = 0;
     float gz_ms = 0;
+    // the large-member route (pf_deflate.h: large_call), off unless the owner's pf_*_set_large_members turns it on: the
+    // member that is open between calls, the route's counters, its passes on the device
+    bool large_on = false;
+    uint32_t piece_bytes = 0;
+    pfgz::LargeState lg_state;
+    pfgz::LargeStats lg_stats;
+    PfGzLarge lg;
     TimedStream ts;
 
     // the complete lines of host text: *n bytes of them, uploaded unless there are none.  `before(*n)`: what the owner has to
@@ -262,7 +270,15 @@ struct TextFeed {
     }
 
     // a file of members starts: nothing carried; with `with_header`, its first line is not a row
-    int members_begin(int with_header) { carry_n = 0; want_header = with_header != 0; header.clear(); return PF_OK; }
+    int members_begin(int with_header) {
+        carry_n = 0; want_header = with_header != 0; header.clear(); lg_state = pfgz::LargeState{};
+        return PF_OK;
+    }
+    int set_large(int on, uint32_t piece) {
+        if (piece && piece < pfgz::PIECE_MIN) return fail(PF_ERR_ARG, "set_large_members: piece_bytes is 0 (the default) or at least %u", pfgz::PIECE_MIN);
+        large_on = on != 0; piece_bytes = piece; lg_state = pfgz::LargeState{};
+        return PF_OK;
+    }
     // that line, with its newline, once a members call has seen it (the messages are the row filter's for every owner)
     int header_line(const char** line, uint64_t* nbytes) const {
         if (!line || !nbytes) return fail(PF_ERR_ARG, "pf_rowfilter_members_header: null argument");
@@ -277,9 +293,18 @@ struct TextFeed {
     template <class F> int members(const char* bytes, uint64_t nbytes, int last, uint64_t* consumed, int* taken, F&& work) {
         *consumed = 0; *taken = 0;
         RfMembers c{reinterpret_cast<const uint8_t*>(bytes), nbytes, last != 0};
-        PFCHK(plan(c));
-        if (c.refused || c.none_yet) { *taken = !c.refused; return PF_OK; }
-        PFCHK(inflate(c));
+        // a member of the large route that is open goes on there; else the block's head and its listed members say which
+        // route takes it, and what the small-member kernels refuse the large route tries from the block's first byte
+        c.go_large = large_on && lg_state.open;
+        if (!c.go_large) {
+            PFCHK(plan(c));
+            if (!c.go_large && (c.refused || c.none_yet)) { *taken = !c.refused; return PF_OK; }
+            if (!c.go_large) PFCHK(inflate(c));
+        }
+        if (c.go_large) {
+            PFCHK(inflate_large(c));
+            if (c.refused || c.none_yet) { *taken = !c.refused; return PF_OK; }
+        }
         if (!c.refused) PFCHK(peel_header(c));
         if (c.refused) return PF_OK;
         gz_members += c.take; gz_text_bytes += c.text_n;
@@ -291,8 +316,14 @@ struct TextFeed {
 
 private:
     // (whatever refuses the block leaves no line carried: the caller starts over another way)
+    // what the small-member route's plan and inflate stages refuse: with the switch on it is the large route's to try, from
+    // the block's first byte; a refusal for real otherwise
+    int reroute(RfMembers& c, uint64_t member, uint32_t status) {
+        if (large_on && !c.go_large) { c.go_large = true; return PF_OK; }
+        return refuse(c, member, status);
+    }
     int refuse(RfMembers& c, uint64_t member, uint32_t status) {
-        carry_n = 0; c.refused = true;
+        carry_n = 0; c.refused = true; lg_state = pfgz::LargeState{};
         return fail(PF_OK, "pf_rowfilter_scan_members: not taken: member %llu of the block: %s", (unsigned long long)member,
                     pfgz::inf_status_name(status));
     }
@@ -303,14 +334,15 @@ private:
         // members listed by their BSIZE chain, anything else by the signature search, as ever
         const bool bgzf = pfgz::bgzf_head_ok(c.bytes, c.nbytes);
         if (!(bgzf ? pfgz::list_members_bgzf(c.bytes, c.nbytes, c.last, c.ms, &listed) : pfgz::list_members(c.bytes, c.nbytes, c.last, c.ms, &listed)))
-            return refuse(c, 0, pfgz::INF_BAD_HEAD);
+            return reroute(c, 0, pfgz::INF_BAD_HEAD);
         const bool none = c.ms.empty() && !c.last;
         // a member this decoder takes would have ended by now
-        if (none && c.nbytes >= (bgzf ? pfgz::BGZF_MAX_MEMBER : pfgz::SLOT_BYTES + pfgz::MEMBER_HEAD)) return refuse(c, 0, pfgz::INF_TOO_LARGE);
+        if (none && c.nbytes >= (bgzf ? pfgz::BGZF_MAX_MEMBER : pfgz::SLOT_BYTES + pfgz::MEMBER_HEAD)) return reroute(c, 0, pfgz::INF_TOO_LARGE);
         if (none) { c.none_yet = true; return PF_OK; }
         // at most the decoder's call: the rest is the caller's to give again
         while (c.take < c.ms.size() && c.take < PfGzDecoder::MAX_MEMBERS) {
-            if (c.ms[c.take].status != pfgz::INF_OK) return refuse(c, c.take, c.ms[c.take].status);
+            if (c.ms[c.take].status != pfgz::INF_OK && large_on && c.take) break;      // (the run before it now, that member in a call of its own)
+            if (c.ms[c.take].status != pfgz::INF_OK) return reroute(c, c.take, c.ms[c.take].status);
             if (c.take && c.text_n + c.ms[c.take].isize > PfGzDecoder::MAX_TEXT) break;
             c.text_n += c.ms[c.take].isize; c.take++;
         }
@@ -338,8 +370,47 @@ private:
             ts.add_elapsed(&gz_ms);
             uint32_t status = 0;
             const int64_t bad = dec.first_refused(&status);
-            if (bad >= 0) return refuse(c, (uint64_t)bad, status);
+            if (bad >= 0) return reroute(c, (uint64_t)bad, status);
         }
+        c.n = tail[0]; c.total = tail[1];
+        return PF_OK;
+    }
+
+    // The same by the large-member route: one member, or as much of it as this call confirms, from the block's first byte
+    // on; the text lands behind the carried line once the marker pass has told its size
+    int inflate_large(RfMembers& c) {
+        hipStream_t st = ts.stream;
+        PFCHK(d_tail.ensure(16, true));
+        lg.st = st;
+        lg.place = [this, st](uint64_t text_n, uint8_t** dst) -> int {
+            PFCHK(text.reserve(carry_n + text_n + 1));
+            unsigned char* const to = text.d_text.as<unsigned char>();
+            if (carry_n) HIPCHK(hipMemcpyAsync(to, d_carry.p, carry_n, hipMemcpyDeviceToDevice, st));
+            *dst = to + carry_n;
+            return PF_OK;
+        };
+        const float before = lg.ms[0] + lg.ms[1] + lg.ms[2] + lg.ms[3];
+        const uint64_t members_before = lg_stats.members;
+        pfgz::LargeOut o;
+        PFCHK(pfgz::large_call(lg, lg_state, lg_stats, c.bytes, c.nbytes, c.last, piece_bytes, o));
+        gz_ms += lg.ms[0] + lg.ms[1] + lg.ms[2] + lg.ms[3] - before;
+        if (!o.taken) return refuse(c, 0, o.status);
+        if (o.none_yet) { c.none_yet = true; return PF_OK; }
+        c.take = (size_t)(lg_stats.members - members_before); c.text_n = o.text_n; c.used = o.consumed;
+        c.end = c.last && o.consumed == c.nbytes;
+        c.total = carry_n + c.text_n;
+        return text_tail(c);
+    }
+
+    // where the complete lines of d_text[0 .. c.total) end; the file's last line gets its newline
+    int text_tail(RfMembers& c) {
+        hipStream_t st = ts.stream;
+        unsigned char* const to = text.d_text.as<unsigned char>();
+        hipLaunchKernelGGL(rf_tail_kernel, dim3(1), dim3(256), 0, st, to, c.total, c.end ? 1 : 0, d_tail.as<uint64_t>());
+        HIPCHK(hipGetLastError());
+        uint64_t tail[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(tail, d_tail.p, 16, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
         c.n = tail[0]; c.total = tail[1];
         return PF_OK;
     }
@@ -381,7 +452,19 @@ template <class H> int feed_gunzip_stats(H* h, const char* fn, uint64_t* members
     if (members) *members = h->feed.gz_members;
     if (text_bytes) *text_bytes = h->feed.gz_text_bytes;
     if (inflate_ms) *inflate_ms = h->feed.gz_ms;
-    if (device_bytes) *device_bytes = h->feed.dec.device_bytes();
+    if (device_bytes) *device_bytes = h->feed.dec.device_bytes() + h->feed.lg.device_bytes();
+    return PF_OK;
+}
+// pf_*_set_large_members and pf_*_large_stats: the large-member route's switch and its counters -- pieces[4]: found starts,
+// live pieces, dropped starts, members taken by the route; ms[4]: device time of the find, marker, chain and byte passes
+template <class H> int feed_set_large(H* h, const char* fn, int on, uint32_t piece_bytes) {
+    return h ? h->feed.set_large(on, piece_bytes) : fail(PF_ERR_ARG, "%s: null argument", fn);
+}
+template <class H> int feed_large_stats(H* h, const char* fn, uint64_t* pieces, float* ms) {
+    if (!h) return fail(PF_ERR_ARG, "%s: null argument", fn);
+    const pfgz::LargeStats& t = h->feed.lg_stats;
+    if (pieces) { pieces[0] = t.found; pieces[1] = t.live; pieces[2] = t.dropped; pieces[3] = t.members; }
+    if (ms) for (int i = 0; i < 4; i++) ms[i] = h->feed.lg.ms[i];
     return PF_OK;
 }
 // ... and what their pf_*_create and pf_*_destroy share.  Create: the device checked and made current, the handle made --
@@ -570,6 +653,8 @@ int pf_rowfilter_scan(pf_rowfilter* f, const char* text, uint64_t nbytes, const 
 }
 
 int pf_rowfilter_members_begin(pf_rowfilter* f, int header) { return feed_members_begin(f, "pf_rowfilter_members_begin", header); }
+int pf_rowfilter_set_large_members(pf_rowfilter* f, int on, uint32_t piece_bytes) { return feed_set_large(f, "pf_rowfilter_set_large_members", on, piece_bytes); }
+int pf_rowfilter_large_stats(pf_rowfilter* f, uint64_t* pieces, float* ms) { return feed_large_stats(f, "pf_rowfilter_large_stats", pieces, ms); }
 
 int pf_rowfilter_members_header(pf_rowfilter* f, const char** line, uint64_t* nbytes) {
     return feed_members_header(f, "pf_rowfilter_members_header", line, nbytes);
@@ -1117,6 +1202,8 @@ int pf_plotgrid_scan(pf_plotgrid* g, const char* text, uint64_t nbytes, uint64_t
 }
 
 int pf_plotgrid_members_begin(pf_plotgrid* g, int header) { return feed_members_begin(g, "pf_plotgrid_members_begin", header); }
+int pf_plotgrid_set_large_members(pf_plotgrid* g, int on, uint32_t piece_bytes) { return feed_set_large(g, "pf_plotgrid_set_large_members", on, piece_bytes); }
+int pf_plotgrid_large_stats(pf_plotgrid* g, uint64_t* pieces, float* ms) { return feed_large_stats(g, "pf_plotgrid_large_stats", pieces, ms); }
 
 int pf_plotgrid_members_header(pf_plotgrid* g, const char** line, uint64_t* nbytes) {
     return feed_members_header(g, "pf_plotgrid_members_header", line, nbytes);
@@ -1886,6 +1973,8 @@ int pf_kmerjoin_survey(pf_kmerjoin* j, const char* text, uint64_t nbytes, uint64
 }
 
 int pf_kmerjoin_members_begin(pf_kmerjoin* j, int header) { return feed_members_begin(j, "pf_kmerjoin_members_begin", header); }
+int pf_kmerjoin_set_large_members(pf_kmerjoin* j, int on, uint32_t piece_bytes) { return feed_set_large(j, "pf_kmerjoin_set_large_members", on, piece_bytes); }
+int pf_kmerjoin_large_stats(pf_kmerjoin* j, uint64_t* pieces, float* ms) { return feed_large_stats(j, "pf_kmerjoin_large_stats", pieces, ms); }
 
 int pf_kmerjoin_members_header(pf_kmerjoin* j, const char** line, uint64_t* nbytes) {
     return feed_members_header(j, "pf_kmerjoin_members_header", line, nbytes);
@@ -1963,7 +2052,7 @@ int pf_kmerjoin_stats(pf_kmerjoin* j, uint64_t stats[8], float ms[3]) {
         uint64_t misc[3] = {0, 0, 0};                          // rejects, err, unmatched
         HIPCHK(hipMemcpy(misc, j->d_misc.p, sizeof misc, hipMemcpyDeviceToHost));
         stats[0] = j->bytes_scanned; stats[1] = j->rows_written; stats[2] = j->raw_rows; stats[3] = j->feed.gz_members;
-        stats[4] = j->feed.gz_text_bytes; stats[5] = j->feed.dec.device_bytes(); stats[6] = misc[0]; stats[7] = misc[2];
+        stats[4] = j->feed.gz_text_bytes; stats[5] = j->feed.dec.device_bytes() + j->feed.lg.device_bytes(); stats[6] = misc[0]; stats[7] = misc[2];
     }
     if (ms) { ms[0] = j->survey_ms; ms[1] = j->write_ms; ms[2] = j->feed.gz_ms; }
     return PF_OK;
@@ -2223,6 +2312,8 @@ int pf_assocfilter_scan(pf_assocfilter* f, const char* text, uint64_t nbytes, ui
 }
 
 int pf_assocfilter_members_begin(pf_assocfilter* f, int header) { return feed_members_begin(f, "pf_assocfilter_members_begin", header); }
+int pf_assocfilter_set_large_members(pf_assocfilter* f, int on, uint32_t piece_bytes) { return feed_set_large(f, "pf_assocfilter_set_large_members", on, piece_bytes); }
+int pf_assocfilter_large_stats(pf_assocfilter* f, uint64_t* pieces, float* ms) { return feed_large_stats(f, "pf_assocfilter_large_stats", pieces, ms); }
 
 int pf_assocfilter_members_header(pf_assocfilter* f, const char** line, uint64_t* nbytes) {
     return feed_members_header(f, "pf_assocfilter_members_header", line, nbytes);
@@ -2257,7 +2348,7 @@ int pf_assocfilter_columns(pf_assocfilter* f, const uint32_t** class_bits, uint3
 
 int pf_assocfilter_stats(pf_assocfilter* f, uint64_t stats[4], float ms[2]) {
     if (!f) return fail(PF_ERR_ARG, "pf_assocfilter_stats: null argument");
-    if (stats) { stats[0] = f->bytes_scanned; stats[1] = f->feed.gz_members; stats[2] = f->feed.gz_text_bytes; stats[3] = f->feed.dec.device_bytes(); }
+    if (stats) { stats[0] = f->bytes_scanned; stats[1] = f->feed.gz_members; stats[2] = f->feed.gz_text_bytes; stats[3] = f->feed.dec.device_bytes() + f->feed.lg.device_bytes(); }
     if (ms) { ms[0] = f->device_ms; ms[1] = f->feed.gz_ms; }
     return PF_OK;
 }

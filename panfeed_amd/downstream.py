@@ -83,6 +83,14 @@ def _bgzf_file(path):
     return len(head) == 18 and head[:4] == BGZF_HEAD and head[12:16] == b"BC\x02\x00"
 
 
+def _gz_any_file(path):
+    """whether the file is a .gz of any RFC 1952 head (1f 8b 08): what the large-member route (large_members=True) tries"""
+    if not str(path).endswith(".gz"):
+        return False
+    with open(path, "rb") as fh:
+        return fh.read(3) == GZ_HEAD[:3]
+
+
 def pass_member_file(path, block_bytes, begin, call, after=None, reason=_last_error):
     """One pass over a file of gzip members through a device text feed (TextFeed, csrc/pf_rowfilter.hip): begin(), then
     blocks of the COMPRESSED file go to call(data, last) -> (compressed bytes used, whether the block was taken) as they
@@ -109,15 +117,16 @@ def pass_member_file(path, block_bytes, begin, call, after=None, reason=_last_er
                 return True
 
 
-def route_file(path, device_gunzip, members, host, counts, again=None, reason=_last_error):
+def route_file(path, device_gunzip, members, host, counts, again=None, reason=_last_error, large_members=False):
     """A file by the device gunzip route, members(), or through gzip as pandas reads it by the name, host(); -> what that
     returned.  device_gunzip=None tries members() for a .gz of a header the device decoder takes (plain, or BGZF) and, when it returns
     None -- a block was not taken --, runs again() (what the owner undoes before the file is read once more) and host();
     True tries members() whatever the file and raises NotTaken instead; False never tries.  `counts`: the owner's class,
-    whose device_gunzip_files or fallback_files moves."""
+    whose device_gunzip_files or fallback_files moves.  large_members: the owner's large-member route is on
+    (DeviceTable.set_large_members), so the automatic mode tries members() for a .gz of any gzip head."""
     auto = device_gunzip is None
     if auto:
-        device_gunzip = _gz_members_file(path) or _bgzf_file(path)
+        device_gunzip = _gz_members_file(path) or _bgzf_file(path) or (large_members and _gz_any_file(path))
     if device_gunzip:
         got = members()
         if got is not None:
@@ -142,11 +151,43 @@ class DeviceTable:
         self.L = _lib.load()
         self.h = C.c_void_p()
         self._create_fn, self._destroy_fn, self._begin_fn, self._header_fn = (getattr(self.L, name) for name in self.entry)
+        owner = self.entry[0][:-len("create")]
+        self._set_large_fn, self._large_stats_fn = getattr(self.L, owner + "set_large_members"), getattr(self.L, owner + "large_stats")
+        self.large_members, self.piece_bytes = False, 0
 
     def _create(self, *args):
-        """a fresh handle, create(*args, &handle), in place of the one there may be"""
+        """a fresh handle, create(*args, &handle), in place of the one there may be (the large-member switch stays as set)"""
         self.close()
         _lib.check(self._create_fn(*args, C.byref(self.h)))
+        if self.large_members:
+            _lib.check(self._set_large_fn(self.h, 1, self.piece_bytes))
+
+    def set_large_members(self, on, piece_bytes=0):
+        """the large-member gunzip route (csrc/pf_deflate.h: large_call) for this owner's members passes: off by default.
+        While on, what the small-member kernels do not take -- gzip's, pigz's and Python's whole-file members, 4 MiB zlib
+        members, any RFC 1952 head -- is inflated on the device too, parallel inside a member.  piece_bytes: the compressed
+        bytes between two places a block start is looked for from; 0: the default of 32 KiB, else at least 64"""
+        self.large_members, self.piece_bytes = bool(on), int(piece_bytes)
+        _lib.check(self._set_large_fn(self.h, 1 if on else 0, self.piece_bytes))
+
+    def large_stats(self):
+        """the large-member route so far (a fresh handle counts from zero): starts found, live pieces, starts dropped as false
+        or redundant, members taken, and the device time of its four passes"""
+        pieces, ms = (C.c_uint64 * 4)(), (C.c_float * 4)()
+        _lib.check(self._large_stats_fn(self.h, pieces, ms))
+        return {"pieces_found": int(pieces[0]), "pieces_live": int(pieces[1]), "pieces_dropped": int(pieces[2]),
+                "large_members": int(pieces[3]), "find_ms": float(ms[0]), "marker_ms": float(ms[1]), "chain_ms": float(ms[2]),
+                "bytes_ms": float(ms[3])}
+
+    def _large(self, large_members, piece_bytes=None):
+        """a file call's large_members / piece_bytes arguments: None leaves the switch (the piece) as set_large_members left
+        it, anything else sets it; -> whether the route is on"""
+        if large_members is not None or piece_bytes is not None:
+            on = self.large_members if large_members is None else bool(large_members)
+            piece = self.piece_bytes if piece_bytes is None else int(piece_bytes)
+            if (on, piece) != (self.large_members, self.piece_bytes):
+                self.set_large_members(on, piece)
+        return self.large_members
 
     def close(self):
         if self.h:
@@ -258,8 +299,10 @@ class RowFilter(DeviceTable):
     def _fell_back(self):
         self.fallbacks += 1
 
-    def filter_file(self, path, block_bytes=None, device_gunzip=None):
-        """(header line, matching data lines) of a TSV file.  A .gz file made of small members with the plain gzip header
+    def filter_file(self, path, block_bytes=None, device_gunzip=None, large_members=None, piece_bytes=None):
+        """(header line, matching data lines) of a TSV file.  large_members: True sends a .gz of any head through the
+        large-member route as well, False does not, None (the default) leaves the owner's switch as set_large_members set it;
+        piece_bytes likewise.  A .gz file made of small members with the plain gzip header
         (--gpu-compress writes such) is inflated on the device and scanned there, as device_gunzip says (route_file);
         block_bytes then counts compressed bytes.  Otherwise the file is read block by block straight into one buffer;
         what follows a block's last complete line is moved to the front for the next block."""
@@ -275,7 +318,7 @@ class RowFilter(DeviceTable):
                                       lambda buf: out.append(self._rows(buf, b, e, cnt)))
             return header, b"".join(out)
 
-        return route_file(path, device_gunzip, members, host, RowFilter, self._fell_back)
+        return route_file(path, device_gunzip, members, host, RowFilter, self._fell_back, large_members=self._large(large_members, piece_bytes))
 
 
 KJ_FLAG_NAMES = ((1, "not 10 tabs"), (2, "a control, non-ASCII or quote byte"), (4, "an integer field that is not canonical decimal"),
@@ -335,8 +378,9 @@ class KmerJoin(DeviceTable):
         return [{"rows": int(p[5 * i]), "unmatched": int(p[5 * i + 1]), "bytes": (int(p[5 * i + 2]), int(p[5 * i + 3])),
                  "flags": int(p[5 * i + 4])} for i in range(n.value)]
 
-    def survey_file(self, path, block_bytes=None, device_gunzip=None):
-        """one pass over kmers.tsv for all bunches: counters().  device_gunzip as RowFilter.filter_file's"""
+    def survey_file(self, path, block_bytes=None, device_gunzip=None, large_members=None, piece_bytes=None):
+        """one pass over kmers.tsv for all bunches: counters().  device_gunzip and large_members as RowFilter.filter_file's
+        (join_file reads the file the way the survey found for it, with the switch as the survey left it)"""
         def members():
             self.members[path] = self._members_pass(path, block_bytes, self.L.pf_kmerjoin_survey_members)
             return True if self.members[path] else None
@@ -347,7 +391,8 @@ class KmerJoin(DeviceTable):
 
         self.members[path] = False
         # (a survey that stopped half way has counted rows: they go before the file is read again)
-        route_file(path, device_gunzip, members, host, KmerJoin, lambda: _lib.check(self.L.pf_kmerjoin_reset_counters(self.h)))
+        route_file(path, device_gunzip, members, host, KmerJoin, lambda: _lib.check(self.L.pf_kmerjoin_reset_counters(self.h)),
+                   large_members=self._large(large_members, piece_bytes))
         return self.counters()
 
     def join_file(self, path, bunch, mode, write, block_bytes=None):
@@ -426,8 +471,8 @@ class AssocFilter(DeviceTable):
             self._take(out)
         return b"".join(out), int(used.value), bool(taken.value)
 
-    def filter_file(self, path, block_bytes=None, device_gunzip=None):
-        """the kept data lines of a table file, joined; columns() then speaks of the whole file.  device_gunzip as
+    def filter_file(self, path, block_bytes=None, device_gunzip=None, large_members=None, piece_bytes=None):
+        """the kept data lines of a table file, joined; columns() then speaks of the whole file.  device_gunzip and large_members as
         RowFilter.filter_file's (a pass that stopped half way has ORed classes in: the filter is made anew before the file
         is read again)"""
         args = (C.byref(C.c_uint64()),)
@@ -444,7 +489,8 @@ class AssocFilter(DeviceTable):
             self._plain_pass(path, block_bytes, self.L.pf_assocfilter_scan, args, lambda _block: self._take(out))
             return b"".join(out)
 
-        return route_file(path, device_gunzip, members, host, AssocFilter, lambda: self._create(*self.args))
+        return route_file(path, device_gunzip, members, host, AssocFilter, lambda: self._create(*self.args),
+                          large_members=self._large(large_members, piece_bytes))
 
 
 def assoc_header(line):
@@ -601,6 +647,9 @@ def _options(description, kmers):
     p.add_argument("--host-gunzip", action="store_true", default=False,
                    help="inflate .gz inputs on the host (by default files of small members, as --gpu-compress writes, and BGZF files, "
                         "as bgzip or --gpu-compress --bgzf write, are inflated on the GPU)")
+    p.add_argument("--gpu-gunzip-large", action="store_true", default=False,
+                   help="inflate every other .gz input on the GPU as well -- what gzip, pigz or --compress wrote: large members, "
+                        "decoded in parallel inside a member (off by default; --host-gunzip wins over it)")
     return p
 
 
@@ -626,7 +675,7 @@ def _device_scan(args, field, names):
     peeled it off)"""
     f = AssocFilter(field, len(names), args.threshold, device=args.device)
     try:
-        kept = f.filter_file(args.associations, device_gunzip=False if args.host_gunzip else None)
+        kept = f.filter_file(args.associations, device_gunzip=False if args.host_gunzip else None, large_members=getattr(args, "gpu_gunzip_large", False))
         cols = f.columns()
         AssocFilter.last_stats = f.stats()
         return kept, cols, f.header
@@ -681,7 +730,7 @@ def _filtered(keys, first_field, path, args):
     they are files it takes, unless --host-gunzip"""
     f = RowFilter(keys, first_field=first_field, device=args.device)
     try:
-        return f.filter_file(path, device_gunzip=False if args.host_gunzip else None)
+        return f.filter_file(path, device_gunzip=False if args.host_gunzip else None, large_members=getattr(args, "gpu_gunzip_large", False))
     finally:
         f.close()
 
@@ -782,7 +831,7 @@ def _device_join(args, b, bunch_keys):
     try:
         if args.gz_output is not None:
             join.set_gzip(True)
-        plan = join.survey_file(args.kmers, device_gunzip=False if args.host_gunzip else None)
+        plan = join.survey_file(args.kmers, device_gunzip=False if args.host_gunzip else None, large_members=getattr(args, "gpu_gunzip_large", False))
     except BaseException:
         join.close()
         raise

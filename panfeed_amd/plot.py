@@ -76,6 +76,9 @@ def get_options(argv=None):
     parser.add_argument("--host-gunzip", action="store_true", default=False,
                         help="inflate a .gz table on the host (by default a file of small members, as panfeed-get-kmers "
                              "--gz-output writes, or a bgzip'd file (BGZF) is inflated on the GPU)")
+    parser.add_argument("--gpu-gunzip-large", action="store_true", default=False,
+                        help="inflate any other .gz table on the GPU as well -- what gzip, pigz or --compress wrote: large members, "
+                             "decoded in parallel inside a member (off by default; --host-gunzip wins over it)")
     return parser.parse_args(argv)
 
 
@@ -219,11 +222,13 @@ class GridBuilder(DeviceTable):
         self.fallbacks += 1
         self._create(*self.args)
 
-    def scan_file(self, path, block_bytes=None, device_gunzip=None):
+    def scan_file(self, path, block_bytes=None, device_gunzip=None, large_members=None, piece_bytes=None):
         """The data lines of the annotated table into the grid.  A .gz made of small members with the plain gzip header is
         inflated on the device and scanned there, as device_gunzip says (downstream.route_file: None tries it for such a
         file and reads the file again through gzip when a block is not taken, True raises NotTaken then, False never
-        tries); block_bytes then counts compressed bytes.  Any other file is read block by block through the host."""
+        tries); block_bytes then counts compressed bytes.  Any other file is read block by block through the host.
+        large_members: True, the large-member route as well -- any .gz is tried on the device; None leaves the switch as
+        DeviceTable.set_large_members set it."""
         def members():                               # True, or None when a block was not taken
             return self._members_pass(path, block_bytes or BLOCK_BYTES // GZ_BLOCK_DIVISOR, self.L.pf_plotgrid_scan_members) or None
 
@@ -231,7 +236,7 @@ class GridBuilder(DeviceTable):
             self._plain_pass(path, block_bytes or BLOCK_BYTES, self.L.pf_plotgrid_scan)
             return True
 
-        route_file(path, device_gunzip, members, host, GridBuilder, self._fell_back)
+        route_file(path, device_gunzip, members, host, GridBuilder, self._fell_back, large_members=self._large(large_members, piece_bytes))
 
     def finish(self):
         nc, npv, nr = C.c_uint32(), C.c_uint64(), C.c_uint64()
@@ -338,11 +343,11 @@ def _figure(gene, key, cnt, ph, names, ids_of, mn, mx, threshold, minimum_pvalue
 
 
 def _figures(kmers, ph, columns, threshold=1, start=None, stop=None, minimum_pvalue=1e-10, nucleotides=False,
-             alpha=0, xticks=200, device=0, block_bytes=None, grid_budget=None, device_gunzip=None):
+             alpha=0, xticks=200, device=0, block_bytes=None, grid_budget=None, device_gunzip=None, large_members=False):
     strains = list(dict.fromkeys(ph.index))
     gb = GridBuilder(strains, columns, start, stop, device)
     try:
-        gb.scan_file(kmers, block_bytes, device_gunzip)
+        gb.scan_file(kmers, block_bytes, device_gunzip, large_members)
         gb.finish()
         gb.set_significance(significance_of(gb.pvalue_texts))
         ids_of = {s: i for i, s in enumerate(strains)}
@@ -378,7 +383,7 @@ def _figures(kmers, ph, columns, threshold=1, start=None, stop=None, minimum_pva
 
 def cluster_figures(kmers, phenotype, column="lrt-pvalue", threshold=1, start=None, stop=None, phenotype_column=None,
                     sample=None, minimum_pvalue=1e-10, nucleotides=False, alpha=0, xticks=200, device=0,
-                    block_bytes=None, grid_budget=None, device_gunzip=None):
+                    block_bytes=None, grid_budget=None, device_gunzip=None, large_members=False):
     """One ClusterFigure per cluster of the annotated table `kmers` (panfeed-get-kmers' output; a .gz of small members, as
     its --gz-output writes, is inflated on the GPU, any other .gz read through gzip: device_gunzip as
     GridBuilder.scan_file's) that has rows in the zoom, in sorted() order.  `phenotype` is the phenotype TSV's path.
@@ -386,7 +391,7 @@ def cluster_figures(kmers, phenotype, column="lrt-pvalue", threshold=1, start=No
     ph = read_phenotype(phenotype, phenotype_column, sample)
     columns = table_columns(kmers, column)
     yield from _figures(kmers, ph, columns, threshold, start, stop, minimum_pvalue, nucleotides, alpha, xticks, device,
-                        block_bytes, grid_budget, device_gunzip)
+                        block_bytes, grid_budget, device_gunzip, large_members)
 
 
 def _colormaps():
@@ -482,7 +487,7 @@ def plot(argv=None):
     cmap1, cmap2 = _colormaps()
     for fig in _figures(args.kmers, ph, columns, args.threshold, args.start, args.stop, args.minimum_pvalue,
                         args.nucleotides, args.alpha, args.xticks, args.device,
-                        device_gunzip=False if args.host_gunzip else None):
+                        device_gunzip=False if args.host_gunzip else None, large_members=getattr(args, "gpu_gunzip_large", False)):
         render(fig, args, cmap1, cmap2)
     render_legend(args, cmap2)
     return 0
