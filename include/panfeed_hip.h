@@ -637,7 +637,8 @@ int pf_gzip_members(const char* data, uint64_t n, int level, uint64_t chunk_byte
  * deflate block -- stored, fixed or dynamic Huffman, the smallest by exact bit count -- with matches found through a
  * hash table in LDS (one candidate per position, greedy parse, no match reaching before its chunk), its CRC32 computed on
  * the device.  Any gzip reader gets back exactly the text; the same text gives the same bytes on every run.
- * flags: 0 is the product setting; the others are test hooks.
+ * flags: 0 is the product setting and PF_GZ_DEEP the product's second effort level; FIXED_ONLY, DYNAMIC_ONLY and
+ * LITERALS_ONLY are test hooks.
  */
 #define PF_GZ_FIXED_ONLY 1u     /* every block with the fixed codes */
 #define PF_GZ_DYNAMIC_ONLY 2u   /* every block with dynamic codes */
@@ -647,6 +648,16 @@ int pf_gzip_members(const char* data, uint64_t n, int level, uint64_t chunk_byte
  * framed members.  The 28-byte end-of-file member is the file writer's to append.  Taken by pf_gzip_device[_segments],
  * pf_gzip_host_model[_segments] and pf_set_device_gzip; pf_kmerjoin_set_gzip refuses it. */
 #define PF_GZ_BGZF 8u
+/* Not a test hook: the second effort level (`--gpu-compress-level 2`).  Same container, same cuts, same decoders; the
+ * match search looks further.  Beside the hash table's candidate every position tries the same column of the row before
+ * it -- the position as far behind the previous line's start as it is behind its own line's, if that lies before the
+ * previous line's end; only the chunk's own bytes are looked at -- and takes the longer of the two matches (on a tie the
+ * nearer), a 3-byte one only within 4 096 bytes, so length symbol 257 may appear.  The parse is lazy by one step: a match
+ * is put off for one literal when the next position's match is longer.  The rule depends on the chunk's text alone: the
+ * same text gives the same bytes.  PF_GZ_LITERALS_ONLY wins over it; it combines with the other flags.  Smaller files
+ * for more encoder time: measured in profiles/gzip_deep/.  Taken by pf_gzip_device[_segments],
+ * pf_gzip_host_model[_segments], pf_set_device_gzip and pf_kmerjoin_set_gzip. */
+#define PF_GZ_DEEP 16u
 uint32_t pf_gzip_device_chunk_bytes(void);
 /* Host text in, members out (malloc'd: pf_free_text): uploaded, encoded on the GPU, copied back.  n == 0 gives
  * *out_n == 0.  For tests, tools and text rendered on the host. */

@@ -174,6 +174,17 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_create", "pf_de
 RENDER_NO_PATTERN_ROWS = 1
 GZ_FIXED_ONLY, GZ_DYNAMIC_ONLY, GZ_LITERALS_ONLY = 1, 2, 4     # pf_gzip_device / pf_set_device_gzip test hooks; 0: the product
 GZ_BGZF = 8                                                    # PF_GZ_BGZF: the members leave as BGZF members (no test hook)
+GZ_DEEP = 16                                                   # PF_GZ_DEEP: the second effort level (no test hook)
+GZ_LEVELS = {1: 0, 2: GZ_DEEP}                                 # device_gzip_level -> flags
+
+
+def gzip_level_flags(level):
+    """the encoder flags of a device gzip level (`--gpu-compress-level`, `--gz-level`): 1 or 2, anything else ValueError"""
+    if isinstance(level, bool) or level not in GZ_LEVELS:
+        raise ValueError(f"device_gzip_level is 1 or 2, not {level!r}")
+    return GZ_LEVELS[level]
+
+
 GET_CTX = C.CFUNCTYPE(C.c_void_p, C.c_void_p)     # pf_pangenome_open_device_cb: the context, when the first genome needs it
 ERR_ARG, ERR_OOM, ERR_HIP, ERR_CAPACITY, ERR_STATE = -1, -2, -3, -4, -5
 

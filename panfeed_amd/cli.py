@@ -4,7 +4,8 @@ on N of them.
 Option names, short forms, defaults and meanings are the reference's (`__main__.py:86-222`); so are the refusals, their
 order and their exit status (`__main__.py:234-242`, `input.py:213-216`).  The run itself is `pipeline.run_files`: the
 native reader, the GPU, a writer thread.  Options added: `--device` (as the downstream tools have),
-`--batch-clusters`, `--gpu-compress` and, for `--multiple-files`, `--gpu-compress-clusters`.  `--cores` and `-ql/--queue-limit` are accepted and change nothing (the GPU takes the place of the
+`--batch-clusters`, `--gpu-compress` and, for `--multiple-files`, `--gpu-compress-clusters`, with `--gpu-compress-level`
+for the encoder's effort behind either.  `--cores` and `-ql/--queue-limit` are accepted and change nothing (the GPU takes the place of the
 worker processes).  One refusal is new: `-k` outside 1..PF_MAX_K, before any file is read or the GPU touched.
 
 Unlike the reference, no `<output>/fastas/` directory is made (the reader splits the GFFs' `##FASTA` sections in
@@ -76,6 +77,10 @@ def get_options(argv=None):
                         "read and write (not with --multiple-files or on several GPUs)")
     p.add_argument("--gpu-compress-clusters", action="store_true", default=False,
                    help="with --multiple-files: gzip the per-cluster files on the GPU; implies --compress")
+    p.add_argument("--gpu-compress-level", type=int, choices=(1, 2), default=None,
+                   help="with --gpu-compress or --gpu-compress-clusters: the effort of the GPU's encoder (default: 1); 2 looks "
+                        "for each position's match in the row before as well and parses lazily -- smaller files, "
+                        "hashes_to_patterns.tsv most of all, for more encoder time; also under --bgzf and --gpus N")
     p.add_argument("--passing-hashes", metavar="FILE", default=None,
                    help="write only the kmers.tsv rows of passing patterns: those whose (cluster, k-mer) kmers_to_hashes.tsv "
                         "lists with one of the hashed_pattern values of FILE (one per line); decided on the GPU before a "
@@ -190,6 +195,10 @@ def main(argv=None, run=None, launch=None, rank_entry=None, associations=None):
         logger.error("--gpu-compress-clusters is for the per-cluster files of --multiple-files; --gpu-compress compresses the "
                      "one set of files on the GPU")
         return 2
+    if args.gpu_compress_level is not None and not (args.gpu_compress or args.gpu_compress_clusters):
+        logger.error("--gpu-compress-level sets the effort of the GPU's encoder: give --gpu-compress or "
+                     "--gpu-compress-clusters with it")
+        return 2
     if args.bgzf:
         if not args.gpu_compress:
             logger.error("--bgzf frames the members --gpu-compress makes: give --gpu-compress with it")
@@ -247,6 +256,8 @@ def main(argv=None, run=None, launch=None, rank_entry=None, associations=None):
         more["device_gzip_clusters"] = True
     if args.bgzf:
         more["bgzf"] = True
+    if args.gpu_compress_level is not None:        # (not given: the default of run_files and run_files_sharded, 1)
+        more["device_gzip_level"] = args.gpu_compress_level
     if passing_on:
         if args.passing_hashes is not None:
             logger.debug(f"Reading passing hashes ({args.passing_hashes})")

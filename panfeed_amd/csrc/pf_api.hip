@@ -310,7 +310,7 @@ struct PatternRows {
     std::vector<uint64_t> cut;                // slice i holds rows [cut[i], cut[i + 1])
 };
 int gz_check_flags(uint32_t flags, const char* who) {
-    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY | PF_GZ_BGZF)) return fail(PF_ERR_ARG, "%s: unknown flag", who);
+    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY | PF_GZ_BGZF | PF_GZ_DEEP)) return fail(PF_ERR_ARG, "%s: unknown flag", who);
     return PF_OK;
 }
 

@@ -309,15 +309,82 @@ PF_HD uint32_t hash4(uint32_t w) { return (w * 2654435761u) >> (32 - HASH_BITS);
 // emitted (tests/test_deflate_host_model.py checks both).  The clause is what a candidate from any other source would need.
 PF_HD bool match_ok(uint32_t len, uint32_t dist) { return len >= 4 || (len == 3 && dist <= 4096); }
 
+// ---- the deeper search (PF_GZ_DEEP), written once for the kernel and the host model.  It depends on the chunk's text alone.
+// A position p has up to two candidates.  A is the hash table's, as without the flag (the kernel's and the host model's
+// tables differ, as they do there).  B is the same column of the row before: with s = 1 + the last '\n' before p (0: none,
+// and then no B) and r = 1 + the last '\n' before s - 1 (0: none), B = r + (p - s), taken only if it lies before the
+// previous row's '\n', B < s - 1.  A chunk that starts inside a row gets a misaligned B for its second row, no more.
+// These texts' rows repeat the row before them column by column, and A is usually a "0\t0\t" a few bytes back.
+PF_HD uint32_t match_run(const uint8_t* text, uint32_t c, uint32_t p, uint32_t maxl) {      // c < p, p + maxl within the text
+    uint32_t l = 0;
+    while (l + 4 <= maxl) {
+        uint32_t x, y;
+        __builtin_memcpy(&x, text + c + l, 4);
+        __builtin_memcpy(&y, text + p + l, 4);
+        if (x != y) break;
+        l += 4;
+    }
+    while (l < maxl && text[c + l] == text[p + l]) l++;
+    return l;
+}
+PF_HD bool row_candidate(uint32_t p, uint32_t s, uint32_t r, uint32_t* b) {
+    if (!s) return false;
+    *b = r + (p - s);
+    return *b + 1 < s;
+}
+// L(p), D(p): both candidates extended to MAX_MATCH, the longer taken, on a tie the nearer, accepted through match_ok --
+// B agrees in any number of bytes, so the 3-byte clause is reachable here.  cand_a: 1 + A, or 0 for none.  Defined for
+// every p < n, covered by a match or not.  *len == 0: no match.
+PF_HD void deep_length(const uint8_t* text, uint32_t n, uint32_t p, uint32_t cand_a, uint32_t s, uint32_t r, uint32_t* len, uint32_t* dist) {
+    const uint32_t maxl = n - p < MAX_MATCH ? n - p : MAX_MATCH;
+    uint32_t l = 0, d = 0, b = 0;
+    if (cand_a) { l = match_run(text, cand_a - 1, p, maxl); d = p - (cand_a - 1); }
+    if (row_candidate(p, s, r, &b) && b + 1 != cand_a) {
+        const uint32_t lb = match_run(text, b, p, maxl), db = p - b;
+        if (lb > l || (lb == l && db < d)) { l = lb; d = db; }
+    }
+    const bool ok = match_ok(l, d);
+    *len = ok ? l : 0; *dist = ok ? d : 0;
+}
+// the parse at a token start q with L(q) > 0: one literal in place of the match when the next position's match is longer
+PF_HD bool deep_defers(uint32_t len_q, uint32_t len_next) { return len_next > len_q; }
+
 // ---- the serial host model: same chunking, same coder, one candidate per position from a hash table of the positions
-// seen so far, greedy parse
+// seen so far, greedy parse; under PF_GZ_DEEP the rule above, with that table's candidate as A
 inline void host_model_chunk(const uint8_t* text, uint32_t n, uint32_t flags, std::vector<uint8_t>& out) {
     std::vector<uint32_t> head(1u << HASH_BITS, 0), tokens;
     uint32_t ll_hist[288] = {0}, d_hist[32] = {0};
     auto insert = [&](uint32_t p) {
         if (p + 3 < n) head[hash4(text[p] | text[p + 1] << 8 | text[p + 2] << 16 | (uint32_t)text[p + 3] << 24)] = p + 1;
     };
-    for (uint32_t p = 0; p < n;) {
+    const bool deep = (flags & PF_GZ_DEEP) && !(flags & PF_GZ_LITERALS_ONLY);
+    if (deep) {
+        // candidate A of every position (the last position before it with its hash: every position is inserted, so the
+        // table's state does not depend on the parse) and its row starts, then the lazy parse over L(p), D(p)
+        std::vector<uint32_t> cand(n, 0), rs(n), rr(n);
+        for (uint32_t p = 0, s = 0, r = 0; p < n; p++) {
+            if (p + 3 < n) {
+                uint32_t& e = head[hash4(text[p] | text[p + 1] << 8 | text[p + 2] << 16 | (uint32_t)text[p + 3] << 24)];
+                cand[p] = e; e = p + 1;
+            }
+            rs[p] = s; rr[p] = r;
+            if (text[p] == '\n') { r = s; s = p + 1; }
+        }
+        for (uint32_t q = 0; q < n;) {
+            uint32_t len, dist, len1 = 0, dist1;
+            deep_length(text, n, q, cand[q], rs[q], rr[q], &len, &dist);
+            if (len && q + 1 < n) deep_length(text, n, q + 1, cand[q + 1], rs[q + 1], rr[q + 1], &len1, &dist1);
+            if (len && !deep_defers(len, len1)) {
+                uint32_t eb, ev;
+                tokens.push_back(match_token(len, dist));
+                ll_hist[len_sym(len, &eb, &ev)]++; d_hist[dist_sym(dist - 1, &eb, &ev)]++;
+                q += len;
+            } else {
+                tokens.push_back(text[q]); ll_hist[text[q]]++;
+                q++;
+            }
+        }
+    } else for (uint32_t p = 0; p < n;) {         // level 1, or no match at all (PF_GZ_LITERALS_ONLY)
         uint32_t len = 0, dist = 0;
         if (p + 3 < n && !(flags & PF_GZ_LITERALS_ONLY)) {
             const uint32_t cand = head[hash4(text[p] | text[p + 1] << 8 | text[p + 2] << 16 | (uint32_t)text[p + 3] << 24)];

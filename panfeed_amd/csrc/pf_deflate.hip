@@ -13,6 +13,9 @@
 // the exact sizes of the three block types, and places the tokens' bits by wave prefix sums into a staging area that
 // takes the place of the text and the table; the member leaves LDS in whole words.
 // LDS: 48 KiB of text + table, 10 KiB of tables -- under 64 KiB, two workgroups per CU within its 160 KiB.
+// Under PF_GZ_DEEP the kernel's second instantiation runs: a second candidate from the row before and a parse that is
+// lazy by one step (the rule: pf_deflate.h; how the kernel finds the row starts and the next step's first length: the
+// comment in front of the kernel).
 // gz_scan_kernel / gz_gather_kernel: the member sizes summed from an append cursor, the offset of every segment's first
 // member noted behind the cursor, the members copied from their worst-case slots to their places, contiguous, so that one
 // copy takes them to the host.  Under PF_GZ_BGZF these two also make every member a BGZF member, 8 bytes of head longer.
@@ -65,8 +68,26 @@ __device__ inline void rank_sort(const uint32_t* hist, uint32_t nsym, SymFreq* s
     }
 }
 
+// the last two set bits of `m`, whose bit 0 is position `base`, pushed onto (s, r) = 1 + the last and the second-to-last
+// '\n' seen so far (0: none)
+__device__ inline void push_newlines(uint64_t m, uint32_t base, uint32_t* s, uint32_t* r) {
+    if (!m) return;
+    const uint32_t top = 63u - (uint32_t)__builtin_clzll(m);
+    const uint64_t rest = m ^ (1ull << top);
+    *r = rest ? base + (63u - (uint32_t)__builtin_clzll(rest)) + 1 : *s;
+    *s = base + top + 1;
+}
+
+// DEEP: the PF_GZ_DEEP variant (pf_deflate.h: deep_length, deep_defers); the plain instantiation keeps its code.
+// Row starts: every wave's ballot of "my byte is '\n'" goes into LDS, four 64-bit words a step, and a lane reads its row
+// start and the one before from the bits below its own, or from the last two newlines of the earlier steps, carried in
+// registers -- no list of newline positions is kept.  The deferral asks for L(q + 1) at a token start q; where q is a
+// step's last position the walking lane works that one length out itself: the table then holds exactly the candidates of
+// the next step's first position, whose row starts are the carry.  The next step computes the same value again.
+template <bool DEEP>
 __global__ __launch_bounds__(THREADS, 2) void gz_encode_kernel(EncParams P) {
     __shared__ uint32_t s_buf[TEXT_WORDS + TAB_WORDS];       // the text, the hash table; later the member's staging
+    __shared__ uint64_t s_nl[DEEP ? THREADS / 64 : 1];
     __shared__ uint16_t s_mlen[2][THREADS], s_mdist[2][THREADS], s_tokpos[2][THREADS];
     __shared__ uint32_t s_cnt[2], s_carry, s_nused[2], s_bits[3], s_wsum[2][4];
     __shared__ uint32_t s_ll_hist[288], s_d_hist[32];
@@ -110,9 +131,14 @@ __global__ __launch_bounds__(THREADS, 2) void gz_encode_kernel(EncParams P) {
 
         // ---- matches and the greedy parse, 256 positions a step
         uint32_t ntok = 0;
+        uint32_t nl1 = 0, nl2 = 0;                            // DEEP: 1 + the last and the second-to-last '\n' before the step
         for (uint32_t s0 = 0, par = 0; s0 < n; s0 += THREADS, par ^= 1) {
             const uint32_t p = s0 + tid;
             uint32_t L = 0, D = 0, cand = 0;
+            if constexpr (DEEP) {
+                const uint64_t m = __ballot(p < n && s_text[p] == '\n');
+                if (lane == 0) s_nl[wave] = m;                // (read behind the barriers of the table's groups)
+            }
             const bool hashed = p + 3 < n;
             const uint32_t h = hashed ? hash4(load4(s_text + p)) : 0;
             // look up, then insert, eight positions at a time in text order: a group's candidates are the positions of
@@ -133,7 +159,14 @@ __global__ __launch_bounds__(THREADS, 2) void gz_encode_kernel(EncParams P) {
                     }
                 __syncthreads();
             }
-            if (cand && p >= s_carry && !lit_only) {          // (a position inside the match carried in needs none)
+            uint32_t row = nl1, prev = nl2;                   // DEEP: s(p), r(p); then the carry of the next step
+            if constexpr (DEEP) {
+                for (uint32_t w = 0; w < wave; w++) push_newlines(s_nl[w], s0 + 64 * w, &row, &prev);
+                push_newlines(s_nl[wave] & ((1ull << lane) - 1), s0 + 64 * wave, &row, &prev);
+                if (p < n && p >= s_carry && !lit_only) deep_length(s_text, n, p, cand, row, prev, &L, &D);
+                for (uint32_t w = 0; w < THREADS / 64; w++) push_newlines(s_nl[w], s0 + 64 * w, &nl1, &nl2);
+            }
+            if (!DEEP && cand && p >= s_carry && !lit_only) { // (a position inside the match carried in needs none)
                 const uint32_t c = cand - 1, maxl = min(MAX_MATCH, n - p);
                 uint32_t l = 0;
                 while (l + 4 <= maxl && load4(s_text + c + l) == load4(s_text + p + l)) l += 4;
@@ -146,7 +179,18 @@ __global__ __launch_bounds__(THREADS, 2) void gz_encode_kernel(EncParams P) {
                 const uint32_t end = min(s0 + THREADS, n);
                 uint32_t q = max(s0, s_carry), cnt = 0;
                 while (q < end) {
-                    const uint32_t l = s_mlen[par][q - s0];
+                    uint32_t l = s_mlen[par][q - s0];
+                    if constexpr (DEEP) {
+                        if (l && q + 1 < n) {
+                            uint32_t l1, d1;
+                            if (q + 1 < end) l1 = s_mlen[par][q + 1 - s0];
+                            else {
+                                const uint32_t a = q + 4 < n ? __hip_atomic_load(&s_tab[hash4(load4(s_text + q + 1))], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
+                                deep_length(s_text, n, q + 1, a, nl1, nl2, &l1, &d1);
+                            }
+                            if (deep_defers(l, l1)) s_mlen[par][q - s0] = (uint16_t)(l = 0);      // (a literal; behind the walk)
+                        }
+                    }
                     s_tokpos[par][cnt++] = (uint16_t)(q - s0);
                     q += l ? l : 1;
                 }
@@ -589,7 +633,8 @@ int PfGzEncoder::encode_segments(hipStream_t st, Cursor w, const char* text, uin
         const uint32_t first0 = c0 == 0 || plan[c0 - 1].segment != plan[c0].segment;
         pfgz::EncParams P{reinterpret_cast<const uint8_t*>(text), dplan + c0, nch, flags, slots.as<uint8_t>(), sizes.as<uint32_t>(),
                           tokens.as<uint32_t>()};
-        hipLaunchKernelGGL(pfgz::gz_encode_kernel, dim3(std::min(nch, grid_cap)), dim3(pfgz::THREADS), 0, st, P);
+        if (flags & PF_GZ_DEEP) hipLaunchKernelGGL(pfgz::gz_encode_kernel<true>, dim3(std::min(nch, grid_cap)), dim3(pfgz::THREADS), 0, st, P);
+        else hipLaunchKernelGGL(pfgz::gz_encode_kernel<false>, dim3(std::min(nch, grid_cap)), dim3(pfgz::THREADS), 0, st, P);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(pfgz::gz_scan_kernel, dim3(1), dim3(pfgz::THREADS), 0, st, sizes.as<uint32_t>(), dplan + c0, nch, first0,
                            offs.as<uint64_t>(), cursor, seg_first, frame);

@@ -2030,7 +2030,7 @@ int pf_kmerjoin_next_text(pf_kmerjoin* j, const char** piece, uint64_t* nbytes) 
 
 int pf_kmerjoin_set_gzip(pf_kmerjoin* j, int on, uint32_t flags) {
     if (!j) return fail(PF_ERR_ARG, "pf_kmerjoin_set_gzip: null argument");
-    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY)) return fail(PF_ERR_ARG, "pf_kmerjoin_set_gzip: unknown flag");
+    if (flags & ~(PF_GZ_FIXED_ONLY | PF_GZ_DYNAMIC_ONLY | PF_GZ_LITERALS_ONLY | PF_GZ_DEEP)) return fail(PF_ERR_ARG, "pf_kmerjoin_set_gzip: unknown flag");
     kj_reset_out(j);                              // (a text half handed out would change its kind)
     j->gz_on = on != 0; j->gz_flags = flags;
     return PF_OK;

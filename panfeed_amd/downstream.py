@@ -368,7 +368,7 @@ class KmerJoin(DeviceTable):
 
     def set_gzip(self, on, flags=0):
         """while on, join_file's write() gets gzip members of the annotated rows (modes 0 and 1; KJ_RAW stays text).  flags:
-        the device encoder's test hooks (_lib.GZ_*)"""
+        the device encoder's effort (_lib.GZ_DEEP) and test hooks (_lib.GZ_*)"""
         _lib.check(self.L.pf_kmerjoin_set_gzip(self.h, 1 if on else 0, int(flags)))
 
     def counters(self):
@@ -639,6 +639,9 @@ def _options(description, kmers):
         p.add_argument("--gz-output", default=None, metavar="PATH",
                        help="write the annotated table to PATH (ending in .gz) as small gzip members, compressed on the GPU where "
                             "the GPU wrote the rows, in place of printing it; panfeed-plot inflates such a file on the GPU")
+        p.add_argument("--gz-level", type=int, choices=(1, 2), default=None,
+                       help="with --gz-output: the effort of the GPU's encoder (default: 1); 2 looks for each position's match "
+                            "in the row before as well and parses lazily: a smaller file for more encoder time")
     p.add_argument("--host-associations", action="store_true", default=False,
                    help="read the whole associations table with pandas (by default the GPU keeps the lines that may pass the "
                         "threshold and pandas reads those)")
@@ -759,6 +762,8 @@ def get_kmers(argv=None, out=None):
     args = parser.parse_args(argv)
     if args.gz_output is not None and not args.gz_output.endswith(".gz"):
         parser.error("--gz-output: the path must end in .gz (the downstream tools choose the device route by that suffix)")
+    if args.gz_level is not None and args.gz_output is None:
+        parser.error("--gz-level sets the effort of the encoder behind --gz-output: give --gz-output with it")
     a, passing = _associations(args, index_name="hashed_pattern")
     header, rows = _filtered(passing, False, args.kmers_to_hashes, args)
     h = _table(header, rows).set_index("hashed_pattern")
@@ -830,7 +835,7 @@ def _device_join(args, b, bunch_keys):
                     device=args.device)
     try:
         if args.gz_output is not None:
-            join.set_gzip(True)
+            join.set_gzip(True, _lib.gzip_level_flags(1 if getattr(args, "gz_level", None) is None else args.gz_level))
         plan = join.survey_file(args.kmers, device_gunzip=False if args.host_gunzip else None, large_members=getattr(args, "gpu_gunzip_large", False))
     except BaseException:
         join.close()

@@ -257,7 +257,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
               patfilt=True, maf=0.01, upstream=0, downstream=0, downstream_start_codon=False, targets=(), genes=None,
               compress=False, multiple_files=False, batch_clusters=256, resident=True, device_text=True, device=0,
               max_items=0, pattern_capacity=0, overlap=True, one_pass=True, raise_missing=False, device_gzip=False,
-              targets_text_budget=None, device_gzip_clusters=False, bgzf=False, passing_hashes=None):
+              targets_text_budget=None, device_gzip_clusters=False, bgzf=False, passing_hashes=None, device_gzip_level=1):
     """One directory of outputs (`kmers.tsv`, `kmers_to_hashes.tsv`, `hashes_to_patterns.tsv`, `.gz` under
     `compress`; under `multiple_files` one such directory per gene cluster, `<output>/<cluster>/`, the pattern set
     starting empty in each: `panfeed.py:35-43,153-167`) from a panaroo table and a directory (or file of files) of GFFs.  Option names and meaning follow
@@ -276,6 +276,10 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
     bgzf (`--bgzf`, with device_gzip, not for multiple_files: ValueError): the three files are BGZF -- the GPU's members
     leave it as BGZF members, host text is written in BGZF members of at most 65 280 bytes, every file ends with the
     end-of-file member; htslib's readers take them, and so does the device gunzip route of the downstream tools.
+    device_gzip_level (`--gpu-compress-level`; 1 or 2, else ValueError): the effort of the GPU's encoder wherever
+    device_gzip or device_gzip_clusters has it compress, BGZF included -- 2 (PF_GZ_DEEP) also tries the same column of the
+    row before and parses lazily: smaller files, hashes_to_patterns.tsv most of all, for more encoder time
+    (profiles/gzip_deep/).  Without either switch it changes nothing.
     targets_text_budget: device memory a batch's kmers.tsv text may take (default: the engine's).
     passing_hashes (`--passing-hashes` / `--passing-associations`; None: off): an iterable of `hashed_pattern` strings or
     16-byte digests -- kmers.tsv holds only the rows whose (cluster, k-mer) kmers_to_hashes.tsv lists with one of them,
@@ -285,6 +289,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
     run = _FileRun(output, compress, multiple_files, device_gzip, device_gzip_clusters, bgzf)
     if run.bgzf and not run.device_gzip:
         raise ValueError("bgzf is for device_gzip without multiple_files")
+    gzip_flags = _lib.gzip_level_flags(device_gzip_level)
     err = existing_output_error(output)
     if err is not None:
         raise err
@@ -295,6 +300,7 @@ def run_files(presence_absence, gffdir, output, fastadir=None, klength=31, canon
                                     multiple_files=multiple_files, stroi=set(targets), device=device,
                                     pattern_capacity=pattern_capacity, device_gzip=run.device_gzip,
                                     device_gzip_clusters=run.device_gzip_clusters, bgzf=run.bgzf,
+                                    device_gzip_flags=gzip_flags,
                                     **({} if passing_hashes is None else {"passing_hashes": list(passing_hashes)}),
                                     **({} if targets_text_budget is None else {"targets_text_budget": targets_text_budget}))
     open_reader = functools.partial(Pangenome, presence_absence, gffdir, fastadir, upstream, downstream,

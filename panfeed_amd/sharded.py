@@ -194,11 +194,12 @@ def run_records_sharded(records, output, strains, rank, world, dist=None, device
                         consider_missing=False, patfilt=True, maf=0.01, targets=(), compress=False,
                         multiple_files=False, batch_clusters=256, weights=None, method="owner", gpu=0,
                         max_items=0, pattern_capacity=0, dedup=True, device_gzip=False, targets_text_budget=None,
-                        device_gzip_clusters=False):
+                        device_gzip_clusters=False, device_gzip_level=1):
     """One rank of a sharded run over in-memory reference-shaped records (the tuples input.py:468 yields; every rank
     is given the same list).  Returns a dict of counters; the files are complete once rank 0 returns.  device_gzip,
-    device_gzip_clusters, targets_text_budget: as in `run_files_sharded`; where either is given the batches' texts are written on the device
+    device_gzip_clusters, device_gzip_level, targets_text_budget: as in `run_files_sharded`; where either is given the batches' texts are written on the device
     (the members and the ranges are the device's), else by the host renderers as before."""
+    from . import _lib
     from .distributed import shard_range
     from .engine import Engine
     _bind_device(device)
@@ -209,7 +210,8 @@ def run_records_sharded(records, output, strains, rank, world, dist=None, device
     eng = Engine(klength=klength, canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
                  multiple_files=multiple_files, max_strains=(max_strains + 31) // 32 * 32, stroi=set(targets) if targets else (),
                  device=gpu, max_items=max_items, pattern_capacity=pattern_capacity, dedup=dedup, device_gzip=device_gzip,
-                 device_gzip_clusters=device_gzip_clusters, **_budget(targets_text_budget))
+                 device_gzip_clusters=device_gzip_clusters, device_gzip_flags=_lib.gzip_level_flags(device_gzip_level),
+                 **_budget(targets_text_budget))
     try:
         eng.next_ordinal = start                          # global ordinals: first_seen is unique over the run
         batches = functools.partial(eng.run_stream, records[start:stop], batch_clusters=batch_clusters,
@@ -226,7 +228,7 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
                       downstream_start_codon=False, targets=(), genes=None, compress=False, multiple_files=False,
                       batch_clusters=256, resident=True, device_text=True, method="owner", gpu=0, max_items=0,
                       pattern_capacity=0, device_gzip=False, raise_missing=False, targets_text_budget=None,
-                      device_gzip_clusters=False):
+                      device_gzip_clusters=False, device_gzip_level=1):
     """`pipeline.run_files` on N GPUs: every rank opens the pangenome, takes its range of the processing order
     (balanced by the number of gene entries per table row) and writes its parts; rank 0 assembles.  Option names as
     in the reference's CLI (`__main__.py:86-186`).
@@ -234,16 +236,20 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
     assembled files are ones the device decoder takes (under `multiple_files` the host's gzip stays, as on one GPU).
     device_gzip_clusters (`--gpu-compress-clusters`): with `multiple_files`, the per-cluster files compressed on each
     rank's GPU, as in `pipeline.run_files`; implies `compress`.
+    device_gzip_level (`--gpu-compress-level`; 1 or 2, else ValueError): the effort of every rank's encoder, as in
+    `pipeline.run_files`.
     raise_missing (`--stop-on-missing`): the reader's; a rank that fails in its shard makes every rank fail before the
     pattern exchange, `.parts/` is removed, and so is the output directory where that leaves it empty (under
     `multiple_files` the clusters written until then stay, and the directory with them).  targets_text_budget: device memory a batch's kmers.tsv text may take (default: the engine's) --
     the rows go into the rank's part range by range as they leave the device, never as one text."""
     from .distributed import shard_range
     from .native_input import Pangenome
+    from . import _lib
     from .pipeline import _peek_n_strains, existing_output_error, settle_context, sized_engine
     _bind_device(device)
     targets = tuple(targets or ())
     compress, device_gzip, device_gzip_clusters = gzip_modes(compress, device_gzip, multiple_files, device_gzip_clusters)
+    gzip_flags = _lib.gzip_level_flags(device_gzip_level)
     err = existing_output_error(output)
     _barrier(dist, device)                                        # every rank has looked before rank 0 creates it
     if err is not None:
@@ -255,7 +261,8 @@ def run_files_sharded(presence_absence, gffdir, output, rank, world, dist=None, 
                                     canon=canon, consider_missing=consider_missing, patfilt=patfilt, maf=maf,
                                     multiple_files=multiple_files, stroi=set(targets), device=gpu,
                                     pattern_capacity=pattern_capacity, device_gzip=device_gzip,
-                                    device_gzip_clusters=device_gzip_clusters, **_budget(targets_text_budget))
+                                    device_gzip_clusters=device_gzip_clusters, device_gzip_flags=gzip_flags,
+                                    **_budget(targets_text_budget))
     open_reader = functools.partial(Pangenome, presence_absence, gffdir, fastadir, upstream, downstream,
                                     downstream_start_codon, targets=targets, genes=genes, raise_missing=raise_missing)
     # every rank reads every genome (a cluster's sequences come from all of them): with resident genomes the files go to

@@ -4,6 +4,7 @@
 // It runs the device encoder's host model (csrc/pf_deflate.h: the format functions the kernel uses too) and the host
 // path's pf_gzip_members (csrc/pf_gzip.cpp) over the edge cases of tests/deflate_cases.py (cases 1-9, generated here),
 // under every flag set that applies, and inflates every result with zlib: it must be the input.  Exit status 0: all equal.
+// Every case also runs under PF_GZ_DEEP (the second candidate and the lazy parse); case 11 is texts of rows for it.
 // Case 10 is the segmented container (chunk_plan, host_model_segments) over the segment shapes of tests/deflate_segments.py.
 // The cases that are built in Python only (wide_tokens, whose widest tokens put_bits writes into three words, and the
 // fibonacci text that reaches the code length limit) come from a file, given as the one argument:
@@ -134,7 +135,8 @@ bool check_file(const char* path) {
 }  // namespace
 
 int main(int argc, char** argv) {
-    const uint32_t C = pfgz::CHUNK, ALL[3] = {0, PF_GZ_FIXED_ONLY, PF_GZ_DYNAMIC_ONLY};
+    const uint32_t C = pfgz::CHUNK, ALL[6] = {0, PF_GZ_FIXED_ONLY, PF_GZ_DYNAMIC_ONLY, PF_GZ_DEEP, PF_GZ_DEEP | PF_GZ_FIXED_ONLY,
+                                              PF_GZ_DEEP | PF_GZ_DYNAMIC_ONLY};
     auto all = [&](const std::string& name, const Bytes& d) { for (uint32_t f : ALL) check(name, d, f); };
     for (size_t n = 0; n <= 4; n++) all("short", Bytes(n, 'q'));                                  // 1
     Bytes every(512);
@@ -195,6 +197,24 @@ int main(int argc, char** argv) {
             for (uint32_t f : {0u, PF_GZ_FIXED_ONLY, PF_GZ_DYNAMIC_ONLY, PF_GZ_LITERALS_ONLY}) check_segments("segments", d, lens, f);
         }
         check_refusals();
+    }
+    {                                                                                            // 11: rows, for PF_GZ_DEEP's
+        all("only_newlines", Bytes(C + 5, '\n'));                                                // candidate from the row before
+        for (size_t row : {1u, 2u, 3u, 40u, 127u, 255u, 256u, 257u, 300u, 5000u, C - 1, C}) {
+            Bytes d;
+            std::mt19937 rng((uint32_t)row);
+            Bytes cells(row);
+            for (auto& x : cells) x = "01\t"[rng() % 3];
+            while (d.size() < 2 * C + 77) {                     // every row the one before with a few cells changed,
+                for (int k = 0; k < 3; k++) cells[rng() % row] = "01\t"[rng() % 3];
+                const size_t len = rng() % 5 ? row : 1 + rng() % row;      // some cut short: a candidate past the row's end
+                d.insert(d.end(), cells.begin(), cells.begin() + len);
+                d.push_back('\n');
+            }
+            all("rows", d);
+            d.erase(d.begin(), d.begin() + row / 2);             // (a chunk that starts inside a row)
+            all("rows_from_inside_a_row", d);
+        }
     }
     if (argc > 1 && !check_file(argv[1])) { failures++; fprintf(stderr, "FAIL reading %s\n", argv[1]); }
     printf("%d checks, %d failures\n", checks, failures);

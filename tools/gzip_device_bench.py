@@ -9,8 +9,12 @@ Part 2, one BASELINE configs[4]-shaped second-pass batch (tools/targets_stream_s
 kmers.tsv stream with and without device gzip into a counting sink, and the host path's rate on a sample of that text.  Both
 streams run once more, untimed, into a sink that inflates the members: the text behind them must be the plain stream's.
 
+--level: the encoder's effort levels to measure, one or both in one session (1: flags 0; 2: PF_GZ_DEEP).  The first one
+given fills the fields above as before; every level's device bytes and times stand under "levels", and zlib 4 and 6 on the
+same cuts beside 1 and 9.  --skip-e2e leaves the run_files legs out (a kernel-time-only run, as for a parent commit).
+
 Writes one JSON file into profiles/gzip_device/.  Usage:
-    python tools/gzip_device_bench.py [--clusters 300] [--samples 1000] [--targets 4] [--runs 5]
+    python tools/gzip_device_bench.py [--clusters 300] [--samples 1000] [--targets 4] [--runs 5] [--level 1 2]
                                       [--stream-clusters 4] [--stream-samples 5000] [--out profiles/gzip_device/bench.json]
 """
 import argparse
@@ -46,10 +50,19 @@ def zlib_on_cuts(text, cut, level):
     return total
 
 
-def device_gzip(eng, _lib, text):
+LEVEL_FLAGS = {1: 0, 2: 16}          # (2: PF_GZ_DEEP)
+LEVELS = [1]                         # --level
+
+
+def level_kw(level):
+    """run_files' / Engine's argument for a level; none for 1, so that the tool also runs against an older tree"""
+    return {} if level == 1 else {"device_gzip_level": level}
+
+
+def device_gzip(eng, _lib, text, level=1):
     out, n, ms = C.c_void_p(), C.c_uint64(), C.c_float()
     t0 = time.perf_counter()
-    _lib.check(eng.L.pf_gzip_device(eng.ctx, text, len(text), 0, C.byref(out), C.byref(n)))
+    _lib.check(eng.L.pf_gzip_device(eng.ctx, text, len(text), LEVEL_FLAGS[level], C.byref(out), C.byref(n)))
     dt = time.perf_counter() - t0
     _lib.check(eng.L.pf_gzip_device_last_ms(eng.ctx, C.byref(ms)))
     members = C.string_at(out, n.value)
@@ -58,21 +71,31 @@ def device_gzip(eng, _lib, text):
     return int(n.value), float(ms.value), dt
 
 
+def device_level(eng, _lib, text, level):
+    """bytes, kernel ms (median and the runs: their range is the run-to-run spread) and wall seconds of one level"""
+    device_gzip(eng, _lib, text[:1 << 20], level)               # warm-up: buffers, first launch
+    runs = [device_gzip(eng, _lib, text, level) for _ in range(5)]
+    ms = statistics.median(r[1] for r in runs)
+    return {"device_bytes": runs[0][0], "device_kernel_ms": ms, "device_kernel_ms_runs": [r[1] for r in runs],
+            "device_kernel_GBps": len(text) / ms / 1e6, "device_wall_s": statistics.median(r[2] for r in runs),
+            "ratio_device": len(text) / runs[0][0]}
+
+
 def per_file(eng, _lib, name, text):
     cut = int(eng.L.pf_gzip_device_chunk_bytes())
     text = text[:SAMPLE]
-    device_gzip(eng, _lib, text[:1 << 20])                     # warm-up: buffers, first launch
     hb, hs = host_gzip(eng.L, _lib, text)
-    runs = [device_gzip(eng, _lib, text) for _ in range(5)]
-    db = runs[0][0]
-    ms, wall = statistics.median(r[1] for r in runs), statistics.median(r[2] for r in runs)
+    levels = {str(level): device_level(eng, _lib, text, level) for level in LEVELS}
+    first = levels[str(LEVELS[0])]
+    db, ms, wall = first["device_bytes"], first["device_kernel_ms"], first["device_wall_s"]
     z1, z9 = zlib_on_cuts(text, cut, 1), zlib_on_cuts(text, cut, 9)
+    z4, z6 = zlib_on_cuts(text, cut, 4), zlib_on_cuts(text, cut, 6)
     by_cut = {str(c): zlib_on_cuts(text, c, 1) for c in (16 << 10, 32 << 10, 64 << 10)}     # what the chunk size costs
     return {"file": name, "zlib1_bytes_by_cut": by_cut, "text_bytes": len(text), "host_level9_bytes": hb, "host_level9_s": hs,
             "host_level9_MBps": len(text) / hs / 1e6, "zlib1_on_cuts_bytes": z1, "zlib9_on_cuts_bytes": z9,
             "device_bytes": db, "device_over_zlib1": db / z1, "ratio_device": len(text) / db, "ratio_zlib1": len(text) / z1,
             "ratio_host_level9": len(text) / hb, "device_kernel_ms": ms, "device_kernel_GBps": len(text) / ms / 1e6,
-            "device_wall_s": wall}
+            "device_wall_s": wall, "zlib4_on_cuts_bytes": z4, "zlib6_on_cuts_bytes": z6, "levels": levels}
 
 
 def part1(args, res):
@@ -101,7 +124,10 @@ def part1(args, res):
     eng.close()
     shutil.rmtree(os.path.dirname(od))
     e2e = {}
-    for label, kw in (("plain", {}), ("compress", {"compress": True}), ("device_gzip", {"device_gzip": True})):
+    legs = [("plain", {}), ("compress", {"compress": True})]
+    legs += [("device_gzip" if level == LEVELS[0] else f"device_gzip_level{level}", dict(device_gzip=True, **level_kw(level)))
+             for level in LEVELS]
+    for label, kw in ([] if args.skip_e2e else legs):
         times, size = [], 0
         for i in range(args.runs + 1):
             od, st, dt = run(**kw)
@@ -144,8 +170,9 @@ def part2(args, res):
     decoded = {}
     # timed with a counting sink first; then once more each way with a sink that inflates the blocks, untimed: the text
     # behind the members must be the plain stream's (blocks past a range's first included: the batch is one long range)
+    flags = {} if LEVELS[0] == 1 else {"device_gzip_flags": LEVEL_FLAGS[LEVELS[0]]}      # (the stream runs at the first level given)
     for label, gz, check in (("plain", False, False), ("device_gzip", True, False), ("plain", False, True), ("device_gzip", True, True)):
-        eng = Engine(klength=21, max_strains=(args.stream_samples + 31) // 32 * 32, stroi=stroi, device_gzip=gz)
+        eng = Engine(klength=21, max_strains=(args.stream_samples + 31) // 32 * 32, stroi=stroi, device_gzip=gz, **(flags if gz else {}))
         n = [0]
 
         def count(blk):
@@ -187,10 +214,14 @@ def main():
     ap.add_argument("--stream-clusters", type=int, default=4)
     ap.add_argument("--stream-samples", type=int, default=5000)
     ap.add_argument("--skip-stream", action="store_true")
+    ap.add_argument("--skip-e2e", action="store_true", help="leave the run_files legs out")
+    ap.add_argument("--level", type=int, nargs="+", choices=(1, 2), default=[1],
+                    help="the encoder's effort levels to measure (default: 1)")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "gzip_device", "bench.json"))
     args = ap.parse_args()
+    LEVELS[:] = list(dict.fromkeys(args.level))
     from panfeed_amd import _lib
-    res = {"chunk_bytes": int(_lib.load().pf_gzip_device_chunk_bytes()), "flags": 0}
+    res = {"chunk_bytes": int(_lib.load().pf_gzip_device_chunk_bytes()), "flags": LEVEL_FLAGS[LEVELS[0]], "levels": LEVELS}
     part1(args, res)
     _save(args, res)
     if not args.skip_stream:
